@@ -13,9 +13,16 @@ Workloads (iq-tree_amd/synth.py BASELINE_SHAPES):
   dna4     configs[3]: DNA 200 taxa x 1M patterns, pattern-sharded: 1M/N per GPU (strong scaling)
   codon    configs[4]: 64-state 50 x 20k, 20k/N per GPU (strong scaling)
 One RCCL all-reduce (SUM, f64) of the device result vector {lnL, sum_scale per node} per step when N > 1
-(SURVEY.md 8e).  Inputs are resident in HBM before the timed region.  One JSON line on rank 0; with the default
-workload the line also carries the configs[2] / configs[3] / configs[4] results of the same N under "also" (--no-also skips), so
-that the driver's N = 1, 2, 4, 8 runs of the default command give the strong-scaling curves north_star names too.
+(SURVEY.md 8e).  Inputs are resident in HBM before the timed region.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline (value, ms_per_step, lnL).  --full adds
+everything else, per workload: the sustained leg, the dominant-kernel timing pass and the roofline object, and on one
+GPU the oracle parity leg and the CPU baseline; with the default workload the line also carries the configs[2] /
+configs[3] / configs[4] results of the same N under "also" (--no-also skips) and, on one GPU, "branchopt".
+
+--dump-outputs DIR writes what the last timed step computed as float64 .npy files: lnL.npy (the step's return value)
+and pattern_lh.npy (the per-pattern lnL the traversal leaves on the device; pattern_lh_rank<r>.npy per rank when N > 1).
+The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 `python bench.py --gpus N` without WORLD_SIZE in the environment starts its N ranks itself (fresh child
 processes through torch.distributed.run, before this process touches a GPU).
@@ -170,8 +177,10 @@ def kernel_name(pkg, nst, ncat, nclass):
     return "k_traverse_mfma<%d,256>" % nst
 
 
-def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline):
-    """-> the JSON object of one workload at this world size (rank 0 gets the full object)."""
+def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline, full=True, outputs=None):
+    """-> the JSON object of one workload at this world size (rank 0 gets the full object).  full=False: the headline
+    only (no sustained leg, kernel timing pass, roofline or oracle leg).  outputs: a dict that receives what the last
+    timed step computed."""
     lib = pkg.libiqhip()
     torch = D.torch
     T0, P0, nst, ncat0, seq_type = synth.BASELINE_SHAPES[workload]
@@ -207,6 +216,36 @@ def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline
         lnl = step()
     D.barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0)
+    if outputs is not None:   # read back after the timed region: lnL is the step's value, _pattern_lh stays on the device
+        outputs["lnL"] = np.array([lnl], dtype=np.float64)
+        outputs["pattern_lh"] = tree.fetch_pattern_lh()
+
+    updates = steps * (T - 2) * P * D.world
+    value = updates / dt / 1e6
+    out = {
+        "metric": "million pattern-node partial-likelihood updates/sec",
+        "value": value,
+        "unit": "M updates/s",
+        "n_gpus": D.world,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": dt / steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "%s %d taxa x %d patterns/GPU, %s, fixed tree: clearAllPartialLH + "
+                               "full traversal + root-branch lnL" % (workload.upper(), T, P, model.name),
+                   "ntaxa": T, "patterns_per_gpu": P, "patterns_total": P * D.world, "nstates": nst,
+                   "ncat": model.ncat,
+                   "parallelism": "patterns sharded over %d GPU(s), 1 RCCL all-reduce/step" % D.world,
+                   "collective": collective},
+        "lnL": lnl,
+    }
+    if not full:
+        tree.close()
+        return out
 
     # sustained leg (not the reported value): the same step back to back for --sustain-seconds, so that a
     # power / activity sampler sees the region; the K-step region above can be a few milliseconds long
@@ -239,8 +278,6 @@ def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline
     lib.iqhip_timing_collective_read(eng, C.byref(coll_us), C.byref(coll_n), 1)
     lib.iqhip_timing_enable(eng, 0)
 
-    updates = steps * (T - 2) * P * D.world
-    value = updates / dt / 1e6
     block = nst * model.ncat
     # one traversal = one launch of the traversal kernel, or several for a staged plan (independent subtrees, then the
     # ops above them).  Everything below is PER TRAVERSAL (= all its launches together): bytes / flops of the
@@ -305,31 +342,12 @@ def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline
         "kernel_name_source": "rocprofv3 kernel trace (profiles/)" if pmc else "expected instantiation (not observed)",
         "kernel_avg_ms": avg_ms.value, "launches": launches.value, "launches_per_traversal": lpt,
         "kernel_ms_per_traversal": avg_ms.value * lpt})
-    out = {
-        "metric": "million pattern-node partial-likelihood updates/sec",
-        "value": value,
-        "unit": "M updates/s",
-        "n_gpus": D.world,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": dt / steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "%s %d taxa x %d patterns/GPU, %s, fixed tree: clearAllPartialLH + "
-                               "full traversal + root-branch lnL" % (workload.upper(), T, P, model.name),
-                   "ntaxa": T, "patterns_per_gpu": P, "patterns_total": P * D.world, "nstates": nst,
-                   "ncat": model.ncat,
-                   "parallelism": "patterns sharded over %d GPU(s), 1 RCCL all-reduce/step" % D.world,
-                   "collective": collective},
-        "lnL": lnl,
+    out.update({
         "host_overhead_ms_per_step": dt / steps * 1e3 - avg_ms.value * lpt,
         # N > 1 (or --force-collective): the engine's own all-reduce, HIP events around it (incl. waiting for slower ranks)
         "collective_us_per_step": coll_us.value * coll_n.value / float(ntimed) if coll_n.value else None,
         "roofline": roof,
-    }
+    })
     if sustained:
         out["sustained"] = sustained
 
@@ -361,6 +379,26 @@ def run_workload(args, D, pkg, synth, workload, steps, warmup, with_cpu_baseline
                                          "(%d traversals in %.1f s)" % (reps, P, secs, ncores, mups1, reps1, secs1)}
     tree.close()
     return out
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # all ranks' files together stay under 64 MB
+
+
+def write_outputs(dirname, outputs, rank, world):
+    """--dump-outputs: lnL.npy from rank 0 (the all-reduced value, the same on every rank) and each rank's per-pattern
+    lnL.  A shard above its share of the budget is written as a fixed, seeded sample of its patterns, with the sampled
+    pattern indices beside it (pattern_lh_index*.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    if rank == 0:
+        np.save(os.path.join(dirname, "lnL.npy"), outputs["lnL"])
+    plh = np.asarray(outputs["pattern_lh"], dtype=np.float64)
+    cap = DUMP_BUDGET_BYTES // (8 * world)
+    if plh.size > cap:
+        idx = np.sort(np.random.default_rng(20240601).choice(plh.size, cap // 2, replace=False))
+        np.save(os.path.join(dirname, "pattern_lh_index%s.npy" % sfx), idx.astype(np.float64))
+        plh = plh[idx]
+    np.save(os.path.join(dirname, "pattern_lh%s.npy" % sfx), plh)
 
 
 def run_branchopt(pkg, synth, shapes=((50, 100000), (44, 355))):
@@ -416,13 +454,18 @@ def main():
                     help="dna = BASELINE configs[1] (the headline); protein / dna4 / codon = configs[2] / [3] / [4]")
     ap.add_argument("--ntaxa", type=int, default=0)
     ap.add_argument("--patterns", type=int, default=0, help="patterns per GPU (overrides the workload's count)")
-    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: sustained leg, kernel timing + roofline, oracle parity + CPU baseline, "
+                         "and with the default workload the 'also' configs and 'branchopt'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (lnL, per-pattern lnL) as float64 .npy files to DIR")
+    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="--full: budget of the cpu_baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle parity + CPU baseline leg")
     ap.add_argument("--no-also", action="store_true",
-                    help="default workload only: skip the configs[2..4] (protein, dna4, codon) results under 'also'")
-    ap.add_argument("--also", action="store_true", help="add the 'also' results to a non-default workload")
+                    help="--full, default workload: skip the configs[2..4] (protein, dna4, codon) results under 'also'")
+    ap.add_argument("--also", action="store_true", help="--full: add the 'also' results to a non-default workload")
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
-                    help="after the timed K steps, repeat the step for this long (activity evidence; 0 = off)")
+                    help="--full: after the timed K steps, repeat the step for this long (activity evidence; 0 = off)")
     ap.add_argument("--collective", choices=["rccl", "torch"], default="rccl",
                     help="N > 1: rccl = the engine's own communicator (C++), torch = torch.distributed from a Python hook")
     ap.add_argument("--force-collective", action="store_true",
@@ -431,7 +474,11 @@ def main():
                     help="plan subtrees in the reference's neighbour order instead of heavier-first")
     ap.add_argument("--ncat", type=int, default=0, help="rate categories (dna / protein workloads; default: the BASELINE shape)")
     args = ap.parse_args()
-    default_command = args.workload is None   # the driver's command: headline + the multi-GPU configs under "also"
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.also and not args.full:
+        ap.error("--also needs --full")
+    default_command = args.workload is None   # with --full: headline + the multi-GPU configs under "also"
     args.workload = args.workload or "dna"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -446,10 +493,14 @@ def main():
     import importlib
     synth = importlib.import_module("iqtree_amd.synth")
 
-    out = run_workload(args, D, pkg, synth, args.workload, args.steps, args.warmup, not args.no_cpu_baseline)
+    outputs = {} if args.dump_outputs else None
+    out = run_workload(args, D, pkg, synth, args.workload, args.steps, args.warmup,
+                       args.full and not args.no_cpu_baseline, full=args.full, outputs=outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs, D.rank, D.world)
     # the multi-GPU configs north_star names, at this N, beside the headline (the driver runs one command per N)
     plain = not (args.ntaxa or args.patterns or args.ncat)
-    if plain and ((default_command and not args.no_also) or args.also):
+    if args.full and plain and ((default_command and not args.no_also) or args.also):
         also = []
         for w in ("protein", "dna4", "codon"):
             if w == args.workload:

@@ -3,7 +3,7 @@
 set -e -o pipefail
 run() { # libdir env...
   d=$1; shift
-  env IQHIP_LIB_DIR=$PWD/iq-tree_amd/$d "$@" python bench.py --workload protein --steps 100 --warmup 30 --no-also --no-cpu-baseline --sustain-seconds 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$d $*', 'kernel_ms_per_traversal', round(d['roofline']['kernel_ms_per_traversal'],4), 'launches', d['roofline']['launches_per_traversal'], 'ms/step', round(d['ms_per_step'],4))"
+  env IQHIP_LIB_DIR=$PWD/iq-tree_amd/$d "$@" python bench.py --workload protein --steps 100 --warmup 30 --full --no-also --no-cpu-baseline --sustain-seconds 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$d $*', 'kernel_ms_per_traversal', round(d['roofline']['kernel_ms_per_traversal'],4), 'launches', d['roofline']['launches_per_traversal'], 'ms/step', round(d['ms_per_step'],4))"
 }
 for rep in 1 2; do
 run lib IQHIP_LEAF_TABLES=0
