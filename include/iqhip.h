@@ -353,6 +353,25 @@ int iqhip_timing_collective_read(iqhip_engine *e, double *avg_us, int64_t *count
  * the node's three matrix products.  Counters since the engine was created: tables built, node updates answered. */
 int iqhip_debug_cherry_tables(iqhip_engine *e, int64_t *tables_built, int64_t *ops_from_tables);
 
+/* Which Newton and sweep forms an engine ran, counted since it was created; out[k] for k < min(n, IQHIP_PATH_NSLOTS):
+ *   IQHIP_PATH_NEWTON_ONE_LAUNCH  Newton solves as one launch of k_newton (iqhip_newton_branch, iqhip_optimize_branch and
+ *                                 every step of a per-step sweep)
+ *   IQHIP_PATH_NEWTON_CHAIN       Newton solves as the enqueued chain (IQHIP_NEWTON=chain or a communicator rank)
+ *   IQHIP_PATH_SWEEP_PERSISTENT   sweeps as one launch of the 4-state persistent kernel k_sweep4
+ *   IQHIP_PATH_SWEEP_PER_STEP     sweeps as two launches per step enqueued back to back
+ *   IQHIP_PATH_SWEEP_SEQUENTIAL   sweeps (or their remainders) one step at a time with a host round trip each
+ *   IQHIP_PATH_NEWTON_FALLBACK    one-launch solves whose grid barrier gave up and that the enqueued chain finished
+ * IQHIP_NEWTON, IQHIP_SWEEP and IQHIP_SWEEP_KERNEL are read when the engine is created.  A sharded engine counts its
+ * sweeps on the front; its Newton solves run the front's own loop over the shards and are not counted. */
+#define IQHIP_PATH_NEWTON_ONE_LAUNCH 0
+#define IQHIP_PATH_NEWTON_CHAIN 1
+#define IQHIP_PATH_SWEEP_PERSISTENT 2
+#define IQHIP_PATH_SWEEP_PER_STEP 3
+#define IQHIP_PATH_SWEEP_SEQUENTIAL 4
+#define IQHIP_PATH_NEWTON_FALLBACK 5
+#define IQHIP_PATH_NSLOTS 6
+int iqhip_debug_path_counts(iqhip_engine *e, int64_t *out, int n);
+
 /* Debugging aid, no reference counterpart: a PLANNING-ONLY engine makes no HIP call and owns no device memory (its
  * vectors are distinct fake addresses).  iqhip_debug_plan turns an op list into the device descriptors exactly as
  * iqhip_update_partials would (key -> slab map, canonical child order, staging, LDS chunks, K2 table slots, look-ahead

@@ -35,7 +35,12 @@ IQHIP_SYMBOLS = [
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
     "iqhip_debug_create_planner", "iqhip_debug_plan", "iqhip_timing_plan_bytes", "iqhip_timing_collective_read", "iqhip_optimize_sweep", "iqhip_debug_cherry_tables",
+    "iqhip_debug_path_counts",
 ]
+
+# slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
+PATH_SLOTS = ("newton_one_launch", "newton_chain", "sweep_persistent", "sweep_per_step", "sweep_sequential",
+              "newton_fallback")
 
 
 class NodeOp(C.Structure):
@@ -144,6 +149,7 @@ def libiqhip():
     lib.iqhip_timing_plan_bytes.argtypes = [vp, dp, dp]
     lib.iqhip_timing_collective_read.argtypes = [vp, dp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_cherry_tables.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.iqhip_debug_path_counts.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_plan.argtypes = [vp, C.POINTER(NodeOp), C.c_int]
     lib._iq_typed = True
     return lib
@@ -404,6 +410,15 @@ class PhyloTree:
     @property
     def engine(self):
         return self.lib.iqhost_engine(self.h)
+
+    def path_counts(self):
+        """{slot name: count} of the Newton / sweep forms the attached engine ran since it was created
+        (iqhip_debug_path_counts)"""
+        out = (C.c_int64 * len(PATH_SLOTS))()
+        lib = libiqhip()
+        if lib.iqhip_debug_path_counts(self.engine, out, len(PATH_SLOTS)) != 0:
+            raise HostError(lib.iqhip_last_error().decode())
+        return dict(zip(PATH_SLOTS, out))
 
     def set_allreduce_hook(self, fn):
         """fn(device_ptr:int, ndoubles:int) all-reduces the device result vector in place."""

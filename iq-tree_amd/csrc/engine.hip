@@ -85,6 +85,9 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     if (const char *f = getenv("IQHIP_POLL")) e->poll_result = atoi(f) != 0;
     if (const char *f = getenv("IQHIP_CHERRY_TABLES")) e->cherry_on = atoi(f) != 0;
     if (const char *sp = getenv("IQHIP_SPLIT")) e->split_target = atoi(sp);
+    if (const char *v = getenv("IQHIP_NEWTON")) e->newton_chain_forced = !strcmp(v, "chain");
+    if (const char *v = getenv("IQHIP_SWEEP")) e->sweep_one_submission = atoi(v) != 0;
+    if (const char *v = getenv("IQHIP_SWEEP_KERNEL")) e->sweep_persistent = atoi(v) != 0;
     if (const char *kb = getenv("IQHIP_LDS_KB")) {
         int v = atoi(kb);
         if (v >= 8 && v <= 150) e->lds_budget_bytes = v * 1024;
@@ -613,7 +616,8 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
 
 // embedded data: pad the caller's m-state system (m = n_user) to the n-state one the kernels run (see iqhip_engine::embed2):
 // eigenvalues (l_0 .. l_m-1, 0 ...), U = diag(U_m, I), U^-1 = diag(U_m^-1, I); tip rows of the m states padded with zeros;
-// internal state n = "missing" with the caller's unknown row, internal STATE_UNKNOWN = n + 1 (never present in the data)
+// internal state n = "missing" with the caller's unknown row, internal STATE_UNKNOWN = n + 1 (never present in the data, its
+// tip row = the caller's unknown row as well)
 // ---------------------------------------------------------------------------------------
 // cherry tables (DevOp::cherry): which engines use them, and their pair engine
 // ---------------------------------------------------------------------------------------
@@ -680,7 +684,10 @@ static int set_model_binary(iqhip_engine *e, const double *eval, const double *e
     for (int x = m; x < n; x++) U[(size_t)x * n + x] = Ui[(size_t)x * n + x] = 1.0;
     for (int st = 0; st < m; st++)
         for (int i = 0; i < m; i++) tp[(size_t)st * n + i] = tip[st * m + i];
-    for (int i = 0; i < m; i++) tp[(size_t)n * n + i] = tip[m * m + i];   // row n: the caller's unknown row
+    // row n: the caller's unknown row.  Row n + 1 (the kernels' STATE_UNKNOWN, never in the data) gets it too: the scalar
+    // kernel's lh_max == 0 rule writes row STATE_UNKNOWN's vector, which must be the caller's tip_partial_lh[STATE_UNKNOWN]
+    // (phylotreesse.cpp:777-788), not zeros
+    for (int i = 0; i < m; i++) tp[(size_t)n * n + i] = tp[(size_t)(n + 1) * n + i] = tip[m * m + i];
     return set_model_common(e, 1, nullptr, ev.data(), U.data(), Ui.data(), rates, props, n + 1, tp.data());
 }
 
@@ -1297,9 +1304,14 @@ static int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *
             // two workgroups per CU (160 KB LDS): <= 78 KB each, images included (a third workgroup
             // for the 20-state kernel was measured: no gain, more chunks); IQHIP_MFMA_LDS_KB overrides
             int total_kb = e->n == 20 ? 75 : 78;   // (20 states: + 2.6 KB of static arrays per workgroup, the fill's descriptor copies)
-            if (const char *kb = getenv("IQHIP_MFMA_LDS_KB")) total_kb = atoi(kb);
+            const char *kb_env = getenv("IQHIP_MFMA_LDS_KB");
+            if (kb_env) total_kb = atoi(kb_env);
             if (e->plan_nhold > 0) fixed += 4 * 16 * B;   // the waves' parking places (CHILD_HOLD in LDS)
             budget = (total_kb * 1024) / 8 - fixed;
+            // the generic kernel's images leave two workgroups per CU too little for one op with two vector children once
+            // n * ncat > 864 (64 states, 14 .. 16 categories or components): one workgroup per CU, 150 KB (every matrix-core
+            // kernel allows that much dynamic LDS)
+            if (!kb_env && !e->mfma_pipelined && budget < 2 * B) budget = (150 * 1024) / 8 - fixed;
         } else {
             budget = (e->lds_budget_bytes / 8) - 128 - B;
         }
@@ -1897,11 +1909,7 @@ static int newton_chain(iqhip_engine *e, double xguess, double x1, double x2, do
 
 // k_newton's grid barrier needs every workgroup resident; a single workgroup needs no barrier.  IQHIP_NEWTON=chain
 // forces the chain form (tests).
-static bool newton_use_chain(const iqhip_engine *e) {
-    if (e->comm) return true;
-    static const bool forced = [] { const char *v = getenv("IQHIP_NEWTON"); return v && !strcmp(v, "chain"); }();
-    return forced;
-}
+static bool newton_use_chain(const iqhip_engine *e) { return e->comm || e->newton_chain_forced; }
 
 extern "C" int iqhip_newton_branch(iqhip_engine *e, double xguess, double x1, double x2, double xacc,
                                    int max_steps, double *optx, double *d2l, int *nsteps) {
@@ -1916,9 +1924,11 @@ extern "C" int iqhip_newton_branch(iqhip_engine *e, double xguess, double x1, do
     if (rc) return rc;
     if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, "iqhip_newton_branch: theta not computed");
     if (newton_use_chain(e)) {
+        e->path_counts[IQHIP_PATH_NEWTON_CHAIN]++;
         return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
     }
     HIPCHK(launch_newton(e, xguess, x1, x2, xacc, max_steps, e->d_result));
+    e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
     rc = read_result(e, 4);
     if (rc) return rc;
     const int status = (int)e->h_result[3];
@@ -1926,6 +1936,7 @@ extern "C" int iqhip_newton_branch(iqhip_engine *e, double xguess, double x1, do
     if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
     if (status == 4) {  // the grid barrier gave up (another kernel held the CUs): the chain needs no barrier
         (void)hipStreamSynchronize(e->stream);
+        e->path_counts[IQHIP_PATH_NEWTON_FALLBACK]++;
         return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
     }
     if (optx) *optx = e->h_result[0];
@@ -1953,6 +1964,7 @@ extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, 
         }
         rc = iqhip_compute_theta(e, a, b);
         if (rc) return rc;
+        e->path_counts[IQHIP_PATH_NEWTON_CHAIN]++;
         return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
     }
     // two launches per branch: the pending node updates, then one kernel that sums their sum_scale rows,
@@ -1969,6 +1981,7 @@ extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, 
     e->theta_b_sc = br.b_sc;
     double *out = e->d_result + 2 + nops;
     HIPCHK(launch_newton(e, xguess, x1, x2, xacc, max_steps, out, &br, nops, (int)e->ntiles * e->lane_split));
+    e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
     rc = read_result(e, 2 + nops + 4);
     if (rc) return rc;
     if (sum_scale)
@@ -1979,6 +1992,7 @@ extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, 
     if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
     if (status == 4) {  // grid barrier gave up: theta was built by the first evaluation, finish with the chain
         (void)hipStreamSynchronize(e->stream);
+        e->path_counts[IQHIP_PATH_NEWTON_FALLBACK]++;
         return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
     }
     if (optx) *optx = r[0];
@@ -2011,6 +2025,7 @@ static int sweep_resolve_ops(const iqhip_sweep_step &st, const iqhip_branch_resu
 static int sweep_sequential(iqhip_engine *e, const iqhip_sweep_step *steps, int first, int nsteps, double x1, double x2,
                             double xacc, int max_steps, double diverge_frac, double *sum_scale, size_t ss_off,
                             iqhip_branch_result *results) {
+    e->path_counts[IQHIP_PATH_SWEEP_SEQUENTIAL]++;
     std::vector<iqhip_node_op> ops;
     for (int j = first; j < nsteps; j++) {
         const iqhip_sweep_step &st = steps[j];
@@ -2114,6 +2129,7 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts, 0xFF, posts_need * sizeof(double), e->stream));
     double *out = e->d_result + total_ops;      // (rows [0, total_ops) receive the sum_scale sums from k_reduce)
     memset(e->h_result + total_ops, 0, sizeof(double) * 6 * (size_t)nsteps);
+    e->path_counts[IQHIP_PATH_SWEEP_PERSISTENT]++;
     HIPCHK(launch_sweep4(e, reinterpret_cast<const SweepOp *>(e->d_sweep_desc),
                          reinterpret_cast<const SweepStep *>(e->d_sweep_desc + bytes_ops), nsteps, x1, x2, xacc, max_steps,
                          diverge_frac * x2, e->d_sweep_posts, out));
@@ -2171,14 +2187,12 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
                 if (st.len_from[q] >= j) return fail(IQHIP_ERR_INVALID, "a sweep step may only use the lengths of earlier steps");
         total_ops += (size_t)st.nops;
     }
-    static const bool one_submission = [] { const char *v = getenv("IQHIP_SWEEP"); return !v || atoi(v) != 0; }();
-    if (!e->shards.empty() || e->comm || e->n_unobs > 0 || !one_submission || newton_use_chain(e) ||
+    if (!e->shards.empty() || e->comm || e->n_unobs > 0 || !e->sweep_one_submission || newton_use_chain(e) ||
         2 + total_ops + 6 * (size_t)nsteps > (size_t)e->result_cap || e->d_result != e->d_result_own)
         return sweep_sequential(e, steps, 0, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, 0, results);
     int rc = check_ready(e);
     if (rc) return rc;
-    static const bool persistent = [] { const char *v = getenv("IQHIP_SWEEP_KERNEL"); return !v || atoi(v) != 0; }();
-    if (persistent && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
+    if (e->sweep_persistent && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
         return sweep_persistent4(e, steps, nsteps, total_ops, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results);
     if (!e->h_plan_arena) {
         e->plan_arena_cap = 1 << 20;
@@ -2189,6 +2203,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         explicit ArenaScope(iqhip_engine *e_) : e(e_) { e->plan_arena_on = e->h_plan_arena != nullptr; e->plan_arena_used = 0; }
         ~ArenaScope() { e->plan_arena_on = false; }
     } arena_scope(e);
+    e->path_counts[IQHIP_PATH_SWEEP_PER_STEP]++;
     if (nsteps > e->sweep_len_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
         if (e->d_sweep_len) hipFree(e->d_sweep_len);
@@ -2240,6 +2255,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         if (dbg) clock_gettime(CLOCK_MONOTONIC, &tc);
         HIPCHK(launch_newton(e, st.xguess, x1, x2, xacc, max_steps, e->d_result + row + st.nops, &br, st.nops,
                              (int)e->ntiles * e->lane_split, &sw));
+        e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
         if (dbg) { clock_gettime(CLOCK_MONOTONIC, &td); t_newt += (td.tv_sec - tc.tv_sec) * 1e6 + (td.tv_nsec - tc.tv_nsec) * 1e-3; }
         row += (size_t)st.nops + 6;
     }
@@ -2663,6 +2679,13 @@ extern "C" int iqhip_debug_cherry_tables(iqhip_engine *e, int64_t *tables_built,
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (tables_built) *tables_built = e->cherry_built_total;
     if (ops_from_tables) *ops_from_tables = e->cherry_ops_total;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_path_counts(iqhip_engine *e, int64_t *out, int n) {
+    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
+    if (!out && n > 0) return fail(IQHIP_ERR_INVALID, "null argument");
+    for (int k = 0; k < n && k < IQHIP_PATH_NSLOTS; k++) out[k] = e->path_counts[k];
     return IQHIP_OK;
 }
 

@@ -344,6 +344,12 @@ struct iqhip_engine {
     uint64_t cherry_stamp = 0, plan_cherry_model = 0;   // (model version the current plan's tables were scheduled for)
     bool plan_uses_cherry = false;
     int64_t cherry_built_total = 0, cherry_ops_total = 0;   // tables built / node updates answered from a table so far
+    // Newton / sweep forms, read when the engine is created: IQHIP_NEWTON=chain (enqueued chain instead of the one-launch
+    // k_newton), IQHIP_SWEEP=0 (sweeps step by step with a host round trip each), IQHIP_SWEEP_KERNEL=0 (4-state sweeps as
+    // two launches per step instead of k_sweep4)
+    bool newton_chain_forced = false, sweep_one_submission = true, sweep_persistent = true;
+    // since creation, the IQHIP_PATH_* slots of include/iqhip.h (iqhip_debug_path_counts)
+    int64_t path_counts[IQHIP_PATH_NSLOTS] = {};
     bool cherry_model_synced = false;      // the pair engine has the model of this engine's last set_model call
     int plan_tab_dirty = 0;
     int plan_jobs_off = 0;                // DevOp index where the device copy of the job list starts

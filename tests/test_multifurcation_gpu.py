@@ -82,7 +82,13 @@ def test_polytomy_with_scaling_events(pkg, synth, oracle):
 
 
 @pytest.mark.parametrize("n,ncat,seq_type,nptn", [(4, 4, 0, 300), (4, 4, 0, 9000), (20, 4, 1, 200), (20, 4, 1, 6000), (20, 1, 1, 100),
-                                                  (20, 6, 1, 150), (64, 1, 2, 120), (64, 1, 2, 3000), (64, 2, 2, 100)])
+                                                  (20, 6, 1, 150), (64, 1, 2, 120), (64, 1, 2, 3000), (64, 2, 2, 100),
+                                                  # embedded state counts (binary on the 4-state kernel, 3 -> 4, 5 -> the pipelined
+                                                  # 20 x 4 kernel with and without cat_split, 7 -> mix20 with one class, 25 -> the
+                                                  # 64-state kernel with and without row_split): the rule's vector is the caller's
+                                                  # unknown row, which the engine keeps at its own STATE_UNKNOWN as well
+                                                  (2, 4, 3, 300), (3, 1, 3, 300), (3, 4, 3, 300), (5, 4, 3, 200), (5, 4, 3, 6000),
+                                                  (7, 3, 3, 150), (25, 1, 3, 120), (25, 1, 3, 5000)])
 def test_scalar_kernel_zero_rule_at_a_multifurcating_node(pkg, synth, oracle, n, ncat, seq_type, nptn):
     """phylotreesse.cpp:774-788, the scalar kernel's `lh_max == 0.0` branch ("very shitty data"): the pattern's vector becomes
     the unknown tip's in every category, scale_num += 4, sum_scale += 4 log(2^-256) f -- whatever ptn_invar says.  Forced

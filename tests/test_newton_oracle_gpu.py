@@ -26,7 +26,7 @@ CASES = [  # n, ncat, seq_type, ntaxa, nsites
     (4, 4, 0, 12, 40000),    # many workgroups: posted exchange
     (20, 4, 1, 9, 1200),
     (64, 1, 2, 8, 600),
-]
+] + [(4, c, 0, 10, 300) for c in (2, 3, 5, 6, 7, 8)] + [(4, c, 0, 12, 40000) for c in (2, 3, 5, 6, 7, 8)]   # k_newton<C>
 
 
 @pytest.mark.parametrize("n,ncat,seq_type,ntaxa,nsites", CASES)
@@ -54,6 +54,8 @@ def test_device_newton_matches_oracle_newton(pkg, synth, oracle, n, ncat, seq_ty
             assert abs(d2l - ref_d2l) <= 1e-6 * max(1.0, abs(ref_d2l)), (d2l, ref_d2l)
             nchecked += 1
     assert nchecked == 25
+    pc = t.path_counts()                                # the default form: one launch of k_newton per solve
+    assert pc["newton_one_launch"] >= 25 and pc["newton_chain"] == 0, pc
 
 
 def test_optimize_one_branch_is_the_reference_sequence(pkg, synth, oracle):

@@ -51,6 +51,49 @@ def check_all_vectors(t, ot):
     return nchecked
 
 
+def check_derv(t, ot, a, b, length=None):
+    """df / ddf of branch (a, b) at `length` (the tree's own when None) against the oracle"""
+    df, ddf = t.compute_likelihood_derv(a, b)
+    odf, oddf = ot.derv(a, b, length)
+    assert abs(df - odf) <= 1e-9 * max(1.0, abs(odf)) + 1e-12 * abs(oddf), (a, b, length, df, odf)
+    assert abs(ddf - oddf) <= 1e-9 * abs(oddf), (a, b, length, ddf, oddf)
+
+
+def check_paths(t, ot, model, ntaxa, pattern_lh_cat=True):
+    """one engine against the oracle on everything a traversal and a branch produce: lnL, pattern_lh and (plain models)
+    pattern_lh_cat of the root branch; every vector with its counters; then on a leaf branch and on an internal branch the
+    branch lnL, df / ddf at the tree's length and at three others, and the lnL from the theta buffer."""
+    t.clear_all_partial_lh()
+    lnl = t.compute_likelihood()
+    ref, (a, b) = ot.likelihood()
+    assert t.current_branch() == (a, b)
+    assert abs(lnl - ref) <= LNL_RTOL * abs(ref), (lnl, ref)
+    _, plh = ot.branch_lnl(a, b)
+    np.testing.assert_allclose(t.fetch_pattern_lh(), plh, rtol=1e-10, atol=0)
+    if pattern_lh_cat:
+        n, ncat = len(model.eval), len(model.rates)
+        th, _ = ot.theta(a, b)
+        val = (np.exp(np.outer(model.rates * ot.length(a, b), model.eval)) * model.props[:, None]).reshape(-1)
+        expect = (th * val[None, :]).reshape(th.shape[0], ncat, n).sum(axis=2)
+        np.testing.assert_allclose(t.compute_pattern_lh_cat(), expect, rtol=1e-10, atol=1e-300)
+    assert check_all_vectors(t, ot) == ntaxa - 2
+    inner = [(x, y) for x in range(t.num_nodes) for y, _ in t.neighbors(x) if not ot.is_leaf(x) and not ot.is_leaf(y)]
+    for (x, y) in [(0, t.neighbors(0)[0][0])] + inner[len(inner) // 2:len(inner) // 2 + 1]:
+        v = t.compute_likelihood_branch(x, y)
+        assert abs(v - ref) <= LNL_RTOL * abs(ref), (x, y, v, ref)
+        t.reset_theta()
+        check_derv(t, ot, x, y)
+        o, _ = ot.lnl_from_theta(x, y)
+        v = t.compute_likelihood_from_buffer()
+        assert abs(v - o) <= LNL_RTOL * abs(o), (x, y, v, o)
+        ln0 = ot.length(x, y)
+        for length in (0.01, 0.13, 1.7):
+            t.set_branch_length(x, y, length, clear_reverse=False)
+            check_derv(t, ot, x, y, length)
+        t.set_branch_length(x, y, ln0, clear_reverse=True)
+    return ref
+
+
 @pytest.mark.parametrize("ncat", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_dna_full_traversal_all_ncat(pkg, synth, oracle, ncat):
     t, ot, *_ = make_case(synth, oracle, pkg, 14, 700, 4, ncat, 100 + ncat, missing=0.05)
@@ -65,20 +108,25 @@ def test_dna_full_traversal_all_ncat(pkg, synth, oracle, ncat):
 
 
 @pytest.mark.parametrize("nptn", [1, 63, 64, 65, 255, 257, 1000])
-def test_ragged_pattern_counts(pkg, synth, oracle, nptn):
-    """tile edges: nptn not a multiple of the 64-pattern tile / 256-pattern workgroup."""
+def test_ragged_pattern_counts(pkg, synth, oracle, nptn, monkeypatch):
+    """tile edges: nptn not a multiple of the 64-pattern tile / 256-pattern workgroup -- lnL, and under both lane
+    splits every vector, pattern_lh and the derivatives."""
     model = synth.gtr_model()
     nwk = synth.random_tree_newick(7, 5)
     st = synth.simulate_alignment(nwk, model, max(nptn, 4), 9)[:, :nptn]
     freq = np.arange(1, nptn + 1, dtype=np.float64)
     ot = oracle.OracleTree(nwk, 4, 0, st, freq, None, model)
-    t = pkg.PhyloTree(nwk)
-    t.set_alignment(4, 0, st, freq)
-    t.set_model(model)
-    t.attach_engine(0)
-    lnl = t.compute_likelihood()
-    ref, _ = ot.likelihood()
-    assert abs(lnl - ref) <= LNL_RTOL * abs(ref)
+    for ls in ("1", "2"):
+        monkeypatch.setenv("IQHIP_LANE_SPLIT", ls)
+        t = pkg.PhyloTree(nwk)
+        t.set_alignment(4, 0, st, freq)
+        t.set_model(model)
+        t.attach_engine(0)
+        lnl = t.compute_likelihood()
+        ref, _ = ot.likelihood()
+        assert abs(lnl - ref) <= LNL_RTOL * abs(ref)
+        check_paths(t, ot, model, 7)
+        t.close()
 
 
 def test_ambiguity_codes_and_gaps(pkg, synth, oracle):

@@ -42,6 +42,7 @@ SHAPES = [  # nstates, ncat, nptn, ntaxa, nclass: every kernel family and the si
     (4, 4, 100000, 50, 1), (4, 4, 3000, 50, 1), (4, 1, 40000, 30, 1), (4, 3, 500, 9, 1), (4, 4, 20000, 24, 2),
     (20, 4, 50000, 100, 1), (20, 4, 400, 30, 1), (20, 1, 9000, 40, 1), (20, 6, 5000, 20, 1), (20, 8, 3000, 16, 2),
     (64, 1, 20000, 50, 1), (64, 1, 300, 20, 1), (64, 2, 4000, 12, 1), (64, 4, 2000, 12, 2),
+    (64, 16, 2000, 12, 1), (64, 16, 2000, 12, 8), (20, 96, 3000, 12, 24),   # the documented component caps
 ]
 
 

@@ -260,6 +260,8 @@ def test_newton_chain_on_a_plain_engine(pkg, synth, oracle, n, ncat, seq_type, n
             res[mode] = (t.optimize_one_branch(a, b), t.num_derv_calls - c0)
         (lh, ch), (ld, cd) = res[False], res[True]
         assert cd == ch and abs(ld - lh) <= 1e-12 * max(lh, 1e-6), (a, b, res)
+    pc = t.path_counts()                                # the switch reached this engine: no one-launch solve ran
+    assert pc["newton_chain"] >= 6 and pc["newton_one_launch"] == 0, pc
 
 
 @pytest.mark.parametrize("n,ncat,seq_type", [(4, 4, 0), (20, 4, 1)])

@@ -44,7 +44,8 @@ CASES = [  # n, ncat, seq_type, ntaxa, nsites, mem_mode
     (20, 4, 1, 12, 1500, 0),
     (20, 1, 1, 8, 300, 0),
     (64, 1, 2, 9, 500, 0),      # leaf tables: lengths that only exist on the device go through TabJob::len_p
-]
+] + [(4, c, 0, 10, 400, 0) for c in (2, 3, 5, 6, 7, 8)]   # k_sweep4<C> with theta in registers (reg = false:
+# test_kernel_paths_gpu.py::test_persistent_sweep_with_theta_in_memory)
 
 
 @pytest.mark.parametrize("n,ncat,seq_type,ntaxa,nsites,mem_mode", CASES)
@@ -74,6 +75,12 @@ def test_sweep_equals_the_per_branch_form(pkg, synth, oracle, n, ncat, seq_type,
     assert c0 == c1                                          # derivative evaluations
     nbranch = len(len0)
     assert s1 < s0 and s0 - s1 >= nbranch - 1                # one submission per sweep instead of one per branch
+    pc = t1.path_counts()                                    # the form the case names is the one that ran
+    if n == 4 and kernel == "persistent":
+        assert pc["sweep_persistent"] > 0 and pc["sweep_per_step"] == 0, pc
+    else:
+        assert pc["sweep_per_step"] > 0 and pc["sweep_persistent"] == 0, pc
+    assert pc["newton_chain"] == 0, pc
     ot, model, pat, freq = made[-1]
     ot2 = oracle.OracleTree(t1.tree_string(), n, seq_type, pat, freq, None, model)
     ref, _ = ot2.likelihood()
