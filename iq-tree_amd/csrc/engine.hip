@@ -1,4 +1,4 @@
-// engine.hip -- host side of libiqhip.so: device memory, key->slab map, plan building and the
+// engine.hip -- host side of libiqhip.so: device memory, key->slab map, submissions and the
 // extern "C" entry points declared in include/iqhip.h.  There is NO CPU fallback in this
 // library: every compute entry point launches HIP kernels or fails with a status.
 #include <math.h>
@@ -9,7 +9,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <unordered_set>
 
 #include "iqhip_internal.h"
 
@@ -23,12 +22,6 @@ int set_error(int code, const std::string &msg) {
 }
 }  // namespace iqhip
 static int fail(int code, const std::string &msg) { return set_error(code, msg); }
-#define HIPCHK(call)                                                                  \
-    do {                                                                              \
-        hipError_t _s = (call);                                                       \
-        if (_s != hipSuccess)                                                         \
-            return fail(IQHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
-    } while (0)
 
 extern "C" const char *iqhip_last_error(void) { return g_err.c_str(); }
 extern "C" int iqhip_abi_version(void) { return IQHIP_ABI_VERSION; }
@@ -40,20 +33,8 @@ extern "C" int iqhip_device_count(void) {
 
 static int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-template <typename T>
-static hipError_t dmalloc(T **p, size_t count) {
-    return hipMalloc((void **)p, count * sizeof(T));
-}
 // a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
 static hipError_t use_device(const iqhip_engine *e) { return e->planner ? hipErrorInvalidDevice : hipSetDevice(e->device); }
-// planning-only engines: a distinct, 256-byte aligned address range that is never dereferenced
-template <typename T>
-static T *fake_alloc(iqhip_engine *e, size_t count) {
-    const uint64_t a = e->fake_next;
-    e->fake_next += (count * sizeof(T) + 255) / 256 * 256 + 256;
-    return reinterpret_cast<T *>(a);
-}
-
 // everything about an engine that follows from its shape, the CU count (e->num_cus, set by the caller) and the
 // environment switches -- no HIP call, so that the planning-only engine of iqhip_debug_create_planner shares it
 static void configure_engine(iqhip_engine *e, int device, int nstates, int nstates_user, int ncat, int64_t nptn, int ntaxa) {
@@ -85,6 +66,10 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     if (const char *f = getenv("IQHIP_POLL")) e->poll_result = atoi(f) != 0;
     if (const char *f = getenv("IQHIP_CHERRY_TABLES")) e->cherry_on = atoi(f) != 0;
     if (const char *sp = getenv("IQHIP_SPLIT")) e->split_target = atoi(sp);
+    if (const char *ml = getenv("IQHIP_LEVELS")) e->max_levels = std::max(1, atoi(ml));
+    if (const char *kb = getenv("IQHIP_MFMA_LDS_KB")) e->mfma_lds_kb = std::max(0, atoi(kb));
+    e->debug_plan = getenv("IQHIP_DEBUG_PLAN") != nullptr;
+    if (const char *br = getenv("IQHIP_DEBUG_BREAK_PLAN")) e->debug_break_plan = br;
     if (const char *v = getenv("IQHIP_NEWTON")) e->newton_chain_forced = !strcmp(v, "chain");
     if (const char *v = getenv("IQHIP_SWEEP")) e->sweep_one_submission = atoi(v) != 0;
     if (const char *v = getenv("IQHIP_SWEEP_KERNEL")) e->sweep_persistent = atoi(v) != 0;
@@ -311,7 +296,7 @@ static int new_slab(iqhip_engine *e, int *idx) {
     return IQHIP_OK;
 }
 
-static int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx) {
+int iqhip::slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx) {
     auto it = e->key2slab.find(key);
     if (it != e->key2slab.end()) {
         *idx = it->second;
@@ -473,8 +458,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
             else e->lane_split = e->lane_split_valu;
             e->tile = want_mfma ? 16 : 64;
             e->ntiles = e->nptn_pad / e->tile;
-            e->uploaded_plan.clear();
-            e->last_plan_version = 0;
+            e->plan_cache.invalidate();
             e->theta_valid = false;
             // k_newton's posted exchange resets, per launch, the slots its OWN grid used in the other parity; the grid
             // follows ntiles, so after a layout change start both parities from the all-ones state again
@@ -534,14 +518,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
                     Ui4[(size_t)ks * 64 + l] = inv_evec[(size_t)row * n + k];
                 }
     }
-    if (e->d_model && e->model_cap < total) {
-        HIPCHK(hipFree(e->d_model));
-        e->d_model = nullptr;
-    }
-    if (!e->d_model) {
-        HIPCHK(dmalloc(&e->d_model, total));
-        e->model_cap = total;
-    }
+    if (e->model_cap < total) HIPCHK(regrow(e, &e->d_model, &e->model_cap, total, total));
     HIPCHK(hipMemcpy(e->d_model, blk.data(), sizeof(double) * total, hipMemcpyHostToDevice));
     e->d_eval = e->d_model + o_eval;
     e->d_evec = e->d_model + o_evec;
@@ -587,14 +564,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
             }
         }
         e->img_generic_off = mix_doubles;
-        if (e->d_img && e->img_cap < img.size()) {
-            HIPCHK(hipFree(e->d_img));
-            e->d_img = nullptr;
-        }
-        if (!e->d_img) {
-            HIPCHK(dmalloc(&e->d_img, img.size()));
-            e->img_cap = img.size();
-        }
+        if (e->img_cap < img.size()) HIPCHK(regrow(e, &e->d_img, &e->img_cap, img.size(), img.size()));
         HIPCHK(hipMemcpy(e->d_img, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
     }
     // the pipelined kernels hold one eigen-system in registers / LDS: mixtures take the generic kernel,
@@ -602,8 +572,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
     const bool pipelined = e->mfma_pipelined_ok && nclass == 1;
     if (pipelined != e->mfma_pipelined || nclass != e->nclass) {
         e->mfma_pipelined = pipelined;
-        e->uploaded_plan.clear();
-        e->last_plan_version = 0;
+        e->plan_cache.invalidate();
     }
     e->nclass = nclass;
     e->state_unknown = state_unknown;
@@ -621,7 +590,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
 // ---------------------------------------------------------------------------------------
 // cherry tables (DevOp::cherry): which engines use them, and their pair engine
 // ---------------------------------------------------------------------------------------
-static bool cherry_candidate(const iqhip_engine *e) {
+bool iqhip::cherry_candidate(const iqhip_engine *e) {
     if (!e || !e->cherry_on || !e->shards.empty() || e->ablate) return false;   // (a planning-only engine plans them too)
     if (!e->mfma_pipelined_ok || e->n_user != e->n) return false;
     if (e->n == 20) return e->ncat == 4 && !e->leaf_tables && !e->cat_split && e->nptn_pad >= 8 * 1024;
@@ -715,40 +684,12 @@ extern "C" int iqhip_set_mixture_model(iqhip_engine *e, int nclass, const int32_
 }
 
 // ---------------------------------------------------------------------------------------
-// plan building
+// submissions (the descriptors come from the planner, plan.hip)
 // ---------------------------------------------------------------------------------------
-static int ensure_plan_capacity(iqhip_engine *e, int nops) {
-    if (nops <= e->ops_cap) return IQHIP_OK;
-    int cap = std::max(64, nops * 2);
-    if (e->planner) {
-        free(e->h_ops);
-        e->h_ops = static_cast<DevOp *>(calloc((size_t)cap, sizeof(DevOp)));
-        if (!e->h_ops) return fail(IQHIP_ERR_NOMEM, "plan staging");
-        e->d_ops = fake_alloc<DevOp>(e, (size_t)cap);
-        e->ops_cap = cap;
-        e->uploaded_plan.clear();
-        return IQHIP_OK;
-    }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_ops) hipFree(e->d_ops);
-    if (e->h_ops) hipHostFree(e->h_ops);
-    e->d_ops = nullptr; e->h_ops = nullptr; e->ops_cap = 0;
-    e->uploaded_plan.clear();
-    HIPCHK(dmalloc(&e->d_ops, cap));
-    HIPCHK(hipHostMalloc((void **)&e->h_ops, sizeof(DevOp) * cap));
-    e->ops_cap = cap;
-    return IQHIP_OK;
-}
-
 static int ensure_slab_rows(iqhip_engine *e, int nrows) {
     const int64_t need = (int64_t)nrows * e->ntiles * e->lane_split;
     if (need <= e->slab_cap) return IQHIP_OK;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_slab) hipFree(e->d_slab);
-    e->d_slab = nullptr;
-    e->slab_cap = 0;
-    HIPCHK(dmalloc(&e->d_slab, (size_t)need));
-    e->slab_cap = need;
+    HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, need, need));
     return IQHIP_OK;
 }
 
@@ -758,678 +699,6 @@ static int check_ready(iqhip_engine *e) {
         return fail(IQHIP_ERR_INVALID, "engine needs iqhip_set_model and iqhip_set_alignment first");
     hipError_t s = use_device(e);
     if (s != hipSuccess) return fail(IQHIP_ERR_HIP, hipGetErrorString(s));
-    return IQHIP_OK;
-}
-
-// Resolve one child of a node op. prev_dst = slab index written by the previous op (-1: none).
-static int resolve_child(iqhip_engine *e, uint64_t key, int32_t leaf, int prev_dst,
-                         const double **plh, const int16_t **sc, const uint8_t **states,
-                         int32_t *kind) {
-    *plh = nullptr; *sc = nullptr; *states = nullptr;
-    if (leaf >= 0) {
-        if (leaf >= e->ntaxa) return fail(IQHIP_ERR_INVALID, "leaf id out of range");
-        *states = e->d_states + (size_t)leaf * e->nptn_pad;
-        *kind = CHILD_LEAF;
-        return IQHIP_OK;
-    }
-    int idx;
-    int rc = slab_for_key(e, key, false, &idx);
-    if (rc) return rc;
-    *plh = e->slabs[idx].plh;
-    *sc = e->slabs[idx].sc;
-    *kind = (idx == prev_dst) ? CHILD_PREV : CHILD_LOAD;
-    return IQHIP_OK;
-}
-
-// The kernels' contract on a plan, checked on the host before the descriptors go to the device (IQHIP_CHECK_PLAN=1; always
-// for a planning-only engine).  The traversal kernels issue the requests of op k+1 unconditionally while op k computes
-// (streamed child, its counters, leaf state rows, K2 table rows), so EVERY pointer of EVERY descriptor -- the look-ahead
-// sentinels behind the last op included -- must be a dereferenceable address of the right kind even when the op does not
-// use it: a null tabL / tabR of a non-leaf child was a GPU memory fault in round 2 that this check finds without a GPU.
-static int check_plan(iqhip_engine *e, int nops, int nsentinels) {
-    std::unordered_set<const void *> vecs, scs;
-    for (const Slab &sl : e->slabs) { vecs.insert(sl.plh); scs.insert(sl.sc); }
-    vecs.insert(e->dummy.plh);
-    scs.insert(e->dummy.sc);
-    const size_t per = (e->mfma && e->mfma_pipelined) ? leaf_table_doubles(e) : 0;
-    char msg[256];
-    auto bad = [&](int k, const char *what) {
-        snprintf(msg, sizeof msg, "plan check: op %d of %d (+%d sentinels): %s", k, nops, nsentinels, what);
-        return fail(IQHIP_ERR_INVALID, msg);
-    };
-    auto state_row = [&](const uint8_t *p) {
-        if (!p || !e->d_states || p < e->d_states) return false;
-        const size_t off = (size_t)(p - e->d_states);
-        return off % (size_t)e->nptn_pad == 0 && off / (size_t)e->nptn_pad < (size_t)e->ntaxa;
-    };
-    auto table = [&](const double *p) {
-        if (e->plan_nleaf_tabs == 0 && !e->d_leaf_tab) return p == nullptr;  // kernel variant without tables
-        if (!p || !e->d_leaf_tab || p < e->d_leaf_tab || per == 0) return false;
-        const size_t off = (size_t)(p - e->d_leaf_tab);
-        return off % per == 0 && off / per < e->leaf_tab_slots;
-    };
-    for (int k = 0; k < nops + nsentinels; k++) {
-        const DevOp &d = e->h_ops[k];
-        if (!vecs.count(d.dst) || d.dst == nullptr) return bad(k, "dst is not a vector slab");
-        if (!scs.count(d.dst_sc)) return bad(k, "dst_sc is not a counter slab");
-        if (!vecs.count(d.pf)) return bad(k, "pf (streamed child) is not a vector slab / the dummy slab");
-        if (!scs.count(d.pf_sc)) return bad(k, "pf_sc is not a counter slab / the dummy");
-        if (!vecs.count(d.ld)) return bad(k, "ld (second memory child) is not a vector slab / the dummy slab");
-        if (!scs.count(d.ld_sc)) return bad(k, "ld_sc is not a counter slab / the dummy");
-        if (!state_row(d.sl) || !state_row(d.sr)) return bad(k, "sl / sr is not a row of the state matrix");
-        if (!table(d.tabL) || !table(d.tabR)) return bad(k, "tabL / tabR is not a K2 table slot");
-        if (d.cherry) {
-            const size_t cper = (size_t)e->cherry_npairs * e->block;
-            if (!e->d_cherry_tab || cper == 0 || d.cherry < e->d_cherry_tab || (size_t)(d.cherry - e->d_cherry_tab) % cper != 0 ||
-                (size_t)(d.cherry - e->d_cherry_tab) / cper >= e->cherry_cap || k >= nops || d.left_kind != CHILD_LEAF ||
-                d.right_kind != CHILD_LEAF)
-                return bad(k, "cherry is not a cherry-table slot of an op with two leaf children");
-        }
-        if (k >= nops) continue;  // sentinels: pointers only
-        if (d.dst == e->dummy.plh || d.dst_sc == e->dummy.sc) return bad(k, "a real op writes the dummy slab");
-        const bool lk = d.left_kind == CHILD_LEAF || d.left_kind == CHILD_PF || d.left_kind == CHILD_HOLD ||
-                        (d.left_kind == CHILD_LOAD && e->mfma && !e->mfma_pipelined);
-        const bool rk = d.right_kind == CHILD_LEAF || d.right_kind == CHILD_PREV || d.right_kind == CHILD_LOAD;
-        if (!lk || !rk) return bad(k, "child kinds are not in canonical form");
-        if (d.left_kind == CHILD_PF && (d.pf == e->dummy.plh || !(d.real_mask & 1))) return bad(k, "streamed child without a real vector");
-        if (d.left_kind != CHILD_PF && !(e->mfma && !e->mfma_pipelined) && (d.real_mask & 1)) return bad(k, "real_mask set without a streamed child");
-        if (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh) return bad(k, "second memory child without a real vector");
-        if (d.dst == d.pf || d.dst == d.ld) return bad(k, "op writes one of its own children");
-        if (!(d.left_len >= 0.0) || !(d.right_len >= 0.0)) return bad(k, "negative or NaN branch length");
-        if (d.out_row < 0 || d.out_row >= nops) return bad(k, "out_row outside the caller's op list");
-        if (d.lds_left < 0 || d.lds_right < 0 || d.lds_left > e->plan_lds_doubles || d.lds_right > e->plan_lds_doubles)
-            return bad(k, "LDS region outside the launch's allocation");
-        if (d.sl_slot < 0 || d.sr_slot < 0 || d.sl_slot >= e->plan_state_slots || d.sr_slot >= e->plan_state_slots)
-            return bad(k, "leaf-state slot outside the launch's allocation");
-        if (d.chunk_nops < 0 || k + d.chunk_nops > nops) return bad(k, "LDS chunk runs past the plan");
-    }
-    // chunks tile the plan; the segment table stays inside it
-    for (int k = 0; k < nops;) {
-        if (e->h_ops[k].chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
-        k += e->h_ops[k].chunk_nops;
-    }
-    const int *tab = reinterpret_cast<const int *>(e->h_ops + e->plan_table_off);
-    int covered = 0;
-    for (int u = 0; u <= e->plan_nunits; u++) {
-        const int b = tab[2 * u], n = tab[2 * u + 1];
-        if (b < 0 || n < 0 || b + n > nops) return bad(b, "segment outside the plan");
-        covered += n;
-    }
-    if (covered != nops) return bad(nops, "segments do not cover the plan exactly once");
-    return IQHIP_OK;
-}
-
-// len_ptrs (sweeps): 2 * nops device pointers, [2k] / [2k+1] = where the length of op k's left / right child branch will
-// be found when the op runs (nullptr: the host value in the op)
-static int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_dst,
-                      const std::vector<int> *explicit_segs = nullptr, const double *const *len_ptrs = nullptr) {
-    constexpr int kSentinels = 2;  // >= the kernels' deepest look-ahead (streamed child: 1 op)
-    if (nops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
-    // Same op list as last time and no key created / released / moved since: the descriptors on
-    // the device are still the right ones (hot loop 1 re-evaluates one tree many times).
-    const size_t in_bytes = sizeof(iqhip_node_op) * (size_t)nops;
-    const std::vector<int> no_segs;
-    const std::vector<int> &segs_in = explicit_segs ? *explicit_segs : no_segs;
-    if (!len_ptrs && nops > 0 && e->last_plan_version == e->keymap_version && e->last_ops_in.size() == in_bytes &&
-        memcmp(e->last_ops_in.data(), ops, in_bytes) == 0 && !e->uploaded_plan.empty() && e->last_segs == segs_in &&
-        (!e->plan_uses_cherry || e->plan_cherry_model == e->model_version)) {
-        *last_dst = e->last_plan_dst;
-        return IQHIP_OK;
-    }
-    e->last_plan_version = 0;
-    int rc = IQHIP_OK;
-    if (e->staging_busy) {  // the previous submission may still be copying h_ops
-        HIPCHK(hipEventSynchronize(e->staging_free));
-        e->staging_busy = false;
-    }
-    int prev_dst = -1;
-    const int B = e->block;
-    e->plan_has_load = false;
-    e->plan_units_have_load = false;
-    // ---- staging.  A launch gives every 64/16-pattern tile one wave that walks the whole op list, so an
-    // alignment with few tiles leaves SIMDs idle or unevenly loaded (a tile is an indivisible unit of
-    // nops updates).  Independent subtrees of the plan are therefore cut out as "units" that run on
-    // their own workgroups in a first launch (tiles x units waves), and only the ops above them
-    // ("top") walk sequentially in a second launch.  order[p] = caller index of the op at position p.
-    std::vector<int> order(nops), seg_of(nops, 0);
-    std::vector<std::pair<int, int>> units;  // {begin, nops} in the new order, stage after stage
-    std::vector<int> stage_units;            // units per stage (launch)
-    int max_levels = 3;
-    if (const char *ml = getenv("IQHIP_LEVELS")) max_levels = std::max(1, atoi(ml));
-    int top_begin = 0;
-    for (int k = 0; k < nops; k++) order[k] = k;
-    if (explicit_segs) {
-        // caller-defined independent segments (a batch of branch tasks): one set of workgroups each, no top stage
-        std::unordered_set<uint64_t> dsts;
-        for (int k = 0; k < nops; k++)
-            if (!dsts.insert(ops[k].dst_key).second)
-                return fail(IQHIP_ERR_INVALID, "batched node updates must write distinct vectors");
-        int pos = 0;
-        for (size_t s = 0; s < explicit_segs->size(); s++) {
-            const int n = (*explicit_segs)[s];
-            if (n <= 0) continue;
-            units.push_back({pos, n});
-            for (int q = 0; q < n; q++) seg_of[pos + q] = (int)units.size();
-            pos += n;
-        }
-        if (pos != nops) return fail(IQHIP_ERR_INVALID, "segment sizes do not add up to the op count");
-        stage_units.push_back((int)units.size());
-        top_begin = nops;
-    } else {
-        int target = e->split_target;
-        const int64_t simds = (int64_t)e->num_cus * 4;
-        if (target < 0) {
-            // auto: the matrix-core kernels (16-pattern tiles, long per-tile op lists) when there are fewer
-            // than 6 tile-waves per SIMD; unit size so that the first launch has ~4 waves per SIMD.
-            // Measured at the BASELINE shapes: protein 1.28 -> 1.10 ms, codon 0.64 -> 0.49 ms; the 4-state
-            // kernel is store-bound and loses (0.161 -> 0.172..0.184 ms), so it stays unsplit.
-            target = 0;
-            if (e->mfma && e->ntiles < 6 * simds && nops >= 12)
-                target = (int)std::min<int64_t>(nops / 2, std::max<int64_t>(3, ((int64_t)nops * e->ntiles + 4 * simds - 1) / (4 * simds)));
-            // 4-state kernel: only while the whole alignment is at most one wave per SIMD, where a traversal
-            // is a latency-bound chain (50 taxa GTR+G4: 5k patterns 0.082 -> 0.045 ms, 20k 0.086 -> 0.060 ms;
-            // 60k patterns 0.109 -> 0.126 ms, so not there)
-            if (!e->mfma && e->ntiles * e->lane_split <= simds && nops >= 12) target = std::max(6, nops / 4);
-        }
-        if (target > 0 && target < nops && nops >= 4) {
-            std::unordered_map<uint64_t, int> prod;
-            std::unordered_set<uint64_t> ext_in;
-            std::vector<int> lc(nops, -1), rc(nops, -1);
-            std::vector<char> consumed(nops, 0);
-            bool safe = true;
-            for (int k = 0; k < nops && safe; k++) {
-                const iqhip_node_op &o = ops[k];
-                auto child = [&](uint64_t key, int32_t leaf) -> int {
-                    if (leaf >= 0) return -1;
-                    auto it = prod.find(key);
-                    if (it == prod.end()) { ext_in.insert(key); return -1; }
-                    return it->second;
-                };
-                lc[k] = child(o.left_key, o.left_leaf);
-                rc[k] = child(o.right_key, o.right_leaf);
-                if (lc[k] >= 0) { if (consumed[lc[k]]) safe = false; consumed[lc[k]] = 1; }
-                if (rc[k] >= 0) { if (consumed[rc[k]]) safe = false; consumed[rc[k]] = 1; }
-                // re-ordering is only safe when no vector of the plan is both an outside input and a
-                // destination (LM_PER_NODE buffer stealing) and nothing is written twice
-                if (prod.count(o.dst_key)) safe = false;
-                prod[o.dst_key] = k;
-            }
-            for (int k = 0; k < nops && safe; k++)
-                if (ext_in.count(ops[k].dst_key)) safe = false;
-            if (safe) {
-                // Level by level: among the ops not yet placed, the maximal subtrees of 2..target ops (vectors of
-                // earlier levels count as outside inputs) become the units of the next launch; what is left after
-                // the last level walks sequentially.  Every level is a launch of tiles x units waves, so the
-                // sequential tail -- where an alignment with slightly more tiles than SIMDs runs at half speed --
-                // shrinks from "everything above the first cut" to a few ops.
-                std::vector<char> placed(nops, 0);
-                std::vector<int> new_order;
-                new_order.reserve(nops);
-                int nseg = 0, left = nops;
-                const int min_top = std::max(2, std::min(target, 6));
-                for (int level = 0; level < max_levels && left > min_top; level++) {
-                    std::vector<int> rem;  // unplaced ops in post-order
-                    for (int k = 0; k < nops; k++)
-                        if (!placed[k]) rem.push_back(k);
-                    const int R = (int)rem.size();
-                    std::vector<int> pos_of(nops, -1), l2(R, -1), r2(R, -1), sz(R, 1);
-                    std::vector<char> cont(R, 1), cons(R, 0);
-                    for (int q = 0; q < R; q++) pos_of[rem[q]] = q;
-                    for (int q = 0; q < R; q++) {
-                        const int k = rem[q];
-                        if (lc[k] >= 0 && !placed[lc[k]]) { l2[q] = pos_of[lc[k]]; cons[l2[q]] = 1; sz[q] += sz[l2[q]]; }
-                        if (rc[k] >= 0 && !placed[rc[k]]) { r2[q] = pos_of[rc[k]]; cons[r2[q]] = 1; sz[q] += sz[r2[q]]; }
-                        // post-order contiguity within the unplaced sequence: the subtree of q is exactly [q - sz + 1, q]
-                        const int a = std::max(l2[q], r2[q]), b2 = std::min(l2[q], r2[q]);
-                        bool c2 = true;
-                        if (a >= 0) c2 = (a == q - 1) && cont[a];
-                        if (b2 >= 0) c2 = c2 && (b2 == a - sz[a]) && cont[b2];
-                        cont[q] = c2;
-                    }
-                    std::vector<int> stack;
-                    for (int q = R - 1; q >= 0; q--)
-                        if (!cons[q]) stack.push_back(q);
-                    std::vector<std::pair<int, int>> found;  // {root position, size}
-                    while (!stack.empty()) {
-                        const int q = stack.back();
-                        stack.pop_back();
-                        if (sz[q] <= target && sz[q] >= 2 && cont[q]) {
-                            found.push_back({q, sz[q]});
-                        } else {
-                            if (l2[q] >= 0) stack.push_back(l2[q]);
-                            if (r2[q] >= 0) stack.push_back(r2[q]);
-                        }
-                    }
-                    if (found.size() < 2) break;
-                    std::stable_sort(found.begin(), found.end(),
-                                     [](const std::pair<int, int> &x, const std::pair<int, int> &y2) { return x.second > y2.second; });
-                    int in_stage = 0;
-                    for (size_t u = 0; u < found.size(); u++) {
-                        units.push_back({(int)new_order.size(), found[u].second});
-                        nseg++;
-                        in_stage++;
-                        for (int q = found[u].first - found[u].second + 1; q <= found[u].first; q++) {
-                            seg_of[new_order.size()] = nseg;
-                            placed[rem[q]] = 1;
-                            new_order.push_back(rem[q]);
-                            left--;
-                        }
-                    }
-                    stage_units.push_back(in_stage);
-                }
-                if (!units.empty()) {
-                    top_begin = (int)new_order.size();
-                    for (int k = 0; k < nops; k++)
-                        if (!placed[k]) { seg_of[new_order.size()] = 0; new_order.push_back(k); }
-                    order = new_order;
-                }
-            }
-        }
-    }
-    if (getenv("IQHIP_DEBUG_PLAN")) {
-        fprintf(stderr, "[iqhip] plan: %d ops, %zu stages of units (", nops, stage_units.size());
-        size_t ui = 0;
-        for (int n : stage_units) {
-            for (int q = 0; q < n; q++) fprintf(stderr, "%d ", units[ui++].second);
-            fprintf(stderr, "| ");
-        }
-        fprintf(stderr, ") top %d ops\n", nops - top_begin);
-    }
-    const int table_ints = 2 * (1 + (int)units.size());
-    const int table_ops = (int)((table_ints * sizeof(int) + sizeof(DevOp) - 1) / sizeof(DevOp));
-    // (room for the K2 table job list behind the segment table: at most two leaf children per op)
-    const int jobs_ops_max = (int)((sizeof(TabJob) * (size_t)(2 * nops + 1) + sizeof(DevOp) - 1) / sizeof(DevOp));
-    rc = ensure_plan_capacity(e, nops + kSentinels + table_ops + jobs_ops_max);
-    if (rc) return rc;
-    auto dummy_op = [&](DevOp &d) {
-        memset(&d, 0, sizeof(d));
-        d.dst = e->dummy.plh;
-        d.dst_sc = e->dummy.sc;
-        d.pf = d.ld = e->dummy.plh;
-        d.pf_sc = d.ld_sc = e->dummy.sc;
-        d.sl = d.sr = e->d_states;
-        d.tabL = d.tabR = e->d_leaf_tab;
-    };
-    for (int k = 0; k < nops; k++) {
-        const iqhip_node_op &o = ops[order[k]];
-        DevOp &d = e->h_ops[k];
-        dummy_op(d);
-        d.out_row = order[k];
-        d.no_scale = (o.flags & IQHIP_OP_NO_SCALE) ? 1 : (((o.flags & IQHIP_OP_SCALAR_RULE) || e->scalar_rule_all) ? 2 : 0);
-        if (k > 0 && seg_of[k] != seg_of[k - 1]) prev_dst = -1;  // another workgroup: no register hand-over
-        if (!(o.left_len >= 0.0) || !(o.right_len >= 0.0))
-            return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
-        const double *lp, *rp;
-        const int16_t *lsc, *rsc;
-        const uint8_t *lst, *rst;
-        int32_t lkind, rkind;
-        rc = resolve_child(e, o.left_key, o.left_leaf, prev_dst, &lp, &lsc, &lst, &lkind);
-        if (rc) return rc;
-        rc = resolve_child(e, o.right_key, o.right_leaf, prev_dst, &rp, &rsc, &rst, &rkind);
-        if (rc) return rc;
-        int didx;
-        rc = slab_for_key(e, o.dst_key, true, &didx);
-        if (rc) return rc;
-        if ((lkind != CHILD_LEAF && lp == e->slabs[didx].plh) || (rkind != CHILD_LEAF && rp == e->slabs[didx].plh))
-            return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
-        if (lkind == CHILD_PREV && rkind == CHILD_PREV)
-            return fail(IQHIP_ERR_INVALID, "node update uses the same vector for both children");
-        double llen = o.left_len, rlen = o.right_len;
-        const double *llen_p = len_ptrs ? len_ptrs[2 * order[k]] : nullptr, *rlen_p = len_ptrs ? len_ptrs[2 * order[k] + 1] : nullptr;
-        d.dst = e->slabs[didx].plh;
-        d.dst_sc = e->slabs[didx].sc;
-        if (e->mfma && !e->mfma_pipelined) {
-            // generic matrix-core kernel: both children are read from memory (pf = left, ld = right)
-            if (lkind != CHILD_LEAF) { lkind = CHILD_LOAD; d.pf = lp; d.pf_sc = lsc; } else d.sl = lst;
-            if (rkind != CHILD_LEAF) { rkind = CHILD_LOAD; d.ld = rp; d.ld_sc = rsc; } else d.sr = rst;
-        } else {
-            // canonical form (the Hadamard product commutes): left in {LEAF, PF}, right in
-            // {LEAF, PREV}; the only other shape is (PF, LOAD): two memory children, neither of
-            // them the previous result -- the kernel reads the second one synchronously.
-            auto swap_children = [&]() {
-                std::swap(lp, rp); std::swap(lsc, rsc); std::swap(lst, rst);
-                std::swap(lkind, rkind); std::swap(llen, rlen); std::swap(llen_p, rlen_p);
-            };
-            if (lkind == CHILD_PREV) swap_children();                              // PREV goes right
-            else if (lkind == CHILD_LEAF && rkind == CHILD_LOAD) swap_children();  // memory child goes left
-            if (lkind == CHILD_LOAD) lkind = CHILD_PF;
-            if (rkind == CHILD_LOAD) { if (seg_of[k]) e->plan_units_have_load = true; else e->plan_has_load = true; }  // (PF, LOAD)
-            if (lkind == CHILD_PF) { d.pf = lp; d.pf_sc = lsc; d.real_mask |= 1; }
-            if (rkind == CHILD_LOAD) { d.ld = rp; d.ld_sc = rsc; }
-            if (lkind == CHILD_LEAF) d.sl = lst;
-            if (rkind == CHILD_LEAF) d.sr = rst;
-            if (e->ablate & 1) d.real_mask &= ~1;  // timing-only: never stream a child (results wrong)
-        }
-        d.left_kind = lkind;
-        d.right_kind = rkind;
-        d.left_len = llen;
-        d.right_len = rlen;
-        d.left_len_p = llen_p;
-        d.right_len_p = rlen_p;
-        prev_dst = didx;
-    }
-    // HOLD analysis (4-state kernel): a streamed left child produced by op j of this plan can stay
-    // in registers until its join k if no op in (j, k) streams, loads or parks anything itself
-    // (the usual case after heavier-first ordering: the other subtree is a short chain).
-    const bool hold_regs = !e->mfma && !(e->ablate & 4) && (e->use_hold || e->lane_split != 1 || e->wg_size != 256);
-    // (20 states, one wave per tile: the parking place is LDS; the launch reserves it when plan_nhold > 0)
-    const bool hold_in_lds = e->mfma && e->mfma_pipelined && e->hold_lds && e->n == 20 && !e->cat_split;
-    e->plan_nhold = 0;
-    if (hold_regs || hold_in_lds) {
-        std::unordered_map<const double *, int> producer;
-        for (int k = 0; k < nops; k++) {
-            DevOp &d = e->h_ops[k];
-            if (d.left_kind == CHILD_PF) {
-                auto it = producer.find(d.pf);
-                if (it != producer.end()) {
-                    const int j = it->second;
-                    bool ok = !e->h_ops[j].push_hold && seg_of[j] == seg_of[k];
-                    if (hold_in_lds && e->top_cs2 && seg_of[k] == 0) ok = false;   // (two waves per tile there: no parking place)
-                    for (int q = j + 1; q < k && ok; q++) {
-                        const DevOp &m = e->h_ops[q];
-                        ok = m.left_kind != CHILD_PF && m.left_kind != CHILD_HOLD && m.right_kind != CHILD_LOAD &&
-                             !m.push_hold;
-                    }
-                    if (ok) {
-                        e->h_ops[j].push_hold = 1;
-                        d.left_kind = CHILD_HOLD;
-                        d.pf = e->dummy.plh;
-                        d.pf_sc = e->dummy.sc;
-                        d.real_mask &= ~1;
-                        e->plan_nhold++;
-                    }
-                }
-            }
-            producer[d.dst] = k;
-        }
-    }
-    if (getenv("IQHIP_DEBUG_PLAN")) {
-        int npf = 0;
-        for (int k = 0; k < nops; k++) npf += (e->h_ops[k].left_kind == CHILD_PF) + (e->h_ops[k].right_kind == CHILD_LOAD);
-        fprintf(stderr, "[iqhip] plan: %d children read back from memory, %d parked\n", npf, e->plan_nhold);
-    }
-    // K2 tables of the leaf children (pipelined matrix-core kernels): slot = taxon, rebuilt by k_leaf_tables before
-    // the traversal only where the pendant branch length (or the model) changed since the slot was last built
-    e->plan_nleaf_tabs = 0;
-    e->plan_tab_jobs.clear();
-    e->plan_tab_dirty = 0;
-    if (e->mfma && e->mfma_pipelined && e->leaf_tables) {
-        const size_t per = leaf_table_doubles(e);
-        struct Use { double len; const double *len_p; int slot; };
-        std::unordered_map<int, std::vector<Use>> seen;  // taxon -> lengths used in this plan
-        int noverflow = 0;
-        std::vector<TabJob> dirty, clean;
-        std::vector<std::pair<int, int>> uses;  // (op index, side) -> slot, resolved to pointers after (re)allocation
-        std::vector<int> use_slot;
-        const bool model_changed = e->tab_model_version != e->model_version;
-        for (int k = 0; k < nops; k++) {
-            DevOp &d = e->h_ops[k];
-            for (int side = 0; side < 2; side++) {
-                if ((side ? d.right_kind : d.left_kind) != CHILD_LEAF) continue;
-                const uint8_t *row = side ? d.sr : d.sl;
-                const int taxon = (int)((row - e->d_states) / e->nptn_pad);
-                const double *len_p = side ? d.right_len_p : d.left_len_p;   // (sweeps: the length is on the device)
-                const double len = len_p ? NAN : (side ? d.right_len : d.left_len);
-                std::vector<Use> &u = seen[taxon];
-                int slot = -1;
-                for (const Use &x : u)
-                    if (x.len_p == len_p && (len_p || x.len == len)) slot = x.slot;
-                if (slot < 0) {
-                    slot = u.empty() ? taxon : e->ntaxa + noverflow++;
-                    u.push_back({len, len_p, slot});
-                    TabJob j;
-                    j.len = len;
-                    j.len_p = len_p;
-                    j._pad = 0.0;
-                    j.tab = reinterpret_cast<double *>((size_t)slot);  // slot number for now
-                    const bool cached = !len_p && slot < e->ntaxa && !model_changed && (size_t)slot < e->tab_len.size() &&
-                                        e->tab_len[slot] == len;
-                    (cached ? clean : dirty).push_back(j);
-                }
-                uses.push_back({k, side});
-                use_slot.push_back(slot);
-            }
-        }
-        const size_t need = (size_t)e->ntaxa + (size_t)noverflow;
-        if (need > e->leaf_tab_slots) {
-            const size_t slots = need + 16;
-            if (e->planner) {
-                e->d_leaf_tab = fake_alloc<double>(e, slots * per);
-            } else {
-                HIPCHK(hipStreamSynchronize(e->stream));
-                if (e->d_leaf_tab) hipFree(e->d_leaf_tab);
-                e->d_leaf_tab = nullptr;
-                e->leaf_tab_slots = 0;
-                HIPCHK(dmalloc(&e->d_leaf_tab, slots * per));
-            }
-            e->leaf_tab_slots = slots;
-            e->uploaded_plan.clear();
-            // a new buffer holds no tables: everything this plan uses is dirty
-            dirty.insert(dirty.end(), clean.begin(), clean.end());
-            clean.clear();
-            e->tab_len.assign(slots, NAN);
-        }
-        if (e->tab_len.size() < e->leaf_tab_slots) e->tab_len.resize(e->leaf_tab_slots, NAN);
-        if (model_changed) {  // tables of other plans are stale as well
-            std::fill(e->tab_len.begin(), e->tab_len.end(), NAN);
-            e->tab_model_version = e->model_version;
-        }
-        // non-leaf children point at slot 0: the kernels may request a row unconditionally (one step ahead)
-        for (int k = 0; k < nops; k++) e->h_ops[k].tabL = e->h_ops[k].tabR = e->d_leaf_tab;
-        for (size_t q = 0; q < uses.size(); q++) {
-            DevOp &d = e->h_ops[uses[q].first];
-            (uses[q].second ? d.tabR : d.tabL) = e->d_leaf_tab + (size_t)use_slot[q] * per;
-        }
-        for (std::vector<TabJob> *v : {&dirty, &clean})
-            for (TabJob &j : *v) {
-                const size_t slot = (size_t)j.tab;
-                j.tab = e->d_leaf_tab + slot * per;
-                e->tab_len[slot] = slot < (size_t)e->ntaxa ? j.len : NAN;  // overflow slots are never reused
-                e->plan_tab_jobs.push_back(j);
-            }
-        e->plan_tab_dirty = (int)dirty.size();
-        e->plan_nleaf_tabs = (int)e->plan_tab_jobs.size();
-    }
-    // cherry tables: an op whose two children are leaves reads its result out of the table of its pair of taxa
-    e->plan_cherry_jobs.clear();
-    e->plan_uses_cherry = false;
-    e->plan_cherry_model = e->model_version;
-    // (planning-only engine: the tables are never built, their slots are fake addresses like every other buffer)
-    const bool have_pair = e->planner ? e->cherry_s2 > 0 : (e->pair && e->cherry_model_synced);
-    if (cherry_candidate(e) && e->mfma_pipelined && have_pair && nops >= 8) {
-        const size_t per = (size_t)e->cherry_npairs * B;
-        const size_t want = (size_t)2 * e->ntaxa + 16;
-        if (e->cherry_cap < want && e->planner) {
-            e->d_cherry_tab = fake_alloc<double>(e, want * per);
-            e->cherry_cap = want;
-        } else if (e->cherry_cap < want) {
-            HIPCHK(hipStreamSynchronize(e->stream));
-            if (e->d_cherry_tab) hipFree(e->d_cherry_tab);
-            e->d_cherry_tab = nullptr;
-            e->cherry_cap = 0;
-            HIPCHK(dmalloc(&e->d_cherry_tab, want * per));
-            e->cherry_cap = want;
-            e->cherry_slot_of.clear();
-            e->cherry_slots.clear();
-        }
-        // room for every cherry a plan can hold; a search that has walked through more pairs than that starts over
-        if (e->cherry_slots.size() + (size_t)e->ntaxa / 2 + 1 > e->cherry_cap) {
-            e->cherry_slot_of.clear();
-            e->cherry_slots.clear();
-        }
-        const uint64_t stamp = ++e->cherry_stamp;
-        for (int k = 0; k < nops; k++) {
-            DevOp &d = e->h_ops[k];
-            if (d.left_kind != CHILD_LEAF || d.right_kind != CHILD_LEAF || d.left_len_p || d.right_len_p) continue;
-            // (the top stage's two-waves-per-tile / row-split kernels compute their cherries)
-            if ((e->top_cs2 || (e->n == 64 && e->mixed_top)) && seg_of[k] == 0) continue;
-            const uint64_t tl = (uint64_t)((d.sl - e->d_states) / e->nptn_pad), tr = (uint64_t)((d.sr - e->d_states) / e->nptn_pad);
-            const uint64_t key = (tl << 32) | tr;
-            auto it = e->cherry_slot_of.find(key);
-            int slot;
-            if (it == e->cherry_slot_of.end()) {
-                if (e->cherry_slots.size() >= e->cherry_cap) continue;
-                slot = (int)e->cherry_slots.size();
-                e->cherry_slots.emplace_back();
-                e->cherry_slot_of[key] = slot;
-            } else {
-                slot = it->second;
-            }
-            iqhip_engine::CherrySlot &cs = e->cherry_slots[slot];
-            const bool same = cs.len_l == d.left_len && cs.len_r == d.right_len;
-            if (cs.stamp == stamp && !same) continue;   // (the same pair with other lengths in one plan: computed the ordinary way)
-            if (!same || cs.model_version != e->model_version) {
-                cs.len_l = d.left_len;
-                cs.len_r = d.right_len;
-                cs.model_version = 0;   // until built (submit_traverse)
-                if (cs.stamp != stamp) e->plan_cherry_jobs.push_back(slot);
-            }
-            cs.stamp = stamp;
-            d.cherry = e->d_cherry_tab + (size_t)slot * per;
-            e->plan_uses_cherry = true;
-        }
-    }
-    for (int q = 0; q < kSentinels; q++) dummy_op(e->h_ops[nops + q]);  // targets of the look-ahead requests
-    *last_dst = prev_dst;
-    // LDS layout of the per-(op, child) regions, cut into chunks that fit the budget
-    {
-        int budget;
-        if (e->mfma) {
-            const int MT = (e->n + 15) / 16, KS = e->n / 4;
-            int fixed = (e->row_split && e->mfma_pipelined) ? (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128
-                              : (e->mfma_pipelined ? mfma2_fixed_lds_doubles(e->n) : 2 * MT * KS * 64) +
-                                    (e->state_unknown + 1 - e->n) * e->n;
-            // (64 states: a launch may mix both roles, k_traverse_mfma_top64)
-            if (e->mfma_pipelined && e->n == 64) fixed = std::max(fixed, (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128);
-            // two workgroups per CU (160 KB LDS): <= 78 KB each, images included (a third workgroup
-            // for the 20-state kernel was measured: no gain, more chunks); IQHIP_MFMA_LDS_KB overrides
-            int total_kb = e->n == 20 ? 75 : 78;   // (20 states: + 2.6 KB of static arrays per workgroup, the fill's descriptor copies)
-            const char *kb_env = getenv("IQHIP_MFMA_LDS_KB");
-            if (kb_env) total_kb = atoi(kb_env);
-            if (e->plan_nhold > 0) fixed += 4 * 16 * B;   // the waves' parking places (CHILD_HOLD in LDS)
-            budget = (total_kb * 1024) / 8 - fixed;
-            // the generic kernel's images leave two workgroups per CU too little for one op with two vector children once
-            // n * ncat > 864 (64 states, 14 .. 16 categories or components): one workgroup per CU, 150 KB (every matrix-core
-            // kernel allows that much dynamic LDS)
-            if (!kb_env && !e->mfma_pipelined && budget < 2 * B) budget = (150 * 1024) / 8 - fixed;
-        } else {
-            budget = (e->lds_budget_bytes / 8) - 128 - B;
-        }
-        const bool tables_in_lds = e->mfma && e->mfma_pipelined && e->n == 20 && e->plan_nleaf_tabs > 0;
-        int chunk_start = 0, used = e->mfma ? 0 : e->wg_size / 8, regs = 0, max_used = 0, slots = 1, max_slots = 1;
-        for (int k = 0; k < nops; k++) {
-            DevOp &d = e->h_ops[k];
-            // a LEAF child's region: 4 states -- exponentials + the 5-row K2 table; 20 states with leaf tables -- the
-            // child's whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
-            const int leaf_sz = !e->mfma ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
-            const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : B;
-            const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : B;
-            // 4-state path: each leaf child also stages one state byte per thread in LDS
-            const int nleaf = (d.left_kind == CHILD_LEAF) + (d.right_kind == CHILD_LEAF);
-            const int need = szl + szr + (e->mfma ? 0 : nleaf * e->wg_size / 8);
-            if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
-            if ((used + need > budget || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
-                e->h_ops[chunk_start].chunk_nops = k - chunk_start;
-                chunk_start = k;
-                used = e->mfma ? 0 : e->wg_size / 8;  // slot 0
-                regs = 0;
-                slots = 1;
-            }
-            d.lds_left = regs;
-            d.lds_right = regs + szl;
-            regs += szl + szr;
-            used += need;
-            if (regs > max_used) max_used = regs;
-            d.sl_slot = d.left_kind == CHILD_LEAF ? slots++ : 0;
-            d.sr_slot = d.right_kind == CHILD_LEAF ? slots++ : 0;
-            if (slots > max_slots) max_slots = slots;
-        }
-        e->plan_state_slots = max_slots;
-        if (nops > 0) e->h_ops[chunk_start].chunk_nops = nops - chunk_start;
-        e->plan_lds_doubles = max_used;
-    }
-    // the descriptors of a repeated plan (model-parameter optimisation re-evaluates the same
-    // tree) are already on the device: skip the upload, never the computation
-    {
-        int *tab = reinterpret_cast<int *>(e->h_ops + nops + kSentinels);
-        memset(tab, 0, sizeof(DevOp) * (size_t)table_ops);
-        tab[0] = top_begin;
-        tab[1] = nops - top_begin;
-        for (size_t u = 0; u < units.size(); u++) { tab[2 + 2 * u] = units[u].first; tab[3 + 2 * u] = units[u].second; }
-        e->plan_nunits = (int)units.size();
-        e->plan_stage_units = stage_units;
-        e->plan_top_nops = nops - top_begin;
-        e->plan_table_off = nops + kSentinels;
-    }
-    e->plan_jobs_off = nops + kSentinels + table_ops;
-    const int jobs_ops = (int)((sizeof(TabJob) * e->plan_tab_jobs.size() + sizeof(DevOp) - 1) / sizeof(DevOp));
-    if (jobs_ops > 0) {
-        memset(e->h_ops + e->plan_jobs_off, 0, sizeof(DevOp) * (size_t)jobs_ops);
-        memcpy(e->h_ops + e->plan_jobs_off, e->plan_tab_jobs.data(), sizeof(TabJob) * e->plan_tab_jobs.size());
-    }
-    const size_t nbytes = sizeof(DevOp) * (size_t)(nops + kSentinels + table_ops + jobs_ops);
-    e->last_ops_in.assign((const char *)ops, (const char *)ops + in_bytes);
-    e->last_segs = segs_in;
-    e->last_plan_version = len_ptrs ? 0 : e->keymap_version;  // (slabs created while building are included; a sweep step's plan is never re-used)
-    e->last_plan_dst = prev_dst;
-    // a small plan of the 4-state kernel rides in the kernel arguments (launch_traverse4 copies it out of h_ops)
-    // (matrix-core path: the pipelined 20-state kernels without leaf tables -- tables come with a job list in the buffer)
-    const bool small_kernel = !e->mfma || (e->mfma_pipelined && e->n == 20 && !e->leaf_tables && e->plan_nleaf_tabs == 0);
-    e->plan_small = e->small_plans && small_kernel && !explicit_segs && units.empty() && nops > 0 && nops + kSentinels <= kSmallPlanOps;
-    e->plan_small_nops = nops;
-    if (e->planner) {   // negative tests: break one descriptor the way round 2's fault did
-        const char *br = getenv("IQHIP_DEBUG_BREAK_PLAN");
-        if (br && nops > 0) {
-            if (!strcmp(br, "tab")) e->h_ops[nops - 1].tabL = nullptr;
-            else if (!strcmp(br, "sentinel")) e->h_ops[nops + kSentinels - 1].pf = nullptr;
-            else if (!strcmp(br, "states")) e->h_ops[0].sr = nullptr;
-            else if (!strcmp(br, "cherry")) {
-                for (int k = 0; k < nops; k++)
-                    if (e->h_ops[k].cherry) { e->h_ops[k].cherry += 8; break; }   // (inside the buffer, not on a table)
-            }
-        }
-    }
-    if (e->check_plans && !e->ablate) {
-        rc = check_plan(e, nops, kSentinels);
-        if (rc) { e->last_plan_version = 0; e->uploaded_plan.clear(); return rc; }
-    }
-    if (e->planner) return IQHIP_OK;   // (nothing to upload to)
-    if (e->plan_small) {
-        e->uploaded_plan.assign((const char *)e->h_ops, (const char *)e->h_ops + nbytes);   // (what d_ops would hold)
-        return IQHIP_OK;
-    }
-    if (e->uploaded_plan.size() == nbytes && memcmp(e->uploaded_plan.data(), e->h_ops, nbytes) == 0)
-        return IQHIP_OK;
-    if (e->plan_arena_on && e->plan_arena_used + nbytes <= e->plan_arena_cap) {
-        // a sweep enqueues many plans before the device has run the first: each upload goes out of a slice of its own
-        // of a pinned arena, so that re-using h_ops for the next plan never has to wait for the device (that wait -- the
-        // staging event below -- made the host fall in step with the device eight times per 97-branch protein sweep)
-        char *slice = e->h_plan_arena + e->plan_arena_used;
-        memcpy(slice, e->h_ops, nbytes);
-        e->plan_arena_used += (nbytes + 255) / 256 * 256;
-        HIPCHK(hipMemcpyAsync(e->d_ops, slice, nbytes, hipMemcpyHostToDevice, e->stream));
-        e->uploaded_plan.assign((const char *)e->h_ops, (const char *)e->h_ops + nbytes);
-        return IQHIP_OK;
-    }
-    HIPCHK(hipMemcpyAsync(e->d_ops, e->h_ops, nbytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipEventRecord(e->staging_free, e->stream));
-    e->staging_busy = true;
-    e->uploaded_plan.assign((const char *)e->h_ops, (const char *)e->h_ops + nbytes);
-    return IQHIP_OK;
-}
-
-static int build_branch(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len,
-                        int prev_dst, DevBranch *br) {
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
-    if (a.leaf >= 0 && b.leaf >= 0)
-        return fail(IQHIP_ERR_INVALID, "branch with two leaf ends (2-taxon tree) is not supported");
-    if (b.leaf >= 0) std::swap(a, b);  // the reference puts the leaf on the `dad` side (:739-746)
-    const uint8_t *st_unused;
-    int rc = resolve_child(e, a.key, a.leaf, prev_dst, &br->a, &br->a_sc, &br->a_states, &br->a_kind);
-    if (rc) return rc;
-    rc = resolve_child(e, b.key, b.leaf, prev_dst, &br->b, &br->b_sc, &st_unused, &br->b_kind);
-    if (rc) return rc;
-    br->len = len;
     return IQHIP_OK;
 }
 
@@ -1458,14 +727,14 @@ static int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
 // submission, same stream), then the move into register order
 static int build_cherry_tables(iqhip_engine *e) {
     iqhip_engine *p = e->pair;
-    const int n = (int)e->plan_cherry_jobs.size();
+    const int n = (int)e->plan.cherry_jobs.size();
     std::vector<iqhip_node_op> ops((size_t)n);
     const std::vector<int> segs((size_t)n, 1);
     for (int i = 0; i < n; i++) {
-        const iqhip_engine::CherrySlot &cs = e->cherry_slots[e->plan_cherry_jobs[i]];
+        const iqhip_engine::CherrySlot &cs = e->cherry_slots[e->plan.cherry_jobs[i]];
         iqhip_node_op &o = ops[i];
         memset(&o, 0, sizeof o);
-        o.dst_key = (uint64_t)e->plan_cherry_jobs[i] + 1;
+        o.dst_key = (uint64_t)e->plan.cherry_jobs[i] + 1;
         o.left_leaf = 0;
         o.right_leaf = 1;
         o.left_len = cs.len_l;
@@ -1482,12 +751,12 @@ static int build_cherry_tables(iqhip_engine *e) {
         rc = slab_for_key(p, ops[i].dst_key, false, &idx);
         if (rc) return rc;
         src[i] = p->slabs[idx].plh;
-        dst[i] = e->d_cherry_tab + (size_t)e->plan_cherry_jobs[i] * per;
+        dst[i] = e->d_cherry_tab + (size_t)e->plan.cherry_jobs[i] * per;
     }
     HIPCHK(launch_cherry_transpose(e, src.data(), dst.data(), n, e->cherry_npairs));
-    for (int i = 0; i < n; i++) e->cherry_slots[e->plan_cherry_jobs[i]].model_version = e->model_version;
+    for (int i = 0; i < n; i++) e->cherry_slots[e->plan.cherry_jobs[i]].model_version = e->model_version;
     e->cherry_built_total += n;
-    e->plan_cherry_jobs.clear();
+    e->plan.cherry_jobs.clear();
     return IQHIP_OK;
 }
 
@@ -1513,49 +782,40 @@ static int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
     rc = ensure_slab_rows(e, 2 + nops);
     if (rc) return rc;
     const int nwaves = (int)e->ntiles * e->lane_split;  // columns of the wave-partial slab
-    if (e->plan_nleaf_tabs > 0) {
+    if (e->plan.nleaf_tabs > 0) {
         // tables whose branch length changed since they were built -- all of the plan's after a model change
         // (a cached plan skipped build_plan, which is where a model change is normally noticed)
-        int njobs = e->plan_tab_dirty;
-        if (e->tab_model_version != e->model_version) {
-            std::fill(e->tab_len.begin(), e->tab_len.end(), NAN);
-            for (const TabJob &j : e->plan_tab_jobs) {
-                const size_t slot = (size_t)(j.tab - e->d_leaf_tab) / leaf_table_doubles(e);
-                if (slot < (size_t)e->ntaxa) e->tab_len[slot] = j.len;
-            }
-            e->tab_model_version = e->model_version;
-            njobs = e->plan_nleaf_tabs;
-        }
+        const int njobs = leaf_tables_follow_model(e) ? e->plan.nleaf_tabs : e->plan.tab_dirty;
         if (njobs > 0)
-            HIPCHK(launch_leaf_tables(e, reinterpret_cast<const TabJob *>(e->d_ops + e->plan_jobs_off), njobs));
-        e->plan_tab_dirty = 0;  // built; the same (cached) plan needs nothing until a length or the model changes
+            HIPCHK(launch_leaf_tables(e, reinterpret_cast<const TabJob *>(e->d_ops + e->plan.jobs_off), njobs));
+        e->plan.tab_dirty = 0;  // built; the same (cached) plan needs nothing until a length or the model changes
     }
-    if (!e->plan_cherry_jobs.empty()) {
+    if (!e->plan.cherry_jobs.empty()) {
         rc = build_cherry_tables(e);
         if (rc) return rc;
     }
-    if (e->plan_uses_cherry)
+    if (e->plan.uses_cherry)
         for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops[k].cherry != nullptr;
     timing_begin(e);
-    const int *table = reinterpret_cast<const int *>(e->d_ops + e->plan_table_off);
+    const int *table = reinterpret_cast<const int *>(e->d_ops + e->plan.table_off);
     {   // the stages of independent subtrees, level by level: one launch each, one set of workgroups per unit
         int off = 2;
-        for (int n : e->plan_stage_units) {
+        for (int n : e->plan.stage_units) {
             if (e->mfma) HIPCHK(launch_traverse_mfma(e, table + off, n, nwaves));
-            else HIPCHK(launch_traverse4(e, table + off, n, e->plan_units_have_load, nullptr, nwaves));
+            else HIPCHK(launch_traverse4(e, table + off, n, e->plan.units_have_load, nullptr, nwaves));
             off += 2 * n;
         }
     }
-    const bool empty_top = e->plan_nunits > 0 && !has_root && e->plan_top_nops == 0;  // explicit segments only
+    const bool empty_top = e->plan.nunits > 0 && !has_root && e->plan.top_nops == 0;  // explicit segments only
     // the submission's last kernel sums the wave partials itself (FoldArgs) where it can: the 4-state traversal
     // (its top-stage launch) and the matrix-core path's root-branch kernel; otherwise a k_reduce launch follows
     const bool fold4 = e->fold_reduce && !e->mfma && !empty_top && !skip_reduce && e->wg_size == 256;
     const bool foldm = e->fold_reduce && e->mfma && has_root && e->n_unobs == 0;
     if (empty_top) {
     } else if (e->mfma) HIPCHK(launch_traverse_mfma(e, table, nops > 0 ? 1 : 0, nwaves, /*top_stage=*/true));
-    else HIPCHK(launch_traverse4(e, table, 1, e->plan_has_load, has_root ? &br : nullptr, nwaves, fold4 ? nops : -1));
+    else HIPCHK(launch_traverse4(e, table, 1, e->plan.has_load, has_root ? &br : nullptr, nwaves, fold4 ? nops : -1));
     timing_end(e);
-    if (e->timing) e->tev_launches += (int)e->plan_stage_units.size() + (empty_top ? 0 : 1);
+    if (e->timing) e->tev_launches += (int)e->plan.stage_units.size() + (empty_top ? 0 : 1);
     if (e->mfma && has_root) HIPCHK(launch_stream_mfma(e, 0, &br, br.len, nwaves, nullptr, foldm ? nops : -1));
     if (fold4 || foldm) {
     } else if (has_root) HIPCHK(launch_reduce(e, 0, 2 + nops, nwaves));
@@ -2059,14 +1319,11 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     const size_t bytes_ops = sizeof(SweepOp) * total_ops, bytes_steps = sizeof(SweepStep) * (size_t)nsteps;
     const size_t need = bytes_ops + bytes_steps;
     if (need > e->sweep_desc_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
-        if (e->d_sweep_desc) hipFree(e->d_sweep_desc);
-        e->h_sweep_desc = e->d_sweep_desc = nullptr;
-        e->sweep_desc_cap = 0;
         const size_t cap = need * 2 + 4096;
+        HIPCHK(regrow(e, &e->d_sweep_desc, &e->sweep_desc_cap, 0, cap));   // (sweep_desc_cap: once the host copy has grown too)
+        if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
+        e->h_sweep_desc = nullptr;
         HIPCHK(hipHostMalloc((void **)&e->h_sweep_desc, cap));
-        HIPCHK(hipMalloc((void **)&e->d_sweep_desc, cap));
         e->sweep_desc_cap = cap;
     }
     SweepOp *hops = reinterpret_cast<SweepOp *>(e->h_sweep_desc);
@@ -2108,23 +1365,10 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
         if (rc) return rc;
     }
     const int grid = sweep4_grid(e), nwaves = grid * sweep4_waves(e);
-    if ((int64_t)total_ops * nwaves > e->slab_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_slab) hipFree(e->d_slab);
-        e->d_slab = nullptr;
-        e->slab_cap = 0;
-        HIPCHK(dmalloc(&e->d_slab, total_ops * (size_t)nwaves + 1024));
-        e->slab_cap = (int64_t)(total_ops * (size_t)nwaves + 1024);
-    }
+    const size_t slab_need = total_ops * (size_t)nwaves + 1024;
+    if ((int64_t)total_ops * nwaves > e->slab_cap) HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, slab_need, slab_need));
     const size_t posts_need = (size_t)2 * kNewtonPostEpochs * grid * 2;
-    if (posts_need > e->sweep_posts_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_sweep_posts) hipFree(e->d_sweep_posts);
-        e->d_sweep_posts = nullptr;
-        e->sweep_posts_cap = 0;
-        HIPCHK(dmalloc(&e->d_sweep_posts, posts_need));
-        e->sweep_posts_cap = posts_need;
-    }
+    if (posts_need > e->sweep_posts_cap) HIPCHK(regrow(e, &e->d_sweep_posts, &e->sweep_posts_cap, posts_need, posts_need));
     HIPCHK(hipMemcpyAsync(e->d_sweep_desc, e->h_sweep_desc, need, hipMemcpyHostToDevice, e->stream));
     if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts, 0xFF, posts_need * sizeof(double), e->stream));
     double *out = e->d_result + total_ops;      // (rows [0, total_ops) receive the sum_scale sums from k_reduce)
@@ -2138,7 +1382,7 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     e->theta_valid = true;
     e->theta_a_sc = last.a_sc;
     e->theta_b_sc = last.b_sc;
-    e->last_plan_version = 0;
+    e->plan_cache.version = 0;
     if (dbg) clock_gettime(CLOCK_MONOTONIC, &t1);
     int rc = read_result(e, (int)(total_ops + 6 * (size_t)nsteps));
     if (rc) return rc;
@@ -2204,14 +1448,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         ~ArenaScope() { e->plan_arena_on = false; }
     } arena_scope(e);
     e->path_counts[IQHIP_PATH_SWEEP_PER_STEP]++;
-    if (nsteps > e->sweep_len_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_sweep_len) hipFree(e->d_sweep_len);
-        e->d_sweep_len = nullptr;
-        e->sweep_len_cap = 0;
-        HIPCHK(dmalloc(&e->d_sweep_len, (size_t)nsteps + 64));
-        e->sweep_len_cap = nsteps + 64;
-    }
+    if (nsteps > e->sweep_len_cap) HIPCHK(regrow(e, &e->d_sweep_len, &e->sweep_len_cap, nsteps + 64, (size_t)nsteps + 64));
     static const bool dbg = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
     double t_trav = 0.0, t_newt = 0.0;
     int n_uploaded = 0;
@@ -2238,7 +1475,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
             if (dbg) clock_gettime(CLOCK_MONOTONIC, &ta);
             rc = submit_traverse(e, st.ops, st.nops, false, none, none, 0.0, /*skip_reduce=*/true, nullptr, lp);
             if (rc) return rc;
-            if (dbg) { clock_gettime(CLOCK_MONOTONIC, &tb); t_trav += (tb.tv_sec - ta.tv_sec) * 1e6 + (tb.tv_nsec - ta.tv_nsec) * 1e-3; n_uploaded += e->plan_small ? 0 : 1; }
+            if (dbg) { clock_gettime(CLOCK_MONOTONIC, &tb); t_trav += (tb.tv_sec - ta.tv_sec) * 1e6 + (tb.tv_nsec - ta.tv_nsec) * 1e-3; n_uploaded += e->plan.small ? 0 : 1; }
         }
         DevBranch br;
         rc = build_branch(e, st.a, st.b, 0.0, -1, &br);
@@ -2315,22 +1552,9 @@ int eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, co
     rc = ensure_slab_rows(e, std::max(5, 2 * m));
     if (rc) return rc;
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)m * theta_stride > e->theta_batch_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_theta_batch) hipFree(e->d_theta_batch);
-        e->d_theta_batch = nullptr;
-        e->theta_batch_cap = 0;
-        HIPCHK(dmalloc(&e->d_theta_batch, (size_t)m * theta_stride));
-        e->theta_batch_cap = (size_t)m * theta_stride;
-    }
-    if (m > e->bstates_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_bstates) hipFree(e->d_bstates);
-        e->d_bstates = nullptr;
-        e->bstates_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->d_bstates, sizeof(NewtonState) * (size_t)m));
-        e->bstates_cap = m;
-    }
+    if ((size_t)m * theta_stride > e->theta_batch_cap)
+        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)m * theta_stride, (size_t)m * theta_stride));
+    if (m > e->bstates_cap) HIPCHK(regrow(e, &e->d_bstates, &e->bstates_cap, m, m));
     for (int t = 0; t < m; t++) {
         DevBranch br;
         rc = build_branch(e, tasks[t].a, tasks[t].b, 0.0, -1, &br);
@@ -2567,14 +1791,8 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
     if (const char *bc = getenv("IQHIP_BATCH_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(bc)));
     const int G = std::max(1, std::min(wgs_needed, capacity / chunk));
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)chunk * theta_stride > e->theta_batch_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_theta_batch) hipFree(e->d_theta_batch);
-        e->d_theta_batch = nullptr;
-        e->theta_batch_cap = 0;
-        HIPCHK(dmalloc(&e->d_theta_batch, (size_t)chunk * theta_stride));
-        e->theta_batch_cap = (size_t)chunk * theta_stride;
-    }
+    if ((size_t)chunk * theta_stride > e->theta_batch_cap)
+        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)chunk * theta_stride, (size_t)chunk * theta_stride));
     if (chunk > e->batch_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
         void *old[] = {e->d_batch_partials, e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks};
@@ -2615,13 +1833,8 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
             post_epochs = max_steps + 4;   // derivative evaluations + the lnL pass(es)
             const size_t need = (size_t)m * post_epochs * G * 2;
             if (need > e->batch_posts_cap) {
-                HIPCHK(hipStreamSynchronize(e->stream));
-                if (e->d_batch_posts) hipFree(e->d_batch_posts);
-                e->d_batch_posts = nullptr;
-                e->batch_posts_cap = 0;
-                HIPCHK(dmalloc(&e->d_batch_posts, 2 * need));
+                HIPCHK(regrow(e, &e->d_batch_posts, &e->batch_posts_cap, need, 2 * need));   // (two launch parities)
                 HIPCHK(hipMemsetAsync(e->d_batch_posts, 0xFF, 2 * need * sizeof(double), e->stream));
-                e->batch_posts_cap = need;
                 e->batch_posts_used[0] = e->batch_posts_used[1] = 0;
             }
             const unsigned int pp = e->batch_post_launches & 1u;
@@ -3098,9 +2311,9 @@ extern "C" int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int n
     int last_dst = -1;
     const int rc = build_plan(e, ops, nops, &last_dst, nullptr);
     if (!rc) {   // (what submit_traverse would count: iqhip_debug_cherry_tables)
-        e->cherry_built_total += (int64_t)e->plan_cherry_jobs.size();
-        for (int slot : e->plan_cherry_jobs) e->cherry_slots[slot].model_version = e->model_version;   // ("built")
-        e->plan_cherry_jobs.clear();
+        e->cherry_built_total += (int64_t)e->plan.cherry_jobs.size();
+        for (int slot : e->plan.cherry_jobs) e->cherry_slots[slot].model_version = e->model_version;   // ("built")
+        e->plan.cherry_jobs.clear();
         for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops[k].cherry != nullptr;
     }
     return rc;

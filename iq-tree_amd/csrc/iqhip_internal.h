@@ -150,6 +150,42 @@ struct __attribute__((aligned(16))) TabJob {  // one K2 table to build: tab[c][s
     double _pad;
 };
 
+// What build_plan (plan.hip) leaves for the launchers besides the descriptors: one submission's plan.  Every field is
+// reset when a plan is built; submit_traverse clears tab_dirty once the tables are built and empties cherry_jobs.
+struct Plan {
+    int lds_doubles = 0;            // LDS region size (doubles) of the largest chunk
+    int state_slots = 1;            // leaf-state LDS slots of the largest chunk (4-state path)
+    bool has_load = false;          // some op of the top stage has two memory children (slow kernel instantiation)
+    bool units_have_load = false;   // ... some op of a unit
+    // a plan of at most kSmallPlanOps - 2 ops with no units travels in the kernel arguments instead of d_ops (the copy
+    // and the dependent-launch gap behind it cost ~9 us per changed plan, i.e. per branch of a sweep; IQHIP_SMALL_PLANS)
+    bool small = false;
+    int small_nops = 0;
+    // Staged plans: independent subtrees ("units") run as their own workgroups in first launches, the ops above them
+    // ("top") in a last one.  Segment table after the sentinel descriptors: {top_begin, top_nops, unit1_begin, unit1_nops, ...}
+    int nunits = 0, top_nops = 0;
+    std::vector<int> stage_units;   // units per stage, in launch order
+    int table_off = 0, jobs_off = 0;  // DevOp index where the segment table / the K2 table job list starts
+    int nhold = 0;                  // ops whose left child is parked (CHILD_HOLD)
+    int nleaf_tabs = 0;             // K2 tables the plan uses (0: kernel variant without tables)
+    std::vector<TabJob> tab_jobs;   // the plan's tables: [0, tab_dirty) need (re)building
+    int tab_dirty = 0;
+    std::vector<int> cherry_jobs;   // cherry-table slots the plan needs (re)built before its traversal
+    bool uses_cherry = false;
+    uint64_t cherry_model = 0;      // model version the plan's cherry tables were scheduled for
+};
+
+// What the descriptors in d_ops were built from: an identical op list (same keys, leaves, lengths) with an unchanged key
+// map needs no rebuilding at all
+struct PlanCache {
+    std::vector<char> ops_in;     // the caller's op list
+    std::vector<int> segs;        // explicit segment sizes
+    uint64_t version = 0;         // keymap_version the plan was built at (0: never re-used)
+    int dst = -1;                 // slab the plan's last op writes
+    std::vector<char> uploaded;   // bytes of the descriptors currently in d_ops
+    void invalidate() { version = 0; uploaded.clear(); }
+};
+
 // Optimization::minimizeNewton (optimization.cpp:388-465) as a state machine that is advanced once per derivative
 // evaluation: `newton_init`, then after every evaluation at `rts` one `newton_update(sum f*df_ptn, sum f*ddf_ptn)`
 // until `done`.  The same function runs in a 1-thread kernel (sharded engines: derivative kernel -> all-reduce of
@@ -217,8 +253,8 @@ __host__ __device__ inline void newton_update(NewtonState &s, double pdf, double
 struct iqhip_engine {
     int device = 0;
     // planning-only engine (iqhip_debug_create_planner): no HIP call is ever made for it; "device" allocations are
-    // distinct fake addresses that are never dereferenced.  It exists so that build_plan and the plan check below run
-    // in CPU tests (tests/test_plan_check.py): the descriptors a kernel would receive are validated without a GPU.
+    // distinct fake addresses that are never dereferenced.  It exists so that the planner (plan.hip build_plan, check_plan)
+    // runs in CPU tests (tests/test_plan_check.py): the descriptors a kernel would receive are validated without a GPU.
     bool planner = false;
     uint64_t fake_next = 0x100000000000ull;
     bool check_plans = false;  // IQHIP_CHECK_PLAN=1 (always on for a planner): validate every DevOp before upload
@@ -253,29 +289,16 @@ struct iqhip_engine {
     // 20-state pipelined kernel: the same idea with the parking place in LDS (10 KB per wave) -- a result that is the
     // streamed child of a later op of the same unit is kept there instead of being read back from memory (IQHIP_HOLD_LDS)
     bool hold_lds = true;
-    int plan_nhold = 0;      // ops of the current plan whose left child is parked (diagnostics)
     int ablate = 0;        // IQHIP_ABLATE: timing-only host-side switches (results wrong when set)
     int lds_budget_bytes = 64 * 1024;  // per-workgroup LDS for the per-branch regions (IQHIP_LDS_KB)
-    int plan_lds_doubles = 0;
-    int plan_state_slots = 1;    // leaf-state LDS slots of the largest chunk (4-state path)
-    bool plan_has_load = false;  // some op has two memory children (slow kernel instantiation)
-    // 4-state kernel: a plan of at most kSmallPlanOps - 2 ops with no units travels in the kernel arguments instead of
-    // being copied to d_ops first (the copy kernel and the dependent-launch gap behind it cost ~9 us per changed plan,
-    // i.e. per branch of a branch-length sweep); IQHIP_SMALL_PLANS=0 switches it off
-    bool plan_small = false;
-    int plan_small_nops = 0;
-    bool small_plans = true;
-    // Staged plans (engine.hip, build_plan): independent subtrees ("units") run as their own workgroups in a
-    // first launch, the ops above them ("top") in a second one.  Segment table on the device, after the
-    // sentinel descriptors: {top_begin, top_nops, unit1_begin, unit1_nops, ...}
-    int plan_nunits = 0;
-    std::vector<int> plan_stage_units;  // units per stage, in launch order
-    int plan_top_nops = 0;
-    std::vector<int> last_segs;   // explicit segment sizes the cached descriptors were built with
-    int plan_table_off = 0;      // DevOp index where the table starts
-    bool plan_units_have_load = false;
-    int split_target = -1;       // IQHIP_SPLIT: -1 auto, 0 never, n > 0: unit size
-    iqhip::Slab dummy;           // valid target of unconditional prefetches  // LDS region size (doubles) of the largest chunk of the current plan
+    bool small_plans = true;     // IQHIP_SMALL_PLANS (iqhip::Plan::small)
+    int split_target = -1;       // IQHIP_SPLIT: -1 auto, 0 never, n > 0: unit size (plan.hip cut_units)
+    int max_levels = 3;          // IQHIP_LEVELS: stages of units at most
+    int mfma_lds_kb = -1;        // IQHIP_MFMA_LDS_KB: LDS per matrix-core workgroup (-1: by state count, plan.hip lds_budget)
+    bool debug_plan = false;     // IQHIP_DEBUG_PLAN: print each plan's staging and parking to stderr
+    std::string debug_break_plan;  // IQHIP_DEBUG_BREAK_PLAN (planning-only engines): break one descriptor on purpose
+    iqhip::Plan plan;            // the current plan (plan.hip build_plan)
+    iqhip::Slab dummy;           // valid target of unconditional prefetches
     int block = 0;         // n*ncat
     int state_unknown = -1;
     bool model_set = false, aln_set = false, theta_valid = false;
@@ -324,7 +347,6 @@ struct iqhip_engine {
     size_t leaf_tab_slots = 0;            // capacity in tables
     std::vector<double> tab_len;          // per slot: branch length the table was built for (NaN: none)
     uint64_t model_version = 1, tab_model_version = 0;
-    std::vector<iqhip::TabJob> plan_tab_jobs;  // the current plan's tables: [0, plan_tab_dirty) need (re)building
     // cherry tables (20 states x 4 categories, DevOp::cherry): slot = pair of taxa; `pair` is a small engine of our own on
     // the same stream whose pseudo-alignment lists every pair of states -- a cherry's table is that engine's ordinary
     // node update for the two pendant lengths, moved into register order by k_cherry_transpose
@@ -340,9 +362,7 @@ struct iqhip_engine {
     size_t cherry_cap = 0;                 // slots allocated
     std::unordered_map<uint64_t, int> cherry_slot_of;   // (taxon_l << 32 | taxon_r) -> slot
     std::vector<CherrySlot> cherry_slots;
-    std::vector<int> plan_cherry_jobs;     // slots the current plan needs (re)built before its traversal
-    uint64_t cherry_stamp = 0, plan_cherry_model = 0;   // (model version the current plan's tables were scheduled for)
-    bool plan_uses_cherry = false;
+    uint64_t cherry_stamp = 0;
     int64_t cherry_built_total = 0, cherry_ops_total = 0;   // tables built / node updates answered from a table so far
     // Newton / sweep forms, read when the engine is created: IQHIP_NEWTON=chain (enqueued chain instead of the one-launch
     // k_newton), IQHIP_SWEEP=0 (sweeps step by step with a host round trip each), IQHIP_SWEEP_KERNEL=0 (4-state sweeps as
@@ -351,9 +371,6 @@ struct iqhip_engine {
     // since creation, the IQHIP_PATH_* slots of include/iqhip.h (iqhip_debug_path_counts)
     int64_t path_counts[IQHIP_PATH_NSLOTS] = {};
     bool cherry_model_synced = false;      // the pair engine has the model of this engine's last set_model call
-    int plan_tab_dirty = 0;
-    int plan_jobs_off = 0;                // DevOp index where the device copy of the job list starts
-    int plan_nleaf_tabs = 0;              // tables the current plan uses (0: kernel variant without tables)
     bool leaf_tables = false;       // IQHIP_LEAF_TABLES (default on for the pipelined matrix-core kernels)
     // Mixture models (phylokernelmixture.h, phylokernelmixrate.h): the ncat categories are (class, rate)
     // components; category c uses eigen-system cat_class[c].  Per-category expansions for the kernels
@@ -407,9 +424,6 @@ struct iqhip_engine {
     int sweep_len_cap = 0;
     // ... persistent form (4 states): descriptors of all steps (pinned staging + device copy) and the exchange slots
     char *h_sweep_desc = nullptr, *d_sweep_desc = nullptr;
-    char *h_plan_arena = nullptr;     // pinned slices for the plan uploads of a per-step sweep (build_plan)
-    size_t plan_arena_cap = 0, plan_arena_used = 0;
-    bool plan_arena_on = false;
     size_t sweep_desc_cap = 0;
     double *d_sweep_posts = nullptr;
     size_t sweep_posts_cap = 0;
@@ -432,12 +446,11 @@ struct iqhip_engine {
     // pinned host staging
     iqhip::DevOp *h_ops = nullptr;
     double *h_result = nullptr;
-    std::vector<char> uploaded_plan;  // bytes of the descriptors currently in d_ops
-    // the caller's op list the current descriptors were built from: an identical list (same keys,
-    // leaves, lengths) with an unchanged key map needs no rebuilding at all
-    std::vector<char> last_ops_in;
-    uint64_t keymap_version = 1, last_plan_version = 0;
-    int last_plan_dst = -1;
+    iqhip::PlanCache plan_cache;
+    char *h_plan_arena = nullptr;     // pinned slices for the plan uploads of a per-step sweep (plan.hip upload_plan)
+    size_t plan_arena_cap = 0, plan_arena_used = 0;
+    bool plan_arena_on = false;
+    uint64_t keymap_version = 1;      // bumped whenever a key is created, released or moved
     hipEvent_t staging_free = nullptr;
     bool staging_busy = false;
 
@@ -602,6 +615,56 @@ __device__ inline void fold_tail(const FoldArgs &F) {
 
 // engine.hip: records the calling thread's error text (iqhip_last_error) and returns `code`
 int set_error(int code, const std::string &msg);
+// in a function that returns an IQHIP status: a failed HIP call returns IQHIP_ERR_HIP with the call's text
+#define HIPCHK(call)                                                                                           \
+    do {                                                                                                       \
+        hipError_t _s = (call);                                                                                \
+        if (_s != hipSuccess)                                                                                  \
+            return iqhip::set_error(IQHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s));        \
+    } while (0)
+
+template <typename T>
+hipError_t dmalloc(T **p, size_t count) { return hipMalloc((void **)p, count * sizeof(T)); }
+// planning-only engines: a distinct, 256-byte aligned address range that is never dereferenced
+template <typename T>
+T *fake_alloc(iqhip_engine *e, size_t count) {
+    const uint64_t a = e->fake_next;
+    e->fake_next += (count * sizeof(T) + 255) / 256 * 256 + 256;
+    return reinterpret_cast<T *>(a);
+}
+// Replaces a device buffer by one of `count` elements once the engine's stream has drained (the contents are dropped);
+// *cap = new_cap when that succeeded, 0 while it has not.  A planning-only engine gets a fake address.
+template <typename T, typename C>
+hipError_t regrow(iqhip_engine *e, T **buf, C *cap, size_t new_cap, size_t count) {
+    if (e->planner) {
+        *buf = fake_alloc<T>(e, count);
+    } else {
+        hipError_t s = hipStreamSynchronize(e->stream);
+        if (s != hipSuccess) return s;
+        if (*buf) hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+        if ((s = dmalloc(buf, count)) != hipSuccess) return s;
+    }
+    *cap = (C)new_cap;
+    return hipSuccess;
+}
+int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);   // engine.hip (create: a new key gets a slab)
+bool cherry_candidate(const iqhip_engine *e);   // engine.hip: the engine uses cherry tables (DevOp::cherry)
+
+// plan.hip -- the planner.  build_plan: one submission's descriptors into h_ops and d_ops, e->plan; *last_dst = the slab
+// the last op writes.  explicit_segs: op counts of independent groups (each on its own workgroups); len_ptrs (sweeps):
+// 2 * nops device pointers, [2k] / [2k+1] = where op k's left / right child length is found when it runs (nullptr: host)
+int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_dst,
+               const std::vector<int> *explicit_segs = nullptr, const double *const *len_ptrs = nullptr);
+// the descriptor of a root branch; prev_dst: slab written by the op just before it (-1: none)
+int build_branch(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, int prev_dst, DevBranch *br);
+// one child of a node op: a leaf's state row or a slab (CHILD_PREV when it is prev_dst)
+int resolve_child(iqhip_engine *e, uint64_t key, int32_t leaf, int prev_dst, const double **plh, const int16_t **sc,
+                  const uint8_t **states, int32_t *kind);
+// After a model change every K2 table is stale: forget what the slots were built for, except the current plan's tables,
+// which are then all (re)built.  Returns whether the model changed.
+bool leaf_tables_follow_model(iqhip_engine *e);
 
 // comm.hip -- RCCL, loaded lazily.  comm_allreduce: in-place SUM/f64 all-reduce of the first n doubles of the
 // engine's device result vector on its stream (no-op without a communicator).  comm_group_allreduce: the same for

@@ -184,7 +184,7 @@ struct TravMArgs {
     int state_unknown;
     int *fold_flags;        // per result row: raised by a wave that rescaled patterns at that node (FoldArgs::flags)
     int hold_off;           // 20-state pipelined kernel: offset (doubles) of the waves' parking places in LDS, -1: none
-    // a small plan inside the kernel arguments (iqhip_engine::plan_small; read by trav_mfma2_body only)
+    // a small plan inside the kernel arguments (iqhip_engine::plan.small; read by trav_mfma2_body only)
     int small_plan;
     int small_segs[2];
     DevOp small_ops[kSmallPlanOps];
@@ -1073,17 +1073,17 @@ __global__ __launch_bounds__(256, 3) void k_traverse_mfma_top20(const TravMArgs 
 
 static hipError_t launch_trav_top20(iqhip_engine *e, TravMArgs &A, int nfull_wg) {
     const int nx = e->state_unknown + 1 - 20;
-    const size_t lds = (size_t)(mfma2_fixed_lds_doubles(20) + nx * 20 + e->plan_lds_doubles) * sizeof(double);
+    const size_t lds = (size_t)(mfma2_fixed_lds_doubles(20) + nx * 20 + e->plan.lds_doubles) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_top20), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         attr_set = true;
     }
     A.hold_off = -1;
-    if (e->plan_small && A.nsegs_launch == 1) {
+    if (e->plan.small && A.nsegs_launch == 1) {
         A.small_plan = 1;
         A.small_segs[0] = 0;
-        A.small_segs[1] = e->plan_small_nops;
+        A.small_segs[1] = e->plan.small_nops;
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
     }
     TravMArgs F = A, R = A;
@@ -1100,7 +1100,7 @@ template <int N, bool MIX>
 static hipError_t launch_trav_m(iqhip_engine *e, TravMArgs &A) {
     constexpr int MT = (N + 15) / 16, KS = N / 4, WG = 256;
     const int nx = e->state_unknown + 1 - N;
-    const size_t lds = (size_t)(2 * MT * KS * 64 + nx * N + e->plan_lds_doubles) * sizeof(double);
+    const size_t lds = (size_t)(2 * MT * KS * 64 + nx * N + e->plan.lds_doubles) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma<N, WG, MIX>),
@@ -1273,7 +1273,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse_mfma_mix20(const TravMArgs A
 template <int CS>
 static hipError_t launch_trav_mix20_cs(iqhip_engine *e, TravMArgs &A) {
     constexpr int WG = 256;
-    const size_t lds = (size_t)e->plan_lds_doubles * sizeof(double);
+    const size_t lds = (size_t)e->plan.lds_doubles * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_mix20<WG, CS>),
@@ -1491,7 +1491,7 @@ template <bool TAB>
 static hipError_t launch_trav_rows64(iqhip_engine *e, TravMArgs &A) {
     constexpr int WG = 256;
     const int nx = e->state_unknown + 1 - 64;
-    const size_t lds = (size_t)((64 + nx) * 64 + 4 * 16 * 64 + e->plan_lds_doubles) * sizeof(double);
+    const size_t lds = (size_t)((64 + nx) * 64 + 4 * 16 * 64 + e->plan.lds_doubles) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_rows64<WG, TAB>),
@@ -1515,9 +1515,9 @@ template <int N, int C, int CS = 1, bool TAB = false>
 static hipError_t launch_trav_m2(iqhip_engine *e, TravMArgs &A) {
     constexpr int KS = N / 4, WG = 256;
     const int nx = e->state_unknown + 1 - N;
-    size_t lds = (size_t)(mfma2_fixed_lds_doubles(N) + nx * N + e->plan_lds_doubles) * sizeof(double);
+    size_t lds = (size_t)(mfma2_fixed_lds_doubles(N) + nx * N + e->plan.lds_doubles) * sizeof(double);
     A.hold_off = -1;
-    if (N < 64 && CS == 1 && e->plan_nhold > 0) {   // parking places: one tile vector (16 patterns x block) per tile
+    if (N < 64 && CS == 1 && e->plan.nhold > 0) {   // parking places: one tile vector (16 patterns x block) per tile
         A.hold_off = (int)(lds / sizeof(double));
         lds += (size_t)(WG / 64 / CS) * 16 * e->block * sizeof(double);
     }
@@ -1529,10 +1529,10 @@ static hipError_t launch_trav_m2(iqhip_engine *e, TravMArgs &A) {
     }
     A.ngroups = (int)((A.ntiles * CS + 3) / 4);
     const int grid = A.ngroups * A.nsegs_launch;
-    if (e->plan_small && A.nsegs_launch == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
+    if (e->plan.small && A.nsegs_launch == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
         A.small_plan = 1;
         A.small_segs[0] = 0;
-        A.small_segs[1] = e->plan_small_nops;
+        A.small_segs[1] = e->plan.small_nops;
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
     }
     (void)hipGetLastError();
@@ -1546,7 +1546,7 @@ template <bool TAB>
 static hipError_t launch_trav_top64(iqhip_engine *e, TravMArgs &A, int nfull) {
     const int nx = e->state_unknown + 1 - 64;
     const size_t fixed = std::max<size_t>((size_t)mfma2_fixed_lds_doubles(64) + (size_t)nx * 64, (size_t)(64 + nx) * 64 + 4 * 16 * 64);
-    const size_t lds = (fixed + e->plan_lds_doubles) * sizeof(double);
+    const size_t lds = (fixed + e->plan.lds_doubles) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_top64<TAB>),
@@ -1646,11 +1646,11 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
         const int64_t rounds = e->ntiles / per_round, rest = e->ntiles - rounds * per_round;
         if (rounds >= 1 && rest > 0 && rest <= per_round / 2) {
             const int nfull = (int)(rounds * e->num_cus);
-            return (e->plan_nleaf_tabs > 0 || e->leaf_tables) ? launch_trav_top64<true>(e, A, nfull) : launch_trav_top64<false>(e, A, nfull);
+            return (e->plan.nleaf_tabs > 0 || e->leaf_tables) ? launch_trav_top64<true>(e, A, nfull) : launch_trav_top64<false>(e, A, nfull);
         }
     }
     if (e->mfma_pipelined) {  // plan was built in canonical (PF, PREV) form
-        if (e->plan_nleaf_tabs > 0 || e->leaf_tables) {  // leaf children from the K2 tables (k_leaf_tables)
+        if (e->plan.nleaf_tabs > 0 || e->leaf_tables) {  // leaf children from the K2 tables (k_leaf_tables)
             if (e->n == 20 && e->ncat == 4)
                 return e->cat_split ? launch_trav_m2<20, 1, 4, true>(e, A) : launch_trav_m2<20, 4, 1, true>(e, A);
             if (e->n == 20 && e->ncat == 1) return launch_trav_m2<20, 1, 1, true>(e, A);

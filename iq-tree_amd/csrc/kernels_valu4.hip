@@ -97,7 +97,7 @@ struct Trav4Args {
     int has_load;
     FoldArgs fold;
     DevBranch root;
-    // a small plan inside the kernel arguments (iqhip_engine::plan_small): ops + look-ahead sentinels, one segment
+    // a small plan inside the kernel arguments (iqhip_engine::plan.small): ops + look-ahead sentinels, one segment
     int small_plan;
     int small_segs[2];
     DevOp small_ops[kSmallPlanOps];
@@ -583,8 +583,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
 template <int C, int WG, bool HAS_LOAD, int SP, bool USE_HOLD>
 static hipError_t launch_trav_h(iqhip_engine *e, Trav4Args &A) {
     constexpr int B = 4 * C;
-    const size_t lds = (size_t)(128 + B + (size_t)e->plan_lds_doubles) * sizeof(double) +
-                       (size_t)e->plan_state_slots * WG;
+    const size_t lds = (size_t)(128 + B + (size_t)e->plan.lds_doubles) * sizeof(double) +
+                       (size_t)e->plan.state_slots * WG;
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>),
@@ -677,13 +677,13 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     A.nwaves = nwaves;
     A.state_unknown = e->state_unknown;
     A.has_root = root ? 1 : 0;
-    A.lds_reg_doubles = e->plan_lds_doubles;
+    A.lds_reg_doubles = e->plan.lds_doubles;
     if (root) A.root = *root; else A.root = DevBranch{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.0};
     A.small_plan = 0;
     A.small_segs[0] = A.small_segs[1] = 0;
-    if (e->plan_small && nsegs == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
+    if (e->plan.small && nsegs == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
         A.small_plan = 1;
-        A.small_segs[1] = e->plan_small_nops;
+        A.small_segs[1] = e->plan.small_nops;
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
     } else {
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = DevOp{};

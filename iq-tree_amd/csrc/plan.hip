@@ -1,0 +1,721 @@
+// plan.hip -- host side of libiqhip.so: the planner.  build_plan turns the op list of one submission into the DevOp
+// descriptors the traversal kernels walk (+ segment table and K2 job list) and iqhip_engine::plan, one pass per job.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <unordered_set>
+
+#include "iqhip_internal.h"
+
+using namespace iqhip;
+
+namespace {
+
+int fail(int code, const std::string &msg) { return set_error(code, msg); }
+constexpr int kSentinels = 2;  // descriptors behind the last op: >= the kernels' deepest look-ahead (streamed child: 1 op)
+
+// DevOps needed to hold `bytes` (the segment table and the job list ride in the descriptor buffer)
+int devops_for(size_t bytes) { return (int)((bytes + sizeof(DevOp) - 1) / sizeof(DevOp)); }
+
+// the staging of one op list (cut_units)
+struct Units {
+    std::vector<int> order;                  // order[p] = caller index of the op at position p
+    std::vector<int> seg_of;                 // position -> its unit (1, 2, ...); 0: the top stage
+    std::vector<std::pair<int, int>> units;  // {begin, nops} in the new order, stage after stage
+    std::vector<int> stage_units;            // units per stage (launch)
+    int top_begin = 0;                       // first position of the top stage
+};
+
+// the segment table behind the sentinels: {top_begin, top_nops, unit1_begin, unit1_nops, ...}
+int segment_table_ops(const Units &u) { return devops_for(sizeof(int) * 2 * (1 + u.units.size())); }
+
+// d_ops and its pinned staging copy h_ops (plain host memory for a planning-only engine) for `nops` DevOps
+int ensure_plan_capacity(iqhip_engine *e, int nops) {
+    if (nops <= e->ops_cap) return IQHIP_OK;
+    const int cap = std::max(64, nops * 2);
+    e->plan_cache.uploaded.clear();
+    HIPCHK(regrow(e, &e->d_ops, &e->ops_cap, 0, cap));   // (ops_cap: once h_ops has grown too)
+    if (e->planner) free(e->h_ops);
+    else if (e->h_ops) hipHostFree(e->h_ops);
+    e->h_ops = nullptr;
+    if (e->planner) e->h_ops = static_cast<DevOp *>(calloc((size_t)cap, sizeof(DevOp)));
+    else HIPCHK(hipHostMalloc((void **)&e->h_ops, sizeof(DevOp) * cap));
+    if (!e->h_ops) return fail(IQHIP_ERR_NOMEM, "plan staging");
+    e->ops_cap = cap;
+    return IQHIP_OK;
+}
+
+// every pointer a valid target, nothing used: the starting point of each descriptor, and the look-ahead sentinels
+void dummy_op(const iqhip_engine *e, DevOp &d) {
+    memset(&d, 0, sizeof(d));
+    d.dst = e->dummy.plh;
+    d.dst_sc = e->dummy.sc;
+    d.pf = d.ld = e->dummy.plh;
+    d.pf_sc = d.ld_sc = e->dummy.sc;
+    d.sl = d.sr = e->d_states;
+    d.tabL = d.tabR = e->d_leaf_tab;
+}
+
+// Same op list as last time and no key created / released / moved since: the descriptors on the device are still the
+// right ones (hot loop 1 re-evaluates one tree many times).
+bool plan_is_cached(const iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *explicit_segs,
+                    const double *const *len_ptrs) {
+    const PlanCache &c = e->plan_cache;
+    const size_t in_bytes = sizeof(iqhip_node_op) * (size_t)nops;
+    return !len_ptrs && nops > 0 && c.version == e->keymap_version && c.ops_in.size() == in_bytes &&
+           memcmp(c.ops_in.data(), ops, in_bytes) == 0 && !c.uploaded.empty() &&
+           (explicit_segs ? c.segs == *explicit_segs : c.segs.empty()) &&
+           (!e->plan.uses_cherry || e->plan.cherry_model == e->model_version);
+}
+
+// caller-defined independent segments (a batch of branch tasks): one set of workgroups each, no top stage
+int cut_explicit(const iqhip_node_op *ops, int nops, const std::vector<int> &segs, Units &u) {
+    std::unordered_set<uint64_t> dsts;
+    for (int k = 0; k < nops; k++)
+        if (!dsts.insert(ops[k].dst_key).second)
+            return fail(IQHIP_ERR_INVALID, "batched node updates must write distinct vectors");
+    int pos = 0;
+    for (const int n : segs) {
+        if (n <= 0) continue;
+        if (pos + n > nops) break;   // (refused below)
+        u.units.push_back({pos, n});
+        for (int q = 0; q < n; q++) u.seg_of[pos + q] = (int)u.units.size();
+        pos += n;
+    }
+    if (pos != nops) return fail(IQHIP_ERR_INVALID, "segment sizes do not add up to the op count");
+    u.stage_units.push_back((int)u.units.size());
+    u.top_begin = nops;
+    return IQHIP_OK;
+}
+
+// unit size of the automatic staging (0: none)
+int unit_target(const iqhip_engine *e, int nops) {
+    if (e->split_target >= 0) return e->split_target;
+    const int64_t simds = (int64_t)e->num_cus * 4;
+    // the matrix-core kernels (16-pattern tiles, long per-tile op lists) when there are fewer than 6 tile-waves per
+    // SIMD; unit size so that the first launch has ~4 waves per SIMD.  Measured at the BASELINE shapes: protein 1.28 ->
+    // 1.10 ms, codon 0.64 -> 0.49 ms; the 4-state kernel is store-bound and loses (0.161 -> 0.172..0.184 ms), so it
+    // stays unsplit.
+    int target = 0;
+    if (e->mfma && e->ntiles < 6 * simds && nops >= 12)
+        target = (int)std::min<int64_t>(nops / 2, std::max<int64_t>(3, ((int64_t)nops * e->ntiles + 4 * simds - 1) / (4 * simds)));
+    // 4-state kernel: only while the whole alignment is at most one wave per SIMD, where a traversal is a latency-bound
+    // chain (50 taxa GTR+G4: 5k patterns 0.082 -> 0.045 ms, 20k 0.086 -> 0.060 ms; 60k patterns 0.109 -> 0.126 ms, so
+    // not there)
+    if (!e->mfma && e->ntiles * e->lane_split <= simds && nops >= 12) target = std::max(6, nops / 4);
+    return target;
+}
+
+// lc[k] / rc[k]: the op whose result is op k's left / right child (-1: a leaf or an outside vector).  False when re-ordering
+// is unsafe: a vector is both an outside input and a destination (LM_PER_NODE buffer stealing), written or consumed twice.
+bool producer_links(const iqhip_node_op *ops, int nops, std::vector<int> &lc, std::vector<int> &rc) {
+    std::unordered_map<uint64_t, int> prod;
+    std::unordered_set<uint64_t> ext_in;
+    std::vector<char> consumed(nops, 0);
+    lc.assign(nops, -1);
+    rc.assign(nops, -1);
+    for (int k = 0; k < nops; k++) {
+        const iqhip_node_op &o = ops[k];
+        for (int side = 0; side < 2; side++) {
+            if ((side ? o.right_leaf : o.left_leaf) >= 0) continue;
+            const uint64_t key = side ? o.right_key : o.left_key;
+            auto it = prod.find(key);
+            if (it == prod.end()) { ext_in.insert(key); continue; }
+            if (consumed[it->second]++) return false;
+            (side ? rc : lc)[k] = it->second;
+        }
+        if (!prod.emplace(o.dst_key, k).second) return false;
+    }
+    for (int k = 0; k < nops; k++)
+        if (ext_in.count(ops[k].dst_key)) return false;
+    return true;
+}
+
+// Level by level: among the ops not yet placed, the maximal subtrees of 2..target ops (vectors of earlier levels count
+// as outside inputs) become the units of the next launch; what is left after the last level walks sequentially.  Every
+// level is a launch of tiles x units waves, so the sequential tail -- where an alignment with slightly more tiles than
+// SIMDs runs at half speed -- shrinks from "everything above the first cut" to a few ops.
+void cut_subtrees(int nops, int target, int max_levels, const std::vector<int> &lc, const std::vector<int> &rc, Units &u) {
+    std::vector<char> placed(nops, 0);
+    std::vector<int> new_order;
+    new_order.reserve(nops);
+    const int min_top = std::max(2, std::min(target, 6));
+    for (int level = 0; level < max_levels && nops - (int)new_order.size() > min_top; level++) {
+        std::vector<int> rem;  // unplaced ops in post-order
+        for (int k = 0; k < nops; k++)
+            if (!placed[k]) rem.push_back(k);
+        const int R = (int)rem.size();
+        std::vector<int> pos_of(nops, -1), l2(R, -1), r2(R, -1), sz(R, 1);
+        std::vector<char> cont(R, 1), cons(R, 0);
+        for (int q = 0; q < R; q++) pos_of[rem[q]] = q;
+        for (int q = 0; q < R; q++) {
+            const int k = rem[q];
+            if (lc[k] >= 0 && !placed[lc[k]]) { l2[q] = pos_of[lc[k]]; cons[l2[q]] = 1; sz[q] += sz[l2[q]]; }
+            if (rc[k] >= 0 && !placed[rc[k]]) { r2[q] = pos_of[rc[k]]; cons[r2[q]] = 1; sz[q] += sz[r2[q]]; }
+            // post-order contiguity within the unplaced sequence: the subtree of q is exactly [q - sz + 1, q]
+            const int a = std::max(l2[q], r2[q]), b2 = std::min(l2[q], r2[q]);
+            bool c2 = true;
+            if (a >= 0) c2 = (a == q - 1) && cont[a];
+            if (b2 >= 0) c2 = c2 && (b2 == a - sz[a]) && cont[b2];
+            cont[q] = c2;
+        }
+        std::vector<int> stack;
+        for (int q = R - 1; q >= 0; q--)
+            if (!cons[q]) stack.push_back(q);
+        std::vector<std::pair<int, int>> found;  // {root position, size}
+        while (!stack.empty()) {
+            const int q = stack.back();
+            stack.pop_back();
+            if (sz[q] <= target && sz[q] >= 2 && cont[q]) {
+                found.push_back({q, sz[q]});
+            } else {
+                if (l2[q] >= 0) stack.push_back(l2[q]);
+                if (r2[q] >= 0) stack.push_back(r2[q]);
+            }
+        }
+        if (found.size() < 2) break;
+        std::stable_sort(found.begin(), found.end(),
+                         [](const std::pair<int, int> &x, const std::pair<int, int> &y2) { return x.second > y2.second; });
+        for (const std::pair<int, int> &f : found) {
+            u.units.push_back({(int)new_order.size(), f.second});
+            for (int q = f.first - f.second + 1; q <= f.first; q++) {
+                u.seg_of[new_order.size()] = (int)u.units.size();
+                placed[rem[q]] = 1;
+                new_order.push_back(rem[q]);
+            }
+        }
+        u.stage_units.push_back((int)found.size());
+    }
+    if (u.units.empty()) return;
+    u.top_begin = (int)new_order.size();
+    for (int k = 0; k < nops; k++)
+        if (!placed[k]) { u.seg_of[new_order.size()] = 0; new_order.push_back(k); }
+    u.order = std::move(new_order);
+}
+
+// The staging.  A launch gives every 64/16-pattern tile one wave that walks the whole op list, so an alignment with few
+// tiles leaves SIMDs idle or unevenly loaded (a tile is an indivisible unit of nops updates).  Independent subtrees of
+// the plan are therefore cut out as "units" that run on their own workgroups in a first launch (tiles x units waves),
+// and only the ops above them ("top") walk sequentially in a second launch.  Writes nothing to the engine.
+int cut_units(const iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *explicit_segs, Units &u) {
+    u.order.resize(nops);
+    for (int k = 0; k < nops; k++) u.order[k] = k;
+    u.seg_of.assign(nops, 0);
+    if (explicit_segs) {
+        const int rc = cut_explicit(ops, nops, *explicit_segs, u);
+        if (rc) return rc;
+    } else {
+        const int target = unit_target(e, nops);
+        std::vector<int> lc, rc;
+        if (target > 0 && target < nops && nops >= 4 && producer_links(ops, nops, lc, rc))
+            cut_subtrees(nops, target, e->max_levels, lc, rc, u);
+    }
+    if (e->debug_plan) {
+        fprintf(stderr, "[iqhip] plan: %d ops, %zu stages of units (", nops, u.stage_units.size());
+        size_t ui = 0;
+        for (int n : u.stage_units) {
+            for (int q = 0; q < n; q++) fprintf(stderr, "%d ", u.units[ui++].second);
+            fprintf(stderr, "| ");
+        }
+        fprintf(stderr, ") top %d ops\n", nops - u.top_begin);
+    }
+    return IQHIP_OK;
+}
+
+// One DevOp per op, in the staged order: children resolved to slabs / state rows and put in the kernels' canonical
+// form.  *last_dst: the slab the last op writes (-1: none)
+int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const Units &u, const double *const *len_ptrs,
+                     int *last_dst) {
+    int prev_dst = -1;
+    for (int k = 0; k < nops; k++) {
+        const iqhip_node_op &o = ops[u.order[k]];
+        DevOp &d = e->h_ops[k];
+        dummy_op(e, d);
+        d.out_row = u.order[k];
+        d.no_scale = (o.flags & IQHIP_OP_NO_SCALE) ? 1 : (((o.flags & IQHIP_OP_SCALAR_RULE) || e->scalar_rule_all) ? 2 : 0);
+        if (k > 0 && u.seg_of[k] != u.seg_of[k - 1]) prev_dst = -1;  // another workgroup: no register hand-over
+        if (!(o.left_len >= 0.0) || !(o.right_len >= 0.0))
+            return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
+        const double *lp, *rp; const int16_t *lsc, *rsc;
+        const uint8_t *lst, *rst; int32_t lkind, rkind;
+        int rc = resolve_child(e, o.left_key, o.left_leaf, prev_dst, &lp, &lsc, &lst, &lkind);
+        if (rc) return rc;
+        rc = resolve_child(e, o.right_key, o.right_leaf, prev_dst, &rp, &rsc, &rst, &rkind);
+        if (rc) return rc;
+        int didx;
+        rc = slab_for_key(e, o.dst_key, true, &didx);
+        if (rc) return rc;
+        if ((lkind != CHILD_LEAF && lp == e->slabs[didx].plh) || (rkind != CHILD_LEAF && rp == e->slabs[didx].plh))
+            return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
+        if (lkind == CHILD_PREV && rkind == CHILD_PREV)
+            return fail(IQHIP_ERR_INVALID, "node update uses the same vector for both children");
+        double llen = o.left_len, rlen = o.right_len;
+        const double *llen_p = len_ptrs ? len_ptrs[2 * u.order[k]] : nullptr, *rlen_p = len_ptrs ? len_ptrs[2 * u.order[k] + 1] : nullptr;
+        d.dst = e->slabs[didx].plh;
+        d.dst_sc = e->slabs[didx].sc;
+        if (e->mfma && !e->mfma_pipelined) {
+            // generic matrix-core kernel: both children are read from memory (pf = left, ld = right)
+            if (lkind != CHILD_LEAF) { lkind = CHILD_LOAD; d.pf = lp; d.pf_sc = lsc; } else d.sl = lst;
+            if (rkind != CHILD_LEAF) { rkind = CHILD_LOAD; d.ld = rp; d.ld_sc = rsc; } else d.sr = rst;
+        } else {
+            // canonical form (the Hadamard product commutes): left in {LEAF, PF}, right in
+            // {LEAF, PREV}; the only other shape is (PF, LOAD): two memory children, neither of
+            // them the previous result -- the kernel reads the second one synchronously.
+            auto swap_children = [&]() {
+                std::swap(lp, rp); std::swap(lsc, rsc); std::swap(lst, rst);
+                std::swap(lkind, rkind); std::swap(llen, rlen); std::swap(llen_p, rlen_p);
+            };
+            if (lkind == CHILD_PREV) swap_children();                              // PREV goes right
+            else if (lkind == CHILD_LEAF && rkind == CHILD_LOAD) swap_children();  // memory child goes left
+            if (lkind == CHILD_LOAD) lkind = CHILD_PF;
+            if (rkind == CHILD_LOAD) (u.seg_of[k] ? e->plan.units_have_load : e->plan.has_load) = true;  // (PF, LOAD)
+            if (lkind == CHILD_PF) { d.pf = lp; d.pf_sc = lsc; d.real_mask |= 1; }
+            if (rkind == CHILD_LOAD) { d.ld = rp; d.ld_sc = rsc; }
+            if (lkind == CHILD_LEAF) d.sl = lst;
+            if (rkind == CHILD_LEAF) d.sr = rst;
+            if (e->ablate & 1) d.real_mask &= ~1;  // timing-only: never stream a child (results wrong)
+        }
+        d.left_kind = lkind; d.right_kind = rkind;
+        d.left_len = llen; d.right_len = rlen;
+        d.left_len_p = llen_p; d.right_len_p = rlen_p;
+        prev_dst = didx;
+    }
+    *last_dst = prev_dst;
+    return IQHIP_OK;
+}
+
+// HOLD analysis (4-state kernel): a streamed left child produced by op j of this plan can stay in registers until its
+// join k if no op in (j, k) streams, loads or parks anything itself (the usual case after heavier-first ordering: the
+// other subtree is a short chain).  20 states, one wave per tile: the parking place is LDS; the launch reserves it when
+// plan.nhold > 0.
+void park_operands(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
+    const bool hold_regs = !e->mfma && !(e->ablate & 4) && (e->use_hold || e->lane_split != 1 || e->wg_size != 256);
+    const bool hold_in_lds = e->mfma && e->mfma_pipelined && e->hold_lds && e->n == 20 && !e->cat_split;
+    std::unordered_map<const double *, int> producer;   // vector -> the op of this plan that writes it
+    for (int k = 0; k < nops && (hold_regs || hold_in_lds); k++) {
+        DevOp &d = e->h_ops[k];
+        const auto it = d.left_kind == CHILD_PF ? producer.find(d.pf) : producer.end();
+        const int j = it == producer.end() ? -1 : it->second;
+        producer[d.dst] = k;
+        if (j < 0) continue;
+        bool ok = !e->h_ops[j].push_hold && seg_of[j] == seg_of[k];
+        if (hold_in_lds && e->top_cs2 && seg_of[k] == 0) ok = false;   // (two waves per tile there: no parking place)
+        for (int q = j + 1; q < k && ok; q++) {
+            const DevOp &m = e->h_ops[q];
+            ok = m.left_kind != CHILD_PF && m.left_kind != CHILD_HOLD && m.right_kind != CHILD_LOAD && !m.push_hold;
+        }
+        if (!ok) continue;
+        e->h_ops[j].push_hold = 1;
+        d.left_kind = CHILD_HOLD;
+        d.pf = e->dummy.plh;
+        d.pf_sc = e->dummy.sc;
+        d.real_mask &= ~1;
+        e->plan.nhold++;
+    }
+    if (e->debug_plan) {
+        int npf = 0;
+        for (int k = 0; k < nops; k++) npf += (e->h_ops[k].left_kind == CHILD_PF) + (e->h_ops[k].right_kind == CHILD_LOAD);
+        fprintf(stderr, "[iqhip] plan: %d children read back from memory, %d parked\n", npf, e->plan.nhold);
+    }
+}
+
+// K2 tables of the leaf children (pipelined matrix-core kernels): slot = taxon, rebuilt by k_leaf_tables before the
+// traversal only where the pendant branch length (or the model) changed since the slot was last built
+int assign_leaf_tables(iqhip_engine *e, int nops) {
+    if (!(e->mfma && e->mfma_pipelined && e->leaf_tables)) return IQHIP_OK;
+    const size_t per = leaf_table_doubles(e);
+    leaf_tables_follow_model(e);   // (the new plan has no tables yet: after a model change every slot is stale)
+    struct Use { double len; const double *len_p; int slot; };
+    std::unordered_map<int, std::vector<Use>> seen;  // taxon -> lengths used in this plan
+    int noverflow = 0;
+    std::vector<TabJob> dirty, clean;
+    std::vector<std::pair<int, int>> uses;  // (op index, side) -> slot, resolved to pointers after (re)allocation
+    std::vector<int> use_slot;
+    for (int k = 0; k < nops; k++) {
+        const DevOp &d = e->h_ops[k];
+        for (int side = 0; side < 2; side++) {
+            if ((side ? d.right_kind : d.left_kind) != CHILD_LEAF) continue;
+            const uint8_t *row = side ? d.sr : d.sl;
+            const int taxon = (int)((row - e->d_states) / e->nptn_pad);
+            const double *len_p = side ? d.right_len_p : d.left_len_p;   // (sweeps: the length is on the device)
+            const double len = len_p ? NAN : (side ? d.right_len : d.left_len);
+            std::vector<Use> &u = seen[taxon];
+            int slot = -1;
+            for (const Use &x : u)
+                if (x.len_p == len_p && (len_p || x.len == len)) slot = x.slot;
+            if (slot < 0) {
+                slot = u.empty() ? taxon : e->ntaxa + noverflow++;
+                u.push_back({len, len_p, slot});
+                const TabJob j = {len, reinterpret_cast<double *>((size_t)slot), len_p, 0.0};  // (tab: the slot number for now)
+                const bool cached = !len_p && slot < e->ntaxa && (size_t)slot < e->tab_len.size() && e->tab_len[slot] == len;
+                (cached ? clean : dirty).push_back(j);
+            }
+            uses.push_back({k, side});
+            use_slot.push_back(slot);
+        }
+    }
+    const size_t need = (size_t)e->ntaxa + (size_t)noverflow;
+    if (need > e->leaf_tab_slots) {
+        HIPCHK(regrow(e, &e->d_leaf_tab, &e->leaf_tab_slots, need + 16, (need + 16) * per));
+        e->plan_cache.uploaded.clear();
+        // a new buffer holds no tables: everything this plan uses is dirty
+        dirty.insert(dirty.end(), clean.begin(), clean.end());
+        clean.clear();
+        e->tab_len.assign(e->leaf_tab_slots, NAN);
+    }
+    if (e->tab_len.size() < e->leaf_tab_slots) e->tab_len.resize(e->leaf_tab_slots, NAN);
+    // non-leaf children point at slot 0: the kernels may request a row unconditionally (one step ahead)
+    for (int k = 0; k < nops; k++) e->h_ops[k].tabL = e->h_ops[k].tabR = e->d_leaf_tab;
+    for (size_t q = 0; q < uses.size(); q++) {
+        DevOp &d = e->h_ops[uses[q].first];
+        (uses[q].second ? d.tabR : d.tabL) = e->d_leaf_tab + (size_t)use_slot[q] * per;
+    }
+    for (std::vector<TabJob> *v : {&dirty, &clean})
+        for (TabJob &j : *v) {
+            const size_t slot = (size_t)j.tab;
+            j.tab = e->d_leaf_tab + slot * per;
+            e->tab_len[slot] = slot < (size_t)e->ntaxa ? j.len : NAN;  // overflow slots are never reused
+            e->plan.tab_jobs.push_back(j);
+        }
+    e->plan.tab_dirty = (int)dirty.size();
+    e->plan.nleaf_tabs = (int)e->plan.tab_jobs.size();
+    return IQHIP_OK;
+}
+
+// cherry tables: an op whose two children are leaves reads its result out of the table of its pair of taxa
+int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
+    // (planning-only engine: the tables are never built, their slots are fake addresses like every other buffer)
+    const bool have_pair = e->planner ? e->cherry_s2 > 0 : (e->pair && e->cherry_model_synced);
+    if (!(cherry_candidate(e) && e->mfma_pipelined && have_pair && nops >= 8)) return IQHIP_OK;
+    const size_t per = (size_t)e->cherry_npairs * e->block;
+    const size_t want = (size_t)2 * e->ntaxa + 16;
+    const bool fresh = e->cherry_cap < want;   // (a new buffer holds no tables)
+    if (fresh) HIPCHK(regrow(e, &e->d_cherry_tab, &e->cherry_cap, want, want * per));
+    // room for every cherry a plan can hold; a search that has walked through more pairs than that starts over
+    if (fresh || e->cherry_slots.size() + (size_t)e->ntaxa / 2 + 1 > e->cherry_cap) {
+        e->cherry_slot_of.clear();
+        e->cherry_slots.clear();
+    }
+    const uint64_t stamp = ++e->cherry_stamp;
+    for (int k = 0; k < nops; k++) {
+        DevOp &d = e->h_ops[k];
+        if (d.left_kind != CHILD_LEAF || d.right_kind != CHILD_LEAF || d.left_len_p || d.right_len_p) continue;
+        // (the top stage's two-waves-per-tile / row-split kernels compute their cherries)
+        if ((e->top_cs2 || (e->n == 64 && e->mixed_top)) && seg_of[k] == 0) continue;
+        const uint64_t tl = (uint64_t)((d.sl - e->d_states) / e->nptn_pad), tr = (uint64_t)((d.sr - e->d_states) / e->nptn_pad);
+        const uint64_t key = (tl << 32) | tr;
+        auto it = e->cherry_slot_of.find(key);
+        int slot;
+        if (it == e->cherry_slot_of.end()) {
+            if (e->cherry_slots.size() >= e->cherry_cap) continue;
+            slot = (int)e->cherry_slots.size();
+            e->cherry_slots.emplace_back();
+            e->cherry_slot_of[key] = slot;
+        } else {
+            slot = it->second;
+        }
+        iqhip_engine::CherrySlot &cs = e->cherry_slots[slot];
+        const bool same = cs.len_l == d.left_len && cs.len_r == d.right_len;
+        if (cs.stamp == stamp && !same) continue;   // (the same pair with other lengths in one plan: computed the ordinary way)
+        if (!same || cs.model_version != e->model_version) {
+            cs.len_l = d.left_len;
+            cs.len_r = d.right_len;
+            cs.model_version = 0;   // until built (submit_traverse)
+            if (cs.stamp != stamp) e->plan.cherry_jobs.push_back(slot);
+        }
+        cs.stamp = stamp;
+        d.cherry = e->d_cherry_tab + (size_t)slot * per;
+        e->plan.uses_cherry = true;
+    }
+    return IQHIP_OK;
+}
+
+// doubles of LDS one chunk's per-(op, child) regions may use
+int lds_budget(const iqhip_engine *e) {
+    const int B = e->block;
+    if (!e->mfma) return (e->lds_budget_bytes / 8) - 128 - B;
+    const int MT = (e->n + 15) / 16, KS = e->n / 4;
+    int fixed = (e->row_split && e->mfma_pipelined) ? (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128
+                      : (e->mfma_pipelined ? mfma2_fixed_lds_doubles(e->n) : 2 * MT * KS * 64) +
+                            (e->state_unknown + 1 - e->n) * e->n;
+    // (64 states: a launch may mix both roles, k_traverse_mfma_top64)
+    if (e->mfma_pipelined && e->n == 64) fixed = std::max(fixed, (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128);
+    // two workgroups per CU (160 KB LDS): <= 78 KB each, images included (a third workgroup for the 20-state kernel was
+    // measured: no gain, more chunks); IQHIP_MFMA_LDS_KB overrides
+    // (20 states: + 2.6 KB of static arrays per workgroup, the fill's descriptor copies)
+    const int total_kb = e->mfma_lds_kb >= 0 ? e->mfma_lds_kb : (e->n == 20 ? 75 : 78);
+    if (e->plan.nhold > 0) fixed += 4 * 16 * B;   // the waves' parking places (CHILD_HOLD in LDS)
+    int budget = (total_kb * 1024) / 8 - fixed;
+    // the generic kernel's images leave two workgroups per CU too little for one op with two vector children once
+    // n * ncat > 864 (64 states, 14 .. 16 categories or components): one workgroup per CU, 150 KB (every matrix-core
+    // kernel allows that much dynamic LDS)
+    if (e->mfma_lds_kb < 0 && !e->mfma_pipelined && budget < 2 * B) budget = (150 * 1024) / 8 - fixed;
+    return budget;
+}
+
+// LDS layout of the per-(op, child) regions, cut into chunks that fit the budget
+int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
+    const int B = e->block, budget = lds_budget(e);
+    const bool tables_in_lds = e->mfma && e->mfma_pipelined && e->n == 20 && e->plan.nleaf_tabs > 0;
+    // a LEAF child's region: 4 states -- exponentials + the 5-row K2 table; 20 states with leaf tables -- the child's
+    // whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
+    const int leaf_sz = !e->mfma ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
+    const int slot0 = e->mfma ? 0 : e->wg_size / 8;
+    int chunk_start = 0, used = slot0, regs = 0, max_used = 0, slots = 1, max_slots = 1;
+    for (int k = 0; k < nops; k++) {
+        DevOp &d = e->h_ops[k];
+        const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : B;
+        const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : B;
+        // 4-state path: each leaf child also stages one state byte per thread in LDS
+        const int nleaf = (d.left_kind == CHILD_LEAF) + (d.right_kind == CHILD_LEAF);
+        const int need = szl + szr + (e->mfma ? 0 : nleaf * e->wg_size / 8);
+        if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
+        if ((used + need > budget || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
+            e->h_ops[chunk_start].chunk_nops = k - chunk_start;
+            chunk_start = k; used = slot0; regs = 0; slots = 1;
+        }
+        d.lds_left = regs; d.lds_right = regs + szl;
+        regs += szl + szr;
+        used += need;
+        if (regs > max_used) max_used = regs;
+        d.sl_slot = d.left_kind == CHILD_LEAF ? slots++ : 0;
+        d.sr_slot = d.right_kind == CHILD_LEAF ? slots++ : 0;
+        if (slots > max_slots) max_slots = slots;
+    }
+    if (nops > 0) e->h_ops[chunk_start].chunk_nops = nops - chunk_start;
+    e->plan.state_slots = max_slots;
+    e->plan.lds_doubles = max_used;
+    return IQHIP_OK;
+}
+
+// The kernels' contract on a plan, checked on the host before the descriptors go to the device (IQHIP_CHECK_PLAN=1; always
+// for a planning-only engine).  The traversal kernels issue the requests of op k+1 unconditionally while op k computes
+// (streamed child, its counters, leaf state rows, K2 table rows), so EVERY pointer of EVERY descriptor -- the look-ahead
+// sentinels behind the last op included -- must be a dereferenceable address of the right kind even when the op does not
+// use it: a null tabL / tabR of a non-leaf child was a GPU memory fault in round 2 that this check finds without a GPU.
+int check_plan(iqhip_engine *e, int nops, int nsentinels) {
+    std::unordered_set<const void *> vecs, scs;
+    for (const Slab &sl : e->slabs) { vecs.insert(sl.plh); scs.insert(sl.sc); }
+    vecs.insert(e->dummy.plh);
+    scs.insert(e->dummy.sc);
+    const size_t per = (e->mfma && e->mfma_pipelined) ? leaf_table_doubles(e) : 0;
+    char msg[256];
+    auto bad = [&](int k, const char *what) {
+        snprintf(msg, sizeof msg, "plan check: op %d of %d (+%d sentinels): %s", k, nops, nsentinels, what);
+        return fail(IQHIP_ERR_INVALID, msg);
+    };
+    auto state_row = [&](const uint8_t *p) {
+        if (!p || !e->d_states || p < e->d_states) return false;
+        const size_t off = (size_t)(p - e->d_states);
+        return off % (size_t)e->nptn_pad == 0 && off / (size_t)e->nptn_pad < (size_t)e->ntaxa;
+    };
+    auto table = [&](const double *p) {
+        if (e->plan.nleaf_tabs == 0 && !e->d_leaf_tab) return p == nullptr;  // kernel variant without tables
+        if (!p || !e->d_leaf_tab || p < e->d_leaf_tab || per == 0) return false;
+        const size_t off = (size_t)(p - e->d_leaf_tab);
+        return off % per == 0 && off / per < e->leaf_tab_slots;
+    };
+    for (int k = 0; k < nops + nsentinels; k++) {
+        const DevOp &d = e->h_ops[k];
+        if (!vecs.count(d.dst) || d.dst == nullptr) return bad(k, "dst is not a vector slab");
+        if (!scs.count(d.dst_sc)) return bad(k, "dst_sc is not a counter slab");
+        if (!vecs.count(d.pf)) return bad(k, "pf (streamed child) is not a vector slab / the dummy slab");
+        if (!scs.count(d.pf_sc)) return bad(k, "pf_sc is not a counter slab / the dummy");
+        if (!vecs.count(d.ld)) return bad(k, "ld (second memory child) is not a vector slab / the dummy slab");
+        if (!scs.count(d.ld_sc)) return bad(k, "ld_sc is not a counter slab / the dummy");
+        if (!state_row(d.sl) || !state_row(d.sr)) return bad(k, "sl / sr is not a row of the state matrix");
+        if (!table(d.tabL) || !table(d.tabR)) return bad(k, "tabL / tabR is not a K2 table slot");
+        if (d.cherry) {
+            const size_t cper = (size_t)e->cherry_npairs * e->block;
+            if (!e->d_cherry_tab || cper == 0 || d.cherry < e->d_cherry_tab || (size_t)(d.cherry - e->d_cherry_tab) % cper != 0 ||
+                (size_t)(d.cherry - e->d_cherry_tab) / cper >= e->cherry_cap || k >= nops || d.left_kind != CHILD_LEAF ||
+                d.right_kind != CHILD_LEAF)
+                return bad(k, "cherry is not a cherry-table slot of an op with two leaf children");
+        }
+        if (k >= nops) continue;  // sentinels: pointers only
+        if (d.dst == e->dummy.plh || d.dst_sc == e->dummy.sc) return bad(k, "a real op writes the dummy slab");
+        const bool lk = d.left_kind == CHILD_LEAF || d.left_kind == CHILD_PF || d.left_kind == CHILD_HOLD ||
+                        (d.left_kind == CHILD_LOAD && e->mfma && !e->mfma_pipelined);
+        const bool rk = d.right_kind == CHILD_LEAF || d.right_kind == CHILD_PREV || d.right_kind == CHILD_LOAD;
+        if (!lk || !rk) return bad(k, "child kinds are not in canonical form");
+        if (d.left_kind == CHILD_PF && (d.pf == e->dummy.plh || !(d.real_mask & 1))) return bad(k, "streamed child without a real vector");
+        if (d.left_kind != CHILD_PF && !(e->mfma && !e->mfma_pipelined) && (d.real_mask & 1)) return bad(k, "real_mask set without a streamed child");
+        if (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh) return bad(k, "second memory child without a real vector");
+        if (d.dst == d.pf || d.dst == d.ld) return bad(k, "op writes one of its own children");
+        if (!(d.left_len >= 0.0) || !(d.right_len >= 0.0)) return bad(k, "negative or NaN branch length");
+        if (d.out_row < 0 || d.out_row >= nops) return bad(k, "out_row outside the caller's op list");
+        if (d.lds_left < 0 || d.lds_right < 0 || d.lds_left > e->plan.lds_doubles || d.lds_right > e->plan.lds_doubles)
+            return bad(k, "LDS region outside the launch's allocation");
+        if (d.sl_slot < 0 || d.sr_slot < 0 || d.sl_slot >= e->plan.state_slots || d.sr_slot >= e->plan.state_slots)
+            return bad(k, "leaf-state slot outside the launch's allocation");
+        if (d.chunk_nops < 0 || k + d.chunk_nops > nops) return bad(k, "LDS chunk runs past the plan");
+    }
+    // chunks tile the plan; the segment table stays inside it
+    for (int k = 0; k < nops;) {
+        if (e->h_ops[k].chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
+        k += e->h_ops[k].chunk_nops;
+    }
+    const int *tab = reinterpret_cast<const int *>(e->h_ops + e->plan.table_off);
+    int covered = 0;
+    for (int u = 0; u <= e->plan.nunits; u++) {
+        const int b = tab[2 * u], n = tab[2 * u + 1];
+        if (b < 0 || n < 0 || b + n > nops) return bad(b, "segment outside the plan");
+        covered += n;
+    }
+    if (covered != nops) return bad(nops, "segments do not cover the plan exactly once");
+    return IQHIP_OK;
+}
+
+// The descriptors of a repeated plan (model-parameter optimisation re-evaluates the same tree) are already on the
+// device: skip the upload, never the computation.
+int upload_plan(iqhip_engine *e, size_t nbytes) {
+    if (e->planner) return IQHIP_OK;   // (nothing to upload to)
+    std::vector<char> &up = e->plan_cache.uploaded;
+    const char *h = reinterpret_cast<const char *>(e->h_ops);
+    if (e->plan.small) {
+        // (rides in the kernel arguments, which the launch copies out of h_ops; `uploaded` is what d_ops would hold)
+    } else if (up.size() == nbytes && memcmp(up.data(), h, nbytes) == 0) {
+        return IQHIP_OK;
+    } else if (e->plan_arena_on && e->plan_arena_used + nbytes <= e->plan_arena_cap) {
+        // a sweep enqueues many plans before the device has run the first: each upload goes out of a slice of its own
+        // of a pinned arena, so that re-using h_ops for the next plan never has to wait for the device (that wait -- the
+        // staging event below -- made the host fall in step with the device eight times per 97-branch protein sweep)
+        char *slice = e->h_plan_arena + e->plan_arena_used;
+        memcpy(slice, h, nbytes);
+        e->plan_arena_used += (nbytes + 255) / 256 * 256;
+        HIPCHK(hipMemcpyAsync(e->d_ops, slice, nbytes, hipMemcpyHostToDevice, e->stream));
+    } else {
+        HIPCHK(hipMemcpyAsync(e->d_ops, e->h_ops, nbytes, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipEventRecord(e->staging_free, e->stream));
+        e->staging_busy = true;
+    }
+    up.assign(h, h + nbytes);
+    return IQHIP_OK;
+}
+
+// sentinels, segment table and K2 job list behind the descriptors; the cache key; the small-plan decision; check; upload
+int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units &u, const std::vector<int> *explicit_segs,
+                      const double *const *len_ptrs, int last_dst) {
+    Plan &p = e->plan;
+    for (int q = 0; q < kSentinels; q++) dummy_op(e, e->h_ops[nops + q]);  // targets of the look-ahead requests
+    p.table_off = nops + kSentinels;
+    const int table_ops = segment_table_ops(u);
+    int *tab = reinterpret_cast<int *>(e->h_ops + p.table_off);
+    memset(tab, 0, sizeof(DevOp) * (size_t)table_ops);
+    tab[0] = u.top_begin; tab[1] = nops - u.top_begin;
+    for (size_t i = 0; i < u.units.size(); i++) { tab[2 + 2 * i] = u.units[i].first; tab[3 + 2 * i] = u.units[i].second; }
+    p.nunits = (int)u.units.size();
+    p.stage_units = std::move(u.stage_units);
+    p.top_nops = nops - u.top_begin;
+    p.jobs_off = p.table_off + table_ops;
+    const int jobs_ops = devops_for(sizeof(TabJob) * p.tab_jobs.size());
+    if (jobs_ops > 0) {
+        memset(e->h_ops + p.jobs_off, 0, sizeof(DevOp) * (size_t)jobs_ops);
+        memcpy(e->h_ops + p.jobs_off, p.tab_jobs.data(), sizeof(TabJob) * p.tab_jobs.size());
+    }
+    PlanCache &c = e->plan_cache;
+    c.ops_in.assign((const char *)ops, (const char *)(ops + nops));
+    c.segs = explicit_segs ? *explicit_segs : std::vector<int>();
+    c.version = len_ptrs ? 0 : e->keymap_version;  // (slabs created while building are included; a sweep step's plan is never re-used)
+    c.dst = last_dst;
+    // a small plan of the 4-state kernel rides in the kernel arguments (launch_traverse4 copies it out of h_ops)
+    // (matrix-core path: the pipelined 20-state kernels without leaf tables -- tables come with a job list in the buffer)
+    const bool small_kernel = !e->mfma || (e->mfma_pipelined && e->n == 20 && !e->leaf_tables && p.nleaf_tabs == 0);
+    p.small = e->small_plans && small_kernel && !explicit_segs && u.units.empty() && nops > 0 && nops + kSentinels <= kSmallPlanOps;
+    p.small_nops = nops;
+    if (e->planner && nops > 0) {   // negative tests (IQHIP_DEBUG_BREAK_PLAN): break one descriptor the way round 2's fault did
+        const std::string &br = e->debug_break_plan;
+        if (br == "tab") e->h_ops[nops - 1].tabL = nullptr;
+        else if (br == "sentinel") e->h_ops[nops + kSentinels - 1].pf = nullptr;
+        else if (br == "states") e->h_ops[0].sr = nullptr;
+        else if (br == "cherry")
+            for (int k = 0; k < nops; k++)
+                if (e->h_ops[k].cherry) { e->h_ops[k].cherry += 8; break; }   // (inside the buffer, not on a table)
+    }
+    if (e->check_plans && !e->ablate) {
+        const int rc = check_plan(e, nops, kSentinels);
+        if (rc) { c.invalidate(); return rc; }
+    }
+    return upload_plan(e, sizeof(DevOp) * (size_t)(p.jobs_off + jobs_ops));
+}
+
+}  // namespace
+
+namespace iqhip {
+
+// Resolve one child of a node op. prev_dst = slab index written by the previous op (-1: none).
+int resolve_child(iqhip_engine *e, uint64_t key, int32_t leaf, int prev_dst, const double **plh, const int16_t **sc,
+                  const uint8_t **states, int32_t *kind) {
+    *plh = nullptr; *sc = nullptr; *states = nullptr;
+    if (leaf >= 0) {
+        if (leaf >= e->ntaxa) return fail(IQHIP_ERR_INVALID, "leaf id out of range");
+        *states = e->d_states + (size_t)leaf * e->nptn_pad;
+        *kind = CHILD_LEAF;
+        return IQHIP_OK;
+    }
+    int idx;
+    int rc = slab_for_key(e, key, false, &idx);
+    if (rc) return rc;
+    *plh = e->slabs[idx].plh;
+    *sc = e->slabs[idx].sc;
+    *kind = (idx == prev_dst) ? CHILD_PREV : CHILD_LOAD;
+    return IQHIP_OK;
+}
+
+int build_branch(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, int prev_dst, DevBranch *br) {
+    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
+    if (a.leaf >= 0 && b.leaf >= 0)
+        return fail(IQHIP_ERR_INVALID, "branch with two leaf ends (2-taxon tree) is not supported");
+    if (b.leaf >= 0) std::swap(a, b);  // the reference puts the leaf on the `dad` side (:739-746)
+    const uint8_t *st_unused;
+    int rc = resolve_child(e, a.key, a.leaf, prev_dst, &br->a, &br->a_sc, &br->a_states, &br->a_kind);
+    if (rc) return rc;
+    rc = resolve_child(e, b.key, b.leaf, prev_dst, &br->b, &br->b_sc, &st_unused, &br->b_kind);
+    if (rc) return rc;
+    br->len = len;
+    return IQHIP_OK;
+}
+
+bool leaf_tables_follow_model(iqhip_engine *e) {
+    if (e->tab_model_version == e->model_version) return false;
+    std::fill(e->tab_len.begin(), e->tab_len.end(), NAN);
+    const size_t per = leaf_table_doubles(e);
+    for (const TabJob &j : e->plan.tab_jobs) {
+        const size_t slot = (size_t)(j.tab - e->d_leaf_tab) / per;
+        if (slot < (size_t)e->ntaxa) e->tab_len[slot] = j.len;
+    }
+    e->tab_model_version = e->model_version;
+    return true;
+}
+
+int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_dst, const std::vector<int> *explicit_segs,
+               const double *const *len_ptrs) {
+    if (nops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
+    if (plan_is_cached(e, ops, nops, explicit_segs, len_ptrs)) {
+        *last_dst = e->plan_cache.dst;
+        return IQHIP_OK;
+    }
+    e->plan_cache.version = 0;
+    if (e->staging_busy) {  // the previous submission may still be copying h_ops
+        HIPCHK(hipEventSynchronize(e->staging_free));
+        e->staging_busy = false;
+    }
+    e->plan = Plan();
+    e->plan.cherry_model = e->model_version;
+    Units u;
+    int rc = cut_units(e, ops, nops, explicit_segs, u);
+    // (room for the K2 table job list behind the segment table: at most two leaf children per op)
+    if (!rc) rc = ensure_plan_capacity(e, nops + kSentinels + segment_table_ops(u) + devops_for(sizeof(TabJob) * (size_t)(2 * nops + 1)));
+    if (!rc) rc = fill_descriptors(e, ops, nops, u, len_ptrs, last_dst);
+    if (!rc) park_operands(e, nops, u.seg_of);
+    if (!rc) rc = assign_leaf_tables(e, nops);
+    if (!rc) rc = assign_cherry_tables(e, nops, u.seg_of);
+    if (!rc) rc = lay_out_lds(e, nops, u.seg_of);
+    if (!rc) rc = finish_and_upload(e, ops, nops, u, explicit_segs, len_ptrs, *last_dst);
+    return rc;
+}
+
+}  // namespace iqhip

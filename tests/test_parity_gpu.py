@@ -698,7 +698,7 @@ def test_nni_evaluation_on_scratch_buffers(pkg, synth, oracle, nni5):
 
 
 # ------------------------------------------------------------------------------------------
-# staged plans (engine.hip build_plan): units of independent subtrees + top stage
+# staged plans (plan.hip cut_units): units of independent subtrees + top stage
 # ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n,ncat,seq_type,ntaxa,cat", [(4, 4, 0, 40, False), (4, 4, 0, 60, True), (20, 4, 1, 30, False),

@@ -2,7 +2,7 @@
 device addresses).  The traversal kernels request the inputs of op k+1 unconditionally while op k computes, so every
 pointer of every descriptor -- look-ahead sentinels included -- must be a live allocation of the right kind whether the op
 uses it or not.  Round 2 had a GPU memory fault from exactly that (null K2 table pointers of non-leaf children);
-check_plan (engine.hip) finds that class of defect here, without a GPU, for every kernel family and staging variant."""
+check_plan (plan.hip) finds that class of defect here, without a GPU, for every kernel family and staging variant."""
 import ctypes as C
 import os
 
@@ -67,7 +67,7 @@ def test_plans_satisfy_the_kernel_contract(pkg, synth, monkeypatch, nstates, nca
 
 def test_cherry_tables_are_planned_and_checked(pkg, synth, monkeypatch):
     """20 states x 4 categories from 8192 patterns on: ops with two leaf children get a slot of the cherry-table buffer
-    (engine.hip build_plan, DevOp::cherry) -- in the unit stages only, one slot per pair of taxa, rebuilt only for new
+    (plan.hip assign_cherry_tables, DevOp::cherry) -- in the unit stages only, one slot per pair of taxa, rebuilt only for new
     lengths -- and a pointer that is not a slot is refused."""
     lib = pkg.libiqhip()
 
