@@ -5,7 +5,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <atomic>
@@ -20,8 +19,8 @@ int set_error(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+double debug_build_us = 0.0;
 }  // namespace iqhip
-static int fail(int code, const std::string &msg) { return set_error(code, msg); }
 
 extern "C" const char *iqhip_last_error(void) { return g_err.c_str(); }
 extern "C" int iqhip_abi_version(void) { return IQHIP_ABI_VERSION; }
@@ -33,8 +32,7 @@ extern "C" int iqhip_device_count(void) {
 
 static int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
-static hipError_t use_device(const iqhip_engine *e) { return e->planner ? hipErrorInvalidDevice : hipSetDevice(e->device); }
+hipError_t iqhip::use_device(const iqhip_engine *e) { return e->planner ? hipErrorInvalidDevice : hipSetDevice(e->device); }
 // everything about an engine that follows from its shape, the CU count (e->num_cus, set by the caller) and the
 // environment switches -- no HIP call, so that the planning-only engine of iqhip_debug_create_planner shares it
 static void configure_engine(iqhip_engine *e, int device, int nstates, int nstates_user, int ncat, int64_t nptn, int ntaxa) {
@@ -69,6 +67,7 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     if (const char *ml = getenv("IQHIP_LEVELS")) e->max_levels = std::max(1, atoi(ml));
     if (const char *kb = getenv("IQHIP_MFMA_LDS_KB")) e->mfma_lds_kb = std::max(0, atoi(kb));
     e->debug_plan = getenv("IQHIP_DEBUG_PLAN") != nullptr;
+    e->debug_sweep = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
     if (const char *br = getenv("IQHIP_DEBUG_BREAK_PLAN")) e->debug_break_plan = br;
     if (const char *v = getenv("IQHIP_NEWTON")) e->newton_chain_forced = !strcmp(v, "chain");
     if (const char *v = getenv("IQHIP_SWEEP")) e->sweep_one_submission = atoi(v) != 0;
@@ -686,14 +685,14 @@ extern "C" int iqhip_set_mixture_model(iqhip_engine *e, int nclass, const int32_
 // ---------------------------------------------------------------------------------------
 // submissions (the descriptors come from the planner, plan.hip)
 // ---------------------------------------------------------------------------------------
-static int ensure_slab_rows(iqhip_engine *e, int nrows) {
+int iqhip::ensure_slab_rows(iqhip_engine *e, int nrows) {
     const int64_t need = (int64_t)nrows * e->ntiles * e->lane_split;
     if (need <= e->slab_cap) return IQHIP_OK;
     HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, need, need));
     return IQHIP_OK;
 }
 
-static int check_ready(iqhip_engine *e) {
+int iqhip::check_ready(iqhip_engine *e) {
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (!e->model_set || !e->aln_set)
         return fail(IQHIP_ERR_INVALID, "engine needs iqhip_set_model and iqhip_set_alignment first");
@@ -717,11 +716,6 @@ static void timing_end(iqhip_engine *e) {
     hipEventRecord(e->tev[e->tev_used].second, e->stream);
     e->tev_used++;
 }
-
-static double g_dbg_build_us = 0.0;   // IQHIP_DEBUG_SWEEP: host time spent in build_plan
-static int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, bool has_root, iqhip_branch_end a,
-                           iqhip_branch_end b, double len, bool skip_reduce = false, const std::vector<int> *explicit_segs = nullptr,
-                           const double *const *len_ptrs = nullptr);
 
 // the tables the current plan needs: one node update per table on the pair engine (independent segments of one
 // submission, same stream), then the move into register order
@@ -761,19 +755,18 @@ static int build_cherry_tables(iqhip_engine *e) {
 }
 
 // enqueue: plan upload, K1, fused traversal (+ optional root lnL), fixed-order reduction
-static int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, bool has_root,
+int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, bool has_root,
                            iqhip_branch_end a, iqhip_branch_end b, double len, bool skip_reduce,
                            const std::vector<int> *explicit_segs, const double *const *len_ptrs) {
     int rc = check_ready(e);
     if (rc) return rc;
     if (nops < 0 || (nops > 0 && !ops)) return fail(IQHIP_ERR_INVALID, "bad ops array");
     int last_dst = -1;
-    static const bool dbg_t = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
-    timespec q0, q1;
-    if (dbg_t) clock_gettime(CLOCK_MONOTONIC, &q0);
+    Stopwatch watch;
+    if (e->debug_sweep) watch.start();
     rc = build_plan(e, ops, nops, &last_dst, explicit_segs, len_ptrs);
     if (rc) return rc;
-    if (dbg_t) { clock_gettime(CLOCK_MONOTONIC, &q1); g_dbg_build_us += (q1.tv_sec - q0.tv_sec) * 1e6 + (q1.tv_nsec - q0.tv_nsec) * 1e-3; }
+    if (e->debug_sweep) debug_build_us += watch.us();
     DevBranch br;
     if (has_root) {
         rc = build_branch(e, a, b, len, last_dst, &br);
@@ -826,7 +819,7 @@ static int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
     return IQHIP_OK;
 }
 
-static int read_result(iqhip_engine *e, int ndoubles) {
+int iqhip::read_result(iqhip_engine *e, int ndoubles) {
     if (e->d_result != e->d_result_own)  // caller-bound device buffer
         HIPCHK(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double) * ndoubles, hipMemcpyDeviceToHost,
                               e->stream));
@@ -890,14 +883,7 @@ static int asc_finish_lnl(iqhip_engine *e, double *lnl) {
     return IQHIP_OK;
 }
 
-namespace iqhip {
-int eng_read_result(iqhip_engine *e, int ndoubles) { return read_result(e, ndoubles); }
-int eng_submit_updates(iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *segs) {
-    iqhip_branch_end none = {0, -1, 0};
-    return submit_traverse(e, ops, nops, false, none, none, 0.0, /*skip_reduce=*/false, segs);
-}
-int eng_repair_lnl(iqhip_engine *e, double *lnl) { return repair_lnl(e, lnl); }
-}  // namespace iqhip
+int iqhip::eng_repair_lnl(iqhip_engine *e, double *lnl) { return repair_lnl(e, lnl); }
 
 // Sharded engines (comm.hip): a non-finite lnL is repaired rank by rank (each rank fixes its own _pattern_lh and
 // re-sums its share), then the shares are all-reduced again.  Every rank sees the same all-reduced value, so every
@@ -972,6 +958,12 @@ extern "C" int iqhip_update_partials_async(iqhip_engine *e, const iqhip_node_op 
     return submit_traverse(e, ops, nops, false, none, none, 0.0);
 }
 
+void iqhip::set_theta_branch(iqhip_engine *e, const DevBranch &br) {
+    e->theta_valid = true;
+    e->theta_a_sc = br.a_sc;
+    e->theta_b_sc = br.b_sc;
+}
+
 extern "C" int iqhip_compute_theta(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b) {
     if (e && !e->shards.empty()) return sharded::compute_theta(e, a, b);
     int rc = check_ready(e);
@@ -981,9 +973,7 @@ extern "C" int iqhip_compute_theta(iqhip_engine *e, iqhip_branch_end a, iqhip_br
     if (rc) return rc;
     if (e->mfma) HIPCHK(launch_stream_mfma(e, 1, &br, 0.0, (int)e->ntiles));
     else HIPCHK(launch_theta4(e, br));
-    e->theta_valid = true;
-    e->theta_a_sc = br.a_sc;
-    e->theta_b_sc = br.b_sc;
+    set_theta_branch(e, br);
     return IQHIP_OK;
 }
 
@@ -1026,865 +1016,6 @@ extern "C" int iqhip_derv(iqhip_engine *e, double len, double *df, double *ddf) 
     }
     if (df) *df = a;
     if (ddf) *ddf = b;
-    return IQHIP_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Newton as a chain of enqueued steps (kernels_newton.hip, "state machine" kernels): the form a sharded engine
-// uses -- every derivative evaluation is followed by an in-stream all-reduce of {df, ddf}, so the loop cannot live
-// in one kernel -- and the fallback when k_newton's grid barrier cannot be trusted.  Steps are enqueued in chunks;
-// the host reads the 128-byte state once per chunk; steps enqueued after convergence do nothing.
-// ---------------------------------------------------------------------------------------
-namespace iqhip {
-int newton_state_alloc(iqhip_engine *e) {
-    if (e->d_nstate) return IQHIP_OK;
-    if (hipMalloc((void **)&e->d_nstate, sizeof(NewtonState)) != hipSuccess ||
-        hipHostMalloc((void **)&e->h_nstate, sizeof(NewtonState)) != hipSuccess)
-        return set_error(IQHIP_ERR_NOMEM, "Newton state");
-    return IQHIP_OK;
-}
-
-// enqueue `nsteps` evaluations + updates on the engine's stream (with the engine's own all-reduce in between)
-int newton_chain_enqueue(iqhip_engine *e, int nsteps) {
-    const int nwaves = (int)e->ntiles;
-    for (int k = 0; k < nsteps; k++) {
-        const int rows = e->asc_active ? 5 : 2;   // (+ASC: prob_const, df_const, ddf_const ride along)
-        if (e->asc_active && e->n_unobs == 0 && hipMemsetAsync(e->d_result + 2, 0, 3 * sizeof(double), e->stream) != hipSuccess)
-            return set_error(IQHIP_ERR_HIP, "Newton chain: memset failed");
-        if (launch_derv_at_state(e, nwaves) != hipSuccess || launch_reduce(e, 0, e->n_unobs > 0 ? 5 : 2, nwaves) != hipSuccess)
-            return set_error(IQHIP_ERR_HIP, "Newton chain: launch failed");
-        int rc = comm_allreduce(e, rows);
-        if (rc) return rc;
-        if (launch_newton_state_update(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "Newton chain: launch failed");
-    }
-    return IQHIP_OK;
-}
-
-// the same pieces one at a time, for the single-process front, which interleaves its shards' steps with one grouped
-// all-reduce per step
-int eng_newton_begin(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps) {
-    int rc = check_ready(e);
-    if (rc) return rc;
-    if (!e->theta_valid) return set_error(IQHIP_ERR_INVALID, "Newton: theta not computed");
-    rc = newton_state_alloc(e);
-    if (rc) return rc;
-    rc = ensure_slab_rows(e, 5);
-    if (rc) return rc;
-    if (launch_newton_state_init(e, xguess, x1, x2, xacc, max_steps) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "Newton chain: launch failed");
-    return IQHIP_OK;
-}
-int eng_newton_eval_enqueue(iqhip_engine *e) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    const int nwaves = (int)e->ntiles;
-    if (e->asc_active && e->n_unobs == 0 && hipMemsetAsync(e->d_result + 2, 0, 3 * sizeof(double), e->stream) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "Newton chain: memset failed");
-    if (launch_derv_at_state(e, nwaves) != hipSuccess || launch_reduce(e, 0, e->n_unobs > 0 ? 5 : 2, nwaves) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "Newton chain: launch failed");
-    return IQHIP_OK;
-}
-int eng_newton_update_enqueue(iqhip_engine *e) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    if (launch_newton_state_update(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "Newton chain: launch failed");
-    return IQHIP_OK;
-}
-
-int newton_state_read(iqhip_engine *e) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    if (hipMemcpyAsync(e->h_nstate, e->d_nstate, sizeof(NewtonState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "Newton chain: state read failed");
-    e->staging_busy = false;
-    return IQHIP_OK;
-}
-}  // namespace iqhip
-
-// The state machine on the host, for callers that own the collective themselves (they evaluate {df, ddf} with
-// iqhip_derv_async, all-reduce them their own way and need the reference's update rule between evaluations) and for
-// the CPU tests, which check it step by step against the loop form of optimization.cpp:388-465.
-extern "C" int iqhip_newton_host_init(void *state, double xguess, double x1, double x2, double xacc, int max_steps,
-                                      double *first_x) {
-    if (!state) return fail(IQHIP_ERR_INVALID, "null argument");
-    if (!(x1 >= 0.0) || !(x2 > x1) || !(xacc > 0.0) || max_steps < 1 || !(xguess >= 0.0))
-        return fail(IQHIP_ERR_INVALID, "iqhip_newton_host_init: bad bounds / tolerance / step count");
-    static_assert(sizeof(NewtonState) == IQHIP_NEWTON_STATE_BYTES, "NewtonState size");
-    NewtonState st;
-    newton_init(st, xguess, x1, x2, xacc, max_steps);
-    memcpy(state, &st, sizeof st);
-    if (first_x) *first_x = st.rts;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_newton_host_update(void *state, double df_sum, double ddf_sum, double *next_x, int *done) {
-    if (!state) return fail(IQHIP_ERR_INVALID, "null argument");
-    NewtonState st;
-    memcpy(&st, state, sizeof st);
-    newton_update(st, df_sum, ddf_sum);
-    memcpy(state, &st, sizeof st);
-    if (next_x) *next_x = st.rts;
-    if (done) *done = st.done;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_newton_host_result(const void *state, double *optx, double *d2l, int *nsteps, int *status) {
-    if (!state) return fail(IQHIP_ERR_INVALID, "null argument");
-    NewtonState st;
-    memcpy(&st, state, sizeof st);
-    if (!st.done) return fail(IQHIP_ERR_INVALID, "Newton state machine has not finished");
-    if (optx) *optx = st.result;
-    if (d2l) *d2l = st.d2l;
-    if (nsteps) *nsteps = st.neval;
-    if (status) *status = st.status;
-    return IQHIP_OK;
-}
-
-// theta must be resident; result[2..] untouched
-static int newton_chain(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps,
-                        double *optx, double *d2l, int *nsteps) {
-    int rc = newton_state_alloc(e);
-    if (rc) return rc;
-    rc = ensure_slab_rows(e, 5);
-    if (rc) return rc;
-    HIPCHK(launch_newton_state_init(e, xguess, x1, x2, xacc, max_steps));
-    // a typical solve converges in 3..5 evaluations: enqueue that many before looking
-    int enq = 0;
-    for (;;) {
-        const int chunk = enq == 0 ? std::min(4, max_steps + 1) : 2;
-        rc = newton_chain_enqueue(e, chunk);
-        if (rc) return rc;
-        enq += chunk;
-        rc = newton_state_read(e);
-        if (rc) return rc;
-        if (e->h_nstate->done) break;
-        if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
-    }
-    const NewtonState &st = *e->h_nstate;
-    if (st.status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-    if (st.status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-    if (optx) *optx = st.result;
-    if (d2l) *d2l = st.d2l;
-    if (nsteps) *nsteps = st.neval;
-    return IQHIP_OK;
-}
-
-// k_newton's grid barrier needs every workgroup resident; a single workgroup needs no barrier.  IQHIP_NEWTON=chain
-// forces the chain form (tests).
-static bool newton_use_chain(const iqhip_engine *e) { return e->comm || e->newton_chain_forced; }
-
-extern "C" int iqhip_newton_branch(iqhip_engine *e, double xguess, double x1, double x2, double xacc,
-                                   int max_steps, double *optx, double *d2l, int *nsteps) {
-    if (!(x1 >= 0.0) || !(x2 > x1) || !(xacc > 0.0) || max_steps < 1 || !(xguess >= 0.0))
-        return fail(IQHIP_ERR_INVALID, "iqhip_newton_branch: bad bounds / tolerance / step count");
-    if (e && !e->shards.empty()) {
-        iqhip_branch_end none = {0, -1, 0};
-        return sharded::optimize_branch(e, nullptr, 0, false, none, none, xguess, x1, x2, xacc, max_steps, nullptr, optx,
-                                        d2l, nsteps);
-    }
-    int rc = check_ready(e);
-    if (rc) return rc;
-    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, "iqhip_newton_branch: theta not computed");
-    if (newton_use_chain(e)) {
-        e->path_counts[IQHIP_PATH_NEWTON_CHAIN]++;
-        return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
-    }
-    HIPCHK(launch_newton(e, xguess, x1, x2, xacc, max_steps, e->d_result));
-    e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
-    rc = read_result(e, 4);
-    if (rc) return rc;
-    const int status = (int)e->h_result[3];
-    if (status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-    if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-    if (status == 4) {  // the grid barrier gave up (another kernel held the CUs): the chain needs no barrier
-        (void)hipStreamSynchronize(e->stream);
-        e->path_counts[IQHIP_PATH_NEWTON_FALLBACK]++;
-        return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
-    }
-    if (optx) *optx = e->h_result[0];
-    if (d2l) *d2l = e->h_result[1];
-    if (nsteps) *nsteps = (int)e->h_result[2];
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, int nops, iqhip_branch_end a,
-                                     iqhip_branch_end b, double xguess, double x1, double x2, double xacc,
-                                     int max_steps, double *sum_scale, double *optx, double *d2l, int *nsteps) {
-    if (!(x1 >= 0.0) || !(x2 > x1) || !(xacc > 0.0) || max_steps < 1 || !(xguess >= 0.0))
-        return fail(IQHIP_ERR_INVALID, "iqhip_optimize_branch: bad bounds / tolerance / step count");
-    if (e && !e->shards.empty())
-        return sharded::optimize_branch(e, ops, nops, true, a, b, xguess, x1, x2, xacc, max_steps, sum_scale, optx, d2l,
-                                        nsteps);
-    iqhip_branch_end none = {0, -1, 0};
-    int rc = IQHIP_OK;
-    if (e && newton_use_chain(e)) {
-
-        // sharded rank: node updates (their sum_scale rows all-reduced), theta, then the enqueued Newton chain
-        if (nops > 0) {
-            rc = iqhip_update_partials(e, ops, nops, sum_scale);
-            if (rc) return rc;
-        }
-        rc = iqhip_compute_theta(e, a, b);
-        if (rc) return rc;
-        e->path_counts[IQHIP_PATH_NEWTON_CHAIN]++;
-        return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
-    }
-    // two launches per branch: the pending node updates, then one kernel that sums their sum_scale rows,
-    // builds theta during its first derivative evaluation and runs the whole Newton-Raphson loop
-    if (nops > 0) rc = submit_traverse(e, ops, nops, false, none, none, 0.0, /*skip_reduce=*/true);
-    else rc = check_ready(e);
-    if (rc) return rc;
-    if (nops + 6 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
-    DevBranch br;
-    rc = build_branch(e, a, b, 0.0, -1, &br);
-    if (rc) return rc;
-    e->theta_valid = true;
-    e->theta_a_sc = br.a_sc;
-    e->theta_b_sc = br.b_sc;
-    double *out = e->d_result + 2 + nops;
-    HIPCHK(launch_newton(e, xguess, x1, x2, xacc, max_steps, out, &br, nops, (int)e->ntiles * e->lane_split));
-    e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
-    rc = read_result(e, 2 + nops + 4);
-    if (rc) return rc;
-    if (sum_scale)
-        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result[2 + k];
-    const double *r = e->h_result + 2 + nops;
-    const int status = (int)r[3];
-    if (status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-    if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-    if (status == 4) {  // grid barrier gave up: theta was built by the first evaluation, finish with the chain
-        (void)hipStreamSynchronize(e->stream);
-        e->path_counts[IQHIP_PATH_NEWTON_FALLBACK]++;
-        return newton_chain(e, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
-    }
-    if (optx) *optx = r[0];
-    if (d2l) *d2l = r[1];
-    if (nsteps) *nsteps = (int)r[2];
-    return IQHIP_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// A whole branch-length sweep -- PhyloTree::optimizeAllBranches' loop over optimizeOneBranch (phylotree.cpp:2252-2332,
-// 2148-2192) -- in ONE submission.  Step j = {the node updates that are pending at both ends of branch j, theta, the
-// Newton solve, the diverged-solve rule}; a child branch that an earlier step of the sweep optimised has its length read
-// from device memory (sweep_len[step]), where that step's Newton kernel left it, so nothing comes back to the host
-// between steps: 2 launches per step are enqueued back to back and the host reads one result block per sweep.
-// The caller builds the steps as if every step changed its branch (optimizeOneBranch's clearReversePartialLh on both
-// sides); a step that ends where it started only makes the later steps recompute vectors that were still valid.
-// ---------------------------------------------------------------------------------------
-static int sweep_resolve_ops(const iqhip_sweep_step &st, const iqhip_branch_result *results, std::vector<iqhip_node_op> &ops) {
-    ops.assign(st.ops, st.ops + st.nops);
-    if (st.len_from)
-        for (int k = 0; k < st.nops; k++) {
-            if (st.len_from[2 * k] >= 0) ops[k].left_len = results[st.len_from[2 * k]].optx;
-            if (st.len_from[2 * k + 1] >= 0) ops[k].right_len = results[st.len_from[2 * k + 1]].optx;
-        }
-    return IQHIP_OK;
-}
-
-// the same sweep one step at a time (a host round trip per step): sharded engines and engines with a communicator, where
-// every Newton step contains an all-reduce; +ASC; and the remainder of a sweep whose grid-wide exchange timed out
-static int sweep_sequential(iqhip_engine *e, const iqhip_sweep_step *steps, int first, int nsteps, double x1, double x2,
-                            double xacc, int max_steps, double diverge_frac, double *sum_scale, size_t ss_off,
-                            iqhip_branch_result *results) {
-    e->path_counts[IQHIP_PATH_SWEEP_SEQUENTIAL]++;
-    std::vector<iqhip_node_op> ops;
-    for (int j = first; j < nsteps; j++) {
-        const iqhip_sweep_step &st = steps[j];
-        sweep_resolve_ops(st, results, ops);
-        iqhip_branch_result &r = results[j];
-        r.status = 0;
-        r.lnl = 0.0;
-        int rc = iqhip_optimize_branch(e, ops.empty() ? nullptr : ops.data(), st.nops, st.a, st.b, st.xguess, x1, x2, xacc, max_steps,
-                                       sum_scale ? sum_scale + ss_off : nullptr, &r.optx, &r.d2l, &r.nsteps);
-        if (rc) return rc;
-        if (diverge_frac > 0.0 && r.optx > diverge_frac * x2) {   // phylotree.cpp:2167-2176
-            double opt_lh = 0.0, orig_lh = 0.0;
-            rc = iqhip_lnl_from_theta(e, r.optx, &opt_lh);
-            if (!rc) rc = iqhip_lnl_from_theta(e, st.xguess, &orig_lh);
-            if (rc) return rc;
-            if (orig_lh > opt_lh) r.optx = st.xguess;
-            r.status = 5;   // (informational: the rule was applied)
-        }
-        ss_off += (size_t)st.nops;
-    }
-    return IQHIP_OK;
-}
-
-// 4-state engines: the whole sweep as ONE launch of the persistent kernel k_sweep4 (kernels_sweep.hip) + one k_reduce for
-// the sum_scale rows; the host only resolves keys into descriptors, copies them down once and reads one result block
-static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int nsteps, size_t total_ops, double x1, double x2,
-                             double xacc, int max_steps, double diverge_frac, double *sum_scale, iqhip_branch_result *results) {
-    static const bool dbg = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
-    timespec t0, t1, t2;
-    if (dbg) clock_gettime(CLOCK_MONOTONIC, &t0);
-    const size_t bytes_ops = sizeof(SweepOp) * total_ops, bytes_steps = sizeof(SweepStep) * (size_t)nsteps;
-    const size_t need = bytes_ops + bytes_steps;
-    if (need > e->sweep_desc_cap) {
-        const size_t cap = need * 2 + 4096;
-        HIPCHK(regrow(e, &e->d_sweep_desc, &e->sweep_desc_cap, 0, cap));   // (sweep_desc_cap: once the host copy has grown too)
-        if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
-        e->h_sweep_desc = nullptr;
-        HIPCHK(hipHostMalloc((void **)&e->h_sweep_desc, cap));
-        e->sweep_desc_cap = cap;
-    }
-    SweepOp *hops = reinterpret_cast<SweepOp *>(e->h_sweep_desc);
-    SweepStep *hsteps = reinterpret_cast<SweepStep *>(e->h_sweep_desc + bytes_ops);
-    size_t row = 0;
-    for (int j = 0; j < nsteps; j++) {
-        const iqhip_sweep_step &st = steps[j];
-        SweepStep &hs = hsteps[j];
-        hs.op_begin = (int32_t)row;
-        hs.nops = st.nops;
-        hs.xguess = st.xguess;
-        for (int k = 0; k < st.nops; k++, row++) {
-            const iqhip_node_op &o = st.ops[k];
-            SweepOp &d = hops[row];
-            memset(&d, 0, sizeof d);
-            if (!(o.left_len >= 0.0) || !(o.right_len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
-            const uint8_t *lst, *rst;
-            int32_t lk, rk;
-            int rc = resolve_child(e, o.left_key, o.left_leaf, -1, &d.lv, &d.lsc, &lst, &lk);
-            if (rc) return rc;
-            rc = resolve_child(e, o.right_key, o.right_leaf, -1, &d.rv, &d.rsc, &rst, &rk);
-            if (rc) return rc;
-            d.ls = lst ? lst : e->d_states;
-            d.rs = rst ? rst : e->d_states;
-            int didx;
-            rc = slab_for_key(e, o.dst_key, true, &didx);
-            if (rc) return rc;
-            d.dst = e->slabs[didx].plh;
-            d.dst_sc = e->slabs[didx].sc;
-            if (d.lv == d.dst || d.rv == d.dst) return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
-            d.llen = o.left_len;
-            d.rlen = o.right_len;
-            d.llen_step = st.len_from ? st.len_from[2 * k] : -1;
-            d.rlen_step = st.len_from ? st.len_from[2 * k + 1] : -1;
-            d.no_scale = (o.flags & IQHIP_OP_NO_SCALE) ? 1 : (((o.flags & IQHIP_OP_SCALAR_RULE) || e->scalar_rule_all) ? 2 : 0);
-            d.row = (int32_t)row;
-        }
-        int rc = build_branch(e, st.a, st.b, 0.0, -1, &hs.br);
-        if (rc) return rc;
-    }
-    const int grid = sweep4_grid(e), nwaves = grid * sweep4_waves(e);
-    const size_t slab_need = total_ops * (size_t)nwaves + 1024;
-    if ((int64_t)total_ops * nwaves > e->slab_cap) HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, slab_need, slab_need));
-    const size_t posts_need = (size_t)2 * kNewtonPostEpochs * grid * 2;
-    if (posts_need > e->sweep_posts_cap) HIPCHK(regrow(e, &e->d_sweep_posts, &e->sweep_posts_cap, posts_need, posts_need));
-    HIPCHK(hipMemcpyAsync(e->d_sweep_desc, e->h_sweep_desc, need, hipMemcpyHostToDevice, e->stream));
-    if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts, 0xFF, posts_need * sizeof(double), e->stream));
-    double *out = e->d_result + total_ops;      // (rows [0, total_ops) receive the sum_scale sums from k_reduce)
-    memset(e->h_result + total_ops, 0, sizeof(double) * 6 * (size_t)nsteps);
-    e->path_counts[IQHIP_PATH_SWEEP_PERSISTENT]++;
-    HIPCHK(launch_sweep4(e, reinterpret_cast<const SweepOp *>(e->d_sweep_desc),
-                         reinterpret_cast<const SweepStep *>(e->d_sweep_desc + bytes_ops), nsteps, x1, x2, xacc, max_steps,
-                         diverge_frac * x2, e->d_sweep_posts, out));
-    HIPCHK(launch_reduce(e, 0, (int)total_ops, nwaves));
-    const DevBranch &last = hsteps[nsteps - 1].br;
-    e->theta_valid = true;
-    e->theta_a_sc = last.a_sc;
-    e->theta_b_sc = last.b_sc;
-    e->plan_cache.version = 0;
-    if (dbg) clock_gettime(CLOCK_MONOTONIC, &t1);
-    int rc = read_result(e, (int)(total_ops + 6 * (size_t)nsteps));
-    if (rc) return rc;
-    if (dbg) {
-        clock_gettime(CLOCK_MONOTONIC, &t2);
-        fprintf(stderr, "[iqhip] persistent sweep of %d steps (%zu node updates): descriptors + enqueue %.1f us, wait %.1f us\n", nsteps,
-                total_ops, (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3,
-                (t2.tv_sec - t1.tv_sec) * 1e6 + (t2.tv_nsec - t1.tv_nsec) * 1e-3);
-    }
-    if (sum_scale)
-        for (size_t k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[k];
-    size_t ss = 0;
-    for (int j = 0; j < nsteps; j++) {
-        const double *o = e->h_result + total_ops + 6 * (size_t)j;
-        const int status = (int)o[3];
-        if (status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-        if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-        if (status == 4) {   // the exchange between the workgroups gave up: finish from here one step at a time
-            (void)hipStreamSynchronize(e->stream);
-            return sweep_sequential(e, steps, j, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, ss, results);
-        }
-        results[j].optx = o[0];
-        results[j].d2l = o[1];
-        results[j].nsteps = (int)o[2];
-        results[j].status = o[4] != 0.0 ? 5 : 0;
-        results[j].lnl = 0.0;
-        ss += (size_t)steps[j].nops;
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *steps, int nsteps, double x1, double x2,
-                                    double xacc, int max_steps, double diverge_frac, double *sum_scale,
-                                    iqhip_branch_result *results) {
-    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
-    if (!steps || !results || nsteps < 1) return fail(IQHIP_ERR_INVALID, "iqhip_optimize_sweep: bad step array");
-    if (!(x1 >= 0.0) || !(x2 > x1) || !(xacc > 0.0) || max_steps < 1 || !(diverge_frac >= 0.0) || diverge_frac >= 1.0)
-        return fail(IQHIP_ERR_INVALID, "iqhip_optimize_sweep: bad bounds / tolerance / step count");
-    size_t total_ops = 0;
-    for (int j = 0; j < nsteps; j++) {
-        const iqhip_sweep_step &st = steps[j];
-        if (st.nops < 0 || (st.nops > 0 && !st.ops)) return fail(IQHIP_ERR_INVALID, "bad ops array in a sweep step");
-        if (!(st.xguess >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_optimize_sweep: bad starting length");
-        if (st.len_from)
-            for (int q = 0; q < 2 * st.nops; q++)
-                if (st.len_from[q] >= j) return fail(IQHIP_ERR_INVALID, "a sweep step may only use the lengths of earlier steps");
-        total_ops += (size_t)st.nops;
-    }
-    if (!e->shards.empty() || e->comm || e->n_unobs > 0 || !e->sweep_one_submission || newton_use_chain(e) ||
-        2 + total_ops + 6 * (size_t)nsteps > (size_t)e->result_cap || e->d_result != e->d_result_own)
-        return sweep_sequential(e, steps, 0, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, 0, results);
-    int rc = check_ready(e);
-    if (rc) return rc;
-    if (e->sweep_persistent && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
-        return sweep_persistent4(e, steps, nsteps, total_ops, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results);
-    if (!e->h_plan_arena) {
-        e->plan_arena_cap = 1 << 20;
-        if (hipHostMalloc((void **)&e->h_plan_arena, e->plan_arena_cap) != hipSuccess) { e->h_plan_arena = nullptr; e->plan_arena_cap = 0; }
-    }
-    struct ArenaScope {   // plan uploads of this sweep go through the arena; whatever happens, switched off on return
-        iqhip_engine *e;
-        explicit ArenaScope(iqhip_engine *e_) : e(e_) { e->plan_arena_on = e->h_plan_arena != nullptr; e->plan_arena_used = 0; }
-        ~ArenaScope() { e->plan_arena_on = false; }
-    } arena_scope(e);
-    e->path_counts[IQHIP_PATH_SWEEP_PER_STEP]++;
-    if (nsteps > e->sweep_len_cap) HIPCHK(regrow(e, &e->d_sweep_len, &e->sweep_len_cap, nsteps + 64, (size_t)nsteps + 64));
-    static const bool dbg = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
-    double t_trav = 0.0, t_newt = 0.0;
-    int n_uploaded = 0;
-    timespec ts0;
-    clock_gettime(CLOCK_MONOTONIC, &ts0);
-    // result block in the (host-mapped) result vector: per step its sum_scale rows, then {optx, d2l, nsteps, status, diverged, -}
-    std::vector<size_t> row_of(nsteps);
-    size_t row = 2;
-    std::vector<const double *> len_ptrs;
-    iqhip_branch_end none = {0, -1, 0};
-    for (int j = 0; j < nsteps; j++) {
-        const iqhip_sweep_step &st = steps[j];
-        row_of[j] = row;
-        if (st.nops > 0) {
-            const double *const *lp = nullptr;
-            if (st.len_from) {
-                len_ptrs.assign((size_t)2 * st.nops, nullptr);
-                bool any = false;
-                for (int q = 0; q < 2 * st.nops; q++)
-                    if (st.len_from[q] >= 0) { len_ptrs[q] = e->d_sweep_len + st.len_from[q]; any = true; }
-                if (any) lp = len_ptrs.data();
-            }
-            timespec ta, tb;
-            if (dbg) clock_gettime(CLOCK_MONOTONIC, &ta);
-            rc = submit_traverse(e, st.ops, st.nops, false, none, none, 0.0, /*skip_reduce=*/true, nullptr, lp);
-            if (rc) return rc;
-            if (dbg) { clock_gettime(CLOCK_MONOTONIC, &tb); t_trav += (tb.tv_sec - ta.tv_sec) * 1e6 + (tb.tv_nsec - ta.tv_nsec) * 1e-3; n_uploaded += e->plan.small ? 0 : 1; }
-        }
-        DevBranch br;
-        rc = build_branch(e, st.a, st.b, 0.0, -1, &br);
-        if (rc) return rc;
-        e->theta_valid = true;
-        e->theta_a_sc = br.a_sc;
-        e->theta_b_sc = br.b_sc;
-        NewtonSweepStep sw;
-        sw.len_out = e->d_sweep_len + j;
-        sw.rows_base = e->d_result + row;
-        sw.diverge_x = diverge_frac * x2;
-        sw.publish = (j == nsteps - 1);
-        timespec tc, td;
-        if (dbg) clock_gettime(CLOCK_MONOTONIC, &tc);
-        HIPCHK(launch_newton(e, st.xguess, x1, x2, xacc, max_steps, e->d_result + row + st.nops, &br, st.nops,
-                             (int)e->ntiles * e->lane_split, &sw));
-        e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
-        if (dbg) { clock_gettime(CLOCK_MONOTONIC, &td); t_newt += (td.tv_sec - tc.tv_sec) * 1e6 + (td.tv_nsec - tc.tv_nsec) * 1e-3; }
-        row += (size_t)st.nops + 6;
-    }
-    timespec ts1;
-    if (dbg) clock_gettime(CLOCK_MONOTONIC, &ts1);
-    rc = read_result(e, (int)row);
-    if (rc) return rc;
-    if (dbg) {
-        timespec ts2;
-        clock_gettime(CLOCK_MONOTONIC, &ts2);
-        fprintf(stderr, "[iqhip] sweep of %d steps (%d plans uploaded, the others in the kernel arguments): submit_traverse %.1f us (build_plan %.1f us since the last report), launch_newton %.1f us; enqueue %.1f us, wait %.1f us\n", nsteps, n_uploaded, t_trav, g_dbg_build_us, t_newt,
-                (ts1.tv_sec - ts0.tv_sec) * 1e6 + (ts1.tv_nsec - ts0.tv_nsec) * 1e-3,
-                (ts2.tv_sec - ts1.tv_sec) * 1e6 + (ts2.tv_nsec - ts1.tv_nsec) * 1e-3);
-        g_dbg_build_us = 0.0;
-    }
-    size_t ss = 0;
-    for (int j = 0; j < nsteps; j++) {
-        const iqhip_sweep_step &st = steps[j];
-        const double *r = e->h_result + row_of[j];
-        if (sum_scale)
-            for (int k = 0; k < st.nops; k++) sum_scale[ss + k] = r[k];
-        const double *o = r + st.nops;
-        const int status = (int)o[3];
-        if (status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-        if (status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-        if (status == 4) {
-            // the grid-wide exchange of this step's solve gave up (another kernel held the CUs): its length and everything
-            // after it is void -- finish the sweep from here one step at a time (the chain form needs no co-residency)
-            (void)hipStreamSynchronize(e->stream);
-            return sweep_sequential(e, steps, j, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, ss, results);
-        }
-        results[j].optx = o[0];
-        results[j].d2l = o[1];
-        results[j].nsteps = (int)o[2];
-        results[j].status = o[4] != 0.0 ? 5 : 0;
-        results[j].lnl = 0.0;
-        ss += (size_t)st.nops;
-    }
-    return IQHIP_OK;
-}
-
-// ---------------------------------------------------------------------------------------
-// Batched chain: iqhip_optimize_branch_batch on pattern shards.  The m tasks of a chunk advance side by side: per Newton
-// step ONE derivative launch (grid.y = task, branch length read from the task's device-resident state machine), ONE
-// k_reduce over 2m slab rows, ONE all-reduce of 2m doubles, ONE update kernel (thread = task); tasks that have converged
-// do nothing.  Identical sums on every rank => identical iterates, so all ranks leave the loop together.
-// ---------------------------------------------------------------------------------------
-namespace iqhip {
-static BatchChain batch_chain_of(const iqhip_engine *e, int m) {
-    return BatchChain{e->d_theta_batch, (size_t)e->nptn_pad * e->block, e->d_bstates, m};
-}
-
-int eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, const NewtonState *init) {
-    int rc = check_ready(e);
-    if (rc) return rc;
-    if (2 * m > e->result_cap) return set_error(IQHIP_ERR_INVALID, "too many tasks in one chunk");
-    rc = ensure_slab_rows(e, std::max(5, 2 * m));
-    if (rc) return rc;
-    const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)m * theta_stride > e->theta_batch_cap)
-        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)m * theta_stride, (size_t)m * theta_stride));
-    if (m > e->bstates_cap) HIPCHK(regrow(e, &e->d_bstates, &e->bstates_cap, m, m));
-    for (int t = 0; t < m; t++) {
-        DevBranch br;
-        rc = build_branch(e, tasks[t].a, tasks[t].b, 0.0, -1, &br);
-        if (rc) return rc;
-        double *slot = e->d_theta_batch + (size_t)t * theta_stride;
-        if (e->mfma) HIPCHK(launch_stream_mfma(e, 1, &br, 0.0, (int)e->ntiles, nullptr, -1, slot));
-        else HIPCHK(launch_theta4(e, br, slot));
-    }
-    return eng_batch_states_write(e, m, init);
-}
-
-int eng_batch_states_write(iqhip_engine *e, int m, const NewtonState *in) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    // (pageable source: the copy has left the host buffer when the call returns)
-    if (hipMemcpyAsync(e->d_bstates, in, sizeof(NewtonState) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "batched chain: state upload failed");
-    return IQHIP_OK;
-}
-
-int eng_batch_states_read(iqhip_engine *e, int m, NewtonState *out) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    if (hipMemcpyAsync(out, e->d_bstates, sizeof(NewtonState) * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "batched chain: state read failed");
-    e->staging_busy = false;
-    return IQHIP_OK;
-}
-
-int eng_batch_eval_enqueue(iqhip_engine *e, int m) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    const BatchChain bc = batch_chain_of(e, m);
-    const int nwaves = (int)e->ntiles;
-    const hipError_t s = e->mfma ? launch_stream_mfma(e, 2, nullptr, 0.0, nwaves, nullptr, -1, nullptr, &bc)
-                                 : launch_derv4(e, 0.0, nwaves, nullptr, &bc);
-    if (s != hipSuccess || launch_reduce(e, 0, 2 * m, nwaves) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "batched chain: launch failed");
-    return IQHIP_OK;
-}
-
-int eng_batch_update_enqueue(iqhip_engine *e, int m) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    if (launch_newton_state_update_batch(e, e->d_bstates, m) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "batched chain: launch failed");
-    return IQHIP_OK;
-}
-
-int eng_batch_lnl_enqueue(iqhip_engine *e, int m) {
-    if (use_device(e) != hipSuccess) return set_error(IQHIP_ERR_HIP, "hipSetDevice");
-    const BatchChain bc = batch_chain_of(e, m);
-    const int nwaves = (int)e->ntiles;
-    const hipError_t s = e->mfma ? launch_stream_mfma(e, 3, nullptr, 0.0, nwaves, nullptr, -1, nullptr, &bc)
-                                 : launch_lnl_theta4(e, 0.0, nwaves, &bc);
-    if (s != hipSuccess || launch_reduce(e, 0, 2 * m, nwaves) != hipSuccess)
-        return set_error(IQHIP_ERR_HIP, "batched chain: launch failed");
-    return IQHIP_OK;
-}
-}  // namespace iqhip
-
-// tasks per chunk of the batched chain: the same on every rank (the ranks' collectives must pair up), so a fixed number
-// and not what the free memory of this device suggests
-static int batch_chain_chunk(int ntasks) {
-    int chunk = std::min(ntasks, 64);
-    if (const char *bc = getenv("IQHIP_BATCH_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(bc)));
-    return chunk;
-}
-
-static int batch_task_check(const iqhip_branch_task &k) {
-    if (k.nops < 0 || (k.nops > 0 && !k.ops)) return fail(IQHIP_ERR_INVALID, "bad ops array in a task");
-    if (!(k.x1 >= 0.0) || !(k.x2 > k.x1) || !(k.xacc > 0.0) || k.max_steps < 1 || !(k.xguess >= 0.0))
-        return fail(IQHIP_ERR_INVALID, "iqhip_optimize_branch_batch: bad bounds / tolerance / step count");
-    return IQHIP_OK;
-}
-
-static int batch_task_results(const std::vector<NewtonState> &st, int m, iqhip_branch_result *results) {
-    for (int t = 0; t < m; t++) {
-        if (st[t].status == 2) return fail(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-        if (st[t].status == 3) return fail(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-        results[t].optx = st[t].result;
-        results[t].d2l = st[t].d2l;
-        results[t].nsteps = st[t].neval;
-        results[t].status = 0;
-    }
-    return IQHIP_OK;
-}
-
-// a rank with a communicator: node updates of all tasks in one submission, then the batched chain
-static int optimize_branch_batch_comm(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks, double *sum_scale,
-                                      iqhip_branch_result *results) {
-    int rc = check_ready(e);
-    if (rc) return rc;
-    std::vector<iqhip_node_op> all;
-    std::vector<int> segs(ntasks);
-    for (int t = 0; t < ntasks; t++) {
-        rc = batch_task_check(tasks[t]);
-        if (rc) return rc;
-        segs[t] = tasks[t].nops;
-        all.insert(all.end(), tasks[t].ops, tasks[t].ops + tasks[t].nops);
-    }
-    const int total_ops = (int)all.size();
-    if (total_ops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
-    iqhip_branch_end none = {0, -1, 0};
-    if (total_ops > 0) {
-        rc = submit_traverse(e, all.data(), total_ops, false, none, none, 0.0, /*skip_reduce=*/false, &segs);
-        if (rc) return rc;
-        rc = comm_allreduce(e, 2 + total_ops);
-        if (rc) return rc;
-        rc = read_result(e, 2 + total_ops);
-        if (rc) return rc;
-        if (sum_scale)
-            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[2 + k];
-    }
-    const int chunk = batch_chain_chunk(ntasks);
-    std::vector<NewtonState> st((size_t)chunk);
-    for (int first = 0; first < ntasks; first += chunk) {
-        const int m = std::min(chunk, ntasks - first);
-        int max_steps = 1;
-        for (int t = 0; t < m; t++) {
-            const iqhip_branch_task &k = tasks[first + t];
-            newton_init(st[t], k.xguess, k.x1, k.x2, k.xacc, k.max_steps);
-            max_steps = std::max(max_steps, k.max_steps);
-        }
-        rc = eng_batch_prepare(e, tasks + first, m, st.data());
-        if (rc) return rc;
-        int enq = 0;
-        for (;;) {
-            const int steps = enq == 0 ? std::min(4, max_steps + 1) : 2;
-            for (int k = 0; k < steps; k++) {
-                rc = eng_batch_eval_enqueue(e, m);
-                if (!rc) rc = comm_allreduce(e, 2 * m);
-                if (!rc) rc = eng_batch_update_enqueue(e, m);
-                if (rc) return rc;
-            }
-            enq += steps;
-            rc = eng_batch_states_read(e, m, st.data());
-            if (rc) return rc;
-            bool all_done = true;
-            for (int t = 0; t < m; t++) all_done = all_done && st[t].done;
-            if (all_done) break;
-            if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
-        }
-        rc = batch_task_results(st, m, results + first);
-        if (rc) return rc;
-        // lnL of every task at its accepted length: one launch, one reduction, one all-reduce
-        rc = eng_batch_lnl_enqueue(e, m);
-        if (!rc) rc = comm_allreduce(e, 2 * m);
-        if (!rc) rc = read_result(e, 2 * m);
-        if (rc) return rc;
-        std::vector<double> lnl((size_t)m);
-        for (int t = 0; t < m; t++) lnl[t] = e->h_result[2 * t];
-        for (int t = 0; t < m; t++) {
-            results[first + t].lnl = lnl[t];
-            if (isnan(lnl[t]) || isinf(lnl[t])) {   // phylokernel.h:1091-1109: redo this task alone (same decision on every rank)
-                const iqhip_branch_task &k = tasks[first + t];
-                rc = iqhip_compute_theta(e, k.a, k.b);
-                if (!rc) rc = iqhip_lnl_from_theta(e, results[first + t].optx, &results[first + t].lnl);
-                if (rc) return rc;
-            }
-        }
-    }
-    return IQHIP_OK;
-}
-
-// iqhip_optimize_branch_batch, one task after the other through the chain form (IQHIP_BATCH_SEQUENTIAL=1: the form the
-// batched chain is tested against)
-static int optimize_branch_batch_sequential(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks,
-                                            double *sum_scale, iqhip_branch_result *results) {
-    size_t off = 0;
-    for (int t = 0; t < ntasks; t++) {
-        const iqhip_branch_task &k = tasks[t];
-        if (k.nops < 0 || (k.nops > 0 && !k.ops)) return fail(IQHIP_ERR_INVALID, "bad ops array in a task");
-        iqhip_branch_result &r = results[t];
-        r.status = 0;
-        int rc = iqhip_optimize_branch(e, k.ops, k.nops, k.a, k.b, k.xguess, k.x1, k.x2, k.xacc, k.max_steps,
-                                       sum_scale ? sum_scale + off : nullptr, &r.optx, &r.d2l, &r.nsteps);
-        if (rc) return rc;
-        rc = iqhip_lnl_from_theta(e, r.optx, &r.lnl);
-        if (rc) return rc;
-        off += (size_t)k.nops;
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks,
-                                           double *sum_scale, iqhip_branch_result *results) {
-    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
-    if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, "bad task array");
-    const char *seq_env = getenv("IQHIP_BATCH_SEQUENTIAL");   // (read per call: the tests compare the two forms)
-    const bool sequential = (seq_env && atoi(seq_env) != 0) || e->asc_active;   // (+ASC: 5-row results, one task at a time)
-    if (!e->shards.empty())
-        return sequential ? optimize_branch_batch_sequential(e, tasks, ntasks, sum_scale, results)
-                          : sharded::optimize_branch_batch(e, tasks, ntasks, sum_scale, results);
-    if (e->comm)
-        return sequential ? optimize_branch_batch_sequential(e, tasks, ntasks, sum_scale, results)
-                          : optimize_branch_batch_comm(e, tasks, ntasks, sum_scale, results);
-    int rc = check_ready(e);
-    if (rc) return rc;
-    if (e->n_unobs > 0) return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_optimize_branch_batch: +ASC is not supported");
-    std::vector<iqhip_node_op> all;
-    std::vector<int> segs(ntasks);
-    for (int t = 0; t < ntasks; t++) {
-        const iqhip_branch_task &k = tasks[t];
-        if (k.nops < 0 || (k.nops > 0 && !k.ops)) return fail(IQHIP_ERR_INVALID, "bad ops array in a task");
-        if (!(k.x1 >= 0.0) || !(k.x2 > k.x1) || !(k.xacc > 0.0) || k.max_steps < 1 || !(k.xguess >= 0.0))
-            return fail(IQHIP_ERR_INVALID, "iqhip_optimize_branch_batch: bad bounds / tolerance / step count");
-        segs[t] = k.nops;
-        all.insert(all.end(), k.ops, k.ops + k.nops);
-    }
-    const int total_ops = (int)all.size();
-    if (total_ops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
-    iqhip_branch_end none = {0, -1, 0};
-    if (total_ops > 0) {
-        rc = submit_traverse(e, all.data(), total_ops, false, none, none, 0.0, /*skip_reduce=*/false, &segs);
-        if (rc) return rc;
-    }
-    // workgroups per task: every workgroup of a launch must be resident (grid barrier inside each task)
-    // ... which bounds the batch by what fits the chip at once: 3 workgroups per CU (k_newton_batch: 125 VGPRs, i.e.
-    // four waves per SIMD would fit exactly -- keep a margin), fewer when its LDS (3 val arrays of a block) says so
-    const size_t newton_lds = (size_t)(3 * e->block + 8) * sizeof(double) + 64;
-    const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (size_t)(150 * 1024) / newton_lds));
-    const int capacity = e->num_cus * wg_per_cu;
-    const int wgs_needed = (int)std::max<int64_t>(1, (e->ntiles + 3) / 4);
-    int chunk = std::min(ntasks, capacity);             // tasks per launch
-    {   // every task of a launch owns a theta buffer: keep them within a quarter of the free device memory and
-        // run larger batches in several launches (protein+G4 at 50k patterns: 32 MB per task)
-        size_t free_b = 0, total_b = 0;
-        const size_t per_task = (size_t)e->nptn_pad * e->block * sizeof(double);
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t have = e->theta_batch_cap * sizeof(double);
-            const size_t room = (free_b + have) / 4;
-            const size_t fit = std::max<size_t>(1, room / std::max<size_t>(1, per_task));
-            if ((size_t)chunk > fit) chunk = (int)fit;
-        }
-    }
-    if (const char *bc = getenv("IQHIP_BATCH_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(bc)));
-    const int G = std::max(1, std::min(wgs_needed, capacity / chunk));
-    const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)chunk * theta_stride > e->theta_batch_cap)
-        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)chunk * theta_stride, (size_t)chunk * theta_stride));
-    if (chunk > e->batch_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        void *old[] = {e->d_batch_partials, e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks};
-        for (void *p : old)
-            if (p) hipFree(p);
-        e->d_batch_partials = e->d_batch_out = nullptr;
-        e->d_batch_barriers = nullptr;
-        e->d_batch_tasks = nullptr;
-        e->batch_cap = 0;
-        HIPCHK(dmalloc(&e->d_batch_partials, (size_t)chunk * 4 * (e->num_cus * 4)));
-        HIPCHK(dmalloc(&e->d_batch_out, (size_t)chunk * 6));
-        HIPCHK(dmalloc(&e->d_batch_barriers, (size_t)2 * chunk));
-        HIPCHK(hipMalloc(&e->d_batch_tasks, newton_task_bytes() * (size_t)chunk));
-        HIPCHK(hipMemsetAsync(e->d_batch_barriers, 0, sizeof(unsigned int) * 2 * chunk, e->stream));
-        e->batch_cap = chunk;
-    }
-    std::vector<char> host_tasks(newton_task_bytes() * (size_t)chunk);
-    std::vector<double> out((size_t)chunk * 6);
-    for (int first = 0; first < ntasks; first += chunk) {
-        const int m = std::min(chunk, ntasks - first);
-        for (int t = 0; t < m; t++) {
-            const iqhip_branch_task &k = tasks[first + t];
-            DevBranch br;
-            rc = build_branch(e, k.a, k.b, 0.0, -1, &br);
-            if (rc) return rc;
-            newton_task_fill(host_tasks.data() + newton_task_bytes() * (size_t)t, br, k.xguess, k.x1, k.x2, k.xacc,
-                             k.max_steps);
-        }
-        HIPCHK(hipMemcpyAsync(e->d_batch_tasks, host_tasks.data(), newton_task_bytes() * (size_t)m,
-                              hipMemcpyHostToDevice, e->stream));
-        // posted exchange of the tasks' partial sums (k_newton_batch): slots of this launch, [task][evaluation][workgroup][2]
-        double *posts = nullptr, *posts_other = nullptr;
-        size_t posts_other_used = 0;
-        int post_epochs = 0;
-        if (G > 1 && e->newton_posts) {
-            int max_steps = 1;
-            for (int t = 0; t < m; t++) max_steps = std::max(max_steps, tasks[first + t].max_steps);
-            post_epochs = max_steps + 4;   // derivative evaluations + the lnL pass(es)
-            const size_t need = (size_t)m * post_epochs * G * 2;
-            if (need > e->batch_posts_cap) {
-                HIPCHK(regrow(e, &e->d_batch_posts, &e->batch_posts_cap, need, 2 * need));   // (two launch parities)
-                HIPCHK(hipMemsetAsync(e->d_batch_posts, 0xFF, 2 * need * sizeof(double), e->stream));
-                e->batch_posts_used[0] = e->batch_posts_used[1] = 0;
-            }
-            const unsigned int pp = e->batch_post_launches & 1u;
-            e->batch_post_launches++;
-            posts = e->d_batch_posts + (size_t)pp * e->batch_posts_cap;
-            posts_other = e->d_batch_posts + (size_t)(1u - pp) * e->batch_posts_cap;
-            posts_other_used = e->batch_posts_used[1u - pp];
-            e->batch_posts_used[pp] = need;
-            e->batch_posts_used[1u - pp] = 0;   // (reset by this launch)
-        }
-        const unsigned int parity = e->batch_launches & 1u;
-        e->batch_launches++;
-        // this launch's arrival counters start at zero whatever the task counts of earlier launches were (a launch
-        // only clears the first m counters of the other parity, so a smaller batch in between leaves the rest dirty)
-        HIPCHK(hipMemsetAsync(e->d_batch_barriers + (size_t)parity * e->batch_cap, 0, sizeof(unsigned int) * (size_t)m,
-                              e->stream));
-        HIPCHK(launch_newton_batch(e, e->d_batch_tasks, m, G, e->d_theta_batch, theta_stride, e->d_batch_partials,
-                                   e->d_batch_barriers + (size_t)parity * e->batch_cap,
-                                   e->d_batch_barriers + (size_t)(1u - parity) * e->batch_cap, e->d_batch_out, posts, posts_other,
-                                   posts_other_used, post_epochs));
-        HIPCHK(hipMemcpyAsync(out.data(), e->d_batch_out, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToHost,
-                              e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));  // also: host_tasks / out are reused by the next chunk
-        for (int t = 0; t < m; t++) {
-            const double *o = &out[(size_t)t * 6];
-            iqhip_branch_result &r = results[first + t];
-            r.optx = o[0];
-            r.d2l = o[1];
-            r.nsteps = (int)o[2];
-            r.status = (int)o[3];
-            r.lnl = o[4];
-            if (r.status == 4) {
-                // the task's grid barrier gave up (its workgroups were not co-resident): redo this one task with the
-                // barrier-free chain form -- its node updates have run, so only theta + the solve + lnL remain
-                const iqhip_branch_task &k = tasks[first + t];
-                (void)hipStreamSynchronize(e->stream);
-                rc = iqhip_compute_theta(e, k.a, k.b);
-                if (!rc) rc = newton_chain(e, k.xguess, k.x1, k.x2, k.xacc, k.max_steps, &r.optx, &r.d2l, &r.nsteps);
-                if (!rc) rc = iqhip_lnl_from_theta(e, r.optx, &r.lnl);
-                if (rc) return rc;
-                r.status = 0;
-            }
-        }
-    }
-    if (total_ops > 0) {
-        rc = read_result(e, 2 + total_ops);
-        if (rc) return rc;
-        if (sum_scale)
-            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[2 + k];
-    }
     return IQHIP_OK;
 }
 

@@ -11,6 +11,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <time.h>
+#include <algorithm>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -296,6 +298,7 @@ struct iqhip_engine {
     int max_levels = 3;          // IQHIP_LEVELS: stages of units at most
     int mfma_lds_kb = -1;        // IQHIP_MFMA_LDS_KB: LDS per matrix-core workgroup (-1: by state count, plan.hip lds_budget)
     bool debug_plan = false;     // IQHIP_DEBUG_PLAN: print each plan's staging and parking to stderr
+    bool debug_sweep = false;    // IQHIP_DEBUG_SWEEP: print where a sweep's host and kernel time went to stderr
     std::string debug_break_plan;  // IQHIP_DEBUG_BREAK_PLAN (planning-only engines): break one descriptor on purpose
     iqhip::Plan plan;            // the current plan (plan.hip build_plan)
     iqhip::Slab dummy;           // valid target of unconditional prefetches
@@ -615,6 +618,7 @@ __device__ inline void fold_tail(const FoldArgs &F) {
 
 // engine.hip: records the calling thread's error text (iqhip_last_error) and returns `code`
 int set_error(int code, const std::string &msg);
+inline int fail(int code, const std::string &msg) { return set_error(code, msg); }
 // in a function that returns an IQHIP status: a failed HIP call returns IQHIP_ERR_HIP with the call's text
 #define HIPCHK(call)                                                                                           \
     do {                                                                                                       \
@@ -676,11 +680,79 @@ int comm_init_all(const std::vector<iqhip_engine *> &shards);
 void comm_destroy(iqhip_engine *e);
 int comm_use_device_result(iqhip_engine *e);  // switch the engine to a device-memory result vector
 
-// engine.hip internals the sharded front drives its shards with
-int eng_read_result(iqhip_engine *e, int ndoubles);   // D2H of the result vector (if it is device memory) + stream sync
-// node updates, asynchronous; segs: op counts of independent groups (each runs on its own workgroups)
-int eng_submit_updates(iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *segs);
+// engine.hip internals the solvers (solve.hip) and the sharded front drive an engine with
+// a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
+hipError_t use_device(const iqhip_engine *e);
+int check_ready(iqhip_engine *e);                     // model and alignment set, device selected
+int ensure_slab_rows(iqhip_engine *e, int nrows);     // the wave-partial slab holds nrows rows
+// enqueue: plan upload, K1, fused traversal (+ optional root lnL), fixed-order reduction (skip_reduce: the caller's next
+// kernel sums the slab); explicit_segs, len_ptrs: see build_plan
+int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, bool has_root, iqhip_branch_end a,
+                    iqhip_branch_end b, double len, bool skip_reduce = false, const std::vector<int> *explicit_segs = nullptr,
+                    const double *const *len_ptrs = nullptr);
+int read_result(iqhip_engine *e, int ndoubles);       // D2H of the result vector (if it is device memory) + stream sync
+void set_theta_branch(iqhip_engine *e, const DevBranch &br);   // theta is (being) built from this branch's two ends
 int eng_repair_lnl(iqhip_engine *e, double *lnl);     // phylokernel.h:848-866 on this engine's _pattern_lh -> its own sum
+extern double debug_build_us;                         // IQHIP_DEBUG_SWEEP: host time in build_plan since the last sweep report
+
+// IQHIP_DEBUG_SWEEP: host time in microseconds
+struct Stopwatch {
+    timespec t0;
+    void start() { clock_gettime(CLOCK_MONOTONIC, &t0); }
+    double us() const {
+        timespec t1;
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        return (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
+    }
+};
+
+// solve.hip -- the branch-length solvers: Newton on one branch, a whole sweep, the batched NNI evaluator
+// the pieces every form shares ...
+int newton_check_bounds(const char *entry, double xguess, double x1, double x2, double xacc, int max_steps);
+// the solver status every form reports: IQHIP_OK for 0, the reference's two failures for 2 (non-finite derivative) and
+// 3 (step limit); 4 (the kernel's exchange between workgroups gave up) is no error: *gave_up tells the caller, who runs
+// the fallback of its own form
+int newton_status(int status, bool *gave_up = nullptr);
+// what a solve hands back, from a result row {optx, d2l, nsteps, status, ..} of the kernels or from a state machine
+struct NewtonResult {
+    double optx, d2l;
+    int nsteps, status;
+    explicit NewtonResult(const double *row) : optx(row[0]), d2l(row[1]), nsteps((int)row[2]), status((int)row[3]) {}
+    explicit NewtonResult(const NewtonState &st) : optx(st.result), d2l(st.d2l), nsteps(st.neval), status(st.status) {}
+    void store(double *x, double *d, int *n) const {
+        if (x) *x = optx;
+        if (d) *d = d2l;
+        if (n) *n = nsteps;
+    }
+    void store(iqhip_branch_result &r) const { r.optx = optx; r.d2l = d2l; r.nsteps = nsteps; r.status = status; }
+};
+// The pacing of every enqueued Newton chain.  A typical solve converges in 3..5 evaluations, so that many steps are
+// enqueued before the first look at the state machine(s), then two at a time; steps enqueued after convergence do nothing.
+// step(): enqueue one evaluation + reduction + update; all_done(&done): read the state(s) back.  Both return a status.
+template <typename Step, typename AllDone>
+int drive_chain(int max_steps, Step &&step, AllDone &&all_done) {
+    for (int enq = 0;;) {
+        const int chunk = enq == 0 ? std::min(4, max_steps + 1) : 2;
+        for (int k = 0; k < chunk; k++) {
+            const int rc = step();
+            if (rc) return rc;
+        }
+        enq += chunk;
+        bool done = false;
+        const int rc = all_done(&done);
+        if (rc) return rc;
+        if (done) return IQHIP_OK;
+        if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
+    }
+}
+// ... of the batch: every task checked, its ops appended to `all`, their count to `segs`
+int batch_gather_ops(const iqhip_branch_task *tasks, int ntasks, std::vector<iqhip_node_op> &all, std::vector<int> &segs);
+// tasks per chunk of the batched chain: the same on every rank (the ranks' collectives must pair up), so a fixed number
+// and not what the free memory of a device suggests
+constexpr int kBatchChainChunk = 64;
+int batch_chunk(int chunk);   // ... clamped by IQHIP_BATCH_CHUNK (read per call)
+int batch_task_results(const std::vector<NewtonState> &st, int m, iqhip_branch_result *results);
+// Newton as a chain of enqueued steps, one piece at a time
 int newton_state_alloc(iqhip_engine *e);
 int newton_state_read(iqhip_engine *e);               // -> e->h_nstate (syncs the stream)
 int eng_newton_begin(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps);
@@ -696,7 +768,7 @@ int eng_batch_states_read(iqhip_engine *e, int m, NewtonState *out);        // (
 int eng_batch_states_write(iqhip_engine *e, int m, const NewtonState *in);
 
 // sharded.hip -- the single-process multi-device front (iqhip_create_sharded); every public entry point of
-// engine.hip forwards here when e->shards is non-empty
+// engine.hip and solve.hip forwards here when e->shards is non-empty
 namespace sharded {
 void destroy(iqhip_engine *p);
 int reserve(iqhip_engine *p, int nvectors);

@@ -418,10 +418,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
 
 // IQHIP_DEBUG_SWEEP: workgroup 0's split of the persistent kernel's time (100 MHz clock); the previous launch's figures are
 // printed when the next sweep is launched
-static unsigned long long *sweep_prof_buffer() {
-    static const bool dbg = getenv("IQHIP_DEBUG_SWEEP") != nullptr;
+static unsigned long long *sweep_prof_buffer(const iqhip_engine *e) {
     static unsigned long long *d_prof = nullptr;
-    if (!dbg) return nullptr;
+    if (!e->debug_sweep) return nullptr;
     if (!d_prof) {
         if (hipMalloc((void **)&d_prof, 8 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
         (void)hipMemset(d_prof, 0, 8 * sizeof(unsigned long long));
@@ -485,7 +484,7 @@ hipError_t launch_sweep4(iqhip_engine *e, const SweepOp *d_ops, const SweepStep 
     A.max_steps = max_steps;
     A.posts = posts;
     A.out = out;
-    A.prof = sweep_prof_buffer();
+    A.prof = sweep_prof_buffer(e);
     const bool reg = e->ntiles <= (int64_t)grid * waves;
     switch (e->ncat) {
         case 1: return launch_sweep_c<1>(e, A, grid, reg, waves);

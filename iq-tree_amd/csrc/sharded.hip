@@ -27,19 +27,29 @@ using namespace iqhip;
 namespace {
 int bad(int code, const std::string &msg) { return set_error(code, msg); }
 
+// f(shard) for every shard, until one fails
+template <typename F>
+int each_shard(iqhip_engine *p, F &&f) {
+    for (iqhip_engine *c : p->shards) {
+        const int rc = f(c);
+        if (rc) return rc;
+    }
+    return IQHIP_OK;
+}
+
 // sum of the shards' result vectors -> out[0..n)
 int reduce_results(iqhip_engine *p, int n, std::vector<double> &out) {
     out.assign((size_t)n, 0.0);
     if (p->reduce_mode == IQHIP_REDUCE_RCCL) {
         int rc = comm_group_allreduce(p->shards, n);
         if (rc) return rc;
-        rc = eng_read_result(p->shards[0], n);
+        rc = read_result(p->shards[0], n);
         if (rc) return rc;
         memcpy(out.data(), p->shards[0]->h_result, sizeof(double) * (size_t)n);
         return IQHIP_OK;
     }
     for (iqhip_engine *c : p->shards) {
-        int rc = eng_read_result(c, n);
+        int rc = read_result(c, n);
         if (rc) return rc;
         for (int i = 0; i < n; i++) out[i] += c->h_result[i];
     }
@@ -321,27 +331,20 @@ int optimize_branch(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool bu
             rc = eng_newton_begin(c, xguess, x1, x2, xacc, max_steps);
             if (rc) return rc;
         }
-        int enq = 0;
-        for (;;) {
-            const int chunk = enq == 0 ? std::min(4, max_steps + 1) : 2;
-            for (int k = 0; k < chunk; k++) {
-                for (iqhip_engine *c : p->shards) {
-                    rc = eng_newton_eval_enqueue(c);
-                    if (rc) return rc;
-                }
-                rc = comm_group_allreduce(p->shards, p->asc_active ? 5 : 2);
-                if (rc) return rc;
-                for (iqhip_engine *c : p->shards) {
-                    rc = eng_newton_update_enqueue(c);
-                    if (rc) return rc;
-                }
-            }
-            enq += chunk;
-            rc = newton_state_read(p->shards[0]);
-            if (rc) return rc;
-            if (p->shards[0]->h_nstate->done) break;
-            if (enq > max_steps + 2) return bad(IQHIP_ERR_INVALID, "Newton chain did not terminate");
-        }
+        rc = drive_chain(
+            max_steps,
+            [&] {   // every shard's evaluation, one grouped all-reduce, every shard's update
+                int rc = each_shard(p, eng_newton_eval_enqueue);
+                if (!rc) rc = comm_group_allreduce(p->shards, p->asc_active ? 5 : 2);
+                if (!rc) rc = each_shard(p, eng_newton_update_enqueue);
+                return rc;
+            },
+            [&](bool *done) {
+                const int rc = newton_state_read(p->shards[0]);
+                *done = !rc && p->shards[0]->h_nstate->done;
+                return rc;
+            });
+        if (rc) return rc;
         st = *p->shards[0]->h_nstate;
     } else {
         // pinned-host reduction: the host adds the shards' {df, ddf} and advances the same state machine itself
@@ -359,35 +362,27 @@ int optimize_branch(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool bu
             newton_update(st, v[0], v[1]);
         }
     }
-    if (st.status == 2) return bad(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-    if (st.status == 3) return bad(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-    if (optx) *optx = st.result;
-    if (d2l) *d2l = st.d2l;
-    if (nsteps) *nsteps = st.neval;
+    rc = newton_status(st.status);
+    if (rc) return rc;
+    NewtonResult(st).store(optx, d2l, nsteps);
     return IQHIP_OK;
 }
 
 // iqhip_optimize_branch_batch on the front: the tasks' node updates in one submission per shard, then the batched chain
-// (engine.hip eng_batch_*): per Newton step one derivative launch per shard for all tasks and ONE reduction of 2m values
+// (solve.hip eng_batch_*): per Newton step one derivative launch per shard for all tasks and ONE reduction of 2m values
 // across the shards (grouped all-reduce, or the host's sum with the state machines advanced on the host)
 int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int ntasks, double *sum_scale,
                           iqhip_branch_result *results) {
     std::vector<iqhip_node_op> all;
-    std::vector<int> segs((size_t)ntasks);
-    for (int t = 0; t < ntasks; t++) {
-        const iqhip_branch_task &k = tasks[t];
-        if (k.nops < 0 || (k.nops > 0 && !k.ops)) return bad(IQHIP_ERR_INVALID, "bad ops array in a task");
-        if (!(k.x1 >= 0.0) || !(k.x2 > k.x1) || !(k.xacc > 0.0) || k.max_steps < 1 || !(k.xguess >= 0.0))
-            return bad(IQHIP_ERR_INVALID, "iqhip_optimize_branch_batch: bad bounds / tolerance / step count");
-        segs[t] = k.nops;
-        all.insert(all.end(), k.ops, k.ops + k.nops);
-    }
+    std::vector<int> segs;
+    int rc = batch_gather_ops(tasks, ntasks, all, segs);
+    if (rc) return rc;
     const int total_ops = (int)all.size();
-    int rc = IQHIP_OK;
     std::vector<double> v;
     if (total_ops > 0) {
+        const iqhip_branch_end none = {0, -1, 0};
         for (iqhip_engine *c : p->shards) {
-            rc = eng_submit_updates(c, all.data(), total_ops, &segs);
+            rc = submit_traverse(c, all.data(), total_ops, false, none, none, 0.0, /*skip_reduce=*/false, &segs);
             if (rc) return rc;
         }
         rc = reduce_results(p, 2 + total_ops, v);
@@ -395,8 +390,7 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
         if (sum_scale)
             for (int k = 0; k < total_ops; k++) sum_scale[k] = v[2 + k];
     }
-    int chunk = std::min(ntasks, 64);
-    if (const char *bc = getenv("IQHIP_BATCH_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(bc)));
+    const int chunk = batch_chunk(std::min(ntasks, kBatchChainChunk));
     const bool rccl = p->reduce_mode == IQHIP_REDUCE_RCCL;
     std::vector<NewtonState> st((size_t)chunk);
     for (int first = 0; first < ntasks; first += chunk) {
@@ -417,27 +411,20 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
             return true;
         };
         if (rccl) {
-            int enq = 0;
-            for (;;) {
-                const int steps = enq == 0 ? std::min(4, max_steps + 1) : 2;
-                for (int k = 0; k < steps; k++) {
-                    for (iqhip_engine *c : p->shards) {
-                        rc = eng_batch_eval_enqueue(c, m);
-                        if (rc) return rc;
-                    }
-                    rc = comm_group_allreduce(p->shards, 2 * m);
-                    if (rc) return rc;
-                    for (iqhip_engine *c : p->shards) {
-                        rc = eng_batch_update_enqueue(c, m);
-                        if (rc) return rc;
-                    }
-                }
-                enq += steps;
-                rc = eng_batch_states_read(p->shards[0], m, st.data());
-                if (rc) return rc;
-                if (all_done()) break;
-                if (enq > max_steps + 2) return bad(IQHIP_ERR_INVALID, "Newton chain did not terminate");
-            }
+            rc = drive_chain(
+                max_steps,
+                [&] {
+                    int rc = each_shard(p, [&](iqhip_engine *c) { return eng_batch_eval_enqueue(c, m); });
+                    if (!rc) rc = comm_group_allreduce(p->shards, 2 * m);
+                    if (!rc) rc = each_shard(p, [&](iqhip_engine *c) { return eng_batch_update_enqueue(c, m); });
+                    return rc;
+                },
+                [&](bool *done) {
+                    const int rc = eng_batch_states_read(p->shards[0], m, st.data());
+                    *done = !rc && all_done();
+                    return rc;
+                });
+            if (rc) return rc;
         } else {
             for (int guard = 0; !all_done(); guard++) {
                 if (guard > max_steps + 2) return bad(IQHIP_ERR_INVALID, "Newton loop did not terminate");
@@ -456,15 +443,8 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
                 if (rc) return rc;
             }
         }
-        for (int t = 0; t < m; t++) {
-            if (st[t].status == 2) return bad(IQHIP_ERR_INVALID, "Wrong computeFuncDerv (non-finite derivative)");
-            if (st[t].status == 3) return bad(IQHIP_ERR_INVALID, "Maximum number of iterations exceeded in minimizeNewton");
-            iqhip_branch_result &r = results[first + t];
-            r.optx = st[t].result;
-            r.d2l = st[t].d2l;
-            r.nsteps = st[t].neval;
-            r.status = 0;
-        }
+        rc = batch_task_results(st, m, results + first);
+        if (rc) return rc;
         for (iqhip_engine *c : p->shards) {
             rc = eng_batch_lnl_enqueue(c, m);
             if (rc) return rc;
