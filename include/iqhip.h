@@ -155,8 +155,8 @@ int iqhip_set_ptn_invar(iqhip_engine *e, const double *ptn_invar); /* +I changed
  * iqhip_set_alignment are the unobserved constant patterns (ModelFactory::unobserved_ptns,
  * phylokernel.h:87; frequency 0, ptn_invar = p_invar*pi) and nsites = aln->getNSite().  The lnL and
  * derivative calls then apply phylokernel.h:868-909,968-1016 (branch), :655-725 (derivatives) and
- * :1124-1187 (from buffer), also inside iqhip_newton_branch / iqhip_optimize_sweep.  0 switches it off.  Not available
- * with the *_async calls and the batched NNI evaluator.  Sharded engines (iqhip_create_sharded): the unobserved patterns
+ * :1124-1187 (from buffer), also inside iqhip_newton_branch / iqhip_optimize_sweep / iqhip_optimize_branch_batch.  0
+ * switches it off.  Not available with the *_async calls (the caller owns the collective there).  Sharded engines (iqhip_create_sharded): the unobserved patterns
  * must fit the last shard; prob_const / df_const / ddf_const are reduced with the result.  Comm engines
  * (iqhip_comm_init_rank): the rank holding the unobserved patterns (the last one) passes their number, every other
  * rank passes (0, nsites). */
@@ -266,10 +266,11 @@ int iqhip_fetch_theta(iqhip_engine *e, double *out /* nptn*block, ref layout */)
  * read any existing vector, must write vectors no other task touches -- the nni_partial_lh scratch buffers,
  * phylotree.cpp:2901-2924), then optimises the length of branch (a, b) as iqhip_optimize_branch does and
  * evaluates computeLikelihoodFromBuffer at the optimum.  results[t].lnl excludes the lh_scale_factor terms;
- * sum_scale receives the per-op values of all tasks, concatenated in task order.  +ASC is not supported.
+ * sum_scale receives the per-op values of all tasks, concatenated in task order.  +ASC engines included: results[t].lnl
+ * then carries -nsites * log(1 - prob_const) of its own branch.
  * On a sharded engine (iqhip_create_sharded, iqhip_comm_init_rank) the tasks advance side by side as well: per Newton
  * step one derivative launch for all tasks and ONE all-reduce of 2 * ntasks doubles (chunks of 64 tasks, the same on
- * every rank); +ASC engines run the tasks one after the other. */
+ * every rank); with +ASC 5 * ntasks doubles ({df, ddf, prob_const, df_const, ddf_const} per task). */
 typedef struct iqhip_branch_task {
     const iqhip_node_op *ops;
     int32_t nops;
@@ -296,8 +297,9 @@ int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_task *tasks,
  * diverge_frac > 0 applies optimizeOneBranch's "newton raphson diverged, reset" rule (phylotree.cpp:2167-2176, 0.95 there)
  * inside the sweep: a result above diverge_frac * x2 is kept only if the branch lnL there is not below the lnL at
  * xguess; results[j].status = 5 reports that the rule ran.  results[j].lnl is not filled.  sum_scale receives the per-op
- * values of all steps, concatenated.  Two launches per step, one host round trip per sweep; on sharded engines (every
- * Newton step contains an all-reduce) and with +ASC the steps run one after the other inside this call. */
+ * values of all steps, concatenated.  Two launches per step, one host round trip per sweep (+ASC engines included: both
+ * lnL of the diverged-solve rule carry their own -nsites * log(1 - prob_const)); on sharded engines (every Newton step
+ * contains an all-reduce) the steps run one after the other inside this call. */
 typedef struct iqhip_sweep_step {
     const iqhip_node_op *ops;
     const int32_t *len_from; /* NULL or 2 * nops entries */

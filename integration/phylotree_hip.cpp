@@ -200,7 +200,8 @@ double PhyloTree::computeLikelihoodFromBufferHIP() {
 // enqueued chain with one in-stream all-reduce per step).  Hunk in optimizeOneBranch:
 //   if (optimize_by_newton && hip_engine && computePartialLikelihoodPointer == &PhyloTree::computePartialLikelihoodHIP)
 //       optx = hipMinimizeNewton(current_len, maxNRStep); else ...        (+ASC models included: phylokernel.h:655-725 runs
-//                                                                         inside the device solve)
+//                                                                         inside the device solve, also in the batched
+//                                                                         NNI evaluators and the one-submission sweep)
 // The call leaves current_it / current_it_back at the length it returns -- the last evaluated point, as the reference's
 // computeFuncDerv does -- so the diverged-Newton test that follows in optimizeOneBranch (phylotree.cpp:2167-2176) evaluates
 // opt_lh = computeLikelihoodFromBuffer() at the right length, unchanged.

@@ -220,6 +220,7 @@ extern "C" void iqhip_destroy(iqhip_engine *e) {
     if (e->d_result_dev) hipFree(e->d_result_dev);
     if (e->d_nstate) hipFree(e->d_nstate);
     if (e->d_bstates) hipFree(e->d_bstates);
+    if (e->d_bsc) hipFree(e->d_bsc);
     if (e->h_nstate) hipHostFree(e->h_nstate);
     if (e->stream) hipStreamSynchronize(e->stream);
     for (auto &s : e->slabs) {
@@ -871,13 +872,19 @@ static int repair_lnl(iqhip_engine *e, double *lnl) {
 
 // +ASC finalisation of a lnL evaluation (phylokernel.h:1009-1016, 1183-1186): result[1] holds
 // prob_const; tree_lh -= nsites*log(1-prob_const), _pattern_lh[observed] -= log(1-prob_const)
+int iqhip::asc_log_term(double prob_const, double *lp) {
+    if (!(prob_const < 1.0 && prob_const >= 0.0))
+        return fail(IQHIP_ERR_INVALID, "+ASC: prob_const outside [0,1) (the reference asserts here)");
+    *lp = log(1.0 - prob_const);
+    return IQHIP_OK;
+}
+
 static int asc_finish_lnl(iqhip_engine *e, double *lnl) {
     e->pattern_lh_shift = 0.0;
     if (!e->asc_active) return IQHIP_OK;
-    const double pc = e->h_result[1];
-    if (!(pc < 1.0 && pc >= 0.0))
-        return fail(IQHIP_ERR_INVALID, "+ASC: prob_const outside [0,1) (the reference asserts here)");
-    const double lp = log(1.0 - pc);
+    double lp;
+    const int rc = asc_log_term(e->h_result[1], &lp);
+    if (rc) return rc;
     e->pattern_lh_shift = lp;
     *lnl -= e->asc_nsites * lp;
     return IQHIP_OK;

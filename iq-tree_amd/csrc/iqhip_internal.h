@@ -441,6 +441,8 @@ struct iqhip_engine {
     iqhip::NewtonState *d_nstate = nullptr, *h_nstate = nullptr;  // Newton state machine: device copy / pinned host copy
     iqhip::NewtonState *d_bstates = nullptr;                      // batched chain: one state machine per task
     int bstates_cap = 0;
+    const int16_t **d_bsc = nullptr;                              // ... and (+ASC) the scale counters of its two branch ends
+    int bsc_cap = 0;
     // ---- single-process sharding (sharded.hip): this object owns no device memory, it fronts `shards`
     // (pattern ranges [shard_first[g], shard_first[g+1]) on the devices of iqhip_create_sharded)
     std::vector<iqhip_engine *> shards;
@@ -752,6 +754,9 @@ int batch_gather_ops(const iqhip_branch_task *tasks, int ntasks, std::vector<iqh
 constexpr int kBatchChainChunk = 64;
 int batch_chunk(int chunk);   // ... clamped by IQHIP_BATCH_CHUNK (read per call)
 int batch_task_results(const std::vector<NewtonState> &st, int m, iqhip_branch_result *results);
+int batch_derv_rows(const iqhip_engine *e);   // result rows per task of a derivative pass: 2, +ASC 5
+int batch_asc_lnl(const iqhip_engine *e, double prob_const, double *lnl);   // +ASC: lnl -= nsites * log(1 - prob_const)
+int asc_log_term(double prob_const, double *lp);   // log(1 - prob_const) after the reference's range assertion (engine.hip)
 // Newton as a chain of enqueued steps, one piece at a time
 int newton_state_alloc(iqhip_engine *e);
 int newton_state_read(iqhip_engine *e);               // -> e->h_nstate (syncs the stream)
@@ -812,6 +817,10 @@ struct BatchChain {
     size_t theta_stride;
     const NewtonState *states;
     int ntasks;
+    // slab rows per task of a derivative pass: 2 = {df, ddf}; 5 (+ASC) = {df, ddf, prob_const, df_const, ddf_const}, the last
+    // three zero on an engine that holds none of the unobserved patterns.  The lnL pass has 2 = {lnl, prob_const} always.
+    int derv_rows;
+    const int16_t *const *sc;   // +ASC: [2 * ntasks] scale counters of the tasks' branch ends (the lnL pass's rescale rule)
 };
 hipError_t launch_theta4(iqhip_engine *e, const DevBranch &br, double *theta_out = nullptr);
 hipError_t launch_derv4(iqhip_engine *e, double len, int nwaves, const NewtonState *st = nullptr, const BatchChain *bc = nullptr);
@@ -839,7 +848,8 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
 hipError_t launch_newton_state_init(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps);
 hipError_t launch_derv_at_state(iqhip_engine *e, int nwaves);
 hipError_t launch_newton_state_update(iqhip_engine *e);   // (+ASC: result[2..4] and asc_nsites enter the update)
-hipError_t launch_newton_state_update_batch(iqhip_engine *e, NewtonState *states, int ntasks);   // from result[2t], result[2t+1]
+// from result[2t], result[2t+1]; +ASC: from result[5t .. 5t+4], corrected like launch_newton_state_update
+hipError_t launch_newton_state_update_batch(iqhip_engine *e, NewtonState *states, int ntasks);
 
 // kernels_sweep.hip: a whole sweep of a 4-state engine in one launch; posts: [2][kNewtonPostEpochs][grid][2] all-ones
 int sweep4_grid(const iqhip_engine *e);

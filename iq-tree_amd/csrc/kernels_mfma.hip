@@ -1716,7 +1716,9 @@ struct StreamMArgs {
     int ncat;
     double len;
     const NewtonState *st;    // a step of the enqueued Newton chain: len = st->rts, nothing to do once st->done
-    size_t theta_stride;      // > 0: batched chain, blockIdx.y = task (own theta, state, pair of slab rows)
+    size_t theta_stride;      // > 0: batched chain, blockIdx.y = task (own theta, state, task_rows slab rows)
+    int task_rows;            // 2, or 5 in the derivative pass of a batched +ASC engine
+    const int16_t *const *task_sc;   // batched +ASC lnL pass: [2 * ntasks] scale counters of the tasks' branch ends
     FoldArgs fold;            // the last workgroup sums the slab itself (no k_reduce launch)
 };
 
@@ -1729,10 +1731,12 @@ __global__ __launch_bounds__(256) void k_stream_mfma(const StreamMArgs A) {
     const NewtonState *st = A.st;
     const double *theta_in = A.theta;
     double *slab = A.slab;
+    const int16_t *a_sc = A.a_sc, *b_sc = A.b_sc;
     if (A.theta_stride) {
         theta_in += (size_t)blockIdx.y * A.theta_stride;
-        slab += (size_t)2 * blockIdx.y * A.nwaves;
+        slab += (size_t)A.task_rows * blockIdx.y * A.nwaves;
         st += blockIdx.y;
+        if (A.task_sc) { a_sc = A.task_sc[2 * blockIdx.y]; b_sc = A.task_sc[2 * blockIdx.y + 1]; }
     }
     if (st) {
         if (MODE == 2) {
@@ -1808,7 +1812,7 @@ __global__ __launch_bounds__(256) void k_stream_mfma(const StreamMArgs A) {
             fold_store(&slab[tile], wa);
             fold_store(&slab[(size_t)A.nwaves + tile], wb);
         }
-        if (asc) {  // phylokernel.h:655-725
+        if (asc || A.task_rows == 5) {  // phylokernel.h:655-725 (a batched +ASC engine without unobserved patterns: zeros)
             const double w2 = wave_sum_m(unobs ? lhi : 0.0), w3 = wave_sum_m(unobs ? d1 : 0.0),
                          w4 = wave_sum_m(unobs ? d2 : 0.0);
             if (lane == 0) {
@@ -1821,8 +1825,8 @@ __global__ __launch_bounds__(256) void k_stream_mfma(const StreamMArgs A) {
         double pc = 0.0;
         if (asc && unobs) {  // phylokernel.h:894-900, 989-995, 1157-1163
             int ssc = 0;
-            if (A.a_sc) ssc += A.a_sc[ptn];
-            if (A.b_sc) ssc += A.b_sc[ptn];
+            if (a_sc) ssc += a_sc[ptn];
+            if (b_sc) ssc += b_sc[ptn];
             pc = (ssc >= 1 ? lh * kScalingThreshold : lh) + iv;
         }
         const double plh = log(fabs(lh + iv));
@@ -1842,6 +1846,8 @@ hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, do
     StreamMArgs A;
     A.st = bc ? bc->states : st;
     A.theta_stride = bc ? bc->theta_stride : 0;
+    A.task_rows = (bc && mode == 2) ? bc->derv_rows : 2;
+    A.task_sc = bc ? bc->sc : nullptr;
     if (bc) fold_rows = -1;
     A.fold.slab = e->d_slab;
     A.fold.result = e->d_result;

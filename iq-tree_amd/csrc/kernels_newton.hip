@@ -314,7 +314,9 @@ __device__ __forceinline__ void wg_partial(const NewtonArgs &A, const double *th
 // nstates such patterns, in the last tile(s); wave 0 of EVERY workgroup computes them for itself (theta of those
 // patterns from the resident theta_all, or on the fly from the branch ends while theta is being built by its owner), so
 // the exchange between the workgroups stays two doubles and every workgroup applies the same correction.
-template <bool BUILD>
+// MODE 1: prob_const of computeLikelihoodFromBuffer (phylokernel.h:1138-1163) in s_asc[0]: a pattern whose two ends were
+// rescaled at least once enters as lh * 2^-256 (the counters of the branch ends, DevBranch::a_sc / b_sc).
+template <bool BUILD, int MODE = 0>
 __device__ __forceinline__ void asc_unobserved_sums(const NewtonArgs &A, const double *theta_c, const DevBranch &br,
                                                     const double *s_v0, const double *s_v1, const double *s_v2, double *s_asc) {
     if (threadIdx.x < 64) {
@@ -347,8 +349,10 @@ __device__ __forceinline__ void asc_unobserved_sums(const NewtonArgs &A, const d
                         t = p[j * 64];
                     }
                     lh = fma(s_v0[2 * j], t.x, lh); lh = fma(s_v0[2 * j + 1], t.y, lh);
-                    d1 = fma(s_v1[2 * j], t.x, d1); d1 = fma(s_v1[2 * j + 1], t.y, d1);
-                    d2 = fma(s_v2[2 * j], t.x, d2); d2 = fma(s_v2[2 * j + 1], t.y, d2);
+                    if (MODE == 0) {
+                        d1 = fma(s_v1[2 * j], t.x, d1); d1 = fma(s_v1[2 * j + 1], t.y, d1);
+                        d2 = fma(s_v2[2 * j], t.x, d2); d2 = fma(s_v2[2 * j + 1], t.y, d2);
+                    }
                 }
             } else {
                 const int p = lane & 15, g = lane >> 4;
@@ -363,16 +367,31 @@ __device__ __forceinline__ void asc_unobserved_sums(const NewtonArgs &A, const d
                 for (int e = g; e < B; e += 4) {
                     const double t = BUILD ? (tp ? tp[e] : av[(size_t)e * 16 + p]) * bv[(size_t)e * 16 + p] : th[(size_t)e * 16 + p];
                     lh = fma(s_v0[e], t, lh);
-                    d1 = fma(s_v1[e], t, d1);
-                    d2 = fma(s_v2[e], t, d2);
+                    if (MODE == 0) {
+                        d1 = fma(s_v1[e], t, d1);
+                        d2 = fma(s_v2[e], t, d2);
+                    }
                 }
                 lh = group_sum(lh);
-                d1 = group_sum(d1);
-                d2 = group_sum(d2);
+                if (MODE == 0) {
+                    d1 = group_sum(d1);
+                    d2 = group_sum(d2);
+                }
             }
             const bool unobs = mine && ptn >= A.nobs && ptn < A.nptn;
-            const double w0 = wsum(unobs ? lh + A.invar[ptn] : 0.0), w1 = wsum(unobs ? d1 : 0.0), w2 = wsum(unobs ? d2 : 0.0);
-            u0 += w0; u1 += w1; u2 += w2;
+            if (MODE == 1) {
+                double pc = 0.0;
+                if (unobs) {
+                    int ssc = 0;
+                    if (br.a_sc) ssc += br.a_sc[ptn];
+                    if (br.b_sc) ssc += br.b_sc[ptn];
+                    pc = (ssc >= 1 ? lh * kScalingThreshold : lh) + A.invar[ptn];
+                }
+                u0 += wsum(pc);
+            } else {
+                const double w0 = wsum(unobs ? lh + A.invar[ptn] : 0.0), w1 = wsum(unobs ? d1 : 0.0), w2 = wsum(unobs ? d2 : 0.0);
+                u0 += w0; u1 += w1; u2 += w2;
+            }
         }
         if (lane == 0) { s_asc[0] = u0; s_asc[1] = u1; s_asc[2] = u2; }
     }
@@ -545,6 +564,11 @@ __global__ __launch_bounds__(256) void k_newton(const NewtonArgs A) {
         }
         __syncthreads();
         double p0, p1;
+        const bool asc = A.nobs < A.nptn;
+        if (asc) {   // (as in eval_at: from the branch ends when this launch built theta)
+            if (A.build) asc_unobserved_sums<true, 1>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
+            else asc_unobserved_sums<false, 1>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
+        }
         wg_partial<false, 1>(A, A.theta, A.br, blockIdx.x, gridDim.x, s_v0, s_v1, s_v2, s_red, p0, p1, &treg);
         if (gridDim.x > 1 && A.posts) {
             unsigned long long *slots = reinterpret_cast<unsigned long long *>(A.posts) + (size_t)epoch * gridDim.x * 2;
@@ -601,6 +625,8 @@ __global__ __launch_bounds__(256) void k_newton(const NewtonArgs A) {
             __syncthreads();
             epoch++;
         }
+        // +ASC (phylokernel.h:1183-1186): both lengths of the comparison carry their own -nsites * log(1 - prob_const)
+        if (asc) p0 -= A.asc_nsites * log(1.0 - s_asc[0]);
         return p0;
     };
 
@@ -707,6 +733,7 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
     const int B = A.n * A.ncat;
     double *s_v0 = smem, *s_v1 = smem + B, *s_v2 = smem + 2 * B, *s_red = smem + 3 * B;  // s_red[8]
     __shared__ double s_bcast[2];
+    __shared__ double s_asc[3];
     __shared__ int s_fail;
     const int task = (int)blockIdx.x / P.G, wg = (int)blockIdx.x - task * P.G, G = P.G;
     // (read through the constant address space: the branch-end pointers inside are then known to be global and the first
@@ -729,7 +756,9 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
             reinterpret_cast<unsigned long long *>(P.posts_other)[t] = ~0ull;
     unsigned int epoch = 0;
     bool first = true;
-    // sums over the task's patterns of (f*df, f*ddf) -- or of f*log|lh| when lnl_pass -- at branch length x
+    const bool asc = A.nobs < A.nptn;
+    // sums over the task's patterns of (f*df, f*ddf) -- or of f*log|lh| when lnl_pass -- at branch length x; +ASC: the sums
+    // over the unobserved constant patterns at the same val arrays are left in s_asc (every workgroup its own copy)
     auto eval_at = [&](double x, bool lnl_pass, double &r0, double &r1) {
         for (int t = threadIdx.x; t < B; t += 256) {
             const int c = t / A.n;
@@ -741,6 +770,19 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
         }
         __syncthreads();
         double p0, p1;
+        if (asc) {
+            // theta of the last tile(s) is in flight from its owner during the task's first evaluation, and with several
+            // workgroups per task the owner's plain stores never become visible to the others in this launch (k_newton's
+            // rule): from the branch ends then; a task of one workgroup reads back what it wrote itself
+            const bool from_ends = first || G > 1;
+            if (lnl_pass) {
+                if (from_ends) asc_unobserved_sums<true, 1>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
+                else asc_unobserved_sums<false, 1>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
+            } else {
+                if (from_ends) asc_unobserved_sums<true, 0>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
+                else asc_unobserved_sums<false, 0>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
+            }
+        }
         if (lnl_pass) wg_partial<false, 1>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
         else if (first) wg_partial<true, 0>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
         else wg_partial<false, 0>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
@@ -819,6 +861,12 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
         double pdf, pddf;
         eval_at(x, false, pdf, pddf);
         if (isnan(pdf) || isinf(pdf)) { pdf = 0.0; pddf = 0.0; }  // phylokernel.h:647-651
+        if (asc) {   // phylokernel.h:719-724
+            const double prob_const = 1.0 - s_asc[0];
+            const double df_frac = s_asc[1] / prob_const, ddf_frac = s_asc[2] / prob_const;
+            pdf += A.asc_nsites * df_frac;
+            pddf += A.asc_nsites * (ddf_frac + df_frac * df_frac);
+        }
         f = -pdf;
         df = -pddf;
     };
@@ -865,6 +913,7 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
     // lnL of the branch at the returned length (computeLikelihoodFromBuffer, phylokernel.h:1022-1192)
     double lnl, unused;
     eval_at(result, true, lnl, unused);
+    if (asc) lnl -= A.asc_nsites * log(1.0 - s_asc[0]);   // phylokernel.h:1183-1186
     __syncthreads();
     if (s_fail) status = 4;
     if (wg == 0 && threadIdx.x == 0) {
@@ -922,8 +971,8 @@ hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks,
     A.max_steps = 0;
     A.len_out = nullptr;
     A.diverge_x = 0.0;
-    A.nobs = e->nptn;   // (+ASC is refused for batches)
-    A.asc_nsites = 0.0;
+    A.nobs = e->nptn - e->n_unobs;
+    A.asc_nsites = e->asc_nsites;
     P.tasks = static_cast<const NewtonTask *>(d_tasks);
     P.theta_base = theta_base;
     P.theta_stride = theta_stride;
@@ -975,19 +1024,31 @@ __global__ void k_newton_state_update(NewtonState *st, const double *result, dou
     }
 }
 
-// batched chain: thread t advances task t's state machine from result[2t], result[2t + 1]
-__global__ void k_newton_state_update_batch(NewtonState *st, const double *result, int ntasks) {
+// batched chain: thread t advances task t's state machine from result[2t], result[2t + 1]; asc_nsites > 0 (+ASC): from
+// result[5t .. 5t + 4] = {df, ddf, prob_const, df_const, ddf_const} summed over all shards, as k_newton_state_update
+__global__ void k_newton_state_update_batch(NewtonState *st, const double *result, int ntasks, double asc_nsites) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntasks) return;
     NewtonState s = st[t];
     if (s.done) return;
-    newton_update(s, result[2 * t], result[2 * t + 1]);
+    if (asc_nsites > 0.0) {
+        const double *r = result + 5 * t;
+        double df = r[0], ddf = r[1];
+        if (isnan(df) || isinf(df)) { df = 0.0; ddf = 0.0; }
+        const double prob_const = 1.0 - r[2];
+        const double df_frac = r[3] / prob_const, ddf_frac = r[4] / prob_const;
+        df += asc_nsites * df_frac;
+        ddf += asc_nsites * (ddf_frac + df_frac * df_frac);
+        newton_update(s, df, ddf);
+    } else {
+        newton_update(s, result[2 * t], result[2 * t + 1]);
+    }
     st[t] = s;
 }
 
 hipError_t launch_newton_state_update_batch(iqhip_engine *e, NewtonState *states, int ntasks) {
     hipLaunchKernelGGL(k_newton_state_update_batch, dim3((unsigned)((ntasks + 63) / 64)), dim3(64), 0, e->stream, states,
-                       e->d_result, ntasks);
+                       e->d_result, ntasks, e->asc_active ? e->asc_nsites : 0.0);
     return hipGetLastError();
 }
 

@@ -758,13 +758,14 @@ __global__ __launch_bounds__(256) void k_theta_reduce4(
     const double *__restrict__ freq, const double *__restrict__ invar,
     double *__restrict__ pattern_lh, double *__restrict__ slab, int64_t ntiles, int64_t nptn,
     int nwaves, int64_t nobs, const int16_t *__restrict__ a_sc, const int16_t *__restrict__ b_sc,
-    const NewtonState *st, size_t theta_stride) {
+    const NewtonState *st, size_t theta_stride, int task_rows, const int16_t *const *task_sc) {
     constexpr int B = 4 * C;
     __shared__ double s_v0[B], s_v1[B], s_v2[B];
-    if (theta_stride) {   // batched chain (blockIdx.y = task): own theta, own state, own pair of slab rows
+    if (theta_stride) {   // batched chain (blockIdx.y = task): own theta, own state, own task_rows slab rows (+ASC: own counters)
         theta += (size_t)blockIdx.y * theta_stride;
-        slab += (size_t)2 * blockIdx.y * nwaves;
+        slab += (size_t)task_rows * blockIdx.y * nwaves;
         st += blockIdx.y;
+        if (task_sc) { a_sc = task_sc[2 * blockIdx.y]; b_sc = task_sc[2 * blockIdx.y + 1]; }
     }
     if (st) {  // a step of the enqueued Newton chain: the branch length is the state's current iterate
         if (MODE == 0) {
@@ -814,7 +815,8 @@ __global__ __launch_bounds__(256) void k_theta_reduce4(
             slab[gw] = wa;
             slab[(size_t)nwaves + gw] = wb;
         }
-        if (nobs < nptn) {  // phylokernel.h:655-725: plain sums over the unobserved patterns, no rescale
+        // (task_rows == 5: a batched +ASC engine without unobserved patterns of its own writes its zeros)
+        if (nobs < nptn || task_rows == 5) {  // phylokernel.h:655-725: plain sums over the unobserved patterns, no rescale
             const double w2 = wave_sum(unobs ? lhi : 0.0), w3 = wave_sum(unobs ? d1 : 0.0),
                          w4 = wave_sum(unobs ? d2 : 0.0);
             if (lane == 0) {
@@ -851,12 +853,15 @@ static hipError_t launch_theta_reduce(iqhip_engine *e, double len, int nwaves, c
     double *plh = bc ? nullptr : e->d_pattern_lh;
     const size_t stride = bc ? bc->theta_stride : 0;
     const int ny = bc ? bc->ntasks : 1;
+    const int task_rows = (bc && MODE == 0) ? bc->derv_rows : 2;
+    const int16_t *const *task_sc = bc ? bc->sc : nullptr;
 #define IQ_TR(Cv)                                                                              \
     case Cv:                                                                                   \
         hipLaunchKernelGGL((k_theta_reduce4<Cv, MODE>), dim3(grid, ny), dim3(256), 0, e->stream, \
                            theta, e->d_eval, e->d_rates, e->d_props, len, e->d_freq,           \
                            e->d_invar, plh, e->d_slab, e->ntiles, e->nptn, nwaves,             \
-                           e->nptn - e->n_unobs, e->theta_a_sc, e->theta_b_sc, st, stride);    \
+                           e->nptn - e->n_unobs, e->theta_a_sc, e->theta_b_sc, st, stride,     \
+                           task_rows, task_sc);                                                \
         break;
     switch (e->ncat) {
         IQ_TR(1) IQ_TR(2) IQ_TR(3) IQ_TR(4) IQ_TR(5) IQ_TR(6) IQ_TR(7) IQ_TR(8)

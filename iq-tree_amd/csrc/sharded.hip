@@ -214,9 +214,9 @@ int set_ascertainment(iqhip_engine *p, int64_t n_unobserved, double nsites) {
 // phylokernel.h:1009-1016 / 1183-1186 on the summed prob_const; the shards learn the shift for their _pattern_lh views
 static int asc_finish(iqhip_engine *p, double prob_const, double *lnl) {
     if (!p->asc_active) return IQHIP_OK;
-    if (!(prob_const < 1.0 && prob_const >= 0.0))
-        return bad(IQHIP_ERR_INVALID, "+ASC: prob_const outside [0,1) (the reference asserts here)");
-    const double lp = log(1.0 - prob_const);
+    double lp;
+    const int rc = asc_log_term(prob_const, &lp);
+    if (rc) return rc;
     *lnl -= p->asc_nsites * lp;
     p->pattern_lh_shift = lp;
     for (iqhip_engine *c : p->shards) c->pattern_lh_shift = lp;
@@ -224,7 +224,8 @@ static int asc_finish(iqhip_engine *p, double prob_const, double *lnl) {
 }
 
 // phylokernel.h:647-651, then :719-724 on the summed {prob_const, df_const, ddf_const} = v[2..4]
-static void asc_derv(const iqhip_engine *p, std::vector<double> &v) {
+// (one copy of this arithmetic: the batched chain must give the bits of the one-task form)
+__attribute__((noinline)) static void asc_derv(const iqhip_engine *p, double *v) {
     if (isnan(v[0]) || isinf(v[0])) v[0] = v[1] = 0.0;
     if (!p->asc_active) return;
     const double prob_const = 1.0 - v[2];
@@ -280,7 +281,7 @@ int derv(iqhip_engine *p, double len, double *df, double *ddf) {
     std::vector<double> v;
     int rc = reduce_results(p, p->asc_active ? 5 : 2, v);
     if (rc) return rc;
-    asc_derv(p, v);
+    asc_derv(p, v.data());
     if (df) *df = v[0];
     if (ddf) *ddf = v[1];
     return IQHIP_OK;
@@ -358,7 +359,7 @@ int optimize_branch(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool bu
             std::vector<double> v;
             rc = reduce_results(p, p->asc_active ? 5 : 2, v);
             if (rc) return rc;
-            if (p->asc_active) asc_derv(p, v);
+            if (p->asc_active) asc_derv(p, v.data());
             newton_update(st, v[0], v[1]);
         }
     }
@@ -370,7 +371,7 @@ int optimize_branch(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool bu
 
 // iqhip_optimize_branch_batch on the front: the tasks' node updates in one submission per shard, then the batched chain
 // (solve.hip eng_batch_*): per Newton step one derivative launch per shard for all tasks and ONE reduction of 2m values
-// across the shards (grouped all-reduce, or the host's sum with the state machines advanced on the host)
+// across the shards (grouped all-reduce, or the host's sum with the state machines advanced on the host); +ASC: 5m values
 int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int ntasks, double *sum_scale,
                           iqhip_branch_result *results) {
     std::vector<iqhip_node_op> all;
@@ -392,6 +393,7 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
     }
     const int chunk = batch_chunk(std::min(ntasks, kBatchChainChunk));
     const bool rccl = p->reduce_mode == IQHIP_REDUCE_RCCL;
+    const int rows = batch_derv_rows(p);
     std::vector<NewtonState> st((size_t)chunk);
     for (int first = 0; first < ntasks; first += chunk) {
         const int m = std::min(chunk, ntasks - first);
@@ -415,7 +417,7 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
                 max_steps,
                 [&] {
                     int rc = each_shard(p, [&](iqhip_engine *c) { return eng_batch_eval_enqueue(c, m); });
-                    if (!rc) rc = comm_group_allreduce(p->shards, 2 * m);
+                    if (!rc) rc = comm_group_allreduce(p->shards, rows * m);
                     if (!rc) rc = each_shard(p, [&](iqhip_engine *c) { return eng_batch_update_enqueue(c, m); });
                     return rc;
                 },
@@ -433,10 +435,14 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
                     if (!rc) rc = eng_batch_eval_enqueue(c, m);
                     if (rc) return rc;
                 }
-                rc = reduce_results(p, 2 * m, v);
+                rc = reduce_results(p, rows * m, v);
                 if (rc) return rc;
-                for (int t = 0; t < m; t++)
-                    if (!st[t].done) newton_update(st[t], v[2 * t], v[2 * t + 1]);
+                for (int t = 0; t < m; t++) {
+                    if (st[t].done) continue;
+                    double *r = &v[(size_t)rows * t];
+                    if (p->asc_active) asc_derv(p, r);
+                    newton_update(st[t], r[0], r[1]);
+                }
             }
             for (iqhip_engine *c : p->shards) {   // (the lnL launch reads the accepted lengths from the states)
                 rc = eng_batch_states_write(c, m, st.data());
@@ -458,8 +464,10 @@ int optimize_branch_batch(iqhip_engine *p, const iqhip_branch_task *tasks, int n
             if (isnan(r.lnl) || isinf(r.lnl)) {   // rare: redo this task alone, with the per-shard repair
                 rc = compute_theta(p, tasks[first + t].a, tasks[first + t].b);
                 if (!rc) rc = lnl_from_theta(p, r.optx, &r.lnl);
-                if (rc) return rc;
+            } else {
+                rc = batch_asc_lnl(p, lnl[2 * t + 1], &r.lnl);
             }
+            if (rc) return rc;
         }
     }
     return IQHIP_OK;

@@ -257,7 +257,7 @@ static int sweep_resolve_ops(const iqhip_sweep_step &st, const iqhip_branch_resu
 }
 
 // the same sweep one step at a time (a host round trip per step): sharded engines and engines with a communicator, where
-// every Newton step contains an all-reduce; +ASC; and the remainder of a sweep whose grid-wide exchange timed out
+// every Newton step contains an all-reduce; and the remainder of a sweep whose grid-wide exchange timed out
 static int sweep_sequential(iqhip_engine *e, const iqhip_sweep_step *steps, int first, int nsteps, double x1, double x2,
                             double xacc, int max_steps, double diverge_frac, double *sum_scale, size_t ss_off,
                             iqhip_branch_result *results) {
@@ -411,12 +411,13 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
                 if (st.len_from[q] >= j) return fail(IQHIP_ERR_INVALID, "a sweep step may only use the lengths of earlier steps");
         total_ops += (size_t)st.nops;
     }
-    if (!e->shards.empty() || e->comm || e->n_unobs > 0 || !e->sweep_one_submission || newton_use_chain(e) ||
+    if (!e->shards.empty() || e->comm || !e->sweep_one_submission || newton_use_chain(e) ||
         2 + total_ops + 6 * (size_t)nsteps > (size_t)e->result_cap || e->d_result != e->d_result_own)
         return sweep_sequential(e, steps, 0, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, 0, results);
     int rc = check_ready(e);
     if (rc) return rc;
-    if (e->sweep_persistent && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
+    // (+ASC: k_sweep4 has no correction; k_newton applies it to the derivatives and to both lnL of the diverged-solve rule)
+    if (e->sweep_persistent && !e->asc_active && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
         return sweep_persistent4(e, steps, nsteps, total_ops, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results);
     if (!e->h_plan_arena) {
         e->plan_arena_cap = 1 << 20;
@@ -494,29 +495,52 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
 // step ONE derivative launch (grid.y = task, branch length read from the task's device-resident state machine), ONE
 // k_reduce over 2m slab rows, ONE all-reduce of 2m doubles, ONE update kernel (thread = task); tasks that have converged
 // do nothing.  Identical sums on every rank => identical iterates, so all ranks leave the loop together.
+// +ASC: 5 rows per task and step, {df, ddf, prob_const, df_const, ddf_const} (an engine without unobserved patterns of its
+// own writes zeros into the last three); the lnL pass has its 2 rows {lnl, prob_const} as ever.
 // ---------------------------------------------------------------------------------------
+int iqhip::batch_derv_rows(const iqhip_engine *e) { return e->asc_active ? 5 : 2; }
+
 static BatchChain batch_chain_of(const iqhip_engine *e, int m) {
-    return BatchChain{e->d_theta_batch, (size_t)e->nptn_pad * e->block, e->d_bstates, m};
+    return BatchChain{e->d_theta_batch, (size_t)e->nptn_pad * e->block, e->d_bstates, m, batch_derv_rows(e),
+                      e->asc_active ? e->d_bsc : nullptr};
+}
+
+// phylokernel.h:1183-1186 on a task's all-reduced {lnl, prob_const}
+int iqhip::batch_asc_lnl(const iqhip_engine *e, double prob_const, double *lnl) {
+    if (!e->asc_active) return IQHIP_OK;
+    double lp;
+    const int rc = asc_log_term(prob_const, &lp);
+    if (rc) return rc;
+    *lnl -= e->asc_nsites * lp;
+    return IQHIP_OK;
 }
 
 int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, const NewtonState *init) {
     int rc = check_ready(e);
     if (rc) return rc;
-    if (2 * m > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many tasks in one chunk");
-    rc = ensure_slab_rows(e, std::max(5, 2 * m));
+    const int rows = batch_derv_rows(e);
+    if (rows * m > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many tasks in one chunk");
+    rc = ensure_slab_rows(e, std::max(5, rows * m));
     if (rc) return rc;
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
     if ((size_t)m * theta_stride > e->theta_batch_cap)
         HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)m * theta_stride, (size_t)m * theta_stride));
     if (m > e->bstates_cap) HIPCHK(regrow(e, &e->d_bstates, &e->bstates_cap, m, m));
+    if (e->asc_active && 2 * m > e->bsc_cap) HIPCHK(regrow(e, &e->d_bsc, &e->bsc_cap, 2 * m, 2 * m));
+    std::vector<const int16_t *> sc;
     for (int t = 0; t < m; t++) {
         DevBranch br;
         rc = build_branch(e, tasks[t].a, tasks[t].b, 0.0, -1, &br);
         if (rc) return rc;
+        sc.push_back(br.a_sc);
+        sc.push_back(br.b_sc);
         double *slot = e->d_theta_batch + (size_t)t * theta_stride;
         if (e->mfma) HIPCHK(launch_stream_mfma(e, 1, &br, 0.0, (int)e->ntiles, nullptr, -1, slot));
         else HIPCHK(launch_theta4(e, br, slot));
     }
+    // (pageable source, as the states below)
+    if (e->asc_active)
+        HIPCHK(hipMemcpyAsync(e->d_bsc, sc.data(), sizeof(const int16_t *) * sc.size(), hipMemcpyHostToDevice, e->stream));
     return eng_batch_states_write(e, m, init);
 }
 
@@ -537,8 +561,8 @@ int iqhip::eng_batch_states_read(iqhip_engine *e, int m, NewtonState *out) {
     return IQHIP_OK;
 }
 
-// one pass over the tasks' theta slots at the lengths in their state machines + k_reduce -> result[0..2m):
-// {df, ddf} at states[t].rts, or lnL at states[t].result
+// one pass over the tasks' theta slots at the lengths in their state machines + k_reduce -> result[0..2m) (+ASC
+// derivatives: [0..5m)): {df, ddf} at states[t].rts, or {lnL, prob_const} at states[t].result
 static int batch_pass_enqueue(iqhip_engine *e, int m, bool lnl) {
     if (use_device(e) != hipSuccess) return fail(IQHIP_ERR_HIP, "hipSetDevice");
     const BatchChain bc = batch_chain_of(e, m);
@@ -546,7 +570,7 @@ static int batch_pass_enqueue(iqhip_engine *e, int m, bool lnl) {
     const hipError_t s = e->mfma ? launch_stream_mfma(e, lnl ? 3 : 2, nullptr, 0.0, nwaves, nullptr, -1, nullptr, &bc)
                          : lnl   ? launch_lnl_theta4(e, 0.0, nwaves, &bc)
                                  : launch_derv4(e, 0.0, nwaves, nullptr, &bc);
-    if (s != hipSuccess || launch_reduce(e, 0, 2 * m, nwaves) != hipSuccess)
+    if (s != hipSuccess || launch_reduce(e, 0, (lnl ? 2 : bc.derv_rows) * m, nwaves) != hipSuccess)
         return fail(IQHIP_ERR_HIP, "batched chain: launch failed");
     return IQHIP_OK;
 }
@@ -629,7 +653,7 @@ static int optimize_branch_batch_comm(iqhip_engine *e, const iqhip_branch_task *
             max_steps,
             [&] {
                 int rc = eng_batch_eval_enqueue(e, m);
-                if (!rc) rc = comm_allreduce(e, 2 * m);
+                if (!rc) rc = comm_allreduce(e, batch_derv_rows(e) * m);
                 if (!rc) rc = eng_batch_update_enqueue(e, m);
                 return rc;
             },
@@ -646,16 +670,17 @@ static int optimize_branch_batch_comm(iqhip_engine *e, const iqhip_branch_task *
         if (!rc) rc = comm_allreduce(e, 2 * m);
         if (!rc) rc = read_result(e, 2 * m);
         if (rc) return rc;
-        std::vector<double> lnl((size_t)m);
-        for (int t = 0; t < m; t++) lnl[t] = e->h_result[2 * t];
+        const std::vector<double> lnl(e->h_result, e->h_result + 2 * (size_t)m);   // {lnl, prob_const} per task
         for (int t = 0; t < m; t++) {
-            results[first + t].lnl = lnl[t];
-            if (isnan(lnl[t]) || isinf(lnl[t])) {   // phylokernel.h:1091-1109: redo this task alone (same decision on every rank)
+            results[first + t].lnl = lnl[2 * t];
+            if (isnan(lnl[2 * t]) || isinf(lnl[2 * t])) {   // phylokernel.h:1091-1109: redo this task alone (same decision on every rank)
                 const iqhip_branch_task &k = tasks[first + t];
                 rc = iqhip_compute_theta(e, k.a, k.b);
                 if (!rc) rc = iqhip_lnl_from_theta(e, results[first + t].optx, &results[first + t].lnl);
-                if (rc) return rc;
+            } else {
+                rc = batch_asc_lnl(e, lnl[2 * t + 1], &results[first + t].lnl);
             }
+            if (rc) return rc;
         }
     }
     return IQHIP_OK;
@@ -686,7 +711,7 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, "bad task array");
     const char *seq_env = getenv("IQHIP_BATCH_SEQUENTIAL");   // (read per call: the tests compare the two forms)
-    const bool sequential = (seq_env && atoi(seq_env) != 0) || e->asc_active;   // (+ASC: 5-row results, one task at a time)
+    const bool sequential = seq_env && atoi(seq_env) != 0;
     if (!e->shards.empty())
         return sequential ? optimize_branch_batch_sequential(e, tasks, ntasks, sum_scale, results)
                           : sharded::optimize_branch_batch(e, tasks, ntasks, sum_scale, results);
@@ -695,7 +720,6 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
                           : optimize_branch_batch_comm(e, tasks, ntasks, sum_scale, results);
     int rc = check_ready(e);
     if (rc) return rc;
-    if (e->n_unobs > 0) return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_optimize_branch_batch: +ASC is not supported");
     std::vector<iqhip_node_op> all;
     std::vector<int> segs;
     rc = batch_gather_ops(tasks, ntasks, all, segs);
@@ -708,8 +732,8 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
         if (rc) return rc;
     }
     // workgroups per task: every workgroup of a launch must be resident (grid barrier inside each task)
-    // ... which bounds the batch by what fits the chip at once: 3 workgroups per CU (k_newton_batch: 125 VGPRs, i.e.
-    // four waves per SIMD would fit exactly -- keep a margin), fewer when its LDS (3 val arrays of a block) says so
+    // ... which bounds the batch by what fits the chip at once: 3 workgroups per CU (k_newton_batch: 145 VGPRs, i.e.
+    // three waves per SIMD), fewer when its LDS (3 val arrays of a block + the exchange and +ASC cells) says so
     const size_t newton_lds = (size_t)(3 * e->block + 8) * sizeof(double) + 64;
     const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(3, (size_t)(150 * 1024) / newton_lds));
     const int capacity = e->num_cus * wg_per_cu;

@@ -924,7 +924,7 @@ void PhyloTree::computeAllPartialLh() {
 
 void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves) {
     if (!engine || dry_run) throw std::runtime_error("evaluateNNIsBatch needs an attached engine");
-    if (allreduce_hook || n_unobserved > 0) throw std::runtime_error("evaluateNNIsBatch: sharded / +ASC runs use getBestNNIForBran");
+    if (allreduce_hook) throw std::runtime_error("evaluateNNIsBatch: runs with a caller-owned collective use getBestNNIForBran");
     computeAllPartialLh();
     pushInputs();
     struct Cand {
@@ -1029,7 +1029,7 @@ void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves) {
 
 void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves) {
     if (!engine || dry_run) throw std::runtime_error("evaluateNNIs5Batch needs an attached engine");
-    if (allreduce_hook || n_unobserved > 0) throw std::runtime_error("evaluateNNIs5Batch: sharded / +ASC runs use getBestNNIForBran");
+    if (allreduce_hook) throw std::runtime_error("evaluateNNIs5Batch: runs with a caller-owned collective use getBestNNIForBran");
     computeAllPartialLh();
     pushInputs();
     // an outward subtree vector around the branch: fixed while the candidate is evaluated
