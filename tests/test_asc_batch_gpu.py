@@ -196,11 +196,12 @@ def oracle_swap(ot, node1, node2, nei1, nei2, new_len):
 NNI_MAX_NR_STEP = 10   # the step limit of the NNI evaluators (phylotree.h), batched and branch by branch alike
 
 
-def oracle_candidates(oracle, inputs, n, seq_type, batch):
-    """every candidate of `batch` on the oracle: [(optimum, evaluated points, lnL of the swapped tree at the batch's length)]"""
+def oracle_candidates(make_ot, batch):
+    """every candidate of `batch` on the oracle, each on a fresh tree from make_ot():
+    [(optimum, evaluated points, lnL of the swapped tree at the batch's length)]"""
     out = []
     for k, m in enumerate(batch):
-        ot = asc_oracle(oracle, inputs, n, seq_type)
+        ot = make_ot()
         a, b = m["node1"], m["node2"]
         # (the second swap of a branch starts from the length the first swap's solve left: phylotree.cpp:3036-3051)
         start = ot.length(a, b) if k % 2 == 0 else batch[k - 1]["new_len"]
@@ -220,7 +221,7 @@ def test_asc_batch_against_the_oracle(pkg, synth, oracle, n, ncat, seq_type, nta
     c0 = t.num_derv_calls
     batch = t.evaluate_nnis_batch()
     nevals = t.num_derv_calls - c0
-    ref = oracle_candidates(oracle, inputs, n, seq_type, batch)
+    ref = oracle_candidates(lambda: asc_oracle(oracle, inputs, n, seq_type), batch)
     assert all(r[0] <= 0.95 * 100.0 for r in ref)                     # no candidate takes the diverged-solve detour
     best = max(range(len(batch)), key=lambda k: batch[k]["newloglh"])
     optx, pts, lnl = ref[best]

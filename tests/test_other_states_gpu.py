@@ -15,13 +15,14 @@ pytestmark = pytest.mark.gpu
 SEQ_OTHER = 3
 
 
-def build(pkg, synth, oracle, n, ncat, ntaxa, nsites, seed, multif=False, **kw):
+def build(pkg, synth, oracle, n, ncat, ntaxa, nsites, seed, multif=False, mem_mode=0, **kw):
     model = synth.random_reversible_model(n, seed, alpha=0.9 if ncat > 1 else None, ncat=ncat)
     nwk = synth.random_multifurcating_newick(ntaxa, seed) if multif else synth.random_tree_newick(ntaxa, seed, **kw)
     st = synth.simulate_alignment(nwk, model, nsites, seed + 1, 0.04, n)   # 4 % missing characters (state n)
     pat, freq = synth.compress_patterns(st)
     ot = oracle.OracleTree(nwk, n, SEQ_OTHER, pat, freq, None, model)
     t = pkg.PhyloTree(nwk)
+    t.set_mem_mode(mem_mode)
     t.set_alignment(n, SEQ_OTHER, pat, freq)
     t.set_model(model)
     t.set_likelihood_kernel(pkg.LK_EIGEN_HIP)
