@@ -18,7 +18,7 @@ all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/lib
 $(LIBDIR):
 	mkdir -p $(LIBDIR)
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h include/iqhip.h | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/trav_lds.h include/iqhip.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIBDIR)/libiqhip.so: $(HIP_OBJS)

@@ -383,6 +383,17 @@ int iqhip_debug_path_counts(iqhip_engine *e, int64_t *out, int n);
 int iqhip_debug_create_planner(iqhip_engine **out, int nstates /* 4, 20, 64 */, int ncat, int64_t nptn, int ntaxa,
                                int num_cus, int state_unknown, int nclass);
 int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
+/* Read-only: the shape of the planner's last plan and the launches it would get, out[k] for k < IQHIP_PLAN_SHAPE_NSLOTS
+ * (n must be at least that):
+ *   0..5    LDS budget of a chunk (doubles), plan regions of the largest chunk (doubles), leaf-state slots, parked operands,
+ *           LDS chunks, stages of units
+ *   6..13   units per stage (the first 8 stages)
+ *   14..20  the top-stage launch: kernel variant (the engine's TravVariant; -1: the 4-state kernel), leaf tables, full-role
+ *           workgroups of a mixed-role launch, workgroups per segment, grid, dynamic LDS bytes, offset of the parking places
+ *           (doubles, -1: none)
+ *   21..27  the same for the first stage of units (zeros: the plan has none) */
+#define IQHIP_PLAN_SHAPE_NSLOTS 28
+int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n);
 
 #ifdef __cplusplus
 }

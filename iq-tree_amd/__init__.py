@@ -35,10 +35,15 @@ IQHIP_SYMBOLS = [
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
     "iqhip_debug_create_planner", "iqhip_debug_plan", "iqhip_timing_plan_bytes", "iqhip_timing_collective_read", "iqhip_optimize_sweep", "iqhip_debug_cherry_tables",
-    "iqhip_debug_path_counts",
+    "iqhip_debug_path_counts", "iqhip_debug_plan_shape",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
+# slots of iqhip_debug_plan_shape (include/iqhip.h IQHIP_PLAN_SHAPE_NSLOTS)
+_LAUNCH_SLOTS = ("variant", "tab", "nfull", "ngroups", "grid", "lds_bytes", "hold_off")
+PLAN_SHAPE_SLOTS = (("lds_budget", "lds_doubles", "state_slots", "nhold", "chunks", "stages") +
+                    tuple("stage_units_%d" % s for s in range(8)) +
+                    tuple("top_" + f for f in _LAUNCH_SLOTS) + tuple("unit_" + f for f in _LAUNCH_SLOTS))
 PATH_SLOTS = ("newton_one_launch", "newton_chain", "sweep_persistent", "sweep_per_step", "sweep_sequential",
               "newton_fallback")
 
@@ -151,6 +156,7 @@ def libiqhip():
     lib.iqhip_debug_cherry_tables.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.iqhip_debug_path_counts.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_plan.argtypes = [vp, C.POINTER(NodeOp), C.c_int]
+    lib.iqhip_debug_plan_shape.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib._iq_typed = True
     return lib
 

@@ -103,6 +103,14 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
         e->top_cs2 = !e->cat_split && e->ntiles < 6 * (int64_t)e->num_cus * 4;
         if (const char *cs = getenv("IQHIP_TOP_CS2")) e->top_cs2 = atoi(cs) != 0;
     }
+    if (e->n == 20) {
+        e->mix_generic = getenv("IQHIP_MIX_GENERIC") != nullptr;
+        // the mixture kernel's component split while the alignment is small (at most 3/4 tile per SIMD: 10k patterns x 40
+        // components 1.96 -> 1.77 ms, but 30k patterns x 8 components 1.78 -> 2.62 ms) and the components divide by 4
+        e->mix_split = 4 * e->ntiles <= 3 * (int64_t)e->num_cus * 4;
+        if (const char *cs = getenv("IQHIP_CAT_SPLIT")) e->mix_split = atoi(cs) != 0;
+        e->mix_split = e->mix_split && e->ncat % 4 == 0;
+    }
     if (e->mfma_pipelined_ok && e->n == 64 && e->ncat == 1) {
         e->row_split = 4 * e->ntiles <= (int64_t)e->num_cus * 4;
         if (const char *rs = getenv("IQHIP_ROW_SPLIT")) e->row_split = atoi(rs) != 0;
@@ -1455,4 +1463,33 @@ extern "C" int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int n
         for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops[k].cherry != nullptr;
     }
     return rc;
+}
+
+// the shape of the last plan and of the launches it would get (tests/test_plan_check.py pins them)
+extern "C" int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n) {
+    if (!e || !e->planner || !out || n < IQHIP_PLAN_SHAPE_NSLOTS)
+        return fail(IQHIP_ERR_INVALID, "iqhip_debug_plan_shape needs a planning-only engine and IQHIP_PLAN_SHAPE_NSLOTS slots");
+    std::fill(out, out + n, (int64_t)0);
+    const Plan &p = e->plan;
+    const int nops = p.small_nops;   // (the plan's op count, small or not)
+    int chunks = 0;
+    for (int k = 0; k < nops; k += e->h_ops[k].chunk_nops) chunks++;
+    out[0] = lds_budget(e); out[1] = p.lds_doubles; out[2] = p.state_slots; out[3] = p.nhold; out[4] = chunks;
+    out[5] = (int64_t)p.stage_units.size();
+    for (size_t s = 0; s < p.stage_units.size() && s < 8; s++) out[6 + s] = p.stage_units[s];
+    auto launch = [&](int64_t *o, bool top_stage, int nsegs) {
+        TravLaunch L = {TRAV_NONE, false, 0, 0, 0, 0, -1};
+        if (e->mfma) L = choose_traverse_mfma(e, top_stage, nsegs);
+        else {   // k_traverse4 (kernels_valu4.hip launch_traverse4)
+            L.variant = (TravVariant)-1;
+            L.ngroups = trav4_ngroups(e);
+            L.grid = L.ngroups * nsegs;
+            L.lds_bytes = trav4_lds_bytes(e->block, e->wg_size, p.lds_doubles, p.state_slots);
+        }
+        const int64_t v[7] = {L.variant, L.tab, L.nfull, L.ngroups, L.grid, (int64_t)L.lds_bytes, L.hold_off};
+        std::copy(v, v + 7, o);
+    };
+    launch(out + 14, true, nops > 0 ? 1 : 0);
+    if (!p.stage_units.empty()) launch(out + 21, false, p.stage_units[0]);
+    return IQHIP_OK;
 }

@@ -17,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 #include "../../include/iqhip.h"
+#include "trav_lds.h"
 
 namespace iqhip {
 
@@ -286,6 +287,8 @@ struct iqhip_engine {
     bool top_cs2 = false;   // 20 states, 4 categories: the sequential top stage with two waves per tile (two categories each), IQHIP_TOP_CS2
     int lane_split = 1;    // 4-state traversal: lanes per pattern (2: each lane owns half of the categories)
     int lane_split_valu = 1;  // ... remembered while a 4-state engine runs a mixture on the matrix-core kernels
+    bool mix_generic = false; // 20-state mixtures and unpipelined category counts on the generic kernel instead of k_traverse_mfma_mix20 (IQHIP_MIX_GENERIC)
+    bool mix_split = false;   // k_traverse_mfma_mix20: one wave per quarter of a tile's components (small alignments; IQHIP_CAT_SPLIT)
     bool mixed_top = true; // 64 states: mixed-role top stage (kernels_mfma.hip k_traverse_mfma_top64; IQHIP_MIXED_TOP)
     bool use_hold = true;  // 4-state traversal: park join operands in a second register set (IQHIP_HOLD)
     // 20-state pipelined kernel: the same idea with the parking place in LDS (10 KB per wave) -- a result that is the
@@ -671,6 +674,47 @@ int resolve_child(iqhip_engine *e, uint64_t key, int32_t leaf, int prev_dst, con
 // After a model change every K2 table is stale: forget what the slots were built for, except the current plan's tables,
 // which are then all (re)built.  Returns whether the model changed.
 bool leaf_tables_follow_model(iqhip_engine *e);
+int lds_budget(const iqhip_engine *e);   // doubles of LDS one chunk's per-(op, child) regions may use
+
+// The dispatch of the matrix-core traversal kernels (kernels_mfma.hip), decided in one place without a HIP call, so that
+// the planner and a planning-only engine ask the same function the launcher does.
+enum TravVariant : int {
+    TRAV_NONE = 0,           // no kernel for this shape
+    TRAV_GENERIC,            // k_traverse_mfma<n, 256, nclass > 1>; 4-state mixtures: <4, 256, true>
+    TRAV_MIX20,              // k_traverse_mfma_mix20<256, 1>
+    TRAV_MIX20_SPLIT,        // k_traverse_mfma_mix20<256, 4>
+    TRAV_M2,                 // k_traverse_mfma2<n, ncat, 256, 1, tab>
+    TRAV_M2_CAT_SPLIT,       // k_traverse_mfma2<20, 1, 256, 4, tab>
+    TRAV_M2_TOP_CS2,         // k_traverse_mfma2<20, 2, 256, 2, false>
+    TRAV_TOP20,              // k_traverse_mfma_top20
+    TRAV_ROWS64,             // k_traverse_mfma_rows64<256, tab>
+    TRAV_TOP64,              // k_traverse_mfma_top64<tab>
+};
+struct TravLaunch {
+    TravVariant variant;
+    bool tab;        // leaf children from the K2 tables
+    int nfull;       // mixed-role launches: workgroups of the full role (they come first), else 0
+    int ngroups;     // workgroups per segment (mixed-role launches: of the other role)
+    int grid;
+    size_t lds_bytes;
+    int hold_off;    // TravMArgs::hold_off
+};
+TravLaunch choose_traverse_mfma(const iqhip_engine *e, bool top_stage, int nsegs);
+// what the planner has to know of that choice before the plan exists
+// the top stage may run with several waves per tile (TRAV_M2_TOP_CS2, TRAV_TOP20): no parking places, no cherry block there
+inline bool top_stage_may_share_tiles(const iqhip_engine *e) { return e->top_cs2; }
+// 64 states: the top stage may give its last tiles to row-split workgroups (TRAV_TOP64)
+inline bool top_stage_may_mix_roles64(const iqhip_engine *e) { return e->n == 64 && e->mixed_top; }
+// workgroups per segment of k_traverse4: one wave per tile and lane split
+inline int trav4_ngroups(const iqhip_engine *e) {
+    const int wpb = e->wg_size / 64;
+    return (int)((e->ntiles * e->lane_split + wpb - 1) / wpb);
+}
+// the engine's kernel reads a small plan out of its arguments (Plan::small): k_traverse4 and the 20-state pipelined
+// kernels without leaf tables (tables come with a job list in the plan buffer)
+inline bool kernel_takes_small_plan(const iqhip_engine *e) {
+    return !e->mfma || (e->mfma_pipelined && e->n == 20 && !e->leaf_tables && e->plan.nleaf_tabs == 0);
+}
 
 // comm.hip -- RCCL, loaded lazily.  comm_allreduce: in-place SUM/f64 all-reduce of the first n doubles of the
 // engine's device result vector on its stream (no-op without a communicator).  comm_group_allreduce: the same for
@@ -877,7 +921,6 @@ hipError_t launch_leaf_tables(iqhip_engine *e, const TabJob *d_jobs, int njobs);
 // cherry tables: src[i] (tile layout, npairs patterns) -> dst[i] (register order of the traversal kernel), host pointer arrays
 hipError_t launch_cherry_transpose(iqhip_engine *e, const double *const *src, double *const *dst, int n, int npairs);
 size_t leaf_table_doubles(const iqhip_engine *e);          // doubles per (leaf child) table: ncat * state_unknown * n
-int mfma2_fixed_lds_doubles(int n);
 // mode 0: branch lnL, 1: theta, 2: df/ddf from theta, 3: lnL from theta
 // theta_out (mode 1): write theta there instead of the engine's buffer; bc (modes 2, 3): batched chain, see BatchChain
 hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, double len, int nwaves,

@@ -202,11 +202,12 @@ __global__ __launch_bounds__(WG) void k_traverse_mfma(const TravMArgs A) {
     constexpr int KS = N / 4;          // k-steps of 4
     constexpr int WPB = WG / 64;
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    double *sU = smem;                       // [MT][KS][64]   A image of U     (rows x, k = i)
-    double *sUi = sU + MT * KS * 64;         // [MT][KS][64]   A image of U^-1  (rows i, k = x)
-    double *sTipx = sUi + MT * KS * 64;      // [nx][N]        tip vectors of states >= N
     const int nx = A.state_unknown + 1 - N;
-    double *sReg = sTipx + nx * N;           // per (op, child) exponentials [C*N] of the chunk
+    const GenericLds L = generic_lds(N, nx);
+    double *sU = smem + L.sU;                // [MT][KS][64]   A image of U     (rows x, k = i)
+    double *sUi = smem + L.sUi;              // [MT][KS][64]   A image of U^-1  (rows i, k = x)
+    double *sTipx = smem + L.sTipx;          // [nx][N]        tip vectors of states >= N
+    double *sReg = smem + L.sReg;            // per (op, child) exponentials [C*N] of the chunk
     const int C = A.ncat;
     const int B = C * N;
 
@@ -510,23 +511,26 @@ __device__ __forceinline__ void trav_mfma2_body(const TravMArgs &A, const int vb
     constexpr int B = CT * N;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // (20 states keep the fragments of U / U^-1 in registers, AREG below: no LDS image)
-    constexpr int IMG1 = (N < 64) ? 0 : MTF * KS * 64, IMG4 = (N < 64) ? 0 : (TAIL4 ? KS * 64 : 0);
-    double *sU = smem;                           // [MTF][KS][64]
-    double *sUi = sU + IMG1;                     // [MTF][KS][64]
-    double *sU4 = sUi + IMG1;                    // [KS][64] tail rows (TAIL4)
-    double *sUi4 = sU4 + IMG4;
+    constexpr Mfma2Lds L = mfma2_lds(N, 0);      // (nx moves sReg only)
+    double *sU = smem + L.sU;                    // [MTF][KS][64]
+    double *sUi = smem + L.sUi;                  // [MTF][KS][64]
+    double *sU4 = smem + L.sU4;                  // [KS][64] tail rows (TAIL4)
+    double *sUi4 = smem + L.sUi4;
     // tip_partial_lh rows of states < N (= columns of U^-1): a plain [N][N] copy when it is small,
     // otherwise read out of the U^-1 fragment image
-    constexpr bool TIP_COPY = (N * N * 8 <= 4096);
-    double *sUiT = sUi4 + IMG4;
-    double *sTipx = sUiT + (TIP_COPY ? N * N : 0);
+    constexpr bool TIP_COPY = L.tip_copy;
+    double *sUiT = smem + L.sUiT;
+    double *sTipx = smem + L.sTipx;
     const int nx = A.state_unknown + 1 - N;
+    // = smem + mfma2_lds(N, nx).sReg (static_assert below).  Spelled as the sum: with the run-time nx passed through the
+    // layout function the 64-state body compiles to other address arithmetic (one SGPR less, 4 bytes more)
     double *sReg = sTipx + nx * N;
+    static_assert(mfma2_lds(N, 3).sReg == L.sTipx + 3 * N, "sReg follows the [nx][N] tip vectors");
 
     // fragment images of U and U^-1: a straight 16-byte copy of the engine's pre-formatted image (only the 64-state
     // instantiations read them from LDS; 20 states keep the fragments in registers, read below)
     if constexpr (N >= 64) {
-        constexpr int NIMG2 = (2 * MTF * KS * 64 + (TAIL4 ? 2 * KS * 64 : 0)) / 2;
+        constexpr int NIMG2 = L.sUiT / 2;   // (the images are the layout's first regions)
         const double2 *src = reinterpret_cast<const double2 *>(A.aimg);
         double2 *dst2 = reinterpret_cast<double2 *>(smem);
 #pragma unroll 8
@@ -1071,49 +1075,6 @@ __global__ __launch_bounds__(256, 3) void k_traverse_mfma_top20(const TravMArgs 
     else trav_mfma2_body<20, 1, 256, 4, false>(R, (int)blockIdx.x - nfull, tile0R);
 }
 
-static hipError_t launch_trav_top20(iqhip_engine *e, TravMArgs &A, int nfull_wg) {
-    const int nx = e->state_unknown + 1 - 20;
-    const size_t lds = (size_t)(mfma2_fixed_lds_doubles(20) + nx * 20 + e->plan.lds_doubles) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_top20), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-    A.hold_off = -1;
-    if (e->plan.small && A.nsegs_launch == 1) {
-        A.small_plan = 1;
-        A.small_segs[0] = 0;
-        A.small_segs[1] = e->plan.small_nops;
-        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
-    }
-    TravMArgs F = A, R = A;
-    F.ntiles = (int64_t)nfull_wg * 2;
-    F.ngroups = nfull_wg;
-    const int nrest = (int)(A.ntiles - F.ntiles);
-    R.ngroups = nrest;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_traverse_mfma_top20, dim3((unsigned)(nrest + nfull_wg)), dim3(256), lds, e->stream, F, nfull_wg, R, F.ntiles);
-    return hipGetLastError();
-}
-
-template <int N, bool MIX>
-static hipError_t launch_trav_m(iqhip_engine *e, TravMArgs &A) {
-    constexpr int MT = (N + 15) / 16, KS = N / 4, WG = 256;
-    const int nx = e->state_unknown + 1 - N;
-    const size_t lds = (size_t)(2 * MT * KS * 64 + nx * N + e->plan.lds_doubles) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma<N, WG, MIX>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    A.ngroups = (int)((A.ntiles + 3) / 4);
-    const int grid = A.ngroups * A.nsegs_launch;
-    hipLaunchKernelGGL((k_traverse_mfma<N, WG, MIX>), dim3(grid), dim3(WG), lds, e->stream, A);
-    return hipGetLastError();
-}
-
-
 // ---------------------------------------------------------------------------------------
 // Mixture models (phylokernelmixture.h:20-460, phylokernelmixrate.h:22-450), 20 states.  The block of a
 // pattern is C = (class, rate) components x 20 doubles -- too large for the register-resident scheme of
@@ -1127,7 +1088,7 @@ template <int WG, int CS>
 __global__ __launch_bounds__(WG, 2) void k_traverse_mfma_mix20(const TravMArgs A) {
     constexpr int N = 20, KS = 5, WPB = WG / 64;
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    double *sReg = smem;  // per (op, child) exponentials [C*N] of the chunk
+    double *sReg = smem + mix20_lds().sReg;  // per (op, child) exponentials [C*N] of the chunk
     const int C = A.ncat;
     const int B = C * N;
     const int lane = threadIdx.x & 63;
@@ -1270,30 +1231,6 @@ __global__ __launch_bounds__(WG, 2) void k_traverse_mfma_mix20(const TravMArgs A
     }
 }
 
-template <int CS>
-static hipError_t launch_trav_mix20_cs(iqhip_engine *e, TravMArgs &A) {
-    constexpr int WG = 256;
-    const size_t lds = (size_t)e->plan.lds_doubles * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_mix20<WG, CS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-    A.ngroups = (int)((A.ntiles * CS + 3) / 4);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_traverse_mfma_mix20<WG, CS>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(WG), lds, e->stream, A);
-    return hipGetLastError();
-}
-
-static hipError_t launch_trav_mix20(iqhip_engine *e, TravMArgs &A) {
-    // component split while the alignment is small (at most 3/4 tile per SIMD: 10k patterns x 40 components 1.96 ->
-    // 1.77 ms, but 30k patterns x 8 components 1.78 -> 2.62 ms) and the components divide by 4
-    bool split = (e->ncat % 4 == 0) && 4 * e->ntiles <= 3 * (int64_t)e->num_cus * 4;
-    if (const char *cs = getenv("IQHIP_CAT_SPLIT")) split = (atoi(cs) != 0) && (e->ncat % 4 == 0);
-    return split ? launch_trav_mix20_cs<4>(e, A) : launch_trav_mix20_cs<1>(e, A);
-}
-
 // ---------------------------------------------------------------------------------------
 // 64 states, small alignments: ROW SPLIT.  The four waves of a workgroup share one tile; wave w owns the output
 // rows [16w, 16w+16) of every product (one M-tile), i.e. 48 instead of 192 dependent MFMAs per op.  Its 2 x 16 A
@@ -1309,10 +1246,11 @@ __device__ __forceinline__ void trav_rows64_body(const TravMArgs &A, const int v
     static_assert(WG == 256, "one tile per workgroup of four waves");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int nx = A.state_unknown + 1 - N;
-    double *sTip = smem;                       // [N + nx][N] tip_partial_lh rows
-    double *sX = sTip + (N + nx) * N;          // [2 parities][KS][64] previous result as k-step slices
-    double *sT = sX + 2 * KS * 64;             // [2 parities][KS][64] Hadamard product
-    double *sReg = sT + 2 * KS * 64;           // per (op, child) exponentials [N] of the chunk
+    const Rows64Lds L = rows64_lds(nx);
+    double *sTip = smem + L.sTip;              // [N + nx][N] tip_partial_lh rows
+    double *sX = smem + L.sX;                  // [2 parities][KS][64] previous result as k-step slices
+    double *sT = smem + L.sT;                  // [2 parities][KS][64] Hadamard product
+    double *sReg = smem + L.sReg;              // per (op, child) exponentials [N] of the chunk
     __shared__ unsigned s_lmax[2][4][16];
     for (int t = threadIdx.x; t < (N + nx) * N; t += WG) sTip[t] = A.tip[t];
 
@@ -1487,79 +1425,50 @@ __global__ __launch_bounds__(256, 2) void k_traverse_mfma_top64(const TravMArgs 
     else trav_rows64_body<256, TAB>(R, (int)blockIdx.x - nfull, (int64_t)nfull * 4);
 }
 
+// One launch of the kernel the chooser picked: its dynamic-LDS ceiling is raised the first time it is used
+template <auto Kernel, int MaxLdsBytes = kTravMaxLdsBytes, typename... Args>
+static hipError_t launch_trav(iqhip_engine *e, const TravLaunch &L, const Args &...args) {
+    static bool attr_set = false;   // (per instantiation, i.e. per kernel)
+    if (!attr_set) {
+        hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MaxLdsBytes);
+        attr_set = true;
+    }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)L.grid), dim3(kTravWg), L.lds_bytes, e->stream, args...);
+    return hipGetLastError();
+}
+
+// TravVariant -> kernel instantiation.  F: the arguments of a mixed-role launch's full role (its tiles come first).
 template <bool TAB>
-static hipError_t launch_trav_rows64(iqhip_engine *e, TravMArgs &A) {
-    constexpr int WG = 256;
-    const int nx = e->state_unknown + 1 - 64;
-    const size_t lds = (size_t)((64 + nx) * 64 + 4 * 16 * 64 + e->plan.lds_doubles) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_rows64<WG, TAB>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
+static hipError_t launch_variant(iqhip_engine *e, const TravLaunch &L, const TravMArgs &A, const TravMArgs &F) {
+    const int n = e->n, C = e->ncat;
+    switch (L.variant) {
+        case TRAV_M2:
+            if (n == 64) return launch_trav<k_traverse_mfma2<64, 1, kTravWg, 1, TAB>>(e, L, A);
+            if (C == 4) return launch_trav<k_traverse_mfma2<20, 4, kTravWg, 1, TAB>>(e, L, A);
+            return launch_trav<k_traverse_mfma2<20, 1, kTravWg, 1, TAB>>(e, L, A);
+        case TRAV_M2_CAT_SPLIT: return launch_trav<k_traverse_mfma2<20, 1, kTravWg, 4, TAB>>(e, L, A);
+        case TRAV_ROWS64: return launch_trav<k_traverse_mfma_rows64<kTravWg, TAB>>(e, L, A);
+        case TRAV_TOP64: return launch_trav<k_traverse_mfma_top64<TAB>>(e, L, F, L.nfull, A);
+        default: break;
     }
-    A.ngroups = (int)A.ntiles;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_traverse_mfma_rows64<WG, TAB>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(WG), lds, e->stream, A);
-    return hipGetLastError();
-}
-
-// LDS doubles of k_traverse_mfma2 that do not depend on the plan (A images, tail images, U^-1 transposed)
-int mfma2_fixed_lds_doubles(int n) {
-    const int mtf = n / 16, ks = n / 4;
-    const int images = n < 64 ? 0 : 2 * mtf * ks * 64 + ((n % 16) == 4 ? 2 * ks * 64 : 0);   // (20 states: fragments in registers)
-    return images + (n * n * 8 <= 4096 ? n * n : 0);
-}
-
-template <int N, int C, int CS = 1, bool TAB = false>
-static hipError_t launch_trav_m2(iqhip_engine *e, TravMArgs &A) {
-    constexpr int KS = N / 4, WG = 256;
-    const int nx = e->state_unknown + 1 - N;
-    size_t lds = (size_t)(mfma2_fixed_lds_doubles(N) + nx * N + e->plan.lds_doubles) * sizeof(double);
-    A.hold_off = -1;
-    if (N < 64 && CS == 1 && e->plan.nhold > 0) {   // parking places: one tile vector (16 patterns x block) per tile
-        A.hold_off = (int)(lds / sizeof(double));
-        lds += (size_t)(WG / 64 / CS) * 16 * e->block * sizeof(double);
+    if constexpr (!TAB) {   // (the variants without a table form)
+        const bool mix = e->nclass > 1;
+        switch (L.variant) {
+            case TRAV_M2_TOP_CS2: return launch_trav<k_traverse_mfma2<20, 2, kTravWg, 2, false>>(e, L, A);
+            case TRAV_TOP20: return launch_trav<k_traverse_mfma_top20>(e, L, F, L.nfull, A, F.ntiles);
+            case TRAV_MIX20: return launch_trav<k_traverse_mfma_mix20<kTravWg, 1>>(e, L, A);
+            case TRAV_MIX20_SPLIT: return launch_trav<k_traverse_mfma_mix20<kTravWg, 4>>(e, L, A);
+            case TRAV_GENERIC:
+                if (n == 4) return launch_trav<k_traverse_mfma<4, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A);
+                if (n == 20) return mix ? launch_trav<k_traverse_mfma<20, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A)
+                                        : launch_trav<k_traverse_mfma<20, kTravWg, false>, kTravGenericMaxLdsBytes>(e, L, A);
+                return mix ? launch_trav<k_traverse_mfma<64, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A)
+                           : launch_trav<k_traverse_mfma<64, kTravWg, false>, kTravGenericMaxLdsBytes>(e, L, A);
+            default: break;
+        }
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma2<N, C, WG, CS, TAB>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-    A.ngroups = (int)((A.ntiles * CS + 3) / 4);
-    const int grid = A.ngroups * A.nsegs_launch;
-    if (e->plan.small && A.nsegs_launch == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
-        A.small_plan = 1;
-        A.small_segs[0] = 0;
-        A.small_segs[1] = e->plan.small_nops;
-        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
-    }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_traverse_mfma2<N, C, WG, CS, TAB>), dim3(grid), dim3(WG), lds, e->stream, A);
-    return hipGetLastError();
-}
-
-// the mixed-role top stage (k_traverse_mfma_top64): full-chain workgroups for whole rounds of the chip, row-split
-// workgroups for the tiles that are left over
-template <bool TAB>
-static hipError_t launch_trav_top64(iqhip_engine *e, TravMArgs &A, int nfull) {
-    const int nx = e->state_unknown + 1 - 64;
-    const size_t fixed = std::max<size_t>((size_t)mfma2_fixed_lds_doubles(64) + (size_t)nx * 64, (size_t)(64 + nx) * 64 + 4 * 16 * 64);
-    const size_t lds = (fixed + e->plan.lds_doubles) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse_mfma_top64<TAB>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        attr_set = true;
-    }
-    TravMArgs F = A, R = A;
-    F.ntiles = (int64_t)nfull * 4;
-    F.ngroups = nfull;
-    R.ngroups = (int)(A.ntiles - F.ntiles);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((k_traverse_mfma_top64<TAB>), dim3((unsigned)(nfull + R.ngroups)), dim3(256), lds, e->stream, F, nfull, R);
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 #ifdef IQHIP_WAVE_TRACE
@@ -1640,51 +1549,21 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
     A.small_segs[0] = A.small_segs[1] = 0;
     for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = DevOp{};
     if (nsegs <= 0) return hipSuccess;
-    if (e->mfma_pipelined && top_stage && nsegs == 1 && e->n == 64 && e->ncat == 1 && !e->row_split && e->mixed_top) {
-        // whole rounds of one chain per SIMD go to full-chain workgroups, a small remainder to row-split ones
-        const int64_t per_round = (int64_t)e->num_cus * 4;
-        const int64_t rounds = e->ntiles / per_round, rest = e->ntiles - rounds * per_round;
-        if (rounds >= 1 && rest > 0 && rest <= per_round / 2) {
-            const int nfull = (int)(rounds * e->num_cus);
-            return (e->plan.nleaf_tabs > 0 || e->leaf_tables) ? launch_trav_top64<true>(e, A, nfull) : launch_trav_top64<false>(e, A, nfull);
-        }
+    const TravLaunch L = choose_traverse_mfma(e, top_stage, nsegs);
+    A.ngroups = L.ngroups;
+    A.hold_off = L.hold_off;
+    if (e->plan.small && nsegs == 1) {   // (the plan was not copied to d_ops: it travels with the launch; Plan::small
+        // implies a kernel that reads it there, kernel_takes_small_plan)
+        A.small_plan = 1;
+        A.small_segs[1] = e->plan.small_nops;
+        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
     }
-    if (e->mfma_pipelined) {  // plan was built in canonical (PF, PREV) form
-        if (e->plan.nleaf_tabs > 0 || e->leaf_tables) {  // leaf children from the K2 tables (k_leaf_tables)
-            if (e->n == 20 && e->ncat == 4)
-                return e->cat_split ? launch_trav_m2<20, 1, 4, true>(e, A) : launch_trav_m2<20, 4, 1, true>(e, A);
-            if (e->n == 20 && e->ncat == 1) return launch_trav_m2<20, 1, 1, true>(e, A);
-            if (e->n == 64 && e->ncat == 1) return e->row_split ? launch_trav_rows64<true>(e, A) : launch_trav_m2<64, 1, 1, true>(e, A);
-            return hipErrorInvalidValue;
-        }
-        if (e->n == 20 && e->ncat == 4) {
-            if (e->cat_split) return launch_trav_m2<20, 1, 4>(e, A);
-            if (e->top_cs2 && top_stage) {
-                // whole rounds of two-waves-per-tile workgroups; a small remainder as one wave per category (launch_trav_top20)
-                const bool mixed20 = e->mixed_top;
-                const int64_t per_round = (int64_t)e->num_cus * 3 * 2;
-                const int64_t rounds = e->ntiles / per_round, rest = e->ntiles - rounds * per_round;
-                if (mixed20 && nsegs == 1 && rounds >= 1 && rest > 0 && rest <= per_round / 4)
-                    return launch_trav_top20(e, A, (int)(rounds * e->num_cus * 3));
-                return launch_trav_m2<20, 2, 2>(e, A);
-            }
-            return launch_trav_m2<20, 4>(e, A);
-        }
-        if (e->n == 20 && e->ncat == 1) return launch_trav_m2<20, 1>(e, A);
-        if (e->n == 64 && e->ncat == 1) return e->row_split ? launch_trav_rows64<false>(e, A) : launch_trav_m2<64, 1>(e, A);
-        return hipErrorInvalidValue;
+    TravMArgs F = A;
+    if (L.nfull > 0) {
+        F.ngroups = L.nfull;
+        F.ntiles = (int64_t)L.nfull * (L.variant == TRAV_TOP20 ? 2 : 4);   // (two waves / one wave per tile in the full role)
     }
-    switch (e->n) {
-        case 20:
-            if (e->nclass > 1) return getenv("IQHIP_MIX_GENERIC") ? launch_trav_m<20, true>(e, A) : launch_trav_mix20(e, A);
-            // plain model, category count without a pipelined instantiation (+G8, +R5, ...): the mixture kernel
-            // with one class (16+4-row MFMA split, A fragments in registers) beats the padded generic kernel
-            if (e->d_img && !getenv("IQHIP_MIX_GENERIC")) return launch_trav_mix20(e, A);
-            return launch_trav_m<20, false>(e, A);
-        case 64: return e->nclass > 1 ? launch_trav_m<64, true>(e, A) : launch_trav_m<64, false>(e, A);
-        case 4: return launch_trav_m<4, true>(e, A);  // 4-state mixtures (a plain 4-state model never comes here)
-        default: return hipErrorInvalidValue;
-    }
+    return L.tab ? launch_variant<true>(e, L, A, F) : launch_variant<false>(e, L, A, F);
 }
 
 // ---------------------------------------------------------------------------------------

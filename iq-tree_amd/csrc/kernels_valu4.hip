@@ -268,9 +268,10 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
     constexpr int CL = C / SP, BL = 4 * CL;  // categories / doubles per lane
     constexpr int WPB = WG / 64;  // waves per block (64 patterns each, 32 with SP = 2)
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    double *s_tip = smem;             // [32][4]
-    double *s_val = smem + 128;       // [B]
-    double *s_reg = smem + 128 + B;   // per (op, child) regions of the current chunk
+    constexpr Trav4Lds L = trav4_lds(B, WG);
+    double *s_tip = smem + L.s_tip;   // [32][4]
+    double *s_val = smem + L.s_val;   // [B]
+    double *s_reg = smem + L.s_reg;   // per (op, child) regions of the current chunk
     uint8_t *s_states = reinterpret_cast<uint8_t *>(s_reg + A.lds_reg_doubles);  // [slot][WG] leaf states
 
     __shared__ double s_model[32];    // U [16], eigenvalues [4], rates [C <= 8]: the chunk fills read them many times
@@ -583,16 +584,14 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
 template <int C, int WG, bool HAS_LOAD, int SP, bool USE_HOLD>
 static hipError_t launch_trav_h(iqhip_engine *e, Trav4Args &A) {
     constexpr int B = 4 * C;
-    const size_t lds = (size_t)(128 + B + (size_t)e->plan.lds_doubles) * sizeof(double) +
-                       (size_t)e->plan.state_slots * WG;
+    const size_t lds = trav4_lds_bytes(B, WG, e->plan.lds_doubles, e->plan.state_slots);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);  // (160 KB minus the static arrays: fold_tail, the fill's descriptor copies)
+                            hipFuncAttributeMaxDynamicSharedMemorySize, kTrav4MaxLdsBytes);
         attr_set = true;
     }
-    constexpr int WPB = WG / 64;
-    A.ngroups = (int)((e->ntiles * SP + WPB - 1) / WPB);
+    A.ngroups = trav4_ngroups(e);
     hipLaunchKernelGGL((k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(WG), lds, e->stream, A);
     return hipGetLastError();
 }

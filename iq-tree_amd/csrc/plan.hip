@@ -302,7 +302,7 @@ void park_operands(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         producer[d.dst] = k;
         if (j < 0) continue;
         bool ok = !e->h_ops[j].push_hold && seg_of[j] == seg_of[k];
-        if (hold_in_lds && e->top_cs2 && seg_of[k] == 0) ok = false;   // (two waves per tile there: no parking place)
+        if (hold_in_lds && top_stage_may_share_tiles(e) && seg_of[k] == 0) ok = false;   // (no parking place there)
         for (int q = j + 1; q < k && ok; q++) {
             const DevOp &m = e->h_ops[q];
             ok = m.left_kind != CHILD_PF && m.left_kind != CHILD_HOLD && m.right_kind != CHILD_LOAD && !m.push_hold;
@@ -404,7 +404,7 @@ int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_
         DevOp &d = e->h_ops[k];
         if (d.left_kind != CHILD_LEAF || d.right_kind != CHILD_LEAF || d.left_len_p || d.right_len_p) continue;
         // (the top stage's two-waves-per-tile / row-split kernels compute their cherries)
-        if ((e->top_cs2 || (e->n == 64 && e->mixed_top)) && seg_of[k] == 0) continue;
+        if ((top_stage_may_share_tiles(e) || top_stage_may_mix_roles64(e)) && seg_of[k] == 0) continue;
         const uint64_t tl = (uint64_t)((d.sl - e->d_states) / e->nptn_pad), tr = (uint64_t)((d.sr - e->d_states) / e->nptn_pad);
         const uint64_t key = (tl << 32) | tr;
         auto it = e->cherry_slot_of.find(key);
@@ -433,29 +433,6 @@ int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_
     return IQHIP_OK;
 }
 
-// doubles of LDS one chunk's per-(op, child) regions may use
-int lds_budget(const iqhip_engine *e) {
-    const int B = e->block;
-    if (!e->mfma) return (e->lds_budget_bytes / 8) - 128 - B;
-    const int MT = (e->n + 15) / 16, KS = e->n / 4;
-    int fixed = (e->row_split && e->mfma_pipelined) ? (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128
-                      : (e->mfma_pipelined ? mfma2_fixed_lds_doubles(e->n) : 2 * MT * KS * 64) +
-                            (e->state_unknown + 1 - e->n) * e->n;
-    // (64 states: a launch may mix both roles, k_traverse_mfma_top64)
-    if (e->mfma_pipelined && e->n == 64) fixed = std::max(fixed, (e->state_unknown + 1) * e->n + 4 * 16 * 64 + 128);
-    // two workgroups per CU (160 KB LDS): <= 78 KB each, images included (a third workgroup for the 20-state kernel was
-    // measured: no gain, more chunks); IQHIP_MFMA_LDS_KB overrides
-    // (20 states: + 2.6 KB of static arrays per workgroup, the fill's descriptor copies)
-    const int total_kb = e->mfma_lds_kb >= 0 ? e->mfma_lds_kb : (e->n == 20 ? 75 : 78);
-    if (e->plan.nhold > 0) fixed += 4 * 16 * B;   // the waves' parking places (CHILD_HOLD in LDS)
-    int budget = (total_kb * 1024) / 8 - fixed;
-    // the generic kernel's images leave two workgroups per CU too little for one op with two vector children once
-    // n * ncat > 864 (64 states, 14 .. 16 categories or components): one workgroup per CU, 150 KB (every matrix-core
-    // kernel allows that much dynamic LDS)
-    if (e->mfma_lds_kb < 0 && !e->mfma_pipelined && budget < 2 * B) budget = (150 * 1024) / 8 - fixed;
-    return budget;
-}
-
 // LDS layout of the per-(op, child) regions, cut into chunks that fit the budget
 int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     const int B = e->block, budget = lds_budget(e);
@@ -463,19 +440,19 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     // a LEAF child's region: 4 states -- exponentials + the 5-row K2 table; 20 states with leaf tables -- the child's
     // whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
     const int leaf_sz = !e->mfma ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
-    const int slot0 = e->mfma ? 0 : e->wg_size / 8;
-    int chunk_start = 0, used = slot0, regs = 0, max_used = 0, slots = 1, max_slots = 1;
+    const int slot_sz = e->mfma ? 0 : trav4_lds(B, e->wg_size).slot_doubles;   // (slot 0: the non-leaf children's)
+    int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
     for (int k = 0; k < nops; k++) {
         DevOp &d = e->h_ops[k];
         const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : B;
         const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : B;
         // 4-state path: each leaf child also stages one state byte per thread in LDS
         const int nleaf = (d.left_kind == CHILD_LEAF) + (d.right_kind == CHILD_LEAF);
-        const int need = szl + szr + (e->mfma ? 0 : nleaf * e->wg_size / 8);
+        const int need = szl + szr + nleaf * slot_sz;
         if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
         if ((used + need > budget || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
             e->h_ops[chunk_start].chunk_nops = k - chunk_start;
-            chunk_start = k; used = slot0; regs = 0; slots = 1;
+            chunk_start = k; used = slot_sz; regs = 0; slots = 1;
         }
         d.lds_left = regs; d.lds_right = regs + szl;
         regs += szl + szr;
@@ -621,10 +598,8 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
     c.segs = explicit_segs ? *explicit_segs : std::vector<int>();
     c.version = len_ptrs ? 0 : e->keymap_version;  // (slabs created while building are included; a sweep step's plan is never re-used)
     c.dst = last_dst;
-    // a small plan of the 4-state kernel rides in the kernel arguments (launch_traverse4 copies it out of h_ops)
-    // (matrix-core path: the pipelined 20-state kernels without leaf tables -- tables come with a job list in the buffer)
-    const bool small_kernel = !e->mfma || (e->mfma_pipelined && e->n == 20 && !e->leaf_tables && p.nleaf_tabs == 0);
-    p.small = e->small_plans && small_kernel && !explicit_segs && u.units.empty() && nops > 0 && nops + kSentinels <= kSmallPlanOps;
+    // a small plan rides in the kernel arguments (the launch copies it out of h_ops)
+    p.small = e->small_plans && kernel_takes_small_plan(e) && !explicit_segs && u.units.empty() && nops > 0 && nops + kSentinels <= kSmallPlanOps;
     p.small_nops = nops;
     if (e->planner && nops > 0) {   // negative tests (IQHIP_DEBUG_BREAK_PLAN): break one descriptor the way round 2's fault did
         const std::string &br = e->debug_break_plan;
@@ -689,6 +664,97 @@ bool leaf_tables_follow_model(iqhip_engine *e) {
     }
     e->tab_model_version = e->model_version;
     return true;
+}
+
+// Slack in two budgets below: charged to the chunk, allocated by no launch and read by no kernel.  Kept because a
+// larger budget would move chunk boundaries (and with them speed).
+constexpr int kRows64BudgetSlack = 128;   // on top of rows64_lds(), also in the role maximum of the 64-state pipelined kernels
+
+int lds_budget(const iqhip_engine *e) {
+    const int B = e->block, nx = e->state_unknown + 1 - e->n;
+    if (!e->mfma) return e->lds_budget_bytes / 8 - trav4_lds(B, e->wg_size).s_reg;
+    // (a 20-state engine on k_traverse_mfma_mix20, whose fixed part is mix20_lds().sReg = 0, is charged the generic kernel's
+    // images all the same: slack as above)
+    int fixed = !e->mfma_pipelined ? generic_lds(e->n, nx).sReg
+                : e->row_split     ? rows64_lds(nx).sReg + kRows64BudgetSlack
+                                   : mfma2_lds(e->n, nx).sReg;
+    // (64 states: a launch may mix both roles, k_traverse_mfma_top64)
+    if (e->mfma_pipelined && e->n == 64) fixed = std::max(fixed, rows64_lds(nx).sReg + kRows64BudgetSlack);
+    // two workgroups per CU (160 KB LDS): <= 78 KB each, images included (a third workgroup for the 20-state kernel was
+    // measured: no gain, more chunks); IQHIP_MFMA_LDS_KB overrides
+    // (20 states: + 2.6 KB of static arrays per workgroup, the fill's descriptor copies)
+    const int total_kb = e->mfma_lds_kb >= 0 ? e->mfma_lds_kb : (e->n == 20 ? 75 : 78);
+    if (e->plan.nhold > 0) fixed += mfma2_park_doubles(B);   // the waves' parking places (CHILD_HOLD in LDS)
+    int budget = (total_kb * 1024) / 8 - fixed;
+    // the generic kernel's images leave two workgroups per CU too little for one op with two vector children once
+    // n * ncat > 864 (64 states, 14 .. 16 categories or components): one workgroup per CU, all the dynamic LDS the
+    // matrix-core kernels allow
+    if (e->mfma_lds_kb < 0 && !e->mfma_pipelined && budget < 2 * B) budget = kTravMaxLdsBytes / 8 - fixed;
+    return budget;
+}
+
+// Which kernel a launch of `nsegs` segments runs, with its grid and dynamic LDS; reads the engine's shape and switches
+// and the current plan, makes no HIP call.
+TravLaunch choose_traverse_mfma(const iqhip_engine *e, bool top_stage, int nsegs) {
+    const int n = e->n, C = e->ncat, nx = e->state_unknown + 1 - n, regs = e->plan.lds_doubles;
+    const int64_t tiles = e->ntiles;
+    TravLaunch L = {TRAV_NONE, false, 0, 0, 0, 0, -1};
+    int fixed = 0, waves_per_tile = 1;
+    if (!e->mfma_pipelined) {   // both children from memory: mixtures, category counts without a pipelined instantiation
+        // (20 states: the mixture kernel -- with one class for a plain model: 16+4-row MFMA split, A fragments in
+        // registers -- beats the padded generic kernel)
+        if (n == 20 && !e->mix_generic) {
+            L.variant = e->mix_split ? TRAV_MIX20_SPLIT : TRAV_MIX20;
+            waves_per_tile = e->mix_split ? 4 : 1;
+            fixed = mix20_lds().sReg;
+        } else if (n == 20 || n == 64 || n == 4) {   // (4: mixtures; a plain 4-state model never comes here)
+            L.variant = TRAV_GENERIC;
+            fixed = generic_lds(n, nx).sReg;
+        }
+    } else if ((n == 20 && (C == 4 || C == 1)) || (n == 64 && C == 1)) {   // plan in canonical (PF, PREV) form
+        L.tab = e->plan.nleaf_tabs > 0 || e->leaf_tables;
+        L.variant = TRAV_M2;
+        fixed = mfma2_lds(n, nx).sReg;
+        if (n == 64) {
+            // whole rounds of one chain per SIMD go to full-chain workgroups, a small remainder to row-split ones
+            const int64_t per_round = (int64_t)e->num_cus * 4, rounds = tiles / per_round, rest = tiles - rounds * per_round;
+            if (e->row_split) {
+                L.variant = TRAV_ROWS64;
+                waves_per_tile = 4;
+                fixed = rows64_lds(nx).sReg;
+            } else if (top_stage && nsegs == 1 && top_stage_may_mix_roles64(e) && rounds >= 1 && rest > 0 && rest <= per_round / 2) {
+                L.variant = TRAV_TOP64;
+                L.nfull = (int)(rounds * e->num_cus);
+                L.ngroups = (int)(tiles - (int64_t)L.nfull * 4);
+                fixed = top64_fixed_doubles(nx);
+            }
+        } else if (C == 4 && e->cat_split) {
+            L.variant = TRAV_M2_CAT_SPLIT;
+            waves_per_tile = 4;
+        } else if (C == 4 && !L.tab && top_stage && top_stage_may_share_tiles(e)) {
+            // whole rounds of two-waves-per-tile workgroups (three per CU); a small remainder as one wave per category
+            const int64_t per_round = (int64_t)e->num_cus * 3 * 2, rounds = tiles / per_round, rest = tiles - rounds * per_round;
+            L.variant = TRAV_M2_TOP_CS2;
+            waves_per_tile = 2;
+            if (e->mixed_top && nsegs == 1 && rounds >= 1 && rest > 0 && rest <= per_round / 4) {
+                L.variant = TRAV_TOP20;
+                L.nfull = (int)(rounds * e->num_cus * 3);
+                L.ngroups = (int)(tiles - (int64_t)L.nfull * 2);
+            }
+        }
+    }
+    if (L.variant == TRAV_NONE) return L;
+    if (L.nfull > 0) L.grid = L.nfull + L.ngroups;
+    else {
+        L.ngroups = (int)((tiles * waves_per_tile + kTravWg / 64 - 1) / (kTravWg / 64));
+        L.grid = L.ngroups * nsegs;
+    }
+    L.lds_bytes = (size_t)(fixed + regs) * sizeof(double);
+    if (L.variant == TRAV_M2 && n < 64 && e->plan.nhold > 0) {   // parking places: one tile vector per wave
+        L.hold_off = fixed + regs;
+        L.lds_bytes += (size_t)mfma2_park_doubles(e->block) * sizeof(double);
+    }
+    return L;
 }
 
 int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_dst, const std::vector<int> *explicit_segs,

@@ -154,3 +154,42 @@ def test_mixed_role_top_stage_gives_the_same_bits(pkg, synth, oracle, monkeypatc
     for k in v0:
         assert np.array_equal(v0[k][0], v1[k][0]), k
         assert np.array_equal(v0[k][1], v1[k][1]), k
+
+
+@pytest.fixture(scope="module")
+def codon_top_case(synth, oracle):
+    """64 states, one category, 9 taxa, 16 (4 CUs + 3) - 5 patterns: one whole round of full-chain workgroups plus a remainder
+    of less than half a round, the last real tile ragged (the engine pads to 64 patterns, i.e. to 4 CUs + 4 tiles); too
+    large for the row split.  The oracle's lnL is computed once for both table settings."""
+    from test_kernel_paths_gpu import num_cus
+    ntiles = 4 * num_cus() + 3
+    nptn = 16 * ntiles - 5
+    model = synth.random_reversible_model(64, 71, alpha=None, ncat=1)
+    su = oracle.state_unknown_for(64, 2)
+    nwk = synth.random_tree_newick(9, 72, 0.02, 0.3)
+    pat = np.ascontiguousarray(synth.simulate_alignment(nwk, model, nptn, 73, 0.02, su))   # (sites as they are)
+    freq = np.ones(nptn)
+    invar = synth.ptn_invar_for(pat, model)
+    ot = oracle.OracleTree(nwk, 64, 2, pat, freq, invar, model)
+    ref, _ = ot.likelihood()
+    return model, nwk, pat, freq, invar, ot, ref
+
+
+@pytest.mark.parametrize("tables", ["0", "1"])
+def test_mixed_role_top_stage_64_gives_the_same_bits(pkg, codon_top_case, monkeypatch, tables):
+    """64 states, top stage of a plan (kernels_mfma.hip k_traverse_mfma_top64<TAB>): whole rounds of the chip as full-chain
+    workgroups, the tiles beyond them as row-split workgroups.  Same lnL, vectors and counters bit for bit as the
+    single-role launch (IQHIP_MIXED_TOP=0), with and without leaf tables; lnL equal to the oracle's."""
+    model, nwk, pat, freq, invar, ot, ref = codon_top_case
+    monkeypatch.setenv("IQHIP_LEAF_TABLES", tables)
+    res = []
+    for mixed in ("0", "1"):
+        monkeypatch.setenv("IQHIP_MIXED_TOP", mixed)
+        t = make(pkg, nwk, pat, freq, invar, model, pkg.LM_ALL_BRANCH, 64, 2)
+        res.append((t.compute_likelihood(), vectors(t, ot)))
+    (l0, v0), (l1, v1) = res
+    assert l0 == l1 and abs(l1 - ref) <= 1e-9 * abs(ref)
+    assert v0.keys() == v1.keys() and len(v0) >= 9 - 3
+    for k in v0:
+        assert np.array_equal(v0[k][0], v1[k][0]), k
+        assert np.array_equal(v0[k][1], v1[k][1]), k

@@ -4,6 +4,7 @@ pointer of every descriptor -- look-ahead sentinels included -- must be a live a
 uses it or not.  Round 2 had a GPU memory fault from exactly that (null K2 table pointers of non-leaf children);
 check_plan (plan.hip) finds that class of defect here, without a GPU, for every kernel family and staging variant."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -46,9 +47,12 @@ SHAPES = [  # nstates, ncat, nptn, ntaxa, nclass: every kernel family and the si
 ]
 
 
+ENVS = [{}, {"IQHIP_LEAF_TABLES": "1"}, {"IQHIP_LEAF_TABLES": "0", "IQHIP_HOLD": "0", "IQHIP_HOLD_LDS": "0"},
+        {"IQHIP_SPLIT": "5", "IQHIP_LEVELS": "3"}, {"IQHIP_SPLIT": "0", "IQHIP_SMALL_PLANS": "0"}]
+
+
 @pytest.mark.parametrize("nstates,ncat,nptn,ntaxa,nclass", SHAPES)
-@pytest.mark.parametrize("env", [{}, {"IQHIP_LEAF_TABLES": "1"}, {"IQHIP_LEAF_TABLES": "0", "IQHIP_HOLD": "0", "IQHIP_HOLD_LDS": "0"},
-                                 {"IQHIP_SPLIT": "5", "IQHIP_LEVELS": "3"}, {"IQHIP_SPLIT": "0", "IQHIP_SMALL_PLANS": "0"}])
+@pytest.mark.parametrize("env", ENVS)
 def test_plans_satisfy_the_kernel_contract(pkg, synth, monkeypatch, nstates, ncat, nptn, ntaxa, nclass, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -63,6 +67,52 @@ def test_plans_satisfy_the_kernel_contract(pkg, synth, monkeypatch, nstates, nca
             assert rc == 0, lib.iqhip_last_error()
     finally:
         lib.iqhip_destroy(e)
+
+
+GOLDEN_PLAN_SHAPES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_shapes.json")
+
+
+def plan_shape_key(shape, env, cus):
+    return "%s|%s|cus=%d" % ("-".join(map(str, shape)), ",".join("%s=%s" % kv for kv in sorted(env.items())), cus)
+
+
+def plan_shapes(pkg, synth, shape, cus):
+    """iqhip_debug_plan_shape after each plan test_plans_satisfy_the_kernel_contract builds (the environment is the caller's)"""
+    nstates, ncat, nptn, ntaxa, nclass = shape
+    lib, e = planner(pkg, nstates, ncat, nptn, ntaxa, cus=cus, nclass=nclass)
+    out = []
+    try:
+        for seed, mf in ((1, False), (2, False), (3, True)):
+            ops = plan_of(pkg, synth, ntaxa, 40 + seed, nstates, multifurcating=mf)
+            for nops in (len(ops), min(2, len(ops))):
+                assert lib.iqhip_debug_plan(e, ops, nops) == 0, lib.iqhip_last_error()
+                rec = (C.c_int64 * len(pkg.PLAN_SHAPE_SLOTS))()
+                assert lib.iqhip_debug_plan_shape(e, rec, len(rec)) == 0, lib.iqhip_last_error()
+                out.append(list(rec))
+    finally:
+        lib.iqhip_destroy(e)
+    return out
+
+
+@pytest.mark.parametrize("cus", [256, 64])
+@pytest.mark.parametrize("env", ENVS)
+def test_plan_shapes_match_the_recorded_ones(pkg, synth, monkeypatch, env, cus):
+    """Budget, largest chunk, state slots, parked operands, chunk and stage counts of every plan above, at two chip sizes,
+    equal the record of the planner as it was before the kernels' LDS layouts and their dispatch were described in one
+    place (trav_lds.h, choose_traverse_mfma); the launches chosen for those plans (variant, grid, dynamic LDS bytes) equal
+    the record made when the chooser was introduced.  A kernel change that moves any of them shows up here as a diff;
+    tools/record_plan_shapes.py re-records."""
+    golden = json.load(open(GOLDEN_PLAN_SHAPES))
+    assert golden["slots"] == list(pkg.PLAN_SHAPE_SLOTS)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for shape in SHAPES:
+        want = golden["records"][plan_shape_key(shape, env, cus)]
+        got = plan_shapes(pkg, synth, shape, cus)
+        assert len(got) == len(want)
+        for q, (g, w) in enumerate(zip(got, want)):
+            for name, gv, wv in zip(pkg.PLAN_SHAPE_SLOTS, g, w):
+                assert gv == wv, (shape, env, cus, "plan %d" % q, name, gv, wv)
 
 
 def test_cherry_tables_are_planned_and_checked(pkg, synth, monkeypatch):
