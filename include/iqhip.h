@@ -103,8 +103,11 @@ int iqhip_device_count(void);
  * tip table of STATE_UNKNOWN + 1 rows, vectors of nstates*ncat doubles per pattern); embedded counts (everything but 4, 20,
  * 64) have STATE_UNKNOWN = nstates and no mixtures.
  * nptn = aln->size() + unobserved patterns of this shard; ntaxa = leafNum.
- * ncat: 1..8 on the 4-state kernels; 1..16 on the 64-state kernels; 1..96 on the 20-state kernels (the (class, rate)
- * components of a mixture model count as categories, see iqhip_set_mixture_model). */
+ * ncat: 1..32 for exactly 4 states (9..32: "wide DNA", e.g. +R10, +G16, MIX{JC,HKY,GTR}+G4 -- such an engine keeps the
+ * 16-pattern tile layout from creation; IQHIP_WIDE4, read at creation, picks its node update: generic (the default), the padded
+ * matrix-core kernel, or valu, k_traverse4w on the same plans; any other word is IQHIP_ERR_INVALID); 1..8 for 2- and 3-state data, which run on the 4-state kernels through the
+ * embedding (nstates = 3 with ncat = 9 is IQHIP_ERR_UNSUPPORTED); 1..16 on the 64-state kernels; 1..96 on the 20-state
+ * kernels (the (class, rate) components of a mixture model count as categories, see iqhip_set_mixture_model). */
 int iqhip_create(iqhip_engine **out, int device, int nstates, int ncat, int64_t nptn,
                  int ntaxa);
 void iqhip_destroy(iqhip_engine *e);
@@ -176,7 +179,9 @@ int iqhip_set_model(iqhip_engine *e, const double *eval, const double *evec,
  * phylokernelmixture.h:55-56): component q uses eigen-system cat_class[q], rate rates[q] and weight
  * props[q] (= class weight x category proportion).  eval / evec / inv_evec are the nclass systems
  * concatenated (model->getEigenvalues() etc. of ModelMixture); tip_partial_lh is [state][class][n]
- * (phylotreesse.cpp:395-458, phylokernelmixture.h:151).  20 states only (IQHIP_ERR_UNSUPPORTED else). */
+ * (phylotreesse.cpp:395-458, phylokernelmixture.h:151).  4, 20 and 64 states; any nclass in 1..ncat, so a 4-state engine
+ * of 12 components takes MIX{JC,HKY,GTR}+G4, and plain -> mixture -> plain on one engine works (the caller invalidates all
+ * vectors at a model change, as always). */
 int iqhip_set_mixture_model(iqhip_engine *e, int nclass, const int32_t *cat_class /* [ncat] */,
                             const double *eval, const double *evec, const double *inv_evec,
                             const double *rates /* [ncat] */, const double *props /* [ncat] */,
@@ -388,7 +393,7 @@ int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
  *   0..5    LDS budget of a chunk (doubles), plan regions of the largest chunk (doubles), leaf-state slots, parked operands,
  *           LDS chunks, stages of units
  *   6..13   units per stage (the first 8 stages)
- *   14..20  the top-stage launch: kernel variant (the engine's TravVariant; -1: the 4-state kernel), leaf tables, full-role
+ *   14..20  the top-stage launch: kernel variant (the engine's TravVariant, 10 = TRAV_WIDE4 = k_traverse4w; -1: the 4-state kernel), leaf tables, full-role
  *           workgroups of a mixed-role launch, workgroups per segment, grid, dynamic LDS bytes, offset of the parking places
  *           (doubles, -1: none)
  *   21..27  the same for the first stage of units (zeros: the plan has none) */

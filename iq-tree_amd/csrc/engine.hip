@@ -44,7 +44,12 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     e->ncat = ncat;
     e->ntaxa = ntaxa;
     e->nptn = nptn;
-    e->mfma = nstates != 4;
+    e->wide4 = nstates_user == 4 && ncat > 8;
+    // IQHIP_WIDE4=valu | generic: the node update of a wide engine (k_traverse4w | the padded matrix-core kernel).  The
+    // default is the generic kernel until k_traverse4w has been measured faster on an MI355X
+    e->wide4_generic = e->wide4;
+    if (const char *w = getenv("IQHIP_WIDE4")) e->wide4_generic = e->wide4 && strcmp(w, "valu") != 0;   // (check_shape4 has refused every other word)
+    e->mfma = nstates != 4 || e->wide4;
     e->mfma_pipelined_ok = ((nstates == 20 && (ncat == 4 || ncat == 1)) || (nstates == 64 && ncat == 1)) &&
                            !getenv("IQHIP_MFMA_V1");
     e->mfma_pipelined = e->mfma_pipelined_ok;
@@ -117,6 +122,20 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     }
 }
 
+// 4-state kernels: 1 .. 8 categories, and 9 .. 32 for exactly 4 states (binary and 3-state data run on the 4-state
+// kernels through the embedding and keep the limit of 8).  A wide engine reads IQHIP_WIDE4: a word other than the two
+// routes is refused here, before the device is opened, not taken for one of them
+static int check_shape4(const char *who, int nstates, int nstates_user, int ncat) {
+    if (nstates != 4) return IQHIP_OK;
+    if (!(ncat >= 1 && ncat <= (nstates_user == 4 ? 32 : 8)))
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(who) + (nstates_user == 4 ? ": 4 states support ncat in {1..32}"
+                                                                                 : ": 2- and 3-state data support ncat in {1..8}"));
+    const char *w = ncat > 8 ? getenv("IQHIP_WIDE4") : nullptr;
+    if (w && strcmp(w, "valu") != 0 && strcmp(w, "generic") != 0)
+        return fail(IQHIP_ERR_INVALID, std::string(who) + ": IQHIP_WIDE4 must be generic or valu, not '" + w + "'");
+    return IQHIP_OK;
+}
+
 extern "C" int iqhip_create(iqhip_engine **out, int device, int nstates, int ncat, int64_t nptn,
                             int ntaxa) {
     if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_create: out == NULL");
@@ -128,8 +147,10 @@ extern "C" int iqhip_create(iqhip_engine **out, int device, int nstates, int nca
     // phylotreesse.cpp:281-309), run on the next kernel size up through an exact embedding (iqhip_internal.h: embed2)
     if (nstates < 2 || nstates > 64) return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_create: nstates must be 2 .. 64");
     nstates = nstates <= 4 ? 4 : nstates <= 20 ? 20 : 64;
-    if (nstates == 4 && !(ncat >= 1 && ncat <= 8))
-        return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_create: 4-state path supports ncat in {1..8}");
+    {
+        const int rc = check_shape4("iqhip_create", nstates, nstates_user, ncat);
+        if (rc) return rc;
+    }
     if (nstates != 4 && ncat > (nstates == 20 ? 96 : 16))  // 20 states: (class, rate) components of mixtures
         return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_create: ncat must be <= 16 (<= 96 components for 20 states)");
     // the 4-state kernels address a vector slab with a wave-uniform base + one 32-bit per-lane byte offset
@@ -456,7 +477,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
     // matrix-core kernel with per-class A images.  A 4-state engine therefore changes its vector layout (64-pattern
     // tiles of the VALU kernels <-> 16-pattern tiles of the matrix-core kernels) when the model becomes / stops being
     // a mixture; as with every model change the caller invalidates all vectors (clearAllPartialLH).
-    if (e->n == 4) {
+    if (e->n == 4 && !e->wide4) {   // (a wide engine stays on the 16-pattern tiles)
         const bool want_mfma = nclass > 1;
         if (want_mfma != e->mfma) {
             HIPCHK(use_device(e));
@@ -539,8 +560,8 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
     e->d_cls = reinterpret_cast<int *>(e->d_model + o_cls);
     e->d_aimg = aimg_doubles ? e->d_model + o_aimg : nullptr;
     e->aimg_doubles = (int)aimg_doubles;
-    if (nclass > 1 || (e->n == 20 && !e->mfma_pipelined_ok)) {  // (20 states with a category count that has no
-        // pipelined instantiation also run on the mixture kernel: one class)
+    if (nclass > 1 || (e->n == 20 && !e->mfma_pipelined_ok) || e->wide4) {  // (20 states with a category count that has no
+        // pipelined instantiation also run on the mixture kernel: one class; wide DNA reads the generic images, one class too)
         // MFMA A-operand images of every class for k_traverse_mfma_mix20: [class][U16 | U4 | Ui16 | Ui4][s][lane]
         // (16-row tile: row = lane & 15; 4-row tail: row = 16 + (lane & 3); k = 4s + (lane >> 4)), followed by
         // the padded two-tile images [class][U | U^-1][m][s][lane] of the generic kernel (IQHIP_MIX_GENERIC)
@@ -1358,11 +1379,22 @@ extern "C" int iqhip_timing_plan_bytes(iqhip_engine *e, double *stored, double *
         }
     } else {
         const double P = (double)e->nptn_pad, V = (double)e->block * 8.0;
+        // k_traverse4w takes a child that is the previous op's result from registers, within one segment: a wave starts
+        // every segment (and so every launch) with nothing held, whatever op k - 1 of the array was
+        const bool hands_over = e->wide4 && !e->wide4_generic && e->h_ops && e->last_nops > 0;
+        std::vector<char> seg_first(hands_over ? (size_t)e->last_nops : 0, 0);
+        if (hands_over) {
+            const int *tab = reinterpret_cast<const int *>(e->h_ops + e->plan.table_off);
+            for (int u = 0; u <= e->plan.nunits; u++)
+                if (tab[2 * u + 1] > 0 && tab[2 * u] >= 0 && tab[2 * u] < e->last_nops) seg_first[tab[2 * u]] = 1;
+        }
         for (int k = 0; k < e->last_nops && e->h_ops; k++) {
             const DevOp &d = e->h_ops[k];
             st += P * (V + 2.0);
-            if (d.left_kind == CHILD_LEAF) ld += P; else if (d.left_kind == CHILD_PF || d.left_kind == CHILD_LOAD) ld += P * (V + 2.0);
-            if (d.right_kind == CHILD_LEAF) ld += P; else if (d.right_kind == CHILD_LOAD) ld += P * (V + 2.0);
+            const double *held = (hands_over && k > 0 && !seg_first[k]) ? e->h_ops[k - 1].dst : nullptr;
+            if (d.left_kind == CHILD_LEAF) ld += P;
+            else if ((d.left_kind == CHILD_PF || d.left_kind == CHILD_LOAD) && d.pf != held) ld += P * (V + 2.0);
+            if (d.right_kind == CHILD_LEAF) ld += P; else if (d.right_kind == CHILD_LOAD && d.ld != held) ld += P * (V + 2.0);
         }
         if (e->last_has_root) {
             st += P * 8.0;
@@ -1419,6 +1451,10 @@ extern "C" int iqhip_debug_create_planner(iqhip_engine **out, int nstates, int n
     if (nstates != 4 && nstates != 20 && nstates != 64)
         return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_debug_create_planner: nstates must be 4, 20 or 64");
     if (state_unknown < nstates || state_unknown > 255) return fail(IQHIP_ERR_INVALID, "state_unknown out of range");
+    {
+        const int rc = check_shape4("iqhip_debug_create_planner", nstates, nstates, ncat);
+        if (rc) return rc;
+    }
     iqhip_engine *e = new iqhip_engine();
     e->planner = true;
     e->check_plans = true;
@@ -1431,7 +1467,7 @@ extern "C" int iqhip_debug_create_planner(iqhip_engine **out, int nstates, int n
     e->result_cap = 8 + 16384;
     e->state_unknown = state_unknown;
     e->nclass = nclass;
-    if (nclass > 1 && nstates == 4) {   // as set_model_common: a 4-state mixture runs on the matrix-core kernels
+    if (nclass > 1 && nstates == 4 && !e->wide4) {   // as set_model_common: a 4-state mixture runs on the matrix-core kernels
         e->mfma = true;
         e->lane_split = 1;
         e->tile = 16;

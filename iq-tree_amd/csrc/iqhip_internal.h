@@ -103,6 +103,27 @@ __device__ __forceinline__ double wave_sum64(double v) {
     return v;
 }
 
+// The scaling test max|x| < 2^-256 on the 32-bit vector ALU: for finite doubles |x| < 2^-256 <=> the high word of |x|
+// is below that of 2^-256 (whose low word is 0), and the high words order like the values.  fp64 vector instructions
+// run on the unit that executes the fp64 matrix instructions and ADD to their time (3.1 ns each against 29.5 ns for a
+// 16x16x4, tools/mfma_issue_probe.hip), 32-bit ones overlap with them: v_and + v_max_u32 replace two v_max_f64 per value.
+constexpr unsigned kScalingThresholdHi = 0x2FF00000u;   // high word of 0x1p-256
+__device__ __forceinline__ unsigned amax_hi(unsigned m, double v) {
+    const unsigned h = (unsigned)__double2hiint(v) & 0x7fffffffu;
+    return m > h ? m : h;
+}
+// exactly-zero test for the scalar kernel's `lh_max == 0.0` branch (IQHIP_OP_SCALAR_RULE ops only): any bit of |x|
+__device__ __forceinline__ unsigned nonzero_bits(double v) {
+    return ((unsigned)__double2hiint(v) & 0x7fffffffu) | (unsigned)__double2loint(v);
+}
+// maximum over the four lane groups of a pattern (lanes p, p+16, p+32, p+48): kernels_mfma.hip group_max on one register
+__device__ __forceinline__ unsigned group_max_u(unsigned v) {
+    auto a = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    v = a[0] > a[1] ? a[0] : a[1];
+    auto b = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    return b[0] > b[1] ? b[0] : b[1];
+}
+
 // length of a child branch of a node update: the host value, or the result of an earlier step of a sweep
 template <typename OpRef>
 __device__ __forceinline__ double op_child_len(const OpRef &d, int child) {
@@ -286,6 +307,11 @@ struct iqhip_engine {
     bool cat_split = false; // 20 states, 4 categories: one wave per category of a tile (small alignments)
     bool top_cs2 = false;   // 20 states, 4 categories: the sequential top stage with two waves per tile (two categories each), IQHIP_TOP_CS2
     int lane_split = 1;    // 4-state traversal: lanes per pattern (2: each lane owns half of the categories)
+    // wide DNA: exactly 4 states with 9 .. 32 categories or components.  Such an engine lives on the 16-pattern tile
+    // layout from creation (mfma semantics: tile 16, no lane split, no small plans, no persistent sweep) whatever its
+    // number of classes; its node update is the padded matrix-core kernel k_traverse_mfma<4, 256, true> (IQHIP_WIDE4=generic,
+    // the default) or, with IQHIP_WIDE4=valu, k_traverse4w (kernels_valu4w.hip) on the same plans
+    bool wide4 = false, wide4_generic = false;
     int lane_split_valu = 1;  // ... remembered while a 4-state engine runs a mixture on the matrix-core kernels
     bool mix_generic = false; // 20-state mixtures and unpipelined category counts on the generic kernel instead of k_traverse_mfma_mix20 (IQHIP_MIX_GENERIC)
     bool mix_split = false;   // k_traverse_mfma_mix20: one wave per quarter of a tile's components (small alignments; IQHIP_CAT_SPLIT)
@@ -689,6 +715,7 @@ enum TravVariant : int {
     TRAV_TOP20,              // k_traverse_mfma_top20
     TRAV_ROWS64,             // k_traverse_mfma_rows64<256, tab>
     TRAV_TOP64,              // k_traverse_mfma_top64<tab>
+    TRAV_WIDE4,              // k_traverse4w<ceil(ncat / 4), nclass > 1> (kernels_valu4w.hip): 4 states, 9 .. 32 categories
 };
 struct TravLaunch {
     TravVariant variant;
@@ -914,6 +941,9 @@ hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks,
                                int post_epochs = 0);
 size_t newton_task_bytes();
 void newton_task_fill(void *dst, const DevBranch &br, double xguess, double x1, double x2, double xacc, int max_steps);
+
+// kernels_valu4w.hip (4 states, 9 .. 32 categories): the launch choose_traverse_mfma described as TRAV_WIDE4
+hipError_t launch_traverse4w(iqhip_engine *e, const TravLaunch &L, const int *seg_table, int nwaves);
 
 // kernels_mfma.hip (nstates 20 / 64)
 hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs, int nwaves, bool top_stage = false);

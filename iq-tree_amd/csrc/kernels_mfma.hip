@@ -136,26 +136,8 @@ __device__ __forceinline__ double group_max(double v) {
     return fmax(__hiloint2double(d[0], c[0]), __hiloint2double(d[1], c[1]));
 }
 
-// The scaling test max|x| < 2^-256 on the 32-bit vector ALU: for finite doubles |x| < 2^-256 <=> the high word of |x|
-// is below that of 2^-256 (whose low word is 0), and the high words order like the values.  fp64 vector instructions
-// run on the unit that executes the fp64 matrix instructions and ADD to their time (3.1 ns each against 29.5 ns for a
-// 16x16x4, tools/mfma_issue_probe.hip), 32-bit ones overlap with them: v_and + v_max_u32 replace two v_max_f64 per value.
-constexpr unsigned kScalingThresholdHi = 0x2FF00000u;   // high word of 0x1p-256
-__device__ __forceinline__ unsigned amax_hi(unsigned m, double v) {
-    const unsigned h = (unsigned)__double2hiint(v) & 0x7fffffffu;
-    return m > h ? m : h;
-}
-// exactly-zero test for the scalar kernel's `lh_max == 0.0` branch (IQHIP_OP_SCALAR_RULE ops only): any bit of |x|
-__device__ __forceinline__ unsigned nonzero_bits(double v) {
-    return ((unsigned)__double2hiint(v) & 0x7fffffffu) | (unsigned)__double2loint(v);
-}
-__device__ __forceinline__ unsigned group_max_u(unsigned v) {
-    auto a = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    v = a[0] > a[1] ? a[0] : a[1];
-    auto b = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return b[0] > b[1] ? b[0] : b[1];
-}
-
+// (the scaling test on the high words -- kScalingThresholdHi, amax_hi, nonzero_bits, group_max_u -- is shared with
+// kernels_valu4w.hip: iqhip_internal.h)
 __device__ __forceinline__ double wave_sum_m(double v) { return wave_sum64(v); }
 
 struct TravMArgs {
@@ -1550,6 +1532,7 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
     for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = DevOp{};
     if (nsegs <= 0) return hipSuccess;
     const TravLaunch L = choose_traverse_mfma(e, top_stage, nsegs);
+    if (L.variant == TRAV_WIDE4) return launch_traverse4w(e, L, seg_table, nwaves);   // (kernels_valu4w.hip)
     A.ngroups = L.ngroups;
     A.hold_off = L.hold_off;
     if (e->plan.small && nsegs == 1) {   // (the plan was not copied to d_ops: it travels with the launch; Plan::small

@@ -439,7 +439,8 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     const bool tables_in_lds = e->mfma && e->mfma_pipelined && e->n == 20 && e->plan.nleaf_tabs > 0;
     // a LEAF child's region: 4 states -- exponentials + the 5-row K2 table; 20 states with leaf tables -- the child's
     // whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
-    const int leaf_sz = !e->mfma ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
+    // (wide DNA: as the 4-state kernel, on both of its routes -- the generic kernel reads the exponentials only)
+    const int leaf_sz = (!e->mfma || e->wide4) ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
     const int slot_sz = e->mfma ? 0 : trav4_lds(B, e->wg_size).slot_doubles;   // (slot 0: the non-leaf children's)
     int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
     for (int k = 0; k < nops; k++) {
@@ -529,6 +530,17 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         if (d.sl_slot < 0 || d.sr_slot < 0 || d.sl_slot >= e->plan.state_slots || d.sr_slot >= e->plan.state_slots)
             return bad(k, "leaf-state slot outside the launch's allocation");
         if (d.chunk_nops < 0 || k + d.chunk_nops > nops) return bad(k, "LDS chunk runs past the plan");
+        if (e->wide4) {   // k_traverse4w: both children in the memory form, a leaf's region holds its table as well
+            if ((d.left_kind != CHILD_LEAF && d.left_kind != CHILD_LOAD) || (d.right_kind != CHILD_LEAF && d.right_kind != CHILD_LOAD))
+                return bad(k, "wide 4-state op is not in the (memory, memory) form");
+            if ((d.left_kind == CHILD_LOAD && d.pf == e->dummy.plh) || (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh))
+                return bad(k, "memory child without a real vector");
+            const int szl = (d.left_kind == CHILD_LEAF ? 6 : 1) * e->block, szr = (d.right_kind == CHILD_LEAF ? 6 : 1) * e->block;
+            if (d.lds_left + szl > e->plan.lds_doubles || d.lds_right + szr > e->plan.lds_doubles ||
+                (d.lds_left < d.lds_right + szr && d.lds_right < d.lds_left + szl))
+                return bad(k, "LDS regions of the two children overlap or leave the launch's allocation");
+            if (d.no_scale < 0 || d.no_scale > 2) return bad(k, "unknown scaling rule");
+        }
     }
     // chunks tile the plan; the segment table stays inside it
     for (int k = 0; k < nops;) {
@@ -675,6 +687,10 @@ int lds_budget(const iqhip_engine *e) {
     if (!e->mfma) return e->lds_budget_bytes / 8 - trav4_lds(B, e->wg_size).s_reg;
     // (a 20-state engine on k_traverse_mfma_mix20, whose fixed part is mix20_lds().sReg = 0, is charged the generic kernel's
     // images all the same: slack as above)
+    if (e->wide4) {   // both routes get the same chunks: the larger of the two kernels' fixed parts
+        const int kb = e->mfma_lds_kb >= 0 ? e->mfma_lds_kb : kWide4LdsKb;
+        return kb * 1024 / 8 - std::max(wide4_lds(e->nclass, B).sReg, generic_lds(4, nx).sReg);
+    }
     int fixed = !e->mfma_pipelined ? generic_lds(e->n, nx).sReg
                 : e->row_split     ? rows64_lds(nx).sReg + kRows64BudgetSlack
                                    : mfma2_lds(e->n, nx).sReg;
@@ -703,11 +719,14 @@ TravLaunch choose_traverse_mfma(const iqhip_engine *e, bool top_stage, int nsegs
     if (!e->mfma_pipelined) {   // both children from memory: mixtures, category counts without a pipelined instantiation
         // (20 states: the mixture kernel -- with one class for a plain model: 16+4-row MFMA split, A fragments in
         // registers -- beats the padded generic kernel)
-        if (n == 20 && !e->mix_generic) {
+        if (e->wide4 && !e->wide4_generic) {
+            L.variant = TRAV_WIDE4;
+            fixed = wide4_lds(e->nclass, e->block).sReg;
+        } else if (n == 20 && !e->mix_generic) {
             L.variant = e->mix_split ? TRAV_MIX20_SPLIT : TRAV_MIX20;
             waves_per_tile = e->mix_split ? 4 : 1;
             fixed = mix20_lds().sReg;
-        } else if (n == 20 || n == 64 || n == 4) {   // (4: mixtures; a plain 4-state model never comes here)
+        } else if (n == 20 || n == 64 || n == 4) {   // (4: mixtures, and wide DNA under IQHIP_WIDE4=generic; a plain model of at most 8 categories never comes here)
             L.variant = TRAV_GENERIC;
             fixed = generic_lds(n, nx).sReg;
         }

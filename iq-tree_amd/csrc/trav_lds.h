@@ -52,6 +52,13 @@ __host__ __device__ constexpr int top64_fixed_doubles(int nx) {
     return mfma2_lds(64, nx).sReg > rows64_lds(nx).sReg ? mfma2_lds(64, nx).sReg : rows64_lds(nx).sReg;
 }
 
+// k_traverse4w (4 states, 9 .. 32 categories): U and U^-1 of every class, [nclass][U 16 | U^-1 16]; the per-category tip
+// vectors of the four plain states, [4][block], for the fill of the leaf tables; then the plan regions -- a leaf child's is
+// [ex block][table 5 * block] as in k_traverse4, an inner child's [ex block]
+struct Wide4Lds { int sW, sTipc, sReg; };
+__host__ __device__ constexpr Wide4Lds wide4_lds(int nclass, int block) { return {0, 32 * nclass, 32 * nclass + 4 * block}; }
+constexpr int kWide4LdsKb = 40;   // per workgroup, fixed part included: four workgroups (16 waves) per CU
+
 // k_traverse4: tip vectors [32][4], one block of values, the plan regions, then the leaf-state slots -- one byte per
 // thread each, i.e. wg / 8 doubles; slot 0 is shared by all non-leaf children
 struct Trav4Lds { int s_tip, s_val, s_reg, slot_doubles; };

@@ -373,6 +373,31 @@ ModelSpec parseModelString(const std::string &s) {
             std::vector<double> v = parseBraces(tok, open);
             if (v.size() != 1 || v[0] <= 0.0) throw std::runtime_error("Wrong gamma shape");
             spec.gamma_shape = v[0];
+            spec.free_props.clear();
+            spec.free_rates.clear();
+        } else if (u[0] == 'R') {   // FreeRate with given weights and rates (model/ratefree.cpp:25-55)
+            size_t i = 1;
+            int ncat = 0;
+            while (i < u.size() && isdigit((unsigned char)u[i])) ncat = 10 * ncat + (u[i++] - '0');
+            if (open == std::string::npos || i != open) throw std::runtime_error("+R needs its weights and rates: +R2{w1,r1,w2,r2}");
+            std::vector<double> v = parseBraces(tok, open);
+            if (ncat == 0) ncat = 4;
+            if (v.size() != (size_t)2 * ncat)
+                throw std::runtime_error("Number of parameters for FreeRate model must be twice number of categories");
+            double mean = 0.0, sum_prop = 0.0;
+            spec.free_props.resize(ncat);
+            spec.free_rates.resize(ncat);
+            for (int c = 0; c < ncat; c++) {
+                spec.free_props[c] = v[2 * c];
+                spec.free_rates[c] = v[2 * c + 1];
+                if (!(v[2 * c] >= 0.0) || !(v[2 * c + 1] >= 0.0)) throw std::runtime_error("Negative FreeRate weight or rate");
+                mean += v[2 * c] * v[2 * c + 1];
+                sum_prop += v[2 * c];
+            }
+            if (!(fabs(sum_prop - 1.0) <= 1e-5)) throw std::runtime_error("Sum of category proportions not equal to 1");
+            if (!(mean > 0.0)) throw std::runtime_error("FreeRate rates are all zero");
+            for (double &r : spec.free_rates) r /= mean;
+            spec.ncat = ncat;
         } else
             throw std::runtime_error("Unknown model component +" + tok);
     }
@@ -497,6 +522,10 @@ void buildModel(const ModelSpec &spec, const Alignment &aln, ModelInputs &out) {
     if (spec.ncat == 1 && spec.p_invar > 0.0) out.rates[0] = 1.0 / (1.0 - spec.p_invar);  // RateInvar::getRate (model/rateinvar.h)
     // category proportions (model/rategamma.h:114, rategammainvar): (1 - p_invar)/ncat
     out.props.assign(spec.ncat, (1.0 - spec.p_invar) / spec.ncat);
+    if (!spec.free_rates.empty()) {   // +R, +I+R: the rates as given, weights (1 - p_invar) * w (model/ratefreeinvar.h:45-52)
+        out.rates = spec.free_rates;
+        for (int c = 0; c < spec.ncat; c++) out.props[c] = (1.0 - spec.p_invar) * spec.free_props[c];
+    }
 }
 
 }  // namespace iqhost

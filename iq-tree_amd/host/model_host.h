@@ -51,6 +51,9 @@ struct ModelSpec {
     double gamma_shape = 1.0;
     bool gamma_median = false;
     double p_invar = 0.0;
+    // +R<k>{w1,r1,...,wk,rk} (model/ratefree.cpp:25-55): free-rate categories, weights summing to 1, rates already
+    // rescaled to mean 1; empty: discrete Gamma
+    std::vector<double> free_props, free_rates;
     bool ascertainment = false;
 };
 ModelSpec parseModelString(const std::string &s);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# timing-only variant of the library: tools/build_alt.sh <name> <hipcc flags for kernels_mfma.hip / kernels_valu4.hip ...>
+# timing-only variant of the library: tools/build_alt.sh <name> <hipcc flags for kernels_mfma.hip / kernels_valu4.hip / kernels_valu4w.hip ...>
 # -> iq-tree_amd/lib_alt_<name>/ (git-ignored), selected at run time with IQHIP_LIB_DIR.  Results of such a build may be wrong.
 set -e
 name=$1; shift
@@ -7,9 +7,9 @@ cd "$(dirname "$0")/.."
 d=iq-tree_amd/lib_alt_$name
 mkdir -p $d
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -Wno-unused-value -Wno-unused-result -Iinclude"
-for f in engine kernels_valu4 kernels_mfma kernels_newton kernels_sweep kernels_rell comm sharded; do
+for f in engine solve plan kernels_valu4 kernels_valu4w kernels_mfma kernels_newton kernels_sweep kernels_rell comm sharded; do
   case $f in
-    kernels_mfma|kernels_valu4) /opt/rocm/bin/hipcc $FLAGS "$@" -c iq-tree_amd/csrc/$f.hip -o $d/$f.o & ;;
+    kernels_mfma|kernels_valu4|kernels_valu4w) /opt/rocm/bin/hipcc $FLAGS "$@" -c iq-tree_amd/csrc/$f.hip -o $d/$f.o & ;;
     *) cp iq-tree_amd/lib/$f.o $d/$f.o ;;
   esac
 done
