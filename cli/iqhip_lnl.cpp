@@ -4,13 +4,17 @@
 // Everything it does goes through the same host mirror and C ABI as the tests: read the alignment
 // (alignment_host), build the model inputs (model_host), read the tree, setLikelihoodKernel(HIP),
 // computeLikelihood(), optionally optimizeAllBranches(), write X.iqhip (full-precision numbers) and
-// X.sitelh.  There is no CPU path: without a GPU it fails with the engine's error.
+// X.sitelh.  With -alrt N [-lbp N] [-seed S] it then runs the SH-aLRT / local-bootstrap branch tests on the device
+// (PhyloTree::testAllBranches) and prints the tree with SH-aLRT[/LBP] node labels; the site resamples are multinomial
+// draws of its own generator (std::mt19937_64), not the reference's RNG stream.
+// There is no CPU path: without a GPU it fails with the engine's error.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <chrono>
 #include <fstream>
+#include <random>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -24,7 +28,7 @@ using namespace iqhost;
 static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
-            "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave]\n"
+            "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
 }
@@ -32,7 +36,8 @@ static void usage() {
 int main(int argc, char **argv) {
     std::string aln_file, tree_file, model_str, seq_type, prefix;
     bool blfix = false, wsl = false, all_branch = false;
-    int dev = 0, reps = 0;
+    int dev = 0, reps = 0, alrt = 0, lbp = 0;
+    unsigned long long seed = 1;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -49,11 +54,16 @@ int main(int argc, char **argv) {
         else if (a == "-nolhmemsave") all_branch = true;
         else if (a == "-dev") dev = atoi(next().c_str());
         else if (a == "-reps") reps = atoi(next().c_str());
+        else if (a == "-alrt") alrt = atoi(next().c_str());
+        else if (a == "-lbp") lbp = atoi(next().c_str());
+        else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
     }
     if (aln_file.empty() || tree_file.empty() || model_str.empty()) { usage(); return 2; }
     if (prefix.empty()) prefix = aln_file;
+    if (alrt < 0 || lbp < 0) { usage(); return 2; }
+    if (alrt > 0 || lbp > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
         Alignment aln;
         aln.readFile(aln_file, seq_type);
@@ -123,6 +133,28 @@ int main(int argc, char **argv) {
             out << "rates";
             for (double r : mi.rates) { snprintf(buf, sizeof buf, " %.17g", r); out << buf; }
             out << "\ntree " << tree.getTreeString() << "\n";
+        }
+        if (alrt > 0 || lbp > 0) {
+            // bootstrap weightings: nsite sites drawn with replacement, counted per pattern (the unobserved +ASC patterns
+            // have frequency 0 and are never drawn)
+            const int times = alrt > lbp ? alrt : lbp;
+            const size_t np = (size_t)aln.getNPattern();
+            std::vector<float> samples((size_t)times * np, 0.0f);
+            std::mt19937_64 gen(seed);
+            std::discrete_distribution<size_t> pick(freq.begin(), freq.end());
+            for (int r = 0; r < times; r++)
+                for (int k = 0; k < nsite; k++) samples[(size_t)r * np + pick(gen)] += 1.0f;
+            tree.setBootSamples(samples.data(), times);
+            std::vector<PhyloTree::BranchSupport> sup;
+            auto t0 = std::chrono::steady_clock::now();
+            tree.testAllBranches(alrt, lbp, sup, true);
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("Branch tests (%d SH-aLRT, %d local bootstrap replicates) on %d internal branches: %.4f s\n", alrt, lbp,
+                   (int)sup.size(), sec);
+            const std::string labelled = tree.supportTreeString(sup, alrt > 0, lbp > 0);
+            printf("Tree with %s%s supports: %s\n", alrt > 0 ? "SH-aLRT" : "", lbp > 0 ? "/LBP" : "", labelled.c_str());
+            std::ofstream out((prefix + ".iqhip").c_str(), std::ios::app);
+            out << "support_tree " << labelled << "\n";
         }
         if (wsl) {
             writeSiteLh(prefix + ".sitelh", aln, pattern_lh.data());

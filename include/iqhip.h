@@ -334,6 +334,47 @@ int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a, iqhip_bra
 int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int nsamples);
 int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *rell /* nsamples */);
 int iqhip_rell_async(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b);
+/* ---- SH-aLRT and local-bootstrap branch supports (PhyloTree::testAllBranches / testOneBranch / computeNNIPatternLh /
+ * resampleLh, phylotree.cpp:3779-3809, 3984-4103) --------------------------------------------------------------------
+ * The engine keeps a STORE of per-pattern log-likelihood rows on the device (nptn_pad doubles each).  A row holds exactly
+ * what iqhip_fetch_pattern_lh_scaled returns for a branch at a length: the scale counters of both ends put back, 0 for
+ * the unobserved +ASC patterns and the padding, the +ASC shift as there.  Rows are filled without leaving the device:
+ *   iqhip_ptnlh_put_current        row <- the branch (a, b) the last lnL evaluation ran on (the current tree's row, and the
+ *                                  candidates of a branch-by-branch getBestNNIForBran)
+ *   iqhip_optimize_branch_batch_rows  iqhip_optimize_branch_batch, and for every task t with rows[t] >= 0 the per-pattern
+ *                                  log-likelihood of its branch at results[t].optx goes to row rows[t] (the reference's
+ *                                  nniMoves[cnt].ptnlh, phylotree.cpp:3019-3020).  rows == NULL: iqhip_optimize_branch_batch.
+ *   iqhip_ptnlh_reserve grows the store (existing rows keep their contents), iqhip_ptnlh_fetch copies one row to the host.
+ * iqhip_ptnlh_rell: the raw RELL sums R[i][s] = sum_p row(rows[i])[p] * boot_samples[s][p] for the first nsamples samples of
+ *   iqhip_set_boot_samples: ONE tall-skinny fp64 product R = L W^T on the matrix cores (every distinct row is multiplied
+ *   once, the sample matrix is read from HBM once), K-split over workgroups and combined in a fixed order: the same bits
+ *   run to run.
+ * iqhip_branch_tests: per branch b the three rows rows3[3b .. 3b+2] = {current tree, NNI 1, NNI 2} and their total
+ *   log-likelihoods lh3[3b .. 3b+2] (lh_scale_factor terms included; the caller has them); the comparisons of
+ *   phylotree.cpp:4018-4044 run on the device for the first max(reps_sh, reps_lbp) samples, and only nbranch result
+ *   structs leave it.  Both fractions are over max(reps_sh, reps_lbp) replicates, as testOneBranch returns them.
+ * DEVIATION from the reference: it draws a fresh resample per (branch, replicate); here ONE sample matrix serves every
+ *   branch of a call.  Each branch's support has the same distribution, supports of different branches share their draws.
+ *   A caller who wants independent draws uploads new samples and calls per branch.
+ * Out of scope: sharded engines (iqhip_create_sharded) and engines with a communicator return IQHIP_ERR_UNSUPPORTED from
+ *   all of these calls (iqhip_optimize_branch_batch_rows with rows == NULL excepted), planning-only engines
+ *   IQHIP_ERR_INVALID; the parametric aLRT probability (Statistics_To_Probabilities) stays with the caller, who needs
+ *   only alrt_stat for it. */
+typedef struct iqhip_branch_support {
+    double sh_alrt;   /* fraction of the max(reps_sh, reps_lbp) replicates, as testOneBranch returns it */
+    double lbp;       /* local bootstrap fraction */
+    double abayes;    /* 1 / (1 + exp(lh1-lh0) + exp(lh2-lh0)) */
+    double alrt_stat; /* 2 * (lh0 - max(lh1, lh2)) */
+} iqhip_branch_support;
+int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows);
+int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_end a, iqhip_branch_end b);
+int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out /* nptn */);
+int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks, double *sum_scale,
+                                     iqhip_branch_result *results, const int32_t *rows /* ntasks or NULL */);
+int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const double *lh3, int nbranch, int reps_sh, int reps_lbp,
+                       iqhip_branch_support *out);
+int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows, int nsamples, double *out /* nrows*nsamples */);
+
 /* Host -> device (tests; SPR/NNI code that fills a buffer on the host). */
 int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
                          const int16_t *scale_num);

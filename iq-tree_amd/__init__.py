@@ -36,6 +36,8 @@ IQHIP_SYMBOLS = [
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
     "iqhip_debug_create_planner", "iqhip_debug_plan", "iqhip_timing_plan_bytes", "iqhip_timing_collective_read", "iqhip_optimize_sweep", "iqhip_debug_cherry_tables",
     "iqhip_debug_path_counts", "iqhip_debug_plan_shape",
+    "iqhip_ptnlh_reserve", "iqhip_ptnlh_put_current", "iqhip_ptnlh_fetch", "iqhip_optimize_branch_batch_rows",
+    "iqhip_branch_tests", "iqhip_ptnlh_rell",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -58,6 +60,27 @@ class NodeOp(C.Structure):
 class BranchEnd(C.Structure):
     """struct iqhip_branch_end (include/iqhip.h)."""
     _fields_ = [("key", C.c_uint64), ("leaf", C.c_int32), ("_pad", C.c_int32)]
+
+
+class BranchSupport(C.Structure):
+    """struct iqhip_branch_support (include/iqhip.h)."""
+    _fields_ = [("sh_alrt", C.c_double), ("lbp", C.c_double), ("abayes", C.c_double), ("alrt_stat", C.c_double)]
+
+
+class BranchTask(C.Structure):
+    """struct iqhip_branch_task (include/iqhip.h)."""
+    _fields_ = [("ops", C.c_void_p), ("nops", C.c_int32), ("max_steps", C.c_int32), ("a", BranchEnd), ("b", BranchEnd),
+                ("xguess", C.c_double), ("x1", C.c_double), ("x2", C.c_double), ("xacc", C.c_double)]
+
+
+class BranchResult(C.Structure):
+    """struct iqhip_branch_result (include/iqhip.h)."""
+    _fields_ = [("optx", C.c_double), ("d2l", C.c_double), ("lnl", C.c_double), ("nsteps", C.c_int32), ("status", C.c_int32)]
+
+
+# test_all_branches: one record per internal branch
+SUPPORT_DTYPE = np.dtype([("node1", np.int32), ("node2", np.int32), ("lh", np.float64, (3,)), ("sh_alrt", np.float64),
+                          ("lbp", np.float64), ("abayes", np.float64), ("alrt_stat", np.float64)])
 
 
 def leaf_end(leaf):
@@ -157,6 +180,13 @@ def libiqhip():
     lib.iqhip_debug_path_counts.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_plan.argtypes = [vp, C.POINTER(NodeOp), C.c_int]
     lib.iqhip_debug_plan_shape.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+    i32p = C.POINTER(C.c_int32)
+    lib.iqhip_ptnlh_reserve.argtypes = [vp, C.c_int]
+    lib.iqhip_ptnlh_put_current.argtypes = [vp, C.c_int, BranchEnd, BranchEnd]
+    lib.iqhip_ptnlh_fetch.argtypes = [vp, C.c_int, dp]
+    lib.iqhip_optimize_branch_batch_rows.argtypes = [vp, C.POINTER(BranchTask), C.c_int, dp, C.POINTER(BranchResult), i32p]
+    lib.iqhip_branch_tests.argtypes = [vp, i32p, dp, C.c_int, C.c_int, C.c_int, C.POINTER(BranchSupport)]
+    lib.iqhip_ptnlh_rell.argtypes = [vp, i32p, C.c_int, C.c_int, dp]
     lib._iq_typed = True
     return lib
 
@@ -216,6 +246,10 @@ def libiqhost():
     lib.iqhost_compute_all_partial_lh.argtypes = [vp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
+    lib.iqhost_test_all_branches.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), dp, C.c_int,
+                                             C.POINTER(C.c_int), dp]
+    lib.iqhost_support_tree_string.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.iqhost_fetch_scale_num.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int16)]
     lib.iqhost_fetch_partial.argtypes = [vp, C.c_int, C.c_int, dp]
     lib.iqhost_fetch_pattern_lh.argtypes = [vp, dp]
@@ -556,17 +590,91 @@ class PhyloTree:
                      node2_nei=int(ids[4 * k + 3]), new_len=float(vals[2 * k]), newloglh=float(vals[2 * k + 1]))
                 for k in range(n.value)]
 
-    def evaluate_nnis5_batch(self):
-        """all nni5 candidates in ten submissions -> list of dict(node1, node2, node1_nei, node2_nei, new_lens[5], newloglh)"""
+    def evaluate_nnis5_batch(self, first_row=None):
+        """all nni5 candidates in ten submissions -> list of dict(node1, node2, node1_nei, node2_nei, new_lens[5], newloglh);
+        first_row: candidate k's per-pattern lnL is kept in row first_row + k of the engine's store (ptnlh_fetch)"""
         cap = 4 * self.num_nodes
         ids = np.zeros(4 * cap, dtype=np.int32)
         vals = np.zeros(6 * cap)
         n = C.c_int()
-        self._chk(self.lib.iqhost_evaluate_nnis5_batch(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), cap,
-                                                       C.byref(n)))
+        if first_row is None:
+            self._chk(self.lib.iqhost_evaluate_nnis5_batch(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), cap,
+                                                           C.byref(n)))
+        else:
+            self._chk(self.lib.iqhost_evaluate_nnis5_batch_rows(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals),
+                                                                cap, C.byref(n), int(first_row)))
         return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
                      node2_nei=int(ids[4 * k + 3]), new_lens=[float(x) for x in vals[6 * k:6 * k + 5]],
                      newloglh=float(vals[6 * k + 5])) for k in range(n.value)]
+
+    # ---- SH-aLRT / local bootstrap (include/iqhip.h "branch supports")
+    def _hip(self, rc):
+        if rc != 0:
+            raise HostError(libiqhip().iqhip_last_error().decode())
+
+    def test_all_branches(self, reps, lbp_reps=0, batched=True):
+        """PhyloTree::testAllBranches on the device with the samples of set_boot_samples: a SUPPORT_DTYPE record per
+        internal branch (lh = lnL of the tree and of its two NNI neighbours; fractions over max(reps, lbp_reps)
+        replicates).  Row 0 of the engine's store then holds the tree's per-pattern lnL, rows 1 + 2 q + cnt the
+        neighbours'.  batched=False evaluates the neighbours branch by branch (getBestNNIForBran)."""
+        cap = self.num_nodes
+        ids = np.zeros(2 * cap, dtype=np.int32)
+        vals = np.zeros(7 * cap)
+        n, lnl = C.c_int(), C.c_double()
+        self._chk(self.lib.iqhost_test_all_branches(self.h, int(reps), int(lbp_reps), int(bool(batched)),
+                                                    ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), cap, C.byref(n),
+                                                    C.byref(lnl)))
+        out = np.zeros(n.value, dtype=SUPPORT_DTYPE)
+        v = vals[:7 * n.value].reshape(n.value, 7)
+        out["node1"], out["node2"] = ids[0:2 * n.value:2], ids[1:2 * n.value:2]
+        out["lh"] = v[:, 0:3]
+        for k, f in enumerate(("sh_alrt", "lbp", "abayes", "alrt_stat")):
+            out[f] = v[:, 3 + k]
+        return out
+
+    def support_tree_string(self, supports, with_sh=True, with_lbp=False):
+        """the tree with `SH-aLRT[/LBP]` labels (percent) on its internal nodes, the reference's label order"""
+        n = len(supports)
+        ids = np.zeros(2 * max(n, 1), dtype=np.int32)
+        vals = np.zeros(7 * max(n, 1))
+        for q in range(n):
+            ids[2 * q], ids[2 * q + 1] = supports["node1"][q], supports["node2"][q]
+            vals[7 * q + 3], vals[7 * q + 4] = supports["sh_alrt"][q], supports["lbp"][q]
+        buf = C.create_string_buffer(1 << 20)
+        self._chk(self.lib.iqhost_support_tree_string(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), n,
+                                                      int(with_sh), int(with_lbp), buf, len(buf)))
+        return buf.value.decode()
+
+    def ptnlh_reserve(self, nrows):
+        self._hip(libiqhip().iqhip_ptnlh_reserve(self.engine, int(nrows)))
+
+    def ptnlh_put_current(self, row, a, b):
+        """row <- per-pattern lnL of the branch (a, b) (BranchEnd) the last lnL evaluation ran on"""
+        self._hip(libiqhip().iqhip_ptnlh_put_current(self.engine, int(row), a, b))
+
+    def ptnlh_fetch(self, row):
+        out = np.zeros(self.nptn)
+        self._hip(libiqhip().iqhip_ptnlh_fetch(self.engine, int(row), _dptr(out)))
+        return out
+
+    def ptnlh_rell(self, rows, nsamples):
+        """R[i, s] = <store row rows[i], boot sample s> for the first nsamples samples (matrix-core product)"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        out = np.zeros((r.size, int(nsamples)))
+        self._hip(libiqhip().iqhip_ptnlh_rell(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size, int(nsamples),
+                                              _dptr(out)))
+        return out
+
+    def branch_tests(self, rows3, lh3, reps_sh, reps_lbp=0):
+        """iqhip_branch_tests: rows3 [nbranch, 3] store rows, lh3 [nbranch, 3] total lnL -> [nbranch, 4] =
+        sh_alrt, lbp, abayes, alrt_stat"""
+        r = np.ascontiguousarray(rows3, dtype=np.int32).reshape(-1, 3)
+        l = np.ascontiguousarray(lh3, dtype=np.float64).reshape(-1, 3)
+        assert r.shape == l.shape
+        out = (BranchSupport * max(r.shape[0], 1))()
+        self._hip(libiqhip().iqhip_branch_tests(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(l), r.shape[0],
+                                                int(reps_sh), int(reps_lbp), out))
+        return np.array([[o.sh_alrt, o.lbp, o.abayes, o.alrt_stat] for o in out[:r.shape[0]]])
 
     def compute_all_partial_lh(self):
         self._chk(self.lib.iqhost_compute_all_partial_lh(self.h))

@@ -259,7 +259,8 @@ extern "C" void iqhip_destroy(iqhip_engine *e) {
     void *ptrs[] = {e->d_states, e->d_freq, e->d_invar, e->d_model, e->d_ops, e->d_slab,
                     e->d_theta, e->d_pattern_lh, e->d_leaf_tab, e->dummy.plh, e->dummy.sc, e->d_newton_partials,
                     e->d_newton_barrier, e->d_newton_posts, e->d_fold_ticket, e->d_fold_flags, e->d_ptn_scaled, e->d_boot, e->d_img, e->d_theta_batch, e->d_batch_partials,
-                    e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks, e->d_batch_posts, e->d_sweep_len};
+                    e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks, e->d_batch_posts, e->d_sweep_len,
+                    e->d_ptnlh, e->d_bt_rows, e->d_bt_part, e->d_bt_sums, e->d_bt_out, e->d_batch_rows};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (e->h_ops) hipHostFree(e->h_ops);
@@ -1302,6 +1303,141 @@ extern "C" int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end 
     rc = read_result(e, e->nboot);
     if (rc) return rc;
     memcpy(rell, e->h_result, sizeof(double) * (size_t)e->nboot);
+    return IQHIP_OK;
+}
+
+// ---- branch tests (SH-aLRT, local bootstrap): the store of per-pattern log-likelihood rows and its consumers --------
+// (kernels_rell.hip k_ptnlh_rows fills rows from batched tasks, kernels_alrt.hip multiplies them with the sample matrix)
+int iqhip::ptnlh_plain_engine(iqhip_engine *e, const char *what) {
+    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
+    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines keep no per-pattern store");
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_reserve");
+    if (rc) return rc;
+    if (nrows < 0 || nrows > (1 << 20)) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_reserve: bad row count");
+    HIPCHK(use_device(e));
+    if (nrows <= e->ptnlh_rows) return IQHIP_OK;   // (rows keep their contents while the store does not grow)
+    double *grown = nullptr;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (hipMalloc((void **)&grown, sizeof(double) * (size_t)nrows * e->nptn_pad) != hipSuccess)
+        return fail(IQHIP_ERR_NOMEM, "iqhip_ptnlh_reserve: out of device memory");
+    // (on the engine's stream: a memset on the null stream is not ordered against the kernels that fill rows next)
+    HIPCHK(hipMemsetAsync(grown, 0, sizeof(double) * (size_t)nrows * e->nptn_pad, e->stream));
+    if (e->d_ptnlh)
+        HIPCHK(hipMemcpyAsync(grown, e->d_ptnlh, sizeof(double) * (size_t)e->ptnlh_rows * e->nptn_pad, hipMemcpyDeviceToDevice,
+                              e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->d_ptnlh) HIPCHK(hipFree(e->d_ptnlh));
+    e->d_ptnlh = grown;
+    e->ptnlh_rows = nrows;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_end a, iqhip_branch_end b) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_put_current");
+    if (rc) return rc;
+    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_put_current: row outside the store (iqhip_ptnlh_reserve)");
+    HIPCHK(use_device(e));
+    const int16_t *sc[2] = {nullptr, nullptr};
+    const iqhip_branch_end ends[2] = {a, b};
+    for (int k = 0; k < 2; k++) {
+        if (ends[k].leaf >= 0) continue;
+        int idx;
+        rc = slab_for_key(e, ends[k].key, false, &idx);
+        if (rc) return rc;
+        sc[k] = e->slabs[idx].sc;
+    }
+    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptnlh + (size_t)row * e->nptn_pad));
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_fetch");
+    if (rc) return rc;
+    if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_fetch: null argument");
+    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_fetch: row outside the store");
+    HIPCHK(use_device(e));
+    HIPCHK(hipMemcpyAsync(out, e->d_ptnlh + (size_t)row * e->nptn_pad, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+// the distinct rows of a row list in first-appearance order (d_bt_rows[0, M)) and, behind them, every entry's index into
+// that list; the product R = L W^T of the distinct rows ends in d_bt_sums [M][nsamples]
+static int ptnlh_product(iqhip_engine *e, const char *what, const int32_t *rows, int nrows, int nsamples, int *M_out) {
+    if (nsamples < 1 || nsamples > e->nboot)
+        return fail(IQHIP_ERR_INVALID, std::string(what) + (e->nboot == 0 ? ": no bootstrap samples (iqhip_set_boot_samples)"
+                                                                          : ": more replicates than uploaded samples"));
+    std::vector<int32_t> host((size_t)nrows, 0), distinct;
+    std::unordered_map<int32_t, int32_t> seen;
+    for (int i = 0; i < nrows; i++) {
+        if (rows[i] < 0 || rows[i] >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store");
+        auto it = seen.find(rows[i]);
+        if (it == seen.end()) {
+            it = seen.emplace(rows[i], (int32_t)distinct.size()).first;
+            distinct.push_back(rows[i]);
+        }
+        host[i] = it->second;
+    }
+    const int M = (int)distinct.size();
+    distinct.insert(distinct.end(), host.begin(), host.end());
+    HIPCHK(use_device(e));
+    if (distinct.size() > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, distinct.size(), distinct.size()));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source: the copy below must not outlive `distinct`)
+    HIPCHK(hipMemcpyAsync(e->d_bt_rows, distinct.data(), sizeof(int32_t) * distinct.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int ksplit = alrt_ksplit(e, M, nsamples);
+    const size_t sums = (size_t)M * nsamples, part = sums * ksplit;
+    if (part > e->bt_part_cap) HIPCHK(regrow(e, &e->d_bt_part, &e->bt_part_cap, part, part));
+    if (sums > e->bt_sums_cap) HIPCHK(regrow(e, &e->d_bt_sums, &e->bt_sums_cap, sums, sums));
+    HIPCHK(launch_alrt_product(e, e->d_bt_rows, M, nsamples, ksplit, e->d_bt_part, e->d_bt_sums));
+    *M_out = M;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows, int nsamples, double *out) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_rell");
+    if (rc) return rc;
+    if (!rows || !out || nrows < 1) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_rell: bad row list");
+    int M = 0;
+    rc = ptnlh_product(e, "iqhip_ptnlh_rell", rows, nrows, nsamples, &M);
+    if (rc) return rc;
+    std::vector<double> sums((size_t)M * nsamples);
+    HIPCHK(hipMemcpyAsync(sums.data(), e->d_bt_sums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::unordered_map<int32_t, int> idx;
+    for (int i = 0; i < nrows; i++) {
+        const int k = idx.emplace(rows[i], (int)idx.size()).first->second;
+        memcpy(out + (size_t)i * nsamples, sums.data() + (size_t)k * nsamples, sizeof(double) * (size_t)nsamples);
+    }
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const double *lh3, int nbranch, int reps_sh,
+                                  int reps_lbp, iqhip_branch_support *out) {
+    int rc = ptnlh_plain_engine(e, "iqhip_branch_tests");
+    if (rc) return rc;
+    if (!rows3 || !lh3 || !out || nbranch < 1 || nbranch > (1 << 24) || reps_sh < 0 || reps_lbp < 0)
+        return fail(IQHIP_ERR_INVALID, "iqhip_branch_tests: bad arguments");
+    const int times = std::max(reps_sh, reps_lbp);
+    int M = 0;
+    rc = ptnlh_product(e, "iqhip_branch_tests", rows3, 3 * nbranch, times, &M);
+    if (rc) return rc;
+    const size_t need = (size_t)7 * nbranch;
+    if (need > e->bt_out_cap) HIPCHK(regrow(e, &e->d_bt_out, &e->bt_out_cap, need, need));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_bt_out, lh3, sizeof(double) * 3 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
+    double *d_res = e->d_bt_out + 3 * (size_t)nbranch;
+    HIPCHK(launch_alrt_stats(e, e->d_bt_rows + M, e->d_bt_out, nbranch, times, e->d_bt_sums, d_res));
+    static_assert(sizeof(iqhip_branch_support) == 4 * sizeof(double), "iqhip_branch_support is four doubles");
+    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(iqhip_branch_support) * (size_t)nbranch, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
 }
 

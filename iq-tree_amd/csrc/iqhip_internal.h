@@ -428,6 +428,20 @@ struct iqhip_engine {
     double *d_ptn_scaled = nullptr;
     float *d_boot = nullptr;  // [nboot][nptn_pad], zero padded
     int nboot = 0;
+    // branch tests (SH-aLRT / local bootstrap): the store of per-pattern log-likelihood rows [ptnlh_rows][nptn_pad] and the
+    // scratch of iqhip_branch_tests / iqhip_ptnlh_rell (row lists, K-split partial products, combined sums, results)
+    double *d_ptnlh = nullptr;
+    int ptnlh_rows = 0;
+    int32_t *d_bt_rows = nullptr;       // [distinct rows] ++ [3 * nbranch indices into them]
+    size_t bt_rows_cap = 0;
+    double *d_bt_part = nullptr;        // [ksplit][M][nsamples]
+    size_t bt_part_cap = 0;
+    double *d_bt_sums = nullptr;        // [M][nsamples]
+    size_t bt_sums_cap = 0;
+    double *d_bt_out = nullptr;         // lh3 [3 * nbranch] ++ iqhip_branch_support [nbranch]
+    size_t bt_out_cap = 0;
+    int32_t *d_batch_rows = nullptr;    // iqhip_optimize_branch_batch_rows: store row per task of a chunk
+    size_t batch_rows_cap = 0;
     double *d_result_own = nullptr, *d_result = nullptr;
     double *d_newton_partials = nullptr;   // [2][num_cus][2]
     unsigned int *d_newton_barrier = nullptr;  // [2], used alternately by consecutive k_newton launches
@@ -756,6 +770,7 @@ int comm_use_device_result(iqhip_engine *e);  // switch the engine to a device-m
 // engine.hip internals the solvers (solve.hip) and the sharded front drive an engine with
 // a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
 hipError_t use_device(const iqhip_engine *e);
+int ptnlh_plain_engine(iqhip_engine *e, const char *what);   // the per-pattern store: single-device engines only
 int check_ready(iqhip_engine *e);                     // model and alignment set, device selected
 int ensure_slab_rows(iqhip_engine *e, int nrows);     // the wave-partial slab holds nrows rows
 // enqueue: plan upload, K1, fused traversal (+ optional root lnL), fixed-order reduction (skip_reduce: the caller's next
@@ -932,6 +947,17 @@ hipError_t launch_sweep4(iqhip_engine *e, const SweepOp *d_ops, const SweepStep 
 hipError_t launch_pattern_lh_scaled(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double *out);
 hipError_t launch_rell(iqhip_engine *e, double *out);
 hipError_t launch_pattern_lh_cat(iqhip_engine *e, double len, double *out);
+// rows of the per-pattern store from a chunk of k_newton_batch: task t of the m tasks -> store row d_rows[t] (< 0: none)
+hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const double *theta_base, size_t theta_stride,
+                             const double *batch_out, const int32_t *d_rows);
+
+// kernels_alrt.hip: R = L W^T on the fp64 matrix cores (K-split partial products, then a fixed-order combine) and the
+// SH-aLRT / local-bootstrap counts
+int alrt_ksplit(const iqhip_engine *e, int nrows, int nsamples);
+hipError_t launch_alrt_product(iqhip_engine *e, const int32_t *d_rows, int nrows, int nsamples, int ksplit, double *part,
+                               double *sums);
+hipError_t launch_alrt_stats(iqhip_engine *e, const int32_t *d_idx3, const double *d_lh3, int nbranch, int nsamples,
+                             const double *sums, double *out /* 4 per branch */);
 
 // batched branch optimisation (k_newton_batch); d_tasks: device array of NewtonTask (kernels_newton.hip)
 hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,
@@ -940,6 +966,7 @@ hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks,
                                double *posts = nullptr, double *posts_other = nullptr, size_t posts_other_used = 0,
                                int post_epochs = 0);
 size_t newton_task_bytes();
+size_t newton_task_branch_offset();   // of the DevBranch inside a NewtonTask
 void newton_task_fill(void *dst, const DevBranch &br, double xguess, double x1, double x2, double xacc, int max_steps);
 
 // kernels_valu4w.hip (4 states, 9 .. 32 categories): the launch choose_traverse_mfma described as TRAV_WIDE4

@@ -928,6 +928,7 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
 }
 
 size_t newton_task_bytes() { return sizeof(NewtonTask); }
+size_t newton_task_branch_offset() { return offsetof(NewtonTask, br); }
 void newton_task_fill(void *dst, const DevBranch &br, double xguess, double x1, double x2, double xacc, int max_steps) {
     NewtonTask t;
     memset(&t, 0, sizeof t);

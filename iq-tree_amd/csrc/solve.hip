@@ -708,8 +708,23 @@ static int optimize_branch_batch_sequential(iqhip_engine *e, const iqhip_branch_
 
 extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks,
                                            double *sum_scale, iqhip_branch_result *results) {
+    return iqhip_optimize_branch_batch_rows(e, tasks, ntasks, sum_scale, results, nullptr);
+}
+
+// rows != NULL: after each chunk of k_newton_batch, k_ptnlh_rows (kernels_rell.hip) writes the per-pattern log-likelihood
+// of every task with a row from the task's theta buffer (complete in memory once the launch has finished: the first
+// evaluation of a task stores every tile of it, in both vector layouts) at the accepted length in the result block
+extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_branch_task *tasks, int ntasks,
+                                                double *sum_scale, iqhip_branch_result *results, const int32_t *rows) {
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, "bad task array");
+    if (rows) {
+        const int rc = ptnlh_plain_engine(e, "iqhip_optimize_branch_batch_rows");
+        if (rc) return rc;
+        for (int t = 0; t < ntasks; t++)
+            if (rows[t] >= e->ptnlh_rows)
+                return fail(IQHIP_ERR_INVALID, "iqhip_optimize_branch_batch_rows: row outside the store (iqhip_ptnlh_reserve)");
+    }
     const char *seq_env = getenv("IQHIP_BATCH_SEQUENTIAL");   // (read per call: the tests compare the two forms)
     const bool sequential = seq_env && atoi(seq_env) != 0;
     if (!e->shards.empty())
@@ -773,6 +788,8 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
     }
     std::vector<char> host_tasks(newton_task_bytes() * (size_t)chunk);
     std::vector<double> out((size_t)chunk * 6);
+    if (rows && (size_t)chunk > e->batch_rows_cap)
+        HIPCHK(regrow(e, &e->d_batch_rows, &e->batch_rows_cap, (size_t)chunk, (size_t)chunk));
     for (int first = 0; first < ntasks; first += chunk) {
         const int m = std::min(chunk, ntasks - first);
         for (int t = 0; t < m; t++) {
@@ -817,6 +834,10 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
                                    e->d_batch_barriers + (size_t)parity * e->batch_cap,
                                    e->d_batch_barriers + (size_t)(1u - parity) * e->batch_cap, e->d_batch_out, posts, posts_other,
                                    posts_other_used, post_epochs));
+        if (rows) {   // (the theta buffers are reused by the next chunk: per chunk)
+            HIPCHK(hipMemcpyAsync(e->d_batch_rows, rows + first, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(launch_ptnlh_rows(e, e->d_batch_tasks, m, e->d_theta_batch, theta_stride, e->d_batch_out, e->d_batch_rows));
+        }
         HIPCHK(hipMemcpyAsync(out.data(), e->d_batch_out, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToHost,
                               e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));  // also: host_tasks / out are reused by the next chunk
@@ -833,6 +854,7 @@ extern "C" int iqhip_optimize_branch_batch(iqhip_engine *e, const iqhip_branch_t
                 rc = iqhip_compute_theta(e, k.a, k.b);
                 if (!rc) rc = newton_chain(e, k.xguess, k.x1, k.x2, k.xacc, k.max_steps, &r.optx, &r.d2l, &r.nsteps);
                 if (!rc) rc = iqhip_lnl_from_theta(e, r.optx, &r.lnl);
+                if (!rc && rows && rows[first + t] >= 0) rc = iqhip_ptnlh_put_current(e, rows[first + t], k.a, k.b);
                 if (rc) return rc;
                 r.status = 0;
             }

@@ -273,6 +273,57 @@ int iqhost_evaluate_nnis5_batch(void *h, int *ids, double *vals, int cap, int *n
         }
     });
 }
+// nni5 batch with the candidates' per-pattern lnL kept in the engine's store: candidate k -> row first_row + k
+int iqhost_evaluate_nnis5_batch_rows(void *h, int *ids, double *vals, int cap, int *n, int first_row) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<PhyloNode *> n1;
+        std::vector<PhyloNode *> n2;
+        t->internalBranches(n1, n2);
+        std::vector<int> rows(2 * n1.size());
+        for (size_t k = 0; k < rows.size(); k++) rows[k] = first_row + (int)k;
+        if (!t->engine) throw std::runtime_error("no engine");
+        if (iqhip_ptnlh_reserve(t->engine, first_row + (int)rows.size()) != 0) throw std::runtime_error(iqhip_last_error());
+        std::vector<PhyloTree::NNIMove> mv;
+        t->evaluateNNIs5Batch(mv, rows.data());
+        if ((int)mv.size() > cap) throw std::runtime_error("output too small");
+        *n = (int)mv.size();
+        for (size_t k = 0; k < mv.size(); k++) {
+            ids[4 * k] = mv[k].node1; ids[4 * k + 1] = mv[k].node2;
+            ids[4 * k + 2] = mv[k].node1_nei; ids[4 * k + 3] = mv[k].node2_nei;
+            for (int i = 0; i < 5; i++) vals[6 * k + i] = mv[k].newLen[i];
+            vals[6 * k + 5] = mv[k].newloglh;
+        }
+    });
+}
+// testAllBranches: ids[2q + {0,1}] = node1, node2; vals[7q + {0..6}] = lh0, lh1, lh2, sh_alrt, lbp, abayes, alrt_stat
+int iqhost_test_all_branches(void *h, int reps, int lbp_reps, int batched, int *ids, double *vals, int cap, int *n, double *lnl) {
+    IQHOST_TRY({
+        std::vector<PhyloTree::BranchSupport> sup;
+        *lnl = ((PhyloTree *)h)->testAllBranches(reps, lbp_reps, sup, batched != 0);
+        if ((int)sup.size() > cap) throw std::runtime_error("output too small");
+        *n = (int)sup.size();
+        for (size_t q = 0; q < sup.size(); q++) {
+            ids[2 * q] = sup[q].node1; ids[2 * q + 1] = sup[q].node2;
+            for (int k = 0; k < 3; k++) vals[7 * q + k] = sup[q].lh[k];
+            vals[7 * q + 3] = sup[q].sh_alrt; vals[7 * q + 4] = sup[q].lbp;
+            vals[7 * q + 5] = sup[q].abayes; vals[7 * q + 6] = sup[q].alrt_stat;
+        }
+    });
+}
+// the tree with "SH-aLRT[/LBP]" labels from n supports laid out as iqhost_test_all_branches returns them
+int iqhost_support_tree_string(void *h, const int *ids, const double *vals, int n, int with_sh, int with_lbp, char *out, int cap) {
+    IQHOST_TRY({
+        std::vector<PhyloTree::BranchSupport> sup((size_t)n);
+        for (int q = 0; q < n; q++) {
+            sup[q].node1 = ids[2 * q]; sup[q].node2 = ids[2 * q + 1];
+            sup[q].sh_alrt = vals[7 * q + 3]; sup[q].lbp = vals[7 * q + 4];
+        }
+        std::string s = ((PhyloTree *)h)->supportTreeString(sup, with_sh != 0, with_lbp != 0);
+        if ((int)s.size() + 1 > cap) throw std::runtime_error("output too small");
+        memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {
     PhyloTree *t = (PhyloTree *)h;

@@ -799,7 +799,7 @@ double PhyloTree::optimizeAllBranches(int my_iterations, double tolerance, int m
 }
 
 // =========================================================================================
-// NNI evaluation, phylotree.cpp:2873-3066 (upper-bound shortcut and ptnlh output left out)
+// NNI evaluation, phylotree.cpp:2873-3066 (upper-bound shortcut left out; the ptnlh output goes to the engine's store)
 // =========================================================================================
 static void updateNeighborNode(PhyloNode *at, PhyloNode *oldn, PhyloNode *newn) {
     for (PhyloNeighbor *nb : at->neighbors)
@@ -807,7 +807,8 @@ static void updateNeighborNode(PhyloNode *at, PhyloNode *oldn, PhyloNode *newn) 
     throw std::runtime_error("updateNeighbor: not adjacent");
 }
 
-PhyloTree::NNIMove PhyloTree::getBestNNIForBran(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2]) {
+PhyloTree::NNIMove PhyloTree::getBestNNIForBran(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2],
+                                                const int *ptnlh_rows) {
     if (node1->isLeaf() || node2->isLeaf() || node1->degree() != 3 || node2->degree() != 3)
         throw std::runtime_error("getBestNNIForBran needs an internal branch of a binary tree");
     if (!central_partial_lh) initializeAllPartialLh();
@@ -883,6 +884,12 @@ PhyloTree::NNIMove PhyloTree::getBestNNIForBran(PhyloNode *node1, PhyloNode *nod
             node12_it->clearPartialLh();
         }
         moves[cnt].newloglh = computeLikelihoodFromBuffer();
+        if (ptnlh_rows && ptnlh_rows[cnt] >= 0) {  // computePatternLikelihood(nniMoves[cnt].ptnlh), phylotree.cpp:3019-3020
+            if (!engine || dry_run) throw std::runtime_error("getBestNNIForBran: store rows need an attached engine");
+            check(iqhip_ptnlh_put_current(engine, ptnlh_rows[cnt], branchEnd(current_it), branchEnd(current_it_back)),
+                  "iqhip_ptnlh_put_current");
+            moves[cnt].ptnlh_row = ptnlh_rows[cnt];
+        }
         // swap back (:3027-3030)
         node1->neighbors[i1] = node1_nei;
         updateNeighborNode(node1_nei->node, node2, node1);
@@ -1027,7 +1034,19 @@ void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves) {
     }
 }
 
-void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves) {
+void PhyloTree::internalBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2) const {
+    n1.clear();
+    n2.clear();
+    for (PhyloNode *node1 : nodes)
+        for (PhyloNeighbor *nb12 : node1->neighbors) {
+            PhyloNode *node2 = nb12->node;
+            if (node1->isLeaf() || node2->isLeaf() || node1->id > node2->id) continue;
+            n1.push_back(node1);
+            n2.push_back(node2);
+        }
+}
+
+void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows) {
     if (!engine || dry_run) throw std::runtime_error("evaluateNNIs5Batch needs an attached engine");
     if (allreduce_hook) throw std::runtime_error("evaluateNNIs5Batch: runs with a caller-owned collective use getBestNNIForBran");
     computeAllPartialLh();
@@ -1140,8 +1159,15 @@ void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves) {
             }
             std::vector<double> ss(2 * nb + 2, 0.0);
             std::vector<iqhip_branch_result> rr(nb);
-            check(iqhip_optimize_branch_batch(engine, tasks.data(), (int)nb, ss.data(), rr.data()),
-                  "iqhip_optimize_branch_batch");
+            if (round == 4 && ptnlh_rows) {  // the lnL of the last round is the candidate's: keep its per-pattern values
+                std::vector<int32_t> rows(nb);
+                for (size_t q = 0; q < nb; q++) rows[q] = ptnlh_rows[2 * q + cnt];
+                check(iqhip_optimize_branch_batch_rows(engine, tasks.data(), (int)nb, ss.data(), rr.data(), rows.data()),
+                      "iqhip_optimize_branch_batch_rows");
+                for (size_t q = 0; q < nb; q++) moves[2 * q + cnt].ptnlh_row = rows[q];
+            } else
+                check(iqhip_optimize_branch_batch(engine, tasks.data(), (int)nb, ss.data(), rr.data()),
+                      "iqhip_optimize_branch_batch");
             num_submissions++;
             size_t sp = 0;
             for (size_t q = 0; q < nb; q++) {
@@ -1186,12 +1212,122 @@ void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves) {
             branches[q].l0 = w.l0;
             if (w.diverged) {  // diverged Newton (phylotree.cpp:2167-2176): rare; take the branch-by-branch path
                 NNIMove two[2];
-                getBestNNIForBran(branches[q].node1, branches[q].node2, true, two);
+                getBestNNIForBran(branches[q].node1, branches[q].node2, true, two, ptnlh_rows ? ptnlh_rows + 2 * q : nullptr);
                 moves[2 * q] = two[0];
                 moves[2 * q + 1] = two[1];
             }
         }
     }
+}
+
+// =========================================================================================
+// SH-aLRT / local bootstrap, phylotree.cpp:3984-4103
+// =========================================================================================
+double PhyloTree::testAllBranches(int reps, int lbp_reps, std::vector<BranchSupport> &out, bool batched) {
+    if (!engine || dry_run) throw std::runtime_error("testAllBranches needs an attached engine");
+    if (allreduce_hook) throw std::runtime_error("testAllBranches: not available with a caller-owned collective");
+    if (reps < 0 || lbp_reps < 0 || std::max(reps, lbp_reps) < 1) throw std::runtime_error("testAllBranches: no replicates");
+    if (std::max(reps, lbp_reps) > num_boot_samples) throw std::runtime_error("testAllBranches: more replicates than setBootSamples uploaded");
+    if (batched && lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error("testAllBranches(batched) needs LM_ALL_BRANCH");
+    std::vector<PhyloNode *> n1, n2;
+    internalBranches(n1, n2);
+    const size_t nb = n1.size();
+    if (nb == 0) throw std::runtime_error("testAllBranches: the tree has no internal branch");
+    const double lh0 = computeLikelihood();
+    check(iqhip_ptnlh_reserve(engine, (int)(1 + 2 * nb)), "iqhip_ptnlh_reserve");
+    check(iqhip_ptnlh_put_current(engine, 0, branchEnd(current_it), branchEnd(current_it_back)), "iqhip_ptnlh_put_current");
+    std::vector<int> rows(2 * nb);
+    for (size_t k = 0; k < 2 * nb; k++) rows[k] = (int)(1 + k);
+    std::vector<NNIMove> moves;
+    if (batched) {
+        evaluateNNIs5Batch(moves, rows.data());
+    } else {
+        moves.resize(2 * nb);
+        for (size_t q = 0; q < nb; q++) {
+            NNIMove two[2];
+            getBestNNIForBran(n1[q], n2[q], true, two, &rows[2 * q]);
+            moves[2 * q] = two[0];
+            moves[2 * q + 1] = two[1];
+        }
+    }
+    std::vector<int32_t> rows3(3 * nb);
+    std::vector<double> lh3(3 * nb);
+    for (size_t q = 0; q < nb; q++) {
+        rows3[3 * q] = 0;
+        lh3[3 * q] = lh0;
+        for (int cnt = 0; cnt < 2; cnt++) {
+            const NNIMove &m = moves[2 * q + cnt];
+            if (m.node1 != n1[q]->id || m.node2 != n2[q]->id || m.ptnlh_row != rows[2 * q + cnt])
+                throw std::runtime_error("testAllBranches: NNI moves out of order");
+            rows3[3 * q + 1 + cnt] = m.ptnlh_row;
+            lh3[3 * q + 1 + cnt] = m.newloglh;
+        }
+    }
+    std::vector<iqhip_branch_support> res(nb);
+    check(iqhip_branch_tests(engine, rows3.data(), lh3.data(), (int)nb, reps, lbp_reps, res.data()), "iqhip_branch_tests");
+    out.assign(nb, BranchSupport());
+    for (size_t q = 0; q < nb; q++) {
+        BranchSupport &b = out[q];
+        b.node1 = n1[q]->id;
+        b.node2 = n2[q]->id;
+        for (int k = 0; k < 3; k++) b.lh[k] = lh3[3 * q + k];
+        b.sh_alrt = res[q].sh_alrt;
+        b.lbp = res[q].lbp;
+        b.abayes = res[q].abayes;
+        b.alrt_stat = res[q].alrt_stat;
+    }
+    return lh0;
+}
+
+std::string PhyloTree::supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp) {
+    std::ostringstream ss;  // phylotree.cpp:4078-4091 (node names are empty here)
+    ss.precision(3);
+    if (with_sh) ss << sh_alrt * 100;
+    if (with_lbp) ss << "/" << lbp * 100;
+    return ss.str();
+}
+
+static void writeSupportNewick(std::ostringstream &os, const PhyloNode *node, const PhyloNode *dad,
+                               const std::vector<std::string> &label) {
+    if (node->isLeaf() && dad) {
+        if (node->name.empty()) os << node->id;
+        else os << node->name;
+        return;
+    }
+    os << "(";
+    bool first = true;
+    for (PhyloNeighbor *nb : node->neighbors)
+        if (nb->node != dad) {
+            if (!first) os << ",";
+            first = false;
+            writeSupportNewick(os, nb->node, node, label);
+            os.precision(17);
+            os << ":" << nb->length;
+        }
+    os << ")" << label[node->id];
+}
+
+std::string PhyloTree::supportTreeString(const std::vector<BranchSupport> &sup, bool with_sh, bool with_lbp) const {
+    // testAllBranches walks from the root leaf and names `node` of every internal (node, dad): the far end of the branch,
+    // which is also where a Newick string printed from the root's neighbour puts the label of that branch
+    if (!root) return ";";
+    std::vector<std::string> label(nodes.size());
+    std::vector<std::pair<PhyloNode *, PhyloNode *>> stack;
+    stack.push_back({root, nullptr});
+    while (!stack.empty()) {
+        PhyloNode *node = stack.back().first, *dad = stack.back().second;
+        stack.pop_back();
+        if (dad && !node->isLeaf() && !dad->isLeaf())
+            for (const BranchSupport &b : sup)
+                if ((b.node1 == node->id && b.node2 == dad->id) || (b.node2 == node->id && b.node1 == dad->id))
+                    label[node->id] = supportLabel(b.sh_alrt, b.lbp, with_sh, with_lbp);
+        for (PhyloNeighbor *nb : node->neighbors)
+            if (nb->node != dad) stack.push_back({nb->node, node});
+    }
+    std::ostringstream os;
+    writeSupportNewick(os, root->neighbors[0]->node, nullptr, label);
+    os << ";";
+    return os.str();
 }
 
 // =========================================================================================

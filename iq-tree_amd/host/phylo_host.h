@@ -171,8 +171,12 @@ public:
         int node1_nei = -1, node2_nei = -1;  // the two subtrees (by their root node id) that were swapped
         double newloglh = 0.0;
         double newLen[5] = {0, 0, 0, 0, 0};
+        int ptnlh_row = -1;  // row of the engine's per-pattern store holding this neighbour's pattern lnL (the reference's ptnlh)
     };
-    NNIMove getBestNNIForBran(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2]);
+    // ptnlh_rows (optional, 2 entries): store rows that receive the per-pattern lnL of the two neighbours
+    // (iqhip_ptnlh_put_current after the final computeLikelihoodFromBuffer, phylotree.cpp:3019-3020)
+    NNIMove getBestNNIForBran(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2],
+                              const int *ptnlh_rows = nullptr);
     static const int NNI_MAX_NR_STEP = 10;  // phylotree.h
     // computeAllPartialLh (phylotree.cpp:504-514): every directed vector valid (needs LM_ALL_BRANCH)
     void computeAllPartialLh();
@@ -183,7 +187,27 @@ public:
     // the same with nni5 (the reference's default, params.nni5): per candidate the two branches at node1, the
     // central branch and the two at node2 are optimised in that order (phylotree.cpp:2984-3024); five rounds of
     // batched tasks per swap, ten submissions per tree instead of ~10 per branch
-    void evaluateNNIs5Batch(std::vector<NNIMove> &moves);
+    // ptnlh_rows (optional, 2 per internal branch in move order): the last round goes through
+    // iqhip_optimize_branch_batch_rows, so every candidate's per-pattern lnL lands in its store row on the device
+    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows = nullptr);
+    // the internal branches in the order both NNI evaluations list them (node1->id < node2->id)
+    void internalBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2) const;
+
+    // ---- SH-aLRT / local bootstrap (PhyloTree::testAllBranches, phylotree.cpp:3984-4103) on the device:
+    //      computeLikelihood -> store row 0; both NNI neighbours of every internal branch with five branches re-optimised
+    //      -> rows 1 + 2 q + cnt; one iqhip_branch_tests on the samples of setBootSamples (ONE sample matrix for all
+    //      branches, see include/iqhip.h).  batched: evaluateNNIs5Batch (needs LM_ALL_BRANCH); else getBestNNIForBran
+    //      branch by branch.  Returns the tree's lnL.
+    struct BranchSupport {
+        int node1 = -1, node2 = -1;
+        double lh[3] = {0, 0, 0};
+        double sh_alrt = 0, lbp = 0, abayes = 0, alrt_stat = 0;
+    };
+    double testAllBranches(int reps, int lbp_reps, std::vector<BranchSupport> &out, bool batched = true);
+    // Newick with "SH-aLRT[/LBP]" labels (percent, precision 3) on the internal nodes, in the reference's label order
+    // (phylotree.cpp:4078-4091); the label of an internal branch sits on its node farther from the root
+    std::string supportTreeString(const std::vector<BranchSupport> &sup, bool with_sh, bool with_lbp) const;
+    static std::string supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp);
 
     // ---- consumers of the per-pattern lnL (phylotree.cpp:1200-1230, iqtree.cpp:2676-2750) ----------
     // computePatternLikelihood: lnL per pattern of the last computeLikelihood(), scaling events of
