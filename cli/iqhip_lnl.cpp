@@ -7,6 +7,11 @@
 // X.sitelh.  With -alrt N [-lbp N] [-seed S] it then runs the SH-aLRT / local-bootstrap branch tests on the device
 // (PhyloTree::testAllBranches) and prints the tree with SH-aLRT[/LBP] node labels; the site resamples are multinomial
 // draws of its own generator (std::mt19937_64), not the reference's RNG stream.
+// With -z <treefile> -zb N [-zw] [-au] [-seed S] it runs the tree topology tests of the reference's evaluateTrees on the
+// trees of <treefile> (Newick, one after the other; -blfix keeps their branch lengths): one line per tree with logL,
+// bp-RELL, p-KH, p-SH, [p-WKH, p-WSH,] c-ELW and +/- marks (confidence set; p >= 0.05), and with -au the bootstrap
+// proportions of the AU test's ten scales r = 0.5 .. 1.4 (the AU p-value itself is not computed).  The resamples are drawn
+// on the device by the engine's own generator (include/iqhip.h), not the reference's RNG stream.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,6 +34,7 @@ static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
+            "                 [-z <tree set file> -zb <n> [-zw] [-au]]\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
 }
@@ -38,6 +44,9 @@ int main(int argc, char **argv) {
     bool blfix = false, wsl = false, all_branch = false;
     int dev = 0, reps = 0, alrt = 0, lbp = 0;
     unsigned long long seed = 1;
+    std::string treeset_file;
+    int zb = 0;
+    bool zw = false, au = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -56,6 +65,10 @@ int main(int argc, char **argv) {
         else if (a == "-reps") reps = atoi(next().c_str());
         else if (a == "-alrt") alrt = atoi(next().c_str());
         else if (a == "-lbp") lbp = atoi(next().c_str());
+        else if (a == "-z") treeset_file = next();
+        else if (a == "-zb") zb = atoi(next().c_str());
+        else if (a == "-zw") zw = true;
+        else if (a == "-au") au = true;
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
@@ -63,6 +76,7 @@ int main(int argc, char **argv) {
     if (aln_file.empty() || tree_file.empty() || model_str.empty()) { usage(); return 2; }
     if (prefix.empty()) prefix = aln_file;
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
+    if (zb < 0 || (!treeset_file.empty() && zb < 1) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
     if (alrt > 0 || lbp > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
         Alignment aln;
@@ -155,6 +169,51 @@ int main(int argc, char **argv) {
             printf("Tree with %s%s supports: %s\n", alrt > 0 ? "SH-aLRT" : "", lbp > 0 ? "/LBP" : "", labelled.c_str());
             std::ofstream out((prefix + ".iqhip").c_str(), std::ios::app);
             out << "support_tree " << labelled << "\n";
+        }
+        if (!treeset_file.empty()) {
+            std::ifstream zin(treeset_file.c_str());
+            if (!zin) throw std::runtime_error("cannot open tree set file " + treeset_file);
+            std::stringstream zss;
+            zss << zin.rdbuf();
+            std::vector<std::string> newicks;
+            std::string cur;
+            for (char c : zss.str()) {
+                cur += c;
+                if (c == ';') {
+                    if (cur.find('(') != std::string::npos) newicks.push_back(cur);
+                    cur.clear();
+                }
+            }
+            std::vector<double> scales;
+            if (au) scales = {0.5, 0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3, 1.4};
+            std::vector<PhyloTree::TreeTest> res;
+            std::vector<double> au_bp;
+            auto t0 = std::chrono::steady_clock::now();
+            tree.evaluateTrees(newicks, blfix, zb, zw, scales, seed, res, au_bp);
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("Tree topology tests (%d trees, %d RELL replicates%s): %.4f s\n", (int)res.size(), zb,
+                   au ? ", AU replicates at 10 scales" : "", sec);
+            printf("Tree      logL    bp-RELL    p-KH     p-SH    %sc-ELW\n", zw ? "p-WKH    p-WSH    " : "");
+            for (size_t t = 0; t < res.size(); t++) {
+                const iqhip_tree_test &r = res[t].t;
+                printf("TOPOTEST %3d %.6f  %.4f %c  %.4f %c  %.4f %c  ", (int)t + 1, res[t].logl, r.rell_bp,
+                       r.rell_confident ? '+' : '-', r.kh_pvalue, r.kh_pvalue < 0.05 ? '-' : '+', r.sh_pvalue,
+                       r.sh_pvalue < 0.05 ? '-' : '+');
+                if (zw)
+                    printf("%.4f %c  %.4f %c  ", r.wkh_pvalue, r.wkh_pvalue < 0.05 ? '-' : '+', r.wsh_pvalue,
+                           r.wsh_pvalue < 0.05 ? '-' : '+');
+                printf("%.4f %c\n", r.elw_value, r.elw_confident ? '+' : '-');
+            }
+            if (au) {
+                printf("AU bootstrap proportions per scale r (STEP 2 of the AU test; no AU p-value is computed)\nAUSCALE   r");
+                for (double r : scales) printf(" %6.1f", r);
+                printf("\n");
+                for (size_t t = 0; t < res.size(); t++) {
+                    printf("AUBP    %3d", (int)t + 1);
+                    for (size_t k = 0; k < scales.size(); k++) printf(" %.4f", au_bp[k * res.size() + t]);
+                    printf("\n");
+                }
+            }
         }
         if (wsl) {
             writeSiteLh(prefix + ".sitelh", aln, pattern_lh.data());

@@ -375,6 +375,63 @@ int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const double *lh3,
                        iqhip_branch_support *out);
 int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows, int nsamples, double *out /* nrows*nsamples */);
 
+/* ---- Tree topology tests: RELL-BP, KH, SH, weighted KH / SH, c-ELW and the bootstrap proportions of the AU test
+ * (evaluateTrees / performAUTest, phylotesting.cpp:1916-2050, 2053-2442; options -z trees -zb N [-zw] [-au]) ------------
+ * The caller fills one store row per candidate tree (iqhip_ptnlh_put_current after optimising the tree, or
+ * iqhip_ptnlh_upload) and keeps the trees' total log-likelihoods; the rows stay on the device, the RELL sums are the
+ * matrix-core product of iqhip_ptnlh_rell, the comparisons run per replicate on the device and a few doubles per tree
+ * leave it.
+ * iqhip_ptnlh_upload: host -> one store row (nptn doubles, the padding zeroed), the counterpart of iqhip_ptnlh_fetch.
+ * iqhip_gen_boot_samples: draws rows [0, nsamples) of the engine's sample matrix ON THE DEVICE; it allocates the matrix
+ *   as iqhip_set_boot_samples does and replaces its content, and iqhip_rell, iqhip_ptnlh_rell, iqhip_branch_tests and
+ *   iqhip_tree_tests then work on the generated samples.  Row i is replicate rho = first_replicate + i; for every draw
+ *   j < ndraws
+ *       z = mix(mix(mix(seed + G (stream + 1)) + G (rho + 1)) + G (j + 1)),   G = 0x9E3779B97F4A7C15,
+ *       mix = the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
+ *             z ^= z >> 31), all modulo 2^64,
+ *       site = mulhi64(z, nsite), nsite = sum ptn_freq; pattern = the first p whose inclusive integer prefix sum of
+ *       ptn_freq exceeds site; count[pattern] += 1
+ *   -- the distribution of the reference's per-site loop (alignment.cpp:2319-2350; its multinomial branch has the same).
+ *   Patterns of frequency 0 (the unobserved +ASC patterns, the padding) never receive a draw.  Counts are integer
+ *   atomics converted to float afterwards: the same arguments give the same matrix on every run, and generating [0, n)
+ *   at once equals generating any split of it.  ptn_freq must hold non-negative integers (IQHIP_ERR_INVALID otherwise);
+ *   ndraws <= 2^24 (a float holds no larger count exactly).
+ * iqhip_ptnlh_diff_variance: computeLogLDiffVariance (phylotree.cpp:1390-1416) for all pairs of the row list: the
+ *   weighted mean of the difference, then sum f (d - mean)^2 nsite / (nsite - 1); symmetric, diagonal 0, nsite <= 1 gives 0.
+ * iqhip_tree_tests: phylotesting.cpp:2218-2411 on the first nsamples rows of the sample matrix for the trees whose rows
+ *   and total log-likelihoods are given (rows may repeat; each distinct row is multiplied once).  avg_lh is summed in
+ *   replicate order, so every comparison sees the reference's bits for the same sums.  epsilon is params.ufboot_epsilon
+ *   of the RELL-BP tie rule (:2230-2239); its random_double() is (z >> 11) 2^-53 with z of the generator above for
+ *   (tie_seed, stream 0xB9, rho = replicate, j = tree).  weighted != 0 adds the weighted KH / SH tests (:2323-2370) with
+ *   weights 1 / sqrt(iqhip_ptnlh_diff_variance); otherwise wkh_pvalue = wsh_pvalue = -1.  The two 95 % confidence sets
+ *   (:2248-2255, :2404-2411) are formed on the host from the returned shares; among equal shares the tree with the
+ *   highest index enters first (the reference's order among equal shares is that of its quicksort).
+ * iqhip_multiscale_bp: STEP 2 of performAUTest: for every scale k, nsamples replicates of ndraws = (int)round(scales[k]
+ *   nsite) draws (replicates rho = 0 .. nsamples-1 of stream k of `seed`), generated, multiplied and counted chunk by
+ *   chunk on the device -- no sample matrix crosses the bus; bp[k * ntrees + tid] = fraction of the replicates in which
+ *   tree tid is the first with the strictly largest sum (:1974-1979).  The chunk keeps the sample matrix within 256 MB
+ *   (IQHIP_BOOT_CHUNK, read per call, overrides the replicates per chunk); the K-split of the products follows from the
+ *   pattern and CU counts only, so the counts do not depend on the chunk size.  The sample matrix is left with the last
+ *   chunk.  STEP 3 / 4 of the AU test (the weighted-least-squares / maximum-likelihood fit of (d, c) and the normal
+ *   quantiles) stay with the caller, as Statistics_To_Probabilities does for the aLRT.
+ * DEVIATIONS from the reference: the resamples and the tie draws come from the counter-based generator above, not from
+ *   the reference's RNG stream (as for -alrt); the AU replicates of all trees share one sample matrix, as they do there.
+ * Out of scope: sharded engines and communicator ranks return IQHIP_ERR_UNSUPPORTED from all five calls, planning-only
+ *   engines IQHIP_ERR_INVALID.  IQHIP_ERR_INVALID also for rows outside the store, fewer than two trees, more replicates
+ *   than the matrix holds (iqhip_tree_tests) and a scale <= 0. */
+typedef struct iqhip_tree_test {
+    double rell_bp, kh_pvalue, sh_pvalue, wkh_pvalue, wsh_pvalue, elw_value;
+    int32_t rell_confident, elw_confident;
+} iqhip_tree_test;
+int iqhip_ptnlh_upload(iqhip_engine *e, int row, const double *in /* nptn */);
+int iqhip_gen_boot_samples(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t seed,
+                           uint32_t stream);
+int iqhip_ptnlh_diff_variance(iqhip_engine *e, const int32_t *rows, int nrows, double *var /* nrows*nrows */);
+int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int ntrees, int nsamples, double epsilon,
+                     int weighted, uint64_t tie_seed, iqhip_tree_test *out /* ntrees */);
+int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales, int nsamples,
+                        uint64_t seed, double *bp /* nscales*ntrees, bp[k*ntrees+tid] */);
+
 /* Host -> device (tests; SPR/NNI code that fills a buffer on the host). */
 int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
                          const int16_t *scale_num);

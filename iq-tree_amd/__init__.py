@@ -38,6 +38,7 @@ IQHIP_SYMBOLS = [
     "iqhip_debug_path_counts", "iqhip_debug_plan_shape",
     "iqhip_ptnlh_reserve", "iqhip_ptnlh_put_current", "iqhip_ptnlh_fetch", "iqhip_optimize_branch_batch_rows",
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
+    "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -67,6 +68,13 @@ class BranchSupport(C.Structure):
     _fields_ = [("sh_alrt", C.c_double), ("lbp", C.c_double), ("abayes", C.c_double), ("alrt_stat", C.c_double)]
 
 
+class TreeTest(C.Structure):
+    """struct iqhip_tree_test (include/iqhip.h)."""
+    _fields_ = [("rell_bp", C.c_double), ("kh_pvalue", C.c_double), ("sh_pvalue", C.c_double), ("wkh_pvalue", C.c_double),
+                ("wsh_pvalue", C.c_double), ("elw_value", C.c_double), ("rell_confident", C.c_int32),
+                ("elw_confident", C.c_int32)]
+
+
 class BranchTask(C.Structure):
     """struct iqhip_branch_task (include/iqhip.h)."""
     _fields_ = [("ops", C.c_void_p), ("nops", C.c_int32), ("max_steps", C.c_int32), ("a", BranchEnd), ("b", BranchEnd),
@@ -78,6 +86,11 @@ class BranchResult(C.Structure):
     _fields_ = [("optx", C.c_double), ("d2l", C.c_double), ("lnl", C.c_double), ("nsteps", C.c_int32), ("status", C.c_int32)]
 
 
+# tree_tests / evaluate_trees: one record per tree
+TREE_TEST_DTYPE = np.dtype([("logl", np.float64), ("rell_bp", np.float64), ("kh_pvalue", np.float64),
+                            ("sh_pvalue", np.float64), ("wkh_pvalue", np.float64), ("wsh_pvalue", np.float64),
+                            ("elw_value", np.float64), ("rell_confident", np.bool_), ("elw_confident", np.bool_)])
+AU_SCALES = (0.5, 0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3, 1.4)   # performAUTest, phylotesting.cpp:1920
 # test_all_branches: one record per internal branch
 SUPPORT_DTYPE = np.dtype([("node1", np.int32), ("node2", np.int32), ("lh", np.float64, (3,)), ("sh_alrt", np.float64),
                           ("lbp", np.float64), ("abayes", np.float64), ("alrt_stat", np.float64)])
@@ -187,6 +200,11 @@ def libiqhip():
     lib.iqhip_optimize_branch_batch_rows.argtypes = [vp, C.POINTER(BranchTask), C.c_int, dp, C.POINTER(BranchResult), i32p]
     lib.iqhip_branch_tests.argtypes = [vp, i32p, dp, C.c_int, C.c_int, C.c_int, C.POINTER(BranchSupport)]
     lib.iqhip_ptnlh_rell.argtypes = [vp, i32p, C.c_int, C.c_int, dp]
+    lib.iqhip_ptnlh_upload.argtypes = [vp, C.c_int, dp]
+    lib.iqhip_gen_boot_samples.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32]
+    lib.iqhip_ptnlh_diff_variance.argtypes = [vp, i32p, C.c_int, dp]
+    lib.iqhip_tree_tests.argtypes = [vp, i32p, dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.POINTER(TreeTest)]
+    lib.iqhip_multiscale_bp.argtypes = [vp, i32p, C.c_int, dp, C.c_int, C.c_int, C.c_uint64, dp]
     lib._iq_typed = True
     return lib
 
@@ -249,6 +267,9 @@ def libiqhost():
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.iqhost_test_all_branches.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), dp, C.c_int,
                                              C.POINTER(C.c_int), dp]
+    lib.iqhost_gen_boot_samples.argtypes = [vp, C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32]
+    lib.iqhost_evaluate_trees.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int,
+                                          C.c_uint64, C.c_double, dp, dp]
     lib.iqhost_support_tree_string.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]
     lib.iqhost_fetch_scale_num.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int16)]
     lib.iqhost_fetch_partial.argtypes = [vp, C.c_int, C.c_int, dp]
@@ -675,6 +696,66 @@ class PhyloTree:
         self._hip(libiqhip().iqhip_branch_tests(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(l), r.shape[0],
                                                 int(reps_sh), int(reps_lbp), out))
         return np.array([[o.sh_alrt, o.lbp, o.abayes, o.alrt_stat] for o in out[:r.shape[0]]])
+
+    # ---- tree topology tests (include/iqhip.h "tree topology tests")
+    def ptnlh_upload(self, row, values):
+        """store row <- nptn host doubles (the counterpart of ptnlh_fetch)"""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        assert v.size == self.nptn
+        self._hip(libiqhip().iqhip_ptnlh_upload(self.engine, int(row), _dptr(v)))
+
+    def gen_boot_samples(self, nsamples, ndraws, seed, stream=0xA0, first_replicate=0):
+        """iqhip_gen_boot_samples: rows [0, nsamples) of the sample matrix drawn on the device (ndraws sites each)"""
+        self._chk(self.lib.iqhost_gen_boot_samples(self.h, int(nsamples), int(first_replicate), int(ndraws), int(seed),
+                                                   int(stream)))
+        self._nboot = int(nsamples)
+
+    def ptnlh_diff_variance(self, rows):
+        """computeLogLDiffVariance for all pairs of store rows -> [nrows, nrows]"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        out = np.zeros((r.size, r.size))
+        self._hip(libiqhip().iqhip_ptnlh_diff_variance(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size, _dptr(out)))
+        return out
+
+    def tree_tests(self, rows, lh, nsamples, epsilon=0.5, weighted=False, tie_seed=0):
+        """iqhip_tree_tests -> TREE_TEST_DTYPE record per tree (logl = lh)"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        l = np.ascontiguousarray(lh, dtype=np.float64)
+        assert r.shape == l.shape and r.ndim == 1
+        res = (TreeTest * max(r.size, 1))()
+        self._hip(libiqhip().iqhip_tree_tests(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(l), r.size,
+                                              int(nsamples), float(epsilon), int(bool(weighted)), int(tie_seed), res))
+        out = np.zeros(r.size, dtype=TREE_TEST_DTYPE)
+        out["logl"] = l
+        for f in TREE_TEST_DTYPE.names[1:]:
+            out[f] = [getattr(o, f) for o in res[:r.size]]
+        return out
+
+    def multiscale_bp(self, rows, scales, nsamples, seed):
+        """iqhip_multiscale_bp -> bp[nscales, ntrees], the bootstrap proportions of the AU test's STEP 2"""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        sc = np.ascontiguousarray(scales, dtype=np.float64)
+        out = np.zeros((sc.size, r.size))
+        self._hip(libiqhip().iqhip_multiscale_bp(self.engine, r.ctypes.data_as(C.POINTER(C.c_int32)), r.size, _dptr(sc), sc.size,
+                                                 int(nsamples), int(seed), _dptr(out)))
+        return out
+
+    def evaluate_trees(self, newicks, nsamples, fixed_lengths=False, weighted=False, au_scales=None, seed=1, epsilon=0.5):
+        """evaluateTrees (-z trees -zb nsamples [-zw] [-au]) on the device: (TREE_TEST_DTYPE record per tree,
+        bp[nscales, ntrees] of the AU scales or None).  Store row t holds tree t's per-pattern lnL afterwards."""
+        n = len(newicks)
+        arr = (C.c_char_p * n)(*[s.encode() for s in newicks])
+        sc = np.ascontiguousarray([] if au_scales is None else au_scales, dtype=np.float64)
+        vals = np.zeros(9 * max(n, 1))
+        bp = np.zeros((max(sc.size, 1), max(n, 1)))
+        self._chk(self.lib.iqhost_evaluate_trees(self.h, arr, n, int(bool(fixed_lengths)), int(nsamples), int(bool(weighted)),
+                                                 _dptr(sc), sc.size, int(seed), float(epsilon), _dptr(vals), _dptr(bp)))
+        self._nboot = int(nsamples)
+        out = np.zeros(n, dtype=TREE_TEST_DTYPE)
+        v = vals[:9 * n].reshape(n, 9)
+        for k, f in enumerate(TREE_TEST_DTYPE.names):
+            out[f] = v[:, k]
+        return out, (bp[:sc.size, :n].copy() if sc.size else None)
 
     def compute_all_partial_lh(self):
         self._chk(self.lib.iqhost_compute_all_partial_lh(self.h))

@@ -1,12 +1,14 @@
 // engine.hip -- host side of libiqhip.so: device memory, key->slab map, submissions and the
 // extern "C" entry points declared in include/iqhip.h.  There is NO CPU fallback in this
 // library: every compute entry point launches HIP kernels or fails with a status.
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 
 #include "iqhip_internal.h"
@@ -260,7 +262,8 @@ extern "C" void iqhip_destroy(iqhip_engine *e) {
                     e->d_theta, e->d_pattern_lh, e->d_leaf_tab, e->dummy.plh, e->dummy.sc, e->d_newton_partials,
                     e->d_newton_barrier, e->d_newton_posts, e->d_fold_ticket, e->d_fold_flags, e->d_ptn_scaled, e->d_boot, e->d_img, e->d_theta_batch, e->d_batch_partials,
                     e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks, e->d_batch_posts, e->d_sweep_len,
-                    e->d_ptnlh, e->d_bt_rows, e->d_bt_part, e->d_bt_sums, e->d_bt_out, e->d_batch_rows};
+                    e->d_ptnlh, e->d_bt_rows, e->d_bt_part, e->d_bt_sums, e->d_bt_out, e->d_batch_rows,
+                    e->d_freq_prefix, e->d_tt_var, e->d_tt_dbl, e->d_tt_int};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (e->h_ops) hipHostFree(e->h_ops);
@@ -395,6 +398,7 @@ extern "C" int iqhip_set_ptn_freq(iqhip_engine *e, const double *ptn_freq) {
     HIPCHK(hipMemcpyAsync(e->d_freq, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    e->freq_prefix_valid = false;   // (iqhip_gen_boot_samples rebuilds its prefix sums)
     return IQHIP_OK;
 }
 
@@ -1438,6 +1442,308 @@ extern "C" int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const d
     static_assert(sizeof(iqhip_branch_support) == 4 * sizeof(double), "iqhip_branch_support is four doubles");
     HIPCHK(hipMemcpyAsync(out, d_res, sizeof(iqhip_branch_support) * (size_t)nbranch, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+// ---- tree topology tests (evaluateTrees / performAUTest, phylotesting.cpp:1916-2442; kernels_topo.hip) ---------------
+extern "C" int iqhip_ptnlh_upload(iqhip_engine *e, int row, const double *in) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_upload");
+    if (rc) return rc;
+    if (!in) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_upload: null argument");
+    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_upload: row outside the store (iqhip_ptnlh_reserve)");
+    HIPCHK(use_device(e));
+    std::vector<double> tmp((size_t)e->nptn_pad, 0.0);
+    memcpy(tmp.data(), in, sizeof(double) * (size_t)e->nptn);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_ptnlh + (size_t)row * e->nptn_pad, tmp.data(), sizeof(double) * tmp.size(), hipMemcpyHostToDevice,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+// the int64 inclusive prefix sums of ptn_freq and nsite = their last entry, from the engine's own copy of the frequencies
+static int topo_freq_prefix(iqhip_engine *e, const char *what) {
+    if (e->freq_prefix_valid) return IQHIP_OK;
+    if (!e->aln_set) return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_alignment first");
+    std::vector<double> freq((size_t)e->nptn);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(freq.data(), e->d_freq, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
+    std::vector<int64_t> prefix(freq.size());
+    int64_t total = 0;
+    for (size_t p = 0; p < freq.size(); p++) {
+        const double f = freq[p];
+        if (!(f >= 0.0) || f != floor(f) || f > 9007199254740992.0 || total > (INT64_MAX >> 2) - (int64_t)f)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": pattern frequencies must be non-negative integers");
+        total += (int64_t)f;
+        prefix[p] = total;
+    }
+    if (total < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": the alignment has no site");
+    if (!e->d_freq_prefix) HIPCHK(dmalloc(&e->d_freq_prefix, prefix.size()));
+    HIPCHK(hipMemcpy(e->d_freq_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice));
+    e->freq_nsite = total;
+    e->freq_prefix_valid = true;
+    return IQHIP_OK;
+}
+
+// a sample matrix of exactly (exact) or at least nsamples rows, contents undefined
+static int topo_boot_rows(iqhip_engine *e, int nsamples, bool exact) {
+    if (e->d_boot && (exact ? e->nboot == nsamples : e->nboot >= nsamples)) return IQHIP_OK;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->d_boot) HIPCHK(hipFree(e->d_boot));
+    e->d_boot = nullptr;
+    e->nboot = 0;
+    if (hipMalloc((void **)&e->d_boot, sizeof(float) * (size_t)e->nptn_pad * nsamples) != hipSuccess)
+        return fail(IQHIP_ERR_NOMEM, "bootstrap sample matrix: out of device memory");
+    e->nboot = nsamples;
+    return IQHIP_OK;
+}
+
+static const int64_t kTopoMaxDraws = (int64_t)1 << 24;   // counts above 2^24 are not representable in float
+
+extern "C" int iqhip_gen_boot_samples(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t seed,
+                                      uint32_t stream) {
+    int rc = ptnlh_plain_engine(e, "iqhip_gen_boot_samples");
+    if (rc) return rc;
+    if (nsamples < 1 || nsamples > 16384) return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: 1 .. 16384 bootstrap samples");
+    if (first_replicate < 0 || first_replicate > INT64_MAX - nsamples - 1)
+        return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: bad first replicate");
+    if (ndraws < 0 || ndraws > kTopoMaxDraws)
+        return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: ndraws must be 0 .. 2^24 (a float holds no larger count exactly)");
+    HIPCHK(use_device(e));
+    rc = topo_freq_prefix(e, "iqhip_gen_boot_samples");
+    if (rc) return rc;
+    rc = topo_boot_rows(e, nsamples, true);
+    if (rc) return rc;
+    HIPCHK(launch_topo_gen(e, nsamples, first_replicate, ndraws, topo_stream_key(seed, stream)));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+static int topo_check_rows(iqhip_engine *e, const char *what, const int32_t *rows, int nrows) {
+    for (int i = 0; i < nrows; i++)
+        if (rows[i] < 0 || rows[i] >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store");
+    return IQHIP_OK;
+}
+
+// variances of all pairs of the row list -> host [nrows][nrows] (uses d_bt_rows for the list)
+static int topo_diff_variance(iqhip_engine *e, const char *what, const int32_t *rows, int nrows, double *var) {
+    int rc = topo_freq_prefix(e, what);
+    if (rc) return rc;
+    const size_t nn = (size_t)nrows * nrows;
+    if ((size_t)nrows > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, (size_t)nrows, (size_t)nrows));
+    if (nn > e->tt_var_cap) HIPCHK(regrow(e, &e->d_tt_var, &e->tt_var_cap, nn, nn));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_bt_rows, rows, sizeof(int32_t) * (size_t)nrows, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_topo_diff_variance(e, e->d_bt_rows, nrows, e->d_tt_var));
+    HIPCHK(hipMemcpyAsync(var, e->d_tt_var, sizeof(double) * nn, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_ptnlh_diff_variance(iqhip_engine *e, const int32_t *rows, int nrows, double *var) {
+    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_diff_variance");
+    if (rc) return rc;
+    if (!rows || !var || nrows < 1 || nrows > 4096) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_diff_variance: bad row list");
+    rc = topo_check_rows(e, "iqhip_ptnlh_diff_variance", rows, nrows);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    return topo_diff_variance(e, "iqhip_ptnlh_diff_variance", rows, nrows, var);
+}
+
+// the 95 % confidence set of phylotesting.cpp:2248-2255 / 2404-2411: trees by decreasing share until the shares pass 0.95;
+// equal shares are taken highest index first (the reference's order among equal shares is its quicksort's)
+static void topo_confidence_set(const std::vector<double> &share, std::vector<int32_t> &in_set) {
+    const int n = (int)share.size();
+    std::vector<int> rank((size_t)n);
+    for (int i = 0; i < n; i++) rank[i] = i;
+    std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return share[a] < share[b]; });
+    in_set.assign((size_t)n, 0);
+    double prob_sum = 0.0;
+    for (int k = n - 1; k >= 0; k--) {
+        in_set[rank[k]] = 1;
+        prob_sum += share[rank[k]];
+        if (prob_sum > 0.95) break;
+    }
+}
+
+extern "C" int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int ntrees, int nsamples, double epsilon,
+                                int weighted, uint64_t tie_seed, iqhip_tree_test *out) {
+    int rc = ptnlh_plain_engine(e, "iqhip_tree_tests");
+    if (rc) return rc;
+    if (!rows || !lh || !out || ntrees < 2 || ntrees > 4096 || !(epsilon >= 0.0) || !std::isfinite(epsilon))
+        return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: bad arguments (at least two trees)");
+    if (nsamples < 1 || nsamples > e->nboot)
+        return fail(IQHIP_ERR_INVALID, e->nboot == 0 ? "iqhip_tree_tests: no bootstrap samples (iqhip_gen_boot_samples / iqhip_set_boot_samples)"
+                                                     : "iqhip_tree_tests: more replicates than samples in the matrix");
+    for (int t = 0; t < ntrees; t++)
+        if (!std::isfinite(lh[t])) return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: log-likelihoods must be finite");
+    rc = topo_check_rows(e, "iqhip_tree_tests", rows, ntrees);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    const size_t T = (size_t)ntrees, S = (size_t)nsamples;
+    // phylotesting.cpp:2284-2299, 2308: the tree every tree is compared with in the KH test
+    int orig_max_id = 0, orig_2ndmax_id = -1;
+    double orig_max_lh = lh[0], orig_2ndmax_lh = -DBL_MAX;
+    for (int t = 1; t < ntrees; t++)
+        if (orig_max_lh < lh[t]) {
+            orig_max_lh = lh[t];
+            orig_max_id = t;
+        }
+    for (int t = 0; t < ntrees; t++)
+        if (t != orig_max_id && orig_2ndmax_lh < lh[t]) {
+            orig_2ndmax_lh = lh[t];
+            orig_2ndmax_id = t;
+        }
+    if (orig_2ndmax_id < 0) return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: log-likelihoods out of range");
+    // host staging: doubles lh, avg, w_orig [T each] ++ weights [T][T]; ints kh_id, w_id [T each]
+    std::vector<double> hd(3 * T + (weighted ? T * T : 0), 0.0);
+    std::vector<int32_t> hi(2 * T, -1);
+    for (int t = 0; t < ntrees; t++) {
+        hd[t] = lh[t];
+        hi[t] = t != orig_max_id ? orig_max_id : orig_2ndmax_id;
+    }
+    if (weighted) {
+        // :2327-2352: weights 1 / sqrt(variance of the difference), and per tree the largest weighted difference
+        std::vector<double> var(T * T);
+        rc = topo_diff_variance(e, "iqhip_tree_tests", rows, ntrees, var.data());
+        if (rc) return rc;
+        double *w = hd.data() + 3 * T;
+        for (size_t a = 0; a < T; a++)
+            for (size_t b = a + 1; b < T; b++) w[a * T + b] = w[b * T + a] = 1.0 / sqrt(var[a * T + b]);
+        for (int t = 0; t < ntrees; t++) {
+            double worig_diff = -DBL_MAX;
+            int max_id = -1;
+            for (int t2 = 0; t2 < ntrees; t2++)
+                if (t2 != t) {
+                    const double wdiff = (lh[t2] - lh[t]) * w[(size_t)t * T + t2];
+                    if (wdiff > worig_diff) {
+                        worig_diff = wdiff;
+                        max_id = t2;
+                    }
+                }
+            hd[2 * T + t] = worig_diff;
+            hi[T + t] = max_id;
+        }
+    }
+    int M = 0;
+    rc = ptnlh_product(e, "iqhip_tree_tests", rows, ntrees, nsamples, &M);
+    if (rc) return rc;
+    const size_t ndbl = hd.size() + 3 * S + 6 * T, nint = 2 * T + S;
+    if (ndbl > e->tt_dbl_cap) HIPCHK(regrow(e, &e->d_tt_dbl, &e->tt_dbl_cap, ndbl, ndbl));
+    if (nint > e->tt_int_cap) HIPCHK(regrow(e, &e->d_tt_int, &e->tt_int_cap, nint, nint));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_tt_dbl, hd.data(), sizeof(double) * hd.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_tt_int, hi.data(), sizeof(int32_t) * hi.size(), hipMemcpyHostToDevice, e->stream));
+    TopoTestArgs a;
+    a.sums = e->d_bt_sums;
+    a.idx = e->d_bt_rows + M;
+    a.T = ntrees;
+    a.S = nsamples;
+    a.epsilon = epsilon;
+    a.tie_key = topo_stream_key(tie_seed, 0xB9u);
+    a.lh = e->d_tt_dbl;
+    a.avg = e->d_tt_dbl + T;
+    a.w_orig = e->d_tt_dbl + 2 * T;
+    a.weights = weighted ? e->d_tt_dbl + 3 * T : nullptr;
+    a.max_sh = e->d_tt_dbl + hd.size();
+    a.max_elw = a.max_sh + S;
+    a.sum_l = a.max_elw + S;
+    a.out = a.sum_l + S;
+    a.kh_id = e->d_tt_int;
+    a.w_id = e->d_tt_int + T;
+    a.winner = e->d_tt_int + 2 * T;
+    HIPCHK(launch_topo_tests(e, a));
+    HIPCHK(launch_topo_tree(e, a));
+    std::vector<double> res(6 * T);
+    HIPCHK(hipMemcpyAsync(res.data(), a.out, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<double> share(T);
+    std::vector<int32_t> rell_set, elw_set;
+    for (size_t t = 0; t < T; t++) share[t] = res[6 * t];
+    topo_confidence_set(share, rell_set);
+    for (size_t t = 0; t < T; t++) share[t] = res[6 * t + 5];
+    topo_confidence_set(share, elw_set);
+    for (size_t t = 0; t < T; t++) {
+        iqhip_tree_test &o = out[t];
+        o.rell_bp = res[6 * t];
+        o.kh_pvalue = res[6 * t + 1];
+        o.sh_pvalue = res[6 * t + 2];
+        o.wkh_pvalue = res[6 * t + 3];
+        o.wsh_pvalue = res[6 * t + 4];
+        o.elw_value = res[6 * t + 5];
+        o.rell_confident = rell_set[t];
+        o.elw_confident = elw_set[t];
+    }
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales,
+                                   int nsamples, uint64_t seed, double *bp) {
+    int rc = ptnlh_plain_engine(e, "iqhip_multiscale_bp");
+    if (rc) return rc;
+    if (!rows || !scales || !bp || ntrees < 2 || ntrees > 4096 || nscales < 1 || nscales > 4096 || nsamples < 1)
+        return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: bad arguments (at least two trees, one scale, one replicate)");
+    rc = topo_check_rows(e, "iqhip_multiscale_bp", rows, ntrees);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    rc = topo_freq_prefix(e, "iqhip_multiscale_bp");
+    if (rc) return rc;
+    std::vector<int64_t> ndraws((size_t)nscales);
+    for (int k = 0; k < nscales; k++) {
+        if (!(scales[k] > 0.0) || !std::isfinite(scales[k])) return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: a scale must be > 0");
+        const double d = round(scales[k] * (double)e->freq_nsite);
+        if (d < 1.0 || d > (double)kTopoMaxDraws)
+            return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: round(scale * nsite) must be 1 .. 2^24 draws");
+        ndraws[k] = (int64_t)d;
+    }
+    // distinct rows in first-appearance order, then every tree's index into them (as ptnlh_product lays d_bt_rows out)
+    std::vector<int32_t> list;
+    std::vector<int32_t> idx((size_t)ntrees);
+    {
+        std::unordered_map<int32_t, int32_t> seen;
+        for (int t = 0; t < ntrees; t++) {
+            auto it = seen.find(rows[t]);
+            if (it == seen.end()) {
+                it = seen.emplace(rows[t], (int32_t)list.size()).first;
+                list.push_back(rows[t]);
+            }
+            idx[t] = it->second;
+        }
+    }
+    const int M = (int)list.size();
+    list.insert(list.end(), idx.begin(), idx.end());
+    // replicates per chunk: the sample matrix stays within 256 MB; IQHIP_BOOT_CHUNK (read per call) overrides.  The K-split
+    // follows from the pattern count and the CU count alone (the budget's chunk, not this call's), so that a (row,
+    // replicate) sum has the same bits whatever the chunk size
+    const int64_t budget = std::max<int64_t>(1, std::min<int64_t>(16384, ((int64_t)256 << 20) / (4 * e->nptn_pad)));
+    const int ksplit = alrt_ksplit(e, M, (int)budget);
+    int64_t chunk = budget;
+    if (const char *bc = getenv("IQHIP_BOOT_CHUNK")) chunk = std::max(1, std::min(16384, atoi(bc)));
+    chunk = std::min<int64_t>(chunk, nsamples);
+    rc = topo_boot_rows(e, (int)chunk, false);
+    if (rc) return rc;
+    const size_t sums = (size_t)M * chunk, part = sums * ksplit, ncount = (size_t)nscales * ntrees;
+    if (list.size() > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, list.size(), list.size()));
+    if (part > e->bt_part_cap) HIPCHK(regrow(e, &e->d_bt_part, &e->bt_part_cap, part, part));
+    if (sums > e->bt_sums_cap) HIPCHK(regrow(e, &e->d_bt_sums, &e->bt_sums_cap, sums, sums));
+    if (ncount > e->tt_int_cap) HIPCHK(regrow(e, &e->d_tt_int, &e->tt_int_cap, ncount, ncount));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_bt_rows, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(e->d_tt_int);
+    HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * ncount, e->stream));
+    for (int k = 0; k < nscales; k++) {
+        const uint64_t key = topo_stream_key(seed, (uint32_t)k);
+        for (int64_t first = 0; first < nsamples; first += chunk) {
+            const int n = (int)std::min<int64_t>(chunk, nsamples - first);
+            HIPCHK(launch_topo_gen(e, n, first, ndraws[k], key));
+            HIPCHK(launch_alrt_product(e, e->d_bt_rows, M, n, ksplit, e->d_bt_part, e->d_bt_sums));
+            HIPCHK(launch_topo_argmax(e, e->d_bt_sums, e->d_bt_rows + M, ntrees, n, d_counts + (size_t)k * ntrees));
+        }
+    }
+    std::vector<uint32_t> counts(ncount);
+    HIPCHK(hipMemcpyAsync(counts.data(), d_counts, sizeof(uint32_t) * ncount, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < ncount; i++) bp[i] = (double)counts[i] / nsamples;
     return IQHIP_OK;
 }
 

@@ -440,6 +440,18 @@ struct iqhip_engine {
     size_t bt_sums_cap = 0;
     double *d_bt_out = nullptr;         // lh3 [3 * nbranch] ++ iqhip_branch_support [nbranch]
     size_t bt_out_cap = 0;
+    // tree topology tests (kernels_topo.hip): int64 inclusive prefix sums of ptn_freq for iqhip_gen_boot_samples (built when
+    // first needed, dropped by iqhip_set_ptn_freq) and the scratch of iqhip_ptnlh_diff_variance / iqhip_tree_tests /
+    // iqhip_multiscale_bp
+    int64_t *d_freq_prefix = nullptr;
+    bool freq_prefix_valid = false;
+    int64_t freq_nsite = 0;
+    double *d_tt_var = nullptr;         // [n][n] variances of the pairwise differences
+    size_t tt_var_cap = 0;
+    double *d_tt_dbl = nullptr;         // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
+    size_t tt_dbl_cap = 0;
+    int32_t *d_tt_int = nullptr;        // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
+    size_t tt_int_cap = 0;
     int32_t *d_batch_rows = nullptr;    // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     size_t batch_rows_cap = 0;
     double *d_result_own = nullptr, *d_result = nullptr;
@@ -958,6 +970,31 @@ hipError_t launch_alrt_product(iqhip_engine *e, const int32_t *d_rows, int nrows
                                double *sums);
 hipError_t launch_alrt_stats(iqhip_engine *e, const int32_t *d_idx3, const double *d_lh3, int nbranch, int nsamples,
                              const double *sums, double *out /* 4 per branch */);
+
+// kernels_topo.hip: tree topology tests on the sums of launch_alrt_product.  launch_topo_gen fills rows [0, nsamples) of
+// e->d_boot from e->d_freq_prefix; launch_topo_tests enqueues avg_lh and the per-replicate pass, launch_topo_tree the counts
+struct TopoTestArgs {
+    const double *sums;       // [M][S]
+    const int32_t *idx;       // [T] tree -> row of sums
+    int T, S;
+    double epsilon;
+    uint64_t tie_key;         // topo_stream_key(tie_seed, 0xB9)
+    const double *lh;         // [T]
+    double *avg;              // [T]
+    double *max_sh, *max_elw, *sum_l;   // [S]
+    int32_t *winner;          // [S]
+    const int32_t *kh_id;     // [T]
+    const double *weights;    // [T][T] or nullptr (unweighted)
+    const int32_t *w_id;      // [T]
+    const double *w_orig;     // [T]
+    double *out;              // [T][6] = bp, kh, sh, wkh, wsh, elw
+};
+uint64_t topo_stream_key(uint64_t seed, uint32_t stream);
+hipError_t launch_topo_gen(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t stream_key);
+hipError_t launch_topo_diff_variance(iqhip_engine *e, const int32_t *d_rows, int n, double *d_var);
+hipError_t launch_topo_tests(iqhip_engine *e, const TopoTestArgs &a);
+hipError_t launch_topo_tree(iqhip_engine *e, const TopoTestArgs &a);
+hipError_t launch_topo_argmax(iqhip_engine *e, const double *sums, const int32_t *d_idx, int T, int S, uint32_t *counts);
 
 // batched branch optimisation (k_newton_batch); d_tasks: device array of NewtonTask (kernels_newton.hip)
 hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,

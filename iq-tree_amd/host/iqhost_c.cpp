@@ -324,6 +324,30 @@ int iqhost_support_tree_string(void *h, const int *ids, const double *vals, int 
         memcpy(out, s.c_str(), s.size() + 1);
     });
 }
+int iqhost_gen_boot_samples(void *h, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t seed, uint32_t stream) {
+    IQHOST_TRY(((PhyloTree *)h)->genBootSamples(nsamples, ndraws, seed, stream, first_replicate));
+}
+// evaluateTrees: vals[9t + {0..8}] = logL, bp-RELL, p-KH, p-SH, p-WKH, p-WSH, c-ELW, in the RELL-BP confidence set, in the
+// ELW one; au_bp[k * ntrees + t] for the nscales scales (nscales == 0: no AU replicates)
+int iqhost_evaluate_trees(void *h, const char **newicks, int ntrees, int fixed_lengths, int nsamples, int weighted,
+                          const double *au_scales, int nscales, uint64_t seed, double epsilon, double *vals, double *au_bp) {
+    IQHOST_TRY({
+        std::vector<std::string> nwk;
+        for (int t = 0; t < ntrees; t++) nwk.push_back(newicks[t]);
+        std::vector<double> scales(au_scales, au_scales + (nscales > 0 ? nscales : 0));
+        std::vector<PhyloTree::TreeTest> res;
+        std::vector<double> bp;
+        ((PhyloTree *)h)->evaluateTrees(nwk, fixed_lengths != 0, nsamples, weighted != 0, scales, seed, res, bp, epsilon);
+        for (size_t t = 0; t < res.size(); t++) {
+            const iqhip_tree_test &r = res[t].t;
+            double *v = vals + 9 * t;
+            v[0] = res[t].logl; v[1] = r.rell_bp; v[2] = r.kh_pvalue; v[3] = r.sh_pvalue;
+            v[4] = r.wkh_pvalue; v[5] = r.wsh_pvalue; v[6] = r.elw_value;
+            v[7] = (double)r.rell_confident; v[8] = (double)r.elw_confident;
+        }
+        if (!bp.empty()) memcpy(au_bp, bp.data(), sizeof(double) * bp.size());
+    });
+}
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {
     PhyloTree *t = (PhyloTree *)h;

@@ -1279,6 +1279,55 @@ double PhyloTree::testAllBranches(int reps, int lbp_reps, std::vector<BranchSupp
     return lh0;
 }
 
+// =========================================================================================
+// tree topology tests, phylotesting.cpp:2053-2442
+// =========================================================================================
+void PhyloTree::evaluateTrees(const std::vector<std::string> &newicks, bool fixed_lengths, int nsamples, bool weighted,
+                              const std::vector<double> &au_scales, uint64_t seed, std::vector<TreeTest> &out,
+                              std::vector<double> &au_bp, double epsilon) {
+    if (!engine || dry_run) throw std::runtime_error("evaluateTrees needs an attached engine");
+    if (allreduce_hook) throw std::runtime_error("evaluateTrees: not available with a caller-owned collective");
+    if (newicks.size() < 2) throw std::runtime_error("evaluateTrees: at least two trees");
+    if (nsamples < 1) throw std::runtime_error("evaluateTrees: no replicates");
+    const int ntrees = (int)newicks.size();
+    std::vector<std::string> names((size_t)leafNum);
+    for (int i = 0; i < leafNum; i++) names[i] = nodes[i]->name.empty() ? std::to_string(i) : nodes[i]->name;
+    const int leaves = leafNum;
+    check(iqhip_ptnlh_reserve(engine, ntrees), "iqhip_ptnlh_reserve");
+    out.assign((size_t)ntrees, TreeTest());
+    std::vector<int32_t> rows((size_t)ntrees);
+    std::vector<double> lh((size_t)ntrees);
+    for (int tid = 0; tid < ntrees; tid++) {
+        readTreeString(newicks[tid], names);
+        if (leafNum != leaves) throw std::runtime_error("evaluateTrees: a tree with another number of taxa");
+        initializeAllPartialLh();
+        clearAllPartialLH();
+        double lnl = computeLikelihood();
+        if (!fixed_lengths) {
+            optimizeAllBranches();
+            clearAllPartialLH();
+            lnl = computeLikelihood();
+        }
+        check(iqhip_ptnlh_put_current(engine, tid, branchEnd(current_it), branchEnd(current_it_back)), "iqhip_ptnlh_put_current");
+        rows[tid] = tid;
+        lh[tid] = out[tid].logl = lnl;
+    }
+    double nsite = 0.0;
+    for (double f : ptn_freq) nsite += f;
+    genBootSamples(nsamples, (int64_t)nsite, seed, 0xA0u);
+    std::vector<iqhip_tree_test> res((size_t)ntrees);
+    check(iqhip_tree_tests(engine, rows.data(), lh.data(), ntrees, nsamples, epsilon, weighted ? 1 : 0, seed, res.data()),
+          "iqhip_tree_tests");
+    for (int tid = 0; tid < ntrees; tid++) out[tid].t = res[tid];
+    au_bp.clear();
+    if (!au_scales.empty()) {
+        au_bp.assign(au_scales.size() * (size_t)ntrees, 0.0);
+        check(iqhip_multiscale_bp(engine, rows.data(), ntrees, au_scales.data(), (int)au_scales.size(), nsamples, seed,
+                                  au_bp.data()),
+              "iqhip_multiscale_bp");
+    }
+}
+
 std::string PhyloTree::supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp) {
     std::ostringstream ss;  // phylotree.cpp:4078-4091 (node names are empty here)
     ss.precision(3);
@@ -1368,6 +1417,13 @@ void PhyloTree::setBootSamples(const float *samples, int nsamples) {
     if (!engine) throw std::runtime_error("no engine");
     pushInputs();
     check(iqhip_set_boot_samples(engine, samples, nsamples), "iqhip_set_boot_samples");
+    num_boot_samples = nsamples;
+}
+
+void PhyloTree::genBootSamples(int nsamples, int64_t ndraws, uint64_t seed, uint32_t stream, int64_t first_replicate) {
+    if (!engine) throw std::runtime_error("no engine");
+    pushInputs();
+    check(iqhip_gen_boot_samples(engine, nsamples, first_replicate, ndraws, seed, stream), "iqhip_gen_boot_samples");
     num_boot_samples = nsamples;
 }
 

@@ -209,6 +209,20 @@ public:
     std::string supportTreeString(const std::vector<BranchSupport> &sup, bool with_sh, bool with_lbp) const;
     static std::string supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp);
 
+    // ---- tree topology tests (evaluateTrees, phylotesting.cpp:2053-2442; -z trees -zb N [-zw] [-au]) on the device.
+    //      Per tree: read the topology (the Newick reader above; same taxa as the current tree), computeLikelihood,
+    //      optimizeAllBranches unless fixed_lengths, iqhip_ptnlh_put_current into store row tid, keep the total lnL.  Then
+    //      iqhip_gen_boot_samples (nsite draws per replicate, stream 0xA0 of `seed`), iqhip_tree_tests (tie draws of `seed`)
+    //      and, with au_scales, iqhip_multiscale_bp with nsamples replicates per scale: au_bp[k * ntrees + tid].
+    //      Harness code like testAllBranches; the tree is left at the last topology.
+    struct TreeTest {
+        double logl = 0.0;
+        iqhip_tree_test t = {};
+    };
+    void evaluateTrees(const std::vector<std::string> &newicks, bool fixed_lengths, int nsamples, bool weighted,
+                       const std::vector<double> &au_scales, uint64_t seed, std::vector<TreeTest> &out,
+                       std::vector<double> &au_bp, double epsilon = 0.5);
+
     // ---- consumers of the per-pattern lnL (phylotree.cpp:1200-1230, iqtree.cpp:2676-2750) ----------
     // computePatternLikelihood: lnL per pattern of the last computeLikelihood(), scaling events of
     // both ends of current_it put back -- computed on the device, one D2H of nptn doubles
@@ -217,6 +231,8 @@ public:
     void computePatternLhCat(double *ptn_lh_cat);
     // UFBoot: boot_samples uploaded once; computeRELL = saveCurrentTree's dot products, on the device
     void setBootSamples(const float *samples /*[nsamples][nptn]*/, int nsamples);
+    // the same matrix drawn on the device (iqhip_gen_boot_samples): nsamples replicates of ndraws sites each
+    void genBootSamples(int nsamples, int64_t ndraws, uint64_t seed, uint32_t stream, int64_t first_replicate = 0);
     void computeRELL(std::vector<double> &rell);
     int num_boot_samples = 0;
 
