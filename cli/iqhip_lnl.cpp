@@ -12,11 +12,17 @@
 // bp-RELL, p-KH, p-SH, [p-WKH, p-WSH,] c-ELW and +/- marks (confidence set; p >= 0.05), and with -au the bootstrap
 // proportions of the AU test's ten scales r = 0.5 .. 1.4 (the AU p-value itself is not computed).  The resamples are drawn
 // on the device by the engine's own generator (include/iqhip.h), not the reference's RNG stream.
+// With -mldist <file> it computes the maximum-likelihood distance of every pair of sequences under the model on the device
+// (PhyloTree::computeDist; it needs the model only, not the tree's lengths) and writes the matrix in the format of
+// Alignment::printDist: the number of taxa, then per taxon its name left-aligned in max(10, longest name) columns, a blank
+// and the distances in fixed notation with 7 decimals, each followed by a blank.
 // There is no CPU path: without a GPU it fails with the engine's error.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <fstream>
 #include <random>
@@ -34,7 +40,7 @@ static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
-            "                 [-z <tree set file> -zb <n> [-zw] [-au]]\n"
+            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>]\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
 }
@@ -44,7 +50,7 @@ int main(int argc, char **argv) {
     bool blfix = false, wsl = false, all_branch = false;
     int dev = 0, reps = 0, alrt = 0, lbp = 0;
     unsigned long long seed = 1;
-    std::string treeset_file;
+    std::string treeset_file, mldist_file;
     int zb = 0;
     bool zw = false, au = false;
     for (int i = 1; i < argc; i++) {
@@ -69,6 +75,7 @@ int main(int argc, char **argv) {
         else if (a == "-zb") zb = atoi(next().c_str());
         else if (a == "-zw") zw = true;
         else if (a == "-au") au = true;
+        else if (a == "-mldist") mldist_file = next();
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
@@ -109,6 +116,27 @@ int main(int argc, char **argv) {
         tree.lh_mem_save = all_branch ? LM_ALL_BRANCH : LM_PER_NODE;
         tree.setLikelihoodKernel(LK_EIGEN_HIP);
         tree.attachEngine(dev);
+        if (!mldist_file.empty()) {
+            const int nseq = aln.getNSeq();
+            std::vector<double> dist((size_t)nseq * nseq), d2l((size_t)nseq * nseq);
+            auto t0 = std::chrono::steady_clock::now();
+            tree.computeDist(nullptr, dist.data(), d2l.data());
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            size_t max_len = 10;
+            for (int i = 0; i < nseq; i++) max_len = std::max(max_len, aln.seq_names[i].size());
+            std::ofstream out(mldist_file.c_str());
+            if (!out) throw std::runtime_error("cannot write " + mldist_file);
+            out << nseq << std::endl;
+            out.precision(std::max((int)ceil(-log10(tree.min_branch_length)) + 1, 6));   // alignment.cpp:2592
+            out << std::fixed;
+            for (int i = 0; i < nseq; i++) {
+                out.width((std::streamsize)max_len);
+                out << std::left << aln.seq_names[i] << " ";
+                for (int j = 0; j < nseq; j++) out << dist[(size_t)i * nseq + j] << " ";
+                out << std::endl;
+            }
+            printf("ML distances of %d pairs: %.4f s, printed to %s\n", nseq * (nseq - 1) / 2, sec, mldist_file.c_str());
+        }
         tree.initializeAllPartialLh();
         tree.clearAllPartialLH();
         std::vector<double> pattern_lh(aln.getNPattern());

@@ -432,6 +432,46 @@ int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int
 int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales, int nsamples,
                         uint64_t seed, double *bp /* nscales*ntrees, bp[k*ntrees+tid] */);
 
+/* ---- Pairwise maximum-likelihood distances (PhyloTree::computeDist, phylotree.cpp:2432-2541; per pair AlignmentPairwise,
+ * alignmentpairwise.cpp:29-312, and Optimization::minimizeNewton) -- the likelihood computation the reference runs before
+ * a tree exists; the matrix feeds BIONJ and is written as .mldist.  Everything it needs is resident in any engine: the state
+ * rows and ptn_freq of iqhip_set_alignment, the eigen-system, rates and proportions of iqhip_set_model.
+ * iqhip_pair_counts: AlignmentPairwise's constructor: counts[k*n*n + a*n + b] = sum of ptn_freq over the patterns where taxon
+ *   pairs[2k] shows state a and taxon pairs[2k+1] shows state b, a, b < nstates (n = nstates).  Patterns where either state
+ *   is >= nstates (ambiguity codes, gaps, STATE_UNKNOWN) are skipped -- addPattern returns before its ambiguity branch
+ *   (alignmentpairwise.cpp:68-79).  Integer-valued frequencies give exact counts, the same bits on every run.
+ * iqhip_pair_distances: PhyloTree::computeDist(dist_mat, var_mat) for all pairs in one submission.  init: ntaxa*ntaxa initial
+ *   distances or NULL; an entry of 0 (or NULL) means "start from the JC distance of the pair" (Alignment::computeJCDist,
+ *   alignment.cpp:2552-2584, MAX_GENETIC_DIST = 9 when there is no overlap or the correction diverges), as
+ *   phylotree.cpp:2434-2439.  dist: ntaxa*ntaxa, symmetric, diagonal 0.  d2l: NULL or ntaxa*ntaxa, minimizeNewton's d2l per
+ *   pair (symmetric, diagonal 0), from which the caller forms var_mat for its ls_var_type (phylotree.cpp:2505-2514).
+ *   nsteps: NULL or ntaxa*ntaxa derivative evaluations per pair.  The reference calls minimizeNewton with x1 = xacc =
+ *   min_branch_length, x2 = MAX_GENETIC_DIST and max_steps = 100; a pair with no overlapping characters then returns 9 after
+ *   one evaluation (f = df = 0).  The update rule, bracketing, stopping tests and d2l are those of iqhip_newton_branch; a
+ *   pair that ends in one of minimizeNewton's two errors makes the call return IQHIP_ERR_INVALID with the matrices filled.
+ *   The function of a pair is computeFuncDerv's default branch (alignmentpairwise.cpp:253-279) over computeTransDerv
+ *   (modelgtr.cpp:301-338): per category c, e_k = exp(t rates[c] eval[k]), P_ij = sum_k evec[i,k] inv_evec[k,j] e_k, P' and
+ *   P'' with one and two more factors eval[k]; a negative P_ij becomes 0 (the derivatives are left as they are);
+ *   S = sum_c props[c] P, S' = sum_c props[c] rates[c] P', S'' = sum_c props[c] rates[c]^2 P''; over the cells with
+ *   count > 0 and S_ij > 0: df = -sum count S'/S, ddf = -sum count (S''/S - (S'/S)^2).  The invariant-site term is not part
+ *   of the function, as in the reference.
+ * DEVIATION from the reference: it adds the categories unweighted.  S'/S and S''/S do not change under a common factor, so
+ *   with equal proportions (with or without +I) this is the reference's function; with unequal proportions (+R) it is the
+ *   weighted form the model means.
+ * Supported: plain engines of 4, 20 and 64 states with any category count the engine accepts (the 9..32-category DNA engines
+ *   included) and +ASC engines (the unobserved patterns carry frequency 0).  IQHIP_ERR_UNSUPPORTED: mixture models, sharded
+ *   engines and communicator ranks, embedded state counts.  IQHIP_ERR_INVALID: planning-only engines, a call before the
+ *   alignment or the model is set, pair indices outside [0, ntaxa), x1 > x2, max_steps < 1.
+ *   Without a GPU there is no engine to call them on: iqhip_create returns IQHIP_ERR_NO_DEVICE, as for every compute call.
+ * The pairs are processed in chunks whose counts fit 64 MB (IQHIP_PAIR_CHUNK, read per call, overrides the pairs per
+ *   chunk); a chunk is counted and solved before the next one overwrites its counts, and no result depends on the chunking.
+ * iqhip_debug_pair_timing: with iqhip_timing_enable, the device time (HIP events, milliseconds) the last
+ *   iqhip_pair_distances call spent in its count launches and in its solve launches. */
+int iqhip_pair_counts(iqhip_engine *e, const int32_t *pairs /* 2*npairs */, int npairs, double *counts);
+int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double x2, double xacc, int max_steps,
+                         double *dist, double *d2l, int32_t *nsteps);
+int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms);
+
 /* Host -> device (tests; SPR/NNI code that fills a buffer on the host). */
 int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
                          const int16_t *scale_num);

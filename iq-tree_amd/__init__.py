@@ -39,6 +39,7 @@ IQHIP_SYMBOLS = [
     "iqhip_ptnlh_reserve", "iqhip_ptnlh_put_current", "iqhip_ptnlh_fetch", "iqhip_optimize_branch_batch_rows",
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
     "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
+    "iqhip_pair_counts", "iqhip_pair_distances", "iqhip_debug_pair_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -205,6 +206,9 @@ def libiqhip():
     lib.iqhip_ptnlh_diff_variance.argtypes = [vp, i32p, C.c_int, dp]
     lib.iqhip_tree_tests.argtypes = [vp, i32p, dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.POINTER(TreeTest)]
     lib.iqhip_multiscale_bp.argtypes = [vp, i32p, C.c_int, dp, C.c_int, C.c_int, C.c_uint64, dp]
+    lib.iqhip_pair_counts.argtypes = [vp, i32p, C.c_int, dp]
+    lib.iqhip_pair_distances.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, i32p]
+    lib.iqhip_debug_pair_timing.argtypes = [vp, dp, dp]
     lib._iq_typed = True
     return lib
 
@@ -262,6 +266,8 @@ def libiqhost():
     lib.iqhost_nni_for_branch.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     lib.iqhost_evaluate_nnis_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_compute_all_partial_lh.argtypes = [vp]
+    lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
+    lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
@@ -756,6 +762,26 @@ class PhyloTree:
         for k, f in enumerate(TREE_TEST_DTYPE.names):
             out[f] = v[:, k]
         return out, (bp[:sc.size, :n].copy() if sc.size else None)
+
+    # ---- pairwise ML distances (include/iqhip.h "pairwise maximum-likelihood distances")
+    def pair_counts(self, pairs):
+        """iqhip_pair_counts: pairs [npairs, 2] taxon ids -> counts[npairs, nstates, nstates], the pair-state frequencies
+        of AlignmentPairwise (patterns with an ambiguous or unknown state in either taxon are skipped)"""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros((pr.shape[0], self.nstates, self.nstates))
+        self._chk(self.lib.iqhost_pair_counts(self.h, pr.ctypes.data_as(C.POINTER(C.c_int32)), pr.shape[0], _dptr(out)))
+        return out
+
+    def compute_dist(self, init=None, want_d2l=False):
+        """PhyloTree::computeDist(dist_mat, var_mat): the ML distance of every pair of sequences under the current model,
+        dist[ntaxa, ntaxa] (symmetric, zero diagonal); with want_d2l also minimizeNewton's d2l per pair.  init: None or
+        [ntaxa, ntaxa] initial distances, 0 = start from the pair's JC distance."""
+        n = self.num_leaves
+        dist, d2l = np.zeros((n, n)), np.zeros((n, n))
+        ini = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+        assert ini is None or ini.shape == (n, n)
+        self._chk(self.lib.iqhost_compute_dist(self.h, None if ini is None else _dptr(ini), _dptr(dist), _dptr(d2l)))
+        return (dist, d2l) if want_d2l else dist
 
     def compute_all_partial_lh(self):
         self._chk(self.lib.iqhost_compute_all_partial_lh(self.h))

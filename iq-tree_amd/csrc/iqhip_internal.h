@@ -162,6 +162,13 @@ struct __attribute__((aligned(16))) SweepStep {
     int32_t op_begin, nops;
 };
 
+// pairwise distances (kernels_dist.hip): a tile of 4 x 4 taxa of the pair list -- the pair (ra[x], rb[y]) is counted into
+// slot out[4 x + y] of the chunk's counts (< 0: not asked for); unused rows name any valid taxon
+struct __attribute__((aligned(16))) PairTile {
+    int32_t ra[4], rb[4];
+    int32_t out[16];
+};
+
 struct Slab {
     double *plh = nullptr;
     int16_t *sc = nullptr;
@@ -452,6 +459,20 @@ struct iqhip_engine {
     size_t tt_dbl_cap = 0;
     int32_t *d_tt_int = nullptr;        // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
     size_t tt_int_cap = 0;
+    // pairwise ML distances (kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
+    // coefficients evec[i][k] * inv_evec[k][j] of the call's model [n][n][n], per pair the initial distance and the result
+    // {optx, d2l, evaluations, status}; with iqhip_timing_enable the device time of the last iqhip_pair_distances call
+    iqhip::PairTile *d_pd_tiles = nullptr;
+    size_t pd_tiles_cap = 0;
+    double *d_pd_counts = nullptr;
+    size_t pd_counts_cap = 0;
+    double *d_pd_coef = nullptr;
+    size_t pd_coef_cap = 0;
+    double *d_pd_init = nullptr;
+    size_t pd_init_cap = 0;
+    double *d_pd_out = nullptr;
+    size_t pd_out_cap = 0;
+    double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
     int32_t *d_batch_rows = nullptr;    // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     size_t batch_rows_cap = 0;
     double *d_result_own = nullptr, *d_result = nullptr;
@@ -995,6 +1016,23 @@ hipError_t launch_topo_diff_variance(iqhip_engine *e, const int32_t *d_rows, int
 hipError_t launch_topo_tests(iqhip_engine *e, const TopoTestArgs &a);
 hipError_t launch_topo_tree(iqhip_engine *e, const TopoTestArgs &a);
 hipError_t launch_topo_argmax(iqhip_engine *e, const double *sums, const int32_t *d_idx, int T, int S, uint32_t *counts);
+
+// kernels_dist.hip: pairwise ML distances.  launch_pair_counts: the tiles' pairs -> d_counts[slot][n * n]; launch_pair_solve:
+// slot s of the chunk is pair first_pair + s of the call: start init[pair] (0 or no array: the pair's JC distance), result
+// out[4 pair .. 4 pair + 3] = {optx, d2l, derivative evaluations, status of NewtonState}
+struct PairSolveArgs {
+    const double *counts;   // [chunk][n * n]
+    const double *coef;     // [n][n][n] = evec[i][k] * inv_evec[k][j]
+    const double *eval, *rates, *props;
+    const double *init;     // [npairs] or nullptr
+    double *out;            // [npairs][4]
+    int64_t first_pair;
+    int n, ncat, max_steps;
+    double x1, x2, xacc;
+};
+hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts);
+hipError_t launch_pair_coef(iqhip_engine *e, double *d_coef);
+hipError_t launch_pair_solve(iqhip_engine *e, const PairSolveArgs &a, int npairs);
 
 // batched branch optimisation (k_newton_batch); d_tasks: device array of NewtonTask (kernels_newton.hip)
 hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,

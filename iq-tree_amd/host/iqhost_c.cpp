@@ -348,6 +348,12 @@ int iqhost_evaluate_trees(void *h, const char **newicks, int ntrees, int fixed_l
         if (!bp.empty()) memcpy(au_bp, bp.data(), sizeof(double) * bp.size());
     });
 }
+int iqhost_compute_dist(void *h, const double *init, double *dist, double *d2l) {
+    IQHOST_TRY(((PhyloTree *)h)->computeDist(init, dist, d2l));
+}
+int iqhost_pair_counts(void *h, const int32_t *pairs, int npairs, double *counts) {
+    IQHOST_TRY(((PhyloTree *)h)->pairCounts(pairs, npairs, counts));
+}
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {
     PhyloTree *t = (PhyloTree *)h;

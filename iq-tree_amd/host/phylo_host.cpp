@@ -1328,6 +1328,23 @@ void PhyloTree::evaluateTrees(const std::vector<std::string> &newicks, bool fixe
     }
 }
 
+// =========================================================================================
+// pairwise ML distances, phylotree.cpp:2432-2541
+// =========================================================================================
+void PhyloTree::computeDist(const double *init, double *dist, double *d2l) {
+    if (!engine || dry_run) throw std::runtime_error("computeDist needs an attached engine");
+    if (allreduce_hook) throw std::runtime_error("computeDist: not available with a caller-owned collective");
+    pushInputs();
+    check(iqhip_pair_distances(engine, init, min_branch_length, MAX_GENETIC_DIST, min_branch_length, 100, dist, d2l, nullptr),
+          "iqhip_pair_distances");
+}
+
+void PhyloTree::pairCounts(const int32_t *pairs, int npairs, double *counts) {
+    if (!engine || dry_run) throw std::runtime_error("pairCounts needs an attached engine");
+    pushInputs();
+    check(iqhip_pair_counts(engine, pairs, npairs, counts), "iqhip_pair_counts");
+}
+
 std::string PhyloTree::supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp) {
     std::ostringstream ss;  // phylotree.cpp:4078-4091 (node names are empty here)
     ss.precision(3);

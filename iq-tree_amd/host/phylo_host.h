@@ -223,6 +223,15 @@ public:
                        const std::vector<double> &au_scales, uint64_t seed, std::vector<TreeTest> &out,
                        std::vector<double> &au_bp, double epsilon = 0.5);
 
+    // ---- pairwise ML distances (PhyloTree::computeDist(dist_mat, var_mat), phylotree.cpp:2476-2541) on the device: one
+    //      iqhip_pair_distances with x1 = xacc = min_branch_length, x2 = MAX_GENETIC_DIST and 100 Newton steps, as
+    //      AlignmentPairwise::optimizeDist calls minimizeNewton.  dist, d2l: leafNum * leafNum (symmetric, zero diagonal);
+    //      init: nullptr or leafNum * leafNum initial distances (0: the pair's JC distance).  The caller forms var_mat
+    //      from d2l for its ls_var_type.  Needs no tree beyond the taxa.  pairCounts: AlignmentPairwise's pair_freq.
+    static constexpr double MAX_GENETIC_DIST = 9.0;
+    void computeDist(const double *init, double *dist, double *d2l);
+    void pairCounts(const int32_t *pairs, int npairs, double *counts);
+
     // ---- consumers of the per-pattern lnL (phylotree.cpp:1200-1230, iqtree.cpp:2676-2750) ----------
     // computePatternLikelihood: lnL per pattern of the last computeLikelihood(), scaling events of
     // both ends of current_it put back -- computed on the device, one D2H of nptn doubles
