@@ -16,6 +16,11 @@
 // (PhyloTree::computeDist; it needs the model only, not the tree's lengths) and writes the matrix in the format of
 // Alignment::printDist: the number of taxa, then per taxon its name left-aligned in max(10, longest name) columns, a blank
 // and the distances in fixed notation with 7 decimals, each followed by a blank.
+// With -parstree and no -te it builds the starting tree itself: stepwise addition by maximum parsimony on the device
+// (PhyloTree::computeParsimonyTree; the addition order is a shuffle of the taxa drawn from -seed with std::mt19937_64, not
+// the reference's RNG stream), branch lengths from fixNegativeBranch(true); it prints "Parsimony score: N (based on M
+// informative sites)", writes <prefix>.parstree and goes on as if that file had been given with -te.  With -te, -pars
+// prints the same line for the given tree.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -40,7 +45,8 @@ static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
-            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>]\n"
+            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars]\n"
+            "       iqhip_lnl -s <alignment> -parstree -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
 }
@@ -52,7 +58,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
     int zb = 0;
-    bool zw = false, au = false;
+    bool zw = false, au = false, parstree = false, pars = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -76,11 +82,13 @@ int main(int argc, char **argv) {
         else if (a == "-zw") zw = true;
         else if (a == "-au") au = true;
         else if (a == "-mldist") mldist_file = next();
+        else if (a == "-parstree") parstree = true;
+        else if (a == "-pars") pars = true;
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
     }
-    if (aln_file.empty() || tree_file.empty() || model_str.empty()) { usage(); return 2; }
+    if (aln_file.empty() || model_str.empty() || (tree_file.empty() != parstree)) { usage(); return 2; }
     if (prefix.empty()) prefix = aln_file;
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
@@ -97,10 +105,16 @@ int main(int argc, char **argv) {
             const int k = aln.appendUnobservedConstPatterns();
             printf("Ascertainment bias correction: %d unobservable constant patterns\n", k);
         }
-        std::ifstream tin(tree_file.c_str());
-        if (!tin) throw std::runtime_error("cannot open tree file " + tree_file);
         std::stringstream tss;
-        tss << tin.rdbuf();
+        if (parstree) {   // a star of all taxa: only the taxa matter until computeParsimonyTree builds the topology
+            tss << "(";
+            for (int i = 0; i < aln.getNSeq(); i++) tss << (i ? "," : "") << aln.seq_names[i] << ":0.1";
+            tss << ");";
+        } else {
+            std::ifstream tin(tree_file.c_str());
+            if (!tin) throw std::runtime_error("cannot open tree file " + tree_file);
+            tss << tin.rdbuf();
+        }
 
         PhyloTree tree;
         tree.readTreeString(tss.str(), aln.seq_names);
@@ -116,6 +130,25 @@ int main(int argc, char **argv) {
         tree.lh_mem_save = all_branch ? LM_ALL_BRANCH : LM_PER_NODE;
         tree.setLikelihoodKernel(LK_EIGEN_HIP);
         tree.attachEngine(dev);
+        if (parstree) {
+            std::vector<int> order((size_t)aln.getNSeq());
+            for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
+            std::mt19937_64 gen(seed);
+            for (size_t i = order.size(); i > 1; i--) std::swap(order[i - 1], order[(size_t)(gen() % i)]);
+            auto t0 = std::chrono::steady_clock::now();
+            const int score = tree.computeParsimonyTree(order.data());
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("Parsimony score: %d (based on %lld informative sites)\n", score, (long long)tree.pars_nsites);
+            const std::string nwk = tree.getTreeString();
+            std::ofstream out((prefix + ".parstree").c_str());
+            if (!out) throw std::runtime_error("cannot write " + prefix + ".parstree");
+            out << nwk << std::endl;
+            printf("Parsimony tree: %.4f s, printed to %s.parstree\n", sec, prefix.c_str());
+            tree.readTreeString(nwk, aln.seq_names);   // from here on exactly what -te <prefix>.parstree does
+        } else if (pars) {
+            const int score = tree.computeParsimony();
+            printf("Parsimony score: %d (based on %lld informative sites)\n", score, (long long)tree.pars_nsites);
+        }
         if (!mldist_file.empty()) {
             const int nseq = aln.getNSeq();
             std::vector<double> dist((size_t)nseq * nseq), d2l((size_t)nseq * nseq);

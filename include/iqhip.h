@@ -472,6 +472,64 @@ int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double 
                          double *dist, double *d2l, int32_t *nsteps);
 int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms);
 
+/* ---- Fitch parsimony (PhyloTree::setParsimonyKernel, phylotreesse.cpp:34-61: computePartialParsimonyPointer and
+ * computeParsimonyBranchPointer, the bit-parallel kernels of phylotreepars.cpp:18-282) -- what the reference runs before a
+ * tree exists to build its stepwise-addition starting trees (computeParsimonyTree, phylotreepars.cpp:309-426) and, through
+ * fixNegativeBranch(true) (phylotree.cpp:2654-2694), the first branch lengths.  Everything is integer arithmetic; every
+ * result is exact.  The state lives in a plain engine and is built from the state rows and ptn_freq of
+ * iqhip_set_alignment and the tip table and eigenvectors of iqhip_set_model.
+ * iqhip_pars_init: lays out the sites and writes the tip vectors (phylotreepars.cpp:39-146).  Pattern p contributes
+ *   ptn_freq[p] consecutive sites when informative[p] != 0 (NULL: every pattern), in pattern order; frequencies must be
+ *   non-negative integers (IQHIP_ERR_INVALID otherwise), frequency 0 -- the unobserved +ASC patterns -- contributes
+ *   nothing.  The reference first sorts the informative patterns by their number of characters (orderPatternByNumChars);
+ *   all scores are sums over sites, so the order changes no result and is not reproduced.  *nsites = the site count;
+ *   nwords = ceil(nsites / 32), at least 1.  Bit-plane i of a taxon's site is set exactly when its state code allows state i:
+ *   the indicator of a code is recovered from the engine's tip table row, which is in eigen-space (U^-1 times the
+ *   indicator), as round(U * row) -- the DNA codes 4..17 give the mask `state - 3`, B/Z/J the ambi_aa pairs,
+ *   STATE_UNKNOWN every plane, without a sequence-type switch.  The padding bits of the last word get plane 0 at every
+ *   tip (the reference's dummy states, :74-75) and can never score.
+ *   Slots 0 .. ntaxa-1 are the tip vectors, slots ntaxa .. ntaxa+nvectors-1 the caller's (the reference's arena holds
+ *   4 * (ntaxa - 1) blocks, phylotree.cpp:601).  A vector is nwords * nstates words plus its subtree score, kept as one
+ *   uint32 per word column (x_score[w] + y_score[w] + popcount(w)), so that an update needs no reduction.
+ * iqhip_pars_update: the node update of phylotreepars.cpp:169-211 for a whole op list, in one launch at any tree depth
+ *   (the ops are levelled on the host; a column of a vector depends on the same column of its children only).  Checked
+ *   on the host before anything is launched: every slot in range, dst not a tip slot and not one of its own children, no
+ *   slot written twice in a call, every slot read a tip or written by an earlier op of the call or by an earlier call
+ *   (one valid flag per slot), no slot read by an op and written by a later one.  IQHIP_ERR_INVALID otherwise.
+ * iqhip_pars_branch_scores: computeParsimonyBranchFast (:218-282) for nbranch branches, ends[2b], ends[2b+1] = the slots
+ *   of the two directed vectors of branch b: score = sum_w (a_score[w] + c_score[w] + popcount(~OR_i(a_i & c_i))),
+ *   subst = the popcount part.  The reference's early exit at a lower bound (:251) truncates only scores that lose anyway;
+ *   full scores are returned here.
+ * iqhip_pars_insert_scores: the scan of one stepwise-addition step (addTaxonMPFast, :428-465): for branch (a, c) and tip
+ *   slot `taxon`, m = fitch(a, c) in registers, score = sum_w (a_score + c_score + popcount(w_ac) + popcount(~OR_i(m_i & t_i)))
+ *   -- the score of the tree with the taxon inserted into that branch.  *best = the FIRST minimum in list order (the
+ *   reference accepts a candidate on score < best_pars_score only, :371), *best_score its score; score: NULL or nbranch.
+ * iqhip_pars_shape: what the last iqhip_pars_init laid out: the site count, nwords and nvectors (any of them may be NULL).
+ * iqhip_pars_fetch: a vector in the reference's layout, out[w * nstates + i], and out[nwords * nstates] = its subtree score.
+ * iqhip_debug_pars_levels: iqhip_pars_update's validation and level assignment alone (no engine, no device): valid[k] != 0
+ *   means slot ntaxa + k was written by an earlier call (NULL: none); level[k] = 0 for an op whose children are tips or
+ *   earlier calls' vectors, else 1 + the larger level of the ops that write its children.
+ * iqhip_set_alignment and iqhip_set_ptn_freq after iqhip_pars_init invalidate the parsimony state: the later calls return
+ *   IQHIP_ERR_INVALID until the next iqhip_pars_init, which also resets the valid flags.
+ * IQHIP_ERR_UNSUPPORTED: sharded engines and communicator ranks, embedded state counts (anything but 4, 20, 64).
+ * IQHIP_ERR_INVALID: planning-only engines, init before the alignment or the model is set, every other call before init,
+ *   nvectors < 0, nbranch < 1, `taxon` not a tip slot.  Mixture engines are accepted (class 0's tip table is read).
+ * iqhip_debug_pars_timing: since the last reset, ms[0] / ms[1] = the device time (HIP events, milliseconds; counted while
+ *   iqhip_timing_enable is on) of the iqhip_pars_update launches / of the iqhip_pars_insert_scores launches, and counts =
+ *   {update launches, scan launches (scores + first minimum), ops updated, branches scanned}. */
+typedef struct iqhip_pars_op { int32_t dst, left, right, _pad; } iqhip_pars_op; /* slots */
+int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative /* nptn or NULL */, int nvectors, int64_t *nsites);
+int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int nops);
+int iqhip_pars_branch_scores(iqhip_engine *e, const int32_t *ends /* 2*nbranch slots */, int nbranch, int32_t *score,
+                             int32_t *subst /* either may be NULL */);
+int iqhip_pars_insert_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int32_t taxon,
+                             int32_t *score /* nbranch or NULL */, int32_t *best, int32_t *best_score);
+int iqhip_pars_shape(iqhip_engine *e, int64_t *nsites, int64_t *nwords, int *nvectors);
+int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out /* nwords*nstates + 1 */);
+int iqhip_debug_pars_levels(int ntaxa, int nvectors, const uint8_t *valid /* nvectors or NULL */, const iqhip_pars_op *ops,
+                            int nops, int32_t *level);
+int iqhip_debug_pars_timing(iqhip_engine *e, double *ms /* 2 */, int64_t *counts /* 4 */, int reset);
+
 /* Host -> device (tests; SPR/NNI code that fills a buffer on the host). */
 int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
                          const int16_t *scale_num);

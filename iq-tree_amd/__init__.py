@@ -40,6 +40,8 @@ IQHIP_SYMBOLS = [
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
     "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
     "iqhip_pair_counts", "iqhip_pair_distances", "iqhip_debug_pair_timing",
+    "iqhip_pars_init", "iqhip_pars_update", "iqhip_pars_branch_scores", "iqhip_pars_insert_scores", "iqhip_pars_fetch", "iqhip_pars_shape",
+    "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -62,6 +64,11 @@ class NodeOp(C.Structure):
 class BranchEnd(C.Structure):
     """struct iqhip_branch_end (include/iqhip.h)."""
     _fields_ = [("key", C.c_uint64), ("leaf", C.c_int32), ("_pad", C.c_int32)]
+
+
+class ParsOp(C.Structure):
+    """struct iqhip_pars_op (include/iqhip.h): slots."""
+    _fields_ = [("dst", C.c_int32), ("left", C.c_int32), ("right", C.c_int32), ("_pad", C.c_int32)]
 
 
 class BranchSupport(C.Structure):
@@ -209,6 +216,15 @@ def libiqhip():
     lib.iqhip_pair_counts.argtypes = [vp, i32p, C.c_int, dp]
     lib.iqhip_pair_distances.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, i32p]
     lib.iqhip_debug_pair_timing.argtypes = [vp, dp, dp]
+    u8p, u32p, i64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
+    lib.iqhip_pars_init.argtypes = [vp, u8p, C.c_int, i64p]
+    lib.iqhip_pars_update.argtypes = [vp, C.POINTER(ParsOp), C.c_int]
+    lib.iqhip_pars_branch_scores.argtypes = [vp, i32p, C.c_int, i32p, i32p]
+    lib.iqhip_pars_insert_scores.argtypes = [vp, i32p, C.c_int, C.c_int32, i32p, i32p, i32p]
+    lib.iqhip_pars_fetch.argtypes = [vp, C.c_int32, u32p]
+    lib.iqhip_pars_shape.argtypes = [vp, i64p, i64p, C.POINTER(C.c_int)]
+    lib.iqhip_debug_pars_levels.argtypes = [C.c_int, C.c_int, u8p, C.POINTER(ParsOp), C.c_int, i32p]
+    lib.iqhip_debug_pars_timing.argtypes = [vp, dp, i64p, C.c_int]
     lib._iq_typed = True
     return lib
 
@@ -266,6 +282,17 @@ def libiqhost():
     lib.iqhost_nni_for_branch.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     lib.iqhost_evaluate_nnis_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_compute_all_partial_lh.argtypes = [vp]
+    lib.iqhost_sync_inputs.argtypes = [vp]
+    ipp = C.POINTER(C.c_int)
+    lib.iqhost_compute_parsimony.argtypes = [vp, ipp]
+    lib.iqhost_parsimony_branch.argtypes = [vp, C.c_int, C.c_int, ipp, ipp]
+    lib.iqhost_initialize_all_partial_pars.argtypes = [vp]
+    lib.iqhost_compute_all_partial_pars.argtypes = [vp]
+    lib.iqhost_fix_negative_branch.argtypes = [vp, C.c_int, ipp]
+    lib.iqhost_pars_nsites.argtypes = [vp]
+    lib.iqhost_pars_nsites.restype = C.c_int64
+    lib.iqhost_get_branches.argtypes = [vp, ipp, C.c_int]
+    lib.iqhost_compute_parsimony_tree.argtypes = [vp, ipp, ipp, ipp, C.c_int, ipp, ipp]
     lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
     lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
@@ -312,6 +339,8 @@ def libiqhost():
     lib.iqaln_append_unobserved.argtypes = [vp, ip]
     lib.iqaln_get.argtypes = [vp, u8p, dp, ip, ip]
     lib.iqaln_ptn_invar.argtypes = [vp, C.c_double, dp, dp]
+    lib.iqaln_num_informative_sites.argtypes = [vp]
+    lib.iqaln_informative.argtypes = [vp, u8p]
     lib.iqaln_state_freq.argtypes = [vp, dp]
     lib.iqaln_codon_freq.argtypes = [vp, C.c_int, dp, dp]
     lib.iqaln_write_sitelh.argtypes = [vp, C.c_char_p, dp]
@@ -326,6 +355,42 @@ def _dptr(a):
 
 class HostError(RuntimeError):
     pass
+
+
+class EngineError(HostError):
+    """a raw engine call returned a status: .code is the IQHIP_ERR_* value"""
+
+    def __init__(self, code, text):
+        super().__init__("%s (status %d)" % (text, code))
+        self.code = code
+
+
+ERR_INVALID, ERR_UNSUPPORTED = 2, 3
+
+
+def _echk(rc):
+    if rc != 0:
+        raise EngineError(rc, libiqhip().iqhip_last_error().decode())
+
+
+def _pars_ops(ops):
+    a = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 3)
+    arr = (ParsOp * max(1, a.shape[0]))()
+    for k, (d, l, r) in enumerate(a):
+        arr[k] = ParsOp(int(d), int(l), int(r), 0)
+    return arr, a.shape[0]
+
+
+def pars_levels(ntaxa, nvectors, ops, valid=None):
+    """iqhip_debug_pars_levels: the validation and the level of every op of an iqhip_pars_update list (ops: rows of
+    (dst, left, right) slots; valid: None or nvectors flags of the slots written by earlier calls); no device needed"""
+    arr, n = _pars_ops(ops)
+    lev = np.zeros(max(1, n), dtype=np.int32)
+    v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    assert v is None or v.size == nvectors
+    _echk(libiqhip().iqhip_debug_pars_levels(int(ntaxa), int(nvectors), None if v is None else v.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            arr, n, lev.ctypes.data_as(C.POINTER(C.c_int32))))
+    return lev[:n]
 
 
 LK_EIGEN, LK_EIGEN_SSE, LK_EIGEN_HIP = 0, 1, 2
@@ -786,6 +851,123 @@ class PhyloTree:
     def compute_all_partial_lh(self):
         self._chk(self.lib.iqhost_compute_all_partial_lh(self.h))
 
+    # ---- Fitch parsimony (PhyloTree::computeParsimony ... computeParsimonyTree of the host mirror)
+    def compute_parsimony(self):
+        """the Fitch parsimony score of the tree over the parsimony-informative sites"""
+        out = C.c_int()
+        self._chk(self.lib.iqhost_compute_parsimony(self.h, C.byref(out)))
+        return out.value
+
+    def parsimony_branch(self, a, b):
+        """computeParsimonyBranch at branch a-b -> (score, substitutions on the branch)"""
+        sc, sb = C.c_int(), C.c_int()
+        self._chk(self.lib.iqhost_parsimony_branch(self.h, int(a), int(b), C.byref(sc), C.byref(sb)))
+        return sc.value, sb.value
+
+    def initialize_all_partial_pars(self):
+        self._chk(self.lib.iqhost_initialize_all_partial_pars(self.h))
+
+    def compute_all_partial_pars(self):
+        self._chk(self.lib.iqhost_compute_all_partial_pars(self.h))
+
+    @property
+    def pars_nsites(self):
+        """parsimony-informative sites of the last initialisation"""
+        return int(self.lib.iqhost_pars_nsites(self.h))
+
+    def fix_negative_branch(self, force=True):
+        """fixNegativeBranch: branch lengths from the per-branch substitution counts (Jukes-Cantor corrected) -> branches set"""
+        out = C.c_int()
+        self._chk(self.lib.iqhost_fix_negative_branch(self.h, int(force), C.byref(out)))
+        return out.value
+
+    def get_branches(self):
+        """MTree::getBranches from the root: [(node1, node2)] with node1 < node2"""
+        cap = 2 * self.num_leaves
+        out = (C.c_int * (2 * cap))()
+        n = self.lib.iqhost_get_branches(self.h, out, cap)
+        return [(out[2 * k], out[2 * k + 1]) for k in range(n)]
+
+    def compute_parsimony_tree(self, order, trace=False):
+        """stepwise addition by maximum parsimony in the given taxon order (computeParsimonyTree without its shuffle): the
+        tree is replaced, its branch lengths come from fix_negative_branch(True) -> score, or with trace
+        (score, [per step dict(branches=[(node1, node2)], scores=[...], chosen=index)])"""
+        T = self.num_leaves
+        od = (C.c_int * T)(*[int(x) for x in order])
+        assert len(order) == T
+        score = C.c_int()
+        if not trace:
+            self._chk(self.lib.iqhost_compute_parsimony_tree(self.h, od, C.byref(score), None, 0, None, None))
+            return score.value
+        cap = max(1, T * T)
+        rows, chosen, n = (C.c_int * (4 * cap))(), (C.c_int * max(1, T))(), C.c_int()
+        self._chk(self.lib.iqhost_compute_parsimony_tree(self.h, od, C.byref(score), rows, cap, C.byref(n), chosen))
+        steps = [dict(branches=[], scores=[], chosen=chosen[s]) for s in range(max(0, T - 3))]
+        for k in range(n.value):
+            st = steps[rows[4 * k]]
+            st["branches"].append((rows[4 * k + 1], rows[4 * k + 2]))
+            st["scores"].append(rows[4 * k + 3])
+        return score.value, steps
+
+    # ---- Fitch parsimony: thin wrappers of the raw calls (include/iqhip.h "Fitch parsimony"); a status other than OK
+    #      raises EngineError with its code
+    def _pars_engine(self):
+        self._chk(self.lib.iqhost_sync_inputs(self.h))
+        return self.engine
+
+    def pars_init(self, informative=None, nvectors=None):
+        """iqhip_pars_init -> number of sites; nvectors defaults to the reference's arena, 4 * (ntaxa - 1)"""
+        inf = None if informative is None else np.ascontiguousarray(informative, dtype=np.uint8)
+        assert inf is None or inf.size == self.nptn
+        nv = 4 * (self.num_leaves - 1) if nvectors is None else int(nvectors)
+        nsites = C.c_int64()
+        _echk(libiqhip().iqhip_pars_init(self._pars_engine(), None if inf is None else inf.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        nv, C.byref(nsites)))
+        return nsites.value
+
+    def pars_update(self, ops):
+        """iqhip_pars_update: ops = rows of (dst, left, right) slots, one launch"""
+        arr, n = _pars_ops(ops)
+        _echk(libiqhip().iqhip_pars_update(self._pars_engine(), arr, n))
+
+    def pars_branch_scores(self, ends):
+        """iqhip_pars_branch_scores: ends [nbranch, 2] slots -> (score[nbranch], subst[nbranch])"""
+        en = np.ascontiguousarray(ends, dtype=np.int32).reshape(-1, 2)
+        sc, sb = np.zeros(max(1, en.shape[0]), dtype=np.int32), np.zeros(max(1, en.shape[0]), dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _echk(libiqhip().iqhip_pars_branch_scores(self._pars_engine(), en.ctypes.data_as(i32p), en.shape[0],
+                                                 sc.ctypes.data_as(i32p), sb.ctypes.data_as(i32p)))
+        return sc[:en.shape[0]], sb[:en.shape[0]]
+
+    def pars_insert_scores(self, ends, taxon, want_scores=True):
+        """iqhip_pars_insert_scores: the scan of one stepwise-addition step -> (score[nbranch] or None, best, best_score)"""
+        en = np.ascontiguousarray(ends, dtype=np.int32).reshape(-1, 2)
+        sc = np.zeros(max(1, en.shape[0]), dtype=np.int32) if want_scores else None
+        best, bs = C.c_int32(), C.c_int32()
+        i32p = C.POINTER(C.c_int32)
+        _echk(libiqhip().iqhip_pars_insert_scores(self._pars_engine(), en.ctypes.data_as(i32p), en.shape[0], int(taxon),
+                                                 None if sc is None else sc.ctypes.data_as(i32p), C.byref(best), C.byref(bs)))
+        return (None if sc is None else sc[:en.shape[0]]), best.value, bs.value
+
+    def pars_fetch(self, slot):
+        """iqhip_pars_fetch -> (planes[nwords, nstates] uint32 in the reference's layout, subtree score)"""
+        nwords = self.pars_shape()[1]
+        out = np.zeros(nwords * self.nstates + 1, dtype=np.uint32)
+        _echk(libiqhip().iqhip_pars_fetch(self._pars_engine(), int(slot), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:-1].reshape(nwords, self.nstates).copy(), int(out[-1])
+
+    def pars_shape(self):
+        """iqhip_pars_shape -> (nsites, nwords, nvectors) of the engine's current parsimony state, whoever initialised it"""
+        ns, nw, nv = C.c_int64(), C.c_int64(), C.c_int()
+        _echk(libiqhip().iqhip_pars_shape(self._pars_engine(), C.byref(ns), C.byref(nw), C.byref(nv)))
+        return ns.value, nw.value, nv.value
+
+    def pars_timing(self, reset=True):
+        """iqhip_debug_pars_timing -> {update_ms, scan_ms, update_launches, scan_launches, ops, branches} since the last reset"""
+        ms, ln = (C.c_double * 2)(), (C.c_int64 * 4)()
+        _echk(libiqhip().iqhip_debug_pars_timing(self.engine, ms, ln, int(reset)))
+        return dict(update_ms=ms[0], scan_ms=ms[1], update_launches=ln[0], scan_launches=ln[1], ops=ln[2], branches=ln[3])
+
     def set_branch_bounds(self, lo, hi):
         self._chk(self.lib.iqhost_set_branch_bounds(self.h, lo, hi))
 
@@ -933,6 +1115,16 @@ class Alignment:
         _mchk(self.lib, self.lib.iqaln_get(self.h, st.ctypes.data_as(C.POINTER(C.c_uint8)), _dptr(fr),
                                            sp.ctypes.data_as(C.POINTER(C.c_int)), cc.ctypes.data_as(C.POINTER(C.c_int))))
         return st, fr, sp, cc
+
+    def informative(self):
+        """-> is_informative[nptn] uint8 (Alignment::computeConst's parsimony-informative flag per pattern)"""
+        out = np.zeros(self.npattern, dtype=np.uint8)
+        _mchk(self.lib, self.lib.iqaln_informative(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    @property
+    def num_informative_sites(self):
+        return int(self.lib.iqaln_num_informative_sites(self.h))
 
     def ptn_invar(self, p_invar, state_freq):
         out = np.zeros(self.npattern)

@@ -264,10 +264,13 @@ extern "C" void iqhip_destroy(iqhip_engine *e) {
                     e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks, e->d_batch_posts, e->d_sweep_len,
                     e->d_ptnlh, e->d_bt_rows, e->d_bt_part, e->d_bt_sums, e->d_bt_out, e->d_batch_rows,
                     e->d_freq_prefix, e->d_tt_var, e->d_tt_dbl, e->d_tt_int,
-                    e->d_pd_tiles, e->d_pd_counts, e->d_pd_coef, e->d_pd_init, e->d_pd_out};
+                    e->d_pd_tiles, e->d_pd_counts, e->d_pd_coef, e->d_pd_init, e->d_pd_out,
+                    e->d_pars_vec, e->d_pars_score, e->d_pars_int, e->d_pars_out, e->d_pars_masks};
     for (void *p : ptrs)
         if (p) hipFree(p);
     if (e->h_ops) hipHostFree(e->h_ops);
+    for (int32_t *h : {e->h_pars_ops, e->h_pars_ends, e->h_pars_out})
+        if (h) hipHostFree(h);
     if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
     if (e->h_plan_arena) hipHostFree(e->h_plan_arena);
     if (e->d_sweep_desc) hipFree(e->d_sweep_desc);
@@ -400,6 +403,8 @@ extern "C" int iqhip_set_ptn_freq(iqhip_engine *e, const double *ptn_freq) {
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->freq_prefix_valid = false;   // (iqhip_gen_boot_samples rebuilds its prefix sums)
+    e->h_freq.assign(ptn_freq, ptn_freq + e->nptn);
+    e->pars_ready = false;          // (the parsimony sites follow the frequencies: iqhip_pars_init lays them out again)
     return IQHIP_OK;
 }
 
@@ -445,6 +450,7 @@ extern "C" int iqhip_set_alignment(iqhip_engine *e, const uint8_t *states, const
     }
     HIPCHK(hipMemcpyAsync(e->d_states, tmp.data(), tmp.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    e->pars_ready = false;
     int rc = iqhip_set_ptn_freq(e, ptn_freq);
     if (rc) return rc;
     rc = iqhip_set_ptn_invar(e, ptn_invar);
@@ -536,6 +542,9 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
         for (int c = 0; c < C; c++)
             memcpy(&blk[o_tipc + (s * C + c) * n], &tip[(s * nclass + cls[c]) * n], sizeof(double) * n);
     memcpy(&blk[o_cls], cls.data(), sizeof(int) * C);
+    // (iqhip_pars_init recovers the states a code allows from class 0's eigenvectors and tip rows)
+    e->h_evec0.assign(evec, evec + (size_t)n * n);
+    e->h_tip0.assign(&blk[o_tip], &blk[o_tip] + nst * n);
     if (aimg_doubles) {
         double *U = &blk[o_aimg], *Ui = U + (size_t)a_mt * a_ks * 64, *U4 = Ui + (size_t)a_mt * a_ks * 64, *Ui4 = U4 + (size_t)a_ks * 64;
         for (int m = 0; m < a_mt; m++)

@@ -473,7 +473,31 @@ struct iqhip_engine {
     double *d_pd_out = nullptr;
     size_t pd_out_cap = 0;
     double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
-    int32_t *d_batch_rows = nullptr;    // iqhip_optimize_branch_batch_rows: store row per task of a chunk
+    // Fitch parsimony (pars.hip, kernels_pars.hip).  Host copies of what iqhip_pars_init reads: ptn_freq
+    // (iqhip_set_ptn_freq), class 0's eigenvectors and tip table (set_model_common).  Vectors [ntaxa + nvectors] of
+    // pars_nwords * n words (4 states: word-major, a column is one 16-byte load; 20 / 64 states: plane-major, lanes on
+    // consecutive columns coalesce) and their score columns [ntaxa + nvectors][pars_nwords]; one valid flag per caller slot
+    std::vector<double> h_freq, h_evec0, h_tip0;
+    bool pars_ready = false;
+    int pars_nvec = 0;
+    int64_t pars_nsites = 0, pars_nwords = 0;
+    uint32_t *d_pars_vec = nullptr, *d_pars_score = nullptr;
+    size_t pars_vec_cap = 0, pars_score_cap = 0;
+    std::vector<uint8_t> pars_valid;
+    int32_t *d_pars_int = nullptr;      // per call: ops ++ level starts, or branch ends; init: the pattern of every site
+    size_t pars_int_cap = 0;
+    int32_t *d_pars_out = nullptr;      // score [nbranch] ++ subst [nbranch] ++ {best, best_score}
+    size_t pars_out_cap = 0;
+    // pinned staging, one buffer per direction and kind so that none is rewritten while a copy of it may be in flight: the
+    // levelled ops of an update (rewritten only after a synchronise), the branch ends and the results of a scores call
+    // (every scores call ends with a synchronise)
+    int32_t *h_pars_ops = nullptr, *h_pars_ends = nullptr, *h_pars_out = nullptr;
+    size_t h_pars_ops_cap = 0, h_pars_ends_cap = 0, h_pars_out_cap = 0;
+    uint64_t *d_pars_masks = nullptr;   // [state_unknown + 1] the states a code allows
+    size_t pars_masks_cap = 0;
+    double pars_ms[2] = {0.0, 0.0};     // iqhip_debug_pars_timing: update, scan (while timing is enabled)
+    int64_t pars_counts[4] = {0, 0, 0, 0};   // launches of the updates and of the scans, ops updated, branches scanned
+    int32_t *d_batch_rows = nullptr;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     size_t batch_rows_cap = 0;
     double *d_result_own = nullptr, *d_result = nullptr;
     double *d_newton_partials = nullptr;   // [2][num_cus][2]
@@ -1033,6 +1057,15 @@ struct PairSolveArgs {
 hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts);
 hipError_t launch_pair_coef(iqhip_engine *e, double *d_coef);
 hipError_t launch_pair_solve(iqhip_engine *e, const PairSolveArgs &a, int npairs);
+
+// Fitch parsimony (kernels_pars.hip); all on e->stream, shapes from e->pars_nwords / e->n
+constexpr int kParsWordsPerWg = 16;   // word columns a workgroup of k_pars_update owns ...
+constexpr int kParsThreads = 1024;    // ... and its threads: 64 ops of a level side by side (measured: DESIGN.md 3.8)
+hipError_t launch_pars_tips(iqhip_engine *e, const int32_t *d_site_ptn);
+// d_ops: nops ops sorted by level; d_lev_start: nlev + 1 offsets into them
+hipError_t launch_pars_update(iqhip_engine *e, const iqhip_pars_op *d_ops, const int32_t *d_lev_start, int nlev);
+// d_out: score [nbranch] ++ subst [nbranch]; taxon >= 0: the insertion scan, which also writes {best, best_score} behind them
+hipError_t launch_pars_branch(iqhip_engine *e, const int32_t *d_ends, int nbranch, int taxon, int32_t *d_out, int *nlaunches);
 
 // batched branch optimisation (k_newton_batch); d_tasks: device array of NewtonTask (kernels_newton.hip)
 hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,

@@ -1,0 +1,320 @@
+// pars.hip -- host side of the Fitch parsimony calls (include/iqhip.h "Fitch parsimony"; kernels in kernels_pars.hip):
+// the site layout and the state masks of iqhip_pars_init, the validation and level assignment of an op list (in the spirit
+// of check_plan: everything is checked before anything is launched), and the launches.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "iqhip_internal.h"
+
+using namespace iqhip;
+
+// Validation of an op list and its levels.  valid: one flag per caller slot (NULL: none written yet).  level: nops entries
+// or NULL.  Returns an empty string or what is wrong.
+static std::string pars_levels(int ntaxa, int nvectors, const uint8_t *valid, const iqhip_pars_op *ops, int nops,
+                               int32_t *level) {
+    if (ntaxa < 1 || nvectors < 0) return "bad slot counts";
+    if (nops < 0 || (nops > 0 && !ops)) return "bad op list";
+    const int64_t nslots = (int64_t)ntaxa + nvectors;
+    // per slot: the op of this call that writes it (-1: none), and whether an op of this call has read it so far
+    std::vector<int32_t> writer((size_t)nslots, -1);
+    std::vector<uint8_t> was_read((size_t)nslots, 0);
+    std::vector<int32_t> lev((size_t)nops, 0);
+    auto op_name = [](int k) { return "op " + std::to_string(k); };
+    for (int k = 0; k < nops; k++) {
+        const iqhip_pars_op &o = ops[k];
+        const int32_t ch[2] = {o.left, o.right};
+        if (o.dst < 0 || o.dst >= nslots || o.left < 0 || o.left >= nslots || o.right < 0 || o.right >= nslots)
+            return op_name(k) + ": slot outside [0, ntaxa + nvectors)";
+        if (o.dst < ntaxa) return op_name(k) + ": dst is a tip slot";
+        if (o.dst == o.left || o.dst == o.right) return op_name(k) + ": dst is one of its own children";
+        if (writer[(size_t)o.dst] >= 0) return op_name(k) + ": slot " + std::to_string(o.dst) + " is written twice in one call";
+        if (was_read[(size_t)o.dst])
+            return op_name(k) + ": slot " + std::to_string(o.dst) + " is read by an earlier op of this call";
+        int l = 0;
+        for (int c : ch) {
+            if (c >= ntaxa) {
+                if (writer[(size_t)c] >= 0) l = std::max(l, lev[(size_t)writer[(size_t)c]] + 1);
+                else if (!(valid && valid[c - ntaxa]))
+                    return op_name(k) + ": slot " + std::to_string(c) + " is read before anything has written it";
+            }
+            was_read[(size_t)c] = 1;
+        }
+        writer[(size_t)o.dst] = k;
+        lev[(size_t)k] = l;
+    }
+    if (level) std::copy(lev.begin(), lev.end(), level);
+    return std::string();
+}
+
+extern "C" int iqhip_debug_pars_levels(int ntaxa, int nvectors, const uint8_t *valid, const iqhip_pars_op *ops, int nops,
+                                       int32_t *level) {
+    const std::string err = pars_levels(ntaxa, nvectors, valid, ops, nops, level);
+    if (!err.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pars_levels: " + err);
+    return IQHIP_OK;
+}
+
+static int pars_engine(iqhip_engine *e, const char *what, bool need_init) {
+    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
+    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines are out of scope (a word column would span shards)");
+    if (e->n_user != e->n || (e->n != 4 && e->n != 20 && e->n != 64))
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": 4, 20 or 64 states only (no embedded state counts)");
+    if (!e->model_set || !e->aln_set)
+        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_model and iqhip_set_alignment first");
+    if (need_init && !e->pars_ready)
+        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_pars_init first (the alignment or its frequencies changed since)");
+    return IQHIP_OK;
+}
+
+// HIP events around the launches of a call while iqhip_timing_enable is on
+struct ParsTimer {
+    iqhip_engine *e;
+    int which;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ParsTimer(iqhip_engine *e_, int which_) : e(e_), which(which_) {}
+    hipError_t start() {
+        if (!e->timing) return hipSuccess;
+        for (auto &v : ev) {
+            const hipError_t s = hipEventCreate(&v);
+            if (s != hipSuccess) return s;
+        }
+        return hipEventRecord(ev[0], e->stream);
+    }
+    hipError_t stop(int nlaunches, int64_t work) {
+        e->pars_counts[which] += nlaunches;
+        e->pars_counts[2 + which] += work;
+        if (!e->timing) return hipSuccess;
+        hipError_t s = hipEventRecord(ev[1], e->stream);
+        if (s == hipSuccess) s = hipEventSynchronize(ev[1]);
+        float ms = 0.f;
+        if (s == hipSuccess) s = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        if (s == hipSuccess) {
+            e->pars_ms[which] += ms;
+        }
+        return s;
+    }
+    ~ParsTimer() {
+        for (auto v : ev)
+            if (v) hipEventDestroy(v);
+    }
+};
+
+// a pinned staging buffer of at least `need` words (the stream is drained before an old one is freed)
+static hipError_t pars_pinned(iqhip_engine *e, int32_t **buf, size_t *cap, size_t need) {
+    if (need <= *cap) return hipSuccess;
+    hipError_t s = hipStreamSynchronize(e->stream);
+    if (s != hipSuccess) return s;
+    if (*buf) hipHostFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    const size_t want = need + need / 2 + 64;
+    if ((s = hipHostMalloc((void **)buf, want * sizeof(int32_t))) != hipSuccess) return s;
+    *cap = want;
+    return hipSuccess;
+}
+
+extern "C" int iqhip_pars_shape(iqhip_engine *e, int64_t *nsites, int64_t *nwords, int *nvectors) {
+    int rc = pars_engine(e, "iqhip_pars_shape", true);
+    if (rc) return rc;
+    if (nsites) *nsites = e->pars_nsites;
+    if (nwords) *nwords = e->pars_nwords;
+    if (nvectors) *nvectors = e->pars_nvec;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative, int nvectors, int64_t *nsites) {
+    int rc = pars_engine(e, "iqhip_pars_init", false);
+    if (rc) return rc;
+    e->pars_ready = false;
+    if (nvectors < 0) return fail(IQHIP_ERR_INVALID, "iqhip_pars_init: nvectors < 0");
+    const int n = e->n;
+    const int nst = e->state_unknown + 1;
+    if ((int64_t)e->h_freq.size() != e->nptn || e->h_evec0.size() != (size_t)n * n || e->h_tip0.size() != (size_t)nst * n)
+        return fail(IQHIP_ERR_INVALID, "iqhip_pars_init: the alignment or the model is not set");
+    // the sites: pattern p, ptn_freq[p] times, in pattern order
+    int64_t total = 0;
+    for (int64_t p = 0; p < e->nptn; p++) {
+        const double f = e->h_freq[(size_t)p];
+        if (!(f >= 0.0) || f != std::floor(f) || f > 2147483647.0)
+            return fail(IQHIP_ERR_INVALID, "iqhip_pars_init: pattern frequencies must be non-negative integers");
+        if (!informative || informative[p]) total += (int64_t)f;
+    }
+    if (total > 2147483647LL - 32) return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_pars_init: more than 2^31 sites");
+    std::vector<int32_t> site_ptn;
+    site_ptn.reserve((size_t)total + 1);
+    for (int64_t p = 0; p < e->nptn; p++)
+        if (!informative || informative[p]) site_ptn.insert(site_ptn.end(), (size_t)e->h_freq[(size_t)p], (int32_t)p);
+    const int64_t nwords = std::max<int64_t>(1, (total + 31) / 32);
+    // the states a code allows: the tip table row is U^-1 times the indicator, so U times the row gives it back
+    std::vector<uint64_t> masks((size_t)nst, 0);
+    for (int s = 0; s < nst; s++)
+        for (int i = 0; i < n; i++) {
+            double v = 0.0;
+            for (int k = 0; k < n; k++) v += e->h_evec0[(size_t)i * n + k] * e->h_tip0[(size_t)s * n + k];
+            if (v > 0.5) masks[(size_t)s] |= 1ull << i;
+        }
+    HIPCHK(use_device(e));
+    const size_t nslots = (size_t)e->ntaxa + (size_t)nvectors;
+    const size_t vec_words = nslots * (size_t)nwords * n, score_words = nslots * (size_t)nwords;
+    if (vec_words > e->pars_vec_cap) HIPCHK(regrow(e, &e->d_pars_vec, &e->pars_vec_cap, vec_words, vec_words));
+    if (score_words > e->pars_score_cap) HIPCHK(regrow(e, &e->d_pars_score, &e->pars_score_cap, score_words, score_words));
+    if (site_ptn.size() + 1 > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, site_ptn.size() + 1, site_ptn.size() + 1));
+    if ((size_t)nst > e->pars_masks_cap) HIPCHK(regrow(e, &e->d_pars_masks, &e->pars_masks_cap, (size_t)nst, (size_t)nst));
+    e->pars_nsites = total;
+    e->pars_nwords = nwords;
+    e->pars_nvec = nvectors;
+    e->pars_valid.assign((size_t)nvectors, 0);
+    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable sources: the copies must not outlive them)
+    if (!site_ptn.empty())
+        HIPCHK(hipMemcpyAsync(e->d_pars_int, site_ptn.data(), sizeof(int32_t) * site_ptn.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_pars_masks, masks.data(), sizeof(uint64_t) * masks.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_pars_tips(e, e->d_pars_int));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (nsites) *nsites = total;
+    e->pars_ready = true;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int nops) {
+    int rc = pars_engine(e, "iqhip_pars_update", true);
+    if (rc) return rc;
+    std::vector<int32_t> level((size_t)std::max(nops, 0));
+    const std::string err = pars_levels(e->ntaxa, e->pars_nvec, e->pars_valid.data(), ops, nops, level.data());
+    if (!err.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_pars_update: " + err);
+    if (nops == 0) return IQHIP_OK;
+    // the ops sorted by level (stable), and where each level starts
+    int nlev = 0;
+    for (int k = 0; k < nops; k++) nlev = std::max(nlev, level[(size_t)k] + 1);
+    std::vector<int32_t> start((size_t)nlev + 1, 0);
+    for (int k = 0; k < nops; k++) start[(size_t)level[(size_t)k] + 1]++;
+    for (int l = 0; l < nlev; l++) start[(size_t)l + 1] += start[(size_t)l];
+    // one upload from pinned staging: ops (4 words each) ++ level starts.  The staging buffer may still feed the previous
+    // update's copy, so the stream is drained first (after a scores call it is idle); nothing waits after the launch
+    const size_t nblob = (size_t)4 * nops + (size_t)nlev + 1;
+    HIPCHK(use_device(e));
+    if (nblob > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, nblob, nblob));
+    HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    {
+        std::vector<int32_t> at(start.begin(), start.end() - 1);
+        iqhip_pars_op *sorted = reinterpret_cast<iqhip_pars_op *>(e->h_pars_ops);
+        for (int k = 0; k < nops; k++) sorted[at[(size_t)level[(size_t)k]]++] = ops[k];
+        std::copy(start.begin(), start.end(), e->h_pars_ops + (size_t)4 * nops);
+    }
+    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    ParsTimer tm(e, 0);
+    HIPCHK(tm.start());
+    HIPCHK(launch_pars_update(e, reinterpret_cast<const iqhip_pars_op *>(e->d_pars_int), e->d_pars_int + (size_t)4 * nops, nlev));
+    HIPCHK(tm.stop(1, nops));
+    for (int k = 0; k < nops; k++) e->pars_valid[(size_t)(ops[k].dst - e->ntaxa)] = 1;
+    return IQHIP_OK;
+}
+
+// the slots of a branch list must hold something
+static int pars_check_ends(iqhip_engine *e, const char *what, const int32_t *ends, int nbranch) {
+    if (!ends || nbranch < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad branch list (nbranch >= 1)");
+    const int64_t nslots = (int64_t)e->ntaxa + e->pars_nvec;
+    for (int64_t k = 0; k < 2 * (int64_t)nbranch; k++) {
+        const int32_t s = ends[k];
+        if (s < 0 || s >= nslots) return fail(IQHIP_ERR_INVALID, std::string(what) + ": slot outside [0, ntaxa + nvectors)");
+        if (s >= e->ntaxa && !e->pars_valid[(size_t)(s - e->ntaxa)])
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": slot " + std::to_string(s) + " has never been written");
+    }
+    return IQHIP_OK;
+}
+
+static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int taxon, std::vector<int32_t> &out, size_t from,
+                       size_t count) {
+    HIPCHK(use_device(e));
+    const size_t need_out = (size_t)2 * nbranch + 2;
+    if ((size_t)2 * nbranch > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, (size_t)2 * nbranch, (size_t)2 * nbranch));
+    if (need_out > e->pars_out_cap) HIPCHK(regrow(e, &e->d_pars_out, &e->pars_out_cap, need_out, need_out));
+    HIPCHK(pars_pinned(e, &e->h_pars_ends, &e->h_pars_ends_cap, (size_t)2 * nbranch));
+    HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
+    // (no copy of h_pars_ends or into h_pars_out is in flight: every call of this function ends with a synchronise)
+    memcpy(e->h_pars_ends, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
+    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ends, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
+    ParsTimer tm(e, 1);
+    int nlaunches = 0;
+    if (taxon >= 0) HIPCHK(tm.start());
+    HIPCHK(launch_pars_branch(e, e->d_pars_int, nbranch, taxon, e->d_pars_out, &nlaunches));
+    if (taxon >= 0) HIPCHK(tm.stop(nlaunches, nbranch));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->d_pars_out + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    out.assign(e->h_pars_out, e->h_pars_out + count);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_branch_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int32_t *score, int32_t *subst) {
+    int rc = pars_engine(e, "iqhip_pars_branch_scores", true);
+    if (rc) return rc;
+    rc = pars_check_ends(e, "iqhip_pars_branch_scores", ends, nbranch);
+    if (rc) return rc;
+    std::vector<int32_t> out;
+    rc = pars_scores(e, ends, nbranch, -1, out, 0, (size_t)2 * nbranch);
+    if (rc) return rc;
+    if (score) memcpy(score, out.data(), sizeof(int32_t) * (size_t)nbranch);
+    if (subst) memcpy(subst, out.data() + nbranch, sizeof(int32_t) * (size_t)nbranch);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_insert_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int32_t taxon, int32_t *score,
+                                        int32_t *best, int32_t *best_score) {
+    int rc = pars_engine(e, "iqhip_pars_insert_scores", true);
+    if (rc) return rc;
+    rc = pars_check_ends(e, "iqhip_pars_insert_scores", ends, nbranch);
+    if (rc) return rc;
+    if (taxon < 0 || taxon >= e->ntaxa) return fail(IQHIP_ERR_INVALID, "iqhip_pars_insert_scores: taxon is not a tip slot");
+    // without `score` the host reads back two integers
+    std::vector<int32_t> out;
+    const size_t from = score ? 0 : (size_t)2 * nbranch, count = score ? (size_t)2 * nbranch + 2 : 2;
+    rc = pars_scores(e, ends, nbranch, taxon, out, from, count);
+    if (rc) return rc;
+    if (score) memcpy(score, out.data(), sizeof(int32_t) * (size_t)nbranch);
+    if (best) *best = out[count - 2];
+    if (best_score) *best_score = out[count - 1];
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out) {
+    int rc = pars_engine(e, "iqhip_pars_fetch", true);
+    if (rc) return rc;
+    if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_pars_fetch: null argument");
+    if (slot < 0 || slot >= (int64_t)e->ntaxa + e->pars_nvec) return fail(IQHIP_ERR_INVALID, "iqhip_pars_fetch: slot outside [0, ntaxa + nvectors)");
+    if (slot >= e->ntaxa && !e->pars_valid[(size_t)(slot - e->ntaxa)])
+        return fail(IQHIP_ERR_INVALID, "iqhip_pars_fetch: the slot has never been written");
+    HIPCHK(use_device(e));
+    const int n = e->n;
+    const size_t nw = (size_t)e->pars_nwords;
+    std::vector<uint32_t> v(nw * n), sc(nw);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(v.data(), e->d_pars_vec + (size_t)slot * nw * n, sizeof(uint32_t) * v.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), e->d_pars_score + (size_t)slot * nw, sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
+    if (n == 4) memcpy(out, v.data(), sizeof(uint32_t) * v.size());
+    else
+        for (size_t w = 0; w < nw; w++)
+            for (int i = 0; i < n; i++) out[w * n + i] = v[(size_t)i * nw + w];
+    uint32_t total = 0;
+    for (size_t w = 0; w < nw; w++) total += sc[w];
+    out[nw * n] = total;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_pars_timing(iqhip_engine *e, double *ms, int64_t *counts, int reset) {
+    if (!e || !e->shards.empty() || e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pars_timing: needs a single-device engine");
+    for (int k = 0; k < 2; k++)
+        if (ms) ms[k] = e->pars_ms[k];
+    for (int k = 0; k < 4; k++)
+        if (counts) counts[k] = e->pars_counts[k];
+    if (reset) {
+        e->pars_ms[0] = e->pars_ms[1] = 0.0;
+        for (int k = 0; k < 4; k++) e->pars_counts[k] = 0;
+    }
+    return IQHIP_OK;
+}

@@ -254,9 +254,30 @@ void Alignment::getAppearance(int state, double *state_app) const {  // alignmen
         throw std::runtime_error("ambiguous state in a data type without ambiguity codes");
 }
 
+bool Alignment::isInformative(const uint8_t *column, int nseq, size_t stride) const {  // alignment.cpp:624-650
+    std::vector<double> app(num_states);
+    std::vector<int> num_app(num_states, 0);   // sequences that show each state
+    for (int t = 0; t < nseq; t++) {
+        const int s = column[(size_t)t * stride];
+        if (s == STATE_UNKNOWN) continue;      // counts towards no state
+        if (s < num_states) {
+            num_app[s]++;
+            continue;
+        }
+        getAppearance(s, app.data());          // an ambiguity code: towards every state it allows
+        for (int j = 0; j < num_states; j++)
+            if (app[j] != 0.0) num_app[j]++;
+    }
+    int twice = 0;
+    for (int j = 0; j < num_states; j++)
+        if (num_app[j] >= 2) twice++;
+    return twice >= 2;
+}
+
 void Alignment::computeConst(Pattern &pat) const {  // alignment.cpp:609-671
     pat.is_const = false;
     pat.const_char = (STATE_UNKNOWN == num_states) ? STATE_UNKNOWN + 1 : STATE_UNKNOWN;
+    pat.is_informative = isInformative(pat.states.data(), (int)pat.states.size(), 1);
     std::vector<char> all(num_states, 1);
     std::vector<double> app(num_states);
     for (uint8_t s : pat.states) {
@@ -281,8 +302,11 @@ void Alignment::computeConst(Pattern &pat) const {  // alignment.cpp:609-671
 
 void Alignment::countConstSite() {  // alignment.cpp:2501-2511
     long num_const = 0;
-    for (const Pattern &p : patterns)
+    num_informative_sites = 0;
+    for (const Pattern &p : patterns) {
         if (p.is_const) num_const += p.frequency;
+        if (p.is_informative) num_informative_sites += p.frequency;
+    }
     frac_const_sites = getNSite() ? (double)num_const / getNSite() : 0.0;
 }
 

@@ -28,6 +28,9 @@ struct Pattern {
     int frequency = 0;
     bool is_const = false;
     int const_char = 0;  // state shared by all sequences (num_states for an all-gap pattern)
+    // parsimony-informative (alignment.cpp:624-650): at least two states, each shown by at least two sequences; an
+    // ambiguity code counts towards every state it allows, STATE_UNKNOWN towards none
+    bool is_informative = false;
 };
 
 class Alignment {
@@ -49,11 +52,16 @@ public:
     int getNSeq() const { return (int)seq_names.size(); }
     int getNSite() const { return (int)site_pattern.size(); }
     int getNPattern() const { return (int)patterns.size(); }
+    int num_informative_sites = 0;       // sum of the frequencies of the informative patterns (alignment.cpp:2503-2508)
     bool isStopCodon(int state) const {
         return seq_type == SEQ_CODON && state < 64 && genetic_code[state] == '*';
     }
     // which of the num_states states a (possibly ambiguous) state stands for
     void getAppearance(int state, double *state_app) const;
+    // the parsimony-informative rule of computeConst (alignment.cpp:624-650) for one column of nseq states, `stride` bytes
+    // apart: at least two states shown by at least two sequences each.  Needs only seq_type, num_states and STATE_UNKNOWN,
+    // so PhyloTree::initializeAllPartialPars asks a bare Alignment of its own data type: one implementation of the rule
+    bool isInformative(const uint8_t *column, int nseq, size_t stride) const;
 
     // kernel inputs: states[leaf][ptn] (leaf = sequence index), ptn_freq, ptn_invar
     void statesByLeaf(std::vector<uint8_t> &out) const;

@@ -354,6 +354,51 @@ int iqhost_compute_dist(void *h, const double *init, double *dist, double *d2l) 
 int iqhost_pair_counts(void *h, const int32_t *pairs, int npairs, double *counts) {
     IQHOST_TRY(((PhyloTree *)h)->pairCounts(pairs, npairs, counts));
 }
+int iqhost_compute_parsimony(void *h, int *score) { IQHOST_TRY(*score = ((PhyloTree *)h)->computeParsimony()); }
+int iqhost_parsimony_branch(void *h, int a, int b, int *score, int *subst) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        *score = t->computeParsimonyBranch(nei(t, a, b), t->nodes[a], subst);
+    });
+}
+int iqhost_initialize_all_partial_pars(void *h) { IQHOST_TRY(((PhyloTree *)h)->initializeAllPartialPars()); }
+int iqhost_compute_all_partial_pars(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialPars()); }
+int iqhost_fix_negative_branch(void *h, int force, int *fixed) {
+    IQHOST_TRY(*fixed = ((PhyloTree *)h)->fixNegativeBranch(force != 0));
+}
+int64_t iqhost_pars_nsites(void *h) { return ((PhyloTree *)h)->pars_nsites; }
+int iqhost_get_branches(void *h, int *out /* 2 per branch */, int cap) {
+    PhyloTree *t = (PhyloTree *)h;
+    std::vector<PhyloNode *> n1, n2;
+    if (t->root) t->getBranches(n1, n2);
+    for (size_t k = 0; k < n1.size() && (int)k < cap; k++) {
+        out[2 * k] = n1[k]->id;
+        out[2 * k + 1] = n2[k]->id;
+    }
+    return (int)n1.size();
+}
+// trace (optional): rows of (step, node1, node2, score), at most trace_cap of them, *ntrace = how many there are;
+// chosen: per step the index of the branch taken (ntaxa - 3 entries)
+int iqhost_compute_parsimony_tree(void *h, const int *order, int *score, int *trace, int trace_cap, int *ntrace, int *chosen) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<PhyloTree::ParsStep> steps;
+        *score = t->computeParsimonyTree(order, trace ? &steps : nullptr);
+        int rows = 0;
+        for (size_t s = 0; s < steps.size(); s++) {
+            if (chosen) chosen[s] = steps[s].chosen;
+            for (size_t k = 0; k < steps[s].node1.size(); k++, rows++)
+                if (rows < trace_cap) {
+                    trace[4 * rows] = (int)s;
+                    trace[4 * rows + 1] = steps[s].node1[k];
+                    trace[4 * rows + 2] = steps[s].node2[k];
+                    trace[4 * rows + 3] = steps[s].score[k];
+                }
+        }
+        if (ntrace) *ntrace = rows;
+    });
+}
+int iqhost_sync_inputs(void *h) { IQHOST_TRY(((PhyloTree *)h)->syncInputs()); }
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {
     PhyloTree *t = (PhyloTree *)h;

@@ -83,6 +83,13 @@ int iqaln_get(void *h, uint8_t *states, double *ptn_freq, int *site_pattern, int
             for (size_t p = 0; p < a->patterns.size(); p++) const_char[p] = a->patterns[p].is_const ? a->patterns[p].const_char : -1;
     });
 }
+int iqaln_num_informative_sites(void *h) { return ((Alignment *)h)->num_informative_sites; }
+int iqaln_informative(void *h, uint8_t *out) {
+    IQM_TRY({
+        Alignment *a = (Alignment *)h;
+        for (size_t p = 0; p < a->patterns.size(); p++) out[p] = a->patterns[p].is_informative ? 1 : 0;
+    });
+}
 int iqaln_ptn_invar(void *h, double p_invar, const double *state_freq, double *out) {
     IQM_TRY({
         std::vector<double> v;

@@ -2,6 +2,7 @@
 // vectors happens in libiqhip.so.
 #include <time.h>
 #include "phylo_host.h"
+#include "alignment_host.h"
 
 #include <assert.h>
 #include <math.h>
@@ -61,6 +62,7 @@ void PhyloTree::freeTree() {
     nodes.clear();
     root = nullptr;
     current_it = current_it_back = nullptr;
+    pars_initialized = false;   // (the new tree's vectors have no slots yet)
 }
 
 namespace {
@@ -272,6 +274,7 @@ void PhyloTree::setPtnFreq(const double *f) {
     if (nptn <= 0) throw std::runtime_error("setAlignment first");
     ptn_freq.assign(f, f + nptn);
     inputs_dirty = weights_dirty = true;
+    pars_initialized = false;   // (the parsimony sites follow the frequencies)
 }
 
 void PhyloTree::setPtnInvar(const double *v) {
@@ -422,6 +425,12 @@ void PhyloTree::setLikelihoodKernel(LikelihoodKernel lk) {
     computeLikelihoodBranchPointer = &PhyloTree::computeLikelihoodBranchHIP;
     computeLikelihoodDervPointer = &PhyloTree::computeLikelihoodDervHIP;
     computeLikelihoodFromBufferPointer = &PhyloTree::computeLikelihoodFromBufferHIP;
+    setParsimonyKernel(lk);
+}
+
+void PhyloTree::setParsimonyKernel(LikelihoodKernel) {  // phylotreesse.cpp:34-58 (one device form for every kernel choice)
+    computePartialParsimonyPointer = &PhyloTree::computePartialParsimonyHIP;
+    computeParsimonyBranchPointer = &PhyloTree::computeParsimonyBranchHIP;
 }
 
 void PhyloTree::computePartialLikelihood(PhyloNeighbor *dad_branch, PhyloNode *dad) {
@@ -1343,6 +1352,288 @@ void PhyloTree::pairCounts(const int32_t *pairs, int npairs, double *counts) {
     if (!engine || dry_run) throw std::runtime_error("pairCounts needs an attached engine");
     pushInputs();
     check(iqhip_pair_counts(engine, pairs, npairs, counts), "iqhip_pair_counts");
+}
+
+// =========================================================================================
+// Fitch parsimony (phylotreepars.cpp; include/iqhip.h "Fitch parsimony")
+// =========================================================================================
+void PhyloTree::needParsimony(const char *what) {
+    if (!engine || dry_run) throw std::runtime_error(std::string(what) + " needs an attached engine");
+    if (!pars_initialized) initializeAllPartialPars();
+}
+
+void PhyloTree::initializeAllPartialPars() {
+    if (!engine || dry_run) throw std::runtime_error("initializeAllPartialPars needs an attached engine");
+    if (!root) throw std::runtime_error("no tree");
+    pushInputs();
+    // parsimony-informative patterns: Alignment::isInformative, the rule of computeConst, asked of this tree's data type
+    Alignment rule;
+    rule.seq_type = seq_type;
+    rule.num_states = num_states;
+    rule.STATE_UNKNOWN = STATE_UNKNOWN;
+    pars_informative.assign((size_t)nptn, 0);
+    for (int64_t p = 0; p < nptn; p++)
+        pars_informative[(size_t)p] = rule.isInformative(aln_states.data() + p, leafNum, (size_t)nptn);
+    check(iqhip_pars_init(engine, pars_informative.data(), 4 * (leafNum - 1), &pars_nsites), "iqhip_pars_init");
+    pars_next_slot = leafNum;
+    for (PhyloNeighbor *nb : all_neighbors) {
+        nb->pars_slot = nb->node->isLeaf() ? nb->node->id : pars_next_slot++;
+        nb->partial_lh_computed &= ~2;
+    }
+    pars_initialized = true;
+}
+
+void PhyloTree::collectParsOps(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_pars_op> &ops) {
+    PhyloNode *node = dad_branch->node;
+    if (node->isLeaf() || (dad_branch->partial_lh_computed & 2)) return;
+    PhyloNeighbor *kid[2] = {nullptr, nullptr};
+    int nkid = 0;
+    for (PhyloNeighbor *nb : node->neighbors)
+        if (nb->node != dad) {
+            if (nkid == 2) throw std::runtime_error("parsimony needs a strictly bifurcating tree");
+            kid[nkid++] = nb;
+        }
+    if (nkid != 2) throw std::runtime_error("parsimony needs a strictly bifurcating tree");
+    collectParsOps(kid[0], node, ops);
+    collectParsOps(kid[1], node, ops);
+    ops.push_back(iqhip_pars_op{dad_branch->pars_slot, kid[0]->pars_slot, kid[1]->pars_slot, 0});
+    dad_branch->partial_lh_computed |= 2;
+}
+
+void PhyloTree::submitParsOps(std::vector<iqhip_pars_op> &ops) {
+    if (ops.empty()) return;
+    check(iqhip_pars_update(engine, ops.data(), (int)ops.size()), "iqhip_pars_update");
+    ops.clear();
+}
+
+void PhyloTree::computePartialParsimony(PhyloNeighbor *dad_branch, PhyloNode *dad) {
+    (this->*computePartialParsimonyPointer)(dad_branch, dad);
+}
+int PhyloTree::computeParsimonyBranch(PhyloNeighbor *dad_branch, PhyloNode *dad, int *branch_subst) {
+    return (this->*computeParsimonyBranchPointer)(dad_branch, dad, branch_subst);
+}
+
+void PhyloTree::computePartialParsimonyHIP(PhyloNeighbor *dad_branch, PhyloNode *dad) {
+    needParsimony("computePartialParsimony");
+    std::vector<iqhip_pars_op> ops;
+    collectParsOps(dad_branch, dad, ops);
+    submitParsOps(ops);
+}
+
+int PhyloTree::computeParsimonyBranchHIP(PhyloNeighbor *dad_branch, PhyloNode *dad, int *branch_subst) {
+    needParsimony("computeParsimonyBranch");
+    PhyloNeighbor *node_branch = dad_branch->node->findNeighbor(dad);
+    std::vector<iqhip_pars_op> ops;
+    collectParsOps(dad_branch, dad, ops);
+    collectParsOps(node_branch, dad_branch->node, ops);
+    submitParsOps(ops);
+    const int32_t ends[2] = {dad_branch->pars_slot, node_branch->pars_slot};
+    int32_t score = 0, subst = 0;
+    check(iqhip_pars_branch_scores(engine, ends, 1, &score, &subst), "iqhip_pars_branch_scores");
+    if (branch_subst) *branch_subst = subst;
+    return score;
+}
+
+int PhyloTree::computeParsimony() {
+    if (!root) throw std::runtime_error("no tree");
+    return computeParsimonyBranch(root->neighbors[0], root);
+}
+
+void PhyloTree::computeAllPartialPars() {
+    needParsimony("computeAllPartialPars");
+    std::vector<iqhip_pars_op> ops;
+    std::vector<PhyloNode *> n1, n2;
+    getBranches(n1, n2);
+    for (size_t k = 0; k < n1.size(); k++) {
+        collectParsOps(n1[k]->findNeighbor(n2[k]), n1[k], ops);
+        collectParsOps(n2[k]->findNeighbor(n1[k]), n2[k], ops);
+    }
+    submitParsOps(ops);
+}
+
+void PhyloTree::getBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2, PhyloNode *node, PhyloNode *dad) const {
+    if (!node) node = root;
+    for (PhyloNeighbor *nb : node->neighbors)
+        if (nb->node != dad) {
+            const bool lower = node->id < nb->node->id;
+            n1.push_back(lower ? node : nb->node);
+            n2.push_back(lower ? nb->node : node);
+            getBranches(n1, n2, nb->node, node);
+        }
+}
+
+int PhyloTree::fixNegativeBranch(bool force) {
+    if (!root) throw std::runtime_error("no tree");
+    // the branches in the reference's recursion order: (node, neighbour) from the root downwards
+    std::vector<PhyloNeighbor *> todo, all;
+    struct Rec {
+        std::vector<PhyloNeighbor *> &all;
+        std::vector<PhyloNode *> from;
+        void go(PhyloNode *node, PhyloNode *dad) {
+            for (PhyloNeighbor *nb : node->neighbors)
+                if (nb->node != dad) {
+                    all.push_back(nb);
+                    from.push_back(node);
+                    go(nb->node, node);
+                }
+        }
+    } rec{all, {}};
+    rec.go(root, nullptr);
+    std::vector<int32_t> ends;
+    for (size_t k = 0; k < all.size(); k++)
+        if (all[k]->length < 0.0 || force) todo.push_back(all[k]);
+    std::vector<int32_t> subst(todo.size());
+    if (!todo.empty()) {
+        computeAllPartialPars();
+        for (size_t k = 0; k < all.size(); k++)
+            if (all[k]->length < 0.0 || force) {
+                ends.push_back(all[k]->pars_slot);
+                ends.push_back(all[k]->node->findNeighbor(rec.from[k])->pars_slot);
+            }
+        check(iqhip_pars_branch_scores(engine, ends.data(), (int)todo.size(), nullptr, subst.data()), "iqhip_pars_branch_scores");
+    }
+    double nsite = 0.0;   // getAlnNSite()
+    for (double f : ptn_freq) nsite += f;
+    int fixed = 0;
+    size_t q = 0;
+    for (size_t k = 0; k < all.size(); k++) {
+        PhyloNeighbor *nb = all[k], *back = nb->node->findNeighbor(rec.from[k]);
+        if (nb->length < 0.0 || force) {
+            const int branch_subst = subst[q++];
+            double branch_length = (branch_subst > 0) ? ((double)branch_subst / nsite) : (1.0 / nsite);
+            const double z = (double)num_states / (num_states - 1);
+            const double x = 1.0 - (z * branch_length);
+            if (x > 0) branch_length = -log(x) / z;
+            if (branch_length < min_branch_length) branch_length = min_branch_length;
+            nb->length = back->length = branch_length;
+            fixed++;
+        }
+        if (nb->length <= 0.0) nb->length = back->length = min_branch_length;
+    }
+    if (fixed) {   // new lengths: every likelihood vector is stale (the parsimony flags stay)
+        for (PhyloNeighbor *nb : all_neighbors) nb->partial_lh_computed &= ~1;
+        current_it = current_it_back = nullptr;
+        theta_computed = false;
+    }
+    return fixed;
+}
+
+int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep> *trace) {
+    if (!engine || dry_run) throw std::runtime_error("computeParsimonyTree needs an attached engine");
+    const int size = leafNum;
+    if (size < 3) throw std::runtime_error("computeParsimonyTree needs at least 3 taxa");
+    {
+        std::vector<char> seen((size_t)size, 0);
+        for (int k = 0; k < size; k++) {
+            if (taxon_order[k] < 0 || taxon_order[k] >= size || seen[(size_t)taxon_order[k]])
+                throw std::runtime_error("computeParsimonyTree: the addition order is not a permutation of the taxa");
+            seen[(size_t)taxon_order[k]] = 1;
+        }
+    }
+    std::vector<std::string> names((size_t)size);
+    for (int k = 0; k < size && k < (int)nodes.size(); k++)
+        if (nodes[(size_t)k]) names[(size_t)k] = nodes[(size_t)k]->name;
+    deleteAllPartialLh();
+    freeTree();
+    nodes.assign((size_t)(2 * size - 2), nullptr);
+    auto new_node = [&](int id) {
+        PhyloNode *nd = new PhyloNode();
+        nd->id = id;
+        if (id < size) nd->name = names[(size_t)id];
+        nodes[(size_t)id] = nd;
+        return nd;
+    };
+    auto add_neighbor = [&](PhyloNode *from, PhyloNode *to) {
+        PhyloNeighbor *nb = new PhyloNeighbor();
+        nb->node = to;
+        nb->length = -1.0;
+        from->neighbors.push_back(nb);
+        all_neighbors.push_back(nb);
+        return nb;
+    };
+    // the initial tree of 3 taxa around node `size`
+    PhyloNode *centre = new_node(size);
+    for (int k = 0; k < 3; k++) {
+        PhyloNode *leaf = new_node(taxon_order[k]);
+        add_neighbor(centre, leaf);
+        add_neighbor(leaf, centre);
+    }
+    root = nodes[(size_t)taxon_order[0]];
+    pars_initialized = false;
+    initializeAllPartialPars();   // (the three vectors that point at the centre take slots; leaves are their own)
+    if (trace) trace->clear();
+    int best_pars_score = 0;
+    std::vector<iqhip_pars_op> ops;
+    for (int cur = 3; cur < size; cur++) {
+        std::vector<PhyloNode *> nodes1, nodes2;
+        getBranches(nodes1, nodes2);
+        // every vector the scan reads, in one submission
+        std::vector<int32_t> ends;
+        for (size_t k = 0; k < nodes1.size(); k++) {
+            PhyloNeighbor *a = nodes2[k]->findNeighbor(nodes1[k]), *c = nodes1[k]->findNeighbor(nodes2[k]);
+            collectParsOps(a, nodes2[k], ops);
+            collectParsOps(c, nodes1[k], ops);
+            ends.push_back(a->pars_slot);
+            ends.push_back(c->pars_slot);
+        }
+        submitParsOps(ops);
+        ParsStep step;
+        int32_t best = 0, best_score = 0;
+        if (trace) step.score.resize(nodes1.size());
+        check(iqhip_pars_insert_scores(engine, ends.data(), (int)nodes1.size(), taxon_order[cur], trace ? step.score.data() : nullptr,
+                                       &best, &best_score),
+              "iqhip_pars_insert_scores");
+        best_pars_score = best_score;
+        if (trace) {
+            for (size_t k = 0; k < nodes1.size(); k++) {
+                step.node1.push_back(nodes1[k]->id);
+                step.node2.push_back(nodes2[k]->id);
+            }
+            step.chosen = best;
+            step.best_score = best_score;
+            trace->push_back(step);
+        }
+        // insert added_node in the middle of target_node -- target_dad (:382-405); its neighbours: the new taxon, then
+        // target_node, then target_dad
+        PhyloNode *target_node = nodes1[(size_t)best], *target_dad = nodes2[(size_t)best];
+        PhyloNode *new_taxon = new_node(taxon_order[cur]), *added_node = new_node(size + cur - 2);
+        PhyloNeighbor *to_taxon = add_neighbor(added_node, new_taxon);
+        PhyloNeighbor *from_taxon = add_neighbor(new_taxon, added_node);
+        PhyloNeighbor *dad_side = target_dad->findNeighbor(target_node), *node_side = target_node->findNeighbor(target_dad);
+        PhyloNeighbor *to_node = add_neighbor(added_node, target_node), *to_dad = add_neighbor(added_node, target_dad);
+        // added_node -> target_node inherits what target_dad saw of target_node, and the other way round
+        to_node->pars_slot = dad_side->pars_slot;
+        to_node->partial_lh_computed = dad_side->partial_lh_computed;
+        to_dad->pars_slot = node_side->pars_slot;
+        to_dad->partial_lh_computed = node_side->partial_lh_computed;
+        dad_side->node = added_node;    // updateNeighbor: in place, the position in the neighbour list is kept
+        node_side->node = added_node;
+        to_taxon->pars_slot = new_taxon->id;
+        // (the reference copies the scan's fitch(a, c) into this vector; here its flag stays down and the next
+        // submission computes it with everything else)
+        from_taxon->pars_slot = pars_next_slot++;
+        dad_side->clearPartialLh();
+        dad_side->pars_slot = pars_next_slot++;
+        node_side->clearPartialLh();
+        node_side->pars_slot = pars_next_slot++;
+        target_dad->clearReversePartialLh(added_node);
+        target_node->clearReversePartialLh(added_node);
+    }
+    nodeNum = 2 * size - 2;
+    branchNum = 2 * size - 3;
+    {   // branch ids in traversal order from the root
+        int next_id = 0;
+        std::vector<PhyloNode *> n1, n2;
+        getBranches(n1, n2);
+        for (size_t k = 0; k < n1.size(); k++) {
+            n1[k]->findNeighbor(n2[k])->id = n2[k]->findNeighbor(n1[k])->id = next_id++;
+        }
+    }
+    current_it = current_it_back = nullptr;
+    theta_computed = false;
+    fixNegativeBranch(true);
+    if (size == 3) best_pars_score = computeParsimony();
+    return best_pars_score;
 }
 
 std::string PhyloTree::supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp) {

@@ -39,7 +39,8 @@ struct PhyloNeighbor {
     PhyloNode *node = nullptr;  // the node this neighbor points TO
     double length = 0.0;
     int id = -1;                // branch id
-    int partial_lh_computed = 0;  // bit0 = likelihood vector valid (phylonode.h:104)
+    int partial_lh_computed = 0;  // bit0 = likelihood vector valid, bit1 = parsimony vector valid (phylonode.h:104)
+    int pars_slot = -1;           // the engine slot that stands for partial_pars (phylonode.h); a leaf's is its taxon id
     uint64_t partial_lh = 0;      // opaque device key; 0 == NULL (phylonode.h:112)
     double lh_scale_factor = 0.0; // phylonode.h:117
     inline void clearPartialLh() { partial_lh_computed = 0; }
@@ -131,6 +132,9 @@ public:
     void attachEngineSharded(const int *device_ids, int ndev, int reduce_mode);
     void attachComm(int nranks, int rank, const void *unique_id);
     void setDryRun(bool on) { dry_run = on; }
+    // sends what changed since the last submission (model, alignment, weights) to the engine now; callers of the raw
+    // engine calls (the thin pars_* wrappers) need it, every member function below does it itself
+    void syncInputs() { pushInputs(); }
     bool heavy_first = true;  // plan order of independent subtrees (see collectPlan)
     // optimizeOneBranch: run the whole Newton-Raphson solve on the device (iqhip_newton_branch)
     // instead of one computeLikelihoodDerv round trip per step; off -> the reference's host loop
@@ -232,6 +236,35 @@ public:
     void computeDist(const double *init, double *dist, double *d2l);
     void pairCounts(const int32_t *pairs, int npairs, double *counts);
 
+    // ---- Fitch parsimony (PhyloTree::setParsimonyKernel, phylotreesse.cpp:34-61; phylotreepars.cpp) on the device.  The
+    //      two kernels are iqhip_pars_update and iqhip_pars_branch_scores; a vector is named by the engine slot in
+    //      PhyloNeighbor::pars_slot, bit 1 of partial_lh_computed is its flag.  Only the parsimony-informative patterns
+    //      are packed, as in the reference (alignment.cpp:624-650).  Trees must be strictly bifurcating (:150).
+    void setParsimonyKernel(LikelihoodKernel lk);   // called by setLikelihoodKernel, as the reference's last line
+    void initializeAllPartialPars();                // phylotree.cpp:590-650: iqhip_pars_init + one slot per directed vector
+    // collects every vector below dad_branch whose flag is down into ONE iqhip_pars_update (as collectPlan does)
+    void computePartialParsimony(PhyloNeighbor *dad_branch, PhyloNode *dad);
+    int computeParsimonyBranch(PhyloNeighbor *dad_branch, PhyloNode *dad, int *branch_subst = nullptr);
+    int computeParsimony();                         // phylotreepars.cpp: the score at the root branch
+    void computeAllPartialPars();                   // :284-294, one submission
+    // phylotree.cpp:2654-2694: all substitution counts from ONE iqhip_pars_branch_scores, then the Jukes-Cantor
+    // correction and the min_branch_length clamp on the host; returns the number of branches set
+    int fixNegativeBranch(bool force);
+    // phylotreepars.cpp:309-426 with the addition order as an input (the reference shuffles): discards the topology and
+    // all likelihood vectors, builds the stepwise-addition tree -- per step one update submission and one
+    // iqhip_pars_insert_scores over getBranches order (mtree.cpp:905-919) -- and runs fixNegativeBranch(true).
+    // Afterwards the tree is ready for initializeAllPartialLh().  Returns the parsimony score.
+    struct ParsStep {
+        std::vector<int> node1, node2, score;   // the branches scanned (ids, node1 < node2) and, with trace, their scores
+        int chosen = -1, best_score = 0;
+    };
+    int computeParsimonyTree(const int *taxon_order, std::vector<ParsStep> *trace = nullptr);
+    void getBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2, PhyloNode *node = nullptr,
+                     PhyloNode *dad = nullptr) const;   // mtree.cpp:905-919
+    std::vector<uint8_t> pars_informative;          // per pattern, computed by initializeAllPartialPars
+    int64_t pars_nsites = 0;                        // informative sites
+    bool pars_initialized = false;
+
     // ---- consumers of the per-pattern lnL (phylotree.cpp:1200-1230, iqtree.cpp:2676-2750) ----------
     // computePatternLikelihood: lnL per pattern of the last computeLikelihood(), scaling events of
     // both ends of current_it put back -- computed on the device, one D2H of nptn doubles
@@ -278,6 +311,17 @@ private:
     double minimizeNewton(double x1, double xguess, double x2, double xacc, double &d2l, int maxNRStep);
     void getPreOrderBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2, PhyloNode *node,
                              PhyloNode *dad);
+
+    typedef void (PhyloTree::*ComputePartialParsimonyType)(PhyloNeighbor *, PhyloNode *);
+    typedef int (PhyloTree::*ComputeParsimonyBranchType)(PhyloNeighbor *, PhyloNode *, int *);
+    ComputePartialParsimonyType computePartialParsimonyPointer = nullptr;
+    ComputeParsimonyBranchType computeParsimonyBranchPointer = nullptr;
+    void computePartialParsimonyHIP(PhyloNeighbor *dad_branch, PhyloNode *dad);
+    int computeParsimonyBranchHIP(PhyloNeighbor *dad_branch, PhyloNode *dad, int *branch_subst);
+    void collectParsOps(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_pars_op> &ops);
+    void submitParsOps(std::vector<iqhip_pars_op> &ops);
+    void needParsimony(const char *what);
+    int pars_next_slot = 0;
 
     AllReduceHook allreduce_hook = nullptr;
     void *allreduce_ctx = nullptr;
