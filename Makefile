@@ -10,7 +10,7 @@ CSRC       := $(PKG)/csrc
 HOST       := $(PKG)/host
 LIBDIR     := $(PKG)/lib
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
-HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_pars.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
+HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_bionj.hip $(CSRC)/kernels_pars.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(HIP_SRCS))
 
 all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/liblh_oracle.so
@@ -25,6 +25,8 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/trav_lds.h include
 $(LIBDIR)/kernels_topo.o: HIPFLAGS += -ffp-contract=off
 # ... and the pairwise distances follow a numpy restatement step for step
 $(LIBDIR)/kernels_dist.o: HIPFLAGS += -ffp-contract=off
+# ... and so does BIONJ
+$(LIBDIR)/kernels_bionj.o: HIPFLAGS += -ffp-contract=off
 
 $(LIBDIR)/libiqhip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS) -ldl

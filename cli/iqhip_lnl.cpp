@@ -21,6 +21,11 @@
 // the reference's RNG stream), branch lengths from fixNegativeBranch(true); it prints "Parsimony score: N (based on M
 // informative sites)", writes <prefix>.parstree and goes on as if that file had been given with -te.  With -te, -pars
 // prints the same line for the given tree.
+// With -bionjtree and no -te it builds the BIONJ starting tree (PhyloTree::computeBioNJ): the distances are computed and
+// written as for -mldist (to <prefix>.mldist unless -mldist names the file), that text is read back -- the tree is a
+// function of the file, as in the reference, whose BioNj::create reads it -- iqhip_bionj runs on the device, the tree is
+// written to <prefix>.bionj with the reference's %10.8f lengths, fixNegativeBranch(false) replaces the negative ones and
+// the run goes on as if the tree had been given with -te.  -te, -parstree and -bionjtree exclude each other.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -47,6 +52,7 @@ static void usage() {
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars]\n"
             "       iqhip_lnl -s <alignment> -parstree -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
+            "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
 }
@@ -58,7 +64,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
     int zb = 0;
-    bool zw = false, au = false, parstree = false, pars = false;
+    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -84,12 +90,14 @@ int main(int argc, char **argv) {
         else if (a == "-mldist") mldist_file = next();
         else if (a == "-parstree") parstree = true;
         else if (a == "-pars") pars = true;
+        else if (a == "-bionjtree") bionjtree = true;
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
     }
-    if (aln_file.empty() || model_str.empty() || (tree_file.empty() != parstree)) { usage(); return 2; }
+    if (aln_file.empty() || model_str.empty() || (int)!tree_file.empty() + (int)parstree + (int)bionjtree != 1) { usage(); return 2; }
     if (prefix.empty()) prefix = aln_file;
+    if (bionjtree && mldist_file.empty()) mldist_file = prefix + ".mldist";
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
     if (alrt > 0 || lbp > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
@@ -106,7 +114,7 @@ int main(int argc, char **argv) {
             printf("Ascertainment bias correction: %d unobservable constant patterns\n", k);
         }
         std::stringstream tss;
-        if (parstree) {   // a star of all taxa: only the taxa matter until computeParsimonyTree builds the topology
+        if (parstree || bionjtree) {   // a star of all taxa: only the taxa matter until the tree is built
             tss << "(";
             for (int i = 0; i < aln.getNSeq(); i++) tss << (i ? "," : "") << aln.seq_names[i] << ":0.1";
             tss << ");";
@@ -169,6 +177,32 @@ int main(int argc, char **argv) {
                 out << std::endl;
             }
             printf("ML distances of %d pairs: %.4f s, printed to %s\n", nseq * (nseq - 1) / 2, sec, mldist_file.c_str());
+        }
+        if (bionjtree) {
+            const int nseq = aln.getNSeq();
+            std::vector<double> dist((size_t)nseq * nseq);
+            {   // the matrix as the file holds it
+                std::ifstream in(mldist_file.c_str());
+                int n_in = 0;
+                if (!(in >> n_in) || n_in != nseq) throw std::runtime_error("cannot read " + mldist_file);
+                std::string name;
+                for (int i = 0; i < nseq; i++) {
+                    if (!(in >> name) || name != aln.seq_names[i]) throw std::runtime_error("unexpected sequence name in " + mldist_file);
+                    for (int j = 0; j < nseq; j++)
+                        if (!(in >> dist[(size_t)i * nseq + j])) throw std::runtime_error("cannot read " + mldist_file);
+                }
+            }
+            auto t0 = std::chrono::steady_clock::now();
+            std::string nwk;
+            tree.computeBioNJ(dist.data(), nullptr, &nwk);
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            std::ofstream out((prefix + ".bionj").c_str());
+            if (!out) throw std::runtime_error("cannot write " + prefix + ".bionj");
+            out << nwk << std::endl;
+            printf("BIONJ tree: %.4f s, printed to %s.bionj\n", sec, prefix.c_str());
+            const int fixed = tree.fixNegativeBranch(false);   // phyloanalysis.cpp:1832-1837
+            printf("%d negative branch lengths fixed\n", fixed);
+            tree.readTreeString(tree.getTreeString(), aln.seq_names);   // from here on what -te does with a tree file
         }
         tree.initializeAllPartialLh();
         tree.clearAllPartialLH();

@@ -472,6 +472,49 @@ int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double 
                          double *dist, double *d2l, int32_t *nsteps);
 int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms);
 
+/* ---- BIONJ (PhyloTree::computeBioNJ, phylotree.cpp:2619-2635; BioNj::create, bionj.h) -- the tree the reference builds from
+ * the distance matrix above before any search.  The engine supplies the device and the stream only: n is free and need not
+ * be the engine's taxon count, and no model or alignment has to be set.
+ * All arithmetic is fp64, indices are 0-based, A is the set of active rows and r = |A|.
+ *   Initialisation: D_ij = (dist[i][j] + dist[j][i]) / 2, the diagonal is ignored.  V = var symmetrised the same way, or
+ *     V = D when var is NULL (the reference reads both from the same file, so V = D is its behaviour).
+ *   While r > 3:
+ *     S_i = sum over j in A, j != i of D_ij                                  (recomputed every step, Compute_sums_Sx)
+ *     Q_xy = (r - 2) D_xy - S_x - S_y for active x > y;  m = min Q
+ *     (a, b) = the first pair, in the reference's scan order (x ascending, then y < x ascending), with Q_xy <= m + 1e-6;
+ *       hence a > b
+ *     vab = V_ab;  la = 0.5 (D_ab + (S_a - S_b) / (r - 2));  lb = 0.5 (D_ab + (S_b - S_a) / (r - 2))
+ *     lambda = 0.5 if vab == 0, else 0.5 + sum over i in A \ {a, b} of (V_bi - V_ai) / (2 (r - 2) vab), clamped to [0, 1]
+ *     for i in A \ {a, b}:  D_ai <- lambda (D_ai - la) + (1 - lambda) (D_bi - lb)
+ *                           V_ai <- lambda V_ai + (1 - lambda) V_bi - lambda (1 - lambda) vab
+ *     steps[k] = {a, b, la, lb, lambda}; b leaves A; r <- r - 1
+ *   Finish: the three rows left are last[0] < last[1] < last[2] = l0, l1, l2 with the lengths
+ *     last_len = {0.5 (D_01 + D_02 - D_12), 0.5 (D_10 + D_12 - D_02), 0.5 (D_21 + D_20 - D_10)}.
+ *   The tree: merging b into a makes sub[a] = "(" sub[a] ":" la "," sub[b] ":" lb ")"; the end is
+ *     "(" sub[l0] ":" .. "," sub[l1] ":" .. "," sub[l2] ":" .. ");" (iqhost_bionj_newick of the host mirror writes it).
+ * DEVIATION from the reference: Best_pair (bionj.h:426-452) keeps a running minimum and replaces it only when
+ *   Q < Qmin - 1e-6, a serial, order-dependent rule.  Its state is 1e300 until the scan reaches the first pair within 1e-6 of
+ *   m; it accepts that pair and can accept nothing after it unless some Q lies in (m + 1e-6, m + 2e-6] -- so the rule above
+ *   picks the same pair whenever no Q lies in that interval.  Unlike a bare arg-min it does not depend on the summation
+ *   order when pairs tie exactly in exact arithmetic (duplicate sequences, star-like data).  The reference computes in
+ *   float; which of several exactly tied pairs it merges first is decided by its rounding noise, so compare split sets with
+ *   their lengths, never Newick strings.
+ * Negative lengths are returned as they come (the reference prints them too).  The same input gives the same bits on every
+ *   run: no floating-point atomics, every sum in a fixed order, the kernels are built without contraction.
+ * The whole merge loop is enqueued on the engine's stream without a host read in between (four launches per step: row
+ *   minima of Q, the pick with la / lb / lambda and the log entry, the update of row and column a, the row sums); the host
+ *   reads the log once.  D, V and a staging matrix (3 n^2 doubles) are allocated per call and freed before it returns.
+ * IQHIP_ERR_INVALID: n < 3, a NULL dist / last / last_len, NULL steps with n > 3, a non-finite off-diagonal entry of dist or
+ *   var, a planning-only engine.  IQHIP_ERR_UNSUPPORTED: sharded engines and communicator ranks; n > 65536 (the pairs no
+ *   longer fit a 32-bit index).  IQHIP_ERR_NOMEM: the three matrices do not fit.  n == 3 runs no merge and returns the
+ *   finish only.
+ * iqhip_debug_bionj_timing: *launches = the kernel launches of the last iqhip_bionj call; with iqhip_timing_enable, *ms =
+ *   the device time (HIP events, milliseconds) from its first launch to its last (otherwise 0). */
+typedef struct iqhip_bionj_step { int32_t a, b; double la, lb, lambda; } iqhip_bionj_step;   /* 32 bytes */
+int iqhip_bionj(iqhip_engine *e, int n, const double *dist /* n*n */, const double *var /* n*n or NULL */,
+                iqhip_bionj_step *steps /* n-3 */, int32_t *last /* 3 */, double *last_len /* 3 */);
+int iqhip_debug_bionj_timing(iqhip_engine *e, double *ms, int64_t *launches);
+
 /* ---- Fitch parsimony (PhyloTree::setParsimonyKernel, phylotreesse.cpp:34-61: computePartialParsimonyPointer and
  * computeParsimonyBranchPointer, the bit-parallel kernels of phylotreepars.cpp:18-282) -- what the reference runs before a
  * tree exists to build its stepwise-addition starting trees (computeParsimonyTree, phylotreepars.cpp:309-426) and, through

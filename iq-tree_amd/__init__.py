@@ -42,6 +42,7 @@ IQHIP_SYMBOLS = [
     "iqhip_pair_counts", "iqhip_pair_distances", "iqhip_debug_pair_timing",
     "iqhip_pars_init", "iqhip_pars_update", "iqhip_pars_branch_scores", "iqhip_pars_insert_scores", "iqhip_pars_fetch", "iqhip_pars_shape",
     "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
+    "iqhip_bionj", "iqhip_debug_bionj_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -99,6 +100,8 @@ TREE_TEST_DTYPE = np.dtype([("logl", np.float64), ("rell_bp", np.float64), ("kh_
                             ("sh_pvalue", np.float64), ("wkh_pvalue", np.float64), ("wsh_pvalue", np.float64),
                             ("elw_value", np.float64), ("rell_confident", np.bool_), ("elw_confident", np.bool_)])
 AU_SCALES = (0.5, 0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3, 1.4)   # performAUTest, phylotesting.cpp:1920
+# bionj / compute_bionj: one record per merge, the layout of struct iqhip_bionj_step (include/iqhip.h; 32 bytes)
+BIONJ_STEP_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("la", np.float64), ("lb", np.float64), ("lambda", np.float64)])
 # test_all_branches: one record per internal branch
 SUPPORT_DTYPE = np.dtype([("node1", np.int32), ("node2", np.int32), ("lh", np.float64, (3,)), ("sh_alrt", np.float64),
                           ("lbp", np.float64), ("abayes", np.float64), ("alrt_stat", np.float64)])
@@ -225,6 +228,8 @@ def libiqhip():
     lib.iqhip_pars_shape.argtypes = [vp, i64p, i64p, C.POINTER(C.c_int)]
     lib.iqhip_debug_pars_levels.argtypes = [C.c_int, C.c_int, u8p, C.POINTER(ParsOp), C.c_int, i32p]
     lib.iqhip_debug_pars_timing.argtypes = [vp, dp, i64p, C.c_int]
+    lib.iqhip_bionj.argtypes = [vp, C.c_int, dp, dp, vp, i32p, dp]
+    lib.iqhip_debug_bionj_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
 
@@ -295,6 +300,8 @@ def libiqhost():
     lib.iqhost_compute_parsimony_tree.argtypes = [vp, ipp, ipp, ipp, C.c_int, ipp, ipp]
     lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
     lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
+    lib.iqhost_bionj_newick.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp, C.POINTER(C.c_char_p), C.c_char_p, C.c_int, ipp]
+    lib.iqhost_compute_bionj.argtypes = [vp, dp, dp, vp, C.POINTER(C.c_int32), dp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
@@ -371,6 +378,35 @@ ERR_INVALID, ERR_UNSUPPORTED = 2, 3
 def _echk(rc):
     if rc != 0:
         raise EngineError(rc, libiqhip().iqhip_last_error().decode())
+
+
+def bionj_newick(steps, last, last_len, names):
+    """The reference's Newick string of a BIONJ step log (PhyloTree::bionjNewick of the host mirror; no device): steps =
+    records of BIONJ_STEP_DTYPE (or rows of (a, b, la, lb, lambda)), one per merge, for len(names) = len(steps) + 3 taxa;
+    last / last_len = the three rows left, ascending, and their lengths.  Lengths are printed with %10.8f."""
+    lib = libiqhost()
+    st = np.asarray(steps)
+    if st.dtype != BIONJ_STEP_DTYPE:
+        rows = np.asarray(steps, dtype=np.float64).reshape(-1, 5)
+        st = np.zeros(rows.shape[0], dtype=BIONJ_STEP_DTYPE)
+        for k, f in enumerate(BIONJ_STEP_DTYPE.names):
+            st[f] = rows[:, k]
+    st = np.ascontiguousarray(st)
+    n = len(names)
+    if st.size != max(0, n - 3):
+        raise HostError("bionj_newick: %d taxa need %d steps, not %d" % (n, max(0, n - 3), st.size))
+    la = np.ascontiguousarray(last, dtype=np.int32)
+    ll = np.ascontiguousarray(last_len, dtype=np.float64)
+    assert la.size == 3 and ll.size == 3
+    arr = (C.c_char_p * max(1, n))(*[str(x).encode() for x in names])
+    need = C.c_int()
+    args = (st.ctypes.data_as(C.c_void_p) if st.size else None, n, la.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(ll), arr)
+    if lib.iqhost_bionj_newick(*args, None, 0, C.byref(need)) != 0:
+        raise HostError(lib.iqhost_last_error().decode())
+    buf = C.create_string_buffer(need.value)
+    if lib.iqhost_bionj_newick(*args, buf, need.value, C.byref(need)) != 0:
+        raise HostError(lib.iqhost_last_error().decode())
+    return buf.value.decode()
 
 
 def _pars_ops(ops):
@@ -847,6 +883,48 @@ class PhyloTree:
         assert ini is None or ini.shape == (n, n)
         self._chk(self.lib.iqhost_compute_dist(self.h, None if ini is None else _dptr(ini), _dptr(dist), _dptr(d2l)))
         return (dist, d2l) if want_d2l else dist
+
+    # ---- BIONJ (include/iqhip.h "BIONJ")
+    def bionj(self, dist, var=None):
+        """iqhip_bionj on the attached engine (it supplies the device and the stream only): dist [n, n], any n >= 3, var
+        None (V = D) or [n, n] -> (steps of BIONJ_STEP_DTYPE [n - 3], last int32[3], last_len float64[3]).  A status other
+        than OK raises EngineError with its code."""
+        d = np.ascontiguousarray(dist, dtype=np.float64)
+        assert d.ndim == 2 and d.shape[0] == d.shape[1]
+        n = d.shape[0]
+        v = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+        assert v is None or v.shape == d.shape
+        steps = np.zeros(max(0, n - 3), dtype=BIONJ_STEP_DTYPE)
+        last, last_len = np.zeros(3, dtype=np.int32), np.zeros(3)
+        _echk(libiqhip().iqhip_bionj(self.engine, n, _dptr(d), None if v is None else _dptr(v),
+                                     steps.ctypes.data_as(C.c_void_p) if steps.size else None,
+                                     last.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(last_len)))
+        return steps, last, last_len
+
+    def bionj_timing(self):
+        """iqhip_debug_bionj_timing -> (device milliseconds of the last bionj call, 0 unless timing is enabled; its launches)"""
+        ms, launches = C.c_double(), C.c_int64()
+        _echk(libiqhip().iqhip_debug_bionj_timing(self.engine, C.byref(ms), C.byref(launches)))
+        return ms.value, launches.value
+
+    def compute_bionj(self, dist=None, var=None):
+        """PhyloTree::computeBioNJ: the BIONJ tree of dist [ntaxa, ntaxa] (None: compute_dist() first) replaces the tree
+        -> (newick, steps, last, last_len); the Newick string is the reference's, leaf labels = the current ones."""
+        n = self.num_leaves
+        d = self.compute_dist() if dist is None else np.ascontiguousarray(dist, dtype=np.float64)
+        v = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+        assert d.shape == (n, n) and (v is None or v.shape == (n, n))
+        steps = np.zeros(max(1, n - 3), dtype=BIONJ_STEP_DTYPE)
+        last, last_len = np.zeros(3, dtype=np.int32), np.zeros(3)
+        cap = 1 << 20
+        while True:
+            buf, need = C.create_string_buffer(cap), C.c_int()
+            self._chk(self.lib.iqhost_compute_bionj(self.h, _dptr(d), None if v is None else _dptr(v),
+                                                    steps.ctypes.data_as(C.c_void_p), last.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    _dptr(last_len), buf, cap, C.byref(need)))
+            if need.value <= cap:
+                return buf.value.decode(), steps[:max(0, n - 3)].copy(), last, last_len
+            cap = need.value   # (a string beyond 1 MB: the call is repeated with room for it and gives the same tree)
 
     def compute_all_partial_lh(self):
         self._chk(self.lib.iqhost_compute_all_partial_lh(self.h))

@@ -473,6 +473,9 @@ struct iqhip_engine {
     double *d_pd_out = nullptr;
     size_t pd_out_cap = 0;
     double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
+    // BIONJ (kernels_bionj.hip): the device memory lives for one call; iqhip_debug_bionj_timing reads these
+    double bj_ms = 0.0;
+    int64_t bj_launches = 0;
     // Fitch parsimony (pars.hip, kernels_pars.hip).  Host copies of what iqhip_pars_init reads: ptn_freq
     // (iqhip_set_ptn_freq), class 0's eigenvectors and tip table (set_model_common).  Vectors [ntaxa + nvectors] of
     // pars_nwords * n words (4 states: word-major, a column is one 16-byte load; 20 / 64 states: plane-major, lanes on

@@ -354,6 +354,29 @@ int iqhost_compute_dist(void *h, const double *init, double *dist, double *d2l) 
 int iqhost_pair_counts(void *h, const int32_t *pairs, int npairs, double *counts) {
     IQHOST_TRY(((PhyloTree *)h)->pairCounts(pairs, npairs, counts));
 }
+// out: NULL or cap bytes for the Newick string; *need = its length + 1 (the string is copied only when it fits)
+int iqhost_bionj_newick(const iqhip_bionj_step *steps, int n, const int32_t *last, const double *last_len, const char **names,
+                        char *out, int cap, int *need) {
+    IQHOST_TRY({
+        if (n < 3 || !names) throw std::runtime_error("bionjNewick: one name per taxon, at least 3 taxa");
+        std::vector<std::string> nm;
+        for (int i = 0; i < n; i++) nm.push_back(names[i]);
+        const std::string s = PhyloTree::bionjNewick(steps, n, last, last_len, nm);
+        if (need) *need = (int)s.size() + 1;
+        if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+// steps: leafNum - 3 entries (at least room for one), last / last_len: 3; the Newick string as above
+int iqhost_compute_bionj(void *h, const double *dist, const double *var, iqhip_bionj_step *steps, int32_t *last, double *last_len,
+                         char *out, int cap, int *need) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::string s;
+        t->computeBioNJ(dist, var, &s, steps, last, last_len);
+        if (need) *need = (int)s.size() + 1;
+        if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
 int iqhost_compute_parsimony(void *h, int *score) { IQHOST_TRY(*score = ((PhyloTree *)h)->computeParsimony()); }
 int iqhost_parsimony_branch(void *h, int a, int b, int *score, int *subst) {
     IQHOST_TRY({

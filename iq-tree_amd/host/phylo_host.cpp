@@ -1355,6 +1355,62 @@ void PhyloTree::pairCounts(const int32_t *pairs, int npairs, double *counts) {
 }
 
 // =========================================================================================
+// BIONJ, phylotree.cpp:2619-2635 over bionj.h (include/iqhip.h "BIONJ")
+// =========================================================================================
+std::string PhyloTree::bionjNewick(const iqhip_bionj_step *steps, int n, const int32_t *last, const double *last_len,
+                                   const std::vector<std::string> &names) {
+    if (n < 3 || (int)names.size() != n) throw std::runtime_error("bionjNewick: one name per taxon, at least 3 taxa");
+    if (!last || !last_len || (n > 3 && !steps)) throw std::runtime_error("bionjNewick: null argument");
+    auto fmt = [](double len) {
+        char buf[400];
+        snprintf(buf, sizeof buf, "%10.8f", len);
+        return std::string(buf);
+    };
+    std::vector<std::string> sub(names);
+    std::vector<char> gone((size_t)n, 0);
+    for (int k = 0; k < n - 3; k++) {
+        const int a = steps[k].a, b = steps[k].b;
+        if (a < 0 || a >= n || b < 0 || b >= n || a == b || gone[(size_t)a] || gone[(size_t)b])
+            throw std::runtime_error("bionjNewick: step " + std::to_string(k) + " merges a row that is not active");
+        sub[(size_t)a] = "(" + sub[(size_t)a] + ":" + fmt(steps[k].la) + "," + sub[(size_t)b] + ":" + fmt(steps[k].lb) + ")";
+        sub[(size_t)b].clear();
+        gone[(size_t)b] = 1;
+    }
+    std::string out = "(";
+    for (int k = 0; k < 3; k++) {
+        const int l = last[k];
+        if (l < 0 || l >= n || gone[(size_t)l] || (k > 0 && l <= last[k - 1]))
+            throw std::runtime_error("bionjNewick: the last three rows must be active and ascending");
+        out += sub[(size_t)l] + ":" + fmt(last_len[k]) + (k < 2 ? "," : ");");
+    }
+    return out;
+}
+
+void PhyloTree::computeBioNJ(const double *dist, const double *var, std::string *newick, iqhip_bionj_step *steps_out,
+                             int32_t *last_out, double *last_len_out) {
+    if (!engine || dry_run) throw std::runtime_error("computeBioNJ needs an attached engine");
+    const int n = leafNum;
+    if (n < 3) throw std::runtime_error("computeBioNJ needs at least 3 taxa");
+    std::vector<std::string> names((size_t)n);
+    for (int k = 0; k < n; k++) {
+        if (k >= (int)nodes.size() || !nodes[(size_t)k]) throw std::runtime_error("computeBioNJ: the taxa are not known yet");
+        names[(size_t)k] = nodes[(size_t)k]->name.empty() ? std::to_string(k) : nodes[(size_t)k]->name;
+    }
+    std::vector<iqhip_bionj_step> steps((size_t)std::max(1, n - 3));
+    int32_t last[3];
+    double last_len[3];
+    check(iqhip_bionj(engine, n, dist, var, steps.data(), last, last_len), "iqhip_bionj");
+    const std::string nwk = bionjNewick(steps.data(), n, last, last_len, names);
+    const bool non_empty_tree = root != nullptr;
+    readTreeString(nwk, names);   // (a tree read with taxon ids as labels has the ids as its names)
+    if (non_empty_tree) initializeAllPartialLh();
+    if (newick) *newick = nwk;
+    if (steps_out) std::copy(steps.begin(), steps.begin() + (n - 3), steps_out);
+    if (last_out) std::copy(last, last + 3, last_out);
+    if (last_len_out) std::copy(last_len, last_len + 3, last_len_out);
+}
+
+// =========================================================================================
 // Fitch parsimony (phylotreepars.cpp; include/iqhip.h "Fitch parsimony")
 // =========================================================================================
 void PhyloTree::needParsimony(const char *what) {

@@ -236,6 +236,19 @@ public:
     void computeDist(const double *init, double *dist, double *d2l);
     void pairCounts(const int32_t *pairs, int npairs, double *counts);
 
+    // ---- BIONJ (PhyloTree::computeBioNJ, phylotree.cpp:2619-2635, over BioNj::create) on the device: one iqhip_bionj on
+    //      dist (and var, or nullptr for V = D), leafNum * leafNum each; the step log becomes the reference's Newick string
+    //      (bionjNewick, names = the current leaf labels), which replaces the tree through readTreeString -- as the reference
+    //      reads its .bionj file back -- followed by initializeAllPartialLh() when there was a tree before.  Lengths may be
+    //      negative: fixNegativeBranch(false) is the caller's next step, as in the reference.
+    //      steps_out (leafNum - 3), last_out (3), last_len_out (3): optional copies of what iqhip_bionj returned.
+    void computeBioNJ(const double *dist, const double *var, std::string *newick = nullptr, iqhip_bionj_step *steps_out = nullptr,
+                      int32_t *last_out = nullptr, double *last_len_out = nullptr);
+    // pure host: merging b into a makes sub[a] = "(" sub[a] ":" la "," sub[b] ":" lb ")", the end is
+    // "(" sub[l0] ":" .. "," sub[l1] ":" .. "," sub[l2] ":" .. ");", every length printed with %10.8f (bionj.h:741,752,526)
+    static std::string bionjNewick(const iqhip_bionj_step *steps, int n, const int32_t *last, const double *last_len,
+                                   const std::vector<std::string> &names);
+
     // ---- Fitch parsimony (PhyloTree::setParsimonyKernel, phylotreesse.cpp:34-61; phylotreepars.cpp) on the device.  The
     //      two kernels are iqhip_pars_update and iqhip_pars_branch_scores; a vector is named by the engine slot in
     //      PhyloNeighbor::pars_slot, bit 1 of partial_lh_computed is its flag.  Only the parsimony-informative patterns

@@ -1,5 +1,6 @@
 """Create / use / destroy engines repeatedly and watch the device's free memory (hipMemGetInfo)."""
 import ctypes as C, importlib, os, sys
+import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
 pkg = g.load_package(); synth = importlib.import_module("iqtree_amd.synth")
@@ -11,6 +12,9 @@ def free_mb():
 cases = [(4, 0, synth.gtr_model(), 30000), (20, 1, synth.random_reversible_model(20, 3, ncat=4), 3000),
          (20, 1, synth.random_reversible_model(20, 3, ncat=4), 9500),   # (>= 8192 patterns: cherry tables and their pair engine)
          (20, 1, synth.mixture_model(20, 3, 5, ncat=4), 3000), (64, 2, synth.random_reversible_model(64, 4, alpha=None, ncat=1), 2000)]
+_rng = np.random.default_rng(5)
+_A = _rng.uniform(0.05, 1.0, (300, 300))
+bionj_dist = (_A + _A.T) / 2   # iqhip_bionj allocates three n x n matrices per call and frees them before it returns
 base = None
 for rep in range(6):
     for n, st_type, model, P in cases:
@@ -23,6 +27,7 @@ for rep in range(6):
         if not hasattr(model, "classes"):
             t.evaluate_nnis_batch()
         t.set_boot_samples(freq[None, :].astype("float32")); t.compute_rell()
+        t.bionj(bionj_dist)
         t.close()
     f = free_mb()
     if base is None: base = f
