@@ -21,6 +21,11 @@
 // the reference's RNG stream), branch lengths from fixNegativeBranch(true); it prints "Parsimony score: N (based on M
 // informative sites)", writes <prefix>.parstree and goes on as if that file had been given with -te.  With -te, -pars
 // prints the same line for the given tree.
+// -sprrad R (1 .. 10) after -parstree or -pars runs the parsimony SPR search of radius R on that tree
+// (PhyloTree::optimizeParsimonySPR: per round every prune point is scanned on the device and the best move is applied) and
+// prints "Parsimony score after SPR: N (K rounds)" below the first line, K counting the round that found nothing;
+// <prefix>.parstree then holds the improved tree.  Without -sprrad nothing changes (the reference's default radius of 6 is
+// not applied on its own).
 // With -bionjtree and no -te it builds the BIONJ starting tree (PhyloTree::computeBioNJ): the distances are computed and
 // written as for -mldist (to <prefix>.mldist unless -mldist names the file), that text is read back -- the tree is a
 // function of the file, as in the reference, whose BioNj::create reads it -- iqhip_bionj runs on the device, the tree is
@@ -50,8 +55,8 @@ static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
-            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars]\n"
-            "       iqhip_lnl -s <alignment> -parstree -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
+            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]]\n"
+            "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
@@ -63,7 +68,7 @@ int main(int argc, char **argv) {
     int dev = 0, reps = 0, alrt = 0, lbp = 0;
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
-    int zb = 0;
+    int zb = 0, sprrad = 0;
     bool zw = false, au = false, parstree = false, pars = false, bionjtree = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -91,6 +96,10 @@ int main(int argc, char **argv) {
         else if (a == "-parstree") parstree = true;
         else if (a == "-pars") pars = true;
         else if (a == "-bionjtree") bionjtree = true;
+        else if (a == "-sprrad") {
+            sprrad = atoi(next().c_str());
+            if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
+        }
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
@@ -99,6 +108,7 @@ int main(int argc, char **argv) {
     if (prefix.empty()) prefix = aln_file;
     if (bionjtree && mldist_file.empty()) mldist_file = prefix + ".mldist";
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
+    if (sprrad > 0 && !parstree && !pars) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
     if (alrt > 0 || lbp > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
@@ -147,6 +157,12 @@ int main(int argc, char **argv) {
             const int score = tree.computeParsimonyTree(order.data());
             const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             printf("Parsimony score: %d (based on %lld informative sites)\n", score, (long long)tree.pars_nsites);
+            if (sprrad > 0) {   // the SPR rounds that follow the additions in the reference's default starting tree
+                std::vector<PhyloTree::SprRound> rounds;
+                const int improved = tree.optimizeParsimonySPR(sprrad, -1, &rounds);
+                tree.fixNegativeBranch(true);
+                printf("Parsimony score after SPR: %d (%d rounds)\n", improved, (int)rounds.size());
+            }
             const std::string nwk = tree.getTreeString();
             std::ofstream out((prefix + ".parstree").c_str());
             if (!out) throw std::runtime_error("cannot write " + prefix + ".parstree");
@@ -156,6 +172,17 @@ int main(int argc, char **argv) {
         } else if (pars) {
             const int score = tree.computeParsimony();
             printf("Parsimony score: %d (based on %lld informative sites)\n", score, (long long)tree.pars_nsites);
+            if (sprrad > 0) {   // improve the given tree; its branch lengths are merged / split where a move cuts
+                std::vector<PhyloTree::SprRound> rounds;
+                const int improved = tree.optimizeParsimonySPR(sprrad, -1, &rounds);
+                printf("Parsimony score after SPR: %d (%d rounds)\n", improved, (int)rounds.size());
+                const std::string nwk = tree.getTreeString();
+                std::ofstream out((prefix + ".parstree").c_str());
+                if (!out) throw std::runtime_error("cannot write " + prefix + ".parstree");
+                out << nwk << std::endl;
+                printf("Improved tree printed to %s.parstree\n", prefix.c_str());
+                tree.readTreeString(nwk, aln.seq_names);
+            }
         }
         if (!mldist_file.empty()) {
             const int nseq = aln.getNSeq();

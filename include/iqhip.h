@@ -573,6 +573,46 @@ int iqhip_debug_pars_levels(int ntaxa, int nvectors, const uint8_t *valid /* nve
                             int nops, int32_t *level);
 int iqhip_debug_pars_timing(iqhip_engine *e, double *ms /* 2 */, int64_t *counts /* 4 */, int reset);
 
+/* ---- Parsimony SPR scan (the scan inside pllComputeRandomizedStepwiseAdditionParsimonyTree's SPR rounds,
+ * pll/fastDNAparsimony.c:1169-1427 rearrangeParsimony / addTraverseParsimony / testInsertParsimony): the score of every
+ * regraft position within a radius, for many prune points, in ONE launch over the vectors that iqhip_pars_update left.
+ *
+ * A job is one prune point: `subtree` = the slot of the pruned subtree's directed vector S, and nsteps steps from
+ * steps[first_step] in depth-first pre-order.  Step k of a job (parent is relative to the job):
+ *   U_k = V(side)                         when parent < 0 (depth 0: the far end of the branch the pruning merged)
+ *   U_k = fitch(U_parent, V(side))        otherwise (depth = the parent's + 1), score column U_parent + V(side) + popcount(cost)
+ *   score_k = sum_w (U_k.score + V(target).score + S.score + popcount(w(U_k, V(target))) + popcount(~OR_i(m_i & S_i))),
+ *             m = fitch(U_k, V(target)), unless flags has IQHIP_PARS_SPR_NO_SCORE
+ * -- iqhip_pars_insert_scores' formula with a subtree in the place of the tip, plus the subtree's own score: the exact Fitch
+ * length of the tree with S regrafted into that branch.  U_k is, in the pruned tree, the directed vector of everything on
+ * the prune-point side of the target branch; V(side) and V(target) are vectors of the unpruned tree that do not contain S
+ * and are read as stored.  The parent of a step must be the MOST RECENT earlier step of the job one level up, so that a
+ * stack indexed by depth holds every U that is still needed; depth <= IQHIP_PARS_SPR_MAX_RADIUS.  The U never leave the
+ * chip: only scores are written.
+ * score (nsteps or NULL): -1 at NO_SCORE steps and at steps that belong to no job.  best_step[j] / best_score[j]: the
+ * FIRST minimum over job j's scored steps in step order, as an index within the job (-1 and INT32_MAX when none is
+ * scored).  *best_job: the first job in job order that holds the global minimum (-1 when nothing is scored).  All sums are
+ * integer, so the results are exact and the same on every run.
+ * iqhip_debug_pars_spr_check: the validation that iqhip_pars_spr_scan runs before it launches anything, alone (no engine,
+ *   no device): every slot in [0, ntaxa + nvectors) and a tip or marked valid; the step ranges of the jobs inside
+ *   [0, nsteps) and disjoint; 0 <= parent < k or parent < 0, the stack rule, the depth bound; no unknown flag.  depth:
+ *   nsteps entries or NULL (-1 at steps of no job).
+ * njobs == 0 succeeds and launches nothing.  Refusals as for the other iqhip_pars_* calls; anything the check finds is
+ *   IQHIP_ERR_INVALID.
+ * iqhip_debug_pars_spr_timing: since the last reset, *ms = the device time of the scan launches (while iqhip_timing_enable
+ *   is on), counts = {launches, steps scored}. */
+enum { IQHIP_PARS_SPR_NO_SCORE = 1 };
+#define IQHIP_PARS_SPR_MAX_RADIUS 10
+typedef struct iqhip_pars_spr_step { int32_t parent, side, target, flags; } iqhip_pars_spr_step;
+typedef struct iqhip_pars_spr_job { int32_t subtree, first_step, nsteps, _pad; } iqhip_pars_spr_job;
+int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jobs, int njobs, const iqhip_pars_spr_step *steps,
+                        int nsteps, int32_t *score /* nsteps or NULL */, int32_t *best_step /* njobs */,
+                        int32_t *best_score /* njobs */, int32_t *best_job);
+int iqhip_debug_pars_spr_check(int ntaxa, int nvectors, const uint8_t *valid /* nvectors or NULL */,
+                               const iqhip_pars_spr_job *jobs, int njobs, const iqhip_pars_spr_step *steps, int nsteps,
+                               int32_t *depth /* nsteps or NULL */);
+int iqhip_debug_pars_spr_timing(iqhip_engine *e, double *ms /* 1 */, int64_t *counts /* 2 */, int reset);
+
 /* Host -> device (tests; SPR/NNI code that fills a buffer on the host). */
 int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
                          const int16_t *scale_num);

@@ -42,6 +42,7 @@ IQHIP_SYMBOLS = [
     "iqhip_pair_counts", "iqhip_pair_distances", "iqhip_debug_pair_timing",
     "iqhip_pars_init", "iqhip_pars_update", "iqhip_pars_branch_scores", "iqhip_pars_insert_scores", "iqhip_pars_fetch", "iqhip_pars_shape",
     "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
+    "iqhip_pars_spr_scan", "iqhip_debug_pars_spr_check", "iqhip_debug_pars_spr_timing",
     "iqhip_bionj", "iqhip_debug_bionj_timing",
 ]
 
@@ -228,6 +229,9 @@ def libiqhip():
     lib.iqhip_pars_shape.argtypes = [vp, i64p, i64p, C.POINTER(C.c_int)]
     lib.iqhip_debug_pars_levels.argtypes = [C.c_int, C.c_int, u8p, C.POINTER(ParsOp), C.c_int, i32p]
     lib.iqhip_debug_pars_timing.argtypes = [vp, dp, i64p, C.c_int]
+    lib.iqhip_pars_spr_scan.argtypes = [vp, vp, C.c_int, vp, C.c_int, i32p, i32p, i32p, i32p]
+    lib.iqhip_debug_pars_spr_check.argtypes = [C.c_int, C.c_int, u8p, vp, C.c_int, vp, C.c_int, i32p]
+    lib.iqhip_debug_pars_spr_timing.argtypes = [vp, dp, i64p, C.c_int]
     lib.iqhip_bionj.argtypes = [vp, C.c_int, dp, dp, vp, i32p, dp]
     lib.iqhip_debug_bionj_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
@@ -298,6 +302,9 @@ def libiqhost():
     lib.iqhost_pars_nsites.restype = C.c_int64
     lib.iqhost_get_branches.argtypes = [vp, ipp, C.c_int]
     lib.iqhost_compute_parsimony_tree.argtypes = [vp, ipp, ipp, ipp, C.c_int, ipp, ipp]
+    lib.iqhost_collect_spr_jobs.argtypes = [vp, C.c_int, ipp, C.c_int, ipp, ipp, C.c_int, ipp, ipp]
+    lib.iqhost_apply_spr_move.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.iqhost_optimize_parsimony_spr.argtypes = [vp, C.c_int, C.c_int, ipp, ipp, C.c_int, ipp]
     lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
     lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
     lib.iqhost_bionj_newick.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp, C.POINTER(C.c_char_p), C.c_char_p, C.c_int, ipp]
@@ -427,6 +434,35 @@ def pars_levels(ntaxa, nvectors, ops, valid=None):
     _echk(libiqhip().iqhip_debug_pars_levels(int(ntaxa), int(nvectors), None if v is None else v.ctypes.data_as(C.POINTER(C.c_uint8)),
                                             arr, n, lev.ctypes.data_as(C.POINTER(C.c_int32))))
     return lev[:n]
+
+
+PARS_SPR_NO_SCORE = 1        # include/iqhip.h IQHIP_PARS_SPR_NO_SCORE
+PARS_SPR_MAX_RADIUS = 10
+
+
+def _spr_rows(rows, what):
+    """rows of 4 int32 as the structs iqhip_pars_spr_job (subtree, first_step, nsteps[, 0]) / iqhip_pars_spr_step (parent,
+    side, target[, flags]); a missing fourth column is 0"""
+    a = np.asarray(rows, dtype=np.int32)
+    a = a.reshape(-1, a.shape[-1] if a.ndim == 2 and a.size else 4)
+    if a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((a.shape[0], 1), np.int32)], axis=1)
+    assert a.shape[1] == 4, what
+    return np.ascontiguousarray(a)
+
+
+def debug_pars_spr_check(ntaxa, nvectors, jobs, steps, valid=None):
+    """iqhip_debug_pars_spr_check: the validation of an iqhip_pars_spr_scan program -> the depth of every step (-1 at steps
+    of no job); jobs: rows of (subtree, first_step, nsteps), steps: rows of (parent, side, target, flags); valid: None or
+    nvectors flags of the slots written so far; no device needed"""
+    jb, st = _spr_rows(jobs, "jobs"), _spr_rows(steps, "steps")
+    depth = np.zeros(max(1, st.shape[0]), dtype=np.int32)
+    v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    assert v is None or v.size == nvectors
+    _echk(libiqhip().iqhip_debug_pars_spr_check(int(ntaxa), int(nvectors), None if v is None else v.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               jb.ctypes.data_as(C.c_void_p), jb.shape[0], st.ctypes.data_as(C.c_void_p),
+                                               st.shape[0], depth.ctypes.data_as(C.POINTER(C.c_int32))))
+    return depth[:st.shape[0]]
 
 
 LK_EIGEN, LK_EIGEN_SSE, LK_EIGEN_HIP = 0, 1, 2
@@ -1045,6 +1081,63 @@ class PhyloTree:
         ms, ln = (C.c_double * 2)(), (C.c_int64 * 4)()
         _echk(libiqhip().iqhip_debug_pars_timing(self.engine, ms, ln, int(reset)))
         return dict(update_ms=ms[0], scan_ms=ms[1], update_launches=ln[0], scan_launches=ln[1], ops=ln[2], branches=ln[3])
+
+    # ---- parsimony SPR search (include/iqhip.h "Parsimony SPR scan"; PhyloTree::collectSprJobs / optimizeParsimonySPR)
+    def pars_spr_scan(self, jobs, steps, want_scores=True):
+        """iqhip_pars_spr_scan: jobs = rows of (subtree, first_step, nsteps), steps = rows of (parent, side, target, flags)
+        -> (score[nsteps] or None, best_step[njobs], best_score[njobs], best_job)"""
+        jb, st = _spr_rows(jobs, "jobs"), _spr_rows(steps, "steps")
+        i32p = C.POINTER(C.c_int32)
+        sc = np.zeros(max(1, st.shape[0]), dtype=np.int32) if want_scores else None
+        bs, bsc = np.zeros(max(1, jb.shape[0]), dtype=np.int32), np.zeros(max(1, jb.shape[0]), dtype=np.int32)
+        bj = C.c_int32()
+        _echk(libiqhip().iqhip_pars_spr_scan(self._pars_engine(), jb.ctypes.data_as(C.c_void_p), jb.shape[0],
+                                            st.ctypes.data_as(C.c_void_p), st.shape[0], None if sc is None else sc.ctypes.data_as(i32p),
+                                            bs.ctypes.data_as(i32p), bsc.ctypes.data_as(i32p), C.byref(bj)))
+        return (None if sc is None else sc[:st.shape[0]]), bs[:jb.shape[0]], bsc[:jb.shape[0]], bj.value
+
+    def collect_spr_jobs(self, radius):
+        """PhyloTree::collectSprJobs -> (jobs[njobs, 4], steps[nsteps, 4], moves[nsteps, 5] = (prune, subtree, node1, node2,
+        depth)): one job per internal node and neighbour, its steps the branches within `radius` of the merged branch"""
+        nj, ns = C.c_int(), C.c_int()
+        self._chk(self.lib.iqhost_collect_spr_jobs(self.h, int(radius), None, 0, None, None, 0, C.byref(nj), C.byref(ns)))
+        jobs = np.zeros((max(1, nj.value), 4), dtype=np.int32)
+        steps = np.zeros((max(1, ns.value), 4), dtype=np.int32)
+        moves = np.zeros((max(1, ns.value), 5), dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        self._chk(self.lib.iqhost_collect_spr_jobs(self.h, int(radius), jobs.ctypes.data_as(ip), jobs.shape[0], steps.ctypes.data_as(ip),
+                                                   moves.ctypes.data_as(ip), steps.shape[0], C.byref(nj), C.byref(ns)))
+        return jobs[:nj.value], steps[:ns.value], moves[:ns.value]
+
+    def apply_spr_move(self, prune, subtree, node1, node2):
+        """PhyloTree::applySprMove: cut the subtree at node `subtree` off its neighbour `prune` and regraft it, with node
+        `prune`, into the branch node1 -- node2"""
+        self._chk(self.lib.iqhost_apply_spr_move(self.h, int(prune), int(subtree), int(node1), int(node2)))
+
+    def optimize_parsimony_spr(self, radius=6, max_rounds=None, trace=False):
+        """PhyloTree::optimizeParsimonySPR: rounds of (all vectors, one SPR scan of every prune point within `radius`, the
+        best move applied) until no move lowers the score or max_rounds moves -> score, or with trace (score, [per round
+        dict(score_before, job, step, score, steps_scored, move=(prune, subtree, node1, node2), applied)])"""
+        score, n = C.c_int(), C.c_int()
+        mr = -1 if max_rounds is None else int(max_rounds)
+        if not trace:
+            self._chk(self.lib.iqhost_optimize_parsimony_spr(self.h, int(radius), mr, C.byref(score), None, 0, None))
+            return score.value
+        cap = 4096
+        rows = np.zeros((cap, 10), dtype=np.int32)
+        self._chk(self.lib.iqhost_optimize_parsimony_spr(self.h, int(radius), mr, C.byref(score), rows.ctypes.data_as(C.POINTER(C.c_int)),
+                                                         cap, C.byref(n)))
+        if n.value > cap:
+            raise HostError("optimize_parsimony_spr: more than %d rounds; only the first ones were traced" % cap)
+        out = [dict(score_before=int(r[0]), job=int(r[1]), step=int(r[2]), score=int(r[3]), steps_scored=int(r[4]),
+                    move=tuple(int(x) for x in r[5:9]), applied=bool(r[9])) for r in rows[:n.value]]
+        return score.value, out
+
+    def pars_spr_timing(self, reset=True):
+        """iqhip_debug_pars_spr_timing -> {scan_ms, launches, steps_scored} since the last reset"""
+        ms, ln = (C.c_double * 1)(), (C.c_int64 * 2)()
+        _echk(libiqhip().iqhip_debug_pars_spr_timing(self.engine, ms, ln, int(reset)))
+        return dict(scan_ms=ms[0], launches=ln[0], steps_scored=ln[1])
 
     def set_branch_bounds(self, lo, hi):
         self._chk(self.lib.iqhost_set_branch_bounds(self.h, lo, hi))

@@ -500,6 +500,8 @@ struct iqhip_engine {
     size_t pars_masks_cap = 0;
     double pars_ms[2] = {0.0, 0.0};     // iqhip_debug_pars_timing: update, scan (while timing is enabled)
     int64_t pars_counts[4] = {0, 0, 0, 0};   // launches of the updates and of the scans, ops updated, branches scanned
+    double pars_spr_ms = 0.0;           // iqhip_debug_pars_spr_timing: the SPR scan launches (while timing is enabled) ...
+    int64_t pars_spr_counts[2] = {0, 0};   // ... their number and the steps scored
     int32_t *d_batch_rows = nullptr;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     size_t batch_rows_cap = 0;
     double *d_result_own = nullptr, *d_result = nullptr;
@@ -1069,6 +1071,10 @@ hipError_t launch_pars_tips(iqhip_engine *e, const int32_t *d_site_ptn);
 hipError_t launch_pars_update(iqhip_engine *e, const iqhip_pars_op *d_ops, const int32_t *d_lev_start, int nlev);
 // d_out: score [nbranch] ++ subst [nbranch]; taxon >= 0: the insertion scan, which also writes {best, best_score} behind them
 hipError_t launch_pars_branch(iqhip_engine *e, const int32_t *d_ends, int nbranch, int taxon, int32_t *d_out, int *nlaunches);
+// the SPR scan (kernels_spr.hip): d_steps carry the depth in `parent`; d_out = score [nsteps] ++ best_step [njobs] ++
+// best_score [njobs] ++ best_job; max_depth = the deepest step of the launch (sizes the LDS stack)
+hipError_t launch_pars_spr(iqhip_engine *e, const iqhip_pars_spr_job *d_jobs, int njobs, const iqhip_pars_spr_step *d_steps,
+                           int nsteps, int max_depth, int32_t *d_out, int *nlaunches);
 
 // batched branch optimisation (k_newton_batch); d_tasks: device array of NewtonTask (kernels_newton.hip)
 hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,

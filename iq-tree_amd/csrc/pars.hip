@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "iqhip_internal.h"
+#include "pars_spr_check.h"
 
 using namespace iqhip;
 
@@ -75,9 +76,11 @@ static int pars_engine(iqhip_engine *e, const char *what, bool need_init) {
 // HIP events around the launches of a call while iqhip_timing_enable is on
 struct ParsTimer {
     iqhip_engine *e;
-    int which;
+    double *ms;
+    int64_t *launches, *work;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    ParsTimer(iqhip_engine *e_, int which_) : e(e_), which(which_) {}
+    ParsTimer(iqhip_engine *e_, int which) : e(e_), ms(&e_->pars_ms[which]), launches(&e_->pars_counts[which]), work(&e_->pars_counts[2 + which]) {}
+    ParsTimer(iqhip_engine *e_, double *ms_, int64_t *launches_, int64_t *work_) : e(e_), ms(ms_), launches(launches_), work(work_) {}
     hipError_t start() {
         if (!e->timing) return hipSuccess;
         for (auto &v : ev) {
@@ -86,17 +89,15 @@ struct ParsTimer {
         }
         return hipEventRecord(ev[0], e->stream);
     }
-    hipError_t stop(int nlaunches, int64_t work) {
-        e->pars_counts[which] += nlaunches;
-        e->pars_counts[2 + which] += work;
+    hipError_t stop(int nlaunches, int64_t work_done) {
+        *launches += nlaunches;
+        *work += work_done;
         if (!e->timing) return hipSuccess;
         hipError_t s = hipEventRecord(ev[1], e->stream);
         if (s == hipSuccess) s = hipEventSynchronize(ev[1]);
-        float ms = 0.f;
-        if (s == hipSuccess) s = hipEventElapsedTime(&ms, ev[0], ev[1]);
-        if (s == hipSuccess) {
-            e->pars_ms[which] += ms;
-        }
+        float t = 0.f;
+        if (s == hipSuccess) s = hipEventElapsedTime(&t, ev[0], ev[1]);
+        if (s == hipSuccess) *ms += t;
         return s;
     }
     ~ParsTimer() {
@@ -303,6 +304,83 @@ extern "C" int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out) {
     uint32_t total = 0;
     for (size_t w = 0; w < nw; w++) total += sc[w];
     out[nw * n] = total;
+    return IQHIP_OK;
+}
+
+// ---- the SPR scan ---------------------------------------------------------------------------------------------------------
+extern "C" int iqhip_debug_pars_spr_check(int ntaxa, int nvectors, const uint8_t *valid, const iqhip_pars_spr_job *jobs, int njobs,
+                                          const iqhip_pars_spr_step *steps, int nsteps, int32_t *depth) {
+    const std::string err = iqhip::pars_spr_check(ntaxa, nvectors, valid, jobs, njobs, steps, nsteps, depth, nullptr);
+    if (!err.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pars_spr_check: " + err);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jobs, int njobs, const iqhip_pars_spr_step *steps,
+                                   int nsteps, int32_t *score, int32_t *best_step, int32_t *best_score, int32_t *best_job) {
+    int rc = pars_engine(e, "iqhip_pars_spr_scan", true);
+    if (rc) return rc;
+    std::vector<int32_t> depth((size_t)std::max(nsteps, 0));
+    int max_depth = 0;
+    const std::string err = pars_spr_check(e->ntaxa, e->pars_nvec, e->pars_valid.data(), jobs, njobs, steps, nsteps, depth.data(), &max_depth);
+    if (!err.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_pars_spr_scan: " + err);
+    if (best_job) *best_job = -1;
+    if (score) std::fill(score, score + nsteps, -1);
+    if (njobs == 0) return IQHIP_OK;
+    if (nsteps == 0) {   // jobs without steps: nothing to launch
+        for (int j = 0; j < njobs; j++) {
+            if (best_step) best_step[j] = -1;
+            if (best_score) best_score[j] = 0x7fffffff;
+        }
+        return IQHIP_OK;
+    }
+    // one upload from pinned staging: jobs ++ steps (4 words each), the steps with their depth in the place of `parent`
+    const size_t nblob = (size_t)4 * njobs + (size_t)4 * nsteps;
+    const size_t nout = (size_t)nsteps + 2 * (size_t)njobs + 1;
+    const size_t from = score ? 0 : (size_t)nsteps, count = nout - from;
+    HIPCHK(use_device(e));
+    if (nblob > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, nblob, nblob));
+    if (nout > e->pars_out_cap) HIPCHK(regrow(e, &e->d_pars_out, &e->pars_out_cap, nout, nout));
+    HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
+    HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (the staging buffer may still feed the previous update's copy)
+    memcpy(e->h_pars_ops, jobs, sizeof(iqhip_pars_spr_job) * (size_t)njobs);
+    iqhip_pars_spr_step *hs = reinterpret_cast<iqhip_pars_spr_step *>(e->h_pars_ops + (size_t)4 * njobs);
+    int64_t scored = 0;
+    for (int k = 0; k < nsteps; k++) {
+        hs[k] = steps[k];
+        hs[k].parent = depth[(size_t)k];
+        if (depth[(size_t)k] >= 0 && !(steps[k].flags & IQHIP_PARS_SPR_NO_SCORE)) scored++;
+    }
+    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    ParsTimer tm(e, &e->pars_spr_ms, &e->pars_spr_counts[0], &e->pars_spr_counts[1]);
+    int nlaunches = 0;
+    HIPCHK(tm.start());
+    HIPCHK(launch_pars_spr(e, reinterpret_cast<const iqhip_pars_spr_job *>(e->d_pars_int), njobs,
+                           reinterpret_cast<const iqhip_pars_spr_step *>(e->d_pars_int + (size_t)4 * njobs), nsteps, max_depth,
+                           e->d_pars_out, &nlaunches));
+    HIPCHK(tm.stop(nlaunches, scored));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->d_pars_out + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int32_t *res = e->h_pars_out;
+    if (score) {
+        memcpy(score, res, sizeof(int32_t) * (size_t)nsteps);
+        res += nsteps;
+    }
+    if (best_step) memcpy(best_step, res, sizeof(int32_t) * (size_t)njobs);
+    if (best_score) memcpy(best_score, res + njobs, sizeof(int32_t) * (size_t)njobs);
+    if (best_job) *best_job = res[2 * (size_t)njobs];
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_pars_spr_timing(iqhip_engine *e, double *ms, int64_t *counts, int reset) {
+    if (!e || !e->shards.empty() || e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pars_spr_timing: needs a single-device engine");
+    if (ms) *ms = e->pars_spr_ms;
+    for (int k = 0; k < 2; k++)
+        if (counts) counts[k] = e->pars_spr_counts[k];
+    if (reset) {
+        e->pars_spr_ms = 0.0;
+        e->pars_spr_counts[0] = e->pars_spr_counts[1] = 0;
+    }
     return IQHIP_OK;
 }
 

@@ -421,6 +421,67 @@ int iqhost_compute_parsimony_tree(void *h, const int *order, int *score, int *tr
         if (ntrace) *ntrace = rows;
     });
 }
+// jobs / steps: rows of 4 ints as the structs of include/iqhip.h; moves: rows of (prune, subtree, node1, node2, depth).
+// *njobs / *nsteps = how many there are; a buffer is filled only when its cap suffices
+int iqhost_collect_spr_jobs(void *h, int radius, int *jobs, int jobs_cap, int *steps, int *moves, int steps_cap, int *njobs,
+                            int *nsteps) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<iqhip_pars_spr_job> jv;
+        std::vector<iqhip_pars_spr_step> sv;
+        std::vector<PhyloTree::SprMove> mv;
+        t->collectSprJobs(radius, jv, sv, mv);
+        *njobs = (int)jv.size();
+        *nsteps = (int)sv.size();
+        if (jobs && (int)jv.size() <= jobs_cap && !jv.empty()) memcpy(jobs, jv.data(), sizeof(jv[0]) * jv.size());
+        if ((int)sv.size() <= steps_cap)
+            for (size_t k = 0; k < sv.size(); k++) {
+                if (steps) memcpy(steps + 4 * k, &sv[k], sizeof(sv[k]));
+                if (moves) {
+                    int *row = moves + 5 * k;
+                    row[0] = mv[k].prune;
+                    row[1] = mv[k].subtree;
+                    row[2] = mv[k].node1;
+                    row[3] = mv[k].node2;
+                    row[4] = mv[k].depth;
+                }
+            }
+    });
+}
+int iqhost_apply_spr_move(void *h, int prune, int subtree, int node1, int node2) {
+    IQHOST_TRY({
+        PhyloTree::SprMove mv;
+        mv.prune = prune;
+        mv.subtree = subtree;
+        mv.node1 = node1;
+        mv.node2 = node2;
+        mv.depth = 1;
+        ((PhyloTree *)h)->applySprMove(mv);
+    });
+}
+// trace (optional): rows of (score_before, job, step, score, steps_scored, prune, subtree, node1, node2, applied)
+int iqhost_optimize_parsimony_spr(void *h, int radius, int max_rounds, int *score, int *trace, int trace_cap, int *nrounds) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<PhyloTree::SprRound> rounds;
+        *score = t->optimizeParsimonySPR(radius, max_rounds, &rounds);
+        for (size_t k = 0; k < rounds.size() && trace && (int)k < trace_cap; k++) {
+            const PhyloTree::SprRound &r = rounds[k];
+            int *row = trace + 10 * k;
+            row[0] = r.score_before;
+            row[1] = r.job;
+            row[2] = r.step;
+            row[3] = r.score;
+            row[4] = r.steps_scored;
+            row[5] = r.move.prune;
+            row[6] = r.move.subtree;
+            row[7] = r.move.node1;
+            row[8] = r.move.node2;
+            row[9] = r.applied ? 1 : 0;
+        }
+        if (nrounds) *nrounds = (int)rounds.size();
+    });
+}
 int iqhost_sync_inputs(void *h) { IQHOST_TRY(((PhyloTree *)h)->syncInputs()); }
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {

@@ -1431,12 +1431,16 @@ void PhyloTree::initializeAllPartialPars() {
     for (int64_t p = 0; p < nptn; p++)
         pars_informative[(size_t)p] = rule.isInformative(aln_states.data() + p, leafNum, (size_t)nptn);
     check(iqhip_pars_init(engine, pars_informative.data(), 4 * (leafNum - 1), &pars_nsites), "iqhip_pars_init");
+    assignParsSlots();
+    pars_initialized = true;
+}
+
+void PhyloTree::assignParsSlots() {   // one slot per directed vector that is not a tip's; every parsimony flag goes down
     pars_next_slot = leafNum;
     for (PhyloNeighbor *nb : all_neighbors) {
         nb->pars_slot = nb->node->isLeaf() ? nb->node->id : pars_next_slot++;
         nb->partial_lh_computed &= ~2;
     }
-    pars_initialized = true;
 }
 
 void PhyloTree::collectParsOps(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_pars_op> &ops) {
@@ -1690,6 +1694,163 @@ int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep
     fixNegativeBranch(true);
     if (size == 3) best_pars_score = computeParsimony();
     return best_pars_score;
+}
+
+// ---- parsimony SPR search ------------------------------------------------------------------------------------------------
+void PhyloTree::collectSprJobs(int radius, std::vector<iqhip_pars_spr_job> &jobs, std::vector<iqhip_pars_spr_step> &steps,
+                               std::vector<SprMove> &moves) {
+    if (!root) throw std::runtime_error("no tree");
+    if (radius < 1 || radius > IQHIP_PARS_SPR_MAX_RADIUS) throw std::runtime_error("collectSprJobs: radius outside 1 .. 10");
+    if (!pars_initialized) {
+        if (engine && !dry_run) initializeAllPartialPars();
+        else assignParsSlots();
+    }
+    jobs.clear();
+    steps.clear();
+    moves.clear();
+    struct Walk {
+        int radius, first;
+        PhyloNode *p, *s;
+        std::vector<iqhip_pars_spr_step> &steps;
+        std::vector<SprMove> &moves;
+        // the branches beyond node a (reached from dad); step `parent` holds everything on dad's side of dad -- a
+        void go(PhyloNode *a, PhyloNode *dad, int parent, int depth) {
+            if (a->isLeaf() || depth > radius) return;
+            PhyloNeighbor *kid[2] = {nullptr, nullptr};
+            int nkid = 0;
+            for (PhyloNeighbor *nb : a->neighbors)
+                if (nb->node != dad) {
+                    if (nkid == 2) throw std::runtime_error("parsimony needs a strictly bifurcating tree");
+                    kid[nkid++] = nb;
+                }
+            if (nkid != 2) throw std::runtime_error("parsimony needs a strictly bifurcating tree");
+            for (int c = 0; c < 2; c++) {
+                const int k = (int)steps.size() - first;
+                steps.push_back(iqhip_pars_spr_step{parent, kid[1 - c]->pars_slot, kid[c]->pars_slot, 0});
+                moves.push_back(SprMove{p->id, s->id, a->id, kid[c]->node->id, depth});
+                go(kid[c]->node, a, k, depth + 1);
+            }
+        }
+    };
+    for (PhyloNode *p : nodes) {
+        if (!p || p->isLeaf()) continue;
+        if (p->degree() != 3) throw std::runtime_error("parsimony needs a strictly bifurcating tree");
+        for (int i = 0; i < 3; i++) {
+            PhyloNeighbor *to_s = p->neighbors[(size_t)i], *to_q1 = p->neighbors[(size_t)(i == 0 ? 1 : 0)],
+                          *to_q2 = p->neighbors[(size_t)(i == 2 ? 1 : 2)];
+            PhyloNode *q1 = to_q1->node, *q2 = to_q2->node;
+            const int first = (int)steps.size();
+            Walk w{radius, first, p, to_s->node, steps, moves};
+            steps.push_back(iqhip_pars_spr_step{-1, to_q2->pars_slot, to_q1->pars_slot, 0});
+            moves.push_back(SprMove{p->id, to_s->node->id, q1->id, q2->id, 0});
+            // (q1 is reached over the merged branch: its far side is q2, and p itself is not q1's neighbour any more)
+            w.go(q1, p, 0, 1);
+            const int second = (int)steps.size() - first;
+            steps.push_back(iqhip_pars_spr_step{-1, to_q1->pars_slot, to_q2->pars_slot, IQHIP_PARS_SPR_NO_SCORE});
+            moves.push_back(SprMove{p->id, to_s->node->id, q2->id, q1->id, 0});
+            w.go(q2, p, second, 1);
+            const int n = (int)steps.size() - first;
+            if (n == 2) {   // two leaves beyond p: nowhere to go
+                steps.resize((size_t)first);
+                moves.resize((size_t)first);
+                continue;
+            }
+            jobs.push_back(iqhip_pars_spr_job{to_s->pars_slot, first, n, 0});
+        }
+    }
+}
+
+void PhyloTree::applySprMove(const SprMove &mv) {
+    const int nn = (int)nodes.size();
+    auto node_of = [&](int id) -> PhyloNode * {
+        if (id < 0 || id >= nn || !nodes[(size_t)id]) throw std::runtime_error("applySprMove: no such node");
+        return nodes[(size_t)id];
+    };
+    PhyloNode *p = node_of(mv.prune), *s = node_of(mv.subtree), *a = node_of(mv.node1), *b = node_of(mv.node2);
+    if (p->degree() != 3 || !p->findNeighbor(s)) throw std::runtime_error("applySprMove: the subtree does not hang at the prune node");
+    PhyloNeighbor *to_q[2] = {nullptr, nullptr};
+    int nq = 0;
+    for (PhyloNeighbor *nb : p->neighbors)
+        if (nb->node != s) to_q[nq++] = nb;
+    PhyloNode *q1 = to_q[0]->node, *q2 = to_q[1]->node;
+    // the target: a branch of the tree as it stands that neither touches the prune node nor lies inside the pruned subtree
+    // (every branch of the pruned tree but the merged one); everything is checked before anything changes
+    PhyloNeighbor *a_b = a->findNeighbor(b), *b_a = b->findNeighbor(a);
+    if (a == p || b == p || !a_b || !b_a) throw std::runtime_error("applySprMove: the target is not a branch of the pruned tree");
+    {
+        std::vector<std::pair<PhyloNode *, PhyloNode *>> todo{{s, p}};
+        while (!todo.empty()) {
+            PhyloNode *x = todo.back().first, *dad = todo.back().second;
+            todo.pop_back();
+            if (x == a || x == b) throw std::runtime_error("applySprMove: the target lies inside the pruned subtree");
+            for (PhyloNeighbor *nb : x->neighbors)
+                if (nb->node != dad) todo.push_back({nb->node, x});
+        }
+    }
+    deleteAllPartialLh();   // (topology change: every likelihood vector and every parsimony flag)
+    // merge q1 -- p -- q2 into q1 -- q2 (in place: the positions in the neighbour lists are kept)
+    PhyloNeighbor *q1_p = q1->findNeighbor(p), *q2_p = q2->findNeighbor(p);
+    const double merged = to_q[0]->length + to_q[1]->length;
+    q1_p->node = q2;
+    q2_p->node = q1;
+    q1_p->length = q2_p->length = merged;
+    // split a -- b with p
+    const double half = a_b->length * 0.5;
+    a_b->node = p;
+    b_a->node = p;
+    to_q[0]->node = a;
+    to_q[1]->node = b;
+    a_b->length = b_a->length = to_q[0]->length = to_q[1]->length = half;
+    {   // branch ids in traversal order from the root
+        int next_id = 0;
+        std::vector<PhyloNode *> n1, n2;
+        getBranches(n1, n2);
+        for (size_t k = 0; k < n1.size(); k++) n1[k]->findNeighbor(n2[k])->id = n2[k]->findNeighbor(n1[k])->id = next_id++;
+    }
+    assignParsSlots();   // (a neighbour that pointed at a leaf may point at an internal node now, and the other way round)
+    current_it = current_it_back = nullptr;
+    theta_computed = false;
+}
+
+int PhyloTree::optimizeParsimonySPR(int radius, int max_rounds, std::vector<SprRound> *trace) {
+    if (!engine || dry_run) throw std::runtime_error("optimizeParsimonySPR needs an attached engine");
+    if (radius < 1 || radius > IQHIP_PARS_SPR_MAX_RADIUS) throw std::runtime_error("optimizeParsimonySPR: radius outside 1 .. 10");
+    if (trace) trace->clear();
+    std::vector<iqhip_pars_spr_job> jobs;
+    std::vector<iqhip_pars_spr_step> steps;
+    std::vector<SprMove> moves;
+    std::vector<int32_t> score, best_step, best_score;
+    int current = -1;
+    for (int round = 0; max_rounds < 0 || round < max_rounds; round++) {
+        computeAllPartialPars();
+        collectSprJobs(radius, jobs, steps, moves);
+        if (jobs.empty()) break;   // (4 taxa or fewer branches than a move needs)
+        score.resize(steps.size());
+        best_step.resize(jobs.size());
+        best_score.resize(jobs.size());
+        int32_t best_job = -1;
+        check(iqhip_pars_spr_scan(engine, jobs.data(), (int)jobs.size(), steps.data(), (int)steps.size(), score.data(),
+                                  best_step.data(), best_score.data(), &best_job),
+              "iqhip_pars_spr_scan");
+        SprRound r;
+        r.score_before = score[(size_t)jobs[0].first_step];
+        for (const iqhip_pars_spr_job &job : jobs)   // every scored root step is the tree as it stands
+            if (score[(size_t)job.first_step] != r.score_before)
+                throw std::runtime_error("optimizeParsimonySPR: the prune points disagree about the score of the current tree");
+        for (int32_t v : score) r.steps_scored += v >= 0;
+        if (best_job < 0) throw std::runtime_error("optimizeParsimonySPR: nothing was scored");
+        r.job = best_job;
+        r.step = best_step[(size_t)best_job];
+        r.score = best_score[(size_t)best_job];
+        r.move = moves[(size_t)jobs[(size_t)best_job].first_step + (size_t)r.step];
+        r.applied = r.score < r.score_before;
+        if (r.applied && r.move.depth < 1) throw std::runtime_error("optimizeParsimonySPR: a root step beats the current tree");
+        current = r.applied ? r.score : r.score_before;
+        if (r.applied) applySprMove(r.move);
+        if (trace) trace->push_back(r);
+        if (!r.applied) break;
+    }
+    return current >= 0 ? current : computeParsimony();
 }
 
 std::string PhyloTree::supportLabel(double sh_alrt, double lbp, bool with_sh, bool with_lbp) {

@@ -272,6 +272,38 @@ public:
         int chosen = -1, best_score = 0;
     };
     int computeParsimonyTree(const int *taxon_order, std::vector<ParsStep> *trace = nullptr);
+    // ---- parsimony SPR search (the SPR rounds of pllComputeRandomizedStepwiseAdditionParsimonyTree,
+    //      pll/fastDNAparsimony.c:1857-1942 over rearrangeParsimony / addTraverseParsimony / testInsertParsimony,
+    //      :1169-1427) on iqhip_pars_spr_scan.
+    // DEVIATION from the reference: PLL visits the nodes one after the other and applies the first node's best improvement
+    // at once; here EVERY prune point of the tree is scanned against the same tree in one launch and the single best move
+    // (the first minimum in job and step order) is applied per round.  Both end in a tree that no SPR within the radius
+    // improves; the trees may differ.
+    struct SprMove {
+        int prune = -1, subtree = -1;   // the subtree at node `subtree` seen from its neighbour `prune` is cut off ...
+        int node1 = -1, node2 = -1;     // ... and regrafted, together with node `prune`, into the branch node1 -- node2
+        int depth = 0;                  // 0: the branch the pruning merged (node1, node2 = prune's other neighbours)
+    };
+    // one job per (internal node p ascending, neighbour s of p in neighbour order): p's other neighbours q1, q2; two root
+    // steps for the merged branch (the first scored: the current tree; the second NO_SCORE), the first followed by the walk
+    // outward from q1, the second by the walk from q2, to depth <= radius (depth 1 = the branches next to the merged
+    // branch: addTraverseParsimony with mintrav = 1, maxtrav = radius).  moves[k] = what step k stands for.  Jobs without a
+    // step of depth >= 1 are left out.  Needs no device: without an initialised parsimony state the slots are assigned here.
+    void collectSprJobs(int radius, std::vector<iqhip_pars_spr_job> &jobs, std::vector<iqhip_pars_spr_step> &steps,
+                        std::vector<SprMove> &moves);
+    struct SprRound {
+        int score_before = 0, job = -1, step = -1, score = 0, steps_scored = 0;
+        SprMove move;
+        bool applied = false;
+    };
+    // per round: computeAllPartialPars (one update submission), collectSprJobs, ONE iqhip_pars_spr_scan; the scan's global
+    // first minimum is applied on the host tree when it is below the current score (it then has depth >= 1: every scored
+    // root step is the current tree, which is also checked), else the search stops.  max_rounds < 0: until no move improves.
+    // The last trace entry of a converged search is the round that found nothing (applied = false).  Returns the score;
+    // all likelihood vectors are dropped when a move is applied, branch lengths are split / merged (fixNegativeBranch(true)
+    // gives parsimony lengths), node ids stay.
+    int optimizeParsimonySPR(int radius, int max_rounds = -1, std::vector<SprRound> *trace = nullptr);
+    void applySprMove(const SprMove &mv);   // prune-and-regraft on the host tree, reusing node `prune`
     void getBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2, PhyloNode *node = nullptr,
                      PhyloNode *dad = nullptr) const;   // mtree.cpp:905-919
     std::vector<uint8_t> pars_informative;          // per pattern, computed by initializeAllPartialPars
@@ -334,6 +366,7 @@ private:
     void collectParsOps(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_pars_op> &ops);
     void submitParsOps(std::vector<iqhip_pars_op> &ops);
     void needParsimony(const char *what);
+    void assignParsSlots();
     int pars_next_slot = 0;
 
     AllReduceHook allreduce_hook = nullptr;
