@@ -1,7 +1,6 @@
 // engine.hip -- host side of libiqhip.so: device memory, key->slab map, submissions and the
 // extern "C" entry points declared in include/iqhip.h.  There is NO CPU fallback in this
 // library: every compute entry point launches HIP kernels or fails with a status.
-#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -246,37 +245,23 @@ extern "C" void iqhip_destroy(iqhip_engine *e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->pair) iqhip_destroy(e->pair);   // (runs on this engine's stream, which it does not own)
     e->pair = nullptr;
-    if (e->d_cherry_tab) hipFree(e->d_cherry_tab);
     comm_destroy(e);
-    if (e->d_result_dev) hipFree(e->d_result_dev);
-    if (e->d_nstate) hipFree(e->d_nstate);
-    if (e->d_bstates) hipFree(e->d_bstates);
-    if (e->d_bsc) hipFree(e->d_bsc);
-    if (e->h_nstate) hipHostFree(e->h_nstate);
     if (e->stream) hipStreamSynchronize(e->stream);
     for (auto &s : e->slabs) {
         if (s.plh) hipFree(s.plh);
         if (s.sc) hipFree(s.sc);
     }
-    void *ptrs[] = {e->d_states, e->d_freq, e->d_invar, e->d_model, e->d_ops, e->d_slab,
-                    e->d_theta, e->d_pattern_lh, e->d_leaf_tab, e->dummy.plh, e->dummy.sc, e->d_newton_partials,
-                    e->d_newton_barrier, e->d_newton_posts, e->d_fold_ticket, e->d_fold_flags, e->d_ptn_scaled, e->d_boot, e->d_img, e->d_theta_batch, e->d_batch_partials,
-                    e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks, e->d_batch_posts, e->d_sweep_len,
-                    e->d_ptnlh, e->d_bt_rows, e->d_bt_part, e->d_bt_sums, e->d_bt_out, e->d_batch_rows,
-                    e->d_freq_prefix, e->d_tt_var, e->d_tt_dbl, e->d_tt_int,
-                    e->d_pd_tiles, e->d_pd_counts, e->d_pd_coef, e->d_pd_init, e->d_pd_out,
-                    e->d_pars_vec, e->d_pars_score, e->d_pars_int, e->d_pars_out, e->d_pars_masks};
+    // (every DevBuf of the engine frees itself when the engine is deleted below)
+    void *ptrs[] = {e->d_states, e->d_freq, e->d_invar, e->d_ops, e->d_theta, e->d_pattern_lh, e->d_leaf_tab, e->dummy.plh,
+                    e->dummy.sc, e->d_newton_partials, e->d_newton_barrier, e->d_newton_posts, e->d_fold_ticket,
+                    e->d_fold_flags, e->d_ptn_scaled, e->d_boot, e->d_ptnlh, e->d_freq_prefix, e->d_sweep_desc,
+                    e->d_cherry_tab, e->d_result_dev, e->d_nstate};
     for (void *p : ptrs)
         if (p) hipFree(p);
-    if (e->h_ops) hipHostFree(e->h_ops);
-    for (int32_t *h : {e->h_pars_ops, e->h_pars_ends, e->h_pars_out})
+    void *pinned[] = {e->h_ops, e->h_nstate, e->h_pars_ops, e->h_pars_ends, e->h_pars_out, e->h_sweep_desc,
+                      e->h_plan_arena, e->h_result, (void *)e->h_done};
+    for (void *h : pinned)
         if (h) hipHostFree(h);
-    if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
-    if (e->h_plan_arena) hipHostFree(e->h_plan_arena);
-    if (e->d_sweep_desc) hipFree(e->d_sweep_desc);
-    if (e->d_sweep_posts) hipFree(e->d_sweep_posts);
-    if (e->h_result) hipHostFree(e->h_result);
-    if (e->h_done) hipHostFree((void *)e->h_done);
     if (e->staging_free) hipEventDestroy(e->staging_free);
     for (auto &p : e->tev) {
         hipEventDestroy(p.first);
@@ -562,18 +547,19 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
                     Ui4[(size_t)ks * 64 + l] = inv_evec[(size_t)row * n + k];
                 }
     }
-    if (e->model_cap < total) HIPCHK(regrow(e, &e->d_model, &e->model_cap, total, total));
-    HIPCHK(hipMemcpy(e->d_model, blk.data(), sizeof(double) * total, hipMemcpyHostToDevice));
-    e->d_eval = e->d_model + o_eval;
-    e->d_evec = e->d_model + o_evec;
-    e->d_inv_evec = e->d_model + o_ievec;
-    e->d_rates = e->d_model + o_rates;
-    e->d_props = e->d_model + o_props;
-    e->d_tip = e->d_model + o_tip;
-    e->d_evalc = e->d_model + o_evalc;
-    e->d_tipc = e->d_model + o_tipc;
-    e->d_cls = reinterpret_cast<int *>(e->d_model + o_cls);
-    e->d_aimg = aimg_doubles ? e->d_model + o_aimg : nullptr;
+    HIPCHK(e->d_model.ensure(e, total));
+    double *const d_model = e->d_model.p;
+    HIPCHK(hipMemcpy(d_model, blk.data(), sizeof(double) * total, hipMemcpyHostToDevice));
+    e->d_eval = d_model + o_eval;
+    e->d_evec = d_model + o_evec;
+    e->d_inv_evec = d_model + o_ievec;
+    e->d_rates = d_model + o_rates;
+    e->d_props = d_model + o_props;
+    e->d_tip = d_model + o_tip;
+    e->d_evalc = d_model + o_evalc;
+    e->d_tipc = d_model + o_tipc;
+    e->d_cls = reinterpret_cast<int *>(d_model + o_cls);
+    e->d_aimg = aimg_doubles ? d_model + o_aimg : nullptr;
     e->aimg_doubles = (int)aimg_doubles;
     if (nclass > 1 || (e->n == 20 && !e->mfma_pipelined_ok) || e->wide4) {  // (20 states with a category count that has no
         // pipelined instantiation also run on the mixture kernel: one class; wide DNA reads the generic images, one class too)
@@ -608,8 +594,8 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
             }
         }
         e->img_generic_off = mix_doubles;
-        if (e->img_cap < img.size()) HIPCHK(regrow(e, &e->d_img, &e->img_cap, img.size(), img.size()));
-        HIPCHK(hipMemcpy(e->d_img, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
+        HIPCHK(e->d_img.ensure(e, img.size()));
+        HIPCHK(hipMemcpy(e->d_img.p, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
     }
     // the pipelined kernels hold one eigen-system in registers / LDS: mixtures take the generic kernel,
     // whose plans have a different canonical form -> drop the cached descriptors
@@ -731,9 +717,7 @@ extern "C" int iqhip_set_mixture_model(iqhip_engine *e, int nclass, const int32_
 // submissions (the descriptors come from the planner, plan.hip)
 // ---------------------------------------------------------------------------------------
 int iqhip::ensure_slab_rows(iqhip_engine *e, int nrows) {
-    const int64_t need = (int64_t)nrows * e->ntiles * e->lane_split;
-    if (need <= e->slab_cap) return IQHIP_OK;
-    HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, need, need));
+    HIPCHK(e->d_slab.ensure(e, (size_t)nrows * e->ntiles * e->lane_split));
     return IQHIP_OK;
 }
 
@@ -1198,6 +1182,32 @@ extern "C" int iqhip_fetch_partial(iqhip_engine *e, uint64_t key, double *out) {
     return fetch_vec(e, e->slabs[idx].plh, out);
 }
 
+extern "C" int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
+                                    const int16_t *scale_num) {
+    if (!e || !partial_lh || !scale_num) return fail(IQHIP_ERR_INVALID, "null argument");
+    if (!e->shards.empty()) return sharded::upload_partial(e, key, partial_lh, scale_num);
+    HIPCHK(use_device(e));
+    int idx;
+    int rc = slab_for_key(e, key, true, &idx);
+    if (rc) return rc;
+    const int B = e->block;
+    std::vector<double> tmp((size_t)e->nptn_pad * B, 0.0);
+    if (e->embed2) {
+        const int m = e->n_user, n = e->n;
+        for (int64_t p = 0; p < e->nptn; p++)
+            for (int c = 0; c < e->ncat; c++)
+                for (int i = 0; i < m; i++) tmp[dev_index(e, p, c * n + i)] = partial_lh[((size_t)p * e->ncat + c) * m + i];
+    } else
+    for (int64_t p = 0; p < e->nptn; p++)
+        for (int k = 0; k < B; k++) tmp[dev_index(e, p, k)] = partial_lh[(size_t)p * B + k];
+    std::vector<int16_t> sc((size_t)e->nptn_pad, 0);
+    memcpy(sc.data(), scale_num, sizeof(int16_t) * (size_t)e->nptn);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(e->slabs[idx].plh, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->slabs[idx].sc, sc.data(), sc.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    return IQHIP_OK;
+}
+
 extern "C" int iqhip_fetch_theta(iqhip_engine *e, double *out) {
     if (!e || !out) return fail(IQHIP_ERR_INVALID, "null argument");
     if (!e->shards.empty()) return sharded::fetch_vec(e, 0, true, out);
@@ -1228,743 +1238,6 @@ extern "C" int iqhip_fetch_pattern_lh(iqhip_engine *e, double *out) {
         for (int64_t p = 0; p < nobs; p++) out[p] -= e->pattern_lh_shift;
         for (int64_t p = nobs; p < e->nptn; p++) out[p] = 0.0;
     }
-    return IQHIP_OK;
-}
-
-// ---- consumers of the device-resident pattern lnL (kernels_rell.hip) ---------------------------
-static int scaled_pattern_lh(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b) {
-    const int16_t *sc[2] = {nullptr, nullptr};
-    const iqhip_branch_end ends[2] = {a, b};
-    for (int k = 0; k < 2; k++) {
-        if (ends[k].leaf >= 0) continue;  // leaves carry no scaling events
-        int idx;
-        int rc = slab_for_key(e, ends[k].key, false, &idx);
-        if (rc) return rc;
-        sc[k] = e->slabs[idx].sc;
-    }
-    if (!e->d_ptn_scaled) HIPCHK(hipMalloc((void **)&e->d_ptn_scaled, sizeof(double) * (size_t)e->nptn_pad));
-    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptn_scaled));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *out) {
-    if (!e || !out) return fail(IQHIP_ERR_INVALID, "null argument");
-    if (!e->shards.empty()) return sharded::fetch_pattern_lh(e, out, 1, a, b);
-    HIPCHK(use_device(e));
-    int rc = scaled_pattern_lh(e, a, b);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_ptn_scaled, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_pattern_lh_cat(iqhip_engine *e, double len, double *out) {
-    if (!e || !out) return fail(IQHIP_ERR_INVALID, "null argument");
-    if (!e->shards.empty()) return sharded::pattern_lh_cat(e, len, out);
-    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, "iqhip_pattern_lh_cat needs iqhip_compute_theta first");
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
-    HIPCHK(use_device(e));
-    const size_t count = (size_t)e->nptn * e->ncat;
-    double *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, sizeof(double) * count));
-    hipError_t s = launch_pattern_lh_cat(e, len, d_out);
-    if (s == hipSuccess) s = hipMemcpyAsync(out, d_out, sizeof(double) * count, hipMemcpyDeviceToHost, e->stream);
-    if (s == hipSuccess) s = hipStreamSynchronize(e->stream);
-    hipFree(d_out);
-    if (s != hipSuccess) return fail(IQHIP_ERR_HIP, hipGetErrorString(s));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int nsamples) {
-    if (!e || (nsamples > 0 && !samples) || nsamples < 0) return fail(IQHIP_ERR_INVALID, "bad bootstrap samples");
-    if (nsamples > 16384) return fail(IQHIP_ERR_INVALID, "at most 16384 bootstrap samples");
-    if (!e->shards.empty()) return sharded::set_boot_samples(e, samples, nsamples);
-    HIPCHK(use_device(e));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_boot) HIPCHK(hipFree(e->d_boot));
-    e->d_boot = nullptr;
-    e->nboot = 0;
-    if (nsamples == 0) return IQHIP_OK;
-    const size_t pitch = (size_t)e->nptn_pad;
-    HIPCHK(hipMalloc((void **)&e->d_boot, sizeof(float) * pitch * nsamples));
-    HIPCHK(hipMemset(e->d_boot, 0, sizeof(float) * pitch * nsamples));
-    HIPCHK(hipMemcpy2D(e->d_boot, pitch * sizeof(float), samples, (size_t)e->nptn * sizeof(float),
-                       (size_t)e->nptn * sizeof(float), nsamples, hipMemcpyHostToDevice));
-    e->nboot = nsamples;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_rell_async(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b) {
-    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
-    if (!e->shards.empty())
-        return fail(IQHIP_ERR_UNSUPPORTED, "a sharded engine reduces its results itself: use the synchronous calls");
-    if (e->nboot == 0) return fail(IQHIP_ERR_INVALID, "no bootstrap samples (iqhip_set_boot_samples)");
-    if (e->nboot > e->result_cap) return fail(IQHIP_ERR_INVALID, "result buffer too small for the sample count");
-    HIPCHK(use_device(e));
-    int rc = scaled_pattern_lh(e, a, b);
-    if (rc) return rc;
-    HIPCHK(launch_rell(e, e->d_result));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *rell) {
-    if (!rell) return fail(IQHIP_ERR_INVALID, "null argument");
-    if (e && !e->shards.empty()) return sharded::rell(e, a, b, rell);
-    int rc = iqhip_rell_async(e, a, b);
-    if (rc) return rc;
-    rc = comm_allreduce(e, e->nboot);
-    if (rc) return rc;
-    rc = read_result(e, e->nboot);
-    if (rc) return rc;
-    memcpy(rell, e->h_result, sizeof(double) * (size_t)e->nboot);
-    return IQHIP_OK;
-}
-
-// ---- branch tests (SH-aLRT, local bootstrap): the store of per-pattern log-likelihood rows and its consumers --------
-// (kernels_rell.hip k_ptnlh_rows fills rows from batched tasks, kernels_alrt.hip multiplies them with the sample matrix)
-int iqhip::ptnlh_plain_engine(iqhip_engine *e, const char *what) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines keep no per-pattern store");
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_reserve");
-    if (rc) return rc;
-    if (nrows < 0 || nrows > (1 << 20)) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_reserve: bad row count");
-    HIPCHK(use_device(e));
-    if (nrows <= e->ptnlh_rows) return IQHIP_OK;   // (rows keep their contents while the store does not grow)
-    double *grown = nullptr;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (hipMalloc((void **)&grown, sizeof(double) * (size_t)nrows * e->nptn_pad) != hipSuccess)
-        return fail(IQHIP_ERR_NOMEM, "iqhip_ptnlh_reserve: out of device memory");
-    // (on the engine's stream: a memset on the null stream is not ordered against the kernels that fill rows next)
-    HIPCHK(hipMemsetAsync(grown, 0, sizeof(double) * (size_t)nrows * e->nptn_pad, e->stream));
-    if (e->d_ptnlh)
-        HIPCHK(hipMemcpyAsync(grown, e->d_ptnlh, sizeof(double) * (size_t)e->ptnlh_rows * e->nptn_pad, hipMemcpyDeviceToDevice,
-                              e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_ptnlh) HIPCHK(hipFree(e->d_ptnlh));
-    e->d_ptnlh = grown;
-    e->ptnlh_rows = nrows;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_end a, iqhip_branch_end b) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_put_current");
-    if (rc) return rc;
-    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_put_current: row outside the store (iqhip_ptnlh_reserve)");
-    HIPCHK(use_device(e));
-    const int16_t *sc[2] = {nullptr, nullptr};
-    const iqhip_branch_end ends[2] = {a, b};
-    for (int k = 0; k < 2; k++) {
-        if (ends[k].leaf >= 0) continue;
-        int idx;
-        rc = slab_for_key(e, ends[k].key, false, &idx);
-        if (rc) return rc;
-        sc[k] = e->slabs[idx].sc;
-    }
-    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptnlh + (size_t)row * e->nptn_pad));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_fetch");
-    if (rc) return rc;
-    if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_fetch: null argument");
-    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_fetch: row outside the store");
-    HIPCHK(use_device(e));
-    HIPCHK(hipMemcpyAsync(out, e->d_ptnlh + (size_t)row * e->nptn_pad, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost,
-                          e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-// the distinct rows of a row list in first-appearance order (d_bt_rows[0, M)) and, behind them, every entry's index into
-// that list; the product R = L W^T of the distinct rows ends in d_bt_sums [M][nsamples]
-static int ptnlh_product(iqhip_engine *e, const char *what, const int32_t *rows, int nrows, int nsamples, int *M_out) {
-    if (nsamples < 1 || nsamples > e->nboot)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + (e->nboot == 0 ? ": no bootstrap samples (iqhip_set_boot_samples)"
-                                                                          : ": more replicates than uploaded samples"));
-    std::vector<int32_t> host((size_t)nrows, 0), distinct;
-    std::unordered_map<int32_t, int32_t> seen;
-    for (int i = 0; i < nrows; i++) {
-        if (rows[i] < 0 || rows[i] >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store");
-        auto it = seen.find(rows[i]);
-        if (it == seen.end()) {
-            it = seen.emplace(rows[i], (int32_t)distinct.size()).first;
-            distinct.push_back(rows[i]);
-        }
-        host[i] = it->second;
-    }
-    const int M = (int)distinct.size();
-    distinct.insert(distinct.end(), host.begin(), host.end());
-    HIPCHK(use_device(e));
-    if (distinct.size() > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, distinct.size(), distinct.size()));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source: the copy below must not outlive `distinct`)
-    HIPCHK(hipMemcpyAsync(e->d_bt_rows, distinct.data(), sizeof(int32_t) * distinct.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const int ksplit = alrt_ksplit(e, M, nsamples);
-    const size_t sums = (size_t)M * nsamples, part = sums * ksplit;
-    if (part > e->bt_part_cap) HIPCHK(regrow(e, &e->d_bt_part, &e->bt_part_cap, part, part));
-    if (sums > e->bt_sums_cap) HIPCHK(regrow(e, &e->d_bt_sums, &e->bt_sums_cap, sums, sums));
-    HIPCHK(launch_alrt_product(e, e->d_bt_rows, M, nsamples, ksplit, e->d_bt_part, e->d_bt_sums));
-    *M_out = M;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows, int nsamples, double *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_rell");
-    if (rc) return rc;
-    if (!rows || !out || nrows < 1) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_rell: bad row list");
-    int M = 0;
-    rc = ptnlh_product(e, "iqhip_ptnlh_rell", rows, nrows, nsamples, &M);
-    if (rc) return rc;
-    std::vector<double> sums((size_t)M * nsamples);
-    HIPCHK(hipMemcpyAsync(sums.data(), e->d_bt_sums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    std::unordered_map<int32_t, int> idx;
-    for (int i = 0; i < nrows; i++) {
-        const int k = idx.emplace(rows[i], (int)idx.size()).first->second;
-        memcpy(out + (size_t)i * nsamples, sums.data() + (size_t)k * nsamples, sizeof(double) * (size_t)nsamples);
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const double *lh3, int nbranch, int reps_sh,
-                                  int reps_lbp, iqhip_branch_support *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_branch_tests");
-    if (rc) return rc;
-    if (!rows3 || !lh3 || !out || nbranch < 1 || nbranch > (1 << 24) || reps_sh < 0 || reps_lbp < 0)
-        return fail(IQHIP_ERR_INVALID, "iqhip_branch_tests: bad arguments");
-    const int times = std::max(reps_sh, reps_lbp);
-    int M = 0;
-    rc = ptnlh_product(e, "iqhip_branch_tests", rows3, 3 * nbranch, times, &M);
-    if (rc) return rc;
-    const size_t need = (size_t)7 * nbranch;
-    if (need > e->bt_out_cap) HIPCHK(regrow(e, &e->d_bt_out, &e->bt_out_cap, need, need));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_bt_out, lh3, sizeof(double) * 3 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
-    double *d_res = e->d_bt_out + 3 * (size_t)nbranch;
-    HIPCHK(launch_alrt_stats(e, e->d_bt_rows + M, e->d_bt_out, nbranch, times, e->d_bt_sums, d_res));
-    static_assert(sizeof(iqhip_branch_support) == 4 * sizeof(double), "iqhip_branch_support is four doubles");
-    HIPCHK(hipMemcpyAsync(out, d_res, sizeof(iqhip_branch_support) * (size_t)nbranch, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-// ---- tree topology tests (evaluateTrees / performAUTest, phylotesting.cpp:1916-2442; kernels_topo.hip) ---------------
-extern "C" int iqhip_ptnlh_upload(iqhip_engine *e, int row, const double *in) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_upload");
-    if (rc) return rc;
-    if (!in) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_upload: null argument");
-    if (row < 0 || row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_upload: row outside the store (iqhip_ptnlh_reserve)");
-    HIPCHK(use_device(e));
-    std::vector<double> tmp((size_t)e->nptn_pad, 0.0);
-    memcpy(tmp.data(), in, sizeof(double) * (size_t)e->nptn);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_ptnlh + (size_t)row * e->nptn_pad, tmp.data(), sizeof(double) * tmp.size(), hipMemcpyHostToDevice,
-                          e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-// the int64 inclusive prefix sums of ptn_freq and nsite = their last entry, from the engine's own copy of the frequencies
-static int topo_freq_prefix(iqhip_engine *e, const char *what) {
-    if (e->freq_prefix_valid) return IQHIP_OK;
-    if (!e->aln_set) return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_alignment first");
-    std::vector<double> freq((size_t)e->nptn);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(freq.data(), e->d_freq, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
-    std::vector<int64_t> prefix(freq.size());
-    int64_t total = 0;
-    for (size_t p = 0; p < freq.size(); p++) {
-        const double f = freq[p];
-        if (!(f >= 0.0) || f != floor(f) || f > 9007199254740992.0 || total > (INT64_MAX >> 2) - (int64_t)f)
-            return fail(IQHIP_ERR_INVALID, std::string(what) + ": pattern frequencies must be non-negative integers");
-        total += (int64_t)f;
-        prefix[p] = total;
-    }
-    if (total < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": the alignment has no site");
-    if (!e->d_freq_prefix) HIPCHK(dmalloc(&e->d_freq_prefix, prefix.size()));
-    HIPCHK(hipMemcpy(e->d_freq_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice));
-    e->freq_nsite = total;
-    e->freq_prefix_valid = true;
-    return IQHIP_OK;
-}
-
-// a sample matrix of exactly (exact) or at least nsamples rows, contents undefined
-static int topo_boot_rows(iqhip_engine *e, int nsamples, bool exact) {
-    if (e->d_boot && (exact ? e->nboot == nsamples : e->nboot >= nsamples)) return IQHIP_OK;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_boot) HIPCHK(hipFree(e->d_boot));
-    e->d_boot = nullptr;
-    e->nboot = 0;
-    if (hipMalloc((void **)&e->d_boot, sizeof(float) * (size_t)e->nptn_pad * nsamples) != hipSuccess)
-        return fail(IQHIP_ERR_NOMEM, "bootstrap sample matrix: out of device memory");
-    e->nboot = nsamples;
-    return IQHIP_OK;
-}
-
-static const int64_t kTopoMaxDraws = (int64_t)1 << 24;   // counts above 2^24 are not representable in float
-
-extern "C" int iqhip_gen_boot_samples(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t seed,
-                                      uint32_t stream) {
-    int rc = ptnlh_plain_engine(e, "iqhip_gen_boot_samples");
-    if (rc) return rc;
-    if (nsamples < 1 || nsamples > 16384) return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: 1 .. 16384 bootstrap samples");
-    if (first_replicate < 0 || first_replicate > INT64_MAX - nsamples - 1)
-        return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: bad first replicate");
-    if (ndraws < 0 || ndraws > kTopoMaxDraws)
-        return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: ndraws must be 0 .. 2^24 (a float holds no larger count exactly)");
-    HIPCHK(use_device(e));
-    rc = topo_freq_prefix(e, "iqhip_gen_boot_samples");
-    if (rc) return rc;
-    rc = topo_boot_rows(e, nsamples, true);
-    if (rc) return rc;
-    HIPCHK(launch_topo_gen(e, nsamples, first_replicate, ndraws, topo_stream_key(seed, stream)));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-static int topo_check_rows(iqhip_engine *e, const char *what, const int32_t *rows, int nrows) {
-    for (int i = 0; i < nrows; i++)
-        if (rows[i] < 0 || rows[i] >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store");
-    return IQHIP_OK;
-}
-
-// variances of all pairs of the row list -> host [nrows][nrows] (uses d_bt_rows for the list)
-static int topo_diff_variance(iqhip_engine *e, const char *what, const int32_t *rows, int nrows, double *var) {
-    int rc = topo_freq_prefix(e, what);
-    if (rc) return rc;
-    const size_t nn = (size_t)nrows * nrows;
-    if ((size_t)nrows > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, (size_t)nrows, (size_t)nrows));
-    if (nn > e->tt_var_cap) HIPCHK(regrow(e, &e->d_tt_var, &e->tt_var_cap, nn, nn));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_bt_rows, rows, sizeof(int32_t) * (size_t)nrows, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_topo_diff_variance(e, e->d_bt_rows, nrows, e->d_tt_var));
-    HIPCHK(hipMemcpyAsync(var, e->d_tt_var, sizeof(double) * nn, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ptnlh_diff_variance(iqhip_engine *e, const int32_t *rows, int nrows, double *var) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_diff_variance");
-    if (rc) return rc;
-    if (!rows || !var || nrows < 1 || nrows > 4096) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_diff_variance: bad row list");
-    rc = topo_check_rows(e, "iqhip_ptnlh_diff_variance", rows, nrows);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    return topo_diff_variance(e, "iqhip_ptnlh_diff_variance", rows, nrows, var);
-}
-
-// the 95 % confidence set of phylotesting.cpp:2248-2255 / 2404-2411: trees by decreasing share until the shares pass 0.95;
-// equal shares are taken highest index first (the reference's order among equal shares is its quicksort's)
-static void topo_confidence_set(const std::vector<double> &share, std::vector<int32_t> &in_set) {
-    const int n = (int)share.size();
-    std::vector<int> rank((size_t)n);
-    for (int i = 0; i < n; i++) rank[i] = i;
-    std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return share[a] < share[b]; });
-    in_set.assign((size_t)n, 0);
-    double prob_sum = 0.0;
-    for (int k = n - 1; k >= 0; k--) {
-        in_set[rank[k]] = 1;
-        prob_sum += share[rank[k]];
-        if (prob_sum > 0.95) break;
-    }
-}
-
-extern "C" int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int ntrees, int nsamples, double epsilon,
-                                int weighted, uint64_t tie_seed, iqhip_tree_test *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_tree_tests");
-    if (rc) return rc;
-    if (!rows || !lh || !out || ntrees < 2 || ntrees > 4096 || !(epsilon >= 0.0) || !std::isfinite(epsilon))
-        return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: bad arguments (at least two trees)");
-    if (nsamples < 1 || nsamples > e->nboot)
-        return fail(IQHIP_ERR_INVALID, e->nboot == 0 ? "iqhip_tree_tests: no bootstrap samples (iqhip_gen_boot_samples / iqhip_set_boot_samples)"
-                                                     : "iqhip_tree_tests: more replicates than samples in the matrix");
-    for (int t = 0; t < ntrees; t++)
-        if (!std::isfinite(lh[t])) return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: log-likelihoods must be finite");
-    rc = topo_check_rows(e, "iqhip_tree_tests", rows, ntrees);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    const size_t T = (size_t)ntrees, S = (size_t)nsamples;
-    // phylotesting.cpp:2284-2299, 2308: the tree every tree is compared with in the KH test
-    int orig_max_id = 0, orig_2ndmax_id = -1;
-    double orig_max_lh = lh[0], orig_2ndmax_lh = -DBL_MAX;
-    for (int t = 1; t < ntrees; t++)
-        if (orig_max_lh < lh[t]) {
-            orig_max_lh = lh[t];
-            orig_max_id = t;
-        }
-    for (int t = 0; t < ntrees; t++)
-        if (t != orig_max_id && orig_2ndmax_lh < lh[t]) {
-            orig_2ndmax_lh = lh[t];
-            orig_2ndmax_id = t;
-        }
-    if (orig_2ndmax_id < 0) return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: log-likelihoods out of range");
-    // host staging: doubles lh, avg, w_orig [T each] ++ weights [T][T]; ints kh_id, w_id [T each]
-    std::vector<double> hd(3 * T + (weighted ? T * T : 0), 0.0);
-    std::vector<int32_t> hi(2 * T, -1);
-    for (int t = 0; t < ntrees; t++) {
-        hd[t] = lh[t];
-        hi[t] = t != orig_max_id ? orig_max_id : orig_2ndmax_id;
-    }
-    if (weighted) {
-        // :2327-2352: weights 1 / sqrt(variance of the difference), and per tree the largest weighted difference
-        std::vector<double> var(T * T);
-        rc = topo_diff_variance(e, "iqhip_tree_tests", rows, ntrees, var.data());
-        if (rc) return rc;
-        double *w = hd.data() + 3 * T;
-        for (size_t a = 0; a < T; a++)
-            for (size_t b = a + 1; b < T; b++) w[a * T + b] = w[b * T + a] = 1.0 / sqrt(var[a * T + b]);
-        for (int t = 0; t < ntrees; t++) {
-            double worig_diff = -DBL_MAX;
-            int max_id = -1;
-            for (int t2 = 0; t2 < ntrees; t2++)
-                if (t2 != t) {
-                    const double wdiff = (lh[t2] - lh[t]) * w[(size_t)t * T + t2];
-                    if (wdiff > worig_diff) {
-                        worig_diff = wdiff;
-                        max_id = t2;
-                    }
-                }
-            hd[2 * T + t] = worig_diff;
-            hi[T + t] = max_id;
-        }
-    }
-    int M = 0;
-    rc = ptnlh_product(e, "iqhip_tree_tests", rows, ntrees, nsamples, &M);
-    if (rc) return rc;
-    const size_t ndbl = hd.size() + 3 * S + 6 * T, nint = 2 * T + S;
-    if (ndbl > e->tt_dbl_cap) HIPCHK(regrow(e, &e->d_tt_dbl, &e->tt_dbl_cap, ndbl, ndbl));
-    if (nint > e->tt_int_cap) HIPCHK(regrow(e, &e->d_tt_int, &e->tt_int_cap, nint, nint));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_tt_dbl, hd.data(), sizeof(double) * hd.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_tt_int, hi.data(), sizeof(int32_t) * hi.size(), hipMemcpyHostToDevice, e->stream));
-    TopoTestArgs a;
-    a.sums = e->d_bt_sums;
-    a.idx = e->d_bt_rows + M;
-    a.T = ntrees;
-    a.S = nsamples;
-    a.epsilon = epsilon;
-    a.tie_key = topo_stream_key(tie_seed, 0xB9u);
-    a.lh = e->d_tt_dbl;
-    a.avg = e->d_tt_dbl + T;
-    a.w_orig = e->d_tt_dbl + 2 * T;
-    a.weights = weighted ? e->d_tt_dbl + 3 * T : nullptr;
-    a.max_sh = e->d_tt_dbl + hd.size();
-    a.max_elw = a.max_sh + S;
-    a.sum_l = a.max_elw + S;
-    a.out = a.sum_l + S;
-    a.kh_id = e->d_tt_int;
-    a.w_id = e->d_tt_int + T;
-    a.winner = e->d_tt_int + 2 * T;
-    HIPCHK(launch_topo_tests(e, a));
-    HIPCHK(launch_topo_tree(e, a));
-    std::vector<double> res(6 * T);
-    HIPCHK(hipMemcpyAsync(res.data(), a.out, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    std::vector<double> share(T);
-    std::vector<int32_t> rell_set, elw_set;
-    for (size_t t = 0; t < T; t++) share[t] = res[6 * t];
-    topo_confidence_set(share, rell_set);
-    for (size_t t = 0; t < T; t++) share[t] = res[6 * t + 5];
-    topo_confidence_set(share, elw_set);
-    for (size_t t = 0; t < T; t++) {
-        iqhip_tree_test &o = out[t];
-        o.rell_bp = res[6 * t];
-        o.kh_pvalue = res[6 * t + 1];
-        o.sh_pvalue = res[6 * t + 2];
-        o.wkh_pvalue = res[6 * t + 3];
-        o.wsh_pvalue = res[6 * t + 4];
-        o.elw_value = res[6 * t + 5];
-        o.rell_confident = rell_set[t];
-        o.elw_confident = elw_set[t];
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales,
-                                   int nsamples, uint64_t seed, double *bp) {
-    int rc = ptnlh_plain_engine(e, "iqhip_multiscale_bp");
-    if (rc) return rc;
-    if (!rows || !scales || !bp || ntrees < 2 || ntrees > 4096 || nscales < 1 || nscales > 4096 || nsamples < 1)
-        return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: bad arguments (at least two trees, one scale, one replicate)");
-    rc = topo_check_rows(e, "iqhip_multiscale_bp", rows, ntrees);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    rc = topo_freq_prefix(e, "iqhip_multiscale_bp");
-    if (rc) return rc;
-    std::vector<int64_t> ndraws((size_t)nscales);
-    for (int k = 0; k < nscales; k++) {
-        if (!(scales[k] > 0.0) || !std::isfinite(scales[k])) return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: a scale must be > 0");
-        const double d = round(scales[k] * (double)e->freq_nsite);
-        if (d < 1.0 || d > (double)kTopoMaxDraws)
-            return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: round(scale * nsite) must be 1 .. 2^24 draws");
-        ndraws[k] = (int64_t)d;
-    }
-    // distinct rows in first-appearance order, then every tree's index into them (as ptnlh_product lays d_bt_rows out)
-    std::vector<int32_t> list;
-    std::vector<int32_t> idx((size_t)ntrees);
-    {
-        std::unordered_map<int32_t, int32_t> seen;
-        for (int t = 0; t < ntrees; t++) {
-            auto it = seen.find(rows[t]);
-            if (it == seen.end()) {
-                it = seen.emplace(rows[t], (int32_t)list.size()).first;
-                list.push_back(rows[t]);
-            }
-            idx[t] = it->second;
-        }
-    }
-    const int M = (int)list.size();
-    list.insert(list.end(), idx.begin(), idx.end());
-    // replicates per chunk: the sample matrix stays within 256 MB; IQHIP_BOOT_CHUNK (read per call) overrides.  The K-split
-    // follows from the pattern count and the CU count alone (the budget's chunk, not this call's), so that a (row,
-    // replicate) sum has the same bits whatever the chunk size
-    const int64_t budget = std::max<int64_t>(1, std::min<int64_t>(16384, ((int64_t)256 << 20) / (4 * e->nptn_pad)));
-    const int ksplit = alrt_ksplit(e, M, (int)budget);
-    int64_t chunk = budget;
-    if (const char *bc = getenv("IQHIP_BOOT_CHUNK")) chunk = std::max(1, std::min(16384, atoi(bc)));
-    chunk = std::min<int64_t>(chunk, nsamples);
-    rc = topo_boot_rows(e, (int)chunk, false);
-    if (rc) return rc;
-    const size_t sums = (size_t)M * chunk, part = sums * ksplit, ncount = (size_t)nscales * ntrees;
-    if (list.size() > e->bt_rows_cap) HIPCHK(regrow(e, &e->d_bt_rows, &e->bt_rows_cap, list.size(), list.size()));
-    if (part > e->bt_part_cap) HIPCHK(regrow(e, &e->d_bt_part, &e->bt_part_cap, part, part));
-    if (sums > e->bt_sums_cap) HIPCHK(regrow(e, &e->d_bt_sums, &e->bt_sums_cap, sums, sums));
-    if (ncount > e->tt_int_cap) HIPCHK(regrow(e, &e->d_tt_int, &e->tt_int_cap, ncount, ncount));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_bt_rows, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(e->d_tt_int);
-    HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * ncount, e->stream));
-    for (int k = 0; k < nscales; k++) {
-        const uint64_t key = topo_stream_key(seed, (uint32_t)k);
-        for (int64_t first = 0; first < nsamples; first += chunk) {
-            const int n = (int)std::min<int64_t>(chunk, nsamples - first);
-            HIPCHK(launch_topo_gen(e, n, first, ndraws[k], key));
-            HIPCHK(launch_alrt_product(e, e->d_bt_rows, M, n, ksplit, e->d_bt_part, e->d_bt_sums));
-            HIPCHK(launch_topo_argmax(e, e->d_bt_sums, e->d_bt_rows + M, ntrees, n, d_counts + (size_t)k * ntrees));
-        }
-    }
-    std::vector<uint32_t> counts(ncount);
-    HIPCHK(hipMemcpyAsync(counts.data(), d_counts, sizeof(uint32_t) * ncount, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (size_t i = 0; i < ncount; i++) bp[i] = (double)counts[i] / nsamples;
-    return IQHIP_OK;
-}
-
-// ---- pairwise ML distances (PhyloTree::computeDist, phylotree.cpp:2432-2541; kernels_dist.hip) -----------------------
-static int pair_engine(iqhip_engine *e, const char *what) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines are out of scope (the counts would need an all-reduce)");
-    if (e->n_user != e->n || (e->n != 4 && e->n != 20 && e->n != 64))
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": 4, 20 or 64 states only (no embedded state counts)");
-    if (!e->model_set || !e->aln_set)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_model and iqhip_set_alignment first");
-    if (e->nclass > 1) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": mixture models are out of scope");
-    return IQHIP_OK;
-}
-
-// pairs per chunk: the counts of a chunk stay within 64 MB; IQHIP_PAIR_CHUNK (read per call) overrides
-static int64_t pair_chunk(const iqhip_engine *e, int64_t npairs) {
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * (int64_t)e->n * e->n));
-    if (const char *pc = getenv("IQHIP_PAIR_CHUNK")) chunk = std::max(1, atoi(pc));
-    return std::max<int64_t>(1, std::min(chunk, npairs));
-}
-
-// tiles of 4 x 4 taxa for the m pairs of a chunk: pair k goes to slot k.  Pairs of one block of taxa share a tile, whatever
-// their order in the list; a pair listed twice opens a new tile
-static void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<PairTile> &tiles) {
-    std::unordered_map<uint64_t, size_t> open;
-    for (int64_t k = 0; k < m; k++) {
-        const int i = pairs[2 * k], j = pairs[2 * k + 1];
-        const uint64_t key = ((uint64_t)(i >> 2) << 32) | (uint64_t)(j >> 2);
-        const int cell = (i & 3) * 4 + (j & 3);
-        auto it = open.find(key);
-        if (it == open.end() || tiles[it->second].out[cell] >= 0) {
-            PairTile t;
-            for (int x = 0; x < 4; x++) {
-                t.ra[x] = std::min((i & ~3) + x, ntaxa - 1);
-                t.rb[x] = std::min((j & ~3) + x, ntaxa - 1);
-            }
-            for (int c = 0; c < 16; c++) t.out[c] = -1;
-            open[key] = tiles.size();
-            tiles.push_back(t);
-            it = open.find(key);
-        }
-        tiles[it->second].out[cell] = (int32_t)k;
-    }
-}
-
-extern "C" int iqhip_pair_counts(iqhip_engine *e, const int32_t *pairs, int npairs, double *counts) {
-    int rc = pair_engine(e, "iqhip_pair_counts");
-    if (rc) return rc;
-    if (!pairs || !counts || npairs < 0) return fail(IQHIP_ERR_INVALID, "iqhip_pair_counts: bad pair list");
-    for (int64_t k = 0; k < 2 * (int64_t)npairs; k++)
-        if (pairs[k] < 0 || pairs[k] >= e->ntaxa) return fail(IQHIP_ERR_INVALID, "iqhip_pair_counts: pair index outside [0, ntaxa)");
-    HIPCHK(use_device(e));
-    const size_t nn = (size_t)e->n * e->n;
-    const int64_t chunk = pair_chunk(e, npairs);
-    for (int64_t first = 0; first < npairs; first += chunk) {
-        const int64_t m = std::min<int64_t>(chunk, npairs - first);
-        std::vector<PairTile> tiles;
-        pair_tiles(pairs + 2 * first, m, e->ntaxa, tiles);
-        if (tiles.size() > e->pd_tiles_cap) HIPCHK(regrow(e, &e->d_pd_tiles, &e->pd_tiles_cap, tiles.size(), tiles.size()));
-        if ((size_t)m * nn > e->pd_counts_cap) HIPCHK(regrow(e, &e->d_pd_counts, &e->pd_counts_cap, (size_t)m * nn, (size_t)m * nn));
-        HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source: the copy must not outlive `tiles`)
-        HIPCHK(hipMemcpyAsync(e->d_pd_tiles, tiles.data(), sizeof(PairTile) * tiles.size(), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(launch_pair_counts(e, e->d_pd_tiles, (int)tiles.size(), e->d_pd_counts));
-        HIPCHK(hipMemcpyAsync(counts + (size_t)first * nn, e->d_pd_counts, sizeof(double) * (size_t)m * nn, hipMemcpyDeviceToHost,
-                              e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double x2, double xacc, int max_steps,
-                                    double *dist, double *d2l, int32_t *nsteps) {
-    int rc = pair_engine(e, "iqhip_pair_distances");
-    if (rc) return rc;
-    if (!dist) return fail(IQHIP_ERR_INVALID, "iqhip_pair_distances: null argument");
-    if (!(x1 >= 0.0) || x1 > x2 || !std::isfinite(x2) || !(xacc > 0.0) || max_steps < 1)
-        return fail(IQHIP_ERR_INVALID, "iqhip_pair_distances: bad bounds / tolerance / step count (x1 <= x2, max_steps >= 1)");
-    const int T = e->ntaxa, n = e->n;
-    const int64_t npairs = (int64_t)T * (T - 1) / 2;
-    // the pairs i < j block by block of 4 x 4 taxa, so that the pairs of a tile are neighbours in the list (and in a chunk)
-    std::vector<int32_t> pairs;
-    pairs.reserve((size_t)2 * npairs);
-    for (int I = 0; I < T; I += 4)
-        for (int J = I; J < T; J += 4)
-            for (int i = I; i < std::min(I + 4, T); i++)
-                for (int j = std::max(J, i + 1); j < std::min(J + 4, T); j++) {
-                    pairs.push_back(i);
-                    pairs.push_back(j);
-                }
-    std::vector<double> h_init;
-    if (init) {
-        h_init.resize((size_t)npairs);
-        for (int64_t k = 0; k < npairs; k++) {
-            const double v = init[(size_t)pairs[2 * k] * T + pairs[2 * k + 1]];
-            if (!(v >= 0.0) || !std::isfinite(v)) return fail(IQHIP_ERR_INVALID, "iqhip_pair_distances: an initial distance is negative or not finite");
-            h_init[(size_t)k] = v;
-        }
-    }
-    for (size_t k = 0; k < (size_t)T * T; k++) {
-        dist[k] = 0.0;
-        if (d2l) d2l[k] = 0.0;
-        if (nsteps) nsteps[k] = 0;
-    }
-    if (npairs == 0) return IQHIP_OK;
-    HIPCHK(use_device(e));
-    const size_t nn = (size_t)n * n, n3 = nn * n;
-    const int64_t chunk = pair_chunk(e, npairs);
-    // all tiles up front, chunk by chunk (a chunk's slots start at 0): the chunk loop below makes no host round trip
-    std::vector<PairTile> tiles;
-    std::vector<size_t> tile_first;
-    for (int64_t first = 0; first < npairs; first += chunk) {
-        tile_first.push_back(tiles.size());
-        pair_tiles(pairs.data() + 2 * first, std::min<int64_t>(chunk, npairs - first), T, tiles);
-    }
-    tile_first.push_back(tiles.size());
-    if (tiles.size() > e->pd_tiles_cap) HIPCHK(regrow(e, &e->d_pd_tiles, &e->pd_tiles_cap, tiles.size(), tiles.size()));
-    if ((size_t)chunk * nn > e->pd_counts_cap) HIPCHK(regrow(e, &e->d_pd_counts, &e->pd_counts_cap, (size_t)chunk * nn, (size_t)chunk * nn));
-    if (n3 > e->pd_coef_cap) HIPCHK(regrow(e, &e->d_pd_coef, &e->pd_coef_cap, n3, n3));
-    if ((size_t)npairs > e->pd_init_cap) HIPCHK(regrow(e, &e->d_pd_init, &e->pd_init_cap, (size_t)npairs, (size_t)npairs));
-    if ((size_t)4 * npairs > e->pd_out_cap) HIPCHK(regrow(e, &e->d_pd_out, &e->pd_out_cap, (size_t)4 * npairs, (size_t)4 * npairs));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_pd_tiles, tiles.data(), sizeof(PairTile) * tiles.size(), hipMemcpyHostToDevice, e->stream));
-    if (init) HIPCHK(hipMemcpyAsync(e->d_pd_init, h_init.data(), sizeof(double) * h_init.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_pair_coef(e, e->d_pd_coef));
-    PairSolveArgs a;
-    a.counts = e->d_pd_counts;
-    a.coef = e->d_pd_coef;
-    a.eval = e->d_eval;
-    a.rates = e->d_rates;
-    a.props = e->d_props;
-    a.init = init ? e->d_pd_init : nullptr;
-    a.out = e->d_pd_out;
-    a.n = n;
-    a.ncat = e->ncat;
-    a.max_steps = max_steps;
-    a.x1 = x1;
-    a.x2 = x2;
-    a.xacc = xacc;
-    // iqhip_timing_enable: device time of the count and the solve launches (HIP events), summed over the chunks
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (e->timing)
-        for (int k = 0; k < 3; k++) HIPCHK(hipEventCreate(&ev[k]));
-    e->pd_counts_ms = e->pd_solve_ms = 0.0;
-    int64_t first = 0;
-    for (size_t c = 0; first < npairs; c++, first += chunk) {
-        const int m = (int)std::min<int64_t>(chunk, npairs - first);
-        a.first_pair = first;
-        if (e->timing) HIPCHK(hipEventRecord(ev[0], e->stream));
-        HIPCHK(launch_pair_counts(e, e->d_pd_tiles + tile_first[c], (int)(tile_first[c + 1] - tile_first[c]), e->d_pd_counts));
-        if (e->timing) HIPCHK(hipEventRecord(ev[1], e->stream));
-        HIPCHK(launch_pair_solve(e, a, m));
-        if (e->timing) {
-            HIPCHK(hipEventRecord(ev[2], e->stream));
-            HIPCHK(hipEventSynchronize(ev[2]));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            e->pd_counts_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-            e->pd_solve_ms += ms;
-        }
-    }
-    for (int k = 0; k < 3; k++)
-        if (ev[k]) hipEventDestroy(ev[k]);
-    std::vector<double> out((size_t)4 * npairs);
-    HIPCHK(hipMemcpyAsync(out.data(), e->d_pd_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    int worst = 0;
-    for (int64_t k = 0; k < npairs; k++) {
-        const size_t ij = (size_t)pairs[2 * k] * T + pairs[2 * k + 1], ji = (size_t)pairs[2 * k + 1] * T + pairs[2 * k];
-        const NewtonResult r(out.data() + 4 * k);
-        dist[ij] = dist[ji] = r.optx;
-        if (d2l) d2l[ij] = d2l[ji] = r.d2l;
-        if (nsteps) nsteps[ij] = nsteps[ji] = r.nsteps;
-        if (r.status && !worst) worst = r.status;
-    }
-    return newton_status(worst);   // (minimizeNewton's two nrerror() exits; the matrices are filled all the same)
-}
-
-extern "C" int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms) {
-    if (!e || !e->shards.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pair_timing: needs a single-device engine");
-    if (counts_ms) *counts_ms = e->pd_counts_ms;
-    if (solve_ms) *solve_ms = e->pd_solve_ms;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
-                                    const int16_t *scale_num) {
-    if (!e || !partial_lh || !scale_num) return fail(IQHIP_ERR_INVALID, "null argument");
-    if (!e->shards.empty()) return sharded::upload_partial(e, key, partial_lh, scale_num);
-    HIPCHK(use_device(e));
-    int idx;
-    int rc = slab_for_key(e, key, true, &idx);
-    if (rc) return rc;
-    const int B = e->block;
-    std::vector<double> tmp((size_t)e->nptn_pad * B, 0.0);
-    if (e->embed2) {
-        const int m = e->n_user, n = e->n;
-        for (int64_t p = 0; p < e->nptn; p++)
-            for (int c = 0; c < e->ncat; c++)
-                for (int i = 0; i < m; i++) tmp[dev_index(e, p, c * n + i)] = partial_lh[((size_t)p * e->ncat + c) * m + i];
-    } else
-    for (int64_t p = 0; p < e->nptn; p++)
-        for (int k = 0; k < B; k++) tmp[dev_index(e, p, k)] = partial_lh[(size_t)p * B + k];
-    std::vector<int16_t> sc((size_t)e->nptn_pad, 0);
-    memcpy(sc.data(), scale_num, sizeof(int16_t) * (size_t)e->nptn);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(e->slabs[idx].plh, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->slabs[idx].sc, sc.data(), sc.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     return IQHIP_OK;
 }
 

@@ -279,6 +279,20 @@ __host__ __device__ inline void newton_update(NewtonState &s, double pdf, double
     if (fabs(s.dx) < s.xacc || s.j == s.max_steps) { s.result = s.rts_old; s.done = 1; return; }
 }
 
+// A device scratch buffer of an engine that grows on demand.  ensure(e, count): nothing while count <= cap; otherwise the
+// buffer is replaced as regrow (below) replaces one -- the engine's stream drains, the old contents are dropped, cap stays
+// 0 while an allocation has failed, and a planning-only engine gets a fake address.  The destructor frees the memory (never
+// a fake address): iqhip_destroy makes the device current and drains the stream before it deletes the engine.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr; size_t cap = 0;   // cap in elements
+    bool fake = false;                // p is a planning-only engine's fake address
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p && !fake) hipFree(p); }
+    hipError_t ensure(iqhip_engine *e, size_t count);
+};
+
 }  // namespace iqhip
 
 struct iqhip_engine {
@@ -366,8 +380,7 @@ struct iqhip_engine {
     // per-call buffers
     iqhip::DevOp *d_ops = nullptr;
     int ops_cap = 0;
-    double *d_slab = nullptr;   // wave partials [nvals][nwaves]
-    int64_t slab_cap = 0;
+    iqhip::DevBuf<double> d_slab;   // wave partials [nvals][nwaves]
     unsigned int *d_fold_ticket = nullptr;  // folded reduction (FoldArgs): ticket + per-row flags, zero between launches
     int *d_fold_flags = nullptr;
     bool fold_reduce = false;               // IQHIP_FOLD=1: the last kernel of a submission sums the slab itself (measured
@@ -426,52 +439,42 @@ struct iqhip_engine {
     int aimg_doubles = 0;
     double *d_tipc = nullptr;    // [state_unknown+1][ncat][n]
     int *d_cls = nullptr;        // [ncat]
-    double *d_img = nullptr;     // mixture A images: mix20 layout, then the generic kernel's (engine.hip)
-    size_t img_generic_off = 0, img_cap = 0;
-    double *d_model = nullptr;   // the block all model arrays below point into (set_model_common)
-    size_t model_cap = 0;
+    iqhip::DevBuf<double> d_img;     // mixture A images: mix20 layout, then the generic kernel's (engine.hip)
+    size_t img_generic_off = 0;
+    iqhip::DevBuf<double> d_model;   // the block all model arrays above point into (set_model_common)
     bool mfma_pipelined_ok = false;  // (n, ncat) has a pipelined instantiation (used when nclass == 1)
     // UFBoot / RELL (kernels_rell.hip): scaled per-pattern lnL and the bootstrap sample matrix
     double *d_ptn_scaled = nullptr;
     float *d_boot = nullptr;  // [nboot][nptn_pad], zero padded
     int nboot = 0;
-    // branch tests (SH-aLRT / local bootstrap): the store of per-pattern log-likelihood rows [ptnlh_rows][nptn_pad] and the
-    // scratch of iqhip_branch_tests / iqhip_ptnlh_rell (row lists, K-split partial products, combined sums, results)
+    // branch tests (SH-aLRT / local bootstrap, ptnlh.hip): the store of per-pattern log-likelihood rows [ptnlh_rows][nptn_pad]
+    // and the scratch of iqhip_branch_tests / iqhip_ptnlh_rell (row lists, K-split partial products, combined sums, results)
     double *d_ptnlh = nullptr;
     int ptnlh_rows = 0;
-    int32_t *d_bt_rows = nullptr;       // [distinct rows] ++ [3 * nbranch indices into them]
-    size_t bt_rows_cap = 0;
-    double *d_bt_part = nullptr;        // [ksplit][M][nsamples]
-    size_t bt_part_cap = 0;
-    double *d_bt_sums = nullptr;        // [M][nsamples]
-    size_t bt_sums_cap = 0;
-    double *d_bt_out = nullptr;         // lh3 [3 * nbranch] ++ iqhip_branch_support [nbranch]
-    size_t bt_out_cap = 0;
+    struct {
+        iqhip::DevBuf<int32_t> rows;    // [distinct rows] ++ [3 * nbranch indices into them]
+        iqhip::DevBuf<double> part;     // [ksplit][M][nsamples]
+        iqhip::DevBuf<double> sums;     // [M][nsamples]
+        iqhip::DevBuf<double> out;      // lh3 [3 * nbranch] ++ iqhip_branch_support [nbranch]
+    } bt;
     // tree topology tests (kernels_topo.hip): int64 inclusive prefix sums of ptn_freq for iqhip_gen_boot_samples (built when
     // first needed, dropped by iqhip_set_ptn_freq) and the scratch of iqhip_ptnlh_diff_variance / iqhip_tree_tests /
     // iqhip_multiscale_bp
     int64_t *d_freq_prefix = nullptr;
     bool freq_prefix_valid = false;
     int64_t freq_nsite = 0;
-    double *d_tt_var = nullptr;         // [n][n] variances of the pairwise differences
-    size_t tt_var_cap = 0;
-    double *d_tt_dbl = nullptr;         // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
-    size_t tt_dbl_cap = 0;
-    int32_t *d_tt_int = nullptr;        // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
-    size_t tt_int_cap = 0;
-    // pairwise ML distances (kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
+    struct {
+        iqhip::DevBuf<double> var;      // [n][n] variances of the pairwise differences
+        iqhip::DevBuf<double> dbl;      // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
+        iqhip::DevBuf<int32_t> ints;    // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
+    } tt;
+    // pairwise ML distances (pairdist.hip, kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
     // coefficients evec[i][k] * inv_evec[k][j] of the call's model [n][n][n], per pair the initial distance and the result
     // {optx, d2l, evaluations, status}; with iqhip_timing_enable the device time of the last iqhip_pair_distances call
-    iqhip::PairTile *d_pd_tiles = nullptr;
-    size_t pd_tiles_cap = 0;
-    double *d_pd_counts = nullptr;
-    size_t pd_counts_cap = 0;
-    double *d_pd_coef = nullptr;
-    size_t pd_coef_cap = 0;
-    double *d_pd_init = nullptr;
-    size_t pd_init_cap = 0;
-    double *d_pd_out = nullptr;
-    size_t pd_out_cap = 0;
+    struct {
+        iqhip::DevBuf<iqhip::PairTile> tiles;
+        iqhip::DevBuf<double> counts, coef, init, out;
+    } pd;
     double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
     // BIONJ (kernels_bionj.hip): the device memory lives for one call; iqhip_debug_bionj_timing reads these
     double bj_ms = 0.0;
@@ -484,26 +487,23 @@ struct iqhip_engine {
     bool pars_ready = false;
     int pars_nvec = 0;
     int64_t pars_nsites = 0, pars_nwords = 0;
-    uint32_t *d_pars_vec = nullptr, *d_pars_score = nullptr;
-    size_t pars_vec_cap = 0, pars_score_cap = 0;
     std::vector<uint8_t> pars_valid;
-    int32_t *d_pars_int = nullptr;      // per call: ops ++ level starts, or branch ends; init: the pattern of every site
-    size_t pars_int_cap = 0;
-    int32_t *d_pars_out = nullptr;      // score [nbranch] ++ subst [nbranch] ++ {best, best_score}
-    size_t pars_out_cap = 0;
+    struct {
+        iqhip::DevBuf<uint32_t> vec, score;
+        iqhip::DevBuf<int32_t> ints;    // per call: ops ++ level starts, or branch ends; init: the pattern of every site
+        iqhip::DevBuf<int32_t> out;     // score [nbranch] ++ subst [nbranch] ++ {best, best_score}
+        iqhip::DevBuf<uint64_t> masks;  // [state_unknown + 1] the states a code allows
+    } pars;
     // pinned staging, one buffer per direction and kind so that none is rewritten while a copy of it may be in flight: the
     // levelled ops of an update (rewritten only after a synchronise), the branch ends and the results of a scores call
     // (every scores call ends with a synchronise)
     int32_t *h_pars_ops = nullptr, *h_pars_ends = nullptr, *h_pars_out = nullptr;
     size_t h_pars_ops_cap = 0, h_pars_ends_cap = 0, h_pars_out_cap = 0;
-    uint64_t *d_pars_masks = nullptr;   // [state_unknown + 1] the states a code allows
-    size_t pars_masks_cap = 0;
     double pars_ms[2] = {0.0, 0.0};     // iqhip_debug_pars_timing: update, scan (while timing is enabled)
     int64_t pars_counts[4] = {0, 0, 0, 0};   // launches of the updates and of the scans, ops updated, branches scanned
     double pars_spr_ms = 0.0;           // iqhip_debug_pars_spr_timing: the SPR scan launches (while timing is enabled) ...
     int64_t pars_spr_counts[2] = {0, 0};   // ... their number and the steps scored
-    int32_t *d_batch_rows = nullptr;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
-    size_t batch_rows_cap = 0;
+    iqhip::DevBuf<int32_t> d_batch_rows;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     double *d_result_own = nullptr, *d_result = nullptr;
     double *d_newton_partials = nullptr;   // [2][num_cus][2]
     unsigned int *d_newton_barrier = nullptr;  // [2], used alternately by consecutive k_newton launches
@@ -514,27 +514,23 @@ struct iqhip_engine {
     double *d_newton_posts = nullptr;      // [2][kNewtonPostEpochs][num_cus][2]
     unsigned int newton_post_launches = 0;
     bool newton_posts = true;              // IQHIP_NEWTON_POSTS=0: the arrival-counter barrier of round 1
-    // the same for k_newton_batch: [2 launch parities][batch_posts_cap]; a launch lays its slots out as
+    // the same for k_newton_batch: [2 launch parities][cap / 2]; a launch lays its slots out as
     // [task][evaluation][workgroup][2] and resets what the previous launch of the other parity used
-    double *d_batch_posts = nullptr;
-    size_t batch_posts_cap = 0;            // doubles per parity
+    iqhip::DevBuf<double> d_batch_posts;
     size_t batch_posts_used[2] = {0, 0};
     unsigned int batch_post_launches = 0;
     // batched branch optimisation (iqhip_optimize_branch_batch): per-task theta buffers, partial sums, arrival
     // counters (two sets, alternating per launch), results and the task descriptors
-    double *d_theta_batch = nullptr, *d_batch_partials = nullptr, *d_batch_out = nullptr;
-    unsigned int *d_batch_barriers = nullptr;
-    void *d_batch_tasks = nullptr;
-    size_t theta_batch_cap = 0;
-    int batch_cap = 0;
+    iqhip::DevBuf<double> d_theta_batch, d_batch_partials, d_batch_out;
+    iqhip::DevBuf<unsigned int> d_batch_barriers;
+    iqhip::DevBuf<char> d_batch_tasks;   // NewtonTask descriptors (kernels_newton.hip), as bytes
+    int batch_cap = 0;                   // tasks all four were last grown for
     unsigned int batch_launches = 0;
-    double *d_sweep_len = nullptr;   // iqhip_optimize_sweep: the accepted length of every step, read by later steps' node updates
-    int sweep_len_cap = 0;
+    iqhip::DevBuf<double> d_sweep_len;   // iqhip_optimize_sweep: the accepted length of every step, read by later steps' node updates
     // ... persistent form (4 states): descriptors of all steps (pinned staging + device copy) and the exchange slots
     char *h_sweep_desc = nullptr, *d_sweep_desc = nullptr;
     size_t sweep_desc_cap = 0;
-    double *d_sweep_posts = nullptr;
-    size_t sweep_posts_cap = 0;
+    iqhip::DevBuf<double> d_sweep_posts;
     int num_cus = 256;
     int result_cap = 0;
     // ---- collectives (comm.hip).  comm != nullptr: this engine is one rank of a pattern-sharded run; every
@@ -544,10 +540,8 @@ struct iqhip_engine {
     int comm_nranks = 1, comm_rank = 0;
     double *d_result_dev = nullptr;  // device-memory result vector of a comm engine (the default one is mapped host memory)
     iqhip::NewtonState *d_nstate = nullptr, *h_nstate = nullptr;  // Newton state machine: device copy / pinned host copy
-    iqhip::NewtonState *d_bstates = nullptr;                      // batched chain: one state machine per task
-    int bstates_cap = 0;
-    const int16_t **d_bsc = nullptr;                              // ... and (+ASC) the scale counters of its two branch ends
-    int bsc_cap = 0;
+    iqhip::DevBuf<iqhip::NewtonState> d_bstates;                  // batched chain: one state machine per task
+    iqhip::DevBuf<const int16_t *> d_bsc;                         // ... and (+ASC) the scale counters of its two branch ends
     // ---- single-process sharding (sharded.hip): this object owns no device memory, it fronts `shards`
     // (pattern ranges [shard_first[g], shard_first[g+1]) on the devices of iqhip_create_sharded)
     std::vector<iqhip_engine *> shards;
@@ -744,7 +738,8 @@ T *fake_alloc(iqhip_engine *e, size_t count) {
     return reinterpret_cast<T *>(a);
 }
 // Replaces a device buffer by one of `count` elements once the engine's stream has drained (the contents are dropped);
-// *cap = new_cap when that succeeded, 0 while it has not.  A planning-only engine gets a fake address.
+// *cap = new_cap when that succeeded, 0 while it has not.  A planning-only engine gets a fake address.  Called directly only
+// where the capacity field means something other than the allocation's element count; everything else is a DevBuf.
 template <typename T, typename C>
 hipError_t regrow(iqhip_engine *e, T **buf, C *cap, size_t new_cap, size_t count) {
     if (e->planner) {
@@ -759,6 +754,12 @@ hipError_t regrow(iqhip_engine *e, T **buf, C *cap, size_t new_cap, size_t count
     }
     *cap = (C)new_cap;
     return hipSuccess;
+}
+template <typename T>
+hipError_t DevBuf<T>::ensure(iqhip_engine *e, size_t count) {
+    if (count <= cap) return hipSuccess;
+    fake = e->planner;
+    return regrow(e, &p, &cap, count, count);
 }
 int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);   // engine.hip (create: a new key gets a slab)
 bool cherry_candidate(const iqhip_engine *e);   // engine.hip: the engine uses cherry tables (DevOp::cherry)
@@ -829,10 +830,11 @@ int comm_init_all(const std::vector<iqhip_engine *> &shards);
 void comm_destroy(iqhip_engine *e);
 int comm_use_device_result(iqhip_engine *e);  // switch the engine to a device-memory result vector
 
-// engine.hip internals the solvers (solve.hip) and the sharded front drive an engine with
+// engine.hip internals the solvers (solve.hip), the feature drivers (ptnlh.hip, pairdist.hip) and the sharded front drive
+// an engine with
 // a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
 hipError_t use_device(const iqhip_engine *e);
-int ptnlh_plain_engine(iqhip_engine *e, const char *what);   // the per-pattern store: single-device engines only
+int ptnlh_plain_engine(iqhip_engine *e, const char *what);   // ptnlh.hip -- the per-pattern store: single-device engines only
 int check_ready(iqhip_engine *e);                     // model and alignment set, device selected
 int ensure_slab_rows(iqhip_engine *e, int nrows);     // the wave-partial slab holds nrows rows
 // enqueue: plan upload, K1, fused traversal (+ optional root lnL), fixed-order reduction (skip_reduce: the caller's next
@@ -921,7 +923,7 @@ int eng_batch_states_read(iqhip_engine *e, int m, NewtonState *out);        // (
 int eng_batch_states_write(iqhip_engine *e, int m, const NewtonState *in);
 
 // sharded.hip -- the single-process multi-device front (iqhip_create_sharded); every public entry point of
-// engine.hip and solve.hip forwards here when e->shards is non-empty
+// engine.hip, solve.hip and ptnlh.hip forwards here when e->shards is non-empty
 namespace sharded {
 void destroy(iqhip_engine *p);
 int reserve(iqhip_engine *p, int nvectors);

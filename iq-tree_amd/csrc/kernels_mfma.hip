@@ -1515,9 +1515,9 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
     A.evalc = e->d_evalc;
     A.tipc = e->d_tipc;
     A.cls = e->d_cls;
-    A.img = e->d_img;
-    A.img_generic = e->d_img ? e->d_img + e->img_generic_off : nullptr;
-    A.slab = e->d_slab;
+    A.img = e->d_img.p;
+    A.img_generic = e->d_img.p ? e->d_img.p + e->img_generic_off : nullptr;
+    A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
     A.segs = seg_table;
@@ -1711,7 +1711,7 @@ hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, do
     A.task_rows = (bc && mode == 2) ? bc->derv_rows : 2;
     A.task_sc = bc ? bc->sc : nullptr;
     if (bc) fold_rows = -1;
-    A.fold.slab = e->d_slab;
+    A.fold.slab = e->d_slab.p;
     A.fold.result = e->d_result;
     A.fold.ticket = e->d_fold_ticket;
     A.fold.flags = e->d_fold_flags;
@@ -1730,7 +1730,7 @@ hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, do
     A.invar = e->d_invar;
     A.theta = bc ? const_cast<double *>(bc->theta) : (theta_out ? theta_out : e->d_theta);
     A.pattern_lh = bc ? nullptr : e->d_pattern_lh;
-    A.slab = e->d_slab;
+    A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
     A.nobs = e->nptn - e->n_unobs;

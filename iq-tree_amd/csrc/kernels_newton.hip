@@ -1079,7 +1079,7 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
     A.build = build_from ? 1 : 0;
     A.br = build_from ? *build_from : DevBranch{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.0};
     A.tipc = e->d_tipc;
-    A.slab = e->d_slab;
+    A.slab = e->d_slab.p;
     A.result = sweep ? sweep->rows_base - 2 : e->d_result;   // (row r of the node updates goes to result[2 + r])
     A.nrows = reduce_rows;
     A.nwaves = reduce_nwaves;

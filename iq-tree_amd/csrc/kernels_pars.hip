@@ -231,8 +231,8 @@ __global__ __launch_bounds__(256) void k_pars_argmin(int32_t *out, int nbranch) 
 hipError_t launch_pars_tips(iqhip_engine *e, const int32_t *d_site_ptn) {
     const int64_t total = (int64_t)e->ntaxa * e->pars_nwords * e->n;
     hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_states, e->nptn_pad,
-                       d_site_ptn, e->pars_nsites, e->pars_nwords, e->d_pars_masks, e->n, e->ntaxa, e->d_pars_vec,
-                       e->d_pars_score);
+                       d_site_ptn, e->pars_nsites, e->pars_nwords, e->pars.masks.p, e->n, e->ntaxa, e->pars.vec.p,
+                       e->pars.score.p);
     return hipGetLastError();
 }
 
@@ -240,7 +240,7 @@ hipError_t launch_pars_update(iqhip_engine *e, const iqhip_pars_op *d_ops, const
     if (nlev < 1) return hipSuccess;
     const dim3 grid((unsigned)((e->pars_nwords + kParsWordsPerWg - 1) / kParsWordsPerWg));
 #define IQHIP_PARS_UPDATE(N)                                                                                       \
-    hipLaunchKernelGGL(k_pars_update<N>, grid, dim3(kParsThreads), 0, e->stream, e->d_pars_vec, e->d_pars_score, d_ops, d_lev_start, \
+    hipLaunchKernelGGL(k_pars_update<N>, grid, dim3(kParsThreads), 0, e->stream, e->pars.vec.p, e->pars.score.p, d_ops, d_lev_start, \
                        nlev, e->pars_nwords)
     if (e->n == 4) IQHIP_PARS_UPDATE(4);
     else if (e->n == 20) IQHIP_PARS_UPDATE(20);
@@ -254,8 +254,8 @@ hipError_t launch_pars_branch(iqhip_engine *e, const int32_t *d_ends, int nbranc
     *nlaunches = 0;
     if (nbranch < 1) return hipSuccess;
 #define IQHIP_PARS_BRANCH(N, INS)                                                                                     \
-    hipLaunchKernelGGL((k_pars_branch<N, INS>), dim3((unsigned)nbranch), dim3(256), 0, e->stream, e->d_pars_vec,      \
-                       e->d_pars_score, d_ends, nbranch, e->pars_nwords, taxon, d_out)
+    hipLaunchKernelGGL((k_pars_branch<N, INS>), dim3((unsigned)nbranch), dim3(256), 0, e->stream, e->pars.vec.p,      \
+                       e->pars.score.p, d_ends, nbranch, e->pars_nwords, taxon, d_out)
     const bool ins = taxon >= 0;
     if (e->n == 4) { if (ins) IQHIP_PARS_BRANCH(4, true); else IQHIP_PARS_BRANCH(4, false); }
     else if (e->n == 20) { if (ins) IQHIP_PARS_BRANCH(20, true); else IQHIP_PARS_BRANCH(20, false); }

@@ -208,8 +208,8 @@ hipError_t launch_pars_spr(iqhip_engine *e, const iqhip_pars_spr_job *d_jobs, in
     const unsigned gy = (unsigned)(njobs < 65535 ? njobs : 65535);
 #define IQHIP_PARS_SPR(N, Q)                                                                                              \
     hipLaunchKernelGGL((k_pars_spr<N, Q>), dim3((unsigned)((e->pars_nwords + 64 / Q - 1) / (64 / Q)), gy), dim3(64),      \
-                       (N == 4 ? 0 : sizeof(uint32_t) * (size_t)levels * (N / Q + 1) * 64), e->stream, e->d_pars_vec,      \
-                       e->d_pars_score, d_jobs, njobs, d_steps, e->pars_nwords, levels, d_out)
+                       (N == 4 ? 0 : sizeof(uint32_t) * (size_t)levels * (N / Q + 1) * 64), e->stream, e->pars.vec.p,      \
+                       e->pars.score.p, d_jobs, njobs, d_steps, e->pars_nwords, levels, d_out)
     if (e->n == 4) IQHIP_PARS_SPR(4, 1);
     else if (e->n == 20) IQHIP_PARS_SPR(20, 2);
     else if (e->n == 64) IQHIP_PARS_SPR(64, 4);

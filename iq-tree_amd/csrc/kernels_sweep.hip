@@ -471,7 +471,7 @@ hipError_t launch_sweep4(iqhip_engine *e, const SweepOp *d_ops, const SweepStep 
     A.freq = e->d_freq;
     A.invar = e->d_invar;
     A.theta = e->d_theta;
-    A.slab = e->d_slab;
+    A.slab = e->d_slab.p;
     const int grid = sweep4_grid(e), waves = sweep4_waves(e);
     A.nwaves = grid * waves;
     A.ntiles = e->ntiles;

@@ -640,7 +640,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     }
 #endif
     Trav4Args A;
-    A.fold.slab = e->d_slab;
+    A.fold.slab = e->d_slab.p;
     A.fold.result = e->d_result;
     A.fold.ticket = e->d_fold_ticket;
     A.fold.flags = e->d_fold_flags;
@@ -666,7 +666,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     A.rates = e->d_rates;
     A.props = e->d_props;
     A.pattern_lh = e->d_pattern_lh;
-    A.slab = e->d_slab;
+    A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
     A.nobs = e->nptn - e->n_unobs;
@@ -858,7 +858,7 @@ static hipError_t launch_theta_reduce(iqhip_engine *e, double len, int nwaves, c
     case Cv:                                                                                   \
         hipLaunchKernelGGL((k_theta_reduce4<Cv, MODE>), dim3(grid, ny), dim3(256), 0, e->stream, \
                            theta, e->d_eval, e->d_rates, e->d_props, len, e->d_freq,           \
-                           e->d_invar, plh, e->d_slab, e->ntiles, e->nptn, nwaves,             \
+                           e->d_invar, plh, e->d_slab.p, e->ntiles, e->nptn, nwaves,             \
                            e->nptn - e->n_unobs, e->theta_a_sc, e->theta_b_sc, st, stride,     \
                            task_rows, task_sc);                                                \
         break;
@@ -920,7 +920,7 @@ hipError_t launch_reduce(iqhip_engine *e, int first_row, int nrows, int nwaves) 
         done = e->d_done;
         e->poll_pending = true;
     }
-    hipLaunchKernelGGL(k_reduce, dim3(nrows), dim3(256), 0, e->stream, e->d_slab, nwaves,
+    hipLaunchKernelGGL(k_reduce, dim3(nrows), dim3(256), 0, e->stream, e->d_slab.p, nwaves,
                        first_row, e->d_result, e->d_fold_ticket + 1, done, seq);
     return hipGetLastError();
 }

@@ -313,19 +313,19 @@ static hipError_t launch4w(iqhip_engine *e, const TravLaunch &L, const Trav4wArg
 }
 
 hipError_t launch_traverse4w(iqhip_engine *e, const TravLaunch &L, const int *seg_table, int nwaves) {
-    if (L.variant != TRAV_WIDE4 || !e->wide4 || !e->d_img) return hipErrorInvalidValue;
+    if (L.variant != TRAV_WIDE4 || !e->wide4 || !e->d_img.p) return hipErrorInvalidValue;
     Trav4wArgs A;
     A.ops = e->d_ops;
     A.evec = e->d_evec;
     A.inv_evec = e->d_inv_evec;
-    A.img = e->d_img + e->img_generic_off;
+    A.img = e->d_img.p + e->img_generic_off;
     A.evalc = e->d_evalc;
     A.rates = e->d_rates;
     A.tipc = e->d_tipc;
     A.cls = e->d_cls;
     A.freq = e->d_freq;
     A.invar = e->d_invar;
-    A.slab = e->d_slab;
+    A.slab = e->d_slab.p;
     A.fold_flags = e->d_fold_flags;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;

@@ -163,19 +163,19 @@ extern "C" int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative, int 
     HIPCHK(use_device(e));
     const size_t nslots = (size_t)e->ntaxa + (size_t)nvectors;
     const size_t vec_words = nslots * (size_t)nwords * n, score_words = nslots * (size_t)nwords;
-    if (vec_words > e->pars_vec_cap) HIPCHK(regrow(e, &e->d_pars_vec, &e->pars_vec_cap, vec_words, vec_words));
-    if (score_words > e->pars_score_cap) HIPCHK(regrow(e, &e->d_pars_score, &e->pars_score_cap, score_words, score_words));
-    if (site_ptn.size() + 1 > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, site_ptn.size() + 1, site_ptn.size() + 1));
-    if ((size_t)nst > e->pars_masks_cap) HIPCHK(regrow(e, &e->d_pars_masks, &e->pars_masks_cap, (size_t)nst, (size_t)nst));
+    HIPCHK(e->pars.vec.ensure(e, vec_words));
+    HIPCHK(e->pars.score.ensure(e, score_words));
+    HIPCHK(e->pars.ints.ensure(e, site_ptn.size() + 1));
+    HIPCHK(e->pars.masks.ensure(e, (size_t)nst));
     e->pars_nsites = total;
     e->pars_nwords = nwords;
     e->pars_nvec = nvectors;
     e->pars_valid.assign((size_t)nvectors, 0);
     HIPCHK(hipStreamSynchronize(e->stream));   // (pageable sources: the copies must not outlive them)
     if (!site_ptn.empty())
-        HIPCHK(hipMemcpyAsync(e->d_pars_int, site_ptn.data(), sizeof(int32_t) * site_ptn.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_pars_masks, masks.data(), sizeof(uint64_t) * masks.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(launch_pars_tips(e, e->d_pars_int));
+        HIPCHK(hipMemcpyAsync(e->pars.ints.p, site_ptn.data(), sizeof(int32_t) * site_ptn.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.masks.p, masks.data(), sizeof(uint64_t) * masks.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(launch_pars_tips(e, e->pars.ints.p));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (nsites) *nsites = total;
     e->pars_ready = true;
@@ -199,7 +199,7 @@ extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int 
     // update's copy, so the stream is drained first (after a scores call it is idle); nothing waits after the launch
     const size_t nblob = (size_t)4 * nops + (size_t)nlev + 1;
     HIPCHK(use_device(e));
-    if (nblob > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, nblob, nblob));
+    HIPCHK(e->pars.ints.ensure(e, nblob));
     HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
     HIPCHK(hipStreamSynchronize(e->stream));
     {
@@ -208,10 +208,10 @@ extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int 
         for (int k = 0; k < nops; k++) sorted[at[(size_t)level[(size_t)k]]++] = ops[k];
         std::copy(start.begin(), start.end(), e->h_pars_ops + (size_t)4 * nops);
     }
-    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
     ParsTimer tm(e, 0);
     HIPCHK(tm.start());
-    HIPCHK(launch_pars_update(e, reinterpret_cast<const iqhip_pars_op *>(e->d_pars_int), e->d_pars_int + (size_t)4 * nops, nlev));
+    HIPCHK(launch_pars_update(e, reinterpret_cast<const iqhip_pars_op *>(e->pars.ints.p), e->pars.ints.p + (size_t)4 * nops, nlev));
     HIPCHK(tm.stop(1, nops));
     for (int k = 0; k < nops; k++) e->pars_valid[(size_t)(ops[k].dst - e->ntaxa)] = 1;
     return IQHIP_OK;
@@ -234,19 +234,19 @@ static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int ta
                        size_t count) {
     HIPCHK(use_device(e));
     const size_t need_out = (size_t)2 * nbranch + 2;
-    if ((size_t)2 * nbranch > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, (size_t)2 * nbranch, (size_t)2 * nbranch));
-    if (need_out > e->pars_out_cap) HIPCHK(regrow(e, &e->d_pars_out, &e->pars_out_cap, need_out, need_out));
+    HIPCHK(e->pars.ints.ensure(e, (size_t)2 * nbranch));
+    HIPCHK(e->pars.out.ensure(e, need_out));
     HIPCHK(pars_pinned(e, &e->h_pars_ends, &e->h_pars_ends_cap, (size_t)2 * nbranch));
     HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
     // (no copy of h_pars_ends or into h_pars_out is in flight: every call of this function ends with a synchronise)
     memcpy(e->h_pars_ends, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
-    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ends, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ends, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
     ParsTimer tm(e, 1);
     int nlaunches = 0;
     if (taxon >= 0) HIPCHK(tm.start());
-    HIPCHK(launch_pars_branch(e, e->d_pars_int, nbranch, taxon, e->d_pars_out, &nlaunches));
+    HIPCHK(launch_pars_branch(e, e->pars.ints.p, nbranch, taxon, e->pars.out.p, &nlaunches));
     if (taxon >= 0) HIPCHK(tm.stop(nlaunches, nbranch));
-    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->d_pars_out + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     out.assign(e->h_pars_out, e->h_pars_out + count);
     return IQHIP_OK;
@@ -295,8 +295,8 @@ extern "C" int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out) {
     const size_t nw = (size_t)e->pars_nwords;
     std::vector<uint32_t> v(nw * n), sc(nw);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(v.data(), e->d_pars_vec + (size_t)slot * nw * n, sizeof(uint32_t) * v.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sc.data(), e->d_pars_score + (size_t)slot * nw, sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v.data(), e->pars.vec.p + (size_t)slot * nw * n, sizeof(uint32_t) * v.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), e->pars.score.p + (size_t)slot * nw, sizeof(uint32_t) * nw, hipMemcpyDeviceToHost));
     if (n == 4) memcpy(out, v.data(), sizeof(uint32_t) * v.size());
     else
         for (size_t w = 0; w < nw; w++)
@@ -338,8 +338,8 @@ extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jo
     const size_t nout = (size_t)nsteps + 2 * (size_t)njobs + 1;
     const size_t from = score ? 0 : (size_t)nsteps, count = nout - from;
     HIPCHK(use_device(e));
-    if (nblob > e->pars_int_cap) HIPCHK(regrow(e, &e->d_pars_int, &e->pars_int_cap, nblob, nblob));
-    if (nout > e->pars_out_cap) HIPCHK(regrow(e, &e->d_pars_out, &e->pars_out_cap, nout, nout));
+    HIPCHK(e->pars.ints.ensure(e, nblob));
+    HIPCHK(e->pars.out.ensure(e, nout));
     HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
     HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
     HIPCHK(hipStreamSynchronize(e->stream));   // (the staging buffer may still feed the previous update's copy)
@@ -351,15 +351,15 @@ extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jo
         hs[k].parent = depth[(size_t)k];
         if (depth[(size_t)k] >= 0 && !(steps[k].flags & IQHIP_PARS_SPR_NO_SCORE)) scored++;
     }
-    HIPCHK(hipMemcpyAsync(e->d_pars_int, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
     ParsTimer tm(e, &e->pars_spr_ms, &e->pars_spr_counts[0], &e->pars_spr_counts[1]);
     int nlaunches = 0;
     HIPCHK(tm.start());
-    HIPCHK(launch_pars_spr(e, reinterpret_cast<const iqhip_pars_spr_job *>(e->d_pars_int), njobs,
-                           reinterpret_cast<const iqhip_pars_spr_step *>(e->d_pars_int + (size_t)4 * njobs), nsteps, max_depth,
-                           e->d_pars_out, &nlaunches));
+    HIPCHK(launch_pars_spr(e, reinterpret_cast<const iqhip_pars_spr_job *>(e->pars.ints.p), njobs,
+                           reinterpret_cast<const iqhip_pars_spr_step *>(e->pars.ints.p + (size_t)4 * njobs), nsteps, max_depth,
+                           e->pars.out.p, &nlaunches));
     HIPCHK(tm.stop(nlaunches, scored));
-    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->d_pars_out + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     const int32_t *res = e->h_pars_out;
     if (score) {

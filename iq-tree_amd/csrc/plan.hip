@@ -37,7 +37,7 @@ int ensure_plan_capacity(iqhip_engine *e, int nops) {
     if (nops <= e->ops_cap) return IQHIP_OK;
     const int cap = std::max(64, nops * 2);
     e->plan_cache.uploaded.clear();
-    HIPCHK(regrow(e, &e->d_ops, &e->ops_cap, 0, cap));   // (ops_cap: once h_ops has grown too)
+    HIPCHK(regrow(e, &e->d_ops, &e->ops_cap, 0, cap));   // (plain regrow: ops_cap counts ops and is set once h_ops has grown too)
     if (e->planner) free(e->h_ops);
     else if (e->h_ops) hipHostFree(e->h_ops);
     e->h_ops = nullptr;
@@ -359,7 +359,7 @@ int assign_leaf_tables(iqhip_engine *e, int nops) {
     }
     const size_t need = (size_t)e->ntaxa + (size_t)noverflow;
     if (need > e->leaf_tab_slots) {
-        HIPCHK(regrow(e, &e->d_leaf_tab, &e->leaf_tab_slots, need + 16, (need + 16) * per));
+        HIPCHK(regrow(e, &e->d_leaf_tab, &e->leaf_tab_slots, need + 16, (need + 16) * per));   // (plain regrow: the capacity counts tables)
         e->plan_cache.uploaded.clear();
         // a new buffer holds no tables: everything this plan uses is dirty
         dirty.insert(dirty.end(), clean.begin(), clean.end());
@@ -393,7 +393,7 @@ int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_
     const size_t per = (size_t)e->cherry_npairs * e->block;
     const size_t want = (size_t)2 * e->ntaxa + 16;
     const bool fresh = e->cherry_cap < want;   // (a new buffer holds no tables)
-    if (fresh) HIPCHK(regrow(e, &e->d_cherry_tab, &e->cherry_cap, want, want * per));
+    if (fresh) HIPCHK(regrow(e, &e->d_cherry_tab, &e->cherry_cap, want, want * per));   // (plain regrow: cherry_cap counts slots)
     // room for every cherry a plan can hold; a search that has walked through more pairs than that starts over
     if (fresh || e->cherry_slots.size() + (size_t)e->ntaxa / 2 + 1 > e->cherry_cap) {
         e->cherry_slot_of.clear();

@@ -322,7 +322,7 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     const size_t need = bytes_ops + bytes_steps;
     if (need > e->sweep_desc_cap) {
         const size_t cap = need * 2 + 4096;
-        HIPCHK(regrow(e, &e->d_sweep_desc, &e->sweep_desc_cap, 0, cap));   // (sweep_desc_cap: once the host copy has grown too)
+        HIPCHK(regrow(e, &e->d_sweep_desc, &e->sweep_desc_cap, 0, cap));   // (plain regrow: the capacity counts bytes, set once the host copy has grown too)
         if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
         e->h_sweep_desc = nullptr;
         HIPCHK(hipHostMalloc((void **)&e->h_sweep_desc, cap));
@@ -368,17 +368,17 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     }
     const int grid = sweep4_grid(e), nwaves = grid * sweep4_waves(e);
     const size_t slab_need = total_ops * (size_t)nwaves + 1024;
-    if ((int64_t)total_ops * nwaves > e->slab_cap) HIPCHK(regrow(e, &e->d_slab, &e->slab_cap, slab_need, slab_need));
+    if (total_ops * (size_t)nwaves > e->d_slab.cap) HIPCHK(e->d_slab.ensure(e, slab_need));
     const size_t posts_need = (size_t)2 * kNewtonPostEpochs * grid * 2;
-    if (posts_need > e->sweep_posts_cap) HIPCHK(regrow(e, &e->d_sweep_posts, &e->sweep_posts_cap, posts_need, posts_need));
+    HIPCHK(e->d_sweep_posts.ensure(e, posts_need));
     HIPCHK(hipMemcpyAsync(e->d_sweep_desc, e->h_sweep_desc, need, hipMemcpyHostToDevice, e->stream));
-    if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts, 0xFF, posts_need * sizeof(double), e->stream));
+    if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts.p, 0xFF, posts_need * sizeof(double), e->stream));
     double *out = e->d_result + total_ops;      // (rows [0, total_ops) receive the sum_scale sums from k_reduce)
     memset(e->h_result + total_ops, 0, sizeof(double) * 6 * (size_t)nsteps);
     e->path_counts[IQHIP_PATH_SWEEP_PERSISTENT]++;
     HIPCHK(launch_sweep4(e, reinterpret_cast<const SweepOp *>(e->d_sweep_desc),
                          reinterpret_cast<const SweepStep *>(e->d_sweep_desc + bytes_ops), nsteps, x1, x2, xacc, max_steps,
-                         diverge_frac * x2, e->d_sweep_posts, out));
+                         diverge_frac * x2, e->d_sweep_posts.p, out));
     HIPCHK(launch_reduce(e, 0, (int)total_ops, nwaves));
     set_theta_branch(e, hsteps[nsteps - 1].br);
     e->plan_cache.version = 0;
@@ -429,7 +429,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         ~ArenaScope() { e->plan_arena_on = false; }
     } arena_scope(e);
     e->path_counts[IQHIP_PATH_SWEEP_PER_STEP]++;
-    if (nsteps > e->sweep_len_cap) HIPCHK(regrow(e, &e->d_sweep_len, &e->sweep_len_cap, nsteps + 64, (size_t)nsteps + 64));
+    if ((size_t)nsteps > e->d_sweep_len.cap) HIPCHK(e->d_sweep_len.ensure(e, (size_t)nsteps + 64));
     const bool dbg = e->debug_sweep;
     double t_trav = 0.0, t_newt = 0.0;
     int n_uploaded = 0;
@@ -449,7 +449,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
                 len_ptrs.assign((size_t)2 * st.nops, nullptr);
                 bool any = false;
                 for (int q = 0; q < 2 * st.nops; q++)
-                    if (st.len_from[q] >= 0) { len_ptrs[q] = e->d_sweep_len + st.len_from[q]; any = true; }
+                    if (st.len_from[q] >= 0) { len_ptrs[q] = e->d_sweep_len.p + st.len_from[q]; any = true; }
                 if (any) lp = len_ptrs.data();
             }
             if (dbg) part.start();
@@ -462,7 +462,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         if (rc) return rc;
         set_theta_branch(e, br);
         NewtonSweepStep sw;
-        sw.len_out = e->d_sweep_len + j;
+        sw.len_out = e->d_sweep_len.p + j;
         sw.rows_base = e->d_result + row;
         sw.diverge_x = diverge_frac * x2;
         sw.publish = (j == nsteps - 1);
@@ -501,8 +501,8 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
 int iqhip::batch_derv_rows(const iqhip_engine *e) { return e->asc_active ? 5 : 2; }
 
 static BatchChain batch_chain_of(const iqhip_engine *e, int m) {
-    return BatchChain{e->d_theta_batch, (size_t)e->nptn_pad * e->block, e->d_bstates, m, batch_derv_rows(e),
-                      e->asc_active ? e->d_bsc : nullptr};
+    return BatchChain{e->d_theta_batch.p, (size_t)e->nptn_pad * e->block, e->d_bstates.p, m, batch_derv_rows(e),
+                      e->asc_active ? e->d_bsc.p : nullptr};
 }
 
 // phylokernel.h:1183-1186 on a task's all-reduced {lnl, prob_const}
@@ -523,10 +523,9 @@ int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, in
     rc = ensure_slab_rows(e, std::max(5, rows * m));
     if (rc) return rc;
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)m * theta_stride > e->theta_batch_cap)
-        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)m * theta_stride, (size_t)m * theta_stride));
-    if (m > e->bstates_cap) HIPCHK(regrow(e, &e->d_bstates, &e->bstates_cap, m, m));
-    if (e->asc_active && 2 * m > e->bsc_cap) HIPCHK(regrow(e, &e->d_bsc, &e->bsc_cap, 2 * m, 2 * m));
+    HIPCHK(e->d_theta_batch.ensure(e, (size_t)m * theta_stride));
+    HIPCHK(e->d_bstates.ensure(e, (size_t)m));
+    if (e->asc_active) HIPCHK(e->d_bsc.ensure(e, (size_t)2 * m));
     std::vector<const int16_t *> sc;
     for (int t = 0; t < m; t++) {
         DevBranch br;
@@ -534,27 +533,27 @@ int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, in
         if (rc) return rc;
         sc.push_back(br.a_sc);
         sc.push_back(br.b_sc);
-        double *slot = e->d_theta_batch + (size_t)t * theta_stride;
+        double *slot = e->d_theta_batch.p + (size_t)t * theta_stride;
         if (e->mfma) HIPCHK(launch_stream_mfma(e, 1, &br, 0.0, (int)e->ntiles, nullptr, -1, slot));
         else HIPCHK(launch_theta4(e, br, slot));
     }
     // (pageable source, as the states below)
     if (e->asc_active)
-        HIPCHK(hipMemcpyAsync(e->d_bsc, sc.data(), sizeof(const int16_t *) * sc.size(), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_bsc.p, sc.data(), sizeof(const int16_t *) * sc.size(), hipMemcpyHostToDevice, e->stream));
     return eng_batch_states_write(e, m, init);
 }
 
 int iqhip::eng_batch_states_write(iqhip_engine *e, int m, const NewtonState *in) {
     if (use_device(e) != hipSuccess) return fail(IQHIP_ERR_HIP, "hipSetDevice");
     // (pageable source: the copy has left the host buffer when the call returns)
-    if (hipMemcpyAsync(e->d_bstates, in, sizeof(NewtonState) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+    if (hipMemcpyAsync(e->d_bstates.p, in, sizeof(NewtonState) * (size_t)m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
         return fail(IQHIP_ERR_HIP, "batched chain: state upload failed");
     return IQHIP_OK;
 }
 
 int iqhip::eng_batch_states_read(iqhip_engine *e, int m, NewtonState *out) {
     if (use_device(e) != hipSuccess) return fail(IQHIP_ERR_HIP, "hipSetDevice");
-    if (hipMemcpyAsync(out, e->d_bstates, sizeof(NewtonState) * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+    if (hipMemcpyAsync(out, e->d_bstates.p, sizeof(NewtonState) * (size_t)m, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
         hipStreamSynchronize(e->stream) != hipSuccess)
         return fail(IQHIP_ERR_HIP, "batched chain: state read failed");
     e->staging_busy = false;
@@ -579,7 +578,7 @@ int iqhip::eng_batch_lnl_enqueue(iqhip_engine *e, int m) { return batch_pass_enq
 
 int iqhip::eng_batch_update_enqueue(iqhip_engine *e, int m) {
     if (use_device(e) != hipSuccess) return fail(IQHIP_ERR_HIP, "hipSetDevice");
-    if (launch_newton_state_update_batch(e, e->d_bstates, m) != hipSuccess)
+    if (launch_newton_state_update_batch(e, e->d_bstates.p, m) != hipSuccess)
         return fail(IQHIP_ERR_HIP, "batched chain: launch failed");
     return IQHIP_OK;
 }
@@ -759,7 +758,7 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
         size_t free_b = 0, total_b = 0;
         const size_t per_task = (size_t)e->nptn_pad * e->block * sizeof(double);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t have = e->theta_batch_cap * sizeof(double);
+            const size_t have = e->d_theta_batch.cap * sizeof(double);
             const size_t room = (free_b + have) / 4;
             const size_t fit = std::max<size_t>(1, room / std::max<size_t>(1, per_task));
             if ((size_t)chunk > fit) chunk = (int)fit;
@@ -768,28 +767,19 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
     chunk = batch_chunk(chunk);
     const int G = std::max(1, std::min(wgs_needed, capacity / chunk));
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
-    if ((size_t)chunk * theta_stride > e->theta_batch_cap)
-        HIPCHK(regrow(e, &e->d_theta_batch, &e->theta_batch_cap, (size_t)chunk * theta_stride, (size_t)chunk * theta_stride));
+    HIPCHK(e->d_theta_batch.ensure(e, (size_t)chunk * theta_stride));
     if (chunk > e->batch_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        void *old[] = {e->d_batch_partials, e->d_batch_out, e->d_batch_barriers, e->d_batch_tasks};
-        for (void *p : old)
-            if (p) hipFree(p);
-        e->d_batch_partials = e->d_batch_out = nullptr;
-        e->d_batch_barriers = nullptr;
-        e->d_batch_tasks = nullptr;
         e->batch_cap = 0;
-        HIPCHK(dmalloc(&e->d_batch_partials, (size_t)chunk * 4 * (e->num_cus * 4)));
-        HIPCHK(dmalloc(&e->d_batch_out, (size_t)chunk * 6));
-        HIPCHK(dmalloc(&e->d_batch_barriers, (size_t)2 * chunk));
-        HIPCHK(hipMalloc(&e->d_batch_tasks, newton_task_bytes() * (size_t)chunk));
-        HIPCHK(hipMemsetAsync(e->d_batch_barriers, 0, sizeof(unsigned int) * 2 * chunk, e->stream));
+        HIPCHK(e->d_batch_partials.ensure(e, (size_t)chunk * 4 * (e->num_cus * 4)));
+        HIPCHK(e->d_batch_out.ensure(e, (size_t)chunk * 6));
+        HIPCHK(e->d_batch_barriers.ensure(e, (size_t)2 * chunk));
+        HIPCHK(e->d_batch_tasks.ensure(e, newton_task_bytes() * (size_t)chunk));
+        HIPCHK(hipMemsetAsync(e->d_batch_barriers.p, 0, sizeof(unsigned int) * 2 * chunk, e->stream));
         e->batch_cap = chunk;
     }
     std::vector<char> host_tasks(newton_task_bytes() * (size_t)chunk);
     std::vector<double> out((size_t)chunk * 6);
-    if (rows && (size_t)chunk > e->batch_rows_cap)
-        HIPCHK(regrow(e, &e->d_batch_rows, &e->batch_rows_cap, (size_t)chunk, (size_t)chunk));
+    if (rows) HIPCHK(e->d_batch_rows.ensure(e, (size_t)chunk));
     for (int first = 0; first < ntasks; first += chunk) {
         const int m = std::min(chunk, ntasks - first);
         for (int t = 0; t < m; t++) {
@@ -800,7 +790,7 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
             newton_task_fill(host_tasks.data() + newton_task_bytes() * (size_t)t, br, k.xguess, k.x1, k.x2, k.xacc,
                              k.max_steps);
         }
-        HIPCHK(hipMemcpyAsync(e->d_batch_tasks, host_tasks.data(), newton_task_bytes() * (size_t)m,
+        HIPCHK(hipMemcpyAsync(e->d_batch_tasks.p, host_tasks.data(), newton_task_bytes() * (size_t)m,
                               hipMemcpyHostToDevice, e->stream));
         // posted exchange of the tasks' partial sums (k_newton_batch): slots of this launch, [task][evaluation][workgroup][2]
         double *posts = nullptr, *posts_other = nullptr;
@@ -811,15 +801,15 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
             for (int t = 0; t < m; t++) max_steps = std::max(max_steps, tasks[first + t].max_steps);
             post_epochs = max_steps + 4;   // derivative evaluations + the lnL pass(es)
             const size_t need = (size_t)m * post_epochs * G * 2;
-            if (need > e->batch_posts_cap) {
-                HIPCHK(regrow(e, &e->d_batch_posts, &e->batch_posts_cap, need, 2 * need));   // (two launch parities)
-                HIPCHK(hipMemsetAsync(e->d_batch_posts, 0xFF, 2 * need * sizeof(double), e->stream));
+            if (2 * need > e->d_batch_posts.cap) {   // (two launch parities, half of the buffer each)
+                HIPCHK(e->d_batch_posts.ensure(e, 2 * need));
+                HIPCHK(hipMemsetAsync(e->d_batch_posts.p, 0xFF, 2 * need * sizeof(double), e->stream));
                 e->batch_posts_used[0] = e->batch_posts_used[1] = 0;
             }
             const unsigned int pp = e->batch_post_launches & 1u;
             e->batch_post_launches++;
-            posts = e->d_batch_posts + (size_t)pp * e->batch_posts_cap;
-            posts_other = e->d_batch_posts + (size_t)(1u - pp) * e->batch_posts_cap;
+            posts = e->d_batch_posts.p + (size_t)pp * (e->d_batch_posts.cap / 2);
+            posts_other = e->d_batch_posts.p + (size_t)(1u - pp) * (e->d_batch_posts.cap / 2);
             posts_other_used = e->batch_posts_used[1u - pp];
             e->batch_posts_used[pp] = need;
             e->batch_posts_used[1u - pp] = 0;   // (reset by this launch)
@@ -828,17 +818,17 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
         e->batch_launches++;
         // this launch's arrival counters start at zero whatever the task counts of earlier launches were (a launch
         // only clears the first m counters of the other parity, so a smaller batch in between leaves the rest dirty)
-        HIPCHK(hipMemsetAsync(e->d_batch_barriers + (size_t)parity * e->batch_cap, 0, sizeof(unsigned int) * (size_t)m,
+        HIPCHK(hipMemsetAsync(e->d_batch_barriers.p + (size_t)parity * e->batch_cap, 0, sizeof(unsigned int) * (size_t)m,
                               e->stream));
-        HIPCHK(launch_newton_batch(e, e->d_batch_tasks, m, G, e->d_theta_batch, theta_stride, e->d_batch_partials,
-                                   e->d_batch_barriers + (size_t)parity * e->batch_cap,
-                                   e->d_batch_barriers + (size_t)(1u - parity) * e->batch_cap, e->d_batch_out, posts, posts_other,
+        HIPCHK(launch_newton_batch(e, e->d_batch_tasks.p, m, G, e->d_theta_batch.p, theta_stride, e->d_batch_partials.p,
+                                   e->d_batch_barriers.p + (size_t)parity * e->batch_cap,
+                                   e->d_batch_barriers.p + (size_t)(1u - parity) * e->batch_cap, e->d_batch_out.p, posts, posts_other,
                                    posts_other_used, post_epochs));
         if (rows) {   // (the theta buffers are reused by the next chunk: per chunk)
-            HIPCHK(hipMemcpyAsync(e->d_batch_rows, rows + first, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(launch_ptnlh_rows(e, e->d_batch_tasks, m, e->d_theta_batch, theta_stride, e->d_batch_out, e->d_batch_rows));
+            HIPCHK(hipMemcpyAsync(e->d_batch_rows.p, rows + first, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(launch_ptnlh_rows(e, e->d_batch_tasks.p, m, e->d_theta_batch.p, theta_stride, e->d_batch_out.p, e->d_batch_rows.p));
         }
-        HIPCHK(hipMemcpyAsync(out.data(), e->d_batch_out, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(out.data(), e->d_batch_out.p, sizeof(double) * 6 * (size_t)m, hipMemcpyDeviceToHost,
                               e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));  // also: host_tasks / out are reused by the next chunk
         for (int t = 0; t < m; t++) {

@@ -28,6 +28,15 @@ for rep in range(6):
             t.evaluate_nnis_batch()
         t.set_boot_samples(freq[None, :].astype("float32")); t.compute_rell()
         t.bionj(bionj_dist)
+        # the scratch of the topology tests, the pairwise distances and parsimony frees itself with the engine (DevBuf)
+        t.ptnlh_reserve(2)
+        two = _rng.uniform(-12.0, -1.0, (2, t.nptn))
+        for r in range(2):
+            t.ptnlh_upload(r, two[r])
+        t.tree_tests([0, 1], two @ freq, 1, weighted=True)
+        if not hasattr(model, "classes"):
+            t.compute_dist()
+        t.compute_parsimony()
         t.close()
     f = free_mb()
     if base is None: base = f
