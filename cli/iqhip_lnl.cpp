@@ -31,6 +31,17 @@
 // function of the file, as in the reference, whose BioNj::create reads it -- iqhip_bionj runs on the device, the tree is
 // written to <prefix>.bionj with the reference's %10.8f lengths, fixNegativeBranch(false) replaces the negative ones and
 // the run goes on as if the tree had been given with -te.  -te, -parstree and -bionjtree exclude each other.
+// With -emrates (the model must have a +R<k> component) the weights and rates of the free-rate model are estimated by EM on
+// the device (PhyloTree::optimizeFreeRatesEM) inside the loop of ModelFactory::optimizeParameters
+// (model/modelfactory.cpp:952-1040) with the substitution model fixed: initial lnL; per round i = 2, 3, ...
+// optimizeAllBranches(min(i, 3)) unless -blfix, then the EM, until the gain is not above 0.01 (params.modeps); a final
+// optimizeAllBranches(100); rescaleRates; all branch lengths times the mean rate.  A bare +R<k> without braces is accepted
+// with this flag only and starts from RateFree::setNCategory's point (equal weights, Gamma(1) mean rates).  It prints the
+// reference's "Site proportion and rates:  (w,r) ..." line and the model string with the estimated +R<k>{...}, which is
+// also what <prefix>.iqhip records.
+// With -wsr it writes <prefix>.rate in the format of RateHeterogeneity::writeSiteRates (model/rateheterogeneity.cpp:56-81):
+// per site the empirical-Bayes posterior mean rate, the best category (ties: the first, where the reference draws) and that
+// category's rate, and prints the "Empirical proportions for each category:" line.  For +G and +R models alike.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -51,15 +62,56 @@
 
 using namespace iqhost;
 
+// the "+R<k>" / "+R<k>{...}" component of a model string: [begin, end) without the '+', and k (0: none given = 4);
+// false when the string has none
+static bool findFreeRate(const std::string &m, size_t &begin, size_t &end, int &k, bool &bare) {
+    size_t pos = m.find('+');
+    while (pos != std::string::npos) {
+        size_t stop = pos + 1;
+        int depth = 0;
+        while (stop < m.size() && (m[stop] != '+' || depth > 0)) {
+            if (m[stop] == '{') depth++;
+            if (m[stop] == '}') depth--;
+            stop++;
+        }
+        const std::string tok = m.substr(pos + 1, stop - pos - 1);
+        if (!tok.empty() && (tok[0] == 'R' || tok[0] == 'r')) {
+            size_t i = 1;
+            int n = 0;
+            while (i < tok.size() && isdigit((unsigned char)tok[i])) n = 10 * n + (tok[i++] - '0');
+            if (i == tok.size() || tok[i] == '{') {
+                begin = pos + 1;
+                end = stop;
+                k = n == 0 ? 4 : n;
+                bare = i == tok.size();
+                return true;
+            }
+        }
+        pos = stop < m.size() ? stop : std::string::npos;
+    }
+    return false;
+}
+
+static std::string freeRateToken(const std::vector<double> &props, const std::vector<double> &rates) {
+    std::string t = "R" + std::to_string(props.size()) + "{";
+    char buf[64];
+    for (size_t c = 0; c < props.size(); c++) {
+        snprintf(buf, sizeof buf, "%s%.17g,%.17g", c ? "," : "", props[c], rates[c]);
+        t += buf;
+    }
+    return t + "}";
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
-            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]]\n"
+            "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
-            "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC\n");
+            "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC;\n"
+            "         +R3{w1,r1,w2,r2,w3,r3}, or with -emrates (weights and rates estimated by EM) also a bare +R3\n");
 }
 
 int main(int argc, char **argv) {
@@ -69,7 +121,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
     int zb = 0, sprrad = 0;
-    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false;
+    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -96,6 +148,8 @@ int main(int argc, char **argv) {
         else if (a == "-parstree") parstree = true;
         else if (a == "-pars") pars = true;
         else if (a == "-bionjtree") bionjtree = true;
+        else if (a == "-emrates") emrates = true;
+        else if (a == "-wsr") wsr = true;
         else if (a == "-sprrad") {
             sprrad = atoi(next().c_str());
             if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
@@ -115,6 +169,17 @@ int main(int argc, char **argv) {
         Alignment aln;
         aln.readFile(aln_file, seq_type);
         printf("Alignment has %d sequences with %d columns and %d patterns\n", aln.getNSeq(), aln.getNSite(), aln.getNPattern());
+        if (emrates) {
+            size_t r0, r1;
+            int k;
+            bool bare;
+            if (!findFreeRate(model_str, r0, r1, k, bare)) throw std::runtime_error("-emrates needs a +R<k> model");
+            if (bare) {   // RateFree::setNCategory's starting point stands in for the missing values
+                std::vector<double> p0, rt0;
+                PhyloTree::freeRateStart(k, p0, rt0);
+                model_str = model_str.substr(0, r0) + freeRateToken(p0, rt0) + model_str.substr(r1);
+            }
+        }
         ModelSpec spec = parseModelString(model_str);
         ModelInputs mi;
         buildModel(spec, aln, mi);  // frequencies from the observed patterns only
@@ -237,7 +302,48 @@ int main(int argc, char **argv) {
         double lnl = tree.computeLikelihood(pattern_lh.data());
         printf("Log-likelihood of the input tree: %.17g\n", lnl);
         const double lnl_input = lnl;
-        if (!blfix) {
+        if (emrates) {
+            if (spec.p_invar > 0.0) throw std::runtime_error("-emrates: +I+R is not supported");
+            const double logl_epsilon = 0.01;   // params.modeps (tools.cpp)
+            double cur_lh = lnl;
+            printf("1. Initial log-likelihood: %.6f\n", cur_lh);
+            int em_steps = 0, em_rounds = 0;
+            for (int i = 2; i < 100; i++) {   // params.num_param_iterations
+                if (!blfix) tree.optimizeAllBranches(std::min(i, 3), logl_epsilon);
+                std::vector<PhyloTree::EmStep> steps;
+                const double new_lh = tree.optimizeFreeRatesEM(&steps);
+                em_steps += (int)steps.size();
+                for (const PhyloTree::EmStep &st : steps) em_rounds += st.rounds;
+                if (new_lh > cur_lh + logl_epsilon) {
+                    cur_lh = new_lh;
+                    printf("%d. Current log-likelihood: %.6f\n", i, cur_lh);
+                } else {
+                    if (!blfix) cur_lh = tree.optimizeAllBranches(100, logl_epsilon);
+                    break;
+                }
+            }
+            // rescaleRates, then branch lengths in substitutions per site (modelfactory.cpp:1035-1040)
+            std::vector<double> props = tree.getProps(), rates = tree.getRates();
+            double mean_rate = 0.0;
+            for (size_t c = 0; c < rates.size(); c++) mean_rate += props[c] * rates[c];
+            for (double &r : rates) r /= mean_rate;
+            tree.setRateCategories(rates.data(), props.data());
+            if (mean_rate != 1.0) tree.scaleLength(mean_rate);
+            tree.clearAllPartialLH();
+            lnl = tree.computeLikelihood(pattern_lh.data());
+            mi.rates = rates;
+            mi.props = props;
+            size_t r0, r1;
+            int k;
+            bool bare;
+            findFreeRate(model_str, r0, r1, k, bare);
+            model_str = model_str.substr(0, r0) + freeRateToken(props, rates) + model_str.substr(r1);
+            printf("EM: %d steps, %d lockstep rounds\n", em_steps, em_rounds);
+            printf("Site proportion and rates: ");
+            for (size_t c = 0; c < rates.size(); c++) printf(" (%g,%g)", props[c], rates[c]);
+            printf("\nModel with estimated rates: %s\n", model_str.c_str());
+            printf("Optimal log-likelihood: %.17g\n", lnl);
+        } else if (!blfix) {
             lnl = tree.optimizeAllBranches();
             printf("Log-likelihood after branch-length optimisation: %.17g\n", lnl);
             tree.clearAllPartialLH();
@@ -269,6 +375,30 @@ int main(int argc, char **argv) {
             out << "rates";
             for (double r : mi.rates) { snprintf(buf, sizeof buf, " %.17g", r); out << buf; }
             out << "\ntree " << tree.getTreeString() << "\n";
+        }
+        if (wsr) {
+            tree.clearAllPartialLH();
+            tree.computeLikelihood();
+            std::vector<double> ptn_rate;
+            std::vector<int> ptn_cat;
+            tree.computePatternRates(ptn_rate, ptn_cat);
+            const std::vector<double> &cat_rate = tree.getRates();
+            std::ofstream out((prefix + ".rate").c_str());
+            if (!out) throw std::runtime_error("cannot write " + prefix + ".rate");
+            out.setf(std::ios::fixed, std::ios::floatfield);
+            out.precision(5);
+            out << "Site\tRate\tCategory\tCategorized_rate" << std::endl;
+            std::vector<int> count(cat_rate.size(), 0);
+            for (int i = 0; i < nsite; i++) {
+                const int ptn = aln.site_pattern[i];
+                out << i + 1 << "\t";
+                if (ptn_rate[ptn] >= 100.0) out << "100.0"; else out << ptn_rate[ptn];   // MAX_SITE_RATE
+                out << "\t" << ptn_cat[ptn] + 1 << "\t" << cat_rate[ptn_cat[ptn]] << std::endl;
+                count[ptn_cat[ptn]]++;
+            }
+            printf("Empirical proportions for each category:");
+            for (int c : count) printf(" %g", (double)c / nsite);
+            printf("\nSite rates printed to %s.rate\n", prefix.c_str());
         }
         if (alrt > 0 || lbp > 0) {
             // bootstrap weightings: nsite sites drawn with replacement, counted per pattern (the unobserved +ASC patterns

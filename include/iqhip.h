@@ -330,6 +330,38 @@ int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *steps, int nst
  * sum_i exp(eval_i r_c len) prop_c theta[ptn][c][i] for the branch of the last iqhip_compute_theta,
  * unscaled, out[ptn*ncat + c]. */
 int iqhip_pattern_lh_cat(iqhip_engine *e, double len, double *out /* nptn*ncat */);
+
+/* EM estimation of +R free-rate weights and rates (RateFree::optimizeWithEM, model/ratefree.cpp:450-579) and empirical-Bayes
+ * site rates (RateGamma::computePatternRates, model/rategamma.cpp:235-258) on the device.  With L_pc the quantity
+ * iqhip_pattern_lh_cat returns for the branch of the last iqhip_compute_theta at length len:
+ * iqhip_em_posteriors (the E-step): W[p][c] = ptn_freq[p] L_pc / sum_c L_pc stays on the device in an engine-owned
+ *   category-major matrix; cat_sum[c] = sum_p W[p][c].  It also leaves per pattern the posterior mean rate
+ *   sum_c r_c L_pc / sum_c L_pc and the best category, the FIRST maximum of L_pc (the reference breaks ties with its random
+ *   number generator).
+ * iqhip_em_fetch_posteriors / iqhip_em_site_rates: what the last E-step left, copied to the host.
+ * iqhip_em_objective: with the rates and weights the engine holds NOW and the theta resident NOW,
+ *   f[c] = sum_p W[p][c] (log(L_pc / prop_c) + (max(sc_a[p], 0) + max(sc_b[p], 0)) LOG_SCALING_THRESHOLD),
+ *   sc_a / sc_b the scale counters of the branch's two ends, W the matrix of the last E-step.  f[c] is the log-likelihood of
+ *   the reference's one-category tree with pattern weights W[.][c] and all lengths scaled by rates[c]
+ *   (optimizeTreeLengthScaling, phylotree.cpp:2106-2133), so one traversal of the C-category engine evaluates the C
+ *   objectives of the M-step at once.  A term with W == 0 contributes 0.
+ *   UNDERFLOW RULE: the engine rescales a pattern only when ALL of its categories are small, so a fast category can
+ *   underflow where the reference's one-category tree would have rescaled.  A term with W > 0 whose L_pc is not a positive
+ *   normal number takes log(DBL_MIN) in place of the logarithm and is counted in floored[c] (NULL: not reported); callers
+ *   treat a non-zero count as "this objective value is a bound, not the value".
+ * All sums are formed in a fixed order without atomics: the same bits on every run.
+ * Plain engines of 4, 20 or 64 states only: IQHIP_ERR_UNSUPPORTED for mixture models, sharded engines and communicator
+ * ranks, +ASC (the reference switches EM off there as well) and embedded state counts; IQHIP_ERR_INVALID for a null
+ * argument, theta not resident, a negative or NaN len, a weight <= 0 (objective), no E-step yet (objective, fetch, site
+ * rates) and planning-only engines.
+ * iqhip_debug_em_timing: with iqhip_timing_enable, ms[0] / ms[1] = the device time (HIP events, milliseconds) of the launches
+ *   of the last iqhip_em_posteriors / iqhip_em_objective call (kernel plus the fold of the sums). */
+int iqhip_em_posteriors(iqhip_engine *e, double len, double *cat_sum /* ncat */);
+int iqhip_em_fetch_posteriors(iqhip_engine *e, double *out /* nptn*ncat, [ptn][cat] */);
+int iqhip_em_site_rates(iqhip_engine *e, double *ptn_rate /* nptn */, int32_t *ptn_cat /* nptn */);
+int iqhip_em_objective(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, double *f /* ncat */,
+                       int64_t *floored /* ncat or NULL */);
+int iqhip_debug_em_timing(iqhip_engine *e, double *ms /* 2 */);
 int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *out /* nptn */);
 int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int nsamples);
 int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *rell /* nsamples */);

@@ -31,6 +31,7 @@ IQHIP_SYMBOLS = [
     "iqhip_fetch_theta", "iqhip_upload_partial", "iqhip_timing_enable", "iqhip_timing_read",
     "iqhip_fetch_pattern_lh_scaled", "iqhip_set_boot_samples", "iqhip_rell", "iqhip_rell_async",
     "iqhip_set_mixture_model", "iqhip_pattern_lh_cat", "iqhip_optimize_branch_batch",
+    "iqhip_em_posteriors", "iqhip_em_fetch_posteriors", "iqhip_em_site_rates", "iqhip_em_objective", "iqhip_debug_em_timing",
     "iqhip_create_sharded", "iqhip_num_shards", "iqhip_shard_range", "iqhip_comm_unique_id", "iqhip_comm_init_rank",
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
@@ -194,6 +195,11 @@ def libiqhip():
     lib.iqhip_update_partials_async.argtypes = [vp, C.POINTER(NodeOp), C.c_int]
     lib.iqhip_lnl_from_theta_async.argtypes = [vp, C.c_double]
     lib.iqhip_newton_host_init.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp]
+    lib.iqhip_em_posteriors.argtypes = [vp, C.c_double, dp]
+    lib.iqhip_em_fetch_posteriors.argtypes = [vp, dp]
+    lib.iqhip_debug_em_timing.argtypes = [vp, dp]
+    lib.iqhip_em_site_rates.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    lib.iqhip_em_objective.argtypes = [vp, BranchEnd, BranchEnd, C.c_double, dp, C.POINTER(C.c_int64)]
     lib.iqhip_newton_host_update.argtypes = [vp, C.c_double, C.c_double, dp, C.POINTER(C.c_int)]
     lib.iqhip_newton_host_result.argtypes = [vp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.iqhip_timing_enable.argtypes = [vp, C.c_int]
@@ -324,6 +330,14 @@ def libiqhost():
     lib.iqhost_compute_pattern_likelihood.argtypes = [vp, dp]
     lib.iqhost_compute_pattern_lh_cat.argtypes = [vp, dp]
     lib.iqhost_set_boot_samples.argtypes = [vp, C.POINTER(C.c_float), C.c_int]
+    lib.iqhost_brent_init.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, dp]
+    lib.iqhost_brent_update.argtypes = [vp, C.c_double, dp, C.POINTER(C.c_int)]
+    lib.iqhost_brent_result.argtypes = [vp, dp, dp, C.POINTER(C.c_int)]
+    lib.iqhost_free_rate_start.argtypes = [C.c_int, dp, dp]
+    lib.iqhost_em_posteriors.argtypes = [vp, dp, dp]
+    lib.iqhost_em_objective.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int64)]
+    lib.iqhost_site_rates.argtypes = [vp, dp, C.POINTER(C.c_int)]
+    lib.iqhost_optimize_free_rates_em.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int), dp, C.c_int]
     lib.iqhost_compute_rell.argtypes = [vp, dp, C.c_int]
     lib.iqhost_last_plan.argtypes = [vp, C.POINTER(C.c_int), dp, C.POINTER(C.c_uint64), C.c_int]
     lib.iqhost_num_partial_lh_computations.argtypes = [vp]
@@ -491,6 +505,42 @@ class NewtonStateMachine:
         if self.lib.iqhip_newton_host_result(self.buf, C.byref(optx), C.byref(d2l), C.byref(n), C.byref(st)) != 0:
             raise HostError(self.lib.iqhip_last_error().decode())
         return optx.value, d2l.value, n.value, st.value
+
+
+class BrentStateMachine:
+    """Optimization::minimizeOneDimen over brent_opt as the host mirror's step-at-a-time state machine (iqhost_brent_*):
+    evaluate the function at .x and feed the value to update() until .done; then result() -> (optx, fx, nevals)."""
+
+    def __init__(self, xmin, xguess, xmax, tol):
+        self.lib = libiqhost()
+        self.buf = C.create_string_buffer(self.lib.iqhost_brent_state_bytes() + 8)
+        self.state = C.c_void_p((C.addressof(self.buf) + 7) & ~7)
+        x = C.c_double()
+        if self.lib.iqhost_brent_init(self.state, xmin, xguess, xmax, tol, C.byref(x)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self.x, self.done = x.value, False
+
+    def update(self, f):
+        x, d = C.c_double(), C.c_int()
+        if self.lib.iqhost_brent_update(self.state, float(f), C.byref(x), C.byref(d)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self.x, self.done = x.value, bool(d.value)
+        return self.x
+
+    def result(self):
+        optx, fx, n = C.c_double(), C.c_double(), C.c_int()
+        if self.lib.iqhost_brent_result(self.state, C.byref(optx), C.byref(fx), C.byref(n)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return optx.value, fx.value, n.value
+
+
+def free_rate_start(k):
+    """RateFree::setNCategory: the +R<k> starting point -> (props, rates): equal weights, gamma_rates(1.0, k)."""
+    lib = libiqhost()
+    props, rates = np.zeros(max(1, int(k))), np.zeros(max(1, int(k)))
+    if lib.iqhost_free_rate_start(int(k), _dptr(props), _dptr(rates)) != 0:
+        raise HostError(lib.iqhost_last_error().decode())
+    return props, rates
 
 
 def comm_unique_id():
@@ -1168,6 +1218,41 @@ class PhyloTree:
         """_pattern_lh_cat[nptn, ncat] of the current branch (unscaled category likelihoods)."""
         out = np.zeros((self.nptn, self.ncat))
         self._chk(self.lib.iqhost_compute_pattern_lh_cat(self.h, _dptr(out)))
+        return out
+
+    def em_posteriors(self):
+        """One E-step of the +R EM on the current branch (iqhip_em_posteriors) -> (W[nptn, ncat], cat_sum[ncat]):
+        W[p, c] = ptn_freq[p] * L_pc / sum_c L_pc, cat_sum = its column sums as the device summed them."""
+        W, s = np.zeros((self.nptn, self.ncat)), np.zeros(self.ncat)
+        self._chk(self.lib.iqhost_em_posteriors(self.h, _dptr(W), _dptr(s)))
+        return W, s
+
+    def em_objective(self, a, b):
+        """iqhip_em_objective for the branch a -> b with the model the tree holds now, after em_posteriors()
+        -> (F[ncat], floored[ncat])."""
+        f, fl = np.zeros(self.ncat), np.zeros(self.ncat, dtype=np.int64)
+        self._chk(self.lib.iqhost_em_objective(self.h, a, b, _dptr(f), fl.ctypes.data_as(C.POINTER(C.c_int64))))
+        return f, fl
+
+    def site_rates(self):
+        """RateGamma::computePatternRates -> (posterior mean rate[nptn], best category[nptn]; ties: the first)."""
+        r, c = np.zeros(self.nptn), np.zeros(self.nptn, dtype=np.int32)
+        self._chk(self.lib.iqhost_site_rates(self.h, _dptr(r), c.ctypes.data_as(C.POINTER(C.c_int))))
+        return r, c
+
+    def optimize_free_rates_em(self, trace=False):
+        """PhyloTree::optimizeFreeRatesEM (RateFree::optimizeWithEM with the rate searches in lockstep on the device)
+        -> dict(props, rates, lnl, steps[, trace: per EM step dict(lnl_before, rounds, props, rates, evals, floored)])."""
+        k = self.ncat
+        props, rates, lnl, n = np.zeros(k), np.zeros(k), C.c_double(), C.c_int()
+        tr = np.zeros((max(1, k), 2 + 4 * k))
+        self._chk(self.lib.iqhost_optimize_free_rates_em(self.h, _dptr(props), _dptr(rates), C.byref(lnl), C.byref(n),
+                                                         _dptr(tr), tr.shape[0]))
+        out = dict(props=props, rates=rates, lnl=lnl.value, steps=n.value)
+        if trace:
+            out["trace"] = [dict(lnl_before=row[0], rounds=int(row[1]), props=row[2:2 + k].copy(), rates=row[2 + k:2 + 2 * k].copy(),
+                                 evals=row[2 + 2 * k:2 + 3 * k].astype(int), floored=row[2 + 3 * k:2 + 4 * k].astype(np.int64))
+                            for row in tr[:n.value]]
         return out
 
     def set_boot_samples(self, samples):

@@ -604,6 +604,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
         e->mfma_pipelined = pipelined;
         e->plan_cache.invalidate();
     }
+    e->h_props.assign(props, props + e->ncat);   // (iqhip_em_objective checks the weights it divides by)
     e->nclass = nclass;
     e->state_unknown = state_unknown;
     e->model_set = true;

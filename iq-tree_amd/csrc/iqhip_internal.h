@@ -468,6 +468,16 @@ struct iqhip_engine {
         iqhip::DevBuf<double> dbl;      // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
         iqhip::DevBuf<int32_t> ints;    // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
     } tt;
+    // EM for +R free-rate models and empirical-Bayes site rates (ptnlh.hip, kernels_em.hip): what the last E-step left -- the
+    // posterior matrix W [ncat][nptn_pad] (category-major, padding patterns 0), per pattern its posterior mean rate and
+    // best category -- and the scratch of the sums (workgroup rows, folded values).  valid: an E-step has run for an
+    // engine of these dimensions
+    struct {
+        iqhip::DevBuf<double> w, rate, part, out;
+        iqhip::DevBuf<int32_t> cat;
+        bool valid = false;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_em_timing: the last E-step / objective launches (while timing is enabled)
+    } em;
     // pairwise ML distances (pairdist.hip, kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
     // coefficients evec[i][k] * inv_evec[k][j] of the call's model [n][n][n], per pair the initial distance and the result
     // {optx, d2l, evaluations, status}; with iqhip_timing_enable the device time of the last iqhip_pair_distances call
@@ -1011,6 +1021,11 @@ hipError_t launch_sweep4(iqhip_engine *e, const SweepOp *d_ops, const SweepStep 
 hipError_t launch_pattern_lh_scaled(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double *out);
 hipError_t launch_rell(iqhip_engine *e, double *out);
 hipError_t launch_pattern_lh_cat(iqhip_engine *e, double len, double *out);
+// kernels_em.hip: part holds one row of ncat (E-step) or 2 ncat (objective) doubles per 256 patterns of nptn_pad
+hipError_t launch_em_posteriors(iqhip_engine *e, double len, double *W, double *ptn_rate, int32_t *ptn_cat, double *part,
+                                double *out);
+hipError_t launch_em_objective(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double len, const double *W,
+                               double *part, double *out);
 // rows of the per-pattern store from a chunk of k_newton_batch: task t of the m tasks -> store row d_rows[t] (< 0: none)
 hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const double *theta_base, size_t theta_stride,
                              const double *batch_out, const int32_t *d_rows);

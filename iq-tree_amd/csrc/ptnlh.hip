@@ -1,6 +1,7 @@
 // ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: UFBoot / RELL, the store of
-// per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests.  Host code only; the kernels are
-// in kernels_rell.hip, kernels_alrt.hip and kernels_topo.hip.
+// per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests, the EM for +R free-rate models and
+// the empirical-Bayes site rates.  Host code only; the kernels are in kernels_rell.hip, kernels_alrt.hip, kernels_topo.hip
+// and kernels_em.hip.
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -59,6 +60,126 @@ extern "C" int iqhip_pattern_lh_cat(iqhip_engine *e, double len, double *out) {
     if (s == hipSuccess) s = hipStreamSynchronize(e->stream);
     hipFree(d_out);
     if (s != hipSuccess) return fail(IQHIP_ERR_HIP, hipGetErrorString(s));
+    return IQHIP_OK;
+}
+
+// ---- EM for +R free-rate models, empirical-Bayes site rates (kernels_em.hip) ----------------------------------------
+// plain engines of 4 / 20 / 64 states only; needs_estep: the call reads what the last E-step left
+static int em_engine(iqhip_engine *e, const char *what, bool needs_theta, bool needs_estep) {
+    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
+    if (e->nclass > 1) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for mixture models");
+    if (e->asc_active || e->n_unobs > 0)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available with ascertainment bias correction");
+    if (e->embed2 || e->n_user != e->n)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
+    if (needs_theta && !e->theta_valid) return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_compute_theta first");
+    if (needs_estep && (!e->em.valid || e->em.w.cap < (size_t)e->ncat * (size_t)e->nptn_pad))
+        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_em_posteriors first");
+    return IQHIP_OK;
+}
+
+static size_t em_part_rows(const iqhip_engine *e) { return (size_t)((e->nptn_pad + 255) / 256); }
+
+// with iqhip_timing_enable: HIP events around the launches of one call; stop() after the stream has drained
+struct EmTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    iqhip_engine *e;
+    explicit EmTimer(iqhip_engine *e_) : e(e_) {
+        if (e->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) hipEventRecord(ev[0], e->stream);
+    }
+    void mark() { if (ev[1]) hipEventRecord(ev[1], e->stream); }
+    void stop(double *ms) {
+        float t = 0.0f;
+        if (ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) *ms = t;
+    }
+    ~EmTimer() {
+        for (hipEvent_t x : ev) if (x) hipEventDestroy(x);
+    }
+};
+
+extern "C" int iqhip_debug_em_timing(iqhip_engine *e, double *ms) {
+    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_em_timing: null argument");
+    ms[0] = e->em.ms[0];
+    ms[1] = e->em.ms[1];
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_em_posteriors(iqhip_engine *e, double len, double *cat_sum) {
+    if (!e || !cat_sum) return fail(IQHIP_ERR_INVALID, "iqhip_em_posteriors: null argument");
+    int rc = em_engine(e, "iqhip_em_posteriors", true, false);
+    if (rc) return rc;
+    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_posteriors: negative or NaN branch length");
+    HIPCHK(use_device(e));
+    const size_t P = (size_t)e->nptn_pad, C = (size_t)e->ncat;
+    e->em.valid = false;
+    HIPCHK(e->em.w.ensure(e, C * P));
+    HIPCHK(e->em.rate.ensure(e, P));
+    HIPCHK(e->em.cat.ensure(e, P));
+    HIPCHK(e->em.part.ensure(e, em_part_rows(e) * 2 * C));
+    HIPCHK(e->em.out.ensure(e, 2 * C));
+    EmTimer timer(e);
+    HIPCHK(launch_em_posteriors(e, len, e->em.w.p, e->em.rate.p, e->em.cat.p, e->em.part.p, e->em.out.p));
+    timer.mark();
+    HIPCHK(hipMemcpyAsync(cat_sum, e->em.out.p, sizeof(double) * C, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    timer.stop(&e->em.ms[0]);
+    e->em.valid = true;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_em_fetch_posteriors(iqhip_engine *e, double *out) {
+    if (!e || !out) return fail(IQHIP_ERR_INVALID, "iqhip_em_fetch_posteriors: null argument");
+    int rc = em_engine(e, "iqhip_em_fetch_posteriors", false, true);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    const size_t P = (size_t)e->nptn_pad, C = (size_t)e->ncat, N = (size_t)e->nptn;
+    std::vector<double> w(C * P);
+    HIPCHK(hipMemcpyAsync(w.data(), e->em.w.p, sizeof(double) * w.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t p = 0; p < N; p++)
+        for (size_t c = 0; c < C; c++) out[p * C + c] = w[c * P + p];
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_em_site_rates(iqhip_engine *e, double *ptn_rate, int32_t *ptn_cat) {
+    if (!e || !ptn_rate || !ptn_cat) return fail(IQHIP_ERR_INVALID, "iqhip_em_site_rates: null argument");
+    int rc = em_engine(e, "iqhip_em_site_rates", false, true);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    HIPCHK(hipMemcpyAsync(ptn_rate, e->em.rate.p, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(ptn_cat, e->em.cat.p, sizeof(int32_t) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_em_objective(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, double *f,
+                                  int64_t *floored) {
+    if (!e || !f) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: null argument");
+    int rc = em_engine(e, "iqhip_em_objective", true, true);
+    if (rc) return rc;
+    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: negative or NaN branch length");
+    for (int c = 0; c < e->ncat; c++)
+        if (!(e->h_props[c] > 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: every category weight must be > 0");
+    HIPCHK(use_device(e));
+    const int16_t *sc[2];
+    rc = branch_scale_counters(e, a, b, sc);
+    if (rc) return rc;
+    const size_t C = (size_t)e->ncat;
+    HIPCHK(e->em.part.ensure(e, em_part_rows(e) * 2 * C));
+    HIPCHK(e->em.out.ensure(e, 2 * C));
+    EmTimer timer(e);
+    HIPCHK(launch_em_objective(e, sc[0], sc[1], len, e->em.w.p, e->em.part.p, e->em.out.p));
+    timer.mark();
+    std::vector<double> res(2 * C);
+    HIPCHK(hipMemcpyAsync(res.data(), e->em.out.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    timer.stop(&e->em.ms[1]);
+    for (size_t c = 0; c < C; c++) {
+        f[c] = res[c];
+        if (floored) floored[c] = (int64_t)res[C + c];
+    }
     return IQHIP_OK;
 }
 

@@ -3,9 +3,12 @@
 // the repository drives the same call sequence the reference's C++ callers use.
 #include <string.h>
 
+#include <new>
+
 #include <string>
 #include <vector>
 
+#include "brent_host.h"
 #include "phylo_host.h"
 
 using namespace iqhost;
@@ -229,6 +232,92 @@ int iqhost_fetch_partial(void *h, int from, int to, double *out) {
 int iqhost_fetch_pattern_lh(void *h, double *out) { IQHOST_TRY(((PhyloTree *)h)->fetchPatternLh(out)); }
 int iqhost_compute_pattern_likelihood(void *h, double *out) { IQHOST_TRY(((PhyloTree *)h)->computePatternLikelihood(out)); }
 int iqhost_compute_pattern_lh_cat(void *h, double *out) { IQHOST_TRY(((PhyloTree *)h)->computePatternLhCat(out)); }
+// ---- Brent's minimiser as a state machine (brent_host.h); state: IQHOST_BRENT_STATE_BYTES opaque bytes, 8-byte aligned
+#define IQHOST_BRENT_STATE_BYTES 512
+static_assert(sizeof(BrentMachine) <= IQHOST_BRENT_STATE_BYTES, "BrentMachine must fit its opaque state");
+int iqhost_brent_state_bytes(void) { return IQHOST_BRENT_STATE_BYTES; }
+int iqhost_brent_init(void *state, double xmin, double xguess, double xmax, double tolerance, double *first_x) {
+    IQHOST_TRY({
+        if (!state || !first_x) throw std::runtime_error("iqhost_brent_init: null argument");
+        if (!(xmin <= xmax) || xguess != xguess || !(tolerance > 0.0)) throw std::runtime_error("iqhost_brent_init: bad bounds");
+        *first_x = (new (state) BrentMachine())->init(xmin, xguess, xmax, tolerance);
+    });
+}
+int iqhost_brent_update(void *state, double f, double *next_x, int *done) {
+    IQHOST_TRY({
+        if (!state || !next_x || !done) throw std::runtime_error("iqhost_brent_update: null argument");
+        BrentMachine *m = (BrentMachine *)state;
+        *next_x = m->update(f);
+        *done = m->done ? 1 : 0;
+    });
+}
+int iqhost_brent_result(const void *state, double *optx, double *fx, int *nevals) {
+    IQHOST_TRY({
+        if (!state || !optx || !fx || !nevals) throw std::runtime_error("iqhost_brent_result: null argument");
+        const BrentMachine *m = (const BrentMachine *)state;
+        if (!m->done) throw std::runtime_error("iqhost_brent_result: the search has not finished");
+        *optx = m->optx;
+        *fx = m->fx_opt;
+        *nevals = m->nevals;
+    });
+}
+int iqhost_free_rate_start(int k, double *props, double *rates) {
+    IQHOST_TRY({
+        std::vector<double> p;
+        std::vector<double> r;
+        PhyloTree::freeRateStart(k, p, r);
+        memcpy(props, p.data(), sizeof(double) * p.size());
+        memcpy(rates, r.data(), sizeof(double) * r.size());
+    });
+}
+// one E-step on the current branch; W: NULL or nptn * ncat doubles [ptn][cat]
+int iqhost_em_posteriors(void *h, double *W, double *cat_sum) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        t->emPosteriors(cat_sum);
+        if (W && iqhip_em_fetch_posteriors(t->engine, W) != 0) throw std::runtime_error(iqhip_last_error());
+    });
+}
+int iqhost_em_objective(void *h, int a, int b, double *f, int64_t *floored) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        t->emObjective(nei(t, a, b), t->nodes[a], f, floored);
+    });
+}
+int iqhost_site_rates(void *h, double *rates, int *cats) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<double> r;
+        std::vector<int> c;
+        t->computePatternRates(r, c);
+        memcpy(rates, r.data(), sizeof(double) * r.size());
+        memcpy(cats, c.data(), sizeof(int) * c.size());
+    });
+}
+// props / rates: ncat each; trace: NULL or rows of 2 + 4 ncat doubles {lnl_before, rounds, props, rates, evals, floored},
+// at most trace_cap rows (ncat suffice); *nsteps = the EM steps taken
+int iqhost_optimize_free_rates_em(void *h, double *props, double *rates, double *lnl, int *nsteps, double *trace, int trace_cap) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        std::vector<PhyloTree::EmStep> steps;
+        *lnl = t->optimizeFreeRatesEM(&steps);
+        const size_t C = (size_t)t->ncat;
+        memcpy(props, t->getProps().data(), sizeof(double) * C);
+        memcpy(rates, t->getRates().data(), sizeof(double) * C);
+        *nsteps = (int)steps.size();
+        for (size_t k = 0; k < steps.size() && trace && (int)k < trace_cap; k++) {
+            double *row = trace + k * (2 + 4 * C);
+            row[0] = steps[k].lnl_before;
+            row[1] = steps[k].rounds;
+            for (size_t c = 0; c < C; c++) {
+                row[2 + c] = steps[k].props[c];
+                row[2 + C + c] = steps[k].rates[c];
+                row[2 + 2 * C + c] = steps[k].evals[c];
+                row[2 + 3 * C + c] = (double)steps[k].floored[c];
+            }
+        }
+    });
+}
 int iqhost_set_boot_samples(void *h, const float *samples, int nsamples) {
     IQHOST_TRY(((PhyloTree *)h)->setBootSamples(samples, nsamples));
 }

@@ -2,6 +2,8 @@
 // vectors happens in libiqhip.so.
 #include <time.h>
 #include "phylo_host.h"
+#include "brent_host.h"
+#include "model_host.h"
 #include "alignment_host.h"
 
 #include <assert.h>
@@ -1936,6 +1938,151 @@ void PhyloTree::computePatternLhCat(double *ptn_lh_cat) {
     theta_computed = false;
     computeLikelihoodDerv(current_it, current_it_back->node, df, ddf);  // (re)builds theta of current_it
     check(iqhip_pattern_lh_cat(engine, current_it->length, ptn_lh_cat), "iqhip_pattern_lh_cat");
+}
+
+// =========================================================================================
+// EM for +R free-rate models, empirical-Bayes site rates (kernels_em.hip; model/ratefree.cpp:450-579)
+// =========================================================================================
+void PhyloTree::setRateCategories(const double *rates, const double *props) {
+    if (m_rates.empty()) throw std::runtime_error("setRateCategories before setModel");
+    m_rates.assign(rates, rates + ncat);
+    m_props.assign(props, props + ncat);
+    inputs_dirty = model_dirty = true;
+    theta_computed = false;
+}
+
+void PhyloTree::scaleLength(double norm) {
+    for (PhyloNeighbor *nb : all_neighbors) nb->length *= norm;
+    theta_computed = false;
+}
+
+void PhyloTree::freeRateStart(int k, std::vector<double> &props, std::vector<double> &rates) {
+    if (k < 1) throw std::runtime_error("freeRateStart: at least one category");
+    props.assign((size_t)k, 1.0 / k);
+    rates.assign((size_t)k, 1.0);
+    discreteGammaRates(1.0, k, false, 0.0, rates.data());
+}
+
+void PhyloTree::emPosteriors(double *cat_sum) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (!current_it) throw std::runtime_error("emPosteriors before computeLikelihood");
+    double df, ddf;
+    theta_computed = false;
+    computeLikelihoodDerv(current_it, current_it_back->node, df, ddf);  // (re)builds theta of current_it
+    check(iqhip_em_posteriors(engine, current_it->length, cat_sum), "iqhip_em_posteriors");
+}
+
+void PhyloTree::emObjective(PhyloNeighbor *dad_branch, PhyloNode *dad, double *f, int64_t *floored) {
+    if (!engine) throw std::runtime_error("no engine");
+    PhyloNeighbor *back = dad_branch->node->findNeighbor(dad);
+    if (!back) throw std::runtime_error("emObjective: not a branch");
+    current_it = dad_branch;
+    current_it_back = back;
+    double df, ddf;
+    theta_computed = false;
+    computeLikelihoodDerv(dad_branch, dad, df, ddf);
+    check(iqhip_em_objective(engine, branchEnd(dad_branch), branchEnd(back), dad_branch->length, f, floored),
+          "iqhip_em_objective");
+}
+
+void PhyloTree::computePatternRates(std::vector<double> &rates_out, std::vector<int> &cat_out) {
+    std::vector<double> cat_sum((size_t)ncat);
+    emPosteriors(cat_sum.data());
+    rates_out.assign((size_t)nptn, 0.0);
+    std::vector<int32_t> cat((size_t)nptn);
+    check(iqhip_em_site_rates(engine, rates_out.data(), cat.data()), "iqhip_em_site_rates");
+    cat_out.assign(cat.begin(), cat.end());
+}
+
+double PhyloTree::optimizeFreeRatesEM(std::vector<EmStep> *trace) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (nmixture > 1) throw std::runtime_error("optimizeFreeRatesEM: mixture models are not supported (ModelMixture::optimizeWithEM)");
+    if (n_unobserved > 0) throw std::runtime_error("optimizeFreeRatesEM: +ASC is not supported (the reference switches EM off for it)");
+    for (double v : ptn_invar)
+        if (v != 0.0) throw std::runtime_error("optimizeFreeRatesEM: +I+R (p_invar > 0) is not supported");
+    const double MIN_PROP = 1e-4;
+    const int nmix = ncat;
+    double nsite = 0.0;   // getAlnNSite
+    for (double f : ptn_freq) nsite += f;
+    std::vector<double> prop(m_props), rates(m_rates), new_prop((size_t)nmix), f((size_t)nmix);
+    std::vector<int64_t> floored((size_t)nmix);
+    if (trace) trace->clear();
+    for (int step = 0; step < nmix; step++) {
+        EmStep rec;
+        rec.evals.assign((size_t)nmix, 0);
+        rec.floored.assign((size_t)nmix, 0);
+        // E-step on the current parameters (computePatternLhCat: a likelihood evaluation, then theta of its branch)
+        rec.lnl_before = computeLikelihood();
+        emPosteriors(new_prop.data());
+        // M-step, weights
+        int maxpropid = 0;
+        for (int c = 0; c < nmix; c++) {
+            new_prop[c] = new_prop[c] / nsite;
+            if (new_prop[c] > new_prop[maxpropid]) maxpropid = c;
+        }
+        bool zero_prop = false;
+        for (int c = 0; c < nmix; c++)
+            if (new_prop[c] < MIN_PROP) {
+                new_prop[maxpropid] -= (MIN_PROP - new_prop[c]);
+                new_prop[c] = MIN_PROP;
+                zero_prop = true;
+            }
+        if (zero_prop) {   // the reference breaks BEFORE the weights are assigned
+            rec.props = prop;
+            rec.rates = rates;
+            if (trace) trace->push_back(rec);
+            break;
+        }
+        bool converged = true;
+        for (int c = 0; c < nmix; c++) {
+            converged = converged && (fabs(prop[c] - new_prop[c]) < 1e-4);
+            prop[c] = new_prop[c];
+        }
+        // M-step, rates: optimizeTreeLengthScaling(MIN_PROP, rates[c], 1 / prop[c], 0.001) for all c in lockstep
+        std::vector<BrentMachine> bm((size_t)nmix);
+        std::vector<double> trial(rates);
+        int running = 0;
+        for (int c = 0; c < nmix; c++) {
+            const double scaling = rates[c];
+            trial[c] = bm[c].init(std::min(scaling, MIN_PROP), scaling, std::max(1.0 / prop[c], scaling), std::max(0.001, 0.001));
+            running++;
+        }
+        while (running > 0) {
+            setRateCategories(trial.data(), prop.data());
+            clearAllPartialLH();
+            computeLikelihood();
+            emObjective(current_it, current_it_back->node, f.data(), floored.data());
+            rec.rounds++;
+            for (int c = 0; c < nmix; c++) {
+                if (bm[c].done) continue;
+                rec.floored[c] += floored[c];
+                const double next = bm[c].update(-f[c]);
+                rec.evals[c]++;
+                if (bm[c].done) {
+                    running--;
+                    trial[c] = bm[c].optx;   // a finished machine keeps its accepted rate
+                } else
+                    trial[c] = next;
+            }
+        }
+        double sum = 0.0;
+        for (int c = 0; c < nmix; c++) {
+            const double scaling = bm[c].optx;
+            converged = converged && (fabs(rates[c] - scaling) < 1e-4);
+            rates[c] = scaling;
+            sum += prop[c] * rates[c];   // (computed and never used, as in the reference)
+        }
+        (void)sum;
+        setRateCategories(rates.data(), prop.data());
+        clearAllPartialLH();
+        rec.props = prop;
+        rec.rates = rates;
+        if (trace) trace->push_back(rec);
+        if (converged) break;
+    }
+    setRateCategories(rates.data(), prop.data());
+    clearAllPartialLH();
+    return computeLikelihood();
 }
 
 void PhyloTree::setBootSamples(const float *samples, int nsamples) {

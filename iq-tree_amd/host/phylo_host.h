@@ -316,6 +316,39 @@ public:
     void computePatternLikelihood(double *ptn_lh);
     // _pattern_lh_cat[ptn*ncat + c] of the current branch (phylotree.cpp:1119-1124 -> scalar kernels), unscaled
     void computePatternLhCat(double *ptn_lh_cat);
+    // ---- EM estimation of +R free-rate models (RateFree::optimizeWithEM, model/ratefree.cpp:450-579) on the device ------
+    // The reference optimises the rate of category c by Brent's method on a tree-length scaling of a one-category copy of
+    // the tree whose pattern weights are the posteriors of c -- C x (3 .. ~20) one-category traversals per EM step, one after
+    // the other.  A one-category tree with all lengths scaled by s IS a category of rate s, so here the C Brent searches
+    // (BrentMachine, brent_host.h) advance in lockstep on the C-category engine: per round every unfinished machine puts its
+    // trial point into rates[c], ONE traversal runs, and ONE iqhip_em_objective returns all C objective values.  An EM step
+    // costs 1 + max_c(evals_c) traversals instead of sum_c evals_c, and no nptn x ncat matrix crosses to the host.
+    // Rates are NOT renormalised here (the reference's sum += prop[c] * rates[c] is computed and never used): that is the
+    // caller's rescaleRates.  Refuses +I+R (p_invar > 0), mixtures and +ASC.  Returns the lnL at the estimated parameters.
+    struct EmStep {
+        std::vector<double> props, rates;   // after the step (unchanged when the step broke off before assigning them)
+        double lnl_before = 0.0;
+        std::vector<int> evals;             // Brent evaluations per category
+        int rounds = 0;                     // lockstep rounds = traversals spent on the rates
+        std::vector<int64_t> floored;       // floored objective terms per category, summed over the rounds (include/iqhip.h)
+    };
+    double optimizeFreeRatesEM(std::vector<EmStep> *trace = nullptr);
+    // one E-step on current_it (theta is rebuilt): cat_sum[ncat]; W stays on the device (iqhip_em_fetch_posteriors)
+    void emPosteriors(double *cat_sum);
+    // the M-step objectives of all categories for the branch dad_branch (theta is rebuilt), after an E-step
+    void emObjective(PhyloNeighbor *dad_branch, PhyloNode *dad, double *f, int64_t *floored);
+    // RateGamma::computePatternRates (model/rategamma.cpp:235-258): one E-step plus iqhip_em_site_rates; ties go to the
+    // first best category
+    void computePatternRates(std::vector<double> &rates_out, std::vector<int> &cat_out);
+    // RateFree::setNCategory (model/ratefree.cpp:81-90): equal weights and the discrete-Gamma mean rates of shape 1
+    static void freeRateStart(int k, std::vector<double> &props, std::vector<double> &rates);
+    // the category rates and weights of the current model; setRateCategories replaces them (same eigen-system; every
+    // likelihood vector is stale afterwards: clearAllPartialLH)
+    const std::vector<double> &getRates() const { return m_rates; }
+    const std::vector<double> &getProps() const { return m_props; }
+    void setRateCategories(const double *rates, const double *props);
+    void scaleLength(double norm);   // mtree.cpp: every branch length times norm
+
     // UFBoot: boot_samples uploaded once; computeRELL = saveCurrentTree's dot products, on the device
     void setBootSamples(const float *samples /*[nsamples][nptn]*/, int nsamples);
     // the same matrix drawn on the device (iqhip_gen_boot_samples): nsamples replicates of ndraws sites each
