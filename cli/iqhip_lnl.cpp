@@ -42,6 +42,15 @@
 // With -wsr it writes <prefix>.rate in the format of RateHeterogeneity::writeSiteRates (model/rateheterogeneity.cpp:56-81):
 // per site the empirical-Bayes posterior mean rate, the best category (ties: the first, where the reference draws) and that
 // category's rate, and prints the "Empirical proportions for each category:" line.  For +G and +R models alike.
+// -m also takes the reference's MIX{m1[:rate[:weight]],m2,...} over the model names above, each class with its own {params}
+// and +F{..}, followed by the rate suffixes (ModelMixture::initMixture): weights 1 / k unless given, normalised to sum 1,
+// class rates rescaled to a global rate of 1, components in [class][rate] order.  With -mixweights the class weights are
+// estimated by EM on the device (PhyloTree::optimizeMixtureWeights = ModelMixture::optimizeWeights) inside the same
+// parameter / branch-length loop as -emrates; it prints the reference's "Mixture weights: w1 w2 ..." line and the model
+// string with the estimated :rate:weight fields, which is also what <prefix>.iqhip records.  Before that the class rates are
+// divided by their mean under the new weights and all branch lengths multiplied by it (likelihood unchanged), so the printed
+// string, read back, is the model of the printed tree.  -mixweights refuses +I (the category rates would follow p_invar);
+// -emrates, -wsr and +ASC refuse mixtures.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -102,16 +111,55 @@ static std::string freeRateToken(const std::vector<double> &props, const std::ve
     return t + "}";
 }
 
+// "MIX{...}" at the head of a model string rewritten with the given class rates and weights as :rate:weight fields
+static std::string mixtureString(const std::string &m, const std::vector<double> &rates, const std::vector<double> &weights) {
+    size_t close = 4;
+    int depth = 1;
+    while (close < m.size() && depth > 0) {
+        if (m[close] == '{') depth++;
+        if (m[close] == '}') depth--;
+        close++;
+    }
+    std::string out = m.substr(0, 4);
+    size_t start = 4, cls = 0;
+    depth = 0;
+    for (size_t i = 4; i < close; i++) {
+        if (m[i] == '{') depth++;
+        const bool last = i + 1 == close;
+        if (m[i] == '}' && !last) depth--;
+        if ((m[i] == ',' && depth == 0) || last) {
+            std::string item = m.substr(start, i - start);
+            int d = 0;
+            for (size_t k = 0; k < item.size(); k++) {
+                if (item[k] == '{') d++;
+                if (item[k] == '}') d--;
+                if (item[k] == ':' && d == 0) {
+                    item.resize(k);
+                    break;
+                }
+            }
+            char buf[80];
+            snprintf(buf, sizeof buf, ":%.17g:%.17g", rates[cls], weights[cls]);
+            out += (cls ? "," : "") + item + buf;
+            cls++;
+            start = i + 1;
+        }
+    }
+    return out + "}" + m.substr(close);
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
+            "                 [-mixweights]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC;\n"
-            "         +R3{w1,r1,w2,r2,w3,r3}, or with -emrates (weights and rates estimated by EM) also a bare +R3\n");
+            "         +R3{w1,r1,w2,r2,w3,r3}, or with -emrates (weights and rates estimated by EM) also a bare +R3;\n"
+            "         'MIX{JC,HKY{2.0}:1.5,GTR{..}+F{..}:0.5:0.2}+G4{0.8}' (class[:rate[:weight]]); -mixweights estimates the weights by EM\n");
 }
 
 int main(int argc, char **argv) {
@@ -121,7 +169,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
     int zb = 0, sprrad = 0;
-    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false;
+    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -150,6 +198,7 @@ int main(int argc, char **argv) {
         else if (a == "-bionjtree") bionjtree = true;
         else if (a == "-emrates") emrates = true;
         else if (a == "-wsr") wsr = true;
+        else if (a == "-mixweights") mixweights = true;
         else if (a == "-sprrad") {
             sprrad = atoi(next().c_str());
             if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
@@ -184,6 +233,15 @@ int main(int argc, char **argv) {
         ModelInputs mi;
         buildModel(spec, aln, mi);  // frequencies from the observed patterns only
         const int nsite = aln.getNSite();
+        const bool mixture = mi.nclass > 1;
+        if (mixweights && !mixture) throw std::runtime_error("-mixweights needs a MIX{...} model");
+        // (the reference's setPInvar also replaces the category rates: 1 / (1 - p) for +I alone, the Gamma rates over 1 - p with
+        // +G; the re-send of weights and ptn_invar does not restate that)
+        if (mixweights && spec.p_invar > 0.0)
+            throw std::runtime_error("-mixweights: +I is not supported (the category rates would follow p_invar)");
+        if (mixture && (emrates || wsr)) throw std::runtime_error("-emrates and -wsr are not available for mixture models");
+        if (mixture && spec.ascertainment) throw std::runtime_error("Mixture model +ASC is not supported yet");
+        if (mixture && !mldist_file.empty()) throw std::runtime_error("-mldist and -bionjtree are not available for mixture models");
         if (spec.ascertainment) {
             const int k = aln.appendUnobservedConstPatterns();
             printf("Ascertainment bias correction: %d unobservable constant patterns\n", k);
@@ -209,7 +267,11 @@ int main(int argc, char **argv) {
         aln.ptnInvar(mi.p_invar, mi.state_freq.data(), invar);
         tree.setAlignment(aln.num_states, aln.seq_type, aln.getNPattern(), states.data(), freq.data(), invar.data());
         if (spec.ascertainment) tree.setAscertainment(aln.n_unobserved, (double)nsite);
-        tree.setModel(mi.ncat, mi.eig.eval.data(), mi.eig.evec.data(), mi.eig.inv_evec.data(), mi.rates.data(), mi.props.data());
+        if (mixture)
+            tree.setMixtureModel(mi.nclass, mi.ncat, mi.cat_class.data(), mi.eig.eval.data(), mi.eig.evec.data(),
+                                 mi.eig.inv_evec.data(), mi.rates.data(), mi.props.data());
+        else
+            tree.setModel(mi.ncat, mi.eig.eval.data(), mi.eig.evec.data(), mi.eig.inv_evec.data(), mi.rates.data(), mi.props.data());
         tree.lh_mem_save = all_branch ? LM_ALL_BRANCH : LM_PER_NODE;
         tree.setLikelihoodKernel(LK_EIGEN_HIP);
         tree.attachEngine(dev);
@@ -342,6 +404,50 @@ int main(int argc, char **argv) {
             printf("Site proportion and rates: ");
             for (size_t c = 0; c < rates.size(); c++) printf(" (%g,%g)", props[c], rates[c]);
             printf("\nModel with estimated rates: %s\n", model_str.c_str());
+            printf("Optimal log-likelihood: %.17g\n", lnl);
+        } else if (mixweights) {
+            // the loop of ModelFactory::optimizeParameters with the substitution models fixed, as for -emrates
+            const double logl_epsilon = 0.01;   // params.modeps
+            double cur_lh = lnl;
+            printf("1. Initial log-likelihood: %.6f\n", cur_lh);
+            int em_steps = 0;
+            for (int i = 2; i < 100; i++) {   // params.num_param_iterations
+                if (!blfix) tree.optimizeAllBranches(std::min(i, 3), logl_epsilon);
+                int steps = 0;
+                const double new_lh = tree.optimizeMixtureWeights(nullptr, &steps);
+                em_steps += steps;
+                if (new_lh > cur_lh + logl_epsilon) {
+                    cur_lh = new_lh;
+                    printf("%d. Current log-likelihood: %.6f\n", i, cur_lh);
+                } else {
+                    if (!blfix) cur_lh = tree.optimizeAllBranches(100, logl_epsilon);
+                    break;
+                }
+            }
+            // The class rates were normalised with the weights the run started from.  As the reference does when it writes the
+            // model (modelmixture.cpp:1552-1563) and as -emrates does for +R: rates over their new mean, all branch lengths
+            // times it -- the likelihood is unchanged and the printed string reads back as the model the tree holds
+            const std::vector<double> w = tree.getMixtureWeights();
+            mi.props = tree.getProps();
+            double mean_rate = 0.0;
+            for (int m = 0; m < mi.nclass; m++) mean_rate += w[m] * mi.class_rates[m];
+            if (mean_rate != 1.0) {
+                const size_t n = (size_t)mi.nstates;
+                for (int m = 0; m < mi.nclass; m++) {
+                    mi.class_rates[m] /= mean_rate;
+                    for (size_t i = 0; i < n; i++) mi.eig.eval[(size_t)m * n + i] /= mean_rate;
+                }
+                tree.setMixtureModel(mi.nclass, mi.ncat, mi.cat_class.data(), mi.eig.eval.data(), mi.eig.evec.data(),
+                                     mi.eig.inv_evec.data(), mi.rates.data(), mi.props.data());
+                tree.scaleLength(mean_rate);
+            }
+            tree.clearAllPartialLH();
+            lnl = tree.computeLikelihood(pattern_lh.data());
+            model_str = mixtureString(model_str, mi.class_rates, w);
+            printf("EM: %d steps\n", em_steps);
+            printf("Mixture weights:");
+            for (double x : w) printf(" %g", x);
+            printf("\nModel with estimated weights: %s\n", model_str.c_str());
             printf("Optimal log-likelihood: %.17g\n", lnl);
         } else if (!blfix) {
             lnl = tree.optimizeAllBranches();

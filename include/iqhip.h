@@ -362,6 +362,50 @@ int iqhip_em_site_rates(iqhip_engine *e, double *ptn_rate /* nptn */, int32_t *p
 int iqhip_em_objective(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, double *f /* ncat */,
                        int64_t *floored /* ncat or NULL */);
 int iqhip_debug_em_timing(iqhip_engine *e, double *ms /* 2 */);
+
+/* EM estimation of mixture class weights (ModelMixture::optimizeWeights, model/modelmixture.cpp:1355-1416; Wang, Li, Susko and
+ * Roger 2008), per-pattern class posteriors and PhyloTree::computePatternStateFreq (phylotree.cpp:1162-1196) on the device.
+ * iqhip_mix_class_lh: with L_pq the quantity iqhip_pattern_lh_cat returns for the branch of the last iqhip_compute_theta at
+ *   length len, Lc[p][m] = sum of L_pq over the components q with cat_class[q] == m, in ascending q starting from the first
+ *   (computePatternLhCat(WSL_MIXTURE), phylotree.cpp:1132-1143; cat_class is an arbitrary map).  The matrix stays on the
+ *   device, class-major and unscaled -- every consumer below uses per-pattern ratios only; out (or NULL) receives a copy.
+ * iqhip_mix_weights_em: the reference's loop on the matrix of the last iqhip_mix_class_lh, at most max_steps steps (the
+ *   reference passes nclass), with no tree traversal in between.  One step, over the patterns with ptn_freq > 0:
+ *     s_p = v ptn_invar[p] + sum_m g[m] Lc[p][m]    (ascending m, starting from the invariant term)
+ *     new_m = (sum_p g[m] Lc[p][m] ptn_freq[p] / s_p) / nsites
+ *     converged = all |w[m] - new_m| < 1e-4;   g[m] *= new_m / w[m];   w[m] = new_m;   p_invar_new = 1 - sum_m w[m]
+ *   and with +I: converged &= |p_invar - p_invar_new| < 1e-4; v = p_invar_new / (the p_invar passed in); p_invar = p_invar_new.
+ *   g and v start at 1.  All max_steps steps are enqueued on the engine's stream without a host read in between -- the
+ *   steps behind the converged one do nothing -- and the step count, the flag, the weights and the log are read once.
+ *   weights: in, the class weights inside the engine's props; out, the estimate.  trace (or NULL): row k < *nsteps =
+ *   {w[0 .. nclass), p_invar} after step k, the rows behind them 0.  max_steps is at most IQHIP_MIX_MAX_STEPS: the log
+ *   (max_steps rows of nclass + 1 doubles, 3 MB at 96 classes) lives on the device for the run and is read back whole.  The call changes nothing the likelihood kernels read: the caller re-sends the
+ *   model (props[q] *= w_new[m] / w_old[m] through iqhip_set_mixture_model, then iqhip_set_ptn_invar) and invalidates all
+ *   vectors as at any model change.
+ *   +I: with p_invar != NULL and *p_invar > 0 the engine's resident ptn_invar is taken to belong to *p_invar; computePtnInvar
+ *   is linear in p_invar, so the factor v is exact up to rounding.
+ *   DEVIATIONS from the reference: (1) with p_invar NULL or 0 there is no +I handling (the reference would store the
+ *   rounding noise of 1 - sum w as p_invar); (2) the reference rescales its matrix in place by new / old after every step,
+ *   here the matrix is never rewritten and the cumulative factors g carry the product -- equal up to rounding, not in bits;
+ *   (3) the random number generator of computePatternRates is not involved.
+ * iqhip_mix_posteriors: post[p][m] = Lc[p][m] * (1 / sum_m Lc[p][m]) -- no invariant term, as phylotree.cpp:1174-1182 -- and,
+ *   with the classes' state frequencies class_freq[m][i], state_freq[p][i] = sum_m class_freq[m][i] post[p][m].
+ * All sums are formed in a fixed order without atomics, in a decomposition that follows from the pattern and class counts
+ * alone: the same bits on every run and on every device.
+ * Mixture engines of 4, 20 or 64 states.  IQHIP_ERR_UNSUPPORTED: one class, sharded engines and communicator ranks, +ASC
+ * (the reference: "Mixture model +ASC is not supported yet"), embedded state counts.  IQHIP_ERR_INVALID: a null argument,
+ * planning-only engines, theta not resident, a negative or NaN len, max_steps outside 1 .. IQHIP_MIX_MAX_STEPS, nsites <= 0, a weight <= 0 or not
+ * finite, *p_invar outside [0, 1), EM or posteriors before iqhip_mix_class_lh or after the engine's model changed.
+ * iqhip_debug_mix_timing: with iqhip_timing_enable, ms[0] / ms[1] = the device time (HIP events, milliseconds) of the last
+ *   class-lh launch / of the last EM chain; launches (or NULL) = the kernels that chain enqueued, 2 max_steps. */
+#define IQHIP_MIX_MAX_STEPS 4096
+int iqhip_mix_class_lh(iqhip_engine *e, double len, double *out /* nptn*nclass [ptn][class], or NULL: device only */);
+int iqhip_mix_weights_em(iqhip_engine *e, int max_steps, double nsites, double *weights /* nclass, in/out */,
+                         double *p_invar /* NULL or in/out */, int *nsteps, int *converged,
+                         double *trace /* NULL or max_steps*(nclass+1) */);
+int iqhip_mix_posteriors(iqhip_engine *e, const double *class_freq /* nclass*nstates or NULL */,
+                         double *post /* nptn*nclass or NULL */, double *state_freq /* nptn*nstates or NULL */);
+int iqhip_debug_mix_timing(iqhip_engine *e, double *ms /* 2 */, int64_t *launches);
 int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *out /* nptn */);
 int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int nsamples);
 int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *rell /* nsamples */);

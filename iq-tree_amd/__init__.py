@@ -32,6 +32,7 @@ IQHIP_SYMBOLS = [
     "iqhip_fetch_pattern_lh_scaled", "iqhip_set_boot_samples", "iqhip_rell", "iqhip_rell_async",
     "iqhip_set_mixture_model", "iqhip_pattern_lh_cat", "iqhip_optimize_branch_batch",
     "iqhip_em_posteriors", "iqhip_em_fetch_posteriors", "iqhip_em_site_rates", "iqhip_em_objective", "iqhip_debug_em_timing",
+    "iqhip_mix_class_lh", "iqhip_mix_weights_em", "iqhip_mix_posteriors", "iqhip_debug_mix_timing",
     "iqhip_create_sharded", "iqhip_num_shards", "iqhip_shard_range", "iqhip_comm_unique_id", "iqhip_comm_init_rank",
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
@@ -200,6 +201,10 @@ def libiqhip():
     lib.iqhip_debug_em_timing.argtypes = [vp, dp]
     lib.iqhip_em_site_rates.argtypes = [vp, dp, C.POINTER(C.c_int32)]
     lib.iqhip_em_objective.argtypes = [vp, BranchEnd, BranchEnd, C.c_double, dp, C.POINTER(C.c_int64)]
+    lib.iqhip_mix_class_lh.argtypes = [vp, C.c_double, dp]
+    lib.iqhip_mix_weights_em.argtypes = [vp, C.c_int, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), dp]
+    lib.iqhip_mix_posteriors.argtypes = [vp, dp, dp, dp]
+    lib.iqhip_debug_mix_timing.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     lib.iqhip_newton_host_update.argtypes = [vp, C.c_double, C.c_double, dp, C.POINTER(C.c_int)]
     lib.iqhip_newton_host_result.argtypes = [vp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.iqhip_timing_enable.argtypes = [vp, C.c_int]
@@ -338,6 +343,12 @@ def libiqhost():
     lib.iqhost_em_objective.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int64)]
     lib.iqhost_site_rates.argtypes = [vp, dp, C.POINTER(C.c_int)]
     lib.iqhost_optimize_free_rates_em.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int), dp, C.c_int]
+    lib.iqhost_mix_class_lh.argtypes = [vp, dp]
+    lib.iqhost_mix_weights_em.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), dp]
+    lib.iqhost_mix_posteriors.argtypes = [vp, dp, dp, dp]
+    lib.iqhost_pattern_state_freq.argtypes = [vp, dp, dp]
+    lib.iqhost_optimize_mixture_weights.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.iqhost_mix_timing.argtypes = [vp, dp, C.POINTER(C.c_int64)]
     lib.iqhost_compute_rell.argtypes = [vp, dp, C.c_int]
     lib.iqhost_last_plan.argtypes = [vp, C.POINTER(C.c_int), dp, C.POINTER(C.c_uint64), C.c_int]
     lib.iqhost_num_partial_lh_computations.argtypes = [vp]
@@ -373,6 +384,8 @@ def libiqhost():
     lib.iqaln_codon_freq.argtypes = [vp, C.c_int, dp, dp]
     lib.iqaln_write_sitelh.argtypes = [vp, C.c_char_p, dp]
     lib.iqmodel_build.argtypes = [vp, C.c_char_p, ip, dp, ip, dp, dp, dp, dp, dp, dp]
+    lib.iqmodel_mixture_dims.argtypes = [vp, C.c_char_p, ip, ip]
+    lib.iqmodel_build_mixture.argtypes = [vp, C.c_char_p, dp, ip, dp, dp, dp, dp, dp, ip, dp, dp, dp, dp]
     lib._iq_typed = True
     return lib
 
@@ -617,6 +630,7 @@ class PhyloTree:
         self.ncat = len(a[3])
         self.block = self.nstates * self.ncat
         nclass = int(getattr(model, "nclass", 1))
+        self.nclass = nclass
         if nclass > 1:
             cls = np.ascontiguousarray(model.cat_class, dtype=np.int32)
             self._chk(self.lib.iqhost_set_mixture_model(self.h, nclass, self.ncat, cls.ctypes.data_as(C.POINTER(C.c_int)),
@@ -1255,6 +1269,70 @@ class PhyloTree:
                             for row in tr[:n.value]]
         return out
 
+    def mix_class_lh(self):
+        """computePatternLhCat(WSL_MIXTURE) on the current branch (iqhip_mix_class_lh) -> Lc[nptn, nclass], the sum of the
+        pattern likelihoods of every class's components, unscaled; the matrix also stays on the device for the calls below."""
+        out = np.zeros((self.nptn, self.nclass))
+        self._chk(self.lib.iqhost_mix_class_lh(self.h, _dptr(out)))
+        return out
+
+    def mix_weights_em(self, weights, max_steps=None, p_invar=None, trace=False):
+        """The EM of ModelMixture::optimizeWeights on the matrix of the last mix_class_lh() (iqhip_mix_weights_em), at most
+        max_steps steps (default: nclass, as the reference); the tree and its model are left as they are
+        -> dict(weights, p_invar (None without +I), steps, converged[, trace: [steps, nclass + 1] rows {w, p_invar}])."""
+        k = self.nclass
+        w = np.array(weights, dtype=np.float64)
+        assert w.size == k
+        max_steps = k if max_steps is None else int(max_steps)
+        n, conv = C.c_int(), C.c_int()
+        pinv = C.c_double(0.0 if p_invar is None else float(p_invar))
+        tr = np.zeros((max(1, max_steps), k + 1))
+        self._chk(self.lib.iqhost_mix_weights_em(self.h, max_steps, _dptr(w), None if p_invar is None else C.byref(pinv),
+                                                 C.byref(n), C.byref(conv), _dptr(tr) if trace else None))
+        out = dict(weights=w, p_invar=None if p_invar is None else pinv.value, steps=n.value, converged=conv.value)
+        if trace:
+            out["trace"] = tr[:n.value].copy()
+        return out
+
+    def mix_posteriors(self, class_freq=None):
+        """Class posteriors of the matrix of the last mix_class_lh() -> post[nptn, nclass], or with class_freq[nclass, nstates]
+        (post, state_freq[nptn, nstates]) as PhyloTree::computePatternStateFreq."""
+        post = np.zeros((self.nptn, self.nclass))
+        if class_freq is None:
+            self._chk(self.lib.iqhost_mix_posteriors(self.h, None, _dptr(post), None))
+            return post
+        cf = np.ascontiguousarray(class_freq, dtype=np.float64)
+        assert cf.shape == (self.nclass, self.nstates)
+        sf = np.zeros((self.nptn, self.nstates))
+        self._chk(self.lib.iqhost_mix_posteriors(self.h, _dptr(cf), _dptr(post), _dptr(sf)))
+        return post, sf
+
+    def pattern_state_freq(self, class_freq):
+        """PhyloTree::computePatternStateFreq on the current branch: the class likelihoods are rebuilt (as mix_class_lh()), then
+        state_freq[nptn, nstates] = sum_m class_freq[m] * posterior of class m."""
+        cf = np.ascontiguousarray(class_freq, dtype=np.float64)
+        assert cf.shape == (self.nclass, self.nstates)
+        sf = np.zeros((self.nptn, self.nstates))
+        self._chk(self.lib.iqhost_pattern_state_freq(self.h, _dptr(cf), _dptr(sf)))
+        return sf
+
+    def optimize_mixture_weights(self, p_invar=None):
+        """ModelMixture::optimizeWeights: class likelihoods on the current branch, the EM with nclass steps, the component
+        weights (and with +I ptn_invar) rescaled and re-sent, all vectors cleared
+        -> dict(weights, props, p_invar, lnl, steps, converged)."""
+        w, props, lnl, n, conv = np.zeros(self.nclass), np.zeros(self.ncat), C.c_double(), C.c_int(), C.c_int()
+        pinv = C.c_double(0.0 if p_invar is None else float(p_invar))
+        self._chk(self.lib.iqhost_optimize_mixture_weights(self.h, None if p_invar is None else C.byref(pinv), _dptr(w),
+                                                           _dptr(props), C.byref(lnl), C.byref(n), C.byref(conv)))
+        return dict(weights=w, props=props, p_invar=None if p_invar is None else pinv.value, lnl=lnl.value, steps=n.value,
+                    converged=conv.value)
+
+    def mix_timing(self):
+        """iqhip_debug_mix_timing -> dict(class_lh_ms, em_ms, launches) of the last calls (times while timing is enabled)."""
+        ms, n = np.zeros(2), C.c_int64()
+        self._chk(self.lib.iqhost_mix_timing(self.h, _dptr(ms), C.byref(n)))
+        return dict(class_lh_ms=ms[0], em_ms=ms[1], launches=n.value)
+
     def set_boot_samples(self, samples):
         """UFBoot boot_samples: float32 [nsamples, nptn] pattern weights, uploaded once."""
         s = np.ascontiguousarray(samples, dtype=np.float32)
@@ -1406,6 +1484,20 @@ class Alignment:
         """-m string -> the dict PhyloTree.set_model() takes (+ state_freq, p_invar, asc)."""
         n = self.nstates
         ncat, asc, pinv = C.c_int(), C.c_int(), C.c_double()
+        if model_string.upper().startswith("MIX{"):
+            # a mixture: + nclass, cat_class, class_freq[nclass, n], class_rates, class_weights; state_freq = their weighted mean
+            M = C.c_int()
+            _mchk(self.lib, self.lib.iqmodel_mixture_dims(self.h, model_string.encode(), C.byref(M), C.byref(ncat)))
+            M, k = M.value, ncat.value
+            ev, U, Ui, cf, fr = np.zeros((M, n)), np.zeros((M, n, n)), np.zeros((M, n, n)), np.zeros((M, n)), np.zeros(n)
+            cls, rates, props, cr, cw = np.zeros(k, dtype=np.int32), np.zeros(k), np.zeros(k), np.zeros(M), np.zeros(M)
+            _mchk(self.lib, self.lib.iqmodel_build_mixture(self.h, model_string.encode(), C.byref(pinv), C.byref(asc), _dptr(ev),
+                                                           _dptr(U), _dptr(Ui), _dptr(cf), _dptr(fr),
+                                                           cls.ctypes.data_as(C.POINTER(C.c_int)), _dptr(rates), _dptr(props),
+                                                           _dptr(cr), _dptr(cw)))
+            return AttrDict(nstates=n, ncat=k, nclass=M, cat_class=cls, eval=ev, evec=U, inv_evec=Ui, state_freq=fr,
+                            class_freq=cf, class_rates=cr, class_weights=cw, rates=rates, props=props, p_invar=pinv.value,
+                            asc=bool(asc.value))
         ev, U, Ui, fr = np.zeros(n), np.zeros((n, n)), np.zeros((n, n)), np.zeros(n)
         rates, props = np.zeros(64), np.zeros(64)
         _mchk(self.lib, self.lib.iqmodel_build(self.h, model_string.encode(), C.byref(ncat), C.byref(pinv), C.byref(asc),

@@ -605,6 +605,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
         e->plan_cache.invalidate();
     }
     e->h_props.assign(props, props + e->ncat);   // (iqhip_em_objective checks the weights it divides by)
+    e->h_cls = cls;                              // (iqhip_mix_class_lh builds the per-class component lists from it)
     e->nclass = nclass;
     e->state_unknown = state_unknown;
     e->model_set = true;

@@ -23,6 +23,10 @@ namespace iqhip {
 
 constexpr int kSmallPlanOps = 4;         // op descriptors (incl. the two look-ahead sentinels) that fit the kernel arguments
 constexpr int kNewtonPostEpochs = 128;   // evaluations of one k_newton launch that have a post slot
+constexpr int kMixEmTile = 256;           // kernels_mixem.hip k_mixem_step: patterns per workgroup, one per thread ...
+constexpr int kMixEmRegClasses = 8;       // ... classes whose tile values stay in registers between the two passes
+constexpr int kMixEmBatch = 16;           // ... classes whose loads are issued together when there are more
+constexpr int kMixEmUpdateThreads = 1024; // k_mixem_update: one workgroup; at most that many classes
 constexpr double kScalingThreshold = 0x1p-256;       // phylotree.h:52
 constexpr double kScalingThresholdInv = 0x1p256;     // phylotree.h:51
 // log(2^-256) as libm returns it (phylotree.h:53)
@@ -377,6 +381,7 @@ struct iqhip_engine {
     double *d_eval = nullptr, *d_evec = nullptr, *d_inv_evec = nullptr;
     double *d_rates = nullptr, *d_props = nullptr, *d_tip = nullptr;
     std::vector<double> h_eval, h_rates, h_props;
+    std::vector<int> h_cls;      // category -> class of the last set_model call (all 0 for a plain model)
     // per-call buffers
     iqhip::DevOp *d_ops = nullptr;
     int ops_cap = 0;
@@ -478,6 +483,19 @@ struct iqhip_engine {
         bool valid = false;
         double ms[2] = {0.0, 0.0};   // iqhip_debug_em_timing: the last E-step / objective launches (while timing is enabled)
     } em;
+    // EM for mixture class weights, class posteriors, pattern state frequencies (ptnlh.hip, kernels_mixem.hip): the class
+    // likelihoods Lc [nclass][nptn_pad] of the last iqhip_mix_class_lh (class-major, padding patterns 0) with the model
+    // version and dimensions they belong to (0: none), the per-class component lists (first [nclass + 1] ++ components), the
+    // state of an EM run (kernels_mixem.hip MIXEM_*), the workgroup rows of its sums, posteriors / state frequencies scratch
+    struct {
+        iqhip::DevBuf<double> lc, state, part, post, cfreq;
+        iqhip::DevBuf<int32_t> list;
+        uint64_t model_version = 0;
+        int64_t nptn_pad = 0;
+        int nclass = 0;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_mix_timing: the class-lh launch, the EM chain (while timing is enabled)
+        int64_t launches = 0;        // kernels the last EM chain enqueued
+    } mix;
     // pairwise ML distances (pairdist.hip, kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
     // coefficients evec[i][k] * inv_evec[k][j] of the call's model [n][n][n], per pair the initial distance and the result
     // {optx, d2l, evaluations, status}; with iqhip_timing_enable the device time of the last iqhip_pair_distances call
@@ -1026,6 +1044,14 @@ hipError_t launch_em_posteriors(iqhip_engine *e, double len, double *W, double *
                                 double *out);
 hipError_t launch_em_objective(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double len, const double *W,
                                double *part, double *out);
+// kernels_mixem.hip: d_cls_list = first [nclass + 1] ++ the components of every class; one EM step = the E-step kernel over
+// Lc plus the one-workgroup update of the state (two launches); part holds mixem_part_rows rows of nclass doubles
+hipError_t launch_mix_class_lh(iqhip_engine *e, double len, const int32_t *d_cls_list, double *Lc);
+int64_t mixem_part_rows(const iqhip_engine *e);
+// the device-resident state of one EM run, all doubles: these scalars, then g [nclass], w [nclass], the log [max_steps][nclass + 1]
+enum { MIXEM_DONE = 0, MIXEM_STEPS, MIXEM_PINV, MIXEM_V, MIXEM_PINV_IN, MIXEM_USE_INV, MIXEM_NSITES, MIXEM_HDR = 8 };
+hipError_t launch_mixem_step(iqhip_engine *e, const double *Lc, double *state, int max_steps, double *part);
+hipError_t launch_mix_posteriors(iqhip_engine *e, const double *Lc, const double *d_class_freq, double *post, double *sfreq);
 // rows of the per-pattern store from a chunk of k_newton_batch: task t of the m tasks -> store row d_rows[t] (< 0: none)
 hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const double *theta_base, size_t theta_stride,
                              const double *batch_out, const int32_t *d_rows);

@@ -1,7 +1,7 @@
 // ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: UFBoot / RELL, the store of
-// per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests, the EM for +R free-rate models and
-// the empirical-Bayes site rates.  Host code only; the kernels are in kernels_rell.hip, kernels_alrt.hip, kernels_topo.hip
-// and kernels_em.hip.
+// per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests, the EM for +R free-rate models, the
+// empirical-Bayes site rates and the EM for mixture class weights.  Host code only; the kernels are in kernels_rell.hip,
+// kernels_alrt.hip, kernels_topo.hip, kernels_em.hip and kernels_mixem.hip.
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -180,6 +180,153 @@ extern "C" int iqhip_em_objective(iqhip_engine *e, iqhip_branch_end a, iqhip_bra
         f[c] = res[c];
         if (floored) floored[c] = (int64_t)res[C + c];
     }
+    return IQHIP_OK;
+}
+
+// ---- EM for mixture class weights, class posteriors, pattern state frequencies (kernels_mixem.hip) -------------------
+// plain mixture engines of 4 / 20 / 64 states only; needs_lc: the call reads what the last iqhip_mix_class_lh left
+static int mix_engine(iqhip_engine *e, const char *what, bool needs_lc) {
+    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
+    if (e->asc_active || e->n_unobs > 0)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": mixture models with ascertainment bias correction are not supported");
+    if (e->embed2 || e->n_user != e->n)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
+    if (e->nclass < 2) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": the model is no mixture (one class)");
+    if (needs_lc && (e->mix.model_version != e->model_version || e->mix.nptn_pad != e->nptn_pad || e->mix.nclass != e->nclass ||
+                     e->mix.lc.cap < (size_t)e->nclass * (size_t)e->nptn_pad))
+        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_mix_class_lh first (again after every model change)");
+    return IQHIP_OK;
+}
+
+// rows [nrows][nptn_pad] on the device -> out [nptn][nrows] on the host
+static int mix_fetch_transposed(iqhip_engine *e, const double *d_rows, size_t nrows, double *out) {
+    const size_t P = (size_t)e->nptn_pad, N = (size_t)e->nptn;
+    std::vector<double> rows(nrows * P);
+    HIPCHK(hipMemcpyAsync(rows.data(), d_rows, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (size_t p = 0; p < N; p++)
+        for (size_t r = 0; r < nrows; r++) out[p * nrows + r] = rows[r * P + p];
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_mix_timing(iqhip_engine *e, double *ms, int64_t *launches) {
+    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_mix_timing: null argument");
+    ms[0] = e->mix.ms[0];
+    ms[1] = e->mix.ms[1];
+    if (launches) *launches = e->mix.launches;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_mix_class_lh(iqhip_engine *e, double len, double *out) {
+    if (!e) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh: null argument");
+    int rc = mix_engine(e, "iqhip_mix_class_lh", false);
+    if (rc) return rc;
+    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh needs iqhip_compute_theta first");
+    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh: negative or NaN branch length");
+    HIPCHK(use_device(e));
+    const size_t P = (size_t)e->nptn_pad, M = (size_t)e->nclass, C = (size_t)e->ncat;
+    // the components of every class in ascending order: cat_class is an arbitrary map
+    std::vector<int32_t> list(M + 1 + C);
+    size_t at = 0;
+    for (size_t m = 0; m < M; m++) {
+        list[m] = (int32_t)at;
+        for (size_t c = 0; c < C; c++)
+            if ((size_t)e->h_cls[c] == m) list[M + 1 + at++] = (int32_t)c;
+    }
+    list[M] = (int32_t)at;
+    e->mix.model_version = 0;
+    HIPCHK(e->mix.lc.ensure(e, M * P));
+    HIPCHK(e->mix.list.ensure(e, list.size()));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source, and an earlier launch may still read the list)
+    HIPCHK(hipMemcpyAsync(e->mix.list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    EmTimer timer(e);
+    HIPCHK(launch_mix_class_lh(e, len, e->mix.list.p, e->mix.lc.p));
+    timer.mark();
+    HIPCHK(hipStreamSynchronize(e->stream));
+    timer.stop(&e->mix.ms[0]);
+    e->mix.model_version = e->model_version;
+    e->mix.nptn_pad = e->nptn_pad;
+    e->mix.nclass = e->nclass;
+    return out ? mix_fetch_transposed(e, e->mix.lc.p, M, out) : IQHIP_OK;
+}
+
+extern "C" int iqhip_mix_weights_em(iqhip_engine *e, int max_steps, double nsites, double *weights, double *p_invar, int *nsteps,
+                                    int *converged, double *trace) {
+    if (!e || !weights || !nsteps || !converged) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: null argument");
+    int rc = mix_engine(e, "iqhip_mix_weights_em", true);
+    if (rc) return rc;
+    if (max_steps < 1 || max_steps > IQHIP_MIX_MAX_STEPS)
+        return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: max_steps must be 1 .. " + std::to_string(IQHIP_MIX_MAX_STEPS));
+    if (!(nsites > 0.0) || !std::isfinite(nsites)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: nsites must be > 0");
+    const size_t M = (size_t)e->nclass;
+    static_assert(kMixEmUpdateThreads >= 96, "k_mixem_update runs one thread per class: nclass <= ncat <= 96 (iqhip_create)");
+    for (size_t m = 0; m < M; m++)
+        if (!(weights[m] > 0.0) || !std::isfinite(weights[m]))
+            return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: every class weight must be > 0 and finite");
+    if (p_invar && !(*p_invar >= 0.0 && *p_invar < 1.0)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: p_invar outside [0, 1)");
+    HIPCHK(use_device(e));
+    const bool use_inv = p_invar && *p_invar > 0.0;
+    std::vector<double> st(MIXEM_HDR + 2 * M + (size_t)max_steps * (M + 1), 0.0);
+    st[MIXEM_PINV] = st[MIXEM_PINV_IN] = use_inv ? *p_invar : 0.0;
+    st[MIXEM_V] = 1.0;
+    st[MIXEM_USE_INV] = use_inv ? 1.0 : 0.0;
+    st[MIXEM_NSITES] = nsites;
+    for (size_t m = 0; m < M; m++) {
+        st[MIXEM_HDR + m] = 1.0;
+        st[MIXEM_HDR + M + m] = weights[m];
+    }
+    HIPCHK(e->mix.state.ensure(e, st.size()));
+    HIPCHK(e->mix.part.ensure(e, (size_t)mixem_part_rows(e) * M));
+    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source)
+    // (the log is not uploaded: step k writes row k before anything reads it, and only the rows below *nsteps are handed out)
+    HIPCHK(hipMemcpyAsync(e->mix.state.p, st.data(), sizeof(double) * (MIXEM_HDR + 2 * M), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    // the whole loop is enqueued: the steps behind the converged one return at once
+    EmTimer timer(e);
+    int64_t launches = 0;
+    for (int k = 0; k < max_steps; k++) {
+        HIPCHK(launch_mixem_step(e, e->mix.lc.p, e->mix.state.p, max_steps, e->mix.part.p));
+        launches += 2;
+    }
+    timer.mark();
+    HIPCHK(hipMemcpyAsync(st.data(), e->mix.state.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    timer.stop(&e->mix.ms[1]);
+    e->mix.launches = launches;
+    *nsteps = (int)st[MIXEM_STEPS];
+    *converged = st[MIXEM_DONE] != 0.0 ? 1 : 0;
+    memcpy(weights, &st[MIXEM_HDR + M], sizeof(double) * M);
+    if (use_inv) *p_invar = st[MIXEM_PINV];
+    if (trace) {
+        const size_t taken = (size_t)*nsteps * (M + 1), all = (size_t)max_steps * (M + 1);
+        memcpy(trace, &st[MIXEM_HDR + 2 * M], sizeof(double) * taken);
+        std::fill(trace + taken, trace + all, 0.0);
+    }
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_mix_posteriors(iqhip_engine *e, const double *class_freq, double *post, double *state_freq) {
+    if (!e || (!post && !state_freq) || (state_freq && !class_freq))
+        return fail(IQHIP_ERR_INVALID, "iqhip_mix_posteriors: null argument");
+    int rc = mix_engine(e, "iqhip_mix_posteriors", true);
+    if (rc) return rc;
+    HIPCHK(use_device(e));
+    const size_t P = (size_t)e->nptn_pad, M = (size_t)e->nclass, n = (size_t)e->n;
+    const size_t post_doubles = post ? M * P : 0;
+    HIPCHK(e->mix.post.ensure(e, post_doubles + (state_freq ? n * P : 0)));
+    double *d_post = post ? e->mix.post.p : nullptr, *d_sf = state_freq ? e->mix.post.p + post_doubles : nullptr;
+    if (state_freq) {
+        HIPCHK(e->mix.cfreq.ensure(e, M * n));
+        HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source)
+        HIPCHK(hipMemcpyAsync(e->mix.cfreq.p, class_freq, sizeof(double) * M * n, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    HIPCHK(launch_mix_posteriors(e, e->mix.lc.p, e->mix.cfreq.p, d_post, d_sf));
+    if (post && (rc = mix_fetch_transposed(e, d_post, M, post))) return rc;
+    if (state_freq && (rc = mix_fetch_transposed(e, d_sf, n, state_freq))) return rc;
     return IQHIP_OK;
 }
 

@@ -318,6 +318,42 @@ int iqhost_optimize_free_rates_em(void *h, double *props, double *rates, double 
         }
     });
 }
+// ---- EM for mixture class weights.  out / post / state_freq: NULL or [ptn][class] / [ptn][class] / [ptn][state]
+int iqhost_mix_class_lh(void *h, double *out) {
+    IQHOST_TRY(((PhyloTree *)h)->computePatternLhCat(PhyloTree::WSL_MIXTURE, out));
+}
+int iqhost_mix_weights_em(void *h, int max_steps, double *weights, double *p_invar, int *nsteps, int *converged, double *trace) {
+    IQHOST_TRY(((PhyloTree *)h)->mixWeightsEM(max_steps, weights, p_invar, nsteps, converged, trace));
+}
+// on the matrix of the last iqhost_mix_class_lh
+int iqhost_mix_posteriors(void *h, const double *class_freq, double *post, double *state_freq) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        if (!t->engine) throw std::runtime_error("no engine");
+        if (iqhip_mix_posteriors(t->engine, class_freq, post, state_freq) != 0) throw std::runtime_error(iqhip_last_error());
+    });
+}
+int iqhost_pattern_state_freq(void *h, const double *class_freq, double *state_freq) {
+    IQHOST_TRY(((PhyloTree *)h)->computePatternStateFreq(class_freq, state_freq));
+}
+// weights: nmixture, props: ncat (the component weights re-sent to the engine); p_invar: NULL or in/out
+int iqhost_optimize_mixture_weights(void *h, double *p_invar, double *weights, double *props, double *lnl, int *nsteps,
+                                    int *converged) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        *lnl = t->optimizeMixtureWeights(p_invar, nsteps, converged);
+        const std::vector<double> w = t->getMixtureWeights();
+        memcpy(weights, w.data(), sizeof(double) * w.size());
+        memcpy(props, t->getProps().data(), sizeof(double) * (size_t)t->ncat);
+    });
+}
+int iqhost_mix_timing(void *h, double *ms, int64_t *launches) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        if (!t->engine) throw std::runtime_error("no engine");
+        if (iqhip_debug_mix_timing(t->engine, ms, launches) != 0) throw std::runtime_error(iqhip_last_error());
+    });
+}
 int iqhost_set_boot_samples(void *h, const float *samples, int nsamples) {
     IQHOST_TRY(((PhyloTree *)h)->setBootSamples(samples, nsamples));
 }

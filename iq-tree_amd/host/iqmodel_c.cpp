@@ -111,6 +111,7 @@ int iqmodel_build(void *aln, const char *model_string, int *ncat, double *p_inva
                   double *evec, double *inv_evec, double *state_freq, double *rates, double *props) {
     IQM_TRY({
         ModelSpec spec = parseModelString(model_string);
+        if (!spec.mix_classes.empty()) throw std::runtime_error("a MIX{} model takes iqmodel_build_mixture");
         if (spec.ncat > 64) throw std::runtime_error("too many rate categories");
         ModelInputs mi;
         buildModel(spec, *(Alignment *)aln, mi);
@@ -124,6 +125,48 @@ int iqmodel_build(void *aln, const char *model_string, int *ncat, double *p_inva
         memcpy(state_freq, mi.state_freq.data(), sizeof(double) * n);
         memcpy(rates, mi.rates.data(), sizeof(double) * mi.ncat);
         memcpy(props, mi.props.data(), sizeof(double) * mi.ncat);
+    });
+}
+
+// MIX{...} strings.  iqmodel_mixture_dims: the class and component counts (nclass = 1, ncat = the rate categories for a
+// plain model); iqmodel_build_mixture: out arrays sized from them -- eval [nclass * n], evec / inv_evec [nclass * n * n],
+// class_freq [nclass * n], state_freq [n] (the weighted mean), cat_class / rates / props [ncat], class_rates /
+// class_weights [nclass]
+int iqmodel_mixture_dims(void *aln, const char *model_string, int *nclass, int *ncat) {
+    IQM_TRY({
+        const ModelSpec spec = parseModelString(model_string);
+        const int M = spec.mix_classes.empty() ? 1 : (int)spec.mix_classes.size();
+        const int limit = maxModelComponents(((Alignment *)aln)->num_states);
+        if (!spec.mix_classes.empty() && (long long)M * spec.ncat > limit)
+            throw std::runtime_error("MIX{}: " + std::to_string((long long)M * spec.ncat) + " components; an engine of " +
+                                     std::to_string(((Alignment *)aln)->num_states) + " states takes at most " + std::to_string(limit));
+        *nclass = M;
+        *ncat = M * spec.ncat;
+    });
+}
+int iqmodel_build_mixture(void *aln, const char *model_string, double *p_invar, int *asc, double *eval, double *evec,
+                          double *inv_evec, double *class_freq, double *state_freq, int *cat_class, double *rates,
+                          double *props, double *class_rates, double *class_weights) {
+    IQM_TRY({
+        ModelSpec spec = parseModelString(model_string);
+        if (spec.mix_classes.empty()) throw std::runtime_error("iqmodel_build_mixture: not a MIX{} model");
+        ModelInputs mi;
+        buildModel(spec, *(Alignment *)aln, mi);
+        const size_t n = (size_t)mi.nstates;
+        const size_t M = (size_t)mi.nclass;
+        const size_t C = (size_t)mi.ncat;
+        *p_invar = mi.p_invar;
+        *asc = spec.ascertainment;
+        memcpy(eval, mi.eig.eval.data(), sizeof(double) * M * n);
+        memcpy(evec, mi.eig.evec.data(), sizeof(double) * M * n * n);
+        memcpy(inv_evec, mi.eig.inv_evec.data(), sizeof(double) * M * n * n);
+        memcpy(class_freq, mi.class_freq.data(), sizeof(double) * M * n);
+        memcpy(state_freq, mi.state_freq.data(), sizeof(double) * n);
+        memcpy(cat_class, mi.cat_class.data(), sizeof(int) * C);
+        memcpy(rates, mi.rates.data(), sizeof(double) * C);
+        memcpy(props, mi.props.data(), sizeof(double) * C);
+        memcpy(class_rates, mi.class_rates.data(), sizeof(double) * M);
+        memcpy(class_weights, mi.class_weights.data(), sizeof(double) * M);
     });
 }
 

@@ -3,6 +3,7 @@
 
 #include <ctype.h>
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 
@@ -326,6 +327,80 @@ std::string upper(std::string s) {
 
 }  // namespace
 
+int maxModelComponents(int nstates) { return nstates == 4 ? 32 : nstates == 20 ? 96 : 16; }
+
+namespace {
+
+// the body of MIX{...}: classes at the commas of depth 0, each "model[:rate[:weight]]"
+void parseMixture(const std::string &body, ModelSpec &spec) {
+    std::vector<std::string> items;
+    size_t start = 0;
+    int depth = 0;
+    for (size_t i = 0; i <= body.size(); i++) {
+        if (i < body.size() && body[i] == '{') depth++;
+        if (i < body.size() && body[i] == '}') depth--;
+        if (i == body.size() || (body[i] == ',' && depth == 0)) {
+            items.push_back(body.substr(start, i - start));
+            start = i + 1;
+        }
+    }
+    for (const std::string &item : items) {
+        if (item.empty()) throw std::runtime_error("One model name in the mixture is empty.");
+        std::string name = item;
+        double rate = 1.0, weight = 1.0;
+        size_t pos_rate = std::string::npos;
+        depth = 0;
+        for (size_t i = 0; i < item.size() && pos_rate == std::string::npos; i++) {
+            if (item[i] == '{') depth++;
+            if (item[i] == '}') depth--;
+            if (item[i] == ':' && depth == 0) pos_rate = i;
+        }
+        auto number = [&](const std::string &t) {
+            char *end = nullptr;
+            const double v = strtod(t.c_str(), &end);
+            if (t.empty() || *end != 0 || !std::isfinite(v)) throw std::runtime_error("Mixture class " + item + ": bad number '" + t + "'");
+            return v;
+        };
+        if (pos_rate != std::string::npos) {
+            const size_t pos_weight = item.find(':', pos_rate + 1);
+            if (pos_weight == std::string::npos)
+                rate = number(item.substr(pos_rate + 1));
+            else {
+                rate = number(item.substr(pos_rate + 1, pos_weight - pos_rate - 1));
+                weight = number(item.substr(pos_weight + 1));
+                spec.mix_weights_given = true;
+                if (weight <= 0.0) throw std::runtime_error("Mixture component weight is negative!");
+            }
+            if (!(rate > 0.0)) throw std::runtime_error("Mixture class " + item + ": the rate must be > 0");
+            name = item.substr(0, pos_rate);
+        }
+        if (upper(name).compare(0, 4, "MIX{") == 0) throw std::runtime_error("A MIX{} inside a MIX{} is not supported");
+        ModelSpec cls = parseModelString(name);
+        if (cls.ncat != 1 || cls.p_invar != 0.0 || !cls.free_rates.empty() || cls.ascertainment)
+            throw std::runtime_error("Mixture class " + name + ": rate heterogeneity and +ASC go behind the closing brace of MIX{}");
+        spec.mix_classes.push_back(cls);
+        spec.mix_rates.push_back(rate);
+        spec.mix_weights.push_back(weight);
+    }
+    const size_t k = spec.mix_classes.size();
+    if (k < 2) throw std::runtime_error("MIX{} needs at least two classes");
+    // modelmixture.cpp:1203-1228: weights 1 / k unless given, normalised to sum 1; rates so that the global rate is 1
+    double sum = 0.0;
+    for (size_t m = 0; m < k; m++) {
+        if (!spec.mix_weights_given) spec.mix_weights[m] = 1.0 / (double)k;
+        sum += spec.mix_weights[m];
+    }
+    if (sum != 1.0) {
+        sum = 1.0 / sum;
+        for (double &w : spec.mix_weights) w *= sum;
+    }
+    sum = 0.0;
+    for (size_t m = 0; m < k; m++) sum += spec.mix_weights[m] * spec.mix_rates[m];
+    for (double &r : spec.mix_rates) r /= sum;
+}
+
+}  // namespace
+
 ModelSpec parseModelString(const std::string &s) {
     ModelSpec spec;
     std::vector<std::string> toks;
@@ -340,7 +415,11 @@ ModelSpec parseModelString(const std::string &s) {
         }
     }
     if (toks.empty() || toks[0].empty()) throw std::runtime_error("empty model string");
-    {
+    if (upper(toks[0]).compare(0, 4, "MIX{") == 0) {
+        if (toks[0].back() != '}') throw std::runtime_error("Missing } in model string " + toks[0]);
+        spec.name = "MIX";
+        parseMixture(toks[0].substr(4, toks[0].size() - 5), spec);
+    } else {
         const size_t open = toks[0].find('{');
         spec.name = toks[0].substr(0, open);
         if (open != std::string::npos) spec.params = parseBraces(toks[0], open);
@@ -350,6 +429,8 @@ ModelSpec parseModelString(const std::string &s) {
         const std::string u = upper(tok);
         const size_t open = tok.find('{');
         if (u == "ASC") spec.ascertainment = true;
+        else if (u[0] == 'F' && !spec.mix_classes.empty())   // (+F, +FO, +FQ, +F1X4, +F3X4, +F{..} alike)
+            throw std::runtime_error("+" + tok + ": the frequencies of a mixture go inside MIX{}, per class");
         else if (u == "F1X4") spec.freq_type = ModelSpec::FREQ_CODON_1x4;
         else if (u == "F3X4") spec.freq_type = ModelSpec::FREQ_CODON_3x4;
         else if (u == "FQ") spec.freq_type = ModelSpec::FREQ_EQUAL;
@@ -424,7 +505,58 @@ void readPamlFile(const std::string &file, std::vector<double> &rates, std::vect
 
 }  // namespace
 
+// MIX{}: every class built on its own, then laid out as [class][rate] components
+static void buildMixture(const ModelSpec &spec, const Alignment &aln, ModelInputs &out) {
+    const int n = aln.num_states, M = (int)spec.mix_classes.size();
+    const int limit = maxModelComponents(n);
+    if ((long long)M * spec.ncat > limit) {
+        std::ostringstream e;
+        e << "MIX{}: " << M << " classes x " << spec.ncat << " rate categories = " << M * spec.ncat
+          << " components; an engine of " << n << " states takes at most " << limit;
+        throw std::runtime_error(e.str());
+    }
+    std::vector<double> cat_rates, cat_props;
+    out = ModelInputs();
+    out.nstates = n;
+    out.nclass = M;
+    out.eig.n = n;
+    out.state_freq.assign((size_t)n, 0.0);
+    for (int m = 0; m < M; m++) {
+        ModelSpec cls = spec.mix_classes[m];
+        cls.ncat = spec.ncat;
+        cls.gamma_shape = spec.gamma_shape;
+        cls.gamma_median = spec.gamma_median;
+        cls.p_invar = spec.p_invar;
+        cls.free_props = spec.free_props;
+        cls.free_rates = spec.free_rates;
+        ModelInputs one;
+        buildModel(cls, aln, one);
+        if (m == 0) {
+            cat_rates = one.rates;
+            cat_props = one.props;
+        }
+        for (double ev : one.eig.eval) out.eig.eval.push_back(ev * spec.mix_rates[m]);   // total_num_subst = the class rate
+        out.eig.evec.insert(out.eig.evec.end(), one.eig.evec.begin(), one.eig.evec.end());
+        out.eig.inv_evec.insert(out.eig.inv_evec.end(), one.eig.inv_evec.begin(), one.eig.inv_evec.end());
+        out.class_freq.insert(out.class_freq.end(), one.state_freq.begin(), one.state_freq.end());
+        for (int i = 0; i < n; i++) out.state_freq[i] += spec.mix_weights[m] * one.state_freq[i];
+        for (int c = 0; c < spec.ncat; c++) {
+            out.cat_class.push_back(m);
+            out.rates.push_back(cat_rates[c]);
+            out.props.push_back(spec.mix_weights[m] * cat_props[c]);
+        }
+    }
+    out.ncat = M * spec.ncat;
+    out.p_invar = spec.p_invar;
+    out.class_rates = spec.mix_rates;
+    out.class_weights = spec.mix_weights;
+}
+
 void buildModel(const ModelSpec &spec, const Alignment &aln, ModelInputs &out) {
+    if (!spec.mix_classes.empty()) {
+        buildMixture(spec, aln, out);
+        return;
+    }
     const int n = aln.num_states;
     const std::string name = upper(spec.name);
     std::vector<double> rates((size_t)n * n, 0.0), freq(n, 1.0 / n), file_freq;

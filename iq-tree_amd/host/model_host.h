@@ -55,7 +55,15 @@ struct ModelSpec {
     // rescaled to mean 1; empty: discrete Gamma
     std::vector<double> free_props, free_rates;
     bool ascertainment = false;
+    // MIX{m1[:rate[:weight]],m2,...} (ModelMixture::initMixture, model/modelmixture.cpp:1132-1230): name == "MIX", one spec
+    // per class (substitution model and frequencies only), the class rates rescaled so that sum_m w_m rate_m = 1 and the
+    // weights normalised to sum 1 (1 / k each when none is given); the rate suffixes of the whole string apply to every class
+    std::vector<ModelSpec> mix_classes;
+    std::vector<double> mix_rates, mix_weights;
+    bool mix_weights_given = false;   // some class carried a :weight (the reference's fix_prop)
 };
+// components (classes x rate categories) an engine of this state count takes
+int maxModelComponents(int nstates);
 ModelSpec parseModelString(const std::string &s);
 
 struct ModelInputs {      // what PhyloTree::setModel / iqhip_set_model consume
@@ -63,6 +71,13 @@ struct ModelInputs {      // what PhyloTree::setModel / iqhip_set_model consume
     EigenSystem eig;
     std::vector<double> state_freq, rates, props;
     double p_invar = 0.0;
+    // mixtures (nclass > 1): eig holds the classes' systems one after the other (eval [nclass][n], evec / inv_evec
+    // [nclass][n][n], the eigenvalues of class m times its rate, as total_num_subst scales them in the reference); ncat
+    // counts the components, in [class][rate] order: cat_class[q] = q / (rate categories), props[q] = w_m * p_c;
+    // state_freq = sum_m w_m class_freq[m] (what ptn_invar is built from)
+    int nclass = 1;
+    std::vector<int> cat_class;
+    std::vector<double> class_freq, class_rates, class_weights;   // [nclass][n], [nclass], [nclass]
 };
 
 class Alignment;

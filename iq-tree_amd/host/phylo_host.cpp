@@ -2085,6 +2085,72 @@ double PhyloTree::optimizeFreeRatesEM(std::vector<EmStep> *trace) {
     return computeLikelihood();
 }
 
+// =========================================================================================
+// EM for mixture class weights (kernels_mixem.hip; model/modelmixture.cpp:1355-1416)
+// =========================================================================================
+double PhyloTree::getAlnNSite() const {
+    double nsite = 0.0;
+    for (double f : ptn_freq) nsite += f;
+    return nsite;
+}
+
+void PhyloTree::computePatternLhCat(SiteLoglType wsl, double *out) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (wsl != WSL_MIXTURE) throw std::runtime_error("computePatternLhCat: only WSL_MIXTURE takes this form");
+    if (!current_it) throw std::runtime_error("computePatternLhCat before computeLikelihood");
+    double df, ddf;
+    theta_computed = false;
+    computeLikelihoodDerv(current_it, current_it_back->node, df, ddf);  // (re)builds theta of current_it
+    check(iqhip_mix_class_lh(engine, current_it->length, out), "iqhip_mix_class_lh");
+}
+
+std::vector<double> PhyloTree::getMixtureWeights() const {
+    std::vector<double> w((size_t)nmixture, 0.0);
+    std::vector<char> seen((size_t)nmixture, 0);
+    for (int q = 0; q < ncat; q++) {
+        const int m = m_cat_class[q];
+        w[m] = seen[m] ? w[m] + m_props[q] : m_props[q];
+        seen[m] = 1;
+    }
+    return w;
+}
+
+void PhyloTree::mixWeightsEM(int max_steps, double *weights, double *p_invar, int *nsteps, int *converged, double *trace) {
+    if (!engine) throw std::runtime_error("no engine");
+    check(iqhip_mix_weights_em(engine, max_steps, getAlnNSite(), weights, p_invar, nsteps, converged, trace), "iqhip_mix_weights_em");
+}
+
+double PhyloTree::optimizeMixtureWeights(double *p_invar, int *nsteps, int *converged) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (nmixture < 2) throw std::runtime_error("optimizeMixtureWeights: the model is no mixture");
+    if (!current_it) computeLikelihood();
+    computePatternLhCat(WSL_MIXTURE, nullptr);
+    const std::vector<double> w_old = getMixtureWeights();
+    std::vector<double> w(w_old);
+    const double pinv_old = p_invar ? *p_invar : 0.0;
+    int n = 0, conv = 0;
+    mixWeightsEM(nmixture, w.data(), p_invar, &n, &conv, nullptr);
+    if (nsteps) *nsteps = n;
+    if (converged) *converged = conv;
+    for (int q = 0; q < ncat; q++) m_props[q] *= w[m_cat_class[q]] / w_old[m_cat_class[q]];
+    if (p_invar && pinv_old > 0.0) {   // computePtnInvar is linear in p_invar
+        const double v = *p_invar / pinv_old;
+        for (double &x : ptn_invar) x *= v;
+        weights_dirty = true;
+    }
+    inputs_dirty = model_dirty = true;
+    theta_computed = false;
+    clearAllPartialLH();
+    return computeLikelihood();
+}
+
+void PhyloTree::computePatternStateFreq(const double *class_freq, double *ptn_state_freq) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (!class_freq || !ptn_state_freq) throw std::runtime_error("computePatternStateFreq: null argument");
+    computePatternLhCat(WSL_MIXTURE, nullptr);
+    check(iqhip_mix_posteriors(engine, class_freq, nullptr, ptn_state_freq), "iqhip_mix_posteriors");
+}
+
 void PhyloTree::setBootSamples(const float *samples, int nsamples) {
     if (!engine) throw std::runtime_error("no engine");
     pushInputs();

@@ -349,6 +349,25 @@ public:
     void setRateCategories(const double *rates, const double *props);
     void scaleLength(double norm);   // mtree.cpp: every branch length times norm
 
+    // ---- EM estimation of mixture class weights (ModelMixture::optimizeWeights, model/modelmixture.cpp:1355-1416) -------
+    // computePatternLhCat(WSL_MIXTURE) (phylotree.cpp:1108-1160): theta of current_it is rebuilt and the per-class pattern
+    // likelihoods are left on the device (iqhip_mix_class_lh); out: nullptr or nptn * nmixture doubles [ptn][class]
+    enum SiteLoglType { WSL_MIXTURE = 3 };
+    void computePatternLhCat(SiteLoglType wsl, double *out);
+    // the class weights inside the component weights: w[m] = sum of m_props over the components of class m (ascending)
+    std::vector<double> getMixtureWeights() const;
+    // optimizeWeights restated: evaluate on the current branch, run the EM on the device with max_steps = nmixture, rescale
+    // the component weights (props[q] *= w_new[m] / w_old[m]) and, with +I (p_invar != nullptr and *p_invar > 0; updated),
+    // ptn_invar (linear in p_invar), re-send the model, clear all vectors; returns computeLikelihood().
+    // nsteps / converged (or nullptr): what the EM reported
+    double optimizeMixtureWeights(double *p_invar = nullptr, int *nsteps = nullptr, int *converged = nullptr);
+    // the EM alone on the matrix of the last computePatternLhCat(WSL_MIXTURE) (iqhip_mix_weights_em); the tree is unchanged
+    void mixWeightsEM(int max_steps, double *weights, double *p_invar, int *nsteps, int *converged, double *trace);
+    // PhyloTree::computePatternStateFreq (phylotree.cpp:1162-1196): class_freq [nmixture][nstates] -> ptn_state_freq
+    // [nptn][nstates]
+    void computePatternStateFreq(const double *class_freq, double *ptn_state_freq);
+    double getAlnNSite() const;   // the sum of the pattern frequencies
+
     // UFBoot: boot_samples uploaded once; computeRELL = saveCurrentTree's dot products, on the device
     void setBootSamples(const float *samples /*[nsamples][nptn]*/, int nsamples);
     // the same matrix drawn on the device (iqhip_gen_boot_samples): nsamples replicates of ndraws sites each
