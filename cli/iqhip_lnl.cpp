@@ -51,6 +51,15 @@
 // divided by their mean under the new weights and all branch lengths multiplied by it (likelihood unchanged), so the printed
 // string, read back, is the model of the printed tree.  -mixweights refuses +I (the category rates would follow p_invar);
 // -emrates, -wsr and +ASC refuse mixtures.
+// With -optmodel the parameters of the model are estimated (ModelOptimizer, model_opt_host.h = ModelFactory::optimizeParameters
+// over ModelGTR / RateGamma / RateInvar / RateGammaInvar::optimizeParameters): the rate parameters of the DNA models by the
+// reference's BFGS, whose forward-difference stencils run as the classes of one candidate mixture engine (one traversal per
+// stencil), the Gamma shape and the proportion of invariable sites by Brent, branch lengths in between unless -blfix.  With
+// this flag the substitution model, +I and +G<k> may come without braces (-m GTR+I+G4) and start from the reference's
+// defaults: rates 1, alpha 1, p-inv = half the fraction of constant sites; values in braces are starting values.  It prints
+// the reference's "Optimal log-likelihood:", "Rate parameters:", "Proportion of invariable sites:" and "Gamma shape alpha:"
+// lines and the model string with the estimates, which is also what <prefix>.iqhip records.  MIX{}, +R, +ASC and +FO are
+// refused with this flag; without it a string that leaves values out is refused as before.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -67,6 +76,7 @@
 
 #include "../iq-tree_amd/host/alignment_host.h"
 #include "../iq-tree_amd/host/model_host.h"
+#include "../iq-tree_amd/host/model_opt_host.h"
 #include "../iq-tree_amd/host/phylo_host.h"
 
 using namespace iqhost;
@@ -153,12 +163,13 @@ static void usage() {
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
-            "                 [-mixweights]\n"
+            "                 [-mixweights] [-optmodel]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC;\n"
             "         +R3{w1,r1,w2,r2,w3,r3}, or with -emrates (weights and rates estimated by EM) also a bare +R3;\n"
+            "         with -optmodel (parameters estimated) also GTR+I+G4, HKY+G4{0.7}, <paml matrix file>+I+G4: braces are starting values;\n"
             "         'MIX{JC,HKY{2.0}:1.5,GTR{..}+F{..}:0.5:0.2}+G4{0.8}' (class[:rate[:weight]]); -mixweights estimates the weights by EM\n");
 }
 
@@ -169,7 +180,7 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
     int zb = 0, sprrad = 0;
-    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false;
+    bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false, optmodel = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -199,6 +210,7 @@ int main(int argc, char **argv) {
         else if (a == "-emrates") emrates = true;
         else if (a == "-wsr") wsr = true;
         else if (a == "-mixweights") mixweights = true;
+        else if (a == "-optmodel") optmodel = true;
         else if (a == "-sprrad") {
             sprrad = atoi(next().c_str());
             if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
@@ -229,7 +241,12 @@ int main(int argc, char **argv) {
                 model_str = model_str.substr(0, r0) + freeRateToken(p0, rt0) + model_str.substr(r1);
             }
         }
-        ModelSpec spec = parseModelString(model_str);
+        ModelSpec spec = parseModelString(model_str, optmodel);
+        if (optmodel) {
+            if (emrates || mixweights) throw std::runtime_error("-optmodel excludes -emrates and -mixweights");
+            ModelOptimizer::checkScope(spec);
+            ModelOptimizer::startingValues(spec, aln);
+        }
         ModelInputs mi;
         buildModel(spec, aln, mi);  // frequencies from the observed patterns only
         const int nsite = aln.getNSite();
@@ -367,23 +384,14 @@ int main(int argc, char **argv) {
         if (emrates) {
             if (spec.p_invar > 0.0) throw std::runtime_error("-emrates: +I+R is not supported");
             const double logl_epsilon = 0.01;   // params.modeps (tools.cpp)
-            double cur_lh = lnl;
-            printf("1. Initial log-likelihood: %.6f\n", cur_lh);
             int em_steps = 0, em_rounds = 0;
-            for (int i = 2; i < 100; i++) {   // params.num_param_iterations
-                if (!blfix) tree.optimizeAllBranches(std::min(i, 3), logl_epsilon);
+            ModelOptimizer::parameterLoop(tree, blfix, logl_epsilon, lnl, [&]() {
                 std::vector<PhyloTree::EmStep> steps;
                 const double new_lh = tree.optimizeFreeRatesEM(&steps);
                 em_steps += (int)steps.size();
                 for (const PhyloTree::EmStep &st : steps) em_rounds += st.rounds;
-                if (new_lh > cur_lh + logl_epsilon) {
-                    cur_lh = new_lh;
-                    printf("%d. Current log-likelihood: %.6f\n", i, cur_lh);
-                } else {
-                    if (!blfix) cur_lh = tree.optimizeAllBranches(100, logl_epsilon);
-                    break;
-                }
-            }
+                return new_lh;
+            }, true);
             // rescaleRates, then branch lengths in substitutions per site (modelfactory.cpp:1035-1040)
             std::vector<double> props = tree.getProps(), rates = tree.getRates();
             double mean_rate = 0.0;
@@ -408,22 +416,13 @@ int main(int argc, char **argv) {
         } else if (mixweights) {
             // the loop of ModelFactory::optimizeParameters with the substitution models fixed, as for -emrates
             const double logl_epsilon = 0.01;   // params.modeps
-            double cur_lh = lnl;
-            printf("1. Initial log-likelihood: %.6f\n", cur_lh);
             int em_steps = 0;
-            for (int i = 2; i < 100; i++) {   // params.num_param_iterations
-                if (!blfix) tree.optimizeAllBranches(std::min(i, 3), logl_epsilon);
+            ModelOptimizer::parameterLoop(tree, blfix, logl_epsilon, lnl, [&]() {
                 int steps = 0;
                 const double new_lh = tree.optimizeMixtureWeights(nullptr, &steps);
                 em_steps += steps;
-                if (new_lh > cur_lh + logl_epsilon) {
-                    cur_lh = new_lh;
-                    printf("%d. Current log-likelihood: %.6f\n", i, cur_lh);
-                } else {
-                    if (!blfix) cur_lh = tree.optimizeAllBranches(100, logl_epsilon);
-                    break;
-                }
-            }
+                return new_lh;
+            }, true);
             // The class rates were normalised with the weights the run started from.  As the reference does when it writes the
             // model (modelmixture.cpp:1552-1563) and as -emrates does for +R: rates over their new mean, all branch lengths
             // times it -- the likelihood is unchanged and the printed string reads back as the model the tree holds
@@ -448,6 +447,25 @@ int main(int argc, char **argv) {
             printf("Mixture weights:");
             for (double x : w) printf(" %g", x);
             printf("\nModel with estimated weights: %s\n", model_str.c_str());
+            printf("Optimal log-likelihood: %.17g\n", lnl);
+        } else if (optmodel) {
+            ModelOptimizer opt(tree, aln, spec, true);
+            opt.optimizeParameters(blfix, DEFAULT_LOGL_EPSILON, DEFAULT_GRADIENT_EPSILON, true);
+            tree.clearAllPartialLH();
+            lnl = tree.computeLikelihood(pattern_lh.data());
+            mi = opt.getInputs();
+            model_str = opt.modelString();
+            int stencils = 0, stencil_trav = 0, single_trav = 0, redone = 0;
+            for (const ModelOptimizer::Call &c : opt.trace) {
+                stencils += c.stencils;
+                stencil_trav += c.stencil_traversals;
+                single_trav += c.single_traversals;
+                redone += c.stencils_redone;
+            }
+            printf("Parameters optimization took %d rounds: %d stencils in %d batched traversals (%d redone), %d single traversals\n",
+                   opt.rounds, stencils, stencil_trav, redone, single_trav);
+            printf("%s", opt.writeInfo().c_str());
+            printf("Model with estimated parameters: %s\n", model_str.c_str());
             printf("Optimal log-likelihood: %.17g\n", lnl);
         } else if (!blfix) {
             lnl = tree.optimizeAllBranches();

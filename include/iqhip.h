@@ -406,6 +406,32 @@ int iqhip_mix_weights_em(iqhip_engine *e, int max_steps, double nsites, double *
 int iqhip_mix_posteriors(iqhip_engine *e, const double *class_freq /* nclass*nstates or NULL */,
                          double *post /* nptn*nclass or NULL */, double *state_freq /* nptn*nstates or NULL */);
 int iqhip_debug_mix_timing(iqhip_engine *e, double *ms /* 2 */, int64_t *launches);
+/* Per-class log-likelihoods of a mixture engine: K candidate models as the K classes of one engine (class m = candidate m:
+ * its own eigen-system and tip_partial_lh slice, its components' rates and props), one traversal, K values.
+ * iqhip_class_lnl reads the theta resident for the branch (a, b).  With Lc[p][m] what iqhip_mix_class_lh defines (the
+ * components of class m in ascending q, the same table and the same arithmetic per component):
+ *   lnl[m] = sum over p with ptn_freq[p] > 0 of
+ *            ptn_freq[p] (log(Lc[p][m] / class_weight[m] + inv_m[p]) + (max(sc_a[p], 0) + max(sc_b[p], 0)) LOG_SCALING_THRESHOLD)
+ *   inv_m[p] = class_invar[m][p] when the pointer is given, else the engine's resident ptn_invar[p] for every class (a
+ *   stencil over substitution parameters with fixed frequencies and fixed p-inv).  This is the expression the branch lnL
+ *   forms for a plain model with the two scale counters put back (as iqhip_em_objective): lnl[m] is the log-likelihood of
+ *   class m's model alone on this tree.  class_weight[m] is the weight the caller folded into that class's props; it may
+ *   be 1 (iqhip_set_mixture_model does not require the weights to sum to 1).
+ *   UNDERFLOW RULE as iqhip_em_objective: the engine rescales a pattern only when ALL components are small.  A term whose
+ *   argument is not a positive normal number takes log(DBL_MIN) and is counted in floored[m] (NULL: not reported).
+ *   The nptn x nclass matrix is not written: every workgroup reduces its tile to one partial per class and a fold kernel adds
+ *   the rows in a fixed order.  No atomics; the decomposition follows from the padded pattern count and nclass alone: a
+ *   repeated call returns the same bits.
+ * Engines whose model came through iqhip_set_mixture_model (one class is allowed), 4, 20 or 64 states, the wide 4-state
+ * engines included.  IQHIP_ERR_UNSUPPORTED: a model set through iqhip_set_model, +ASC, sharded engines and communicator
+ * ranks, embedded state counts.  IQHIP_ERR_INVALID: a null argument, a planning-only engine, theta not resident for that
+ * branch, a negative or NaN len, a class_weight <= 0 or not finite.
+ * iqhip_debug_class_lnl_timing: with iqhip_timing_enable, *ms = the device time (HIP events, milliseconds) of the two
+ *   launches of the last iqhip_class_lnl call. */
+int iqhip_class_lnl(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len,
+                    const double *class_weight /* nclass */, const double *class_invar /* NULL or nclass*nptn, [class][ptn] */,
+                    double *lnl /* nclass */, int64_t *floored /* nclass or NULL */);
+int iqhip_debug_class_lnl_timing(iqhip_engine *e, double *ms);
 int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *out /* nptn */);
 int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int nsamples);
 int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double *rell /* nsamples */);

@@ -33,6 +33,7 @@ IQHIP_SYMBOLS = [
     "iqhip_set_mixture_model", "iqhip_pattern_lh_cat", "iqhip_optimize_branch_batch",
     "iqhip_em_posteriors", "iqhip_em_fetch_posteriors", "iqhip_em_site_rates", "iqhip_em_objective", "iqhip_debug_em_timing",
     "iqhip_mix_class_lh", "iqhip_mix_weights_em", "iqhip_mix_posteriors", "iqhip_debug_mix_timing",
+    "iqhip_class_lnl", "iqhip_debug_class_lnl_timing",
     "iqhip_create_sharded", "iqhip_num_shards", "iqhip_shard_range", "iqhip_comm_unique_id", "iqhip_comm_init_rank",
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
@@ -156,6 +157,7 @@ def libiqhip():
     lib.iqhip_set_ptn_invar.argtypes = [vp, dp]
     lib.iqhip_set_ascertainment.argtypes = [vp, C.c_int64, C.c_double]
     lib.iqhip_set_model.argtypes = [vp, dp, dp, dp, dp, dp, C.c_int, dp]
+    lib.iqhip_set_mixture_model.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp, dp, dp, dp, dp, C.c_int, dp]
     lib.iqhip_update_partials.argtypes = [vp, C.POINTER(NodeOp), C.c_int, dp]
     lib.iqhip_branch_lnl.argtypes = [vp, BranchEnd, BranchEnd, C.c_double, dp]
     lib.iqhip_traverse_lnl.argtypes = [vp, C.POINTER(NodeOp), C.c_int, BranchEnd, BranchEnd,
@@ -205,6 +207,8 @@ def libiqhip():
     lib.iqhip_mix_weights_em.argtypes = [vp, C.c_int, C.c_double, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int), dp]
     lib.iqhip_mix_posteriors.argtypes = [vp, dp, dp, dp]
     lib.iqhip_debug_mix_timing.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.iqhip_class_lnl.argtypes = [vp, BranchEnd, BranchEnd, C.c_double, dp, dp, dp, C.POINTER(C.c_int64)]
+    lib.iqhip_debug_class_lnl_timing.argtypes = [vp, dp]
     lib.iqhip_newton_host_update.argtypes = [vp, C.c_double, C.c_double, dp, C.POINTER(C.c_int)]
     lib.iqhip_newton_host_result.argtypes = [vp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.iqhip_timing_enable.argtypes = [vp, C.c_int]
@@ -338,6 +342,22 @@ def libiqhost():
     lib.iqhost_brent_init.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, dp]
     lib.iqhost_brent_update.argtypes = [vp, C.c_double, dp, C.POINTER(C.c_int)]
     lib.iqhost_brent_result.argtypes = [vp, dp, dp, C.POINTER(C.c_int)]
+    lib.iqhost_modelopt_create.argtypes = [C.POINTER(vp), vp, vp, C.c_char_p, C.c_int]
+    lib.iqhost_modelopt_destroy.argtypes = [vp]
+    lib.iqhost_modelopt_destroy.restype = None
+    lib.iqhost_modelopt_run.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, C.POINTER(C.c_int)]
+    lib.iqhost_modelopt_string.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+    lib.iqhost_modelopt_values.argtypes = [vp, dp, dp, C.c_int]
+    lib.iqhost_modelopt_trace_len.argtypes = [vp]
+    lib.iqhost_modelopt_trace_row.argtypes = [vp, C.c_int, C.c_char_p, C.POINTER(C.c_int), dp, dp, dp, dp, dp, C.c_int]
+    lib.iqhost_modelopt_describe.argtypes = [C.c_char_p, C.c_int, dp]
+    lib.iqhost_bfgs_create.argtypes = [C.POINTER(vp), C.c_int, dp, dp, dp, C.POINTER(C.c_int), C.c_double]
+    lib.iqhost_bfgs_destroy.argtypes = [vp]
+    lib.iqhost_bfgs_destroy.restype = None
+    lib.iqhost_bfgs_request.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.iqhost_bfgs_points.argtypes = [vp, dp, dp]
+    lib.iqhost_bfgs_update.argtypes = [vp, dp, C.c_int]
+    lib.iqhost_bfgs_result.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int)]
     lib.iqhost_free_rate_start.argtypes = [C.c_int, dp, dp]
     lib.iqhost_em_posteriors.argtypes = [vp, dp, dp]
     lib.iqhost_em_objective.argtypes = [vp, C.c_int, C.c_int, dp, C.POINTER(C.c_int64)]
@@ -349,6 +369,8 @@ def libiqhost():
     lib.iqhost_pattern_state_freq.argtypes = [vp, dp, dp]
     lib.iqhost_optimize_mixture_weights.argtypes = [vp, dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.iqhost_mix_timing.argtypes = [vp, dp, C.POINTER(C.c_int64)]
+    lib.iqhost_class_lnl.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.POINTER(C.c_int64)]
+    lib.iqhost_class_lnl_timing.argtypes = [vp, dp]
     lib.iqhost_compute_rell.argtypes = [vp, dp, C.c_int]
     lib.iqhost_last_plan.argtypes = [vp, C.POINTER(C.c_int), dp, C.POINTER(C.c_uint64), C.c_int]
     lib.iqhost_num_partial_lh_computations.argtypes = [vp]
@@ -545,6 +567,166 @@ class BrentStateMachine:
         if self.lib.iqhost_brent_result(self.state, C.byref(optx), C.byref(fx), C.byref(n)) != 0:
             raise HostError(self.lib.iqhost_last_error().decode())
         return optx.value, fx.value, n.value
+
+
+class BfgsStateMachine:
+    """The first pass of Optimization::minimizeMultiDimen (dfpmin over lnsrch and the forward-difference derivativeFunk) as
+    the host mirror's resumable machine (bfgs_host.h, iqhost_bfgs_*).  .kind is "stencil" (.points[ndim + 1, ndim]: the base
+    point and its ndim forward points, .steps[ndim]; independent of each other, so they may be evaluated in one batch),
+    "single" (.points[1, ndim]: a line-search trial) or "done".  Feed the function values, in the order of the points, to
+    update() until .done; then result() -> dict(x, fret, iter, gradient, stencils, singles).  bound_check = True (the
+    reference's random restart at the boundary) is refused."""
+    KINDS = ("stencil", "single", "done")
+
+    def __init__(self, guess, lower, upper, gtol, bound_check=None):
+        self.lib = libiqhost()
+        g, lo, up = (np.ascontiguousarray(v, dtype=np.float64) for v in (guess, lower, upper))
+        self.ndim = g.size
+        assert lo.size == self.ndim and up.size == self.ndim
+        bc = None
+        if bound_check is not None:
+            bc = np.ascontiguousarray(bound_check, dtype=np.int32)
+            assert bc.size == self.ndim
+        self.h = C.c_void_p()
+        if self.lib.iqhost_bfgs_create(C.byref(self.h), self.ndim, _dptr(g), _dptr(lo), _dptr(up),
+                                       None if bc is None else bc.ctypes.data_as(C.POINTER(C.c_int)), float(gtol)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self._fetch()
+
+    def _fetch(self):
+        kind, npts = C.c_int(), C.c_int()
+        if self.lib.iqhost_bfgs_request(self.h, C.byref(kind), C.byref(npts)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self.kind = self.KINDS[kind.value]
+        self.done = self.kind == "done"
+        self.points = np.zeros((npts.value, self.ndim))
+        self.steps = np.zeros(self.ndim)
+        if npts.value and self.lib.iqhost_bfgs_points(self.h, _dptr(self.points), _dptr(self.steps)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        if self.kind != "stencil":
+            self.steps = None
+
+    def update(self, values):
+        v = np.ascontiguousarray(np.atleast_1d(values), dtype=np.float64)
+        if self.lib.iqhost_bfgs_update(self.h, _dptr(v), v.size) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self._fetch()
+        return self.kind
+
+    def result(self):
+        x, g, fret, cnt = np.zeros(self.ndim), np.zeros(self.ndim), C.c_double(), (C.c_int * 3)()
+        if self.lib.iqhost_bfgs_result(self.h, _dptr(x), C.byref(fret), _dptr(g), cnt) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return dict(x=x, fret=fret.value, iter=cnt[0], gradient=g, stencils=cnt[1], singles=cnt[2])
+
+    def close(self):
+        if self.h:
+            self.lib.iqhost_bfgs_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+GRADIENT_EPSILON = 0.0001   # the default of ModelFactory::optimizeParameters (model/modelfactory.h:169)
+LOGL_EPSILON = 0.01         # params.modeps (tools.cpp:871)
+
+
+def model_opt_describe(model_string, nstates=4):
+    """No device: what ModelOptimizer would estimate for this -m string -> dict(ndim, K, lower, upper, has_gamma, has_invar,
+    alpha_bounds, pinv_lower); raises HostError for what it refuses (MIX{}, +R, +ASC, +FO)."""
+    lib = libiqhost()
+    out = np.zeros(9)
+    if lib.iqhost_modelopt_describe(model_string.encode(), int(nstates), _dptr(out)) != 0:
+        raise HostError(lib.iqhost_last_error().decode())
+    return dict(ndim=int(out[0]), K=int(out[1]), lower=out[2], upper=out[3], has_gamma=bool(out[4]), has_invar=bool(out[5]),
+                alpha_bounds=(out[6], out[7]), pinv_lower=out[8])
+
+
+class ModelOptimizer:
+    """Estimation of model parameters on the device (model_opt_host.h): the DNA substitution rates by the reference's BFGS
+    with the forward-difference stencil batched as the classes of a candidate mixture engine (batch=True: for alignments of
+    at most BATCH_MAX_PATTERNS = 5 000 patterns, the measured crossover; batch="always": at every size), the Gamma shape
+    and p-inv by Brent, inside the loop of ModelFactory::optimizeParameters.  tree: a PhyloTree holding aln's patterns
+    (aln.states, aln.ptn_freq), its engine attached, with a model of the string's category count; model_string: the -m
+    string, values in braces are starting values, a substitution model, +I or +G<k> without braces starts from the
+    reference's defaults.  .trace: per optimiser call dict(what, requests, stencils, stencil_traversals, single_traversals,
+    stencils_redone, K, lnl_before, lnl_after, x0, grad0, h0, values0 (the first stencil))."""
+
+    def __init__(self, tree, aln, model_string, batch=True):
+        self.lib = libiqhost()
+        self.tree, self.aln = tree, aln          # (kept alive: the optimiser refers to both)
+        self.h = C.c_void_p()
+        mode = 2 if batch == "always" else int(bool(batch))
+        if self.lib.iqhost_modelopt_create(C.byref(self.h), tree.h, aln.h, model_string.encode(), mode) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+
+    def _run(self, what, fixed_len=False, logl_epsilon=LOGL_EPSILON, gradient_epsilon=GRADIENT_EPSILON):
+        lnl, rounds = C.c_double(), C.c_int()
+        if self.lib.iqhost_modelopt_run(self.h, what, int(bool(fixed_len)), float(logl_epsilon), float(gradient_epsilon),
+                                        C.byref(lnl), C.byref(rounds)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        self.rounds = rounds.value
+        return lnl.value
+
+    def optimize_model(self, gradient_epsilon=GRADIENT_EPSILON):
+        """ModelGTR::optimizeParameters -> lnL (0.0: the model has no free rate parameter)"""
+        return self._run(0, gradient_epsilon=gradient_epsilon)
+
+    def optimize_rates(self, gradient_epsilon=GRADIENT_EPSILON):
+        """RateGamma / RateInvar / RateGammaInvar::optimizeParameters -> lnL (0.0: neither +G nor +I)"""
+        return self._run(1, gradient_epsilon=gradient_epsilon)
+
+    def optimize_parameters(self, fixed_len=False, logl_epsilon=LOGL_EPSILON, gradient_epsilon=GRADIENT_EPSILON):
+        """ModelFactory::optimizeParameters -> lnL; .rounds = the rounds taken"""
+        return self._run(3, fixed_len, logl_epsilon, gradient_epsilon)
+
+    def model_string(self):
+        buf = C.create_string_buffer(4096)
+        if self.lib.iqhost_modelopt_string(self.h, 0, buf, len(buf)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return buf.value.decode()
+
+    def write_info(self):
+        buf = C.create_string_buffer(4096)
+        if self.lib.iqhost_modelopt_string(self.h, 1, buf, len(buf)) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return buf.value.decode()
+
+    def values(self):
+        """-> dict(params, alpha (None without +G), p_invar (None without +I))"""
+        v, p = np.zeros(5), np.zeros(8)
+        if self.lib.iqhost_modelopt_values(self.h, _dptr(v), _dptr(p), p.size) != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return dict(params=p[:int(v[0])].copy(), alpha=v[1] if v[3] else None, p_invar=v[2] if v[4] else None)
+
+    @property
+    def trace(self):
+        out = []
+        for k in range(self.lib.iqhost_modelopt_trace_len(self.h)):
+            what, ints, lnl = C.create_string_buffer(16), (C.c_int * 7)(), np.zeros(2)
+            x0, g0, h0, v0 = np.zeros(8), np.zeros(8), np.zeros(8), np.zeros(9)
+            if self.lib.iqhost_modelopt_trace_row(self.h, k, what, ints, _dptr(lnl), _dptr(x0), _dptr(g0), _dptr(h0), _dptr(v0), 8) != 0:
+                raise HostError(self.lib.iqhost_last_error().decode())
+            n = ints[6]
+            out.append(dict(what=what.value.decode(), requests=ints[0], stencils=ints[1], stencil_traversals=ints[2],
+                            single_traversals=ints[3], stencils_redone=ints[4], K=ints[5], lnl_before=lnl[0], lnl_after=lnl[1],
+                            x0=x0[:n].copy(), grad0=g0[:n].copy(), h0=h0[:n].copy(), values0=v0[:n + 1].copy() if n else v0[:0]))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.iqhost_modelopt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def free_rate_start(k):
@@ -1332,6 +1514,29 @@ class PhyloTree:
         ms, n = np.zeros(2), C.c_int64()
         self._chk(self.lib.iqhost_mix_timing(self.h, _dptr(ms), C.byref(n)))
         return dict(class_lh_ms=ms[0], em_ms=ms[1], launches=n.value)
+
+    def class_lnl(self, a, b, class_weight, class_invar=None):
+        """iqhip_class_lnl for the branch a -> b (theta is rebuilt): the log-likelihood of every class's model alone on this
+        tree, K candidate models as the K classes of the mixture the tree holds.  class_weight[nclass]: the weight folded
+        into each class's props (1 for candidates); class_invar: None (the resident ptn_invar for every class) or
+        [nclass, nptn] -> (lnl[nclass], floored[nclass])."""
+        k = self.nclass
+        w = np.ascontiguousarray(class_weight, dtype=np.float64)
+        assert w.shape == (k,)
+        inv = None
+        if class_invar is not None:
+            inv = np.ascontiguousarray(class_invar, dtype=np.float64)
+            assert inv.shape == (k, self.nptn)
+        lnl, fl = np.zeros(k), np.zeros(k, dtype=np.int64)
+        self._chk(self.lib.iqhost_class_lnl(self.h, a, b, _dptr(w), None if inv is None else _dptr(inv), _dptr(lnl),
+                                            fl.ctypes.data_as(C.POINTER(C.c_int64))))
+        return lnl, fl
+
+    def class_lnl_timing(self):
+        """iqhip_debug_class_lnl_timing -> the device time (ms) of the last class_lnl() launches (while timing is enabled)."""
+        ms = C.c_double()
+        self._chk(self.lib.iqhost_class_lnl_timing(self.h, C.byref(ms)))
+        return ms.value
 
     def set_boot_samples(self, samples):
         """UFBoot boot_samples: float32 [nsamples, nptn] pattern weights, uploaded once."""

@@ -698,6 +698,7 @@ extern "C" int iqhip_set_model(iqhip_engine *e, const double *eval, const double
     if (e && e->embed2 && e->shards.empty())
         return set_model_binary(e, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
     int rc = set_model_common(e, 1, nullptr, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
+    if (!rc) e->mixture_api = false;
     if (!rc && cherry_candidate(e)) {
         rc = cherry_sync_model(e, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
         e->cherry_model_synced = !rc && e->pair != nullptr;
@@ -712,7 +713,9 @@ extern "C" int iqhip_set_mixture_model(iqhip_engine *e, int nclass, const int32_
         return fail(IQHIP_ERR_UNSUPPORTED, "mixture models of embedded data (state counts other than 4, 20, 64) are not implemented");
     if (e && e->embed2 && e->shards.empty())
         return set_model_binary(e, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
-    return set_model_common(e, nclass, cat_class, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
+    const int rc = set_model_common(e, nclass, cat_class, eval, evec, inv_evec, rates, props, state_unknown, tip_partial_lh);
+    if (!rc) e->mixture_api = true;   // (iqhip_class_lnl: a mixture engine, even with one class)
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------

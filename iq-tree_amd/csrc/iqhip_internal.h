@@ -496,6 +496,15 @@ struct iqhip_engine {
         double ms[2] = {0.0, 0.0};   // iqhip_debug_mix_timing: the class-lh launch, the EM chain (while timing is enabled)
         int64_t launches = 0;        // kernels the last EM chain enqueued
     } mix;
+    // per-class log-likelihoods (iqhip_class_lnl; ptnlh.hip, kernels_classlnl.hip): the per-class component lists as mix.list,
+    // the class weights [nclass], the caller's per-class invariant terms [nclass][nptn_pad], the workgroup rows of the sums
+    // and the folded values {lnl, floored} [2 nclass].  mixture_api: the model came through iqhip_set_mixture_model
+    struct {
+        iqhip::DevBuf<double> cw, inv, part, out;
+        iqhip::DevBuf<int32_t> list;
+        double ms = 0.0;             // iqhip_debug_class_lnl_timing: the last call's two launches (while timing is enabled)
+    } cl;
+    bool mixture_api = false;
     // pairwise ML distances (pairdist.hip, kernels_dist.hip): tiles of the pair list, the counts of one chunk of pairs [chunk][n * n], the
     // coefficients evec[i][k] * inv_evec[k][j] of the call's model [n][n][n], per pair the initial distance and the result
     // {optx, d2l, evaluations, status}; with iqhip_timing_enable the device time of the last iqhip_pair_distances call
@@ -1048,6 +1057,10 @@ hipError_t launch_em_objective(iqhip_engine *e, const int16_t *sc_a, const int16
 // Lc plus the one-workgroup update of the state (two launches); part holds mixem_part_rows rows of nclass doubles
 hipError_t launch_mix_class_lh(iqhip_engine *e, double len, const int32_t *d_cls_list, double *Lc);
 int64_t mixem_part_rows(const iqhip_engine *e);
+// kernels_classlnl.hip: part holds class_lnl_part_rows rows of 2 nclass doubles; out = lnl [nclass] ++ floored [nclass]
+int64_t class_lnl_part_rows(const iqhip_engine *e);
+hipError_t launch_class_lnl(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double len, const int32_t *d_cls_list,
+                            int max_comp, const double *d_cw, const double *d_class_invar, double *part, double *out);
 // the device-resident state of one EM run, all doubles: these scalars, then g [nclass], w [nclass], the log [max_steps][nclass + 1]
 enum { MIXEM_DONE = 0, MIXEM_STEPS, MIXEM_PINV, MIXEM_V, MIXEM_PINV_IN, MIXEM_USE_INV, MIXEM_NSITES, MIXEM_HDR = 8 };
 hipError_t launch_mixem_step(iqhip_engine *e, const double *Lc, double *state, int max_steps, double *part);

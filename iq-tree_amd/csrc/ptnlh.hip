@@ -1,7 +1,7 @@
 // ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: UFBoot / RELL, the store of
 // per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests, the EM for +R free-rate models, the
-// empirical-Bayes site rates and the EM for mixture class weights.  Host code only; the kernels are in kernels_rell.hip,
-// kernels_alrt.hip, kernels_topo.hip, kernels_em.hip and kernels_mixem.hip.
+// empirical-Bayes site rates, the EM for mixture class weights and the per-class log-likelihoods.  Host code only; the kernels
+// are in kernels_rell.hip, kernels_alrt.hip, kernels_topo.hip, kernels_em.hip, kernels_mixem.hip and kernels_classlnl.hip.
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -251,6 +251,80 @@ extern "C" int iqhip_mix_class_lh(iqhip_engine *e, double len, double *out) {
     e->mix.nptn_pad = e->nptn_pad;
     e->mix.nclass = e->nclass;
     return out ? mix_fetch_transposed(e, e->mix.lc.p, M, out) : IQHIP_OK;
+}
+
+// ---- per-class log-likelihoods: K candidate models as the K classes of a mixture engine (kernels_classlnl.hip) ----------
+extern "C" int iqhip_debug_class_lnl_timing(iqhip_engine *e, double *ms) {
+    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_class_lnl_timing: null argument");
+    *ms = e->cl.ms;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_class_lnl(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, const double *class_weight,
+                               const double *class_invar, double *lnl, int64_t *floored) {
+    const char *what = "iqhip_class_lnl";
+    if (!e || !class_weight || !lnl) return fail(IQHIP_ERR_INVALID, "iqhip_class_lnl: null argument");
+    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
+    if (e->asc_active || e->n_unobs > 0)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available with ascertainment bias correction");
+    if (e->embed2 || e->n_user != e->n)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
+    if (!e->model_set || !e->mixture_api)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": the model was not set through iqhip_set_mixture_model");
+    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_compute_theta first");
+    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": negative or NaN branch length");
+    const size_t P = (size_t)e->nptn_pad, N = (size_t)e->nptn, M = (size_t)e->nclass, C = (size_t)e->ncat;
+    for (size_t m = 0; m < M; m++)
+        if (!(class_weight[m] > 0.0) || !std::isfinite(class_weight[m]))
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": every class weight must be > 0 and finite");
+    HIPCHK(use_device(e));
+    const int16_t *sc[2];
+    int rc = branch_scale_counters(e, a, b, sc);
+    if (rc) return rc;
+    // theta remembers the scale counters of the ends it was built from (either order: build_branch puts a leaf first)
+    if (!((sc[0] == e->theta_a_sc && sc[1] == e->theta_b_sc) || (sc[0] == e->theta_b_sc && sc[1] == e->theta_a_sc)))
+        return fail(IQHIP_ERR_INVALID, std::string(what) + ": theta is not resident for this branch");
+    // the components of every class in ascending order, as iqhip_mix_class_lh
+    std::vector<int32_t> list(M + 1 + C);
+    size_t at = 0, max_comp = 0;
+    for (size_t m = 0; m < M; m++) {
+        list[m] = (int32_t)at;
+        for (size_t c = 0; c < C; c++)
+            if ((size_t)e->h_cls[c] == m) list[M + 1 + at++] = (int32_t)c;
+        max_comp = std::max(max_comp, at - (size_t)list[m]);
+    }
+    list[M] = (int32_t)at;
+    const size_t rows = (size_t)class_lnl_part_rows(e);
+    HIPCHK(e->cl.list.ensure(e, list.size()));
+    HIPCHK(e->cl.cw.ensure(e, M));
+    HIPCHK(e->cl.part.ensure(e, rows * 2 * M));
+    HIPCHK(e->cl.out.ensure(e, 2 * M));
+    std::vector<double> inv;
+    if (class_invar) {   // [class][nptn] -> [class][nptn_pad], padding 0
+        HIPCHK(e->cl.inv.ensure(e, M * P));
+        inv.assign(M * P, 0.0);
+        for (size_t m = 0; m < M; m++) memcpy(&inv[m * P], class_invar + m * N, sizeof(double) * N);
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable sources, and an earlier launch may still read the buffers)
+    HIPCHK(hipMemcpyAsync(e->cl.list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->cl.cw.p, class_weight, sizeof(double) * M, hipMemcpyHostToDevice, e->stream));
+    if (class_invar) HIPCHK(hipMemcpyAsync(e->cl.inv.p, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    EmTimer timer(e);
+    HIPCHK(launch_class_lnl(e, sc[0], sc[1], len, e->cl.list.p, (int)max_comp, e->cl.cw.p, class_invar ? e->cl.inv.p : nullptr,
+                            e->cl.part.p, e->cl.out.p));
+    timer.mark();
+    std::vector<double> res(2 * M);
+    HIPCHK(hipMemcpyAsync(res.data(), e->cl.out.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    timer.stop(&e->cl.ms);
+    for (size_t m = 0; m < M; m++) {
+        lnl[m] = res[m];
+        if (floored) floored[m] = (int64_t)res[M + m];
+    }
+    return IQHIP_OK;
 }
 
 extern "C" int iqhip_mix_weights_em(iqhip_engine *e, int max_steps, double nsites, double *weights, double *p_invar, int *nsteps,

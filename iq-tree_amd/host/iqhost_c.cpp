@@ -3,12 +3,16 @@
 // the repository drives the same call sequence the reference's C++ callers use.
 #include <string.h>
 
+#include <algorithm>
+#include <memory>
 #include <new>
 
 #include <string>
 #include <vector>
 
+#include "bfgs_host.h"
 #include "brent_host.h"
+#include "model_opt_host.h"
 #include "phylo_host.h"
 
 using namespace iqhost;
@@ -261,6 +265,163 @@ int iqhost_brent_result(const void *state, double *optx, double *fx, int *nevals
         *nevals = m->nevals;
     });
 }
+// ---- the reference's BFGS as a state machine (bfgs_host.h).  bound_check: NULL or ndim ints
+int iqhost_bfgs_create(void **out, int ndim, const double *guess, const double *lower, const double *upper, const int *bound_check,
+                       double gtol) {
+    IQHOST_TRY({
+        if (!out || !guess || !lower || !upper) throw std::runtime_error("iqhost_bfgs_create: null argument");
+        *out = nullptr;
+        if (ndim < 1) throw std::runtime_error("iqhost_bfgs_create: at least one dimension");
+        std::unique_ptr<bool[]> bc(new bool[(size_t)ndim]);
+        for (int i = 0; i < ndim; i++) bc[i] = bound_check && bound_check[i] != 0;
+        BfgsMachine *m = new BfgsMachine();
+        try {
+            m->init(ndim, guess, lower, upper, bc.get(), gtol);
+        } catch (...) {
+            delete m;
+            throw;
+        }
+        *out = m;
+    });
+}
+void iqhost_bfgs_destroy(void *m) { delete (BfgsMachine *)m; }
+// *kind: BfgsMachine::Request (0 stencil, 1 single, 2 done); *npoints: the points of the pending request
+int iqhost_bfgs_request(const void *h, int *kind, int *npoints) {
+    IQHOST_TRY({
+        const BfgsMachine *m = (const BfgsMachine *)h;
+        if (!m || !kind || !npoints) throw std::runtime_error("iqhost_bfgs_request: null argument");
+        *kind = (int)m->request;
+        *npoints = m->npoints();
+    });
+}
+// points: npoints * ndim doubles; steps: NULL or ndim (the stencil's h)
+int iqhost_bfgs_points(const void *h, double *points, double *steps) {
+    IQHOST_TRY({
+        const BfgsMachine *m = (const BfgsMachine *)h;
+        if (!m || !points) throw std::runtime_error("iqhost_bfgs_points: null argument");
+        memcpy(points, m->points.data(), sizeof(double) * m->points.size());
+        if (steps) memcpy(steps, m->h.data(), sizeof(double) * m->h.size());
+    });
+}
+int iqhost_bfgs_update(void *h, const double *values, int nvalues) {
+    IQHOST_TRY({
+        BfgsMachine *m = (BfgsMachine *)h;
+        if (!m || !values) throw std::runtime_error("iqhost_bfgs_update: null argument");
+        if (m->request == BfgsMachine::DONE) throw std::runtime_error("iqhost_bfgs_update: the search has finished");
+        if (nvalues != m->npoints()) throw std::runtime_error("iqhost_bfgs_update: one value per requested point");
+        m->update(values);
+    });
+}
+// x, gradient: ndim each (gradient: of the last stencil); counts: {iter, stencils, singles}
+int iqhost_bfgs_result(const void *h, double *x, double *fret, double *gradient, int *counts) {
+    IQHOST_TRY({
+        const BfgsMachine *m = (const BfgsMachine *)h;
+        if (!m || !x || !fret || !counts) throw std::runtime_error("iqhost_bfgs_result: null argument");
+        memcpy(x, m->x.data(), sizeof(double) * m->x.size());
+        if (gradient) memcpy(gradient, m->g.data(), sizeof(double) * m->g.size());
+        *fret = m->fret;
+        counts[0] = m->iter;
+        counts[1] = m->nstencils;
+        counts[2] = m->nsingles;
+    });
+}
+// ---- model parameter estimation (model_opt_host.h).  tree: an iqhost tree with its engine attached; aln: an iqaln handle;
+// batch: 0 every point on the main tree, 1 stencils batched up to BATCH_MAX_PATTERNS patterns, 2 batched at every size
+int iqhost_modelopt_create(void **out, void *tree, void *aln, const char *model, int batch) {
+    IQHOST_TRY({
+        if (!out || !tree || !aln || !model) throw std::runtime_error("iqhost_modelopt_create: null argument");
+        *out = nullptr;
+        ModelOptimizer *o = new ModelOptimizer(*(PhyloTree *)tree, *(const Alignment *)aln, parseModelString(model, true), batch != 0);
+        if (batch == 2) o->batch_max_patterns = INT64_MAX;   // batched at every size
+        *out = o;
+    });
+}
+void iqhost_modelopt_destroy(void *h) { delete (ModelOptimizer *)h; }
+// what: 0 optimizeModel, 1 optimizeRates, 2 optimizeParametersOnly, 3 optimizeParameters (fixed_len, logl_epsilon used)
+int iqhost_modelopt_run(void *h, int what, int fixed_len, double logl_epsilon, double gradient_epsilon, double *lnl, int *rounds) {
+    IQHOST_TRY({
+        ModelOptimizer *o = (ModelOptimizer *)h;
+        if (!o || !lnl) throw std::runtime_error("iqhost_modelopt_run: null argument");
+        if (what == 0) *lnl = o->optimizeModel(gradient_epsilon);
+        else if (what == 1) *lnl = o->optimizeRates(gradient_epsilon);
+        else if (what == 2) *lnl = o->optimizeParametersOnly(gradient_epsilon);
+        else if (what == 3) *lnl = o->optimizeParameters(fixed_len != 0, logl_epsilon, gradient_epsilon, false);
+        else throw std::runtime_error("iqhost_modelopt_run: unknown step");
+        if (rounds) *rounds = o->rounds;
+    });
+}
+// which: 0 the model string with the estimates, 1 the writeInfo lines
+int iqhost_modelopt_string(void *h, int which, char *buf, int cap) {
+    IQHOST_TRY({
+        const ModelOptimizer *o = (const ModelOptimizer *)h;
+        if (!o || !buf || cap < 1) throw std::runtime_error("iqhost_modelopt_string: null argument");
+        const std::string s = which == 0 ? o->modelString() : o->writeInfo();
+        if ((int)s.size() + 1 > cap) throw std::runtime_error("iqhost_modelopt_string: buffer too small");
+        memcpy(buf, s.c_str(), s.size() + 1);
+    });
+}
+// vals: {nparams, alpha, p_invar, has_gamma, has_invar}; params: up to cap rate parameters
+int iqhost_modelopt_values(void *h, double *vals, double *params, int cap) {
+    IQHOST_TRY({
+        const ModelOptimizer *o = (const ModelOptimizer *)h;
+        if (!o || !vals) throw std::runtime_error("iqhost_modelopt_values: null argument");
+        const ModelSpec &s = o->getSpec();
+        const int k = ModelOptimizer::numParams(s);
+        vals[0] = k;
+        vals[1] = s.gamma_shape;
+        vals[2] = s.p_invar;
+        vals[3] = s.has_gamma;
+        vals[4] = s.has_invar;
+        for (int i = 0; i < k && i < cap && params; i++) params[i] = s.params[(size_t)i];
+    });
+}
+int iqhost_modelopt_trace_len(void *h) { return h ? (int)((ModelOptimizer *)h)->trace.size() : 0; }
+// what: 16 bytes; ints: {requests, stencils, stencil_traversals, single_traversals, stencils_redone, K, ndim of the first
+// stencil}; lnl: {before, after}; x0 / grad0 / h0: ndim each, values0: ndim + 1 (NULL: not wanted; cap doubles each)
+int iqhost_modelopt_trace_row(void *h, int k, char *what, int *ints, double *lnl, double *x0, double *grad0, double *h0,
+                              double *values0, int cap) {
+    IQHOST_TRY({
+        const ModelOptimizer *o = (const ModelOptimizer *)h;
+        if (!o || k < 0 || k >= (int)o->trace.size() || !what || !ints || !lnl) throw std::runtime_error("iqhost_modelopt_trace_row: bad argument");
+        const ModelOptimizer::Call &c = o->trace[(size_t)k];
+        snprintf(what, 16, "%s", c.what.c_str());
+        ints[0] = c.requests;
+        ints[1] = c.stencils;
+        ints[2] = c.stencil_traversals;
+        ints[3] = c.single_traversals;
+        ints[4] = c.stencils_redone;
+        ints[5] = c.K;
+        ints[6] = (int)c.x0.size();
+        lnl[0] = c.lnl_before;
+        lnl[1] = c.lnl_after;
+        auto put = [&](double *dst, const std::vector<double> &src) {
+            if (dst) memcpy(dst, src.data(), sizeof(double) * std::min((size_t)cap, src.size()));
+        };
+        put(x0, c.x0);
+        put(grad0, c.grad0);
+        put(h0, c.h0);
+        put(values0, c.values0);
+    });
+}
+// no device: the refusals of the optimiser, the number of free rate parameters, their bounds, the candidates per traversal
+// and whether alpha / p-inv are estimated.  out: {ndim, K, lower, upper, has_gamma, has_invar, alpha bounds 2, p-inv lower}
+int iqhost_modelopt_describe(const char *model, int nstates, double *out) {
+    IQHOST_TRY({
+        if (!model || !out) throw std::runtime_error("iqhost_modelopt_describe: null argument");
+        const ModelSpec s = parseModelString(model, true);
+        ModelOptimizer::checkScope(s);
+        const int k = ModelOptimizer::numParams(s);
+        out[0] = k;
+        out[1] = ModelOptimizer::candidatesPerTraversal(k, s.ncat, nstates);
+        out[2] = MIN_RATE;
+        out[3] = MAX_RATE;
+        out[4] = s.has_gamma;
+        out[5] = s.has_invar;
+        out[6] = MIN_GAMMA_SHAPE;
+        out[7] = MAX_GAMMA_SHAPE;
+        out[8] = MIN_PINVAR;
+    });
+}
 int iqhost_free_rate_start(int k, double *props, double *rates) {
     IQHOST_TRY({
         std::vector<double> p;
@@ -352,6 +513,20 @@ int iqhost_mix_timing(void *h, double *ms, int64_t *launches) {
         PhyloTree *t = (PhyloTree *)h;
         if (!t->engine) throw std::runtime_error("no engine");
         if (iqhip_debug_mix_timing(t->engine, ms, launches) != 0) throw std::runtime_error(iqhip_last_error());
+    });
+}
+// ---- per-class log-likelihoods of the branch a -> b.  class_invar: NULL or [class][ptn]; floored: NULL or nmixture
+int iqhost_class_lnl(void *h, int a, int b, const double *class_weight, const double *class_invar, double *lnl, int64_t *floored) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        t->classLnl(nei(t, a, b), t->nodes[a], class_weight, class_invar, lnl, floored);
+    });
+}
+int iqhost_class_lnl_timing(void *h, double *ms) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        if (!t->engine) throw std::runtime_error("no engine");
+        if (iqhip_debug_class_lnl_timing(t->engine, ms) != 0) throw std::runtime_error(iqhip_last_error());
     });
 }
 int iqhost_set_boot_samples(void *h, const float *samples, int nsamples) {

@@ -401,8 +401,9 @@ void parseMixture(const std::string &body, ModelSpec &spec) {
 
 }  // namespace
 
-ModelSpec parseModelString(const std::string &s) {
+ModelSpec parseModelString(const std::string &s, bool allow_missing) {
     ModelSpec spec;
+    spec.source = s;
     std::vector<std::string> toks;
     size_t start = 0;
     int depth = 0;
@@ -434,12 +435,20 @@ ModelSpec parseModelString(const std::string &s) {
         else if (u == "F1X4") spec.freq_type = ModelSpec::FREQ_CODON_1x4;
         else if (u == "F3X4") spec.freq_type = ModelSpec::FREQ_CODON_3x4;
         else if (u == "FQ") spec.freq_type = ModelSpec::FREQ_EQUAL;
-        else if (u == "F" || u == "FO") spec.freq_type = ModelSpec::FREQ_EMPIRICAL;
+        else if (u == "F" || u == "FO") {
+            spec.freq_type = ModelSpec::FREQ_EMPIRICAL;
+            spec.freq_optimized = u == "FO";
+        }
         else if (u[0] == 'F' && open == 1) {
             spec.freq_type = ModelSpec::FREQ_USER;
             spec.user_freq = parseBraces(tok, open);
         } else if (u[0] == 'I' && (u.size() == 1 || open == 1)) {
-            if (open == std::string::npos) throw std::runtime_error("+I needs a value: +I{p}");
+            spec.has_invar = true;
+            if (open == std::string::npos) {
+                if (!allow_missing) throw std::runtime_error("+I needs a value: +I{p}");
+                spec.pinvar_missing = true;
+                continue;
+            }
             std::vector<double> v = parseBraces(tok, open);
             if (v.size() != 1 || v[0] < 0.0 || v[0] >= 1.0) throw std::runtime_error("Wrong proportion of invariable sites");
             spec.p_invar = v[0];
@@ -450,12 +459,17 @@ ModelSpec parseModelString(const std::string &s) {
             int ncat = 0;
             while (i < u.size() && isdigit((unsigned char)u[i])) ncat = 10 * ncat + (u[i++] - '0');
             spec.ncat = ncat ? ncat : 4;
-            if (open == std::string::npos) throw std::runtime_error("+G needs a shape: +G4{alpha}");
+            spec.has_gamma = true;
+            spec.free_props.clear();
+            spec.free_rates.clear();
+            if (open == std::string::npos) {
+                if (!allow_missing) throw std::runtime_error("+G needs a shape: +G4{alpha}");
+                spec.gamma_missing = true;
+                continue;
+            }
             std::vector<double> v = parseBraces(tok, open);
             if (v.size() != 1 || v[0] <= 0.0) throw std::runtime_error("Wrong gamma shape");
             spec.gamma_shape = v[0];
-            spec.free_props.clear();
-            spec.free_rates.clear();
         } else if (u[0] == 'R') {   // FreeRate with given weights and rates (model/ratefree.cpp:25-55)
             size_t i = 1;
             int ncat = 0;
@@ -482,7 +496,34 @@ ModelSpec parseModelString(const std::string &s) {
         } else
             throw std::runtime_error("Unknown model component +" + tok);
     }
+    // (without allow_missing buildModel refuses such a string: "<name> expects k rate parameter(s) in {}")
+    if (allow_missing && spec.mix_classes.empty() && spec.params.empty() && numRateParams(spec) > 0) spec.params_missing = true;
     return spec;
+}
+
+int numRateParams(const ModelSpec &spec) {
+    if (!spec.mix_classes.empty()) return -1;
+    const std::string name = upper(spec.name);
+    if (name == "JC" || name == "JC69" || name == "F81" || name == "POISSON") return 0;
+    if (name == "K80" || name == "K2P" || name == "HKY" || name == "HKY85") return 1;
+    if (name == "TN" || name == "TRN" || name == "TN93") return 2;
+    if (name == "GTR") return 5;
+    if (name == "GY" || name == "GY94") return -1;
+    return 0;   // a PAML-format matrix file
+}
+
+void buildRateCategories(const ModelSpec &spec, ModelInputs &out) {
+    out.ncat = spec.ncat;
+    out.p_invar = spec.p_invar;
+    out.rates.assign(spec.ncat, 1.0);
+    discreteGammaRates(spec.gamma_shape, spec.ncat, spec.gamma_median, spec.p_invar, out.rates.data());
+    if (spec.ncat == 1 && spec.p_invar > 0.0) out.rates[0] = 1.0 / (1.0 - spec.p_invar);  // RateInvar::getRate (model/rateinvar.h)
+    // category proportions (model/rategamma.h:114, rategammainvar): (1 - p_invar)/ncat
+    out.props.assign(spec.ncat, (1.0 - spec.p_invar) / spec.ncat);
+    if (!spec.free_rates.empty()) {   // +R, +I+R: the rates as given, weights (1 - p_invar) * w (model/ratefreeinvar.h:45-52)
+        out.rates = spec.free_rates;
+        for (int c = 0; c < spec.ncat; c++) out.props[c] = (1.0 - spec.p_invar) * spec.free_props[c];
+    }
 }
 
 namespace {
@@ -647,17 +688,7 @@ void buildModel(const ModelSpec &spec, const Alignment &aln, ModelInputs &out) {
     out.nstates = n;
     out.state_freq = freq;
     decomposeRateMatrix(rates.data(), freq.data(), n, out.eig, false);
-    out.ncat = spec.ncat;
-    out.p_invar = spec.p_invar;
-    out.rates.assign(spec.ncat, 1.0);
-    discreteGammaRates(spec.gamma_shape, spec.ncat, spec.gamma_median, spec.p_invar, out.rates.data());
-    if (spec.ncat == 1 && spec.p_invar > 0.0) out.rates[0] = 1.0 / (1.0 - spec.p_invar);  // RateInvar::getRate (model/rateinvar.h)
-    // category proportions (model/rategamma.h:114, rategammainvar): (1 - p_invar)/ncat
-    out.props.assign(spec.ncat, (1.0 - spec.p_invar) / spec.ncat);
-    if (!spec.free_rates.empty()) {   // +R, +I+R: the rates as given, weights (1 - p_invar) * w (model/ratefreeinvar.h:45-52)
-        out.rates = spec.free_rates;
-        for (int c = 0; c < spec.ncat; c++) out.props[c] = (1.0 - spec.p_invar) * spec.free_props[c];
-    }
+    buildRateCategories(spec, out);
 }
 
 }  // namespace iqhost

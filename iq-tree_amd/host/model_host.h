@@ -61,10 +61,25 @@ struct ModelSpec {
     std::vector<ModelSpec> mix_classes;
     std::vector<double> mix_rates, mix_weights;
     bool mix_weights_given = false;   // some class carried a :weight (the reference's fix_prop)
+    // what the string named, and which values it left out (parseModelString with allow_missing; the model optimiser,
+    // model_opt_host.h, fills them with the reference's starting values): +I / +G given at all; no {} behind the
+    // substitution model although it has rate parameters, behind +I, behind +G; +FO (frequencies to be estimated)
+    bool has_invar = false, has_gamma = false;
+    bool params_missing = false, pinvar_missing = false, gamma_missing = false;
+    bool freq_optimized = false;
+    std::string source;               // the string as parsed
 };
 // components (classes x rate categories) an engine of this state count takes
 int maxModelComponents(int nstates);
-ModelSpec parseModelString(const std::string &s);
+// allow_missing: a substitution model, +I or +G<k> may come without braces (the *_missing flags); without it such a string is
+// refused
+ModelSpec parseModelString(const std::string &s, bool allow_missing = false);
+// free rate parameters of a substitution model by name, in the reference's order (ModelDNA::init, model/modeldna.cpp; a
+// protein matrix has none): JC / F81 / POISSON / a PAML file 0, K80 / HKY 1, TN 2, GTR 5; -1: not a model with rate
+// parameters this library optimises (GY, MIX)
+int numRateParams(const ModelSpec &spec);
+// the category rates and proportions of spec's rate heterogeneity (discrete Gamma, +I, +R) -> out.ncat / rates / props / p_invar
+void buildRateCategories(const ModelSpec &spec, struct ModelInputs &out);
 
 struct ModelInputs {      // what PhyloTree::setModel / iqhip_set_model consume
     int nstates = 0, ncat = 1;

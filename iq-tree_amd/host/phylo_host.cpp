@@ -206,6 +206,47 @@ void PhyloTree::readTreeString(const std::string &newick, const std::vector<std:
     theta_computed = false;
 }
 
+void PhyloTree::copyTopology(const PhyloTree &src) {
+    if (&src == this) return;
+    deleteAllPartialLh();
+    freeTree();
+    leafNum = src.leafNum;
+    nodeNum = src.nodeNum;
+    branchNum = src.branchNum;
+    nodes.assign(src.nodes.size(), nullptr);
+    for (size_t i = 0; i < src.nodes.size(); i++) {
+        PhyloNode *pn = new PhyloNode();
+        pn->id = src.nodes[i]->id;
+        pn->name = src.nodes[i]->name;
+        nodes[i] = pn;
+    }
+    for (size_t i = 0; i < src.nodes.size(); i++)
+        for (const PhyloNeighbor *snb : src.nodes[i]->neighbors) {
+            PhyloNeighbor *nb = new PhyloNeighbor();
+            nb->node = nodes[(size_t)snb->node->id];
+            nb->length = snb->length;
+            nb->id = snb->id;
+            nodes[i]->neighbors.push_back(nb);
+            all_neighbors.push_back(nb);
+        }
+    root = src.root ? nodes[(size_t)src.root->id] : nullptr;
+    current_it = current_it_back = nullptr;
+    theta_computed = false;
+}
+
+void PhyloTree::copyBranchLengths(const PhyloTree &src) {
+    if (src.nodes.size() != nodes.size()) throw std::runtime_error("copyBranchLengths: the trees differ");
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const std::vector<PhyloNeighbor *> &a = nodes[i]->neighbors, &b = src.nodes[i]->neighbors;
+        if (a.size() != b.size()) throw std::runtime_error("copyBranchLengths: the trees differ");
+        for (size_t k = 0; k < a.size(); k++) {
+            if (a[k]->node->id != b[k]->node->id) throw std::runtime_error("copyBranchLengths: the trees differ");
+            a[k]->length = b[k]->length;
+        }
+    }
+    theta_computed = false;
+}
+
 static void writeNewick(std::ostringstream &os, const PhyloNode *node, const PhyloNode *dad) {
     if (node->isLeaf() && dad) {
         if (node->name.empty()) os << node->id;  // leaf labels as read (MTree::printTree writes names)
@@ -362,6 +403,7 @@ void PhyloTree::attachEngine(int device) {
     if (engine) throw std::runtime_error("engine already attached");
     if (m_eval.empty() || aln_states.empty()) throw std::runtime_error("setAlignment and setModel first");
     check(iqhip_create(&engine, device, num_states, ncat, nptn, leafNum), "iqhip_create");
+    engine_device = device;
     inputs_dirty = model_dirty = aln_dirty = true;
     pushInputs();
     // the reference's arena: leafNum-2 vectors (LM_PER_NODE) or 3*leafNum-6 (phylotree.cpp:867-873)
@@ -2149,6 +2191,22 @@ void PhyloTree::computePatternStateFreq(const double *class_freq, double *ptn_st
     if (!class_freq || !ptn_state_freq) throw std::runtime_error("computePatternStateFreq: null argument");
     computePatternLhCat(WSL_MIXTURE, nullptr);
     check(iqhip_mix_posteriors(engine, class_freq, nullptr, ptn_state_freq), "iqhip_mix_posteriors");
+}
+
+void PhyloTree::classLnl(PhyloNeighbor *dad_branch, PhyloNode *dad, const double *class_weight, const double *class_invar,
+                         double *lnl, int64_t *floored) {
+    if (!engine) throw std::runtime_error("no engine");
+    if (nmixture < 2) throw std::runtime_error("classLnl: the model is no mixture (candidates are the classes of a mixture)");
+    PhyloNeighbor *back = dad_branch->node->findNeighbor(dad);
+    if (!back) throw std::runtime_error("classLnl: not a branch");
+    current_it = dad_branch;
+    current_it_back = back;
+    double df, ddf;
+    theta_computed = false;
+    computeLikelihoodDerv(dad_branch, dad, df, ddf);   // (re)builds theta of dad_branch
+    check(iqhip_class_lnl(engine, branchEnd(dad_branch), branchEnd(back), dad_branch->length, class_weight, class_invar, lnl,
+                          floored),
+          "iqhip_class_lnl");
 }
 
 void PhyloTree::setBootSamples(const float *samples, int nsamples) {

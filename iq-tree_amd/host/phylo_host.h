@@ -89,6 +89,11 @@ public:
     // when names is empty, parsed as integer taxon ids.  A bifurcating top level is unrooted.
     void readTreeString(const std::string &newick, const std::vector<std::string> &names);
     std::string getTreeString() const;
+    // the same tree as src, field by field: node ids, names, the order of every node's neighbours, branch ids and lengths
+    // (no printed string in between).  Drops this tree's vectors as readTreeString does
+    void copyTopology(const PhyloTree &src);
+    // lengths only, looked up by node id; throws when the topologies differ.  The caller invalidates the vectors
+    void copyBranchLengths(const PhyloTree &src);
     int leafNum = 0, nodeNum = 0, branchNum = 0;
     PhyloNode *root = nullptr;  // a leaf, as in the reference (phylotree.cpp:1034)
     std::vector<PhyloNode *> nodes;  // index == id
@@ -142,6 +147,7 @@ public:
     bool device_sweep = true;   // optimizeAllBranches: a whole sweep as one engine submission (iqhip_optimize_sweep)
     long num_derv_calls = 0;  // derivative evaluations (host loop: calls; device loop: reported steps)
     iqhip_engine *engine = nullptr;
+    int engine_device = -1;   // the GPU of attachEngine
     // Pattern-sharded runs (one process per GPU): when set, every host-visible result vector
     // {lnL | df,ddf | sum_scale per op} is left on the device, handed to this hook (which
     // all-reduces it in place over RCCL on the engine's stream) and only then read back.
@@ -363,6 +369,12 @@ public:
     double optimizeMixtureWeights(double *p_invar = nullptr, int *nsteps = nullptr, int *converged = nullptr);
     // the EM alone on the matrix of the last computePatternLhCat(WSL_MIXTURE) (iqhip_mix_weights_em); the tree is unchanged
     void mixWeightsEM(int max_steps, double *weights, double *p_invar, int *nsteps, int *converged, double *trace);
+    // ---- per-class log-likelihoods: K candidate models as the K classes of a mixture (iqhip_class_lnl) -------------------
+    // theta of dad_branch is rebuilt; lnl[nmixture] = the log-likelihood of every class's model alone on this tree.
+    // class_weight[nmixture]: the weight folded into each class's props (1 for candidates); class_invar: nullptr (the
+    // resident ptn_invar for every class) or [nmixture][nptn]; floored: nullptr or [nmixture]
+    void classLnl(PhyloNeighbor *dad_branch, PhyloNode *dad, const double *class_weight, const double *class_invar, double *lnl,
+                  int64_t *floored);
     // PhyloTree::computePatternStateFreq (phylotree.cpp:1162-1196): class_freq [nmixture][nstates] -> ptn_state_freq
     // [nptn][nstates]
     void computePatternStateFreq(const double *class_freq, double *ptn_state_freq);

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 d=iq-tree_amd/lib_alt_$name
 mkdir -p $d
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -Wno-unused-value -Wno-unused-result -Iinclude"
-for f in engine solve plan ptnlh pairdist pars kernels_valu4 kernels_valu4w kernels_mfma kernels_newton kernels_sweep kernels_rell kernels_em kernels_mixem kernels_alrt kernels_topo kernels_dist kernels_bionj kernels_pars kernels_spr comm sharded; do
+for f in engine solve plan ptnlh pairdist pars kernels_valu4 kernels_valu4w kernels_mfma kernels_newton kernels_sweep kernels_rell kernels_em kernels_mixem kernels_classlnl kernels_alrt kernels_topo kernels_dist kernels_bionj kernels_pars kernels_spr comm sharded; do
   case $f in
     kernels_mfma|kernels_valu4|kernels_valu4w) /opt/rocm/bin/hipcc $FLAGS "$@" -c iq-tree_amd/csrc/$f.hip -o $d/$f.o & ;;
     *) cp iq-tree_amd/lib/$f.o $d/$f.o ;;
