@@ -60,6 +60,16 @@
 // the reference's "Optimal log-likelihood:", "Rate parameters:", "Proportion of invariable sites:" and "Gamma shape alpha:"
 // lines and the model string with the estimates, which is also what <prefix>.iqhip records.  MIX{}, +R, +ASC and +FO are
 // refused with this flag; without it a string that leaves values out is refused as before.
+// With -bb N [-beps E] [-seed S] [-z <treefile>] [-wbt] it runs the ultrafast bootstrap's bookkeeping on the candidate trees of
+// ONE search iteration per tree: N resamples of all sites are drawn on the device (iqhip_gen_boot_samples, stream 0xA0 of
+// -seed); the -te tree goes first, then every tree of -z in file order; each is fed itself (after branch optimisation
+// unless -blfix; PhyloTree::saveCurrentTree) and then its whole NNI neighbourhood through one update
+// (PhyloTree::saveNNITrees), the log-likelihood cutoff following iqtree.cpp:1887-1888 between the trees.  It prints
+// "UFBoot: K candidate trees, D distinct bootstrap trees", writes <prefix>.suptree (the -te tree with the supports
+// round(100 count / N) as node labels) and <prefix>.contree (the greedy consensus of the winners) and, with -wbt,
+// <prefix>.ufboot: the winner of every replicate in replicate order, topology only, children by ascending smallest taxon.
+// E is params.ufboot_epsilon (0.5).  There is no tree search: what is fed is what the given trees offer.  With -bb a -z
+// file needs no -zb.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -158,12 +168,51 @@ static std::string mixtureString(const std::string &m, const std::vector<double>
     return out + "}" + m.substr(close);
 }
 
+// the Newick strings of a tree set file, one after the other
+static std::vector<std::string> readTreeSet(const std::string &file) {
+    std::ifstream zin(file.c_str());
+    if (!zin) throw std::runtime_error("cannot open tree set file " + file);
+    std::stringstream zss;
+    zss << zin.rdbuf();
+    std::vector<std::string> newicks;
+    std::string cur;
+    for (char c : zss.str()) {
+        cur += c;
+        if (c == ';') {
+            if (cur.find('(') != std::string::npos) newicks.push_back(cur);
+            cur.clear();
+        }
+    }
+    return newicks;
+}
+
+static void writeText(const std::string &file, const std::string &text) {
+    std::ofstream out(file.c_str());
+    if (!out) throw std::runtime_error("cannot write " + file);
+    out << text;
+}
+
+// a topology string of taxon ids with the ids replaced by the sequence names
+static std::string namedTopology(const std::string &ids, const std::vector<std::string> &names) {
+    std::string out;
+    for (size_t i = 0; i < ids.size();) {
+        if (isdigit((unsigned char)ids[i])) {
+            size_t j = i;
+            while (j < ids.size() && isdigit((unsigned char)ids[j])) j++;
+            out += names.at((size_t)atoi(ids.substr(i, j - i).c_str()));
+            i = j;
+        } else
+            out += ids[i++];
+    }
+    return out;
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
-            "                 [-mixweights] [-optmodel]\n"
+            "                 [-mixweights] [-optmodel] [-bb <n> [-beps <e>] [-z <tree set file>] [-wbt]]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
@@ -179,7 +228,9 @@ int main(int argc, char **argv) {
     int dev = 0, reps = 0, alrt = 0, lbp = 0;
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file;
-    int zb = 0, sprrad = 0;
+    int zb = 0, sprrad = 0, bb = 0;
+    double beps = 0.5;
+    bool wbt = false;
     bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false, optmodel = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -201,6 +252,9 @@ int main(int argc, char **argv) {
         else if (a == "-lbp") lbp = atoi(next().c_str());
         else if (a == "-z") treeset_file = next();
         else if (a == "-zb") zb = atoi(next().c_str());
+        else if (a == "-bb") bb = atoi(next().c_str());
+        else if (a == "-beps") beps = atof(next().c_str());
+        else if (a == "-wbt") wbt = true;
         else if (a == "-zw") zw = true;
         else if (a == "-au") au = true;
         else if (a == "-mldist") mldist_file = next();
@@ -224,8 +278,9 @@ int main(int argc, char **argv) {
     if (bionjtree && mldist_file.empty()) mldist_file = prefix + ".mldist";
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
     if (sprrad > 0 && !parstree && !pars) { usage(); return 2; }
-    if (zb < 0 || (!treeset_file.empty() && zb < 1) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
-    if (alrt > 0 || lbp > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
+    if (bb < 0 || !(beps >= 0.0) || (bb == 0 && wbt)) { usage(); return 2; }
+    if (zb < 0 || (!treeset_file.empty() && zb < 1 && bb == 0) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
+    if (alrt > 0 || lbp > 0 || bb > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
         Alignment aln;
         aln.readFile(aln_file, seq_type);
@@ -546,20 +601,58 @@ int main(int argc, char **argv) {
             std::ofstream out((prefix + ".iqhip").c_str(), std::ios::app);
             out << "support_tree " << labelled << "\n";
         }
-        if (!treeset_file.empty()) {
-            std::ifstream zin(treeset_file.c_str());
-            if (!zin) throw std::runtime_error("cannot open tree set file " + treeset_file);
-            std::stringstream zss;
-            zss << zin.rdbuf();
+        if (bb > 0) {
+            if (mixture || spec.ascertainment) throw std::runtime_error("-bb is not available for mixture models and +ASC");
             std::vector<std::string> newicks;
-            std::string cur;
-            for (char c : zss.str()) {
-                cur += c;
-                if (c == ';') {
-                    if (cur.find('(') != std::string::npos) newicks.push_back(cur);
-                    cur.clear();
+            if (!treeset_file.empty()) newicks = readTreeSet(treeset_file);
+            auto t0 = std::chrono::steady_clock::now();
+            tree.genBootSamples(bb, nsite, seed, 0xA0u);
+            tree.initUFBoot(bb, seed);
+            tree.ufboot_epsilon = beps;
+            const std::string te_tree = tree.getTreeString();
+            for (size_t k = 0; k <= newicks.size(); k++) {
+                double cur = lnl;
+                if (k > 0) {
+                    tree.readTreeString(newicks[k - 1], aln.seq_names);
+                    if (tree.leafNum != aln.getNSeq()) throw std::runtime_error("-z: a tree with another number of taxa");
+                    tree.initializeAllPartialLh();
+                    tree.clearAllPartialLH();
+                    cur = tree.computeLikelihood();
+                    if (!blfix) {
+                        tree.optimizeAllBranches();
+                        tree.clearAllPartialLH();
+                        cur = tree.computeLikelihood();
+                    }
+                } else {
+                    tree.clearAllPartialLH();
+                    cur = tree.computeLikelihood();
                 }
+                tree.ufbootNextIteration();
+                tree.saveCurrentTree(cur);
+                tree.saveNNITrees();
             }
+            if (!newicks.empty()) {   // the supports go onto the -te tree
+                tree.readTreeString(te_tree, aln.seq_names);
+                tree.initializeAllPartialLh();
+            }
+            PhyloTree::UFBootSummary sum;
+            tree.summarizeBootstrap(sum);
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("UFBoot: %lld candidate trees, %d distinct bootstrap trees\n", (long long)tree.ufboot_next_id, sum.distinct_trees);
+            printf("UFBoot bookkeeping (%d replicates, %d trees and their NNI neighbourhoods): %.4f s\n", bb, (int)newicks.size() + 1, sec);
+            printf("Log-likelihood cutoff on original alignment: %.6f\n", tree.ufboot_min_orig_logl);
+            writeText(prefix + ".suptree", sum.support_tree + "\n");
+            writeText(prefix + ".contree", sum.consensus_tree + "\n");
+            printf("Tree with UFBoot supports written to %s.suptree, consensus tree to %s.contree\n", prefix.c_str(), prefix.c_str());
+            if (wbt) {
+                std::string all;
+                for (const std::string &t : sum.boot_trees) all += namedTopology(t, aln.seq_names) + "\n";
+                writeText(prefix + ".ufboot", all);
+                printf("UFBoot trees printed to %s.ufboot\n", prefix.c_str());
+            }
+        }
+        if (!treeset_file.empty() && zb > 0) {
+            const std::vector<std::string> newicks = readTreeSet(treeset_file);
             std::vector<double> scales;
             if (au) scales = {0.5, 0.6, 0.7, 0.8, 0.9, 1.0, 1.1, 1.2, 1.3, 1.4};
             std::vector<PhyloTree::TreeTest> res;

@@ -534,6 +534,57 @@ int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int
 int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales, int nsamples,
                         uint64_t seed, double *bp /* nscales*ntrees, bp[k*ntrees+tid] */);
 
+/* ---- Ultrafast bootstrap: the online RELL bookkeeping per candidate tree (IQTree::saveCurrentTree, iqtree.cpp:2676-2786;
+ * option -bb) -----------------------------------------------------------------------------------------------------------
+ * The reference calls saveCurrentTree for the current tree of every search iteration (iqtree.cpp:2135-2136) and for every
+ * NNI candidate getBestNNIForBran evaluates (phylotree.cpp:3022-3023): the tree's RELL score in every replicate is compared
+ * with the best score that replicate has seen, and the replicate's tree is replaced under an epsilon / random-tie rule.
+ * Here the per-replicate state lives on the device next to the sample matrix and the store rows; a call applies a whole
+ * list of candidate trees and only a few words leave the device.
+ * iqhip_ufboot_init: engine-owned state for the first nsamples rows of the sample matrix, started as iqtree.cpp:308-312:
+ *   boot_logl = boot_orig_logl = -DBL_MAX, boot_counts = 0, boot_tree = -1.  A second init resets the state.  Replacing
+ *   the sample matrix (iqhip_set_boot_samples, iqhip_gen_boot_samples, iqhip_multiscale_bp) invalidates it: update and
+ *   fetch return IQHIP_ERR_INVALID until the next init.
+ * iqhip_ufboot_update: one entry = one saveCurrentTree(cur_logl): row = the store row with the tree's per-pattern lnL,
+ *   logl = cur_logl, rand = the ONE random_double() the reference draws per call and shares over all replicates (in
+ *   [0, 1]), tree_id >= 0 = the caller's tag for the tree string.  Entries with logl_cutoff != 0 && logl < logl_cutoff - 1.0
+ *   are dropped on the host (:2678).  The others are applied IN LIST ORDER; for every replicate s < nsamples, with
+ *   rell = R[row][s] of iqhip_ptnlh_rell (:2738-2750):
+ *       better = rell > boot_logl[s] + epsilon
+ *       if (!better && rell > boot_logl[s] - epsilon) better = (rand <= 1.0 / (boot_counts[s] + 1))
+ *       if (better) {
+ *           if (rell <= boot_logl[s] + epsilon) boot_counts[s]++; else boot_counts[s] = 1;
+ *           boot_logl[s] = max(boot_logl[s], rell); boot_orig_logl[s] = logl; boot_tree[s] = tree_id;
+ *       }
+ *   counts (or NULL) = {entries applied, entries dropped by the cutoff, replicate slots replaced}; *min_orig_logl (or NULL)
+ *   = the minimum of boot_orig_logl over the replicates that hold a tree, DBL_MAX when none does -- the reference's next
+ *   logl_cutoff (iqtree.cpp:1888).  Both come back in one small read; the sums never leave the device.
+ *   The list is processed in chunks of consecutive entries so that the product's staging stays within 256 MB
+ *   (IQHIP_UFBOOT_CHUNK, read per call, overrides the entries per chunk).  A sum depends on its row, its sample, the
+ *   padded pattern count, nsamples and the CU count only, so the state after a call is bit-identical for every chunk size
+ *   and to the rule applied to iqhip_ptnlh_rell(rows, nsamples) at the same nsamples.
+ * iqhip_ufboot_fetch: the state, nsamples entries each (any pointer may be NULL).
+ * iqhip_debug_ufboot_timing: *launches = the kernels the last update enqueued; with iqhip_timing_enable, ms[0] / ms[1] =
+ *   the device time (HIP events, milliseconds) of its products / of its update kernels.
+ * DEVIATION from the reference: it is built with BOOT_VAL_FLOAT -- the pattern lnL is cast to float and the dot product
+ *   runs in float.  Here the rows stay fp64 and the product is fp64, as for -alrt and the topology tests; epsilon
+ *   (params.ufboot_epsilon, 0.5 by default) is many orders of magnitude above the difference.  The tie draws are the
+ *   caller's; they do not follow the reference's RNG stream.
+ * IQHIP_ERR_UNSUPPORTED: sharded engines and communicator ranks.  IQHIP_ERR_INVALID: planning-only engines; init with
+ *   nsamples < 1 or above the number of uploaded samples; a null `trees`, ntrees < 1, a row outside the store, tree_id < 0,
+ *   rand outside [0, 1] or NaN, a non-finite logl, epsilon < 0 or NaN, any call before init.  Everything is validated on
+ *   the host before the first launch. */
+typedef struct iqhip_ufboot_tree {
+    int32_t row, _pad;
+    int64_t tree_id;
+    double logl, rand;
+} iqhip_ufboot_tree; /* 32 bytes */
+int iqhip_ufboot_init(iqhip_engine *e, int nsamples);
+int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *trees, int ntrees, double epsilon, double logl_cutoff,
+                        int64_t *counts /* 3 or NULL */, double *min_orig_logl /* or NULL */);
+int iqhip_ufboot_fetch(iqhip_engine *e, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts, int64_t *boot_tree);
+int iqhip_debug_ufboot_timing(iqhip_engine *e, double *ms /* 2: product, update */, int64_t *launches);
+
 /* ---- Pairwise maximum-likelihood distances (PhyloTree::computeDist, phylotree.cpp:2432-2541; per pair AlignmentPairwise,
  * alignmentpairwise.cpp:29-312, and Optimization::minimizeNewton) -- the likelihood computation the reference runs before
  * a tree exists; the matrix feeds BIONJ and is written as .mldist.  Everything it needs is resident in any engine: the state

@@ -47,6 +47,7 @@ IQHIP_SYMBOLS = [
     "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
     "iqhip_pars_spr_scan", "iqhip_debug_pars_spr_check", "iqhip_debug_pars_spr_timing",
     "iqhip_bionj", "iqhip_debug_bionj_timing",
+    "iqhip_ufboot_init", "iqhip_ufboot_update", "iqhip_ufboot_fetch", "iqhip_debug_ufboot_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -86,6 +87,11 @@ class TreeTest(C.Structure):
     _fields_ = [("rell_bp", C.c_double), ("kh_pvalue", C.c_double), ("sh_pvalue", C.c_double), ("wkh_pvalue", C.c_double),
                 ("wsh_pvalue", C.c_double), ("elw_value", C.c_double), ("rell_confident", C.c_int32),
                 ("elw_confident", C.c_int32)]
+
+
+class UFBootTree(C.Structure):
+    """struct iqhip_ufboot_tree (include/iqhip.h; 32 bytes)."""
+    _fields_ = [("row", C.c_int32), ("_pad", C.c_int32), ("tree_id", C.c_int64), ("logl", C.c_double), ("rand", C.c_double)]
 
 
 class BranchTask(C.Structure):
@@ -249,6 +255,10 @@ def libiqhip():
     lib.iqhip_debug_pars_spr_timing.argtypes = [vp, dp, i64p, C.c_int]
     lib.iqhip_bionj.argtypes = [vp, C.c_int, dp, dp, vp, i32p, dp]
     lib.iqhip_debug_bionj_timing.argtypes = [vp, dp, i64p]
+    lib.iqhip_ufboot_init.argtypes = [vp, C.c_int]
+    lib.iqhip_ufboot_update.argtypes = [vp, C.POINTER(UFBootTree), C.c_int, C.c_double, C.c_double, i64p, dp]
+    lib.iqhip_ufboot_fetch.argtypes = [vp, dp, dp, i32p, i64p]
+    lib.iqhip_debug_ufboot_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
 
@@ -372,6 +382,18 @@ def libiqhost():
     lib.iqhost_class_lnl.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, C.POINTER(C.c_int64)]
     lib.iqhost_class_lnl_timing.argtypes = [vp, dp]
     lib.iqhost_compute_rell.argtypes = [vp, dp, C.c_int]
+    i64p, cpp = C.POINTER(C.c_int64), C.POINTER(C.c_char_p)
+    lib.iqhost_ufboot_init.argtypes = [vp, C.c_int, C.c_uint64]
+    lib.iqhost_ufboot_params.argtypes = [vp, C.c_double, C.c_double]
+    lib.iqhost_ufboot_next_iteration.argtypes = [vp]
+    lib.iqhost_ufboot_info.argtypes = [vp, i64p, dp]
+    lib.iqhost_save_current_tree.argtypes = [vp, C.c_double, i64p, dp]
+    lib.iqhost_save_nni_trees.argtypes = [vp, i64p, dp]
+    lib.iqhost_sorted_taxon_id_string.argtypes = [vp, C.c_char_p, C.c_int, ipp]
+    lib.iqhost_summarize_bootstrap.argtypes = [vp, ipp, ipp, C.c_int, ipp, ipp, C.c_char_p, C.c_int, ipp]
+    lib.iqhost_ufboot_newick_splits.argtypes = [C.c_char_p, C.c_int, cpp, C.POINTER(C.c_uint64), C.c_int, ipp]
+    lib.iqhost_ufboot_split_supports.argtypes = [cpp, C.c_int, i64p, C.c_int, cpp, C.c_char_p, ipp, C.c_int, ipp]
+    lib.iqhost_ufboot_consensus.argtypes = [cpp, C.c_int, i64p, C.c_int, cpp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_last_plan.argtypes = [vp, C.POINTER(C.c_int), dp, C.POINTER(C.c_uint64), C.c_int]
     lib.iqhost_num_partial_lh_computations.argtypes = [vp]
     lib.iqhost_num_partial_lh_computations.restype = C.c_long
@@ -463,6 +485,81 @@ def bionj_newick(steps, last, last_len, names):
     if lib.iqhost_bionj_newick(*args, buf, need.value, C.byref(need)) != 0:
         raise HostError(lib.iqhost_last_error().decode())
     return buf.value.decode()
+
+
+def _hchk(rc):
+    if rc != 0:
+        raise HostError(libiqhost().iqhost_last_error().decode())
+
+
+def _c_strings(items):
+    return None if items is None else (C.c_char_p * max(len(items), 1))(*[x.encode() for x in items])
+
+
+def _c_weights(weights, n):
+    if weights is None:
+        return None, None
+    w = np.ascontiguousarray(weights, dtype=np.int64)
+    assert w.shape == (n,)
+    return w, w.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def newick_splits(newick, ntaxa, names=None):
+    """The non-trivial splits of a Newick string (iq-tree_amd/host/ufboot_splits.h) in the post-order of the string, each a
+    frozenset of taxon ids: the side WITHOUT taxon 0.  Leaf labels are taxon ids, or are looked up in names."""
+    lib = libiqhost()
+    words_per = (int(ntaxa) + 63) // 64
+    cap = max(int(ntaxa), 1)
+    words = np.zeros((cap, words_per), dtype=np.uint64)
+    n = C.c_int()
+    _hchk(lib.iqhost_ufboot_newick_splits(newick.encode(), int(ntaxa), _c_strings(names),
+                                          words.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(n)))
+    assert n.value <= cap
+    return [frozenset(t for t in range(int(ntaxa)) if (int(words[k, t >> 6]) >> (t & 63)) & 1) for k in range(n.value)]
+
+
+def split_supports(trees, query, ntaxa, weights=None, names=None):
+    """createBootstrapSupport's numbers: for every split of `query` (newick_splits order) round(100 count / sum of the
+    weights) over `trees` (weights: one integer per tree, default 1 each); 0 for a split no tree has."""
+    lib = libiqhost()
+    trees = list(trees)
+    cap = max(int(ntaxa), 1)
+    out = np.zeros(cap, dtype=np.int32)
+    n = C.c_int()
+    w, wp = _c_weights(weights, len(trees))
+    _hchk(lib.iqhost_ufboot_split_supports(_c_strings(trees), len(trees), wp, int(ntaxa), _c_strings(names), query.encode(),
+                                           out.ctypes.data_as(C.POINTER(C.c_int)), cap, C.byref(n)))
+    return [int(x) for x in out[:n.value]]
+
+
+def consensus_tree(trees, ntaxa, weights=None, names=None):
+    """The greedy consensus (findMaxCompatibleSplits) of `trees`: splits by descending weight, ties to the split that
+    appeared first, the supports as labels; rooted at taxon 0's node, children by ascending smallest taxon."""
+    lib = libiqhost()
+    trees = list(trees)
+    need = C.c_int()
+    w, wp = _c_weights(weights, len(trees))
+    args = (_c_strings(trees), len(trees), wp, int(ntaxa), _c_strings(names))
+    _hchk(lib.iqhost_ufboot_consensus(*args, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    _hchk(lib.iqhost_ufboot_consensus(*args, buf, len(buf), C.byref(need)))
+    return buf.value.decode()
+
+
+def ufboot_rand(seed, tree_id):
+    """The tie draw of tree `tree_id`: (z >> 11) 2^-53 with z of the generator of include/iqhip.h for (seed, stream 0xBB,
+    rho = tree_id, j = 0)."""
+    m64, g = (1 << 64) - 1, 0x9E3779B97F4A7C15
+
+    def mix(z):
+        z ^= z >> 30
+        z = z * 0xBF58476D1CE4E5B9 & m64
+        z ^= z >> 27
+        z = z * 0x94D049BB133111EB & m64
+        return z ^ (z >> 31)
+
+    z = mix((mix((mix((int(seed) + g * (0xBB + 1)) & m64) + g * (int(tree_id) + 1)) & m64) + g) & m64)
+    return (z >> 11) * 2.0 ** -53
 
 
 def _pars_ops(ops):
@@ -1537,6 +1634,101 @@ class PhyloTree:
         ms = C.c_double()
         self._chk(self.lib.iqhost_class_lnl_timing(self.h, C.byref(ms)))
         return ms.value
+
+    # ---- ultrafast bootstrap bookkeeping (include/iqhip.h "ultrafast bootstrap")
+    def ufboot_init(self, nsamples, seed=0):
+        """iqhip_ufboot_init on the first nsamples rows of the sample matrix; seed: the tie draws of save_current_tree /
+        save_nni_trees"""
+        self._chk(self.lib.iqhost_ufboot_init(self.h, int(nsamples), int(seed)))
+        self._ufboot = int(nsamples)
+
+    def ufboot_update(self, rows, tree_ids, logl, rand, epsilon=0.5, logl_cutoff=0.0):
+        """iqhip_ufboot_update: one entry per candidate tree, applied in list order ->
+        (counts = [applied, dropped by the cutoff, replicate slots replaced], min_orig_logl)"""
+        r = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+        ids = np.ascontiguousarray(tree_ids, dtype=np.int64).ravel()
+        l = np.ascontiguousarray(logl, dtype=np.float64).ravel()
+        u = np.ascontiguousarray(rand, dtype=np.float64).ravel()
+        assert r.size == ids.size == l.size == u.size
+        ent = (UFBootTree * max(r.size, 1))()
+        for k in range(r.size):
+            ent[k] = UFBootTree(int(r[k]), 0, int(ids[k]), float(l[k]), float(u[k]))
+        counts = np.zeros(3, dtype=np.int64)
+        mn = C.c_double()
+        _echk(libiqhip().iqhip_ufboot_update(self.engine, ent, r.size, float(epsilon), float(logl_cutoff),
+                                             counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+        return counts, mn.value
+
+    def ufboot_state(self):
+        """iqhip_ufboot_fetch -> dict(boot_logl, boot_orig_logl, boot_counts, boot_tree), nsamples entries each"""
+        n = self._ufboot
+        st = dict(boot_logl=np.zeros(n), boot_orig_logl=np.zeros(n), boot_counts=np.zeros(n, dtype=np.int32),
+                  boot_tree=np.zeros(n, dtype=np.int64))
+        _echk(libiqhip().iqhip_ufboot_fetch(self.engine, _dptr(st["boot_logl"]), _dptr(st["boot_orig_logl"]),
+                                            st["boot_counts"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                            st["boot_tree"].ctypes.data_as(C.POINTER(C.c_int64))))
+        return st
+
+    def ufboot_timing(self):
+        """(device ms of the products, of the update kernels, kernels enqueued) of the last ufboot_update"""
+        ms = np.zeros(2)
+        n = C.c_int64()
+        _echk(libiqhip().iqhip_debug_ufboot_timing(self.engine, _dptr(ms), C.byref(n)))
+        return float(ms[0]), float(ms[1]), int(n.value)
+
+    def ufboot_params(self, epsilon=0.5, logl_cutoff=0.0):
+        """params.ufboot_epsilon and logl_cutoff of the following save_current_tree / save_nni_trees calls"""
+        self._chk(self.lib.iqhost_ufboot_params(self.h, float(epsilon), float(logl_cutoff)))
+
+    def ufboot_next_iteration(self):
+        """the start of a search iteration (iqtree.cpp:1887-1888): logl_cutoff = min boot_orig_logl"""
+        self._chk(self.lib.iqhost_ufboot_next_iteration(self.h))
+
+    def ufboot_info(self):
+        info = np.zeros(2, dtype=np.int64)
+        vals = np.zeros(2)
+        self._chk(self.lib.iqhost_ufboot_info(self.h, info.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(vals)))
+        return dict(trees_fed=int(info[0]), trees_kept=int(info[1]), logl_cutoff=float(vals[0]), min_orig_logl=float(vals[1]))
+
+    def save_current_tree(self, logl):
+        """IQTree::saveCurrentTree(logl) for the tree of the last compute_likelihood -> (counts, min_orig_logl)"""
+        counts = np.zeros(3, dtype=np.int64)
+        mn = C.c_double()
+        self._chk(self.lib.iqhost_save_current_tree(self.h, float(logl), counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+        return counts, mn.value
+
+    def save_nni_trees(self):
+        """all 2(n-3) NNI neighbours (evaluate_nnis5_batch with store rows) through ONE update -> (counts, min_orig_logl)"""
+        counts = np.zeros(3, dtype=np.int64)
+        mn = C.c_double()
+        self._chk(self.lib.iqhost_save_nni_trees(self.h, counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+        return counts, mn.value
+
+    def sorted_taxon_id_string(self):
+        """the topology as the reference prints it with WT_TAXON_ID + WT_SORT_TAXA"""
+        need = C.c_int()
+        self._chk(self.lib.iqhost_sorted_taxon_id_string(self.h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._chk(self.lib.iqhost_sorted_taxon_id_string(self.h, buf, len(buf), C.byref(need)))
+        return buf.value.decode()
+
+    def summarize_bootstrap(self):
+        """summarizeBootstrap -> dict(support_tree, supports = [(node1, node2, percent)], consensus_tree, boot_trees =
+        the winner of every replicate (taxon ids, taxa sorted), distinct_trees)"""
+        cap = self.num_nodes
+        ids = np.zeros(2 * cap, dtype=np.int32)
+        sup = np.zeros(cap, dtype=np.int32)
+        n, distinct, need = C.c_int(), C.c_int(), C.c_int()
+        ip = C.POINTER(C.c_int)
+        self._chk(self.lib.iqhost_summarize_bootstrap(self.h, ids.ctypes.data_as(ip), sup.ctypes.data_as(ip), cap, C.byref(n),
+                                                      C.byref(distinct), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._chk(self.lib.iqhost_summarize_bootstrap(self.h, ids.ctypes.data_as(ip), sup.ctypes.data_as(ip), cap, C.byref(n),
+                                                      C.byref(distinct), buf, len(buf), C.byref(need)))
+        lines = buf.value.decode().split("\n")
+        return dict(support_tree=lines[0], consensus_tree=lines[1], boot_trees=lines[2:2 + self._ufboot],
+                    supports=[(int(ids[2 * q]), int(ids[2 * q + 1]), int(sup[q])) for q in range(n.value)],
+                    distinct_trees=distinct.value)
 
     def set_boot_samples(self, samples):
         """UFBoot boot_samples: float32 [nsamples, nptn] pattern weights, uploaded once."""

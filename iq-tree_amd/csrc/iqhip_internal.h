@@ -473,6 +473,19 @@ struct iqhip_engine {
         iqhip::DevBuf<double> dbl;      // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
         iqhip::DevBuf<int32_t> ints;    // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
     } tt;
+    // UFBoot bookkeeping (iqhip_ufboot_*; ptnlh.hip, kernels_ufboot.hip): per replicate boot_logl, boot_orig_logl [nsamples
+    // each, in `dbl`], boot_tree [nsamples], boot_counts [nsamples]; the entries of a call with `row` rewritten to the row
+    // of the chunk's sums; res = {replaced slots (64-bit integer), wgmin [workgroups]}.  nsamples == 0: no state
+    // (before iqhip_ufboot_init, and after the sample matrix was replaced)
+    struct {
+        iqhip::DevBuf<double> dbl, res;
+        iqhip::DevBuf<int64_t> tree;
+        iqhip::DevBuf<int32_t> counts;
+        iqhip::DevBuf<iqhip_ufboot_tree> entries;
+        int nsamples = 0;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_ufboot_timing: the products, the update kernels (while timing is enabled)
+        int64_t launches = 0;        // kernels the last iqhip_ufboot_update enqueued
+    } ufb;
     // EM for +R free-rate models and empirical-Bayes site rates (ptnlh.hip, kernels_em.hip): what the last E-step left -- the
     // posterior matrix W [ncat][nptn_pad] (category-major, padding patterns 0), per pattern its posterior mean rate and
     // best category -- and the scratch of the sums (workgroup rows, folded values).  valid: an E-step has run for an
@@ -1101,6 +1114,14 @@ hipError_t launch_topo_diff_variance(iqhip_engine *e, const int32_t *d_rows, int
 hipError_t launch_topo_tests(iqhip_engine *e, const TopoTestArgs &a);
 hipError_t launch_topo_tree(iqhip_engine *e, const TopoTestArgs &a);
 hipError_t launch_topo_argmax(iqhip_engine *e, const double *sums, const int32_t *d_idx, int T, int S, uint32_t *counts);
+
+// kernels_ufboot.hip: saveCurrentTree's per-replicate rule on the sums of launch_alrt_product [M][nsamples].  d_entries: n
+// entries in list order whose `row` is the row of `sums`; *replaced += the slots replaced (one integer atomic per
+// workgroup), wgmin[ufboot_workgroups(nsamples)] = per workgroup the minimum of boot_orig_logl over the slots holding a tree
+int ufboot_workgroups(int nsamples);
+hipError_t launch_ufboot_update(iqhip_engine *e, const double *sums, int nsamples, const iqhip_ufboot_tree *d_entries, int n,
+                                double epsilon, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts,
+                                int64_t *boot_tree, unsigned long long *replaced, double *wgmin);
 
 // kernels_dist.hip: pairwise ML distances.  launch_pair_counts: the tiles' pairs -> d_counts[slot][n * n]; launch_pair_solve:
 // slot s of the chunk is pair first_pair + s of the call: start init[pair] (0 or no array: the pair's JC distance), result

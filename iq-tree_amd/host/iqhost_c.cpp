@@ -14,6 +14,7 @@
 #include "brent_host.h"
 #include "model_opt_host.h"
 #include "phylo_host.h"
+#include "ufboot_splits.h"
 
 using namespace iqhost;
 
@@ -808,5 +809,125 @@ int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) 
 }
 long iqhost_num_partial_lh_computations(void *h) { return ((PhyloTree *)h)->num_partial_lh_computations; }
 long iqhost_num_submissions(void *h) { return ((PhyloTree *)h)->num_submissions; }
+
+
+// ---- ultrafast bootstrap bookkeeping (PhyloTree::initUFBoot ...) and the pure split functions of ufboot_splits.h
+static void ufboot_report(PhyloTree *t, int64_t *counts, double *min_orig_logl) {
+    if (counts) memcpy(counts, t->ufboot_counts, sizeof t->ufboot_counts);
+    if (min_orig_logl) *min_orig_logl = t->ufboot_min_orig_logl;
+}
+int iqhost_ufboot_init(void *h, int nsamples, uint64_t seed) { IQHOST_TRY(((PhyloTree *)h)->initUFBoot(nsamples, seed)); }
+int iqhost_ufboot_params(void *h, double epsilon, double logl_cutoff) {
+    IQHOST_TRY({
+        if (!(epsilon >= 0.0)) throw std::runtime_error("ufboot epsilon must be >= 0");
+        ((PhyloTree *)h)->ufboot_epsilon = epsilon;
+        ((PhyloTree *)h)->ufboot_logl_cutoff = logl_cutoff;
+    });
+}
+int iqhost_ufboot_next_iteration(void *h) { IQHOST_TRY(((PhyloTree *)h)->ufbootNextIteration()); }
+// info: {trees fed so far, Newick strings kept}; vals: {logl_cutoff, min_orig_logl}
+int iqhost_ufboot_info(void *h, int64_t *info, double *vals) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        info[0] = t->ufboot_next_id;
+        info[1] = (int64_t)t->ufboot_trees.size();
+        vals[0] = t->ufboot_logl_cutoff;
+        vals[1] = t->ufboot_min_orig_logl;
+    });
+}
+int iqhost_save_current_tree(void *h, double logl, int64_t *counts, double *min_orig_logl) {
+    IQHOST_TRY({
+        ((PhyloTree *)h)->saveCurrentTree(logl);
+        ufboot_report((PhyloTree *)h, counts, min_orig_logl);
+    });
+}
+int iqhost_save_nni_trees(void *h, int64_t *counts, double *min_orig_logl) {
+    IQHOST_TRY({
+        ((PhyloTree *)h)->saveNNITrees();
+        ufboot_report((PhyloTree *)h, counts, min_orig_logl);
+    });
+}
+int iqhost_sorted_taxon_id_string(void *h, char *out, int cap, int *need) {
+    IQHOST_TRY({
+        const std::string s = ((PhyloTree *)h)->sortedTaxonIdString();
+        if (need) *need = (int)s.size() + 1;
+        if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+// ids: node1, node2 per internal branch; text: support tree, consensus tree and the nsamples winners, one per line
+int iqhost_summarize_bootstrap(void *h, int *ids, int *support, int cap, int *nbranch, int *distinct, char *text, int text_cap,
+                               int *need) {
+    IQHOST_TRY({
+        PhyloTree::UFBootSummary sum;
+        ((PhyloTree *)h)->summarizeBootstrap(sum);
+        const int n = (int)sum.support.size();
+        if (nbranch) *nbranch = n;
+        if (distinct) *distinct = sum.distinct_trees;
+        if (n > cap) throw std::runtime_error("summarizeBootstrap: output too small");
+        for (int q = 0; q < n; q++) {
+            ids[2 * q] = sum.node1[q];
+            ids[2 * q + 1] = sum.node2[q];
+            support[q] = sum.support[q];
+        }
+        std::string s = sum.support_tree + "\n" + sum.consensus_tree + "\n";
+        for (const std::string &t : sum.boot_trees) s += t + "\n";
+        if (need) *need = (int)s.size() + 1;
+        if (text && (int)s.size() + 1 <= text_cap) memcpy(text, s.c_str(), s.size() + 1);
+    });
+}
+static std::vector<std::string> ufboot_names(const char **names, int ntaxa) {
+    std::vector<std::string> nm;
+    if (names)
+        for (int i = 0; i < ntaxa; i++) nm.push_back(names[i]);
+    return nm;
+}
+static void ufboot_count_trees(ufboot::SplitCounts &sc, const char **trees, int ntrees, const int64_t *weights,
+                               const std::vector<std::string> &nm) {
+    if (ntrees < 0 || (ntrees > 0 && !trees)) throw std::runtime_error("bad tree list");
+    std::vector<ufboot::Split> splits;
+    for (int k = 0; k < ntrees; k++) {
+        if (weights && weights[k] < 0) throw std::runtime_error("a tree weight must be >= 0");
+        ufboot::newickSplits(trees[k], sc.ntaxa, splits, nm);
+        sc.addTree(splits, weights ? weights[k] : 1);
+    }
+}
+// words: cap * ((ntaxa + 63) / 64) uint64; names: NULL (integer taxon ids) or ntaxa labels
+int iqhost_ufboot_newick_splits(const char *newick, int ntaxa, const char **names, uint64_t *words, int cap, int *nsplits) {
+    IQHOST_TRY({
+        if (!newick || !nsplits) throw std::runtime_error("newickSplits: null argument");
+        std::vector<ufboot::Split> splits;
+        ufboot::newickSplits(newick, ntaxa, splits, ufboot_names(names, ntaxa));
+        *nsplits = (int)splits.size();
+        const size_t W = ufboot::splitWords(ntaxa);
+        if (words && (int)splits.size() <= cap)
+            for (size_t k = 0; k < splits.size(); k++) memcpy(words + k * W, splits[k].data(), sizeof(uint64_t) * W);
+    });
+}
+// the supports round(100 count / sum of weights) of the splits of `query` (iqhost_ufboot_newick_splits order) among `trees`
+int iqhost_ufboot_split_supports(const char **trees, int ntrees, const int64_t *weights, int ntaxa, const char **names,
+                                 const char *query, int *support, int cap, int *nsplits) {
+    IQHOST_TRY({
+        if (!query || !nsplits) throw std::runtime_error("splitSupports: null argument");
+        const std::vector<std::string> nm = ufboot_names(names, ntaxa);
+        ufboot::SplitCounts sc(ntaxa);
+        ufboot_count_trees(sc, trees, ntrees, weights, nm);
+        std::vector<ufboot::Split> splits;
+        ufboot::newickSplits(query, ntaxa, splits, nm);
+        *nsplits = (int)splits.size();
+        if (support && (int)splits.size() <= cap)
+            for (size_t k = 0; k < splits.size(); k++) support[k] = ufboot::splitSupport(sc, splits[k], sc.total);
+    });
+}
+int iqhost_ufboot_consensus(const char **trees, int ntrees, const int64_t *weights, int ntaxa, const char **names, char *out,
+                            int cap, int *need) {
+    IQHOST_TRY({
+        const std::vector<std::string> nm = ufboot_names(names, ntaxa);
+        ufboot::SplitCounts sc(ntaxa);
+        ufboot_count_trees(sc, trees, ntrees, weights, nm);
+        const std::string s = ufboot::consensusTree(sc, nm);
+        if (need) *need = (int)s.size() + 1;
+        if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/iqhip.h"
@@ -386,6 +387,39 @@ public:
     void genBootSamples(int nsamples, int64_t ndraws, uint64_t seed, uint32_t stream, int64_t first_replicate = 0);
     void computeRELL(std::vector<double> &rell);
     int num_boot_samples = 0;
+
+    // ---- ultrafast bootstrap bookkeeping (IQTree::saveCurrentTree / saveNNITrees / summarizeBootstrap, iqtree.cpp:2676-2801,
+    //      2803-2880) on iqhip_ufboot_update.  The per-replicate state lives in the engine; the mirror keeps tree id -> Newick
+    //      (taxon ids, taxa sorted: WT_TAXON_ID + WT_SORT_TAXA) for the ids some replicate still refers to.  Tree ids are
+    //      sequential from 0.  A tree's rand is (z >> 11) 2^-53 with z of the generator of include/iqhip.h for
+    //      (seed, stream 0xBB, rho = tree id, j = 0).  Store rows 0 .. 2 (leafNum - 3) are scratch: row 0 the current tree,
+    //      row 1 + k NNI candidate k.
+    void initUFBoot(int nsamples, uint64_t seed);   // on the first nsamples rows of the sample matrix (setBootSamples / genBootSamples)
+    // one saveCurrentTree(cur_logl) for the tree of the last computeLikelihood(): its row, then one update
+    void saveCurrentTree(double logl);
+    // evaluateNNIs5Batch with store rows, then ONE update over all 2 (leafNum - 3) candidates in move order, logl = newloglh;
+    // a candidate's string is made from (current tree, move) only when a replicate took it.  Needs LM_ALL_BRANCH
+    void saveNNITrees();
+    // iqtree.cpp:1887-1888, the start of a search iteration: logl_cutoff = the minimum of boot_orig_logl
+    void ufbootNextIteration();
+    static double ufbootRand(uint64_t seed, int64_t tree_id);
+    // WT_TAXON_ID + WT_SORT_TAXA of the current tree, or of its NNI neighbour `mv`
+    std::string sortedTaxonIdString(const NNIMove *mv = nullptr) const;
+    struct UFBootSummary {
+        std::vector<int> node1, node2, support;   // per internal branch (internalBranches order): round(100 count / nsamples)
+        std::string support_tree;                  // the current tree with the supports as labels (supportTreeString's layout)
+        std::string consensus_tree;                // greedy consensus of the winners (ufboot_splits.h), supports as labels
+        std::vector<std::string> boot_trees;       // the winner of every replicate, in replicate order
+        int distinct_trees = 0;
+    };
+    void summarizeBootstrap(UFBootSummary &out);
+    int ufboot_nsamples = 0;
+    uint64_t ufboot_seed = 0;
+    int64_t ufboot_next_id = 0;          // = candidate trees fed so far
+    double ufboot_epsilon = 0.5;         // params.ufboot_epsilon
+    double ufboot_logl_cutoff = 0.0, ufboot_min_orig_logl = 0.0;
+    int64_t ufboot_counts[3] = {0, 0, 0};   // of the last update (include/iqhip.h)
+    std::vector<std::pair<int64_t, std::string>> ufboot_trees;   // id (ascending) -> Newick of the ids still referred to
 
     // ---- host views ----------------------------------------------------------------------
     void fetchScaleNum(PhyloNeighbor *nei, UBYTE *out);
