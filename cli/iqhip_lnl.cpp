@@ -70,6 +70,14 @@
 // <prefix>.ufboot: the winner of every replicate in replicate order, topology only, children by ascending smallest taxon.
 // E is params.ufboot_epsilon (0.5).  There is no tree search: what is fed is what the given trees offer.  With -bb a -z
 // file needs no -zb.
+// With -q <partition file> (edge-linked, all partition rates 1) or -spp <partition file> (edge-linked, proportional: the
+// rates start at 1 and are estimated) instead of -m it evaluates an edge-linked partition model (PhyloSuperTree,
+// supertree_host.h): the file is RAxML-style, `MODEL, name = 1-100, 250-400, 401-500\3`, MODEL a string in the -m syntax
+// above (JC2 / GTR2 name binary columns); every partition keeps every taxon.  PartitionModelPlen::optimizeParameters runs
+// with the substitution parameters as given (-blfix: fixed branch lengths too).  It prints "Partition-specific rates:  r1
+// r2 ..." (-spp only), one line "Partition <name>: <nsite> sites, <nptn> patterns, lnL <value>" per partition and "Optimal
+// log-likelihood: <sum>", and writes <prefix>.treefile with the super tree's lengths.  -q / -spp exclude -m, -alrt, -z, -bb,
+// -mldist, -pars*, -bionjtree, -emrates, -mixweights and -optmodel.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -88,6 +96,7 @@
 #include "../iq-tree_amd/host/model_host.h"
 #include "../iq-tree_amd/host/model_opt_host.h"
 #include "../iq-tree_amd/host/phylo_host.h"
+#include "../iq-tree_amd/host/supertree_host.h"
 
 using namespace iqhost;
 
@@ -207,6 +216,46 @@ static std::string namedTopology(const std::string &ids, const std::vector<std::
     return out;
 }
 
+// -q / -spp: the edge-linked partition model on a fixed topology
+static int runPartitionModel(const std::string &aln_file, const std::string &part_file, const std::string &tree_file,
+                             const std::string &prefix, bool proportional, bool blfix, int dev) {
+    std::vector<std::string> names;
+    std::vector<PartitionInput> parts;
+    readPartitionRaxml(aln_file, part_file, names, parts);
+    std::ifstream tin(tree_file.c_str());
+    if (!tin) throw std::runtime_error("cannot open tree file " + tree_file);
+    std::stringstream tss;
+    tss << tin.rdbuf();
+    PhyloSuperTree tree;
+    tree.readTreeString(tss.str(), names);
+    if (tree.super.leafNum != (int)names.size()) throw std::runtime_error("Tree and alignment have different numbers of taxa");
+    for (const PartitionInput &in : parts) tree.addPartition(in);
+    tree.fixed_rates = !proportional;
+    tree.attachEngines(dev);
+    printf("Edge-linked partition model with %d partitions (%s)\n", tree.size(), proportional ? "-spp" : "-q");
+    const double lnl = tree.optimizeParameters(blfix, 0.001, 0.001);   // params.modeps defaults
+    const double total = tree.computeLikelihood();
+    (void)lnl;
+    if (proportional) {   // PartitionModelPlen::writeInfo
+        std::ostringstream os;
+        os << "Partition-specific rates: ";
+        for (double r : tree.part_rate) os << " " << r;
+        printf("%s\n", os.str().c_str());
+    }
+    for (int p = 0; p < tree.size(); p++)
+        printf("Partition %s: %d sites, %d patterns, lnL %.6f\n", tree.part_name[(size_t)p].c_str(), parts[(size_t)p].aln.getNSite(),
+               parts[(size_t)p].aln.getNPattern(), tree.cur_score[(size_t)p]);
+    printf("Optimal log-likelihood: %.6f\n", total);
+    writeText(prefix + ".treefile", tree.getTreeString() + "\n");
+    std::ostringstream rep;
+    rep.precision(17);
+    rep << "lnL " << total << "\n";
+    for (int p = 0; p < tree.size(); p++)
+        rep << "partition " << tree.part_name[(size_t)p] << " rate " << tree.part_rate[(size_t)p] << " lnL " << tree.cur_score[(size_t)p] << "\n";
+    writeText(prefix + ".iqhip", rep.str());
+    return 0;
+}
+
 static void usage() {
     fprintf(stderr,
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
@@ -215,6 +264,9 @@ static void usage() {
             "                 [-mixweights] [-optmodel] [-bb <n> [-beps <e>] [-z <tree set file>] [-wbt]]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
+            "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
+            "                 (edge-linked partition model instead of -m; lines 'MODEL, name = 1-100, 250-400, 401-500\\3';\n"
+            "                  -q: all partition rates 1, -spp: rates estimated)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
             "         POISSON+G4{1}, <paml matrix file>+G4{0.9}, 'GY{kappa,omega}+F1X4', any of them +ASC;\n"
             "         +R3{w1,r1,w2,r2,w3,r3}, or with -emrates (weights and rates estimated by EM) also a bare +R3;\n"
@@ -227,7 +279,8 @@ int main(int argc, char **argv) {
     bool blfix = false, wsl = false, all_branch = false;
     int dev = 0, reps = 0, alrt = 0, lbp = 0;
     unsigned long long seed = 1;
-    std::string treeset_file, mldist_file;
+    std::string treeset_file, mldist_file, part_file;
+    bool part_proportional = false;
     int zb = 0, sprrad = 0, bb = 0;
     double beps = 0.5;
     bool wbt = false;
@@ -265,6 +318,11 @@ int main(int argc, char **argv) {
         else if (a == "-wsr") wsr = true;
         else if (a == "-mixweights") mixweights = true;
         else if (a == "-optmodel") optmodel = true;
+        else if (a == "-q" || a == "-spp") {
+            if (!part_file.empty()) { usage(); return 2; }
+            part_file = next();
+            part_proportional = a == "-spp";
+        }
         else if (a == "-sprrad") {
             sprrad = atoi(next().c_str());
             if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
@@ -272,6 +330,23 @@ int main(int argc, char **argv) {
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
         else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
         else { usage(); return 2; }
+    }
+    if (!part_file.empty()) {
+        const char *with = !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
+                           : !mldist_file.empty() ? "-mldist" : pars || parstree || sprrad > 0 ? "-pars / -parstree / -sprrad"
+                           : bionjtree ? "-bionjtree" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : nullptr;
+        if (with) {
+            fprintf(stderr, "error: -q / -spp cannot be combined with %s (the models come from the partition file; the partition model evaluates a fixed topology)\n", with);
+            return 2;
+        }
+        if (aln_file.empty() || tree_file.empty()) { usage(); return 2; }
+        if (prefix.empty()) prefix = part_file;
+        try {
+            return runPartitionModel(aln_file, part_file, tree_file, prefix, part_proportional, blfix, dev);
+        } catch (const std::exception &ex) {
+            fprintf(stderr, "error: %s\n", ex.what());
+            return 1;
+        }
     }
     if (aln_file.empty() || model_str.empty() || (int)!tree_file.empty() + (int)parstree + (int)bionjtree != 1) { usage(); return 2; }
     if (prefix.empty()) prefix = aln_file;

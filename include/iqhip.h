@@ -832,6 +832,51 @@ int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
 #define IQHIP_PLAN_SHAPE_NSLOTS 28
 int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n);
 
+/* ---- Edge-linked partition models (-q / -spp; PhyloSuperTreePlen::computeFuncDerv, phylosupertreeplen.cpp:530-578):
+ * a GROUP of existing single-device engines, one per partition, all running the super tree's topology (a taxon without
+ * data in a partition stays in its alignment as an all-unknown row), whose branch lengths are the super tree's times
+ * the partition's rate r_p.  The group owns nothing of its members: destroying it leaves them usable, and a member must
+ * outlive the group.  All members sit on one device.
+ * iqhip_partition_create: IQHIP_ERR_UNSUPPORTED for sharded engines, communicator ranks, +ASC members and mixture
+ *   members; IQHIP_ERR_INVALID for planning-only engines, members without alignment or model, nparts < 1, a member
+ *   listed twice, a null argument, members on different devices.  Every state count and category count iqhip_create
+ *   accepts is accepted (embedded counts and wide DNA included).
+ * iqhip_partition_set_rates: r_p, finite and > 0 (IQHIP_ERR_INVALID otherwise); 1 for every member after create (-q).
+ * iqhip_partition_newton_branch: Optimization::minimizeNewton on f(x) = -sum_p r_p df_p(r_p x), f'(x) = -sum_p r_p^2
+ *   ddf_p(r_p x).  Every member must hold a valid theta (iqhip_compute_theta, or a call that leaves one) for the SAME
+ *   branch, i.e. the same two iqhip_branch_end values on every member -- leaf ids and keys: the members of a group share
+ *   one key space, as trees of one topology built alike do; IQHIP_ERR_INVALID otherwise.  A member whose df is NaN or
+ *   infinite contributes df = ddf = 0 (phylokernel.h:647-651, applied per partition before the weighted sum).  Bounds,
+ *   update rule, stopping tests, d2l and nsteps (derivative evaluations) are those of iqhip_newton_branch, and so are the
+ *   two errors of minimizeNewton.  part_lnl (nparts doubles or NULL) receives every member's computeLikelihoodFromBuffer at
+ *   r_p * optx, its scale-factor term included (taken from the scale counters of the two branch ends).
+ *   The solve is an enqueued chain on the group's stream: a state-machine init, then per evaluation one launch over all
+ *   members' thetas and one single-workgroup update; the host reads the 128-byte state once per chunk of steps
+ *   (IQHIP_PART_STEPS, read per call, overrides the steps per chunk; the result does not depend on it).  All sums run in
+ *   a fixed order: the same call gives the same bits.  The group's stream waits for the members' streams and they wait
+ *   for it (events, no host synchronisation per member).
+ * iqhip_partition_lnl_from_theta: the same per-member values at a given x >= 0.
+ * iqhip_partition_traverse_lnl: one op list and root branch for every member, member p with every length multiplied by
+ *   scale[p] (NULL: the rates); everything is enqueued on the members' streams and the nparts log-likelihoods are read
+ *   after one synchronisation.  part_lnl[p] is member p's whole log-likelihood (scale-factor term included); the per-op
+ *   sum_scale rows are not returned.  The evaluation of PhyloSuperTreePlen::computeFunction and of
+ *   optimizeTreeLengthScaling for all partitions in lockstep.
+ * iqhip_debug_partition_timing: *launches = kernels the group's last call enqueued on its own stream; with
+ *   iqhip_timing_enable on the FIRST member, ms[0] / ms[1] = device time (HIP events) of the derivative launches / of the
+ *   update launches of the last iqhip_partition_newton_branch. */
+typedef struct iqhip_partition iqhip_partition;
+int iqhip_partition_create(iqhip_partition **out, iqhip_engine *const *members, int nparts);
+void iqhip_partition_destroy(iqhip_partition *g);
+int iqhip_partition_set_rates(iqhip_partition *g, const double *rate /* nparts */);
+int iqhip_partition_newton_branch(iqhip_partition *g, double xguess, double x1, double x2, double xacc, int max_steps,
+                                  double *optx, double *d2l, int *nsteps, double *part_lnl /* nparts or NULL */);
+int iqhip_partition_lnl_from_theta(iqhip_partition *g, double x, double *part_lnl /* nparts */);
+int iqhip_partition_traverse_lnl(iqhip_partition *g, const iqhip_node_op *ops, int nops, iqhip_branch_end a,
+                                 iqhip_branch_end b, double len, const double *scale /* nparts or NULL */,
+                                 double *part_lnl /* nparts */);
+int iqhip_debug_partition_timing(iqhip_partition *g, double *ms /* 2: derivative launches, update launches */,
+                                 int64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

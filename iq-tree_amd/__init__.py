@@ -48,6 +48,8 @@ IQHIP_SYMBOLS = [
     "iqhip_pars_spr_scan", "iqhip_debug_pars_spr_check", "iqhip_debug_pars_spr_timing",
     "iqhip_bionj", "iqhip_debug_bionj_timing",
     "iqhip_ufboot_init", "iqhip_ufboot_update", "iqhip_ufboot_fetch", "iqhip_debug_ufboot_timing",
+    "iqhip_partition_create", "iqhip_partition_destroy", "iqhip_partition_set_rates", "iqhip_partition_newton_branch",
+    "iqhip_partition_lnl_from_theta", "iqhip_partition_traverse_lnl", "iqhip_debug_partition_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -259,6 +261,15 @@ def libiqhip():
     lib.iqhip_ufboot_update.argtypes = [vp, C.POINTER(UFBootTree), C.c_int, C.c_double, C.c_double, i64p, dp]
     lib.iqhip_ufboot_fetch.argtypes = [vp, dp, dp, i32p, i64p]
     lib.iqhip_debug_ufboot_timing.argtypes = [vp, dp, i64p]
+    lib.iqhip_partition_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_int]
+    lib.iqhip_partition_destroy.argtypes = [vp]
+    lib.iqhip_partition_destroy.restype = None
+    lib.iqhip_partition_set_rates.argtypes = [vp, dp]
+    lib.iqhip_partition_newton_branch.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp,
+                                                  C.POINTER(C.c_int), dp]
+    lib.iqhip_partition_lnl_from_theta.argtypes = [vp, C.c_double, dp]
+    lib.iqhip_partition_traverse_lnl.argtypes = [vp, C.POINTER(NodeOp), C.c_int, BranchEnd, BranchEnd, C.c_double, dp, dp]
+    lib.iqhip_debug_partition_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
 
@@ -336,6 +347,30 @@ def libiqhost():
     lib.iqhost_compute_bionj.argtypes = [vp, dp, dp, vp, C.POINTER(C.c_int32), dp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
     lib.iqhost_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.iqhost_super_create.argtypes = [C.POINTER(vp), C.c_char_p, C.POINTER(C.c_char_p), C.c_int]
+    lib.iqhost_super_destroy.argtypes = [vp]
+    lib.iqhost_super_destroy.restype = None
+    lib.iqhost_super_add_partition.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
+    lib.iqhost_super_attach_engines.argtypes = [vp, C.c_int]
+    lib.iqhost_super_num_parts.argtypes = [vp]
+    lib.iqhost_super_group.argtypes = [vp]
+    lib.iqhost_super_group.restype = vp
+    lib.iqhost_super_set_fixed_rates.argtypes = [vp, C.c_int]
+    lib.iqhost_super_set_rates.argtypes = [vp, dp]
+    lib.iqhost_super_get_rates.argtypes = [vp, dp]
+    lib.iqhost_super_part_lnl.argtypes = [vp, dp]
+    lib.iqhost_super_set_branch_bounds.argtypes = [vp, C.c_double, C.c_double]
+    lib.iqhost_super_compute_likelihood.argtypes = [vp, dp]
+    lib.iqhost_super_optimize_one_branch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    lib.iqhost_super_optimize_all_branches.argtypes = [vp, C.c_int, C.c_double, C.c_int, dp]
+    lib.iqhost_super_optimize_gene_rates.argtypes = [vp, C.c_double, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.iqhost_super_optimize_parameters.argtypes = [vp, C.c_int, C.c_double, C.c_double, dp]
+    lib.iqhost_super_newton_branch.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                               dp, dp, C.POINTER(C.c_int), dp]
+    lib.iqhost_super_branch_length.argtypes = [vp, C.c_int, C.c_int, dp]
+    lib.iqhost_super_branch_order.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    lib.iqhost_super_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
+    lib.iqhost_super_counters.argtypes = [vp, C.POINTER(C.c_long)]
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.iqhost_test_all_branches.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), dp, C.c_int,
                                              C.POINTER(C.c_int), dp]
@@ -411,6 +446,20 @@ def libiqhost():
     lib.iqmodel_genetic_code.argtypes = [C.c_int]
     lib.iqmodel_genetic_code.restype = C.c_char_p
     lib.iqaln_read.argtypes = [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p]
+    lib.iqpart_spec_parse.argtypes = [C.POINTER(vp), C.c_char_p, C.c_int]
+    lib.iqpart_spec_free.argtypes = [vp]
+    lib.iqpart_spec_free.restype = None
+    lib.iqpart_spec_count.argtypes = [vp]
+    for f in ("iqpart_spec_model", "iqpart_spec_name", "iqpart_model", "iqpart_name"):
+        getattr(lib, f).argtypes = [vp, C.c_int]
+        getattr(lib, f).restype = C.c_char_p
+    lib.iqpart_spec_nsites.argtypes = [vp, C.c_int]
+    lib.iqpart_spec_sites.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    lib.iqpart_read.argtypes = [C.POINTER(vp), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+    lib.iqpart_free.argtypes = [vp]
+    lib.iqpart_free.restype = None
+    lib.iqpart_count.argtypes = [vp]
+    lib.iqpart_alignment.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.iqaln_destroy.argtypes = [vp]
     lib.iqaln_destroy.restype = None
     for f in ("iqaln_nseq", "iqaln_nsite", "iqaln_npattern", "iqaln_nstates", "iqaln_seq_type", "iqaln_state_unknown"):
@@ -1768,6 +1817,267 @@ class PhyloTree:
 # ---------------------------------------------------------------------------------------------
 # model / alignment producers: C++ in iq-tree_amd/host/{model,alignment}_host.cpp
 # ---------------------------------------------------------------------------------------------
+
+class PartitionGroup:
+    """A group of engines, one per partition of an edge-linked partition model (iqhip_partition_*, include/iqhip.h).
+    `members`: PhyloTree objects with attached engines, or raw engine handles.  The group owns nothing of them."""
+
+    def __init__(self, members):
+        self.lib = libiqhip()
+        self.members = list(members)
+        handles = [m.engine if isinstance(m, PhyloTree) else m for m in self.members]
+        self.nparts = len(handles)
+        arr = (C.c_void_p * max(1, self.nparts))(*handles)
+        self.h = C.c_void_p()
+        self._chk(self.lib.iqhip_partition_create(C.byref(self.h), arr, self.nparts))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise EngineError(rc, self.lib.iqhip_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.lib.iqhip_partition_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_rates(self, rates):
+        r = np.ascontiguousarray(rates, dtype=np.float64)
+        if r.shape != (self.nparts,):
+            raise ValueError("one rate per member")
+        self._chk(self.lib.iqhip_partition_set_rates(self.h, r.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def newton_branch(self, xguess, x1, x2, xacc, max_steps, want_lnl=True):
+        """-> (optx, d2l, derivative evaluations, part_lnl or None)"""
+        optx, d2l, ns = C.c_double(), C.c_double(), C.c_int()
+        out = np.zeros(self.nparts) if want_lnl else None
+        self._chk(self.lib.iqhip_partition_newton_branch(
+            self.h, xguess, x1, x2, xacc, max_steps, C.byref(optx), C.byref(d2l), C.byref(ns),
+            out.ctypes.data_as(C.POINTER(C.c_double)) if want_lnl else None))
+        return optx.value, d2l.value, ns.value, out
+
+    def lnl_from_theta(self, x):
+        out = np.zeros(self.nparts)
+        self._chk(self.lib.iqhip_partition_lnl_from_theta(self.h, x, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def traverse_lnl(self, ops, a, b, length, scale=None):
+        """ops: a ctypes array of NodeOp (or None); a, b: BranchEnd; -> part_lnl"""
+        out = np.zeros(self.nparts)
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        self._chk(self.lib.iqhip_partition_traverse_lnl(
+            self.h, ops, 0 if ops is None else len(ops), a, b, length,
+            None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def timing(self):
+        """-> {"derv_ms", "update_ms", "launches"} of the last call (the times need iqhip_timing_enable on member 0)"""
+        ms = (C.c_double * 2)()
+        n = C.c_int64()
+        self._chk(self.lib.iqhip_debug_partition_timing(self.h, ms, C.byref(n)))
+        return {"derv_ms": ms[0], "update_ms": ms[1], "launches": n.value}
+
+
+def parse_partition_spec(text, nsite):
+    """RAxML-style partition file text (host/partition_spec.h) -> [(model string verbatim, name, [0-based sites])]"""
+    lib = libiqhost()
+    h = C.c_void_p()
+    _mchk(lib, lib.iqpart_spec_parse(C.byref(h), text.encode(), int(nsite)))
+    try:
+        out = []
+        for k in range(lib.iqpart_spec_count(h)):
+            sites = (C.c_int * lib.iqpart_spec_nsites(h, k))()
+            _mchk(lib, lib.iqpart_spec_sites(h, k, sites))
+            out.append((lib.iqpart_spec_model(h, k).decode(), lib.iqpart_spec_name(h, k).decode(), list(sites)))
+        return out
+    finally:
+        lib.iqpart_spec_free(h)
+
+
+def read_partition_file(aln, path, aln_content=None, part_content=None):
+    """One alignment file + a RAxML-style partition file `MODEL, name = 1-100, 250-400, 401-500\\3` (readPartitionRaxml):
+    -> (sequence names, parts), one dict per partition ready for PhyloSuperTree: name, model_string, alignment (an
+    Alignment), nstates, seq_type, pat, freq, invar, model, nsite.  Every taxon is kept (all-unknown rows)."""
+    lib = libiqhost()
+    h = C.c_void_p()
+    if aln_content is not None:
+        _mchk(lib, lib.iqpart_read(C.byref(h), None, aln_content.encode(), None, part_content.encode()))
+    else:
+        _mchk(lib, lib.iqpart_read(C.byref(h), str(aln).encode(), None, str(path).encode(), None))
+    try:
+        parts, names = [], None
+        for k in range(lib.iqpart_count(h)):
+            a = Alignment.__new__(Alignment)
+            a.lib, a.h, a.n_unobserved = lib, C.c_void_p(), 0
+            _mchk(lib, lib.iqpart_alignment(h, k, C.byref(a.h)))
+            ms = lib.iqpart_model(h, k).decode()
+            model = a.build_model(ms)
+            pat, freq, _, _ = a.arrays()
+            names = a.seq_names
+            parts.append(dict(name=lib.iqpart_name(h, k).decode(), model_string=ms, alignment=a, nstates=a.nstates,
+                              seq_type=a.seq_type, pat=pat, freq=freq, invar=a.ptn_invar(model.p_invar, model.state_freq),
+                              model=model, nsite=a.nsite))
+        return names, parts
+    finally:
+        lib.iqpart_free(h)
+
+
+class _MemberTree(PhyloTree):
+    """a PhyloTree owned by a PhyloSuperTree: every method works, destruction is the super tree's"""
+
+    def __init__(self, handle):
+        self.lib = libiqhost()
+        self.h = handle
+        self.nptn = 0
+        self.block = 0
+
+    def close(self):
+        self.h = C.c_void_p()
+
+
+class PhyloSuperTree:
+    """Edge-linked partition model (-q / -spp; host/supertree_host.h): P trees of the super tree's topology, member p's
+    lengths the super tree's times part_rates[p].  parts: dicts with nstates, seq_type, pat, freq, model and optionally
+    invar, name.  Every member keeps every taxon (all-unknown rows where a partition has no data)."""
+
+    def __init__(self, newick, parts, names=None, device=0, fixed_rates=True, attach=True):
+        self.lib = libiqhost()
+        self.h = C.c_void_p()
+        if names:
+            arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
+            rc = self.lib.iqhost_super_create(C.byref(self.h), newick.encode(), arr, len(names))
+        else:
+            rc = self.lib.iqhost_super_create(C.byref(self.h), newick.encode(), None, 0)
+        self._chk(rc)
+        self.members = []
+        for k, d in enumerate(parts):
+            mh = C.c_void_p()
+            self._chk(self.lib.iqhost_super_add_partition(self.h, str(d.get("name", "part%d" % (k + 1))).encode(), C.byref(mh)))
+            t = _MemberTree(mh)
+            t.set_alignment(d["nstates"] if "nstates" in d else d["n"], d["seq_type"], d["pat"], d["freq"], d.get("invar"))
+            t.set_model(d["model"])
+            self.members.append(t)
+        self.nparts = len(self.members)
+        self.nsites = [float(np.sum(d["freq"])) for d in parts]
+        self._chk(self.lib.iqhost_super_set_fixed_rates(self.h, int(fixed_rates)))
+        if attach:
+            self._chk(self.lib.iqhost_super_attach_engines(self.h, device))
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+
+    def close(self):
+        if self.h:
+            for t in self.members:
+                t.close()
+            self.lib.iqhost_super_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def part_rates(self):
+        out = np.zeros(self.nparts)
+        self._chk(self.lib.iqhost_super_get_rates(self.h, _dptr(out)))
+        return out
+
+    @part_rates.setter
+    def part_rates(self, rates):
+        r = np.ascontiguousarray(rates, dtype=np.float64)
+        if r.shape != (self.nparts,):
+            raise ValueError("one rate per partition")
+        self._chk(self.lib.iqhost_super_set_rates(self.h, _dptr(r)))
+
+    def set_fixed_rates(self, on=True):
+        self._chk(self.lib.iqhost_super_set_fixed_rates(self.h, int(on)))
+
+    def set_branch_bounds(self, lo, hi):
+        self._chk(self.lib.iqhost_super_set_branch_bounds(self.h, lo, hi))
+
+    def part_lnl(self):
+        """every member's log-likelihood as of the last call (part_info[part].cur_score)"""
+        out = np.zeros(self.nparts)
+        self._chk(self.lib.iqhost_super_part_lnl(self.h, _dptr(out)))
+        return out
+
+    def compute_likelihood(self):
+        v = C.c_double()
+        self._chk(self.lib.iqhost_super_compute_likelihood(self.h, C.byref(v)))
+        return v.value
+
+    def optimize_one_branch(self, a, b, clear_lh=True, max_nr_step=100):
+        v = C.c_double()
+        self._chk(self.lib.iqhost_super_optimize_one_branch(self.h, a, b, int(clear_lh), max_nr_step, C.byref(v)))
+        return v.value
+
+    def optimize_all_branches(self, iterations=100, tolerance=0.001, max_nr_step=100):
+        v = C.c_double()
+        self._chk(self.lib.iqhost_super_optimize_all_branches(self.h, iterations, tolerance, max_nr_step, C.byref(v)))
+        return v.value
+
+    def optimize_gene_rates(self, gradient_epsilon=0.001):
+        """-> dict(lnl, rates, evals per member, rounds = group traversals)"""
+        v, rounds = C.c_double(), C.c_int()
+        evals = (C.c_int * self.nparts)()
+        self._chk(self.lib.iqhost_super_optimize_gene_rates(self.h, gradient_epsilon, C.byref(v), evals, C.byref(rounds)))
+        return dict(lnl=v.value, rates=self.part_rates, evals=list(evals), rounds=rounds.value)
+
+    def optimize_parameters(self, fixed_len=False, logl_epsilon=0.001, gradient_epsilon=0.001):
+        v = C.c_double()
+        self._chk(self.lib.iqhost_super_optimize_parameters(self.h, int(fixed_len), logl_epsilon, gradient_epsilon, C.byref(v)))
+        return v.value
+
+    def partition_newton_branch(self, a, b, xguess, x1, x2, xacc, max_steps):
+        """theta of (a, b) on every member, then iqhip_partition_newton_branch -> (optx, d2l, evaluations, part_lnl)"""
+        optx, d2l, ns = C.c_double(), C.c_double(), C.c_int()
+        out = np.zeros(self.nparts)
+        self._chk(self.lib.iqhost_super_newton_branch(self.h, a, b, xguess, x1, x2, xacc, max_steps, C.byref(optx), C.byref(d2l),
+                                                      C.byref(ns), _dptr(out)))
+        return optx.value, d2l.value, ns.value, out
+
+    def branch_length(self, a, b):
+        v = C.c_double()
+        self._chk(self.lib.iqhost_super_branch_length(self.h, a, b, C.byref(v)))
+        return v.value
+
+    def branch_order(self):
+        """the branches in optimize_all_branches' order"""
+        cap = 4 * self.members[0].num_nodes
+        n1, n2 = (C.c_int * cap)(), (C.c_int * cap)()
+        n = self.lib.iqhost_super_branch_order(self.h, n1, n2, cap)
+        if n < 0:
+            raise HostError(self.lib.iqhost_last_error().decode())
+        return [(n1[k], n2[k]) for k in range(n)]
+
+    def tree_string(self):
+        buf = C.create_string_buffer(1 << 20)
+        self._chk(self.lib.iqhost_super_tree_string(self.h, buf, len(buf)))
+        return buf.value.decode()
+
+    def counters(self):
+        out = (C.c_long * 3)()
+        self.lib.iqhost_super_counters(self.h, out)
+        return dict(group_solves=out[0], group_traversals=out[1], diverged=out[2])
+
+    def partition_timing(self):
+        """iqhip_debug_partition_timing of the group's last call (times need iqhip_timing_enable on member 0)"""
+        hip = libiqhip()
+        ms = (C.c_double * 2)()
+        n = C.c_int64()
+        if hip.iqhip_debug_partition_timing(self.lib.iqhost_super_group(self.h), ms, C.byref(n)) != 0:
+            raise HostError(hip.iqhip_last_error().decode())
+        return {"derv_ms": ms[0], "update_ms": ms[1], "launches": n.value}
+
 
 class AttrDict(dict):
     """dict whose keys also read as attributes (so it can stand where a synth.Model is expected)."""

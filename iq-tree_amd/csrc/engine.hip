@@ -888,6 +888,16 @@ int iqhip::read_result(iqhip_engine *e, int ndoubles) {
     return IQHIP_OK;
 }
 
+void iqhip::result_arrived(iqhip_engine *e) {
+    e->poll_pending = false;
+    e->staging_busy = false;
+    if (e->folded_rows >= 0) {
+        if (e->h_result[2 + e->folded_rows] == 0.0)
+            for (int k = 0; k < e->folded_rows; k++) e->h_result[2 + k] = 0.0;
+        e->folded_rows = -1;
+    }
+}
+
 // the NaN/Inf repair of phylokernel.h:848-866 / :1100-1122, done on the (rare) slow path
 static int repair_lnl(iqhip_engine *e, double *lnl) {
     std::vector<double> plh((size_t)e->nptn_pad), freq((size_t)e->nptn_pad);
@@ -998,10 +1008,13 @@ extern "C" int iqhip_update_partials_async(iqhip_engine *e, const iqhip_node_op 
     return submit_traverse(e, ops, nops, false, none, none, 0.0);
 }
 
-void iqhip::set_theta_branch(iqhip_engine *e, const DevBranch &br) {
+void iqhip::set_theta_branch(iqhip_engine *e, const DevBranch &br, iqhip_branch_end a, iqhip_branch_end b) {
     e->theta_valid = true;
     e->theta_a_sc = br.a_sc;
     e->theta_b_sc = br.b_sc;
+    if (b.leaf >= 0) std::swap(a, b);   // (build_branch's order)
+    e->theta_end[0] = a;
+    e->theta_end[1] = b;
 }
 
 extern "C" int iqhip_compute_theta(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b) {
@@ -1013,7 +1026,7 @@ extern "C" int iqhip_compute_theta(iqhip_engine *e, iqhip_branch_end a, iqhip_br
     if (rc) return rc;
     if (e->mfma) HIPCHK(launch_stream_mfma(e, 1, &br, 0.0, (int)e->ntiles));
     else HIPCHK(launch_theta4(e, br));
-    set_theta_branch(e, br);
+    set_theta_branch(e, br, a, b);
     return IQHIP_OK;
 }
 

@@ -107,6 +107,21 @@ __device__ __forceinline__ double wave_sum64(double v) {
     return v;
 }
 
+// sum over the four lane groups of a pattern (lanes p, p+16, p+32, p+48) with gfx950's permlane swaps instead of
+// ds_bpermute: swap(x, x) hands every lane its partner's value; (x + x^16) + (that of the lanes ^32), the order of
+// the shuffle form (fp addition commutes), so the bits are the same
+__device__ __forceinline__ double group_sum(double v) {
+    unsigned lo = __double2loint(v), hi = __double2hiint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+    lo = __double2loint(v);
+    hi = __double2hiint(v);
+    auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
+}
+
 // The scaling test max|x| < 2^-256 on the 32-bit vector ALU: for finite doubles |x| < 2^-256 <=> the high word of |x|
 // is below that of 2^-256 (whose low word is 0), and the high words order like the values.  fp64 vector instructions
 // run on the unit that executes the fp64 matrix instructions and ADD to their time (3.1 ns each against 29.5 ns for a
@@ -370,6 +385,7 @@ struct iqhip_engine {
     double pattern_lh_shift = 0.0;        // log(1 - prob_const) of the last lnL evaluation
     const int16_t *theta_a_sc = nullptr;  // scale counters of the ends theta was built from
     const int16_t *theta_b_sc = nullptr;
+    iqhip_branch_end theta_end[2] = {{0, -1, 0}, {0, -1, 0}};   // ... and the ends as the caller named them (a leaf end first)
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -893,7 +909,11 @@ int submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, bool ha
                     iqhip_branch_end b, double len, bool skip_reduce = false, const std::vector<int> *explicit_segs = nullptr,
                     const double *const *len_ptrs = nullptr);
 int read_result(iqhip_engine *e, int ndoubles);       // D2H of the result vector (if it is device memory) + stream sync
-void set_theta_branch(iqhip_engine *e, const DevBranch &br);   // theta is (being) built from this branch's two ends
+// theta is (being) built from this branch's two ends, which the caller named a and b
+void set_theta_branch(iqhip_engine *e, const DevBranch &br, iqhip_branch_end a, iqhip_branch_end b);
+// read_result's bookkeeping for a caller that has waited for the engine's stream itself (partition.hip: one wait for
+// all members); a caller-bound device result vector must have been copied to h_result on that stream before
+void result_arrived(iqhip_engine *e);
 int eng_repair_lnl(iqhip_engine *e, double *lnl);     // phylokernel.h:848-866 on this engine's _pattern_lh -> its own sum
 extern double debug_build_us;                         // IQHIP_DEBUG_SWEEP: host time in build_plan since the last sweep report
 
@@ -1046,6 +1066,9 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
 // Newton as a chain of enqueued steps (kernels_newton.hip): state init, derivative evaluation at state->rts
 // (skipped once state->done), state update from result[0..1]
 hipError_t launch_newton_state_init(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps);
+// ... of a state machine that belongs to no engine (partition.hip)
+hipError_t launch_newton_state_init_on(hipStream_t s, NewtonState *st, double xguess, double x1, double x2, double xacc,
+                                       int max_steps);
 hipError_t launch_derv_at_state(iqhip_engine *e, int nwaves);
 hipError_t launch_newton_state_update(iqhip_engine *e);   // (+ASC: result[2..4] and asc_nsites enter the update)
 // from result[2t], result[2t+1]; +ASC: from result[5t .. 5t+4], corrected like launch_newton_state_update
@@ -1177,5 +1200,38 @@ size_t leaf_table_doubles(const iqhip_engine *e);          // doubles per (leaf 
 hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, double len, int nwaves,
                               const NewtonState *st = nullptr, int fold_rows = -1, double *theta_out = nullptr,
                               const BatchChain *bc = nullptr);
+
+// kernels_partnewton.hip: the joint branch solve of a partition group (partition.hip).  One descriptor per member, filled
+// from the engine fields that fill NewtonArgs; a work item is a contiguous run of tiles of ONE member, one workgroup each
+struct __attribute__((aligned(16))) PartDesc {
+    const double *theta, *evalc, *rates, *props, *freq, *invar;
+    const int16_t *a_sc, *b_sc;   // scale counters of the ends theta was built from (nullptr: a leaf end)
+    int64_t nptn, ntiles;
+    int32_t n, ncat, mfma;
+    int32_t item_first, nitems;   // the member's work items, in tile order
+    int32_t _pad;
+    double rate;
+};
+struct __attribute__((aligned(16))) PartItem {
+    int64_t first_tile;
+    int32_t member, ntiles;
+};
+// the root branch of one member for the scale-factor term of a traversal's lnL
+struct __attribute__((aligned(16))) PartScale {
+    const int16_t *a_sc, *b_sc;
+    const double *freq;
+    int64_t nptn;
+};
+constexpr int kPartUpdateThreads = 64;   // k_part_newton_update: thread t owns members t, t + 64, ..
+// mode 0: {df, ddf} of every item at rate * st->rts (nothing once st->done); mode 1: f * log|lh| sums (scale-factor term
+// included) at rate * (st ? st->result : x) -> partials[2 item], [2 item + 1]; lds_doubles = 3 * the largest block
+hipError_t launch_part_derv(hipStream_t s, int mode, const PartDesc *d_desc, const PartItem *d_items, int nitems,
+                            int lds_doubles, const NewtonState *st, double x, double *partials);
+// per member: its items summed in item order, the NaN rule; then r df, r^2 ddf summed in member order -> newton_update
+hipError_t launch_part_newton_update(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials,
+                                     NewtonState *st);
+hipError_t launch_part_lnl_finish(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials, double *out);
+// out[p] = kLogScalingThreshold * sum over patterns of freq * (a_sc + b_sc), fixed order
+hipError_t launch_part_scale_terms(hipStream_t s, const PartScale *d_sc, int nparts, double *out);
 
 }  // namespace iqhip

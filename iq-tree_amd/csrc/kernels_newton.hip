@@ -98,21 +98,6 @@ struct NewtonArgs {
     double diverge_x;
 };
 
-// sum over the four lane groups of a pattern (lanes p, p+16, p+32, p+48) with gfx950's permlane swaps instead of
-// ds_bpermute: swap(x, x) hands every lane its partner's value; (x + x^16) + (that of the lanes ^32), the order of
-// the shuffle form (fp addition commutes), so the bits are the same
-__device__ __forceinline__ double group_sum(double v) {
-    unsigned lo = __double2loint(v), hi = __double2hiint(v);
-    auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    v = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-    lo = __double2loint(v);
-    hi = __double2hiint(v);
-    auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    auto d = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return __hiloint2double(d[0], c[0]) + __hiloint2double(d[1], c[1]);
-}
-
 __device__ __forceinline__ double wsum(double v) { return wave_sum64(v); }
 
 // sum over this workgroup's patterns of f*df_ptn and f*ddf_ptn at the val arrays in LDS
@@ -1055,6 +1040,12 @@ hipError_t launch_newton_state_update_batch(iqhip_engine *e, NewtonState *states
 
 hipError_t launch_newton_state_init(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps) {
     hipLaunchKernelGGL(k_newton_state_init, dim3(1), dim3(64), 0, e->stream, e->d_nstate, xguess, x1, x2, xacc, max_steps);
+    return hipGetLastError();
+}
+
+hipError_t launch_newton_state_init_on(hipStream_t s, NewtonState *st, double xguess, double x1, double x2, double xacc,
+                                       int max_steps) {
+    hipLaunchKernelGGL(k_newton_state_init, dim3(1), dim3(64), 0, s, st, xguess, x1, x2, xacc, max_steps);
     return hipGetLastError();
 }
 

@@ -1,0 +1,452 @@
+// partition.hip -- host side of the edge-linked partition model (-q / -spp): a group of existing single-device engines,
+// one per partition, and the calls that span them (include/iqhip.h, "Edge-linked partition models").  The kernels are in
+// kernels_partnewton.hip.  The group owns a stream, a device-resident NewtonState, the descriptor table of its members and
+// the work-item slots; it owns nothing of the members.
+//
+// Descriptors: re-filled from the members' engine fields on EVERY call (a few hundred bytes per member) and uploaded only
+// when the bytes differ from what the device holds -- so a new model, alignment, theta buffer or rate is picked up without
+// a generation counter on the engine.
+// Streams: every call first makes the group's stream wait for an event recorded on each member's stream (the thetas and
+// vectors the group reads are complete), and after its last launch makes every member's stream wait for an event of the
+// group's stream (no member overwrites theta while the group still reads it).  The host waits once, for the group's stream.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "iqhip_internal.h"
+
+using namespace iqhip;
+
+namespace {
+constexpr int kPartItemTiles4 = 16;     // 64-pattern tiles per work item (4-state engines): 1024 patterns
+constexpr int kPartItemTilesM = 32;     // 16-pattern tiles per work item (matrix-core engines): 512 patterns
+constexpr size_t kPartMaxLdsBytes = 64 * 1024;
+
+// a device buffer with its pinned staging twin
+template <typename T>
+struct Twin {
+    T *d = nullptr, *h = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(hipStream_t s, size_t count) {
+        if (count <= cap) return hipSuccess;
+        hipError_t rc = hipStreamSynchronize(s);
+        if (rc != hipSuccess) return rc;
+        release();
+        const size_t want = std::max(count, (size_t)64);
+        if ((rc = hipMalloc((void **)&d, want * sizeof(T))) != hipSuccess) return rc;
+        if ((rc = hipHostMalloc((void **)&h, want * sizeof(T))) != hipSuccess) return rc;
+        cap = want;
+        return hipSuccess;
+    }
+    void release() {
+        if (d) hipFree(d);
+        if (h) hipHostFree(h);
+        d = nullptr; h = nullptr; cap = 0;
+    }
+};
+}  // namespace
+
+struct iqhip_partition {
+    int device = 0, nparts = 0;
+    std::vector<iqhip_engine *> m;
+    std::vector<double> rate;
+    hipStream_t stream = nullptr;
+    std::vector<hipEvent_t> ev;      // one per member, recorded on its stream
+    hipEvent_t ev_done = nullptr;    // recorded on the group's stream behind its last launch
+    Twin<char> table;                // [nparts] PartDesc ++ [nitems] PartItem
+    std::vector<char> uploaded;      // the bytes of `table` the device holds
+    Twin<PartScale> scale;
+    Twin<double> out;                // per member: lnL sums / scale-factor terms
+    Twin<NewtonState> state;
+    double *d_partials = nullptr;    // [nitems][2]
+    size_t partials_cap = 0;
+    int nitems = 0, lds_doubles = 0;
+    // iqhip_debug_partition_timing
+    std::vector<hipEvent_t> tev;
+    double ms[2] = {0.0, 0.0};
+    int64_t launches = 0;
+};
+
+namespace {
+
+// what a member must be, at create and again at every call (a model or a correction may have been set since)
+int member_ok(const iqhip_engine *e, int p) {
+    const std::string who = "partition member " + std::to_string(p);
+    if (!e) return fail(IQHIP_ERR_INVALID, who + ": null engine");
+    if (!e->shards.empty() || e->comm)
+        return fail(IQHIP_ERR_UNSUPPORTED, who + ": sharded engines and communicator ranks cannot join a partition group");
+    if (e->planner) return fail(IQHIP_ERR_INVALID, who + ": planning-only engine");
+    if (!e->model_set || !e->aln_set) return fail(IQHIP_ERR_INVALID, who + ": needs iqhip_set_model and iqhip_set_alignment first");
+    if (e->asc_active || e->n_unobs > 0)
+        return fail(IQHIP_ERR_UNSUPPORTED, who + ": ascertainment bias correction is not available in a partition group");
+    if (e->nclass > 1) return fail(IQHIP_ERR_UNSUPPORTED, who + ": mixture models are not available in a partition group");
+    return IQHIP_OK;
+}
+
+int members_ok(const iqhip_partition *g) {
+    for (int p = 0; p < g->nparts; p++) {
+        const int rc = member_ok(g->m[p], p);
+        if (rc) return rc;
+    }
+    return IQHIP_OK;
+}
+
+bool same_end(const iqhip_branch_end &x, const iqhip_branch_end &y) {
+    if (x.leaf >= 0 || y.leaf >= 0) return x.leaf == y.leaf;
+    return x.key == y.key;
+}
+
+int thetas_ok(const iqhip_partition *g, const char *what) {
+    for (int p = 0; p < g->nparts; p++) {
+        const iqhip_engine *e = g->m[p], *e0 = g->m[0];
+        if (!e->theta_valid)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": theta not computed on member " + std::to_string(p));
+        // (two internal ends come in the caller's order)
+        const bool same = (same_end(e->theta_end[0], e0->theta_end[0]) && same_end(e->theta_end[1], e0->theta_end[1])) ||
+                          (same_end(e->theta_end[0], e0->theta_end[1]) && same_end(e->theta_end[1], e0->theta_end[0]));
+        if (!same)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": theta of member " + std::to_string(p) +
+                                               " was built for another branch than that of member 0");
+    }
+    return IQHIP_OK;
+}
+
+// the descriptor table from the members as they are now; uploaded when its bytes changed
+int refresh_table(iqhip_partition *g) {
+    const int P = g->nparts;
+    std::vector<PartDesc> desc((size_t)P);
+    std::vector<PartItem> items;
+    int maxB = 0;
+    for (int p = 0; p < P; p++) {
+        const iqhip_engine *e = g->m[p];
+        PartDesc &D = desc[p];
+        memset(&D, 0, sizeof D);
+        D.theta = e->d_theta;
+        D.evalc = e->d_evalc;
+        D.rates = e->d_rates;
+        D.props = e->d_props;
+        D.freq = e->d_freq;
+        D.invar = e->d_invar;
+        D.a_sc = e->theta_a_sc;
+        D.b_sc = e->theta_b_sc;
+        D.nptn = e->nptn;
+        D.ntiles = e->ntiles;
+        D.n = e->n;
+        D.ncat = e->ncat;
+        D.mfma = e->mfma ? 1 : 0;
+        D.rate = g->rate[p];
+        D.item_first = (int32_t)items.size();
+        const int64_t per = e->mfma ? kPartItemTilesM : kPartItemTiles4;
+        for (int64_t t = 0; t < e->ntiles; t += per) {
+            PartItem it;
+            it.first_tile = t;
+            it.member = p;
+            it.ntiles = (int32_t)std::min<int64_t>(per, e->ntiles - t);
+            items.push_back(it);
+        }
+        D.nitems = (int32_t)items.size() - D.item_first;
+        maxB = std::max(maxB, e->block);
+        if (items.size() > (size_t)1 << 30) return fail(IQHIP_ERR_UNSUPPORTED, "partition group: too many work items");
+    }
+    if ((size_t)(3 * maxB + 8) * sizeof(double) > kPartMaxLdsBytes)
+        return fail(IQHIP_ERR_UNSUPPORTED, "partition group: nstates * ncat of a member exceeds the solve's LDS");
+    g->lds_doubles = 3 * maxB;
+    g->nitems = (int)items.size();
+    const size_t bytes_desc = sizeof(PartDesc) * (size_t)P, bytes = bytes_desc + sizeof(PartItem) * items.size();
+    std::vector<char> now(bytes);
+    memcpy(now.data(), desc.data(), bytes_desc);
+    memcpy(now.data() + bytes_desc, items.data(), bytes - bytes_desc);
+    if ((size_t)g->nitems > g->partials_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->d_partials) hipFree(g->d_partials);
+        g->d_partials = nullptr;
+        g->partials_cap = 0;
+        HIPCHK(hipMalloc((void **)&g->d_partials, sizeof(double) * 2 * (size_t)g->nitems));
+        g->partials_cap = (size_t)g->nitems;
+    }
+    if (now == g->uploaded) return IQHIP_OK;
+    const size_t old_cap = g->table.cap;
+    HIPCHK(g->table.ensure(g->stream, bytes));
+    if (g->table.cap != old_cap) g->uploaded.clear();
+    // (the staging is free: every call of the group ends with a wait for its stream)
+    memcpy(g->table.h, now.data(), bytes);
+    HIPCHK(hipMemcpyAsync(g->table.d, g->table.h, bytes, hipMemcpyHostToDevice, g->stream));
+    g->uploaded.swap(now);
+    return IQHIP_OK;
+}
+
+const PartDesc *d_desc(const iqhip_partition *g) { return reinterpret_cast<const PartDesc *>(g->table.d); }
+const PartItem *d_items(const iqhip_partition *g) {
+    return reinterpret_cast<const PartItem *>(g->table.d + sizeof(PartDesc) * (size_t)g->nparts);
+}
+
+// the group's stream waits for everything enqueued on the members' streams so far
+int wait_for_members(iqhip_partition *g) {
+    for (int p = 0; p < g->nparts; p++) {
+        HIPCHK(hipEventRecord(g->ev[p], g->m[p]->stream));
+        HIPCHK(hipStreamWaitEvent(g->stream, g->ev[p], 0));
+    }
+    return IQHIP_OK;
+}
+// ... and the members' streams for everything enqueued on the group's
+int members_wait(iqhip_partition *g) {
+    HIPCHK(hipEventRecord(g->ev_done, g->stream));
+    for (int p = 0; p < g->nparts; p++) HIPCHK(hipStreamWaitEvent(g->m[p]->stream, g->ev_done, 0));
+    return IQHIP_OK;
+}
+
+int use_group(iqhip_partition *g, const char *what) {
+    if (!g) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null group");
+    const int rc = members_ok(g);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(g->device));
+    return IQHIP_OK;
+}
+
+// the MODE 1 pass over the thetas -> out.h[0 .. nparts) after the caller's wait for the stream; st: at its result, only once
+// it is done (the pass is enqueued behind a chunk of steps that may not have finished the solve)
+int enqueue_part_lnl(iqhip_partition *g, const NewtonState *st, double x) {
+    HIPCHK(launch_part_derv(g->stream, 1, d_desc(g), d_items(g), g->nitems, g->lds_doubles, st, x, g->d_partials));
+    HIPCHK(launch_part_lnl_finish(g->stream, d_desc(g), g->nparts, g->d_partials, g->out.d));
+    HIPCHK(hipMemcpyAsync(g->out.h, g->out.d, sizeof(double) * (size_t)g->nparts, hipMemcpyDeviceToHost, g->stream));
+    g->launches += 2;
+    return IQHIP_OK;
+}
+
+hipEvent_t timing_event(iqhip_partition *g, size_t k) {
+    while (g->tev.size() <= k) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) return nullptr;
+        g->tev.push_back(e);
+    }
+    return g->tev[k];
+}
+
+int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, int max_steps, bool want_lnl,
+          NewtonState *result) {
+    int chunk_env = 0;
+    if (const char *s = getenv("IQHIP_PART_STEPS")) chunk_env = atoi(s);
+    const bool timing = g->m[0]->timing;
+    size_t nev = 0;
+    HIPCHK(launch_newton_state_init_on(g->stream, g->state.d, xguess, x1, x2, xacc, max_steps));
+    g->launches++;
+    for (int enq = 0;;) {
+        const int chunk = chunk_env > 0 ? chunk_env : (enq == 0 ? std::min(4, max_steps + 1) : 2);
+        for (int k = 0; k < chunk; k++) {
+            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+            if (timing) {
+                e0 = timing_event(g, nev);
+                e1 = timing_event(g, nev + 1);
+                e2 = timing_event(g, nev + 2);
+                if (!e0 || !e1 || !e2) return fail(IQHIP_ERR_HIP, "partition group: hipEventCreate failed");
+                nev += 3;
+                HIPCHK(hipEventRecord(e0, g->stream));
+            }
+            HIPCHK(launch_part_derv(g->stream, 0, d_desc(g), d_items(g), g->nitems, g->lds_doubles, g->state.d, 0.0,
+                                    g->d_partials));
+            if (timing) HIPCHK(hipEventRecord(e1, g->stream));
+            HIPCHK(launch_part_newton_update(g->stream, d_desc(g), g->nparts, g->d_partials, g->state.d));
+            if (timing) HIPCHK(hipEventRecord(e2, g->stream));
+            g->launches += 2;
+        }
+        enq += chunk;
+        if (want_lnl) {
+            const int rc = enqueue_part_lnl(g, g->state.d, 0.0);
+            if (rc) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(g->state.h, g->state.d, sizeof(NewtonState), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->state.h->done) break;
+        if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
+    }
+    if (timing) {
+        g->ms[0] = g->ms[1] = 0.0;
+        for (size_t k = 0; k + 3 <= nev; k += 3) {
+            float a = 0.0f, b = 0.0f;
+            HIPCHK(hipEventElapsedTime(&a, g->tev[k], g->tev[k + 1]));
+            HIPCHK(hipEventElapsedTime(&b, g->tev[k + 1], g->tev[k + 2]));
+            g->ms[0] += a;
+            g->ms[1] += b;
+        }
+    }
+    *result = *g->state.h;
+    return IQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int iqhip_partition_create(iqhip_partition **out, iqhip_engine *const *members, int nparts) {
+    if (!out || !members) return fail(IQHIP_ERR_INVALID, "iqhip_partition_create: null argument");
+    *out = nullptr;
+    if (nparts < 1) return fail(IQHIP_ERR_INVALID, "iqhip_partition_create: nparts < 1");
+    for (int p = 0; p < nparts; p++) {
+        const int rc = member_ok(members[p], p);
+        if (rc) return rc;
+        if (members[p]->device != members[0]->device)
+            return fail(IQHIP_ERR_INVALID, "iqhip_partition_create: all members must sit on one device");
+    }
+    {
+        std::vector<iqhip_engine *> sorted(members, members + nparts);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return fail(IQHIP_ERR_INVALID, "iqhip_partition_create: a member is listed twice");
+    }
+    iqhip_partition *g = new iqhip_partition;
+    g->device = members[0]->device;
+    g->nparts = nparts;
+    g->m.assign(members, members + nparts);
+    g->rate.assign((size_t)nparts, 1.0);
+    hipError_t s = hipSetDevice(g->device);
+    if (s == hipSuccess) s = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
+    if (s == hipSuccess) s = hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming);
+    for (int p = 0; p < nparts && s == hipSuccess; p++) {
+        hipEvent_t e = nullptr;
+        s = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (s == hipSuccess) g->ev.push_back(e);
+    }
+    if (s == hipSuccess) s = g->state.ensure(g->stream, 1);
+    if (s == hipSuccess) s = g->out.ensure(g->stream, (size_t)nparts);
+    if (s == hipSuccess) s = g->scale.ensure(g->stream, (size_t)nparts);
+    if (s != hipSuccess) {
+        iqhip_partition_destroy(g);
+        return fail(IQHIP_ERR_HIP, std::string("iqhip_partition_create: ") + hipGetErrorString(s));
+    }
+    *out = g;
+    return IQHIP_OK;
+}
+
+extern "C" void iqhip_partition_destroy(iqhip_partition *g) {
+    if (!g) return;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    g->table.release();
+    g->scale.release();
+    g->out.release();
+    g->state.release();
+    if (g->d_partials) hipFree(g->d_partials);
+    for (hipEvent_t e : g->ev) hipEventDestroy(e);
+    for (hipEvent_t e : g->tev) hipEventDestroy(e);
+    if (g->ev_done) hipEventDestroy(g->ev_done);
+    if (g->stream) hipStreamDestroy(g->stream);
+    delete g;
+}
+
+extern "C" int iqhip_partition_set_rates(iqhip_partition *g, const double *rate) {
+    if (!g || !rate) return fail(IQHIP_ERR_INVALID, "iqhip_partition_set_rates: null argument");
+    for (int p = 0; p < g->nparts; p++)
+        if (!(rate[p] > 0.0) || !std::isfinite(rate[p]))
+            return fail(IQHIP_ERR_INVALID, "iqhip_partition_set_rates: every rate must be finite and > 0");
+    g->rate.assign(rate, rate + g->nparts);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_newton_branch(iqhip_partition *g, double xguess, double x1, double x2, double xacc,
+                                             int max_steps, double *optx, double *d2l, int *nsteps, double *part_lnl) {
+    const char *what = "iqhip_partition_newton_branch";
+    int rc = newton_check_bounds(what, xguess, x1, x2, xacc, max_steps);
+    if (rc) return rc;
+    rc = use_group(g, what);
+    if (rc) return rc;
+    rc = thetas_ok(g, what);
+    if (rc) return rc;
+    g->launches = 0;
+    rc = refresh_table(g);
+    if (rc) return rc;
+    rc = wait_for_members(g);
+    if (rc) return rc;
+    NewtonState st;
+    rc = solve(g, xguess, x1, x2, xacc, max_steps, part_lnl != nullptr, &st);
+    // (whatever happened: the members wait for what the group did enqueue)
+    const int rc2 = members_wait(g);
+    if (rc) return rc;
+    if (rc2) return rc2;
+    rc = newton_status(st.status);
+    if (rc) return rc;
+    NewtonResult(st).store(optx, d2l, nsteps);
+    if (part_lnl) memcpy(part_lnl, g->out.h, sizeof(double) * (size_t)g->nparts);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_lnl_from_theta(iqhip_partition *g, double x, double *part_lnl) {
+    const char *what = "iqhip_partition_lnl_from_theta";
+    if (!part_lnl) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null argument");
+    if (!(x >= 0.0) || !std::isfinite(x)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": negative or non-finite branch length");
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    rc = thetas_ok(g, what);
+    if (rc) return rc;
+    g->launches = 0;
+    rc = refresh_table(g);
+    if (rc) return rc;
+    rc = wait_for_members(g);
+    if (rc) return rc;
+    rc = enqueue_part_lnl(g, nullptr, x);
+    const int rc2 = members_wait(g);
+    if (rc) return rc;
+    if (rc2) return rc2;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    memcpy(part_lnl, g->out.h, sizeof(double) * (size_t)g->nparts);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_traverse_lnl(iqhip_partition *g, const iqhip_node_op *ops, int nops, iqhip_branch_end a,
+                                            iqhip_branch_end b, double len, const double *scale, double *part_lnl) {
+    const char *what = "iqhip_partition_traverse_lnl";
+    if (!part_lnl) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null argument");
+    if (nops < 0 || (nops > 0 && !ops)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad ops array");
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    const int P = g->nparts;
+    for (int p = 0; scale && p < P; p++)
+        if (!(scale[p] > 0.0) || !std::isfinite(scale[p]))
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": every scale must be finite and > 0");
+    g->launches = 0;
+    std::vector<iqhip_node_op> mine(ops, ops + nops);
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        const double s = scale ? scale[p] : g->rate[p];
+        for (int k = 0; k < nops; k++) {
+            mine[k].left_len = ops[k].left_len * s;
+            mine[k].right_len = ops[k].right_len * s;
+        }
+        rc = submit_traverse(e, nops ? mine.data() : nullptr, nops, true, a, b, len * s);
+        if (rc) return rc;
+        if (e->d_result != e->d_result_own)   // caller-bound device result vector
+            HIPCHK(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double) * (size_t)(2 + nops), hipMemcpyDeviceToHost, e->stream));
+        DevBranch br;
+        rc = build_branch(e, a, b, len * s, -1, &br);   // (a lookup: the scale counters of the two ends)
+        if (rc) return rc;
+        g->scale.h[p] = PartScale{br.a_sc, br.b_sc, e->d_freq, e->nptn};
+    }
+    HIPCHK(hipSetDevice(g->device));
+    rc = wait_for_members(g);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(g->scale.d, g->scale.h, sizeof(PartScale) * (size_t)P, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(launch_part_scale_terms(g->stream, g->scale.d, P, g->out.d));
+    g->launches++;
+    HIPCHK(hipMemcpyAsync(g->out.h, g->out.d, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g->stream));
+    rc = members_wait(g);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g->stream));   // the one wait: every member's stream has drained behind its event
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        result_arrived(e);
+        double v = e->h_result[0];
+        if (isnan(v) || isinf(v)) {   // phylokernel.h:848-866, the rare slow path
+            rc = eng_repair_lnl(e, &v);
+            if (rc) return rc;
+        }
+        part_lnl[p] = v + g->out.h[p];
+    }
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_partition_timing(iqhip_partition *g, double *ms, int64_t *launches) {
+    if (!g) return fail(IQHIP_ERR_INVALID, "iqhip_debug_partition_timing: null group");
+    if (ms) { ms[0] = g->ms[0]; ms[1] = g->ms[1]; }
+    if (launches) *launches = g->launches;
+    return IQHIP_OK;
+}

@@ -225,7 +225,7 @@ extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, 
     DevBranch br;
     rc = build_branch(e, a, b, 0.0, -1, &br);
     if (rc) return rc;
-    set_theta_branch(e, br);
+    set_theta_branch(e, br, a, b);
     double *out = e->d_result + 2 + nops;
     HIPCHK(launch_newton(e, xguess, x1, x2, xacc, max_steps, out, &br, nops, (int)e->ntiles * e->lane_split));
     e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
@@ -380,7 +380,7 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
                          reinterpret_cast<const SweepStep *>(e->d_sweep_desc + bytes_ops), nsteps, x1, x2, xacc, max_steps,
                          diverge_frac * x2, e->d_sweep_posts.p, out));
     HIPCHK(launch_reduce(e, 0, (int)total_ops, nwaves));
-    set_theta_branch(e, hsteps[nsteps - 1].br);
+    set_theta_branch(e, hsteps[nsteps - 1].br, steps[nsteps - 1].a, steps[nsteps - 1].b);
     e->plan_cache.version = 0;
     const double enqueue_us = dbg ? watch.us() : 0.0;
     int rc = read_result(e, (int)(total_ops + 6 * (size_t)nsteps));
@@ -460,7 +460,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
         DevBranch br;
         rc = build_branch(e, st.a, st.b, 0.0, -1, &br);
         if (rc) return rc;
-        set_theta_branch(e, br);
+        set_theta_branch(e, br, st.a, st.b);
         NewtonSweepStep sw;
         sw.len_out = e->d_sweep_len.p + j;
         sw.rows_base = e->d_result + row;

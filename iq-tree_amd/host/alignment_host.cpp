@@ -54,6 +54,9 @@ void buildStateMap(int *map, SeqType seq_type, int state_unknown) {
         map[(int)'X'] = state_unknown;
         map[(int)'B'] = 20; map[(int)'Z'] = 21; map[(int)'J'] = 22;
         map[(int)'*'] = state_unknown; map[(int)'U'] = state_unknown;
+    } else if (seq_type == SEQ_OTHER) {   // binary (alignment.cpp:859-862)
+        map[(int)'0'] = 0;
+        map[(int)'1'] = 1;
     }
 }
 
@@ -68,8 +71,15 @@ void Alignment::readFile(const std::string &filename, const std::string &sequenc
 }
 
 void Alignment::readString(const std::string &content, const std::string &sequence_type) {
-    seq_names.clear();
     std::vector<std::string> sequences;
+    readSequences(content, seq_names, sequences);
+    buildPattern(sequences, sequence_type);
+}
+
+void Alignment::readSequences(const std::string &content, std::vector<std::string> &seq_names,
+                              std::vector<std::string> &sequences) {
+    seq_names.clear();
+    sequences.clear();
     std::istringstream in(content);
     std::string line;
     size_t first = content.find_first_not_of(" \t\r\n");
@@ -144,7 +154,6 @@ void Alignment::readString(const std::string &content, const std::string &sequen
                 throw std::runtime_error(e.str());
             }
     }
-    buildPattern(sequences, sequence_type);
 }
 
 void Alignment::buildPattern(const std::vector<std::string> &sequences, const std::string &sequence_type) {
@@ -169,12 +178,16 @@ void Alignment::buildPattern(const std::vector<std::string> &sequences, const st
         if (!gc) throw std::runtime_error("Unsupported genetic code " + sequence_type.substr(5));
         genetic_code = gc;
         seq_type = SEQ_CODON;
+    } else if (sequence_type == "BIN") {   // asked for by name only: detection never picks it
+        seq_type = SEQ_OTHER;
     } else if (!sequence_type.empty())
         throw std::runtime_error("Invalid sequence type " + sequence_type);
+    if (seq_type == SEQ_OTHER && sequence_type != "BIN") throw std::runtime_error("Unknown sequence type.");
     switch (seq_type) {
         case SEQ_DNA: num_states = 4; STATE_UNKNOWN = 18; break;       // alignment.cpp:470-472
         case SEQ_PROTEIN: num_states = 20; STATE_UNKNOWN = 23; break;
         case SEQ_CODON: num_states = 64; STATE_UNKNOWN = 64; break;
+        case SEQ_OTHER: num_states = 2; STATE_UNKNOWN = 2; break;      // binary
         default: throw std::runtime_error("Unknown sequence type.");
     }
     int char_to_state[256];

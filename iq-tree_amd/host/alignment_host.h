@@ -36,10 +36,15 @@ struct Pattern {
 class Alignment {
 public:
     // format by content: '>' starts FASTA, anything else is PHYLIP (sequential or interleaved).
-    // sequence_type: "" (detect DNA vs protein), "DNA", "AA", "CODON" or "CODON<ncbi table>"
+    // sequence_type: "" (detect DNA vs protein), "DNA", "AA", "CODON", "CODON<ncbi table>" or "BIN" (characters 0 / 1, two
+    // states, STATE_UNKNOWN = 2; never detected, only taken when named)
     void readFile(const std::string &filename, const std::string &sequence_type = "");
     void readString(const std::string &content, const std::string &sequence_type = "");
     void buildPattern(const std::vector<std::string> &sequences, const std::string &sequence_type);
+    // the file's names and raw sequences (upper case, one string of equal length per sequence), before any encoding: what a
+    // partition file cuts its sites from (supertree_host.h readPartitionRaxml)
+    static void readSequences(const std::string &content, std::vector<std::string> &seq_names,
+                              std::vector<std::string> &sequences);
 
     std::vector<std::string> seq_names;
     std::vector<Pattern> patterns;       // first-appearance order, as the reference

@@ -14,6 +14,7 @@
 #include "brent_host.h"
 #include "model_opt_host.h"
 #include "phylo_host.h"
+#include "supertree_host.h"
 #include "ufboot_splits.h"
 
 using namespace iqhost;
@@ -928,6 +929,100 @@ int iqhost_ufboot_consensus(const char **trees, int ntrees, const int64_t *weigh
         if (need) *need = (int)s.size() + 1;
         if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
     });
+}
+
+// ---- edge-linked partition models (supertree_host.h).  A member handle is a PhyloTree owned by the super tree: every
+// iqhost_* call above takes it, iqhost_destroy must not.
+int iqhost_super_create(void **out, const char *newick, const char **names, int nnames) {
+    *out = nullptr;
+    PhyloSuperTree *t = nullptr;
+    try {
+        t = new PhyloSuperTree();
+        std::vector<std::string> nm;
+        for (int i = 0; i < nnames; i++) nm.push_back(names[i]);
+        t->readTreeString(newick, nm);
+        *out = t;
+        return 0;
+    } catch (const std::exception &ex) {
+        g_host_err = ex.what();
+        delete t;
+        return 1;
+    }
+}
+void iqhost_super_destroy(void *h) { delete (PhyloSuperTree *)h; }
+int iqhost_super_add_partition(void *h, const char *name, void **member) {
+    IQHOST_TRY(*member = ((PhyloSuperTree *)h)->addPartition(name ? name : ""));
+}
+int iqhost_super_attach_engines(void *h, int device) { IQHOST_TRY(((PhyloSuperTree *)h)->attachEngines(device)); }
+int iqhost_super_num_parts(void *h) { return ((PhyloSuperTree *)h)->size(); }
+void *iqhost_super_group(void *h) { return ((PhyloSuperTree *)h)->group; }
+int iqhost_super_set_fixed_rates(void *h, int on) { IQHOST_TRY(((PhyloSuperTree *)h)->fixed_rates = on != 0); }
+int iqhost_super_set_rates(void *h, const double *rates) { IQHOST_TRY(((PhyloSuperTree *)h)->setRates(rates)); }
+int iqhost_super_get_rates(void *h, double *rates) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        for (int p = 0; p < t->size(); p++) rates[p] = t->part_rate[(size_t)p];
+    });
+}
+int iqhost_super_part_lnl(void *h, double *out) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        for (int p = 0; p < t->size(); p++) out[p] = t->cur_score[(size_t)p];
+    });
+}
+int iqhost_super_set_branch_bounds(void *h, double lo, double hi) { IQHOST_TRY(((PhyloSuperTree *)h)->setBranchBounds(lo, hi)); }
+int iqhost_super_compute_likelihood(void *h, double *lnl) { IQHOST_TRY(*lnl = ((PhyloSuperTree *)h)->computeLikelihood()); }
+int iqhost_super_optimize_one_branch(void *h, int a, int b, int clear_lh, int max_nr_step, double *new_len) {
+    IQHOST_TRY(*new_len = ((PhyloSuperTree *)h)->optimizeOneBranch(a, b, clear_lh != 0, max_nr_step));
+}
+int iqhost_super_optimize_all_branches(void *h, int iterations, double tolerance, int max_nr_step, double *lnl) {
+    IQHOST_TRY(*lnl = ((PhyloSuperTree *)h)->optimizeAllBranches(iterations, tolerance, max_nr_step));
+}
+// evals: Brent evaluations per member (nparts); *rounds: lockstep rounds = group traversals of this call
+int iqhost_super_optimize_gene_rates(void *h, double gradient_epsilon, double *lnl, int *evals, int *rounds) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        *lnl = t->optimizeGeneRate(gradient_epsilon);
+        if (evals)
+            for (int p = 0; p < t->size(); p++) evals[p] = t->gene_rate_evals[(size_t)p];
+        if (rounds) *rounds = t->gene_rate_rounds;
+    });
+}
+int iqhost_super_optimize_parameters(void *h, int fixed_len, double logl_epsilon, double gradient_epsilon, double *lnl) {
+    IQHOST_TRY(*lnl = ((PhyloSuperTree *)h)->optimizeParameters(fixed_len != 0, logl_epsilon, gradient_epsilon));
+}
+int iqhost_super_newton_branch(void *h, int a, int b, double xguess, double x1, double x2, double xacc, int max_steps,
+                               double *optx, double *d2l, int *nsteps, double *part_lnl) {
+    IQHOST_TRY(((PhyloSuperTree *)h)->partitionNewtonBranch(a, b, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps, part_lnl));
+}
+int iqhost_super_branch_length(void *h, int a, int b, double *len) {
+    IQHOST_TRY(*len = nei(&((PhyloSuperTree *)h)->super, a, b)->length);
+}
+// the branches in optimizeAllBranches' order; returns their number
+int iqhost_super_branch_order(void *h, int *n1, int *n2, int cap) {
+    try {
+        std::vector<int> a, b;
+        ((PhyloSuperTree *)h)->branchOrder(a, b);
+        for (size_t k = 0; k < a.size() && (int)k < cap; k++) { n1[k] = a[k]; n2[k] = b[k]; }
+        return (int)a.size();
+    } catch (const std::exception &ex) {
+        g_host_err = ex.what();
+        return -1;
+    }
+}
+int iqhost_super_tree_string(void *h, char *out, int cap) {
+    std::string s = ((PhyloSuperTree *)h)->getTreeString();
+    if ((int)s.size() + 1 > cap) return (int)s.size() + 1;
+    memcpy(out, s.c_str(), s.size() + 1);
+    return 0;
+}
+// out[3] = joint solves, group traversals, diverged-Newton resets so far
+int iqhost_super_counters(void *h, long *out) {
+    PhyloSuperTree *t = (PhyloSuperTree *)h;
+    out[0] = t->num_group_solves;
+    out[1] = t->num_group_traversals;
+    out[2] = t->num_diverged;
+    return 0;
 }
 
 }  // extern "C"

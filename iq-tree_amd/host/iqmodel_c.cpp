@@ -2,11 +2,14 @@
 // for ctypes; test and tool plumbing, not part of the drop-in boundary.
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "alignment_host.h"
 #include "model_host.h"
+#include "partition_spec.h"
+#include "supertree_host.h"
 
 using namespace iqhost;
 
@@ -168,6 +171,45 @@ int iqmodel_build_mixture(void *aln, const char *model_string, double *p_invar, 
         memcpy(class_rates, mi.class_rates.data(), sizeof(double) * M);
         memcpy(class_weights, mi.class_weights.data(), sizeof(double) * M);
     });
+}
+
+// ---- partition files (partition_spec.h, supertree_host.h) ----------------------------------------------------------------
+// the parser alone: *out = a list of PartitionSpec for iqpart_spec_*; nsite = sites of the alignment the positions refer to
+int iqpart_spec_parse(void **out, const char *text, int nsite) {
+    *out = nullptr;
+    IQM_TRY(*out = new std::vector<PartitionSpec>(parsePartitionFile(text ? text : "", nsite)));
+}
+void iqpart_spec_free(void *h) { delete (std::vector<PartitionSpec> *)h; }
+int iqpart_spec_count(void *h) { return (int)((std::vector<PartitionSpec> *)h)->size(); }
+const char *iqpart_spec_model(void *h, int k) { return (*(std::vector<PartitionSpec> *)h)[(size_t)k].model.c_str(); }
+const char *iqpart_spec_name(void *h, int k) { return (*(std::vector<PartitionSpec> *)h)[(size_t)k].name.c_str(); }
+int iqpart_spec_nsites(void *h, int k) { return (int)(*(std::vector<PartitionSpec> *)h)[(size_t)k].sites.size(); }
+int iqpart_spec_sites(void *h, int k, int *out) {
+    IQM_TRY({
+        const std::vector<int> &v = (*(std::vector<PartitionSpec> *)h).at((size_t)k).sites;
+        for (size_t i = 0; i < v.size(); i++) out[i] = v[i];
+    });
+}
+// the whole reader: one alignment (file or content) + one partition file (file or content) -> a list of PartitionInput
+int iqpart_read(void **out, const char *aln_file, const char *aln_content, const char *part_file, const char *part_content) {
+    *out = nullptr;
+    IQM_TRY({
+        std::vector<std::string> names;
+        std::unique_ptr<std::vector<PartitionInput>> parts(new std::vector<PartitionInput>());
+        if (aln_file && part_file) readPartitionRaxml(aln_file, part_file, names, *parts);
+        else if (aln_content && part_content) readPartitionStrings(aln_content, part_content, names, *parts);
+        else throw std::runtime_error("iqpart_read: give both files or both contents");
+        *out = parts.release();
+    });
+}
+void iqpart_free(void *h) { delete (std::vector<PartitionInput> *)h; }
+int iqpart_count(void *h) { return (int)((std::vector<PartitionInput> *)h)->size(); }
+const char *iqpart_model(void *h, int k) { return (*(std::vector<PartitionInput> *)h)[(size_t)k].model.c_str(); }
+const char *iqpart_name(void *h, int k) { return (*(std::vector<PartitionInput> *)h)[(size_t)k].name.c_str(); }
+// a copy of partition k's alignment as an iqaln_* handle of its own (iqaln_destroy frees it)
+int iqpart_alignment(void *h, int k, void **aln) {
+    *aln = nullptr;
+    IQM_TRY(*aln = new Alignment((*(std::vector<PartitionInput> *)h).at((size_t)k).aln));
 }
 
 }  // extern "C"

@@ -504,7 +504,7 @@ ModelSpec parseModelString(const std::string &s, bool allow_missing) {
 int numRateParams(const ModelSpec &spec) {
     if (!spec.mix_classes.empty()) return -1;
     const std::string name = upper(spec.name);
-    if (name == "JC" || name == "JC69" || name == "F81" || name == "POISSON") return 0;
+    if (name == "JC" || name == "JC69" || name == "F81" || name == "POISSON" || name == "JC2" || name == "GTR2") return 0;
     if (name == "K80" || name == "K2P" || name == "HKY" || name == "HKY85") return 1;
     if (name == "TN" || name == "TRN" || name == "TN93") return 2;
     if (name == "GTR") return 5;
@@ -655,6 +655,11 @@ void buildModel(const ModelSpec &spec, const Alignment &aln, ModelInputs &out) {
             }
         }
         if (ft == ModelSpec::FREQ_DEFAULT) ft = ModelSpec::FREQ_EMPIRICAL;
+    } else if (aln.seq_type == SEQ_OTHER && n == 2) {   // binary data (model/modelbin.cpp): JC2 equal, GTR2 free frequencies
+        need(0);
+        if (name == "JC2") { if (ft == ModelSpec::FREQ_DEFAULT) ft = ModelSpec::FREQ_EQUAL; }
+        else if (name != "GTR2") throw std::runtime_error("Unknown binary model " + spec.name);
+        sym(0, 1, 1.0);
     } else
         throw std::runtime_error("unsupported data type");
 

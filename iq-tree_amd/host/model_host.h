@@ -43,7 +43,7 @@ const char *geneticCode(int ncbi_table);
 // A parsed `-m` string, e.g. "GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}",
 // "HKY{2.0}+G4{0.5}", "JC", "POISSON+G4{1.0}", "GY{2.0,0.5}+F1X4", "file.paml+G4{0.9}", "...+ASC".
 struct ModelSpec {
-    std::string name;                 // JC F81 K80 HKY TN GTR POISSON GY <paml file>
+    std::string name;                 // JC F81 K80 HKY TN GTR POISSON GY JC2 GTR2 (binary data) <paml file>
     std::vector<double> params;       // rate parameters in the reference's order
     enum FreqType { FREQ_DEFAULT, FREQ_EQUAL, FREQ_USER, FREQ_EMPIRICAL, FREQ_CODON_1x4, FREQ_CODON_3x4 } freq_type = FREQ_DEFAULT;
     std::vector<double> user_freq;

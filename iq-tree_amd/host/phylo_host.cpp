@@ -699,6 +699,25 @@ double PhyloTree::computeLikelihoodFromBufferHIP() {
     return iqhip_adapter::computeLikelihoodFromBuffer<MirrorPolicy>(this);
 }
 
+void PhyloTree::collectBranchPlan(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_node_op> &ops,
+                                  std::vector<int> &len_branch, iqhip_branch_end &a, iqhip_branch_end &b, int &root_branch) {
+    PhyloNode *node;
+    PhyloNeighbor *node_branch;
+    MirrorPolicy::ensureBuffers(this);
+    iqhip_adapter::orientBranch<MirrorPolicy>(dad_branch, dad, node_branch, node);
+    MirrorPolicy::Plan plan;
+    if ((dad_branch->partial_lh_computed & 1) == 0) iqhip_adapter::collectPlan<MirrorPolicy>(this, dad_branch, dad, plan);
+    if ((node_branch->partial_lh_computed & 1) == 0) iqhip_adapter::collectPlan<MirrorPolicy>(this, node_branch, node, plan);
+    pushInputs();
+    ops = plan.ops;
+    len_branch.assign(2 * plan.size(), -1);
+    for (size_t q = 0; q < len_branch.size(); q++)
+        if (plan.len_nb[q]) len_branch[q] = plan.len_nb[q]->id;
+    a = branchEnd(node_branch);
+    b = branchEnd(dad_branch);
+    root_branch = dad_branch->id;
+}
+
 // =========================================================================================
 // callers
 // =========================================================================================

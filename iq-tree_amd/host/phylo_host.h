@@ -430,8 +430,18 @@ public:
     long num_partial_lh_computations = 0;  // phylokernel.h:85 (counts leaf visits too)
     long num_submissions = 0;
 
+    // ---- partition models (supertree_host.h) ----------------------------------------------------------------------
+    // What computeLikelihoodBranch(dad_branch, dad) would submit, WITHOUT submitting it: the pending node updates of both
+    // ends (their flags go up, as if they had run), len_branch[2k], [2k+1] = the branch ids whose lengths are op k's
+    // left_len / right_len (-1: the zero-length hand-over inside a multifurcating node), the two ends of the branch and
+    // its id.  The caller runs the ops itself (iqhip_partition_traverse_lnl); the lh_scale_factor of the planned vectors
+    // is NOT maintained on that route, so the caller ends with clearAllPartialLH().
+    void collectBranchPlan(PhyloNeighbor *dad_branch, PhyloNode *dad, std::vector<iqhip_node_op> &ops,
+                           std::vector<int> &len_branch, iqhip_branch_end &a, iqhip_branch_end &b, int &root_branch);
+
 private:
     friend struct MirrorPolicy;
+    friend class PhyloSuperTree;
     ComputePartialLikelihoodType computePartialLikelihoodPointer = nullptr;
     ComputeLikelihoodBranchType computeLikelihoodBranchPointer = nullptr;
     ComputeLikelihoodFromBufferType computeLikelihoodFromBufferPointer = nullptr;

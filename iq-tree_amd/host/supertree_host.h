@@ -1,0 +1,110 @@
+// supertree_host.h -- host mirror of the edge-linked partition model: the slice of PhyloSuperTreePlen /
+// PartitionModelPlen (phylosupertreeplen.cpp) that sits on the likelihood kernels, on top of a partition group of engines
+// (include/iqhip.h, iqhip_partition_*).
+//
+// P PhyloTrees of identical topology (copyTopology of the super tree), each with its own alignment, model and engine.
+// Every member runs the FULL super-tree topology: a taxon without data in a partition stays in its alignment as an
+// all-unknown row (the reference drops it with removeGappySeq and links the trees with linkTrees / mapTrees; the
+// likelihood is the same, and a branch with only such taxa behind it has df = ddf = 0 exactly).  Member p's branch
+// lengths are the super tree's times part_rate[p] -- written by this class whenever either changes.
+//
+//   computeLikelihood      PhyloSuperTreePlen::computeFunction (:474-511): the sum of the members' likelihoods
+//   optimizeOneBranch      :425-472 over PhyloTree::optimizeOneBranch (phylotree.cpp:2148-2192): per member the pending
+//                          partials and theta through its own computeLikelihoodDerv path, then ONE
+//                          iqhip_partition_newton_branch on sum_p r_p df_p(r_p x); the diverged-Newton reset
+//                          (phylotree.cpp:2167-2176) on the summed lnL through iqhip_partition_lnl_from_theta
+//   optimizeAllBranches    :415-423 over PhyloTree::optimizeAllBranches (phylotree.cpp:2232-2332): the reference's
+//                          branch order and stopping rule on the super tree
+//   optimizeGeneRate       PartitionModelPlen::optimizeGeneRate (:219-254): the P optimizeTreeLengthScaling Brent
+//                          searches (phylotree.cpp:2103-2118) in lockstep (BrentMachine), one
+//                          iqhip_partition_traverse_lnl per round, then the normalisation
+//   optimizeParameters     PartitionModelPlen::optimizeParameters (:107-200).  DEVIATION: the per-partition
+//                          substitution parameters are taken as given (no optimizeParametersOnly, no linked alpha):
+//                          rates and branch lengths only
+#pragma once
+#include <string>
+#include <vector>
+
+#include "alignment_host.h"
+#include "model_host.h"
+#include "partition_spec.h"
+#include "phylo_host.h"
+
+struct iqhip_partition;
+
+namespace iqhost {
+
+// One partition as read from a partition file: the sites cut from the one alignment (extractSites), pattern-compressed
+// anew, and the model its string names.  EVERY taxon is kept; one without data in the partition is an all-unknown row
+// (the reference drops it with removeGappySeq; the likelihood is the same).
+struct PartitionInput {
+    std::string name, model;
+    Alignment aln;
+    ModelInputs inputs;
+};
+// the data type a partition's model string asks for: "DNA" (JC F81 K80 HKY TN GTR), "CODON" (GY), "BIN" (JC2 GTR2), else "AA"
+std::string partitionSequenceType(const std::string &model);
+// RAxML-style partition file (partition_spec.h; readPartitionRaxml, phylosupertree.cpp:150-266) over ONE alignment file
+// (PHYLIP or FASTA, its columns of whatever data types the models name).  Mixtures and +ASC are refused: such members
+// cannot join a partition group.
+void readPartitionRaxml(const std::string &aln_file, const std::string &part_file, std::vector<std::string> &seq_names,
+                        std::vector<PartitionInput> &parts);
+void readPartitionStrings(const std::string &aln_content, const std::string &part_content, std::vector<std::string> &seq_names,
+                          std::vector<PartitionInput> &parts);
+
+class PhyloSuperTree {
+public:
+    PhyloSuperTree();
+    ~PhyloSuperTree();
+    PhyloSuperTree(const PhyloSuperTree &) = delete;
+    PhyloSuperTree &operator=(const PhyloSuperTree &) = delete;
+
+    void readTreeString(const std::string &newick, const std::vector<std::string> &names);
+    std::string getTreeString() const { return super.getTreeString(); }
+    // a new member of the super tree's topology; the caller gives it its alignment and model (setAlignment, setModel)
+    PhyloTree *addPartition(const std::string &name);
+    PhyloTree *addPartition(const PartitionInput &in);   // ... with the alignment and model of a partition file's entry
+    // one engine per member on `device` + the group; member lengths = rate x super lengths
+    void attachEngines(int device);
+
+    PhyloTree super;                      // topology and lengths; it never gets an engine
+    std::vector<PhyloTree *> parts;
+    std::vector<std::string> part_name;
+    std::vector<double> part_rate;        // 1 after addPartition
+    std::vector<double> cur_score;        // part_info[part].cur_score
+    bool fixed_rates = true;              // -q; false: -spp
+    iqhip_partition *group = nullptr;
+    double min_branch_length = 1e-6, max_branch_length = 100.0;
+    int num_param_iterations = 100;       // params.num_param_iterations
+
+    int size() const { return (int)parts.size(); }
+    void setRates(const double *rates);   // also rescales the members' lengths
+    double computeLikelihood();
+    // returns the accepted length of the super-tree branch (node ids a, b)
+    double optimizeOneBranch(int a, int b, bool clearLH = true, int maxNRStep = 100);
+    double optimizeAllBranches(int my_iterations = 100, double tolerance = 0.001, int maxNRStep = 100);
+    double optimizeGeneRate(double gradient_epsilon);
+    double optimizeParameters(bool fixed_len, double logl_epsilon, double gradient_epsilon);
+    // the thin call: theta of (a, b) on every member, then iqhip_partition_newton_branch with these arguments
+    void partitionNewtonBranch(int a, int b, double xguess, double x1, double x2, double xacc, int max_steps, double *optx,
+                               double *d2l, int *nsteps, double *part_lnl);
+    double totalNSite() const;
+    void setBranchBounds(double lo, double hi);   // of the super tree and every member
+    // the branches in the order optimizeAllBranches visits them (node ids)
+    void branchOrder(std::vector<int> &n1, std::vector<int> &n2);
+
+    // counters (tests, bench): joint solves, group traversals, diverged-Newton resets; of the last optimizeGeneRate: Brent
+    // evaluations per member and lockstep rounds
+    long num_group_solves = 0, num_group_traversals = 0, num_diverged = 0;
+    std::vector<int> gene_rate_evals;
+    int gene_rate_rounds = 0;
+
+private:
+    void needGroup() const;
+    void pushLengths();                   // member lengths = rate x super lengths; all member vectors dropped
+    void prepareBranch(int a, int b);     // current_it + pending partials + theta of (a, b) on every member
+    void hip(int rc, const char *what) const;
+    double sumScores() const;
+};
+
+}  // namespace iqhost
