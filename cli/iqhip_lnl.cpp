@@ -77,7 +77,14 @@
 // with the substitution parameters as given (-blfix: fixed branch lengths too).  It prints "Partition-specific rates:  r1
 // r2 ..." (-spp only), one line "Partition <name>: <nsite> sites, <nptn> patterns, lnL <value>" per partition and "Optimal
 // log-likelihood: <sum>", and writes <prefix>.treefile with the super tree's lengths.  -q / -spp exclude -m, -alrt, -z, -bb,
-// -mldist, -pars*, -bionjtree, -emrates, -mixweights and -optmodel.
+// -mldist, -pars*, -bionjtree, -emrates, -mixweights, -optmodel and -lmap.
+// With -lmap N [-wql] [-seed S] it runs likelihood mapping (PhyloTree::doLikelihoodMapping) under the model after the tree's
+// lnL and branch optimisation: N quartets drawn from -seed (N = 0 or N >= C(n,4): every unique quartet), the three trees of
+// each optimised on the device in one call.  It prints "Computing N quartet likelihoods", "Quartets in region k: .." for
+// the seven regions and the three summary lines (fully resolved = regions 1-3, partly resolved = 4-6, unresolved = 7, with
+// percentages); -wql writes <prefix>.lmap.quartetlh in the reference's format: "SeqIDs lh1 lh2 lh3 weight1 weight2 weight3"
+// tab-separated, ids 1-based as (a,b,c,d).  4-state data; refused for mixtures, +ASC and with -q / -spp.  No cluster file,
+// no SVG / EPS plot.
 // There is no CPU path: without a GPU it fails with the engine's error.
 #include <math.h>
 #include <stdio.h>
@@ -261,6 +268,7 @@ static void usage() {
             "usage: iqhip_lnl -s <alignment> -te <newick file> -m <model> [-st DNA|AA|CODON[n]] [-pre <prefix>]\n"
             "                 [-blfix] [-wsl] [-dev <gpu>] [-reps <n>] [-nolhmemsave] [-alrt <n>] [-lbp <n>] [-seed <s>]\n"
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
+            "                 [-lmap <n quartets, 0 = all> [-wql]]\n"
             "                 [-mixweights] [-optmodel] [-bb <n> [-beps <e>] [-z <tree set file>] [-wbt]]\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
@@ -281,6 +289,8 @@ int main(int argc, char **argv) {
     unsigned long long seed = 1;
     std::string treeset_file, mldist_file, part_file;
     bool part_proportional = false;
+    long long lmap = -1;   // -lmap <n>: likelihood mapping over n drawn quartets (0: all unique quartets)
+    bool wql = false;
     int zb = 0, sprrad = 0, bb = 0;
     double beps = 0.5;
     bool wbt = false;
@@ -318,6 +328,11 @@ int main(int argc, char **argv) {
         else if (a == "-wsr") wsr = true;
         else if (a == "-mixweights") mixweights = true;
         else if (a == "-optmodel") optmodel = true;
+        else if (a == "-lmap") {
+            lmap = atoll(next().c_str());
+            if (lmap < 0) { usage(); return 2; }
+        }
+        else if (a == "-wql") wql = true;
         else if (a == "-q" || a == "-spp") {
             if (!part_file.empty()) { usage(); return 2; }
             part_file = next();
@@ -334,7 +349,7 @@ int main(int argc, char **argv) {
     if (!part_file.empty()) {
         const char *with = !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
                            : !mldist_file.empty() ? "-mldist" : pars || parstree || sprrad > 0 ? "-pars / -parstree / -sprrad"
-                           : bionjtree ? "-bionjtree" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : nullptr;
+                           : bionjtree ? "-bionjtree" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : lmap >= 0 ? "-lmap" : nullptr;
         if (with) {
             fprintf(stderr, "error: -q / -spp cannot be combined with %s (the models come from the partition file; the partition model evaluates a fixed topology)\n", with);
             return 2;
@@ -355,6 +370,7 @@ int main(int argc, char **argv) {
     if (sprrad > 0 && !parstree && !pars) { usage(); return 2; }
     if (bb < 0 || !(beps >= 0.0) || (bb == 0 && wbt)) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1 && bb == 0) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
+    if (wql && lmap < 0) { usage(); return 2; }
     if (alrt > 0 || lbp > 0 || bb > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
         Alignment aln;
@@ -389,6 +405,8 @@ int main(int argc, char **argv) {
         if (mixture && (emrates || wsr)) throw std::runtime_error("-emrates and -wsr are not available for mixture models");
         if (mixture && spec.ascertainment) throw std::runtime_error("Mixture model +ASC is not supported yet");
         if (mixture && !mldist_file.empty()) throw std::runtime_error("-mldist and -bionjtree are not available for mixture models");
+        if (lmap >= 0 && (mixture || spec.ascertainment)) throw std::runtime_error("-lmap is not available for mixture models and +ASC");
+        if (lmap >= 0 && aln.num_states != 4) throw std::runtime_error("-lmap: 4-state data only");
         if (spec.ascertainment) {
             const int k = aln.appendUnobservedConstPatterns();
             printf("Ascertainment bias correction: %d unobservable constant patterns\n", k);
@@ -629,6 +647,40 @@ int main(int argc, char **argv) {
             out << "rates";
             for (double r : mi.rates) { snprintf(buf, sizeof buf, " %.17g", r); out << buf; }
             out << "\ntree " << tree.getTreeString() << "\n";
+        }
+        if (lmap >= 0) {   // likelihood mapping (doLikelihoodMapping, quartet.cpp:1340-1505), under the model and not the tree
+            const int nseq = aln.getNSeq();
+            const long long all = (long long)lmap::numQuartets(nseq);
+            const long long nq = (lmap == 0 || lmap >= all) ? all : lmap;
+            std::vector<double> const_invar;
+            if (mi.p_invar > 0.0) {
+                for (int x = 0; x < 4; x++) const_invar.push_back(mi.p_invar * mi.state_freq[(size_t)x]);
+                const_invar.push_back(mi.p_invar);
+            }
+            printf("Computing %lld quartet likelihoods\n", nq);
+            PhyloTree::LmapResult r;
+            auto t0 = std::chrono::steady_clock::now();
+            tree.doLikelihoodMapping(lmap, seed, r, const_invar.empty() ? nullptr : const_invar.data());
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("Likelihood mapping of %lld quartets: %.4f s\n", nq, sec);
+            for (int k = 0; k < 7; k++) printf("Quartets in region %d: %lld\n", k + 1, (long long)r.areacount[k]);
+            const long long resolved = r.areacount[0] + r.areacount[1] + r.areacount[2];
+            const long long partly = r.areacount[3] + r.areacount[4] + r.areacount[5];
+            const long long unresolved = r.areacount[6], total = resolved + partly + unresolved;
+            printf("Number of fully resolved  quartets: %lld (%g%%)\n", resolved, 100.0 * resolved / total);
+            printf("Number of partly resolved quartets: %lld (%g%%)\n", partly, 100.0 * partly / total);
+            printf("Number of unresolved      quartets: %lld (%g%%)\n", unresolved, 100.0 * unresolved / total);
+            if (wql) {   // quartet.cpp:1455-1467: 1-based ids, the stream's default number format
+                const std::string name = prefix + ".lmap.quartetlh";
+                std::ofstream out(name.c_str());
+                if (!out) throw std::runtime_error("cannot write " + name);
+                out << "SeqIDs\tlh1\tlh2\tlh3\tweight1\tweight2\tweight3" << std::endl;
+                for (const lmap::QuartetInfo &q : r.info)
+                    out << "(" << q.seqID[0] + 1 << "," << q.seqID[1] + 1 << "," << q.seqID[2] + 1 << "," << q.seqID[3] + 1 << ")"
+                        << "\t" << q.logl[0] << "\t" << q.logl[1] << "\t" << q.logl[2] << "\t" << q.qweight[0] << "\t"
+                        << q.qweight[1] << "\t" << q.qweight[2] << std::endl;
+                printf("likelihood mapping results written to %s\n", name.c_str());
+            }
         }
         if (wsr) {
             tree.clearAllPartialLH();

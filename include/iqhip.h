@@ -625,6 +625,64 @@ int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double 
                          double *dist, double *d2l, int32_t *nsteps);
 int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms);
 
+/* ---- Likelihood mapping (-lmap; PhyloTree::computeQuartetLikelihoods, quartet.cpp:676-1152): for every quartet (a, b, c, d)
+ * of taxa the maximised log-likelihoods of its three trees, from what is resident in any plain 4-state engine: the state
+ * rows and ptn_freq of iqhip_set_alignment, the eigen-system, rates, proportions and tip rows of iqhip_set_model.
+ * quartets: 4 * nq taxon ids, four distinct ones per quartet, in the caller's order (never sorted).
+ * iqhip_quartet_cells: the quartet's columns collapsed.  cells[q * 256 + ((s0 * 4 + s1) * 4 + s2) * 4 + s3] = the sum of
+ *   ptn_freq over the patterns that show the unambiguous states (s0, s1, s2, s3) in the four taxa; nother[q] = the number of
+ *   all other patterns with a frequency > 0 (an ambiguity code, a gap or STATE_UNKNOWN among the four states).  This is what
+ *   the reference gets by re-compressing the sub-alignment (extractSubAlignment, alignment.cpp:1892-1935).  Integer-valued
+ *   frequencies give exact sums, the same bits on every run.
+ * iqhip_quartet_likelihoods: per quartet and topology k = 0, 1, 2 the tree (p0, p1, (p2, p3)) with p_j = quartet[qc[4 k + j]],
+ *   qc = {0,1,2,3, 0,2,1,3, 0,3,1,2} (quartet.cpp:925), i.e. 12|34, 13|24, 14|23.  Its five branches are numbered
+ *     0 .. 3 = the pendant branch of p0 .. p3, 4 = the internal branch;
+ *   len[k][j] is the optimised length of branch j.
+ *   Starting lengths: fixNegativeBranch(true) (phylotree.cpp:2654-2694): Fitch on the four leaves over the parsimony-
+ *     informative columns (Alignment::isInformative on the four states: an ambiguity code counts towards every state it allows,
+ *     STATE_UNKNOWN towards none; in Fitch an ambiguity code is its set of states and STATE_UNKNOWN the full set),
+ *     branch_subst = the weighted number of columns whose two Fitch sets across the branch are disjoint, length =
+ *     (branch_subst > 0 ? branch_subst : 1) / nsite with nsite = the sum of ALL pattern frequencies of the engine, then the JC
+ *     correction -log(1 - z length) / z, z = 4/3, where its argument is positive, and the lower bound x1.
+ *   optimizeAllBranches(iterations, tolerance) (phylotree.cpp:2252-2332): the initial lnL on branch 2; up to `iterations`
+ *     sweeps over the branches in the TRAVERSAL TABLE order {2, 3, 4, 0, 1} -- computeBestTraversal for the Newick string
+ *     above: the farthest leaf from p0 is p2, the pre-order from p2 takes neighbours by ascending edge-count height, so p2's
+ *     own branch, p3's, the internal one, then p0's and p1's; it depends on neither the lengths nor the data.  Per branch
+ *     optimizeOneBranch: minimizeNewton(x1, current, x2, xacc, max_steps) with the update rule of iqhip_newton_branch, then
+ *     the diverged-solve rule: optx > diverge_frac * x2 keeps the better of the lnL at optx and at the old length.  After a
+ *     sweep the lnL on the last branch (1); a lnL below the previous one restores the lengths saved before the sweep and
+ *     returns the lnL recomputed there (on branch 2); old <= new <= old + tolerance stops.  nsweeps = sweeps run, neval =
+ *     derivative evaluations of all its solves, status = 0 or minimizeNewton's error (2 non-finite derivative, 3 step limit)
+ *     of the first solve that hit one -- the call then returns IQHIP_ERR_INVALID with the results filled.
+ *   The function is the engine's (K1-K9 on four leaves): per category the cherry vectors U^-1 ((E tip) o (E tip)), for a
+ *     pendant branch the far side U^-1 ((E tip) o (E_uv partial)), lh = invar + sum_c prop_c sum_i exp(eval_i rate_c t) theta_i,
+ *     lnL = sum w log|lh|, df and ddf as phylokernel.h:599-646.  A leaf of STATE_UNKNOWN contributes exactly 1.0 (the K2 rule).
+ *     No scaling: with four leaves and lengths in [1e-6, 100] no vector gets near 2^-256.
+ *   const_invar: NULL (no +I) or 5 values, p_inv * pi[x] for x < 4 and [4] = p_inv.  The invariant term of a column follows
+ *     Alignment::computeConst on its four states: the states allowed by all four; exactly one common state x gives
+ *     const_invar[x], all four (a column of STATE_UNKNOWN only) const_invar[4], anything else 0.
+ * Supported: plain 4-state engines (iqhip_set_model) with any category count they accept, +G and +R alike.
+ *   IQHIP_ERR_UNSUPPORTED: 20- and 64-state engines, embedded state counts, mixtures, +ASC, sharded engines and communicator
+ *   ranks.  IQHIP_ERR_INVALID: planning-only engines, a call before the alignment or the model is set, null arguments, nq < 1,
+ *   a taxon outside [0, ntaxa) or twice in a quartet, x1 > x2, max_steps < 1, iterations < 1, tolerance < 0 or NaN, a pattern
+ *   frequency that is not a non-negative integer below 2^53.  Everything is validated on the host before the first launch.
+ * The quartets run in chunks whose cell tables and other-lists (nptn entries each, the worst case) fit 64 MB;
+ *   IQHIP_QUARTET_CHUNK (read per call) overrides the quartets per chunk.  No result depends on the chunking.
+ * iqhip_debug_quartet_timing: with iqhip_timing_enable, the device time (HIP events, milliseconds) the last
+ *   iqhip_quartet_likelihoods call spent in its cell launches and in its solve launches. */
+typedef struct iqhip_quartet_result {   /* per quartet */
+    double  logl[3];        /* topology k = 0,1,2: 12|34, 13|24, 14|23 in quartet order */
+    double  len[3][5];      /* optimised lengths, branch numbers as above */
+    int32_t nsweeps[3], neval[3], status[3], _pad;
+} iqhip_quartet_result; /* 184 bytes */
+int iqhip_quartet_cells(iqhip_engine *e, const int32_t *quartets /* 4*nq */, int nq,
+                        double *cells /* nq*256 */, int32_t *nother /* nq */);
+int iqhip_quartet_likelihoods(iqhip_engine *e, const int32_t *quartets, int nq,
+                              const double *const_invar /* 5 or NULL: p_inv*pi[x], x<4; [4] = p_inv */,
+                              double x1, double x2, double xacc, int max_steps, double diverge_frac,
+                              int iterations, double tolerance, iqhip_quartet_result *results);
+int iqhip_debug_quartet_timing(iqhip_engine *e, double *cells_ms, double *solve_ms);
+
 /* ---- BIONJ (PhyloTree::computeBioNJ, phylotree.cpp:2619-2635; BioNj::create, bionj.h) -- the tree the reference builds from
  * the distance matrix above before any search.  The engine supplies the device and the stream only: n is free and need not
  * be the engine's taxon count, and no model or alignment has to be set.

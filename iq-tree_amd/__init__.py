@@ -43,6 +43,7 @@ IQHIP_SYMBOLS = [
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
     "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
     "iqhip_pair_counts", "iqhip_pair_distances", "iqhip_debug_pair_timing",
+    "iqhip_quartet_cells", "iqhip_quartet_likelihoods", "iqhip_debug_quartet_timing",
     "iqhip_pars_init", "iqhip_pars_update", "iqhip_pars_branch_scores", "iqhip_pars_insert_scores", "iqhip_pars_fetch", "iqhip_pars_shape",
     "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
     "iqhip_pars_spr_scan", "iqhip_debug_pars_spr_check", "iqhip_debug_pars_spr_timing",
@@ -243,6 +244,10 @@ def libiqhip():
     lib.iqhip_pair_counts.argtypes = [vp, i32p, C.c_int, dp]
     lib.iqhip_pair_distances.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, i32p]
     lib.iqhip_debug_pair_timing.argtypes = [vp, dp, dp]
+    lib.iqhip_quartet_cells.argtypes = [vp, i32p, C.c_int, dp, i32p]
+    lib.iqhip_quartet_likelihoods.argtypes = [vp, i32p, C.c_int, dp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double,
+                                              C.c_int, C.c_double, vp]
+    lib.iqhip_debug_quartet_timing.argtypes = [vp, dp, dp]
     u8p, u32p, i64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)
     lib.iqhip_pars_init.argtypes = [vp, u8p, C.c_int, i64p]
     lib.iqhip_pars_update.argtypes = [vp, C.POINTER(ParsOp), C.c_int]
@@ -343,6 +348,16 @@ def libiqhost():
     lib.iqhost_optimize_parsimony_spr.argtypes = [vp, C.c_int, C.c_int, ipp, ipp, C.c_int, ipp]
     lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
     lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
+    i32q, i64q = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    lib.iqhost_quartet_cells.argtypes = [vp, i32q, C.c_int, dp, i32q]
+    lib.iqhost_quartet_likelihoods.argtypes = [vp, i32q, C.c_int, C.c_int, C.c_double, dp, vp]
+    lib.iqhost_likelihood_mapping.argtypes = [vp, C.c_int64, C.c_uint64, dp, C.c_int64, i64q, i32q, dp, dp, i32q, i32q, i64q,
+                                              i64q]
+    lib.iqhost_lmap_region.argtypes = [dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.iqhost_lmap_num_quartets.argtypes = [C.c_int]
+    lib.iqhost_lmap_num_quartets.restype = C.c_int64
+    lib.iqhost_lmap_all_quartets.argtypes = [C.c_int, i32q]
+    lib.iqhost_lmap_draw_quartets.argtypes = [C.c_int, C.c_int64, C.c_uint64, i32q]
     lib.iqhost_bionj_newick.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dp, C.POINTER(C.c_char_p), C.c_char_p, C.c_int, ipp]
     lib.iqhost_compute_bionj.argtypes = [vp, dp, dp, vp, C.POINTER(C.c_int32), dp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_evaluate_nnis5_batch.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int)]
@@ -539,6 +554,45 @@ def bionj_newick(steps, last, last_len, names):
 def _hchk(rc):
     if rc != 0:
         raise HostError(libiqhost().iqhost_last_error().decode())
+
+
+# ---- likelihood mapping: the pure host pieces (iq-tree_amd/host/lmap_host.h)
+# iqhip_quartet_result of include/iqhip.h
+QUARTET_RESULT_DTYPE = np.dtype([("logl", np.float64, (3,)), ("len", np.float64, (3, 5)), ("nsweeps", np.int32, (3,)),
+                                 ("neval", np.int32, (3,)), ("status", np.int32, (3,)), ("_pad", np.int32)])
+assert QUARTET_RESULT_DTYPE.itemsize == 184
+
+
+def lmap_region(logl3):
+    """(weights[3], corner 0..2, region 0..6) of a quartet's three log-likelihoods: the Bayesian weights (differences beyond
+    40 give weight 0), the corner of the best tree and the region of the triangle, ties as the reference breaks them"""
+    l3 = np.ascontiguousarray(logl3, dtype=np.float64)
+    assert l3.shape == (3,)
+    w = np.zeros(3)
+    corner, area = C.c_int(), C.c_int()
+    _hchk(libiqhost().iqhost_lmap_region(_dptr(l3), _dptr(w), C.byref(corner), C.byref(area)))
+    return w, corner.value, area.value
+
+
+def lmap_weights(logl3):
+    """the Bayesian weights of a quartet's three log-likelihoods"""
+    return lmap_region(logl3)[0]
+
+
+def all_quartets(n):
+    """every unique quartet of n taxa, i0 < i1 < i2 < i3 in the reference's nested-loop order: int32 [C(n, 4), 4]"""
+    lib = libiqhost()
+    out = np.zeros((int(lib.iqhost_lmap_num_quartets(int(n))), 4), dtype=np.int32)
+    _hchk(lib.iqhost_lmap_all_quartets(int(n), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
+
+
+def draw_quartets(n, count, seed):
+    """count random quartets of n taxa (four distinct taxa each, in the order drawn): int32 [count, 4]; quartet q of a seed
+    does not depend on count"""
+    out = np.zeros((int(count), 4), dtype=np.int32)
+    _hchk(libiqhost().iqhost_lmap_draw_quartets(int(n), int(count), int(seed), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out
 
 
 def _c_strings(items):
@@ -1311,6 +1365,63 @@ class PhyloTree:
         assert ini is None or ini.shape == (n, n)
         self._chk(self.lib.iqhost_compute_dist(self.h, None if ini is None else _dptr(ini), _dptr(dist), _dptr(d2l)))
         return (dist, d2l) if want_d2l else dist
+
+    # ---- likelihood mapping (include/iqhip.h "Likelihood mapping")
+    @staticmethod
+    def _quartets(quartets):
+        q = np.ascontiguousarray(quartets, dtype=np.int32).reshape(-1, 4)
+        return q, q.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def quartet_cells(self, quartets):
+        """iqhip_quartet_cells: quartets [nq, 4] taxon ids -> (cells [nq, 4, 4, 4, 4] indexed by the four unambiguous states in
+        quartet order, nother [nq] = the patterns with an ambiguous or unknown state among the four)"""
+        q, qp = self._quartets(quartets)
+        cells = np.zeros((q.shape[0], 4, 4, 4, 4))
+        nother = np.zeros(q.shape[0], dtype=np.int32)
+        self._chk(self.lib.iqhost_quartet_cells(self.h, qp, q.shape[0], _dptr(cells), nother.ctypes.data_as(C.POINTER(C.c_int32))))
+        return cells, nother
+
+    def quartet_likelihoods(self, quartets, iterations=10, tolerance=0.1, const_invar=None):
+        """PhyloTree::computeQuartetLikelihoods: per quartet the three trees 12|34, 13|24, 14|23 from Fitch starting lengths
+        through optimizeAllBranches(iterations, tolerance), one engine call -> records of QUARTET_RESULT_DTYPE (logl[3],
+        len[3, 5]: pendant branches of the tree's four taxa, then the internal one; nsweeps, neval, status).  const_invar:
+        None or (p_inv pi[0..3], p_inv) of a +I model."""
+        q, qp = self._quartets(quartets)
+        out = np.zeros(q.shape[0], dtype=QUARTET_RESULT_DTYPE)
+        ci = None if const_invar is None else np.ascontiguousarray(const_invar, dtype=np.float64)
+        assert ci is None or ci.shape == (5,)
+        self._chk(self.lib.iqhost_quartet_likelihoods(self.h, qp, q.shape[0], int(iterations), float(tolerance),
+                                                      None if ci is None else _dptr(ci), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def likelihood_mapping(self, nquartets=0, seed=0, const_invar=None):
+        """PhyloTree::doLikelihoodMapping: nquartets = 0 (or >= C(ntaxa, 4)) evaluates every unique quartet, otherwise
+        draw_quartets(ntaxa, nquartets, seed) -> AttrDict(seq_id [nq, 4], logl [nq, 3], qweight [nq, 3], corner [nq], area [nq],
+        areacount [7], cornercount [3], seq_count [ntaxa + 1, 10]: regions 0..6 and corners 7..9 per sequence, last row all)"""
+        ci = None if const_invar is None else np.ascontiguousarray(const_invar, dtype=np.float64)
+        assert ci is None or ci.shape == (5,)
+        cip = None if ci is None else _dptr(ci)
+        nq = C.c_int64()
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(self.lib.iqhost_likelihood_mapping(self.h, int(nquartets), int(seed), cip, 0, C.byref(nq), None, None, None,
+                                                     None, None, None, None))
+        n = nq.value
+        seq_id, logl, w = np.zeros((n, 4), dtype=np.int32), np.zeros((n, 3)), np.zeros((n, 3))
+        corner, area = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        counts = np.zeros(10, dtype=np.int64)
+        seq_count = np.zeros((self.num_leaves + 1, 10), dtype=np.int64)
+        self._chk(self.lib.iqhost_likelihood_mapping(self.h, int(nquartets), int(seed), cip, n, C.byref(nq),
+                                                     seq_id.ctypes.data_as(i32p), _dptr(logl), _dptr(w),
+                                                     corner.ctypes.data_as(i32p), area.ctypes.data_as(i32p),
+                                                     counts.ctypes.data_as(i64p), seq_count.ctypes.data_as(i64p)))
+        return AttrDict(seq_id=seq_id, logl=logl, qweight=w, corner=corner, area=area, areacount=counts[:7].copy(),
+                        cornercount=counts[7:].copy(), seq_count=seq_count)
+
+    def quartet_timing(self):
+        """(cells_ms, solve_ms): device time of the last quartet_likelihoods call's launches (with iqhip_timing_enable)"""
+        a, b = C.c_double(), C.c_double()
+        self._hip(libiqhip().iqhip_debug_quartet_timing(self.engine, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # ---- BIONJ (include/iqhip.h "BIONJ")
     def bionj(self, dist, var=None):

@@ -542,6 +542,15 @@ struct iqhip_engine {
         iqhip::DevBuf<double> counts, coef, init, out;
     } pd;
     double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
+    // likelihood mapping (quartet.hip, kernels_quartet.hip): the taxa of the call's quartets, one chunk's cell tables
+    // [chunk][256], other-list lengths [chunk] and other-lists [chunk][nptn], the results of the call; with
+    // iqhip_timing_enable the device time of the last iqhip_quartet_likelihoods call
+    struct {
+        iqhip::DevBuf<int32_t> quartets, nother, other;
+        iqhip::DevBuf<double> cells;
+        iqhip::DevBuf<iqhip_quartet_result> out;
+    } qt;
+    double qt_cells_ms = 0.0, qt_solve_ms = 0.0;
     // BIONJ (kernels_bionj.hip): the device memory lives for one call; iqhip_debug_bionj_timing reads these
     double bj_ms = 0.0;
     int64_t bj_launches = 0;
@@ -1162,6 +1171,29 @@ struct PairSolveArgs {
 hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts);
 hipError_t launch_pair_coef(iqhip_engine *e, double *d_coef);
 hipError_t launch_pair_solve(iqhip_engine *e, const PairSolveArgs &a, int npairs);
+
+// kernels_quartet.hip: likelihood mapping.  launch_quartet_cells: quartet s of the chunk (taxa d_quartets[4 s ..]) ->
+// d_cells[s][256], d_nother[s], d_other[s * nptn ..].  launch_quartet_solve: one workgroup per (slot, topology); slot s is
+// quartet `first + s` of the call and writes out[first + s]
+struct QuartetSolveArgs {
+    const double *cells;        // [chunk][256]
+    const int32_t *nother;      // [chunk]
+    const int32_t *other;       // [chunk][nptn]
+    const int32_t *quartets;    // [chunk][4]
+    const uint8_t *states;      // [ntaxa][nptn_pad]
+    const double *freq;
+    const double *evec, *inv_evec, *eval, *rates, *props, *tip;
+    iqhip_quartet_result *out;  // [nq]
+    int64_t nptn_pad, nptn, first;
+    double const_invar[5];      // all 0 without +I
+    double nsite, x1, x2, xacc, diverge_frac, tolerance;
+    int32_t ncat, state_unknown, max_steps, iterations;
+    uint8_t mask[32];           // the states every state code allows (bit j: state j)
+};
+size_t quartet_solve_lds_bytes(int ncat, int state_unknown);
+hipError_t launch_quartet_cells(iqhip_engine *e, const int32_t *d_quartets, int m, double *d_cells, int32_t *d_nother,
+                                int32_t *d_other);
+hipError_t launch_quartet_solve(iqhip_engine *e, const QuartetSolveArgs &a, int m);
 
 // Fitch parsimony (kernels_pars.hip); all on e->stream, shapes from e->pars_nwords / e->n
 constexpr int kParsWordsPerWg = 16;   // word columns a workgroup of k_pars_update owns ...

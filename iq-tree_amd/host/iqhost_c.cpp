@@ -656,6 +656,62 @@ int iqhost_compute_dist(void *h, const double *init, double *dist, double *d2l) 
 int iqhost_pair_counts(void *h, const int32_t *pairs, int npairs, double *counts) {
     IQHOST_TRY(((PhyloTree *)h)->pairCounts(pairs, npairs, counts));
 }
+// likelihood mapping: results = nq records of iqhip_quartet_result
+int iqhost_quartet_cells(void *h, const int32_t *quartets, int nq, double *cells, int32_t *nother) {
+    IQHOST_TRY(((PhyloTree *)h)->quartetCells(quartets, nq, cells, nother));
+}
+int iqhost_quartet_likelihoods(void *h, const int32_t *quartets, int nq, int iterations, double tolerance,
+                               const double *const_invar, iqhip_quartet_result *results) {
+    IQHOST_TRY(((PhyloTree *)h)->computeQuartetLikelihoods(quartets, nq, results, iterations, tolerance, const_invar));
+}
+// *nq = the number of quartets evaluated (call with cap = 0 first: nothing is computed then); with cap >= *nq: seq_id
+// [4 nq], logl and weight [3 nq each], corner and area [nq each], counts = 7 areas ++ 3 corners, seq_count [(leafNum + 1) * 10]
+int iqhost_likelihood_mapping(void *h, int64_t nquartets, uint64_t seed, const double *const_invar, int64_t cap, int64_t *nq,
+                              int32_t *seq_id, double *logl, double *weight, int32_t *corner, int32_t *area, int64_t *counts,
+                              int64_t *seq_count) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        if (t->leafNum < 4) throw std::runtime_error("likelihood mapping needs at least 4 taxa");
+        const int64_t all = lmap::numQuartets(t->leafNum);
+        const int64_t n = (nquartets == 0 || nquartets >= all) ? all : nquartets;
+        *nq = n;
+        if (cap >= n && n > 0) {
+            PhyloTree::LmapResult r;
+            t->doLikelihoodMapping(nquartets, seed, r, const_invar);
+            for (size_t q = 0; q < r.info.size(); q++) {
+                for (int k = 0; k < 4; k++) seq_id[4 * q + k] = r.info[q].seqID[k];
+                for (int k = 0; k < 3; k++) {
+                    logl[3 * q + k] = r.info[q].logl[k];
+                    weight[3 * q + k] = r.info[q].qweight[k];
+                }
+                corner[q] = r.info[q].corner;
+                area[q] = r.info[q].area;
+            }
+            for (int k = 0; k < 7; k++) counts[k] = r.areacount[k];
+            for (int k = 0; k < 3; k++) counts[7 + k] = r.cornercount[k];
+            memcpy(seq_count, r.seq_count.data(), sizeof(int64_t) * r.seq_count.size());
+        }
+    });
+}
+// the pure host pieces of lmap_host.h
+int iqhost_lmap_region(const double *logl3, double *weight3, int *corner, int *area) {
+    IQHOST_TRY(lmap::region(logl3, weight3, corner, area));
+}
+int64_t iqhost_lmap_num_quartets(int n) { return lmap::numQuartets(n); }
+int iqhost_lmap_all_quartets(int n, int32_t *out) {
+    IQHOST_TRY({
+        std::vector<int32_t> q;
+        lmap::allQuartets(n, q);
+        if (!q.empty()) memcpy(out, q.data(), sizeof(int32_t) * q.size());
+    });
+}
+int iqhost_lmap_draw_quartets(int n, int64_t count, uint64_t seed, int32_t *out) {
+    IQHOST_TRY({
+        std::vector<int32_t> q;
+        lmap::drawQuartets(n, count, seed, q);
+        if (!q.empty()) memcpy(out, q.data(), sizeof(int32_t) * q.size());
+    });
+}
 // out: NULL or cap bytes for the Newick string; *need = its length + 1 (the string is copied only when it fits)
 int iqhost_bionj_newick(const iqhip_bionj_step *steps, int n, const int32_t *last, const double *last_len, const char **names,
                         char *out, int cap, int *need) {

@@ -1420,6 +1420,52 @@ void PhyloTree::pairCounts(const int32_t *pairs, int npairs, double *counts) {
 }
 
 // =========================================================================================
+// likelihood mapping, quartet.cpp:676-1152, 1340-1505 (include/iqhip.h "Likelihood mapping"; lmap_host.h)
+// =========================================================================================
+void PhyloTree::quartetCells(const int32_t *quartets, int nq, double *cells, int32_t *nother) {
+    if (!engine || dry_run) throw std::runtime_error("quartetCells needs an attached engine");
+    pushInputs();
+    check(iqhip_quartet_cells(engine, quartets, nq, cells, nother), "iqhip_quartet_cells");
+}
+
+void PhyloTree::computeQuartetLikelihoods(const int32_t *quartets, int nq, iqhip_quartet_result *results, int iterations,
+                                          double tolerance, const double *const_invar) {
+    if (!engine || dry_run) throw std::runtime_error("computeQuartetLikelihoods needs an attached engine");
+    if (allreduce_hook) throw std::runtime_error("computeQuartetLikelihoods: not available with a caller-owned collective");
+    pushInputs();
+    check(iqhip_quartet_likelihoods(engine, quartets, nq, const_invar, min_branch_length, max_branch_length, min_branch_length,
+                                    100, 0.95, iterations, tolerance, results),
+          "iqhip_quartet_likelihoods");
+}
+
+void PhyloTree::doLikelihoodMapping(int64_t nquartets, uint64_t seed, LmapResult &out, const double *const_invar) {
+    if (leafNum < 4) throw std::runtime_error("likelihood mapping needs at least 4 taxa");
+    if (nquartets < 0) throw std::runtime_error("doLikelihoodMapping: negative number of quartets");
+    std::vector<int32_t> quartets;
+    if (nquartets == 0 || nquartets >= lmap::numQuartets(leafNum)) lmap::allQuartets(leafNum, quartets);
+    else lmap::drawQuartets(leafNum, nquartets, seed, quartets);
+    const size_t nq = quartets.size() / 4;
+    if (nq > 2147483647u) throw std::runtime_error("doLikelihoodMapping: too many quartets for one call");
+    std::vector<iqhip_quartet_result> res(nq);
+    computeQuartetLikelihoods(quartets.data(), (int)nq, res.data(), 10, 0.1, const_invar);
+    out = LmapResult();
+    out.info.resize(nq);
+    out.seq_count.assign((size_t)(leafNum + 1) * 10, 0);
+    for (size_t q = 0; q < nq; q++) {
+        lmap::QuartetInfo &qi = out.info[q];
+        for (int k = 0; k < 4; k++) qi.seqID[k] = quartets[4 * q + k];
+        for (int k = 0; k < 3; k++) qi.logl[k] = res[q].logl[k];
+        lmap::region(qi.logl, qi.qweight, &qi.corner, &qi.area);
+        out.areacount[qi.area]++;
+        out.cornercount[qi.corner]++;
+        for (int col : {qi.area, 7 + qi.corner}) {
+            out.seq_count[(size_t)leafNum * 10 + col]++;
+            for (int k = 0; k < 4; k++) out.seq_count[(size_t)qi.seqID[k] * 10 + col]++;
+        }
+    }
+}
+
+// =========================================================================================
 // BIONJ, phylotree.cpp:2619-2635 over bionj.h (include/iqhip.h "BIONJ")
 // =========================================================================================
 std::string PhyloTree::bionjNewick(const iqhip_bionj_step *steps, int n, const int32_t *last, const double *last_len,

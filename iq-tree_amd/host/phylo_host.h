@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/iqhip.h"
+#include "lmap_host.h"
 
 namespace iqhost {
 
@@ -242,6 +243,26 @@ public:
     static constexpr double MAX_GENETIC_DIST = 9.0;
     void computeDist(const double *init, double *dist, double *d2l);
     void pairCounts(const int32_t *pairs, int npairs, double *counts);
+
+    // ---- likelihood mapping (-lmap; PhyloTree::computeQuartetLikelihoods / doLikelihoodMapping, quartet.cpp:676-1152,
+    //      1340-1505) on the device.  computeQuartetLikelihoods: ONE iqhip_quartet_likelihoods call for the nq quartets
+    //      (4 taxon ids each, order kept) with x1 = xacc = min_branch_length, x2 = max_branch_length, 100 Newton steps and
+    //      the diverged-solve fraction 0.95, as optimizeOneBranch; the reference's optimizeAllBranches(10, 0.1) per quartet
+    //      tree are the defaults.  const_invar: nullptr or {p_inv pi[0..3], p_inv} of a +I model.  Needs no tree beyond the
+    //      taxa.  quartetCells: the 256 cells and the number of other patterns per quartet.
+    //      doLikelihoodMapping: nquartets = 0 or >= C(leafNum, 4): all unique quartets in the reference's order, otherwise
+    //      nquartets draws of lmap::drawQuartets(seed); per quartet lmap::region; area / corner counts overall and per
+    //      sequence (seq_count[(leafNum + 1) * 10]: row = sequence, the last row all quartets; columns 0..6 regions, 7..9
+    //      corners, as countarr of the reference).  Throws below 4 taxa.  Cluster files and the plots are out of scope.
+    struct LmapResult {
+        std::vector<lmap::QuartetInfo> info;
+        int64_t areacount[7] = {0, 0, 0, 0, 0, 0, 0}, cornercount[3] = {0, 0, 0};
+        std::vector<int64_t> seq_count;
+    };
+    void quartetCells(const int32_t *quartets, int nq, double *cells, int32_t *nother);
+    void computeQuartetLikelihoods(const int32_t *quartets, int nq, iqhip_quartet_result *results, int iterations = 10,
+                                   double tolerance = 0.1, const double *const_invar = nullptr);
+    void doLikelihoodMapping(int64_t nquartets, uint64_t seed, LmapResult &out, const double *const_invar = nullptr);
 
     // ---- BIONJ (PhyloTree::computeBioNJ, phylotree.cpp:2619-2635, over BioNj::create) on the device: one iqhip_bionj on
     //      dist (and var, or nullptr for V = D), leafNum * leafNum each; the step log becomes the reference's Newick string
