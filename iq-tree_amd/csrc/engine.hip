@@ -735,6 +735,28 @@ int iqhip::check_ready(iqhip_engine *e) {
     return IQHIP_OK;
 }
 
+int iqhip::require(iqhip_engine *e, const char *what, unsigned needs) {
+    const auto no = [what](int code, const char *why) { return fail(code, std::string(what) + ": " + why); };
+    if (!e) return no(IQHIP_ERR_INVALID, "null engine");
+    if (e->planner) return no(IQHIP_ERR_INVALID, "not available on a planning-only engine");
+    if ((needs & REQ_SINGLE_DEVICE) && (!e->shards.empty() || e->comm))
+        return no(IQHIP_ERR_UNSUPPORTED, "not available on pattern-sharded engines");
+    if ((needs & REQ_NO_ASC) && (e->asc_active || e->n_unobs > 0))
+        return no(IQHIP_ERR_UNSUPPORTED, "not available with ascertainment bias correction (+ASC)");
+    const bool only4 = needs & REQ_STATES_4;
+    if ((needs & REQ_PLAIN_STATES) && (e->embed2 || e->n_user != e->n))
+        return no(IQHIP_ERR_UNSUPPORTED, only4 ? "not available for embedded state counts (4 states only)"
+                                               : "not available for embedded state counts (4, 20 or 64 states only)");
+    if ((needs & REQ_STATES_4_20_64) && e->n != 4 && e->n != 20 && e->n != 64) return no(IQHIP_ERR_UNSUPPORTED, "4, 20 or 64 states only");
+    if (only4 && e->n != 4) return no(IQHIP_ERR_UNSUPPORTED, "4 states only");
+    if ((needs & REQ_NO_MIXTURE) && e->nclass > 1) return no(IQHIP_ERR_UNSUPPORTED, "not available for mixture models");
+    if ((needs & REQ_MIXTURE) && e->nclass < 2) return no(IQHIP_ERR_UNSUPPORTED, "the model is no mixture (one class)");
+    if ((needs & REQ_MODEL_ALN) && (!e->model_set || !e->aln_set))
+        return no(IQHIP_ERR_INVALID, "needs iqhip_set_model and iqhip_set_alignment first");
+    if ((needs & REQ_THETA) && !e->theta_valid) return no(IQHIP_ERR_INVALID, "needs iqhip_compute_theta first");
+    return IQHIP_OK;
+}
+
 static void timing_begin(iqhip_engine *e) {
     if (!e->timing) return;
     if (e->tev_used == e->tev.size()) {

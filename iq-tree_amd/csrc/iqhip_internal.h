@@ -502,7 +502,7 @@ struct iqhip_engine {
         double ms[2] = {0.0, 0.0};   // iqhip_debug_ufboot_timing: the products, the update kernels (while timing is enabled)
         int64_t launches = 0;        // kernels the last iqhip_ufboot_update enqueued
     } ufb;
-    // EM for +R free-rate models and empirical-Bayes site rates (ptnlh.hip, kernels_em.hip): what the last E-step left -- the
+    // EM for +R free-rate models and empirical-Bayes site rates (classlh.hip, kernels_em.hip): what the last E-step left -- the
     // posterior matrix W [ncat][nptn_pad] (category-major, padding patterns 0), per pattern its posterior mean rate and
     // best category -- and the scratch of the sums (workgroup rows, folded values).  valid: an E-step has run for an
     // engine of these dimensions
@@ -512,7 +512,7 @@ struct iqhip_engine {
         bool valid = false;
         double ms[2] = {0.0, 0.0};   // iqhip_debug_em_timing: the last E-step / objective launches (while timing is enabled)
     } em;
-    // EM for mixture class weights, class posteriors, pattern state frequencies (ptnlh.hip, kernels_mixem.hip): the class
+    // EM for mixture class weights, class posteriors, pattern state frequencies (classlh.hip, kernels_mixem.hip): the class
     // likelihoods Lc [nclass][nptn_pad] of the last iqhip_mix_class_lh (class-major, padding patterns 0) with the model
     // version and dimensions they belong to (0: none), the per-class component lists (first [nclass + 1] ++ components), the
     // state of an EM run (kernels_mixem.hip MIXEM_*), the workgroup rows of its sums, posteriors / state frequencies scratch
@@ -525,7 +525,7 @@ struct iqhip_engine {
         double ms[2] = {0.0, 0.0};   // iqhip_debug_mix_timing: the class-lh launch, the EM chain (while timing is enabled)
         int64_t launches = 0;        // kernels the last EM chain enqueued
     } mix;
-    // per-class log-likelihoods (iqhip_class_lnl; ptnlh.hip, kernels_classlnl.hip): the per-class component lists as mix.list,
+    // per-class log-likelihoods (iqhip_class_lnl; classlh.hip, kernels_classlnl.hip): the per-class component lists as mix.list,
     // the class weights [nclass], the caller's per-class invariant terms [nclass][nptn_pad], the workgroup rows of the sums
     // and the folded values {lnl, floored} [2 nclass].  mixture_api: the model came through iqhip_set_mixture_model
     struct {
@@ -540,8 +540,8 @@ struct iqhip_engine {
     struct {
         iqhip::DevBuf<iqhip::PairTile> tiles;
         iqhip::DevBuf<double> counts, coef, init, out;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_pair_timing: the count launches, the solve launches
     } pd;
-    double pd_counts_ms = 0.0, pd_solve_ms = 0.0;
     // likelihood mapping (quartet.hip, kernels_quartet.hip): the taxa of the call's quartets, one chunk's cell tables
     // [chunk][256], other-list lengths [chunk] and other-lists [chunk][nptn], the results of the call; with
     // iqhip_timing_enable the device time of the last iqhip_quartet_likelihoods call
@@ -549,11 +549,13 @@ struct iqhip_engine {
         iqhip::DevBuf<int32_t> quartets, nother, other;
         iqhip::DevBuf<double> cells;
         iqhip::DevBuf<iqhip_quartet_result> out;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_quartet_timing: the cell launches, the solve launches
     } qt;
-    double qt_cells_ms = 0.0, qt_solve_ms = 0.0;
     // BIONJ (kernels_bionj.hip): the device memory lives for one call; iqhip_debug_bionj_timing reads these
-    double bj_ms = 0.0;
-    int64_t bj_launches = 0;
+    struct {
+        double ms = 0.0;
+        int64_t launches = 0;
+    } bj;
     // Fitch parsimony (pars.hip, kernels_pars.hip).  Host copies of what iqhip_pars_init reads: ptn_freq
     // (iqhip_set_ptn_freq), class 0's eigenvectors and tip table (set_model_common).  Vectors [ntaxa + nvectors] of
     // pars_nwords * n words (4 states: word-major, a column is one 16-byte load; 20 / 64 states: plane-major, lanes on
@@ -836,6 +838,40 @@ hipError_t DevBuf<T>::ensure(iqhip_engine *e, size_t count) {
     fake = e->planner;
     return regrow(e, &p, &cap, count, count);
 }
+// HIP events around the phases of one feature call; nothing at all while e->timing is off.  mark() records the next
+// boundary on e->stream: a round of nphases phases is nphases + 1 marks, a call may record any number of rounds (one per
+// chunk) and nothing waits inside its loop.  read() waits for the last recorded event, then ms[k] = the time of phase k
+// summed over all rounds; false, ms untouched, while timing is off, nothing was recorded or an event call failed.  A failed
+// event call never fails the feature call: the reading is then missing, not the result.  The destructor destroys every
+// event, on every return path.
+struct PhaseTimer {
+    PhaseTimer(iqhip_engine *e_, int nphases_) : e(e_), nphases(nphases_), ok(e_->timing) {}
+    PhaseTimer(const PhaseTimer &) = delete; PhaseTimer &operator=(const PhaseTimer &) = delete;
+    void mark() {
+        hipEvent_t x = nullptr;
+        if (!ok || !(ok = hipEventCreate(&x) == hipSuccess)) return;
+        ev.push_back(x);
+        ok = hipEventRecord(x, e->stream) == hipSuccess;
+    }
+    bool read(double *ms) {
+        const size_t round = (size_t)nphases + 1;
+        if (!ok || ev.empty() || ev.size() % round || hipEventSynchronize(ev.back()) != hipSuccess) return false;
+        std::vector<double> sum((size_t)nphases, 0.0);
+        for (size_t k = 0; k < ev.size(); k += round)
+            for (int h = 0; h < nphases; h++) {
+                float t = 0.0f;
+                if (hipEventElapsedTime(&t, ev[k + h], ev[k + h + 1]) != hipSuccess) return false;
+                sum[(size_t)h] += t;
+            }
+        std::copy(sum.begin(), sum.end(), ms);
+        return true;
+    }
+    ~PhaseTimer() { for (hipEvent_t x : ev) hipEventDestroy(x); }
+    iqhip_engine *e;
+    int nphases;
+    bool ok;
+    std::vector<hipEvent_t> ev;
+};
 int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);   // engine.hip (create: a new key gets a slab)
 bool cherry_candidate(const iqhip_engine *e);   // engine.hip: the engine uses cherry tables (DevOp::cherry)
 
@@ -905,12 +941,29 @@ int comm_init_all(const std::vector<iqhip_engine *> &shards);
 void comm_destroy(iqhip_engine *e);
 int comm_use_device_result(iqhip_engine *e);  // switch the engine to a device-memory result vector
 
-// engine.hip internals the solvers (solve.hip), the feature drivers (ptnlh.hip, pairdist.hip) and the sharded front drive
-// an engine with
+// engine.hip internals the solvers (solve.hip), the feature drivers (ptnlh.hip, classlh.hip, pairdist.hip, ...) and the
+// sharded front drive an engine with
 // a planning-only engine has no device: every entry point that would touch one fails here ("invalid device ordinal")
 hipError_t use_device(const iqhip_engine *e);
-int ptnlh_plain_engine(iqhip_engine *e, const char *what);   // ptnlh.hip -- the per-pattern store: single-device engines only
+// May this engine run the feature `what` (an entry point's name)?  A null engine and a planning-only engine are always
+// refused (IQHIP_ERR_INVALID); then, as far as `needs` asks: a sharded engine or communicator rank, the shape refusals in
+// the order of the bits below (IQHIP_ERR_UNSUPPORTED), the state preconditions (IQHIP_ERR_INVALID).  Every text starts
+// with "<what>: ".  What only one feature knows of (an E-step that must have run, iqhip_pars_init, ...) stays with it.
+enum : unsigned {
+    REQ_SINGLE_DEVICE = 1u << 0,    // no shards, no communicator
+    REQ_NO_ASC = 1u << 1,
+    REQ_PLAIN_STATES = 1u << 2,     // the caller's state count is the kernels' (no embedded state counts)
+    REQ_STATES_4_20_64 = 1u << 3,
+    REQ_STATES_4 = 1u << 4,
+    REQ_NO_MIXTURE = 1u << 5,
+    REQ_MIXTURE = 1u << 6,          // at least two classes
+    REQ_MODEL_ALN = 1u << 7,        // model and alignment set
+    REQ_THETA = 1u << 8,            // theta valid
+};
+int require(iqhip_engine *e, const char *what, unsigned needs);
 int check_ready(iqhip_engine *e);                     // model and alignment set, device selected
+// the scale counters of a branch's two ends; a leaf carries no scaling events: nullptr
+int branch_scale_counters(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, const int16_t *sc[2]);
 int ensure_slab_rows(iqhip_engine *e, int nrows);     // the wave-partial slab holds nrows rows
 // enqueue: plan upload, K1, fused traversal (+ optional root lnL), fixed-order reduction (skip_reduce: the caller's next
 // kernel sums the slab); explicit_segs, len_ptrs: see build_plan

@@ -228,13 +228,6 @@ struct BjBuffers {
         return s;
     }
 };
-struct BjEvents {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~BjEvents() {
-        for (hipEvent_t x : ev)
-            if (x) hipEventDestroy(x);
-    }
-};
 }  // namespace
 
 }  // namespace iqhip
@@ -243,10 +236,8 @@ using namespace iqhip;
 
 extern "C" int iqhip_bionj(iqhip_engine *e, int n, const double *dist, const double *var, iqhip_bionj_step *steps,
                            int32_t *last, double *last_len) {
-    if (!e) return fail(IQHIP_ERR_INVALID, "iqhip_bionj: null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_bionj: not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, "iqhip_bionj: sharded engines and communicator ranks are out of scope");
+    const int rc = require(e, "iqhip_bionj", REQ_SINGLE_DEVICE);
+    if (rc) return rc;
     if (n < 3) return fail(IQHIP_ERR_INVALID, "iqhip_bionj: at least 3 taxa");
     if (!dist || !last || !last_len || (n > 3 && !steps)) return fail(IQHIP_ERR_INVALID, "iqhip_bionj: null argument");
     if (n > 65536)
@@ -273,14 +264,12 @@ extern "C" int iqhip_bionj(iqhip_engine *e, int n, const double *dist, const dou
         (void)hipGetLastError();
         return fail(IQHIP_ERR_NOMEM, "iqhip_bionj: out of device memory (three n x n matrices of doubles)");
     }
-    BjEvents tm;
-    if (e->timing)
-        for (hipEvent_t &x : tm.ev) HIPCHK(hipEventCreate(&x));
+    PhaseTimer timer(e, 1);
     hipStream_t st = e->stream;
     const unsigned nn_blocks = (unsigned)((nn + kBjThreads - 1) / kBjThreads);
     int64_t launches = 0;
     HIPCHK(hipMemcpyAsync(d_T, dist, sizeof(double) * nn, hipMemcpyHostToDevice, st));
-    if (e->timing) HIPCHK(hipEventRecord(tm.ev[0], st));
+    timer.mark();
     hipLaunchKernelGGL(k_bj_sym, dim3(nn_blocks), dim3(kBjThreads), 0, st, d_T, d_D, n);
     launches++;
     if (var) {
@@ -314,24 +303,20 @@ extern "C" int iqhip_bionj(iqhip_engine *e, int n, const double *dist, const dou
     hipLaunchKernelGGL(k_bj_finish, dim3(1), dim3(64), 0, st, d_D, n, d_act[cur], d_last, d_last_len);
     launches++;
     HIPCHK(hipGetLastError());
-    if (e->timing) HIPCHK(hipEventRecord(tm.ev[1], st));
+    timer.mark();
     if (nsteps > 0) HIPCHK(hipMemcpyAsync(steps, d_steps, sizeof(iqhip_bionj_step) * (size_t)nsteps, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(last, d_last, sizeof(int32_t) * 3, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(last_len, d_last_len, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    e->bj_ms = 0.0;
-    e->bj_launches = launches;
-    if (e->timing) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, tm.ev[0], tm.ev[1]));
-        e->bj_ms = ms;
-    }
+    e->bj.ms = 0.0;
+    timer.read(&e->bj.ms);
+    e->bj.launches = launches;
     return IQHIP_OK;
 }
 
 extern "C" int iqhip_debug_bionj_timing(iqhip_engine *e, double *ms, int64_t *launches) {
     if (!e || e->planner || !e->shards.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_bionj_timing: needs a single-device engine");
-    if (ms) *ms = e->bj_ms;
-    if (launches) *launches = e->bj_launches;
+    if (ms) *ms = e->bj.ms;
+    if (launches) *launches = e->bj.launches;
     return IQHIP_OK;
 }

@@ -8,17 +8,11 @@
 using namespace iqhip;
 
 // ---- pairwise ML distances (PhyloTree::computeDist, phylotree.cpp:2432-2541; kernels_dist.hip) -----------------------
-static int pair_engine(iqhip_engine *e, const char *what) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines are out of scope (the counts would need an all-reduce)");
-    if (e->n_user != e->n || (e->n != 4 && e->n != 20 && e->n != 64))
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": 4, 20 or 64 states only (no embedded state counts)");
-    if (!e->model_set || !e->aln_set)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_model and iqhip_set_alignment first");
-    if (e->nclass > 1) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": mixture models are out of scope");
-    return IQHIP_OK;
+// single-device plain engines of 4 / 20 / 64 states with model and alignment; mixtures are refused behind that: a mixture
+// without an alignment is an invalid call here, not an unsupported model
+static int pair_require(iqhip_engine *e, const char *what) {
+    int rc = require(e, what, REQ_SINGLE_DEVICE | REQ_PLAIN_STATES | REQ_STATES_4_20_64 | REQ_MODEL_ALN);
+    return rc ? rc : require(e, what, REQ_NO_MIXTURE);
 }
 
 // pairs per chunk: the counts of a chunk stay within 64 MB; IQHIP_PAIR_CHUNK (read per call) overrides
@@ -53,7 +47,7 @@ static void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<P
 }
 
 extern "C" int iqhip_pair_counts(iqhip_engine *e, const int32_t *pairs, int npairs, double *counts) {
-    int rc = pair_engine(e, "iqhip_pair_counts");
+    int rc = pair_require(e, "iqhip_pair_counts");
     if (rc) return rc;
     if (!pairs || !counts || npairs < 0) return fail(IQHIP_ERR_INVALID, "iqhip_pair_counts: bad pair list");
     for (int64_t k = 0; k < 2 * (int64_t)npairs; k++)
@@ -79,7 +73,7 @@ extern "C" int iqhip_pair_counts(iqhip_engine *e, const int32_t *pairs, int npai
 
 extern "C" int iqhip_pair_distances(iqhip_engine *e, const double *init, double x1, double x2, double xacc, int max_steps,
                                     double *dist, double *d2l, int32_t *nsteps) {
-    int rc = pair_engine(e, "iqhip_pair_distances");
+    int rc = pair_require(e, "iqhip_pair_distances");
     if (rc) return rc;
     if (!dist) return fail(IQHIP_ERR_INVALID, "iqhip_pair_distances: null argument");
     if (!(x1 >= 0.0) || x1 > x2 || !std::isfinite(x2) || !(xacc > 0.0) || max_steps < 1)
@@ -145,34 +139,23 @@ extern "C" int iqhip_pair_distances(iqhip_engine *e, const double *init, double 
     a.x1 = x1;
     a.x2 = x2;
     a.xacc = xacc;
-    // iqhip_timing_enable: device time of the count and the solve launches (HIP events), summed over the chunks
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (e->timing)
-        for (int k = 0; k < 3; k++) HIPCHK(hipEventCreate(&ev[k]));
-    e->pd_counts_ms = e->pd_solve_ms = 0.0;
+    // iqhip_timing_enable: device time of the count and the solve launches, summed over the chunks
+    PhaseTimer timer(e, 2);
+    e->pd.ms[0] = e->pd.ms[1] = 0.0;
     int64_t first = 0;
     for (size_t c = 0; first < npairs; c++, first += chunk) {
         const int m = (int)std::min<int64_t>(chunk, npairs - first);
         a.first_pair = first;
-        if (e->timing) HIPCHK(hipEventRecord(ev[0], e->stream));
+        timer.mark();
         HIPCHK(launch_pair_counts(e, e->pd.tiles.p + tile_first[c], (int)(tile_first[c + 1] - tile_first[c]), e->pd.counts.p));
-        if (e->timing) HIPCHK(hipEventRecord(ev[1], e->stream));
+        timer.mark();
         HIPCHK(launch_pair_solve(e, a, m));
-        if (e->timing) {
-            HIPCHK(hipEventRecord(ev[2], e->stream));
-            HIPCHK(hipEventSynchronize(ev[2]));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            e->pd_counts_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-            e->pd_solve_ms += ms;
-        }
+        timer.mark();
     }
-    for (int k = 0; k < 3; k++)
-        if (ev[k]) hipEventDestroy(ev[k]);
     std::vector<double> out((size_t)4 * npairs);
     HIPCHK(hipMemcpyAsync(out.data(), e->pd.out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    timer.read(e->pd.ms);
     int worst = 0;
     for (int64_t k = 0; k < npairs; k++) {
         const size_t ij = (size_t)pairs[2 * k] * T + pairs[2 * k + 1], ji = (size_t)pairs[2 * k + 1] * T + pairs[2 * k];
@@ -187,7 +170,7 @@ extern "C" int iqhip_pair_distances(iqhip_engine *e, const double *init, double 
 
 extern "C" int iqhip_debug_pair_timing(iqhip_engine *e, double *counts_ms, double *solve_ms) {
     if (!e || !e->shards.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pair_timing: needs a single-device engine");
-    if (counts_ms) *counts_ms = e->pd_counts_ms;
-    if (solve_ms) *solve_ms = e->pd_solve_ms;
+    if (counts_ms) *counts_ms = e->pd.ms[0];
+    if (solve_ms) *solve_ms = e->pd.ms[1];
     return IQHIP_OK;
 }

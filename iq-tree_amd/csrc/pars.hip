@@ -59,52 +59,21 @@ extern "C" int iqhip_debug_pars_levels(int ntaxa, int nvectors, const uint8_t *v
     return IQHIP_OK;
 }
 
-static int pars_engine(iqhip_engine *e, const char *what, bool need_init) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines are out of scope (a word column would span shards)");
-    if (e->n_user != e->n || (e->n != 4 && e->n != 20 && e->n != 64))
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": 4, 20 or 64 states only (no embedded state counts)");
-    if (!e->model_set || !e->aln_set)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_model and iqhip_set_alignment first");
+// single-device plain engines of 4 / 20 / 64 states with model and alignment; need_init: the call works on what
+// iqhip_pars_init laid out
+static int pars_require(iqhip_engine *e, const char *what, bool need_init) {
+    const int rc = require(e, what, REQ_SINGLE_DEVICE | REQ_PLAIN_STATES | REQ_STATES_4_20_64 | REQ_MODEL_ALN);
+    if (rc) return rc;
     if (need_init && !e->pars_ready)
         return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_pars_init first (the alignment or its frequencies changed since)");
     return IQHIP_OK;
 }
 
-// HIP events around the launches of a call while iqhip_timing_enable is on
-struct ParsTimer {
-    iqhip_engine *e;
-    double *ms;
-    int64_t *launches, *work;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ParsTimer(iqhip_engine *e_, int which) : e(e_), ms(&e_->pars_ms[which]), launches(&e_->pars_counts[which]), work(&e_->pars_counts[2 + which]) {}
-    ParsTimer(iqhip_engine *e_, double *ms_, int64_t *launches_, int64_t *work_) : e(e_), ms(ms_), launches(launches_), work(work_) {}
-    hipError_t start() {
-        if (!e->timing) return hipSuccess;
-        for (auto &v : ev) {
-            const hipError_t s = hipEventCreate(&v);
-            if (s != hipSuccess) return s;
-        }
-        return hipEventRecord(ev[0], e->stream);
-    }
-    hipError_t stop(int nlaunches, int64_t work_done) {
-        *launches += nlaunches;
-        *work += work_done;
-        if (!e->timing) return hipSuccess;
-        hipError_t s = hipEventRecord(ev[1], e->stream);
-        if (s == hipSuccess) s = hipEventSynchronize(ev[1]);
-        float t = 0.f;
-        if (s == hipSuccess) s = hipEventElapsedTime(&t, ev[0], ev[1]);
-        if (s == hipSuccess) *ms += t;
-        return s;
-    }
-    ~ParsTimer() {
-        for (auto v : ev)
-            if (v) hipEventDestroy(v);
-    }
-};
+// the device time of a call's launches (with iqhip_timing_enable) adds up across calls until the debug read resets it
+static void pars_add_ms(PhaseTimer &timer, double *ms) {
+    double t;
+    if (timer.read(&t)) *ms += t;
+}
 
 // a pinned staging buffer of at least `need` words (the stream is drained before an old one is freed)
 static hipError_t pars_pinned(iqhip_engine *e, int32_t **buf, size_t *cap, size_t need) {
@@ -121,7 +90,7 @@ static hipError_t pars_pinned(iqhip_engine *e, int32_t **buf, size_t *cap, size_
 }
 
 extern "C" int iqhip_pars_shape(iqhip_engine *e, int64_t *nsites, int64_t *nwords, int *nvectors) {
-    int rc = pars_engine(e, "iqhip_pars_shape", true);
+    int rc = pars_require(e, "iqhip_pars_shape", true);
     if (rc) return rc;
     if (nsites) *nsites = e->pars_nsites;
     if (nwords) *nwords = e->pars_nwords;
@@ -130,7 +99,7 @@ extern "C" int iqhip_pars_shape(iqhip_engine *e, int64_t *nsites, int64_t *nword
 }
 
 extern "C" int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative, int nvectors, int64_t *nsites) {
-    int rc = pars_engine(e, "iqhip_pars_init", false);
+    int rc = pars_require(e, "iqhip_pars_init", false);
     if (rc) return rc;
     e->pars_ready = false;
     if (nvectors < 0) return fail(IQHIP_ERR_INVALID, "iqhip_pars_init: nvectors < 0");
@@ -183,7 +152,7 @@ extern "C" int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative, int 
 }
 
 extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int nops) {
-    int rc = pars_engine(e, "iqhip_pars_update", true);
+    int rc = pars_require(e, "iqhip_pars_update", true);
     if (rc) return rc;
     std::vector<int32_t> level((size_t)std::max(nops, 0));
     const std::string err = pars_levels(e->ntaxa, e->pars_nvec, e->pars_valid.data(), ops, nops, level.data());
@@ -209,10 +178,13 @@ extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int 
         std::copy(start.begin(), start.end(), e->h_pars_ops + (size_t)4 * nops);
     }
     HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
-    ParsTimer tm(e, 0);
-    HIPCHK(tm.start());
+    PhaseTimer timer(e, 1);
+    timer.mark();
     HIPCHK(launch_pars_update(e, reinterpret_cast<const iqhip_pars_op *>(e->pars.ints.p), e->pars.ints.p + (size_t)4 * nops, nlev));
-    HIPCHK(tm.stop(1, nops));
+    timer.mark();
+    e->pars_counts[0] += 1;
+    e->pars_counts[2] += nops;
+    pars_add_ms(timer, &e->pars_ms[0]);
     for (int k = 0; k < nops; k++) e->pars_valid[(size_t)(ops[k].dst - e->ntaxa)] = 1;
     return IQHIP_OK;
 }
@@ -241,11 +213,16 @@ static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int ta
     // (no copy of h_pars_ends or into h_pars_out is in flight: every call of this function ends with a synchronise)
     memcpy(e->h_pars_ends, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
     HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ends, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
-    ParsTimer tm(e, 1);
+    PhaseTimer timer(e, 1);
     int nlaunches = 0;
-    if (taxon >= 0) HIPCHK(tm.start());
+    timer.mark();
     HIPCHK(launch_pars_branch(e, e->pars.ints.p, nbranch, taxon, e->pars.out.p, &nlaunches));
-    if (taxon >= 0) HIPCHK(tm.stop(nlaunches, nbranch));
+    timer.mark();
+    if (taxon >= 0) {   // (the insertion scans: plain branch scores are not tallied)
+        e->pars_counts[1] += nlaunches;
+        e->pars_counts[3] += nbranch;
+        pars_add_ms(timer, &e->pars_ms[1]);
+    }
     HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     out.assign(e->h_pars_out, e->h_pars_out + count);
@@ -253,7 +230,7 @@ static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int ta
 }
 
 extern "C" int iqhip_pars_branch_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int32_t *score, int32_t *subst) {
-    int rc = pars_engine(e, "iqhip_pars_branch_scores", true);
+    int rc = pars_require(e, "iqhip_pars_branch_scores", true);
     if (rc) return rc;
     rc = pars_check_ends(e, "iqhip_pars_branch_scores", ends, nbranch);
     if (rc) return rc;
@@ -267,7 +244,7 @@ extern "C" int iqhip_pars_branch_scores(iqhip_engine *e, const int32_t *ends, in
 
 extern "C" int iqhip_pars_insert_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int32_t taxon, int32_t *score,
                                         int32_t *best, int32_t *best_score) {
-    int rc = pars_engine(e, "iqhip_pars_insert_scores", true);
+    int rc = pars_require(e, "iqhip_pars_insert_scores", true);
     if (rc) return rc;
     rc = pars_check_ends(e, "iqhip_pars_insert_scores", ends, nbranch);
     if (rc) return rc;
@@ -284,7 +261,7 @@ extern "C" int iqhip_pars_insert_scores(iqhip_engine *e, const int32_t *ends, in
 }
 
 extern "C" int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out) {
-    int rc = pars_engine(e, "iqhip_pars_fetch", true);
+    int rc = pars_require(e, "iqhip_pars_fetch", true);
     if (rc) return rc;
     if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_pars_fetch: null argument");
     if (slot < 0 || slot >= (int64_t)e->ntaxa + e->pars_nvec) return fail(IQHIP_ERR_INVALID, "iqhip_pars_fetch: slot outside [0, ntaxa + nvectors)");
@@ -317,7 +294,7 @@ extern "C" int iqhip_debug_pars_spr_check(int ntaxa, int nvectors, const uint8_t
 
 extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jobs, int njobs, const iqhip_pars_spr_step *steps,
                                    int nsteps, int32_t *score, int32_t *best_step, int32_t *best_score, int32_t *best_job) {
-    int rc = pars_engine(e, "iqhip_pars_spr_scan", true);
+    int rc = pars_require(e, "iqhip_pars_spr_scan", true);
     if (rc) return rc;
     std::vector<int32_t> depth((size_t)std::max(nsteps, 0));
     int max_depth = 0;
@@ -352,13 +329,16 @@ extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jo
         if (depth[(size_t)k] >= 0 && !(steps[k].flags & IQHIP_PARS_SPR_NO_SCORE)) scored++;
     }
     HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
-    ParsTimer tm(e, &e->pars_spr_ms, &e->pars_spr_counts[0], &e->pars_spr_counts[1]);
+    PhaseTimer timer(e, 1);
     int nlaunches = 0;
-    HIPCHK(tm.start());
+    timer.mark();
     HIPCHK(launch_pars_spr(e, reinterpret_cast<const iqhip_pars_spr_job *>(e->pars.ints.p), njobs,
                            reinterpret_cast<const iqhip_pars_spr_step *>(e->pars.ints.p + (size_t)4 * njobs), nsteps, max_depth,
                            e->pars.out.p, &nlaunches));
-    HIPCHK(tm.stop(nlaunches, scored));
+    timer.mark();
+    e->pars_spr_counts[0] += nlaunches;
+    e->pars_spr_counts[1] += scored;
+    pars_add_ms(timer, &e->pars_spr_ms);
     HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     const int32_t *res = e->h_pars_out;

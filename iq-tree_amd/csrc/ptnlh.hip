@@ -1,8 +1,7 @@
-// ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: UFBoot / RELL, the store of
-// per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree topology tests, UFBoot's per-replicate bookkeeping, the EM for +R free-rate models, the
-// empirical-Bayes site rates, the EM for mixture class weights and the per-class log-likelihoods.  Host code only; the kernels
-// are in kernels_rell.hip, kernels_alrt.hip, kernels_topo.hip, kernels_ufboot.hip, kernels_em.hip, kernels_mixem.hip and
-// kernels_classlnl.hip.
+// ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: the scaled pattern-lh fetches,
+// the bootstrap sample matrix and RELL, the store of per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree
+// topology tests and UFBoot's per-replicate bookkeeping.  Host code only; the kernels are in kernels_rell.hip,
+// kernels_alrt.hip, kernels_topo.hip and kernels_ufboot.hip.  (What consumes theta per class is in classlh.hip.)
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -13,8 +12,7 @@
 using namespace iqhip;
 
 // ---- consumers of the device-resident pattern lnL (kernels_rell.hip) ---------------------------
-// the scale counters of a branch's two ends; a leaf carries no scaling events: nullptr
-static int branch_scale_counters(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, const int16_t *sc[2]) {
+int iqhip::branch_scale_counters(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, const int16_t *sc[2]) {
     const iqhip_branch_end ends[2] = {a, b};
     for (int k = 0; k < 2; k++) {
         sc[k] = nullptr;
@@ -61,347 +59,6 @@ extern "C" int iqhip_pattern_lh_cat(iqhip_engine *e, double len, double *out) {
     if (s == hipSuccess) s = hipStreamSynchronize(e->stream);
     hipFree(d_out);
     if (s != hipSuccess) return fail(IQHIP_ERR_HIP, hipGetErrorString(s));
-    return IQHIP_OK;
-}
-
-// ---- EM for +R free-rate models, empirical-Bayes site rates (kernels_em.hip) ----------------------------------------
-// plain engines of 4 / 20 / 64 states only; needs_estep: the call reads what the last E-step left
-static int em_engine(iqhip_engine *e, const char *what, bool needs_theta, bool needs_estep) {
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
-    if (e->nclass > 1) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for mixture models");
-    if (e->asc_active || e->n_unobs > 0)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available with ascertainment bias correction");
-    if (e->embed2 || e->n_user != e->n)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
-    if (needs_theta && !e->theta_valid) return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_compute_theta first");
-    if (needs_estep && (!e->em.valid || e->em.w.cap < (size_t)e->ncat * (size_t)e->nptn_pad))
-        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_em_posteriors first");
-    return IQHIP_OK;
-}
-
-static size_t em_part_rows(const iqhip_engine *e) { return (size_t)((e->nptn_pad + 255) / 256); }
-
-// with iqhip_timing_enable: HIP events around the launches of one call; stop() after the stream has drained
-struct EmTimer {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    iqhip_engine *e;
-    explicit EmTimer(iqhip_engine *e_) : e(e_) {
-        if (e->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess) hipEventRecord(ev[0], e->stream);
-    }
-    void mark() { if (ev[1]) hipEventRecord(ev[1], e->stream); }
-    void stop(double *ms) {
-        float t = 0.0f;
-        if (ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) *ms = t;
-    }
-    ~EmTimer() {
-        for (hipEvent_t x : ev) if (x) hipEventDestroy(x);
-    }
-};
-
-extern "C" int iqhip_debug_em_timing(iqhip_engine *e, double *ms) {
-    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_em_timing: null argument");
-    ms[0] = e->em.ms[0];
-    ms[1] = e->em.ms[1];
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_em_posteriors(iqhip_engine *e, double len, double *cat_sum) {
-    if (!e || !cat_sum) return fail(IQHIP_ERR_INVALID, "iqhip_em_posteriors: null argument");
-    int rc = em_engine(e, "iqhip_em_posteriors", true, false);
-    if (rc) return rc;
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_posteriors: negative or NaN branch length");
-    HIPCHK(use_device(e));
-    const size_t P = (size_t)e->nptn_pad, C = (size_t)e->ncat;
-    e->em.valid = false;
-    HIPCHK(e->em.w.ensure(e, C * P));
-    HIPCHK(e->em.rate.ensure(e, P));
-    HIPCHK(e->em.cat.ensure(e, P));
-    HIPCHK(e->em.part.ensure(e, em_part_rows(e) * 2 * C));
-    HIPCHK(e->em.out.ensure(e, 2 * C));
-    EmTimer timer(e);
-    HIPCHK(launch_em_posteriors(e, len, e->em.w.p, e->em.rate.p, e->em.cat.p, e->em.part.p, e->em.out.p));
-    timer.mark();
-    HIPCHK(hipMemcpyAsync(cat_sum, e->em.out.p, sizeof(double) * C, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    timer.stop(&e->em.ms[0]);
-    e->em.valid = true;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_em_fetch_posteriors(iqhip_engine *e, double *out) {
-    if (!e || !out) return fail(IQHIP_ERR_INVALID, "iqhip_em_fetch_posteriors: null argument");
-    int rc = em_engine(e, "iqhip_em_fetch_posteriors", false, true);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    const size_t P = (size_t)e->nptn_pad, C = (size_t)e->ncat, N = (size_t)e->nptn;
-    std::vector<double> w(C * P);
-    HIPCHK(hipMemcpyAsync(w.data(), e->em.w.p, sizeof(double) * w.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (size_t p = 0; p < N; p++)
-        for (size_t c = 0; c < C; c++) out[p * C + c] = w[c * P + p];
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_em_site_rates(iqhip_engine *e, double *ptn_rate, int32_t *ptn_cat) {
-    if (!e || !ptn_rate || !ptn_cat) return fail(IQHIP_ERR_INVALID, "iqhip_em_site_rates: null argument");
-    int rc = em_engine(e, "iqhip_em_site_rates", false, true);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    HIPCHK(hipMemcpyAsync(ptn_rate, e->em.rate.p, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(ptn_cat, e->em.cat.p, sizeof(int32_t) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_em_objective(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, double *f,
-                                  int64_t *floored) {
-    if (!e || !f) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: null argument");
-    int rc = em_engine(e, "iqhip_em_objective", true, true);
-    if (rc) return rc;
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: negative or NaN branch length");
-    for (int c = 0; c < e->ncat; c++)
-        if (!(e->h_props[c] > 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_em_objective: every category weight must be > 0");
-    HIPCHK(use_device(e));
-    const int16_t *sc[2];
-    rc = branch_scale_counters(e, a, b, sc);
-    if (rc) return rc;
-    const size_t C = (size_t)e->ncat;
-    HIPCHK(e->em.part.ensure(e, em_part_rows(e) * 2 * C));
-    HIPCHK(e->em.out.ensure(e, 2 * C));
-    EmTimer timer(e);
-    HIPCHK(launch_em_objective(e, sc[0], sc[1], len, e->em.w.p, e->em.part.p, e->em.out.p));
-    timer.mark();
-    std::vector<double> res(2 * C);
-    HIPCHK(hipMemcpyAsync(res.data(), e->em.out.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    timer.stop(&e->em.ms[1]);
-    for (size_t c = 0; c < C; c++) {
-        f[c] = res[c];
-        if (floored) floored[c] = (int64_t)res[C + c];
-    }
-    return IQHIP_OK;
-}
-
-// ---- EM for mixture class weights, class posteriors, pattern state frequencies (kernels_mixem.hip) -------------------
-// plain mixture engines of 4 / 20 / 64 states only; needs_lc: the call reads what the last iqhip_mix_class_lh left
-static int mix_engine(iqhip_engine *e, const char *what, bool needs_lc) {
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
-    if (e->asc_active || e->n_unobs > 0)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": mixture models with ascertainment bias correction are not supported");
-    if (e->embed2 || e->n_user != e->n)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
-    if (e->nclass < 2) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": the model is no mixture (one class)");
-    if (needs_lc && (e->mix.model_version != e->model_version || e->mix.nptn_pad != e->nptn_pad || e->mix.nclass != e->nclass ||
-                     e->mix.lc.cap < (size_t)e->nclass * (size_t)e->nptn_pad))
-        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_mix_class_lh first (again after every model change)");
-    return IQHIP_OK;
-}
-
-// rows [nrows][nptn_pad] on the device -> out [nptn][nrows] on the host
-static int mix_fetch_transposed(iqhip_engine *e, const double *d_rows, size_t nrows, double *out) {
-    const size_t P = (size_t)e->nptn_pad, N = (size_t)e->nptn;
-    std::vector<double> rows(nrows * P);
-    HIPCHK(hipMemcpyAsync(rows.data(), d_rows, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (size_t p = 0; p < N; p++)
-        for (size_t r = 0; r < nrows; r++) out[p * nrows + r] = rows[r * P + p];
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_debug_mix_timing(iqhip_engine *e, double *ms, int64_t *launches) {
-    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_mix_timing: null argument");
-    ms[0] = e->mix.ms[0];
-    ms[1] = e->mix.ms[1];
-    if (launches) *launches = e->mix.launches;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_mix_class_lh(iqhip_engine *e, double len, double *out) {
-    if (!e) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh: null argument");
-    int rc = mix_engine(e, "iqhip_mix_class_lh", false);
-    if (rc) return rc;
-    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh needs iqhip_compute_theta first");
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_class_lh: negative or NaN branch length");
-    HIPCHK(use_device(e));
-    const size_t P = (size_t)e->nptn_pad, M = (size_t)e->nclass, C = (size_t)e->ncat;
-    // the components of every class in ascending order: cat_class is an arbitrary map
-    std::vector<int32_t> list(M + 1 + C);
-    size_t at = 0;
-    for (size_t m = 0; m < M; m++) {
-        list[m] = (int32_t)at;
-        for (size_t c = 0; c < C; c++)
-            if ((size_t)e->h_cls[c] == m) list[M + 1 + at++] = (int32_t)c;
-    }
-    list[M] = (int32_t)at;
-    e->mix.model_version = 0;
-    HIPCHK(e->mix.lc.ensure(e, M * P));
-    HIPCHK(e->mix.list.ensure(e, list.size()));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source, and an earlier launch may still read the list)
-    HIPCHK(hipMemcpyAsync(e->mix.list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    EmTimer timer(e);
-    HIPCHK(launch_mix_class_lh(e, len, e->mix.list.p, e->mix.lc.p));
-    timer.mark();
-    HIPCHK(hipStreamSynchronize(e->stream));
-    timer.stop(&e->mix.ms[0]);
-    e->mix.model_version = e->model_version;
-    e->mix.nptn_pad = e->nptn_pad;
-    e->mix.nclass = e->nclass;
-    return out ? mix_fetch_transposed(e, e->mix.lc.p, M, out) : IQHIP_OK;
-}
-
-// ---- per-class log-likelihoods: K candidate models as the K classes of a mixture engine (kernels_classlnl.hip) ----------
-extern "C" int iqhip_debug_class_lnl_timing(iqhip_engine *e, double *ms) {
-    if (!e || !ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_class_lnl_timing: null argument");
-    *ms = e->cl.ms;
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_class_lnl(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double len, const double *class_weight,
-                               const double *class_invar, double *lnl, int64_t *floored) {
-    const char *what = "iqhip_class_lnl";
-    if (!e || !class_weight || !lnl) return fail(IQHIP_ERR_INVALID, "iqhip_class_lnl: null argument");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available on pattern-sharded engines");
-    if (e->asc_active || e->n_unobs > 0)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available with ascertainment bias correction");
-    if (e->embed2 || e->n_user != e->n)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for embedded state counts");
-    if (!e->model_set || !e->mixture_api)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": the model was not set through iqhip_set_mixture_model");
-    if (!e->theta_valid) return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_compute_theta first");
-    if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": negative or NaN branch length");
-    const size_t P = (size_t)e->nptn_pad, N = (size_t)e->nptn, M = (size_t)e->nclass, C = (size_t)e->ncat;
-    for (size_t m = 0; m < M; m++)
-        if (!(class_weight[m] > 0.0) || !std::isfinite(class_weight[m]))
-            return fail(IQHIP_ERR_INVALID, std::string(what) + ": every class weight must be > 0 and finite");
-    HIPCHK(use_device(e));
-    const int16_t *sc[2];
-    int rc = branch_scale_counters(e, a, b, sc);
-    if (rc) return rc;
-    // theta remembers the scale counters of the ends it was built from (either order: build_branch puts a leaf first)
-    if (!((sc[0] == e->theta_a_sc && sc[1] == e->theta_b_sc) || (sc[0] == e->theta_b_sc && sc[1] == e->theta_a_sc)))
-        return fail(IQHIP_ERR_INVALID, std::string(what) + ": theta is not resident for this branch");
-    // the components of every class in ascending order, as iqhip_mix_class_lh
-    std::vector<int32_t> list(M + 1 + C);
-    size_t at = 0, max_comp = 0;
-    for (size_t m = 0; m < M; m++) {
-        list[m] = (int32_t)at;
-        for (size_t c = 0; c < C; c++)
-            if ((size_t)e->h_cls[c] == m) list[M + 1 + at++] = (int32_t)c;
-        max_comp = std::max(max_comp, at - (size_t)list[m]);
-    }
-    list[M] = (int32_t)at;
-    const size_t rows = (size_t)class_lnl_part_rows(e);
-    HIPCHK(e->cl.list.ensure(e, list.size()));
-    HIPCHK(e->cl.cw.ensure(e, M));
-    HIPCHK(e->cl.part.ensure(e, rows * 2 * M));
-    HIPCHK(e->cl.out.ensure(e, 2 * M));
-    std::vector<double> inv;
-    if (class_invar) {   // [class][nptn] -> [class][nptn_pad], padding 0
-        HIPCHK(e->cl.inv.ensure(e, M * P));
-        inv.assign(M * P, 0.0);
-        for (size_t m = 0; m < M; m++) memcpy(&inv[m * P], class_invar + m * N, sizeof(double) * N);
-    }
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable sources, and an earlier launch may still read the buffers)
-    HIPCHK(hipMemcpyAsync(e->cl.list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->cl.cw.p, class_weight, sizeof(double) * M, hipMemcpyHostToDevice, e->stream));
-    if (class_invar) HIPCHK(hipMemcpyAsync(e->cl.inv.p, inv.data(), sizeof(double) * inv.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    EmTimer timer(e);
-    HIPCHK(launch_class_lnl(e, sc[0], sc[1], len, e->cl.list.p, (int)max_comp, e->cl.cw.p, class_invar ? e->cl.inv.p : nullptr,
-                            e->cl.part.p, e->cl.out.p));
-    timer.mark();
-    std::vector<double> res(2 * M);
-    HIPCHK(hipMemcpyAsync(res.data(), e->cl.out.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    timer.stop(&e->cl.ms);
-    for (size_t m = 0; m < M; m++) {
-        lnl[m] = res[m];
-        if (floored) floored[m] = (int64_t)res[M + m];
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_mix_weights_em(iqhip_engine *e, int max_steps, double nsites, double *weights, double *p_invar, int *nsteps,
-                                    int *converged, double *trace) {
-    if (!e || !weights || !nsteps || !converged) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: null argument");
-    int rc = mix_engine(e, "iqhip_mix_weights_em", true);
-    if (rc) return rc;
-    if (max_steps < 1 || max_steps > IQHIP_MIX_MAX_STEPS)
-        return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: max_steps must be 1 .. " + std::to_string(IQHIP_MIX_MAX_STEPS));
-    if (!(nsites > 0.0) || !std::isfinite(nsites)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: nsites must be > 0");
-    const size_t M = (size_t)e->nclass;
-    static_assert(kMixEmUpdateThreads >= 96, "k_mixem_update runs one thread per class: nclass <= ncat <= 96 (iqhip_create)");
-    for (size_t m = 0; m < M; m++)
-        if (!(weights[m] > 0.0) || !std::isfinite(weights[m]))
-            return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: every class weight must be > 0 and finite");
-    if (p_invar && !(*p_invar >= 0.0 && *p_invar < 1.0)) return fail(IQHIP_ERR_INVALID, "iqhip_mix_weights_em: p_invar outside [0, 1)");
-    HIPCHK(use_device(e));
-    const bool use_inv = p_invar && *p_invar > 0.0;
-    std::vector<double> st(MIXEM_HDR + 2 * M + (size_t)max_steps * (M + 1), 0.0);
-    st[MIXEM_PINV] = st[MIXEM_PINV_IN] = use_inv ? *p_invar : 0.0;
-    st[MIXEM_V] = 1.0;
-    st[MIXEM_USE_INV] = use_inv ? 1.0 : 0.0;
-    st[MIXEM_NSITES] = nsites;
-    for (size_t m = 0; m < M; m++) {
-        st[MIXEM_HDR + m] = 1.0;
-        st[MIXEM_HDR + M + m] = weights[m];
-    }
-    HIPCHK(e->mix.state.ensure(e, st.size()));
-    HIPCHK(e->mix.part.ensure(e, (size_t)mixem_part_rows(e) * M));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source)
-    // (the log is not uploaded: step k writes row k before anything reads it, and only the rows below *nsteps are handed out)
-    HIPCHK(hipMemcpyAsync(e->mix.state.p, st.data(), sizeof(double) * (MIXEM_HDR + 2 * M), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    // the whole loop is enqueued: the steps behind the converged one return at once
-    EmTimer timer(e);
-    int64_t launches = 0;
-    for (int k = 0; k < max_steps; k++) {
-        HIPCHK(launch_mixem_step(e, e->mix.lc.p, e->mix.state.p, max_steps, e->mix.part.p));
-        launches += 2;
-    }
-    timer.mark();
-    HIPCHK(hipMemcpyAsync(st.data(), e->mix.state.p, sizeof(double) * st.size(), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    timer.stop(&e->mix.ms[1]);
-    e->mix.launches = launches;
-    *nsteps = (int)st[MIXEM_STEPS];
-    *converged = st[MIXEM_DONE] != 0.0 ? 1 : 0;
-    memcpy(weights, &st[MIXEM_HDR + M], sizeof(double) * M);
-    if (use_inv) *p_invar = st[MIXEM_PINV];
-    if (trace) {
-        const size_t taken = (size_t)*nsteps * (M + 1), all = (size_t)max_steps * (M + 1);
-        memcpy(trace, &st[MIXEM_HDR + 2 * M], sizeof(double) * taken);
-        std::fill(trace + taken, trace + all, 0.0);
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_mix_posteriors(iqhip_engine *e, const double *class_freq, double *post, double *state_freq) {
-    if (!e || (!post && !state_freq) || (state_freq && !class_freq))
-        return fail(IQHIP_ERR_INVALID, "iqhip_mix_posteriors: null argument");
-    int rc = mix_engine(e, "iqhip_mix_posteriors", true);
-    if (rc) return rc;
-    HIPCHK(use_device(e));
-    const size_t P = (size_t)e->nptn_pad, M = (size_t)e->nclass, n = (size_t)e->n;
-    const size_t post_doubles = post ? M * P : 0;
-    HIPCHK(e->mix.post.ensure(e, post_doubles + (state_freq ? n * P : 0)));
-    double *d_post = post ? e->mix.post.p : nullptr, *d_sf = state_freq ? e->mix.post.p + post_doubles : nullptr;
-    if (state_freq) {
-        HIPCHK(e->mix.cfreq.ensure(e, M * n));
-        HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source)
-        HIPCHK(hipMemcpyAsync(e->mix.cfreq.p, class_freq, sizeof(double) * M * n, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    HIPCHK(launch_mix_posteriors(e, e->mix.lc.p, e->mix.cfreq.p, d_post, d_sf));
-    if (post && (rc = mix_fetch_transposed(e, d_post, M, post))) return rc;
-    if (state_freq && (rc = mix_fetch_transposed(e, d_sf, n, state_freq))) return rc;
     return IQHIP_OK;
 }
 
@@ -459,15 +116,8 @@ extern "C" int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end 
 }
 
 // ---- branch tests (SH-aLRT, local bootstrap): the store of per-pattern log-likelihood rows and its consumers --------
-// (kernels_rell.hip k_ptnlh_rows fills rows from batched tasks, kernels_alrt.hip multiplies them with the sample matrix)
-int iqhip::ptnlh_plain_engine(iqhip_engine *e, const char *what) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines keep no per-pattern store");
-    return IQHIP_OK;
-}
-
+// (kernels_rell.hip k_ptnlh_rows fills rows from batched tasks, kernels_alrt.hip multiplies them with the sample matrix;
+// single-device engines only: a pattern-sharded engine keeps no per-pattern store)
 // every row of a list lies inside the store
 static int ptnlh_check_rows(iqhip_engine *e, const char *what, const int32_t *rows, int nrows, const char *hint = "") {
     for (int i = 0; i < nrows; i++)
@@ -477,7 +127,7 @@ static int ptnlh_check_rows(iqhip_engine *e, const char *what, const int32_t *ro
 }
 
 extern "C" int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_reserve");
+    int rc = require(e, "iqhip_ptnlh_reserve", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (nrows < 0 || nrows > (1 << 20)) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_reserve: bad row count");
     HIPCHK(use_device(e));
@@ -499,7 +149,7 @@ extern "C" int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows) {
 }
 
 extern "C" int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_end a, iqhip_branch_end b) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_put_current");
+    int rc = require(e, "iqhip_ptnlh_put_current", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     rc = ptnlh_check_rows(e, "iqhip_ptnlh_put_current", &row, 1, " (iqhip_ptnlh_reserve)");
     if (rc) return rc;
@@ -512,7 +162,7 @@ extern "C" int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_en
 }
 
 extern "C" int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_fetch");
+    int rc = require(e, "iqhip_ptnlh_fetch", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!out) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_fetch: null argument");
     rc = ptnlh_check_rows(e, "iqhip_ptnlh_fetch", &row, 1);
@@ -572,7 +222,7 @@ static int ptnlh_product(iqhip_engine *e, const char *what, const int32_t *rows,
 }
 
 extern "C" int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows, int nsamples, double *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_rell");
+    int rc = require(e, "iqhip_ptnlh_rell", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!rows || !out || nrows < 1) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_rell: bad row list");
     RowList rl;
@@ -589,7 +239,7 @@ extern "C" int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows,
 
 extern "C" int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const double *lh3, int nbranch, int reps_sh,
                                   int reps_lbp, iqhip_branch_support *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_branch_tests");
+    int rc = require(e, "iqhip_branch_tests", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!rows3 || !lh3 || !out || nbranch < 1 || nbranch > (1 << 24) || reps_sh < 0 || reps_lbp < 0)
         return fail(IQHIP_ERR_INVALID, "iqhip_branch_tests: bad arguments");
@@ -610,7 +260,7 @@ extern "C" int iqhip_branch_tests(iqhip_engine *e, const int32_t *rows3, const d
 
 // ---- tree topology tests (evaluateTrees / performAUTest, phylotesting.cpp:1916-2442; kernels_topo.hip) ---------------
 extern "C" int iqhip_ptnlh_upload(iqhip_engine *e, int row, const double *in) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_upload");
+    int rc = require(e, "iqhip_ptnlh_upload", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!in) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_upload: null argument");
     rc = ptnlh_check_rows(e, "iqhip_ptnlh_upload", &row, 1, " (iqhip_ptnlh_reserve)");
@@ -662,7 +312,7 @@ static const int64_t kTopoMaxDraws = (int64_t)1 << 24;   // counts above 2^24 ar
 
 extern "C" int iqhip_gen_boot_samples(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t seed,
                                       uint32_t stream) {
-    int rc = ptnlh_plain_engine(e, "iqhip_gen_boot_samples");
+    int rc = require(e, "iqhip_gen_boot_samples", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (nsamples < 1 || nsamples > 16384) return fail(IQHIP_ERR_INVALID, "iqhip_gen_boot_samples: 1 .. 16384 bootstrap samples");
     if (first_replicate < 0 || first_replicate > INT64_MAX - nsamples - 1)
@@ -696,7 +346,7 @@ static int topo_diff_variance(iqhip_engine *e, const char *what, const int32_t *
 }
 
 extern "C" int iqhip_ptnlh_diff_variance(iqhip_engine *e, const int32_t *rows, int nrows, double *var) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ptnlh_diff_variance");
+    int rc = require(e, "iqhip_ptnlh_diff_variance", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!rows || !var || nrows < 1 || nrows > 4096) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_diff_variance: bad row list");
     rc = ptnlh_check_rows(e, "iqhip_ptnlh_diff_variance", rows, nrows);
@@ -723,7 +373,7 @@ static void topo_confidence_set(const std::vector<double> &share, std::vector<in
 
 extern "C" int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const double *lh, int ntrees, int nsamples, double epsilon,
                                 int weighted, uint64_t tie_seed, iqhip_tree_test *out) {
-    int rc = ptnlh_plain_engine(e, "iqhip_tree_tests");
+    int rc = require(e, "iqhip_tree_tests", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!rows || !lh || !out || ntrees < 2 || ntrees > 4096 || !(epsilon >= 0.0) || !std::isfinite(epsilon))
         return fail(IQHIP_ERR_INVALID, "iqhip_tree_tests: bad arguments (at least two trees)");
@@ -835,7 +485,7 @@ extern "C" int iqhip_tree_tests(iqhip_engine *e, const int32_t *rows, const doub
 
 extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntrees, const double *scales, int nscales,
                                    int nsamples, uint64_t seed, double *bp) {
-    int rc = ptnlh_plain_engine(e, "iqhip_multiscale_bp");
+    int rc = require(e, "iqhip_multiscale_bp", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!rows || !scales || !bp || ntrees < 2 || ntrees > 4096 || nscales < 1 || nscales > 4096 || nsamples < 1)
         return fail(IQHIP_ERR_INVALID, "iqhip_multiscale_bp: bad arguments (at least two trees, one scale, one replicate)");
@@ -888,7 +538,7 @@ extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntr
 
 // ---- ultrafast bootstrap: saveCurrentTree's per-replicate bookkeeping (iqtree.cpp:2676-2786; kernels_ufboot.hip) -----------
 extern "C" int iqhip_ufboot_init(iqhip_engine *e, int nsamples) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ufboot_init");
+    int rc = require(e, "iqhip_ufboot_init", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (nsamples < 1 || nsamples > e->nboot)
         return fail(IQHIP_ERR_INVALID, e->nboot == 0 ? "iqhip_ufboot_init: no bootstrap samples (iqhip_gen_boot_samples / iqhip_set_boot_samples)"
@@ -924,7 +574,7 @@ static int ufboot_ready(iqhip_engine *e, const char *what) {
 extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *trees, int ntrees, double epsilon, double logl_cutoff,
                                    int64_t *counts, double *min_orig_logl) {
     const char *what = "iqhip_ufboot_update";
-    int rc = ptnlh_plain_engine(e, what);
+    int rc = require(e, what, REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!trees || ntrees < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad tree list");
     if (!(epsilon >= 0.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": epsilon must be >= 0");
@@ -970,16 +620,7 @@ extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *tre
     HIPCHK(hipStreamSynchronize(e->stream));
     unsigned long long *d_replaced = reinterpret_cast<unsigned long long *>(e->ufb.res.p);
     double *boot_logl = e->ufb.dbl.p, *boot_orig = e->ufb.dbl.p + S;
-    // with iqhip_timing_enable: three events per chunk (before the product, between, behind the update)
-    std::vector<hipEvent_t> ev;
-    auto mark = [&]() {
-        if (!e->timing) return;
-        hipEvent_t x = nullptr;
-        if (hipEventCreate(&x) == hipSuccess) {
-            hipEventRecord(x, e->stream);
-            ev.push_back(x);
-        }
-    };
+    PhaseTimer timer(e, 2);   // per chunk: before the product, between, behind the update
     int64_t launches = 0;
     hipError_t s = hipSuccess;
     if (n == 0) {   // everything fell to the cutoff: the state is only read for its minimum
@@ -991,13 +632,13 @@ extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *tre
         const RowList &rl = lists[c];
         const int m = (int)(rl.list.size() - (size_t)rl.M);
         if ((rc = bt_stage(e, rl, ksplit, (size_t)S))) break;
-        mark();
+        timer.mark();
         s = launch_alrt_product(e, e->bt.rows.p, rl.M, S, ksplit, e->bt.part.p, e->bt.sums.p);
-        mark();
+        timer.mark();
         if (s == hipSuccess)
             s = launch_ufboot_update(e, e->bt.sums.p, S, e->ufb.entries.p + first, m, epsilon, boot_logl, boot_orig,
                                      e->ufb.counts.p, e->ufb.tree.p, d_replaced, e->ufb.res.p + 1);
-        mark();
+        timer.mark();
         launches += 3;
         first += (size_t)m;
     }
@@ -1006,17 +647,10 @@ extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *tre
         s = hipMemcpyAsync(res.data(), e->ufb.res.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream);
     const hipError_t drained = hipStreamSynchronize(e->stream);
     if (s == hipSuccess) s = drained;
-    double ms[2] = {0.0, 0.0};
-    for (size_t k = 0; k + 2 < ev.size() && ev.size() % 3 == 0; k += 3)
-        for (int h = 0; h < 2; h++) {
-            float t = 0.0f;
-            if (hipEventElapsedTime(&t, ev[k + h], ev[k + h + 1]) == hipSuccess) ms[h] += t;
-        }
-    for (hipEvent_t x : ev) hipEventDestroy(x);
     if (rc) return rc;
     HIPCHK(s);
-    e->ufb.ms[0] = ms[0];
-    e->ufb.ms[1] = ms[1];
+    e->ufb.ms[0] = e->ufb.ms[1] = 0.0;
+    timer.read(e->ufb.ms);
     e->ufb.launches = launches;
     if (counts) {
         unsigned long long replaced;
@@ -1036,7 +670,7 @@ extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *tre
 
 extern "C" int iqhip_ufboot_fetch(iqhip_engine *e, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts,
                                   int64_t *boot_tree) {
-    int rc = ptnlh_plain_engine(e, "iqhip_ufboot_fetch");
+    int rc = require(e, "iqhip_ufboot_fetch", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if ((rc = ufboot_ready(e, "iqhip_ufboot_fetch"))) return rc;
     HIPCHK(use_device(e));
@@ -1050,7 +684,7 @@ extern "C" int iqhip_ufboot_fetch(iqhip_engine *e, double *boot_logl, double *bo
 }
 
 extern "C" int iqhip_debug_ufboot_timing(iqhip_engine *e, double *ms, int64_t *launches) {
-    int rc = ptnlh_plain_engine(e, "iqhip_debug_ufboot_timing");
+    int rc = require(e, "iqhip_debug_ufboot_timing", REQ_SINGLE_DEVICE);
     if (rc) return rc;
     if (!ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_ufboot_timing: null argument");
     ms[0] = e->ufb.ms[0];

@@ -8,18 +8,13 @@
 
 using namespace iqhip;
 
-static int quartet_engine(iqhip_engine *e, const char *what) {
-    if (!e) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null engine");
-    if (e->planner) return fail(IQHIP_ERR_INVALID, std::string(what) + ": not available on a planning-only engine");
-    if (!e->shards.empty() || e->comm)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": pattern-sharded engines are out of scope");
-    if (e->n_user != e->n || e->n != 4)
-        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": 4 states only (the cell tally has 4^4 cells; no embedded state counts)");
-    if (e->nclass > 1 || e->mixture_api) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": mixture models are out of scope");
-    if (e->asc_active || e->n_unobs > 0) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": +ASC is out of scope");
-    if (!e->model_set || !e->aln_set)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_model and iqhip_set_alignment first");
-    return IQHIP_OK;
+// single-device plain 4-state engines (the cell tally has 4^4 cells) without mixture or +ASC, model and alignment set.  A
+// one-class model set through iqhip_set_mixture_model counts as a mixture, and as such before the alignment is asked for
+static int quartet_require(iqhip_engine *e, const char *what) {
+    int rc = require(e, what, REQ_SINGLE_DEVICE | REQ_NO_ASC | REQ_PLAIN_STATES | REQ_STATES_4 | REQ_NO_MIXTURE);
+    if (rc) return rc;
+    if (e->mixture_api) return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": not available for mixture models");
+    return require(e, what, REQ_MODEL_ALN);
 }
 
 // the quartet list and the pattern frequencies; *nsite = the sum of all frequencies
@@ -64,7 +59,7 @@ static int quartet_buffers(iqhip_engine *e, const int32_t *quartets, int nq, int
 }
 
 extern "C" int iqhip_quartet_cells(iqhip_engine *e, const int32_t *quartets, int nq, double *cells, int32_t *nother) {
-    int rc = quartet_engine(e, "iqhip_quartet_cells");
+    int rc = quartet_require(e, "iqhip_quartet_cells");
     if (rc) return rc;
     if (!cells || !nother) return fail(IQHIP_ERR_INVALID, "iqhip_quartet_cells: null argument");
     rc = quartet_inputs(e, "iqhip_quartet_cells", quartets, nq, nullptr);
@@ -87,7 +82,7 @@ extern "C" int iqhip_quartet_cells(iqhip_engine *e, const int32_t *quartets, int
 extern "C" int iqhip_quartet_likelihoods(iqhip_engine *e, const int32_t *quartets, int nq, const double *const_invar, double x1,
                                          double x2, double xacc, int max_steps, double diverge_frac, int iterations,
                                          double tolerance, iqhip_quartet_result *results) {
-    int rc = quartet_engine(e, "iqhip_quartet_likelihoods");
+    int rc = quartet_require(e, "iqhip_quartet_likelihoods");
     if (rc) return rc;
     if (!results) return fail(IQHIP_ERR_INVALID, "iqhip_quartet_likelihoods: null argument");
     if (!(x1 >= 0.0) || x1 > x2 || !std::isfinite(x2) || !(xacc > 0.0) || max_steps < 1)
@@ -146,33 +141,22 @@ extern "C" int iqhip_quartet_likelihoods(iqhip_engine *e, const int32_t *quartet
     a.state_unknown = e->state_unknown;
     a.max_steps = max_steps;
     a.iterations = iterations;
-    // iqhip_timing_enable: device time of the cell and the solve launches (HIP events), summed over the chunks
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (e->timing)
-        for (int k = 0; k < 3; k++) HIPCHK(hipEventCreate(&ev[k]));
-    e->qt_cells_ms = e->qt_solve_ms = 0.0;
+    // iqhip_timing_enable: device time of the cell and the solve launches, summed over the chunks
+    PhaseTimer timer(e, 2);
+    e->qt.ms[0] = e->qt.ms[1] = 0.0;
     for (int64_t first = 0; first < nq; first += chunk) {
         const int m = (int)std::min<int64_t>(chunk, nq - first);
         a.quartets = e->qt.quartets.p + 4 * first;
         a.first = first;
-        if (e->timing) HIPCHK(hipEventRecord(ev[0], e->stream));
+        timer.mark();
         HIPCHK(launch_quartet_cells(e, a.quartets, m, e->qt.cells.p, e->qt.nother.p, e->qt.other.p));
-        if (e->timing) HIPCHK(hipEventRecord(ev[1], e->stream));
+        timer.mark();
         HIPCHK(launch_quartet_solve(e, a, m));
-        if (e->timing) {
-            HIPCHK(hipEventRecord(ev[2], e->stream));
-            HIPCHK(hipEventSynchronize(ev[2]));
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            e->qt_cells_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2]));
-            e->qt_solve_ms += ms;
-        }
+        timer.mark();
     }
-    for (int k = 0; k < 3; k++)
-        if (ev[k]) hipEventDestroy(ev[k]);
     HIPCHK(hipMemcpyAsync(results, e->qt.out.p, sizeof(iqhip_quartet_result) * (size_t)nq, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    timer.read(e->qt.ms);
     int worst = 0;
     for (int64_t q = 0; q < nq && !worst; q++)
         for (int k = 0; k < 3 && !worst; k++) worst = results[q].status[k];
@@ -181,7 +165,7 @@ extern "C" int iqhip_quartet_likelihoods(iqhip_engine *e, const int32_t *quartet
 
 extern "C" int iqhip_debug_quartet_timing(iqhip_engine *e, double *cells_ms, double *solve_ms) {
     if (!e || !e->shards.empty()) return fail(IQHIP_ERR_INVALID, "iqhip_debug_quartet_timing: needs a single-device engine");
-    if (cells_ms) *cells_ms = e->qt_cells_ms;
-    if (solve_ms) *solve_ms = e->qt_solve_ms;
+    if (cells_ms) *cells_ms = e->qt.ms[0];
+    if (solve_ms) *solve_ms = e->qt.ms[1];
     return IQHIP_OK;
 }

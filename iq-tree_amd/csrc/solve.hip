@@ -718,7 +718,7 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, "bad task array");
     if (rows) {
-        const int rc = ptnlh_plain_engine(e, "iqhip_optimize_branch_batch_rows");
+        const int rc = require(e, "iqhip_optimize_branch_batch_rows", REQ_SINGLE_DEVICE);   // (the per-pattern store)
         if (rc) return rc;
         for (int t = 0; t < ntasks; t++)
             if (rows[t] >= e->ptnlh_rows)
