@@ -890,6 +890,16 @@ int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
 #define IQHIP_PLAN_SHAPE_NSLOTS 28
 int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n);
 
+/* Debugging aids, no reference counterpart: the library's memory accounting.  Every device and pinned-host allocation of
+ * every engine and partition group in this process goes through one allocate / free pair, which counts bytes.
+ * iqhip_debug_memory: what is live now -- device memory, and pinned or host staging memory (the plain host staging of a
+ *   planning-only engine counts here; its fake device addresses count as nothing).  Either pointer may be NULL.  After
+ *   every engine and group has been destroyed both are 0.
+ * iqhip_debug_fail_alloc: the nth allocation from now (1-based) returns out-of-memory without a HIP call, the ones
+ *   before and after it are served; 0 clears a pending failure.  Process-wide, like the counts. */
+void iqhip_debug_memory(int64_t *device_bytes, int64_t *host_bytes);
+void iqhip_debug_fail_alloc(int nth);
+
 /* ---- Edge-linked partition models (-q / -spp; PhyloSuperTreePlen::computeFuncDerv, phylosupertreeplen.cpp:530-578):
  * a GROUP of existing single-device engines, one per partition, all running the super tree's topology (a taxon without
  * data in a partition stays in its alignment as an all-unknown row), whose branch lengths are the super tree's times

@@ -38,7 +38,7 @@ IQHIP_SYMBOLS = [
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
     "iqhip_debug_create_planner", "iqhip_debug_plan", "iqhip_timing_plan_bytes", "iqhip_timing_collective_read", "iqhip_optimize_sweep", "iqhip_debug_cherry_tables",
-    "iqhip_debug_path_counts", "iqhip_debug_plan_shape",
+    "iqhip_debug_path_counts", "iqhip_debug_plan_shape", "iqhip_debug_memory", "iqhip_debug_fail_alloc",
     "iqhip_ptnlh_reserve", "iqhip_ptnlh_put_current", "iqhip_ptnlh_fetch", "iqhip_optimize_branch_batch_rows",
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
     "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
@@ -229,6 +229,10 @@ def libiqhip():
     lib.iqhip_debug_path_counts.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_plan.argtypes = [vp, C.POINTER(NodeOp), C.c_int]
     lib.iqhip_debug_plan_shape.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+    lib.iqhip_debug_memory.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.iqhip_debug_memory.restype = None
+    lib.iqhip_debug_fail_alloc.argtypes = [C.c_int]
+    lib.iqhip_debug_fail_alloc.restype = None
     i32p = C.POINTER(C.c_int32)
     lib.iqhip_ptnlh_reserve.argtypes = [vp, C.c_int]
     lib.iqhip_ptnlh_put_current.argtypes = [vp, C.c_int, BranchEnd, BranchEnd]
@@ -945,6 +949,20 @@ def comm_unique_id():
     if lib.iqhip_comm_unique_id(buf) != 0:
         raise HostError(lib.iqhip_last_error().decode())
     return buf.raw
+
+
+def debug_memory():
+    """iqhip_debug_memory: (device bytes, pinned / host staging bytes) live through the library's owners in this process."""
+    dev, host = C.c_int64(0), C.c_int64(0)
+    libiqhip().iqhip_debug_memory(C.byref(dev), C.byref(host))
+    return dev.value, host.value
+
+
+def debug_fail_alloc(nth):
+    """iqhip_debug_fail_alloc: the nth allocation from now (1-based) fails with out-of-memory; 0 clears it."""
+    libiqhip().iqhip_debug_fail_alloc(int(nth))
+
+
 LM_PER_NODE, LM_ALL_BRANCH = 0, 1
 SEQ_DNA, SEQ_PROTEIN, SEQ_CODON, SEQ_OTHER = 0, 1, 2, 3
 

@@ -86,14 +86,13 @@ int nccl_fail(Rccl &R, const char *what, ncclResult_t s) {
 // k_reduce so that the single-GPU path has no D2H copy).  A comm engine gets a device vector instead and copies
 // the few doubles it needs back after the all-reduce (read_result's "caller-bound buffer" path).
 int comm_use_device_result(iqhip_engine *e) {
-    if (e->d_result_dev) return IQHIP_OK;
+    if (e->d_result_dev.p) return IQHIP_OK;
     if (e->d_result != e->d_result_own)
         return set_error(IQHIP_ERR_INVALID, "a caller-bound result buffer and an engine communicator exclude each other");
-    if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess ||
-        hipMalloc((void **)&e->d_result_dev, sizeof(double) * (size_t)e->result_cap) != hipSuccess)
+    if (hipSetDevice(e->device) != hipSuccess || e->d_result_dev.ensure(e, (size_t)e->result_cap) != hipSuccess)
         return set_error(IQHIP_ERR_NOMEM, "device result vector");
-    hipMemsetAsync(e->d_result_dev, 0, sizeof(double) * (size_t)e->result_cap, e->stream);
-    e->d_result = e->d_result_dev;
+    hipMemsetAsync(e->d_result_dev.p, 0, sizeof(double) * (size_t)e->result_cap, e->stream);
+    e->d_result = e->d_result_dev.p;
     return IQHIP_OK;
 }
 

@@ -23,6 +23,12 @@ int set_error(int code, const std::string &msg) {
 double debug_build_us = 0.0;
 }  // namespace iqhip
 
+extern "C" void iqhip_debug_memory(int64_t *device_bytes, int64_t *host_bytes) {
+    if (device_bytes) *device_bytes = g_mem_bytes[0].load();
+    if (host_bytes) *host_bytes = g_mem_bytes[1].load();
+}
+extern "C" void iqhip_debug_fail_alloc(int nth) { g_fail_alloc_in.store(nth > 0 ? nth : 0); }
+
 extern "C" const char *iqhip_last_error(void) { return g_err.c_str(); }
 extern "C" int iqhip_abi_version(void) { return IQHIP_ABI_VERSION; }
 extern "C" int iqhip_device_count(void) {
@@ -181,87 +187,55 @@ extern "C" int iqhip_create(iqhip_engine **out, int device, int nstates, int nca
     }
     e->own_stream = true;
     const size_t P = (size_t)e->nptn_pad;
-    bool ok = dmalloc(&e->d_states, (size_t)ntaxa * P) == hipSuccess &&
-              dmalloc(&e->d_freq, P) == hipSuccess && dmalloc(&e->d_invar, P) == hipSuccess &&
-              dmalloc(&e->d_theta, P * e->block) == hipSuccess &&
-              dmalloc(&e->d_pattern_lh, P) == hipSuccess;
     e->result_cap = 8 + 16384;  // up to 16384 node updates per submission
+    const size_t nposts = (size_t)2 * kNewtonPostEpochs * (2 * e->num_cus) * 2;
     // default result buffer: pinned host memory mapped into the device address space -- the
     // reduction kernel writes the handful of result doubles straight to the host (no D2H copy
     // on the critical path); a caller-bound device buffer (RCCL) replaces it
-    ok = ok && hipHostMalloc((void **)&e->h_result, e->result_cap * sizeof(double), hipHostMallocMapped) == hipSuccess &&
-         hipHostGetDevicePointer((void **)&e->d_result_own, e->h_result, 0) == hipSuccess &&
-         hipHostMalloc((void **)&e->h_done, 64, hipHostMallocMapped) == hipSuccess &&
-         hipHostGetDevicePointer((void **)&e->d_done, (void *)e->h_done, 0) == hipSuccess &&
-         hipEventCreateWithFlags(&e->staging_free, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
+    const bool ok = e->d_states.ensure(e, (size_t)ntaxa * P) == hipSuccess && e->d_freq.ensure(e, P) == hipSuccess &&
+                    e->d_invar.ensure(e, P) == hipSuccess && e->d_theta.ensure(e, P * e->block) == hipSuccess &&
+                    e->d_pattern_lh.ensure(e, P) == hipSuccess &&
+                    e->h_result.ensure(e, (size_t)e->result_cap, true) == hipSuccess &&
+                    hipHostGetDevicePointer((void **)&e->d_result_own, e->h_result.p, 0) == hipSuccess &&
+                    e->h_done.ensure(e, 8, true) == hipSuccess &&
+                    hipHostGetDevicePointer((void **)&e->d_done, (void *)e->h_done.p, 0) == hipSuccess &&
+                    hipEventCreateWithFlags(&e->staging_free, hipEventDisableTiming) == hipSuccess &&
+                    e->dummy.plh.ensure(e, P * e->block) == hipSuccess && e->dummy.sc.ensure(e, P) == hipSuccess &&
+                    e->d_newton_partials.ensure(e, (size_t)4 * e->num_cus) == hipSuccess &&
+                    e->d_newton_barrier.ensure(e, 2) == hipSuccess && e->d_fold_ticket.ensure(e, 4) == hipSuccess &&
+                    e->d_newton_posts.ensure(e, nposts) == hipSuccess &&
+                    e->d_fold_flags.ensure(e, (size_t)e->result_cap) == hipSuccess;
+    if (!ok) {   // (nothing has been enqueued on the half-built engine)
         iqhip_destroy(e);
         return fail(IQHIP_ERR_NOMEM, "iqhip_create: device allocation failed");
     }
-    ok = dmalloc(&e->dummy.plh, P * e->block) == hipSuccess && dmalloc(&e->dummy.sc, P) == hipSuccess;
-    if (!ok) {
-        iqhip_destroy(e);
-        return fail(IQHIP_ERR_NOMEM, "iqhip_create: device allocation failed");
-    }
-    hipMemsetAsync(e->dummy.plh, 0, P * e->block * sizeof(double), e->stream);
-    hipMemsetAsync(e->dummy.sc, 0, P * sizeof(int16_t), e->stream);
-    {
-        ok = dmalloc(&e->d_newton_partials, (size_t)4 * e->num_cus) == hipSuccess &&
-             dmalloc(&e->d_newton_barrier, 2) == hipSuccess && dmalloc(&e->d_fold_ticket, 4) == hipSuccess &&
-             dmalloc(&e->d_newton_posts, (size_t)2 * kNewtonPostEpochs * (2 * e->num_cus) * 2) == hipSuccess &&
-             dmalloc(&e->d_fold_flags, (size_t)e->result_cap) == hipSuccess;
-        if (ok) hipMemsetAsync(e->d_newton_barrier, 0, 2 * sizeof(unsigned int), e->stream);
-        if (ok) hipMemsetAsync(e->d_newton_posts, 0xFF, (size_t)2 * kNewtonPostEpochs * (2 * e->num_cus) * 2 * sizeof(double), e->stream);
-        if (ok) hipMemsetAsync(e->d_fold_ticket, 0, 4 * sizeof(unsigned int), e->stream);
-        if (ok) hipMemsetAsync(e->d_fold_flags, 0, (size_t)e->result_cap * sizeof(int), e->stream);
-        if (!ok) {
-            iqhip_destroy(e);
-            return fail(IQHIP_ERR_NOMEM, "iqhip_create: device allocation failed");
-        }
-    }
+    hipMemsetAsync(e->dummy.plh.p, 0, P * e->block * sizeof(double), e->stream);
+    hipMemsetAsync(e->dummy.sc.p, 0, P * sizeof(int16_t), e->stream);
+    hipMemsetAsync(e->d_newton_barrier.p, 0, 2 * sizeof(unsigned int), e->stream);
+    hipMemsetAsync(e->d_newton_posts.p, 0xFF, nposts * sizeof(double), e->stream);
+    hipMemsetAsync(e->d_fold_ticket.p, 0, 4 * sizeof(unsigned int), e->stream);
+    hipMemsetAsync(e->d_fold_flags.p, 0, (size_t)e->result_cap * sizeof(int), e->stream);
     e->d_result = e->d_result_own;
-    hipMemsetAsync(e->d_theta, 0, P * e->block * sizeof(double), e->stream);
-    hipMemsetAsync(e->d_pattern_lh, 0, P * sizeof(double), e->stream);
-    memset(e->h_result, 0, e->result_cap * sizeof(double));
-    *e->h_done = 0;
+    hipMemsetAsync(e->d_theta.p, 0, P * e->block * sizeof(double), e->stream);
+    hipMemsetAsync(e->d_pattern_lh.p, 0, P * sizeof(double), e->stream);
+    memset(e->h_result.p, 0, e->result_cap * sizeof(double));
+    *e->h_done.p = 0;
     hipStreamSynchronize(e->stream);
     *out = e;
     return IQHIP_OK;
 }
 
+// (every DevBuf and PinBuf of the engine, its slabs included, frees itself when the engine is deleted: the device is
+// current and the stream drained by then; a sharded front and a planning-only engine have no device and no stream)
 extern "C" void iqhip_destroy(iqhip_engine *e) {
     if (!e) return;
-    if (!e->shards.empty()) {
-        sharded::destroy(e);
-        delete e;
-        return;
-    }
-    if (e->planner) {
-        free(e->h_ops);
-        delete e;
-        return;
-    }
+    if (!e->shards.empty()) sharded::destroy(e);
     use_device(e);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->pair) iqhip_destroy(e->pair);   // (runs on this engine's stream, which it does not own)
     e->pair = nullptr;
     comm_destroy(e);
     if (e->stream) hipStreamSynchronize(e->stream);
-    for (auto &s : e->slabs) {
-        if (s.plh) hipFree(s.plh);
-        if (s.sc) hipFree(s.sc);
-    }
-    // (every DevBuf of the engine frees itself when the engine is deleted below)
-    void *ptrs[] = {e->d_states, e->d_freq, e->d_invar, e->d_ops, e->d_theta, e->d_pattern_lh, e->d_leaf_tab, e->dummy.plh,
-                    e->dummy.sc, e->d_newton_partials, e->d_newton_barrier, e->d_newton_posts, e->d_fold_ticket,
-                    e->d_fold_flags, e->d_ptn_scaled, e->d_boot, e->d_ptnlh, e->d_freq_prefix, e->d_sweep_desc,
-                    e->d_cherry_tab, e->d_result_dev, e->d_nstate};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    void *pinned[] = {e->h_ops, e->h_nstate, e->h_pars_ops, e->h_pars_ends, e->h_pars_out, e->h_sweep_desc,
-                      e->h_plan_arena, e->h_result, (void *)e->h_done};
-    for (void *h : pinned)
-        if (h) hipHostFree(h);
     if (e->staging_free) hipEventDestroy(e->staging_free);
     for (auto &p : e->tev) {
         hipEventDestroy(p.first);
@@ -298,22 +272,12 @@ static int new_slab(iqhip_engine *e, int *idx) {
     }
     Slab s;
     const size_t P = (size_t)e->nptn_pad;
-    if (e->planner) {
-        s.plh = fake_alloc<double>(e, P * e->block);
-        s.sc = fake_alloc<int16_t>(e, P);
-        e->slabs.push_back(s);
-        *idx = (int)e->slabs.size() - 1;
-        return IQHIP_OK;
+    if (s.plh.ensure(e, P * e->block) != hipSuccess || s.sc.ensure(e, P) != hipSuccess) return fail(IQHIP_ERR_NOMEM, "slab alloc");
+    if (!e->planner) {   // padded lanes must hold finite values from the start
+        hipMemsetAsync(s.plh.p, 0, P * e->block * sizeof(double), e->stream);
+        hipMemsetAsync(s.sc.p, 0, P * sizeof(int16_t), e->stream);
     }
-    if (dmalloc(&s.plh, P * e->block) != hipSuccess) return fail(IQHIP_ERR_NOMEM, "slab alloc");
-    if (dmalloc(&s.sc, P) != hipSuccess) {
-        hipFree(s.plh);
-        return fail(IQHIP_ERR_NOMEM, "slab alloc");
-    }
-    // padded lanes must hold finite values from the start
-    hipMemsetAsync(s.plh, 0, P * e->block * sizeof(double), e->stream);
-    hipMemsetAsync(s.sc, 0, P * sizeof(int16_t), e->stream);
-    e->slabs.push_back(s);
+    e->slabs.push_back(std::move(s));
     *idx = (int)e->slabs.size() - 1;
     return IQHIP_OK;
 }
@@ -384,7 +348,7 @@ extern "C" int iqhip_set_ptn_freq(iqhip_engine *e, const double *ptn_freq) {
     HIPCHK(use_device(e));
     std::vector<double> tmp((size_t)e->nptn_pad, 0.0);
     memcpy(tmp.data(), ptn_freq, sizeof(double) * (size_t)e->nptn);
-    HIPCHK(hipMemcpyAsync(e->d_freq, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(e->d_freq.p, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->freq_prefix_valid = false;   // (iqhip_gen_boot_samples rebuilds its prefix sums)
@@ -399,7 +363,7 @@ extern "C" int iqhip_set_ptn_invar(iqhip_engine *e, const double *ptn_invar) {
     HIPCHK(use_device(e));
     std::vector<double> tmp((size_t)e->nptn_pad, 0.0);
     memcpy(tmp.data(), ptn_invar, sizeof(double) * (size_t)e->nptn);
-    HIPCHK(hipMemcpyAsync(e->d_invar, tmp.data(), tmp.size() * sizeof(double),
+    HIPCHK(hipMemcpyAsync(e->d_invar.p, tmp.data(), tmp.size() * sizeof(double),
                           hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
@@ -433,7 +397,7 @@ extern "C" int iqhip_set_alignment(iqhip_engine *e, const uint8_t *states, const
                 return fail(IQHIP_ERR_INVALID, "iqhip_set_alignment: state > STATE_UNKNOWN");
         memcpy(tmp.data() + (size_t)t * P, src, N);
     }
-    HIPCHK(hipMemcpyAsync(e->d_states, tmp.data(), tmp.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_states.p, tmp.data(), tmp.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->pars_ready = false;
     int rc = iqhip_set_ptn_freq(e, ptn_freq);
@@ -488,7 +452,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
             e->theta_valid = false;
             // k_newton's posted exchange resets, per launch, the slots its OWN grid used in the other parity; the grid
             // follows ntiles, so after a layout change start both parities from the all-ones state again
-            HIPCHK(hipMemsetAsync(e->d_newton_posts, 0xFF, (size_t)2 * kNewtonPostEpochs * (2 * e->num_cus) * 2 * sizeof(double), e->stream));
+            HIPCHK(hipMemsetAsync(e->d_newton_posts.p, 0xFF, (size_t)2 * kNewtonPostEpochs * (2 * e->num_cus) * 2 * sizeof(double), e->stream));
             e->newton_post_launches = 0;
         }
     }
@@ -800,8 +764,8 @@ static int build_cherry_tables(iqhip_engine *e) {
         int idx;
         rc = slab_for_key(p, ops[i].dst_key, false, &idx);
         if (rc) return rc;
-        src[i] = p->slabs[idx].plh;
-        dst[i] = e->d_cherry_tab + (size_t)e->plan.cherry_jobs[i] * per;
+        src[i] = p->slabs[idx].plh.p;
+        dst[i] = e->d_cherry_tab.p + (size_t)e->plan.cherry_jobs[i] * per;
     }
     HIPCHK(launch_cherry_transpose(e, src.data(), dst.data(), n, e->cherry_npairs));
     for (int i = 0; i < n; i++) e->cherry_slots[e->plan.cherry_jobs[i]].model_version = e->model_version;
@@ -836,7 +800,7 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
         // (a cached plan skipped build_plan, which is where a model change is normally noticed)
         const int njobs = leaf_tables_follow_model(e) ? e->plan.nleaf_tabs : e->plan.tab_dirty;
         if (njobs > 0)
-            HIPCHK(launch_leaf_tables(e, reinterpret_cast<const TabJob *>(e->d_ops + e->plan.jobs_off), njobs));
+            HIPCHK(launch_leaf_tables(e, reinterpret_cast<const TabJob *>(e->d_ops.p + e->plan.jobs_off), njobs));
         e->plan.tab_dirty = 0;  // built; the same (cached) plan needs nothing until a length or the model changes
     }
     if (!e->plan.cherry_jobs.empty()) {
@@ -844,9 +808,9 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
         if (rc) return rc;
     }
     if (e->plan.uses_cherry)
-        for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops[k].cherry != nullptr;
+        for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops.p[k].cherry != nullptr;
     timing_begin(e);
-    const int *table = reinterpret_cast<const int *>(e->d_ops + e->plan.table_off);
+    const int *table = reinterpret_cast<const int *>(e->d_ops.p + e->plan.table_off);
     {   // the stages of independent subtrees, level by level: one launch each, one set of workgroups per unit
         int off = 2;
         for (int n : e->plan.stage_units) {
@@ -877,7 +841,7 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
 
 int iqhip::read_result(iqhip_engine *e, int ndoubles) {
     if (e->d_result != e->d_result_own)  // caller-bound device buffer
-        HIPCHK(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double) * ndoubles, hipMemcpyDeviceToHost,
+        HIPCHK(hipMemcpyAsync(e->h_result.p, e->d_result, sizeof(double) * ndoubles, hipMemcpyDeviceToHost,
                               e->stream));
     else if (e->poll_pending) {
         // the last kernel of the submission is a k_reduce that publishes a sequence number in mapped host memory:
@@ -886,12 +850,12 @@ int iqhip::read_result(iqhip_engine *e, int ndoubles) {
         e->poll_pending = false;
         const unsigned long long want = e->result_seq;
         for (int spin = 0; spin < 200000; spin++) {
-            if (*e->h_done == want) {
+            if (*e->h_done.p == want) {
                 std::atomic_thread_fence(std::memory_order_acquire);
                 e->staging_busy = false;  // (in-order stream: the plan upload finished long before k_reduce)
                 if (e->folded_rows >= 0) {   // folded reduction: unflagged sum_scale rows were not written (fold_tail)
-                    if (e->h_result[2 + e->folded_rows] == 0.0)
-                        for (int k = 0; k < e->folded_rows; k++) e->h_result[2 + k] = 0.0;
+                    if (e->h_result.p[2 + e->folded_rows] == 0.0)
+                        for (int k = 0; k < e->folded_rows; k++) e->h_result.p[2 + k] = 0.0;
                     e->folded_rows = -1;
                 }
                 return IQHIP_OK;
@@ -903,8 +867,8 @@ int iqhip::read_result(iqhip_engine *e, int ndoubles) {
     HIPCHK(hipStreamSynchronize(e->stream));
     e->staging_busy = false;
     if (e->folded_rows >= 0) {
-        if (e->h_result[2 + e->folded_rows] == 0.0)
-            for (int k = 0; k < e->folded_rows; k++) e->h_result[2 + k] = 0.0;
+        if (e->h_result.p[2 + e->folded_rows] == 0.0)
+            for (int k = 0; k < e->folded_rows; k++) e->h_result.p[2 + k] = 0.0;
         e->folded_rows = -1;
     }
     return IQHIP_OK;
@@ -914,8 +878,8 @@ void iqhip::result_arrived(iqhip_engine *e) {
     e->poll_pending = false;
     e->staging_busy = false;
     if (e->folded_rows >= 0) {
-        if (e->h_result[2 + e->folded_rows] == 0.0)
-            for (int k = 0; k < e->folded_rows; k++) e->h_result[2 + k] = 0.0;
+        if (e->h_result.p[2 + e->folded_rows] == 0.0)
+            for (int k = 0; k < e->folded_rows; k++) e->h_result.p[2 + k] = 0.0;
         e->folded_rows = -1;
     }
 }
@@ -923,14 +887,14 @@ void iqhip::result_arrived(iqhip_engine *e) {
 // the NaN/Inf repair of phylokernel.h:848-866 / :1100-1122, done on the (rare) slow path
 static int repair_lnl(iqhip_engine *e, double *lnl) {
     std::vector<double> plh((size_t)e->nptn_pad), freq((size_t)e->nptn_pad);
-    HIPCHK(hipMemcpy(plh.data(), e->d_pattern_lh, sizeof(double) * plh.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(freq.data(), e->d_freq, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(plh.data(), e->d_pattern_lh.p, sizeof(double) * plh.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(freq.data(), e->d_freq.p, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
     double s = 0.0;
     for (int64_t p = 0; p < e->nptn; p++) {
         if (isnan(plh[p]) || isinf(plh[p])) plh[p] = kLogScalingThreshold * 4;
         s += plh[p] * freq[p];
     }
-    HIPCHK(hipMemcpy(e->d_pattern_lh, plh.data(), sizeof(double) * plh.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_pattern_lh.p, plh.data(), sizeof(double) * plh.size(), hipMemcpyHostToDevice));
     *lnl = s;
     return IQHIP_OK;
 }
@@ -948,7 +912,7 @@ static int asc_finish_lnl(iqhip_engine *e, double *lnl) {
     e->pattern_lh_shift = 0.0;
     if (!e->asc_active) return IQHIP_OK;
     double lp;
-    const int rc = asc_log_term(e->h_result[1], &lp);
+    const int rc = asc_log_term(e->h_result.p[1], &lp);
     if (rc) return rc;
     e->pattern_lh_shift = lp;
     *lnl -= e->asc_nsites * lp;
@@ -968,7 +932,7 @@ static int repair_lnl_comm(iqhip_engine *e, double *lnl) {
     if (rc) return rc;
     rc = read_result(e, 1);
     if (rc) return rc;
-    *lnl = e->h_result[0];
+    *lnl = e->h_result.p[0];
     return IQHIP_OK;
 }
 
@@ -983,7 +947,7 @@ extern "C" int iqhip_update_partials(iqhip_engine *e, const iqhip_node_op *ops, 
     rc = read_result(e, 2 + nops);
     if (rc) return rc;
     if (sum_scale)
-        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result[2 + k];
+        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result.p[2 + k];
     return IQHIP_OK;
 }
 
@@ -998,8 +962,8 @@ extern "C" int iqhip_traverse_lnl(iqhip_engine *e, const iqhip_node_op *ops, int
     rc = read_result(e, 2 + nops);
     if (rc) return rc;
     if (sum_scale)
-        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result[2 + k];
-    double v = e->h_result[0];
+        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result.p[2 + k];
+    double v = e->h_result.p[0];
     if (isnan(v) || isinf(v)) {
         rc = repair_lnl_comm(e, &v);
         if (rc) return rc;
@@ -1061,7 +1025,7 @@ extern "C" int iqhip_derv_async(iqhip_engine *e, double len) {
     if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
     const int nrows = e->n_unobs > 0 ? 5 : 2;  // +ASC: prob_const, df_const, ddf_const as well
     if (e->asc_active && e->n_unobs == 0) {   // a shard without unobserved patterns contributes zeros to those three sums
-        if (e->d_result == e->d_result_own) e->h_result[2] = e->h_result[3] = e->h_result[4] = 0.0;
+        if (e->d_result == e->d_result_own) e->h_result.p[2] = e->h_result.p[3] = e->h_result.p[4] = 0.0;
         else HIPCHK(hipMemsetAsync(e->d_result + 2, 0, 3 * sizeof(double), e->stream));
     }
     rc = ensure_slab_rows(e, nrows);
@@ -1081,11 +1045,11 @@ extern "C" int iqhip_derv(iqhip_engine *e, double len, double *df, double *ddf) 
     if (rc) return rc;
     rc = read_result(e, e->asc_active ? 5 : 2);
     if (rc) return rc;
-    double a = e->h_result[0], b = e->h_result[1];
+    double a = e->h_result.p[0], b = e->h_result.p[1];
     if (isnan(a) || isinf(a)) { a = 0.0; b = 0.0; }  // phylokernel.h:647-651
     if (e->asc_active) {  // phylokernel.h:719-724
-        const double prob_const = 1.0 - e->h_result[2];
-        const double df_frac = e->h_result[3] / prob_const, ddf_frac = e->h_result[4] / prob_const;
+        const double prob_const = 1.0 - e->h_result.p[2];
+        const double df_frac = e->h_result.p[3] / prob_const, ddf_frac = e->h_result.p[4] / prob_const;
         a += e->asc_nsites * df_frac;
         b += e->asc_nsites * (ddf_frac + df_frac * df_frac);
     }
@@ -1132,7 +1096,7 @@ extern "C" int iqhip_lnl_from_theta(iqhip_engine *e, double len, double *lnl) {
     if (rc) return rc;
     rc = read_result(e, 2);
     if (rc) return rc;
-    double v = e->h_result[0];
+    double v = e->h_result.p[0];
     if (isnan(v) || isinf(v)) {
         rc = repair_lnl_comm(e, &v);
         if (rc) return rc;
@@ -1173,7 +1137,7 @@ extern "C" int iqhip_result_read(iqhip_engine *e, double *out, int ndoubles) {
     HIPCHK(use_device(e));
     int rc = read_result(e, ndoubles);
     if (rc) return rc;
-    memcpy(out, e->h_result, sizeof(double) * ndoubles);
+    memcpy(out, e->h_result.p, sizeof(double) * ndoubles);
     return IQHIP_OK;
 }
 
@@ -1219,7 +1183,7 @@ extern "C" int iqhip_fetch_partial(iqhip_engine *e, uint64_t key, double *out) {
     int idx;
     int rc = slab_for_key(e, key, false, &idx);
     if (rc) return rc;
-    return fetch_vec(e, e->slabs[idx].plh, out);
+    return fetch_vec(e, e->slabs[idx].plh.p, out);
 }
 
 extern "C" int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double *partial_lh,
@@ -1243,8 +1207,8 @@ extern "C" int iqhip_upload_partial(iqhip_engine *e, uint64_t key, const double 
     std::vector<int16_t> sc((size_t)e->nptn_pad, 0);
     memcpy(sc.data(), scale_num, sizeof(int16_t) * (size_t)e->nptn);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(e->slabs[idx].plh, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->slabs[idx].sc, sc.data(), sc.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->slabs[idx].plh.p, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->slabs[idx].sc.p, sc.data(), sc.size() * sizeof(int16_t), hipMemcpyHostToDevice));
     return IQHIP_OK;
 }
 
@@ -1252,7 +1216,7 @@ extern "C" int iqhip_fetch_theta(iqhip_engine *e, double *out) {
     if (!e || !out) return fail(IQHIP_ERR_INVALID, "null argument");
     if (!e->shards.empty()) return sharded::fetch_vec(e, 0, true, out);
     HIPCHK(use_device(e));
-    return fetch_vec(e, e->d_theta, out);
+    return fetch_vec(e, e->d_theta.p, out);
 }
 
 extern "C" int iqhip_fetch_scale_num(iqhip_engine *e, uint64_t key, int16_t *out) {
@@ -1263,7 +1227,7 @@ extern "C" int iqhip_fetch_scale_num(iqhip_engine *e, uint64_t key, int16_t *out
     int rc = slab_for_key(e, key, false, &idx);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out, e->slabs[idx].sc, sizeof(int16_t) * (size_t)e->nptn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, e->slabs[idx].sc.p, sizeof(int16_t) * (size_t)e->nptn, hipMemcpyDeviceToHost));
     return IQHIP_OK;
 }
 
@@ -1272,7 +1236,7 @@ extern "C" int iqhip_fetch_pattern_lh(iqhip_engine *e, double *out) {
     if (!e->shards.empty()) return sharded::fetch_pattern_lh(e, out, 0, iqhip_branch_end{0, -1, 0}, iqhip_branch_end{0, -1, 0});
     HIPCHK(use_device(e));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out, e->d_pattern_lh, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, e->d_pattern_lh.p, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost));
     if (e->asc_active) {  // phylokernel.h:1013-1014: observed patterns only
         const int64_t nobs = e->nptn - e->n_unobs;
         for (int64_t p = 0; p < nobs; p++) out[p] -= e->pattern_lh_shift;
@@ -1331,17 +1295,17 @@ extern "C" int iqhip_timing_plan_bytes(iqhip_engine *e, double *stored, double *
         const double P = (double)e->nptn_pad, V = (double)e->block * 8.0;
         // k_traverse4w takes a child that is the previous op's result from registers, within one segment: a wave starts
         // every segment (and so every launch) with nothing held, whatever op k - 1 of the array was
-        const bool hands_over = e->wide4 && !e->wide4_generic && e->h_ops && e->last_nops > 0;
+        const bool hands_over = e->wide4 && !e->wide4_generic && e->h_ops.p && e->last_nops > 0;
         std::vector<char> seg_first(hands_over ? (size_t)e->last_nops : 0, 0);
         if (hands_over) {
-            const int *tab = reinterpret_cast<const int *>(e->h_ops + e->plan.table_off);
+            const int *tab = reinterpret_cast<const int *>(e->h_ops.p + e->plan.table_off);
             for (int u = 0; u <= e->plan.nunits; u++)
                 if (tab[2 * u + 1] > 0 && tab[2 * u] >= 0 && tab[2 * u] < e->last_nops) seg_first[tab[2 * u]] = 1;
         }
-        for (int k = 0; k < e->last_nops && e->h_ops; k++) {
-            const DevOp &d = e->h_ops[k];
+        for (int k = 0; k < e->last_nops && e->h_ops.p; k++) {
+            const DevOp &d = e->h_ops.p[k];
             st += P * (V + 2.0);
-            const double *held = (hands_over && k > 0 && !seg_first[k]) ? e->h_ops[k - 1].dst : nullptr;
+            const double *held = (hands_over && k > 0 && !seg_first[k]) ? e->h_ops.p[k - 1].dst : nullptr;
             if (d.left_kind == CHILD_LEAF) ld += P;
             else if ((d.left_kind == CHILD_PF || d.left_kind == CHILD_LOAD) && d.pf != held) ld += P * (V + 2.0);
             if (d.right_kind == CHILD_LEAF) ld += P; else if (d.right_kind == CHILD_LOAD && d.ld != held) ld += P * (V + 2.0);
@@ -1411,9 +1375,9 @@ extern "C" int iqhip_debug_create_planner(iqhip_engine **out, int nstates, int n
     e->num_cus = num_cus;
     configure_engine(e, -1, nstates, nstates, ncat, nptn, ntaxa);
     const size_t P = (size_t)e->nptn_pad;
-    e->d_states = fake_alloc<uint8_t>(e, (size_t)ntaxa * P);
-    e->dummy.plh = fake_alloc<double>(e, P * e->block);
-    e->dummy.sc = fake_alloc<int16_t>(e, P);
+    e->d_states.ensure(e, (size_t)ntaxa * P);   // (fake addresses: these cannot fail)
+    e->dummy.plh.ensure(e, P * e->block);
+    e->dummy.sc.ensure(e, P);
     e->result_cap = 8 + 16384;
     e->state_unknown = state_unknown;
     e->nclass = nclass;
@@ -1446,7 +1410,7 @@ extern "C" int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int n
         e->cherry_built_total += (int64_t)e->plan.cherry_jobs.size();
         for (int slot : e->plan.cherry_jobs) e->cherry_slots[slot].model_version = e->model_version;   // ("built")
         e->plan.cherry_jobs.clear();
-        for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops[k].cherry != nullptr;
+        for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops.p[k].cherry != nullptr;
     }
     return rc;
 }
@@ -1459,7 +1423,7 @@ extern "C" int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n) {
     const Plan &p = e->plan;
     const int nops = p.small_nops;   // (the plan's op count, small or not)
     int chunks = 0;
-    for (int k = 0; k < nops; k += e->h_ops[k].chunk_nops) chunks++;
+    for (int k = 0; k < nops; k += e->h_ops.p[k].chunk_nops) chunks++;
     out[0] = lds_budget(e); out[1] = p.lds_doubles; out[2] = p.state_slots; out[3] = p.nhold; out[4] = chunks;
     out[5] = (int64_t)p.stage_units.size();
     for (size_t s = 0; s < p.stage_units.size() && s < 8; s++) out[6 + s] = p.stage_units[s];

@@ -11,9 +11,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <time.h>
 #include <algorithm>
+#include <atomic>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include "../../include/iqhip.h"
@@ -188,11 +191,6 @@ struct __attribute__((aligned(16))) PairTile {
     int32_t out[16];
 };
 
-struct Slab {
-    double *plh = nullptr;
-    int16_t *sc = nullptr;
-};
-
 struct __attribute__((aligned(16))) TabJob {  // one K2 table to build: tab[c][state][pos(x)] for branch length len
     double len;
     double *tab;
@@ -298,18 +296,93 @@ __host__ __device__ inline void newton_update(NewtonState &s, double pdf, double
     if (fabs(s.dx) < s.xacc || s.j == s.max_steps) { s.result = s.rts_old; s.done = 1; return; }
 }
 
-// A device scratch buffer of an engine that grows on demand.  ensure(e, count): nothing while count <= cap; otherwise the
-// buffer is replaced as regrow (below) replaces one -- the engine's stream drains, the old contents are dropped, cap stays
-// 0 while an allocation has failed, and a planning-only engine gets a fake address.  The destructor frees the memory (never
-// a fake address): iqhip_destroy makes the device current and drains the stream before it deletes the engine.
+// The one place device and pinned-host memory is allocated and freed.  It keeps two process-wide byte counts, device memory
+// and pinned / host staging memory (iqhip_debug_memory), and can be told to fail the nth allocation from now without a HIP
+// call (iqhip_debug_fail_alloc).  MEM_HOST: plain zeroed host memory, the staging of a planning-only engine.
+enum MemKind : int { MEM_DEVICE = 0, MEM_PINNED, MEM_PINNED_MAPPED, MEM_HOST };
+inline std::atomic<int64_t> g_mem_bytes[2];   // live through mem_alloc: device, pinned / host staging
+inline std::atomic<int> g_fail_alloc_in{0};   // allocations until the one that fails (0: none)
+inline hipError_t mem_alloc(void **p, size_t bytes, MemKind kind) {
+    *p = nullptr;
+    if (g_fail_alloc_in.load() > 0 && g_fail_alloc_in.fetch_sub(1) == 1) return hipErrorOutOfMemory;
+    hipError_t s;
+    if (kind == MEM_DEVICE) s = hipMalloc(p, bytes);
+    else if (kind == MEM_HOST) s = (*p = calloc(1, bytes)) ? hipSuccess : hipErrorOutOfMemory;
+    else s = hipHostMalloc(p, bytes, kind == MEM_PINNED_MAPPED ? hipHostMallocMapped : hipHostMallocDefault);
+    if (s == hipSuccess) g_mem_bytes[kind != MEM_DEVICE] += (int64_t)bytes;
+    return s;
+}
+inline void mem_free(void *p, size_t bytes, MemKind kind) {
+    if (kind == MEM_DEVICE) hipFree(p);
+    else if (kind == MEM_HOST) free(p);
+    else hipHostFree(p);
+    g_mem_bytes[kind != MEM_DEVICE] -= (int64_t)bytes;
+}
+
+// What DevBuf and PinBuf share: the allocation and its release.  Movable, not copyable; frees itself.
 template <typename T>
-struct DevBuf {
+struct OwnedBuf {
     T *p = nullptr; size_t cap = 0;   // cap in elements
-    bool fake = false;                // p is a planning-only engine's fake address
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p && !fake) hipFree(p); }
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept { swap(o); }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept { swap(o); return *this; }
+    ~OwnedBuf() { reset(); }
+    void swap(OwnedBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(bytes, o.bytes); std::swap(kind, o.kind); }
+    void reset() {
+        if (bytes) mem_free(const_cast<std::remove_cv_t<T> *>(p), bytes, kind);
+        p = nullptr; cap = 0; bytes = 0;
+    }
+protected:
+    // a buffer of `count` elements in place of the old one, whose contents are dropped, once stream `s` has drained;
+    // cap == 0 while the allocation has failed
+    hipError_t replace(hipStream_t s, size_t count, MemKind k) {
+        if (k != MEM_HOST) {
+            const hipError_t rc = hipStreamSynchronize(s);
+            if (rc != hipSuccess) return rc;
+        }
+        reset();
+        void *q = nullptr;
+        const hipError_t rc = mem_alloc(&q, count * sizeof(T), k);
+        if (rc != hipSuccess) return rc;
+        p = static_cast<T *>(q); cap = count; bytes = count * sizeof(T); kind = k;
+        return hipSuccess;
+    }
+    size_t bytes = 0;   // what mem_alloc gave (0: nothing, or a planning-only engine's fake address)
+    MemKind kind = MEM_DEVICE;
+};
+
+// A device buffer that grows on demand.  ensure(e, count): nothing while count <= cap; otherwise the buffer is replaced --
+// the engine's stream drains, the old contents are dropped, cap stays 0 while an allocation has failed, and a planning-only
+// engine gets a fake address.  ensure(stream, count): the same for an owner that belongs to no engine.  The destructor frees
+// the memory (never a fake address): iqhip_destroy makes the device current and drains the stream before it deletes the engine.
+template <typename T>
+struct DevBuf : OwnedBuf<T> {
+    hipError_t ensure(hipStream_t s, size_t count) { return count <= this->cap ? hipSuccess : this->replace(s, count, MEM_DEVICE); }
     hipError_t ensure(iqhip_engine *e, size_t count);
+};
+// Its pinned-host counterpart; mapped: the memory is mapped into the device address space (the result vector the reduction
+// kernel writes, the sequence number the host polls).  A planning-only engine gets plain host memory and makes no HIP call.
+template <typename T>
+struct PinBuf : OwnedBuf<T> {
+    hipError_t ensure(hipStream_t s, size_t count, bool mapped = false) {
+        return count <= this->cap ? hipSuccess : this->replace(s, count, mapped ? MEM_PINNED_MAPPED : MEM_PINNED);
+    }
+    hipError_t ensure(iqhip_engine *e, size_t count, bool mapped = false);
+};
+// a device buffer with its pinned staging copy
+template <typename T>
+struct PairBuf {
+    DevBuf<T> d; PinBuf<T> h;
+    template <typename Where>   // an engine or a stream
+    hipError_t ensure(Where w, size_t count) {
+        const hipError_t rc = d.ensure(w, count);
+        return rc != hipSuccess ? rc : h.ensure(w, count);
+    }
+};
+
+struct Slab {
+    DevBuf<double> plh;
+    DevBuf<int16_t> sc;
 };
 
 }  // namespace iqhip
@@ -383,7 +456,7 @@ struct iqhip_engine {
     bool asc_active = false;
     double asc_nsites = 0.0;
     double pattern_lh_shift = 0.0;        // log(1 - prob_const) of the last lnL evaluation
-    const int16_t *theta_a_sc = nullptr;  // scale counters of the ends theta was built from
+    const int16_t *theta_a_sc = nullptr;  // scale counters of the ends theta was built from (they point into slabs)
     const int16_t *theta_b_sc = nullptr;
     iqhip_branch_end theta_end[2] = {{0, -1, 0}, {0, -1, 0}};   // ... and the ends as the caller named them (a leaf end first)
 
@@ -391,33 +464,31 @@ struct iqhip_engine {
     bool own_stream = false;
 
     // alignment side
-    uint8_t *d_states = nullptr;  // [ntaxa][nptn_pad]
-    double *d_freq = nullptr, *d_invar = nullptr;
-    // model side
+    iqhip::DevBuf<uint8_t> d_states;  // [ntaxa][nptn_pad]
+    iqhip::DevBuf<double> d_freq, d_invar;
+    // model side (these point into d_model)
     double *d_eval = nullptr, *d_evec = nullptr, *d_inv_evec = nullptr;
     double *d_rates = nullptr, *d_props = nullptr, *d_tip = nullptr;
     std::vector<double> h_eval, h_rates, h_props;
     std::vector<int> h_cls;      // category -> class of the last set_model call (all 0 for a plain model)
     // per-call buffers
-    iqhip::DevOp *d_ops = nullptr;
-    int ops_cap = 0;
+    iqhip::DevBuf<iqhip::DevOp> d_ops;   // (with its pinned staging copy h_ops: plan.hip ensure_plan_capacity)
     iqhip::DevBuf<double> d_slab;   // wave partials [nvals][nwaves]
-    unsigned int *d_fold_ticket = nullptr;  // folded reduction (FoldArgs): ticket + per-row flags, zero between launches
-    int *d_fold_flags = nullptr;
+    iqhip::DevBuf<unsigned int> d_fold_ticket;  // folded reduction (FoldArgs): ticket + per-row flags, zero between launches
+    iqhip::DevBuf<int> d_fold_flags;
     bool fold_reduce = false;               // IQHIP_FOLD=1: the last kernel of a submission sums the slab itself (measured
                                             // slower than the k_reduce launch on MI355X; off by default)
     // host polling of the result (IQHIP_POLL): k_reduce's last block stores a sequence number to mapped host memory
     bool poll_result = true, poll_pending = false;
     unsigned long long result_seq = 0;
-    volatile unsigned long long *h_done = nullptr;
-    unsigned long long *d_done = nullptr;
-    double *d_theta = nullptr, *d_pattern_lh = nullptr;
+    iqhip::PinBuf<volatile unsigned long long> h_done;   // (mapped)
+    unsigned long long *d_done = nullptr;       // the device address of h_done
+    iqhip::DevBuf<double> d_theta, d_pattern_lh;
     // K2 tables of the leaf children (matrix-core pipelined kernels, kernels_mfma.hip k_leaf_tables).  A table depends
     // on (model, pendant branch length) only, so slot t < ntaxa belongs to taxon t and is rebuilt only when that
     // length or the model changed; a second length of one taxon inside one submission (batched NNI candidates)
     // takes an overflow slot >= ntaxa.
-    double *d_leaf_tab = nullptr;
-    size_t leaf_tab_slots = 0;            // capacity in tables
+    iqhip::DevBuf<double> d_leaf_tab;     // whole tables of leaf_table_doubles(e) each
     std::vector<double> tab_len;          // per slot: branch length the table was built for (NaN: none)
     uint64_t model_version = 1, tab_model_version = 0;
     // cherry tables (20 states x 4 categories, DevOp::cherry): slot = pair of taxa; `pair` is a small engine of our own on
@@ -431,8 +502,7 @@ struct iqhip_engine {
     bool cherry_on = true;                 // IQHIP_CHERRY_TABLES=0 switches the tables off
     iqhip_engine *pair = nullptr;
     int cherry_s2 = 0, cherry_npairs = 0;  // STATE_UNKNOWN + 1; its square padded to whole 64-pattern groups
-    double *d_cherry_tab = nullptr;
-    size_t cherry_cap = 0;                 // slots allocated
+    iqhip::DevBuf<double> d_cherry_tab;    // whole slots of cherry_npairs * block doubles each
     std::unordered_map<uint64_t, int> cherry_slot_of;   // (taxon_l << 32 | taxon_r) -> slot
     std::vector<CherrySlot> cherry_slots;
     uint64_t cherry_stamp = 0;
@@ -465,12 +535,12 @@ struct iqhip_engine {
     iqhip::DevBuf<double> d_model;   // the block all model arrays above point into (set_model_common)
     bool mfma_pipelined_ok = false;  // (n, ncat) has a pipelined instantiation (used when nclass == 1)
     // UFBoot / RELL (kernels_rell.hip): scaled per-pattern lnL and the bootstrap sample matrix
-    double *d_ptn_scaled = nullptr;
-    float *d_boot = nullptr;  // [nboot][nptn_pad], zero padded
+    iqhip::DevBuf<double> d_ptn_scaled;
+    iqhip::DevBuf<float> d_boot;  // [nboot][nptn_pad], zero padded
     int nboot = 0;
     // branch tests (SH-aLRT / local bootstrap, ptnlh.hip): the store of per-pattern log-likelihood rows [ptnlh_rows][nptn_pad]
     // and the scratch of iqhip_branch_tests / iqhip_ptnlh_rell (row lists, K-split partial products, combined sums, results)
-    double *d_ptnlh = nullptr;
+    iqhip::DevBuf<double> d_ptnlh;
     int ptnlh_rows = 0;
     struct {
         iqhip::DevBuf<int32_t> rows;    // [distinct rows] ++ [3 * nbranch indices into them]
@@ -481,7 +551,7 @@ struct iqhip_engine {
     // tree topology tests (kernels_topo.hip): int64 inclusive prefix sums of ptn_freq for iqhip_gen_boot_samples (built when
     // first needed, dropped by iqhip_set_ptn_freq) and the scratch of iqhip_ptnlh_diff_variance / iqhip_tree_tests /
     // iqhip_multiscale_bp
-    int64_t *d_freq_prefix = nullptr;
+    iqhip::DevBuf<int64_t> d_freq_prefix;
     bool freq_prefix_valid = false;
     int64_t freq_nsite = 0;
     struct {
@@ -574,21 +644,21 @@ struct iqhip_engine {
     // pinned staging, one buffer per direction and kind so that none is rewritten while a copy of it may be in flight: the
     // levelled ops of an update (rewritten only after a synchronise), the branch ends and the results of a scores call
     // (every scores call ends with a synchronise)
-    int32_t *h_pars_ops = nullptr, *h_pars_ends = nullptr, *h_pars_out = nullptr;
-    size_t h_pars_ops_cap = 0, h_pars_ends_cap = 0, h_pars_out_cap = 0;
+    iqhip::PinBuf<int32_t> h_pars_ops, h_pars_ends, h_pars_out;
     double pars_ms[2] = {0.0, 0.0};     // iqhip_debug_pars_timing: update, scan (while timing is enabled)
     int64_t pars_counts[4] = {0, 0, 0, 0};   // launches of the updates and of the scans, ops updated, branches scanned
     double pars_spr_ms = 0.0;           // iqhip_debug_pars_spr_timing: the SPR scan launches (while timing is enabled) ...
     int64_t pars_spr_counts[2] = {0, 0};   // ... their number and the steps scored
     iqhip::DevBuf<int32_t> d_batch_rows;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
+    // the result vector the kernels write: d_result_own is the device address of h_result, d_result that or d_result_dev
     double *d_result_own = nullptr, *d_result = nullptr;
-    double *d_newton_partials = nullptr;   // [2][num_cus][2]
-    unsigned int *d_newton_barrier = nullptr;  // [2], used alternately by consecutive k_newton launches
+    iqhip::DevBuf<double> d_newton_partials;   // [2][num_cus][2]
+    iqhip::DevBuf<unsigned int> d_newton_barrier;  // [2], used alternately by consecutive k_newton launches
     unsigned int newton_launches = 0;
     // k_newton's exchange of the workgroup partial sums without an arrival counter: every (evaluation, workgroup) has a
     // slot of its own, {df, ddf}, that holds a sentinel until its owner posts; readers spin on the slots themselves.
     // Two buffers alternate between launches; a launch resets the other buffer's slots of its workgroups.
-    double *d_newton_posts = nullptr;      // [2][kNewtonPostEpochs][num_cus][2]
+    iqhip::DevBuf<double> d_newton_posts;  // [2][kNewtonPostEpochs][num_cus][2]
     unsigned int newton_post_launches = 0;
     bool newton_posts = true;              // IQHIP_NEWTON_POSTS=0: the arrival-counter barrier of round 1
     // the same for k_newton_batch: [2 launch parities][cap / 2]; a launch lays its slots out as
@@ -605,8 +675,9 @@ struct iqhip_engine {
     unsigned int batch_launches = 0;
     iqhip::DevBuf<double> d_sweep_len;   // iqhip_optimize_sweep: the accepted length of every step, read by later steps' node updates
     // ... persistent form (4 states): descriptors of all steps (pinned staging + device copy) and the exchange slots
-    char *h_sweep_desc = nullptr, *d_sweep_desc = nullptr;
-    size_t sweep_desc_cap = 0;
+    iqhip::PinBuf<char> h_sweep_desc;
+    iqhip::DevBuf<char> d_sweep_desc;
+    iqhip::DevBuf<unsigned long long> d_sweep_prof;   // IQHIP_DEBUG_SWEEP: k_sweep4's cycle counters (kernels_sweep.hip)
     iqhip::DevBuf<double> d_sweep_posts;
     int num_cus = 256;
     int result_cap = 0;
@@ -615,8 +686,9 @@ struct iqhip_engine {
     // stream) before it is read back.  RCCL is loaded lazily (dlopen) the first time a communicator is made.
     void *comm = nullptr;            // ncclComm_t
     int comm_nranks = 1, comm_rank = 0;
-    double *d_result_dev = nullptr;  // device-memory result vector of a comm engine (the default one is mapped host memory)
-    iqhip::NewtonState *d_nstate = nullptr, *h_nstate = nullptr;  // Newton state machine: device copy / pinned host copy
+    iqhip::DevBuf<double> d_result_dev;  // device-memory result vector of a comm engine (the default one is mapped host memory)
+    iqhip::DevBuf<iqhip::NewtonState> d_nstate;   // Newton state machine: device copy ...
+    iqhip::PinBuf<iqhip::NewtonState> h_nstate;   // ... / pinned host copy
     iqhip::DevBuf<iqhip::NewtonState> d_bstates;                  // batched chain: one state machine per task
     iqhip::DevBuf<const int16_t *> d_bsc;                         // ... and (+ASC) the scale counters of its two branch ends
     // ---- single-process sharding (sharded.hip): this object owns no device memory, it fronts `shards`
@@ -625,11 +697,11 @@ struct iqhip_engine {
     std::vector<int64_t> shard_first;
     int reduce_mode = 0;             // IQHIP_REDUCE_RCCL / IQHIP_REDUCE_HOST
     // pinned host staging
-    iqhip::DevOp *h_ops = nullptr;
-    double *h_result = nullptr;
+    iqhip::PinBuf<iqhip::DevOp> h_ops;   // (plain host memory on a planning-only engine)
+    iqhip::PinBuf<double> h_result;      // (mapped)
     iqhip::PlanCache plan_cache;
-    char *h_plan_arena = nullptr;     // pinned slices for the plan uploads of a per-step sweep (plan.hip upload_plan)
-    size_t plan_arena_cap = 0, plan_arena_used = 0;
+    iqhip::PinBuf<char> h_plan_arena;     // pinned slices for the plan uploads of a per-step sweep (plan.hip upload_plan)
+    size_t plan_arena_used = 0;
     bool plan_arena_on = false;
     uint64_t keymap_version = 1;      // bumped whenever a key is created, released or moved
     hipEvent_t staging_free = nullptr;
@@ -805,8 +877,6 @@ inline int fail(int code, const std::string &msg) { return set_error(code, msg);
             return iqhip::set_error(IQHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s));        \
     } while (0)
 
-template <typename T>
-hipError_t dmalloc(T **p, size_t count) { return hipMalloc((void **)p, count * sizeof(T)); }
 // planning-only engines: a distinct, 256-byte aligned address range that is never dereferenced
 template <typename T>
 T *fake_alloc(iqhip_engine *e, size_t count) {
@@ -814,29 +884,32 @@ T *fake_alloc(iqhip_engine *e, size_t count) {
     e->fake_next += (count * sizeof(T) + 255) / 256 * 256 + 256;
     return reinterpret_cast<T *>(a);
 }
-// Replaces a device buffer by one of `count` elements once the engine's stream has drained (the contents are dropped);
-// *cap = new_cap when that succeeded, 0 while it has not.  A planning-only engine gets a fake address.  Called directly only
-// where the capacity field means something other than the allocation's element count; everything else is a DevBuf.
-template <typename T, typename C>
-hipError_t regrow(iqhip_engine *e, T **buf, C *cap, size_t new_cap, size_t count) {
-    if (e->planner) {
-        *buf = fake_alloc<T>(e, count);
-    } else {
-        hipError_t s = hipStreamSynchronize(e->stream);
-        if (s != hipSuccess) return s;
-        if (*buf) hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        if ((s = dmalloc(buf, count)) != hipSuccess) return s;
+template <typename T>
+hipError_t DevBuf<T>::ensure(iqhip_engine *e, size_t count) {
+    if (!e->planner) return ensure(e->stream, count);
+    if (count > this->cap) {
+        this->p = fake_alloc<T>(e, count);
+        this->cap = count;
     }
-    *cap = (C)new_cap;
     return hipSuccess;
 }
 template <typename T>
-hipError_t DevBuf<T>::ensure(iqhip_engine *e, size_t count) {
-    if (count <= cap) return hipSuccess;
-    fake = e->planner;
-    return regrow(e, &p, &cap, count, count);
+hipError_t PinBuf<T>::ensure(iqhip_engine *e, size_t count, bool mapped) {
+    if (!e->planner) return ensure(e->stream, count, mapped);
+    return count <= this->cap ? hipSuccess : this->replace(nullptr, count, MEM_HOST);
+}
+// Raises Kernel's dynamic-LDS ceiling to `bytes` on e->device the first time that kernel is launched on that device.  The
+// attribute belongs to the device a launch goes to, so there is one flag per (kernel instantiation, device), not one per
+// process: every launch after the first costs one branch.  A failure is returned and tried again at the next launch.
+constexpr unsigned kLdsCeilingDevices = 64;   // (a device beyond them is opted in at every launch)
+template <auto Kernel>
+hipError_t raise_lds_ceiling(const iqhip_engine *e, int bytes) {
+    static std::atomic<bool> raised[kLdsCeilingDevices];
+    const unsigned dev = (unsigned)e->device;
+    if (dev < kLdsCeilingDevices && raised[dev].load(std::memory_order_relaxed)) return hipSuccess;
+    const hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (s == hipSuccess && dev < kLdsCeilingDevices) raised[dev].store(true, std::memory_order_relaxed);
+    return s;
 }
 // HIP events around the phases of one feature call; nothing at all while e->timing is off.  mark() records the next
 // boundary on e->stream: a round of nphases phases is nphases + 1 marks, a call may record any number of rounds (one per

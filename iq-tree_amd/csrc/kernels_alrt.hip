@@ -195,14 +195,12 @@ static hipError_t launch_product_mt(iqhip_engine *e, const int32_t *d_rows, int 
     const int per = (total_steps + ksplit - 1) / ksplit;
     const int grid = (ksplit + 7) / 8 * 8 * nsb;
     const size_t lds = sizeof(double) * MT * 16 * kAlrtLStride + sizeof(float) * kAlrtNS * kAlrtWStride;
-    // more than 64 KB of dynamic LDS (13 row tiles: 64.25 KB) needs the opt-in on the device the launch goes to; it is a
-    // host-side table entry, so it is set before every such launch rather than remembered per process
+    // more than 64 KB of dynamic LDS (13 row tiles: 64.25 KB) needs the opt-in on the device the launch goes to
     if (lds > 64 * 1024) {
-        const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(k_alrt_product<MT>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t a = raise_lds_ceiling<&k_alrt_product<MT>>(e, (int)lds);
         if (a != hipSuccess) return a;
     }
-    hipLaunchKernelGGL(k_alrt_product<MT>, dim3((unsigned)grid), dim3(256), lds, e->stream, e->d_ptnlh, d_rows, M, e->d_boot, S,
+    hipLaunchKernelGGL(k_alrt_product<MT>, dim3((unsigned)grid), dim3(256), lds, e->stream, e->d_ptnlh.p, d_rows, M, e->d_boot.p, S,
                        e->nptn_pad, nsb, ksplit, per, part);
     return hipGetLastError();
 }

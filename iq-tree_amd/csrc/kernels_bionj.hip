@@ -214,22 +214,6 @@ __global__ void k_bj_finish(const double *__restrict__ D, int n, const int32_t *
     last_len[2] = 0.5 * (d(l2, l1) + d(l2, l0) - d(l1, l0));
 }
 
-namespace {
-// the device memory of one call, freed on every way out
-struct BjBuffers {
-    std::vector<void *> ptrs;
-    ~BjBuffers() {
-        for (void *p : ptrs) hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T **p, size_t count) {
-        const hipError_t s = dmalloc(p, count ? count : 1);
-        if (s == hipSuccess) ptrs.push_back(*p);
-        return s;
-    }
-};
-}  // namespace
-
 }  // namespace iqhip
 
 using namespace iqhip;
@@ -250,20 +234,24 @@ extern "C" int iqhip_bionj(iqhip_engine *e, int n, const double *dist, const dou
                     if (i != j && !std::isfinite(m[i * n + j]))
                         return fail(IQHIP_ERR_INVALID, "iqhip_bionj: a distance or variance is not finite");
     HIPCHK(use_device(e));
-    BjBuffers buf;
-    double *d_T = nullptr, *d_D = nullptr, *d_V = nullptr, *d_S = nullptr, *d_rowmin = nullptr, *d_last_len = nullptr;
-    int32_t *d_act[2] = {nullptr, nullptr}, *d_last = nullptr;
-    BjPick *d_pick = nullptr;
-    iqhip_bionj_step *d_steps = nullptr;
+    // the device memory of one call, freed on every way out
+    DevBuf<double> b_T, b_D, b_V, b_S, b_rowmin, b_last_len;
+    DevBuf<int32_t> b_act[2], b_last;
+    DevBuf<BjPick> b_pick;
+    DevBuf<iqhip_bionj_step> b_steps;
     const int nsteps = n - 3;
-    if (buf.get(&d_T, nn) != hipSuccess || buf.get(&d_D, nn) != hipSuccess || buf.get(&d_V, nn) != hipSuccess ||
-        buf.get(&d_S, (size_t)n) != hipSuccess || buf.get(&d_rowmin, (size_t)n) != hipSuccess ||
-        buf.get(&d_act[0], (size_t)n) != hipSuccess || buf.get(&d_act[1], (size_t)n) != hipSuccess ||
-        buf.get(&d_pick, 1) != hipSuccess || buf.get(&d_steps, (size_t)nsteps) != hipSuccess ||
-        buf.get(&d_last, 3) != hipSuccess || buf.get(&d_last_len, 3) != hipSuccess) {
+    if (b_T.ensure(e, nn) != hipSuccess || b_D.ensure(e, nn) != hipSuccess || b_V.ensure(e, nn) != hipSuccess ||
+        b_S.ensure(e, (size_t)n) != hipSuccess || b_rowmin.ensure(e, (size_t)n) != hipSuccess ||
+        b_act[0].ensure(e, (size_t)n) != hipSuccess || b_act[1].ensure(e, (size_t)n) != hipSuccess ||
+        b_pick.ensure(e, 1) != hipSuccess || b_steps.ensure(e, (size_t)std::max(nsteps, 1)) != hipSuccess ||
+        b_last.ensure(e, 3) != hipSuccess || b_last_len.ensure(e, 3) != hipSuccess) {
         (void)hipGetLastError();
         return fail(IQHIP_ERR_NOMEM, "iqhip_bionj: out of device memory (three n x n matrices of doubles)");
     }
+    double *d_T = b_T.p, *d_D = b_D.p, *d_V = b_V.p, *d_S = b_S.p, *d_rowmin = b_rowmin.p, *d_last_len = b_last_len.p;
+    int32_t *d_act[2] = {b_act[0].p, b_act[1].p}, *d_last = b_last.p;
+    BjPick *d_pick = b_pick.p;
+    iqhip_bionj_step *d_steps = b_steps.p;
     PhaseTimer timer(e, 1);
     hipStream_t st = e->stream;
     const unsigned nn_blocks = (unsigned)((nn + kBjThreads - 1) / kBjThreads);

@@ -112,8 +112,8 @@ hipError_t launch_class_lnl(iqhip_engine *e, const int16_t *sc_a, const int16_t 
     const int M = e->nclass;
     const int64_t rows = class_lnl_part_rows(e);
     const size_t lds = sizeof(double) * ((size_t)max_comp * e->n + 8);
-    hipLaunchKernelGGL(k_class_lnl, dim3((unsigned)rows, (unsigned)M), dim3(256), lds, e->stream, e->d_theta, e->d_evalc,
-                       e->d_rates, e->d_props, d_cls_list, d_cw, e->d_freq, e->d_invar, d_class_invar, sc_a, sc_b, len, e->n,
+    hipLaunchKernelGGL(k_class_lnl, dim3((unsigned)rows, (unsigned)M), dim3(256), lds, e->stream, e->d_theta.p, e->d_evalc,
+                       e->d_rates, e->d_props, d_cls_list, d_cw, e->d_freq.p, e->d_invar.p, d_class_invar, sc_a, sc_b, len, e->n,
                        e->ncat, M, e->tile, e->nptn, e->nptn_pad, part);
     hipLaunchKernelGGL(k_class_fold, dim3((unsigned)(2 * M)), dim3(256), 0, e->stream, part, rows, 2 * M, out);
     return hipGetLastError();

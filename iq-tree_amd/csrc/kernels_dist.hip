@@ -224,23 +224,18 @@ __global__ __launch_bounds__(64) void k_pair_solve(const PairSolveArgs A) {
 hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts) {
     if (ntiles < 1) return hipSuccess;
     if (e->n == 4) {
-        hipLaunchKernelGGL(k_pair_counts4, dim3((unsigned)ntiles), dim3(256), 0, e->stream, d_tiles, e->d_states, e->nptn_pad,
-                           e->nptn, e->d_freq, d_counts);
+        hipLaunchKernelGGL(k_pair_counts4, dim3((unsigned)ntiles), dim3(256), 0, e->stream, d_tiles, e->d_states.p, e->nptn_pad,
+                           e->nptn, e->d_freq.p, d_counts);
     } else if (e->n == 20) {
         constexpr size_t lds = sizeof(double) * 4 * 4 * 400;
-        hipLaunchKernelGGL((k_pair_counts_lds<20, 2, 4>), dim3((unsigned)ntiles), dim3(256), lds, e->stream, d_tiles, e->d_states,
-                           e->nptn_pad, e->nptn, e->d_freq, d_counts);
+        hipLaunchKernelGGL((k_pair_counts_lds<20, 2, 4>), dim3((unsigned)ntiles), dim3(256), lds, e->stream, d_tiles, e->d_states.p,
+                           e->nptn_pad, e->nptn, e->d_freq.p, d_counts);
     } else if (e->n == 64) {
         constexpr size_t lds = sizeof(double) * 2 * 4096;
-        static bool attr_set = false;
-        if (!attr_set) {
-            const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_counts_lds<64, 1, 2>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (a != hipSuccess) return a;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((k_pair_counts_lds<64, 1, 2>), dim3((unsigned)ntiles), dim3(128), lds, e->stream, d_tiles, e->d_states,
-                           e->nptn_pad, e->nptn, e->d_freq, d_counts);
+        const hipError_t a = raise_lds_ceiling<&k_pair_counts_lds<64, 1, 2>>(e, (int)lds);
+        if (a != hipSuccess) return a;
+        hipLaunchKernelGGL((k_pair_counts_lds<64, 1, 2>), dim3((unsigned)ntiles), dim3(128), lds, e->stream, d_tiles, e->d_states.p,
+                           e->nptn_pad, e->nptn, e->d_freq.p, d_counts);
     } else
         return hipErrorInvalidValue;
     return hipGetLastError();

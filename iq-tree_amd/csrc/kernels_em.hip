@@ -169,8 +169,8 @@ hipError_t launch_em_posteriors(iqhip_engine *e, double len, double *W, double *
     const int64_t P = e->nptn_pad;   // a multiple of the tile size; the last workgroup may hang over it
     const unsigned nblocks = (unsigned)((P + 255) / 256);
     const size_t lds = sizeof(double) * ((size_t)e->block + 4 * (size_t)e->ncat);
-    hipLaunchKernelGGL(k_em_posteriors, dim3(nblocks), dim3(256), lds, e->stream, e->d_theta, e->d_evalc, e->d_rates, e->d_props,
-                       e->d_freq, len, e->n, e->ncat, e->tile, e->nptn, P, W, ptn_rate, ptn_cat, part);
+    hipLaunchKernelGGL(k_em_posteriors, dim3(nblocks), dim3(256), lds, e->stream, e->d_theta.p, e->d_evalc, e->d_rates, e->d_props,
+                       e->d_freq.p, len, e->n, e->ncat, e->tile, e->nptn, P, W, ptn_rate, ptn_cat, part);
     hipLaunchKernelGGL(k_em_fold, dim3((unsigned)e->ncat), dim3(256), 0, e->stream, part, (int64_t)nblocks, e->ncat, out);
     return hipGetLastError();
 }
@@ -181,7 +181,7 @@ hipError_t launch_em_objective(iqhip_engine *e, const int16_t *sc_a, const int16
     const int64_t P = e->nptn_pad;
     const unsigned nblocks = (unsigned)((P + 255) / 256);
     const size_t lds = sizeof(double) * ((size_t)e->block + 8 * (size_t)e->ncat);
-    hipLaunchKernelGGL(k_em_objective, dim3(nblocks), dim3(256), lds, e->stream, e->d_theta, e->d_evalc, e->d_rates, e->d_props,
+    hipLaunchKernelGGL(k_em_objective, dim3(nblocks), dim3(256), lds, e->stream, e->d_theta.p, e->d_evalc, e->d_rates, e->d_props,
                        W, sc_a, sc_b, len, e->n, e->ncat, e->tile, e->nptn, P, part);
     hipLaunchKernelGGL(k_em_fold, dim3((unsigned)(2 * e->ncat)), dim3(256), 0, e->stream, part, (int64_t)nblocks, 2 * e->ncat, out);
     return hipGetLastError();

@@ -1407,14 +1407,10 @@ __global__ __launch_bounds__(256, 2) void k_traverse_mfma_top64(const TravMArgs 
     else trav_rows64_body<256, TAB>(R, (int)blockIdx.x - nfull, (int64_t)nfull * 4);
 }
 
-// One launch of the kernel the chooser picked: its dynamic-LDS ceiling is raised the first time it is used
+// One launch of the kernel the chooser picked: its dynamic-LDS ceiling is raised the first time it is used on the engine's device
 template <auto Kernel, int MaxLdsBytes = kTravMaxLdsBytes, typename... Args>
 static hipError_t launch_trav(iqhip_engine *e, const TravLaunch &L, const Args &...args) {
-    static bool attr_set = false;   // (per instantiation, i.e. per kernel)
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MaxLdsBytes);
-        attr_set = true;
-    }
+    (void)raise_lds_ceiling<Kernel>(e, MaxLdsBytes);
     (void)hipGetLastError();
     hipLaunchKernelGGL(Kernel, dim3((unsigned)L.grid), dim3(kTravWg), L.lds_bytes, e->stream, args...);
     return hipGetLastError();
@@ -1503,13 +1499,13 @@ static hipError_t launch_traverse_mfma_impl(iqhip_engine *e, const int *seg_tabl
 hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs, int nwaves, bool top_stage) {
 #endif
     TravMArgs A;
-    A.ops = e->d_ops;
+    A.ops = e->d_ops.p;
     A.evec = e->d_evec;
     A.inv_evec = e->d_inv_evec;
     A.aimg = e->d_aimg;
     A.tip = e->d_tip;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
     A.eval = e->d_eval;
     A.rates = e->d_rates;
     A.evalc = e->d_evalc;
@@ -1525,7 +1521,7 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
     A.nwaves = nwaves;
     A.ncat = e->ncat;
     A.state_unknown = e->state_unknown;
-    A.fold_flags = e->d_fold_flags;
+    A.fold_flags = e->d_fold_flags.p;
     A.hold_off = -1;
     A.small_plan = 0;
     A.small_segs[0] = A.small_segs[1] = 0;
@@ -1539,7 +1535,7 @@ hipError_t launch_traverse_mfma(iqhip_engine *e, const int *seg_table, int nsegs
         // implies a kernel that reads it there, kernel_takes_small_plan)
         A.small_plan = 1;
         A.small_segs[1] = e->plan.small_nops;
-        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
+        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops.p[q];
     }
     TravMArgs F = A;
     if (L.nfull > 0) {
@@ -1713,8 +1709,8 @@ hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, do
     if (bc) fold_rows = -1;
     A.fold.slab = e->d_slab.p;
     A.fold.result = e->d_result;
-    A.fold.ticket = e->d_fold_ticket;
-    A.fold.flags = e->d_fold_flags;
+    A.fold.ticket = e->d_fold_ticket.p;
+    A.fold.flags = e->d_fold_flags.p;
     A.fold.nwaves = nwaves;
     A.fold.nrows_scale = fold_rows > 0 ? fold_rows : 0;
     A.fold.root_rows = 2;
@@ -1726,10 +1722,10 @@ hipError_t launch_stream_mfma(iqhip_engine *e, int mode, const DevBranch *br, do
     A.eval = e->d_evalc;
     A.rates = e->d_rates;
     A.props = e->d_props;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
-    A.theta = bc ? const_cast<double *>(bc->theta) : (theta_out ? theta_out : e->d_theta);
-    A.pattern_lh = bc ? nullptr : e->d_pattern_lh;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
+    A.theta = bc ? const_cast<double *>(bc->theta) : (theta_out ? theta_out : e->d_theta.p);
+    A.pattern_lh = bc ? nullptr : e->d_pattern_lh.p;
     A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;

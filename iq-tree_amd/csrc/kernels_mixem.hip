@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void k_mix_posteriors(const double *__restrict
 hipError_t launch_mix_class_lh(iqhip_engine *e, double len, const int32_t *d_cls_list, double *Lc) {
     const int64_t P = e->nptn_pad;
     hipLaunchKernelGGL(k_mix_class_lh, dim3((unsigned)((P + 255) / 256), (unsigned)e->nclass), dim3(256), sizeof(double) * e->block, e->stream,
-                       e->d_theta, e->d_evalc, e->d_rates, e->d_props, d_cls_list, len, e->n, e->ncat, e->nclass, e->tile,
+                       e->d_theta.p, e->d_evalc, e->d_rates, e->d_props, d_cls_list, len, e->n, e->ncat, e->nclass, e->tile,
                        e->nptn, P, Lc);
     return hipGetLastError();
 }
@@ -213,10 +213,10 @@ hipError_t launch_mixem_step(iqhip_engine *e, const double *Lc, double *state, i
     const int64_t rows = mixem_part_rows(e);
     const size_t lds = sizeof(double) * 5 * (size_t)M;
     if (M <= kMixEmRegClasses)
-        hipLaunchKernelGGL(k_mixem_step<true>, dim3((unsigned)rows), dim3(256), lds, e->stream, Lc, e->d_freq, e->d_invar, state, M,
+        hipLaunchKernelGGL(k_mixem_step<true>, dim3((unsigned)rows), dim3(256), lds, e->stream, Lc, e->d_freq.p, e->d_invar.p, state, M,
                            e->nptn, e->nptn_pad, part);
     else
-        hipLaunchKernelGGL(k_mixem_step<false>, dim3((unsigned)rows), dim3(256), lds, e->stream, Lc, e->d_freq, e->d_invar, state, M,
+        hipLaunchKernelGGL(k_mixem_step<false>, dim3((unsigned)rows), dim3(256), lds, e->stream, Lc, e->d_freq.p, e->d_invar.p, state, M,
                            e->nptn, e->nptn_pad, part);
     hipLaunchKernelGGL(k_mixem_update, dim3(1), dim3(kMixEmUpdateThreads), sizeof(double) * (size_t)(kMixEmUpdateThreads / M) * M, e->stream, part, rows, M, max_steps, state);
     return hipGetLastError();

@@ -935,8 +935,8 @@ hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks,
     A.eval = e->d_evalc;
     A.rates = e->d_rates;
     A.props = e->d_props;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
     A.partials = nullptr;
     A.barrier = nullptr;
     A.barrier_next = nullptr;
@@ -1039,7 +1039,7 @@ hipError_t launch_newton_state_update_batch(iqhip_engine *e, NewtonState *states
 }
 
 hipError_t launch_newton_state_init(iqhip_engine *e, double xguess, double x1, double x2, double xacc, int max_steps) {
-    hipLaunchKernelGGL(k_newton_state_init, dim3(1), dim3(64), 0, e->stream, e->d_nstate, xguess, x1, x2, xacc, max_steps);
+    hipLaunchKernelGGL(k_newton_state_init, dim3(1), dim3(64), 0, e->stream, e->d_nstate.p, xguess, x1, x2, xacc, max_steps);
     return hipGetLastError();
 }
 
@@ -1050,12 +1050,12 @@ hipError_t launch_newton_state_init_on(hipStream_t s, NewtonState *st, double xg
 }
 
 hipError_t launch_derv_at_state(iqhip_engine *e, int nwaves) {
-    if (e->mfma) return launch_stream_mfma(e, 2, nullptr, 0.0, nwaves, e->d_nstate);
-    return launch_derv4(e, 0.0, nwaves, e->d_nstate);
+    if (e->mfma) return launch_stream_mfma(e, 2, nullptr, 0.0, nwaves, e->d_nstate.p);
+    return launch_derv4(e, 0.0, nwaves, e->d_nstate.p);
 }
 
 hipError_t launch_newton_state_update(iqhip_engine *e) {
-    hipLaunchKernelGGL(k_newton_state_update, dim3(1), dim3(64), 0, e->stream, e->d_nstate, e->d_result, e->asc_active ? e->asc_nsites : 0.0);
+    hipLaunchKernelGGL(k_newton_state_update, dim3(1), dim3(64), 0, e->stream, e->d_nstate.p, e->d_result, e->asc_active ? e->asc_nsites : 0.0);
     return hipGetLastError();
 }
 
@@ -1074,13 +1074,13 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
     A.result = sweep ? sweep->rows_base - 2 : e->d_result;   // (row r of the node updates goes to result[2 + r])
     A.nrows = reduce_rows;
     A.nwaves = reduce_nwaves;
-    A.theta = e->d_theta;
+    A.theta = e->d_theta.p;
     A.eval = e->d_evalc;
     A.rates = e->d_rates;
     A.props = e->d_props;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
-    A.partials = e->d_newton_partials;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
+    A.partials = e->d_newton_partials.p;
     A.out = out;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
@@ -1099,8 +1099,8 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
     const int64_t wgs = (e->ntiles + 3) / 4;
     const int64_t max_grid = posts ? 2 * (int64_t)e->num_cus : e->num_cus;
     int grid = (int)(wgs < 1 ? 1 : (wgs > max_grid ? max_grid : wgs));
-    A.barrier = e->d_newton_barrier + (e->newton_launches & 1);
-    A.barrier_next = e->d_newton_barrier + ((e->newton_launches + 1) & 1);
+    A.barrier = e->d_newton_barrier.p + (e->newton_launches & 1);
+    A.barrier_next = e->d_newton_barrier.p + ((e->newton_launches + 1) & 1);
     e->newton_launches++;
     A.done = nullptr;
     A.seq = 0;
@@ -1115,8 +1115,8 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
     A.posts = A.posts_other = nullptr;
     if (grid > 1 && posts) {
         const size_t per = (size_t)kNewtonPostEpochs * (2 * e->num_cus) * 2;   // (slots are indexed with the launch's grid <= 2 num_cus)
-        A.posts = e->d_newton_posts + (e->newton_post_launches & 1) * per;
-        A.posts_other = e->d_newton_posts + ((e->newton_post_launches + 1) & 1) * per;
+        A.posts = e->d_newton_posts.p + (e->newton_post_launches & 1) * per;
+        A.posts_other = e->d_newton_posts.p + ((e->newton_post_launches + 1) & 1) * per;
         e->newton_post_launches++;
     }
     const size_t lds = (size_t)(3 * e->block + 8) * sizeof(double);

@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void k_pars_argmin(int32_t *out, int nbranch) 
 // ---- launches -----------------------------------------------------------------------------------------------------------
 hipError_t launch_pars_tips(iqhip_engine *e, const int32_t *d_site_ptn) {
     const int64_t total = (int64_t)e->ntaxa * e->pars_nwords * e->n;
-    hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_states, e->nptn_pad,
+    hipLaunchKernelGGL(k_pars_tips, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, e->d_states.p, e->nptn_pad,
                        d_site_ptn, e->pars_nsites, e->pars_nwords, e->pars.masks.p, e->n, e->ntaxa, e->pars.vec.p,
                        e->pars.score.p);
     return hipGetLastError();

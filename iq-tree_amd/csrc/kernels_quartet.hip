@@ -432,7 +432,7 @@ hipError_t launch_quartet_cells(iqhip_engine *e, const int32_t *d_quartets, int 
                                 int32_t *d_other) {
     if (m < 1) return hipSuccess;
     hipLaunchKernelGGL(k_quartet_cells4, dim3((unsigned)((m + kQuartetWaves - 1) / kQuartetWaves)), dim3(64 * kQuartetWaves), 0,
-                       e->stream, d_quartets, m, e->d_states, e->nptn_pad, e->nptn, e->d_freq, d_cells, d_nother, d_other);
+                       e->stream, d_quartets, m, e->d_states.p, e->nptn_pad, e->nptn, e->d_freq.p, d_cells, d_nother, d_other);
     return hipGetLastError();
 }
 

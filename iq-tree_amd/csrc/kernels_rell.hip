@@ -176,27 +176,27 @@ hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const 
     const int64_t P = e->nptn_pad;
     hipLaunchKernelGGL(k_ptnlh_rows, dim3((unsigned)((P + 255) / 256), (unsigned)m), dim3(256), sizeof(double) * e->block,
                        e->stream, static_cast<const char *>(d_tasks), newton_task_bytes(), newton_task_branch_offset(),
-                       batch_out, theta_base, theta_stride, e->d_evalc, e->d_rates, e->d_props, e->d_invar, e->n, e->ncat,
-                       e->tile, e->nptn - e->n_unobs, e->nptn, P, d_rows, e->d_ptnlh);
+                       batch_out, theta_base, theta_stride, e->d_evalc, e->d_rates, e->d_props, e->d_invar.p, e->n, e->ncat,
+                       e->tile, e->nptn - e->n_unobs, e->nptn, P, d_rows, e->d_ptnlh.p);
     return hipGetLastError();
 }
 
 hipError_t launch_pattern_lh_cat(iqhip_engine *e, double len, double *out) {
     const int64_t total = e->nptn * e->ncat;
     hipLaunchKernelGGL(k_pattern_lh_cat, dim3((unsigned)((total + 255) / 256)), dim3(256), sizeof(double) * e->block, e->stream,
-                       e->d_theta, e->d_evalc, e->d_rates, e->d_props, len, e->n, e->ncat, e->tile, e->nptn, out);
+                       e->d_theta.p, e->d_evalc, e->d_rates, e->d_props, len, e->n, e->ncat, e->tile, e->nptn, out);
     return hipGetLastError();
 }
 
 hipError_t launch_pattern_lh_scaled(iqhip_engine *e, const int16_t *sc_a, const int16_t *sc_b, double *out) {
     const int64_t P = e->nptn_pad;
-    hipLaunchKernelGGL(k_pattern_lh_scaled, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, e->stream, e->d_pattern_lh,
+    hipLaunchKernelGGL(k_pattern_lh_scaled, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, e->stream, e->d_pattern_lh.p,
                        sc_a, sc_b, e->nptn - e->n_unobs, P, e->asc_active ? e->pattern_lh_shift : 0.0, out);
     return hipGetLastError();
 }
 
 hipError_t launch_rell(iqhip_engine *e, double *out) {
-    hipLaunchKernelGGL(k_rell, dim3((unsigned)e->nboot), dim3(256), 0, e->stream, e->d_ptn_scaled, e->d_boot,
+    hipLaunchKernelGGL(k_rell, dim3((unsigned)e->nboot), dim3(256), 0, e->stream, e->d_ptn_scaled.p, e->d_boot.p,
                        e->nptn_pad, out);
     return hipGetLastError();
 }

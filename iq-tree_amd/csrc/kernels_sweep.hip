@@ -418,16 +418,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
 
 // IQHIP_DEBUG_SWEEP: workgroup 0's split of the persistent kernel's time (100 MHz clock); the previous launch's figures are
 // printed when the next sweep is launched
-static unsigned long long *sweep_prof_buffer(const iqhip_engine *e) {
-    static unsigned long long *d_prof = nullptr;
+static unsigned long long *sweep_prof_buffer(iqhip_engine *e) {
     if (!e->debug_sweep) return nullptr;
-    if (!d_prof) {
-        if (hipMalloc((void **)&d_prof, 8 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-        (void)hipMemset(d_prof, 0, 8 * sizeof(unsigned long long));
-        return d_prof;
-    }
+    const bool fresh = !e->d_sweep_prof.p;
+    if (e->d_sweep_prof.ensure(e, 8) != hipSuccess) return nullptr;
+    unsigned long long *d_prof = e->d_sweep_prof.p;
     unsigned long long h[8];
-    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d_prof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[6] != 0)
+    if (!fresh && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, d_prof, sizeof h, hipMemcpyDeviceToHost) == hipSuccess && h[6] != 0)
         fprintf(stderr, "[iqhip] k_sweep4 workgroup 0: %llu steps, %llu node updates %.2f us each, theta %.2f us, %llu evaluations %.2f us each, tail %.2f us per step\n",
                 h[6], h[4], h[4] ? h[0] * 0.01 / h[4] : 0.0, h[1] * 0.01 / h[6], h[5], h[5] ? h[2] * 0.01 / h[5] : 0.0, h[3] * 0.01 / h[6]);
     (void)hipMemset(d_prof, 0, 8 * sizeof(unsigned long long));
@@ -468,9 +465,9 @@ hipError_t launch_sweep4(iqhip_engine *e, const SweepOp *d_ops, const SweepStep 
     A.evalc = e->d_evalc;
     A.rates = e->d_rates;
     A.props = e->d_props;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
-    A.theta = e->d_theta;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
+    A.theta = e->d_theta.p;
     A.slab = e->d_slab.p;
     const int grid = sweep4_grid(e), waves = sweep4_waves(e);
     A.nwaves = grid * waves;

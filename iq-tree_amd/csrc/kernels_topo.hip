@@ -243,21 +243,21 @@ __global__ __launch_bounds__(256) void k_topo_argmax(const double *__restrict__ 
 // ---- launches ---------------------------------------------------------------------------------------------------------
 hipError_t launch_topo_gen(iqhip_engine *e, int nsamples, int64_t first_replicate, int64_t ndraws, uint64_t stream_key) {
     const size_t count = (size_t)nsamples * e->nptn_pad;
-    hipError_t s = hipMemsetAsync(e->d_boot, 0, sizeof(float) * count, e->stream);
+    hipError_t s = hipMemsetAsync(e->d_boot.p, 0, sizeof(float) * count, e->stream);
     if (s != hipSuccess) return s;
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ndraws + 255) / 256, 256));
-    hipLaunchKernelGGL(k_topo_gen, dim3(gx, (unsigned)nsamples), dim3(256), 0, e->stream, reinterpret_cast<uint32_t *>(e->d_boot),
-                       e->nptn_pad, e->nptn, e->d_freq_prefix, (uint64_t)e->freq_nsite, stream_key, first_replicate, ndraws);
+    hipLaunchKernelGGL(k_topo_gen, dim3(gx, (unsigned)nsamples), dim3(256), 0, e->stream, reinterpret_cast<uint32_t *>(e->d_boot.p),
+                       e->nptn_pad, e->nptn, e->d_freq_prefix.p, (uint64_t)e->freq_nsite, stream_key, first_replicate, ndraws);
     if ((s = hipGetLastError()) != hipSuccess) return s;
-    hipLaunchKernelGGL(k_topo_counts_to_float, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, e->d_boot, count);
+    hipLaunchKernelGGL(k_topo_counts_to_float, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, e->d_boot.p, count);
     return hipGetLastError();
 }
 
 hipError_t launch_topo_diff_variance(iqhip_engine *e, const int32_t *d_rows, int n, double *d_var) {
     hipError_t s = hipMemsetAsync(d_var, 0, sizeof(double) * (size_t)n * n, e->stream);
     if (s != hipSuccess) return s;
-    hipLaunchKernelGGL(k_topo_diff_variance, dim3((unsigned)n, (unsigned)n), dim3(256), 0, e->stream, e->d_ptnlh, d_rows, n,
-                       e->nptn_pad, e->nptn, e->d_freq, (double)e->freq_nsite, d_var);
+    hipLaunchKernelGGL(k_topo_diff_variance, dim3((unsigned)n, (unsigned)n), dim3(256), 0, e->stream, e->d_ptnlh.p, d_rows, n,
+                       e->nptn_pad, e->nptn, e->d_freq.p, (double)e->freq_nsite, d_var);
     return hipGetLastError();
 }
 

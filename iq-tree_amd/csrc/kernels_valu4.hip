@@ -585,12 +585,7 @@ template <int C, int WG, bool HAS_LOAD, int SP, bool USE_HOLD>
 static hipError_t launch_trav_h(iqhip_engine *e, Trav4Args &A) {
     constexpr int B = 4 * C;
     const size_t lds = trav4_lds_bytes(B, WG, e->plan.lds_doubles, e->plan.state_slots);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kTrav4MaxLdsBytes);
-        attr_set = true;
-    }
+    (void)raise_lds_ceiling<&k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>>(e, kTrav4MaxLdsBytes);
     A.ngroups = trav4_ngroups(e);
     hipLaunchKernelGGL((k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(WG), lds, e->stream, A);
     return hipGetLastError();
@@ -642,8 +637,8 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     Trav4Args A;
     A.fold.slab = e->d_slab.p;
     A.fold.result = e->d_result;
-    A.fold.ticket = e->d_fold_ticket;
-    A.fold.flags = e->d_fold_flags;
+    A.fold.ticket = e->d_fold_ticket.p;
+    A.fold.flags = e->d_fold_flags.p;
     A.fold.nwaves = nwaves;
     A.fold.nrows_scale = fold_rows > 0 ? fold_rows : 0;
     A.fold.root_rows = root ? (e->n_unobs > 0 ? 2 : 1) : 0;
@@ -656,16 +651,16 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
         e->poll_pending = true;
         e->folded_rows = A.fold.nrows_scale;
     }
-    A.ops = e->d_ops;
+    A.ops = e->d_ops.p;
     A.evec = e->d_evec;
     A.inv_evec = e->d_inv_evec;
     A.tip = e->d_tip;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
     A.eval = e->d_eval;
     A.rates = e->d_rates;
     A.props = e->d_props;
-    A.pattern_lh = e->d_pattern_lh;
+    A.pattern_lh = e->d_pattern_lh.p;
     A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
@@ -683,7 +678,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     if (e->plan.small && nsegs == 1) {   // (the plan was not copied to d_ops: it travels with the launch)
         A.small_plan = 1;
         A.small_segs[1] = e->plan.small_nops;
-        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops[q];
+        for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = e->h_ops.p[q];
     } else {
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = DevOp{};
     }
@@ -732,7 +727,7 @@ __global__ __launch_bounds__(256) void k_theta4(DevBranch br, const double *__re
 
 hipError_t launch_theta4(iqhip_engine *e, const DevBranch &br, double *theta_out) {
     const int grid = (int)((e->ntiles + 3) / 4);
-    double *const theta = theta_out ? theta_out : e->d_theta;
+    double *const theta = theta_out ? theta_out : e->d_theta.p;
 #define IQ_THETA(Cv)                                                                        \
     case Cv:                                                                                \
         hipLaunchKernelGGL(k_theta4<Cv>, dim3(grid), dim3(256), 0, e->stream, br, e->d_tip, \
@@ -848,8 +843,8 @@ template <int MODE>
 static hipError_t launch_theta_reduce(iqhip_engine *e, double len, int nwaves, const NewtonState *st = nullptr,
                                       const BatchChain *bc = nullptr) {
     const int grid = (int)((e->ntiles + 3) / 4);
-    const double *theta = bc ? bc->theta : e->d_theta;
-    double *plh = bc ? nullptr : e->d_pattern_lh;
+    const double *theta = bc ? bc->theta : e->d_theta.p;
+    double *plh = bc ? nullptr : e->d_pattern_lh.p;
     const size_t stride = bc ? bc->theta_stride : 0;
     const int ny = bc ? bc->ntasks : 1;
     const int task_rows = (bc && MODE == 0) ? bc->derv_rows : 2;
@@ -857,8 +852,8 @@ static hipError_t launch_theta_reduce(iqhip_engine *e, double len, int nwaves, c
 #define IQ_TR(Cv)                                                                              \
     case Cv:                                                                                   \
         hipLaunchKernelGGL((k_theta_reduce4<Cv, MODE>), dim3(grid, ny), dim3(256), 0, e->stream, \
-                           theta, e->d_eval, e->d_rates, e->d_props, len, e->d_freq,           \
-                           e->d_invar, plh, e->d_slab.p, e->ntiles, e->nptn, nwaves,             \
+                           theta, e->d_eval, e->d_rates, e->d_props, len, e->d_freq.p,           \
+                           e->d_invar.p, plh, e->d_slab.p, e->ntiles, e->nptn, nwaves,             \
                            e->nptn - e->n_unobs, e->theta_a_sc, e->theta_b_sc, st, stride,     \
                            task_rows, task_sc);                                                \
         break;
@@ -921,7 +916,7 @@ hipError_t launch_reduce(iqhip_engine *e, int first_row, int nrows, int nwaves) 
         e->poll_pending = true;
     }
     hipLaunchKernelGGL(k_reduce, dim3(nrows), dim3(256), 0, e->stream, e->d_slab.p, nwaves,
-                       first_row, e->d_result, e->d_fold_ticket + 1, done, seq);
+                       first_row, e->d_result, e->d_fold_ticket.p + 1, done, seq);
     return hipGetLastError();
 }
 

@@ -300,12 +300,8 @@ __global__ __launch_bounds__(kTravWg) void k_traverse4w(const Trav4wArgs A) {
 
 template <int CL>
 static hipError_t launch4w(iqhip_engine *e, const TravLaunch &L, const Trav4wArgs &A) {
-    static bool attr_set = false;   // (per instantiation pair)
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_traverse4w<CL, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kTravMaxLdsBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_traverse4w<CL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kTravMaxLdsBytes);
-        attr_set = true;
-    }
+    if (e->nclass > 1) (void)raise_lds_ceiling<&k_traverse4w<CL, true>>(e, kTravMaxLdsBytes);
+    else (void)raise_lds_ceiling<&k_traverse4w<CL, false>>(e, kTravMaxLdsBytes);
     (void)hipGetLastError();
     if (e->nclass > 1) hipLaunchKernelGGL((k_traverse4w<CL, true>), dim3((unsigned)L.grid), dim3(kTravWg), L.lds_bytes, e->stream, A);
     else hipLaunchKernelGGL((k_traverse4w<CL, false>), dim3((unsigned)L.grid), dim3(kTravWg), L.lds_bytes, e->stream, A);
@@ -315,7 +311,7 @@ static hipError_t launch4w(iqhip_engine *e, const TravLaunch &L, const Trav4wArg
 hipError_t launch_traverse4w(iqhip_engine *e, const TravLaunch &L, const int *seg_table, int nwaves) {
     if (L.variant != TRAV_WIDE4 || !e->wide4 || !e->d_img.p) return hipErrorInvalidValue;
     Trav4wArgs A;
-    A.ops = e->d_ops;
+    A.ops = e->d_ops.p;
     A.evec = e->d_evec;
     A.inv_evec = e->d_inv_evec;
     A.img = e->d_img.p + e->img_generic_off;
@@ -323,10 +319,10 @@ hipError_t launch_traverse4w(iqhip_engine *e, const TravLaunch &L, const int *se
     A.rates = e->d_rates;
     A.tipc = e->d_tipc;
     A.cls = e->d_cls;
-    A.freq = e->d_freq;
-    A.invar = e->d_invar;
+    A.freq = e->d_freq.p;
+    A.invar = e->d_invar.p;
     A.slab = e->d_slab.p;
-    A.fold_flags = e->d_fold_flags;
+    A.fold_flags = e->d_fold_flags.p;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
     A.segs = seg_table;

@@ -75,19 +75,8 @@ static void pars_add_ms(PhaseTimer &timer, double *ms) {
     if (timer.read(&t)) *ms += t;
 }
 
-// a pinned staging buffer of at least `need` words (the stream is drained before an old one is freed)
-static hipError_t pars_pinned(iqhip_engine *e, int32_t **buf, size_t *cap, size_t need) {
-    if (need <= *cap) return hipSuccess;
-    hipError_t s = hipStreamSynchronize(e->stream);
-    if (s != hipSuccess) return s;
-    if (*buf) hipHostFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    const size_t want = need + need / 2 + 64;
-    if ((s = hipHostMalloc((void **)buf, want * sizeof(int32_t))) != hipSuccess) return s;
-    *cap = want;
-    return hipSuccess;
-}
+// pinned staging of at least `need` words, grown by half
+static size_t pars_grown(size_t need) { return need + need / 2 + 64; }
 
 extern "C" int iqhip_pars_shape(iqhip_engine *e, int64_t *nsites, int64_t *nwords, int *nvectors) {
     int rc = pars_require(e, "iqhip_pars_shape", true);
@@ -169,15 +158,15 @@ extern "C" int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int 
     const size_t nblob = (size_t)4 * nops + (size_t)nlev + 1;
     HIPCHK(use_device(e));
     HIPCHK(e->pars.ints.ensure(e, nblob));
-    HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
+    if (nblob > e->h_pars_ops.cap) HIPCHK(e->h_pars_ops.ensure(e, pars_grown(nblob)));
     HIPCHK(hipStreamSynchronize(e->stream));
     {
         std::vector<int32_t> at(start.begin(), start.end() - 1);
-        iqhip_pars_op *sorted = reinterpret_cast<iqhip_pars_op *>(e->h_pars_ops);
+        iqhip_pars_op *sorted = reinterpret_cast<iqhip_pars_op *>(e->h_pars_ops.p);
         for (int k = 0; k < nops; k++) sorted[at[(size_t)level[(size_t)k]]++] = ops[k];
-        std::copy(start.begin(), start.end(), e->h_pars_ops + (size_t)4 * nops);
+        std::copy(start.begin(), start.end(), e->h_pars_ops.p + (size_t)4 * nops);
     }
-    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops.p, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
     PhaseTimer timer(e, 1);
     timer.mark();
     HIPCHK(launch_pars_update(e, reinterpret_cast<const iqhip_pars_op *>(e->pars.ints.p), e->pars.ints.p + (size_t)4 * nops, nlev));
@@ -208,11 +197,11 @@ static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int ta
     const size_t need_out = (size_t)2 * nbranch + 2;
     HIPCHK(e->pars.ints.ensure(e, (size_t)2 * nbranch));
     HIPCHK(e->pars.out.ensure(e, need_out));
-    HIPCHK(pars_pinned(e, &e->h_pars_ends, &e->h_pars_ends_cap, (size_t)2 * nbranch));
-    HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
+    if ((size_t)2 * nbranch > e->h_pars_ends.cap) HIPCHK(e->h_pars_ends.ensure(e, pars_grown((size_t)2 * nbranch)));
+    if (count > e->h_pars_out.cap) HIPCHK(e->h_pars_out.ensure(e, pars_grown(count)));
     // (no copy of h_pars_ends or into h_pars_out is in flight: every call of this function ends with a synchronise)
-    memcpy(e->h_pars_ends, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
-    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ends, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
+    memcpy(e->h_pars_ends.p, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ends.p, sizeof(int32_t) * 2 * (size_t)nbranch, hipMemcpyHostToDevice, e->stream));
     PhaseTimer timer(e, 1);
     int nlaunches = 0;
     timer.mark();
@@ -223,9 +212,9 @@ static int pars_scores(iqhip_engine *e, const int32_t *ends, int nbranch, int ta
         e->pars_counts[3] += nbranch;
         pars_add_ms(timer, &e->pars_ms[1]);
     }
-    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out.p, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    out.assign(e->h_pars_out, e->h_pars_out + count);
+    out.assign(e->h_pars_out.p, e->h_pars_out.p + count);
     return IQHIP_OK;
 }
 
@@ -317,18 +306,18 @@ extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jo
     HIPCHK(use_device(e));
     HIPCHK(e->pars.ints.ensure(e, nblob));
     HIPCHK(e->pars.out.ensure(e, nout));
-    HIPCHK(pars_pinned(e, &e->h_pars_ops, &e->h_pars_ops_cap, nblob));
-    HIPCHK(pars_pinned(e, &e->h_pars_out, &e->h_pars_out_cap, count));
+    if (nblob > e->h_pars_ops.cap) HIPCHK(e->h_pars_ops.ensure(e, pars_grown(nblob)));
+    if (count > e->h_pars_out.cap) HIPCHK(e->h_pars_out.ensure(e, pars_grown(count)));
     HIPCHK(hipStreamSynchronize(e->stream));   // (the staging buffer may still feed the previous update's copy)
-    memcpy(e->h_pars_ops, jobs, sizeof(iqhip_pars_spr_job) * (size_t)njobs);
-    iqhip_pars_spr_step *hs = reinterpret_cast<iqhip_pars_spr_step *>(e->h_pars_ops + (size_t)4 * njobs);
+    memcpy(e->h_pars_ops.p, jobs, sizeof(iqhip_pars_spr_job) * (size_t)njobs);
+    iqhip_pars_spr_step *hs = reinterpret_cast<iqhip_pars_spr_step *>(e->h_pars_ops.p + (size_t)4 * njobs);
     int64_t scored = 0;
     for (int k = 0; k < nsteps; k++) {
         hs[k] = steps[k];
         hs[k].parent = depth[(size_t)k];
         if (depth[(size_t)k] >= 0 && !(steps[k].flags & IQHIP_PARS_SPR_NO_SCORE)) scored++;
     }
-    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, e->h_pars_ops.p, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
     PhaseTimer timer(e, 1);
     int nlaunches = 0;
     timer.mark();
@@ -339,9 +328,9 @@ extern "C" int iqhip_pars_spr_scan(iqhip_engine *e, const iqhip_pars_spr_job *jo
     e->pars_spr_counts[0] += nlaunches;
     e->pars_spr_counts[1] += scored;
     pars_add_ms(timer, &e->pars_spr_ms);
-    HIPCHK(hipMemcpyAsync(e->h_pars_out, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_pars_out.p, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    const int32_t *res = e->h_pars_out;
+    const int32_t *res = e->h_pars_out.p;
     if (score) {
         memcpy(score, res, sizeof(int32_t) * (size_t)nsteps);
         res += nsteps;

@@ -24,29 +24,6 @@ namespace {
 constexpr int kPartItemTiles4 = 16;     // 64-pattern tiles per work item (4-state engines): 1024 patterns
 constexpr int kPartItemTilesM = 32;     // 16-pattern tiles per work item (matrix-core engines): 512 patterns
 constexpr size_t kPartMaxLdsBytes = 64 * 1024;
-
-// a device buffer with its pinned staging twin
-template <typename T>
-struct Twin {
-    T *d = nullptr, *h = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(hipStream_t s, size_t count) {
-        if (count <= cap) return hipSuccess;
-        hipError_t rc = hipStreamSynchronize(s);
-        if (rc != hipSuccess) return rc;
-        release();
-        const size_t want = std::max(count, (size_t)64);
-        if ((rc = hipMalloc((void **)&d, want * sizeof(T))) != hipSuccess) return rc;
-        if ((rc = hipHostMalloc((void **)&h, want * sizeof(T))) != hipSuccess) return rc;
-        cap = want;
-        return hipSuccess;
-    }
-    void release() {
-        if (d) hipFree(d);
-        if (h) hipHostFree(h);
-        d = nullptr; h = nullptr; cap = 0;
-    }
-};
 }  // namespace
 
 struct iqhip_partition {
@@ -56,13 +33,12 @@ struct iqhip_partition {
     hipStream_t stream = nullptr;
     std::vector<hipEvent_t> ev;      // one per member, recorded on its stream
     hipEvent_t ev_done = nullptr;    // recorded on the group's stream behind its last launch
-    Twin<char> table;                // [nparts] PartDesc ++ [nitems] PartItem
+    PairBuf<char> table;             // [nparts] PartDesc ++ [nitems] PartItem
     std::vector<char> uploaded;      // the bytes of `table` the device holds
-    Twin<PartScale> scale;
-    Twin<double> out;                // per member: lnL sums / scale-factor terms
-    Twin<NewtonState> state;
-    double *d_partials = nullptr;    // [nitems][2]
-    size_t partials_cap = 0;
+    PairBuf<PartScale> scale;
+    PairBuf<double> out;             // per member: lnL sums / scale-factor terms
+    PairBuf<NewtonState> state;
+    DevBuf<double> d_partials;       // [nitems][2]
     int nitems = 0, lds_doubles = 0;
     // iqhip_debug_partition_timing
     std::vector<hipEvent_t> tev;
@@ -124,12 +100,12 @@ int refresh_table(iqhip_partition *g) {
         const iqhip_engine *e = g->m[p];
         PartDesc &D = desc[p];
         memset(&D, 0, sizeof D);
-        D.theta = e->d_theta;
+        D.theta = e->d_theta.p;
         D.evalc = e->d_evalc;
         D.rates = e->d_rates;
         D.props = e->d_props;
-        D.freq = e->d_freq;
-        D.invar = e->d_invar;
+        D.freq = e->d_freq.p;
+        D.invar = e->d_invar.p;
         D.a_sc = e->theta_a_sc;
         D.b_sc = e->theta_b_sc;
         D.nptn = e->nptn;
@@ -159,28 +135,20 @@ int refresh_table(iqhip_partition *g) {
     std::vector<char> now(bytes);
     memcpy(now.data(), desc.data(), bytes_desc);
     memcpy(now.data() + bytes_desc, items.data(), bytes - bytes_desc);
-    if ((size_t)g->nitems > g->partials_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->d_partials) hipFree(g->d_partials);
-        g->d_partials = nullptr;
-        g->partials_cap = 0;
-        HIPCHK(hipMalloc((void **)&g->d_partials, sizeof(double) * 2 * (size_t)g->nitems));
-        g->partials_cap = (size_t)g->nitems;
-    }
+    HIPCHK(g->d_partials.ensure(g->stream, 2 * (size_t)g->nitems));
     if (now == g->uploaded) return IQHIP_OK;
-    const size_t old_cap = g->table.cap;
+    if (bytes > g->table.d.cap) g->uploaded.clear();   // (a new buffer holds nothing)
     HIPCHK(g->table.ensure(g->stream, bytes));
-    if (g->table.cap != old_cap) g->uploaded.clear();
     // (the staging is free: every call of the group ends with a wait for its stream)
-    memcpy(g->table.h, now.data(), bytes);
-    HIPCHK(hipMemcpyAsync(g->table.d, g->table.h, bytes, hipMemcpyHostToDevice, g->stream));
+    memcpy(g->table.h.p, now.data(), bytes);
+    HIPCHK(hipMemcpyAsync(g->table.d.p, g->table.h.p, bytes, hipMemcpyHostToDevice, g->stream));
     g->uploaded.swap(now);
     return IQHIP_OK;
 }
 
-const PartDesc *d_desc(const iqhip_partition *g) { return reinterpret_cast<const PartDesc *>(g->table.d); }
+const PartDesc *d_desc(const iqhip_partition *g) { return reinterpret_cast<const PartDesc *>(g->table.d.p); }
 const PartItem *d_items(const iqhip_partition *g) {
-    return reinterpret_cast<const PartItem *>(g->table.d + sizeof(PartDesc) * (size_t)g->nparts);
+    return reinterpret_cast<const PartItem *>(g->table.d.p + sizeof(PartDesc) * (size_t)g->nparts);
 }
 
 // the group's stream waits for everything enqueued on the members' streams so far
@@ -209,9 +177,9 @@ int use_group(iqhip_partition *g, const char *what) {
 // the MODE 1 pass over the thetas -> out.h[0 .. nparts) after the caller's wait for the stream; st: at its result, only once
 // it is done (the pass is enqueued behind a chunk of steps that may not have finished the solve)
 int enqueue_part_lnl(iqhip_partition *g, const NewtonState *st, double x) {
-    HIPCHK(launch_part_derv(g->stream, 1, d_desc(g), d_items(g), g->nitems, g->lds_doubles, st, x, g->d_partials));
-    HIPCHK(launch_part_lnl_finish(g->stream, d_desc(g), g->nparts, g->d_partials, g->out.d));
-    HIPCHK(hipMemcpyAsync(g->out.h, g->out.d, sizeof(double) * (size_t)g->nparts, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(launch_part_derv(g->stream, 1, d_desc(g), d_items(g), g->nitems, g->lds_doubles, st, x, g->d_partials.p));
+    HIPCHK(launch_part_lnl_finish(g->stream, d_desc(g), g->nparts, g->d_partials.p, g->out.d.p));
+    HIPCHK(hipMemcpyAsync(g->out.h.p, g->out.d.p, sizeof(double) * (size_t)g->nparts, hipMemcpyDeviceToHost, g->stream));
     g->launches += 2;
     return IQHIP_OK;
 }
@@ -231,7 +199,7 @@ int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, 
     if (const char *s = getenv("IQHIP_PART_STEPS")) chunk_env = atoi(s);
     const bool timing = g->m[0]->timing;
     size_t nev = 0;
-    HIPCHK(launch_newton_state_init_on(g->stream, g->state.d, xguess, x1, x2, xacc, max_steps));
+    HIPCHK(launch_newton_state_init_on(g->stream, g->state.d.p, xguess, x1, x2, xacc, max_steps));
     g->launches++;
     for (int enq = 0;;) {
         const int chunk = chunk_env > 0 ? chunk_env : (enq == 0 ? std::min(4, max_steps + 1) : 2);
@@ -245,21 +213,21 @@ int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, 
                 nev += 3;
                 HIPCHK(hipEventRecord(e0, g->stream));
             }
-            HIPCHK(launch_part_derv(g->stream, 0, d_desc(g), d_items(g), g->nitems, g->lds_doubles, g->state.d, 0.0,
-                                    g->d_partials));
+            HIPCHK(launch_part_derv(g->stream, 0, d_desc(g), d_items(g), g->nitems, g->lds_doubles, g->state.d.p, 0.0,
+                                    g->d_partials.p));
             if (timing) HIPCHK(hipEventRecord(e1, g->stream));
-            HIPCHK(launch_part_newton_update(g->stream, d_desc(g), g->nparts, g->d_partials, g->state.d));
+            HIPCHK(launch_part_newton_update(g->stream, d_desc(g), g->nparts, g->d_partials.p, g->state.d.p));
             if (timing) HIPCHK(hipEventRecord(e2, g->stream));
             g->launches += 2;
         }
         enq += chunk;
         if (want_lnl) {
-            const int rc = enqueue_part_lnl(g, g->state.d, 0.0);
+            const int rc = enqueue_part_lnl(g, g->state.d.p, 0.0);
             if (rc) return rc;
         }
-        HIPCHK(hipMemcpyAsync(g->state.h, g->state.d, sizeof(NewtonState), hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(g->state.h.p, g->state.d.p, sizeof(NewtonState), hipMemcpyDeviceToHost, g->stream));
         HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->state.h->done) break;
+        if (g->state.h.p->done) break;
         if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
     }
     if (timing) {
@@ -272,7 +240,7 @@ int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, 
             g->ms[1] += b;
         }
     }
-    *result = *g->state.h;
+    *result = *g->state.h.p;
     return IQHIP_OK;
 }
 
@@ -322,16 +290,11 @@ extern "C" void iqhip_partition_destroy(iqhip_partition *g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    g->table.release();
-    g->scale.release();
-    g->out.release();
-    g->state.release();
-    if (g->d_partials) hipFree(g->d_partials);
     for (hipEvent_t e : g->ev) hipEventDestroy(e);
     for (hipEvent_t e : g->tev) hipEventDestroy(e);
     if (g->ev_done) hipEventDestroy(g->ev_done);
     if (g->stream) hipStreamDestroy(g->stream);
-    delete g;
+    delete g;   // (its buffers free themselves: the stream has drained)
 }
 
 extern "C" int iqhip_partition_set_rates(iqhip_partition *g, const double *rate) {
@@ -366,7 +329,7 @@ extern "C" int iqhip_partition_newton_branch(iqhip_partition *g, double xguess, 
     rc = newton_status(st.status);
     if (rc) return rc;
     NewtonResult(st).store(optx, d2l, nsteps);
-    if (part_lnl) memcpy(part_lnl, g->out.h, sizeof(double) * (size_t)g->nparts);
+    if (part_lnl) memcpy(part_lnl, g->out.h.p, sizeof(double) * (size_t)g->nparts);
     return IQHIP_OK;
 }
 
@@ -388,7 +351,7 @@ extern "C" int iqhip_partition_lnl_from_theta(iqhip_partition *g, double x, doub
     if (rc) return rc;
     if (rc2) return rc2;
     HIPCHK(hipStreamSynchronize(g->stream));
-    memcpy(part_lnl, g->out.h, sizeof(double) * (size_t)g->nparts);
+    memcpy(part_lnl, g->out.h.p, sizeof(double) * (size_t)g->nparts);
     return IQHIP_OK;
 }
 
@@ -415,31 +378,31 @@ extern "C" int iqhip_partition_traverse_lnl(iqhip_partition *g, const iqhip_node
         rc = submit_traverse(e, nops ? mine.data() : nullptr, nops, true, a, b, len * s);
         if (rc) return rc;
         if (e->d_result != e->d_result_own)   // caller-bound device result vector
-            HIPCHK(hipMemcpyAsync(e->h_result, e->d_result, sizeof(double) * (size_t)(2 + nops), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(e->h_result.p, e->d_result, sizeof(double) * (size_t)(2 + nops), hipMemcpyDeviceToHost, e->stream));
         DevBranch br;
         rc = build_branch(e, a, b, len * s, -1, &br);   // (a lookup: the scale counters of the two ends)
         if (rc) return rc;
-        g->scale.h[p] = PartScale{br.a_sc, br.b_sc, e->d_freq, e->nptn};
+        g->scale.h.p[p] = PartScale{br.a_sc, br.b_sc, e->d_freq.p, e->nptn};
     }
     HIPCHK(hipSetDevice(g->device));
     rc = wait_for_members(g);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(g->scale.d, g->scale.h, sizeof(PartScale) * (size_t)P, hipMemcpyHostToDevice, g->stream));
-    HIPCHK(launch_part_scale_terms(g->stream, g->scale.d, P, g->out.d));
+    HIPCHK(hipMemcpyAsync(g->scale.d.p, g->scale.h.p, sizeof(PartScale) * (size_t)P, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(launch_part_scale_terms(g->stream, g->scale.d.p, P, g->out.d.p));
     g->launches++;
-    HIPCHK(hipMemcpyAsync(g->out.h, g->out.d, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(g->out.h.p, g->out.d.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, g->stream));
     rc = members_wait(g);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g->stream));   // the one wait: every member's stream has drained behind its event
     for (int p = 0; p < P; p++) {
         iqhip_engine *e = g->m[p];
         result_arrived(e);
-        double v = e->h_result[0];
+        double v = e->h_result.p[0];
         if (isnan(v) || isinf(v)) {   // phylokernel.h:848-866, the rare slow path
             rc = eng_repair_lnl(e, &v);
             if (rc) return rc;
         }
-        part_lnl[p] = v + g->out.h[p];
+        part_lnl[p] = v + g->out.h.p[p];
     }
     return IQHIP_OK;
 }

@@ -34,29 +34,23 @@ int segment_table_ops(const Units &u) { return devops_for(sizeof(int) * 2 * (1 +
 
 // d_ops and its pinned staging copy h_ops (plain host memory for a planning-only engine) for `nops` DevOps
 int ensure_plan_capacity(iqhip_engine *e, int nops) {
-    if (nops <= e->ops_cap) return IQHIP_OK;
-    const int cap = std::max(64, nops * 2);
+    if ((size_t)nops <= std::min(e->d_ops.cap, e->h_ops.cap)) return IQHIP_OK;
+    const size_t cap = (size_t)std::max(64, nops * 2);
     e->plan_cache.uploaded.clear();
-    HIPCHK(regrow(e, &e->d_ops, &e->ops_cap, 0, cap));   // (plain regrow: ops_cap counts ops and is set once h_ops has grown too)
-    if (e->planner) free(e->h_ops);
-    else if (e->h_ops) hipHostFree(e->h_ops);
-    e->h_ops = nullptr;
-    if (e->planner) e->h_ops = static_cast<DevOp *>(calloc((size_t)cap, sizeof(DevOp)));
-    else HIPCHK(hipHostMalloc((void **)&e->h_ops, sizeof(DevOp) * cap));
-    if (!e->h_ops) return fail(IQHIP_ERR_NOMEM, "plan staging");
-    e->ops_cap = cap;
+    HIPCHK(e->d_ops.ensure(e, cap));
+    if (e->h_ops.ensure(e, cap) != hipSuccess) return fail(IQHIP_ERR_NOMEM, "plan staging");
     return IQHIP_OK;
 }
 
 // every pointer a valid target, nothing used: the starting point of each descriptor, and the look-ahead sentinels
 void dummy_op(const iqhip_engine *e, DevOp &d) {
     memset(&d, 0, sizeof(d));
-    d.dst = e->dummy.plh;
-    d.dst_sc = e->dummy.sc;
-    d.pf = d.ld = e->dummy.plh;
-    d.pf_sc = d.ld_sc = e->dummy.sc;
-    d.sl = d.sr = e->d_states;
-    d.tabL = d.tabR = e->d_leaf_tab;
+    d.dst = e->dummy.plh.p;
+    d.dst_sc = e->dummy.sc.p;
+    d.pf = d.ld = e->dummy.plh.p;
+    d.pf_sc = d.ld_sc = e->dummy.sc.p;
+    d.sl = d.sr = e->d_states.p;
+    d.tabL = d.tabR = e->d_leaf_tab.p;
 }
 
 // Same op list as last time and no key created / released / moved since: the descriptors on the device are still the
@@ -232,7 +226,7 @@ int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const 
     int prev_dst = -1;
     for (int k = 0; k < nops; k++) {
         const iqhip_node_op &o = ops[u.order[k]];
-        DevOp &d = e->h_ops[k];
+        DevOp &d = e->h_ops.p[k];
         dummy_op(e, d);
         d.out_row = u.order[k];
         d.no_scale = (o.flags & IQHIP_OP_NO_SCALE) ? 1 : (((o.flags & IQHIP_OP_SCALAR_RULE) || e->scalar_rule_all) ? 2 : 0);
@@ -248,14 +242,14 @@ int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const 
         int didx;
         rc = slab_for_key(e, o.dst_key, true, &didx);
         if (rc) return rc;
-        if ((lkind != CHILD_LEAF && lp == e->slabs[didx].plh) || (rkind != CHILD_LEAF && rp == e->slabs[didx].plh))
+        if ((lkind != CHILD_LEAF && lp == e->slabs[didx].plh.p) || (rkind != CHILD_LEAF && rp == e->slabs[didx].plh.p))
             return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
         if (lkind == CHILD_PREV && rkind == CHILD_PREV)
             return fail(IQHIP_ERR_INVALID, "node update uses the same vector for both children");
         double llen = o.left_len, rlen = o.right_len;
         const double *llen_p = len_ptrs ? len_ptrs[2 * u.order[k]] : nullptr, *rlen_p = len_ptrs ? len_ptrs[2 * u.order[k] + 1] : nullptr;
-        d.dst = e->slabs[didx].plh;
-        d.dst_sc = e->slabs[didx].sc;
+        d.dst = e->slabs[didx].plh.p;
+        d.dst_sc = e->slabs[didx].sc.p;
         if (e->mfma && !e->mfma_pipelined) {
             // generic matrix-core kernel: both children are read from memory (pf = left, ld = right)
             if (lkind != CHILD_LEAF) { lkind = CHILD_LOAD; d.pf = lp; d.pf_sc = lsc; } else d.sl = lst;
@@ -296,28 +290,28 @@ void park_operands(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     const bool hold_in_lds = e->mfma && e->mfma_pipelined && e->hold_lds && e->n == 20 && !e->cat_split;
     std::unordered_map<const double *, int> producer;   // vector -> the op of this plan that writes it
     for (int k = 0; k < nops && (hold_regs || hold_in_lds); k++) {
-        DevOp &d = e->h_ops[k];
+        DevOp &d = e->h_ops.p[k];
         const auto it = d.left_kind == CHILD_PF ? producer.find(d.pf) : producer.end();
         const int j = it == producer.end() ? -1 : it->second;
         producer[d.dst] = k;
         if (j < 0) continue;
-        bool ok = !e->h_ops[j].push_hold && seg_of[j] == seg_of[k];
+        bool ok = !e->h_ops.p[j].push_hold && seg_of[j] == seg_of[k];
         if (hold_in_lds && top_stage_may_share_tiles(e) && seg_of[k] == 0) ok = false;   // (no parking place there)
         for (int q = j + 1; q < k && ok; q++) {
-            const DevOp &m = e->h_ops[q];
+            const DevOp &m = e->h_ops.p[q];
             ok = m.left_kind != CHILD_PF && m.left_kind != CHILD_HOLD && m.right_kind != CHILD_LOAD && !m.push_hold;
         }
         if (!ok) continue;
-        e->h_ops[j].push_hold = 1;
+        e->h_ops.p[j].push_hold = 1;
         d.left_kind = CHILD_HOLD;
-        d.pf = e->dummy.plh;
-        d.pf_sc = e->dummy.sc;
+        d.pf = e->dummy.plh.p;
+        d.pf_sc = e->dummy.sc.p;
         d.real_mask &= ~1;
         e->plan.nhold++;
     }
     if (e->debug_plan) {
         int npf = 0;
-        for (int k = 0; k < nops; k++) npf += (e->h_ops[k].left_kind == CHILD_PF) + (e->h_ops[k].right_kind == CHILD_LOAD);
+        for (int k = 0; k < nops; k++) npf += (e->h_ops.p[k].left_kind == CHILD_PF) + (e->h_ops.p[k].right_kind == CHILD_LOAD);
         fprintf(stderr, "[iqhip] plan: %d children read back from memory, %d parked\n", npf, e->plan.nhold);
     }
 }
@@ -335,11 +329,11 @@ int assign_leaf_tables(iqhip_engine *e, int nops) {
     std::vector<std::pair<int, int>> uses;  // (op index, side) -> slot, resolved to pointers after (re)allocation
     std::vector<int> use_slot;
     for (int k = 0; k < nops; k++) {
-        const DevOp &d = e->h_ops[k];
+        const DevOp &d = e->h_ops.p[k];
         for (int side = 0; side < 2; side++) {
             if ((side ? d.right_kind : d.left_kind) != CHILD_LEAF) continue;
             const uint8_t *row = side ? d.sr : d.sl;
-            const int taxon = (int)((row - e->d_states) / e->nptn_pad);
+            const int taxon = (int)((row - e->d_states.p) / e->nptn_pad);
             const double *len_p = side ? d.right_len_p : d.left_len_p;   // (sweeps: the length is on the device)
             const double len = len_p ? NAN : (side ? d.right_len : d.left_len);
             std::vector<Use> &u = seen[taxon];
@@ -358,25 +352,25 @@ int assign_leaf_tables(iqhip_engine *e, int nops) {
         }
     }
     const size_t need = (size_t)e->ntaxa + (size_t)noverflow;
-    if (need > e->leaf_tab_slots) {
-        HIPCHK(regrow(e, &e->d_leaf_tab, &e->leaf_tab_slots, need + 16, (need + 16) * per));   // (plain regrow: the capacity counts tables)
+    if (need > e->d_leaf_tab.cap / per) {
+        HIPCHK(e->d_leaf_tab.ensure(e, (need + 16) * per));
         e->plan_cache.uploaded.clear();
         // a new buffer holds no tables: everything this plan uses is dirty
         dirty.insert(dirty.end(), clean.begin(), clean.end());
         clean.clear();
-        e->tab_len.assign(e->leaf_tab_slots, NAN);
+        e->tab_len.assign(e->d_leaf_tab.cap / per, NAN);
     }
-    if (e->tab_len.size() < e->leaf_tab_slots) e->tab_len.resize(e->leaf_tab_slots, NAN);
+    if (e->tab_len.size() < e->d_leaf_tab.cap / per) e->tab_len.resize(e->d_leaf_tab.cap / per, NAN);
     // non-leaf children point at slot 0: the kernels may request a row unconditionally (one step ahead)
-    for (int k = 0; k < nops; k++) e->h_ops[k].tabL = e->h_ops[k].tabR = e->d_leaf_tab;
+    for (int k = 0; k < nops; k++) e->h_ops.p[k].tabL = e->h_ops.p[k].tabR = e->d_leaf_tab.p;
     for (size_t q = 0; q < uses.size(); q++) {
-        DevOp &d = e->h_ops[uses[q].first];
-        (uses[q].second ? d.tabR : d.tabL) = e->d_leaf_tab + (size_t)use_slot[q] * per;
+        DevOp &d = e->h_ops.p[uses[q].first];
+        (uses[q].second ? d.tabR : d.tabL) = e->d_leaf_tab.p + (size_t)use_slot[q] * per;
     }
     for (std::vector<TabJob> *v : {&dirty, &clean})
         for (TabJob &j : *v) {
             const size_t slot = (size_t)j.tab;
-            j.tab = e->d_leaf_tab + slot * per;
+            j.tab = e->d_leaf_tab.p + slot * per;
             e->tab_len[slot] = slot < (size_t)e->ntaxa ? j.len : NAN;  // overflow slots are never reused
             e->plan.tab_jobs.push_back(j);
         }
@@ -392,25 +386,26 @@ int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_
     if (!(cherry_candidate(e) && e->mfma_pipelined && have_pair && nops >= 8)) return IQHIP_OK;
     const size_t per = (size_t)e->cherry_npairs * e->block;
     const size_t want = (size_t)2 * e->ntaxa + 16;
-    const bool fresh = e->cherry_cap < want;   // (a new buffer holds no tables)
-    if (fresh) HIPCHK(regrow(e, &e->d_cherry_tab, &e->cherry_cap, want, want * per));   // (plain regrow: cherry_cap counts slots)
+    const bool fresh = e->d_cherry_tab.cap < want * per;   // (a new buffer holds no tables)
+    if (fresh) HIPCHK(e->d_cherry_tab.ensure(e, want * per));
+    const size_t cherry_cap = e->d_cherry_tab.cap / per;    // slots allocated
     // room for every cherry a plan can hold; a search that has walked through more pairs than that starts over
-    if (fresh || e->cherry_slots.size() + (size_t)e->ntaxa / 2 + 1 > e->cherry_cap) {
+    if (fresh || e->cherry_slots.size() + (size_t)e->ntaxa / 2 + 1 > cherry_cap) {
         e->cherry_slot_of.clear();
         e->cherry_slots.clear();
     }
     const uint64_t stamp = ++e->cherry_stamp;
     for (int k = 0; k < nops; k++) {
-        DevOp &d = e->h_ops[k];
+        DevOp &d = e->h_ops.p[k];
         if (d.left_kind != CHILD_LEAF || d.right_kind != CHILD_LEAF || d.left_len_p || d.right_len_p) continue;
         // (the top stage's two-waves-per-tile / row-split kernels compute their cherries)
         if ((top_stage_may_share_tiles(e) || top_stage_may_mix_roles64(e)) && seg_of[k] == 0) continue;
-        const uint64_t tl = (uint64_t)((d.sl - e->d_states) / e->nptn_pad), tr = (uint64_t)((d.sr - e->d_states) / e->nptn_pad);
+        const uint64_t tl = (uint64_t)((d.sl - e->d_states.p) / e->nptn_pad), tr = (uint64_t)((d.sr - e->d_states.p) / e->nptn_pad);
         const uint64_t key = (tl << 32) | tr;
         auto it = e->cherry_slot_of.find(key);
         int slot;
         if (it == e->cherry_slot_of.end()) {
-            if (e->cherry_slots.size() >= e->cherry_cap) continue;
+            if (e->cherry_slots.size() >= cherry_cap) continue;
             slot = (int)e->cherry_slots.size();
             e->cherry_slots.emplace_back();
             e->cherry_slot_of[key] = slot;
@@ -427,7 +422,7 @@ int assign_cherry_tables(iqhip_engine *e, int nops, const std::vector<int> &seg_
             if (cs.stamp != stamp) e->plan.cherry_jobs.push_back(slot);
         }
         cs.stamp = stamp;
-        d.cherry = e->d_cherry_tab + (size_t)slot * per;
+        d.cherry = e->d_cherry_tab.p + (size_t)slot * per;
         e->plan.uses_cherry = true;
     }
     return IQHIP_OK;
@@ -444,7 +439,7 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     const int slot_sz = e->mfma ? 0 : trav4_lds(B, e->wg_size).slot_doubles;   // (slot 0: the non-leaf children's)
     int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
     for (int k = 0; k < nops; k++) {
-        DevOp &d = e->h_ops[k];
+        DevOp &d = e->h_ops.p[k];
         const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : B;
         const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : B;
         // 4-state path: each leaf child also stages one state byte per thread in LDS
@@ -452,7 +447,7 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         const int need = szl + szr + nleaf * slot_sz;
         if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
         if ((used + need > budget || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
-            e->h_ops[chunk_start].chunk_nops = k - chunk_start;
+            e->h_ops.p[chunk_start].chunk_nops = k - chunk_start;
             chunk_start = k; used = slot_sz; regs = 0; slots = 1;
         }
         d.lds_left = regs; d.lds_right = regs + szl;
@@ -463,7 +458,7 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         d.sr_slot = d.right_kind == CHILD_LEAF ? slots++ : 0;
         if (slots > max_slots) max_slots = slots;
     }
-    if (nops > 0) e->h_ops[chunk_start].chunk_nops = nops - chunk_start;
+    if (nops > 0) e->h_ops.p[chunk_start].chunk_nops = nops - chunk_start;
     e->plan.state_slots = max_slots;
     e->plan.lds_doubles = max_used;
     return IQHIP_OK;
@@ -476,9 +471,9 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
 // use it: a null tabL / tabR of a non-leaf child was a GPU memory fault in round 2 that this check finds without a GPU.
 int check_plan(iqhip_engine *e, int nops, int nsentinels) {
     std::unordered_set<const void *> vecs, scs;
-    for (const Slab &sl : e->slabs) { vecs.insert(sl.plh); scs.insert(sl.sc); }
-    vecs.insert(e->dummy.plh);
-    scs.insert(e->dummy.sc);
+    for (const Slab &sl : e->slabs) { vecs.insert(sl.plh.p); scs.insert(sl.sc.p); }
+    vecs.insert(e->dummy.plh.p);
+    scs.insert(e->dummy.sc.p);
     const size_t per = (e->mfma && e->mfma_pipelined) ? leaf_table_doubles(e) : 0;
     char msg[256];
     auto bad = [&](int k, const char *what) {
@@ -486,18 +481,18 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         return fail(IQHIP_ERR_INVALID, msg);
     };
     auto state_row = [&](const uint8_t *p) {
-        if (!p || !e->d_states || p < e->d_states) return false;
-        const size_t off = (size_t)(p - e->d_states);
+        if (!p || !e->d_states.p || p < e->d_states.p) return false;
+        const size_t off = (size_t)(p - e->d_states.p);
         return off % (size_t)e->nptn_pad == 0 && off / (size_t)e->nptn_pad < (size_t)e->ntaxa;
     };
     auto table = [&](const double *p) {
-        if (e->plan.nleaf_tabs == 0 && !e->d_leaf_tab) return p == nullptr;  // kernel variant without tables
-        if (!p || !e->d_leaf_tab || p < e->d_leaf_tab || per == 0) return false;
-        const size_t off = (size_t)(p - e->d_leaf_tab);
-        return off % per == 0 && off / per < e->leaf_tab_slots;
+        if (e->plan.nleaf_tabs == 0 && !e->d_leaf_tab.p) return p == nullptr;  // kernel variant without tables
+        if (!p || !e->d_leaf_tab.p || p < e->d_leaf_tab.p || per == 0) return false;
+        const size_t off = (size_t)(p - e->d_leaf_tab.p);
+        return off % per == 0 && off / per < e->d_leaf_tab.cap / per;
     };
     for (int k = 0; k < nops + nsentinels; k++) {
-        const DevOp &d = e->h_ops[k];
+        const DevOp &d = e->h_ops.p[k];
         if (!vecs.count(d.dst) || d.dst == nullptr) return bad(k, "dst is not a vector slab");
         if (!scs.count(d.dst_sc)) return bad(k, "dst_sc is not a counter slab");
         if (!vecs.count(d.pf)) return bad(k, "pf (streamed child) is not a vector slab / the dummy slab");
@@ -508,20 +503,20 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         if (!table(d.tabL) || !table(d.tabR)) return bad(k, "tabL / tabR is not a K2 table slot");
         if (d.cherry) {
             const size_t cper = (size_t)e->cherry_npairs * e->block;
-            if (!e->d_cherry_tab || cper == 0 || d.cherry < e->d_cherry_tab || (size_t)(d.cherry - e->d_cherry_tab) % cper != 0 ||
-                (size_t)(d.cherry - e->d_cherry_tab) / cper >= e->cherry_cap || k >= nops || d.left_kind != CHILD_LEAF ||
+            if (!e->d_cherry_tab.p || cper == 0 || d.cherry < e->d_cherry_tab.p || (size_t)(d.cherry - e->d_cherry_tab.p) % cper != 0 ||
+                (size_t)(d.cherry - e->d_cherry_tab.p) / cper >= e->d_cherry_tab.cap / cper || k >= nops || d.left_kind != CHILD_LEAF ||
                 d.right_kind != CHILD_LEAF)
                 return bad(k, "cherry is not a cherry-table slot of an op with two leaf children");
         }
         if (k >= nops) continue;  // sentinels: pointers only
-        if (d.dst == e->dummy.plh || d.dst_sc == e->dummy.sc) return bad(k, "a real op writes the dummy slab");
+        if (d.dst == e->dummy.plh.p || d.dst_sc == e->dummy.sc.p) return bad(k, "a real op writes the dummy slab");
         const bool lk = d.left_kind == CHILD_LEAF || d.left_kind == CHILD_PF || d.left_kind == CHILD_HOLD ||
                         (d.left_kind == CHILD_LOAD && e->mfma && !e->mfma_pipelined);
         const bool rk = d.right_kind == CHILD_LEAF || d.right_kind == CHILD_PREV || d.right_kind == CHILD_LOAD;
         if (!lk || !rk) return bad(k, "child kinds are not in canonical form");
-        if (d.left_kind == CHILD_PF && (d.pf == e->dummy.plh || !(d.real_mask & 1))) return bad(k, "streamed child without a real vector");
+        if (d.left_kind == CHILD_PF && (d.pf == e->dummy.plh.p || !(d.real_mask & 1))) return bad(k, "streamed child without a real vector");
         if (d.left_kind != CHILD_PF && !(e->mfma && !e->mfma_pipelined) && (d.real_mask & 1)) return bad(k, "real_mask set without a streamed child");
-        if (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh) return bad(k, "second memory child without a real vector");
+        if (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh.p) return bad(k, "second memory child without a real vector");
         if (d.dst == d.pf || d.dst == d.ld) return bad(k, "op writes one of its own children");
         if (!(d.left_len >= 0.0) || !(d.right_len >= 0.0)) return bad(k, "negative or NaN branch length");
         if (d.out_row < 0 || d.out_row >= nops) return bad(k, "out_row outside the caller's op list");
@@ -533,7 +528,7 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         if (e->wide4) {   // k_traverse4w: both children in the memory form, a leaf's region holds its table as well
             if ((d.left_kind != CHILD_LEAF && d.left_kind != CHILD_LOAD) || (d.right_kind != CHILD_LEAF && d.right_kind != CHILD_LOAD))
                 return bad(k, "wide 4-state op is not in the (memory, memory) form");
-            if ((d.left_kind == CHILD_LOAD && d.pf == e->dummy.plh) || (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh))
+            if ((d.left_kind == CHILD_LOAD && d.pf == e->dummy.plh.p) || (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh.p))
                 return bad(k, "memory child without a real vector");
             const int szl = (d.left_kind == CHILD_LEAF ? 6 : 1) * e->block, szr = (d.right_kind == CHILD_LEAF ? 6 : 1) * e->block;
             if (d.lds_left + szl > e->plan.lds_doubles || d.lds_right + szr > e->plan.lds_doubles ||
@@ -544,10 +539,10 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
     }
     // chunks tile the plan; the segment table stays inside it
     for (int k = 0; k < nops;) {
-        if (e->h_ops[k].chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
-        k += e->h_ops[k].chunk_nops;
+        if (e->h_ops.p[k].chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
+        k += e->h_ops.p[k].chunk_nops;
     }
-    const int *tab = reinterpret_cast<const int *>(e->h_ops + e->plan.table_off);
+    const int *tab = reinterpret_cast<const int *>(e->h_ops.p + e->plan.table_off);
     int covered = 0;
     for (int u = 0; u <= e->plan.nunits; u++) {
         const int b = tab[2 * u], n = tab[2 * u + 1];
@@ -563,21 +558,21 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
 int upload_plan(iqhip_engine *e, size_t nbytes) {
     if (e->planner) return IQHIP_OK;   // (nothing to upload to)
     std::vector<char> &up = e->plan_cache.uploaded;
-    const char *h = reinterpret_cast<const char *>(e->h_ops);
+    const char *h = reinterpret_cast<const char *>(e->h_ops.p);
     if (e->plan.small) {
         // (rides in the kernel arguments, which the launch copies out of h_ops; `uploaded` is what d_ops would hold)
     } else if (up.size() == nbytes && memcmp(up.data(), h, nbytes) == 0) {
         return IQHIP_OK;
-    } else if (e->plan_arena_on && e->plan_arena_used + nbytes <= e->plan_arena_cap) {
+    } else if (e->plan_arena_on && e->plan_arena_used + nbytes <= e->h_plan_arena.cap) {
         // a sweep enqueues many plans before the device has run the first: each upload goes out of a slice of its own
         // of a pinned arena, so that re-using h_ops for the next plan never has to wait for the device (that wait -- the
         // staging event below -- made the host fall in step with the device eight times per 97-branch protein sweep)
-        char *slice = e->h_plan_arena + e->plan_arena_used;
+        char *slice = e->h_plan_arena.p + e->plan_arena_used;
         memcpy(slice, h, nbytes);
         e->plan_arena_used += (nbytes + 255) / 256 * 256;
-        HIPCHK(hipMemcpyAsync(e->d_ops, slice, nbytes, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_ops.p, slice, nbytes, hipMemcpyHostToDevice, e->stream));
     } else {
-        HIPCHK(hipMemcpyAsync(e->d_ops, e->h_ops, nbytes, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_ops.p, e->h_ops.p, nbytes, hipMemcpyHostToDevice, e->stream));
         HIPCHK(hipEventRecord(e->staging_free, e->stream));
         e->staging_busy = true;
     }
@@ -589,10 +584,10 @@ int upload_plan(iqhip_engine *e, size_t nbytes) {
 int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units &u, const std::vector<int> *explicit_segs,
                       const double *const *len_ptrs, int last_dst) {
     Plan &p = e->plan;
-    for (int q = 0; q < kSentinels; q++) dummy_op(e, e->h_ops[nops + q]);  // targets of the look-ahead requests
+    for (int q = 0; q < kSentinels; q++) dummy_op(e, e->h_ops.p[nops + q]);  // targets of the look-ahead requests
     p.table_off = nops + kSentinels;
     const int table_ops = segment_table_ops(u);
-    int *tab = reinterpret_cast<int *>(e->h_ops + p.table_off);
+    int *tab = reinterpret_cast<int *>(e->h_ops.p + p.table_off);
     memset(tab, 0, sizeof(DevOp) * (size_t)table_ops);
     tab[0] = u.top_begin; tab[1] = nops - u.top_begin;
     for (size_t i = 0; i < u.units.size(); i++) { tab[2 + 2 * i] = u.units[i].first; tab[3 + 2 * i] = u.units[i].second; }
@@ -602,8 +597,8 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
     p.jobs_off = p.table_off + table_ops;
     const int jobs_ops = devops_for(sizeof(TabJob) * p.tab_jobs.size());
     if (jobs_ops > 0) {
-        memset(e->h_ops + p.jobs_off, 0, sizeof(DevOp) * (size_t)jobs_ops);
-        memcpy(e->h_ops + p.jobs_off, p.tab_jobs.data(), sizeof(TabJob) * p.tab_jobs.size());
+        memset(e->h_ops.p + p.jobs_off, 0, sizeof(DevOp) * (size_t)jobs_ops);
+        memcpy(e->h_ops.p + p.jobs_off, p.tab_jobs.data(), sizeof(TabJob) * p.tab_jobs.size());
     }
     PlanCache &c = e->plan_cache;
     c.ops_in.assign((const char *)ops, (const char *)(ops + nops));
@@ -615,12 +610,12 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
     p.small_nops = nops;
     if (e->planner && nops > 0) {   // negative tests (IQHIP_DEBUG_BREAK_PLAN): break one descriptor the way round 2's fault did
         const std::string &br = e->debug_break_plan;
-        if (br == "tab") e->h_ops[nops - 1].tabL = nullptr;
-        else if (br == "sentinel") e->h_ops[nops + kSentinels - 1].pf = nullptr;
-        else if (br == "states") e->h_ops[0].sr = nullptr;
+        if (br == "tab") e->h_ops.p[nops - 1].tabL = nullptr;
+        else if (br == "sentinel") e->h_ops.p[nops + kSentinels - 1].pf = nullptr;
+        else if (br == "states") e->h_ops.p[0].sr = nullptr;
         else if (br == "cherry")
             for (int k = 0; k < nops; k++)
-                if (e->h_ops[k].cherry) { e->h_ops[k].cherry += 8; break; }   // (inside the buffer, not on a table)
+                if (e->h_ops.p[k].cherry) { e->h_ops.p[k].cherry += 8; break; }   // (inside the buffer, not on a table)
     }
     if (e->check_plans && !e->ablate) {
         const int rc = check_plan(e, nops, kSentinels);
@@ -639,15 +634,15 @@ int resolve_child(iqhip_engine *e, uint64_t key, int32_t leaf, int prev_dst, con
     *plh = nullptr; *sc = nullptr; *states = nullptr;
     if (leaf >= 0) {
         if (leaf >= e->ntaxa) return fail(IQHIP_ERR_INVALID, "leaf id out of range");
-        *states = e->d_states + (size_t)leaf * e->nptn_pad;
+        *states = e->d_states.p + (size_t)leaf * e->nptn_pad;
         *kind = CHILD_LEAF;
         return IQHIP_OK;
     }
     int idx;
     int rc = slab_for_key(e, key, false, &idx);
     if (rc) return rc;
-    *plh = e->slabs[idx].plh;
-    *sc = e->slabs[idx].sc;
+    *plh = e->slabs[idx].plh.p;
+    *sc = e->slabs[idx].sc.p;
     *kind = (idx == prev_dst) ? CHILD_PREV : CHILD_LOAD;
     return IQHIP_OK;
 }
@@ -671,7 +666,7 @@ bool leaf_tables_follow_model(iqhip_engine *e) {
     std::fill(e->tab_len.begin(), e->tab_len.end(), NAN);
     const size_t per = leaf_table_doubles(e);
     for (const TabJob &j : e->plan.tab_jobs) {
-        const size_t slot = (size_t)(j.tab - e->d_leaf_tab) / per;
+        const size_t slot = (size_t)(j.tab - e->d_leaf_tab.p) / per;
         if (slot < (size_t)e->ntaxa) e->tab_len[slot] = j.len;
     }
     e->tab_model_version = e->model_version;

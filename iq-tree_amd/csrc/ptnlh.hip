@@ -20,7 +20,7 @@ int iqhip::branch_scale_counters(iqhip_engine *e, iqhip_branch_end a, iqhip_bran
         int idx;
         const int rc = slab_for_key(e, ends[k].key, false, &idx);
         if (rc) return rc;
-        sc[k] = e->slabs[idx].sc;
+        sc[k] = e->slabs[idx].sc.p;
     }
     return IQHIP_OK;
 }
@@ -29,8 +29,8 @@ static int scaled_pattern_lh(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_e
     const int16_t *sc[2];
     const int rc = branch_scale_counters(e, a, b, sc);
     if (rc) return rc;
-    if (!e->d_ptn_scaled) HIPCHK(hipMalloc((void **)&e->d_ptn_scaled, sizeof(double) * (size_t)e->nptn_pad));
-    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptn_scaled));
+    HIPCHK(e->d_ptn_scaled.ensure(e, (size_t)e->nptn_pad));
+    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptn_scaled.p));
     return IQHIP_OK;
 }
 
@@ -40,7 +40,7 @@ extern "C" int iqhip_fetch_pattern_lh_scaled(iqhip_engine *e, iqhip_branch_end a
     HIPCHK(use_device(e));
     int rc = scaled_pattern_lh(e, a, b);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, e->d_ptn_scaled, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->d_ptn_scaled.p, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
 }
@@ -52,26 +52,23 @@ extern "C" int iqhip_pattern_lh_cat(iqhip_engine *e, double len, double *out) {
     if (!(len >= 0.0)) return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
     HIPCHK(use_device(e));
     const size_t count = (size_t)e->nptn * e->ncat;
-    double *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, sizeof(double) * count));
-    hipError_t s = launch_pattern_lh_cat(e, len, d_out);
-    if (s == hipSuccess) s = hipMemcpyAsync(out, d_out, sizeof(double) * count, hipMemcpyDeviceToHost, e->stream);
-    if (s == hipSuccess) s = hipStreamSynchronize(e->stream);
-    hipFree(d_out);
-    if (s != hipSuccess) return fail(IQHIP_ERR_HIP, hipGetErrorString(s));
+    DevBuf<double> d_out;   // (lives for this call, which ends with the stream drained)
+    HIPCHK(d_out.ensure(e, count));
+    HIPCHK(launch_pattern_lh_cat(e, len, d_out.p));
+    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(double) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
 }
 
 // replaces the sample matrix by one of nsamples rows (0: none) once the engine's stream has drained; contents undefined
 static hipError_t boot_matrix(iqhip_engine *e, int nsamples) {
     hipError_t s = hipStreamSynchronize(e->stream);
-    if (s == hipSuccess && e->d_boot) s = hipFree(e->d_boot);
     if (s != hipSuccess) return s;
-    e->d_boot = nullptr;
+    e->d_boot.reset();
     e->nboot = 0;
     e->ufb.nsamples = 0;   // (the UFBoot state belongs to the matrix it was initialised on)
     if (nsamples == 0) return hipSuccess;
-    if ((s = dmalloc(&e->d_boot, (size_t)e->nptn_pad * nsamples)) == hipSuccess) e->nboot = nsamples;
+    if ((s = e->d_boot.ensure(e, (size_t)e->nptn_pad * nsamples)) == hipSuccess) e->nboot = nsamples;
     return s;
 }
 
@@ -83,8 +80,8 @@ extern "C" int iqhip_set_boot_samples(iqhip_engine *e, const float *samples, int
     HIPCHK(boot_matrix(e, nsamples));
     if (nsamples == 0) return IQHIP_OK;
     const size_t pitch = (size_t)e->nptn_pad;
-    HIPCHK(hipMemset(e->d_boot, 0, sizeof(float) * pitch * nsamples));
-    HIPCHK(hipMemcpy2D(e->d_boot, pitch * sizeof(float), samples, (size_t)e->nptn * sizeof(float),
+    HIPCHK(hipMemset(e->d_boot.p, 0, sizeof(float) * pitch * nsamples));
+    HIPCHK(hipMemcpy2D(e->d_boot.p, pitch * sizeof(float), samples, (size_t)e->nptn * sizeof(float),
                        (size_t)e->nptn * sizeof(float), nsamples, hipMemcpyHostToDevice));
     return IQHIP_OK;
 }
@@ -111,7 +108,7 @@ extern "C" int iqhip_rell(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end 
     if (rc) return rc;
     rc = read_result(e, e->nboot);
     if (rc) return rc;
-    memcpy(rell, e->h_result, sizeof(double) * (size_t)e->nboot);
+    memcpy(rell, e->h_result.p, sizeof(double) * (size_t)e->nboot);
     return IQHIP_OK;
 }
 
@@ -132,18 +129,16 @@ extern "C" int iqhip_ptnlh_reserve(iqhip_engine *e, int nrows) {
     if (nrows < 0 || nrows > (1 << 20)) return fail(IQHIP_ERR_INVALID, "iqhip_ptnlh_reserve: bad row count");
     HIPCHK(use_device(e));
     if (nrows <= e->ptnlh_rows) return IQHIP_OK;   // (rows keep their contents while the store does not grow)
-    double *grown = nullptr;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (hipMalloc((void **)&grown, sizeof(double) * (size_t)nrows * e->nptn_pad) != hipSuccess)
+    DevBuf<double> grown;   // (the old store stays as it is until the new one is complete; whichever is left over frees itself)
+    if (grown.ensure(e, (size_t)nrows * e->nptn_pad) != hipSuccess)
         return fail(IQHIP_ERR_NOMEM, "iqhip_ptnlh_reserve: out of device memory");
     // (on the engine's stream: a memset on the null stream is not ordered against the kernels that fill rows next)
-    HIPCHK(hipMemsetAsync(grown, 0, sizeof(double) * (size_t)nrows * e->nptn_pad, e->stream));
-    if (e->d_ptnlh)
-        HIPCHK(hipMemcpyAsync(grown, e->d_ptnlh, sizeof(double) * (size_t)e->ptnlh_rows * e->nptn_pad, hipMemcpyDeviceToDevice,
+    HIPCHK(hipMemsetAsync(grown.p, 0, sizeof(double) * (size_t)nrows * e->nptn_pad, e->stream));
+    if (e->d_ptnlh.p)
+        HIPCHK(hipMemcpyAsync(grown.p, e->d_ptnlh.p, sizeof(double) * (size_t)e->ptnlh_rows * e->nptn_pad, hipMemcpyDeviceToDevice,
                               e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->d_ptnlh) HIPCHK(hipFree(e->d_ptnlh));
-    e->d_ptnlh = grown;
+    e->d_ptnlh.swap(grown);
     e->ptnlh_rows = nrows;
     return IQHIP_OK;
 }
@@ -157,7 +152,7 @@ extern "C" int iqhip_ptnlh_put_current(iqhip_engine *e, int row, iqhip_branch_en
     const int16_t *sc[2];
     rc = branch_scale_counters(e, a, b, sc);
     if (rc) return rc;
-    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptnlh + (size_t)row * e->nptn_pad));
+    HIPCHK(launch_pattern_lh_scaled(e, sc[0], sc[1], e->d_ptnlh.p + (size_t)row * e->nptn_pad));
     return IQHIP_OK;
 }
 
@@ -168,7 +163,7 @@ extern "C" int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out) {
     rc = ptnlh_check_rows(e, "iqhip_ptnlh_fetch", &row, 1);
     if (rc) return rc;
     HIPCHK(use_device(e));
-    HIPCHK(hipMemcpyAsync(out, e->d_ptnlh + (size_t)row * e->nptn_pad, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(out, e->d_ptnlh.p + (size_t)row * e->nptn_pad, sizeof(double) * (size_t)e->nptn, hipMemcpyDeviceToHost,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
@@ -269,7 +264,7 @@ extern "C" int iqhip_ptnlh_upload(iqhip_engine *e, int row, const double *in) {
     std::vector<double> tmp((size_t)e->nptn_pad, 0.0);
     memcpy(tmp.data(), in, sizeof(double) * (size_t)e->nptn);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_ptnlh + (size_t)row * e->nptn_pad, tmp.data(), sizeof(double) * tmp.size(), hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(e->d_ptnlh.p + (size_t)row * e->nptn_pad, tmp.data(), sizeof(double) * tmp.size(), hipMemcpyHostToDevice,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return IQHIP_OK;
@@ -281,7 +276,7 @@ static int topo_freq_prefix(iqhip_engine *e, const char *what) {
     if (!e->aln_set) return fail(IQHIP_ERR_INVALID, std::string(what) + ": needs iqhip_set_alignment first");
     std::vector<double> freq((size_t)e->nptn);
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(freq.data(), e->d_freq, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(freq.data(), e->d_freq.p, sizeof(double) * freq.size(), hipMemcpyDeviceToHost));
     std::vector<int64_t> prefix(freq.size());
     int64_t total = 0;
     for (size_t p = 0; p < freq.size(); p++) {
@@ -292,8 +287,8 @@ static int topo_freq_prefix(iqhip_engine *e, const char *what) {
         prefix[p] = total;
     }
     if (total < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": the alignment has no site");
-    if (!e->d_freq_prefix) HIPCHK(dmalloc(&e->d_freq_prefix, prefix.size()));
-    HIPCHK(hipMemcpy(e->d_freq_prefix, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice));
+    HIPCHK(e->d_freq_prefix.ensure(e, prefix.size()));
+    HIPCHK(hipMemcpy(e->d_freq_prefix.p, prefix.data(), sizeof(int64_t) * prefix.size(), hipMemcpyHostToDevice));
     e->freq_nsite = total;
     e->freq_prefix_valid = true;
     return IQHIP_OK;
@@ -301,7 +296,7 @@ static int topo_freq_prefix(iqhip_engine *e, const char *what) {
 
 // a sample matrix of exactly (exact) or at least nsamples rows, contents undefined
 static int topo_boot_rows(iqhip_engine *e, int nsamples, bool exact) {
-    if (e->d_boot && (exact ? e->nboot == nsamples : e->nboot >= nsamples)) return IQHIP_OK;
+    if (e->d_boot.p && (exact ? e->nboot == nsamples : e->nboot >= nsamples)) return IQHIP_OK;
     const hipError_t s = boot_matrix(e, nsamples);
     if (s == hipErrorOutOfMemory) return fail(IQHIP_ERR_NOMEM, "bootstrap sample matrix: out of device memory");
     HIPCHK(s);

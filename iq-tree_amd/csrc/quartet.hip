@@ -118,8 +118,8 @@ extern "C" int iqhip_quartet_likelihoods(iqhip_engine *e, const int32_t *quartet
     a.cells = e->qt.cells.p;
     a.nother = e->qt.nother.p;
     a.other = e->qt.other.p;
-    a.states = e->d_states;
-    a.freq = e->d_freq;
+    a.states = e->d_states.p;
+    a.freq = e->d_freq.p;
     a.evec = e->d_evec;
     a.inv_evec = e->d_inv_evec;
     a.eval = e->d_eval;

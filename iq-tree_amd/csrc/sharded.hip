@@ -45,13 +45,13 @@ int reduce_results(iqhip_engine *p, int n, std::vector<double> &out) {
         if (rc) return rc;
         rc = read_result(p->shards[0], n);
         if (rc) return rc;
-        memcpy(out.data(), p->shards[0]->h_result, sizeof(double) * (size_t)n);
+        memcpy(out.data(), p->shards[0]->h_result.p, sizeof(double) * (size_t)n);
         return IQHIP_OK;
     }
     for (iqhip_engine *c : p->shards) {
         int rc = read_result(c, n);
         if (rc) return rc;
-        for (int i = 0; i < n; i++) out[i] += c->h_result[i];
+        for (int i = 0; i < n; i++) out[i] += c->h_result.p[i];
     }
     return IQHIP_OK;
 }
@@ -342,11 +342,11 @@ int optimize_branch(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool bu
             },
             [&](bool *done) {
                 const int rc = newton_state_read(p->shards[0]);
-                *done = !rc && p->shards[0]->h_nstate->done;
+                *done = !rc && p->shards[0]->h_nstate.p->done;
                 return rc;
             });
         if (rc) return rc;
-        st = *p->shards[0]->h_nstate;
+        st = *p->shards[0]->h_nstate.p;
     } else {
         // pinned-host reduction: the host adds the shards' {df, ddf} and advances the same state machine itself
         newton_init(st, xguess, x1, x2, xacc, max_steps);

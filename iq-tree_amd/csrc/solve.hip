@@ -35,9 +35,7 @@ int iqhip::newton_status(int status, bool *gave_up) {
 // (drive_chain); the host reads the 128-byte state once per chunk; steps enqueued after convergence do nothing.
 // ---------------------------------------------------------------------------------------
 int iqhip::newton_state_alloc(iqhip_engine *e) {
-    if (e->d_nstate) return IQHIP_OK;
-    if (hipMalloc((void **)&e->d_nstate, sizeof(NewtonState)) != hipSuccess ||
-        hipHostMalloc((void **)&e->h_nstate, sizeof(NewtonState)) != hipSuccess)
+    if (e->d_nstate.ensure(e, 1) != hipSuccess || e->h_nstate.ensure(e, 1) != hipSuccess)
         return fail(IQHIP_ERR_NOMEM, "Newton state");
     return IQHIP_OK;
 }
@@ -79,7 +77,7 @@ int iqhip::eng_newton_update_enqueue(iqhip_engine *e) {
 
 int iqhip::newton_state_read(iqhip_engine *e) {
     if (use_device(e) != hipSuccess) return fail(IQHIP_ERR_HIP, "hipSetDevice");
-    if (hipMemcpyAsync(e->h_nstate, e->d_nstate, sizeof(NewtonState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+    if (hipMemcpyAsync(e->h_nstate.p, e->d_nstate.p, sizeof(NewtonState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
         hipStreamSynchronize(e->stream) != hipSuccess)
         return fail(IQHIP_ERR_HIP, "Newton chain: state read failed");
     e->staging_busy = false;
@@ -141,11 +139,11 @@ static int newton_chain(iqhip_engine *e, double xguess, double x1, double x2, do
         },
         [&](bool *done) {
             const int rc = newton_state_read(e);
-            *done = !rc && e->h_nstate->done;
+            *done = !rc && e->h_nstate.p->done;
             return rc;
         });
     if (rc) return rc;
-    const NewtonState &st = *e->h_nstate;
+    const NewtonState &st = *e->h_nstate.p;
     rc = newton_status(st.status);
     if (rc) return rc;
     NewtonResult(st).store(optx, d2l, nsteps);
@@ -193,7 +191,7 @@ extern "C" int iqhip_newton_branch(iqhip_engine *e, double xguess, double x1, do
     e->path_counts[IQHIP_PATH_NEWTON_ONE_LAUNCH]++;
     rc = read_result(e, 4);
     if (rc) return rc;
-    return newton_one_launch_result(e, e->h_result, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
+    return newton_one_launch_result(e, e->h_result.p, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
 }
 
 extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, int nops, iqhip_branch_end a,
@@ -232,9 +230,9 @@ extern "C" int iqhip_optimize_branch(iqhip_engine *e, const iqhip_node_op *ops, 
     rc = read_result(e, 2 + nops + 4);
     if (rc) return rc;
     if (sum_scale)
-        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result[2 + k];
+        for (int k = 0; k < nops; k++) sum_scale[k] = e->h_result.p[2 + k];
     // (a barrier that gave up: theta was built by the first evaluation)
-    return newton_one_launch_result(e, e->h_result + 2 + nops, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
+    return newton_one_launch_result(e, e->h_result.p + 2 + nops, xguess, x1, x2, xacc, max_steps, optx, d2l, nsteps);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -294,7 +292,7 @@ static int sweep_results(iqhip_engine *e, const iqhip_sweep_step *steps, int nst
                          int max_steps, double diverge_frac, double *sum_scale, iqhip_branch_result *results, RowOf &&row_of) {
     size_t ss = 0;
     for (int j = 0; j < nsteps; j++) {
-        const double *o = e->h_result + row_of(j);
+        const double *o = e->h_result.p + row_of(j);
         const NewtonResult r(o);
         bool gave_up;
         const int rc = newton_status(r.status, &gave_up);
@@ -320,16 +318,12 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     if (dbg) watch.start();
     const size_t bytes_ops = sizeof(SweepOp) * total_ops, bytes_steps = sizeof(SweepStep) * (size_t)nsteps;
     const size_t need = bytes_ops + bytes_steps;
-    if (need > e->sweep_desc_cap) {
-        const size_t cap = need * 2 + 4096;
-        HIPCHK(regrow(e, &e->d_sweep_desc, &e->sweep_desc_cap, 0, cap));   // (plain regrow: the capacity counts bytes, set once the host copy has grown too)
-        if (e->h_sweep_desc) hipHostFree(e->h_sweep_desc);
-        e->h_sweep_desc = nullptr;
-        HIPCHK(hipHostMalloc((void **)&e->h_sweep_desc, cap));
-        e->sweep_desc_cap = cap;
+    if (need > std::min(e->d_sweep_desc.cap, e->h_sweep_desc.cap)) {
+        HIPCHK(e->d_sweep_desc.ensure(e, need * 2 + 4096));
+        HIPCHK(e->h_sweep_desc.ensure(e, need * 2 + 4096));
     }
-    SweepOp *hops = reinterpret_cast<SweepOp *>(e->h_sweep_desc);
-    SweepStep *hsteps = reinterpret_cast<SweepStep *>(e->h_sweep_desc + bytes_ops);
+    SweepOp *hops = reinterpret_cast<SweepOp *>(e->h_sweep_desc.p);
+    SweepStep *hsteps = reinterpret_cast<SweepStep *>(e->h_sweep_desc.p + bytes_ops);
     size_t row = 0;
     for (int j = 0; j < nsteps; j++) {
         const iqhip_sweep_step &st = steps[j];
@@ -348,13 +342,13 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
             if (rc) return rc;
             rc = resolve_child(e, o.right_key, o.right_leaf, -1, &d.rv, &d.rsc, &rst, &rk);
             if (rc) return rc;
-            d.ls = lst ? lst : e->d_states;
-            d.rs = rst ? rst : e->d_states;
+            d.ls = lst ? lst : e->d_states.p;
+            d.rs = rst ? rst : e->d_states.p;
             int didx;
             rc = slab_for_key(e, o.dst_key, true, &didx);
             if (rc) return rc;
-            d.dst = e->slabs[didx].plh;
-            d.dst_sc = e->slabs[didx].sc;
+            d.dst = e->slabs[didx].plh.p;
+            d.dst_sc = e->slabs[didx].sc.p;
             if (d.lv == d.dst || d.rv == d.dst) return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
             d.llen = o.left_len;
             d.rlen = o.right_len;
@@ -371,13 +365,13 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
     if (total_ops * (size_t)nwaves > e->d_slab.cap) HIPCHK(e->d_slab.ensure(e, slab_need));
     const size_t posts_need = (size_t)2 * kNewtonPostEpochs * grid * 2;
     HIPCHK(e->d_sweep_posts.ensure(e, posts_need));
-    HIPCHK(hipMemcpyAsync(e->d_sweep_desc, e->h_sweep_desc, need, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_sweep_desc.p, e->h_sweep_desc.p, need, hipMemcpyHostToDevice, e->stream));
     if (grid > 1) HIPCHK(hipMemsetAsync(e->d_sweep_posts.p, 0xFF, posts_need * sizeof(double), e->stream));
     double *out = e->d_result + total_ops;      // (rows [0, total_ops) receive the sum_scale sums from k_reduce)
-    memset(e->h_result + total_ops, 0, sizeof(double) * 6 * (size_t)nsteps);
+    memset(e->h_result.p + total_ops, 0, sizeof(double) * 6 * (size_t)nsteps);
     e->path_counts[IQHIP_PATH_SWEEP_PERSISTENT]++;
-    HIPCHK(launch_sweep4(e, reinterpret_cast<const SweepOp *>(e->d_sweep_desc),
-                         reinterpret_cast<const SweepStep *>(e->d_sweep_desc + bytes_ops), nsteps, x1, x2, xacc, max_steps,
+    HIPCHK(launch_sweep4(e, reinterpret_cast<const SweepOp *>(e->d_sweep_desc.p),
+                         reinterpret_cast<const SweepStep *>(e->d_sweep_desc.p + bytes_ops), nsteps, x1, x2, xacc, max_steps,
                          diverge_frac * x2, e->d_sweep_posts.p, out));
     HIPCHK(launch_reduce(e, 0, (int)total_ops, nwaves));
     set_theta_branch(e, hsteps[nsteps - 1].br, steps[nsteps - 1].a, steps[nsteps - 1].b);
@@ -389,7 +383,7 @@ static int sweep_persistent4(iqhip_engine *e, const iqhip_sweep_step *steps, int
         fprintf(stderr, "[iqhip] persistent sweep of %d steps (%zu node updates): descriptors + enqueue %.1f us, wait %.1f us\n", nsteps,
                 total_ops, enqueue_us, watch.us() - enqueue_us);
     if (sum_scale)
-        for (size_t k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[k];
+        for (size_t k = 0; k < total_ops; k++) sum_scale[k] = e->h_result.p[k];
     return sweep_results(e, steps, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results,
                          [&](int j) { return total_ops + 6 * (size_t)j; });
 }
@@ -419,13 +413,10 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
     // (+ASC: k_sweep4 has no correction; k_newton applies it to the derivatives and to both lnL of the diverged-solve rule)
     if (e->sweep_persistent && !e->asc_active && !e->mfma && e->nclass == 1 && nsteps <= 4096 && max_steps + 5 <= kNewtonPostEpochs && total_ops > 0)
         return sweep_persistent4(e, steps, nsteps, total_ops, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results);
-    if (!e->h_plan_arena) {
-        e->plan_arena_cap = 1 << 20;
-        if (hipHostMalloc((void **)&e->h_plan_arena, e->plan_arena_cap) != hipSuccess) { e->h_plan_arena = nullptr; e->plan_arena_cap = 0; }
-    }
+    (void)e->h_plan_arena.ensure(e, (size_t)1 << 20);   // (without it the plans of this sweep upload the ordinary way)
     struct ArenaScope {   // plan uploads of this sweep go through the arena; whatever happens, switched off on return
         iqhip_engine *e;
-        explicit ArenaScope(iqhip_engine *e_) : e(e_) { e->plan_arena_on = e->h_plan_arena != nullptr; e->plan_arena_used = 0; }
+        explicit ArenaScope(iqhip_engine *e_) : e(e_) { e->plan_arena_on = e->h_plan_arena.p != nullptr; e->plan_arena_used = 0; }
         ~ArenaScope() { e->plan_arena_on = false; }
     } arena_scope(e);
     e->path_counts[IQHIP_PATH_SWEEP_PER_STEP]++;
@@ -484,7 +475,7 @@ extern "C" int iqhip_optimize_sweep(iqhip_engine *e, const iqhip_sweep_step *ste
     if (sum_scale) {
         size_t ss = 0;
         for (int j = 0; j < nsteps; j++)
-            for (int k = 0; k < steps[j].nops; k++) sum_scale[ss++] = e->h_result[row_of[j] + k];
+            for (int k = 0; k < steps[j].nops; k++) sum_scale[ss++] = e->h_result.p[row_of[j] + k];
     }
     return sweep_results(e, steps, nsteps, x1, x2, xacc, max_steps, diverge_frac, sum_scale, results,
                          [&](int j) { return row_of[j] + (size_t)steps[j].nops; });
@@ -634,7 +625,7 @@ static int optimize_branch_batch_comm(iqhip_engine *e, const iqhip_branch_task *
         rc = read_result(e, 2 + total_ops);
         if (rc) return rc;
         if (sum_scale)
-            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[2 + k];
+            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result.p[2 + k];
     }
     const int chunk = batch_chunk(std::min(ntasks, kBatchChainChunk));
     std::vector<NewtonState> st((size_t)chunk);
@@ -669,7 +660,7 @@ static int optimize_branch_batch_comm(iqhip_engine *e, const iqhip_branch_task *
         if (!rc) rc = comm_allreduce(e, 2 * m);
         if (!rc) rc = read_result(e, 2 * m);
         if (rc) return rc;
-        const std::vector<double> lnl(e->h_result, e->h_result + 2 * (size_t)m);   // {lnl, prob_const} per task
+        const std::vector<double> lnl(e->h_result.p, e->h_result.p + 2 * (size_t)m);   // {lnl, prob_const} per task
         for (int t = 0; t < m; t++) {
             results[first + t].lnl = lnl[2 * t];
             if (isnan(lnl[2 * t]) || isinf(lnl[2 * t])) {   // phylokernel.h:1091-1109: redo this task alone (same decision on every rank)
@@ -854,7 +845,7 @@ extern "C" int iqhip_optimize_branch_batch_rows(iqhip_engine *e, const iqhip_bra
         rc = read_result(e, 2 + total_ops);
         if (rc) return rc;
         if (sum_scale)
-            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result[2 + k];
+            for (int k = 0; k < total_ops; k++) sum_scale[k] = e->h_result.p[2 + k];
     }
     return IQHIP_OK;
 }

@@ -1,4 +1,5 @@
-"""Create / use / destroy engines repeatedly and watch the device's free memory (hipMemGetInfo)."""
+"""Create / use / destroy engines repeatedly and watch the device's free memory (hipMemGetInfo) and the library's own
+count of live bytes (iqhip_debug_memory), which must be back at its starting value after every round."""
 import ctypes as C, importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +17,7 @@ _rng = np.random.default_rng(5)
 _A = _rng.uniform(0.05, 1.0, (300, 300))
 bionj_dist = (_A + _A.T) / 2   # iqhip_bionj allocates three n x n matrices per call and frees them before it returns
 base = None
+mem0 = pkg.debug_memory()
 for rep in range(6):
     for n, st_type, model, P in cases:
         nwk = synth.random_tree_newick(20, 1)
@@ -40,6 +42,9 @@ for rep in range(6):
         t.close()
     f = free_mb()
     if base is None: base = f
-    print("round %d free %.1f MB (delta vs first %.1f MB)" % (rep, f, f - base))
+    mem = pkg.debug_memory()
+    print("round %d free %.1f MB (delta vs first %.1f MB); live through the owners: device %d B, host %d B" %
+          (rep, f, f - base, mem[0] - mem0[0], mem[1] - mem0[1]))
+    assert mem == mem0, "an allocation outlived its engine"
 assert abs(f - base) < 64, "device memory is leaking"
 print("OK")
