@@ -1046,13 +1046,8 @@ extern "C" int iqhip_derv(iqhip_engine *e, double len, double *df, double *ddf) 
     rc = read_result(e, e->asc_active ? 5 : 2);
     if (rc) return rc;
     double a = e->h_result.p[0], b = e->h_result.p[1];
-    if (isnan(a) || isinf(a)) { a = 0.0; b = 0.0; }  // phylokernel.h:647-651
-    if (e->asc_active) {  // phylokernel.h:719-724
-        const double prob_const = 1.0 - e->h_result.p[2];
-        const double df_frac = e->h_result.p[3] / prob_const, ddf_frac = e->h_result.p[4] / prob_const;
-        a += e->asc_nsites * df_frac;
-        b += e->asc_nsites * (ddf_frac + df_frac * df_frac);
-    }
+    newton_repair(a, b);                                                            // phylokernel.h:647-651
+    if (e->asc_active) asc_derv_correct(e->h_result.p + 2, e->asc_nsites, a, b);   // phylokernel.h:719-724
     if (df) *df = a;
     if (ddf) *ddf = b;
     return IQHIP_OK;

@@ -236,9 +236,13 @@ struct PlanCache {
 
 // Optimization::minimizeNewton (optimization.cpp:388-465) as a state machine that is advanced once per derivative
 // evaluation: `newton_init`, then after every evaluation at `rts` one `newton_update(sum f*df_ptn, sum f*ddf_ptn)`
-// until `done`.  The same function runs in a 1-thread kernel (sharded engines: derivative kernel -> all-reduce of
-// {df, ddf} -> update kernel, all enqueued, no host round trip per step), on the host (single-process sharding with
-// the pinned-host reduction) and in the CPU tests; k_newton / k_newton_batch keep the loop form.
+// until `done`.  It is the one statement of the rule: the in-kernel solvers (k_newton, k_newton_batch, k_sweep4, the
+// pair, quartet and partition solvers) run it in every workgroup, sharded engines in a 1-thread kernel (derivative
+// kernel -> all-reduce of {df, ddf} -> update kernel, all enqueued, no host round trip per step), single-process
+// sharding on the host (pinned-host reduction), and the CPU tests compare it with the reference's loop.
+// newton_update = newton_repair + newton_advance.  A caller with a +ASC correction to add puts it between the two
+// (k_newton, k_newton_batch: a non-finite corrected sum then ends the solve with status 2, as in the reference); the
+// chain forms add the correction first and call newton_update, which repairs such a sum once more.
 struct __attribute__((aligned(16))) NewtonState {
     double x1, x2, xacc;
     double rts, rts_old, xl, xh, dx, f, df, d2l, result;
@@ -260,10 +264,22 @@ __host__ __device__ inline void newton_init(NewtonState &s, double xguess, doubl
 
 __host__ __device__ inline bool newton_finite(double v) { return v == v && v - v == 0.0; }
 
-__host__ __device__ inline void newton_update(NewtonState &s, double pdf, double pddf) {
+// computeLikelihoodDerv's repair of a non-finite derivative sum, phylokernel.h:647-651
+__host__ __device__ inline void newton_repair(double &pdf, double &pddf) {
+    if (!newton_finite(pdf)) { pdf = 0.0; pddf = 0.0; }
+}
+
+// +ASC, phylokernel.h:719-724: c = {prob_const_sum, df_const, ddf_const} over the unobserved constant patterns
+__host__ __device__ inline void asc_derv_correct(const double *c, double asc_nsites, double &df, double &ddf) {
+    const double prob_const = 1.0 - c[0];
+    const double df_frac = c[1] / prob_const, ddf_frac = c[2] / prob_const;
+    df += asc_nsites * df_frac;
+    ddf += asc_nsites * (ddf_frac + df_frac * df_frac);
+}
+
+// one step of the rule from f = -dlnL/dt, df = -d2lnL/dt2 at s.rts (computeFuncDerv, phylotree.cpp:2135-2146)
+__host__ __device__ inline void newton_advance(NewtonState &s, double f, double df) {
     if (s.done) return;
-    if (!newton_finite(pdf)) { pdf = 0.0; pddf = 0.0; }  // computeLikelihoodDerv, phylokernel.h:647-651
-    const double f = -pdf, df = -pddf;                     // computeFuncDerv, phylotree.cpp:2135-2146
     s.f = f; s.df = df;
     s.neval++;
     if (s.neval == 1) {
@@ -294,6 +310,12 @@ __host__ __device__ inline void newton_update(NewtonState &s, double pdf, double
         if (temp == s.rts) { s.result = s.rts; s.done = 1; return; }
     }
     if (fabs(s.dx) < s.xacc || s.j == s.max_steps) { s.result = s.rts_old; s.done = 1; return; }
+}
+
+__host__ __device__ inline void newton_update(NewtonState &s, double pdf, double pddf) {
+    if (s.done) return;
+    newton_repair(pdf, pddf);
+    newton_advance(s, -pdf, -pddf);
 }
 
 // The one place device and pinned-host memory is allocated and freed.  It keeps two process-wide byte counts, device memory

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "iqhip_internal.h"
+#include "wg_exchange.h"
 
 namespace iqhip {
 
@@ -73,7 +74,7 @@ struct NewtonArgs {
     unsigned long long seq;
     unsigned int *barrier;   // arrival counter of this launch (zero at its start), counts up over the epochs
     unsigned int *barrier_next;  // the next launch's counter
-    double *out;             // {optx, d2l, nsteps, status}
+    double *out;             // {optx, d2l, evaluations, status}
     // fused front end (iqhip_optimize_branch): the first evaluation builds theta = a .* b (phylokernel.h:535-573)
     // while it accumulates, and the sum_scale rows of the preceding node updates are reduced here
     int build;               // 1: theta is written by the first evaluation from `br`
@@ -97,8 +98,6 @@ struct NewtonArgs {
     // a result above this length is kept only if the branch lnL there is not below the lnL at the starting length
     double diverge_x;
 };
-
-__device__ __forceinline__ double wsum(double v) { return wave_sum64(v); }
 
 // sum over this workgroup's patterns of f*df_ptn and f*ddf_ptn at the val arrays in LDS
 // MODE 0: derivative sums (f*df_ptn, f*ddf_ptn); MODE 1: lnL sum (f*log|lh_ptn|) in odf.  The workgroup is
@@ -285,8 +284,8 @@ __device__ __forceinline__ void wg_partial(const NewtonArgs &A, const double *th
             }
         }
     }
-    adf = wsum(adf);
-    addf = wsum(addf);
+    adf = wave_sum64(adf);
+    addf = wave_sum64(addf);
     if (lane == 0) { s_red[2 * wave] = adf; s_red[2 * wave + 1] = addf; }
     __syncthreads();
     odf = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
@@ -372,9 +371,9 @@ __device__ __forceinline__ void asc_unobserved_sums(const NewtonArgs &A, const d
                     if (br.b_sc) ssc += br.b_sc[ptn];
                     pc = (ssc >= 1 ? lh * kScalingThreshold : lh) + A.invar[ptn];
                 }
-                u0 += wsum(pc);
+                u0 += wave_sum64(pc);
             } else {
-                const double w0 = wsum(unobs ? lh + A.invar[ptn] : 0.0), w1 = wsum(unobs ? d1 : 0.0), w2 = wsum(unobs ? d2 : 0.0);
+                const double w0 = wave_sum64(unobs ? lh + A.invar[ptn] : 0.0), w1 = wave_sum64(unobs ? d1 : 0.0), w2 = wave_sum64(unobs ? d2 : 0.0);
                 u0 += w0; u1 += w1; u2 += w2;
             }
         }
@@ -383,10 +382,93 @@ __device__ __forceinline__ void asc_unobserved_sums(const NewtonArgs &A, const d
     __syncthreads();
 }
 
+// the three per-evaluation factor arrays at branch length x: exp(cof x) * prop, cof v, cof^2 v (phylokernel.h:600-617)
+__device__ __forceinline__ void fill_factors(const NewtonArgs &A, double x, double *s_v0, double *s_v1, double *s_v2) {
+    const int B = A.n * A.ncat;
+    for (int t = threadIdx.x; t < B; t += 256) {
+        const int c = t / A.n;
+        const double cof = A.eval[t] * A.rates[c];  // eval: per-category expansion [ncat][n]
+        const double v = exp(cof * x) * A.props[c];
+        s_v0[t] = v;
+        s_v1[t] = cof * v;
+        s_v2[t] = cof * (cof * v);
+    }
+    __syncthreads();
+}
+
+// One solve as a workgroup of k_newton / k_newton_batch sees it: the group of workgroups that share the solve's patterns,
+// where that group exchanges its partial sums, and the workgroup's LDS.
+struct SolveGroup {
+    const double *theta;
+    int wg, G;                   // this workgroup's number in the group, workgroups in the group
+    unsigned long long *posts;   // posted exchange: the group's slots [evaluation][G][2]; nullptr: the counter form
+    double *partials;            // counter form: the group's slots [2 parities][G][2] ...
+    unsigned int *counter;       // ... and its arrival counter (zero at the launch's start)
+    ThetaRegs regs;              // theta in registers; regs.use = false: read from memory in every evaluation (the batch).
+                                 // (by value, not an optional pointer: wg_partial's null test on a pointer into this
+                                 // frame does not fold, and v[] then lives in scratch)
+    bool build_first;            // the first evaluation builds theta = a .* b from the branch ends (phylokernel.h:535-573)
+    bool asc_from_ends;          // +ASC: the unobserved patterns' theta comes from the branch ends in EVERY evaluation
+                                 // (it does so in any case while theta is being built)
+    double *s_v0, *s_v1, *s_v2, *s_red /* [8] */, *s_bcast /* [2] */, *s_asc /* [3] */;
+    int *s_fail;
+    unsigned int epoch;          // evaluations exchanged so far
+};
+
+// The group's sums at branch length x, left in every thread of every workgroup of the group.  `first`: this is the solve's
+// first evaluation (a literal at every call: the first evaluation loads or builds theta, the later ones find it in
+// ThetaRegs, and each call site is compiled for its own case).
+// MODE 0: r0 = sum f*df_ptn, r1 = sum f*ddf_ptn as computeLikelihoodDerv returns them (phylokernel.h:583-651, the repair
+// of a non-finite sum, then +ASC's correction :719-724); MODE 1: r0 = sum f*log|lh_ptn| (computeLikelihoodFromBuffer's
+// sum, phylokernel.h:1040-1099) with +ASC's -nsites * log(1 - prob_const) (:1183-1186), r1 = 0.
+template <int MODE>
+__device__ __forceinline__ void solve_sums_at(const NewtonArgs &A, const DevBranch &br, SolveGroup &g, bool first, double x,
+                                              double &r0, double &r1) {
+    fill_factors(A, x, g.s_v0, g.s_v1, g.s_v2);
+    const bool asc = A.nobs < A.nptn;
+    const bool build = first && g.build_first;
+    if (asc) {
+        if (build || g.asc_from_ends) asc_unobserved_sums<true, MODE>(A, g.theta, br, g.s_v0, g.s_v1, g.s_v2, g.s_asc);
+        else asc_unobserved_sums<false, MODE>(A, g.theta, br, g.s_v0, g.s_v1, g.s_v2, g.s_asc);
+    }
+    double p0, p1;
+    if (MODE == 0 && build) wg_partial<true, 0>(A, g.theta, br, g.wg, g.G, g.s_v0, g.s_v1, g.s_v2, g.s_red, p0, p1, &g.regs);
+    else wg_partial<false, MODE>(A, g.theta, br, g.wg, g.G, g.s_v0, g.s_v1, g.s_v2, g.s_red, p0, p1, &g.regs);
+    if (g.G > 1) {
+        if (g.posts)
+            wg_exchange_posted(g.wg, g.G, g.posts + (size_t)g.epoch * g.G * 2, p0, p1, g.s_bcast, g.s_fail);
+        else
+            wg_exchange_counted(g.wg, g.G, g.partials + (size_t)(g.epoch & 1) * g.G * 2, g.counter,
+                                (g.epoch + 1) * (unsigned int)g.G, p0, p1, g.s_bcast, g.s_fail);
+        __syncthreads();   // (one broadcast pair: the next evaluation's wave 0 writes it again)
+        g.epoch++;
+    }
+    if (MODE == 0) {
+        newton_repair(p0, p1);
+        if (asc) asc_derv_correct(g.s_asc, A.asc_nsites, p0, p1);
+    } else if (asc) {
+        p0 -= A.asc_nsites * log(1.0 - g.s_asc[0]);
+    }
+    r0 = p0;
+    r1 = p1;
+}
+
+// Optimization::minimizeNewton (optimization.cpp:388-465) over solve_sums_at, every workgroup of the group for itself
+__device__ __forceinline__ void solve_newton(const NewtonArgs &A, const DevBranch &br, SolveGroup &g, NewtonState &ns,
+                                             double xguess, double x1, double x2, double xacc, int max_steps) {
+    newton_init(ns, xguess, x1, x2, xacc, max_steps);
+    double pdf, pddf;
+    solve_sums_at<0>(A, br, g, true, ns.rts, pdf, pddf);
+    newton_advance(ns, -pdf, -pddf);   // f = -dlnL/dt, df = -d2lnL/dt2 (phylotree.cpp:2135-2146)
+    while (!ns.done) {
+        solve_sums_at<0>(A, br, g, false, ns.rts, pdf, pddf);
+        newton_advance(ns, -pdf, -pddf);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_newton(const NewtonArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int B = A.n * A.ncat;
-    double *s_v0 = smem, *s_v1 = smem + B, *s_v2 = smem + 2 * B, *s_red = smem + 3 * B;  // s_red[8]
     __shared__ double s_bcast[2];
     __shared__ double s_asc[3];
     __shared__ int s_fail;
@@ -423,253 +505,42 @@ __global__ __launch_bounds__(256) void k_newton(const NewtonArgs A) {
             reinterpret_cast<unsigned long long *>(A.posts_other)[((size_t)ep * gridDim.x + blockIdx.x) * 2 + (t & 1)] = ~0ull;
         }
     }
-    unsigned int epoch = 0;
-    bool first = true;
-    ThetaRegs treg;
-    treg.have = false;
-    treg.use = A.ntiles <= (int64_t)gridDim.x * 4 && (A.mfma ? B <= 80 : B <= 20);
-    // f = -dlnL/dt, df = -d2lnL/dt2 at x (phylotree.cpp:2135-2146)
-    auto eval_at = [&](double x, double &f, double &df) {
-        for (int t = threadIdx.x; t < B; t += 256) {
-            const int c = t / A.n, i = t - c * A.n;
-            const double cof = A.eval[t] * A.rates[c];  // eval: per-category expansion [ncat][n]
-            const double v = exp(cof * x) * A.props[c];
-            s_v0[t] = v;
-            s_v1[t] = cof * v;
-            s_v2[t] = cof * (cof * v);
-        }
-        __syncthreads();
-        double pdf, pddf;
-        const bool asc = A.nobs < A.nptn;
-        if (asc) {
-            // a launch that builds theta never reads another workgroup's theta tiles (they are plain stores of this very
-            // launch: not visible across workgroups without a release / acquire): from the branch ends in every evaluation
-            if (A.build) asc_unobserved_sums<true>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
-            else asc_unobserved_sums<false>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
-        }
-        if (A.build && first) wg_partial<true>(A, A.theta, A.br, blockIdx.x, gridDim.x, s_v0, s_v1, s_v2, s_red, pdf, pddf, &treg);
-        else wg_partial<false>(A, A.theta, A.br, blockIdx.x, gridDim.x, s_v0, s_v1, s_v2, s_red, pdf, pddf, &treg);
-        first = false;
-        if (gridDim.x > 1 && A.posts) {
-            // Posted exchange (round 2): every (evaluation, workgroup) owns a slot {df, ddf} that holds the all-ones
-            // pattern until its owner stores into it; each double is an 8-byte agent-scope store, valid on its own, so
-            // there is no arrival counter, no wait for a store acknowledgement before it and no ordering between the
-            // two stores to rely on.  Wave 0 of every workgroup spins on the slots of the evaluation and sums them in
-            // the fixed order of the counter form (same bits).  9 -> 5.5 us per evaluation at 256 workgroups.
-            unsigned long long *slots = reinterpret_cast<unsigned long long *>(A.posts) + (size_t)epoch * gridDim.x * 2;
-            if (threadIdx.x == 0) {
-                unsigned long long ua = __double_as_longlong(pdf), ub = __double_as_longlong(pddf);
-                if (ua == ~0ull) ua = 0x7ff8000000000000ull;   // (a NaN that happens to be the sentinel: any other NaN)
-                if (ub == ~0ull) ub = 0x7ff8000000000000ull;
-                __hip_atomic_store(&slots[2 * blockIdx.x], ua, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&slots[2 * blockIdx.x + 1], ub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (threadIdx.x < 64) {
-                double a = 0.0, b = 0.0;
-                long spins = 0;
-                for (;;) {
-                    bool ready = true;
-                    a = 0.0; b = 0.0;
-                    for (int w = threadIdx.x; w < (int)gridDim.x; w += 64) {
-                        const unsigned long long ua = __hip_atomic_load(&slots[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned long long ub = __hip_atomic_load(&slots[2 * w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ready = ready && ua != ~0ull && ub != ~0ull;
-                        a += __longlong_as_double(ua);
-                        b += __longlong_as_double(ub);
-                    }
-                    if (__all(ready)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 2000000L) { if (threadIdx.x == 0) s_fail = 1; break; }  // never hang the GPU
-                }
-                a = wsum(a);
-                b = wsum(b);
-                if (threadIdx.x == 0) { s_bcast[0] = a; s_bcast[1] = b; }
-            }
-            __syncthreads();
-            pdf = s_bcast[0];
-            pddf = s_bcast[1];
-            __syncthreads();
-            epoch++;
-        } else if (gridDim.x > 1) {
-            double *slot = A.partials + (size_t)(epoch & 1) * gridDim.x * 2;
-            if (threadIdx.x == 0) {
-                // The partials travel as agent-scope (write-through) stores and are read back with agent-scope
-                // loads; no release / acquire fence -- a fence writes back and invalidates the XCD's L2, i.e.
-                // throws away the theta slice this workgroup re-reads in every Newton step.
-                __hip_atomic_store(&slot[2 * blockIdx.x], pdf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&slot[2 * blockIdx.x + 1], pddf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_fetch_add(A.barrier, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned int target = (epoch + 1) * gridDim.x;
-                long spins = 0;
-                while (__hip_atomic_load(A.barrier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 4000000L) { s_fail = 1; break; }  // never hang the GPU (~0.2 s)
-                }
-            }
-            __syncthreads();
-            // fixed-order sum of the workgroup partials by wave 0 (identical on every workgroup)
-            if (threadIdx.x < 64) {
-                double a = 0.0, b = 0.0;
-                for (int w = threadIdx.x; w < (int)gridDim.x; w += 64) {
-                    a += __hip_atomic_load(&slot[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    b += __hip_atomic_load(&slot[2 * w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                a = wsum(a);
-                b = wsum(b);
-                if (threadIdx.x == 0) { s_bcast[0] = a; s_bcast[1] = b; }
-            }
-            __syncthreads();
-            pdf = s_bcast[0];
-            pddf = s_bcast[1];
-            __syncthreads();
-            epoch++;
-        }
-        if (isnan(pdf) || isinf(pdf)) { pdf = 0.0; pddf = 0.0; }  // phylokernel.h:647-651
-        if (asc) {   // phylokernel.h:719-724
-            const double prob_const = 1.0 - s_asc[0];
-            const double df_frac = s_asc[1] / prob_const, ddf_frac = s_asc[2] / prob_const;
-            pdf += A.asc_nsites * df_frac;
-            pddf += A.asc_nsites * (ddf_frac + df_frac * df_frac);
-        }
-        f = -pdf;
-        df = -pddf;
-    };
+    SolveGroup g;
+    g.regs.have = false;
+    g.regs.use = A.ntiles <= (int64_t)gridDim.x * 4 && (A.mfma ? B <= 80 : B <= 20);
+    g.theta = A.theta;
+    g.wg = (int)blockIdx.x;
+    g.G = (int)gridDim.x;
+    g.posts = reinterpret_cast<unsigned long long *>(A.posts);
+    g.partials = A.partials;
+    g.counter = A.barrier;
+    g.build_first = A.build != 0;
+    // a launch that builds theta never reads another workgroup's theta tiles (they are plain stores of this very
+    // launch: not visible across workgroups without a release / acquire): from the branch ends in every evaluation
+    g.asc_from_ends = A.build != 0;
+    g.s_v0 = smem; g.s_v1 = smem + B; g.s_v2 = smem + 2 * B; g.s_red = smem + 3 * B;
+    g.s_bcast = s_bcast; g.s_asc = s_asc; g.s_fail = &s_fail;
+    g.epoch = 0;
 
-    // sum over all patterns of f * log|lh_ptn| at branch length x (computeLikelihoodFromBuffer's sum, phylokernel.h:1040-1099),
-    // exchanged like the derivative sums; only the diverged-solve rule below needs it
-    auto lnl_at = [&](double x) -> double {
-        for (int t = threadIdx.x; t < B; t += 256) {
-            const int c = t / A.n;
-            const double cof = A.eval[t] * A.rates[c];
-            const double v = exp(cof * x) * A.props[c];
-            s_v0[t] = v;
-            s_v1[t] = cof * v;
-            s_v2[t] = cof * (cof * v);
-        }
-        __syncthreads();
-        double p0, p1;
-        const bool asc = A.nobs < A.nptn;
-        if (asc) {   // (as in eval_at: from the branch ends when this launch built theta)
-            if (A.build) asc_unobserved_sums<true, 1>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
-            else asc_unobserved_sums<false, 1>(A, A.theta, A.br, s_v0, s_v1, s_v2, s_asc);
-        }
-        wg_partial<false, 1>(A, A.theta, A.br, blockIdx.x, gridDim.x, s_v0, s_v1, s_v2, s_red, p0, p1, &treg);
-        if (gridDim.x > 1 && A.posts) {
-            unsigned long long *slots = reinterpret_cast<unsigned long long *>(A.posts) + (size_t)epoch * gridDim.x * 2;
-            if (threadIdx.x == 0) {
-                unsigned long long ua = __double_as_longlong(p0);
-                if (ua == ~0ull) ua = 0x7ff8000000000000ull;
-                __hip_atomic_store(&slots[2 * blockIdx.x], ua, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (threadIdx.x < 64) {
-                double a = 0.0;
-                long spins = 0;
-                for (;;) {
-                    bool ready = true;
-                    a = 0.0;
-                    for (int w = threadIdx.x; w < (int)gridDim.x; w += 64) {
-                        const unsigned long long ua = __hip_atomic_load(&slots[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ready = ready && ua != ~0ull;
-                        a += __longlong_as_double(ua);
-                    }
-                    if (__all(ready)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 2000000L) { if (threadIdx.x == 0) s_fail = 1; break; }
-                }
-                a = wsum(a);
-                if (threadIdx.x == 0) s_bcast[0] = a;
-            }
-            __syncthreads();
-            p0 = s_bcast[0];
-            __syncthreads();
-            epoch++;
-        } else if (gridDim.x > 1) {
-            double *slot = A.partials + (size_t)(epoch & 1) * gridDim.x * 2;
-            if (threadIdx.x == 0) {
-                __hip_atomic_store(&slot[2 * blockIdx.x], p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_fetch_add(A.barrier, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned int target = (epoch + 1) * gridDim.x;
-                long spins = 0;
-                while (__hip_atomic_load(A.barrier, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 4000000L) { s_fail = 1; break; }
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x < 64) {
-                double a = 0.0;
-                for (int w = threadIdx.x; w < (int)gridDim.x; w += 64)
-                    a += __hip_atomic_load(&slot[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a = wsum(a);
-                if (threadIdx.x == 0) s_bcast[0] = a;
-            }
-            __syncthreads();
-            p0 = s_bcast[0];
-            __syncthreads();
-            epoch++;
-        }
-        // +ASC (phylokernel.h:1183-1186): both lengths of the comparison carry their own -nsites * log(1 - prob_const)
-        if (asc) p0 -= A.asc_nsites * log(1.0 - s_asc[0]);
-        return p0;
-    };
-
-    // ---- Optimization::minimizeNewton (optimization.cpp:388-450), same control flow
-    double df, dx, f, temp, xh, xl, rts, rts_old, d2l;
-    int nsteps = 1, status = 0;
-    rts = A.xguess;
-    if (rts < A.x1) rts = A.x1;
-    if (rts > A.x2) rts = A.x2;
-    eval_at(rts, f, df);
-    d2l = df;
-    double result = rts;
-    bool done = false;
-    if (!isfinite(f) || !isfinite(df)) { status = 2; done = true; }
-    if (!done && df >= 0.0 && fabs(f) < A.xacc) done = true;
-    if (!done) {
-        if (f < 0.0) { xl = rts; xh = A.x2; } else { xh = rts; xl = A.x1; }
-        dx = fabs(xh - xl);
-        int j;
-        for (j = 1; j <= A.max_steps; j++) {
-            rts_old = rts;
-            if ((df <= 0.0) || (((rts - xh) * df - f) * ((rts - xl) * df - f) >= 0.0)) {
-                dx = 0.5 * (xh - xl);
-                rts = xl + dx;
-                d2l = df;
-                if (xl == rts) { result = rts; break; }
-            } else {
-                dx = f / df;
-                temp = rts;
-                rts -= dx;
-                d2l = df;
-                if (temp == rts) { result = rts; break; }
-            }
-            if (fabs(dx) < A.xacc || (j == A.max_steps)) { result = rts_old; break; }
-            eval_at(rts, f, df);
-            nsteps++;
-            if (!isfinite(f) || !isfinite(df)) { status = 2; result = rts_old; break; }
-            if (df > 0.0 && fabs(f) < A.xacc) { d2l = df; result = rts; break; }
-            if (f < 0.0) xl = rts; else xh = rts;
-        }
-        if (j > A.max_steps) status = 3;  // "Maximum number of iterations exceeded"
-    }
+    NewtonState ns;
+    solve_newton(A, A.br, g, ns, A.xguess, A.x1, A.x2, A.xacc, A.max_steps);
     // "newton raphson diverged, reset" (phylotree.cpp:2167-2176): opt_lh at the result against orig_lh at the starting
-    // length, both computeLikelihoodFromBuffer sums of this branch (their lh_scale_factor terms are the same)
-    double diverged = 0.0;
-    if (A.diverge_x > 0.0 && status == 0 && result > A.diverge_x) {
-        const double opt_lh = lnl_at(result);
-        const double orig_lh = lnl_at(A.xguess);
+    // length, both computeLikelihoodFromBuffer sums of this branch (their lh_scale_factor terms are the same; +ASC: both
+    // carry their own -nsites * log(1 - prob_const)), exchanged like the derivative sums
+    double result = ns.result, diverged = 0.0;
+    if (A.diverge_x > 0.0 && ns.status == 0 && result > A.diverge_x) {
+        double opt_lh, orig_lh, unused;
+        solve_sums_at<1>(A, A.br, g, false, result, opt_lh, unused);
+        solve_sums_at<1>(A, A.br, g, false, A.xguess, orig_lh, unused);
         diverged = 1.0;
         if (orig_lh > opt_lh) result = A.xguess;
     }
     __syncthreads();
-    if (s_fail) status = 4;  // grid barrier timed out
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         A.out[0] = result;
-        A.out[1] = d2l;
-        A.out[2] = (double)nsteps;
-        A.out[3] = (double)status;
+        A.out[1] = ns.d2l;
+        A.out[2] = (double)ns.neval;
+        A.out[3] = (double)(s_fail ? 4 : ns.status);  // 4: the exchange gave up
         if (A.diverge_x > 0.0) A.out[4] = diverged;
         if (A.len_out) *A.len_out = result;
         if (A.done) {
@@ -702,7 +573,7 @@ struct NewtonBatchArgs {
     double *partials;           // [ntasks][2 parities][G][2]
     unsigned int *barriers;     // [ntasks] arrival counters of this launch (zero at its start)
     unsigned int *barriers_next;  // the next launch's counters, cleared here
-    double *out;                // [ntasks][6] = {optx, d2l, nsteps, status, lnl, 0}
+    double *out;                // [ntasks][6] = {optx, d2l, evaluations, status, lnl, 0}
     int G;
     // posted exchange (see k_newton): slots [task][evaluation][workgroup][2] of this launch, sentinel = not yet posted;
     // the first posts_other_used doubles of the other parity's buffer are reset for the launch after this one
@@ -716,7 +587,6 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const NewtonArgs &A = P.c;
     const int B = A.n * A.ncat;
-    double *s_v0 = smem, *s_v1 = smem + B, *s_v2 = smem + 2 * B, *s_red = smem + 3 * B;  // s_red[8]
     __shared__ double s_bcast[2];
     __shared__ double s_asc[3];
     __shared__ int s_fail;
@@ -729,9 +599,6 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
     T.br.a = Tc.br.a; T.br.a_states = Tc.br.a_states; T.br.b = Tc.br.b; T.br.a_sc = Tc.br.a_sc; T.br.b_sc = Tc.br.b_sc;
     T.br.a_kind = Tc.br.a_kind; T.br.b_kind = Tc.br.b_kind; T.br.len = Tc.br.len;
     T.xguess = Tc.xguess; T.x1 = Tc.x1; T.x2 = Tc.x2; T.xacc = Tc.xacc; T.max_steps = Tc.max_steps;
-    double *theta = P.theta_base + (size_t)task * P.theta_stride;
-    double *slots = P.partials + (size_t)task * 4 * G;
-    unsigned int *bar = P.barriers + task;
     if (threadIdx.x == 0) {
         s_fail = 0;
         if (wg == 0) __hip_atomic_store(P.barriers_next + task, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -739,174 +606,35 @@ __global__ __launch_bounds__(256) void k_newton_batch(const NewtonBatchArgs P) {
     if (P.posts)
         for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < P.posts_other_used; t += (size_t)gridDim.x * 256)
             reinterpret_cast<unsigned long long *>(P.posts_other)[t] = ~0ull;
-    unsigned int epoch = 0;
-    bool first = true;
-    const bool asc = A.nobs < A.nptn;
-    // sums over the task's patterns of (f*df, f*ddf) -- or of f*log|lh| when lnl_pass -- at branch length x; +ASC: the sums
-    // over the unobserved constant patterns at the same val arrays are left in s_asc (every workgroup its own copy)
-    auto eval_at = [&](double x, bool lnl_pass, double &r0, double &r1) {
-        for (int t = threadIdx.x; t < B; t += 256) {
-            const int c = t / A.n;
-            const double cof = A.eval[t] * A.rates[c];
-            const double v = exp(cof * x) * A.props[c];
-            s_v0[t] = v;
-            s_v1[t] = cof * v;
-            s_v2[t] = cof * (cof * v);
-        }
-        __syncthreads();
-        double p0, p1;
-        if (asc) {
-            // theta of the last tile(s) is in flight from its owner during the task's first evaluation, and with several
-            // workgroups per task the owner's plain stores never become visible to the others in this launch (k_newton's
-            // rule): from the branch ends then; a task of one workgroup reads back what it wrote itself
-            const bool from_ends = first || G > 1;
-            if (lnl_pass) {
-                if (from_ends) asc_unobserved_sums<true, 1>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
-                else asc_unobserved_sums<false, 1>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
-            } else {
-                if (from_ends) asc_unobserved_sums<true, 0>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
-                else asc_unobserved_sums<false, 0>(A, theta, T.br, s_v0, s_v1, s_v2, s_asc);
-            }
-        }
-        if (lnl_pass) wg_partial<false, 1>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
-        else if (first) wg_partial<true, 0>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
-        else wg_partial<false, 0>(A, theta, T.br, wg, G, s_v0, s_v1, s_v2, s_red, p0, p1);
-        first = false;
-        if (G > 1 && P.posts) {
-            unsigned long long *ps = reinterpret_cast<unsigned long long *>(P.posts) +
-                                     ((size_t)task * P.post_epochs + epoch) * G * 2;
-            if (threadIdx.x == 0) {
-                unsigned long long ua = __double_as_longlong(p0), ub = __double_as_longlong(p1);
-                if (ua == ~0ull) ua = 0x7ff8000000000000ull;
-                if (ub == ~0ull) ub = 0x7ff8000000000000ull;
-                __hip_atomic_store(&ps[2 * wg], ua, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&ps[2 * wg + 1], ub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if (threadIdx.x < 64) {
-                double a = 0.0, b = 0.0;
-                long spins = 0;
-                for (;;) {
-                    bool ready = true;
-                    a = 0.0; b = 0.0;
-                    for (int w = threadIdx.x; w < G; w += 64) {
-                        const unsigned long long ua = __hip_atomic_load(&ps[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const unsigned long long ub = __hip_atomic_load(&ps[2 * w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ready = ready && ua != ~0ull && ub != ~0ull;
-                        a += __longlong_as_double(ua);
-                        b += __longlong_as_double(ub);
-                    }
-                    if (__all(ready)) break;
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 2000000L) { if (threadIdx.x == 0) s_fail = 1; break; }  // never hang the GPU
-                }
-                a = wsum(a);
-                b = wsum(b);
-                if (threadIdx.x == 0) { s_bcast[0] = a; s_bcast[1] = b; }
-            }
-            __syncthreads();
-            p0 = s_bcast[0];
-            p1 = s_bcast[1];
-            __syncthreads();
-            epoch++;
-        } else if (G > 1) {
-            double *slot = slots + (size_t)(epoch & 1) * G * 2;
-            if (threadIdx.x == 0) {
-                __hip_atomic_store(&slot[2 * wg], p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&slot[2 * wg + 1], p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned int target = (epoch + 1) * (unsigned int)G;
-                long spins = 0;
-                while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > 4000000L) { s_fail = 1; break; }  // never hang the GPU (~0.2 s)
-                }
-            }
-            __syncthreads();
-            if (threadIdx.x < 64) {  // fixed-order sum of the task's workgroup partials
-                double a = 0.0, b = 0.0;
-                for (int w = threadIdx.x; w < G; w += 64) {
-                    a += __hip_atomic_load(&slot[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    b += __hip_atomic_load(&slot[2 * w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                a = wsum(a);
-                b = wsum(b);
-                if (threadIdx.x == 0) { s_bcast[0] = a; s_bcast[1] = b; }
-            }
-            __syncthreads();
-            p0 = s_bcast[0];
-            p1 = s_bcast[1];
-            __syncthreads();
-            epoch++;
-        }
-        r0 = p0;
-        r1 = p1;
-    };
-    auto derv_at = [&](double x, double &f, double &df) {
-        double pdf, pddf;
-        eval_at(x, false, pdf, pddf);
-        if (isnan(pdf) || isinf(pdf)) { pdf = 0.0; pddf = 0.0; }  // phylokernel.h:647-651
-        if (asc) {   // phylokernel.h:719-724
-            const double prob_const = 1.0 - s_asc[0];
-            const double df_frac = s_asc[1] / prob_const, ddf_frac = s_asc[2] / prob_const;
-            pdf += A.asc_nsites * df_frac;
-            pddf += A.asc_nsites * (ddf_frac + df_frac * df_frac);
-        }
-        f = -pdf;
-        df = -pddf;
-    };
+    SolveGroup g;
+    g.theta = P.theta_base + (size_t)task * P.theta_stride;
+    g.wg = wg;
+    g.G = G;
+    g.posts = P.posts ? reinterpret_cast<unsigned long long *>(P.posts) + (size_t)task * P.post_epochs * G * 2 : nullptr;
+    g.partials = P.partials + (size_t)task * 4 * G;
+    g.counter = P.barriers + task;
+    g.regs.have = g.regs.use = false;
+    g.build_first = true;
+    // +ASC: theta of the last tile(s) is in flight from its owner during the task's first evaluation, and with several
+    // workgroups per task the owner's plain stores never become visible to the others in this launch (k_newton's
+    // rule): from the branch ends then; a task of one workgroup reads back what it wrote itself
+    g.asc_from_ends = G > 1;
+    g.s_v0 = smem; g.s_v1 = smem + B; g.s_v2 = smem + 2 * B; g.s_red = smem + 3 * B;
+    g.s_bcast = s_bcast; g.s_asc = s_asc; g.s_fail = &s_fail;
+    g.epoch = 0;
 
-    // ---- Optimization::minimizeNewton (optimization.cpp:388-450), same control flow as k_newton
-    double df, dx, f, temp, xh, xl, rts, rts_old, d2l;
-    int nsteps = 1, status = 0;
-    rts = T.xguess;
-    if (rts < T.x1) rts = T.x1;
-    if (rts > T.x2) rts = T.x2;
-    derv_at(rts, f, df);
-    d2l = df;
-    double result = rts;
-    bool done = false;
-    if (!isfinite(f) || !isfinite(df)) { status = 2; done = true; }
-    if (!done && df >= 0.0 && fabs(f) < T.xacc) done = true;
-    if (!done) {
-        if (f < 0.0) { xl = rts; xh = T.x2; } else { xh = rts; xl = T.x1; }
-        dx = fabs(xh - xl);
-        int j;
-        for (j = 1; j <= T.max_steps; j++) {
-            rts_old = rts;
-            if ((df <= 0.0) || (((rts - xh) * df - f) * ((rts - xl) * df - f) >= 0.0)) {
-                dx = 0.5 * (xh - xl);
-                rts = xl + dx;
-                d2l = df;
-                if (xl == rts) { result = rts; break; }
-            } else {
-                dx = f / df;
-                temp = rts;
-                rts -= dx;
-                d2l = df;
-                if (temp == rts) { result = rts; break; }
-            }
-            if (fabs(dx) < T.xacc || (j == T.max_steps)) { result = rts_old; break; }
-            derv_at(rts, f, df);
-            nsteps++;
-            if (!isfinite(f) || !isfinite(df)) { status = 2; result = rts_old; break; }
-            if (df > 0.0 && fabs(f) < T.xacc) { d2l = df; result = rts; break; }
-            if (f < 0.0) xl = rts; else xh = rts;
-        }
-        if (j > T.max_steps) status = 3;
-    }
+    NewtonState ns;
+    solve_newton(A, T.br, g, ns, T.xguess, T.x1, T.x2, T.xacc, T.max_steps);
     // lnL of the branch at the returned length (computeLikelihoodFromBuffer, phylokernel.h:1022-1192)
     double lnl, unused;
-    eval_at(result, true, lnl, unused);
-    if (asc) lnl -= A.asc_nsites * log(1.0 - s_asc[0]);   // phylokernel.h:1183-1186
+    solve_sums_at<1>(A, T.br, g, false, ns.result, lnl, unused);
     __syncthreads();
-    if (s_fail) status = 4;
     if (wg == 0 && threadIdx.x == 0) {
         double *o = P.out + (size_t)task * 6;
-        o[0] = result;
-        o[1] = d2l;
-        o[2] = (double)nsteps;
-        o[3] = (double)status;
+        o[0] = ns.result;
+        o[1] = ns.d2l;
+        o[2] = (double)ns.neval;
+        o[3] = (double)(s_fail ? 4 : ns.status);
         o[4] = lnl;
         o[5] = 0.0;
     }
@@ -926,39 +654,30 @@ void newton_task_fill(void *dst, const DevBranch &br, double xguess, double x1, 
     memcpy(dst, &t, sizeof t);
 }
 
-hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,
-                               size_t theta_stride, double *partials, unsigned int *barriers, unsigned int *barriers_next,
-                               double *out, double *posts, double *posts_other, size_t posts_other_used, int post_epochs) {
-    NewtonBatchArgs P;
-    NewtonArgs &A = P.c;
-    A.theta = nullptr;
+// the model and alignment half of NewtonArgs, the same for every solve of an engine
+static void fill_model_args(NewtonArgs &A, const iqhip_engine *e) {
     A.eval = e->d_evalc;
     A.rates = e->d_rates;
     A.props = e->d_props;
     A.freq = e->d_freq.p;
     A.invar = e->d_invar.p;
-    A.partials = nullptr;
-    A.barrier = nullptr;
-    A.barrier_next = nullptr;
-    A.out = nullptr;
-    A.build = 1;
-    A.br = DevBranch{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.0};
     A.tipc = e->d_tipc;
-    A.slab = nullptr;
-    A.result = nullptr;
-    A.nrows = 0;
-    A.nwaves = 0;
     A.ntiles = e->ntiles;
     A.nptn = e->nptn;
     A.n = e->n;
     A.ncat = e->ncat;
     A.mfma = e->mfma ? 1 : 0;
-    A.xguess = A.x1 = A.x2 = A.xacc = 0.0;
-    A.max_steps = 0;
-    A.len_out = nullptr;
-    A.diverge_x = 0.0;
     A.nobs = e->nptn - e->n_unobs;
     A.asc_nsites = e->asc_nsites;
+}
+
+hipError_t launch_newton_batch(iqhip_engine *e, const void *d_tasks, int ntasks, int G, double *theta_base,
+                               size_t theta_stride, double *partials, unsigned int *barriers, unsigned int *barriers_next,
+                               double *out, double *posts, double *posts_other, size_t posts_other_used, int post_epochs) {
+    NewtonBatchArgs P;
+    P.c = NewtonArgs{};   // (theta, the branch, the bounds and the result are per task)
+    fill_model_args(P.c, e);
+    P.c.build = 1;
     P.tasks = static_cast<const NewtonTask *>(d_tasks);
     P.theta_base = theta_base;
     P.theta_stride = theta_stride;
@@ -998,11 +717,8 @@ __global__ void k_newton_state_update(NewtonState *st, const double *result, dou
         if (!s.done) {
             double df = result[0], ddf = result[1];
             if (asc_nsites > 0.0) {
-                if (isnan(df) || isinf(df)) { df = 0.0; ddf = 0.0; }   // (phylokernel.h:647-651 comes first)
-                const double prob_const = 1.0 - result[2];
-                const double df_frac = result[3] / prob_const, ddf_frac = result[4] / prob_const;
-                df += asc_nsites * df_frac;
-                ddf += asc_nsites * (ddf_frac + df_frac * df_frac);
+                newton_repair(df, ddf);   // (phylokernel.h:647-651 comes first)
+                asc_derv_correct(result + 2, asc_nsites, df, ddf);
             }
             newton_update(s, df, ddf);
             *st = s;
@@ -1020,11 +736,8 @@ __global__ void k_newton_state_update_batch(NewtonState *st, const double *resul
     if (asc_nsites > 0.0) {
         const double *r = result + 5 * t;
         double df = r[0], ddf = r[1];
-        if (isnan(df) || isinf(df)) { df = 0.0; ddf = 0.0; }
-        const double prob_const = 1.0 - r[2];
-        const double df_frac = r[3] / prob_const, ddf_frac = r[4] / prob_const;
-        df += asc_nsites * df_frac;
-        ddf += asc_nsites * (ddf_frac + df_frac * df_frac);
+        newton_repair(df, ddf);
+        asc_derv_correct(r + 2, asc_nsites, df, ddf);
         newton_update(s, df, ddf);
     } else {
         newton_update(s, result[2 * t], result[2 * t + 1]);
@@ -1063,37 +776,25 @@ hipError_t launch_newton(iqhip_engine *e, double xguess, double x1, double x2, d
                          double *out, const DevBranch *build_from, int reduce_rows, int reduce_nwaves,
                          const NewtonSweepStep *sweep) {
     NewtonArgs A;
+    fill_model_args(A, e);
     A.len_out = sweep ? sweep->len_out : nullptr;
-    A.nobs = e->nptn - e->n_unobs;
-    A.asc_nsites = e->asc_nsites;
     A.diverge_x = sweep ? sweep->diverge_x : 0.0;
     A.build = build_from ? 1 : 0;
     A.br = build_from ? *build_from : DevBranch{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.0};
-    A.tipc = e->d_tipc;
     A.slab = e->d_slab.p;
     A.result = sweep ? sweep->rows_base - 2 : e->d_result;   // (row r of the node updates goes to result[2 + r])
     A.nrows = reduce_rows;
     A.nwaves = reduce_nwaves;
     A.theta = e->d_theta.p;
-    A.eval = e->d_evalc;
-    A.rates = e->d_rates;
-    A.props = e->d_props;
-    A.freq = e->d_freq.p;
-    A.invar = e->d_invar.p;
     A.partials = e->d_newton_partials.p;
     A.out = out;
-    A.ntiles = e->ntiles;
-    A.nptn = e->nptn;
-    A.n = e->n;
-    A.ncat = e->ncat;
-    A.mfma = e->mfma ? 1 : 0;
     A.xguess = xguess;
     A.x1 = x1;
     A.x2 = x2;
     A.xacc = xacc;
     A.max_steps = max_steps;
     // every workgroup must be resident for the exchange: one per CU with the arrival counter (its slots are sized for that),
-    // two per CU with the posted exchange (125 registers, little LDS: four would fit), so that a 100 k-pattern alignment
+    // two per CU with the posted exchange (226 registers since theta stays in them: two fit), so that a 100 k-pattern alignment
     // has one tile per wave and a derivative pass is one round trip
     const bool posts = e->newton_posts && max_steps + 5 <= kNewtonPostEpochs;   // (+2: the lnL passes of the diverged-solve rule)
     const int64_t wgs = (e->ntiles + 3) / 4;

@@ -18,6 +18,7 @@
 // a sweep accepts the same lengths, to the last bit, as the one-submission-per-branch form; tests/test_sweep_gpu.py
 // checks exactly that and re-evaluates the optimised tree with the oracle.
 #include "iqhip_internal.h"
+#include "wg_exchange.h"
 
 namespace iqhip {
 
@@ -26,8 +27,6 @@ template <typename T>
 __device__ __forceinline__ const CONST_AS T *sw_const(const T *p) {
     return (const CONST_AS T *)(p);
 }
-
-__device__ __forceinline__ double sw_wsum(double v) { return wave_sum64(v); }
 
 struct SweepArgs {
     const SweepOp *ops;
@@ -235,7 +234,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
             double scale_acc = 0.0;
             for (int64_t tile = gw; tile < A.ntiles; tile += (int64_t)G * WAVES)
                 sweep_node_update<C>(op, s_ex, s_tab, s_tip, U, uinv, tile, lane, A.nptn, A.state_unknown, A.freq, A.invar, scale_acc);
-            const double ws = __any(scale_acc != 0.0) ? sw_wsum(scale_acc) : 0.0;
+            const double ws = __any(scale_acc != 0.0) ? wave_sum64(scale_acc) : 0.0;
             if (lane == 0) A.slab[(size_t)op.row * A.nwaves + gw] = ws;
         }
 
@@ -310,8 +309,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
                 }
             }
             (void)have_tile;
-            adf = sw_wsum(adf);
-            addf = sw_wsum(addf);
+            adf = wave_sum64(adf);
+            addf = wave_sum64(addf);
             // (two buffers, by the evaluation's parity: the waves that are still reading this one cannot be overtaken by a
             // write of the evaluation after the next, which lies behind the next evaluation's barrier)
             if (lane == 0) { red[2 * wave] = adf; red[2 * wave + 1] = addf; }
@@ -323,38 +322,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
                 p1 += (red[9] + red[11]) + (red[13] + red[15]);
             }
             if (G > 1) {
-                unsigned long long *slots = posts + (size_t)epoch * G * 2;
-                if (threadIdx.x == 0) {
-                    unsigned long long ua = __double_as_longlong(p0), ub = __double_as_longlong(p1);
-                    if (ua == ~0ull) ua = 0x7ff8000000000000ull;   // (a NaN that happens to be the sentinel: any other NaN)
-                    if (ub == ~0ull) ub = 0x7ff8000000000000ull;
-                    __hip_atomic_store(&slots[2 * wg], ua, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&slots[2 * wg + 1], ub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (threadIdx.x < 64) {
-                    double a = 0.0, b = 0.0;
-                    long spins = 0;
-                    for (;;) {
-                        bool ready = true;
-                        a = 0.0; b = 0.0;
-                        for (int w = threadIdx.x; w < G; w += 64) {
-                            const unsigned long long ua = __hip_atomic_load(&slots[2 * w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const unsigned long long ub = __hip_atomic_load(&slots[2 * w + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            ready = ready && ua != ~0ull && ub != ~0ull;
-                            a += __longlong_as_double(ua);
-                            b += __longlong_as_double(ub);
-                        }
-                        if (__all(ready)) break;
-                        __builtin_amdgcn_s_sleep(1);
-                        if (++spins > 2000000L) { if (threadIdx.x == 0) s_fail = 1; break; }  // never hang the GPU
-                    }
-                    a = sw_wsum(a);
-                    b = sw_wsum(b);
-                    if (threadIdx.x == 0) { bcast[0] = a; bcast[1] = b; }
-                }
-                __syncthreads();
-                p0 = bcast[0];
-                p1 = bcast[1];
+                // (bcast alternates with the evaluation's parity like red: no barrier behind the exchange)
+                wg_exchange_posted(wg, G, posts + (size_t)epoch * G * 2, p0, p1, bcast, &s_fail);
                 if (epoch == 0) {
                     // every workgroup has posted evaluation 0 of this step, so every workgroup is done with the previous
                     // step's slots (the other parity): back to "not posted" for the step after this one, and acknowledged

@@ -226,12 +226,8 @@ static int asc_finish(iqhip_engine *p, double prob_const, double *lnl) {
 // phylokernel.h:647-651, then :719-724 on the summed {prob_const, df_const, ddf_const} = v[2..4]
 // (one copy of this arithmetic: the batched chain must give the bits of the one-task form)
 __attribute__((noinline)) static void asc_derv(const iqhip_engine *p, double *v) {
-    if (isnan(v[0]) || isinf(v[0])) v[0] = v[1] = 0.0;
-    if (!p->asc_active) return;
-    const double prob_const = 1.0 - v[2];
-    const double df_frac = v[3] / prob_const, ddf_frac = v[4] / prob_const;
-    v[0] += p->asc_nsites * df_frac;
-    v[1] += p->asc_nsites * (ddf_frac + df_frac * df_frac);
+    newton_repair(v[0], v[1]);
+    if (p->asc_active) asc_derv_correct(v + 2, p->asc_nsites, v[0], v[1]);
 }
 
 int traverse(iqhip_engine *p, const iqhip_node_op *ops, int nops, bool has_root, iqhip_branch_end a, iqhip_branch_end b,
