@@ -493,6 +493,7 @@ int iqhost_mix_posteriors(void *h, const double *class_freq, double *post, doubl
     IQHOST_TRY({
         PhyloTree *t = (PhyloTree *)h;
         if (!t->engine) throw std::runtime_error("no engine");
+        t->syncInputs();   // (as mixWeightsEM: a pending model change must reach the engine before it judges the matrix)
         if (iqhip_mix_posteriors(t->engine, class_freq, post, state_freq) != 0) throw std::runtime_error(iqhip_last_error());
     });
 }

@@ -2226,6 +2226,9 @@ std::vector<double> PhyloTree::getMixtureWeights() const {
 
 void PhyloTree::mixWeightsEM(int max_steps, double *weights, double *p_invar, int *nsteps, int *converged, double *trace) {
     if (!engine) throw std::runtime_error("no engine");
+    // a model or weights set since the last submission reach the engine first: it refuses the matrix of another model
+    // (mix.model_version), which it cannot do for a model it has not been sent yet
+    pushInputs();
     check(iqhip_mix_weights_em(engine, max_steps, getAlnNSite(), weights, p_invar, nsteps, converged, trace), "iqhip_mix_weights_em");
 }
 
