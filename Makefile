@@ -18,7 +18,7 @@ all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/lib
 $(LIBDIR):
 	mkdir -p $(LIBDIR)
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/pars_spr_check.h include/iqhip.h | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/trav_phases.h $(CSRC)/pars_spr_check.h include/iqhip.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the topology tests compare sums bit for bit with a plain IEEE evaluation of the reference's expressions

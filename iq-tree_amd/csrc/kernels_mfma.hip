@@ -19,7 +19,8 @@
 //     by a select on the accumulators.
 // Scaling follows the SIMD rule (phylokernel.h:461-474): per pattern max |out| over the whole
 // block (taken on the high words, see kScalingThresholdHi); the vector is stored unscaled per
-// category and re-scaled in place in the rare case.
+// category and re-scaled in place in the rare case.  The tail of an op is trav_phases.h's
+// promote_nonzero, (tile_max,) scale_choice and post_scale_sum around the kernel's OWN rewrite.
 // Kernels: k_traverse_mfma (generic category count, mixtures of 4 / 64 states: both children from
 // memory), k_traverse_mfma2 (20 and 64 states, 1 or 4 categories: previous result in registers,
 // streamed child prefetched, leaf tables, parked results in LDS, staged plans),
@@ -31,6 +32,7 @@
 #include <type_traits>
 
 #include "iqhip_internal.h"
+#include "trav_phases.h"
 
 namespace iqhip {
 
@@ -137,8 +139,7 @@ __device__ __forceinline__ double group_max(double v) {
 }
 
 // (the scaling test on the high words -- kScalingThresholdHi, amax_hi, nonzero_bits, group_max_u -- is shared with
-// kernels_valu4w.hip: iqhip_internal.h)
-__device__ __forceinline__ double wave_sum_m(double v) { return wave_sum64(v); }
+// kernels_valu4w.hip: iqhip_internal.h; the decision taken on it, the cross-wave maximum and the posting: trav_phases.h)
 
 struct TravMArgs {
     const DevOp *ops;
@@ -218,12 +219,8 @@ __global__ __launch_bounds__(WG) void k_traverse_mfma(const TravMArgs A) {
     while (k < k_end) {
         const int kn = A.ops[k].chunk_nops;
         __syncthreads();
-        for (int t = threadIdx.x; t < kn * 2 * B; t += WG) {
-            const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-            const CONST_AS DevOp &d = as_const(A.ops)[k + o];
-            const double len = op_child_len(d, child);
-            sReg[(child ? d.lds_right : d.lds_left) + e] = exp(A.evalc[e] * (A.rates[e / N] * len));
-        }
+        fill_exponentials<WG>(as_const(A.ops), k, kn, B, sReg, [ev = A.evalc](int e) { return ev[e]; },
+                              [rt = A.rates](int e) { return rt[e / N]; }, FillAll{});
         __syncthreads();
         if (!active) { k += kn; continue; }
 
@@ -310,26 +307,20 @@ __global__ __launch_bounds__(WG) void k_traverse_mfma(const TravMArgs A) {
             }
             // column (pattern) max over the 4 lane groups (lmax orders the high words; a denormal below 2^-1042 still counts
             // as non-zero for the scalar rule's exact test)
-            if (nz != 0 && lmax == 0) lmax = 1;
-            lmax = group_max_u(lmax);
             const int rule = op.no_scale;
-            const bool zero = rule == 2 && !(leafL && leafR) && lmax == 0;   // the scalar kernel's `lh_max == 0.0`, phylotreesse.cpp:777-788
-            const bool do_scale = zero || (!(leafL && leafR) && (lmax < kScalingThresholdHi) && (invar == 0.0) && rule != 1);
+            lmax = group_max_u(promote_nonzero(rule, nz, lmax));
+            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lmax, invar);
             double my_scale = 0.0;
-            if (__any(do_scale)) {
-                if (do_scale) {
-                    if (zero) for (int e = g; e < B; e += 4) dst[(size_t)e * 16 + p] = A.tipc[(size_t)A.state_unknown * B + e];
+            if (__any(ch.scale)) {
+                if (ch.scale) {
+                    if (ch.zero) for (int e = g; e < B; e += 4) dst[(size_t)e * 16 + p] = A.tipc[(size_t)A.state_unknown * B + e];
                     else for (int e = g; e < B; e += 4) dst[(size_t)e * 16 + p] *= kScalingThresholdInv;
-                    sc += zero ? 4 : 1;
-                    if (g == 0 && ptn < A.nptn) my_scale = (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq);
+                    sc += ch.events();
+                    if (g == 0 && ptn < A.nptn) my_scale = ch.events() * (kLogScalingThreshold * freq);
                 }
             }
             if (g == 0) op.dst_sc[ptn] = (int16_t)sc;
-            const double ws = __any(my_scale != 0.0) ? wave_sum_m(my_scale) : 0.0;  // (no rescaling in this op: nothing to add)
-            if (lane == 0) {
-                A.slab[(size_t)(2 + op.out_row) * A.nwaves + (int)tl] = ws;
-                if (ws != 0.0) __hip_atomic_fetch_or(&A.fold_flags[2 + op.out_row], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            post_scale_sum(A.slab, A.fold_flags, op.out_row, A.nwaves, tl, lane == 0, my_scale);
         }
     }
 }
@@ -603,13 +594,9 @@ __device__ __forceinline__ void trav_mfma2_body(const TravMArgs &A, const int vb
         // 0.943 ms.  The 64-state kernel keeps the plain form: with the staging it spills 30 registers instead of 18, 0.334 ->
         // 0.349 ms.)
         if constexpr (N >= 64) {
-            for (int t = threadIdx.x; t < kn * 2 * B; t += WG) {
-                const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-                const CONST_AS DevOp &d = ops[k + o];
-                if (TAB && (child ? d.right_kind : d.left_kind) == CHILD_LEAF) continue;  // a table child needs no exponentials
-                const double len = op_child_len(d, child);
-                sReg[(child ? d.lds_right : d.lds_left) + e] = exp(A.eval[e % N] * (A.rates[e / N] * len));
-            }
+            fill_exponentials<WG>(ops, k, kn, B, sReg, [ev = A.eval](int e) { return ev[e % N]; }, [rt = A.rates](int e) { return rt[e / N]; },
+                                  [](const CONST_AS DevOp &d, int child) {   // a table child needs no exponentials
+                                      return TAB && (child ? d.right_kind : d.left_kind) == CHILD_LEAF; });
         } else
         for (int o0 = 0; o0 < kn; o0 += 64) {
             const int on = kn - o0 < 64 ? kn - o0 : 64;
@@ -970,8 +957,8 @@ __device__ __forceinline__ void trav_mfma2_body(const TravMArgs &A, const int vb
                 TRACE_STAMP();   // contraction done, stores issued
             }
             }   // (!from_table)
+            unsigned nz = 0;
             if (no_scale == 2 && lmax == 0) {   // scalar rule: exactly zero, or only below 2^-1042?
-                unsigned nz = 0;
 #pragma unroll
                 for (int c = 0; c < C; c++) {
 #pragma unroll
@@ -980,31 +967,23 @@ __device__ __forceinline__ void trav_mfma2_body(const TravMArgs &A, const int vb
                         for (int r = 0; r < 4; r++) nz |= nonzero_bits(prev[c][m][r]);
                     if (TAIL4) nz |= nonzero_bits(prevT[c]);
                 }
-                if (nz) lmax = 1;
             }
-            lmax = group_max_u(lmax);
+            lmax = group_max_u(promote_nonzero(no_scale, nz, lmax));
             if constexpr (CS > 1) {
-                // maximum over the categories held by the other waves of this tile (LDS + one workgroup barrier per op; a
-                // barrier-free exchange -- maxima posted with tags, a wave waits for its partners only when it has a candidate
-                // pattern -- was measured equal, 199 vs 197 us for the top stage, and is not worth its moving parts)
+                // maximum over the categories held by the other waves of this tile (tile_max: LDS + one workgroup barrier per
+                // op; a barrier-free exchange -- maxima posted with tags, a wave waits for its partners only when it has a
+                // candidate pattern -- was measured equal, 199 vs 197 us for the top stage, and is not worth its moving parts)
                 __shared__ unsigned s_lmax[2][WG / 64][16];
-                const int par = k & 1;
-                if (g == 0) s_lmax[par][wave][p] = lmax;
-                __syncthreads();
-                const int w0 = (wave / CS) * CS;
-#pragma unroll
-                for (int q = 0; q < CS; q++) lmax = max(lmax, s_lmax[par][w0 + q][p]);
+                lmax = tile_max<CS>(s_lmax, k & 1, wave, p, g, lmax);
             }
 #if defined(IQHIP_MFMA_ABLATE_NOLOAD) || defined(IQHIP_MFMA_ABLATE_NOSTORE)
-            const bool zero = false;
-            const bool do_scale = lmax == 0xffffffffu;  // (garbage inputs must not take the rescaling path in a timing build)
+            const ScaleChoice ch = {false, lmax == 0xffffffffu};  // (garbage inputs must not take the rescaling path in a timing build)
 #else
-            const bool zero = no_scale == 2 && !(leafL && leafR) && lmax == 0;   // the scalar kernel's `lh_max == 0.0`, phylotreesse.cpp:777-788
-            const bool do_scale = zero || (!(leafL && leafR) && (lmax < kScalingThresholdHi) && (invar == 0.0) && no_scale != 1);
+            const ScaleChoice ch = scale_choice(no_scale, leafL && leafR, lmax, invar);
 #endif
             double my_scale = 0.0;
-            if (__any(do_scale)) {
-                if (do_scale) {
+            if (__any(ch.scale)) {
+                if (ch.scale) {
 #pragma unroll
                     for (int c = 0; c < C; c++) {
                         const double *tu = A.tipc + ((size_t)A.state_unknown * CT + coff + c) * N;   // unknown tip, this category
@@ -1012,30 +991,26 @@ __device__ __forceinline__ void trav_mfma2_body(const TravMArgs &A, const int vb
                         for (int m = 0; m < MTF; m++)
 #pragma unroll
                             for (int r = 0; r < 4; r++) {
-                                if (zero) prev[c][m][r] = tu[16 * m + 4 * r + g]; else
+                                if (ch.zero) prev[c][m][r] = tu[16 * m + 4 * r + g]; else
                                 prev[c][m][r] *= kScalingThresholdInv;
                                 dst[(size_t)((coff + c) * N + 16 * m + 4 * r + g) * 16 + p] = prev[c][m][r];
                                 if (HOLDS && push) hold[((coff + c) * N + 16 * m + 4 * r) * 16] = prev[c][m][r];
                             }
                         if (TAIL4) {
-                            if (zero) prevT[c] = tu[16 * MTF + g]; else
+                            if (ch.zero) prevT[c] = tu[16 * MTF + g]; else
                             prevT[c] *= kScalingThresholdInv;
                             dst[(size_t)((coff + c) * N + 16 * MTF + g) * 16 + p] = prevT[c];
                             if (HOLDS && push) hold[((coff + c) * N + 16 * MTF) * 16] = prevT[c];
                         }
                     }
-                    sc += zero ? 4 : 1;
-                    if (lead && g == 0 && ptn < A.nptn) my_scale = (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq);
+                    sc += ch.events();
+                    if (lead && g == 0 && ptn < A.nptn) my_scale = ch.events() * (kLogScalingThreshold * freq);
                 }
             }
             prev_sc = sc;
             if (HOLDS && push) hold_sc = sc;
             if (lead && g == 0) dst_sc[ptn] = (int16_t)sc;
-            const double ws = __any(my_scale != 0.0) ? wave_sum_m(my_scale) : 0.0;  // (no rescaling in this op: nothing to add)
-            if (lead && lane == 0) {
-                A.slab[(size_t)(2 + out_row) * A.nwaves + (int)tl] = ws;
-                if (ws != 0.0) __hip_atomic_fetch_or(&A.fold_flags[2 + out_row], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            post_scale_sum(A.slab, A.fold_flags, out_row, A.nwaves, tl, lead && lane == 0, my_scale);
         }
     }
     TRACE_END();
@@ -1097,12 +1072,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse_mfma_mix20(const TravMArgs A
     while (k < k_end) {
         const int kn = ops[k].chunk_nops;
         __syncthreads();
-        for (int t = threadIdx.x; t < kn * 2 * B; t += WG) {
-            const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-            const CONST_AS DevOp &d = ops[k + o];
-            const double len = op_child_len(d, child);
-            sReg[(child ? d.lds_right : d.lds_left) + e] = exp(A.evalc[e] * (A.rates[e / N] * len));
-        }
+        fill_exponentials<WG>(ops, k, kn, B, sReg, [ev = A.evalc](int e) { return ev[e]; }, [rt = A.rates](int e) { return rt[e / N]; },
+                              FillAll{});
         __syncthreads();
         if (!active) { k += kn; continue; }
 
@@ -1180,35 +1151,24 @@ __global__ __launch_bounds__(WG, 2) void k_traverse_mfma_mix20(const TravMArgs A
                 lmax = amax_hi(lmax, o4);
                 if (op.no_scale == 2) nz |= nonzero_bits(O[0]) | nonzero_bits(O[1]) | nonzero_bits(O[2]) | nonzero_bits(O[3]) | nonzero_bits(o4);
             }
-            if (nz != 0 && lmax == 0) lmax = 1;   // (scalar rule: only an exact zero takes its lh_max == 0 branch)
-            lmax = group_max_u(lmax);
+            const int rule = op.no_scale;
+            lmax = group_max_u(promote_nonzero(rule, nz, lmax));
             if constexpr (CS > 1) {
                 __shared__ unsigned s_lmax[2][WG / 64][16];
-                const int par = k & 1;
-                if (g == 0) s_lmax[par][wave][p] = lmax;
-                __syncthreads();
-                const int w0 = (wave / CS) * CS;
-#pragma unroll
-                for (int q = 0; q < CS; q++) lmax = max(lmax, s_lmax[par][w0 + q][p]);
+                lmax = tile_max<CS>(s_lmax, k & 1, wave, p, g, lmax);
             }
-            const int rule = op.no_scale;
-            const bool zero = rule == 2 && !(leafL && leafR) && lmax == 0;   // the scalar kernel's `lh_max == 0.0`, phylotreesse.cpp:777-788
-            const bool do_scale = zero || (!(leafL && leafR) && (lmax < kScalingThresholdHi) && (invar == 0.0) && rule != 1);
+            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lmax, invar);
             double my_scale = 0.0;
-            if (__any(do_scale)) {
-                if (do_scale) {
-                    if (zero) for (int e = c_lo * N + g; e < c_hi * N; e += 4) dst[(size_t)e * 16 + p] = A.tipc[(size_t)A.state_unknown * B + e];
+            if (__any(ch.scale)) {
+                if (ch.scale) {
+                    if (ch.zero) for (int e = c_lo * N + g; e < c_hi * N; e += 4) dst[(size_t)e * 16 + p] = A.tipc[(size_t)A.state_unknown * B + e];
                     else for (int e = c_lo * N + g; e < c_hi * N; e += 4) dst[(size_t)e * 16 + p] *= kScalingThresholdInv;
-                    sc += zero ? 4 : 1;
-                    if (lead && g == 0 && ptn < A.nptn) my_scale = (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq);
+                    sc += ch.events();
+                    if (lead && g == 0 && ptn < A.nptn) my_scale = ch.events() * (kLogScalingThreshold * freq);
                 }
             }
             if (lead && g == 0) op.dst_sc[ptn] = (int16_t)sc;
-            const double ws = __any(my_scale != 0.0) ? wave_sum_m(my_scale) : 0.0;  // (no rescaling in this op: nothing to add)
-            if (lead && lane == 0) {
-                A.slab[(size_t)(2 + op.out_row) * A.nwaves + (int)tl] = ws;
-                if (ws != 0.0) __hip_atomic_fetch_or(&A.fold_flags[2 + op.out_row], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            post_scale_sum(A.slab, A.fold_flags, op.out_row, A.nwaves, tl, lead && lane == 0, my_scale);
         }
     }
 }
@@ -1276,12 +1236,7 @@ __device__ __forceinline__ void trav_rows64_body(const TravMArgs &A, const int v
     while (k < k_end) {
         const int kn = ops[k].chunk_nops;
         __syncthreads();
-        for (int t = threadIdx.x; t < kn * 2 * B; t += WG) {
-            const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-            const CONST_AS DevOp &d = ops[k + o];
-            const double len = op_child_len(d, child);
-            sReg[(child ? d.lds_right : d.lds_left) + e] = exp(A.eval[e] * (A.rates[0] * len));
-        }
+        fill_exponentials<WG>(ops, k, kn, B, sReg, [ev = A.eval](int e) { return ev[e]; }, [rt = A.rates](int) { return rt[0]; }, FillAll{});
         __syncthreads();
         if (!active) { k += kn; continue; }
 
@@ -1355,34 +1310,26 @@ __device__ __forceinline__ void trav_rows64_body(const TravMArgs &A, const int v
             }
             prev = O;
             const int rule = op.no_scale;
-            if (rule == 2 && lmax == 0 && (nonzero_bits(O[0]) | nonzero_bits(O[1]) | nonzero_bits(O[2]) | nonzero_bits(O[3])) != 0)
-                lmax = 1;   // (scalar rule: only an exact zero takes its lh_max == 0 branch)
-            lmax = group_max_u(lmax);
-            if (g == 0) s_lmax[par][wave][p] = lmax;
-            __syncthreads();
-            lmax = max(max(s_lmax[par][0][p], s_lmax[par][1][p]), max(s_lmax[par][2][p], s_lmax[par][3][p]));
-            const bool zero = rule == 2 && !(leafL && leafR) && lmax == 0;   // the scalar kernel's `lh_max == 0.0`, phylotreesse.cpp:777-788
-            const bool do_scale = zero || (!(leafL && leafR) && (lmax < kScalingThresholdHi) && (invar == 0.0) && rule != 1);
+            const unsigned nz = (rule == 2 && lmax == 0) ? (nonzero_bits(O[0]) | nonzero_bits(O[1]) | nonzero_bits(O[2]) | nonzero_bits(O[3])) : 0u;
+            lmax = group_max_u(promote_nonzero(rule, nz, lmax));
+            lmax = tile_max<4>(s_lmax, par, wave, p, g, lmax);   // (the third workgroup barrier of the op)
+            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lmax, invar);
             double my_scale = 0.0;
-            if (__any(do_scale)) {
-                if (do_scale) {
+            if (__any(ch.scale)) {
+                if (ch.scale) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
-                        if (zero) prev[r] = A.tipc[(size_t)A.state_unknown * 64 + 16 * wave + 4 * r + g]; else
+                        if (ch.zero) prev[r] = A.tipc[(size_t)A.state_unknown * 64 + 16 * wave + 4 * r + g]; else
                         prev[r] *= kScalingThresholdInv;
                         dst[(size_t)(16 * wave + 4 * r + g) * 16 + p] = prev[r];
                     }
-                    sc += zero ? 4 : 1;
-                    if (lead && g == 0 && ptn < A.nptn) my_scale = (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq);
+                    sc += ch.events();
+                    if (lead && g == 0 && ptn < A.nptn) my_scale = ch.events() * (kLogScalingThreshold * freq);
                 }
             }
             prev_sc = sc;
             if (lead && g == 0) op.dst_sc[ptn] = (int16_t)sc;
-            const double ws = __any(my_scale != 0.0) ? wave_sum_m(my_scale) : 0.0;  // (no rescaling in this op: nothing to add)
-            if (lead && lane == 0) {
-                A.slab[(size_t)(2 + op.out_row) * A.nwaves + (int)tl] = ws;
-                if (ws != 0.0) __hip_atomic_fetch_or(&A.fold_flags[2 + op.out_row], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            post_scale_sum(A.slab, A.fold_flags, op.out_row, A.nwaves, tl, lead && lane == 0, my_scale);
         }
     }
     TRACE_END();
@@ -1665,14 +1612,14 @@ __global__ __launch_bounds__(256) void k_stream_mfma(const StreamMArgs A) {
         const double inv = 1.0 / fabs(lhi);
         const double dfp = d1 * inv;
         const double ddfp = fma(-dfp, dfp, d2 * inv);
-        const double wa = wave_sum_m(mine ? dfp * f : 0.0), wb = wave_sum_m(mine ? ddfp * f : 0.0);
+        const double wa = wave_sum64(mine ? dfp * f : 0.0), wb = wave_sum64(mine ? ddfp * f : 0.0);
         if (lane == 0) {
             fold_store(&slab[tile], wa);
             fold_store(&slab[(size_t)A.nwaves + tile], wb);
         }
         if (asc || A.task_rows == 5) {  // phylokernel.h:655-725 (a batched +ASC engine without unobserved patterns: zeros)
-            const double w2 = wave_sum_m(unobs ? lhi : 0.0), w3 = wave_sum_m(unobs ? d1 : 0.0),
-                         w4 = wave_sum_m(unobs ? d2 : 0.0);
+            const double w2 = wave_sum64(unobs ? lhi : 0.0), w3 = wave_sum64(unobs ? d1 : 0.0),
+                         w4 = wave_sum64(unobs ? d2 : 0.0);
             if (lane == 0) {
                 slab[(size_t)2 * A.nwaves + tile] = w2;
                 slab[(size_t)3 * A.nwaves + tile] = w3;
@@ -1689,8 +1636,8 @@ __global__ __launch_bounds__(256) void k_stream_mfma(const StreamMArgs A) {
         }
         const double plh = log(fabs(lh + iv));
         if (g == 0 && A.pattern_lh) A.pattern_lh[ptn] = plh;
-        const double wa = wave_sum_m(mine ? plh * f : 0.0);
-        const double wpc = asc ? wave_sum_m(pc) : 0.0;
+        const double wa = wave_sum64(mine ? plh * f : 0.0);
+        const double wpc = asc ? wave_sum64(pc) : 0.0;
         if (lane == 0) {
             fold_store(&slab[tile], wa);
             fold_store(&slab[(size_t)A.nwaves + tile], wpc);

@@ -14,10 +14,12 @@
 // the steps in order, keeps the accepted lengths in LDS, and the host reads one result block at the end.
 //
 // Arithmetic: the node update, theta and the derivative sums are the expressions of k_traverse4 / k_theta4 / k_newton
-// term for term (same association, same fixed-order reductions over the same tile -> wave -> workgroup assignment), so
+// term for term (same association, same fixed-order reductions over the same tile -> wave -> workgroup assignment; the
+// scaling decision and the K2 table entry are the same code, trav_phases.h), so
 // a sweep accepts the same lengths, to the last bit, as the one-submission-per-branch form; tests/test_sweep_gpu.py
 // checks exactly that and re-evaluates the optimised tree with the oracle.
 #include "iqhip_internal.h"
+#include "trav_phases.h"
 #include "wg_exchange.h"
 
 namespace iqhip {
@@ -123,21 +125,20 @@ __device__ __forceinline__ void sweep_node_update(const CONST_AS SweepOp &op, co
             lh_max = fmax(lh_max, fabs(o));
         }
     }
-    // scaling (SIMD rule, phylokernel.h:379-392, 461-474); TIP-TIP never scales
-    // (the last update of a multifurcating node: the scalar kernel's rule, lh_max == 0 first, phylotreesse.cpp:774-788)
-    const int rule = op.no_scale;
-    const bool zero = rule == 2 && !(leafL && leafR) && lh_max == 0.0;   // (TIP-TIP never scales)
-    const bool do_scale = zero || (!(leafL && leafR) && (lh_max < kScalingThreshold) && (invar_p[ptn] == 0.0) && rule != 1);
-    if (do_scale) {
-        if (zero) {
+    // scaling (trav_phases.h).  The invariant-site term is read only for a pattern the rule can ask about it: read for every
+    // pattern it costs k_sweep4<1, true, 4> its third wave per SIMD (168 -> 169 registers) and k_sweep4<5, true> two spills.
+    const bool tip_tip = leafL && leafR;
+    const ScaleChoice ch = scale_choice(op.no_scale, tip_tip, lh_max, (!tip_tip && lh_max < kScalingThreshold) ? invar_p[ptn] : 1.0);
+    if (ch.scale) {
+        if (ch.zero) {
 #pragma unroll
             for (int e = 0; e < B; e++) out[e] = s_tip[state_unknown * 4 + (e & 3)];
         } else {
 #pragma unroll
             for (int e = 0; e < B; e++) out[e] *= kScalingThresholdInv;
         }
-        sc += zero ? 4 : 1;
-        if (ptn < nptn) scale_acc += (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq_p[ptn]);
+        sc += ch.events();
+        if (ptn < nptn) scale_acc += ch.events() * (kLogScalingThreshold * freq_p[ptn]);
     }
     double2 *d = reinterpret_cast<double2 *>(op.dst + tile * (64 * B)) + lane;
 #pragma unroll
@@ -218,17 +219,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_sweep4(const SweepArgs A) {
                 if ((childi ? op.rv : op.lv) != nullptr) continue;
                 const int row = q / B, e = q - row * B, c = e >> 2, x = e & 3;
                 const double *ex = s_ex + childi * B;
-                double v = 1.0;
-                if (row < 4) {
-                    const double e0 = __dmul_rn(s_evec[x * 4 + 0], ex[c * 4 + 0]);
-                    const double e1 = __dmul_rn(s_evec[x * 4 + 1], ex[c * 4 + 1]);
-                    const double e2 = __dmul_rn(s_evec[x * 4 + 2], ex[c * 4 + 2]);
-                    const double e3 = __dmul_rn(s_evec[x * 4 + 3], ex[c * 4 + 3]);
-                    const double *tp = s_tip + row * 4;
-                    v = __dadd_rn(__dadd_rn(__dmul_rn(e0, tp[0]), __dmul_rn(e1, tp[1])),
-                                  __dadd_rn(__dmul_rn(e2, tp[2]), __dmul_rn(e3, tp[3])));
-                }
-                s_tab[t] = v;
+                s_tab[t] = row < 4 ? leaf_entry4(s_evec + x * 4, ex + c * 4, s_tip + row * 4) : 1.0;
             }
             __syncthreads();
             double scale_acc = 0.0;

@@ -12,11 +12,12 @@
 //
 // Reference semantics restated here (file:line are /root/reference paths):
 //   node update     phylokernel.h:183-479   (TIP-TIP / TIP-INTERNAL / INTERNAL-INTERNAL)
-//   scaling rule    phylokernel.h:379-392,461-474  (SIMD rule: *2^256, scale_num+1)
+//   scaling rule    phylokernel.h:379-392,461-474  (SIMD rule: *2^256, scale_num+1; trav_phases.h, as the K2 table entry)
 //   branch lnL      phylokernel.h:779-966
 //   theta / derv    phylokernel.h:516-651
 //   lnL from theta  phylokernel.h:1040-1099
 #include "iqhip_internal.h"
+#include "trav_phases.h"
 
 namespace iqhip {
 
@@ -374,17 +375,9 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                 const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B, c = e >> 2, x = e & 3;
                 if (!s_opi[o][2 + child]) continue;
                 double *reg = s_reg + s_opi[o][child];
-                // E = U*ex rounded first, then the reference's (t0+t1)+(t2+t3), all unfused
-                const double e0 = __dmul_rn(s_model[x * 4 + 0], reg[c * 4 + 0]);
-                const double e1 = __dmul_rn(s_model[x * 4 + 1], reg[c * 4 + 1]);
-                const double e2 = __dmul_rn(s_model[x * 4 + 2], reg[c * 4 + 2]);
-                const double e3 = __dmul_rn(s_model[x * 4 + 3], reg[c * 4 + 3]);
+                const LeafE4 E = leaf_e4(s_model + x * 4, reg + c * 4);   // (trav_phases.h: rounding and association)
 #pragma unroll
-                for (int row = 0; row < 4; row++) {
-                    const double *tp = s_tip + row * 4;
-                    reg[B + row * B + e] = __dadd_rn(__dadd_rn(__dmul_rn(e0, tp[0]), __dmul_rn(e1, tp[1])),
-                                                     __dadd_rn(__dmul_rn(e2, tp[2]), __dmul_rn(e3, tp[3])));
-                }
+                for (int row = 0; row < 4; row++) reg[B + row * B + e] = E.entry(s_tip + row * 4);
                 reg[B + 4 * B + e] = 1.0;
             }
         }
@@ -473,23 +466,21 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                                                           s_tip, U, uinv, sL, sR, A.state_unknown, nx_pf, dstp, coff, PF, HOLD, prev);
             if (SP == 2) lh_max = fmax(lh_max, __shfl_xor(lh_max, 32, 64));  // both category halves of the pattern
             [[maybe_unused]] const unsigned long long c3 = T4_CLK() + (lh_max == -1.0 ? 1 : 0);   // (after the update's results exist)
-            // ---- scaling (SIMD rule, phylokernel.h:379-392,461-474); TIP-TIP never scales
-            // (the last update of a multifurcating node carries the scalar kernel's rule: lh_max == 0 first, phylotreesse.cpp:774-788)
-            const bool zero = rule == 2 && !(leafL && leafR) && lh_max == 0.0;   // (TIP-TIP never scales, scalar kernel :807-843)
-            const bool do_scale = zero || (!(leafL && leafR) && (lh_max < kScalingThreshold) && (invar == 0.0) && rule != 1);
+            // ---- scaling: the decision is trav_phases.h's, the rewrite of the registers and the fold_store form this kernel's
+            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lh_max, invar);
             double my_scale = 0.0;
-            const unsigned long long any = __ballot(do_scale);
+            const unsigned long long any = __ballot(ch.scale);
             if (__builtin_expect(any != 0, 0)) {  // rare, wave-uniform
-                if (do_scale) {
-                    if (zero) {   // "very shitty data": the unknown tip's vector in every category, four scaling events
+                if (ch.scale) {
+                    if (ch.zero) {   // "very shitty data": the unknown tip's vector in every category, four scaling events
 #pragma unroll
                         for (int e = 0; e < BL; e++) prev[e] = s_tip[A.state_unknown * 4 + (e & 3)];
                     } else {
 #pragma unroll
                         for (int e = 0; e < BL; e++) prev[e] *= kScalingThresholdInv;
                     }
-                    sc += zero ? 4 : 1;
-                    my_scale = (lead && ptn < A.nptn) ? (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq) : 0.0;
+                    sc += ch.events();
+                    my_scale = (lead && ptn < A.nptn) ? ch.events() * (kLogScalingThreshold * freq) : 0.0;
 #ifndef IQHIP_ABLATE_NOSTORE
                     store_vec4_off<CL>(op->dst, voff, prev);
 #endif

@@ -19,10 +19,12 @@
 //     path that evaluates E*tip on the fly;
 //   * scaling is the rule of the matrix-core kernels: per-pattern maximum over the whole block on the high words, the four
 //     groups combined with the permlane swaps; the vector is stored unscaled per category and stored again in the rare
-//     rescale; IQHIP_OP_SCALAR_RULE's lh_max == 0 branch writes the tip row of STATE_UNKNOWN.
+//     rescale (IQHIP_OP_SCALAR_RULE's lh_max == 0 branch: the tip row of STATE_UNKNOWN).  The decision, the posting of the
+//     sum_scale partial, the fill of the exponentials and the leaf-table entry are trav_phases.h's.
 // The descriptors are TRAV_GENERIC's (pf = left, ld = right, chunks, segments); patterns are independent, so there is no
 // exchange between workgroups.
 #include "iqhip_internal.h"
+#include "trav_phases.h"
 
 namespace iqhip {
 
@@ -199,31 +201,20 @@ __global__ __launch_bounds__(kTravWg) void k_traverse4w(const Trav4wArgs A) {
         const int kn = as_const(A.ops)[k].chunk_nops;
         __syncthreads();
         // phase 1: the exponentials of every (op, child) of the chunk
-        for (int t = threadIdx.x; t < kn * 2 * B; t += kTravWg) {
-            const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-            const CONST_AS DevOp &d = as_const(A.ops)[k + o];
-            const double len = op_child_len(d, child);
-            sReg[(child ? d.lds_right : d.lds_left) + e] = exp(A.evalc[e] * (A.rates[e >> 2] * len));
-        }
+        fill_exponentials<kTravWg>(as_const(A.ops), k, kn, B, sReg, [ev = A.evalc](int e) { return ev[e]; },
+                                   [rt = A.rates](int e) { return rt[e >> 2]; }, FillAll{});
         __syncthreads();
-        // phase 2: the leaf tables (K2).  One item = one (op, child, category, x): E = U[x][.] * ex rounded first, then the
-        // reference's (t0 + t1) + (t2 + t3), all unfused; the fifth row, STATE_UNKNOWN, is exactly 1.0
+        // phase 2: the leaf tables (K2).  One item = one (op, child, category, x): leaf_e4's four rounded products serve the
+        // four state rows; the fifth row, STATE_UNKNOWN, is exactly 1.0
         for (int t = threadIdx.x; t < kn * 2 * B; t += kTravWg) {
             const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B, c = e >> 2, x = e & 3;
             const CONST_AS DevOp &d = as_const(A.ops)[k + o];
             if ((child ? d.right_kind : d.left_kind) != CHILD_LEAF) continue;
             double *reg = sReg + (child ? d.lds_right : d.lds_left);
             const double *W = sW + 32 * (MIX ? A.cls[c] : 0);
-            const double e0 = __dmul_rn(W[x * 4 + 0], reg[c * 4 + 0]);
-            const double e1 = __dmul_rn(W[x * 4 + 1], reg[c * 4 + 1]);
-            const double e2 = __dmul_rn(W[x * 4 + 2], reg[c * 4 + 2]);
-            const double e3 = __dmul_rn(W[x * 4 + 3], reg[c * 4 + 3]);
+            const LeafE4 E = leaf_e4(W + x * 4, reg + c * 4);
 #pragma unroll
-            for (int row = 0; row < 4; row++) {
-                const double *tp = sTipc + row * B + c * 4;
-                reg[B + row * B + e] = __dadd_rn(__dadd_rn(__dmul_rn(e0, tp[0]), __dmul_rn(e1, tp[1])),
-                                                 __dadd_rn(__dmul_rn(e2, tp[2]), __dmul_rn(e3, tp[3])));
-            }
+            for (int row = 0; row < 4; row++) reg[B + row * B + e] = E.entry(sTipc + row * B + c * 4);
             reg[B + 4 * B + e] = 1.0;
         }
         __syncthreads();
@@ -267,33 +258,27 @@ __global__ __launch_bounds__(kTravWg) void k_traverse4w(const Trav4wArgs A) {
             // pattern maximum over the 4 lane groups (lmax orders the high words; a denormal below 2^-1042 still counts as
             // non-zero for the scalar rule's exact test)
             const int rule = op.no_scale;
-            if (rule == 2 && nz != 0 && lmax == 0) lmax = 1;
-            lmax = group_max_u(lmax);
-            const bool zero = rule == 2 && !(leafL && leafR) && lmax == 0;   // the scalar kernel's `lh_max == 0.0`, phylotreesse.cpp:777-788
-            const bool do_scale = zero || (!(leafL && leafR) && (lmax < kScalingThresholdHi) && (invar == 0.0) && rule != 1);
+            lmax = group_max_u(promote_nonzero(rule, nz, lmax));
+            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lmax, invar);
             double my_scale = 0.0;
-            if (__any(do_scale)) {
-                if (do_scale) {
+            if (__any(ch.scale)) {
+                if (ch.scale) {
 #pragma unroll
                     for (int j = 0; j < CL; j++)
 #pragma unroll
                         for (int i = 0; i < 4; i++) {
-                            const double v = zero ? A.tipc[(size_t)A.state_unknown * B + cc[j] * 4 + i] : prev[4 * j + i] * kScalingThresholdInv;
+                            const double v = ch.zero ? A.tipc[(size_t)A.state_unknown * B + cc[j] * 4 + i] : prev[4 * j + i] * kScalingThresholdInv;
                             prev[4 * j + i] = v;
                             if (g + 4 * j < C) *reinterpret_cast<double *>(dst + voff[j] + i * 128) = v;
                         }
-                    sc += zero ? 4 : 1;
-                    if (g == 0 && ptn < A.nptn) my_scale = (zero ? 4.0 : 1.0) * (kLogScalingThreshold * freq);
+                    sc += ch.events();
+                    if (g == 0 && ptn < A.nptn) my_scale = ch.events() * (kLogScalingThreshold * freq);
                 }
             }
             if (g == 0) op.dst_sc[ptn] = (int16_t)sc;
             prev_sc = sc;
             prev_dst = op.dst;
-            const double ws = __any(my_scale != 0.0) ? wave_sum64(my_scale) : 0.0;  // (no rescaling in this op: nothing to add)
-            if (lane == 0) {
-                A.slab[(size_t)(2 + op.out_row) * A.nwaves + (int)tl] = ws;
-                if (ws != 0.0) __hip_atomic_fetch_or(&A.fold_flags[2 + op.out_row], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            post_scale_sum(A.slab, A.fold_flags, op.out_row, A.nwaves, tl, lane == 0, my_scale);
         }
     }
 }

@@ -95,7 +95,8 @@ def test_scalar_kernel_zero_rule_at_a_multifurcating_node(pkg, synth, oracle, n,
     through the C ABI: three uploaded child vectors, some patterns of one child exactly zero (and one pattern only
     tiny: a denormal is not zero), the node submitted as the adapter submits a polytomy -- a NO_SCALE intermediate over a
     zero-length branch, then the node's own update with IQHIP_OP_SCALAR_RULE -- against the oracle's restatement of the
-    scalar kernel.  Every traversal kernel family: 4 states (VALU), 20 / 64 states (pipelined, generic), small and
+    scalar kernel.  Two more patterns are equally tiny (below 2^-256, not zero): the one with an invariant-site term is
+    left alone, the other counts one event.  Every traversal kernel family: 4 states (VALU), 20 / 64 states (pipelined, generic), small and
     larger pattern counts (cat-split / row-split variants)."""
     import ctypes as C
     lib = pkg.libiqhip()
@@ -112,10 +113,15 @@ def test_scalar_kernel_zero_rule_at_a_multifurcating_node(pkg, synth, oracle, n,
     kids[1][zero_ptn] = 0.0
     for k in range(3):                                  # pattern 3: every child ~1e-104 -> the product is a denormal (~1e-312):
         kids[k][3] *= 1e-104                            # lh_max is tiny but not 0 -> the ordinary rule (count + 1)
+    tiny_invar, tiny_plain = 5, 9                       # two patterns of the same tiny magnitude (product ~1e-90 < 2^-256, not
+    for k in range(3):                                  # zero): one with an invariant-site term -> no event, one without -> one
+        kids[k][tiny_invar] *= 1e-30
+        kids[k][tiny_plain] = kids[k][tiny_invar]
     sc = [rng.integers(0, 3, nptn).astype(np.int16) for _ in range(3)]
     freq = rng.integers(1, 5, nptn).astype(np.float64)
     invar = np.zeros(nptn)
     invar[zero_ptn[0]] = 0.01                           # the zero branch comes before the ptn_invar test
+    invar[tiny_invar] = 0.01                            # ... which then stops the ordinary rule
     lens = np.array([0.11, 0.07, 0.23])
     # oracle: the scalar kernel on the three children
     ot = oracle.OracleTree("(0:0.1,1:0.1,2:0.1);", n, seq_type, np.full((3, nptn), su, dtype=np.uint8), freq, invar, model)
@@ -127,6 +133,9 @@ def test_scalar_kernel_zero_rule_at_a_multifurcating_node(pkg, synth, oracle, n,
         oracle._dp(freq), oracle._dp(invar), oracle._dp(out), oracle._sp(osc))
     assert set(np.nonzero(osc - (sc[0] + sc[1] + sc[2]) == 4)[0]) == set(zero_ptn)
     assert osc[3] - (sc[0][3] + sc[1][3] + sc[2][3]) == 1 and 0.0 < np.abs(out[3]).max() * 2.0 ** -256 < 2.3e-308
+    events = osc - (sc[0] + sc[1] + sc[2])
+    assert events[tiny_invar] == 0 and 0.0 < np.abs(out[tiny_invar]).max() < 2.0 ** -256          # left unscaled
+    assert events[tiny_plain] == 1 and np.array_equal(out[tiny_plain], out[tiny_invar] * 2.0 ** 256)
     # engine
     e = C.c_void_p()
     assert lib.iqhip_create(C.byref(e), 0, n, ncat, nptn, 3) == 0

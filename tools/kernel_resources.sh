@@ -1,5 +1,5 @@
 #!/bin/bash
-# per-kernel register / scratch / occupancy summary of one .hip file (compiler view, gfx950)
+# per-kernel register / scratch / occupancy / LDS summary of one .hip file (compiler view, gfx950)
 # usage: tools/kernel_resources.sh iq-tree_amd/csrc/kernels_mfma.hip [extra hipcc flags]
 set -e -o pipefail   # stop at the first failing step: a faulting kernel must not be followed by more runs on the box
 f=$1; shift
@@ -14,9 +14,12 @@ for line in sys.stdin:
     if k=="Function Name":
         cur={"name":v}; rows.append(cur)
     elif cur is not None: cur[k]=v
+def demangle(name):   # the toolchain demangler, else the system one, else the mangled name
+    for tool in ("/opt/rocm/lib/llvm/bin/llvm-cxxfilt", "c++filt"):
+        try: return subprocess.check_output([tool, name], stderr=subprocess.DEVNULL).decode().strip()
+        except Exception: pass
+    return name
 for r in rows:
-    try: name=subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-cxxfilt",r["name"]]).decode().strip()
-    except Exception: name=r["name"]
-    name=re.sub(r"\(.*","",name)
-    print("%-62s vgpr %-4s agpr %-4s sgpr %-4s scratch %-5s occ %-2s spillV %s" % (name[:62], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs"), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("VGPRs Spill")))
+    name=re.sub(r"^void ","",re.sub(r"\(.*","",demangle(r["name"])))
+    print("%-62s vgpr %-4s agpr %-4s sgpr %-4s scratch %-5s occ %-2s spillV %-3s lds %s" % (name[:62], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs"), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]"), r.get("VGPRs Spill"), r.get("LDS Size [bytes/block]")))
 '
