@@ -68,8 +68,18 @@
 // "UFBoot: K candidate trees, D distinct bootstrap trees", writes <prefix>.suptree (the -te tree with the supports
 // round(100 count / N) as node labels) and <prefix>.contree (the greedy consensus of the winners) and, with -wbt,
 // <prefix>.ufboot: the winner of every replicate in replicate order, topology only, children by ascending smallest taxon.
-// E is params.ufboot_epsilon (0.5).  There is no tree search: what is fed is what the given trees offer.  With -bb a -z
-// file needs no -zb.
+// E is params.ufboot_epsilon (0.5).  Without -search what is fed is what the given trees offer.  With -bb a -z file needs
+// no -zb.
+// With -search (or -t <file> = -te <file> -search) it runs the NNI tree search (TreeSearch, tree_search_host.h =
+// IQTree::doTreeSearch with optimizeNNI) from the starting tree the command line gives (-te, -parstree, -bionjtree) after
+// what comes before it (branch lengths, or -optmodel's estimates: the search takes the model as given): -n N a fixed number
+// of iterations after the starting tree's, else it stops after -numstop N (100) iterations without a better tree; -pers P
+// (0.5) the perturbation strength, -popsize K (5), -nni1 / -nni5, -allnni (every branch in every NNI step), -seed S the
+// search's own random stream.  With -bb N the bootstrap is fed by the search, every evaluated tree as it is evaluated, and
+// the search ends when the split frequencies of the bootstrap trees correlate by -bcor C (0.99) at a multiple of -nstep S
+// (100) and -numstop iterations brought no better tree, or after -nm MAXIT (1000).  It prints "Iteration k / LogL: x" every
+// 10th iteration, "BETTER TREE FOUND at iteration k: x", "NOTE: Bootstrap correlation coefficient of split occurrence
+// frequencies: c" and "Optimal log-likelihood:", and writes <prefix>.treefile.  -search sets LM_ALL_BRANCH.
 // With -q <partition file> (edge-linked, all partition rates 1) or -spp <partition file> (edge-linked, proportional: the
 // rates start at 1 and are estimated) instead of -m it evaluates an edge-linked partition model (PhyloSuperTree,
 // supertree_host.h): the file is RAxML-style, `MODEL, name = 1-100, 250-400, 401-500\3`, MODEL a string in the -m syntax
@@ -104,6 +114,7 @@
 #include "../iq-tree_amd/host/model_opt_host.h"
 #include "../iq-tree_amd/host/phylo_host.h"
 #include "../iq-tree_amd/host/supertree_host.h"
+#include "../iq-tree_amd/host/tree_search_host.h"
 
 using namespace iqhost;
 
@@ -270,6 +281,8 @@ static void usage() {
             "                 [-z <tree set file> -zb <n> [-zw] [-au]] [-mldist <file>] [-pars [-sprrad <r>]] [-emrates] [-wsr]\n"
             "                 [-lmap <n quartets, 0 = all> [-wql]]\n"
             "                 [-mixweights] [-optmodel] [-bb <n> [-beps <e>] [-z <tree set file>] [-wbt]]\n"
+            "                 [-search | -t <newick file>] [-n <iterations>] [-numstop <n>] [-pers <p>] [-popsize <k>] [-nni1|-nni5] [-allnni]\n"
+            "                 (NNI tree search from the starting tree; with -bb <n>: [-bcor <c>] [-nstep <s>] [-nm <max iterations>])\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
@@ -294,6 +307,11 @@ int main(int argc, char **argv) {
     int zb = 0, sprrad = 0, bb = 0;
     double beps = 0.5;
     bool wbt = false;
+    bool search = false, nni5 = true, allnni = false;   // -search: the NNI tree search from the starting tree
+    long long n_iter = -1;
+    bool n_given = false;
+    int numstop = 100, popsize = 5, nstep = 100, nm = 1000;
+    double pers = 0.5, bcor = 0.99;
     bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false, optmodel = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -343,8 +361,36 @@ int main(int argc, char **argv) {
             if (sprrad < 1 || sprrad > IQHIP_PARS_SPR_MAX_RADIUS) { usage(); return 2; }
         }
         else if (a == "-seed") seed = strtoull(next().c_str(), nullptr, 10);
-        else if (a == "-n") next();  // accepted for command-line compatibility (-n 0)
+        else if (a == "-n") {   // with -search / -t: a fixed number of search iterations; else accepted for compatibility (-n 0)
+            char *end = nullptr;
+            const std::string v = next();
+            n_iter = strtoll(v.c_str(), &end, 10);
+            n_given = true;
+            if (v.empty() || *end || n_iter < 0) {
+                fprintf(stderr, "error: -n needs a non-negative number of iterations\n");
+                return 2;
+            }
+        }
+        else if (a == "-search") search = true;
+        else if (a == "-t") { tree_file = next(); search = true; }
+        else if (a == "-numstop") numstop = atoi(next().c_str());
+        else if (a == "-pers") pers = atof(next().c_str());
+        else if (a == "-popsize") popsize = atoi(next().c_str());
+        else if (a == "-nni1") nni5 = false;
+        else if (a == "-nni5") nni5 = true;
+        else if (a == "-allnni") allnni = true;
+        else if (a == "-bcor") bcor = atof(next().c_str());
+        else if (a == "-nstep") nstep = atoi(next().c_str());
+        else if (a == "-nm") nm = atoi(next().c_str());
         else { usage(); return 2; }
+    }
+    if (search && model_str.empty() && part_file.empty()) {
+        fprintf(stderr, "error: -search / -t needs a model (-m): the search takes the model as given\n");
+        return 2;
+    }
+    if (search && !part_file.empty()) {
+        fprintf(stderr, "error: -q / -spp cannot be combined with -search / -t (the partition model evaluates a fixed topology)\n");
+        return 2;
     }
     if (!part_file.empty()) {
         const char *with = !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
@@ -371,7 +417,17 @@ int main(int argc, char **argv) {
     if (bb < 0 || !(beps >= 0.0) || (bb == 0 && wbt)) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1 && bb == 0) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
     if (wql && lmap < 0) { usage(); return 2; }
-    if (alrt > 0 || lbp > 0 || bb > 0) all_branch = true;  // the batched NNI evaluation needs every directed vector
+    if (search) {
+        if (numstop < 1 || popsize < 1 || !(pers >= 0.0 && pers <= 1.0) || nstep < 2 || nstep % 2 || nm < 1 || !(bcor >= 0.0 && bcor <= 1.0)) {
+            fprintf(stderr, "error: -numstop, -popsize, -nm need positive numbers, -pers and -bcor values in [0, 1], -nstep an even number >= 2\n");
+            return 2;
+        }
+        if (bb > 0 && !treeset_file.empty() && zb == 0) {
+            fprintf(stderr, "error: with -search the bootstrap is fed by the search, not by -z\n");
+            return 2;
+        }
+    }
+    if (alrt > 0 || lbp > 0 || bb > 0 || search) all_branch = true;  // the batched NNI evaluation needs every directed vector
     try {
         Alignment aln;
         aln.readFile(aln_file, seq_type);
@@ -621,6 +677,46 @@ int main(int argc, char **argv) {
             tree.clearAllPartialLH();
             lnl = tree.computeLikelihood(pattern_lh.data());
         }
+        if (search) {   // IQTree::doTreeSearch from the tree and the model as they stand now
+            if (bb > 0 && (mixture || spec.ascertainment)) throw std::runtime_error("-bb is not available for mixture models and +ASC");
+            TreeSearch ts(&tree);
+            ts.nni5 = nni5;
+            ts.speednni = !allnni;
+            ts.popSize = popsize;
+            ts.initPS = pers;
+            ts.seed = seed;
+            ts.stop_rule.unsuccess_iteration = numstop;
+            ts.stop_rule.stop_condition = n_given ? iqsearch::SC_FIXED_ITERATION : iqsearch::SC_UNSUCCESS_ITERATION;
+            ts.stop_rule.min_iteration = (int)n_iter;
+            if (bb > 0) {   // every tree the search evaluates feeds the bootstrap; the correlation rule ends the search
+                tree.genBootSamples(bb, nsite, seed, 0xA0u);
+                tree.initUFBoot(bb, seed);
+                tree.ufboot_epsilon = beps;
+                ts.stop_rule.stop_condition = iqsearch::SC_BOOTSTRAP_CORRELATION;
+                ts.stop_rule.min_correlation = bcor;
+                ts.stop_rule.max_iteration = n_given ? std::min((int)n_iter, nm) : nm;
+                ts.step_iterations = nstep;
+            }
+            ts.on_iteration = [&](const TreeSearch &s, const TreeSearch::Iteration &it) {
+                if (it.iteration % 10 == 0) printf("Iteration %d / LogL: %.4f\n", it.iteration, it.score);
+                if (it.new_best && it.iteration > 1) printf("BETTER TREE FOUND at iteration %d: %.4f\n", it.iteration, it.score);
+                if (!s.correlation_log.empty() && s.correlation_log.back().first == it.iteration) {
+                    printf("Log-likelihood cutoff on original alignment: %.6f\n", tree.ufboot_logl_cutoff);
+                    printf("NOTE: Bootstrap correlation coefficient of split occurrence frequencies: %g\n", s.correlation_log.back().second);
+                }
+            };
+            auto t0 = std::chrono::steady_clock::now();
+            const long sub0 = tree.num_submissions;
+            ts.doTreeSearch();
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            tree.clearAllPartialLH();
+            lnl = tree.computeLikelihood(pattern_lh.data());
+            printf("Tree search: %d iterations, %d candidate trees, %ld engine submissions: %.4f s\n", ts.stop_rule.cur_iteration,
+                   (int)ts.candidates.size(), tree.num_submissions - sub0, sec);
+            printf("Optimal log-likelihood: %.17g\n", lnl);
+            writeText(prefix + ".treefile", tree.getTreeString() + "\n");
+            printf("Best tree printed to %s.treefile\n", prefix.c_str());
+        }
         double df = 0.0, ddf = 0.0;
         tree.theta_computed = false;
         tree.computeLikelihoodDerv(tree.current_it, tree.current_it_back->node, df, ddf);
@@ -733,11 +829,13 @@ int main(int argc, char **argv) {
             std::vector<std::string> newicks;
             if (!treeset_file.empty()) newicks = readTreeSet(treeset_file);
             auto t0 = std::chrono::steady_clock::now();
-            tree.genBootSamples(bb, nsite, seed, 0xA0u);
-            tree.initUFBoot(bb, seed);
-            tree.ufboot_epsilon = beps;
+            if (!search) {
+                tree.genBootSamples(bb, nsite, seed, 0xA0u);
+                tree.initUFBoot(bb, seed);
+                tree.ufboot_epsilon = beps;
+            }
             const std::string te_tree = tree.getTreeString();
-            for (size_t k = 0; k <= newicks.size(); k++) {
+            for (size_t k = 0; !search && k <= newicks.size(); k++) {
                 double cur = lnl;
                 if (k > 0) {
                     tree.readTreeString(newicks[k - 1], aln.seq_names);
@@ -758,7 +856,7 @@ int main(int argc, char **argv) {
                 tree.saveCurrentTree(cur);
                 tree.saveNNITrees();
             }
-            if (!newicks.empty()) {   // the supports go onto the -te tree
+            if (!search && !newicks.empty()) {   // the supports go onto the -te tree
                 tree.readTreeString(te_tree, aln.seq_names);
                 tree.initializeAllPartialLh();
             }

@@ -448,6 +448,40 @@ def libiqhost():
     lib.iqhost_ufboot_newick_splits.argtypes = [C.c_char_p, C.c_int, cpp, C.POINTER(C.c_uint64), C.c_int, ipp]
     lib.iqhost_ufboot_split_supports.argtypes = [cpp, C.c_int, i64p, C.c_int, cpp, C.c_char_p, ipp, C.c_int, ipp]
     lib.iqhost_ufboot_consensus.argtypes = [cpp, C.c_int, i64p, C.c_int, cpp, C.c_char_p, C.c_int, ipp]
+    # NNI tree search (search_host.h, tree_search_host.h)
+    u64 = C.c_uint64
+    lib.iqhost_do_nni.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.iqhost_change_nni_brans.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
+    lib.iqhost_do_random_nni.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, ipp]
+    lib.iqhost_save_branch_lengths.argtypes = [vp, dp, C.c_int, ipp]
+    lib.iqhost_restore_branch_lengths.argtypes = [vp, dp, C.c_int]
+    lib.iqhost_evaluate_nnis_list.argtypes = [vp, C.c_int, ipp, C.c_int, C.c_int, ipp, dp, C.c_int, ipp]
+    lib.iqhost_search_sort_moves.argtypes = [dp, C.c_int, ipp]
+    lib.iqhost_search_select_non_conflicting.argtypes = [ipp, C.c_int, ipp, ipp]
+    lib.iqhost_search_branches_for_nni.argtypes = [ipp, C.c_int, ipp, ipp, C.c_int, ipp, C.c_int, ipp]
+    lib.iqhost_search_rand.argtypes = [u64, u64, u64]
+    lib.iqhost_search_rand.restype = u64
+    lib.iqhost_search_rand_int.argtypes = [u64, C.c_int]
+    lib.iqhost_search_stop.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]
+    lib.iqhost_search_bootstrap_correlation.argtypes = [C.c_int, C.c_int, ipp, C.POINTER(u64), i64p, dp]
+    lib.iqhost_candset_create.argtypes = [C.POINTER(vp), C.c_int]
+    lib.iqhost_candset_destroy.argtypes = [vp]
+    lib.iqhost_candset_destroy.restype = None
+    lib.iqhost_candset_update.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, ipp]
+    lib.iqhost_candset_size.argtypes = [vp]
+    lib.iqhost_candset_exists.argtypes = [vp, C.c_char_p]
+    lib.iqhost_candset_best_score.argtypes = [vp]
+    lib.iqhost_candset_best_score.restype = C.c_double
+    lib.iqhost_candset_rand_rank.argtypes = [vp, C.c_int, u64, ipp]
+    lib.iqhost_candset_entry.argtypes = [vp, C.c_int, dp, C.c_char_p, C.c_int, ipp]
+    lib.iqhost_search_create.argtypes = [C.POINTER(vp), vp]
+    lib.iqhost_search_destroy.argtypes = [vp]
+    lib.iqhost_search_destroy.restype = None
+    lib.iqhost_search_set_params.argtypes = [vp, ipp, dp, u64]
+    lib.iqhost_search_optimize_nni.argtypes = [vp, dp, ipp, ipp]
+    lib.iqhost_search_do_random_nnis.argtypes = [vp, C.c_int, u64, ipp, C.c_int, ipp]
+    lib.iqhost_search_do_tree_search.argtypes = [vp, dp]
+    lib.iqhost_search_trace_json.argtypes = [vp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_last_plan.argtypes = [vp, C.POINTER(C.c_int), dp, C.POINTER(C.c_uint64), C.c_int]
     lib.iqhost_num_partial_lh_computations.argtypes = [vp]
     lib.iqhost_num_partial_lh_computations.restype = C.c_long
@@ -667,6 +701,153 @@ def ufboot_rand(seed, tree_id):
 
     z = mix((mix((mix((int(seed) + g * (0xBB + 1)) & m64) + g * (int(tree_id) + 1)) & m64) + g) & m64)
     return (z >> 11) * 2.0 ** -53
+
+
+# ---- NNI tree search: the decisions that need no likelihood (iq-tree_amd/host/search_host.h)
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _move_field(m, key):
+    return m[key] if isinstance(m, dict) else getattr(m, key)
+
+
+def sort_moves(moves):
+    """NNI moves (dicts with newloglh) in descending newloglh; equal scores keep their order (std::stable_sort)."""
+    moves = list(moves)
+    score = np.array([_move_field(m, "newloglh") for m in moves], dtype=np.float64)
+    order = np.zeros(max(len(moves), 1), dtype=np.int32)
+    _hchk(libiqhost().iqhost_search_sort_moves(_dptr(score), len(moves), _iptr(order)))
+    return [moves[int(k)] for k in order[:len(moves)]]
+
+
+def select_non_conflicting(moves):
+    """genNonconfNNIs on moves (dicts with node1, node2) in sorted order: a move is kept unless one of its two nodes is an end
+    of a move already kept."""
+    moves = list(moves)
+    nodes = np.array([[_move_field(m, "node1"), _move_field(m, "node2")] for m in moves], dtype=np.int32).reshape(-1)
+    if not moves:
+        nodes = np.zeros(2, dtype=np.int32)
+    taken = np.zeros(max(len(moves), 1), dtype=np.int32)
+    n = C.c_int()
+    _hchk(libiqhost().iqhost_search_select_non_conflicting(_iptr(nodes), len(moves), _iptr(taken), C.byref(n)))
+    return [moves[int(k)] for k in taken[:n.value]]
+
+
+def branches_for_nni(applied, adjacency):
+    """getBranchesForNNI: per applied move (node1, node2) its branch and the internal branches up to two steps away on
+    either side, each once; adjacency[v] = the neighbours of node v in neighbour order, AFTER the moves were applied."""
+    app = np.array([tuple(a)[:2] for a in applied], dtype=np.int32).reshape(-1)
+    if app.size == 0:
+        app = np.zeros(2, dtype=np.int32)
+    off = np.zeros(len(adjacency) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(a) for a in adjacency])
+    adj = np.array([x for a in adjacency for x in a] or [0], dtype=np.int32)
+    cap = max(int(adj.size), 1)
+    out = np.zeros(2 * cap, dtype=np.int32)
+    n = C.c_int()
+    _hchk(libiqhost().iqhost_search_branches_for_nni(_iptr(app), len(applied), _iptr(off), _iptr(adj), len(adjacency), _iptr(out),
+                                                     cap, C.byref(n)))
+    return [(int(out[2 * q]), int(out[2 * q + 1])) for q in range(n.value)]
+
+
+def search_rand(seed, iteration, draw):
+    """The search's random stream: the 64-bit splitmix value keyed by (seed, iteration, draw index)."""
+    return int(libiqhost().iqhost_search_rand(int(seed), int(iteration), int(draw)))
+
+
+def search_rand_int(z, n):
+    """random_int(n) from a search_rand value: its top 53 bits scaled to [0, n)."""
+    return int(libiqhost().iqhost_search_rand_int(int(z), int(n)))
+
+
+SC_FIXED_ITERATION, SC_UNSUCCESS_ITERATION, SC_BOOTSTRAP_CORRELATION = 0, 1, 2
+
+
+def stop_rule(condition, cur_iteration, cur_correlation=0.0, min_iteration=0, unsuccess_iteration=100, min_correlation=0.99,
+              max_iteration=1000, last_improved=0):
+    """StopRule::meetStopCondition for the three conditions the search uses."""
+    return bool(libiqhost().iqhost_search_stop(int(condition), int(cur_iteration), float(cur_correlation), int(min_iteration),
+                                               int(unsuccess_iteration), float(min_correlation), int(max_iteration),
+                                               int(last_improved)))
+
+
+def bootstrap_correlation(snapshots, ntaxa):
+    """computeBootstrapCorrelation: snapshots = split-count tables {split (iterable of taxon ids): count} in the order they
+    were taken; the table at index (n - 1) // 2 against the last one, a split missing on one side counting 0 there, trivial
+    splits left out; the Pearson correlation.  0.0 with fewer than two snapshots."""
+    wp = (int(ntaxa) + 63) // 64
+    nsplits = np.array([len(s) for s in snapshots] or [0], dtype=np.int32)
+    total = max(int(nsplits.sum()), 1)
+    words = np.zeros((total, wp), dtype=np.uint64)
+    weights = np.zeros(total, dtype=np.int64)
+    at = 0
+    for snap in snapshots:
+        for split, w in snap.items():
+            for t in split:
+                words[at, t >> 6] |= np.uint64(1 << (t & 63))
+            weights[at] = int(w)
+            at += 1
+    out = C.c_double()
+    _hchk(libiqhost().iqhost_search_bootstrap_correlation(int(ntaxa), len(snapshots), _iptr(nsplits),
+                                                          words.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                          weights.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(out)))
+    return out.value
+
+
+class CandidateSet:
+    """candidateset.cpp's set of candidate trees: score -> tree, one entry per topology (the caller's topology string,
+    PhyloTree.sorted_taxon_id_string)."""
+
+    def __init__(self, max_candidates=1000):
+        self.lib = libiqhost()
+        self.h = C.c_void_p()
+        _hchk(self.lib.iqhost_candset_create(C.byref(self.h), int(max_candidates)))
+
+    def close(self):
+        if self.h:
+            self.lib.iqhost_candset_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def update(self, tree, topology, score):
+        """-> True for a new topology; a known one is replaced only by a better score"""
+        new = C.c_int()
+        _hchk(self.lib.iqhost_candset_update(self.h, tree.encode(), topology.encode(), float(score), C.byref(new)))
+        return bool(new.value)
+
+    def __len__(self):
+        return self.lib.iqhost_candset_size(self.h)
+
+    def tree_topology_exist(self, topology):
+        return bool(self.lib.iqhost_candset_exists(self.h, topology.encode()))
+
+    @property
+    def best_score(self):
+        return self.lib.iqhost_candset_best_score(self.h)
+
+    def entry(self, rank):
+        """(score, tree, topology) of the rank-th best tree"""
+        score, need = C.c_double(), C.c_int()
+        _hchk(self.lib.iqhost_candset_entry(self.h, int(rank), C.byref(score), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        _hchk(self.lib.iqhost_candset_entry(self.h, int(rank), C.byref(score), buf, len(buf), C.byref(need)))
+        tree, topo = buf.value.decode().split("\n")
+        return score.value, tree, topo
+
+    def top_trees(self, n=None):
+        return [self.entry(k) for k in range(len(self) if n is None else min(n, len(self)))]
+
+    def rand_cand_rank(self, pop_size, r):
+        """getRandCandTree: the rank drawn by the search_rand value r among the best min(pop_size, size) trees"""
+        rank = C.c_int()
+        _hchk(self.lib.iqhost_candset_rand_rank(self.h, int(pop_size), int(r), C.byref(rank)))
+        return rank.value
 
 
 def _pars_ops(ops):
@@ -1205,35 +1386,84 @@ class PhyloTree:
         self._chk(self.lib.iqhost_nni_for_branch(self.h, a, b, int(nni5), _dptr(out)))
         return [(out[8 * c], int(out[8 * c + 1]), int(out[8 * c + 2]), list(out[8 * c + 3:8 * c + 8])) for c in range(2)]
 
-    def evaluate_nnis_batch(self):
-        """all nni1 candidates (2 per internal branch) in one submission ->
-        list of dict(node1, node2, node1_nei, node2_nei, new_len, newloglh)"""
-        cap = 4 * self.num_nodes
+    def _evaluate_nnis_list(self, nni5, branches, first_row):
+        if branches is None:
+            br, nbr, cap = None, 0, 4 * self.num_nodes
+        else:
+            branches = [tuple(b) for b in branches]
+            br = _iptr(np.array(branches or [(0, 0)], dtype=np.int32).reshape(-1))
+            nbr, cap = len(branches), max(2 * len(branches), 1)
+        w = 6 if nni5 else 2
         ids = np.zeros(4 * cap, dtype=np.int32)
-        vals = np.zeros(2 * cap)
+        vals = np.zeros(w * cap)
         n = C.c_int()
-        self._chk(self.lib.iqhost_evaluate_nnis_batch(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), cap,
-                                                      C.byref(n)))
+        self._chk(self.lib.iqhost_evaluate_nnis_list(self.h, int(nni5), br, nbr, -1 if first_row is None else int(first_row),
+                                                     _iptr(ids), _dptr(vals), cap, C.byref(n)))
+        return ids, vals, n.value
+
+    def evaluate_nnis_batch(self, branches=None):
+        """all nni1 candidates (2 per internal branch) in one submission ->
+        list of dict(node1, node2, node1_nei, node2_nei, new_len, newloglh); branches: only these internal branches
+        [(a, b), ...], in list order, each with the entries the full call gives for it"""
+        ids, vals, n = self._evaluate_nnis_list(False, branches, None)
         return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
                      node2_nei=int(ids[4 * k + 3]), new_len=float(vals[2 * k]), newloglh=float(vals[2 * k + 1]))
-                for k in range(n.value)]
+                for k in range(n)]
 
-    def evaluate_nnis5_batch(self, first_row=None):
+    def evaluate_nnis5_batch(self, first_row=None, branches=None):
         """all nni5 candidates in ten submissions -> list of dict(node1, node2, node1_nei, node2_nei, new_lens[5], newloglh);
-        first_row: candidate k's per-pattern lnL is kept in row first_row + k of the engine's store (ptnlh_fetch)"""
-        cap = 4 * self.num_nodes
-        ids = np.zeros(4 * cap, dtype=np.int32)
-        vals = np.zeros(6 * cap)
-        n = C.c_int()
-        if first_row is None:
-            self._chk(self.lib.iqhost_evaluate_nnis5_batch(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals), cap,
-                                                           C.byref(n)))
-        else:
-            self._chk(self.lib.iqhost_evaluate_nnis5_batch_rows(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), _dptr(vals),
-                                                                cap, C.byref(n), int(first_row)))
+        first_row: candidate k's per-pattern lnL is kept in row first_row + k of the engine's store (ptnlh_fetch);
+        branches: only these internal branches, as evaluate_nnis_batch"""
+        ids, vals, n = self._evaluate_nnis_list(True, branches, first_row)
         return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
                      node2_nei=int(ids[4 * k + 3]), new_lens=[float(x) for x in vals[6 * k:6 * k + 5]],
-                     newloglh=float(vals[6 * k + 5])) for k in range(n.value)]
+                     newloglh=float(vals[6 * k + 5])) for k in range(n)]
+
+    # ---- tree edits of the NNI search (phylo_host.h) and optimizeNNI (tree_search_host.h)
+    def do_nni(self, move, clear_lh=True):
+        """doNNI: the subtrees at move's node1_nei and node2_nei change places wherever they hang on node1 / node2 now, so
+        the same move a second time restores the tree.  move: dict(node1, node2, node1_nei, node2_nei)"""
+        self._chk(self.lib.iqhost_do_nni(self.h, int(move["node1"]), int(move["node2"]), int(move["node1_nei"]),
+                                         int(move["node2_nei"]), int(clear_lh)))
+
+    def change_nni_brans(self, move, nni5=True):
+        """changeNNIBrans: move's new_lens[0] (or new_len) to the central branch; with nni5 new_lens[1..4] to the other branches
+        of node1, then node2, in neighbour order after the swap"""
+        lens = np.zeros(5)
+        if "new_lens" in move:
+            lens[:len(move["new_lens"])] = move["new_lens"]
+        else:
+            lens[0] = move["new_len"]
+        self._chk(self.lib.iqhost_change_nni_brans(self.h, int(move["node1"]), int(move["node2"]), _dptr(lens), int(nni5)))
+
+    def do_random_nni(self, a, b, bit1, bit2):
+        """doOneRandomNNI on the internal branch (a, b) with its two coin flips as arguments -> the move that was made.  No
+        likelihood vector is cleared: clear_all_partial_lh() is the caller's"""
+        out = np.zeros(4, dtype=np.int32)
+        self._chk(self.lib.iqhost_do_random_nni(self.h, int(a), int(b), int(bit1), int(bit2), _iptr(out)))
+        return dict(node1=int(out[0]), node2=int(out[1]), node1_nei=int(out[2]), node2_nei=int(out[3]))
+
+    def save_branch_lengths(self):
+        n = C.c_int()
+        self._chk(self.lib.iqhost_save_branch_lengths(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        self._chk(self.lib.iqhost_save_branch_lengths(self.h, _dptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def restore_branch_lengths(self, lengths):
+        """the lengths of save_branch_lengths back onto the same Neighbor objects (they keep their branch through do_nni);
+        every likelihood vector is stale afterwards: clear_all_partial_lh()"""
+        v = np.ascontiguousarray(lengths, dtype=np.float64)
+        self._chk(self.lib.iqhost_restore_branch_lengths(self.h, _dptr(v), v.size))
+
+    def optimize_nni(self, nni5=True, speed=True, batched=True, trace=False):
+        """compute_likelihood(), then IQTree::optimizeNNI -> (lnL, NNIs applied, steps) or, with trace, (lnL, NNIs applied,
+        steps, [per step dict(branches, all_branches, evaluated, positive, applied, score, rolled_back, submissions)])"""
+        ts = TreeSearch(self, nni5=nni5, speed=speed, batched=batched)
+        try:
+            return ts.optimize_nni(trace=trace)
+        finally:
+            ts.close()
 
     # ---- SH-aLRT / local bootstrap (include/iqhip.h "branch supports")
     def _hip(self, rc):
@@ -1941,6 +2171,117 @@ class PhyloTree:
     @property
     def num_submissions(self):
         return self.lib.iqhost_num_submissions(self.h)
+
+
+def _trace_move(m):
+    return dict(node1=m[0], node2=m[1], node1_nei=m[2], node2_nei=m[3], newloglh=m[4], new_lens=m[5:10])
+
+
+def _trace_steps(steps):
+    for st in steps:
+        st["branches"] = [tuple(b) for b in st["branches"]]
+        for key in ("evaluated", "positive", "applied"):
+            st[key] = [_trace_move(m) for m in st[key]]
+    return steps
+
+
+class TreeSearch:
+    """The NNI tree search on a PhyloTree with an attached engine (iq-tree_amd/host/tree_search_host.h): optimizeNNI and
+    the stochastic loop of doTreeSearch.  iterations: a fixed number of search iterations after the starting tree's
+    (SC_FIXED_ITERATION); None: stop after num_stop iterations without a better tree.  With tree.ufboot_init done before,
+    every evaluated tree feeds the bootstrap and the correlation rule applies: every step_iterations iterations the split
+    frequencies of the bootstrap winners are correlated (correlation_log); the search ends when the correlation reaches
+    min_correlation and num_stop iterations brought no better tree, or after max_iterations (with `iterations` given: after
+    min(iterations, max_iterations))."""
+
+    def __init__(self, tree, seed=0, nni5=True, speed=True, pop_size=5, pers=0.5, iterations=None, num_stop=100, batched=True,
+                 step_iterations=100, min_correlation=0.99, max_iterations=1000):
+        self.lib = libiqhost()
+        self.tree = tree
+        self.h = C.c_void_p()
+        _hchk(self.lib.iqhost_search_create(C.byref(self.h), tree.h))
+        self.params = dict(seed=seed, nni5=nni5, speed=speed, pop_size=pop_size, pers=pers, iterations=iterations,
+                           num_stop=num_stop, batched=batched, step_iterations=step_iterations,
+                           min_correlation=min_correlation, max_iterations=max_iterations)
+        self.best_score = None
+        self.correlation_log = []
+        self._trace = None
+
+    def close(self):
+        if self.h:
+            self.lib.iqhost_search_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _set_params(self, trace):
+        p = self.params
+        boot = getattr(self.tree, "_ufboot", 0) > 0
+        if p["iterations"] is not None and int(p["iterations"]) < 0:
+            raise HostError("TreeSearch: iterations must be >= 0")
+        if boot:   # the correlation rule; a fixed iteration count caps it
+            cond = SC_BOOTSTRAP_CORRELATION
+            max_it = p["max_iterations"] if p["iterations"] is None else min(p["max_iterations"], int(p["iterations"]))
+        else:
+            cond = SC_UNSUCCESS_ITERATION if p["iterations"] is None else SC_FIXED_ITERATION
+            max_it = p["max_iterations"]
+        iv = np.array([p["nni5"], p["speed"], p["batched"], p["pop_size"], cond,
+                       int(p["iterations"] or 0), p["num_stop"], max_it, p["step_iterations"], trace], dtype=np.int32)
+        dv = np.array([p["pers"], p["min_correlation"]], dtype=np.float64)
+        _hchk(self.lib.iqhost_search_set_params(self.h, _iptr(iv), _dptr(dv), int(p["seed"])))
+
+    def _fetch_trace(self):
+        need = C.c_int()
+        _hchk(self.lib.iqhost_search_trace_json(self.h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        _hchk(self.lib.iqhost_search_trace_json(self.h, buf, len(buf), C.byref(need)))
+        import json
+        t = json.loads(buf.value.decode())
+        _trace_steps(t["nni_steps"])
+        for it in t["iterations"]:
+            _trace_steps(it["steps"])
+            it["random_nnis"] = [tuple(x) for x in it["random_nnis"]]
+        t["boot_splits"] = [{frozenset(s): w for s, w in snap} for snap in t["boot_splits"]]
+        return t
+
+    def optimize_nni(self, trace=False):
+        """compute_likelihood(), then optimizeNNI on the tree -> (lnL, NNIs applied, steps[, per-step trace])"""
+        self._set_params(trace)
+        lnl, cnt, steps = C.c_double(), C.c_int(), C.c_int()
+        _hchk(self.lib.iqhost_search_optimize_nni(self.h, C.byref(lnl), C.byref(cnt), C.byref(steps)))
+        if trace:
+            return lnl.value, cnt.value, steps.value, self._fetch_trace()["nni_steps"]
+        return lnl.value, cnt.value, steps.value
+
+    def do_random_nnis(self, num_nni, iteration):
+        """doRandomNNIs with the draws of `iteration` -> [(node1, node2, bit1, bit2)]; all vectors go stale"""
+        self._set_params(False)
+        out = np.zeros(4 * max(int(num_nni), 1), dtype=np.int32)
+        n = C.c_int()
+        _hchk(self.lib.iqhost_search_do_random_nnis(self.h, int(num_nni), int(iteration), _iptr(out), int(num_nni), C.byref(n)))
+        return [tuple(int(x) for x in out[4 * k:4 * k + 4]) for k in range(n.value)]
+
+    def search(self, trace=False):
+        """doTreeSearch -> the best score (with trace: (best score, [per iteration dict(iteration, parent, random_nnis,
+        perturb_score, steps, score, new_best, nni_count)])); the best tree is loaded into the PhyloTree"""
+        self._set_params(trace)
+        best = C.c_double()
+        _hchk(self.lib.iqhost_search_do_tree_search(self.h, C.byref(best)))
+        self.best_score = best.value
+        t = self._fetch_trace()
+        self._trace = t
+        self.correlation_log = [(int(i), float(c)) for i, c in t["correlation_log"]]
+        self.boot_splits = t["boot_splits"]
+        self._candidates = [(c[0], c[1], c[2]) for c in t["candidates"]]
+        return (best.value, t["iterations"]) if trace else best.value
+
+    def candidates(self):
+        """the candidate set after search(): [(score, tree, topology)], the best first"""
+        return list(self._candidates)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,9 +1,11 @@
 // iqhost_c.cpp -- flat C view of iqhost::PhyloTree for ctypes (tests, bench.py, smoke()).
 // Not part of the drop-in boundary (that is include/iqhip.h); this is how the Python side of
 // the repository drives the same call sequence the reference's C++ callers use.
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <memory>
 #include <new>
 
@@ -14,16 +16,18 @@
 #include "brent_host.h"
 #include "model_opt_host.h"
 #include "phylo_host.h"
+#include "search_host.h"
 #include "supertree_host.h"
+#include "tree_search_host.h"
 #include "ufboot_splits.h"
 
 using namespace iqhost;
 
 static thread_local std::string g_host_err;
 
-#define IQHOST_TRY(body)                   \
+#define IQHOST_TRY(...)                    \
     try {                                  \
-        body;                              \
+        __VA_ARGS__;                       \
         return 0;                          \
     } catch (const std::exception &ex) {   \
         g_host_err = ex.what();            \
@@ -546,58 +550,53 @@ int iqhost_compute_rell(void *h, double *out, int cap) {
 
 // last submitted plan: 7 ints per op {dst_from, dst_to, left_node, right_node, left_leaf, right_leaf, 0}
 // plus 2 doubles per op {left_len, right_len}; dst_from->dst_to is the neighbour that was filled
-// all nni1 candidates of the tree in one submission: out[k*5 + {0..4}] = node1, node2, node1_nei, node2_nei ids,
-// then lens/lnls: newLen[0], newloglh.  Returns the number of candidates in *n.
-int iqhost_evaluate_nnis_batch(void *h, int *ids, double *vals, int cap, int *n) {
-    IQHOST_TRY({
-        std::vector<PhyloTree::NNIMove> mv;
-        ((PhyloTree *)h)->evaluateNNIsBatch(mv);
-        if ((int)mv.size() > cap) throw std::runtime_error("output too small");
-        *n = (int)mv.size();
-        for (size_t k = 0; k < mv.size(); k++) {
-            ids[4 * k] = mv[k].node1; ids[4 * k + 1] = mv[k].node2;
-            ids[4 * k + 2] = mv[k].node1_nei; ids[4 * k + 3] = mv[k].node2_nei;
-            vals[2 * k] = mv[k].newLen[0]; vals[2 * k + 1] = mv[k].newloglh;
-        }
-    });
-}
+// all nni1 candidates of the tree in one submission: ids[4*k + {0..3}] = node1, node2, node1_nei, node2_nei ids,
+// vals[2*k + {0,1}] = newLen[0], newloglh.  Returns the number of candidates in *n.
 // nni5 batch: vals[6*k + {0..5}] = newLen[0..4], newloglh
-int iqhost_evaluate_nnis5_batch(void *h, int *ids, double *vals, int cap, int *n) {
-    IQHOST_TRY({
-        std::vector<PhyloTree::NNIMove> mv;
-        ((PhyloTree *)h)->evaluateNNIs5Batch(mv);
-        if ((int)mv.size() > cap) throw std::runtime_error("output too small");
-        *n = (int)mv.size();
-        for (size_t k = 0; k < mv.size(); k++) {
-            ids[4 * k] = mv[k].node1; ids[4 * k + 1] = mv[k].node2;
-            ids[4 * k + 2] = mv[k].node1_nei; ids[4 * k + 3] = mv[k].node2_nei;
-            for (int i = 0; i < 5; i++) vals[6 * k + i] = mv[k].newLen[i];
-            vals[6 * k + 5] = mv[k].newloglh;
-        }
-    });
-}
-// nni5 batch with the candidates' per-pattern lnL kept in the engine's store: candidate k -> row first_row + k
-int iqhost_evaluate_nnis5_batch_rows(void *h, int *ids, double *vals, int cap, int *n, int first_row) {
+// both on a branch list (2 node ids per branch; NULL: all internal branches); first_row >= 0 (nni5 only) keeps candidate
+// k's per-pattern lnL in row first_row + k of the engine's store
+int iqhost_evaluate_nnis_list(void *h, int nni5, const int *branches, int nbranches, int first_row, int *ids, double *vals,
+                              int cap, int *n) {
     IQHOST_TRY({
         PhyloTree *t = (PhyloTree *)h;
-        std::vector<PhyloNode *> n1;
-        std::vector<PhyloNode *> n2;
-        t->internalBranches(n1, n2);
-        std::vector<int> rows(2 * n1.size());
-        for (size_t k = 0; k < rows.size(); k++) rows[k] = first_row + (int)k;
-        if (!t->engine) throw std::runtime_error("no engine");
-        if (iqhip_ptnlh_reserve(t->engine, first_row + (int)rows.size()) != 0) throw std::runtime_error(iqhip_last_error());
+        PhyloTree::BranchList list;
+        for (int q = 0; branches && q < nbranches; q++) list.push_back({branches[2 * q], branches[2 * q + 1]});
         std::vector<PhyloTree::NNIMove> mv;
-        t->evaluateNNIs5Batch(mv, rows.data());
+        if (!nni5) {
+            if (first_row >= 0) throw std::runtime_error("evaluateNNIsBatch keeps no per-pattern rows");
+            t->evaluateNNIsBatch(mv, branches ? &list : nullptr);
+        } else if (first_row >= 0) {
+            std::vector<PhyloNode *> n1, n2;
+            if (!branches) t->internalBranches(n1, n2);
+            std::vector<int> rows(2 * (branches ? list.size() : n1.size()));
+            for (size_t k = 0; k < rows.size(); k++) rows[k] = first_row + (int)k;
+            if (!t->engine) throw std::runtime_error("no engine");
+            if (iqhip_ptnlh_reserve(t->engine, first_row + (int)rows.size()) != 0) throw std::runtime_error(iqhip_last_error());
+            t->evaluateNNIs5Batch(mv, rows.data(), branches ? &list : nullptr);
+        } else
+            t->evaluateNNIs5Batch(mv, nullptr, branches ? &list : nullptr);
         if ((int)mv.size() > cap) throw std::runtime_error("output too small");
         *n = (int)mv.size();
+        const int w = nni5 ? 6 : 2;
         for (size_t k = 0; k < mv.size(); k++) {
             ids[4 * k] = mv[k].node1; ids[4 * k + 1] = mv[k].node2;
             ids[4 * k + 2] = mv[k].node1_nei; ids[4 * k + 3] = mv[k].node2_nei;
-            for (int i = 0; i < 5; i++) vals[6 * k + i] = mv[k].newLen[i];
-            vals[6 * k + 5] = mv[k].newloglh;
+            if (nni5)
+                for (int i = 0; i < 5; i++) vals[w * k + i] = mv[k].newLen[i];
+            else
+                vals[w * k] = mv[k].newLen[0];
+            vals[w * k + w - 1] = mv[k].newloglh;
         }
     });
+}
+int iqhost_evaluate_nnis_batch(void *h, int *ids, double *vals, int cap, int *n) {
+    return iqhost_evaluate_nnis_list(h, 0, nullptr, 0, -1, ids, vals, cap, n);
+}
+int iqhost_evaluate_nnis5_batch(void *h, int *ids, double *vals, int cap, int *n) {
+    return iqhost_evaluate_nnis_list(h, 1, nullptr, 0, -1, ids, vals, cap, n);
+}
+int iqhost_evaluate_nnis5_batch_rows(void *h, int *ids, double *vals, int cap, int *n, int first_row) {
+    return iqhost_evaluate_nnis_list(h, 1, nullptr, 0, first_row, ids, vals, cap, n);
 }
 // testAllBranches: ids[2q + {0,1}] = node1, node2; vals[7q + {0..6}] = lh0, lh1, lh2, sh_alrt, lbp, abayes, alrt_stat
 int iqhost_test_all_branches(void *h, int reps, int lbp_reps, int batched, int *ids, double *vals, int cap, int *n, double *lnl) {
@@ -985,6 +984,291 @@ int iqhost_ufboot_consensus(const char **trees, int ntrees, const int64_t *weigh
         const std::string s = ufboot::consensusTree(sc, nm);
         if (need) *need = (int)s.size() + 1;
         if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+
+// ---- NNI tree search (search_host.h, tree_search_host.h) ---------------------------------------------------------------
+static PhyloTree::NNIMove nni_move(PhyloTree *t, int node1, int node2, int node1_nei, int node2_nei) {
+    if (node1 < 0 || node2 < 0 || node1 >= t->nodeNum || node2 >= t->nodeNum) throw std::runtime_error("bad node id");
+    PhyloTree::NNIMove mv;
+    mv.node1 = node1; mv.node2 = node2; mv.node1_nei = node1_nei; mv.node2_nei = node2_nei;
+    return mv;
+}
+int iqhost_do_nni(void *h, int node1, int node2, int node1_nei, int node2_nei, int clear_lh) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        t->doNNI(nni_move(t, node1, node2, node1_nei, node2_nei), clear_lh != 0);
+    });
+}
+int iqhost_change_nni_brans(void *h, int node1, int node2, const double *new_len, int nni5) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        PhyloTree::NNIMove mv = nni_move(t, node1, node2, -1, -1);
+        for (int i = 0; i < 5; i++) mv.newLen[i] = new_len[i];
+        t->changeNNIBrans(mv, nni5 != 0);
+    });
+}
+// out: node1, node2, node1_nei, node2_nei of the move that was made
+int iqhost_do_random_nni(void *h, int a, int b, int bit1, int bit2, int *out) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        nei(t, a, b);
+        const PhyloTree::NNIMove mv = t->doOneRandomNNI(t->nodes[a], t->nodes[b], bit1, bit2);
+        out[0] = mv.node1; out[1] = mv.node2; out[2] = mv.node1_nei; out[3] = mv.node2_nei;
+    });
+}
+int iqhost_save_branch_lengths(void *h, double *out, int cap, int *n) {
+    IQHOST_TRY({
+        std::vector<double> v;
+        ((PhyloTree *)h)->saveBranchLengths(v);
+        *n = (int)v.size();
+        if (out && (int)v.size() <= cap) memcpy(out, v.data(), sizeof(double) * v.size());
+    });
+}
+int iqhost_restore_branch_lengths(void *h, const double *v, int n) {
+    IQHOST_TRY(((PhyloTree *)h)->restoreBranchLengths(std::vector<double>(v, v + (n > 0 ? n : 0))));
+}
+namespace {
+struct ScoredMove {
+    int node1, node2;
+    double newloglh;
+    int index;
+};
+std::string jnum(double v) {
+    char buf[40];
+    snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+std::string jmove(const PhyloTree::NNIMove &m) {
+    std::string s = "[" + std::to_string(m.node1) + "," + std::to_string(m.node2) + "," + std::to_string(m.node1_nei) + "," +
+                    std::to_string(m.node2_nei) + "," + jnum(m.newloglh);
+    for (int i = 0; i < 5; i++) s += "," + jnum(m.newLen[i]);
+    return s + "]";
+}
+std::string jmoves(const std::vector<PhyloTree::NNIMove> &v) {
+    std::string s = "[";
+    for (size_t k = 0; k < v.size(); k++) s += (k ? "," : "") + jmove(v[k]);
+    return s + "]";
+}
+std::string jsteps(const std::vector<TreeSearch::NNIStep> &steps) {
+    std::string s = "[";
+    for (size_t k = 0; k < steps.size(); k++) {
+        const TreeSearch::NNIStep &st = steps[k];
+        s += k ? ",{" : "{";
+        s += "\"branches\":[";
+        for (size_t q = 0; q < st.branches.size(); q++)
+            s += (q ? ",[" : "[") + std::to_string(st.branches[q].first) + "," + std::to_string(st.branches[q].second) + "]";
+        s += "],\"all_branches\":" + std::string(st.all_branches ? "true" : "false");
+        s += ",\"evaluated\":" + jmoves(st.evaluated) + ",\"positive\":" + jmoves(st.positive) + ",\"applied\":" + jmoves(st.applied);
+        s += ",\"score\":" + jnum(st.score) + ",\"rolled_back\":" + (st.rolled_back ? "true" : "false");
+        s += ",\"submissions\":" + std::to_string(st.submissions) + "}";
+    }
+    return s + "]";
+}
+std::string jstring(const std::string &t) {   // Newick strings and topologies hold no character that needs escaping but these
+    std::string s = "\"";
+    for (char c : t) {
+        if (c == '"' || c == '\\') s += '\\';
+        s += c;
+    }
+    return s + "\"";
+}
+struct SearchHandle {
+    TreeSearch search;
+    std::vector<TreeSearch::NNIStep> nni_steps;   // of the last iqhost_search_optimize_nni
+    explicit SearchHandle(PhyloTree *t) : search(t) {}
+};
+void put_text(const std::string &s, char *out, int cap, int *need) {
+    if (need) *need = (int)s.size() + 1;
+    if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+}
+}  // namespace
+
+// order[k] = index of the k-th move of the descending stable sort
+int iqhost_search_sort_moves(const double *score, int n, int *order) {
+    IQHOST_TRY({
+        std::vector<ScoredMove> mv((size_t)(n > 0 ? n : 0));
+        for (int k = 0; k < n; k++) mv[(size_t)k] = ScoredMove{0, 0, score[k], k};
+        iqsearch::sortMoves(mv);
+        for (int k = 0; k < n; k++) order[k] = mv[(size_t)k].index;
+    });
+}
+// nodes: node1, node2 per move, in sorted order; taken: indices of the moves kept
+int iqhost_search_select_non_conflicting(const int *nodes, int n, int *taken, int *ntaken) {
+    IQHOST_TRY({
+        std::vector<ScoredMove> mv((size_t)(n > 0 ? n : 0));
+        for (int k = 0; k < n; k++) mv[(size_t)k] = ScoredMove{nodes[2 * k], nodes[2 * k + 1], 0.0, k};
+        const std::vector<ScoredMove> sel = iqsearch::selectNonConflicting(mv);
+        *ntaken = (int)sel.size();
+        for (size_t k = 0; k < sel.size(); k++) taken[k] = sel[k].index;
+    });
+}
+// adjacency in CSR form: the neighbours of node v are adj[adj_off[v] .. adj_off[v + 1]); applied: node1, node2 per move
+int iqhost_search_branches_for_nni(const int *applied, int napplied, const int *adj_off, const int *adj, int nnodes, int *out,
+                                   int cap, int *n) {
+    IQHOST_TRY({
+        iqsearch::Adjacency a((size_t)(nnodes > 0 ? nnodes : 0));
+        for (int v = 0; v < nnodes; v++) a[(size_t)v].assign(adj + adj_off[v], adj + adj_off[v + 1]);
+        std::vector<ScoredMove> mv;
+        for (int k = 0; k < napplied; k++) {
+            if (applied[2 * k] < 0 || applied[2 * k] >= nnodes || applied[2 * k + 1] < 0 || applied[2 * k + 1] >= nnodes)
+                throw std::runtime_error("branchesForNNI: bad node id");
+            mv.push_back(ScoredMove{applied[2 * k], applied[2 * k + 1], 0.0, k});
+        }
+        const iqsearch::BranchList list = iqsearch::branchesForNNI(mv, a);
+        *n = (int)list.size();
+        if ((int)list.size() > cap) throw std::runtime_error("output too small");
+        for (size_t q = 0; q < list.size(); q++) { out[2 * q] = list[q].first; out[2 * q + 1] = list[q].second; }
+    });
+}
+uint64_t iqhost_search_rand(uint64_t seed, uint64_t iteration, uint64_t draw) { return iqsearch::searchRand(seed, iteration, draw); }
+int iqhost_search_rand_int(uint64_t z, int n) { return iqsearch::searchRandInt(z, n); }
+int iqhost_search_stop(int condition, int cur_iteration, double cur_correlation, int min_iteration, int unsuccess_iteration,
+                       double min_correlation, int max_iteration, int last_improved) {
+    iqsearch::StopRule r;
+    r.stop_condition = (iqsearch::StopCondition)condition;
+    r.min_iteration = min_iteration;
+    r.unsuccess_iteration = unsuccess_iteration;
+    r.min_correlation = min_correlation;
+    r.max_iteration = max_iteration;
+    r.last_improved_iteration = last_improved;
+    return r.meetStopCondition(cur_iteration, cur_correlation) ? 1 : 0;
+}
+// nsnap snapshots one after the other: snapshot s has nsplits[s] splits of (ntaxa + 63) / 64 words with one weight each
+int iqhost_search_bootstrap_correlation(int ntaxa, int nsnap, const int *nsplits, const uint64_t *words, const int64_t *weights,
+                                        double *out) {
+    IQHOST_TRY({
+        const size_t W = ufboot::splitWords(ntaxa);
+        std::vector<ufboot::SplitCounts> snaps;
+        size_t at = 0;
+        for (int s = 0; s < nsnap; s++) {
+            ufboot::SplitCounts sc(ntaxa);
+            for (int k = 0; k < nsplits[s]; k++, at++) {
+                ufboot::Split sp(words + at * W, words + (at + 1) * W);
+                ufboot::splitNormalise(sp, ntaxa);
+                if (ufboot::splitTrivial(sp, ntaxa)) continue;
+                sc.addTree(std::vector<ufboot::Split>(1, sp), weights[at]);
+            }
+            snaps.push_back(sc);
+        }
+        *out = iqsearch::bootstrapCorrelation(snaps);
+    });
+}
+int iqhost_candset_create(void **out, int max_candidates) {
+    IQHOST_TRY({
+        iqsearch::CandidateSet *c = new iqsearch::CandidateSet();
+        if (max_candidates > 0) c->maxCandidates = max_candidates;
+        *out = c;
+    });
+}
+void iqhost_candset_destroy(void *c) { delete (iqsearch::CandidateSet *)c; }
+int iqhost_candset_update(void *c, const char *tree, const char *topology, double score, int *is_new) {
+    IQHOST_TRY(*is_new = ((iqsearch::CandidateSet *)c)->update(tree, topology, score) ? 1 : 0);
+}
+int iqhost_candset_size(void *c) { return (int)((iqsearch::CandidateSet *)c)->size(); }
+int iqhost_candset_exists(void *c, const char *topology) { return ((iqsearch::CandidateSet *)c)->treeTopologyExist(topology) ? 1 : 0; }
+double iqhost_candset_best_score(void *c) { return ((iqsearch::CandidateSet *)c)->getBestScore(); }
+int iqhost_candset_rand_rank(void *c, int pop_size, uint64_t r, int *rank) {
+    IQHOST_TRY({
+        iqsearch::CandidateSet *s = (iqsearch::CandidateSet *)c;
+        if (s->empty()) throw std::runtime_error("getRandCandTree on an empty candidate set");
+        *rank = (int)s->randCandRank(pop_size, r);
+    });
+}
+// text: tree, newline, topology
+int iqhost_candset_entry(void *c, int rank, double *score, char *text, int cap, int *need) {
+    IQHOST_TRY({
+        iqsearch::CandidateSet *s = (iqsearch::CandidateSet *)c;
+        if (rank < 0 || rank >= (int)s->size()) throw std::runtime_error("candidate rank out of range");
+        const iqsearch::CandidateTree &t = s->byRank((size_t)rank);
+        *score = t.score;
+        put_text(t.tree + "\n" + t.topology, text, cap, need);
+    });
+}
+
+int iqhost_search_create(void **out, void *tree) {
+    IQHOST_TRY(*out = new SearchHandle((PhyloTree *)tree));
+}
+void iqhost_search_destroy(void *s) { delete (SearchHandle *)s; }
+// iv: nni5, speednni, batched, popSize, stop condition, min_iteration, unsuccess_iteration, max_iteration, step_iterations,
+// keep_trace; dv: initPS, min_correlation
+int iqhost_search_set_params(void *s, const int *iv, const double *dv, uint64_t seed) {
+    IQHOST_TRY({
+        TreeSearch &ts = ((SearchHandle *)s)->search;
+        ts.nni5 = iv[0] != 0; ts.speednni = iv[1] != 0; ts.batched = iv[2] != 0; ts.popSize = iv[3];
+        if (iv[4] < 0 || iv[4] > 2) throw std::runtime_error("TreeSearch: unknown stop condition");
+        ts.stop_rule.stop_condition = (iqsearch::StopCondition)iv[4];
+        ts.stop_rule.min_iteration = iv[5]; ts.stop_rule.unsuccess_iteration = iv[6]; ts.stop_rule.max_iteration = iv[7];
+        ts.step_iterations = iv[8]; ts.keep_trace = iv[9] != 0;
+        ts.initPS = dv[0]; ts.stop_rule.min_correlation = dv[1];
+        ts.seed = seed;
+    });
+}
+// computeLikelihood(), then optimizeNNI; the steps are kept for iqhost_search_trace_json when keep_trace is set
+int iqhost_search_optimize_nni(void *s, double *lnl, int *nni_count, int *nni_steps) {
+    IQHOST_TRY({
+        SearchHandle *sh = (SearchHandle *)s;
+        sh->search.checkEligible("optimizeNNI");
+        sh->nni_steps.clear();
+        sh->search.tree->computeLikelihood();
+        *lnl = sh->search.optimizeNNI(*nni_count, *nni_steps, sh->search.keep_trace ? &sh->nni_steps : nullptr);
+    });
+}
+// out: node1, node2, bit1, bit2 per NNI
+int iqhost_search_do_random_nnis(void *s, int num_nni, uint64_t iteration, int *out, int cap, int *n) {
+    IQHOST_TRY({
+        std::vector<std::array<int, 4>> done;
+        ((SearchHandle *)s)->search.doRandomNNIs(num_nni, iteration, &done);
+        *n = (int)done.size();
+        for (size_t k = 0; k < done.size() && (int)k < cap; k++)
+            for (int i = 0; i < 4; i++) out[4 * k + i] = done[k][(size_t)i];
+    });
+}
+int iqhost_search_do_tree_search(void *s, double *best) {
+    IQHOST_TRY(*best = ((SearchHandle *)s)->search.doTreeSearch());
+}
+// {"nni_steps": [...], "iterations": [...], "candidates": [[score, tree, topology] best first], "correlation_log":
+//  [[iteration, correlation]], "boot_splits": [[[taxa of the split], weight] per snapshot]}
+int iqhost_search_trace_json(void *s, char *out, int cap, int *need) {
+    IQHOST_TRY({
+        SearchHandle *sh = (SearchHandle *)s;
+        const TreeSearch &ts = sh->search;
+        std::string j = "{\"nni_steps\":" + jsteps(sh->nni_steps) + ",\"iterations\":[";
+        for (size_t k = 0; k < ts.trace.size(); k++) {
+            const TreeSearch::Iteration &it = ts.trace[k];
+            j += k ? ",{" : "{";
+            j += "\"iteration\":" + std::to_string(it.iteration) + ",\"parent\":" + std::to_string(it.parent) + ",\"random_nnis\":[";
+            for (size_t q = 0; q < it.random_nnis.size(); q++) {
+                j += q ? ",[" : "[";
+                for (size_t i = 0; i < 4; i++) j += (i ? "," : "") + std::to_string(it.random_nnis[q][i]);
+                j += "]";
+            }
+            j += "],\"perturb_score\":" + jnum(it.perturb_score) + ",\"steps\":" + jsteps(it.steps) + ",\"score\":" + jnum(it.score);
+            j += ",\"new_best\":" + std::string(it.new_best ? "true" : "false") + ",\"nni_count\":" + std::to_string(it.nni_count) + "}";
+        }
+        j += "],\"candidates\":[";
+        for (size_t k = 0; k < ts.candidates.size(); k++) {
+            const iqsearch::CandidateTree &c = ts.candidates.byRank(k);
+            j += (k ? ",[" : "[") + jnum(c.score) + "," + jstring(c.tree) + "," + jstring(c.topology) + "]";
+        }
+        j += "],\"correlation_log\":[";
+        for (size_t k = 0; k < ts.correlation_log.size(); k++)
+            j += (k ? ",[" : "[") + std::to_string(ts.correlation_log[k].first) + "," + jnum(ts.correlation_log[k].second) + "]";
+        j += "],\"boot_splits\":[";
+        for (size_t k = 0; k < ts.boot_splits.size(); k++) {
+            const ufboot::SplitCounts &sc = ts.boot_splits[k];
+            j += k ? ",[" : "[";
+            for (size_t q = 0; q < sc.splits.size(); q++) {
+                j += q ? ",[[" : "[[";
+                bool first = true;
+                for (int t = 0; t < sc.ntaxa; t++)
+                    if (ufboot::splitHas(sc.splits[q], t)) { j += (first ? "" : ",") + std::to_string(t); first = false; }
+                j += "]," + std::to_string(sc.weight[q]) + "]";
+            }
+            j += "]";
+        }
+        j += "]}";
+        put_text(j, out, cap, need);
     });
 }
 

@@ -1003,10 +1003,55 @@ void PhyloTree::computeAllPartialLh() {
     iqhip_adapter::applyScaleFactors<MirrorPolicy>(plan, sum_scale.data());
 }
 
-void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves) {
+void PhyloTree::computePartialLhAround(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2) {
+    if (lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error("computePartialLhAround needs LM_ALL_BRANCH");
+    if (!central_partial_lh) initializeAllPartialLh();
+    MirrorPolicy::Plan plan;   // as computeAllPartialLh, for the vectors of the listed branches only
+    for (size_t q = 0; q < n1.size(); q++)
+        for (int side = 0; side < 2; side++) {
+            PhyloNode *node = side ? n2[q] : n1[q], *other = side ? n1[q] : n2[q];
+            for (PhyloNeighbor *nb : node->neighbors)
+                if (nb->node != other && !nb->node->isLeaf() && (nb->partial_lh_computed & 1) == 0)
+                    iqhip_adapter::collectPlan<MirrorPolicy>(this, nb, node, plan);
+        }
+    MirrorPolicy::record(this, plan);
+    if (plan.empty()) return;
+    if (!dry_run && allreduce_hook) throw std::runtime_error("computePartialLhAround: not available with a caller-owned collective");
+    std::vector<double> sum_scale(plan.size(), 0.0);
+    pushInputs();
+    MirrorPolicy::updatePartials(this, plan, sum_scale.data());
+    iqhip_adapter::applyScaleFactors<MirrorPolicy>(plan, sum_scale.data());
+}
+
+// the branches of a batched NNI evaluation: all internal ones, or the caller's list with each branch normalised to
+// node1->id < node2->id (the orientation internalBranches gives, so that a listed branch has the full call's entries)
+static void nniBranches(const PhyloTree *t, const PhyloTree::BranchList *branches, const char *who, std::vector<PhyloNode *> &n1,
+                        std::vector<PhyloNode *> &n2) {
+    if (!branches) t->internalBranches(n1, n2);
+    else {
+        n1.clear();
+        n2.clear();
+        for (const auto &br : *branches) {
+            const int a = std::min(br.first, br.second), b = std::max(br.first, br.second);
+            if (a < 0 || b >= (int)t->nodes.size() || a == b || !t->nodes[(size_t)a]->findNeighbor(t->nodes[(size_t)b]) ||
+                t->nodes[(size_t)a]->isLeaf() || t->nodes[(size_t)b]->isLeaf())
+                throw std::runtime_error(std::string(who) + ": a listed branch is not an internal branch of the tree");
+            n1.push_back(t->nodes[(size_t)a]);
+            n2.push_back(t->nodes[(size_t)b]);
+        }
+    }
+    for (size_t q = 0; q < n1.size(); q++)
+        if (n1[q]->degree() != 3 || n2[q]->degree() != 3) throw std::runtime_error(std::string(who) + " needs a binary tree");
+}
+
+void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches) {
     if (!engine || dry_run) throw std::runtime_error("evaluateNNIsBatch needs an attached engine");
     if (allreduce_hook) throw std::runtime_error("evaluateNNIsBatch: runs with a caller-owned collective use getBestNNIForBran");
-    computeAllPartialLh();
+    std::vector<PhyloNode *> bn1, bn2;
+    nniBranches(this, branches, "evaluateNNIsBatch", bn1, bn2);
+    if (branches && bn1.empty()) { moves.clear(); return; }
+    if (branches) computePartialLhAround(bn1, bn2);
+    else computeAllPartialLh();
     pushInputs();
     struct Cand {
         PhyloNode *node1, *node2;
@@ -1014,22 +1059,18 @@ void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves) {
         iqhip_node_op ops[2];
     };
     std::vector<Cand> cands;
-    for (PhyloNode *node1 : nodes)
-        for (PhyloNeighbor *nb12 : node1->neighbors) {
-            PhyloNode *node2 = nb12->node;
-            if (node1->isLeaf() || node2->isLeaf() || node1->id > node2->id) continue;
-            if (node1->degree() != 3 || node2->degree() != 3)
-                throw std::runtime_error("evaluateNNIsBatch needs a binary tree");
-            std::vector<PhyloNeighbor *> s1, s2;
-            for (PhyloNeighbor *nb : node1->neighbors) if (nb->node != node2) s1.push_back(nb);
-            for (PhyloNeighbor *nb : node2->neighbors) if (nb->node != node1) s2.push_back(nb);
-            for (int cnt = 0; cnt < 2; cnt++) {  // phylotree.cpp:2951-2960: first neighbour of node1 against each of node2's
-                Cand c;
-                c.node1 = node1; c.node2 = node2;
-                c.n1a = s1[0]; c.n1b = s1[1]; c.n2x = s2[cnt]; c.n2o = s2[1 - cnt];
-                cands.push_back(c);
-            }
+    for (size_t bq = 0; bq < bn1.size(); bq++) {
+        PhyloNode *node1 = bn1[bq], *node2 = bn2[bq];
+        std::vector<PhyloNeighbor *> s1, s2;
+        for (PhyloNeighbor *nb : node1->neighbors) if (nb->node != node2) s1.push_back(nb);
+        for (PhyloNeighbor *nb : node2->neighbors) if (nb->node != node1) s2.push_back(nb);
+        for (int cnt = 0; cnt < 2; cnt++) {  // phylotree.cpp:2951-2960: first neighbour of node1 against each of node2's
+            Cand c;
+            c.node1 = node1; c.node2 = node2;
+            c.n1a = s1[0]; c.n1b = s1[1]; c.n2x = s2[cnt]; c.n2o = s2[1 - cnt];
+            cands.push_back(c);
         }
+    }
     while (nni_batch_keys.size() < 2 * cands.size()) nni_batch_keys.push_back(next_key++);
     auto child = [&](PhyloNeighbor *nb, uint64_t &key, int32_t &leaf, double &len) {
         if (nb->node->isLeaf()) { key = 0; leaf = nb->node->id; }
@@ -1120,10 +1161,14 @@ void PhyloTree::internalBranches(std::vector<PhyloNode *> &n1, std::vector<Phylo
         }
 }
 
-void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows) {
+void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows, const BranchList *branches_in) {
     if (!engine || dry_run) throw std::runtime_error("evaluateNNIs5Batch needs an attached engine");
     if (allreduce_hook) throw std::runtime_error("evaluateNNIs5Batch: runs with a caller-owned collective use getBestNNIForBran");
-    computeAllPartialLh();
+    std::vector<PhyloNode *> bn1, bn2;
+    nniBranches(this, branches_in, "evaluateNNIs5Batch", bn1, bn2);
+    if (branches_in && bn1.empty()) { moves.clear(); return; }
+    if (branches_in) computePartialLhAround(bn1, bn2);
+    else computeAllPartialLh();
     pushInputs();
     // an outward subtree vector around the branch: fixed while the candidate is evaluated
     struct Ext { uint64_t key; int32_t leaf; double sf; };
@@ -1139,19 +1184,16 @@ void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh
         double len1[2], len2[2], l0;
     };
     std::vector<Branch> branches;
-    for (PhyloNode *node1 : nodes)
-        for (PhyloNeighbor *nb12 : node1->neighbors) {
-            PhyloNode *node2 = nb12->node;
-            if (node1->isLeaf() || node2->isLeaf() || node1->id > node2->id) continue;
-            if (node1->degree() != 3 || node2->degree() != 3) throw std::runtime_error("evaluateNNIs5Batch needs a binary tree");
-            Branch b;
-            b.node1 = node1; b.node2 = node2;
-            int i = 0, j = 0;
-            for (PhyloNeighbor *nb : node1->neighbors) if (nb->node != node2) { b.n1[i] = nb; b.len1[i++] = nb->length; }
-            for (PhyloNeighbor *nb : node2->neighbors) if (nb->node != node1) { b.n2[j] = nb; b.len2[j++] = nb->length; }
-            b.l0 = nb12->length;
-            branches.push_back(b);
-        }
+    for (size_t bq = 0; bq < bn1.size(); bq++) {
+        PhyloNode *node1 = bn1[bq], *node2 = bn2[bq];
+        Branch b;
+        b.node1 = node1; b.node2 = node2;
+        int i = 0, j = 0;
+        for (PhyloNeighbor *nb : node1->neighbors) if (nb->node != node2) { b.n1[i] = nb; b.len1[i++] = nb->length; }
+        for (PhyloNeighbor *nb : node2->neighbors) if (nb->node != node1) { b.n2[j] = nb; b.len2[j++] = nb->length; }
+        b.l0 = node1->findNeighbor(node2)->length;
+        branches.push_back(b);
+    }
     const size_t nb = branches.size();
     while (nni_batch_keys.size() < 4 * nb) nni_batch_keys.push_back(next_key++);
     moves.assign(2 * nb, NNIMove());
@@ -1292,6 +1334,111 @@ void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh
             }
         }
     }
+}
+
+// =========================================================================================
+// tree edits of the NNI search, phylotree.cpp:2726-2871
+// =========================================================================================
+namespace {
+// the slot of `at`'s neighbour list that holds one of the two subtrees of the move
+PhyloNeighbor **swapSlot(PhyloNode *at, PhyloNode *other_end, int id_a, int id_b) {
+    for (PhyloNeighbor *&nb : at->neighbors)
+        if (nb->node != other_end && (nb->node->id == id_a || nb->node->id == id_b)) return &nb;
+    throw std::runtime_error("doNNI: the move does not belong to this tree");
+}
+// PhyloNeighbor::reorientPartialLh (phylonode.cpp:22-39): `nb` points to a node whose one buffer may sit on another Neighbor
+void reorientPartialLh(PhyloNeighbor *nb, PhyloNode *dad) {
+    if (nb->partial_lh) return;
+    for (PhyloNeighbor *kid : nb->node->neighbors) {
+        if (kid->node == dad) continue;
+        PhyloNeighbor *backnei = kid->node->findNeighbor(nb->node);
+        if (backnei->partial_lh) {
+            nb->partial_lh = backnei->partial_lh;
+            backnei->partial_lh = 0;
+            backnei->partial_lh_computed &= ~1;
+            return;
+        }
+    }
+    throw std::runtime_error("doNNI: partial_lh is not re-oriented");
+}
+}  // namespace
+
+void PhyloTree::doNNI(const NNIMove &move, bool clearLH) {
+    if (move.node1 < 0 || move.node2 < 0 || move.node1 >= (int)nodes.size() || move.node2 >= (int)nodes.size())
+        throw std::runtime_error("doNNI: bad node id");
+    PhyloNode *node1 = nodes[(size_t)move.node1], *node2 = nodes[(size_t)move.node2];
+    PhyloNeighbor *node12_it = node1->findNeighbor(node2), *node21_it = node2->findNeighbor(node1);
+    if (!node12_it || !node21_it || node1->degree() != 3 || node2->degree() != 3)
+        throw std::runtime_error("doNNI needs an internal branch of a binary tree");
+    PhyloNeighbor **slot1 = swapSlot(node1, node2, move.node1_nei, move.node2_nei);
+    PhyloNeighbor **slot2 = swapSlot(node2, node1, move.node1_nei, move.node2_nei);
+    if ((*slot1)->node == (*slot2)->node) throw std::runtime_error("doNNI: the move does not belong to this tree");
+    if (lh_mem_save == LM_PER_NODE && central_partial_lh) {  // reorient partial_lh before swap (:2799-2803)
+        reorientPartialLh(node12_it, node1);
+        reorientPartialLh(node21_it, node2);
+    }
+    PhyloNeighbor *node1_nei = *slot1, *node2_nei = *slot2;
+    *slot1 = node2_nei;
+    updateNeighborNode(node2_nei->node, node2, node1);
+    *slot2 = node1_nei;
+    updateNeighborNode(node1_nei->node, node1, node2);
+    if (clearLH) {
+        node12_it->clearPartialLh();
+        node21_it->clearPartialLh();
+        node2->clearReversePartialLh(node1);
+        node1->clearReversePartialLh(node2);
+    }
+    theta_computed = false;
+}
+
+void PhyloTree::changeNNIBrans(const NNIMove &move, bool nni5) {
+    if (move.node1 < 0 || move.node2 < 0 || move.node1 >= (int)nodes.size() || move.node2 >= (int)nodes.size())
+        throw std::runtime_error("changeNNIBrans: bad node id");
+    PhyloNode *node1 = nodes[(size_t)move.node1], *node2 = nodes[(size_t)move.node2];
+    PhyloNeighbor *n12 = node1->findNeighbor(node2), *n21 = node2->findNeighbor(node1);
+    if (!n12 || !n21) throw std::runtime_error("changeNNIBrans: the move does not belong to this tree");
+    n12->length = n21->length = move.newLen[0];
+    if (!nni5) return;
+    int i = 1;
+    for (PhyloNeighbor *nb : node1->neighbors)
+        if (nb->node != node2) nb->length = nb->node->findNeighbor(node1)->length = move.newLen[i++];
+    for (PhyloNeighbor *nb : node2->neighbors)
+        if (nb->node != node1) nb->length = nb->node->findNeighbor(node2)->length = move.newLen[i++];
+}
+
+void PhyloTree::saveBranchLengths(std::vector<double> &lenvec) const {
+    lenvec.clear();
+    for (const PhyloNeighbor *nb : all_neighbors) lenvec.push_back(nb->length);
+}
+
+void PhyloTree::restoreBranchLengths(const std::vector<double> &lenvec) {
+    if (lenvec.size() != all_neighbors.size()) throw std::runtime_error("restoreBranchLengths: the lengths are not this tree's");
+    for (size_t k = 0; k < all_neighbors.size(); k++) all_neighbors[k]->length = lenvec[k];
+}
+
+PhyloTree::NNIMove PhyloTree::doOneRandomNNI(PhyloNode *node1, PhyloNode *node2, int bit1, int bit2) {
+    if (node1->isLeaf() || node2->isLeaf() || node1->degree() != 3 || node2->degree() != 3 || !node1->findNeighbor(node2))
+        throw std::runtime_error("doOneRandomNNI needs an internal branch of a binary tree");
+    auto pick = [](PhyloNode *at, PhyloNode *other, int bit) {   // :2732-2758: a draw of 0 takes the first, else the next
+        std::vector<PhyloNeighbor *> s;
+        for (PhyloNeighbor *nb : at->neighbors)
+            if (nb->node != other) s.push_back(nb);
+        return s[bit ? 1 : 0];
+    };
+    NNIMove mv;
+    mv.node1 = node1->id;
+    mv.node2 = node2->id;
+    mv.node1_nei = pick(node1, node2, bit1)->node->id;
+    mv.node2_nei = pick(node2, node1, bit2)->node->id;
+    doNNI(mv, false);
+    return mv;
+}
+
+std::vector<std::vector<int>> PhyloTree::adjacency() const {
+    std::vector<std::vector<int>> adj(nodes.size());
+    for (const PhyloNode *nd : nodes)
+        for (const PhyloNeighbor *nb : nd->neighbors) adj[(size_t)nd->id].push_back(nb->node->id);
+    return adj;
 }
 
 // =========================================================================================
@@ -2418,13 +2565,23 @@ void PhyloTree::saveNNITrees() {
     for (size_t k = 0; k < nc; k++) rows[k] = (int)(1 + k);
     std::vector<NNIMove> moves;
     evaluateNNIs5Batch(moves, rows.data());
+    for (size_t k = 0; k < nc; k++)
+        if (moves[k].ptnlh_row != rows[k]) throw std::runtime_error("saveNNITrees: NNI moves out of order");
+    saveNNITrees(moves);
+}
+
+void PhyloTree::saveNNITrees(const std::vector<NNIMove> &moves) {
+    if (!engine || dry_run) throw std::runtime_error("saveNNITrees needs an attached engine");
+    if (ufboot_nsamples < 1) throw std::runtime_error("saveNNITrees before initUFBoot");
+    const size_t nc = moves.size();
+    if (nc == 0) return;
     std::vector<iqhip_ufboot_tree> ent(nc);
     const int64_t first_id = ufboot_next_id;
     for (size_t k = 0; k < nc; k++) {
-        if (moves[k].ptnlh_row != rows[k]) throw std::runtime_error("saveNNITrees: NNI moves out of order");
+        if (moves[k].ptnlh_row < 0) throw std::runtime_error("saveNNITrees: a move was evaluated without a store row");
         iqhip_ufboot_tree &t = ent[k];
         memset(&t, 0, sizeof t);
-        t.row = rows[k];
+        t.row = moves[k].ptnlh_row;
         t.tree_id = ufboot_next_id++;
         t.logl = moves[k].newloglh;
         t.rand = ufbootRand(ufboot_seed, t.tree_id);
@@ -2442,13 +2599,15 @@ void PhyloTree::saveNNITrees() {
     ufbootKeepReferred(ufboot_trees, boot_tree);
 }
 
-void PhyloTree::summarizeBootstrap(UFBootSummary &out) {
+// the winner of every replicate (out.boot_trees, out.distinct_trees) and the split counts of the winners
+void PhyloTree::ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc) {
     if (!engine || dry_run) throw std::runtime_error("summarizeBootstrap needs an attached engine");
     if (ufboot_nsamples < 1) throw std::runtime_error("summarizeBootstrap before initUFBoot");
     const size_t S = (size_t)ufboot_nsamples;
     std::vector<int64_t> boot_tree(S);
     check(iqhip_ufboot_fetch(engine, nullptr, nullptr, nullptr, boot_tree.data()), "iqhip_ufboot_fetch");
     out = UFBootSummary();
+    sc = ufboot::SplitCounts(leafNum);
     out.boot_trees.resize(S);
     // trees.convertSplits(taxname, sg, hash_ss, SW_COUNT, ...): every winner once, weighted by its replicates, in the order
     // the replicates first name it
@@ -2471,12 +2630,22 @@ void PhyloTree::summarizeBootstrap(UFBootSummary &out) {
         weight[k]++;
     }
     out.distinct_trees = (int)order.size();
-    ufboot::SplitCounts sc(leafNum);
     std::vector<ufboot::Split> splits;
     for (size_t k = 0; k < order.size(); k++) {
         ufboot::newickSplits(*text[k], leafNum, splits);
         sc.addTree(splits, weight[k]);
     }
+}
+
+void PhyloTree::ufbootSplitCounts(ufboot::SplitCounts &sc) {
+    UFBootSummary winners;
+    ufbootWinners(winners, sc);
+}
+
+void PhyloTree::summarizeBootstrap(UFBootSummary &out) {
+    ufboot::SplitCounts sc(leafNum);
+    ufbootWinners(out, sc);
+    const size_t S = (size_t)ufboot_nsamples;
     // createBootstrapSupport: the split of every internal branch of the current tree
     std::vector<PhyloNode *> n1, n2;
     internalBranches(n1, n2);

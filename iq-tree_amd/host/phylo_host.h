@@ -27,6 +27,10 @@
 #include "../../include/iqhip.h"
 #include "lmap_host.h"
 
+namespace ufboot {
+struct SplitCounts;   // ufboot_splits.h
+}
+
 namespace iqhost {
 
 typedef short int UBYTE;  // phylonode.h:17
@@ -195,15 +199,40 @@ public:
     // IQTree::evaluateNNIs with nni1 for EVERY internal branch, all 2(n-3) candidates side by side in one
     // iqhip_optimize_branch_batch submission (same swaps, same Newton solve, same lnL as getBestNNIForBran
     // gives one branch at a time).  moves: 2 per internal branch, in branch order.  Needs LM_ALL_BRANCH.
-    void evaluateNNIsBatch(std::vector<NNIMove> &moves);
+    // branches (optional): only these internal branches become tasks, in list order and each normalised to
+    // node1->id < node2->id; the entries of a listed branch are those the full call gives for it.  With a list only the
+    // directed vectors those branches read are made valid (computePartialLhAround), not all of them
+    typedef std::vector<std::pair<int, int>> BranchList;
+    void evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr);
     // the same with nni5 (the reference's default, params.nni5): per candidate the two branches at node1, the
     // central branch and the two at node2 are optimised in that order (phylotree.cpp:2984-3024); five rounds of
     // batched tasks per swap, ten submissions per tree instead of ~10 per branch
     // ptnlh_rows (optional, 2 per internal branch in move order): the last round goes through
     // iqhip_optimize_branch_batch_rows, so every candidate's per-pattern lnL lands in its store row on the device
-    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows = nullptr);
+    // ptnlh_rows with a branch list: 2 per LISTED branch in move order
+    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows = nullptr, const BranchList *branches = nullptr);
     // the internal branches in the order both NNI evaluations list them (node1->id < node2->id)
     void internalBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2) const;
+    // the four subtree vectors around each listed branch (what its NNI candidates read), one submission; LM_ALL_BRANCH
+    void computePartialLhAround(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2);
+
+    // ---- tree edits of the NNI search (phylotree.cpp:2726-2871) --------------------------------------------------------
+    // doNNI: the subtrees at node1_nei and node2_nei change places wherever they hang on node1 / node2 now, so the same
+    // move a second time restores the tree, neighbour order included.  The Neighbor objects move with their lengths.
+    // clearLH: both central vectors and everything that looks through the branch from outside go stale (:2826-2832).
+    // LM_PER_NODE: each end's buffer is first moved onto the central Neighbor that points to it (:2799-2803).
+    void doNNI(const NNIMove &move, bool clearLH = true);
+    // newLen[0] to the central branch and, with nni5, newLen[1..4] to the other branches of node1 then node2 in neighbour
+    // order AFTER the swap -- the order in which getBestNNIForBran / evaluateNNIs5Batch fill newLen
+    void changeNNIBrans(const NNIMove &move, bool nni5);
+    // one length per Neighbor object in creation order; the objects keep their branch through doNNI
+    void saveBranchLengths(std::vector<double> &lenvec) const;
+    void restoreBranchLengths(const std::vector<double> &lenvec);   // the caller clears the vectors (clearAllPartialLH)
+    // doOneRandomNNI with its two coin flips as arguments: bit 0 takes the first other neighbour of the node, bit 1 the
+    // second.  No vector is cleared (the reference's caller recomputes everything); returns the move that was made
+    NNIMove doOneRandomNNI(PhyloNode *node1, PhyloNode *node2, int bit1, int bit2);
+    // node id -> neighbour ids in neighbour order (search_host.h's Adjacency)
+    std::vector<std::vector<int>> adjacency() const;
 
     // ---- SH-aLRT / local bootstrap (PhyloTree::testAllBranches, phylotree.cpp:3984-4103) on the device:
     //      computeLikelihood -> store row 0; both NNI neighbours of every internal branch with five branches re-optimised
@@ -421,6 +450,10 @@ public:
     // evaluateNNIs5Batch with store rows, then ONE update over all 2 (leafNum - 3) candidates in move order, logl = newloglh;
     // a candidate's string is made from (current tree, move) only when a replicate took it.  Needs LM_ALL_BRANCH
     void saveNNITrees();
+    // the update alone, for moves that were ALREADY evaluated on the current tree with store rows (ptnlh_row >= 0 each):
+    // every candidate is fed, positive or not, in the given order (phylotree.cpp:3019-3024), so one evaluation serves the
+    // search and the bootstrap
+    void saveNNITrees(const std::vector<NNIMove> &evaluated);
     // iqtree.cpp:1887-1888, the start of a search iteration: logl_cutoff = the minimum of boot_orig_logl
     void ufbootNextIteration();
     static double ufbootRand(uint64_t seed, int64_t tree_id);
@@ -434,6 +467,8 @@ public:
         int distinct_trees = 0;
     };
     void summarizeBootstrap(UFBootSummary &out);
+    // the weighted split counts of the current winners alone (what the search's correlation rule snapshots)
+    void ufbootSplitCounts(ufboot::SplitCounts &sc);
     int ufboot_nsamples = 0;
     uint64_t ufboot_seed = 0;
     int64_t ufboot_next_id = 0;          // = candidate trees fed so far
@@ -497,6 +532,7 @@ private:
     void needParsimony(const char *what);
     void assignParsSlots();
     int pars_next_slot = 0;
+    void ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc);
 
     AllReduceHook allreduce_hook = nullptr;
     void *allreduce_ctx = nullptr;

@@ -1,0 +1,103 @@
+// tree_search_host.h -- the NNI tree search of the reference on top of the device calls of phylo_host.h:
+//   IQTree::optimizeNNI    iqtree.cpp:2125-2288   hill climbing by sets of non-conflicting NNIs
+//   IQTree::doRandomNNIs   iqtree.cpp:1302-1339   the perturbation of the stochastic search
+//   IQTree::doTreeSearch   iqtree.cpp:1834-2098   the stochastic loop (the snni branch) with the UFBoot stopping rule
+// The decisions that need no likelihood are search_host.h; this file drives the tree and the engine.  The hot path of a
+// search -- NNI evaluation and one-pass branch sweeps -- is evaluateNNIs[5]Batch and optimizeAllBranches: no kernel is
+// added.  Per NNI step the engine sees: one submission for the vectors the listed branches read, ten (nni5) or two (nni1)
+// batched solves over the listed branches only, one for the pending vectors of the sweep and one sweep; with UFBoot one
+// update that reuses the per-pattern rows the evaluation left in the store (no row crosses to the host).
+//
+// DEVIATIONS from the reference (see also search_host.h): all internal branches are listed in internalBranches order
+// (ascending node id), not in the reference's depth-first order; every branch is evaluated as (node1->id < node2->id),
+// the orientation of the batched evaluators, where the reference passes getBranchesForNNI's orientation on; the model is
+// taken as given (optimizeAllBranches(100) stands where the reference re-estimates the model for a better tree); the search
+// starts from ONE tree (no initial candidate set of parsimony trees); doOneRandomNNI's coin flips are real coin flips (the
+// reference draws random_int(1), which is always 0).
+// The reference's moves hold neighbour iterators: when an earlier move of a step has re-hung an end of a later one
+// (non-conflicting moves share no end, but may be adjacent), the later move swaps what its slots hold by then.  The moves here
+// hold node ids, so a step looks the slots up on the evaluated tree and applies what they hold; the applied moves are
+// reverted last first, the order that restores the tree also then (the reference reverts first to last -- the same thing
+// for moves that do not touch).
+// As in the reference, a step that is rolled back ends optimizeNNI: curScore goes back to the score before the step, so
+// the gain of the step is 0 < 0.1.  The "apply only the best move" branch is kept as the reference has it.
+#pragma once
+#include <array>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "phylo_host.h"
+#include "search_host.h"
+
+namespace iqhost {
+
+class TreeSearch {
+public:
+    typedef PhyloTree::NNIMove NNIMove;
+    typedef iqsearch::BranchList BranchList;
+
+    explicit TreeSearch(PhyloTree *tree);
+
+    // ---- parameters (the reference's defaults) ------------------------------------------------------------------------
+    bool nni5 = true;             // params.nni5
+    bool speednni = true;         // searchinfo.speednni: after the first step only branchesForNNI(applied) are evaluated
+    bool batched = true;          // evaluateNNIs[5]Batch (LM_ALL_BRANCH); false: getBestNNIForBran branch by branch
+    double loglh_epsilon = 0.001; // params.loglh_epsilon
+    double modeps = 0.01;         // params.modeps
+    int popSize = 5;              // params.popSize
+    double initPS = 0.5;          // params.initPS
+    uint64_t seed = 0;
+    iqsearch::StopRule stop_rule; // SC_UNSUCCESS_ITERATION with 100; a bootstrap search uses SC_BOOTSTRAP_CORRELATION
+    int step_iterations = 100;    // params.step_iterations
+
+    // ---- trace ----------------------------------------------------------------------------------------------------------
+    struct NNIStep {
+        BranchList branches;             // evaluated, each as (node1 < node2); empty for the step after a rollback
+        bool all_branches = false;       // the list is every internal branch
+        std::vector<NNIMove> evaluated;  // both candidates of every listed branch, in evaluation order
+        std::vector<NNIMove> positive;   // the better candidate of a branch when above curScore + epsilon, sorted
+        std::vector<NNIMove> applied;
+        double score = 0.0;              // after the sweep (before a rollback puts the old score back)
+        bool rolled_back = false;
+        long submissions = 0;            // engine submissions of this step
+    };
+    struct Iteration {
+        int iteration = 0;
+        int parent = -1;                               // rank of the candidate tree that was read (-1: the starting tree)
+        std::vector<std::array<int, 4>> random_nnis;   // node1, node2, bit1, bit2
+        double perturb_score = 0.0;
+        std::vector<NNIStep> steps;
+        double score = 0.0;
+        bool new_best = false;
+        int nni_count = 0;
+    };
+    bool keep_trace = false;
+    std::vector<Iteration> trace;
+    // called at the end of every search iteration (the steps are filled only with keep_trace); a correlation computed in
+    // this iteration is the last entry of correlation_log
+    std::function<void(const TreeSearch &, const Iteration &)> on_iteration;
+    std::vector<ufboot::SplitCounts> boot_splits;   // the snapshots of the correlation rule, every step_iterations / 2
+    std::vector<std::pair<int, double>> correlation_log;   // (iteration, correlation) every step_iterations
+    iqsearch::CandidateSet candidates;
+
+    // ---- the search -------------------------------------------------------------------------------------------------------
+    // on the current tree with curScore valid (computeLikelihood / optimizeAllBranches came last); returns curScore
+    double optimizeNNI(int &nni_count, int &nni_steps, std::vector<NNIStep> *steps = nullptr);
+    // numNNI random NNIs with the draws 1 + 3k (branch), 2 + 3k, 3 + 3k (coins) of `iteration`; all vectors go stale
+    void doRandomNNIs(int numNNI, uint64_t iteration, std::vector<std::array<int, 4>> *done = nullptr);
+    // returns the best score; the best candidate tree is loaded, its lengths as stored, its lnL recomputed
+    double doTreeSearch();
+    // refuses multifurcating trees, fewer than 4 taxa, trees without an engine, sharded engines and communicator ranks,
+    // `batched` without LM_ALL_BRANCH, UFBoot together with mixtures, +ASC or the batched nni1 evaluation (it keeps no
+    // per-pattern rows): throws std::runtime_error, the tree is not touched.  Every entry point calls it first
+    void checkEligible(const char *who) const;
+
+    PhyloTree *tree;
+
+private:
+    void evaluate(const BranchList &branches, bool all, std::vector<NNIMove> &moves);
+    std::vector<std::string> leafNames() const;
+};
+
+}  // namespace iqhost
