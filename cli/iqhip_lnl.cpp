@@ -80,6 +80,13 @@
 // (100) and -numstop iterations brought no better tree, or after -nm MAXIT (1000).  It prints "Iteration k / LogL: x" every
 // 10th iteration, "BETTER TREE FOUND at iteration k: x", "NOTE: Bootstrap correlation coefficient of split occurrence
 // frequencies: c" and "Optimal log-likelihood:", and writes <prefix>.treefile.  -search sets LM_ALL_BRANCH.
+// With -search -numpars N [-toppars M] [-sprrad R] (the reference's flag names; its defaults are 100 and 20) the search
+// starts as the reference's does (initCandidateTreeSet): the starting tree plus N - 1 stepwise-addition parsimony trees built
+// in lockstep on the device (pars_forest_host.h; with -sprrad followed by SPR rounds of radius R), duplicate topologies
+// dropped, every tree scored with two rounds of branch optimisation, the best M (20; lowered to N when N is smaller, as
+// tools.cpp:2523-2525 does) optimised by NNI as the iterations 1 .. M.  It prints "Generating N-1 parsimony trees... D
+// distinct starting trees", "Computing log-likelihood of D initial trees" and "Optimizing top M initial trees with NNI...".
+// -n then counts the iterations after those M.  Without -numpars the search starts from the one tree, as before.
 // With -q <partition file> (edge-linked, all partition rates 1) or -spp <partition file> (edge-linked, proportional: the
 // rates start at 1 and are estimated) instead of -m it evaluates an edge-linked partition model (PhyloSuperTree,
 // supertree_host.h): the file is RAxML-style, `MODEL, name = 1-100, 250-400, 401-500\3`, MODEL a string in the -m syntax
@@ -283,6 +290,8 @@ static void usage() {
             "                 [-mixweights] [-optmodel] [-bb <n> [-beps <e>] [-z <tree set file>] [-wbt]]\n"
             "                 [-search | -t <newick file>] [-n <iterations>] [-numstop <n>] [-pers <p>] [-popsize <k>] [-nni1|-nni5] [-allnni]\n"
             "                 (NNI tree search from the starting tree; with -bb <n>: [-bcor <c>] [-nstep <s>] [-nm <max iterations>])\n"
+            "                 [-numpars <n> [-toppars <m>] [-sprrad <r>]]   (with -search: n starting trees, n - 1 of them parsimony trees,\n"
+            "                  the best m optimised by NNI before the search loop)\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
@@ -311,6 +320,7 @@ int main(int argc, char **argv) {
     long long n_iter = -1;
     bool n_given = false;
     int numstop = 100, popsize = 5, nstep = 100, nm = 1000;
+    int numpars = 0, toppars = 20;   // -numpars / -toppars: the starting population of the search (0: the one tree)
     double pers = 0.5, bcor = 0.99;
     bool zw = false, au = false, parstree = false, pars = false, bionjtree = false, emrates = false, wsr = false, mixweights = false, optmodel = false;
     for (int i = 1; i < argc; i++) {
@@ -374,6 +384,16 @@ int main(int argc, char **argv) {
         else if (a == "-search") search = true;
         else if (a == "-t") { tree_file = next(); search = true; }
         else if (a == "-numstop") numstop = atoi(next().c_str());
+        else if (a == "-numpars" || a == "-toppars") {
+            char *end = nullptr;
+            const std::string v = next();
+            const long long k = strtoll(v.c_str(), &end, 10);
+            if (v.empty() || *end || k < 1 || k > 1000000) {
+                fprintf(stderr, "error: %s needs a positive number of trees\n", a.c_str());
+                return 2;
+            }
+            (a == "-numpars" ? numpars : toppars) = (int)k;
+        }
         else if (a == "-pers") pers = atof(next().c_str());
         else if (a == "-popsize") popsize = atoi(next().c_str());
         else if (a == "-nni1") nni5 = false;
@@ -413,7 +433,9 @@ int main(int argc, char **argv) {
     if (prefix.empty()) prefix = aln_file;
     if (bionjtree && mldist_file.empty()) mldist_file = prefix + ".mldist";
     if (alrt < 0 || lbp < 0) { usage(); return 2; }
-    if (sprrad > 0 && !parstree && !pars) { usage(); return 2; }
+    if (sprrad > 0 && !parstree && !pars && numpars == 0) { usage(); return 2; }
+    if (numpars > 0 && !search) { usage(); return 2; }   // the starting population belongs to the search
+    if (numpars > 0 && numpars < toppars) toppars = numpars;
     if (bb < 0 || !(beps >= 0.0) || (bb == 0 && wbt)) { usage(); return 2; }
     if (zb < 0 || (!treeset_file.empty() && zb < 1 && bb == 0) || (treeset_file.empty() && (zb > 0 || zw || au))) { usage(); return 2; }
     if (wql && lmap < 0) { usage(); return 2; }
@@ -705,6 +727,16 @@ int main(int argc, char **argv) {
                     printf("NOTE: Bootstrap correlation coefficient of split occurrence frequencies: %g\n", s.correlation_log.back().second);
                 }
             };
+            if (numpars > 0) {
+                ts.numInitTrees = numpars;
+                ts.numNNITrees = toppars;
+                ts.initSprRadius = sprrad;
+                ts.on_init_phase = [&](const TreeSearch &, int phase, int count) {
+                    if (phase == 0) printf("Generating %d parsimony trees... %d distinct starting trees\n", numpars - 1, count);
+                    else if (phase == 1) printf("Computing log-likelihood of %d initial trees\n", count);
+                    else printf("Optimizing top %d initial trees with NNI...\n", count);
+                };
+            }
             auto t0 = std::chrono::steady_clock::now();
             const long sub0 = tree.num_submissions;
             ts.doTreeSearch();

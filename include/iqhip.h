@@ -770,7 +770,21 @@ int iqhip_debug_bionj_timing(iqhip_engine *e, double *ms, int64_t *launches);
  *   nvectors < 0, nbranch < 1, `taxon` not a tip slot.  Mixture engines are accepted (class 0's tip table is read).
  * iqhip_debug_pars_timing: since the last reset, ms[0] / ms[1] = the device time (HIP events, milliseconds; counted while
  *   iqhip_timing_enable is on) of the iqhip_pars_update launches / of the iqhip_pars_insert_scores launches, and counts =
- *   {update launches, scan launches (scores + first minimum), ops updated, branches scanned}. */
+ *   {update launches, scan launches (scores + first minimum), ops updated, branches scanned}.
+ * iqhip_pars_insert_scores_batch: one stepwise-addition step of MANY trees that share one arena (the reference builds its
+ *   100 starting trees under "#pragma omp parallel for", iqtree.cpp:591-601; here tree k's step s is segment k of one call).
+ *   The branches [seg_start[g], seg_start[g + 1]) of `ends` form segment g and are scored against the tip slot taxon[g] with
+ *   exactly iqhip_pars_insert_scores' formula; best[g] = the FIRST minimum of segment g in list order as an index WITHIN the
+ *   segment, best_score[g] that minimum; score: NULL or seg_start[nseg] entries -- without it 2 * nseg integers come back.
+ *   Two launches per call (scores, then one workgroup per segment for the minima), no atomics, a fixed order: every run gives
+ *   the same bits.  Two routes over one scoring function, chosen from nwords alone: a wave per branch (four branches per
+ *   workgroup) while nwords <= 256, a workgroup per branch above; the threshold has NOT been measured.
+ *   IQHIP_PARS_BATCH_ROUTE = wave | wg, read per call, forces a route; any other word is IQHIP_ERR_INVALID.
+ *   IQHIP_ERR_INVALID, before anything is launched: a null argument (all but `score`), nseg < 1, seg_start[0] != 0,
+ *   seg_start not strictly increasing (an empty segment), a slot out of range or never written, a taxon[g] that is not a
+ *   tip slot.  Engines are refused as by the other iqhip_pars_* calls.
+ * iqhip_debug_pars_batch_timing: since the last reset, *ms = the device time of the batch scans (while iqhip_timing_enable
+ *   is on), counts = {launches, branches, segments}.  The counters of iqhip_debug_pars_timing do not count batch calls. */
 typedef struct iqhip_pars_op { int32_t dst, left, right, _pad; } iqhip_pars_op; /* slots */
 int iqhip_pars_init(iqhip_engine *e, const uint8_t *informative /* nptn or NULL */, int nvectors, int64_t *nsites);
 int iqhip_pars_update(iqhip_engine *e, const iqhip_pars_op *ops, int nops);
@@ -783,6 +797,12 @@ int iqhip_pars_fetch(iqhip_engine *e, int32_t slot, uint32_t *out /* nwords*nsta
 int iqhip_debug_pars_levels(int ntaxa, int nvectors, const uint8_t *valid /* nvectors or NULL */, const iqhip_pars_op *ops,
                             int nops, int32_t *level);
 int iqhip_debug_pars_timing(iqhip_engine *e, double *ms /* 2 */, int64_t *counts /* 4 */, int reset);
+int iqhip_pars_insert_scores_batch(iqhip_engine *e, const int32_t *ends /* 2*nbranch slots */,
+                                   const int32_t *seg_start /* nseg+1, seg_start[nseg] = nbranch */, int nseg,
+                                   const int32_t *taxon /* nseg tip slots */, int32_t *score /* nbranch or NULL */,
+                                   int32_t *best /* nseg */, int32_t *best_score /* nseg */);
+int iqhip_debug_pars_batch_timing(iqhip_engine *e, double *ms /* 1 */, int64_t *counts /* 3: launches, branches, segments */,
+                                  int reset);
 
 /* ---- Parsimony SPR scan (the scan inside pllComputeRandomizedStepwiseAdditionParsimonyTree's SPR rounds,
  * pll/fastDNAparsimony.c:1169-1427 rearrangeParsimony / addTraverseParsimony / testInsertParsimony): the score of every

@@ -46,6 +46,7 @@ IQHIP_SYMBOLS = [
     "iqhip_quartet_cells", "iqhip_quartet_likelihoods", "iqhip_debug_quartet_timing",
     "iqhip_pars_init", "iqhip_pars_update", "iqhip_pars_branch_scores", "iqhip_pars_insert_scores", "iqhip_pars_fetch", "iqhip_pars_shape",
     "iqhip_debug_pars_levels", "iqhip_debug_pars_timing",
+    "iqhip_pars_insert_scores_batch", "iqhip_debug_pars_batch_timing",
     "iqhip_pars_spr_scan", "iqhip_debug_pars_spr_check", "iqhip_debug_pars_spr_timing",
     "iqhip_bionj", "iqhip_debug_bionj_timing",
     "iqhip_ufboot_init", "iqhip_ufboot_update", "iqhip_ufboot_fetch", "iqhip_debug_ufboot_timing",
@@ -261,6 +262,8 @@ def libiqhip():
     lib.iqhip_pars_shape.argtypes = [vp, i64p, i64p, C.POINTER(C.c_int)]
     lib.iqhip_debug_pars_levels.argtypes = [C.c_int, C.c_int, u8p, C.POINTER(ParsOp), C.c_int, i32p]
     lib.iqhip_debug_pars_timing.argtypes = [vp, dp, i64p, C.c_int]
+    lib.iqhip_pars_insert_scores_batch.argtypes = [vp, i32p, i32p, C.c_int, i32p, i32p, i32p, i32p]
+    lib.iqhip_debug_pars_batch_timing.argtypes = [vp, dp, i64p, C.c_int]
     lib.iqhip_pars_spr_scan.argtypes = [vp, vp, C.c_int, vp, C.c_int, i32p, i32p, i32p, i32p]
     lib.iqhip_debug_pars_spr_check.argtypes = [C.c_int, C.c_int, u8p, vp, C.c_int, vp, C.c_int, i32p]
     lib.iqhip_debug_pars_spr_timing.argtypes = [vp, dp, i64p, C.c_int]
@@ -350,6 +353,12 @@ def libiqhost():
     lib.iqhost_collect_spr_jobs.argtypes = [vp, C.c_int, ipp, C.c_int, ipp, ipp, C.c_int, ipp, ipp]
     lib.iqhost_apply_spr_move.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.iqhost_optimize_parsimony_spr.argtypes = [vp, C.c_int, C.c_int, ipp, ipp, C.c_int, ipp]
+    lib.iqhost_parsimony_orders.argtypes = [C.c_uint64, C.c_int, C.c_int, ipp]
+    lib.iqhost_pars_forest_build.argtypes = [vp, ipp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64)]
+    lib.iqhost_pars_forest_free.argtypes = [vp]
+    lib.iqhost_pars_forest_free.restype = None
+    lib.iqhost_pars_forest_member.argtypes = [vp, C.c_int, ipp, ipp, ipp, C.c_char_p, C.c_int, ipp]
+    lib.iqhost_pars_forest_trace.argtypes = [vp, C.c_int, ipp, C.c_int, ipp, ipp, C.c_int]
     lib.iqhost_compute_dist.argtypes = [vp, dp, dp, dp]
     lib.iqhost_pair_counts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int, dp]
     i32q, i64q = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -754,6 +763,14 @@ def branches_for_nni(applied, adjacency):
 def search_rand(seed, iteration, draw):
     """The search's random stream: the 64-bit splitmix value keyed by (seed, iteration, draw index)."""
     return int(libiqhost().iqhost_search_rand(int(seed), int(iteration), int(draw)))
+
+
+def parsimony_orders(seed, k, ntaxa):
+    """iqsearch::parsimonyOrders: the addition orders of the k parsimony starting trees of a search with `seed` -- order j is
+    a Fisher-Yates shuffle of 0 .. ntaxa-1 on the draws search_rand(seed, 0, j * ntaxa + i) -> [k][ntaxa] lists"""
+    out = np.zeros(max(1, int(k) * int(ntaxa)), dtype=np.int32)
+    _hchk(libiqhost().iqhost_parsimony_orders(int(seed), int(k), int(ntaxa), _iptr(out)))
+    return [[int(x) for x in out[j * int(ntaxa):(j + 1) * int(ntaxa)]] for j in range(int(k))]
 
 
 def search_rand_int(z, n):
@@ -1814,6 +1831,68 @@ class PhyloTree:
                                                  None if sc is None else sc.ctypes.data_as(i32p), C.byref(best), C.byref(bs)))
         return (None if sc is None else sc[:en.shape[0]]), best.value, bs.value
 
+    def pars_insert_scores_batch(self, ends, seg_start, taxa, want_scores=True):
+        """iqhip_pars_insert_scores_batch: one stepwise-addition step of many trees.  ends [nbranch, 2] slots, seg_start
+        [nseg + 1] offsets into the branches, taxa [nseg] tip slots -> (score[nbranch] or None, best[nseg] as indices
+        within the segments, best_score[nseg])"""
+        en = np.ascontiguousarray(ends, dtype=np.int32).reshape(-1, 2)
+        ss = np.ascontiguousarray(seg_start, dtype=np.int32).reshape(-1)
+        tx = np.ascontiguousarray(taxa, dtype=np.int32).reshape(-1)
+        nseg = tx.size
+        if ss.size != nseg + 1:
+            raise HostError("pars_insert_scores_batch: seg_start needs one entry more than taxa")
+        if nseg >= 1 and ss[-1] != en.shape[0]:
+            raise HostError("pars_insert_scores_batch: seg_start must end at the number of branches")
+        sc = np.zeros(max(1, en.shape[0]), dtype=np.int32) if want_scores else None
+        best, bs = np.zeros(max(1, nseg), dtype=np.int32), np.zeros(max(1, nseg), dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _echk(libiqhip().iqhip_pars_insert_scores_batch(self._pars_engine(), en.ctypes.data_as(i32p), ss.ctypes.data_as(i32p), nseg,
+                                                       tx.ctypes.data_as(i32p), None if sc is None else sc.ctypes.data_as(i32p),
+                                                       best.ctypes.data_as(i32p), bs.ctypes.data_as(i32p)))
+        return (None if sc is None else sc[:en.shape[0]]), best[:nseg], bs[:nseg]
+
+    def pars_batch_timing(self, reset=True):
+        """iqhip_debug_pars_batch_timing -> {scan_ms, launches, branches, segments} of the batch scans since the last reset"""
+        ms, ln = C.c_double(), (C.c_int64 * 3)()
+        _echk(libiqhip().iqhip_debug_pars_batch_timing(self.engine, C.byref(ms), ln, int(reset)))
+        return dict(scan_ms=ms.value, launches=ln[0], branches=ln[1], segments=ln[2])
+
+    def compute_parsimony_forest(self, orders, spr_radius=0, trace=False):
+        """K stepwise-addition parsimony trees built in lockstep on this tree's engine (ParsimonyForest): per step ONE
+        update and ONE batch scan for all of them.  orders: K permutations of the taxa.  This tree's topology stays.
+        -> [dict(newick, score, topology, spr_moves, steps)], steps as compute_parsimony_tree's trace plus best_score (None
+        without trace).  The engine calls of the run are in self.forest_calls."""
+        T = self.num_leaves
+        od = np.ascontiguousarray(orders, dtype=np.int32).reshape(-1, T) if len(orders) else np.zeros((0, T), dtype=np.int32)
+        K = od.shape[0]
+        res, calls = C.c_void_p(), (C.c_int64 * 5)()
+        self._chk(self.lib.iqhost_pars_forest_build(self.h, _iptr(od) if K else None, K, int(spr_radius), int(trace),
+                                                    C.byref(res), calls))
+        self.forest_calls = dict(updates=calls[0], scans=calls[1], branch_scores=calls[2], spr_scans=calls[3], inits=calls[4])
+        out = []
+        try:
+            for k in range(K):
+                score, spr, nrows, need = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+                self._chk(self.lib.iqhost_pars_forest_member(res, k, C.byref(score), C.byref(spr), C.byref(nrows), None, 0, C.byref(need)))
+                buf = C.create_string_buffer(need.value)
+                self._chk(self.lib.iqhost_pars_forest_member(res, k, C.byref(score), C.byref(spr), C.byref(nrows), buf, len(buf), C.byref(need)))
+                newick, topology = buf.value.decode().split("\n")
+                steps = None
+                if trace:
+                    ns = max(0, T - 3)
+                    rows = (C.c_int * (4 * max(1, nrows.value)))()
+                    chosen, best = (C.c_int * max(1, ns))(), (C.c_int * max(1, ns))()
+                    self._chk(self.lib.iqhost_pars_forest_trace(res, k, rows, nrows.value, chosen, best, ns))
+                    steps = [dict(branches=[], scores=[], chosen=chosen[s], best_score=best[s]) for s in range(ns)]
+                    for q in range(nrows.value):
+                        st = steps[rows[4 * q]]
+                        st["branches"].append((rows[4 * q + 1], rows[4 * q + 2]))
+                        st["scores"].append(rows[4 * q + 3])
+                out.append(dict(newick=newick, score=score.value, topology=topology, spr_moves=spr.value, steps=steps))
+        finally:
+            self.lib.iqhost_pars_forest_free(res)
+        return out
+
     def pars_fetch(self, slot):
         """iqhip_pars_fetch -> (planes[nwords, nstates] uint32 in the reference's layout, subtree score)"""
         nwords = self.pars_shape()[1]
@@ -2192,17 +2271,26 @@ class TreeSearch:
     every evaluated tree feeds the bootstrap and the correlation rule applies: every step_iterations iterations the split
     frequencies of the bootstrap winners are correlated (correlation_log); the search ends when the correlation reaches
     min_correlation and num_stop iterations brought no better tree, or after max_iterations (with `iterations` given: after
-    min(iterations, max_iterations))."""
+    min(iterations, max_iterations)).
+    num_init_trees > 0: the reference's initCandidateTreeSet first -- the given tree plus num_init_trees - 1 parsimony trees
+    built in lockstep on the orders of parsimony_orders(seed, ...) (with init_spr_radius > 0 followed by SPR rounds),
+    duplicate topologies dropped (init_duplicates), each scored with optimize_all_branches(2) (init_trees), the best
+    num_nni_trees optimised by NNI as the iterations 1 .. M; `iterations` counts the iterations after those (with UFBoot it
+    caps max_iterations, which counts every iteration, as in the reference)."""
 
     def __init__(self, tree, seed=0, nni5=True, speed=True, pop_size=5, pers=0.5, iterations=None, num_stop=100, batched=True,
-                 step_iterations=100, min_correlation=0.99, max_iterations=1000):
+                 step_iterations=100, min_correlation=0.99, max_iterations=1000, num_init_trees=0, num_nni_trees=20,
+                 init_spr_radius=0):
         self.lib = libiqhost()
         self.tree = tree
         self.h = C.c_void_p()
         _hchk(self.lib.iqhost_search_create(C.byref(self.h), tree.h))
         self.params = dict(seed=seed, nni5=nni5, speed=speed, pop_size=pop_size, pers=pers, iterations=iterations,
                            num_stop=num_stop, batched=batched, step_iterations=step_iterations,
-                           min_correlation=min_correlation, max_iterations=max_iterations)
+                           min_correlation=min_correlation, max_iterations=max_iterations, num_init_trees=num_init_trees,
+                           num_nni_trees=num_nni_trees, init_spr_radius=init_spr_radius)
+        self.init_trees = []        # after search(): [(score, tree, topology)] of the distinct starting trees, in generation order
+        self.init_duplicates = 0    # parsimony trees that repeated an earlier topology
         self.best_score = None
         self.correlation_log = []
         self._trace = None
@@ -2230,7 +2318,8 @@ class TreeSearch:
             cond = SC_UNSUCCESS_ITERATION if p["iterations"] is None else SC_FIXED_ITERATION
             max_it = p["max_iterations"]
         iv = np.array([p["nni5"], p["speed"], p["batched"], p["pop_size"], cond,
-                       int(p["iterations"] or 0), p["num_stop"], max_it, p["step_iterations"], trace], dtype=np.int32)
+                       int(p["iterations"] or 0), p["num_stop"], max_it, p["step_iterations"], trace,
+                       p["num_init_trees"], p["num_nni_trees"], p["init_spr_radius"]], dtype=np.int32)
         dv = np.array([p["pers"], p["min_correlation"]], dtype=np.float64)
         _hchk(self.lib.iqhost_search_set_params(self.h, _iptr(iv), _dptr(dv), int(p["seed"])))
 
@@ -2277,6 +2366,8 @@ class TreeSearch:
         self.correlation_log = [(int(i), float(c)) for i, c in t["correlation_log"]]
         self.boot_splits = t["boot_splits"]
         self._candidates = [(c[0], c[1], c[2]) for c in t["candidates"]]
+        self.init_trees = [(c[0], c[1], c[2]) for c in t["init_trees"]]
+        self.init_duplicates = int(t["init_duplicates"])
         return (best.value, t["iterations"]) if trace else best.value
 
     def candidates(self):

@@ -671,6 +671,8 @@ struct iqhip_engine {
     int64_t pars_counts[4] = {0, 0, 0, 0};   // launches of the updates and of the scans, ops updated, branches scanned
     double pars_spr_ms = 0.0;           // iqhip_debug_pars_spr_timing: the SPR scan launches (while timing is enabled) ...
     int64_t pars_spr_counts[2] = {0, 0};   // ... their number and the steps scored
+    double pars_batch_ms = 0.0;         // iqhip_debug_pars_batch_timing: the segmented insertion scans (while timing is enabled) ...
+    int64_t pars_batch_counts[3] = {0, 0, 0};   // ... their launches (scores + first minima), branches and segments
     iqhip::DevBuf<int32_t> d_batch_rows;   // iqhip_optimize_branch_batch_rows: store row per task of a chunk
     // the result vector the kernels write: d_result_own is the device address of h_result, d_result that or d_result_dev
     double *d_result_own = nullptr, *d_result = nullptr;
@@ -1351,6 +1353,16 @@ hipError_t launch_pars_tips(iqhip_engine *e, const int32_t *d_site_ptn);
 hipError_t launch_pars_update(iqhip_engine *e, const iqhip_pars_op *d_ops, const int32_t *d_lev_start, int nlev);
 // d_out: score [nbranch] ++ subst [nbranch]; taxon >= 0: the insertion scan, which also writes {best, best_score} behind them
 hipError_t launch_pars_branch(iqhip_engine *e, const int32_t *d_ends, int nbranch, int taxon, int32_t *d_out, int *nlaunches);
+// the segmented insertion scan (iqhip_pars_insert_scores_batch): a wave per branch while nwords <= kParsBatchWaveWords (a
+// wave then makes at most 4 passes over its 64 columns), a workgroup per branch above.  NOT MEASURED: the threshold is a
+// guess from the shapes; tools/bench_pars_forest.py reports both routes (IQHIP_PARS_BATCH_ROUTE forces one) so that a
+// later change can move it.
+constexpr int64_t kParsBatchWaveWords = 256;
+enum ParsBatchRoute { PARS_BATCH_AUTO = 0, PARS_BATCH_WAVE = 1, PARS_BATCH_WG = 2 };
+// d_ends: 2 * nbranch slots; d_taxon: the tip slot of every branch; d_seg_start: nseg + 1 offsets into the branches;
+// d_out = score [nbranch] ++ best [nseg] (index within the segment) ++ best_score [nseg]
+hipError_t launch_pars_insert_batch(iqhip_engine *e, const int32_t *d_ends, const int32_t *d_taxon, int nbranch,
+                                    const int32_t *d_seg_start, int nseg, ParsBatchRoute route, int32_t *d_out, int *nlaunches);
 // the SPR scan (kernels_spr.hip): d_steps carry the depth in `parent`; d_out = score [nsteps] ++ best_step [njobs] ++
 // best_score [njobs] ++ best_job; max_depth = the deepest step of the launch (sizes the LDS stack)
 hipError_t launch_pars_spr(iqhip_engine *e, const iqhip_pars_spr_job *d_jobs, int njobs, const iqhip_pars_spr_step *d_steps,

@@ -24,6 +24,9 @@
 //   k_pars_branch   computeParsimonyBranchFast (:218-282) / the insertion scan of addTaxonMPFast (:428-465): one workgroup
 //       per branch, columns strided over its threads, shuffle reduction per wave and a cross-wave sum in LDS
 //   k_pars_argmin   the first minimum of the scan's scores in list order (one workgroup)
+//   k_pars_insert_wave / k_pars_insert_wg / k_pars_argmin_seg   the insertion scan of MANY trees in one launch: segments of
+//       branches with a taxon each (one stepwise-addition step of a whole forest), a wave or a workgroup per branch, and a
+//       workgroup per segment for its first minimum
 #include <hip/hip_runtime.h>
 
 #include "iqhip_internal.h"
@@ -197,12 +200,11 @@ __global__ __launch_bounds__(256) void k_pars_branch(const uint32_t *__restrict_
     }
 }
 
-// out[2 nbranch] = the first index of the smallest score, out[2 nbranch + 1] = that score
-__global__ __launch_bounds__(256) void k_pars_argmin(int32_t *out, int nbranch) {
-    __shared__ int32_t s_score[256], s_idx[256];
+// the first minimum of score[lo .. hi) by a workgroup of 256 threads: afterwards s_idx[0] = its index, s_score[0] = it
+__device__ __forceinline__ void pars_block_argmin(const int32_t *score, int lo, int hi, int32_t *s_score, int32_t *s_idx) {
     int32_t best = 0x7fffffff, at = 0x7fffffff;
-    for (int b = threadIdx.x; b < nbranch; b += 256) {   // (ascending b: a strict < keeps the first)
-        const int32_t s = out[b];
+    for (int b = lo + (int)threadIdx.x; b < hi; b += 256) {   // (ascending b: a strict < keeps the first)
+        const int32_t s = score[b];
         if (s < best) {
             best = s;
             at = b;
@@ -221,9 +223,103 @@ __global__ __launch_bounds__(256) void k_pars_argmin(int32_t *out, int nbranch) 
         }
         __syncthreads();
     }
+}
+
+// out[2 nbranch] = the first index of the smallest score, out[2 nbranch + 1] = that score
+__global__ __launch_bounds__(256) void k_pars_argmin(int32_t *out, int nbranch) {
+    __shared__ int32_t s_score[256], s_idx[256];
+    pars_block_argmin(out, 0, nbranch, s_score, s_idx);
     if (threadIdx.x == 0) {
         out[2 * nbranch] = s_idx[0];
         out[2 * nbranch + 1] = s_score[0];
+    }
+}
+
+// ---- the segmented insertion scan (iqhip_pars_insert_scores_batch) ------------------------------------------------------
+// Branch b of segment g against the tip taxon[b] (the host expands the segment's taxon to its branches): one scoring
+// function, two ways to share the columns out.  The vectors were written by an earlier launch on the same stream and are
+// only read here.  Nothing is accumulated across workgroups and there are no atomics: a branch's sum is one wave's (or one
+// workgroup's) fixed reduction tree, so every run gives the same bits.
+//
+// the insertion score of word column w -- k_pars_branch<N, true>'s term: m = fitch(a, c) in registers, then
+// a_score + c_score + popc(w_ac) + popc(~OR_i(m_i & t_i))
+template <int N>
+__device__ __forceinline__ uint32_t pars_insert_word(const uint32_t *__restrict__ va, const uint32_t *__restrict__ vc,
+                                                     const uint32_t *__restrict__ vt, const uint32_t *__restrict__ sa,
+                                                     const uint32_t *__restrict__ sc, int64_t nwords, int64_t w) {
+    uint32_t cost, anyt = 0;
+    if constexpr (N <= 20) {
+        uint32_t x[N], y[N], t[N];
+        pars_load<N>(va, nwords, w, x);
+        pars_load<N>(vc, nwords, w, y);
+        pars_load<N>(vt, nwords, w, t);
+        cost = pars_fitch<N>(x, y);
+#pragma unroll
+        for (int i = 0; i < N; i++) anyt |= x[i] & t[i];
+    } else {   // 64 states: the planes are streamed in two passes, as in k_pars_update, instead of 192 registers of columns
+        uint32_t any = 0;
+#pragma unroll 4
+        for (int i = 0; i < N; i++) any |= va[(size_t)i * nwords + w] & vc[(size_t)i * nwords + w];
+        cost = ~any;
+#pragma unroll 4
+        for (int i = 0; i < N; i++) {
+            const uint32_t xi = va[(size_t)i * nwords + w], yi = vc[(size_t)i * nwords + w];
+            anyt |= ((xi & yi) | (cost & (xi | yi))) & vt[(size_t)i * nwords + w];
+        }
+    }
+    return sa[w] + sc[w] + (uint32_t)__popc(cost) + (uint32_t)__popc(~anyt);
+}
+
+// the partial sum of a branch over the columns first, first + stride, ...
+template <int N>
+__device__ __forceinline__ uint32_t pars_insert_partial(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ score,
+                                                        const int32_t *__restrict__ ends, const int32_t *__restrict__ taxon, int b,
+                                                        int64_t nwords, int first, int stride) {
+    const int a = ends[2 * b], c = ends[2 * b + 1], t = taxon[b];
+    const size_t vstride = (size_t)nwords * N;
+    const uint32_t *va = vec + (size_t)a * vstride, *vc = vec + (size_t)c * vstride, *vt = vec + (size_t)t * vstride;
+    const uint32_t *sa = score + (size_t)a * nwords, *sc = score + (size_t)c * nwords;
+    uint32_t total = 0;
+    for (int64_t w = first; w < nwords; w += stride) total += pars_insert_word<N>(va, vc, vt, sa, sc, nwords, w);
+    return total;
+}
+
+// wave per branch: four branches per workgroup, columns strided over the 64 lanes, shuffle reduction, no LDS and no
+// __syncthreads() -- so a wave whose branch lies past the list simply returns
+template <int N>
+__global__ __launch_bounds__(256) void k_pars_insert_wave(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ score,
+                                                          const int32_t *__restrict__ ends, const int32_t *__restrict__ taxon,
+                                                          int nbranch, int64_t nwords, int32_t *__restrict__ out) {
+    const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (b >= nbranch) return;   // (wave-uniform)
+    uint32_t total = pars_insert_partial<N>(vec, score, ends, taxon, b, nwords, (int)(threadIdx.x & 63), 64);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off);
+    if ((threadIdx.x & 63) == 0) out[b] = (int32_t)total;
+}
+
+// workgroup per branch: the shape of k_pars_branch
+template <int N>
+__global__ __launch_bounds__(256) void k_pars_insert_wg(const uint32_t *__restrict__ vec, const uint32_t *__restrict__ score,
+                                                        const int32_t *__restrict__ ends, const int32_t *__restrict__ taxon,
+                                                        int nbranch, int64_t nwords, int32_t *__restrict__ out) {
+    __shared__ uint32_t s_red[4];
+    const int b = blockIdx.x;   // (the grid is nbranch workgroups)
+    uint32_t total = pars_insert_partial<N>(vec, score, ends, taxon, b, nwords, (int)threadIdx.x, 256);
+    total = pars_block_sum(total, s_red);
+    if (threadIdx.x == 0) out[b] = (int32_t)total;
+}
+
+// one workgroup per segment: out[nbranch + g] = the first minimum of the segment's scores as an index within the segment,
+// out[nbranch + nseg + g] = that score (k_pars_argmin's tie rule: the same reduction)
+__global__ __launch_bounds__(256) void k_pars_argmin_seg(int32_t *out, const int32_t *__restrict__ seg_start, int nbranch, int nseg) {
+    __shared__ int32_t s_score[256], s_idx[256];
+    const int g = blockIdx.x;
+    const int lo = seg_start[g];
+    pars_block_argmin(out, lo, seg_start[g + 1], s_score, s_idx);
+    if (threadIdx.x == 0) {
+        out[nbranch + g] = s_idx[0] - lo;
+        out[nbranch + nseg + g] = s_score[0];
     }
 }
 
@@ -270,6 +366,34 @@ hipError_t launch_pars_branch(iqhip_engine *e, const int32_t *d_ends, int nbranc
         s = hipGetLastError();
         *nlaunches = 2;
     }
+    return s;
+}
+
+hipError_t launch_pars_insert_batch(iqhip_engine *e, const int32_t *d_ends, const int32_t *d_taxon, int nbranch,
+                                    const int32_t *d_seg_start, int nseg, ParsBatchRoute route, int32_t *d_out, int *nlaunches) {
+    *nlaunches = 0;
+    if (nbranch < 1 || nseg < 1) return hipSuccess;
+    const bool wave = route == PARS_BATCH_WAVE || (route == PARS_BATCH_AUTO && e->pars_nwords <= kParsBatchWaveWords);
+#define IQHIP_PARS_INSERT(N)                                                                                                 \
+    do {                                                                                                                     \
+        if (wave)                                                                                                            \
+            hipLaunchKernelGGL(k_pars_insert_wave<N>, dim3((unsigned)((nbranch + 3) / 4)), dim3(256), 0, e->stream,          \
+                               e->pars.vec.p, e->pars.score.p, d_ends, d_taxon, nbranch, e->pars_nwords, d_out);             \
+        else                                                                                                                 \
+            hipLaunchKernelGGL(k_pars_insert_wg<N>, dim3((unsigned)nbranch), dim3(256), 0, e->stream, e->pars.vec.p,         \
+                               e->pars.score.p, d_ends, d_taxon, nbranch, e->pars_nwords, d_out);                            \
+    } while (0)
+    if (e->n == 4) IQHIP_PARS_INSERT(4);
+    else if (e->n == 20) IQHIP_PARS_INSERT(20);
+    else if (e->n == 64) IQHIP_PARS_INSERT(64);
+    else return hipErrorInvalidValue;
+#undef IQHIP_PARS_INSERT
+    hipError_t s = hipGetLastError();
+    if (s != hipSuccess) return s;
+    *nlaunches = 1;
+    hipLaunchKernelGGL(k_pars_argmin_seg, dim3((unsigned)nseg), dim3(256), 0, e->stream, d_out, d_seg_start, nbranch, nseg);
+    s = hipGetLastError();
+    if (s == hipSuccess) *nlaunches = 2;
     return s;
 }
 

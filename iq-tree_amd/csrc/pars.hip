@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -246,6 +247,80 @@ extern "C" int iqhip_pars_insert_scores(iqhip_engine *e, const int32_t *ends, in
     if (score) memcpy(score, out.data(), sizeof(int32_t) * (size_t)nbranch);
     if (best) *best = out[count - 2];
     if (best_score) *best_score = out[count - 1];
+    return IQHIP_OK;
+}
+
+// ---- the segmented insertion scan: one stepwise-addition step of many trees ------------------------------------------------
+extern "C" int iqhip_pars_insert_scores_batch(iqhip_engine *e, const int32_t *ends, const int32_t *seg_start, int nseg,
+                                              const int32_t *taxon, int32_t *score, int32_t *best, int32_t *best_score) {
+    const char *what = "iqhip_pars_insert_scores_batch";
+    int rc = pars_require(e, what, true);
+    if (rc) return rc;
+    // IQHIP_PARS_BATCH_ROUTE, read per call: wave | wg forces a route; any other word is refused
+    ParsBatchRoute route = PARS_BATCH_AUTO;
+    if (const char *w = getenv("IQHIP_PARS_BATCH_ROUTE")) {
+        if (!strcmp(w, "wave")) route = PARS_BATCH_WAVE;
+        else if (!strcmp(w, "wg")) route = PARS_BATCH_WG;
+        else return fail(IQHIP_ERR_INVALID, std::string(what) + ": IQHIP_PARS_BATCH_ROUTE must be wave or wg, not '" + w + "'");
+    }
+    if (!ends || !seg_start || !taxon || !best || !best_score) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null argument");
+    if (nseg < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": nseg < 1");
+    if (seg_start[0] != 0) return fail(IQHIP_ERR_INVALID, std::string(what) + ": seg_start[0] != 0");
+    for (int g = 0; g < nseg; g++) {
+        if (seg_start[g + 1] <= seg_start[g])
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": seg_start is not strictly increasing (segment " + std::to_string(g) + " is empty)");
+        if (taxon[g] < 0 || taxon[g] >= e->ntaxa)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": taxon " + std::to_string(g) + " is not a tip slot");
+    }
+    const int nbranch = seg_start[nseg];
+    rc = pars_check_ends(e, what, ends, nbranch);
+    if (rc) return rc;
+    // one upload from pinned staging: ends ++ the taxon of every branch ++ seg_start; the results are score [nbranch] ++
+    // best [nseg] ++ best_score [nseg], of which only the last 2 nseg come back without `score`
+    const size_t nblob = (size_t)3 * nbranch + (size_t)nseg + 1, nout = (size_t)nbranch + 2 * (size_t)nseg;
+    const size_t from = score ? 0 : (size_t)nbranch, count = nout - from;
+    HIPCHK(use_device(e));
+    HIPCHK(e->pars.ints.ensure(e, nblob));
+    HIPCHK(e->pars.out.ensure(e, nout));
+    if (nblob > e->h_pars_ends.cap) HIPCHK(e->h_pars_ends.ensure(e, pars_grown(nblob)));
+    if (count > e->h_pars_out.cap) HIPCHK(e->h_pars_out.ensure(e, pars_grown(count)));
+    // (no copy of h_pars_ends or into h_pars_out is in flight: every call that uses them ends with a synchronise)
+    int32_t *blob = e->h_pars_ends.p;
+    memcpy(blob, ends, sizeof(int32_t) * 2 * (size_t)nbranch);
+    for (int g = 0; g < nseg; g++) std::fill(blob + 2 * (size_t)nbranch + seg_start[g], blob + 2 * (size_t)nbranch + seg_start[g + 1], taxon[g]);
+    memcpy(blob + 3 * (size_t)nbranch, seg_start, sizeof(int32_t) * ((size_t)nseg + 1));
+    HIPCHK(hipMemcpyAsync(e->pars.ints.p, blob, sizeof(int32_t) * nblob, hipMemcpyHostToDevice, e->stream));
+    PhaseTimer timer(e, 1);
+    int nlaunches = 0;
+    timer.mark();
+    HIPCHK(launch_pars_insert_batch(e, e->pars.ints.p, e->pars.ints.p + 2 * (size_t)nbranch, nbranch, e->pars.ints.p + 3 * (size_t)nbranch,
+                                    nseg, route, e->pars.out.p, &nlaunches));
+    timer.mark();
+    e->pars_batch_counts[0] += nlaunches;
+    e->pars_batch_counts[1] += nbranch;
+    e->pars_batch_counts[2] += nseg;
+    pars_add_ms(timer, &e->pars_batch_ms);
+    HIPCHK(hipMemcpyAsync(e->h_pars_out.p, e->pars.out.p + from, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int32_t *res = e->h_pars_out.p;
+    if (score) {
+        memcpy(score, res, sizeof(int32_t) * (size_t)nbranch);
+        res += nbranch;
+    }
+    memcpy(best, res, sizeof(int32_t) * (size_t)nseg);
+    memcpy(best_score, res + nseg, sizeof(int32_t) * (size_t)nseg);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_pars_batch_timing(iqhip_engine *e, double *ms, int64_t *counts, int reset) {
+    if (!e || !e->shards.empty() || e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_pars_batch_timing: needs a single-device engine");
+    if (ms) *ms = e->pars_batch_ms;
+    for (int k = 0; k < 3; k++)
+        if (counts) counts[k] = e->pars_batch_counts[k];
+    if (reset) {
+        e->pars_batch_ms = 0.0;
+        for (int k = 0; k < 3; k++) e->pars_batch_counts[k] = 0;
+    }
     return IQHIP_OK;
 }
 

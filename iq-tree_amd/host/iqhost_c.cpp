@@ -15,6 +15,7 @@
 #include "bfgs_host.h"
 #include "brent_host.h"
 #include "model_opt_host.h"
+#include "pars_forest_host.h"
 #include "phylo_host.h"
 #include "search_host.h"
 #include "supertree_host.h"
@@ -840,6 +841,73 @@ int iqhost_optimize_parsimony_spr(void *h, int radius, int max_rounds, int *scor
         if (nrounds) *nrounds = (int)rounds.size();
     });
 }
+// ---- the parsimony forest (pars_forest_host.h).  orders: K rows of ntaxa taxon ids.  *out = a result handle for the
+// accessors below, freed with iqhost_pars_forest_free.  calls: updates, batch scans, branch-scores calls, SPR scans, inits
+int iqhost_parsimony_orders(uint64_t seed, int K, int ntaxa, int *out) {
+    IQHOST_TRY({
+        if (K < 0 || ntaxa < 0) throw std::runtime_error("parsimony_orders: negative count");
+        const std::vector<std::vector<int>> o = iqsearch::parsimonyOrders(seed, K, ntaxa);
+        for (int k = 0; k < K; k++)
+            for (int i = 0; i < ntaxa; i++) out[(size_t)k * ntaxa + i] = o[(size_t)k][(size_t)i];
+    });
+}
+int iqhost_pars_forest_build(void *h, const int *orders, int K, int spr_radius, int trace, void **out, int64_t *calls) {
+    IQHOST_TRY({
+        PhyloTree *t = (PhyloTree *)h;
+        *out = nullptr;
+        if (K < 0) throw std::runtime_error("compute_parsimony_forest: negative count");
+        std::vector<std::vector<int>> ord((size_t)K);
+        for (int k = 0; k < K; k++) ord[(size_t)k].assign(orders + (size_t)k * t->leafNum, orders + (size_t)(k + 1) * t->leafNum);
+        std::unique_ptr<ParsimonyForest> f(new ParsimonyForest(t));
+        f->spr_radius = spr_radius;
+        f->keep_trace = trace != 0;
+        f->build(ord);
+        if (calls) {
+            calls[0] = f->calls.updates; calls[1] = f->calls.scans; calls[2] = f->calls.branch_scores;
+            calls[3] = f->calls.spr_scans; calls[4] = f->calls.inits;
+        }
+        *out = f.release();
+    });
+}
+void iqhost_pars_forest_free(void *f) { delete (ParsimonyForest *)f; }
+// text: Newick, newline, topology; nrows = the trace rows of the member
+int iqhost_pars_forest_member(void *f, int k, int *score, int *spr_rounds, int *nrows, char *text, int cap, int *need) {
+    IQHOST_TRY({
+        ParsimonyForest *pf = (ParsimonyForest *)f;
+        if (k < 0 || k >= (int)pf->members.size()) throw std::runtime_error("forest member out of range");
+        const ParsimonyForest::Member &m = pf->members[(size_t)k];
+        *score = m.score;
+        *spr_rounds = m.spr_rounds;
+        int rows = 0;
+        for (const PhyloTree::ParsStep &s : m.steps) rows += (int)s.node1.size();
+        *nrows = rows;
+        const std::string s = m.newick + "\n" + m.topology;
+        if (need) *need = (int)s.size() + 1;
+        if (text && (int)s.size() + 1 <= cap) memcpy(text, s.c_str(), s.size() + 1);
+    });
+}
+// trace: rows of (step, node1, node2, score) as iqhost_compute_parsimony_tree; chosen / best: one entry per step
+int iqhost_pars_forest_trace(void *f, int k, int *trace, int trace_cap, int *chosen, int *best, int steps_cap) {
+    IQHOST_TRY({
+        ParsimonyForest *pf = (ParsimonyForest *)f;
+        if (k < 0 || k >= (int)pf->members.size()) throw std::runtime_error("forest member out of range");
+        const std::vector<PhyloTree::ParsStep> &steps = pf->members[(size_t)k].steps;
+        int rows = 0;
+        for (size_t s = 0; s < steps.size(); s++) {
+            if ((int)s < steps_cap) {
+                chosen[s] = steps[s].chosen;
+                best[s] = steps[s].best_score;
+            }
+            for (size_t q = 0; q < steps[s].node1.size(); q++, rows++)
+                if (rows < trace_cap) {
+                    trace[4 * rows] = (int)s;
+                    trace[4 * rows + 1] = steps[s].node1[q];
+                    trace[4 * rows + 2] = steps[s].node2[q];
+                    trace[4 * rows + 3] = steps[s].score[q];
+                }
+        }
+    });
+}
 int iqhost_sync_inputs(void *h) { IQHOST_TRY(((PhyloTree *)h)->syncInputs()); }
 int iqhost_compute_all_partial_lh(void *h) { IQHOST_TRY(((PhyloTree *)h)->computeAllPartialLh()); }
 int iqhost_last_plan(void *h, int *ints, double *lens, uint64_t *keys, int cap) {
@@ -1191,10 +1259,11 @@ int iqhost_search_create(void **out, void *tree) {
 }
 void iqhost_search_destroy(void *s) { delete (SearchHandle *)s; }
 // iv: nni5, speednni, batched, popSize, stop condition, min_iteration, unsuccess_iteration, max_iteration, step_iterations,
-// keep_trace; dv: initPS, min_correlation
+// keep_trace, numInitTrees, numNNITrees, initSprRadius; dv: initPS, min_correlation
 int iqhost_search_set_params(void *s, const int *iv, const double *dv, uint64_t seed) {
     IQHOST_TRY({
         TreeSearch &ts = ((SearchHandle *)s)->search;
+        ts.numInitTrees = iv[10]; ts.numNNITrees = iv[11]; ts.initSprRadius = iv[12];
         ts.nni5 = iv[0] != 0; ts.speednni = iv[1] != 0; ts.batched = iv[2] != 0; ts.popSize = iv[3];
         if (iv[4] < 0 || iv[4] > 2) throw std::runtime_error("TreeSearch: unknown stop condition");
         ts.stop_rule.stop_condition = (iqsearch::StopCondition)iv[4];
@@ -1249,6 +1318,11 @@ int iqhost_search_trace_json(void *s, char *out, int cap, int *need) {
         j += "],\"candidates\":[";
         for (size_t k = 0; k < ts.candidates.size(); k++) {
             const iqsearch::CandidateTree &c = ts.candidates.byRank(k);
+            j += (k ? ",[" : "[") + jnum(c.score) + "," + jstring(c.tree) + "," + jstring(c.topology) + "]";
+        }
+        j += "],\"init_duplicates\":" + std::to_string(ts.init_duplicates) + ",\"init_trees\":[";
+        for (size_t k = 0; k < ts.init_trees.size(); k++) {
+            const iqsearch::CandidateTree &c = ts.init_trees[k];
             j += (k ? ",[" : "[") + jnum(c.score) + "," + jstring(c.tree) + "," + jstring(c.topology) + "]";
         }
         j += "],\"correlation_log\":[";

@@ -1676,25 +1676,33 @@ void PhyloTree::needParsimony(const char *what) {
     if (!pars_initialized) initializeAllPartialPars();
 }
 
-void PhyloTree::initializeAllPartialPars() {
-    if (!engine || dry_run) throw std::runtime_error("initializeAllPartialPars needs an attached engine");
-    if (!root) throw std::runtime_error("no tree");
-    pushInputs();
+int64_t PhyloTree::parsInformativeSites() {
     // parsimony-informative patterns: Alignment::isInformative, the rule of computeConst, asked of this tree's data type
     Alignment rule;
     rule.seq_type = seq_type;
     rule.num_states = num_states;
     rule.STATE_UNKNOWN = STATE_UNKNOWN;
     pars_informative.assign((size_t)nptn, 0);
-    for (int64_t p = 0; p < nptn; p++)
+    int64_t total = 0;
+    for (int64_t p = 0; p < nptn; p++) {
         pars_informative[(size_t)p] = rule.isInformative(aln_states.data() + p, leafNum, (size_t)nptn);
+        if (pars_informative[(size_t)p]) total += (int64_t)ptn_freq[(size_t)p];
+    }
+    return total;
+}
+
+void PhyloTree::initializeAllPartialPars() {
+    if (!engine || dry_run) throw std::runtime_error("initializeAllPartialPars needs an attached engine");
+    if (!root) throw std::runtime_error("no tree");
+    pushInputs();
+    parsInformativeSites();
     check(iqhip_pars_init(engine, pars_informative.data(), 4 * (leafNum - 1), &pars_nsites), "iqhip_pars_init");
     assignParsSlots();
     pars_initialized = true;
 }
 
 void PhyloTree::assignParsSlots() {   // one slot per directed vector that is not a tip's; every parsimony flag goes down
-    pars_next_slot = leafNum;
+    pars_next_slot = pars_slot_base < 0 ? leafNum : pars_slot_base;
     for (PhyloNeighbor *nb : all_neighbors) {
         nb->pars_slot = nb->node->isLeaf() ? nb->node->id : pars_next_slot++;
         nb->partial_lh_computed &= ~2;
@@ -1760,13 +1768,17 @@ int PhyloTree::computeParsimony() {
 void PhyloTree::computeAllPartialPars() {
     needParsimony("computeAllPartialPars");
     std::vector<iqhip_pars_op> ops;
+    collectAllParsOps(ops);
+    submitParsOps(ops);
+}
+
+void PhyloTree::collectAllParsOps(std::vector<iqhip_pars_op> &ops) {
     std::vector<PhyloNode *> n1, n2;
     getBranches(n1, n2);
     for (size_t k = 0; k < n1.size(); k++) {
         collectParsOps(n1[k]->findNeighbor(n2[k]), n1[k], ops);
         collectParsOps(n2[k]->findNeighbor(n1[k]), n2[k], ops);
     }
-    submitParsOps(ops);
 }
 
 void PhyloTree::getBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2, PhyloNode *node, PhyloNode *dad) const {
@@ -1780,13 +1792,11 @@ void PhyloTree::getBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode 
         }
 }
 
-int PhyloTree::fixNegativeBranch(bool force) {
-    if (!root) throw std::runtime_error("no tree");
+void PhyloTree::fixBranchList(std::vector<PhyloNeighbor *> &all, std::vector<PhyloNode *> &from) const {
     // the branches in the reference's recursion order: (node, neighbour) from the root downwards
-    std::vector<PhyloNeighbor *> todo, all;
     struct Rec {
         std::vector<PhyloNeighbor *> &all;
-        std::vector<PhyloNode *> from;
+        std::vector<PhyloNode *> &from;
         void go(PhyloNode *node, PhyloNode *dad) {
             for (PhyloNeighbor *nb : node->neighbors)
                 if (nb->node != dad) {
@@ -1795,27 +1805,40 @@ int PhyloTree::fixNegativeBranch(bool force) {
                     go(nb->node, node);
                 }
         }
-    } rec{all, {}};
+    } rec{all, from};
     rec.go(root, nullptr);
+}
+
+int PhyloTree::fixNegativeBranch(bool force) {
+    if (!root) throw std::runtime_error("no tree");
+    std::vector<PhyloNeighbor *> all;
+    std::vector<PhyloNode *> from;
+    fixBranchList(all, from);
     std::vector<int32_t> ends;
+    size_t ntodo = 0;
     for (size_t k = 0; k < all.size(); k++)
-        if (all[k]->length < 0.0 || force) todo.push_back(all[k]);
-    std::vector<int32_t> subst(todo.size());
-    if (!todo.empty()) {
+        if (all[k]->length < 0.0 || force) ntodo++;
+    std::vector<int32_t> subst(ntodo);
+    if (ntodo) {
         computeAllPartialPars();
         for (size_t k = 0; k < all.size(); k++)
             if (all[k]->length < 0.0 || force) {
                 ends.push_back(all[k]->pars_slot);
-                ends.push_back(all[k]->node->findNeighbor(rec.from[k])->pars_slot);
+                ends.push_back(all[k]->node->findNeighbor(from[k])->pars_slot);
             }
-        check(iqhip_pars_branch_scores(engine, ends.data(), (int)todo.size(), nullptr, subst.data()), "iqhip_pars_branch_scores");
+        check(iqhip_pars_branch_scores(engine, ends.data(), (int)ntodo, nullptr, subst.data()), "iqhip_pars_branch_scores");
     }
     double nsite = 0.0;   // getAlnNSite()
     for (double f : ptn_freq) nsite += f;
+    return applyParsLengths(all, from, subst.data(), force, nsite);
+}
+
+int PhyloTree::applyParsLengths(const std::vector<PhyloNeighbor *> &all, const std::vector<PhyloNode *> &from, const int32_t *subst,
+                                bool force, double nsite) {
     int fixed = 0;
     size_t q = 0;
     for (size_t k = 0; k < all.size(); k++) {
-        PhyloNeighbor *nb = all[k], *back = nb->node->findNeighbor(rec.from[k]);
+        PhyloNeighbor *nb = all[k], *back = nb->node->findNeighbor(from[k]);
         if (nb->length < 0.0 || force) {
             const int branch_subst = subst[q++];
             double branch_length = (branch_subst > 0) ? ((double)branch_subst / nsite) : (1.0 / nsite);
@@ -1836,10 +1859,8 @@ int PhyloTree::fixNegativeBranch(bool force) {
     return fixed;
 }
 
-int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep> *trace) {
-    if (!engine || dry_run) throw std::runtime_error("computeParsimonyTree needs an attached engine");
+void PhyloTree::startParsimonyTree(const int *taxon_order, const std::vector<std::string> &names) {
     const int size = leafNum;
-    if (size < 3) throw std::runtime_error("computeParsimonyTree needs at least 3 taxa");
     {
         std::vector<char> seen((size_t)size, 0);
         for (int k = 0; k < size; k++) {
@@ -1848,35 +1869,101 @@ int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep
             seen[(size_t)taxon_order[k]] = 1;
         }
     }
-    std::vector<std::string> names((size_t)size);
-    for (int k = 0; k < size && k < (int)nodes.size(); k++)
-        if (nodes[(size_t)k]) names[(size_t)k] = nodes[(size_t)k]->name;
     deleteAllPartialLh();
     freeTree();
     nodes.assign((size_t)(2 * size - 2), nullptr);
-    auto new_node = [&](int id) {
-        PhyloNode *nd = new PhyloNode();
-        nd->id = id;
-        if (id < size) nd->name = names[(size_t)id];
-        nodes[(size_t)id] = nd;
-        return nd;
-    };
-    auto add_neighbor = [&](PhyloNode *from, PhyloNode *to) {
-        PhyloNeighbor *nb = new PhyloNeighbor();
-        nb->node = to;
-        nb->length = -1.0;
-        from->neighbors.push_back(nb);
-        all_neighbors.push_back(nb);
-        return nb;
-    };
+    pars_names = names;
     // the initial tree of 3 taxa around node `size`
-    PhyloNode *centre = new_node(size);
+    PhyloNode *centre = newParsNode(size);
     for (int k = 0; k < 3; k++) {
-        PhyloNode *leaf = new_node(taxon_order[k]);
-        add_neighbor(centre, leaf);
-        add_neighbor(leaf, centre);
+        PhyloNode *leaf = newParsNode(taxon_order[k]);
+        newParsNeighbor(centre, leaf);
+        newParsNeighbor(leaf, centre);
     }
     root = nodes[(size_t)taxon_order[0]];
+}
+
+PhyloNode *PhyloTree::newParsNode(int id) {
+    PhyloNode *nd = new PhyloNode();
+    nd->id = id;
+    if (id < leafNum && id < (int)pars_names.size()) nd->name = pars_names[(size_t)id];
+    nodes[(size_t)id] = nd;
+    return nd;
+}
+
+PhyloNeighbor *PhyloTree::newParsNeighbor(PhyloNode *from, PhyloNode *to) {
+    PhyloNeighbor *nb = new PhyloNeighbor();
+    nb->node = to;
+    nb->length = -1.0;
+    from->neighbors.push_back(nb);
+    all_neighbors.push_back(nb);
+    return nb;
+}
+
+void PhyloTree::collectInsertScan(std::vector<PhyloNode *> &nodes1, std::vector<PhyloNode *> &nodes2, std::vector<iqhip_pars_op> &ops,
+                                  std::vector<int32_t> &ends) {
+    nodes1.clear();
+    nodes2.clear();
+    getBranches(nodes1, nodes2);
+    for (size_t k = 0; k < nodes1.size(); k++) {
+        PhyloNeighbor *a = nodes2[k]->findNeighbor(nodes1[k]), *c = nodes1[k]->findNeighbor(nodes2[k]);
+        collectParsOps(a, nodes2[k], ops);
+        collectParsOps(c, nodes1[k], ops);
+        ends.push_back(a->pars_slot);
+        ends.push_back(c->pars_slot);
+    }
+}
+
+void PhyloTree::insertParsimonyTaxon(PhyloNode *target_node, PhyloNode *target_dad, int taxon, int cur) {
+    // insert added_node in the middle of target_node -- target_dad (:382-405); its neighbours: the new taxon, then
+    // target_node, then target_dad
+    PhyloNode *new_taxon = newParsNode(taxon), *added_node = newParsNode(leafNum + cur - 2);
+    PhyloNeighbor *to_taxon = newParsNeighbor(added_node, new_taxon);
+    PhyloNeighbor *from_taxon = newParsNeighbor(new_taxon, added_node);
+    PhyloNeighbor *dad_side = target_dad->findNeighbor(target_node), *node_side = target_node->findNeighbor(target_dad);
+    PhyloNeighbor *to_node = newParsNeighbor(added_node, target_node), *to_dad = newParsNeighbor(added_node, target_dad);
+    // added_node -> target_node inherits what target_dad saw of target_node, and the other way round
+    to_node->pars_slot = dad_side->pars_slot;
+    to_node->partial_lh_computed = dad_side->partial_lh_computed;
+    to_dad->pars_slot = node_side->pars_slot;
+    to_dad->partial_lh_computed = node_side->partial_lh_computed;
+    dad_side->node = added_node;    // updateNeighbor: in place, the position in the neighbour list is kept
+    node_side->node = added_node;
+    to_taxon->pars_slot = new_taxon->id;
+    // (the reference copies the scan's fitch(a, c) into this vector; here its flag stays down and the next
+    // submission computes it with everything else)
+    from_taxon->pars_slot = pars_next_slot++;
+    dad_side->clearPartialLh();
+    dad_side->pars_slot = pars_next_slot++;
+    node_side->clearPartialLh();
+    node_side->pars_slot = pars_next_slot++;
+    target_dad->clearReversePartialLh(added_node);
+    target_node->clearReversePartialLh(added_node);
+}
+
+void PhyloTree::finishParsimonyTree() {
+    nodeNum = 2 * leafNum - 2;
+    branchNum = 2 * leafNum - 3;
+    {   // branch ids in traversal order from the root
+        int next_id = 0;
+        std::vector<PhyloNode *> n1, n2;
+        getBranches(n1, n2);
+        for (size_t k = 0; k < n1.size(); k++) {
+            n1[k]->findNeighbor(n2[k])->id = n2[k]->findNeighbor(n1[k])->id = next_id++;
+        }
+    }
+    current_it = current_it_back = nullptr;
+    theta_computed = false;
+}
+
+int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep> *trace) {
+    if (!engine || dry_run) throw std::runtime_error("computeParsimonyTree needs an attached engine");
+    const int size = leafNum;
+    if (size < 3) throw std::runtime_error("computeParsimonyTree needs at least 3 taxa");
+    std::vector<std::string> names((size_t)size);
+    for (int k = 0; k < size && k < (int)nodes.size(); k++)
+        if (nodes[(size_t)k]) names[(size_t)k] = nodes[(size_t)k]->name;
+    startParsimonyTree(taxon_order, names);
     pars_initialized = false;
     initializeAllPartialPars();   // (the three vectors that point at the centre take slots; leaves are their own)
     if (trace) trace->clear();
@@ -1884,16 +1971,9 @@ int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep
     std::vector<iqhip_pars_op> ops;
     for (int cur = 3; cur < size; cur++) {
         std::vector<PhyloNode *> nodes1, nodes2;
-        getBranches(nodes1, nodes2);
         // every vector the scan reads, in one submission
         std::vector<int32_t> ends;
-        for (size_t k = 0; k < nodes1.size(); k++) {
-            PhyloNeighbor *a = nodes2[k]->findNeighbor(nodes1[k]), *c = nodes1[k]->findNeighbor(nodes2[k]);
-            collectParsOps(a, nodes2[k], ops);
-            collectParsOps(c, nodes1[k], ops);
-            ends.push_back(a->pars_slot);
-            ends.push_back(c->pars_slot);
-        }
+        collectInsertScan(nodes1, nodes2, ops, ends);
         submitParsOps(ops);
         ParsStep step;
         int32_t best = 0, best_score = 0;
@@ -1911,44 +1991,9 @@ int PhyloTree::computeParsimonyTree(const int *taxon_order, std::vector<ParsStep
             step.best_score = best_score;
             trace->push_back(step);
         }
-        // insert added_node in the middle of target_node -- target_dad (:382-405); its neighbours: the new taxon, then
-        // target_node, then target_dad
-        PhyloNode *target_node = nodes1[(size_t)best], *target_dad = nodes2[(size_t)best];
-        PhyloNode *new_taxon = new_node(taxon_order[cur]), *added_node = new_node(size + cur - 2);
-        PhyloNeighbor *to_taxon = add_neighbor(added_node, new_taxon);
-        PhyloNeighbor *from_taxon = add_neighbor(new_taxon, added_node);
-        PhyloNeighbor *dad_side = target_dad->findNeighbor(target_node), *node_side = target_node->findNeighbor(target_dad);
-        PhyloNeighbor *to_node = add_neighbor(added_node, target_node), *to_dad = add_neighbor(added_node, target_dad);
-        // added_node -> target_node inherits what target_dad saw of target_node, and the other way round
-        to_node->pars_slot = dad_side->pars_slot;
-        to_node->partial_lh_computed = dad_side->partial_lh_computed;
-        to_dad->pars_slot = node_side->pars_slot;
-        to_dad->partial_lh_computed = node_side->partial_lh_computed;
-        dad_side->node = added_node;    // updateNeighbor: in place, the position in the neighbour list is kept
-        node_side->node = added_node;
-        to_taxon->pars_slot = new_taxon->id;
-        // (the reference copies the scan's fitch(a, c) into this vector; here its flag stays down and the next
-        // submission computes it with everything else)
-        from_taxon->pars_slot = pars_next_slot++;
-        dad_side->clearPartialLh();
-        dad_side->pars_slot = pars_next_slot++;
-        node_side->clearPartialLh();
-        node_side->pars_slot = pars_next_slot++;
-        target_dad->clearReversePartialLh(added_node);
-        target_node->clearReversePartialLh(added_node);
+        insertParsimonyTaxon(nodes1[(size_t)best], nodes2[(size_t)best], taxon_order[cur], cur);
     }
-    nodeNum = 2 * size - 2;
-    branchNum = 2 * size - 3;
-    {   // branch ids in traversal order from the root
-        int next_id = 0;
-        std::vector<PhyloNode *> n1, n2;
-        getBranches(n1, n2);
-        for (size_t k = 0; k < n1.size(); k++) {
-            n1[k]->findNeighbor(n2[k])->id = n2[k]->findNeighbor(n1[k])->id = next_id++;
-        }
-    }
-    current_it = current_it_back = nullptr;
-    theta_computed = false;
+    finishParsimonyTree();
     fixNegativeBranch(true);
     if (size == 3) best_pars_score = computeParsimony();
     return best_pars_score;

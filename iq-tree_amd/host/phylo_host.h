@@ -532,6 +532,29 @@ private:
     void needParsimony(const char *what);
     void assignParsSlots();
     int pars_next_slot = 0;
+    // The first slot of this tree's vectors; -1: leafNum, a tree that has the arena to itself.  A member of a
+    // ParsimonyForest (pars_forest_host.h) has no engine of its own: it owns the 3 * leafNum - 6 slots from its base in the
+    // owner's arena and never initialises the arena.
+    int pars_slot_base = -1;
+    friend class ParsimonyForest;
+    // the pieces of initializeAllPartialPars, computeAllPartialPars, fixNegativeBranch and computeParsimonyTree that touch
+    // the topology only, so that a forest drives many trees through them with ONE engine call per step
+    int64_t parsInformativeSites();   // fills pars_informative; the number of parsimony sites iqhip_pars_init will lay out
+    void collectAllParsOps(std::vector<iqhip_pars_op> &ops);
+    // the branches in fixNegativeBranch's recursion order, (neighbour, the node it hangs at)
+    void fixBranchList(std::vector<PhyloNeighbor *> &all, std::vector<PhyloNode *> &from) const;
+    // subst: one count per branch of `all` that is negative or forced, in order; nsite = getAlnNSite()
+    int applyParsLengths(const std::vector<PhyloNeighbor *> &all, const std::vector<PhyloNode *> &from, const int32_t *subst,
+                         bool force, double nsite);
+    void startParsimonyTree(const int *taxon_order, const std::vector<std::string> &names);   // the 3-taxon star, no slots
+    std::vector<std::string> pars_names;   // leaf names by taxon id while a stepwise-addition tree is being built
+    PhyloNode *newParsNode(int id);
+    PhyloNeighbor *newParsNeighbor(PhyloNode *from, PhyloNode *to);
+    // the branches of getBranches order with the ops their two vectors still need and their slots (a, c per branch)
+    void collectInsertScan(std::vector<PhyloNode *> &nodes1, std::vector<PhyloNode *> &nodes2, std::vector<iqhip_pars_op> &ops,
+                           std::vector<int32_t> &ends);
+    void insertParsimonyTaxon(PhyloNode *target_node, PhyloNode *target_dad, int taxon, int cur);   // phylotreepars.cpp:382-405
+    void finishParsimonyTree();   // node and branch counts, branch ids in traversal order
     void ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc);
 
     AllReduceHook allreduce_hook = nullptr;

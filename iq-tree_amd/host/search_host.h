@@ -99,6 +99,35 @@ inline int searchRandInt(uint64_t z, int n) {
     return k < n ? k : n - 1;
 }
 
+// ---- the addition orders of the K parsimony starting trees (createInitTrees -> computeParsimonyTree's shuffle,
+//      phylotreepars.cpp:320-331).  Order k is a Fisher-Yates shuffle of 0 .. ntaxa-1: for i = ntaxa-1 ... 1, swap i with
+//      searchRandInt(searchRand(seed, 0, k * ntaxa + i), i + 1).  Iteration 0 of the stream is otherwise unused, so the
+//      search's own draws do not move.  DEVIATION: the reference shuffles with my_random_shuffle on its own generator.
+inline std::vector<std::vector<int>> parsimonyOrders(uint64_t seed, int K, int ntaxa) {
+    std::vector<std::vector<int>> orders;
+    for (int k = 0; k < K; k++) {
+        std::vector<int> o((size_t)(ntaxa > 0 ? ntaxa : 0));
+        for (int i = 0; i < ntaxa; i++) o[(size_t)i] = i;
+        for (int i = ntaxa - 1; i >= 1; i--) {
+            const int j = searchRandInt(searchRand(seed, 0, (uint64_t)k * (uint64_t)ntaxa + (uint64_t)i), i + 1);
+            std::swap(o[(size_t)i], o[(size_t)j]);
+        }
+        orders.push_back(o);
+    }
+    return orders;
+}
+
+// the indices of `keys` (topology strings) that repeat an earlier key or one of `known`, in order: what the initial
+// candidate set skips and counts
+inline std::vector<int> duplicateKeys(const std::vector<std::string> &keys, const std::vector<std::string> &known) {
+    std::map<std::string, int> seen;
+    for (const std::string &k : known) seen[k] = 1;
+    std::vector<int> dup;
+    for (size_t i = 0; i < keys.size(); i++)
+        if (!seen.insert({keys[i], 1}).second) dup.push_back((int)i);
+    return dup;
+}
+
 // ---- candidate trees (candidateset.cpp:76-99, 158-222, 275-302): a multimap score -> tree, the best last; a topology is
 //      held once.  The topology string is the caller's (PhyloTree::sortedTaxonIdString). --------------------------------
 struct CandidateTree {

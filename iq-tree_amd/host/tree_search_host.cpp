@@ -5,6 +5,8 @@
 
 #include <stdexcept>
 
+#include "pars_forest_host.h"
+
 namespace iqhost {
 
 TreeSearch::TreeSearch(PhyloTree *t) : tree(t) {
@@ -21,6 +23,10 @@ void TreeSearch::checkEligible(const char *who) const {
     if (!t.engine) throw std::runtime_error(w + "the tree has no engine");
     if (iqhip_comm_size(t.engine) > 1) throw std::runtime_error(w + "not available on sharded engines and communicator ranks");
     if (batched && t.lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error(w + "the batched NNI evaluation needs LM_ALL_BRANCH");
+    if (numInitTrees > 0 && t.num_states != 4 && t.num_states != 20 && t.num_states != 64)
+        throw std::runtime_error(w + "the parsimony starting trees (numInitTrees > 0) need an engine of 4, 20 or 64 states: the parsimony calls refuse embedded state counts");
+    if (numInitTrees < 0 || initSprRadius < 0 || initSprRadius > IQHIP_PARS_SPR_MAX_RADIUS)
+        throw std::runtime_error(w + "numInitTrees must be >= 0 and initSprRadius within 0 .. 10");
     if (t.ufboot_nsamples > 0) {
         if (t.nmixture > 1 || t.n_unobserved > 0) throw std::runtime_error(w + "UFBoot is not available with mixture models and +ASC");
         if (batched && !nni5) throw std::runtime_error(w + "UFBoot with the batched evaluation needs nni5 (the nni1 batch keeps no per-pattern rows)");
@@ -195,9 +201,72 @@ double TreeSearch::doTreeSearch() {
     correlation_log.clear();
     candidates = iqsearch::CandidateSet();
 
-    // the starting tree is iteration 1: one optimizeNNI, then into the candidate set
+    init_trees.clear();
+    init_duplicates = 0;
     int nni_count = 0, nni_steps = 0;
-    {
+    int num_start = 1;   // the iterations the starting trees take
+    if (numInitTrees > 0) {
+        // createInitTrees: the given tree (computeInitialTree's) and numInitTrees - 1 parsimony trees; duplicate topologies
+        // are skipped and counted, every other tree is scored with optimizeAllBranches(2) and enters the set
+        auto add_start = [&](const std::string &topology) {
+            t.curScore = t.optimizeAllBranches(2);
+            iqsearch::CandidateTree c;
+            c.tree = t.getTreeString();
+            c.topology = topology;
+            c.score = t.curScore;
+            candidates.update(c.tree, c.topology, c.score);
+            init_trees.push_back(c);
+        };
+        // (the forest works in the engine's parsimony arena: the given tree stays in place while it is built)
+        ParsimonyForest forest(&t);
+        forest.spr_radius = initSprRadius;
+        forest.build(iqsearch::parsimonyOrders(seed, numInitTrees - 1, t.leafNum));
+        const std::string given = t.sortedTaxonIdString();
+        std::vector<std::string> keys;
+        for (const ParsimonyForest::Member &m : forest.members) keys.push_back(m.topology);
+        const std::vector<int> dup = iqsearch::duplicateKeys(keys, std::vector<std::string>(1, given));
+        init_duplicates = (int)dup.size();
+        if (on_init_phase) on_init_phase(*this, 0, numInitTrees - init_duplicates);
+        if (on_init_phase) on_init_phase(*this, 1, numInitTrees - init_duplicates);
+        add_start(given);
+        size_t next_dup = 0;
+        for (size_t k = 0; k < forest.members.size(); k++) {
+            if (next_dup < dup.size() && dup[next_dup] == (int)k) {
+                next_dup++;
+                continue;
+            }
+            t.readTreeString(forest.members[k].newick, names);
+            add_start(forest.members[k].topology);
+        }
+        // initCandidateTreeSet: the best numNNITrees, best first, each one optimizeNNI; the set starts again from them
+        const std::vector<std::string> kept = candidates.getTopTrees(std::max(1, std::min(numNNITrees, (int)candidates.size())));
+        candidates = iqsearch::CandidateSet();
+        num_start = (int)kept.size();
+        if (on_init_phase) on_init_phase(*this, 2, num_start);
+        stop_rule.addImprovedIteration(1);
+        for (int i = 1; i <= num_start; i++) {
+            Iteration it;
+            it.iteration = i;
+            t.readTreeString(kept[(size_t)(i - 1)], names);
+            t.computeLikelihood();
+            it.perturb_score = t.curScore;
+            optimizeNNI(nni_count, nni_steps, keep_trace ? &it.steps : nullptr);
+            it.nni_count = nni_count;
+            if (t.curScore > candidates.getBestScore() + modeps) {
+                t.curScore = t.optimizeAllBranches(100, loglh_epsilon);
+                if (!candidates.treeTopologyExist(t.sortedTaxonIdString())) {
+                    stop_rule.addImprovedIteration(i);
+                    it.new_best = true;
+                }
+            }
+            it.score = t.curScore;
+            candidates.update(t.getTreeString(), t.sortedTaxonIdString(), t.curScore);
+            if (on_iteration) on_iteration(*this, it);
+            if (keep_trace) trace.push_back(it);
+        }
+        stop_rule.cur_iteration = num_start;
+    } else {
+        // the starting tree is iteration 1: one optimizeNNI, then into the candidate set
         Iteration it;
         it.iteration = 1;
         t.computeLikelihood();
@@ -209,13 +278,15 @@ double TreeSearch::doTreeSearch() {
         candidates.update(t.getTreeString(), t.sortedTaxonIdString(), t.curScore);
         if (on_iteration) on_iteration(*this, it);
         if (keep_trace) trace.push_back(it);
+        stop_rule.cur_iteration = 1;
+        stop_rule.addImprovedIteration(1);
     }
-    stop_rule.cur_iteration = 1;
-    stop_rule.addImprovedIteration(1);
     const double curPerStrength = initPS;
     double cur_correlation = 0.0;
+    // a fixed iteration count counts the iterations of the loop below, whatever the starting trees took
+    const int fixed_shift = stop_rule.stop_condition == iqsearch::SC_FIXED_ITERATION ? num_start - 1 : 0;
 
-    while (!stop_rule.meetStopCondition(stop_rule.cur_iteration, cur_correlation)) {
+    while (!stop_rule.meetStopCondition(stop_rule.cur_iteration - fixed_shift, cur_correlation)) {
         const int cur = ++stop_rule.cur_iteration;
         Iteration it;
         it.iteration = cur;

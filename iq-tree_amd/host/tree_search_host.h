@@ -11,9 +11,14 @@
 // DEVIATIONS from the reference (see also search_host.h): all internal branches are listed in internalBranches order
 // (ascending node id), not in the reference's depth-first order; every branch is evaluated as (node1->id < node2->id),
 // the orientation of the batched evaluators, where the reference passes getBranchesForNNI's orientation on; the model is
-// taken as given (optimizeAllBranches(100) stands where the reference re-estimates the model for a better tree); the search
-// starts from ONE tree (no initial candidate set of parsimony trees); doOneRandomNNI's coin flips are real coin flips (the
-// reference draws random_int(1), which is always 0).
+// taken as given (optimizeAllBranches(100) stands where the reference re-estimates the model for a better tree);
+// doOneRandomNNI's coin flips are real coin flips (the reference draws random_int(1), which is always 0).
+// The starting population: with numInitTrees == 0 (the default) the search starts from the one tree it was given; with
+// numInitTrees > 0 doTreeSearch first restates createInitTrees + initCandidateTreeSet (iqtree.cpp:577-773): the given tree
+// plus numInitTrees - 1 stepwise-addition parsimony trees built in lockstep (pars_forest_host.h) on the addition orders of
+// iqsearch::parsimonyOrders (the reference shuffles with its own generator), duplicates dropped, each scored with
+// optimizeAllBranches(2), the best numNNITrees optimised with optimizeNNI.  PLL's randomised visiting order inside its
+// parsimony SPR is not restated (initSprRadius > 0 runs the project's own SPR rounds).
 // The reference's moves hold neighbour iterators: when an earlier move of a step has re-hung an end of a later one
 // (non-conflicting moves share no end, but may be adjacent), the later move swaps what its slots hold by then.  The moves here
 // hold node ids, so a step looks the slots up on the evaluated tree and applies what they hold; the applied moves are
@@ -50,6 +55,9 @@ public:
     uint64_t seed = 0;
     iqsearch::StopRule stop_rule; // SC_UNSUCCESS_ITERATION with 100; a bootstrap search uses SC_BOOTSTRAP_CORRELATION
     int step_iterations = 100;    // params.step_iterations
+    int numInitTrees = 0;         // params.numInitTrees (the reference: 100); 0: start from the given tree alone
+    int numNNITrees = 20;         // params.numNNITrees: the best initial trees that get an optimizeNNI
+    int initSprRadius = 0;        // SPR rounds on the parsimony trees (ParsimonyForest::spr_radius); 0: none
 
     // ---- trace ----------------------------------------------------------------------------------------------------------
     struct NNIStep {
@@ -80,17 +88,29 @@ public:
     std::vector<ufboot::SplitCounts> boot_splits;   // the snapshots of the correlation rule, every step_iterations / 2
     std::vector<std::pair<int, double>> correlation_log;   // (iteration, correlation) every step_iterations
     iqsearch::CandidateSet candidates;
+    // numInitTrees > 0: the distinct starting trees in generation order (the given tree first), each with its string and
+    // score after optimizeAllBranches(2), and how many parsimony trees repeated an earlier topology
+    std::vector<iqsearch::CandidateTree> init_trees;
+    int init_duplicates = 0;
+    // the phases of the starting population, for a driver's log: 0 = the parsimony trees are built (count = distinct
+    // starting trees, the given one included), 1 = their likelihoods come next (the same count), 2 = the NNI optimisation
+    // of the best `count` of them comes next
+    std::function<void(const TreeSearch &, int phase, int count)> on_init_phase;
 
     // ---- the search -------------------------------------------------------------------------------------------------------
     // on the current tree with curScore valid (computeLikelihood / optimizeAllBranches came last); returns curScore
     double optimizeNNI(int &nni_count, int &nni_steps, std::vector<NNIStep> *steps = nullptr);
     // numNNI random NNIs with the draws 1 + 3k (branch), 2 + 3k, 3 + 3k (coins) of `iteration`; all vectors go stale
     void doRandomNNIs(int numNNI, uint64_t iteration, std::vector<std::array<int, 4>> *done = nullptr);
-    // returns the best score; the best candidate tree is loaded, its lengths as stored, its lnL recomputed
+    // returns the best score; the best candidate tree is loaded, its lengths as stored, its lnL recomputed.
+    // With numInitTrees > 0 the M = min(numNNITrees, distinct trees) kept starting trees are the iterations 1 .. M (parent
+    // = -1, each through on_iteration and the UFBoot feeding of optimizeNNI, as iteration 1 without them) and the
+    // stochastic loop continues at M + 1; a fixed iteration count (SC_FIXED_ITERATION) counts the loop's iterations.
     double doTreeSearch();
     // refuses multifurcating trees, fewer than 4 taxa, trees without an engine, sharded engines and communicator ranks,
     // `batched` without LM_ALL_BRANCH, UFBoot together with mixtures, +ASC or the batched nni1 evaluation (it keeps no
-    // per-pattern rows): throws std::runtime_error, the tree is not touched.  Every entry point calls it first
+    // per-pattern rows), numInitTrees > 0 on engines the parsimony calls refuse (anything but 4, 20 or 64 states):
+    // throws std::runtime_error, the tree is not touched.  Every entry point calls it first
     void checkEligible(const char *who) const;
 
     PhyloTree *tree;
