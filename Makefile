@@ -36,8 +36,8 @@ $(LIBDIR)/kernels_bionj.o: HIPFLAGS += -ffp-contract=off
 $(LIBDIR)/libiqhip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS) -ldl
 
-HOST_SRCS  := $(HOST)/phylo_host.cpp $(HOST)/iqhost_c.cpp $(HOST)/model_host.cpp $(HOST)/alignment_host.cpp $(HOST)/iqmodel_c.cpp $(HOST)/model_opt_host.cpp $(HOST)/supertree_host.cpp $(HOST)/tree_search_host.cpp $(HOST)/pars_forest_host.cpp
-HOST_HDRS  := $(HOST)/search_host.h $(HOST)/tree_search_host.h $(HOST)/pars_forest_host.h $(HOST)/pars_forest_plan.h $(HOST)/phylo_host.h $(HOST)/brent_host.h $(HOST)/bfgs_host.h $(HOST)/model_host.h $(HOST)/model_opt_host.h $(HOST)/alignment_host.h $(HOST)/ufboot_splits.h $(HOST)/supertree_host.h $(HOST)/partition_spec.h $(HOST)/lmap_host.h include/iqhip.h include/iqhip_adapter.h
+HOST_SRCS  := $(HOST)/phylo_host.cpp $(HOST)/phylo_nni.cpp $(HOST)/phylo_support.cpp $(HOST)/phylo_dist.cpp $(HOST)/phylo_pars.cpp $(HOST)/phylo_em.cpp $(HOST)/phylo_ufboot.cpp $(HOST)/iqhost_c.cpp $(HOST)/model_host.cpp $(HOST)/alignment_host.cpp $(HOST)/iqmodel_c.cpp $(HOST)/model_opt_host.cpp $(HOST)/supertree_host.cpp $(HOST)/tree_search_host.cpp $(HOST)/pars_forest_host.cpp
+HOST_HDRS  := $(HOST)/search_host.h $(HOST)/tree_search_host.h $(HOST)/pars_forest_host.h $(HOST)/pars_forest_plan.h $(HOST)/phylo_host.h $(HOST)/mirror_policy.h $(HOST)/brent_host.h $(HOST)/bfgs_host.h $(HOST)/model_host.h $(HOST)/model_opt_host.h $(HOST)/alignment_host.h $(HOST)/ufboot_splits.h $(HOST)/supertree_host.h $(HOST)/partition_spec.h $(HOST)/lmap_host.h include/iqhip.h include/iqhip_adapter.h
 
 $(LIBDIR)/libiqhost.so: $(HOST_SRCS) $(HOST_HDRS) $(LIBDIR)/libiqhip.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -o $@ $(HOST_SRCS) -L$(LIBDIR) -liqhip -Wl,-rpath,'$$ORIGIN'

@@ -133,7 +133,7 @@ void PhyloTree::hipSync() {
 // Everything below the engine set-up is include/iqhip_adapter.h -- recursion, lazy flags, LM_PER_NODE re-orientation,
 // lh_scale_factor bookkeeping, leaf-side swap, the bodies of the four kernels, multifurcating nodes -- instantiated
 // with the reference's own types.  The very same templates, instantiated with a stand-alone mirror of these types
-// (iq-tree_amd/host/phylo_host.cpp, MirrorPolicy), are what this repository's test-suite runs on the GPU.
+// (iq-tree_amd/host/mirror_policy.h, MirrorPolicy), are what this repository's test-suite runs on the GPU.
 // phylonode.h / phylotree.h each gain one line: `friend struct HipPolicy;` (PhyloNeighbor's fields are private).
 // ---------------------------------------------------------------------------------------------------------------
 #include "iqhip_adapter.h"

@@ -1,6 +1,6 @@
 // lmap_host.h -- the host side of likelihood mapping (-lmap; quartet.cpp of the reference): what is done with the three
 // log-likelihoods of a quartet, and which quartets are evaluated.  Plain C++, no device call; the likelihoods themselves come
-// from iqhip_quartet_likelihoods (PhyloTree::computeQuartetLikelihoods in phylo_host.cpp).
+// from iqhip_quartet_likelihoods (PhyloTree::computeQuartetLikelihoods in phylo_dist.cpp).
 //   order3        the descending order of three values with the reference's ties (quartet.cpp:974-1005; the same comparison
 //                 tree sorts the three squared distances, :1070-1100)
 //   weights       the Bayesian weights exp(l_k - l_max) / sum with TP_MAX_EXP_DIFF = 40 (:1007-1031)

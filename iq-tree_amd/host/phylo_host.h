@@ -30,6 +30,7 @@
 namespace ufboot {
 struct SplitCounts;   // ufboot_splits.h
 }
+namespace iqhip_adapter { template <class X> struct Plan; }   // include/iqhip_adapter.h
 
 namespace iqhost {
 
@@ -76,7 +77,7 @@ struct PlanOp {
     iqhip_node_op op;
 };
 
-struct MirrorPolicy;  // phylo_host.cpp: this tree's answers to include/iqhip_adapter.h
+struct MirrorPolicy;  // mirror_policy.h: this tree's answers to include/iqhip_adapter.h
 
 class PhyloTree {
 public:
@@ -515,6 +516,22 @@ private:
     iqhip_branch_end branchEnd(PhyloNeighbor *nei) const;
     void check(int rc, const char *what) const;
     void pushInputs();
+    void finishAttach();   // what attachEngine and attachEngineSharded do once the engine exists
+    void rebuildTheta(PhyloNeighbor *dad_branch, PhyloNode *dad);
+    // "<who> needs an attached engine": needEngine accepts a dry-run tree that has an engine, needDevice does not
+    void needEngine(const char *who) const;
+    void needDevice(const char *who) const;
+    void noCallerCollective(const char *who) const;   // "<who>: not available with a caller-owned collective"
+    std::vector<std::string> leafNames() const;        // by taxon id; a leaf without a name goes by its id
+    // the Newick string from the root's neighbour with label[node id] behind every internal node
+    std::string labelledTreeString(const std::vector<std::string> &label) const;
+    // the tail of computeAllPartialLh and computePartialLhAround: the collected node updates as one submission
+    void submitPendingVectors(iqhip_adapter::Plan<MirrorPolicy> &plan, const char *who);
+    // both batched NNI evaluators: the refusals, the branches, their vectors, the inputs (false: an empty list); then rounds of
+    // branch solves (rows: nullptr or a store row per task; sum_scale: per op in task order; diverged: optx > 0.95 max length)
+    bool beginNNIBatch(const char *who, const BranchList *branches, std::vector<PhyloNode *> &bn1, std::vector<PhyloNode *> &bn2);
+    void submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, const int32_t *rows, std::vector<double> &sum_scale,
+                           std::vector<iqhip_branch_result> &res, std::vector<char> &diverged);
 
     double computeFuncDerv(double value, double &df, double &ddf);
     double minimizeNewton(double x1, double xguess, double x2, double xacc, double &d2l, int maxNRStep);
@@ -555,7 +572,9 @@ private:
                            std::vector<int32_t> &ends);
     void insertParsimonyTaxon(PhyloNode *target_node, PhyloNode *target_dad, int taxon, int cur);   // phylotreepars.cpp:382-405
     void finishParsimonyTree();   // node and branch counts, branch ids in traversal order
+    void renumberBranches();
     void ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc);
+    bool ufbootFeed(std::vector<iqhip_ufboot_tree> &ent, std::vector<int64_t> &boot_tree);
 
     AllReduceHook allreduce_hook = nullptr;
     void *allreduce_ctx = nullptr;

@@ -590,7 +590,7 @@ def _(ctx, t, state, k):
     a, b = pin_theta(t, state, k)
     if not is_mixture(ctx, state):
         out = refused(ctx, t.class_lnl, a, b, np.ones(1))
-        assert b"no mixture" in out["refused"].tobytes()        # (the mirror's own check, phylo_host.cpp classLnl)
+        assert b"no mixture" in out["refused"].tobytes()        # (the mirror's own check, phylo_em.cpp classLnl)
         return out
     lnl, fl = t.class_lnl(a, b, class_weights(ctx.model(state)))    # (the weights folded into the components' props)
     return {"class_lnl": lnl, "floored": arr(fl, np.int64)}
@@ -1317,6 +1317,6 @@ def fixed_sequences():
     out["recycling-dna"] = ("dna", LM_PER_NODE, recycling_sequence(2 * KINDS["dna"][2] - 3))
     # found by model-change-prot_mix, its shortest failing prefix: the mirror's mixWeightsEM (and iqhost_mix_posteriors) called
     # the engine without pushing a pending set_model, so the engine compared mix.model_version with the version of the model
-    # it still had and ran the EM on the previous model's matrix.  Both now push their inputs first (phylo_host.cpp)
+    # it still had and ran the EM on the previous model's matrix.  Both now push their inputs first (phylo_em.cpp)
     out["stale-matrix-prot_mix"] = ("prot_mix", LM_ALL_BRANCH, ["mixem@2", "set_model@mix2", "mixem_stale@0", "mixem@2"])
     return out

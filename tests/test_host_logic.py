@@ -154,3 +154,39 @@ def test_multifurcating_node_becomes_a_chain_of_binary_updates(pkg, synth):
     assert c["left_key"] == b["dst_key"] and c["left_len"] == 0.0 and c["right_leaf"] == 5 and c["flags"] == 2   # IQHIP_OP_SCALAR_RULE
     assert a["dst_key"] >> 63 == 1 and b["dst_key"] >> 63 == 1 and a["dst_key"] != b["dst_key"]
     assert c["dst_key"] >> 63 == 0
+
+
+DEVICE_ONLY_CALLS = [
+    ("evaluateNNIsBatch", lambda t: t.evaluate_nnis_batch()),
+    ("evaluateNNIs5Batch", lambda t: t.evaluate_nnis5_batch()),
+    ("testAllBranches", lambda t: t.test_all_branches(10)),
+    ("evaluateTrees", lambda t: t.evaluate_trees([t.tree_string(), t.tree_string()], 10)),
+    ("computeDist", lambda t: t.compute_dist()),
+    ("pairCounts", lambda t: t.pair_counts([(0, 1)])),
+    ("quartetCells", lambda t: t.quartet_cells([(0, 1, 2, 3)])),
+    ("computeQuartetLikelihoods", lambda t: t.quartet_likelihoods([(0, 1, 2, 3)])),
+    ("computeBioNJ", lambda t: t.compute_bionj(dist=np.zeros((5, 5)))),
+    ("computeParsimonyTree", lambda t: t.compute_parsimony_tree(range(5))),
+    ("optimizeParsimonySPR", lambda t: t.optimize_parsimony_spr(2)),
+    ("fetchPatternLh", lambda t: t.fetch_pattern_lh()),
+    ("computePatternLikelihood", lambda t: t.compute_pattern_likelihood()),
+    ("emPosteriors", lambda t: t.em_posteriors()),
+    ("computePatternLhCat", lambda t: t.mix_class_lh()),
+    ("initUFBoot", lambda t: t.ufboot_init(10)),
+    ("saveCurrentTree", lambda t: t.save_current_tree(-1.0)),
+    ("saveNNITrees", lambda t: t.save_nni_trees()),
+    ("summarizeBootstrap", lambda t: t.summarize_bootstrap()),
+]
+
+
+def test_device_only_calls_name_themselves_without_an_engine(pkg, synth):
+    """Every device-only member refuses a tree without an engine with one sentence that names the member.  Not in the
+    table: compute_rell, whose Python wrapper sizes its output from the sample count that only set_boot_samples
+    records -- and that call needs an engine first -- so the wrapper never reaches the mirror."""
+    t = pkg.PhyloTree(synth.random_tree_newick(5, 11))
+    t.set_alignment(4, 0, np.zeros((5, 8), dtype=np.uint8), np.ones(8))
+    t.set_model(synth.gtr_model())
+    for member, call in DEVICE_ONLY_CALLS:
+        with pytest.raises(pkg.HostError) as err:
+            call(t)
+        assert "needs an attached engine" in str(err.value) and member in str(err.value), (member, str(err.value))
