@@ -241,9 +241,20 @@ static std::string namedTopology(const std::string &ids, const std::vector<std::
     return out;
 }
 
-// -q / -spp: the edge-linked partition model on a fixed topology
+// what -search / -t hands to the NNI tree search
+struct SearchOptions {
+    bool on = false, nni5 = true, allnni = false, n_given = false;
+    long long n_iter = -1;
+    int numstop = 100, popsize = 5;
+    double pers = 0.5;
+    unsigned long long seed = 1;
+};
+
+// -q / -spp: the edge-linked partition model on a fixed topology, or with -search / -t the NNI tree search on the super tree
+// between two optimizeParameters (rates with -spp, and lengths); the partition rates and models are taken as given inside
+// the search loop
 static int runPartitionModel(const std::string &aln_file, const std::string &part_file, const std::string &tree_file,
-                             const std::string &prefix, bool proportional, bool blfix, int dev) {
+                             const std::string &prefix, bool proportional, bool blfix, int dev, const SearchOptions &so) {
     std::vector<std::string> names;
     std::vector<PartitionInput> parts;
     readPartitionRaxml(aln_file, part_file, names, parts);
@@ -256,11 +267,32 @@ static int runPartitionModel(const std::string &aln_file, const std::string &par
     if (tree.super.leafNum != (int)names.size()) throw std::runtime_error("Tree and alignment have different numbers of taxa");
     for (const PartitionInput &in : parts) tree.addPartition(in);
     tree.fixed_rates = !proportional;
+    if (so.on) tree.setAllBranchMode();   // the batched NNI evaluation needs every directed vector
     tree.attachEngines(dev);
     printf("Edge-linked partition model with %d partitions (%s)\n", tree.size(), proportional ? "-spp" : "-q");
-    const double lnl = tree.optimizeParameters(blfix, 0.001, 0.001);   // params.modeps defaults
+    tree.optimizeParameters(blfix, 0.001, 0.001);   // params.modeps defaults
+    if (so.on) {
+        TreeSearch ts(&tree);
+        ts.nni5 = so.nni5;
+        ts.speednni = !so.allnni;
+        ts.popSize = so.popsize;
+        ts.initPS = so.pers;
+        ts.seed = so.seed;
+        ts.stop_rule.unsuccess_iteration = so.numstop;
+        ts.stop_rule.stop_condition = so.n_given ? iqsearch::SC_FIXED_ITERATION : iqsearch::SC_UNSUCCESS_ITERATION;
+        ts.stop_rule.min_iteration = (int)so.n_iter;
+        ts.on_iteration = [&](const TreeSearch &, const TreeSearch::Iteration &it) {
+            if (it.iteration % 10 == 0) printf("Iteration %d / LogL: %.4f\n", it.iteration, it.score);
+            if (it.new_best && it.iteration > 1) printf("BETTER TREE FOUND at iteration %d: %.4f\n", it.iteration, it.score);
+        };
+        auto t0 = std::chrono::steady_clock::now();
+        ts.doTreeSearch();
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        printf("Tree search: %d iterations, %d candidate trees, %ld batches of joint solves: %.4f s\n", ts.stop_rule.cur_iteration,
+               (int)ts.candidates.size(), tree.num_group_batches, sec);
+        tree.optimizeParameters(blfix, 0.001, 0.001);
+    }
     const double total = tree.computeLikelihood();
-    (void)lnl;
     if (proportional) {   // PartitionModelPlen::writeInfo
         std::ostringstream os;
         os << "Partition-specific rates: ";
@@ -295,6 +327,7 @@ static void usage() {
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
+            "                 [-search | -t <newick file>] [-n <iterations>] [-numstop <n>] [-pers <p>] [-popsize <k>] [-nni1] [-allnni]\n"
             "                 (edge-linked partition model instead of -m; lines 'MODEL, name = 1-100, 250-400, 401-500\\3';\n"
             "                  -q: all partition rates 1, -spp: rates estimated)\n"
             "  model: e.g. 'GTR{1.5,2.4,1.8,1.9,2.8}+F{0.25,0.26,0.25,0.24}+I{0.1}+G4{0.9}', 'HKY{2}+G4{0.5}', JC,\n"
@@ -408,12 +441,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "error: -search / -t needs a model (-m): the search takes the model as given\n");
         return 2;
     }
-    if (search && !part_file.empty()) {
-        fprintf(stderr, "error: -q / -spp cannot be combined with -search / -t (the partition model evaluates a fixed topology)\n");
-        return 2;
-    }
     if (!part_file.empty()) {
-        const char *with = !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
+        const char *with = numpars > 0 ? "-numpars" : !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
                            : !mldist_file.empty() ? "-mldist" : pars || parstree || sprrad > 0 ? "-pars / -parstree / -sprrad"
                            : bionjtree ? "-bionjtree" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : lmap >= 0 ? "-lmap" : nullptr;
         if (with) {
@@ -423,7 +452,10 @@ int main(int argc, char **argv) {
         if (aln_file.empty() || tree_file.empty()) { usage(); return 2; }
         if (prefix.empty()) prefix = part_file;
         try {
-            return runPartitionModel(aln_file, part_file, tree_file, prefix, part_proportional, blfix, dev);
+            SearchOptions so;
+            so.on = search; so.nni5 = nni5; so.allnni = allnni; so.n_given = n_given; so.n_iter = n_iter;
+            so.numstop = numstop; so.popsize = popsize; so.pers = pers; so.seed = seed;
+            return runPartitionModel(aln_file, part_file, tree_file, prefix, part_proportional, blfix, dev, so);
         } catch (const std::exception &ex) {
             fprintf(stderr, "error: %s\n", ex.what());
             return 1;

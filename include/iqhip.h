@@ -949,9 +949,31 @@ void iqhip_debug_fail_alloc(int nth);
  *   after one synchronisation.  part_lnl[p] is member p's whole log-likelihood (scale-factor term included); the per-op
  *   sum_scale rows are not returned.  The evaluation of PhyloSuperTreePlen::computeFunction and of
  *   optimizeTreeLengthScaling for all partitions in lockstep.
+ * iqhip_partition_optimize_branch_batch: ntasks INDEPENDENT joint solves side by side -- the NNI candidates of a super tree
+ *   -- with the task struct of iqhip_optimize_branch_batch.  Task t first runs its node updates ops[0..nops) on every
+ *   member, member p with every op length multiplied by r_p (they may read any existing vector and must write vectors no
+ *   other task touches; the keys are the same on every member), then solves the length x of branch (a, b) as
+ *   iqhip_partition_newton_branch does, on thetas built into per-task slots: xguess, x1, x2, x and optx are in super-tree
+ *   units, member p is evaluated at r_p * x.  The NaN / inf rule per member, update rule, bounds, stopping tests, d2l and
+ *   nsteps are those of the single solve; minimizeNewton's two failures come back in results[t].status (2, 3) as in
+ *   iqhip_optimize_branch_batch, not as an error of the call.  (A solve that runs into max_steps ends at j == max_steps with
+ *   the last accepted iterate, status 0 and nsteps == max_steps, exactly as iqhip_partition_newton_branch returns it.)  part_lnl[t * nparts + p] (or NULL) is member p's
+ *   computeLikelihoodFromBuffer at r_p * optx of task t, its scale-factor term included (from the scale counters of the
+ *   two branch ends, on the device); results[t].lnl is their sum in member order, formed on the host -- so no sum_scale
+ *   bookkeeping is needed for scratch vectors, and none is returned.
+ *   Per chunk of tasks: one submission of the gathered node updates and the theta slots on every member's stream, then on
+ *   the group's stream ONE enqueued chain for all tasks: per evaluation one derivative launch over (work item x task) and
+ *   one update launch with a workgroup per task; the states are read once per chunk of steps (IQHIP_PART_STEPS), and the
+ *   lnL pass rides behind each chunk.  No grid barrier, no atomics, fixed summation order: a task's result has the bits of
+ *   iqhip_partition_newton_branch on the same theta, whatever the chunking.  Tasks per chunk: at most 64, and all
+ *   members' theta slots together within a quarter of the free device memory; IQHIP_PART_BATCH_CHUNK (read per call)
+ *   lowers it.  The members are left as iqhip_optimize_branch_batch with the same ops leaves them: the theta of
+ *   iqhip_compute_theta and its validity are untouched.  IQHIP_ERR_INVALID for a null group, task array or result array,
+ *   ntasks < 1, a bad ops array, bounds the single solve refuses, a key a member does not know; the member conditions of
+ *   every group call apply.
  * iqhip_debug_partition_timing: *launches = kernels the group's last call enqueued on its own stream; with
  *   iqhip_timing_enable on the FIRST member, ms[0] / ms[1] = device time (HIP events) of the derivative launches / of the
- *   update launches of the last iqhip_partition_newton_branch. */
+ *   update launches of the last iqhip_partition_newton_branch or iqhip_partition_optimize_branch_batch. */
 typedef struct iqhip_partition iqhip_partition;
 int iqhip_partition_create(iqhip_partition **out, iqhip_engine *const *members, int nparts);
 void iqhip_partition_destroy(iqhip_partition *g);
@@ -962,6 +984,9 @@ int iqhip_partition_lnl_from_theta(iqhip_partition *g, double x, double *part_ln
 int iqhip_partition_traverse_lnl(iqhip_partition *g, const iqhip_node_op *ops, int nops, iqhip_branch_end a,
                                  iqhip_branch_end b, double len, const double *scale /* nparts or NULL */,
                                  double *part_lnl /* nparts */);
+int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const iqhip_branch_task *tasks, int ntasks,
+                                          iqhip_branch_result *results,
+                                          double *part_lnl /* ntasks * nparts, [task][member], or NULL */);
 int iqhip_debug_partition_timing(iqhip_partition *g, double *ms /* 2: derivative launches, update launches */,
                                  int64_t *launches);
 

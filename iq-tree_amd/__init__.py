@@ -52,6 +52,7 @@ IQHIP_SYMBOLS = [
     "iqhip_ufboot_init", "iqhip_ufboot_update", "iqhip_ufboot_fetch", "iqhip_debug_ufboot_timing",
     "iqhip_partition_create", "iqhip_partition_destroy", "iqhip_partition_set_rates", "iqhip_partition_newton_branch",
     "iqhip_partition_lnl_from_theta", "iqhip_partition_traverse_lnl", "iqhip_debug_partition_timing",
+    "iqhip_partition_optimize_branch_batch",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -281,6 +282,7 @@ def libiqhip():
                                                   C.POINTER(C.c_int), dp]
     lib.iqhip_partition_lnl_from_theta.argtypes = [vp, C.c_double, dp]
     lib.iqhip_partition_traverse_lnl.argtypes = [vp, C.POINTER(NodeOp), C.c_int, BranchEnd, BranchEnd, C.c_double, dp, dp]
+    lib.iqhip_partition_optimize_branch_batch.argtypes = [vp, C.POINTER(BranchTask), C.c_int, C.POINTER(BranchResult), dp]
     lib.iqhip_debug_partition_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
@@ -399,6 +401,24 @@ def libiqhost():
     lib.iqhost_super_branch_order.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     lib.iqhost_super_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
     lib.iqhost_super_counters.argtypes = [vp, C.POINTER(C.c_long)]
+    lib.iqhost_super_group_batches.argtypes = [vp]
+    lib.iqhost_super_group_batches.restype = C.c_long
+    lib.iqhost_super_set_all_branch_mode.argtypes = [vp]
+    lib.iqhost_super_tree.argtypes = [vp]
+    lib.iqhost_super_tree.restype = vp
+    lib.iqhost_super_read_tree.argtypes = [vp, C.c_char_p]
+    lib.iqhost_super_num_nodes.argtypes = [vp]
+    lib.iqhost_super_num_leaves.argtypes = [vp]
+    lib.iqhost_super_neighbors.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp, C.c_int]
+    lib.iqhost_super_do_nni.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.iqhost_super_change_nni_brans.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
+    lib.iqhost_super_do_random_nni.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.iqhost_super_save_branch_lengths.argtypes = [vp, dp, C.c_int, C.POINTER(C.c_int)]
+    lib.iqhost_super_restore_branch_lengths.argtypes = [vp, dp, C.c_int]
+    lib.iqhost_super_clear_all_partial_lh.argtypes = [vp]
+    lib.iqhost_super_nni_for_branch.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    lib.iqhost_super_evaluate_nnis_list.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), dp, C.c_int,
+                                                    C.POINTER(C.c_int)]
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.iqhost_test_all_branches.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), dp, C.c_int,
                                              C.POINTER(C.c_int), dp]
@@ -484,6 +504,7 @@ def libiqhost():
     lib.iqhost_candset_rand_rank.argtypes = [vp, C.c_int, u64, ipp]
     lib.iqhost_candset_entry.argtypes = [vp, C.c_int, dp, C.c_char_p, C.c_int, ipp]
     lib.iqhost_search_create.argtypes = [C.POINTER(vp), vp]
+    lib.iqhost_search_create_super.argtypes = [C.POINTER(vp), vp]
     lib.iqhost_search_destroy.argtypes = [vp]
     lib.iqhost_search_destroy.restype = None
     lib.iqhost_search_set_params.argtypes = [vp, ipp, dp, u64]
@@ -2284,7 +2305,10 @@ class TreeSearch:
         self.lib = libiqhost()
         self.tree = tree
         self.h = C.c_void_p()
-        _hchk(self.lib.iqhost_search_create(C.byref(self.h), tree.h))
+        if isinstance(tree, PhyloSuperTree):   # UFBoot and num_init_trees > 0 are refused
+            _hchk(self.lib.iqhost_search_create_super(C.byref(self.h), tree.h))
+        else:
+            _hchk(self.lib.iqhost_search_create(C.byref(self.h), tree.h))
         self.params = dict(seed=seed, nni5=nni5, speed=speed, pop_size=pop_size, pers=pers, iterations=iterations,
                            num_stop=num_stop, batched=batched, step_iterations=step_iterations,
                            min_correlation=min_correlation, max_iterations=max_iterations, num_init_trees=num_init_trees,
@@ -2436,6 +2460,19 @@ class PartitionGroup:
             None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    def optimize_branch_batch(self, tasks, want_part_lnl=True):
+        """tasks: a ctypes array of BranchTask (their ops arrays must stay alive for the call), or a list of them;
+        -> (results, part_lnl): a list of dicts {optx, d2l, lnl, nsteps, status} and an array [task][member] or None"""
+        if tasks is not None and not isinstance(tasks, C.Array):
+            tasks = (BranchTask * max(1, len(tasks)))(*tasks) if len(tasks) else None
+        n = 0 if tasks is None else len(tasks)
+        res = (BranchResult * max(1, n))()
+        out = np.zeros((max(1, n), self.nparts)) if want_part_lnl else None
+        self._chk(self.lib.iqhip_partition_optimize_branch_batch(
+            self.h, tasks, n, res, out.ctypes.data_as(C.POINTER(C.c_double)) if want_part_lnl else None))
+        results = [dict(optx=r.optx, d2l=r.d2l, lnl=r.lnl, nsteps=r.nsteps, status=r.status) for r in res[:n]]
+        return results, out
+
     def timing(self):
         """-> {"derv_ms", "update_ms", "launches"} of the last call (the times need iqhip_timing_enable on member 0)"""
         ms = (C.c_double * 2)()
@@ -2506,7 +2543,7 @@ class PhyloSuperTree:
     lengths the super tree's times part_rates[p].  parts: dicts with nstates, seq_type, pat, freq, model and optionally
     invar, name.  Every member keeps every taxon (all-unknown rows where a partition has no data)."""
 
-    def __init__(self, newick, parts, names=None, device=0, fixed_rates=True, attach=True):
+    def __init__(self, newick, parts, names=None, device=0, fixed_rates=True, attach=True, all_branch=False):
         self.lib = libiqhost()
         self.h = C.c_void_p()
         if names:
@@ -2526,6 +2563,8 @@ class PhyloSuperTree:
         self.nparts = len(self.members)
         self.nsites = [float(np.sum(d["freq"])) for d in parts]
         self._chk(self.lib.iqhost_super_set_fixed_rates(self.h, int(fixed_rates)))
+        if all_branch:   # a buffer per directed vector on every member: what the batched NNI evaluations need
+            self._chk(self.lib.iqhost_super_set_all_branch_mode(self.h))
         if attach:
             self._chk(self.lib.iqhost_super_attach_engines(self.h, device))
 
@@ -2628,7 +2667,113 @@ class PhyloSuperTree:
     def counters(self):
         out = (C.c_long * 3)()
         self.lib.iqhost_super_counters(self.h, out)
-        return dict(group_solves=out[0], group_traversals=out[1], diverged=out[2])
+        return dict(group_solves=out[0], group_traversals=out[1], diverged=out[2],
+                    group_batches=self.lib.iqhost_super_group_batches(self.h))
+
+    # ---- NNI on the super tree: the plain tree's surface (PhyloTree above), moves and lengths in super-tree units
+    @property
+    def num_nodes(self):
+        return self.lib.iqhost_super_num_nodes(self.h)
+
+    @property
+    def num_leaves(self):
+        return self.lib.iqhost_super_num_leaves(self.h)
+
+    def neighbors(self, node):
+        ids = (C.c_int * 8)()
+        lens = (C.c_double * 8)()
+        d = self.lib.iqhost_super_neighbors(self.h, node, ids, lens, 8)
+        return [(ids[i], lens[i]) for i in range(d)]
+
+    def nni_for_branch(self, a, b, nni5=False):
+        """the branch-by-branch path: both swaps made on every tree, joint optimize_one_branch solves, the summed lnL ->
+        [(newloglh, swapped subtree at a, swapped subtree at b, [newLen...]), x2]"""
+        out = np.zeros(16)
+        self._chk(self.lib.iqhost_super_nni_for_branch(self.h, a, b, int(nni5), _dptr(out)))
+        return [(out[8 * c], int(out[8 * c + 1]), int(out[8 * c + 2]), list(out[8 * c + 3:8 * c + 8])) for c in range(2)]
+
+    def _evaluate_nnis_list(self, nni5, branches):
+        if branches is None:
+            br, nbr, cap = None, 0, 4 * self.num_nodes
+        else:
+            branches = [tuple(b) for b in branches]
+            br = _iptr(np.array(branches or [(0, 0)], dtype=np.int32).reshape(-1))
+            nbr, cap = len(branches), max(2 * len(branches), 1)
+        w = 6 if nni5 else 2
+        ids = np.zeros(4 * cap, dtype=np.int32)
+        vals = np.zeros(w * cap)
+        n = C.c_int()
+        self._chk(self.lib.iqhost_super_evaluate_nnis_list(self.h, int(nni5), br, nbr, _iptr(ids), _dptr(vals), cap, C.byref(n)))
+        return ids, vals, n.value
+
+    def evaluate_nnis_batch(self, branches=None):
+        """all nni1 candidates in two batches of joint solves (needs all_branch=True) -> as PhyloTree.evaluate_nnis_batch"""
+        ids, vals, n = self._evaluate_nnis_list(False, branches)
+        return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
+                     node2_nei=int(ids[4 * k + 3]), new_len=float(vals[2 * k]), newloglh=float(vals[2 * k + 1]))
+                for k in range(n)]
+
+    def evaluate_nnis5_batch(self, branches=None):
+        """all nni5 candidates in ten batches of joint solves (needs all_branch=True) -> as PhyloTree.evaluate_nnis5_batch"""
+        ids, vals, n = self._evaluate_nnis_list(True, branches)
+        return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
+                     node2_nei=int(ids[4 * k + 3]), new_lens=[float(x) for x in vals[6 * k:6 * k + 5]],
+                     newloglh=float(vals[6 * k + 5])) for k in range(n)]
+
+    def do_nni(self, move):
+        """the move on the super tree and on every member, their stale vectors cleared; twice restores the tree"""
+        self._chk(self.lib.iqhost_super_do_nni(self.h, int(move["node1"]), int(move["node2"]), int(move["node1_nei"]),
+                                               int(move["node2_nei"])))
+
+    def change_nni_brans(self, move, nni5=True):
+        lens = np.zeros(5)
+        if "new_lens" in move:
+            lens[:len(move["new_lens"])] = move["new_lens"]
+        else:
+            lens[0] = move["new_len"]
+        self._chk(self.lib.iqhost_super_change_nni_brans(self.h, int(move["node1"]), int(move["node2"]), _dptr(lens), int(nni5)))
+
+    def do_random_nni(self, a, b, bit1, bit2):
+        out = np.zeros(4, dtype=np.int32)
+        self._chk(self.lib.iqhost_super_do_random_nni(self.h, int(a), int(b), int(bit1), int(bit2), _iptr(out)))
+        return dict(node1=int(out[0]), node2=int(out[1]), node1_nei=int(out[2]), node2_nei=int(out[3]))
+
+    def save_branch_lengths(self):
+        n = C.c_int()
+        self._chk(self.lib.iqhost_super_save_branch_lengths(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value)
+        self._chk(self.lib.iqhost_super_save_branch_lengths(self.h, _dptr(out), n.value, C.byref(n)))
+        return out
+
+    def restore_branch_lengths(self, lengths):
+        v = np.ascontiguousarray(lengths, dtype=np.float64)
+        self._chk(self.lib.iqhost_super_restore_branch_lengths(self.h, _dptr(v), v.size))
+
+    def clear_all_partial_lh(self):
+        self._chk(self.lib.iqhost_super_clear_all_partial_lh(self.h))
+
+    def sorted_taxon_id_string(self):
+        """the super tree's topology as the reference prints it with WT_TAXON_ID + WT_SORT_TAXA"""
+        sup = self.lib.iqhost_super_tree(self.h)
+        need = C.c_int()
+        self._chk(self.lib.iqhost_sorted_taxon_id_string(sup, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._chk(self.lib.iqhost_sorted_taxon_id_string(sup, buf, len(buf), C.byref(need)))
+        return buf.value.decode()
+
+    def read_tree(self, newick):
+        """a candidate tree on the same taxa: re-read by the super tree and every member; engines, models and rates stay,
+        member lengths are rate x super lengths, every vector is dropped"""
+        self._chk(self.lib.iqhost_super_read_tree(self.h, newick.encode()))
+
+    def optimize_nni(self, nni5=True, speed=True, batched=True, trace=False):
+        """compute_likelihood(), then IQTree::optimizeNNI on the super tree -> as PhyloTree.optimize_nni; the partition rates
+        and models are taken as given"""
+        ts = TreeSearch(self, nni5=nni5, speed=speed, batched=batched)
+        try:
+            return ts.optimize_nni(trace=trace)
+        finally:
+            ts.close()
 
     def partition_timing(self):
         """iqhip_debug_partition_timing of the group's last call (times need iqhip_timing_enable on member 0)"""

@@ -1144,7 +1144,7 @@ int eng_newton_eval_enqueue(iqhip_engine *e);         // derivative kernel at st
 int eng_newton_update_enqueue(iqhip_engine *e);       // state machine step from result[0..1]
 // batched chain (iqhip_optimize_branch_batch on sharded engines): m tasks side by side, ONE reduction of 2m rows and
 // hence one all-reduce of 2m doubles per Newton step.  prepare: theta of every task into its slot + the initial states
-int eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, const NewtonState *init);
+int eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, const NewtonState *init);   // init == nullptr: the theta slots only
 int eng_batch_eval_enqueue(iqhip_engine *e, int m);   // derivative kernels at states[t].rts + k_reduce -> result[0..2m)
 int eng_batch_update_enqueue(iqhip_engine *e, int m); // state machines step from result[0..2m)
 int eng_batch_lnl_enqueue(iqhip_engine *e, int m);    // lnL at states[t].result -> result[2t]
@@ -1414,6 +1414,11 @@ struct __attribute__((aligned(16))) PartScale {
     const double *freq;
     int64_t nptn;
 };
+// a member's theta slots of a batch of joint solves: slot t at theta + t * stride (the engine's d_theta_batch)
+struct __attribute__((aligned(16))) PartSlots {
+    const double *theta;
+    size_t stride;
+};
 constexpr int kPartUpdateThreads = 64;   // k_part_newton_update: thread t owns members t, t + 64, ..
 // mode 0: {df, ddf} of every item at rate * st->rts (nothing once st->done); mode 1: f * log|lh| sums (scale-factor term
 // included) at rate * (st ? st->result : x) -> partials[2 item], [2 item + 1]; lds_doubles = 3 * the largest block
@@ -1423,6 +1428,16 @@ hipError_t launch_part_derv(hipStream_t s, int mode, const PartDesc *d_desc, con
 hipError_t launch_part_newton_update(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials,
                                      NewtonState *st);
 hipError_t launch_part_lnl_finish(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials, double *out);
+// the batch of joint solves: task t (grid.y) on slot t of every member at the length in states[t]; d_sc: [ntasks][nparts][2]
+// scale counters of the tasks' branch ends; partials: [ntasks][nitems][2]; out: [ntasks][nparts]; lnl_written: [ntasks], zero
+// when the chain starts -- the finish launch marks a task that is done, and later mode 1 launches leave it alone
+hipError_t launch_part_derv_batch(hipStream_t s, int mode, const PartDesc *d_desc, const PartItem *d_items, int nitems,
+                                  int lds_doubles, const PartSlots *d_slots, const int16_t *const *d_sc, int nparts,
+                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials);
+hipError_t launch_part_newton_update_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems,
+                                           const double *partials, NewtonState *states, int ntasks);
+hipError_t launch_part_lnl_finish_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems, const double *partials,
+                                        const NewtonState *states, int32_t *lnl_written, double *out, int ntasks);
 // out[p] = kLogScalingThreshold * sum over patterns of freq * (a_sc + b_sc), fixed order
 hipError_t launch_part_scale_terms(hipStream_t s, const PartScale *d_sc, int nparts, double *out);
 

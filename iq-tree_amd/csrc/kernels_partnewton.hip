@@ -9,30 +9,29 @@
 // and the host reads the 128-byte state once per chunk of steps (partition.hip).  Workgroups never talk to each other
 // inside a launch -- no grid barrier, no spinning, no atomics: a work item's {df, ddf} goes to a slot of its own and the
 // next launch of the same stream sums the slots in a fixed order, so the bits are the same on every run.
+//
+// The batch of joint solves (iqhip_partition_optimize_branch_batch: the NNI candidates of a super tree side by side) is
+// the same chain with a task dimension: ntasks device-resident states, per evaluation
+//     k_part_derv_batch<0> (grid: work item x task) -> k_part_newton_update_batch (one workgroup per task)
+// and behind the last chunk of steps k_part_derv_batch<1> -> k_part_lnl_finish_batch -> out[task][member].  Task t reads
+// slot t of every member's theta batch (eng_batch_prepare) and writes partials[t][item][2]; a task that is done does
+// nothing.  The per-item body (part_item_sums), the member and item sums (part_newton_update, part_lnl_of_member) are the
+// single solve's own functions, so a task's bits are those of iqhip_partition_newton_branch on the same theta.
 #include "iqhip_internal.h"
 
 namespace iqhip {
 
-// One workgroup per work item: a contiguous run of tiles of one member, wave w taking tiles first + w, first + w + 4, ..
-// The per-pattern arithmetic is wg_partial's (kernels_newton.hip) for a resident theta: 64-pattern double2 tiles for the
+// The per-item body of k_part_derv and k_part_derv_batch.  A work item is a contiguous run of tiles of one member, one
+// workgroup each, wave w taking tiles first + w, first + w + 4, ..
+// The per-pattern arithmetic is wg_partial's (kernels_newton.hip) for a theta in memory: 64-pattern double2 tiles for the
 // 4-state engines, 16-pattern tiles with the block entries spread over the four lane groups for the matrix-core ones.
-// MODE 0: sums of f * df_ptn, f * ddf_ptn at the member's length rate * st->rts; nothing once the solve is done.
-// MODE 1: sum of f * (log|lh_ptn| + scale counters * LOG_SCALING_THRESHOLD) at rate * (st ? st->result : x_given); with a
-// state machine, nothing until it is done.
+// MODE 0: sums of f * df_ptn, f * ddf_ptn at the member's length rate * x.
+// MODE 1: sum of f * (log|lh_ptn| + scale counters * LOG_SCALING_THRESHOLD) at rate * x.
+// theta, a_sc, b_sc: the member's resident theta and its ends' counters (D's own), or those of a task's slot.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ descs, const PartItem *__restrict__ items,
-                                                   const NewtonState *st, double x_given, double *__restrict__ partials) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    double x = x_given;
-    if (MODE == 0) {
-        if (st->done) return;
-        x = st->rts;
-    } else if (st) {   // (enqueued behind a chunk of steps: only once they have finished the solve)
-        if (!st->done) return;
-        x = st->result;
-    }
-    const PartItem it = items[blockIdx.x];
-    const PartDesc D = descs[it.member];
+__device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem &it, const double *__restrict__ theta,
+                                               const int16_t *__restrict__ a_sc, const int16_t *__restrict__ b_sc, double x,
+                                               double *smem, double *__restrict__ out2) {
     const int B = D.n * D.ncat;
     double *s_v0 = smem, *s_v1 = smem + B, *s_v2 = smem + 2 * B, *s_red = smem + 3 * B;   // s_red[8]
     const double len = D.rate * x;
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ 
         if (!D.mfma) {
             ptn = tile * 64 + lane;
             mine = ptn < D.nptn;
-            const double2 *p = reinterpret_cast<const double2 *>(D.theta + tile * (64 * B)) + lane;
+            const double2 *p = reinterpret_cast<const double2 *>(theta + tile * (64 * B)) + lane;
             for (int j = 0; j < B / 2; j++) {
                 const double2 t = p[j * 64];
                 lh = fma(s_v0[2 * j], t.x, lh); lh = fma(s_v0[2 * j + 1], t.y, lh);
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ 
             const int p = lane & 15, g = lane >> 4;
             ptn = tile * 16 + p;
             mine = (g == 0) && ptn < D.nptn;
-            const double *th = D.theta + (size_t)tile * 16 * B;
+            const double *th = theta + (size_t)tile * 16 * B;
             // a pattern's rows 20 at a time: all 20 loads of a lane are in flight together
             for (int e0 = g; e0 < B; e0 += 80) {
                 double tv[20];
@@ -102,8 +101,8 @@ __global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ 
                 double l = log(fabs(lh));
                 if (isnan(l) || isinf(l)) l = kLogScalingThreshold * 4;  // the reference's repair, phylokernel.h:1100-1122
                 int ssc = 0;
-                if (D.a_sc) ssc += D.a_sc[ptn];
-                if (D.b_sc) ssc += D.b_sc[ptn];
+                if (a_sc) ssc += a_sc[ptn];
+                if (b_sc) ssc += b_sc[ptn];
                 l += (double)ssc * kLogScalingThreshold;
                 adf = fma(l, f, adf);
             } else {
@@ -120,18 +119,64 @@ __global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ 
     if (lane == 0) { s_red[2 * wave] = adf; s_red[2 * wave + 1] = addf; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        partials[2 * (size_t)blockIdx.x] = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
-        partials[2 * (size_t)blockIdx.x + 1] = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]);
+        out2[0] = (s_red[0] + s_red[2]) + (s_red[4] + s_red[6]);
+        out2[1] = (s_red[1] + s_red[3]) + (s_red[5] + s_red[7]);
     }
 }
 
-// A single workgroup of kPartUpdateThreads: 64 members at a time, thread t sums the items of member base + t in item order
-// and applies the reference's per-partition NaN / inf rule (phylokernel.h:647-651); thread 0 then adds r df and r^2 ddf of
-// those members in member order.  After the last member: newton_update, the state machine of every enqueued chain.
-__global__ __launch_bounds__(kPartUpdateThreads) void k_part_newton_update(const PartDesc *__restrict__ descs, int nparts,
-                                                                           const double *__restrict__ partials,
-                                                                           NewtonState *st) {
-    __shared__ double s_m[2 * kPartUpdateThreads];
+// One workgroup per work item, the member's resident theta.
+// MODE 0: at st->rts; nothing once the solve is done.
+// MODE 1: at (st ? st->result : x_given); with a state machine, nothing until it is done.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_part_derv(const PartDesc *__restrict__ descs, const PartItem *__restrict__ items,
+                                                   const NewtonState *st, double x_given, double *__restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double x = x_given;
+    if (MODE == 0) {
+        if (st->done) return;
+        x = st->rts;
+    } else if (st) {   // (enqueued behind a chunk of steps: only once they have finished the solve)
+        if (!st->done) return;
+        x = st->result;
+    }
+    const PartItem it = items[blockIdx.x];
+    const PartDesc D = descs[it.member];
+    part_item_sums<MODE>(D, it, D.theta, D.a_sc, D.b_sc, x, smem, partials + 2 * (size_t)blockIdx.x);
+}
+
+// The batch of joint solves (iqhip_partition_optimize_branch_batch): workgroup (item, task) runs the same body on slot
+// `task` of the item's member, at the length in the task's own state machine, into partials[task][item][2].
+// MODE 0: a task that is done does nothing.  MODE 1: at the task's result; the pass rides behind every chunk of steps, as the
+// single solve's does, so a task that is not done yet does nothing, and neither does one whose sums an earlier pass wrote
+// (lnl_written[task], zero at the start of the chain and set by k_part_lnl_finish_batch; nothing overwrites the partials of a
+// task that is done).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_part_derv_batch(const PartDesc *__restrict__ descs, const PartItem *__restrict__ items,
+                                                         const PartSlots *__restrict__ slots,
+                                                         const int16_t *const *__restrict__ sc, int nparts,
+                                                         const NewtonState *__restrict__ states,
+                                                         const int32_t *__restrict__ lnl_written,
+                                                         double *__restrict__ partials) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int task = blockIdx.y;
+    const NewtonState *st = states + task;
+    if ((MODE == 0) == (st->done != 0)) return;
+    if (MODE == 1 && lnl_written[task]) return;   // (its sums are in partials already)
+    const double x = MODE == 0 ? st->rts : st->result;
+    const PartItem it = items[blockIdx.x];
+    const PartDesc D = descs[it.member];
+    const PartSlots S = slots[it.member];
+    const int16_t *const *ends = sc + 2 * ((size_t)task * nparts + it.member);
+    part_item_sums<MODE>(D, it, S.theta + (size_t)task * S.stride, ends[0], ends[1], x, smem,
+                         partials + 2 * ((size_t)task * gridDim.x + blockIdx.x));
+}
+
+// The update of one solve, run by one workgroup of kPartUpdateThreads: 64 members at a time, thread t sums the items of
+// member base + t in item order and applies the reference's per-partition NaN / inf rule (phylokernel.h:647-651); thread 0
+// then adds r df and r^2 ddf of those members in member order.  After the last member: newton_update, the state machine
+// of every enqueued chain.  partials: [nitems][2] of this solve; s_m: 2 * kPartUpdateThreads doubles of LDS.
+__device__ __forceinline__ void part_newton_update(const PartDesc *__restrict__ descs, int nparts,
+                                                   const double *__restrict__ partials, NewtonState *st, double *s_m) {
     if (st->done) return;
     double sdf = 0.0, sddf = 0.0;
     for (int base = 0; base < nparts; base += kPartUpdateThreads) {
@@ -165,15 +210,47 @@ __global__ __launch_bounds__(kPartUpdateThreads) void k_part_newton_update(const
     }
 }
 
-// out[m] = the MODE 1 sums of member m's items, in item order
+__global__ __launch_bounds__(kPartUpdateThreads) void k_part_newton_update(const PartDesc *__restrict__ descs, int nparts,
+                                                                           const double *__restrict__ partials,
+                                                                           NewtonState *st) {
+    __shared__ double s_m[2 * kPartUpdateThreads];
+    part_newton_update(descs, nparts, partials, st, s_m);
+}
+
+// ... of a batch: workgroup t advances the state machine of task t from partials[t][nitems][2]
+__global__ __launch_bounds__(kPartUpdateThreads) void k_part_newton_update_batch(const PartDesc *__restrict__ descs, int nparts,
+                                                                                 int nitems, const double *__restrict__ partials,
+                                                                                 NewtonState *states) {
+    __shared__ double s_m[2 * kPartUpdateThreads];
+    part_newton_update(descs, nparts, partials + 2 * (size_t)blockIdx.x * nitems, states + blockIdx.x, s_m);
+}
+
+// the MODE 1 sums of member m's items, in item order
+__device__ __forceinline__ double part_lnl_of_member(const PartDesc *__restrict__ descs, int m, const double *__restrict__ partials) {
+    const int first = descs[m].item_first, cnt = descs[m].nitems;
+    double s = 0.0;
+    for (int i = 0; i < cnt; i++) s += partials[2 * (size_t)(first + i)];
+    return s;
+}
+
+// out[m] = the MODE 1 sums of member m's items
 __global__ __launch_bounds__(64) void k_part_lnl_finish(const PartDesc *__restrict__ descs, int nparts,
                                                         const double *__restrict__ partials, double *__restrict__ out) {
     const int m = blockIdx.x * 64 + threadIdx.x;
     if (m >= nparts) return;
-    const int first = descs[m].item_first, cnt = descs[m].nitems;
-    double s = 0.0;
-    for (int i = 0; i < cnt; i++) s += partials[2 * (size_t)(first + i)];
-    out[m] = s;
+    out[m] = part_lnl_of_member(descs, m, partials);
+}
+
+// out[task][m] of a batch, task = blockIdx.y (of a task that is not done yet: whatever its partials hold; the pass behind
+// a later chunk of steps writes it again); a task that is done is marked, so that later MODE 1 passes leave it alone
+__global__ __launch_bounds__(64) void k_part_lnl_finish_batch(const PartDesc *__restrict__ descs, int nparts, int nitems,
+                                                              const double *__restrict__ partials,
+                                                              const NewtonState *__restrict__ states,
+                                                              int32_t *__restrict__ lnl_written, double *__restrict__ out) {
+    const int m = blockIdx.x * 64 + threadIdx.x;
+    if (m >= nparts) return;
+    out[(size_t)blockIdx.y * nparts + m] = part_lnl_of_member(descs, m, partials + 2 * (size_t)blockIdx.y * nitems);
+    if (m == 0 && states[blockIdx.y].done) lnl_written[blockIdx.y] = 1;
 }
 
 // The scale-factor term of a traversal's root-branch lnL (the lh_scale_factor of the two ends, phylokernel.h:1028): block m
@@ -214,6 +291,30 @@ hipError_t launch_part_newton_update(hipStream_t s, const PartDesc *d_desc, int 
 
 hipError_t launch_part_lnl_finish(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials, double *out) {
     hipLaunchKernelGGL(k_part_lnl_finish, dim3((unsigned)((nparts + 63) / 64)), dim3(64), 0, s, d_desc, nparts, partials, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_part_derv_batch(hipStream_t s, int mode, const PartDesc *d_desc, const PartItem *d_items, int nitems,
+                                  int lds_doubles, const PartSlots *d_slots, const int16_t *const *d_sc, int nparts,
+                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials) {
+    const size_t lds = (size_t)(lds_doubles + 8) * sizeof(double);
+    const dim3 grid((unsigned)nitems, (unsigned)ntasks);
+    if (mode == 0) hipLaunchKernelGGL(k_part_derv_batch<0>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials);
+    else hipLaunchKernelGGL(k_part_derv_batch<1>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_part_newton_update_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems,
+                                           const double *partials, NewtonState *states, int ntasks) {
+    hipLaunchKernelGGL(k_part_newton_update_batch, dim3((unsigned)ntasks), dim3(kPartUpdateThreads), 0, s, d_desc, nparts,
+                       nitems, partials, states);
+    return hipGetLastError();
+}
+
+hipError_t launch_part_lnl_finish_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems, const double *partials,
+                                        const NewtonState *states, int32_t *lnl_written, double *out, int ntasks) {
+    hipLaunchKernelGGL(k_part_lnl_finish_batch, dim3((unsigned)((nparts + 63) / 64), (unsigned)ntasks), dim3(64), 0, s, d_desc,
+                       nparts, nitems, partials, states, lnl_written, out);
     return hipGetLastError();
 }
 

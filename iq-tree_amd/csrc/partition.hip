@@ -39,6 +39,12 @@ struct iqhip_partition {
     PairBuf<double> out;             // per member: lnL sums / scale-factor terms
     PairBuf<NewtonState> state;
     DevBuf<double> d_partials;       // [nitems][2]
+    // iqhip_partition_optimize_branch_batch, per chunk of tasks
+    PairBuf<NewtonState> bstate;     // [tasks]
+    PairBuf<char> btable;            // [nparts] PartSlots ++ [tasks][nparts][2] scale-counter pointers
+    PairBuf<double> bout;            // [tasks][nparts]
+    DevBuf<double> d_bpartials;      // [tasks][nitems][2]
+    DevBuf<int32_t> d_blnl;          // [tasks]: the task's lnL sums are in d_bpartials
     int nitems = 0, lds_doubles = 0;
     // iqhip_debug_partition_timing
     std::vector<hipEvent_t> tev;
@@ -193,32 +199,62 @@ hipEvent_t timing_event(iqhip_partition *g, size_t k) {
     return g->tev[k];
 }
 
-int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, int max_steps, bool want_lnl,
-          NewtonState *result) {
+// one evaluation of an enqueued chain: the derivative launch, then the update launch; with timing, an event around each
+template <typename Derv, typename Update>
+int enqueue_step(iqhip_partition *g, bool timing, size_t *nev, Derv &&derv, Update &&update) {
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    if (timing) {
+        e0 = timing_event(g, *nev);
+        e1 = timing_event(g, *nev + 1);
+        e2 = timing_event(g, *nev + 2);
+        if (!e0 || !e1 || !e2) return fail(IQHIP_ERR_HIP, "partition group: hipEventCreate failed");
+        *nev += 3;
+        HIPCHK(hipEventRecord(e0, g->stream));
+    }
+    HIPCHK(derv());
+    if (timing) HIPCHK(hipEventRecord(e1, g->stream));
+    HIPCHK(update());
+    if (timing) HIPCHK(hipEventRecord(e2, g->stream));
+    g->launches += 2;
+    return IQHIP_OK;
+}
+
+// ms[0] / ms[1] += the device time of the derivative / update launches between the first nev events (the stream has drained)
+int collect_timing(iqhip_partition *g, size_t nev) {
+    for (size_t k = 0; k + 3 <= nev; k += 3) {
+        float a = 0.0f, b = 0.0f;
+        HIPCHK(hipEventElapsedTime(&a, g->tev[k], g->tev[k + 1]));
+        HIPCHK(hipEventElapsedTime(&b, g->tev[k + 1], g->tev[k + 2]));
+        g->ms[0] += a;
+        g->ms[1] += b;
+    }
+    return IQHIP_OK;
+}
+
+int steps_per_chunk(int enqueued, int max_steps) {
     int chunk_env = 0;
     if (const char *s = getenv("IQHIP_PART_STEPS")) chunk_env = atoi(s);
+    return chunk_env > 0 ? chunk_env : (enqueued == 0 ? std::min(4, max_steps + 1) : 2);
+}
+
+int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, int max_steps, bool want_lnl,
+          NewtonState *result) {
     const bool timing = g->m[0]->timing;
     size_t nev = 0;
+    if (timing) g->ms[0] = g->ms[1] = 0.0;
     HIPCHK(launch_newton_state_init_on(g->stream, g->state.d.p, xguess, x1, x2, xacc, max_steps));
     g->launches++;
     for (int enq = 0;;) {
-        const int chunk = chunk_env > 0 ? chunk_env : (enq == 0 ? std::min(4, max_steps + 1) : 2);
+        const int chunk = steps_per_chunk(enq, max_steps);
         for (int k = 0; k < chunk; k++) {
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-            if (timing) {
-                e0 = timing_event(g, nev);
-                e1 = timing_event(g, nev + 1);
-                e2 = timing_event(g, nev + 2);
-                if (!e0 || !e1 || !e2) return fail(IQHIP_ERR_HIP, "partition group: hipEventCreate failed");
-                nev += 3;
-                HIPCHK(hipEventRecord(e0, g->stream));
-            }
-            HIPCHK(launch_part_derv(g->stream, 0, d_desc(g), d_items(g), g->nitems, g->lds_doubles, g->state.d.p, 0.0,
-                                    g->d_partials.p));
-            if (timing) HIPCHK(hipEventRecord(e1, g->stream));
-            HIPCHK(launch_part_newton_update(g->stream, d_desc(g), g->nparts, g->d_partials.p, g->state.d.p));
-            if (timing) HIPCHK(hipEventRecord(e2, g->stream));
-            g->launches += 2;
+            const int rc = enqueue_step(
+                g, timing, &nev,
+                [&] {
+                    return launch_part_derv(g->stream, 0, d_desc(g), d_items(g), g->nitems, g->lds_doubles, g->state.d.p, 0.0,
+                                            g->d_partials.p);
+                },
+                [&] { return launch_part_newton_update(g->stream, d_desc(g), g->nparts, g->d_partials.p, g->state.d.p); });
+            if (rc) return rc;
         }
         enq += chunk;
         if (want_lnl) {
@@ -231,14 +267,8 @@ int solve(iqhip_partition *g, double xguess, double x1, double x2, double xacc, 
         if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
     }
     if (timing) {
-        g->ms[0] = g->ms[1] = 0.0;
-        for (size_t k = 0; k + 3 <= nev; k += 3) {
-            float a = 0.0f, b = 0.0f;
-            HIPCHK(hipEventElapsedTime(&a, g->tev[k], g->tev[k + 1]));
-            HIPCHK(hipEventElapsedTime(&b, g->tev[k + 1], g->tev[k + 2]));
-            g->ms[0] += a;
-            g->ms[1] += b;
-        }
+        const int rc = collect_timing(g, nev);
+        if (rc) return rc;
     }
     *result = *g->state.h.p;
     return IQHIP_OK;
@@ -405,6 +435,163 @@ extern "C" int iqhip_partition_traverse_lnl(iqhip_partition *g, const iqhip_node
         part_lnl[p] = v + g->out.h.p[p];
     }
     return IQHIP_OK;
+}
+
+namespace {
+
+// Tasks per chunk of a batch: every task owns a theta slot on every member.  All members' slots together stay within a
+// quarter of the free device memory (what the slots hold already counts as free); IQHIP_PART_BATCH_CHUNK, read per call,
+// lowers the bound.
+int batch_tasks_per_chunk(const iqhip_partition *g, int ntasks) {
+    int chunk = std::min(ntasks, kBatchChainChunk);
+    size_t per_task = 0, have = 0;
+    for (const iqhip_engine *e : g->m) {
+        per_task += (size_t)e->nptn_pad * e->block * sizeof(double);
+        have += e->d_theta_batch.cap * sizeof(double);
+        chunk = std::min(chunk, std::max(1, e->result_cap / 2));   // (eng_batch_prepare's own bound)
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        const size_t fit = std::max<size_t>(1, ((free_b + have) / 4) / std::max<size_t>(1, per_task));
+        if ((size_t)chunk > fit) chunk = (int)fit;
+    }
+    // (it cannot raise the bound, which is memory and eng_batch_prepare's limit: the rule of IQHIP_BATCH_CHUNK, batch_chunk())
+    if (const char *s = getenv("IQHIP_PART_BATCH_CHUNK")) chunk = std::max(1, std::min(chunk, atoi(s)));
+    return chunk;
+}
+
+// one chunk of m tasks: node updates and theta slots on the members' streams, the chain of joint solves on the group's
+// ops[0 .. total_ops): the tasks' node updates in task order, seg_of[t] of them task t's
+int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, const iqhip_node_op *ops, int total_ops,
+                    const int *seg_of, iqhip_branch_result *results, double *part_lnl) {
+    const int P = g->nparts;
+    const std::vector<int> segs(seg_of, seg_of + m);
+    int rc = IQHIP_OK;
+    std::vector<NewtonState> init((size_t)m);
+    int max_steps = 1;
+    for (int t = 0; t < m; t++) {
+        const iqhip_branch_task &k = tasks[t];
+        newton_init(init[t], k.xguess, k.x1, k.x2, k.xacc, k.max_steps);
+        max_steps = std::max(max_steps, k.max_steps);
+    }
+    const size_t bytes_slots = sizeof(PartSlots) * (size_t)P;
+    const size_t bytes_table = bytes_slots + sizeof(const int16_t *) * 2 * (size_t)m * P;
+    HIPCHK(hipSetDevice(g->device));
+    HIPCHK(g->bstate.ensure(g->stream, (size_t)m));
+    HIPCHK(g->btable.ensure(g->stream, bytes_table));
+    HIPCHK(g->bout.ensure(g->stream, (size_t)m * P));
+    HIPCHK(g->d_bpartials.ensure(g->stream, 2 * (size_t)m * g->nitems));
+    HIPCHK(g->d_blnl.ensure(g->stream, (size_t)m));
+    PartSlots *slots = reinterpret_cast<PartSlots *>(g->btable.h.p);
+    const int16_t **sc = reinterpret_cast<const int16_t **>(g->btable.h.p + bytes_slots);
+    std::vector<iqhip_node_op> mine(ops, ops + total_ops);
+    const iqhip_branch_end none = {0, -1, 0};
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        if (total_ops > 0) {
+            const double r = g->rate[p];
+            for (int k = 0; k < total_ops; k++) {
+                mine[k].left_len = ops[k].left_len * r;
+                mine[k].right_len = ops[k].right_len * r;
+            }
+            // (no reduction: the sum_scale rows are not read; the lnL takes its scale term from the counters)
+            rc = submit_traverse(e, mine.data(), total_ops, false, none, none, 0.0, /*skip_reduce=*/true, &segs);
+            if (rc) return rc;
+        }
+        rc = eng_batch_prepare(e, tasks, m, nullptr);   // (the states are the group's)
+        if (rc) return rc;
+        slots[p] = PartSlots{e->d_theta_batch.p, (size_t)e->nptn_pad * e->block};
+        for (int t = 0; t < m; t++) {
+            rc = branch_scale_counters(e, tasks[t].a, tasks[t].b, sc + 2 * ((size_t)t * P + p));
+            if (rc) return rc;
+        }
+    }
+    HIPCHK(hipSetDevice(g->device));
+    rc = wait_for_members(g);
+    if (rc) return rc;
+    memcpy(g->bstate.h.p, init.data(), sizeof(NewtonState) * (size_t)m);
+    HIPCHK(hipMemcpyAsync(g->bstate.d.p, g->bstate.h.p, sizeof(NewtonState) * (size_t)m, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->btable.d.p, g->btable.h.p, bytes_table, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemsetAsync(g->d_blnl.p, 0, sizeof(int32_t) * (size_t)m, g->stream));
+    const PartSlots *d_slots = reinterpret_cast<const PartSlots *>(g->btable.d.p);
+    const int16_t *const *d_sc = reinterpret_cast<const int16_t *const *>(g->btable.d.p + bytes_slots);
+    const bool timing = g->m[0]->timing;
+    size_t nev = 0;
+    const auto derv = [&](int mode) {
+        return launch_part_derv_batch(g->stream, mode, d_desc(g), d_items(g), g->nitems, g->lds_doubles, d_slots, d_sc, P,
+                                      g->bstate.d.p, g->d_blnl.p, m, g->d_bpartials.p);
+    };
+    for (int enq = 0;;) {
+        const int chunk = steps_per_chunk(enq, max_steps);
+        for (int k = 0; k < chunk; k++) {
+            rc = enqueue_step(g, timing, &nev, [&] { return derv(0); }, [&] {
+                return launch_part_newton_update_batch(g->stream, d_desc(g), P, g->nitems, g->d_bpartials.p, g->bstate.d.p, m);
+            });
+            if (rc) return rc;
+        }
+        enq += chunk;
+        // the lnL pass rides behind every chunk of steps (the host cannot know which is the last): a task still solving
+        // does nothing, a task done in an earlier chunk has its sums already, and what the last finish wrote is what is read
+        HIPCHK(derv(1));
+        HIPCHK(launch_part_lnl_finish_batch(g->stream, d_desc(g), P, g->nitems, g->d_bpartials.p, g->bstate.d.p, g->d_blnl.p, g->bout.d.p,
+                                            m));
+        g->launches += 2;
+        HIPCHK(hipMemcpyAsync(g->bout.h.p, g->bout.d.p, sizeof(double) * (size_t)m * P, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipMemcpyAsync(g->bstate.h.p, g->bstate.d.p, sizeof(NewtonState) * (size_t)m, hipMemcpyDeviceToHost, g->stream));
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (std::all_of(g->bstate.h.p, g->bstate.h.p + m, [](const NewtonState &s) { return s.done != 0; })) break;
+        if (enq > max_steps + 2) return fail(IQHIP_ERR_INVALID, "Newton chain did not terminate");
+    }
+    // (the group's stream waited for the members' and has drained: so have their submissions)
+    for (iqhip_engine *e : g->m) result_arrived(e);
+    if (timing) {
+        rc = collect_timing(g, nev);
+        if (rc) return rc;
+    }
+    for (int t = 0; t < m; t++) {
+        NewtonResult(g->bstate.h.p[t]).store(results[t]);   // (a status 2 or 3 goes to the caller in results[t].status)
+        const double *o = g->bout.h.p + (size_t)t * P;
+        double lnl = 0.0;
+        for (int p = 0; p < P; p++) lnl += o[p];
+        results[t].lnl = lnl;
+        if (part_lnl) memcpy(part_lnl + (size_t)t * P, o, sizeof(double) * (size_t)P);
+    }
+    return IQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const iqhip_branch_task *tasks, int ntasks,
+                                                     iqhip_branch_result *results, double *part_lnl) {
+    const char *what = "iqhip_partition_optimize_branch_batch";
+    if (!g) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null group");
+    if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad task array");
+    // every task is checked before any member is touched; a chunk takes its slice of the gathered ops
+    std::vector<iqhip_node_op> ops;
+    std::vector<int> segs;
+    int rc = batch_gather_ops(tasks, ntasks, ops, segs);
+    if (rc) return rc;
+    rc = use_group(g, what);
+    if (rc) return rc;
+    g->launches = 0;
+    if (g->m[0]->timing) g->ms[0] = g->ms[1] = 0.0;
+    rc = refresh_table(g);
+    if (rc) return rc;
+    const int chunk = batch_tasks_per_chunk(g, ntasks);
+    size_t op_first = 0;
+    for (int first = 0; first < ntasks && !rc; first += chunk) {
+        const int m = std::min(chunk, ntasks - first);
+        size_t nops = 0;
+        for (int t = 0; t < m; t++) nops += (size_t)segs[first + t];
+        rc = batch_run_chunk(g, tasks + first, m, ops.data() + op_first, (int)nops, segs.data() + first, results + first,
+                             part_lnl ? part_lnl + (size_t)first * g->nparts : nullptr);
+        op_first += nops;
+        // (whatever happened: the members wait for what the group did enqueue, and no slot is rewritten under it)
+        const int rc2 = members_wait(g);
+        if (!rc) rc = rc2;
+    }
+    if (rc) (void)hipStreamSynchronize(g->stream);   // (the staging buffers are free for the next call)
+    return rc;
 }
 
 extern "C" int iqhip_debug_partition_timing(iqhip_partition *g, double *ms, int64_t *launches) {

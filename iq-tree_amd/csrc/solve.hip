@@ -506,6 +506,7 @@ int iqhip::batch_asc_lnl(const iqhip_engine *e, double prob_const, double *lnl) 
     return IQHIP_OK;
 }
 
+// init == nullptr: the theta slots only -- the caller keeps the state machines and sums the slots itself (partition.hip)
 int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, int m, const NewtonState *init) {
     int rc = check_ready(e);
     if (rc) return rc;
@@ -515,7 +516,7 @@ int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, in
     if (rc) return rc;
     const size_t theta_stride = (size_t)e->nptn_pad * e->block;
     HIPCHK(e->d_theta_batch.ensure(e, (size_t)m * theta_stride));
-    HIPCHK(e->d_bstates.ensure(e, (size_t)m));
+    if (init) HIPCHK(e->d_bstates.ensure(e, (size_t)m));
     if (e->asc_active) HIPCHK(e->d_bsc.ensure(e, (size_t)2 * m));
     std::vector<const int16_t *> sc;
     for (int t = 0; t < m; t++) {
@@ -531,7 +532,7 @@ int iqhip::eng_batch_prepare(iqhip_engine *e, const iqhip_branch_task *tasks, in
     // (pageable source, as the states below)
     if (e->asc_active)
         HIPCHK(hipMemcpyAsync(e->d_bsc.p, sc.data(), sizeof(const int16_t *) * sc.size(), hipMemcpyHostToDevice, e->stream));
-    return eng_batch_states_write(e, m, init);
+    return init ? eng_batch_states_write(e, m, init) : IQHIP_OK;
 }
 
 int iqhip::eng_batch_states_write(iqhip_engine *e, int m, const NewtonState *in) {

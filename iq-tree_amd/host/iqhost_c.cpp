@@ -1145,6 +1145,7 @@ struct SearchHandle {
     TreeSearch search;
     std::vector<TreeSearch::NNIStep> nni_steps;   // of the last iqhost_search_optimize_nni
     explicit SearchHandle(PhyloTree *t) : search(t) {}
+    explicit SearchHandle(PhyloSuperTree *t) : search(t) {}
 };
 void put_text(const std::string &s, char *out, int cap, int *need) {
     if (need) *need = (int)s.size() + 1;
@@ -1257,6 +1258,9 @@ int iqhost_candset_entry(void *c, int rank, double *score, char *text, int cap, 
 int iqhost_search_create(void **out, void *tree) {
     IQHOST_TRY(*out = new SearchHandle((PhyloTree *)tree));
 }
+int iqhost_search_create_super(void **out, void *super_tree) {
+    IQHOST_TRY(*out = new SearchHandle((PhyloSuperTree *)super_tree));
+}
 void iqhost_search_destroy(void *s) { delete (SearchHandle *)s; }
 // iv: nni5, speednni, batched, popSize, stop condition, min_iteration, unsuccess_iteration, max_iteration, step_iterations,
 // keep_trace, numInitTrees, numNNITrees, initSprRadius; dv: initPS, min_correlation
@@ -1279,7 +1283,7 @@ int iqhost_search_optimize_nni(void *s, double *lnl, int *nni_count, int *nni_st
         SearchHandle *sh = (SearchHandle *)s;
         sh->search.checkEligible("optimizeNNI");
         sh->nni_steps.clear();
-        sh->search.tree->computeLikelihood();
+        sh->search.computeLikelihood();
         *lnl = sh->search.optimizeNNI(*nni_count, *nni_steps, sh->search.keep_trace ? &sh->nni_steps : nullptr);
     });
 }
@@ -1438,6 +1442,97 @@ int iqhost_super_counters(void *h, long *out) {
     out[1] = t->num_group_traversals;
     out[2] = t->num_diverged;
     return 0;
+}
+long iqhost_super_group_batches(void *h) { return ((PhyloSuperTree *)h)->num_group_batches; }
+
+// ---- NNI on the super tree (supertree_host.h): the layouts of the plain tree's calls above
+int iqhost_super_set_all_branch_mode(void *h) { IQHOST_TRY(((PhyloSuperTree *)h)->setAllBranchMode()); }
+// the super tree's topology as a PhyloTree handle for the read-only calls above (tree string, sorted taxon ids, neighbours);
+// it has no engine and is owned by the super tree
+void *iqhost_super_tree(void *h) { return &((PhyloSuperTree *)h)->super; }
+// a candidate tree on the same taxa: re-read by the super tree and every member, engines kept
+int iqhost_super_read_tree(void *h, const char *newick) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        std::vector<std::string> names;
+        bool named = false;
+        for (int i = 0; i < t->super.leafNum; i++) {
+            const PhyloNode *n = t->super.nodes[(size_t)i];
+            named = named || !n->name.empty();
+            names.push_back(n->name.empty() ? std::to_string(n->id) : n->name);
+        }
+        t->readTreeString(newick, named ? names : std::vector<std::string>());
+    });
+}
+int iqhost_super_num_nodes(void *h) { return ((PhyloSuperTree *)h)->super.nodeNum; }
+int iqhost_super_num_leaves(void *h) { return ((PhyloSuperTree *)h)->super.leafNum; }
+int iqhost_super_neighbors(void *h, int node, int *ids, double *lens, int cap) {
+    return iqhost_neighbors(&((PhyloSuperTree *)h)->super, node, ids, lens, cap);
+}
+int iqhost_super_do_nni(void *h, int node1, int node2, int node1_nei, int node2_nei) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        t->doNNI(nni_move(&t->super, node1, node2, node1_nei, node2_nei));
+    });
+}
+int iqhost_super_change_nni_brans(void *h, int node1, int node2, const double *new_len, int nni5) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        PhyloTree::NNIMove mv = nni_move(&t->super, node1, node2, -1, -1);
+        for (int i = 0; i < 5; i++) mv.newLen[i] = new_len[i];
+        t->changeNNIBrans(mv, nni5 != 0);
+    });
+}
+int iqhost_super_do_random_nni(void *h, int a, int b, int bit1, int bit2, int *out) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        nei(&t->super, a, b);
+        const PhyloTree::NNIMove mv = t->doOneRandomNNI(a, b, bit1, bit2);
+        out[0] = mv.node1; out[1] = mv.node2; out[2] = mv.node1_nei; out[3] = mv.node2_nei;
+    });
+}
+int iqhost_super_save_branch_lengths(void *h, double *out, int cap, int *n) {
+    IQHOST_TRY({
+        std::vector<double> v;
+        ((PhyloSuperTree *)h)->saveBranchLengths(v);
+        *n = (int)v.size();
+        if (out && (int)v.size() <= cap) memcpy(out, v.data(), sizeof(double) * v.size());
+    });
+}
+int iqhost_super_restore_branch_lengths(void *h, const double *in, int n) {
+    IQHOST_TRY(((PhyloSuperTree *)h)->restoreBranchLengths(std::vector<double>(in, in + n)));
+}
+int iqhost_super_clear_all_partial_lh(void *h) { IQHOST_TRY(((PhyloSuperTree *)h)->clearAllPartialLH()); }
+int iqhost_super_nni_for_branch(void *h, int a, int b, int nni5, double *out) {
+    IQHOST_TRY({
+        PhyloTree::NNIMove mv[2];
+        ((PhyloSuperTree *)h)->getBestNNIForBran(a, b, nni5 != 0, mv);
+        for (int c = 0; c < 2; c++) {
+            out[c * 8 + 0] = mv[c].newloglh;
+            out[c * 8 + 1] = mv[c].node1_nei;
+            out[c * 8 + 2] = mv[c].node2_nei;
+            for (int k = 0; k < 5; k++) out[c * 8 + 3 + k] = mv[c].newLen[k];
+        }
+    });
+}
+int iqhost_super_evaluate_nnis_list(void *h, int nni5, const int *branches, int nbranches, int *ids, double *vals, int cap, int *n) {
+    IQHOST_TRY({
+        PhyloSuperTree *t = (PhyloSuperTree *)h;
+        PhyloTree::BranchList list;
+        for (int q = 0; branches && q < nbranches; q++) list.push_back({branches[2 * q], branches[2 * q + 1]});
+        std::vector<PhyloTree::NNIMove> mv;
+        if (nni5) t->evaluateNNIs5Batch(mv, branches ? &list : nullptr);
+        else t->evaluateNNIsBatch(mv, branches ? &list : nullptr);
+        if ((int)mv.size() > cap) throw std::runtime_error("output too small");
+        *n = (int)mv.size();
+        const int w = nni5 ? 6 : 2;
+        for (size_t k = 0; k < mv.size(); k++) {
+            ids[4 * k] = mv[k].node1; ids[4 * k + 1] = mv[k].node2;
+            ids[4 * k + 2] = mv[k].node1_nei; ids[4 * k + 3] = mv[k].node2_nei;
+            for (int i = 0; i < w - 1; i++) vals[w * k + i] = mv[k].newLen[i];
+            vals[w * k + w - 1] = mv[k].newloglh;
+        }
+    });
 }
 
 }  // extern "C"

@@ -212,6 +212,19 @@ public:
     // iqhip_optimize_branch_batch_rows, so every candidate's per-pattern lnL lands in its store row on the device
     // ptnlh_rows with a branch list: 2 per LISTED branch in move order
     void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows = nullptr, const BranchList *branches = nullptr);
+    // Who runs the tasks of a batched NNI evaluation for a tree WITHOUT an engine of its own: the super tree of an
+    // edge-linked partition model (supertree_host.h) sets itself here, and the candidate and task construction, the two
+    // nni1 rounds and the five nni5 rounds of phylo_nni.cpp serve it unchanged.  The tree's Neighbor keys must be the keys
+    // the backend's engines know; results[t].lnl is the whole log-likelihood (the scale-factor terms included), so the
+    // scaffold adds nothing to it: the Neighbors of such a tree carry lh_scale_factor 0 and the per-op sums are 0.
+    struct NNIBackend {
+        virtual ~NNIBackend() {}
+        // every directed vector valid (all), or the four around each listed branch; the tree's keys and next_key in step
+        virtual void pendingVectors(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2, bool all) = 0;
+        virtual void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) = 0;
+        virtual void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2]) = 0;   // the branch-by-branch path
+    };
+    NNIBackend *nni_backend = nullptr;
     // the internal branches in the order both NNI evaluations list them (node1->id < node2->id)
     void internalBranches(std::vector<PhyloNode *> &n1, std::vector<PhyloNode *> &n2) const;
     // the four subtree vectors around each listed branch (what its NNI candidates read), one submission; LM_ALL_BRANCH
@@ -530,6 +543,7 @@ private:
     // both batched NNI evaluators: the refusals, the branches, their vectors, the inputs (false: an empty list); then rounds of
     // branch solves (rows: nullptr or a store row per task; sum_scale: per op in task order; diverged: optx > 0.95 max length)
     bool beginNNIBatch(const char *who, const BranchList *branches, std::vector<PhyloNode *> &bn1, std::vector<PhyloNode *> &bn2);
+    void branchByBranch(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2], const int *ptnlh_rows);
     void submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, const int32_t *rows, std::vector<double> &sum_scale,
                            std::vector<iqhip_branch_result> &res, std::vector<char> &diverged);
 

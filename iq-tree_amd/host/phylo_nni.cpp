@@ -179,13 +179,17 @@ static void nniBranches(const PhyloTree *t, const PhyloTree::BranchList *branche
 // ---- what the two batched evaluators share ---------------------------------------------------------------------------------
 bool PhyloTree::beginNNIBatch(const char *who, const BranchList *branches, std::vector<PhyloNode *> &bn1,
                               std::vector<PhyloNode *> &bn2) {
-    needDevice(who);
+    if (!nni_backend) needDevice(who);
     if (allreduce_hook) throw std::runtime_error(std::string(who) + ": runs with a caller-owned collective use getBestNNIForBran");
     nniBranches(this, branches, who, bn1, bn2);
     if (branches && bn1.empty()) return false;
-    if (branches) computePartialLhAround(bn1, bn2);
-    else computeAllPartialLh();
-    pushInputs();
+    if (nni_backend) {
+        nni_backend->pendingVectors(bn1, bn2, !branches);
+    } else {
+        if (branches) computePartialLhAround(bn1, bn2);
+        else computeAllPartialLh();
+        pushInputs();
+    }
     while (nni_batch_keys.size() < 4 * bn1.size()) nni_batch_keys.push_back(next_key++);   // four scratch vectors per branch
     return true;
 }
@@ -225,7 +229,10 @@ void PhyloTree::submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, c
     for (const iqhip_branch_task &k : tasks) nops += (size_t)k.nops;
     sum_scale.assign(nops, 0.0);
     res.resize(n);
-    if (rows)
+    if (nni_backend) {   // (the backend's lnL carries the scale-factor terms: the per-op sums stay 0)
+        if (rows) throw std::runtime_error("per-pattern rows are not available through an NNI backend");
+        nni_backend->submitTasks(tasks, res);
+    } else if (rows)
         check(iqhip_optimize_branch_batch_rows(engine, tasks.data(), (int)n, sum_scale.data(), res.data(), rows),
               "iqhip_optimize_branch_batch_rows");
     else
@@ -237,6 +244,12 @@ void PhyloTree::submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, c
         num_derv_calls += res[q].nsteps;
         diverged[q] = res[q].optx > max_branch_length * 0.95;
     }
+}
+
+// the fallback of a diverged solve: this tree's own getBestNNIForBran, or the backend's
+void PhyloTree::branchByBranch(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2], const int *ptnlh_rows) {
+    if (nni_backend) nni_backend->bestNNIForBran(node1->id, node2->id, nni5, moves);
+    else getBestNNIForBran(node1, node2, nni5, moves, ptnlh_rows);
 }
 
 void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches) {
@@ -295,7 +308,7 @@ void PhyloTree::evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList 
             // length and may restore the latter): rare; the one-branch path for this candidate -- and for the second swap
             // of a branch whose first swap diverged, because its starting length is whatever that comparison left
             NNIMove two[2];
-            getBestNNIForBran(c.node1, c.node2, false, two);
+            branchByBranch(c.node1, c.node2, false, two, nullptr);
             m = two[round];
         }
     }
@@ -428,7 +441,7 @@ void PhyloTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh
         for (size_t q = 0; q < nb; q++)
             if (work[q].diverged) {  // diverged Newton (phylotree.cpp:2167-2176): rare; take the branch-by-branch path
                 NNIMove two[2];
-                getBestNNIForBran(branches[q].node1, branches[q].node2, true, two, ptnlh_rows ? ptnlh_rows + 2 * q : nullptr);
+                branchByBranch(branches[q].node1, branches[q].node2, true, two, ptnlh_rows ? ptnlh_rows + 2 * q : nullptr);
                 moves[2 * q] = two[0];
                 moves[2 * q + 1] = two[1];
             }

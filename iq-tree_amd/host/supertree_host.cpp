@@ -59,6 +59,7 @@ void readPartitionRaxml(const std::string &aln_file, const std::string &part_fil
 PhyloSuperTree::PhyloSuperTree() {}
 
 PhyloSuperTree::~PhyloSuperTree() {
+    super.nni_backend = nullptr;
     if (group) iqhip_partition_destroy(group);   // before its members
     for (PhyloTree *t : parts) delete t;
 }
@@ -72,8 +73,21 @@ void PhyloSuperTree::needGroup() const {
 }
 
 void PhyloSuperTree::readTreeString(const std::string &newick, const std::vector<std::string> &names) {
-    if (!parts.empty()) throw std::runtime_error("PhyloSuperTree: read the tree before adding partitions");
+    if (parts.empty()) {
+        super.readTreeString(newick, names);
+        return;
+    }
+    // a candidate tree of the search: the same taxa on every tree, engines, models and rates kept.  Every tree parses the
+    // same string, so node ids and neighbour order agree; all member vectors are dropped and their keys handed out anew,
+    // alike on every member
+    const int nleaf = super.leafNum;
     super.readTreeString(newick, names);
+    if (super.leafNum != nleaf) throw std::runtime_error("PhyloSuperTree: the tree has another number of taxa than the partitions");
+    for (PhyloTree *t : parts) {
+        t->readTreeString(newick, names);
+        t->theta_computed = false;
+    }
+    pushLengths();
 }
 
 PhyloTree *PhyloSuperTree::addPartition(const std::string &name) {
@@ -116,6 +130,9 @@ void PhyloSuperTree::attachEngines(int device) {
     hip(iqhip_partition_create(&group, members.data(), (int)members.size()), "iqhip_partition_create");
     hip(iqhip_partition_set_rates(group, part_rate.data()), "iqhip_partition_set_rates");
     pushLengths();
+    super.nni_backend = this;   // from here on the NNI scaffold run on `super` goes to the group
+    super.min_branch_length = min_branch_length;
+    super.max_branch_length = max_branch_length;
 }
 
 double PhyloSuperTree::totalNSite() const {
@@ -221,6 +238,8 @@ double PhyloSuperTree::optimizeOneBranch(int a, int b, bool clearLH, int maxNRSt
 void PhyloSuperTree::setBranchBounds(double lo, double hi) {
     min_branch_length = lo;
     max_branch_length = hi;
+    super.min_branch_length = lo;
+    super.max_branch_length = hi;
     for (PhyloTree *t : parts) {
         t->min_branch_length = lo;
         t->max_branch_length = hi;
@@ -356,6 +375,142 @@ double PhyloSuperTree::optimizeGeneRate(double gradient_epsilon) {
     hip(iqhip_partition_set_rates(group, part_rate.data()), "iqhip_partition_set_rates");
     pushLengths();   // (the members' vectors belong to the last trial scales: all dropped)
     return sumScores();
+}
+
+// ---- NNI on the super tree ------------------------------------------------------------------------------------------------
+void PhyloSuperTree::setAllBranchMode() {
+    if (group) throw std::runtime_error("PhyloSuperTree: setAllBranchMode comes before attachEngines");
+    super.lh_mem_save = LM_ALL_BRANCH;
+    for (PhyloTree *t : parts) t->lh_mem_save = LM_ALL_BRANCH;
+}
+
+void PhyloSuperTree::doNNI(const NNIMove &move) {
+    super.doNNI(move, true);
+    for (PhyloTree *t : parts) t->doNNI(move, true);
+}
+
+void PhyloSuperTree::changeNNIBrans(const NNIMove &move, bool nni5) {
+    super.changeNNIBrans(move, nni5);
+    for (size_t p = 0; p < parts.size(); p++) {
+        PhyloTree *t = parts[p];
+        NNIMove mine = move;
+        for (double &l : mine.newLen) l *= part_rate[p];
+        t->changeNNIBrans(mine, nni5);
+        PhyloNode *node1 = t->nodes[(size_t)move.node1], *node2 = t->nodes[(size_t)move.node2];
+        node1->findNeighbor(node2)->clearPartialLh();
+        node2->findNeighbor(node1)->clearPartialLh();
+        node2->clearReversePartialLh(node1);
+        node1->clearReversePartialLh(node2);
+        t->theta_computed = false;
+    }
+}
+
+PhyloSuperTree::NNIMove PhyloSuperTree::doOneRandomNNI(int a, int b, int bit1, int bit2) {
+    if (a < 0 || b < 0 || a >= super.nodeNum || b >= super.nodeNum) throw std::runtime_error("doOneRandomNNI: bad node id");
+    const NNIMove mv = super.doOneRandomNNI(super.nodes[(size_t)a], super.nodes[(size_t)b], bit1, bit2);
+    for (PhyloTree *t : parts) t->doNNI(mv, false);   // (no vector is cleared: the caller recomputes everything)
+    return mv;
+}
+
+void PhyloSuperTree::restoreBranchLengths(const std::vector<double> &lenvec) {
+    super.restoreBranchLengths(lenvec);
+    pushLengths();
+}
+
+void PhyloSuperTree::clearAllPartialLH() {
+    for (PhyloTree *t : parts) {
+        t->theta_computed = false;
+        t->clearAllPartialLH();
+    }
+}
+
+PhyloSuperTree::NNIMove PhyloSuperTree::getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2]) {
+    needGroup();
+    if (a < 0 || b < 0 || a >= super.nodeNum || b >= super.nodeNum) throw std::runtime_error("getBestNNIForBran: bad node id");
+    PhyloNode *node1 = super.nodes[(size_t)a], *node2 = super.nodes[(size_t)b];
+    if (!node1->findNeighbor(node2) || node1->isLeaf() || node2->isLeaf() || node1->degree() != 3 || node2->degree() != 3)
+        throw std::runtime_error("getBestNNIForBran needs an internal branch of a binary tree");
+    std::vector<double> saved;
+    super.saveBranchLengths(saved);
+    const std::vector<double> backup = cur_score;
+    auto others = [](PhyloNode *at, PhyloNode *other) {
+        std::vector<int> ids;
+        for (PhyloNeighbor *nb : at->neighbors)
+            if (nb->node != other) ids.push_back(nb->node->id);
+        return ids;
+    };
+    // the two moves: first other neighbour of node1 against each other neighbour of node2 (:2951-2960), named before any swap
+    const int first1 = others(node1, node2)[0];
+    const std::vector<int> at2 = others(node2, node1);
+    for (int cnt = 0; cnt < 2; cnt++) {
+        NNIMove &m = moves[cnt] = NNIMove();
+        m.node1 = a; m.node2 = b; m.node1_nei = first1; m.node2_nei = at2[(size_t)cnt];
+        doNNI(m);
+        int i = 1;
+        if (nni5)
+            for (int x : others(node1, node2)) m.newLen[i++] = optimizeOneBranch(a, x, true, PhyloTree::NNI_MAX_NR_STEP);
+        m.newLen[0] = optimizeOneBranch(a, b, true, PhyloTree::NNI_MAX_NR_STEP);
+        if (nni5)
+            for (int y : others(node2, node1)) m.newLen[i++] = optimizeOneBranch(b, y, true, PhyloTree::NNI_MAX_NR_STEP);
+        m.newloglh = sumScores();
+        doNNI(m);   // (the same move again restores the tree, neighbour order included; the lengths stay for the second swap)
+    }
+    restoreBranchLengths(saved);
+    cur_score = backup;
+    return moves[0].newloglh > moves[1].newloglh ? moves[0] : moves[1];
+}
+
+void PhyloSuperTree::pendingVectors(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2, bool all) {
+    needGroup();
+    uint64_t top = super.next_key;
+    for (PhyloTree *t : parts) {
+        if (t->lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error("PhyloSuperTree: the batched NNI evaluation needs setAllBranchMode");
+        if (all) t->computeAllPartialLh();
+        else {
+            std::vector<PhyloNode *> m1, m2;
+            for (size_t q = 0; q < n1.size(); q++) {
+                m1.push_back(t->nodes[(size_t)n1[q]->id]);
+                m2.push_back(t->nodes[(size_t)n2[q]->id]);
+            }
+            t->computePartialLhAround(m1, m2);
+        }
+        t->pushInputs();
+        t->theta_computed = false;
+        top = std::max(top, t->next_key);
+    }
+    // one key space: the super tree's Neighbors name the members' vectors, and no tree hands out a key another one uses
+    for (size_t i = 0; i < super.nodes.size(); i++)
+        for (size_t k = 0; k < super.nodes[i]->neighbors.size(); k++) {
+            const uint64_t key = parts[0]->nodes[i]->neighbors[k]->partial_lh;
+            for (PhyloTree *t : parts)
+                if (t->nodes[i]->neighbors[k]->partial_lh != key || t->nodes[i]->neighbors[k]->node->id != super.nodes[i]->neighbors[k]->node->id)
+                    throw std::runtime_error("PhyloSuperTree: the members' vector keys differ (same memory mode and history needed)");
+            super.nodes[i]->neighbors[k]->partial_lh = key;
+            super.nodes[i]->neighbors[k]->lh_scale_factor = 0.0;
+        }
+    super.central_partial_lh = true;
+    for (uint64_t k : super.nni_batch_keys) top = std::max(top, k + 1);
+    super.next_key = top;
+    const uint64_t after = top + 4 * (uint64_t)n1.size();   // (beyond the scratch keys the scaffold may take now)
+    for (PhyloTree *t : parts) t->next_key = std::max(t->next_key, after);
+}
+
+void PhyloSuperTree::submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) {
+    num_group_batches++;
+    hip(iqhip_partition_optimize_branch_batch(group, tasks.data(), (int)tasks.size(), res.data(), nullptr),
+        "iqhip_partition_optimize_branch_batch");
+    for (const iqhip_branch_result &r : res)
+        for (PhyloTree *t : parts) t->num_derv_calls += r.nsteps;
+}
+
+void PhyloSuperTree::evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches) {
+    needGroup();
+    super.evaluateNNIsBatch(moves, branches);
+}
+
+void PhyloSuperTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const BranchList *branches) {
+    needGroup();
+    super.evaluateNNIs5Batch(moves, nullptr, branches);
 }
 
 double PhyloSuperTree::optimizeParameters(bool fixed_len, double logl_epsilon, double gradient_epsilon) {

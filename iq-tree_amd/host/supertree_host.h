@@ -52,13 +52,18 @@ void readPartitionRaxml(const std::string &aln_file, const std::string &part_fil
 void readPartitionStrings(const std::string &aln_content, const std::string &part_content, std::vector<std::string> &seq_names,
                           std::vector<PartitionInput> &parts);
 
-class PhyloSuperTree {
+class PhyloSuperTree : private PhyloTree::NNIBackend {
 public:
+    typedef PhyloTree::NNIMove NNIMove;
+    typedef PhyloTree::BranchList BranchList;
     PhyloSuperTree();
     ~PhyloSuperTree();
     PhyloSuperTree(const PhyloSuperTree &) = delete;
     PhyloSuperTree &operator=(const PhyloSuperTree &) = delete;
 
+    // before the first partition: the super tree.  Later: a candidate tree of the search on the same taxa -- `super` and every
+    // member re-read it (node ids and neighbour order agree), engines, models and rates stay, member lengths = rate x super
+    // lengths, every member vector is dropped
     void readTreeString(const std::string &newick, const std::vector<std::string> &names);
     std::string getTreeString() const { return super.getTreeString(); }
     // a new member of the super tree's topology; the caller gives it its alignment and model (setAlignment, setModel)
@@ -93,13 +98,38 @@ public:
     // the branches in the order optimizeAllBranches visits them (node ids)
     void branchOrder(std::vector<int> &n1, std::vector<int> &n2);
 
-    // counters (tests, bench): joint solves, group traversals, diverged-Newton resets; of the last optimizeGeneRate: Brent
-    // evaluations per member and lockstep rounds
-    long num_group_solves = 0, num_group_traversals = 0, num_diverged = 0;
+    // ---- NNI on the super tree: the single-tree operation applied to `super` and, by node id, to every member.  Moves
+    //      and their five lengths are in super-tree units; member lengths are rate x super length.
+    // every member (and the super tree, for its keys) keeps a buffer per directed vector: what the batched evaluations
+    // need.  Before the engines are attached.
+    void setAllBranchMode();
+    void doNNI(const NNIMove &move);                        // PhyloTree::doNNI(move, clearLH = true) on all of them
+    void changeNNIBrans(const NNIMove &move, bool nni5);    // ... and the vectors that look through the five branches go stale
+    NNIMove doOneRandomNNI(int a, int b, int bit1, int bit2);
+    void saveBranchLengths(std::vector<double> &lenvec) const { super.saveBranchLengths(lenvec); }
+    void restoreBranchLengths(const std::vector<double> &lenvec);   // and the members' lengths; every member vector dropped
+    void clearAllPartialLH();
+    // The branch-by-branch path (PhyloTree::getBestNNIForBran, phylotree.cpp:2873-3066) from existing calls only: each swap
+    // is made on every tree, the central branch (nni5: the two at node1, the central one, the two at node2) solved jointly
+    // with optimizeOneBranch in the reference's order, the summed lnL taken, and the swap undone; the second swap starts
+    // from the lengths the first left, and all lengths are restored at the end.  Every member vector is dropped.
+    NNIMove getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2]);
+    // the two / ten rounds of phylo_nni.cpp run on `super`, one iqhip_partition_optimize_branch_batch per round; a
+    // candidate whose solve diverged (optx > 0.95 max_branch_length) takes the branch-by-branch path.  setAllBranchMode.
+    void evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr);
+    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr);
+
+    // counters (tests, bench): joint solves, batches of joint solves, group traversals, diverged-Newton resets; of the last
+    // optimizeGeneRate: Brent evaluations per member and lockstep rounds
+    long num_group_solves = 0, num_group_batches = 0, num_group_traversals = 0, num_diverged = 0;
     std::vector<int> gene_rate_evals;
     int gene_rate_rounds = 0;
 
 private:
+    // PhyloTree::NNIBackend for `super`
+    void pendingVectors(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2, bool all) override;
+    void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) override;
+    void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2]) override { getBestNNIForBran(node1, node2, nni5, moves); }
     void needGroup() const;
     void pushLengths();                   // member lengths = rate x super lengths; all member vectors dropped
     void prepareBranch(int a, int b);     // current_it + pending partials + theta of (a, b) on every member

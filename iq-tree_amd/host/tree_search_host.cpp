@@ -13,6 +13,41 @@ TreeSearch::TreeSearch(PhyloTree *t) : tree(t) {
     if (!t) throw std::runtime_error("TreeSearch: no tree");
 }
 
+TreeSearch::TreeSearch(PhyloSuperTree *st) : tree(st ? &st->super : nullptr), stree(st) {
+    if (!st) throw std::runtime_error("TreeSearch: no tree");
+}
+
+double TreeSearch::computeLikelihood() {
+    if (stree) tree->curScore = stree->computeLikelihood();
+    else tree->computeLikelihood();
+    return tree->curScore;
+}
+void TreeSearch::readTree(const std::string &newick, const std::vector<std::string> &names) {
+    if (stree) stree->readTreeString(newick, names);
+    else tree->readTreeString(newick, names);
+}
+void TreeSearch::doNNI(const NNIMove &mv) {
+    if (stree) stree->doNNI(mv);
+    else tree->doNNI(mv);
+}
+void TreeSearch::changeNNIBrans(const NNIMove &mv) {
+    if (stree) stree->changeNNIBrans(mv, nni5);
+    else tree->changeNNIBrans(mv, nni5);
+}
+double TreeSearch::sweep() {
+    return stree ? stree->optimizeAllBranches(1, loglh_epsilon, PhyloTree::NNI_MAX_NR_STEP)
+                 : tree->optimizeAllBranches(1, loglh_epsilon, PhyloTree::NNI_MAX_NR_STEP);
+}
+void TreeSearch::restore(const std::vector<double> &lenvec) {
+    if (stree) {
+        stree->restoreBranchLengths(lenvec);
+        stree->clearAllPartialLH();
+    } else {
+        tree->restoreBranchLengths(lenvec);
+        tree->clearAllPartialLH();
+    }
+}
+
 void TreeSearch::checkEligible(const char *who) const {
     const PhyloTree &t = *tree;
     const std::string w = std::string(who) + ": ";
@@ -20,6 +55,16 @@ void TreeSearch::checkEligible(const char *who) const {
     if (t.leafNum < 4) throw std::runtime_error(w + "a tree search needs at least 4 taxa");
     for (const PhyloNode *n : t.nodes)
         if (!n->isLeaf() && n->degree() != 3) throw std::runtime_error(w + "the tree is multifurcating; a tree search needs a binary tree");
+    if (stree) {
+        if (!stree->group) throw std::runtime_error(w + "the super tree has no engines");
+        if (numInitTrees > 0) throw std::runtime_error(w + "the parsimony starting trees (numInitTrees > 0) are not available on a super tree");
+        for (const PhyloTree *m : stree->parts) {
+            if (m->ufboot_nsamples > 0) throw std::runtime_error(w + "UFBoot is not available on a super tree");
+            if (batched && m->lh_mem_save != LM_ALL_BRANCH)
+                throw std::runtime_error(w + "the batched NNI evaluation needs setAllBranchMode on the super tree");
+        }
+        return;
+    }
     if (!t.engine) throw std::runtime_error(w + "the tree has no engine");
     if (iqhip_comm_size(t.engine) > 1) throw std::runtime_error(w + "not available on sharded engines and communicator ranks");
     if (batched && t.lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error(w + "the batched NNI evaluation needs LM_ALL_BRANCH");
@@ -52,6 +97,21 @@ void TreeSearch::evaluate(const BranchList &branches, bool all, std::vector<NNIM
             n1.push_back(t.nodes[(size_t)std::min(br.first, br.second)]);
             n2.push_back(t.nodes[(size_t)std::max(br.first, br.second)]);
         }
+    moves.clear();
+    if (stree) {
+        if (batched) {
+            if (nni5) stree->evaluateNNIs5Batch(moves, all ? nullptr : &branches);
+            else stree->evaluateNNIsBatch(moves, all ? nullptr : &branches);
+        } else {
+            for (size_t q = 0; q < n1.size(); q++) {
+                NNIMove two[2];
+                stree->getBestNNIForBran(n1[q]->id, n2[q]->id, nni5, two);
+                moves.push_back(two[0]);
+                moves.push_back(two[1]);
+            }
+        }
+        return;
+    }
     const bool boot = t.ufboot_nsamples > 0;
     std::vector<int> rows;
     if (boot) {   // store row 0 is saveCurrentTree's, row 1 + k candidate k's
@@ -59,7 +119,6 @@ void TreeSearch::evaluate(const BranchList &branches, bool all, std::vector<NNIM
         for (size_t k = 0; k < rows.size(); k++) rows[k] = (int)(1 + k);
         if (iqhip_ptnlh_reserve(t.engine, (int)(1 + rows.size())) != 0) throw std::runtime_error(iqhip_last_error());
     }
-    moves.clear();
     if (batched) {
         if (nni5) t.evaluateNNIs5Batch(moves, boot ? rows.data() : nullptr, all ? nullptr : &branches);
         else t.evaluateNNIsBatch(moves, all ? nullptr : &branches);
@@ -134,14 +193,14 @@ double TreeSearch::optimizeNNI(int &nni_count, int &nni_steps, std::vector<NNISt
             NNIMove mv = nonConfNNIs[(size_t)i];
             mv.node1_nei = t.nodes[(size_t)mv.node1]->neighbors[slots[(size_t)i].first]->node->id;
             mv.node2_nei = t.nodes[(size_t)mv.node2]->neighbors[slots[(size_t)i].second]->node->id;
-            t.doNNI(mv);
+            doNNI(mv);
             appliedNNIs.push_back(mv);
-            t.changeNNIBrans(mv, nni5);
+            changeNNIBrans(mv);
         }
         t.current_it = t.current_it_back = nullptr;
         branches.clear();
         if (speednni) branches = iqsearch::branchesForNNI(appliedNNIs, t.adjacency());
-        t.curScore = t.optimizeAllBranches(1, loglh_epsilon, PhyloTree::NNI_MAX_NR_STEP);
+        t.curScore = sweep();
         st.applied = appliedNNIs;
         st.score = t.curScore;
         if (t.curScore >= nonConfNNIs[0].newloglh - loglh_epsilon) {
@@ -151,9 +210,8 @@ double TreeSearch::optimizeNNI(int &nni_count, int &nni_steps, std::vector<NNISt
             // restore the tree by reverting all NNIs -- last first, the order that also undoes adjacent moves; the reference
             // reverts first to last, which is the same for moves that do not touch -- then the lengths; every vector is
             // stale afterwards
-            for (size_t i = appliedNNIs.size(); i-- > 0;) t.doNNI(appliedNNIs[i]);
-            t.restoreBranchLengths(lenvec);
-            t.clearAllPartialLH();
+            for (size_t i = appliedNNIs.size(); i-- > 0;) doNNI(appliedNNIs[i]);
+            restore(lenvec);
             rollBack = true;
             numNNIs = 1;   // only apply the best NNI
             t.curScore = oldScore;
@@ -180,9 +238,11 @@ void TreeSearch::doRandomNNIs(int numNNI, uint64_t iteration, std::vector<std::a
         const int bit1 = (int)(iqsearch::searchRand(seed, iteration, d + 1) >> 63);
         const int bit2 = (int)(iqsearch::searchRand(seed, iteration, d + 2) >> 63);
         if (done) done->push_back({n1[(size_t)index]->id, n2[(size_t)index]->id, bit1, bit2});
-        t.doOneRandomNNI(n1[(size_t)index], n2[(size_t)index], bit1, bit2);
+        if (stree) stree->doOneRandomNNI(n1[(size_t)index]->id, n2[(size_t)index]->id, bit1, bit2);
+        else t.doOneRandomNNI(n1[(size_t)index], n2[(size_t)index], bit1, bit2);
     }
-    t.clearAllPartialLH();   // resetCurScore / setAlignment of the reference: nothing computed survives
+    if (stree) stree->clearAllPartialLH();
+    else t.clearAllPartialLH();   // resetCurScore / setAlignment of the reference: nothing computed survives
 }
 
 double TreeSearch::doTreeSearch() {
@@ -269,7 +329,7 @@ double TreeSearch::doTreeSearch() {
         // the starting tree is iteration 1: one optimizeNNI, then into the candidate set
         Iteration it;
         it.iteration = 1;
-        t.computeLikelihood();
+        computeLikelihood();
         it.perturb_score = t.curScore;
         optimizeNNI(nni_count, nni_steps, keep_trace ? &it.steps : nullptr);
         it.score = t.curScore;
@@ -294,15 +354,15 @@ double TreeSearch::doTreeSearch() {
         // perturb a random one of the best popSize trees
         const int numNNI = (int)floor(curPerStrength * (t.leafNum - 3));
         it.parent = (int)candidates.randCandRank(popSize, iqsearch::searchRand(seed, (uint64_t)cur, 0));
-        t.readTreeString(candidates.byRank((size_t)it.parent).tree, names);
+        readTree(candidates.byRank((size_t)it.parent).tree, names);
         doRandomNNIs(numNNI, (uint64_t)cur, &it.random_nnis);
-        t.computeLikelihood();
+        computeLikelihood();
         it.perturb_score = t.curScore;
         optimizeNNI(nni_count, nni_steps, keep_trace ? &it.steps : nullptr);
         it.nni_count = nni_count;
         // a better tree: the reference re-estimates the model here; the model is given, the lengths are optimised fully
         if (t.curScore > candidates.getBestScore() + modeps) {
-            t.curScore = t.optimizeAllBranches(100, loglh_epsilon);
+            t.curScore = stree ? stree->optimizeAllBranches(100, loglh_epsilon) : t.optimizeAllBranches(100, loglh_epsilon);
             if (!candidates.treeTopologyExist(t.sortedTaxonIdString())) {
                 stop_rule.addImprovedIteration(cur);
                 it.new_best = true;
@@ -323,8 +383,8 @@ double TreeSearch::doTreeSearch() {
         if (on_iteration) on_iteration(*this, it);
         if (keep_trace) trace.push_back(it);
     }
-    t.readTreeString(candidates.getTopTrees(1)[0], names);
-    t.computeLikelihood();
+    readTree(candidates.getTopTrees(1)[0], names);
+    computeLikelihood();
     return candidates.getBestScore();
 }
 

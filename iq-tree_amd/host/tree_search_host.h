@@ -34,6 +34,7 @@
 
 #include "phylo_host.h"
 #include "search_host.h"
+#include "supertree_host.h"
 
 namespace iqhost {
 
@@ -43,6 +44,11 @@ public:
     typedef iqsearch::BranchList BranchList;
 
     explicit TreeSearch(PhyloTree *tree);
+    // over the super tree of an edge-linked partition model: `tree` is its topology (super), every edit and evaluation goes
+    // to the super tree and all members (a candidate tree is re-read by every tree, PhyloSuperTree::readTreeString).
+    // optimizeNNI, doRandomNNIs and doTreeSearch; partition rates and models are taken as given inside the loop, as the
+    // model is on a plain tree
+    explicit TreeSearch(PhyloSuperTree *super_tree);
 
     // ---- parameters (the reference's defaults) ------------------------------------------------------------------------
     bool nni5 = true;             // params.nni5
@@ -110,12 +116,21 @@ public:
     // refuses multifurcating trees, fewer than 4 taxa, trees without an engine, sharded engines and communicator ranks,
     // `batched` without LM_ALL_BRANCH, UFBoot together with mixtures, +ASC or the batched nni1 evaluation (it keeps no
     // per-pattern rows), numInitTrees > 0 on engines the parsimony calls refuse (anything but 4, 20 or 64 states):
-    // throws std::runtime_error, the tree is not touched.  Every entry point calls it first
+    // throws std::runtime_error, the tree is not touched.  Every entry point calls it first.  On a super tree: multifurcations,
+    // fewer than 4 taxa, no engines, UFBoot on a member, numInitTrees > 0, `batched` without setAllBranchMode
     void checkEligible(const char *who) const;
 
     PhyloTree *tree;
+    PhyloSuperTree *stree = nullptr;
+    double computeLikelihood();   // of the tree or of the super tree; curScore follows
 
 private:
+    // the tree edits and the sweep of a step, on the tree or on the super tree and its members
+    void readTree(const std::string &newick, const std::vector<std::string> &names);
+    void doNNI(const NNIMove &mv);
+    void changeNNIBrans(const NNIMove &mv);
+    double sweep();
+    void restore(const std::vector<double> &lenvec);
     void evaluate(const BranchList &branches, bool all, std::vector<NNIMove> &moves);
     std::vector<std::string> leafNames() const;
 };
