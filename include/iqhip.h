@@ -909,6 +909,12 @@ int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
  *   21..27  the same for the first stage of units (zeros: the plan has none) */
 #define IQHIP_PLAN_SHAPE_NSLOTS 28
 int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n);
+/* Read-only: the LDS layout of the planner's last plan, out[k * IQHIP_PLAN_LAYOUT_NSLOTS + f] for op k < nops (the op
+ * count of that plan): ops of the chunk (first op of a chunk, else 0), leaf-state slots of the chunk with the dummy slot
+ * (first op, else 0), left / right child is a leaf, offsets of the two children's regions (doubles), leaf-state slots of
+ * the two children */
+#define IQHIP_PLAN_LAYOUT_NSLOTS 8
+int iqhip_debug_plan_layout(iqhip_engine *e, int32_t *out, int nops);
 
 /* Debugging aids, no reference counterpart: the library's memory accounting.  Every device and pinned-host allocation of
  * every engine and partition group in this process goes through one allocate / free pair, which counts bytes.

@@ -1438,3 +1438,16 @@ extern "C" int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n) {
     if (!p.stage_units.empty()) launch(out + 21, false, p.stage_units[0]);
     return IQHIP_OK;
 }
+
+// the LDS layout of the last plan, op by op (tests/test_fill_states_plan.py)
+extern "C" int iqhip_debug_plan_layout(iqhip_engine *e, int32_t *out, int nops) {
+    if (!e || !e->planner || !out || nops != e->plan.small_nops)
+        return fail(IQHIP_ERR_INVALID, "iqhip_debug_plan_layout needs a planning-only engine and the last plan's op count");
+    for (int k = 0; k < nops; k++) {
+        const DevOp &d = e->h_ops.p[k];
+        const int32_t v[IQHIP_PLAN_LAYOUT_NSLOTS] = {d.chunk_nops, d.chunk_slots, d.left_kind == CHILD_LEAF, d.right_kind == CHILD_LEAF,
+                                                     d.lds_left, d.lds_right, d.sl_slot, d.sr_slot};
+        std::copy(v, v + IQHIP_PLAN_LAYOUT_NSLOTS, out + (size_t)k * IQHIP_PLAN_LAYOUT_NSLOTS);
+    }
+    return IQHIP_OK;
+}

@@ -79,7 +79,8 @@ struct __attribute__((aligned(16))) DevOp {
     // states only -- cherry[(sL * (STATE_UNKNOWN + 1) + sR) * block + ...] holds it for every pair, in the order the lanes
     // keep it in registers (kernels_mfma.hip k_cherry_transpose); nullptr: compute the three matrix products
     const double *cherry;
-    const double *_pad_cherry;
+    int32_t chunk_slots;   // 4-state path, on the first op of an LDS chunk: leaf-state slots of the chunk, the dummy slot 0 included
+    int32_t _pad_slots;
 };
 
 #if defined(__HIPCC__)

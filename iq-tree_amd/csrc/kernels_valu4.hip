@@ -94,6 +94,7 @@ struct Trav4Args {
     int state_unknown;
     int has_root;
     int lds_reg_doubles;  // size of the per-branch region area (largest chunk)
+    int state_slots;      // leaf-state slots per wave behind it (largest chunk, the dummy slot 0 included)
     int nsegs_launch;     // host side only: segments of this launch, instantiation choice
     int has_load;
     FoldArgs fold;
@@ -256,6 +257,10 @@ __device__ __forceinline__ void store_vec4_off(double *base, uint32_t voff, cons
 // USE_HOLD = false: no HOLD register set (the plan then contains no CHILD_HOLD / push_hold): 2*BL fewer registers
 // -DIQHIP_T4_TRACE (timing study, tools/build_alt.sh t4trace -DIQHIP_T4_TRACE): a few waves split their op loop with the
 // shader clock -- chunk fill / op head / node update / op tail -- and every 100th launch prints the averages
+//
+// lds_barrier(): a workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for the wave's outstanding global requests;
+// the chunk fill keeps its state requests in flight across its barriers and waits for them once, at its end.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #ifdef IQHIP_T4_TRACE
 __device__ unsigned long long g_t4[8];
 #define T4_CLK() (t4_on ? (unsigned long long)clock64() : 0ull)
@@ -273,11 +278,14 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
     double *s_tip = smem + L.s_tip;   // [32][4]
     double *s_val = smem + L.s_val;   // [B]
     double *s_reg = smem + L.s_reg;   // per (op, child) regions of the current chunk
-    uint8_t *s_states = reinterpret_cast<uint8_t *>(s_reg + A.lds_reg_doubles);  // [slot][WG] leaf states
+    uint8_t *s_states = reinterpret_cast<uint8_t *>(s_reg + A.lds_reg_doubles);  // [wave][slot][64] leaf states (trav_lds.h)
 
     __shared__ double s_model[32];    // U [16], eigenvalues [4], rates [C <= 8]: the chunk fills read them many times
     __shared__ int s_opi[64][4];      // per op of a fill pass: LDS offsets of its two regions, is-leaf flags
     __shared__ double s_opl[64][2];   // ... child branch lengths
+    __shared__ const uint8_t *s_row[kTrav4RowSlots];   // state rows of the chunk's leaf children, by slot
+    // (The prologue's global reads issued together into registers, ahead of every LDS write, changed nothing measurable:
+    // profiles/r05/experiments.txt.)
     const int nst = A.state_unknown + 1;
     for (int t = threadIdx.x; t < nst * 4; t += WG) s_tip[t] = A.tip[t];
     for (int t = threadIdx.x; t < 20 + C; t += WG) s_model[t] = t < 16 ? A.evec[t] : (t < 20 ? A.eval[t - 16] : A.rates[t - 20]);
@@ -288,6 +296,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // make it provably uniform
+    uint8_t *const w_states = s_states + wave * (A.state_slots * 64);   // this wave's slots, [slot][64]
     const int seg = (int)blockIdx.x / A.ngroups;  // scalar
     // (a small plan is read out of the kernel-argument segment, which is constant memory like the plan buffer)
     const CONST_AS char *kargs = (const CONST_AS char *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -334,6 +343,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                                                    ((nreal & 1) ? soff : (uint32_t)(lane * 2)));
     }
 
+
 #ifdef IQHIP_T4_TRACE
     const bool t4_on = (blockIdx.x % 97) == 5 && threadIdx.x == 0;
     unsigned long long t4_fill = 0, t4_head = 0, t4_upd = 0, t4_tail = 0, t4_n = 0, t4_f1 = 0, t4_f2 = 0;
@@ -342,16 +352,75 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
     while (k < k_end) {
         // ---- fill the LDS regions of the chunk that starts at op k (host-chosen boundaries)
         const int kn = ops[k].chunk_nops;
+        const int nslots = ops[k].chunk_slots;   // the chunk's leaf children own slots 1 .. nslots - 1, in op order
         [[maybe_unused]] const unsigned long long c0 = T4_CLK();
         __syncthreads();  // the previous chunk's regions are no longer read
+        // the state row of every leaf child of the chunk, by slot: what the state requests below read instead of descriptors
+        for (int t = threadIdx.x; t < kn; t += WG) {
+            // (unconditionally: sl / sr of a non-leaf child point at a valid row and its slot 0 is never requested)
+            const CONST_AS DevOp &d = ops[k + t];
+            const int slot_l = d.sl_slot, slot_r = d.sr_slot;
+            const uint8_t *const row_l = d.sl, *const row_r = d.sr;
+            s_row[slot_l] = row_l;
+            s_row[slot_r] = row_r;
+        }
         // The fill reads every op's descriptor and the model once per table entry: from LDS copies (the descriptors' few
         // fields staged per pass of 64 ops, eigenvalues / rates / U at kernel start) instead of dependent reads from memory --
         // those cost 34 k of a wave's 254 k cycles per traversal at 66 k patterns (shader clock; the exponentials themselves
         // are about 9 k of that).
+        // The leaf state bytes of the whole chunk -> LDS, one lane per pattern (SP = 1).  They are read once per traversal (cold
+        // misses) and depend on nothing the fill computes, so they are requested first, as one burst behind the staging
+        // barrier, and waited for last, at the fill's closing barrier: the exponentials and tables run under the misses.
+        // A wave's 64 state bytes of a leaf child are 16 dwords; `global_load_lds_dword` moves a dword per lane straight
+        // into LDS (lane i's lands at base + 4 i: tools/lds_load_probe.hip), so one instruction fills four consecutive slots of
+        // the wave, lane group i >> 4 fetching slot base + (i >> 4) from its row in s_row.  The loop holds no descriptor
+        // read and no wait but the one for its batch of row pointers.
+        // (History of this step, a wave's cycles per traversal at 66 k patterns, shader clock: load / wait / LDS store per leaf
+        // child 87 k of 313 k; through registers, 32 bytes in flight, 22 k of 230 k; one request per leaf child behind its
+        // descriptor's three dependent scalar reads, issued after the tables: see profiles/r05/experiments.txt.)
+        auto request_states = [&]() {
+            if constexpr (SP == 1) {
+                if (active) {
+                    constexpr int RB = 4;   // requests whose row pointers are read together
+                    const int grp = lane >> 4;
+                    const int64_t roff = tl * 64 + 4 * (lane & 15);
+                    for (int s0 = 1; s0 < nslots; s0 += 4 * RB) {
+                        const uint8_t *row[RB];
+#pragma unroll
+                        for (int r = 0; r < RB; r++) {
+                            const int slot = s0 + 4 * r + grp;
+                            row[r] = s_row[slot < nslots ? slot : 0];
+                        }
+#pragma unroll
+                        for (int r = 0; r < RB; r++) {
+                            if (s0 + 4 * r + grp < nslots)   // (groups past the chunk's last slot request nothing)
+                                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(row[r] + roff),
+                                                                 (__attribute__((address_space(3))) void *)(w_states + (s0 + 4 * r) * 64), 4, 0, 0);
+                        }
+                    }
+                }
+            }
+        };
+        lds_barrier();
+        request_states();
+        // The op loop reads each op's descriptor through the scalar cache, one op at a time, every read a dependent round
+        // trip when it misses.  The waves of the workgroup touch the chunk's descriptors here, a few ops each and several
+        // reads in flight, so that the loop finds them cached.  (The per-child descriptor reads this fill used to make
+        // did that as a side effect; without them the op head went from 435 to 683 cycles at 100 k patterns and from 292
+        // to 1 078 at 200 taxa x 1 M, more than the fill had gained: profiles/r05/experiments.txt.)
+        {
+            int touched = 0;
+#pragma unroll 4
+            for (int o = wave; o < kn; o += WPB) {
+                const CONST_AS int *w = reinterpret_cast<const CONST_AS int *>(ops + (k + o));
+                touched ^= w[0] ^ w[16] ^ w[32] ^ w[sizeof(DevOp) / 4 - 1];
+            }
+            asm volatile("" ::"s"(touched));
+        }
         [[maybe_unused]] unsigned long long c0a = T4_CLK();
         for (int o0 = 0; o0 < kn; o0 += 64) {
             const int on = kn - o0 < 64 ? kn - o0 : 64;
-            if (o0 > 0) __syncthreads();
+            if (o0 > 0) lds_barrier();
             for (int t = threadIdx.x; t < on; t += WG) {
                 const CONST_AS DevOp &d = ops[k + o0 + t];
                 s_opi[t][0] = d.lds_left;
@@ -361,12 +430,12 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                 s_opl[t][0] = op_child_len(d, 0);
                 s_opl[t][1] = op_child_len(d, 1);
             }
-            __syncthreads();
+            lds_barrier();
             for (int t = threadIdx.x; t < on * 2 * B; t += WG) {  // phase 1: exponentials
                 const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
                 s_reg[s_opi[o][child] + e] = exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][child]));
             }
-            __syncthreads();
+            lds_barrier();
             c0a = T4_CLK();
             // phase 2: leaf tables (K2).  One item = one (op, child, category, x): the four rounded products E = U[x][.] * ex are
             // made once and serve the table's four state rows (A, C, G, T); the fifth row, STATE_UNKNOWN, is exactly 1.0
@@ -382,29 +451,11 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             }
         }
         [[maybe_unused]] const unsigned long long c0b = T4_CLK();
-        // phase 3: this thread's leaf state bytes of the whole chunk -> LDS.  They are read once per
-        // traversal (cold misses); issuing them as one burst pays the miss latency once per chunk
-        // instead of once per op and keeps the op loop's VMEM sequence short.
-        // (Unconditional requests, sixteen ops = thirty-two bytes in flight at a time: sl / sr of a non-leaf child point at a valid
-        // row and its slot 0 is never read.  The conditional form -- load, wait, LDS store, next child -- paid one cold miss
-        // per LEAF CHILD instead of per chunk: 87 k of a wave's 313 k cycles per traversal at 66 k patterns, measured with
-        // the shader clock.)
-        // One lane per pattern (SP = 1): the wave's 64 state bytes of a leaf child are 16 dwords, which `global_load_lds_dword`
-        // moves straight into LDS (lane i's dword lands at base + 4 i: tools/lds_load_probe.hip) -- no registers, every
-        // request of the chunk in flight at once, one wait.  (Through registers, 32 bytes in flight at a time, the staging
-        // was 22 k of a wave's 230 k cycles per traversal.)
+        // phase 3: the leaf state bytes are in LDS before the op loop starts.  SP = 1: the one wait for the requests issued
+        // above.  SP = 2 (a lane owns half a pattern's categories, 32 patterns per wave): through registers, sixteen ops =
+        // thirty-two bytes in flight at a time, unconditionally -- sl / sr of a non-leaf child point at a valid row and its
+        // slot 0 is never read.
         if constexpr (SP == 1) {
-            if (active && lane < 16) {
-                for (int o = 0; o < kn; o++) {
-                    const CONST_AS DevOp *d = ops + (k + o);
-                    if (d->left_kind == CHILD_LEAF)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(d->sl + tl * 64 + 4 * lane),
-                                                         (__attribute__((address_space(3))) void *)(s_states + d->sl_slot * WG + wave * 64), 4, 0, 0);
-                    if (d->right_kind == CHILD_LEAF)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(d->sr + tl * 64 + 4 * lane),
-                                                         (__attribute__((address_space(3))) void *)(s_states + d->sr_slot * WG + wave * 64), 4, 0, 0);
-                }
-            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else
         if (active) {
@@ -420,8 +471,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                 for (int j = 0; j < 16; j++) {
                     if (o0 + j < kn) {
                         const CONST_AS DevOp *d = ops + (k + o0 + j);
-                        s_states[d->sl_slot * WG + threadIdx.x] = vl[j];
-                        s_states[d->sr_slot * WG + threadIdx.x] = vr[j];
+                        w_states[d->sl_slot * 64 + lane] = vl[j];
+                        w_states[d->sr_slot * 64 + lane] = vr[j];
                     }
                 }
             }
@@ -443,8 +494,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             const int out_row = op->out_row, rule = op->no_scale, push_hold = op->push_hold;
             int sc = 0;
             // leaf states were staged into LDS when the chunk was filled
-            const int sL = s_states[op->sl_slot * WG + threadIdx.x];
-            const int sR = s_states[op->sr_slot * WG + threadIdx.x];
+            const int sL = w_states[op->sl_slot * 64 + lane];
+            const int sR = w_states[op->sr_slot * 64 + lane];
             if (!leafL) sc += holdL ? hold_sc : pf_sc;
             if (HAS_LOAD && op->right_kind == CHILD_LOAD) {
                 // both children come from memory: the left one was streamed into PF; the right
@@ -663,6 +714,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     A.state_unknown = e->state_unknown;
     A.has_root = root ? 1 : 0;
     A.lds_reg_doubles = e->plan.lds_doubles;
+    A.state_slots = e->plan.state_slots;
     if (root) A.root = *root; else A.root = DevBranch{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.0};
     A.small_plan = 0;
     A.small_segs[0] = A.small_segs[1] = 0;

@@ -446,8 +446,11 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         const int nleaf = (d.left_kind == CHILD_LEAF) + (d.right_kind == CHILD_LEAF);
         const int need = szl + szr + nleaf * slot_sz;
         if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
-        if ((used + need > budget || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
+        // (k_traverse4 keeps one row pointer per slot of the chunk in a fixed array)
+        const bool rows_full = !e->mfma && slots + nleaf > kTrav4RowSlots;
+        if ((used + need > budget || rows_full || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
             e->h_ops.p[chunk_start].chunk_nops = k - chunk_start;
+            e->h_ops.p[chunk_start].chunk_slots = slots;
             chunk_start = k; used = slot_sz; regs = 0; slots = 1;
         }
         d.lds_left = regs; d.lds_right = regs + szl;
@@ -458,7 +461,10 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         d.sr_slot = d.right_kind == CHILD_LEAF ? slots++ : 0;
         if (slots > max_slots) max_slots = slots;
     }
-    if (nops > 0) e->h_ops.p[chunk_start].chunk_nops = nops - chunk_start;
+    if (nops > 0) {
+        e->h_ops.p[chunk_start].chunk_nops = nops - chunk_start;
+        e->h_ops.p[chunk_start].chunk_slots = slots;
+    }
     e->plan.state_slots = max_slots;
     e->plan.lds_doubles = max_used;
     return IQHIP_OK;
@@ -539,8 +545,29 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
     }
     // chunks tile the plan; the segment table stays inside it
     for (int k = 0; k < nops;) {
-        if (e->h_ops.p[k].chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
-        k += e->h_ops.p[k].chunk_nops;
+        const DevOp &c = e->h_ops.p[k];
+        if (c.chunk_nops <= 0) return bad(k, "op is not covered by an LDS chunk");
+        if (!e->mfma) {
+            // k_traverse4 requests the state rows of slots 1 .. chunk_slots - 1, four per instruction, from the row pointers
+            // the fill stages per slot: the chunk's leaf children own those slots in op order, none twice and none missing,
+            // the list fits the kernel's array, and regions plus state bytes fit what the launch allocates
+            int next = 1, regs = 0;
+            for (int q = k; q < k + c.chunk_nops; q++) {
+                const DevOp &d = e->h_ops.p[q];
+                if (d.sl_slot != (d.left_kind == CHILD_LEAF ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
+                next += d.left_kind == CHILD_LEAF;
+                if (d.sr_slot != (d.right_kind == CHILD_LEAF ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
+                next += d.right_kind == CHILD_LEAF;
+                const int szl = (d.left_kind == CHILD_LEAF ? 6 : 1) * e->block, szr = (d.right_kind == CHILD_LEAF ? 6 : 1) * e->block;
+                regs = std::max(regs, std::max(d.lds_left + szl, d.lds_right + szr));
+            }
+            if (c.chunk_slots != next) return bad(k, "chunk_slots is not the chunk's slot count");
+            if (next > kTrav4RowSlots) return bad(k, "more leaf-state slots than the kernel's row-pointer list holds");
+            if (next > e->plan.state_slots || regs > e->plan.lds_doubles ||
+                regs + next * trav4_lds(e->block, e->wg_size).slot_doubles > lds_budget(e))
+                return bad(k, "LDS chunk outside the launch's allocation or over the budget");
+        }
+        k += c.chunk_nops;
     }
     const int *tab = reinterpret_cast<const int *>(e->h_ops.p + e->plan.table_off);
     int covered = 0;

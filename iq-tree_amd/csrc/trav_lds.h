@@ -11,7 +11,7 @@ namespace iqhip {
 constexpr int kTravWg = 256;                        // threads per workgroup of every matrix-core traversal kernel
 constexpr int kTravMaxLdsBytes = 150 * 1024;        // dynamic LDS every matrix-core traversal kernel is allowed ...
 constexpr int kTravGenericMaxLdsBytes = 160 * 1024; // ... and k_traverse_mfma, which has no static arrays
-constexpr int kTrav4MaxLdsBytes = 152 * 1024;       // k_traverse4: 160 KB minus the static arrays (fold_tail, the fill's descriptor copies)
+constexpr int kTrav4MaxLdsBytes = 152 * 1024;       // k_traverse4: 160 KB minus the static arrays (fold_tail 3.1 KB, the fill's descriptor copies 2.3 KB and row pointers 2 KB)
 
 __host__ __device__ constexpr int tipx_doubles(int n, int nx) { return nx * n; }   // the [nx][n] tip vectors of the states beyond n
 
@@ -60,7 +60,13 @@ __host__ __device__ constexpr Wide4Lds wide4_lds(int nclass, int block) { return
 constexpr int kWide4LdsKb = 40;   // per workgroup, fixed part included: four workgroups (16 waves) per CU
 
 // k_traverse4: tip vectors [32][4], one block of values, the plan regions, then the leaf-state slots -- one byte per
-// thread each, i.e. wg / 8 doubles; slot 0 is shared by all non-leaf children
+// thread each, i.e. wg / 8 doubles; slot 0 is shared by all non-leaf children.  The state bytes lie [wave][slot][64]
+// (slot < Plan::state_slots): a wave's slots are contiguous, so one LDS-direct dword load fills four of them, each group
+// of 16 lanes fetching the 64 bytes of one leaf child (kernels_valu4.hip, the chunk fill's state requests).
+// The row pointers those requests read, s_row[slot], are a static array of kTrav4RowSlots pointers inside the kernel,
+// not part of the dynamic LDS: budget, chunk cuts and launch bytes of a plan do not depend on it.  lay_out_lds ends a
+// chunk before its slots would outgrow the array and check_plan holds every chunk to it.
+constexpr int kTrav4RowSlots = 256;
 struct Trav4Lds { int s_tip, s_val, s_reg, slot_doubles; };
 __host__ __device__ constexpr Trav4Lds trav4_lds(int block, int wg) { return {0, 128, 128 + block, wg / 8}; }
 __host__ __device__ constexpr size_t trav4_lds_bytes(int block, int wg, int lds_doubles, int state_slots) {
