@@ -57,17 +57,14 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     e->wide4_generic = e->wide4;
     if (const char *w = getenv("IQHIP_WIDE4")) e->wide4_generic = e->wide4 && strcmp(w, "valu") != 0;   // (check_shape4 has refused every other word)
     e->mfma = nstates != 4 || e->wide4;
-    e->mfma_pipelined_ok = ((nstates == 20 && (ncat == 4 || ncat == 1)) || (nstates == 64 && ncat == 1)) &&
-                           !getenv("IQHIP_MFMA_V1");
+    e->mfma_pipelined_ok = (nstates == 20 && (ncat == 4 || ncat == 1)) || (nstates == 64 && ncat == 1);
     e->mfma_pipelined = e->mfma_pipelined_ok;
     e->tile = e->mfma ? 16 : 64;
     e->block = nstates * ncat;
     e->nptn_pad = round_up(nptn, 64);
     e->ntiles = e->nptn_pad / e->tile;
 
-    if (const char *ab = getenv("IQHIP_ABLATE")) e->ablate = atoi(ab);
     if (const char *cp = getenv("IQHIP_CHECK_PLAN")) e->check_plans = atoi(cp) != 0;
-    if (const char *h = getenv("IQHIP_HOLD")) e->use_hold = atoi(h) != 0;
     if (const char *h = getenv("IQHIP_HOLD_LDS")) e->hold_lds = atoi(h) != 0;
     if (const char *h = getenv("IQHIP_NEWTON_POSTS")) e->newton_posts = atoi(h) != 0;
     if (const char *h = getenv("IQHIP_SMALL_PLANS")) e->small_plans = atoi(h) != 0;
@@ -93,10 +90,6 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
     // change would cost a table rebuild per evaluation.  IQHIP_LEAF_TABLES=0|1 overrides (tests run both).
     e->leaf_tables = e->mfma_pipelined_ok && nstates == 64;
     if (const char *lt = getenv("IQHIP_LEAF_TABLES")) e->leaf_tables = e->mfma_pipelined_ok && atoi(lt) != 0;
-    if (const char *wg = getenv("IQHIP_WG")) {
-        int v = atoi(wg);
-        if (v == 64 || v == 128 || v == 256) e->wg_size = v;
-    }
 
     // 4-state kernel, two lanes per pattern: twice the waves with half the register state each, as long as
     // they all fit the chip at once (2 waves per SIMD).  Measured, GTR+G4 50 taxa: 10k..65k patterns 0.116..
@@ -116,7 +109,6 @@ static void configure_engine(iqhip_engine *e, int device, int nstates, int nstat
         if (const char *cs = getenv("IQHIP_TOP_CS2")) e->top_cs2 = atoi(cs) != 0;
     }
     if (e->n == 20) {
-        e->mix_generic = getenv("IQHIP_MIX_GENERIC") != nullptr;
         // the mixture kernel's component split while the alignment is small (at most 3/4 tile per SIMD: 10k patterns x 40
         // components 1.96 -> 1.77 ms, but 30k patterns x 8 components 1.78 -> 2.62 ms) and the components divide by 4
         e->mix_split = 4 * e->ntiles <= 3 * (int64_t)e->num_cus * 4;
@@ -529,7 +521,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
         // pipelined instantiation also run on the mixture kernel: one class; wide DNA reads the generic images, one class too)
         // MFMA A-operand images of every class for k_traverse_mfma_mix20: [class][U16 | U4 | Ui16 | Ui4][s][lane]
         // (16-row tile: row = lane & 15; 4-row tail: row = 16 + (lane & 3); k = 4s + (lane >> 4)), followed by
-        // the padded two-tile images [class][U | U^-1][m][s][lane] of the generic kernel (IQHIP_MIX_GENERIC)
+        // the padded two-tile images [class][U | U^-1][m][s][lane] of the generic kernel (64-state mixtures, wide DNA)
         const int MT = (n + 15) / 16, KS = n / 4;
         const size_t mix_doubles = (size_t)nclass * 4 * KS * 64;  // (only read by the 20-state kernel)
         std::vector<double> img(mix_doubles + (size_t)nclass * 2 * MT * KS * 64, 0.0);
@@ -587,7 +579,7 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
 // cherry tables (DevOp::cherry): which engines use them, and their pair engine
 // ---------------------------------------------------------------------------------------
 bool iqhip::cherry_candidate(const iqhip_engine *e) {
-    if (!e || !e->cherry_on || !e->shards.empty() || e->ablate) return false;   // (a planning-only engine plans them too)
+    if (!e || !e->cherry_on || !e->shards.empty()) return false;   // (a planning-only engine plans them too)
     if (!e->mfma_pipelined_ok || e->n_user != e->n) return false;
     if (e->n == 20) return e->ncat == 4 && !e->leaf_tables && !e->cat_split && e->nptn_pad >= 8 * 1024;
     return false;
@@ -822,7 +814,7 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
     const bool empty_top = e->plan.nunits > 0 && !has_root && e->plan.top_nops == 0;  // explicit segments only
     // the submission's last kernel sums the wave partials itself (FoldArgs) where it can: the 4-state traversal
     // (its top-stage launch) and the matrix-core path's root-branch kernel; otherwise a k_reduce launch follows
-    const bool fold4 = e->fold_reduce && !e->mfma && !empty_top && !skip_reduce && e->wg_size == 256;
+    const bool fold4 = e->fold_reduce && !e->mfma && !empty_top && !skip_reduce;
     const bool foldm = e->fold_reduce && e->mfma && has_root && e->n_unobs == 0;
     if (empty_top) {
     } else if (e->mfma) HIPCHK(launch_traverse_mfma(e, table, nops > 0 ? 1 : 0, nwaves, /*top_stage=*/true));
@@ -1429,7 +1421,7 @@ extern "C" int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n) {
             L.variant = (TravVariant)-1;
             L.ngroups = trav4_ngroups(e);
             L.grid = L.ngroups * nsegs;
-            L.lds_bytes = trav4_lds_bytes(e->block, e->wg_size, p.lds_doubles, p.state_slots);
+            L.lds_bytes = trav4_lds_bytes(e->block, p.lds_doubles, p.state_slots);
         }
         const int64_t v[7] = {L.variant, L.tab, L.nfull, L.ngroups, L.grid, (int64_t)L.lds_bytes, L.hold_off};
         std::copy(v, v + 7, o);

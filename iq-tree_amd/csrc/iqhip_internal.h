@@ -437,8 +437,7 @@ struct iqhip_engine {
     int64_t ntiles = 0;    // tiles of `tile` patterns
     int tile = 64;         // 64 (VALU path) or 16 (MFMA path)
     bool mfma = false;     // nstates 20 / 64: matrix-core path (kernels_mfma.hip)
-    bool mfma_pipelined = false;  // (n, ncat) has a k_traverse_mfma2 instantiation (IQHIP_MFMA_V1=1 disables)
-    int wg_size = 256;     // threads per workgroup of the traversal kernel (IQHIP_WG env)
+    bool mfma_pipelined = false;  // (n, ncat) has a k_traverse_mfma2 instantiation and the model has one class
     bool row_split = false; // 64 states, 1 category: one wave per 16 output rows of a tile (small alignments)
     bool cat_split = false; // 20 states, 4 categories: one wave per category of a tile (small alignments)
     bool top_cs2 = false;   // 20 states, 4 categories: the sequential top stage with two waves per tile (two categories each), IQHIP_TOP_CS2
@@ -449,14 +448,12 @@ struct iqhip_engine {
     // the default) or, with IQHIP_WIDE4=valu, k_traverse4w (kernels_valu4w.hip) on the same plans
     bool wide4 = false, wide4_generic = false;
     int lane_split_valu = 1;  // ... remembered while a 4-state engine runs a mixture on the matrix-core kernels
-    bool mix_generic = false; // 20-state mixtures and unpipelined category counts on the generic kernel instead of k_traverse_mfma_mix20 (IQHIP_MIX_GENERIC)
     bool mix_split = false;   // k_traverse_mfma_mix20: one wave per quarter of a tile's components (small alignments; IQHIP_CAT_SPLIT)
     bool mixed_top = true; // 64 states: mixed-role top stage (kernels_mfma.hip k_traverse_mfma_top64; IQHIP_MIXED_TOP)
-    bool use_hold = true;  // 4-state traversal: park join operands in a second register set (IQHIP_HOLD)
+    // The 4-state traversal parks join operands in a second register set (HOLD, plan.hip park_operands).
     // 20-state pipelined kernel: the same idea with the parking place in LDS (10 KB per wave) -- a result that is the
     // streamed child of a later op of the same unit is kept there instead of being read back from memory (IQHIP_HOLD_LDS)
     bool hold_lds = true;
-    int ablate = 0;        // IQHIP_ABLATE: timing-only host-side switches (results wrong when set)
     int lds_budget_bytes = 64 * 1024;  // per-workgroup LDS for the per-branch regions (IQHIP_LDS_KB)
     bool small_plans = true;     // IQHIP_SMALL_PLANS (iqhip::Plan::small)
     int split_target = -1;       // IQHIP_SPLIT: -1 auto, 0 never, n > 0: unit size (plan.hip cut_units)
@@ -992,7 +989,7 @@ int lds_budget(const iqhip_engine *e);   // doubles of LDS one chunk's per-(op, 
 // the planner and a planning-only engine ask the same function the launcher does.
 enum TravVariant : int {
     TRAV_NONE = 0,           // no kernel for this shape
-    TRAV_GENERIC,            // k_traverse_mfma<n, 256, nclass > 1>; 4-state mixtures: <4, 256, true>
+    TRAV_GENERIC,            // k_traverse_mfma<64, 256, nclass > 1>; 4-state mixtures and wide DNA: <4, 256, true>
     TRAV_MIX20,              // k_traverse_mfma_mix20<256, 1>
     TRAV_MIX20_SPLIT,        // k_traverse_mfma_mix20<256, 4>
     TRAV_M2,                 // k_traverse_mfma2<n, ncat, 256, 1, tab>
@@ -1020,7 +1017,7 @@ inline bool top_stage_may_share_tiles(const iqhip_engine *e) { return e->top_cs2
 inline bool top_stage_may_mix_roles64(const iqhip_engine *e) { return e->n == 64 && e->mixed_top; }
 // workgroups per segment of k_traverse4: one wave per tile and lane split
 inline int trav4_ngroups(const iqhip_engine *e) {
-    const int wpb = e->wg_size / 64;
+    const int wpb = kTravWg / 64;
     return (int)((e->ntiles * e->lane_split + wpb - 1) / wpb);
 }
 // the engine's kernel reads a small plan out of its arguments (Plan::small): k_traverse4 and the 20-state pipelined

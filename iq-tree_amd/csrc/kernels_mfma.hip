@@ -1386,8 +1386,6 @@ static hipError_t launch_variant(iqhip_engine *e, const TravLaunch &L, const Tra
             case TRAV_MIX20_SPLIT: return launch_trav<k_traverse_mfma_mix20<kTravWg, 4>>(e, L, A);
             case TRAV_GENERIC:
                 if (n == 4) return launch_trav<k_traverse_mfma<4, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A);
-                if (n == 20) return mix ? launch_trav<k_traverse_mfma<20, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A)
-                                        : launch_trav<k_traverse_mfma<20, kTravWg, false>, kTravGenericMaxLdsBytes>(e, L, A);
                 return mix ? launch_trav<k_traverse_mfma<64, kTravWg, true>, kTravGenericMaxLdsBytes>(e, L, A)
                            : launch_trav<k_traverse_mfma<64, kTravWg, false>, kTravGenericMaxLdsBytes>(e, L, A);
             default: break;

@@ -141,13 +141,13 @@ __device__ __forceinline__ void leaf_cat4(const double *reg /* [ex B][table 5B] 
 // op k+1's streamed child (nx_pf), so the prefetch needs no second register set and no copy.
 // Returns lh_max (0 for LEAF-LEAF, which the reference never rescales).
 // With SP = 2 lanes per pattern a lane owns C = CF/2 of the block's CF categories, starting at `coff`.
-template <int C, int CF, bool USE_HOLD>
+template <int C, int CF>
 __device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leafR, const double *regL,
                                                const double *regR, const double *s_tip,
                                                const CONST_AS double *U, const CONST_AS double *uinv,
                                                int sL, int sR, int state_unknown, const char *nx_pf,
                                                char *dst, int coff, double (&PF)[4 * C],
-                                               const double (&HOLD)[USE_HOLD ? 4 * C : 1], double (&prev)[4 * C]) {
+                                               const double (&HOLD)[4 * C], double (&prev)[4 * C]) {
     bool slowL = false, slowR = false;
     int rowL = 0, rowR = 0;
     if (leafL) {
@@ -166,9 +166,9 @@ __device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leaf
             leaf_cat4<CF>(regL, s_tip, U, sL, rowL, slowL, state_unknown, coff + c, a);
         } else {
             double l[4];
-            if (USE_HOLD && holdL) {
+            if (holdL) {
 #pragma unroll
-                for (int i = 0; i < 4; i++) l[i] = regL[(coff + c) * 4 + i] * HOLD[USE_HOLD ? c * 4 + i : 0];
+                for (int i = 0; i < 4; i++) l[i] = regL[(coff + c) * 4 + i] * HOLD[c * 4 + i];
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; i++) l[i] = regL[(coff + c) * 4 + i] * PF[c * 4 + i];
@@ -254,7 +254,6 @@ __device__ __forceinline__ void store_vec4_off(double *base, uint32_t voff, cons
 // categories, so a small alignment yields twice as many waves with half the register state each (the
 // 4-state kernel is latency / occupancy limited below ~4 waves per SIMD).  The memory layout is
 // unchanged: the lane's categories are rows [2*coff, 2*coff + 2*CL) of the tile.
-// USE_HOLD = false: no HOLD register set (the plan then contains no CHILD_HOLD / push_hold): 2*BL fewer registers
 // -DIQHIP_T4_TRACE (timing study, tools/build_alt.sh t4trace -DIQHIP_T4_TRACE): a few waves split their op loop with the
 // shader clock -- chunk fill / op head / node update / op tail -- and every 100th launch prints the averages
 //
@@ -267,14 +266,14 @@ __device__ unsigned long long g_t4[8];
 #else
 #define T4_CLK() 0ull
 #endif
-template <int C, int WG, bool HAS_LOAD, int SP, bool USE_HOLD = true>
-__global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
+template <int C, bool HAS_LOAD, int SP>
+__global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
     static_assert(SP == 1 || (SP == 2 && C % 2 == 0), "SP = 2 needs an even category count");
     constexpr int B = 4 * C;
     constexpr int CL = C / SP, BL = 4 * CL;  // categories / doubles per lane
-    constexpr int WPB = WG / 64;  // waves per block (64 patterns each, 32 with SP = 2)
+    constexpr int WPB = kTravWg / 64;  // waves per block (64 patterns each, 32 with SP = 2)
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr Trav4Lds L = trav4_lds(B, WG);
+    constexpr Trav4Lds L = trav4_lds(B);
     double *s_tip = smem + L.s_tip;   // [32][4]
     double *s_val = smem + L.s_val;   // [B]
     double *s_reg = smem + L.s_reg;   // per (op, child) regions of the current chunk
@@ -287,8 +286,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
     // (The prologue's global reads issued together into registers, ahead of every LDS write, changed nothing measurable:
     // profiles/r05/experiments.txt.)
     const int nst = A.state_unknown + 1;
-    for (int t = threadIdx.x; t < nst * 4; t += WG) s_tip[t] = A.tip[t];
-    for (int t = threadIdx.x; t < 20 + C; t += WG) s_model[t] = t < 16 ? A.evec[t] : (t < 20 ? A.eval[t - 16] : A.rates[t - 20]);
+    for (int t = threadIdx.x; t < nst * 4; t += kTravWg) s_tip[t] = A.tip[t];
+    for (int t = threadIdx.x; t < 20 + C; t += kTravWg) s_model[t] = t < 16 ? A.evec[t] : (t < 20 ? A.eval[t - 16] : A.rates[t - 20]);
     if (A.has_root && threadIdx.x < B) {
         const int c = threadIdx.x >> 2, i = threadIdx.x & 3;
         s_val[threadIdx.x] = exp(A.eval[i] * (A.rates[c] * A.root.len)) * A.props[c];
@@ -325,13 +324,13 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
     const CONST_AS double *uinv = as_const(A.inv_evec);
     const CONST_AS DevOp *ops = A.small_plan ? (const CONST_AS DevOp *)(kargs + offsetof(Trav4Args, small_ops)) : as_const(A.ops);
 
-    double prev[BL], PF[BL], HOLD[USE_HOLD ? BL : 1];
+    double prev[BL], PF[BL], HOLD[BL];
     int hold_sc = 0;
     int pf_sc = 0, prev_sc = 0;
 #pragma unroll
     for (int e = 0; e < BL; e++) { prev[e] = 0.0; PF[e] = 0.0; }
 #pragma unroll
-    for (int e = 0; e < (USE_HOLD ? BL : 1); e++) HOLD[e] = 0.0;
+    for (int e = 0; e < BL; e++) HOLD[e] = 0.0;
 
     // everything op k needs from memory is requested while op k-1 computes.  Prime for op 0.
     // (ops[nops] is a sentinel whose pointers are valid dummies, so the requests are unconditional)
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
         [[maybe_unused]] const unsigned long long c0 = T4_CLK();
         __syncthreads();  // the previous chunk's regions are no longer read
         // the state row of every leaf child of the chunk, by slot: what the state requests below read instead of descriptors
-        for (int t = threadIdx.x; t < kn; t += WG) {
+        for (int t = threadIdx.x; t < kn; t += kTravWg) {
             // (unconditionally: sl / sr of a non-leaf child point at a valid row and its slot 0 is never requested)
             const CONST_AS DevOp &d = ops[k + t];
             const int slot_l = d.sl_slot, slot_r = d.sr_slot;
@@ -421,7 +420,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
         for (int o0 = 0; o0 < kn; o0 += 64) {
             const int on = kn - o0 < 64 ? kn - o0 : 64;
             if (o0 > 0) lds_barrier();
-            for (int t = threadIdx.x; t < on; t += WG) {
+            for (int t = threadIdx.x; t < on; t += kTravWg) {
                 const CONST_AS DevOp &d = ops[k + o0 + t];
                 s_opi[t][0] = d.lds_left;
                 s_opi[t][1] = d.lds_right;
@@ -431,7 +430,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                 s_opl[t][1] = op_child_len(d, 1);
             }
             lds_barrier();
-            for (int t = threadIdx.x; t < on * 2 * B; t += WG) {  // phase 1: exponentials
+            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {  // phase 1: exponentials
                 const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
                 s_reg[s_opi[o][child] + e] = exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][child]));
             }
@@ -440,7 +439,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             // phase 2: leaf tables (K2).  One item = one (op, child, category, x): the four rounded products E = U[x][.] * ex are
             // made once and serve the table's four state rows (A, C, G, T); the fifth row, STATE_UNKNOWN, is exactly 1.0
             // (phylokernel.h:228-232).  (Entry by entry -- every entry remaking its E -- this phase was 14.6 k of a wave's cycles.)
-            for (int t = threadIdx.x; t < on * 2 * B; t += WG) {
+            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {
                 const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B, c = e >> 2, x = e & 3;
                 if (!s_opi[o][2 + child]) continue;
                 double *reg = s_reg + s_opi[o][child];
@@ -487,7 +486,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             [[maybe_unused]] const unsigned long long c1 = T4_CLK();
             const CONST_AS DevOp *op = ops + k;
             const bool leafL = op->left_kind == CHILD_LEAF;
-            const bool holdL = USE_HOLD && op->left_kind == CHILD_HOLD;
+            const bool holdL = op->left_kind == CHILD_HOLD;
             const bool leafR = op->right_kind == CHILD_LEAF;
             // (descriptor fields that only the op's tail needs: requested now, or the tail begins with their round trip)
             int16_t *const dst_sc_p = op->dst_sc;
@@ -513,8 +512,8 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             if (nreal & 1) pf_sc = *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(nx->pf_sc) + soff);
             char *dstp = reinterpret_cast<char *>(op->dst) + voff;
             [[maybe_unused]] const unsigned long long c2 = T4_CLK();
-            double lh_max = node_update4<CL, C, USE_HOLD>(leafL, holdL, leafR, s_reg + op->lds_left, s_reg + op->lds_right,
-                                                          s_tip, U, uinv, sL, sR, A.state_unknown, nx_pf, dstp, coff, PF, HOLD, prev);
+            double lh_max = node_update4<CL, C>(leafL, holdL, leafR, s_reg + op->lds_left, s_reg + op->lds_right,
+                                                s_tip, U, uinv, sL, sR, A.state_unknown, nx_pf, dstp, coff, PF, HOLD, prev);
             if (SP == 2) lh_max = fmax(lh_max, __shfl_xor(lh_max, 32, 64));  // both category halves of the pattern
             [[maybe_unused]] const unsigned long long c3 = T4_CLK() + (lh_max == -1.0 ? 1 : 0);   // (after the update's results exist)
             // ---- scaling: the decision is trav_phases.h's, the rewrite of the registers and the fold_store form this kernel's
@@ -538,7 +537,7 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
                 }
             }
             prev_sc = sc;
-            if (USE_HOLD && push_hold) {
+            if (push_hold) {
                 // this result is the left child of a join a few ops ahead whose other subtree is a
                 // plain chain: park it in registers instead of re-reading 8 KiB per wave from memory
 #pragma unroll
@@ -618,46 +617,24 @@ __global__ __launch_bounds__(WG, 2) void k_traverse4(const Trav4Args A) {
             fold_store(&A.slab[(size_t)A.nwaves + gw], wpc);
         }
     }
-    if constexpr (WG == 256) {
-        if (A.fold.enabled) fold_tail(A.fold);
-    }
+    if (A.fold.enabled) fold_tail(A.fold);
 }
 
-template <int C, int WG, bool HAS_LOAD, int SP, bool USE_HOLD>
-static hipError_t launch_trav_h(iqhip_engine *e, Trav4Args &A) {
-    constexpr int B = 4 * C;
-    const size_t lds = trav4_lds_bytes(B, WG, e->plan.lds_doubles, e->plan.state_slots);
-    (void)raise_lds_ceiling<&k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>>(e, kTrav4MaxLdsBytes);
+template <int C, bool HAS_LOAD, int SP>
+static hipError_t launch_trav(iqhip_engine *e, Trav4Args &A) {
+    const size_t lds = trav4_lds_bytes(4 * C, e->plan.lds_doubles, e->plan.state_slots);
+    (void)raise_lds_ceiling<&k_traverse4<C, HAS_LOAD, SP>>(e, kTrav4MaxLdsBytes);
     A.ngroups = trav4_ngroups(e);
-    hipLaunchKernelGGL((k_traverse4<C, WG, HAS_LOAD, SP, USE_HOLD>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(WG), lds, e->stream, A);
+    hipLaunchKernelGGL((k_traverse4<C, HAS_LOAD, SP>), dim3((unsigned)(A.ngroups * A.nsegs_launch)), dim3(kTravWg), lds, e->stream, A);
     return hipGetLastError();
 }
 
-template <int C, int WG, bool HAS_LOAD, int SP>
-static hipError_t launch_trav_l(iqhip_engine *e, Trav4Args &A) {
-    // (only the default workgroup size is instantiated both ways)
-    if constexpr (WG == 256 && SP == 1) {
-        if (!e->use_hold) return launch_trav_h<C, WG, HAS_LOAD, SP, false>(e, A);
-    }
-    return launch_trav_h<C, WG, HAS_LOAD, SP, true>(e, A);
-}
-
-template <int C, int WG>
+template <int C>
 static hipError_t launch_trav_c(iqhip_engine *e, Trav4Args &A) {
     if constexpr (C % 2 == 0) {
-        if (e->lane_split == 2)
-            return A.has_load ? launch_trav_l<C, WG, true, 2>(e, A) : launch_trav_l<C, WG, false, 2>(e, A);
+        if (e->lane_split == 2) return A.has_load ? launch_trav<C, true, 2>(e, A) : launch_trav<C, false, 2>(e, A);
     }
-    return A.has_load ? launch_trav_l<C, WG, true, 1>(e, A) : launch_trav_l<C, WG, false, 1>(e, A);
-}
-
-template <int C>
-static hipError_t launch_trav_wg(iqhip_engine *e, Trav4Args &A) {
-    switch (e->wg_size) {
-        case 64: return launch_trav_c<C, 64>(e, A);
-        case 128: return launch_trav_c<C, 128>(e, A);
-        default: return launch_trav_c<C, 256>(e, A);
-    }
+    return A.has_load ? launch_trav<C, true, 1>(e, A) : launch_trav<C, false, 1>(e, A);
 }
 
 hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bool has_load, const DevBranch *root, int nwaves,
@@ -684,7 +661,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     A.fold.nwaves = nwaves;
     A.fold.nrows_scale = fold_rows > 0 ? fold_rows : 0;
     A.fold.root_rows = root ? (e->n_unobs > 0 ? 2 : 1) : 0;
-    A.fold.enabled = (fold_rows >= 0 && e->wg_size == 256) ? 1 : 0;
+    A.fold.enabled = fold_rows >= 0 ? 1 : 0;
     A.fold.done = nullptr;
     A.fold.seq = 0;
     if (A.fold.enabled && e->poll_result && e->d_result == e->d_result_own) {   // mapped host memory: the host may poll
@@ -726,14 +703,14 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
         for (int q = 0; q < kSmallPlanOps; q++) A.small_ops[q] = DevOp{};
     }
     switch (e->ncat) {
-        case 1: return launch_trav_wg<1>(e, A);
-        case 2: return launch_trav_wg<2>(e, A);
-        case 3: return launch_trav_wg<3>(e, A);
-        case 4: return launch_trav_wg<4>(e, A);
-        case 5: return launch_trav_wg<5>(e, A);
-        case 6: return launch_trav_wg<6>(e, A);
-        case 7: return launch_trav_wg<7>(e, A);
-        case 8: return launch_trav_wg<8>(e, A);
+        case 1: return launch_trav_c<1>(e, A);
+        case 2: return launch_trav_c<2>(e, A);
+        case 3: return launch_trav_c<3>(e, A);
+        case 4: return launch_trav_c<4>(e, A);
+        case 5: return launch_trav_c<5>(e, A);
+        case 6: return launch_trav_c<6>(e, A);
+        case 7: return launch_trav_c<7>(e, A);
+        case 8: return launch_trav_c<8>(e, A);
         default: return hipErrorInvalidValue;
     }
 }

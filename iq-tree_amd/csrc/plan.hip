@@ -270,7 +270,6 @@ int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const 
             if (rkind == CHILD_LOAD) { d.ld = rp; d.ld_sc = rsc; }
             if (lkind == CHILD_LEAF) d.sl = lst;
             if (rkind == CHILD_LEAF) d.sr = rst;
-            if (e->ablate & 1) d.real_mask &= ~1;  // timing-only: never stream a child (results wrong)
         }
         d.left_kind = lkind; d.right_kind = rkind;
         d.left_len = llen; d.right_len = rlen;
@@ -286,7 +285,7 @@ int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const 
 // other subtree is a short chain).  20 states, one wave per tile: the parking place is LDS; the launch reserves it when
 // plan.nhold > 0.
 void park_operands(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
-    const bool hold_regs = !e->mfma && !(e->ablate & 4) && (e->use_hold || e->lane_split != 1 || e->wg_size != 256);
+    const bool hold_regs = !e->mfma;
     const bool hold_in_lds = e->mfma && e->mfma_pipelined && e->hold_lds && e->n == 20 && !e->cat_split;
     std::unordered_map<const double *, int> producer;   // vector -> the op of this plan that writes it
     for (int k = 0; k < nops && (hold_regs || hold_in_lds); k++) {
@@ -436,7 +435,7 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     // whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
     // (wide DNA: as the 4-state kernel, on both of its routes -- the generic kernel reads the exponentials only)
     const int leaf_sz = (!e->mfma || e->wide4) ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
-    const int slot_sz = e->mfma ? 0 : trav4_lds(B, e->wg_size).slot_doubles;   // (slot 0: the non-leaf children's)
+    const int slot_sz = e->mfma ? 0 : trav4_lds(B).slot_doubles;   // (slot 0: the non-leaf children's)
     int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
     for (int k = 0; k < nops; k++) {
         DevOp &d = e->h_ops.p[k];
@@ -564,7 +563,7 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
             if (c.chunk_slots != next) return bad(k, "chunk_slots is not the chunk's slot count");
             if (next > kTrav4RowSlots) return bad(k, "more leaf-state slots than the kernel's row-pointer list holds");
             if (next > e->plan.state_slots || regs > e->plan.lds_doubles ||
-                regs + next * trav4_lds(e->block, e->wg_size).slot_doubles > lds_budget(e))
+                regs + next * trav4_lds(e->block).slot_doubles > lds_budget(e))
                 return bad(k, "LDS chunk outside the launch's allocation or over the budget");
         }
         k += c.chunk_nops;
@@ -644,7 +643,7 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
             for (int k = 0; k < nops; k++)
                 if (e->h_ops.p[k].cherry) { e->h_ops.p[k].cherry += 8; break; }   // (inside the buffer, not on a table)
     }
-    if (e->check_plans && !e->ablate) {
+    if (e->check_plans) {
         const int rc = check_plan(e, nops, kSentinels);
         if (rc) { c.invalidate(); return rc; }
     }
@@ -706,7 +705,7 @@ constexpr int kRows64BudgetSlack = 128;   // on top of rows64_lds(), also in the
 
 int lds_budget(const iqhip_engine *e) {
     const int B = e->block, nx = e->state_unknown + 1 - e->n;
-    if (!e->mfma) return e->lds_budget_bytes / 8 - trav4_lds(B, e->wg_size).s_reg;
+    if (!e->mfma) return e->lds_budget_bytes / 8 - trav4_lds(B).s_reg;
     // (a 20-state engine on k_traverse_mfma_mix20, whose fixed part is mix20_lds().sReg = 0, is charged the generic kernel's
     // images all the same: slack as above)
     if (e->wide4) {   // both routes get the same chunks: the larger of the two kernels' fixed parts
@@ -740,15 +739,15 @@ TravLaunch choose_traverse_mfma(const iqhip_engine *e, bool top_stage, int nsegs
     int fixed = 0, waves_per_tile = 1;
     if (!e->mfma_pipelined) {   // both children from memory: mixtures, category counts without a pipelined instantiation
         // (20 states: the mixture kernel -- with one class for a plain model: 16+4-row MFMA split, A fragments in
-        // registers -- beats the padded generic kernel)
+        // registers -- beats the padded generic kernel, which is not instantiated for 20 states)
         if (e->wide4 && !e->wide4_generic) {
             L.variant = TRAV_WIDE4;
             fixed = wide4_lds(e->nclass, e->block).sReg;
-        } else if (n == 20 && !e->mix_generic) {
+        } else if (n == 20) {
             L.variant = e->mix_split ? TRAV_MIX20_SPLIT : TRAV_MIX20;
             waves_per_tile = e->mix_split ? 4 : 1;
             fixed = mix20_lds().sReg;
-        } else if (n == 20 || n == 64 || n == 4) {   // (4: mixtures, and wide DNA under IQHIP_WIDE4=generic; a plain model of at most 8 categories never comes here)
+        } else if (n == 64 || n == 4) {   // (4: mixtures, and wide DNA under IQHIP_WIDE4=generic; a plain model of at most 8 categories never comes here)
             L.variant = TRAV_GENERIC;
             fixed = generic_lds(n, nx).sReg;
         }

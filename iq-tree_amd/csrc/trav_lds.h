@@ -8,7 +8,7 @@
 
 namespace iqhip {
 
-constexpr int kTravWg = 256;                        // threads per workgroup of every matrix-core traversal kernel
+constexpr int kTravWg = 256;                        // threads per workgroup of every traversal kernel
 constexpr int kTravMaxLdsBytes = 150 * 1024;        // dynamic LDS every matrix-core traversal kernel is allowed ...
 constexpr int kTravGenericMaxLdsBytes = 160 * 1024; // ... and k_traverse_mfma, which has no static arrays
 constexpr int kTrav4MaxLdsBytes = 152 * 1024;       // k_traverse4: 160 KB minus the static arrays (fold_tail 3.1 KB, the fill's descriptor copies 2.3 KB and row pointers 2 KB)
@@ -60,7 +60,7 @@ __host__ __device__ constexpr Wide4Lds wide4_lds(int nclass, int block) { return
 constexpr int kWide4LdsKb = 40;   // per workgroup, fixed part included: four workgroups (16 waves) per CU
 
 // k_traverse4: tip vectors [32][4], one block of values, the plan regions, then the leaf-state slots -- one byte per
-// thread each, i.e. wg / 8 doubles; slot 0 is shared by all non-leaf children.  The state bytes lie [wave][slot][64]
+// thread each, i.e. kTravWg / 8 doubles; slot 0 is shared by all non-leaf children.  The state bytes lie [wave][slot][64]
 // (slot < Plan::state_slots): a wave's slots are contiguous, so one LDS-direct dword load fills four of them, each group
 // of 16 lanes fetching the 64 bytes of one leaf child (kernels_valu4.hip, the chunk fill's state requests).
 // The row pointers those requests read, s_row[slot], are a static array of kTrav4RowSlots pointers inside the kernel,
@@ -68,9 +68,9 @@ constexpr int kWide4LdsKb = 40;   // per workgroup, fixed part included: four wo
 // chunk before its slots would outgrow the array and check_plan holds every chunk to it.
 constexpr int kTrav4RowSlots = 256;
 struct Trav4Lds { int s_tip, s_val, s_reg, slot_doubles; };
-__host__ __device__ constexpr Trav4Lds trav4_lds(int block, int wg) { return {0, 128, 128 + block, wg / 8}; }
-__host__ __device__ constexpr size_t trav4_lds_bytes(int block, int wg, int lds_doubles, int state_slots) {
-    return ((size_t)trav4_lds(block, wg).s_reg + (size_t)lds_doubles + (size_t)state_slots * trav4_lds(block, wg).slot_doubles) * sizeof(double);
+__host__ __device__ constexpr Trav4Lds trav4_lds(int block) { return {0, 128, 128 + block, kTravWg / 8}; }
+__host__ __device__ constexpr size_t trav4_lds_bytes(int block, int lds_doubles, int state_slots) {
+    return ((size_t)trav4_lds(block).s_reg + (size_t)lds_doubles + (size_t)state_slots * trav4_lds(block).slot_doubles) * sizeof(double);
 }
 
 }  // namespace iqhip

@@ -1,5 +1,5 @@
 """GPU parity over the kernel paths the engine dispatches (engine.hip configure_engine, kernels_mfma.hip launch_traverse):
-every category count of the 4-state kernels with both lane splits and every workgroup size, the 20- and 64-state
+every category count of the 4-state kernels with both lane splits, the 20- and 64-state
 category counts with and without a pipelined instantiation (the one-class mix20 kernel, its component split, the generic
 64-state kernel), the documented component caps, and the matrix-core tile edges with each size-chosen variant forced both
 ways.  Each case checks lnL, pattern_lh, pattern_lh_cat, every vector and counter, branch lnL, df / ddf and the lnL from
@@ -39,9 +39,8 @@ def test_dna_category_counts(pkg, synth, oracle, ncat, lane_split, monkeypatch):
 
 
 @pytest.mark.parametrize("ncat", [3, 8])
-@pytest.mark.parametrize("wg", ["64", "128", "256"])
-def test_dna_workgroup_sizes(pkg, synth, oracle, ncat, wg, monkeypatch):
-    monkeypatch.setenv("IQHIP_WG", wg)
+def test_dna_workgroup_sizes(pkg, synth, oracle, ncat):
+    """11 tiles on workgroups of four waves (kTravWg = 256): 11 waves, or 22 with two lanes per pattern -- the last workgroup is ragged"""
     t, ot, model, *_ = make_case(synth, oracle, pkg, 11, 700, 4, ncat, 1400 + ncat, missing=0.03)
     check_paths(t, ot, model, 11)
 

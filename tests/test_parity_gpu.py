@@ -350,16 +350,6 @@ def test_lds_chunking_of_long_plans(pkg, synth, oracle, monkeypatch):
     assert check_all_vectors(t, ot) == 40 - 2
 
 
-@pytest.mark.parametrize("wg", ["64", "128"])
-def test_other_workgroup_sizes(pkg, synth, oracle, monkeypatch, wg):
-    monkeypatch.setenv("IQHIP_WG", wg)
-    t, ot, *_ = make_case(synth, oracle, pkg, 13, 777, 4, 4, 93, missing=0.05)
-    monkeypatch.delenv("IQHIP_WG")
-    lnl = t.compute_likelihood()
-    ref, _ = ot.likelihood()
-    assert abs(lnl - ref) <= LNL_RTOL * abs(ref)
-
-
 # ------------------------------------------------------------------------------------------
 # 20-state (protein) and 64-state (codon) matrix-core path
 # ------------------------------------------------------------------------------------------

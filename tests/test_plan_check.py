@@ -47,7 +47,7 @@ SHAPES = [  # nstates, ncat, nptn, ntaxa, nclass: every kernel family and the si
 ]
 
 
-ENVS = [{}, {"IQHIP_LEAF_TABLES": "1"}, {"IQHIP_LEAF_TABLES": "0", "IQHIP_HOLD": "0", "IQHIP_HOLD_LDS": "0"},
+ENVS = [{}, {"IQHIP_LEAF_TABLES": "1"}, {"IQHIP_LEAF_TABLES": "0", "IQHIP_HOLD_LDS": "0"},
         {"IQHIP_SPLIT": "5", "IQHIP_LEVELS": "3"}, {"IQHIP_SPLIT": "0", "IQHIP_SMALL_PLANS": "0"}]
 
 

@@ -51,7 +51,6 @@ TABLE_CASES = [
     ("t4w-mix3x4", 4, 4, 3, {"IQHIP_WIDE4": "valu"}),
     ("generic-4x9", 4, 9, 1, {"IQHIP_WIDE4": "generic"}), ("generic-64x2", 64, 2, 1, {}),
     ("generic-64-mix2x1", 64, 1, 2, {}),
-    ("v1-20x4", 20, 4, 1, {"IQHIP_MFMA_V1": "1"}),     # (no pipelined instantiation: the one-class mix20 kernel)
     ("mfma2-20x1", 20, 1, 1, {}),
     ("mfma2-20x4-cs0-top0", 20, 4, 1, {"IQHIP_CAT_SPLIT": "0", "IQHIP_TOP_CS2": "0"}),
     ("mfma2-20x4-cs0-top1", 20, 4, 1, {"IQHIP_CAT_SPLIT": "0", "IQHIP_TOP_CS2": "1"}),
@@ -64,9 +63,9 @@ TABLE_CASES = [
     ("mix20-mix3x4", 20, 4, 3, {}),
     ("rows64-64x1", 64, 1, 1, {"IQHIP_ROW_SPLIT": "1"}),
 ]
-# one or two per family; IQHIP_HOLD / IQHIP_HOLD_LDS: joins read the parked copy or memory
+# one or two per family; 4 states: joins read the parked copy; IQHIP_HOLD_LDS: the parked copy or memory
 CHAIN_CASES = [
-    ("t4-c4-hold1", 4, 4, 1, {"IQHIP_HOLD": "1"}), ("t4-c4-hold0", 4, 4, 1, {"IQHIP_HOLD": "0"}),
+    ("t4-c4-hold1", 4, 4, 1, {}),
     ("t4w-c9", 4, 9, 1, {"IQHIP_WIDE4": "valu"}),
     ("generic-64x2", 64, 2, 1, {}),
     ("mfma2-20x4-hold1", 20, 4, 1, {"IQHIP_CAT_SPLIT": "0", "IQHIP_TOP_CS2": "0", "IQHIP_HOLD_LDS": "1"}),
