@@ -996,6 +996,63 @@ int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const iqhip_branch
 int iqhip_debug_partition_timing(iqhip_partition *g, double *ms /* 2: derivative launches, update launches */,
                                  int64_t *launches);
 
+/* ---- UFBoot on edge-linked partition models: per-pattern rows of the batched joint solve, RELL sums and the bootstrap's
+ *      bookkeeping on the group (PhyloSuperTreePlen::getBestNNIForBran, phylosupertreeplen.cpp:1367-1372;
+ *      PhyloSuperTree::computePatternLikelihood, phylosupertree.cpp:981-990; SuperAlignment::createBootstrapAlignment,
+ *      superalignment.cpp:360-370) ----
+ * Row r of the group is row r of EVERY member's store of per-pattern log-likelihood rows (iqhip_ptnlh_*); every member keeps
+ * its own sample matrix, filled on the member with iqhip_set_boot_samples / iqhip_gen_boot_samples (ndraws = the member's
+ * own site count: sites are resampled within partitions).  The RELL score of a super tree in replicate s is
+ *     sum_p sum_ptn W_p[s][ptn] * L_p[row][ptn]
+ * formed as the members' own products (the fp64 matrix-core product of iqhip_ptnlh_rell, each on its member's stream with
+ * its own K-split) added IN MEMBER ORDER, ((R_0 + R_1) + R_2) + ..., on the group's stream.
+ *
+ * iqhip_partition_ptnlh_reserve: iqhip_ptnlh_reserve(nrows) on every member.
+ * iqhip_partition_optimize_branch_batch_rows: iqhip_partition_optimize_branch_batch (rows == NULL is exactly that call),
+ *   and for every task t with rows[t] >= 0 every member p receives in row rows[t] of its own store the per-pattern
+ *   log-likelihood of the task's branch at r_p * optx.  A row means what iqhip_optimize_branch_batch_rows documents:
+ *   log|lh + invar| with the reference's NaN / inf repair, the scale counters of both branch ends put back, 0 in the
+ *   padding; members are never +ASC, so there is no shift.  The row is written by the lnL pass that rides behind every
+ *   chunk of steps, in the launch that forms the task's lnL sums: the pattern's value before the multiplication by its
+ *   frequency, a plain store, exactly once per task.  It is a function of the theta slot, the counters and optx alone: the
+ *   same bits for every IQHIP_PART_BATCH_CHUNK and IQHIP_PART_STEPS; results and part_lnl have the bits of the call
+ *   without rows.  IQHIP_ERR_INVALID, before anything is enqueued, for a row >= 0 outside any member's store
+ *   and for a row >= 0 that two tasks name (the rows of one call are distinct).
+ * iqhip_partition_ptnlh_rell: out[i * nsamples + s] = the member-order sum above for rows[i] and replicate s.  Member p's
+ *   term has the bits of iqhip_ptnlh_rell(member p, rows, nrows, nsamples).
+ * iqhip_partition_ufboot_init: the per-replicate state of iqhip_ufboot_init (boot_logl = boot_orig_logl = -DBL_MAX,
+ *   boot_counts = 0, boot_tree = -1), owned by the group; the members' own UFBoot states are not touched.  Every member must
+ *   hold at least nsamples samples.  The state belongs to the members' sample matrices as they are now: once any member's
+ *   matrix is replaced or refilled (iqhip_set_boot_samples, iqhip_gen_boot_samples, iqhip_multiscale_bp) every call below is
+ *   IQHIP_ERR_INVALID until the next init.
+ * iqhip_partition_ufboot_update: iqhip_ufboot_update on the group -- the same entry struct, the same host-side cutoff
+ *   (an entry with logl_cutoff != 0 and logl < logl_cutoff - 1 is dropped), the entries applied IN LIST ORDER, the same
+ *   three counts {applied, dropped, replaced slots} and minimum.  `rell` of an entry is the member-order sum, formed inside
+ *   the update kernel: no summed matrix is materialised.  Entries per chunk: all members' staging together within 256 MB;
+ *   IQHIP_UFBOOT_CHUNK (read per call) overrides.  A member's K-split follows from nsamples, its pattern count and the CU
+ *   count alone, so the state is bit-identical for every chunk size, and to the rule applied to
+ *   iqhip_partition_ptnlh_rell at the same nsamples.
+ * iqhip_partition_ufboot_fetch: the four state arrays, nsamples entries each (any may be NULL).
+ * iqhip_debug_partition_ufboot_timing: of the last update, *launches = kernels enqueued; with iqhip_timing_enable on the
+ *   FIRST member, ms[0] = device time of the members' products (summed over members), ms[1] = of the update kernels.
+ * Everything is validated on the host before the first launch.  IQHIP_ERR_INVALID: a null group or list; nrows / ntrees < 1;
+ *   a row outside a member's store; tree_id < 0; rand outside [0, 1] or NaN; a non-finite logl; epsilon < 0 or NaN; update
+ *   or fetch before init (or after a member's sample matrix was replaced); nsamples < 1 or above any member's sample count.
+ *   The member conditions of every group call apply. */
+int iqhip_partition_ptnlh_reserve(iqhip_partition *g, int nrows);
+int iqhip_partition_optimize_branch_batch_rows(iqhip_partition *g, const iqhip_branch_task *tasks, int ntasks,
+                                               iqhip_branch_result *results,
+                                               double *part_lnl /* ntasks * nparts, [task][member], or NULL */,
+                                               const int32_t *rows /* ntasks (row, or < 0: none) or NULL */);
+int iqhip_partition_ptnlh_rell(iqhip_partition *g, const int32_t *rows, int nrows, int nsamples,
+                               double *out /* nrows * nsamples */);
+int iqhip_partition_ufboot_init(iqhip_partition *g, int nsamples);
+int iqhip_partition_ufboot_update(iqhip_partition *g, const iqhip_ufboot_tree *trees, int ntrees, double epsilon,
+                                  double logl_cutoff, int64_t *counts /* 3 or NULL */, double *min_orig_logl /* or NULL */);
+int iqhip_partition_ufboot_fetch(iqhip_partition *g, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts,
+                                 int64_t *boot_tree);
+int iqhip_debug_partition_ufboot_timing(iqhip_partition *g, double *ms /* 2: products, update */, int64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,9 @@ IQHIP_SYMBOLS = [
     "iqhip_partition_create", "iqhip_partition_destroy", "iqhip_partition_set_rates", "iqhip_partition_newton_branch",
     "iqhip_partition_lnl_from_theta", "iqhip_partition_traverse_lnl", "iqhip_debug_partition_timing",
     "iqhip_partition_optimize_branch_batch",
+    "iqhip_partition_ptnlh_reserve", "iqhip_partition_optimize_branch_batch_rows", "iqhip_partition_ptnlh_rell",
+    "iqhip_partition_ufboot_init", "iqhip_partition_ufboot_update", "iqhip_partition_ufboot_fetch",
+    "iqhip_debug_partition_ufboot_timing",
 ]
 
 # slots of iqhip_debug_path_counts (include/iqhip.h IQHIP_PATH_*)
@@ -285,6 +288,14 @@ def libiqhip():
     lib.iqhip_partition_traverse_lnl.argtypes = [vp, C.POINTER(NodeOp), C.c_int, BranchEnd, BranchEnd, C.c_double, dp, dp]
     lib.iqhip_partition_optimize_branch_batch.argtypes = [vp, C.POINTER(BranchTask), C.c_int, C.POINTER(BranchResult), dp]
     lib.iqhip_debug_partition_timing.argtypes = [vp, dp, i64p]
+    lib.iqhip_partition_ptnlh_reserve.argtypes = [vp, C.c_int]
+    lib.iqhip_partition_optimize_branch_batch_rows.argtypes = [vp, C.POINTER(BranchTask), C.c_int, C.POINTER(BranchResult), dp,
+                                                               i32p]
+    lib.iqhip_partition_ptnlh_rell.argtypes = [vp, i32p, C.c_int, C.c_int, dp]
+    lib.iqhip_partition_ufboot_init.argtypes = [vp, C.c_int]
+    lib.iqhip_partition_ufboot_update.argtypes = [vp, C.POINTER(UFBootTree), C.c_int, C.c_double, C.c_double, i64p, dp]
+    lib.iqhip_partition_ufboot_fetch.argtypes = [vp, dp, dp, i32p, i64p]
+    lib.iqhip_debug_partition_ufboot_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
 
@@ -418,6 +429,10 @@ def libiqhost():
     lib.iqhost_super_restore_branch_lengths.argtypes = [vp, dp, C.c_int]
     lib.iqhost_super_clear_all_partial_lh.argtypes = [vp]
     lib.iqhost_super_nni_for_branch.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
+    lib.iqhost_super_nni_for_branch_rows.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+    lib.iqhost_super_evaluate_nnis_list_rows.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int), dp,
+                                                         C.c_int, C.POINTER(C.c_int)]
+    lib.iqhost_super_gen_boot_samples.argtypes = [vp, C.c_int, C.c_uint64]
     lib.iqhost_super_evaluate_nnis_list.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), dp, C.c_int,
                                                     C.POINTER(C.c_int)]
     lib.iqhost_evaluate_nnis5_batch_rows.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int, C.POINTER(C.c_int), C.c_int]
@@ -2306,7 +2321,7 @@ class TreeSearch:
         self.lib = libiqhost()
         self.tree = tree
         self.h = C.c_void_p()
-        if isinstance(tree, PhyloSuperTree):   # UFBoot and num_init_trees > 0 are refused
+        if isinstance(tree, PhyloSuperTree):   # num_init_trees > 0 is refused; UFBoot: tree.ufboot_init (the group's state)
             _hchk(self.lib.iqhost_search_create_super(C.byref(self.h), tree.h))
         else:
             _hchk(self.lib.iqhost_search_create(C.byref(self.h), tree.h))
@@ -2461,16 +2476,24 @@ class PartitionGroup:
             None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
-    def optimize_branch_batch(self, tasks, want_part_lnl=True):
+    def optimize_branch_batch(self, tasks, want_part_lnl=True, rows=None):
         """tasks: a ctypes array of BranchTask (their ops arrays must stay alive for the call), or a list of them;
+        rows (optional, one per task; < 0: none): the row of every member's per-pattern store that takes the task's values
+        (iqhip_partition_optimize_branch_batch_rows);
         -> (results, part_lnl): a list of dicts {optx, d2l, lnl, nsteps, status} and an array [task][member] or None"""
         if tasks is not None and not isinstance(tasks, C.Array):
             tasks = (BranchTask * max(1, len(tasks)))(*tasks) if len(tasks) else None
         n = 0 if tasks is None else len(tasks)
         res = (BranchResult * max(1, n))()
         out = np.zeros((max(1, n), self.nparts)) if want_part_lnl else None
-        self._chk(self.lib.iqhip_partition_optimize_branch_batch(
-            self.h, tasks, n, res, out.ctypes.data_as(C.POINTER(C.c_double)) if want_part_lnl else None))
+        outp = out.ctypes.data_as(C.POINTER(C.c_double)) if want_part_lnl else None
+        if rows is None:
+            self._chk(self.lib.iqhip_partition_optimize_branch_batch(self.h, tasks, n, res, outp))
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.int32)
+            if r.shape != (n,):
+                raise ValueError("one row per task")
+            self._chk(self.lib.iqhip_partition_optimize_branch_batch_rows(self.h, tasks, n, res, outp, _iptr(r)))
         results = [dict(optx=r.optx, d2l=r.d2l, lnl=r.lnl, nsteps=r.nsteps, status=r.status) for r in res[:n]]
         return results, out
 
@@ -2480,6 +2503,72 @@ class PartitionGroup:
         n = C.c_int64()
         self._chk(self.lib.iqhip_debug_partition_timing(self.h, ms, C.byref(n)))
         return {"derv_ms": ms[0], "update_ms": ms[1], "launches": n.value}
+
+    # ---- per-pattern rows, RELL sums and UFBoot of the group: row r is row r of every member's store, every member keeps
+    #      its own sample matrix (set_boot_samples / gen_boot_samples on the member)
+    def ptnlh_reserve(self, nrows):
+        self._chk(self.lib.iqhip_partition_ptnlh_reserve(self.h, int(nrows)))
+
+    def ptnlh_rell(self, rows, nsamples):
+        """-> [len(rows), nsamples]: the members' RELL sums added in member order"""
+        return _group_ptnlh_rell(self.lib, self.h, rows, nsamples)
+
+    def ufboot_init(self, nsamples):
+        self._chk(self.lib.iqhip_partition_ufboot_init(self.h, int(nsamples)))
+        self._ufboot = int(nsamples)
+
+    def ufboot_update(self, rows, tree_ids, logl, rand, epsilon=0.5, logl_cutoff=0.0):
+        """iqhip_partition_ufboot_update -> as PhyloTree.ufboot_update"""
+        return _group_ufboot_update(self.lib, self.h, rows, tree_ids, logl, rand, epsilon, logl_cutoff)
+
+    def ufboot_state(self):
+        """iqhip_partition_ufboot_fetch -> dict(boot_logl, boot_orig_logl, boot_counts, boot_tree)"""
+        return _group_ufboot_state(self.lib, self.h, getattr(self, "_ufboot", 0))
+
+    def ufboot_timing(self):
+        """(device ms of the members' products, of the update kernels, kernels enqueued) of the last ufboot_update"""
+        return _group_ufboot_timing(self.lib, self.h)
+
+
+def _gchk(lib, rc):
+    if rc != 0:
+        raise EngineError(rc, lib.iqhip_last_error().decode())
+
+
+def _group_ptnlh_rell(lib, g, rows, nsamples):
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    out = np.zeros((max(1, r.size), max(1, int(nsamples))))
+    _gchk(lib, lib.iqhip_partition_ptnlh_rell(g, _iptr(r), r.size, int(nsamples), _dptr(out)))
+    return out[:r.size, :int(nsamples)]
+
+
+def _group_ufboot_update(lib, g, rows, tree_ids, logl, rand, epsilon, logl_cutoff):
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    assert r.size == len(tree_ids) == len(logl) == len(rand)
+    ent = (UFBootTree * max(1, r.size))()
+    for k in range(r.size):
+        ent[k] = UFBootTree(int(r[k]), 0, int(tree_ids[k]), float(logl[k]), float(rand[k]))
+    counts = np.zeros(3, dtype=np.int64)
+    mn = C.c_double()
+    _gchk(lib, lib.iqhip_partition_ufboot_update(g, ent, r.size, float(epsilon), float(logl_cutoff),
+                                                 counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+    return counts, mn.value
+
+
+def _group_ufboot_state(lib, g, n):
+    n = max(1, int(n))
+    st = dict(boot_logl=np.zeros(n), boot_orig_logl=np.zeros(n), boot_counts=np.zeros(n, dtype=np.int32),
+              boot_tree=np.zeros(n, dtype=np.int64))
+    _gchk(lib, lib.iqhip_partition_ufboot_fetch(g, _dptr(st["boot_logl"]), _dptr(st["boot_orig_logl"]), _iptr(st["boot_counts"]),
+                                                st["boot_tree"].ctypes.data_as(C.POINTER(C.c_int64))))
+    return st
+
+
+def _group_ufboot_timing(lib, g):
+    ms = (C.c_double * 2)()
+    n = C.c_int64()
+    _gchk(lib, lib.iqhip_debug_partition_ufboot_timing(g, ms, C.byref(n)))
+    return ms[0], ms[1], n.value
 
 
 def parse_partition_spec(text, nsite):
@@ -2686,14 +2775,16 @@ class PhyloSuperTree:
         d = self.lib.iqhost_super_neighbors(self.h, node, ids, lens, 8)
         return [(ids[i], lens[i]) for i in range(d)]
 
-    def nni_for_branch(self, a, b, nni5=False):
+    def nni_for_branch(self, a, b, nni5=False, first_row=None):
         """the branch-by-branch path: both swaps made on every tree, joint optimize_one_branch solves, the summed lnL ->
-        [(newloglh, swapped subtree at a, swapped subtree at b, [newLen...]), x2]"""
+        [(newloglh, swapped subtree at a, swapped subtree at b, [newLen...]), x2]; first_row: the two neighbours'
+        per-pattern values are kept in rows first_row, first_row + 1 of every member's store (ptnlh_fetch)"""
         out = np.zeros(16)
-        self._chk(self.lib.iqhost_super_nni_for_branch(self.h, a, b, int(nni5), _dptr(out)))
+        self._chk(self.lib.iqhost_super_nni_for_branch_rows(self.h, a, b, int(nni5), -1 if first_row is None else int(first_row),
+                                                            _dptr(out)))
         return [(out[8 * c], int(out[8 * c + 1]), int(out[8 * c + 2]), list(out[8 * c + 3:8 * c + 8])) for c in range(2)]
 
-    def _evaluate_nnis_list(self, nni5, branches):
+    def _evaluate_nnis_list(self, nni5, branches, first_row=None):
         if branches is None:
             br, nbr, cap = None, 0, 4 * self.num_nodes
         else:
@@ -2704,7 +2795,8 @@ class PhyloSuperTree:
         ids = np.zeros(4 * cap, dtype=np.int32)
         vals = np.zeros(w * cap)
         n = C.c_int()
-        self._chk(self.lib.iqhost_super_evaluate_nnis_list(self.h, int(nni5), br, nbr, _iptr(ids), _dptr(vals), cap, C.byref(n)))
+        self._chk(self.lib.iqhost_super_evaluate_nnis_list_rows(self.h, int(nni5), br, nbr, -1 if first_row is None else int(first_row),
+                                                                _iptr(ids), _dptr(vals), cap, C.byref(n)))
         return ids, vals, n.value
 
     def evaluate_nnis_batch(self, branches=None):
@@ -2714,9 +2806,10 @@ class PhyloSuperTree:
                      node2_nei=int(ids[4 * k + 3]), new_len=float(vals[2 * k]), newloglh=float(vals[2 * k + 1]))
                 for k in range(n)]
 
-    def evaluate_nnis5_batch(self, branches=None):
-        """all nni5 candidates in ten batches of joint solves (needs all_branch=True) -> as PhyloTree.evaluate_nnis5_batch"""
-        ids, vals, n = self._evaluate_nnis_list(True, branches)
+    def evaluate_nnis5_batch(self, first_row=None, branches=None):
+        """all nni5 candidates in ten batches of joint solves (needs all_branch=True) -> as PhyloTree.evaluate_nnis5_batch;
+        first_row: candidate k's per-pattern values are kept in row first_row + k of every member's store (ptnlh_fetch)"""
+        ids, vals, n = self._evaluate_nnis_list(True, branches, first_row)
         return [dict(node1=int(ids[4 * k]), node2=int(ids[4 * k + 1]), node1_nei=int(ids[4 * k + 2]),
                      node2_nei=int(ids[4 * k + 3]), new_lens=[float(x) for x in vals[6 * k:6 * k + 5]],
                      newloglh=float(vals[6 * k + 5])) for k in range(n)]
@@ -2775,6 +2868,95 @@ class PhyloSuperTree:
             return ts.optimize_nni(trace=trace)
         finally:
             ts.close()
+
+    # ---- UFBoot on the super tree: sites are resampled within partitions (every member keeps its own sample matrix), the
+    #      per-replicate state is the group's, the bookkeeping is the plain tree's run on the super tree
+    @property
+    def _group(self):
+        return self.lib.iqhost_super_group(self.h)
+
+    @property
+    def _super(self):
+        return self.lib.iqhost_super_tree(self.h)
+
+    def gen_boot_samples(self, nsamples, seed):
+        """member p: nsamples replicates of its own site count drawn on the device with stream p"""
+        self._chk(self.lib.iqhost_super_gen_boot_samples(self.h, int(nsamples), int(seed)))
+
+    def set_boot_samples(self, list_of_W):
+        """one float32 [nsamples, member's nptn] matrix of pattern weights per member"""
+        if len(list_of_W) != self.nparts:
+            raise ValueError("one sample matrix per partition")
+        for t, W in zip(self.members, list_of_W):
+            t.set_boot_samples(W)
+
+    def ptnlh_reserve(self, nrows):
+        _gchk(libiqhip(), libiqhip().iqhip_partition_ptnlh_reserve(self._group, int(nrows)))
+
+    def ptnlh_fetch(self, row):
+        """-> the row of every member's store, a list of per-member arrays"""
+        return [t.ptnlh_fetch(row) for t in self.members]
+
+    def ptnlh_rell(self, rows, nsamples):
+        """-> [len(rows), nsamples]: sum_p L_p[row] . W_p[s], the members' sums added in member order"""
+        return _group_ptnlh_rell(libiqhip(), self._group, rows, nsamples)
+
+    def ufboot_init(self, nsamples, seed=0):
+        """iqhip_partition_ufboot_init on the first nsamples rows of every member's sample matrix; seed: the tie draws"""
+        self._chk(self.lib.iqhost_ufboot_init(self._super, int(nsamples), int(seed)))
+        self._ufboot = int(nsamples)
+
+    def ufboot_update(self, rows, tree_ids, logl, rand, epsilon=0.5, logl_cutoff=0.0):
+        """iqhip_partition_ufboot_update -> (counts = [applied, dropped by the cutoff, slots replaced], min_orig_logl)"""
+        return _group_ufboot_update(libiqhip(), self._group, rows, tree_ids, logl, rand, epsilon, logl_cutoff)
+
+    def ufboot_state(self):
+        return _group_ufboot_state(libiqhip(), self._group, getattr(self, "_ufboot", 0))
+
+    def ufboot_timing(self):
+        return _group_ufboot_timing(libiqhip(), self._group)
+
+    def ufboot_params(self, epsilon=0.5, logl_cutoff=0.0):
+        self._chk(self.lib.iqhost_ufboot_params(self._super, float(epsilon), float(logl_cutoff)))
+
+    def ufboot_next_iteration(self):
+        self._chk(self.lib.iqhost_ufboot_next_iteration(self._super))
+
+    def ufboot_info(self):
+        info = np.zeros(2, dtype=np.int64)
+        vals = np.zeros(2)
+        self._chk(self.lib.iqhost_ufboot_info(self._super, info.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(vals)))
+        return dict(trees_fed=int(info[0]), trees_kept=int(info[1]), logl_cutoff=float(vals[0]), min_orig_logl=float(vals[1]))
+
+    def save_current_tree(self, logl):
+        """the current tree's row on every member (row 0), then one update -> (counts, min_orig_logl)"""
+        counts = np.zeros(3, dtype=np.int64)
+        mn = C.c_double()
+        self._chk(self.lib.iqhost_save_current_tree(self._super, float(logl), counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+        return counts, mn.value
+
+    def save_nni_trees(self):
+        """all 2(n-3) NNI neighbours (evaluate_nnis5_batch with rows 1 ..) through ONE update -> (counts, min_orig_logl)"""
+        counts = np.zeros(3, dtype=np.int64)
+        mn = C.c_double()
+        self._chk(self.lib.iqhost_save_nni_trees(self._super, counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(mn)))
+        return counts, mn.value
+
+    def summarize_bootstrap(self):
+        """as PhyloTree.summarize_bootstrap, on the super tree"""
+        cap = self.num_nodes
+        ids = np.zeros(2 * cap, dtype=np.int32)
+        sup = np.zeros(cap, dtype=np.int32)
+        n, distinct, need = C.c_int(), C.c_int(), C.c_int()
+        ip = C.POINTER(C.c_int)
+        args = (self._super, ids.ctypes.data_as(ip), sup.ctypes.data_as(ip), cap, C.byref(n), C.byref(distinct))
+        self._chk(self.lib.iqhost_summarize_bootstrap(*args, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self._chk(self.lib.iqhost_summarize_bootstrap(*args, buf, len(buf), C.byref(need)))
+        lines = buf.value.decode().split("\n")
+        return dict(support_tree=lines[0], consensus_tree=lines[1], boot_trees=lines[2:2 + self._ufboot],
+                    supports=[(int(ids[2 * q]), int(ids[2 * q + 1]), int(sup[q])) for q in range(n.value)],
+                    distinct_trees=distinct.value)
 
     def partition_timing(self):
         """iqhip_debug_partition_timing of the group's last call (times need iqhip_timing_enable on member 0)"""

@@ -558,6 +558,8 @@ struct iqhip_engine {
     iqhip::DevBuf<double> d_ptn_scaled;
     iqhip::DevBuf<float> d_boot;  // [nboot][nptn_pad], zero padded
     int nboot = 0;
+    uint64_t boot_generation = 0;   // advances, by one or more, whenever the matrix or its contents are replaced: only inequality
+                                    // means something (a partition group's UFBoot state records it at init and is void once it differs)
     // branch tests (SH-aLRT / local bootstrap, ptnlh.hip): the store of per-pattern log-likelihood rows [ptnlh_rows][nptn_pad]
     // and the scratch of iqhip_branch_tests / iqhip_ptnlh_rell (row lists, K-split partial products, combined sums, results)
     iqhip::DevBuf<double> d_ptnlh;
@@ -1265,6 +1267,15 @@ hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const 
 // kernels_alrt.hip: R = L W^T on the fp64 matrix cores (K-split partial products, then a fixed-order combine) and the
 // SH-aLRT / local-bootstrap counts
 int alrt_ksplit(const iqhip_engine *e, int nrows, int nsamples);
+// ptnlh.hip: the distinct rows of a row list in first-appearance order (list[0, M)) and, behind them, every entry's index
+// into them; bt_stage: the list into e->bt.rows, e->bt.part and e->bt.sums sized for products of its distinct rows with
+// nsamples replicates (the engine's stream drains)
+struct RowList {
+    std::vector<int32_t> list;
+    int M;
+};
+RowList row_list(const int32_t *rows, int nrows);
+int bt_stage(iqhip_engine *e, const RowList &rl, int ksplit, size_t nsamples);
 hipError_t launch_alrt_product(iqhip_engine *e, const int32_t *d_rows, int nrows, int nsamples, int ksplit, double *part,
                                double *sums);
 hipError_t launch_alrt_stats(iqhip_engine *e, const int32_t *d_idx3, const double *d_lh3, int nbranch, int nsamples,
@@ -1428,15 +1439,27 @@ hipError_t launch_part_newton_update(hipStream_t s, const PartDesc *d_desc, int 
 hipError_t launch_part_lnl_finish(hipStream_t s, const PartDesc *d_desc, int nparts, const double *partials, double *out);
 // the batch of joint solves: task t (grid.y) on slot t of every member at the length in states[t]; d_sc: [ntasks][nparts][2]
 // scale counters of the tasks' branch ends; partials: [ntasks][nitems][2]; out: [ntasks][nparts]; lnl_written: [ntasks], zero
-// when the chain starts -- the finish launch marks a task that is done, and later mode 1 launches leave it alone
+// when the chain starts -- the finish launch marks a task that is done, and later mode 1 launches leave it alone.  d_rowp
+// (mode 1; nullptr: none): [ntasks][nparts] rows of the members' per-pattern stores (nullptr: the task keeps no row), written
+// in the one mode 1 pass that gets past the lnl_written guard
 hipError_t launch_part_derv_batch(hipStream_t s, int mode, const PartDesc *d_desc, const PartItem *d_items, int nitems,
                                   int lds_doubles, const PartSlots *d_slots, const int16_t *const *d_sc, int nparts,
-                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials);
+                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials,
+                                  double *const *d_rowp = nullptr);
 hipError_t launch_part_newton_update_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems,
                                            const double *partials, NewtonState *states, int ntasks);
 hipError_t launch_part_lnl_finish_batch(hipStream_t s, const PartDesc *d_desc, int nparts, int nitems, const double *partials,
                                         const NewtonState *states, int32_t *lnl_written, double *out, int ntasks);
 // out[p] = kLogScalingThreshold * sum over patterns of freq * (a_sc + b_sc), fixed order
 hipError_t launch_part_scale_terms(hipStream_t s, const PartScale *d_sc, int nparts, double *out);
+
+// kernels_partboot.hip: the members' RELL sums [M][nsamples] added in member order, ((R_0 + R_1) + R_2) + ..; d_sums: a device
+// table of nparts pointers.  launch_part_rell_sum: the summed matrix (count = M * nsamples elements);
+// launch_part_ufboot_update: launch_ufboot_update with rell formed as that sum inside the kernel
+hipError_t launch_part_rell_sum(hipStream_t s, const double *const *d_sums, int nparts, size_t count, double *out);
+hipError_t launch_part_ufboot_update(hipStream_t s, const double *const *d_sums, int nparts, int nsamples,
+                                     const iqhip_ufboot_tree *d_entries, int n, double epsilon, double *boot_logl,
+                                     double *boot_orig_logl, int32_t *boot_counts, int64_t *boot_tree,
+                                     unsigned long long *replaced, double *wgmin);
 
 }  // namespace iqhip

@@ -17,6 +17,8 @@
 // slot t of every member's theta batch (eng_batch_prepare) and writes partials[t][item][2]; a task that is done does
 // nothing.  The per-item body (part_item_sums), the member and item sums (part_newton_update, part_lnl_of_member) are the
 // single solve's own functions, so a task's bits are those of iqhip_partition_newton_branch on the same theta.
+// With rows (iqhip_partition_optimize_branch_batch_rows) that lnL pass also stores every pattern's value, before the
+// multiplication by its frequency, into the task's row of the member's per-pattern store: no launch and no read is added.
 #include "iqhip_internal.h"
 
 namespace iqhip {
@@ -28,10 +30,14 @@ namespace iqhip {
 // MODE 0: sums of f * df_ptn, f * ddf_ptn at the member's length rate * x.
 // MODE 1: sum of f * (log|lh_ptn| + scale counters * LOG_SCALING_THRESHOLD) at rate * x.
 // theta, a_sc, b_sc: the member's resident theta and its ends' counters (D's own), or those of a task's slot.
+// row (MODE 1; nullptr: none): a row of the member's per-pattern store, nptn_pad doubles.  row[ptn] = the pattern's l before
+// the multiplication by f -- log|lh + invar| with the repair, the counters of both ends put back -- and 0 in the padding of
+// a ragged last tile.  A plain vector store by the lane that holds the value (matrix-core tiles: lane group 0); the tiles of
+// a member cover [0, nptn_pad) exactly, every pattern once.
 template <int MODE>
 __device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem &it, const double *__restrict__ theta,
                                                const int16_t *__restrict__ a_sc, const int16_t *__restrict__ b_sc, double x,
-                                               double *smem, double *__restrict__ out2) {
+                                               double *smem, double *__restrict__ out2, double *__restrict__ row = nullptr) {
     const int B = D.n * D.ncat;
     double *s_v0 = smem, *s_v1 = smem + B, *s_v2 = smem + 2 * B, *s_red = smem + 3 * B;   // s_red[8]
     const double len = D.rate * x;
@@ -50,7 +56,7 @@ __device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem
     for (int64_t tile = it.first_tile + wave; tile < tile_end; tile += 4) {
         double lh = 0.0, d1 = 0.0, d2 = 0.0;
         int64_t ptn;
-        bool mine;
+        bool mine, holder = true;   // holder: this lane has the pattern's value (and writes its row entry)
         if (!D.mfma) {
             ptn = tile * 64 + lane;
             mine = ptn < D.nptn;
@@ -66,7 +72,8 @@ __device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem
         } else {
             const int p = lane & 15, g = lane >> 4;
             ptn = tile * 16 + p;
-            mine = (g == 0) && ptn < D.nptn;
+            holder = g == 0;
+            mine = holder && ptn < D.nptn;
             const double *th = theta + (size_t)tile * 16 * B;
             // a pattern's rows 20 at a time: all 20 loads of a lane are in flight together
             for (int e0 = g; e0 < B; e0 += 80) {
@@ -104,6 +111,7 @@ __device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem
                 if (a_sc) ssc += a_sc[ptn];
                 if (b_sc) ssc += b_sc[ptn];
                 l += (double)ssc * kLogScalingThreshold;
+                if (row) row[ptn] = l;
                 adf = fma(l, f, adf);
             } else {
                 const double inv = 1.0 / fabs(lh);
@@ -112,6 +120,8 @@ __device__ __forceinline__ void part_item_sums(const PartDesc &D, const PartItem
                 adf = fma(dfp, f, adf);
                 addf = fma(ddfp, f, addf);
             }
+        } else if (MODE == 1 && row && holder) {
+            row[ptn] = 0.0;   // (ptn < nptn_pad: the member's tiles end there)
         }
     }
     adf = wave_sum64(adf);
@@ -156,7 +166,7 @@ __global__ __launch_bounds__(256) void k_part_derv_batch(const PartDesc *__restr
                                                          const int16_t *const *__restrict__ sc, int nparts,
                                                          const NewtonState *__restrict__ states,
                                                          const int32_t *__restrict__ lnl_written,
-                                                         double *__restrict__ partials) {
+                                                         double *__restrict__ partials, double *const *__restrict__ rowp) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int task = blockIdx.y;
     const NewtonState *st = states + task;
@@ -167,8 +177,11 @@ __global__ __launch_bounds__(256) void k_part_derv_batch(const PartDesc *__restr
     const PartDesc D = descs[it.member];
     const PartSlots S = slots[it.member];
     const int16_t *const *ends = sc + 2 * ((size_t)task * nparts + it.member);
+    // rowp (MODE 1; nullptr: no rows): [ntasks][nparts], the task's row of the member's store or nullptr.  The guard above
+    // lets a task through once, so its row is written exactly once -- from the slot, the counters and the result alone
+    double *row = (MODE == 1 && rowp) ? rowp[(size_t)task * nparts + it.member] : nullptr;
     part_item_sums<MODE>(D, it, S.theta + (size_t)task * S.stride, ends[0], ends[1], x, smem,
-                         partials + 2 * ((size_t)task * gridDim.x + blockIdx.x));
+                         partials + 2 * ((size_t)task * gridDim.x + blockIdx.x), row);
 }
 
 // The update of one solve, run by one workgroup of kPartUpdateThreads: 64 members at a time, thread t sums the items of
@@ -296,11 +309,12 @@ hipError_t launch_part_lnl_finish(hipStream_t s, const PartDesc *d_desc, int npa
 
 hipError_t launch_part_derv_batch(hipStream_t s, int mode, const PartDesc *d_desc, const PartItem *d_items, int nitems,
                                   int lds_doubles, const PartSlots *d_slots, const int16_t *const *d_sc, int nparts,
-                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials) {
+                                  const NewtonState *states, const int32_t *lnl_written, int ntasks, double *partials,
+                                  double *const *d_rowp) {
     const size_t lds = (size_t)(lds_doubles + 8) * sizeof(double);
     const dim3 grid((unsigned)nitems, (unsigned)ntasks);
-    if (mode == 0) hipLaunchKernelGGL(k_part_derv_batch<0>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials);
-    else hipLaunchKernelGGL(k_part_derv_batch<1>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials);
+    if (mode == 0) hipLaunchKernelGGL(k_part_derv_batch<0>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials, nullptr);
+    else hipLaunchKernelGGL(k_part_derv_batch<1>, grid, dim3(256), lds, s, d_desc, d_items, d_slots, d_sc, nparts, states, lnl_written, partials, d_rowp);
     return hipGetLastError();
 }
 

@@ -7,12 +7,14 @@
 //       s, so a wave's loads are coalesced; the entry descriptors are wave-uniform reads.  The replaced slots are counted
 //       per workgroup (integer LDS tree) and added with ONE integer atomic per workgroup; the minimum of boot_orig_logl
 //       over the replicates that hold a tree goes to wgmin[workgroup], folded by the host in workgroup order.  No
-//       floating-point atomic: the same bits on every run.
+//       floating-point atomic: the same bits on every run.  The state, the rule and the fold are ufboot_rule.h's, shared
+//       with the partition group's update (kernels_partboot.hip).
 // The file is built with -ffp-contract=off (Makefile): every comparison sees the bits a plain IEEE restatement sees.
 #include <float.h>
 #include <hip/hip_runtime.h>
 
 #include "iqhip_internal.h"
+#include "ufboot_rule.h"
 
 #pragma clang fp contract(off)
 
@@ -24,49 +26,17 @@ __global__ __launch_bounds__(256) void k_ufboot_update(const double *__restrict_
                                                        double *__restrict__ boot_logl, double *__restrict__ boot_orig_logl,
                                                        int32_t *__restrict__ boot_counts, int64_t *__restrict__ boot_tree,
                                                        unsigned long long *__restrict__ replaced, double *__restrict__ wgmin) {
-    __shared__ int s_cnt[256];
-    __shared__ double s_min[256];
     const int s = blockIdx.x * 256 + threadIdx.x;
     int nrep = 0;
     double mn = DBL_MAX;
     if (s < S) {
-        double bl = boot_logl[s], bo = boot_orig_logl[s];
-        int32_t bc = boot_counts[s];
-        int64_t bt = boot_tree[s];
-        for (int i = 0; i < n; i++) {
-            const double rell = sums[(size_t)ent[i].row * S + s];
-            bool better = rell > bl + epsilon;
-            if (!better && rell > bl - epsilon) better = (ent[i].rand <= 1.0 / (bc + 1));
-            if (better) {
-                if (rell <= bl + epsilon) bc++;
-                else bc = 1;
-                bl = bl < rell ? rell : bl;   // max(boot_logl, rell)
-                bo = ent[i].logl;
-                bt = ent[i].tree_id;
-                nrep++;
-            }
-        }
-        boot_logl[s] = bl;
-        boot_orig_logl[s] = bo;
-        boot_counts[s] = bc;
-        boot_tree[s] = bt;
-        if (bt >= 0) mn = bo;
+        UfbootSlot z;
+        z.load(boot_logl, boot_orig_logl, boot_counts, boot_tree, s);
+        for (int i = 0; i < n; i++) z.apply(sums[(size_t)ent[i].row * S + s], ent[i], epsilon);
+        mn = z.store(boot_logl, boot_orig_logl, boot_counts, boot_tree, s);
+        nrep = z.nrep;
     }
-    s_cnt[threadIdx.x] = nrep;
-    s_min[threadIdx.x] = mn;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + o];
-            const double other = s_min[threadIdx.x + o];
-            if (other < s_min[threadIdx.x]) s_min[threadIdx.x] = other;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        if (s_cnt[0] > 0) atomicAdd(replaced, (unsigned long long)s_cnt[0]);
-        wgmin[blockIdx.x] = s_min[0];
-    }
+    ufboot_fold(nrep, mn, replaced, wgmin);
 }
 
 int ufboot_workgroups(int nsamples) { return (nsamples + 255) / 256; }

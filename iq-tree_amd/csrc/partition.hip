@@ -1,7 +1,8 @@
 // partition.hip -- host side of the edge-linked partition model (-q / -spp): a group of existing single-device engines,
 // one per partition, and the calls that span them (include/iqhip.h, "Edge-linked partition models").  The kernels are in
 // kernels_partnewton.hip.  The group owns a stream, a device-resident NewtonState, the descriptor table of its members and
-// the work-item slots; it owns nothing of the members.
+// the work-item slots; it owns nothing of the members.  At the end of the file: the group's per-pattern rows, RELL sums and
+// UFBoot state ("UFBoot on edge-linked partition models"; kernels in kernels_partboot.hip).
 //
 // Descriptors: re-filled from the members' engine fields on EVERY call (a few hundred bytes per member) and uploaded only
 // when the bytes differ from what the device holds -- so a new model, alignment, theta buffer or rate is picked up without
@@ -9,6 +10,7 @@
 // Streams: every call first makes the group's stream wait for an event recorded on each member's stream (the thetas and
 // vectors the group reads are complete), and after its last launch makes every member's stream wait for an event of the
 // group's stream (no member overwrites theta while the group still reads it).  The host waits once, for the group's stream.
+#include <float.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,7 +43,7 @@ struct iqhip_partition {
     DevBuf<double> d_partials;       // [nitems][2]
     // iqhip_partition_optimize_branch_batch, per chunk of tasks
     PairBuf<NewtonState> bstate;     // [tasks]
-    PairBuf<char> btable;            // [nparts] PartSlots ++ [tasks][nparts][2] scale-counter pointers
+    PairBuf<char> btable;            // [nparts] PartSlots ++ [tasks][nparts][2] scale-counter pointers ++ [tasks][nparts] row pointers
     PairBuf<double> bout;            // [tasks][nparts]
     DevBuf<double> d_bpartials;      // [tasks][nitems][2]
     DevBuf<int32_t> d_blnl;          // [tasks]: the task's lnL sums are in d_bpartials
@@ -50,6 +52,20 @@ struct iqhip_partition {
     std::vector<hipEvent_t> tev;
     double ms[2] = {0.0, 0.0};
     int64_t launches = 0;
+    // RELL sums and UFBoot bookkeeping of the group (iqhip_partition_ptnlh_rell, iqhip_partition_ufboot_*): the engine's ufb
+    // state, owned by the group; sums: the device table of the members' bt.sums pointers; rell: the summed matrix of
+    // iqhip_partition_ptnlh_rell; gen: every member's sample-matrix generation at init.  nsamples == 0: no state
+    struct {
+        DevBuf<double> dbl, res, rell;
+        DevBuf<int64_t> tree;
+        DevBuf<int32_t> counts;
+        DevBuf<iqhip_ufboot_tree> entries;
+        PairBuf<const double *> sums;
+        std::vector<uint64_t> gen;
+        int nsamples = 0;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_partition_ufboot_timing: the members' products, the update kernels
+        int64_t launches = 0;
+    } ufb;
 };
 
 namespace {
@@ -177,6 +193,16 @@ int use_group(iqhip_partition *g, const char *what) {
     const int rc = members_ok(g);
     if (rc) return rc;
     HIPCHK(hipSetDevice(g->device));
+    return IQHIP_OK;
+}
+
+// every row of a list lies inside every member's store: row r of the group is row r of each member
+int group_rows_ok(const iqhip_partition *g, const char *what, const int32_t *rows, int nrows) {
+    for (int p = 0; p < g->nparts; p++)
+        for (int i = 0; i < nrows; i++)
+            if (rows[i] < 0 || rows[i] >= g->m[p]->ptnlh_rows)
+                return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store of member " + std::to_string(p) +
+                                                   " (iqhip_partition_ptnlh_reserve)");
     return IQHIP_OK;
 }
 
@@ -462,8 +488,9 @@ int batch_tasks_per_chunk(const iqhip_partition *g, int ntasks) {
 
 // one chunk of m tasks: node updates and theta slots on the members' streams, the chain of joint solves on the group's
 // ops[0 .. total_ops): the tasks' node updates in task order, seg_of[t] of them task t's
+// rows (nullptr: none): per task the row of every member's store that takes its per-pattern values (< 0: none), all checked
 int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, const iqhip_node_op *ops, int total_ops,
-                    const int *seg_of, iqhip_branch_result *results, double *part_lnl) {
+                    const int *seg_of, iqhip_branch_result *results, double *part_lnl, const int32_t *rows) {
     const int P = g->nparts;
     const std::vector<int> segs(seg_of, seg_of + m);
     int rc = IQHIP_OK;
@@ -475,7 +502,8 @@ int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, c
         max_steps = std::max(max_steps, k.max_steps);
     }
     const size_t bytes_slots = sizeof(PartSlots) * (size_t)P;
-    const size_t bytes_table = bytes_slots + sizeof(const int16_t *) * 2 * (size_t)m * P;
+    const size_t bytes_sc = sizeof(const int16_t *) * 2 * (size_t)m * P;
+    const size_t bytes_table = bytes_slots + bytes_sc + (rows ? sizeof(double *) * (size_t)m * P : 0);
     HIPCHK(hipSetDevice(g->device));
     HIPCHK(g->bstate.ensure(g->stream, (size_t)m));
     HIPCHK(g->btable.ensure(g->stream, bytes_table));
@@ -484,6 +512,7 @@ int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, c
     HIPCHK(g->d_blnl.ensure(g->stream, (size_t)m));
     PartSlots *slots = reinterpret_cast<PartSlots *>(g->btable.h.p);
     const int16_t **sc = reinterpret_cast<const int16_t **>(g->btable.h.p + bytes_slots);
+    double **rowp = reinterpret_cast<double **>(g->btable.h.p + bytes_slots + bytes_sc);
     std::vector<iqhip_node_op> mine(ops, ops + total_ops);
     const iqhip_branch_end none = {0, -1, 0};
     for (int p = 0; p < P; p++) {
@@ -504,6 +533,7 @@ int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, c
         for (int t = 0; t < m; t++) {
             rc = branch_scale_counters(e, tasks[t].a, tasks[t].b, sc + 2 * ((size_t)t * P + p));
             if (rc) return rc;
+            if (rows) rowp[(size_t)t * P + p] = rows[t] >= 0 ? e->d_ptnlh.p + (size_t)rows[t] * e->nptn_pad : nullptr;
         }
     }
     HIPCHK(hipSetDevice(g->device));
@@ -515,11 +545,12 @@ int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, c
     HIPCHK(hipMemsetAsync(g->d_blnl.p, 0, sizeof(int32_t) * (size_t)m, g->stream));
     const PartSlots *d_slots = reinterpret_cast<const PartSlots *>(g->btable.d.p);
     const int16_t *const *d_sc = reinterpret_cast<const int16_t *const *>(g->btable.d.p + bytes_slots);
+    double *const *d_rowp = rows ? reinterpret_cast<double *const *>(g->btable.d.p + bytes_slots + bytes_sc) : nullptr;
     const bool timing = g->m[0]->timing;
     size_t nev = 0;
     const auto derv = [&](int mode) {
         return launch_part_derv_batch(g->stream, mode, d_desc(g), d_items(g), g->nitems, g->lds_doubles, d_slots, d_sc, P,
-                                      g->bstate.d.p, g->d_blnl.p, m, g->d_bpartials.p);
+                                      g->bstate.d.p, g->d_blnl.p, m, g->d_bpartials.p, mode == 1 ? d_rowp : nullptr);
     };
     for (int enq = 0;;) {
         const int chunk = steps_per_chunk(enq, max_steps);
@@ -563,7 +594,12 @@ int batch_run_chunk(iqhip_partition *g, const iqhip_branch_task *tasks, int m, c
 
 extern "C" int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const iqhip_branch_task *tasks, int ntasks,
                                                      iqhip_branch_result *results, double *part_lnl) {
-    const char *what = "iqhip_partition_optimize_branch_batch";
+    return iqhip_partition_optimize_branch_batch_rows(g, tasks, ntasks, results, part_lnl, nullptr);
+}
+
+extern "C" int iqhip_partition_optimize_branch_batch_rows(iqhip_partition *g, const iqhip_branch_task *tasks, int ntasks,
+                                                          iqhip_branch_result *results, double *part_lnl, const int32_t *rows) {
+    const char *what = rows ? "iqhip_partition_optimize_branch_batch_rows" : "iqhip_partition_optimize_branch_batch";
     if (!g) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null group");
     if (!tasks || !results || ntasks < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad task array");
     // every task is checked before any member is touched; a chunk takes its slice of the gathered ops
@@ -573,6 +609,17 @@ extern "C" int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const i
     if (rc) return rc;
     rc = use_group(g, what);
     if (rc) return rc;
+    if (rows) {   // inside every member's store, and no row named twice: two tasks' passes would store to it in one launch
+        std::vector<int32_t> named;
+        for (int t = 0; t < ntasks; t++)
+            if (rows[t] >= 0) {
+                if ((rc = group_rows_ok(g, what, rows + t, 1))) return rc;
+                named.push_back(rows[t]);
+            }
+        std::sort(named.begin(), named.end());
+        if (std::adjacent_find(named.begin(), named.end()) != named.end())
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": two tasks name the same row");
+    }
     g->launches = 0;
     if (g->m[0]->timing) g->ms[0] = g->ms[1] = 0.0;
     rc = refresh_table(g);
@@ -584,7 +631,7 @@ extern "C" int iqhip_partition_optimize_branch_batch(iqhip_partition *g, const i
         size_t nops = 0;
         for (int t = 0; t < m; t++) nops += (size_t)segs[first + t];
         rc = batch_run_chunk(g, tasks + first, m, ops.data() + op_first, (int)nops, segs.data() + first, results + first,
-                             part_lnl ? part_lnl + (size_t)first * g->nparts : nullptr);
+                             part_lnl ? part_lnl + (size_t)first * g->nparts : nullptr, rows ? rows + first : nullptr);
         op_first += nops;
         // (whatever happened: the members wait for what the group did enqueue, and no slot is rewritten under it)
         const int rc2 = members_wait(g);
@@ -598,5 +645,288 @@ extern "C" int iqhip_debug_partition_timing(iqhip_partition *g, double *ms, int6
     if (!g) return fail(IQHIP_ERR_INVALID, "iqhip_debug_partition_timing: null group");
     if (ms) { ms[0] = g->ms[0]; ms[1] = g->ms[1]; }
     if (launches) *launches = g->launches;
+    return IQHIP_OK;
+}
+
+// ---- per-pattern rows, RELL sums and UFBoot on the group (include/iqhip.h, "UFBoot on edge-linked partition models") --------
+// Every member forms its own product R_p = L_p W_p^T on its own stream (launch_alrt_product, its own K-split); the group's
+// stream waits for them by events, adds them in member order (kernels_partboot.hip), and the members wait for the group
+// before their bt.sums are overwritten again.
+namespace {
+
+// nsamples replicates exist in every member's sample matrix
+int group_samples_ok(const iqhip_partition *g, const char *what, int nsamples) {
+    if (nsamples < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": nsamples < 1");
+    for (int p = 0; p < g->nparts; p++)
+        if (nsamples > g->m[p]->nboot)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": member " + std::to_string(p) +
+                                               (g->m[p]->nboot == 0 ? " has no bootstrap samples (iqhip_gen_boot_samples / iqhip_set_boot_samples)"
+                                                                    : " holds fewer samples than nsamples"));
+    return IQHIP_OK;
+}
+
+// the state exists and every member's sample matrix is still the one it was initialised on
+int group_ufboot_ready(const iqhip_partition *g, const char *what) {
+    bool ok = g->ufb.nsamples >= 1 && g->ufb.gen.size() == (size_t)g->nparts;
+    for (int p = 0; ok && p < g->nparts; p++) ok = g->ufb.gen[p] == g->m[p]->boot_generation && g->ufb.nsamples <= g->m[p]->nboot;
+    if (!ok)
+        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_partition_ufboot_init first (again after a member's sample matrix was replaced)");
+    return IQHIP_OK;
+}
+
+// every member's product buffers sized for M distinct rows (so that the pointers stay put over the chunks of a call), and the
+// table of their bt.sums uploaded on the group's stream
+int group_sums_table(iqhip_partition *g, const std::vector<int> &ksplit, size_t M, size_t S) {
+    const int P = g->nparts;
+    HIPCHK(g->ufb.sums.ensure(g->stream, (size_t)P));
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        HIPCHK(e->bt.part.ensure(e, M * S * ksplit[p]));
+        HIPCHK(e->bt.sums.ensure(e, M * S));
+        g->ufb.sums.h.p[p] = e->bt.sums.p;
+    }
+    HIPCHK(hipMemcpyAsync(g->ufb.sums.d.p, g->ufb.sums.h.p, sizeof(const double *) * (size_t)P, hipMemcpyHostToDevice, g->stream));
+    return IQHIP_OK;
+}
+
+// a pair of events around something enqueued on a stream, while timing is enabled; read once everything has drained
+struct SpanTimer {
+    explicit SpanTimer(bool on_) : on(on_) {}
+    SpanTimer(const SpanTimer &) = delete; SpanTimer &operator=(const SpanTimer &) = delete;
+    ~SpanTimer() { for (hipEvent_t x : ev) hipEventDestroy(x); }
+    void mark(hipStream_t s) {
+        hipEvent_t x = nullptr;
+        if (!on || !(on = hipEventCreate(&x) == hipSuccess)) return;
+        ev.push_back(x);
+        on = hipEventRecord(x, s) == hipSuccess;
+    }
+    double read() {   // the summed time between marks 2k and 2k + 1
+        double sum = 0.0;
+        if (!on || ev.size() % 2) return 0.0;
+        for (size_t k = 0; k < ev.size(); k += 2) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, ev[k], ev[k + 1]) != hipSuccess) return 0.0;
+            sum += t;
+        }
+        return sum;
+    }
+    bool on;
+    std::vector<hipEvent_t> ev;
+};
+
+// one chunk's products: the list staged and multiplied on every member's stream
+int group_products(iqhip_partition *g, const RowList &rl, const std::vector<int> &ksplit, int S, SpanTimer &timer) {
+    for (int p = 0; p < g->nparts; p++) {
+        iqhip_engine *e = g->m[p];
+        const int rc = bt_stage(e, rl, ksplit[p], (size_t)S);
+        if (rc) return rc;
+        timer.mark(e->stream);
+        HIPCHK(launch_alrt_product(e, e->bt.rows.p, rl.M, S, ksplit[p], e->bt.part.p, e->bt.sums.p));
+        timer.mark(e->stream);
+    }
+    return IQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int iqhip_partition_ptnlh_reserve(iqhip_partition *g, int nrows) {
+    int rc = use_group(g, "iqhip_partition_ptnlh_reserve");
+    if (rc) return rc;
+    if (nrows < 0 || nrows > (1 << 20)) return fail(IQHIP_ERR_INVALID, "iqhip_partition_ptnlh_reserve: bad row count");
+    for (int p = 0; p < g->nparts; p++)
+        if ((rc = iqhip_ptnlh_reserve(g->m[p], nrows))) return rc;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_ptnlh_rell(iqhip_partition *g, const int32_t *rows, int nrows, int nsamples, double *out) {
+    const char *what = "iqhip_partition_ptnlh_rell";
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    if (!rows || !out || nrows < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad row list");
+    if ((rc = group_samples_ok(g, what, nsamples))) return rc;
+    if ((rc = group_rows_ok(g, what, rows, nrows))) return rc;
+    const int P = g->nparts;
+    const RowList rl = row_list(rows, nrows);
+    const size_t count = (size_t)rl.M * nsamples;
+    std::vector<int> ksplit((size_t)P);
+    for (int p = 0; p < P; p++) ksplit[p] = alrt_ksplit(g->m[p], rl.M, nsamples);
+    HIPCHK(g->ufb.rell.ensure(g->stream, count));
+    rc = group_sums_table(g, ksplit, (size_t)rl.M, (size_t)nsamples);
+    if (rc) return rc;
+    SpanTimer timer(false);
+    rc = group_products(g, rl, ksplit, nsamples, timer);
+    std::vector<double> sums(count);
+    if (!rc) rc = wait_for_members(g);
+    hipError_t s = hipSuccess;
+    if (!rc) s = launch_part_rell_sum(g->stream, g->ufb.sums.d.p, P, count, g->ufb.rell.p);
+    if (!rc && s == hipSuccess)
+        s = hipMemcpyAsync(sums.data(), g->ufb.rell.p, sizeof(double) * count, hipMemcpyDeviceToHost, g->stream);
+    const int rc2 = members_wait(g);
+    const hipError_t drained = hipStreamSynchronize(g->stream);
+    if (rc) return rc;
+    HIPCHK(s);
+    if (rc2) return rc2;
+    HIPCHK(drained);
+    const int32_t *idx = rl.list.data() + rl.M;
+    for (int i = 0; i < nrows; i++)
+        memcpy(out + (size_t)i * nsamples, sums.data() + (size_t)idx[i] * nsamples, sizeof(double) * (size_t)nsamples);
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_ufboot_init(iqhip_partition *g, int nsamples) {
+    const char *what = "iqhip_partition_ufboot_init";
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    if ((rc = group_samples_ok(g, what, nsamples))) return rc;
+    const size_t S = (size_t)nsamples;
+    g->ufb.nsamples = 0;
+    HIPCHK(g->ufb.dbl.ensure(g->stream, 2 * S));
+    HIPCHK(g->ufb.tree.ensure(g->stream, S));
+    HIPCHK(g->ufb.counts.ensure(g->stream, S));
+    HIPCHK(g->ufb.res.ensure(g->stream, 1 + (size_t)ufboot_workgroups(nsamples)));
+    // iqtree.cpp:308-312, the starting values of iqhip_ufboot_init
+    std::vector<double> lo(2 * S, -DBL_MAX);
+    std::vector<int64_t> none(S, -1);
+    HIPCHK(hipStreamSynchronize(g->stream));   // (pageable sources)
+    HIPCHK(hipMemcpyAsync(g->ufb.dbl.p, lo.data(), sizeof(double) * lo.size(), hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->ufb.tree.p, none.data(), sizeof(int64_t) * S, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemsetAsync(g->ufb.counts.p, 0, sizeof(int32_t) * S, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    g->ufb.gen.resize((size_t)g->nparts);
+    for (int p = 0; p < g->nparts; p++) g->ufb.gen[p] = g->m[p]->boot_generation;
+    g->ufb.nsamples = nsamples;
+    g->ufb.ms[0] = g->ufb.ms[1] = 0.0;
+    g->ufb.launches = 0;
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_ufboot_update(iqhip_partition *g, const iqhip_ufboot_tree *trees, int ntrees, double epsilon,
+                                             double logl_cutoff, int64_t *counts, double *min_orig_logl) {
+    const char *what = "iqhip_partition_ufboot_update";
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    if (!trees || ntrees < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad tree list");
+    if (!(epsilon >= 0.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": epsilon must be >= 0");
+    if ((rc = group_ufboot_ready(g, what))) return rc;
+    for (int i = 0; i < ntrees; i++) {
+        const iqhip_ufboot_tree &t = trees[i];
+        if ((rc = group_rows_ok(g, what, &t.row, 1))) return rc;
+        if (t.tree_id < 0) return fail(IQHIP_ERR_INVALID, std::string(what) + ": tree_id must be >= 0");
+        if (!(t.rand >= 0.0 && t.rand <= 1.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": rand outside [0, 1]");
+        if (!std::isfinite(t.logl)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": log-likelihoods must be finite");
+    }
+    // iqtree.cpp:2678
+    std::vector<iqhip_ufboot_tree> ent;
+    ent.reserve((size_t)ntrees);
+    for (int i = 0; i < ntrees; i++)
+        if (!(logl_cutoff != 0.0 && trees[i].logl < logl_cutoff - 1.0)) ent.push_back(trees[i]);
+    const int n = (int)ent.size(), S = g->ufb.nsamples, P = g->nparts;
+    // entries per chunk: all members' part [ksplit][M][S] and sums [M][S] of M <= chunk distinct rows together within 256 MB.
+    // A member's K-split follows from nsamples, its pattern count and the CU count alone, so a (row, replicate) sum has the
+    // same bits whatever the chunk
+    std::vector<int> ksplit((size_t)P);
+    int64_t per_entry = 0;
+    for (int p = 0; p < P; p++) {
+        ksplit[p] = alrt_ksplit(g->m[p], 1, S);
+        per_entry += (int64_t)sizeof(double) * S * (ksplit[p] + 1);
+    }
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / per_entry);
+    if (const char *uc = getenv("IQHIP_UFBOOT_CHUNK")) chunk = std::max(1, atoi(uc));
+    chunk = std::min<int64_t>(chunk, std::max(n, 1));
+    // every chunk's row list, and the entries with `row` rewritten to the row of their chunk's sums
+    std::vector<RowList> lists;
+    std::vector<int32_t> rows((size_t)chunk);
+    size_t maxM = 1;
+    for (int first = 0; first < n; first += (int)chunk) {
+        const int m = (int)std::min<int64_t>(chunk, n - first);
+        for (int i = 0; i < m; i++) rows[i] = ent[first + i].row;
+        lists.push_back(row_list(rows.data(), m));
+        const int32_t *idx = lists.back().list.data() + lists.back().M;
+        for (int i = 0; i < m; i++) ent[first + i].row = idx[i];
+        maxM = std::max(maxM, (size_t)lists.back().M);
+    }
+    const size_t nwg = (size_t)ufboot_workgroups(S);
+    HIPCHK(g->ufb.entries.ensure(g->stream, (size_t)std::max(n, 1)));
+    HIPCHK(g->ufb.res.ensure(g->stream, 1 + nwg));
+    HIPCHK(hipStreamSynchronize(g->stream));   // (pageable source, and an earlier launch may still read the entries)
+    if (n > 0)
+        HIPCHK(hipMemcpyAsync(g->ufb.entries.p, ent.data(), sizeof(iqhip_ufboot_tree) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+    HIPCHK(hipMemsetAsync(g->ufb.res.p, 0, sizeof(double), g->stream));
+    rc = group_sums_table(g, ksplit, maxM, (size_t)S);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    unsigned long long *d_replaced = reinterpret_cast<unsigned long long *>(g->ufb.res.p);
+    double *boot_logl = g->ufb.dbl.p, *boot_orig = g->ufb.dbl.p + S;
+    const bool timing = g->m[0]->timing;
+    SpanTimer t_prod(timing), t_upd(timing);
+    int64_t launches = 0;
+    hipError_t s = hipSuccess;
+    if (n == 0) {   // everything fell to the cutoff: the state is only read for its minimum
+        s = launch_part_ufboot_update(g->stream, g->ufb.sums.d.p, P, S, g->ufb.entries.p, 0, epsilon, boot_logl, boot_orig,
+                                      g->ufb.counts.p, g->ufb.tree.p, d_replaced, g->ufb.res.p + 1);
+        launches = 1;
+    }
+    for (size_t c = 0, first = 0; c < lists.size() && s == hipSuccess && rc == IQHIP_OK; c++) {
+        const RowList &rl = lists[c];
+        const int m = (int)(rl.list.size() - (size_t)rl.M);
+        // (a member's stream waits for the update of the chunk before: its sums are not overwritten under it)
+        if ((rc = group_products(g, rl, ksplit, S, t_prod))) break;
+        if ((rc = wait_for_members(g))) break;
+        t_upd.mark(g->stream);
+        s = launch_part_ufboot_update(g->stream, g->ufb.sums.d.p, P, S, g->ufb.entries.p + first, m, epsilon, boot_logl, boot_orig,
+                                      g->ufb.counts.p, g->ufb.tree.p, d_replaced, g->ufb.res.p + 1);
+        t_upd.mark(g->stream);
+        const int rc2 = members_wait(g);
+        if (!rc) rc = rc2;
+        launches += 2 * P + 1;
+        first += (size_t)m;
+    }
+    std::vector<double> res(1 + nwg);
+    if (s == hipSuccess && rc == IQHIP_OK)
+        s = hipMemcpyAsync(res.data(), g->ufb.res.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, g->stream);
+    const hipError_t drained = hipStreamSynchronize(g->stream);
+    if (s == hipSuccess) s = drained;
+    if (rc) return rc;
+    HIPCHK(s);
+    g->ufb.ms[0] = t_prod.read();
+    g->ufb.ms[1] = t_upd.read();
+    g->ufb.launches = launches;
+    if (counts) {
+        unsigned long long replaced;
+        memcpy(&replaced, &res[0], sizeof(replaced));
+        counts[0] = n;
+        counts[1] = ntrees - n;
+        counts[2] = (int64_t)replaced;
+    }
+    if (min_orig_logl) {   // the workgroups' minima in workgroup order
+        double mn = DBL_MAX;
+        for (size_t w = 0; w < nwg; w++)
+            if (res[1 + w] < mn) mn = res[1 + w];
+        *min_orig_logl = mn;
+    }
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_partition_ufboot_fetch(iqhip_partition *g, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts,
+                                            int64_t *boot_tree) {
+    const char *what = "iqhip_partition_ufboot_fetch";
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    if ((rc = group_ufboot_ready(g, what))) return rc;
+    const size_t S = (size_t)g->ufb.nsamples;
+    if (boot_logl) HIPCHK(hipMemcpyAsync(boot_logl, g->ufb.dbl.p, sizeof(double) * S, hipMemcpyDeviceToHost, g->stream));
+    if (boot_orig_logl) HIPCHK(hipMemcpyAsync(boot_orig_logl, g->ufb.dbl.p + S, sizeof(double) * S, hipMemcpyDeviceToHost, g->stream));
+    if (boot_counts) HIPCHK(hipMemcpyAsync(boot_counts, g->ufb.counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, g->stream));
+    if (boot_tree) HIPCHK(hipMemcpyAsync(boot_tree, g->ufb.tree.p, sizeof(int64_t) * S, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return IQHIP_OK;
+}
+
+extern "C" int iqhip_debug_partition_ufboot_timing(iqhip_partition *g, double *ms, int64_t *launches) {
+    if (!g) return fail(IQHIP_ERR_INVALID, "iqhip_debug_partition_ufboot_timing: null group");
+    if (!ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_partition_ufboot_timing: null argument");
+    ms[0] = g->ufb.ms[0];
+    ms[1] = g->ufb.ms[1];
+    if (launches) *launches = g->ufb.launches;
     return IQHIP_OK;
 }

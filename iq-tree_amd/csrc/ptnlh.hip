@@ -67,6 +67,7 @@ static hipError_t boot_matrix(iqhip_engine *e, int nsamples) {
     e->d_boot.reset();
     e->nboot = 0;
     e->ufb.nsamples = 0;   // (the UFBoot state belongs to the matrix it was initialised on)
+    e->boot_generation++;
     if (nsamples == 0) return hipSuccess;
     if ((s = e->d_boot.ensure(e, (size_t)e->nptn_pad * nsamples)) == hipSuccess) e->nboot = nsamples;
     return s;
@@ -169,12 +170,7 @@ extern "C" int iqhip_ptnlh_fetch(iqhip_engine *e, int row, double *out) {
     return IQHIP_OK;
 }
 
-// the distinct rows of a row list in first-appearance order (list[0, M)) and, behind them, every entry's index into them
-struct RowList {
-    std::vector<int32_t> list;
-    int M;
-};
-static RowList row_list(const int32_t *rows, int nrows) {
+RowList iqhip::row_list(const int32_t *rows, int nrows) {
     RowList rl;
     std::vector<int32_t> idx((size_t)nrows);
     std::unordered_map<int32_t, int32_t> seen;
@@ -189,7 +185,7 @@ static RowList row_list(const int32_t *rows, int nrows) {
 }
 
 // the list into bt.rows; bt.part and bt.sums sized for products of its distinct rows with nsamples replicates
-static int bt_stage(iqhip_engine *e, const RowList &rl, int ksplit, size_t nsamples) {
+int iqhip::bt_stage(iqhip_engine *e, const RowList &rl, int ksplit, size_t nsamples) {
     const size_t sums = (size_t)rl.M * nsamples;
     HIPCHK(e->bt.rows.ensure(e, rl.list.size()));
     HIPCHK(e->bt.part.ensure(e, sums * ksplit));
@@ -318,6 +314,7 @@ extern "C" int iqhip_gen_boot_samples(iqhip_engine *e, int nsamples, int64_t fir
     rc = topo_freq_prefix(e, "iqhip_gen_boot_samples");
     if (rc) return rc;
     e->ufb.nsamples = 0;   // (new content, even where the matrix keeps its size)
+    e->boot_generation++;
     rc = topo_boot_rows(e, nsamples, true);
     if (rc) return rc;
     HIPCHK(launch_topo_gen(e, nsamples, first_replicate, ndraws, topo_stream_key(seed, stream)));
@@ -507,6 +504,7 @@ extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntr
     if (const char *bc = getenv("IQHIP_BOOT_CHUNK")) chunk = std::max(1, std::min(16384, atoi(bc)));
     chunk = std::min<int64_t>(chunk, nsamples);
     e->ufb.nsamples = 0;   // (the matrix is overwritten chunk by chunk)
+    e->boot_generation++;
     rc = topo_boot_rows(e, (int)chunk, false);
     if (rc) return rc;
     const size_t ncount = (size_t)nscales * ntrees;

@@ -1503,10 +1503,16 @@ int iqhost_super_restore_branch_lengths(void *h, const double *in, int n) {
     IQHOST_TRY(((PhyloSuperTree *)h)->restoreBranchLengths(std::vector<double>(in, in + n)));
 }
 int iqhost_super_clear_all_partial_lh(void *h) { IQHOST_TRY(((PhyloSuperTree *)h)->clearAllPartialLH()); }
-int iqhost_super_nni_for_branch(void *h, int a, int b, int nni5, double *out) {
+int iqhost_super_gen_boot_samples(void *h, int nsamples, uint64_t seed) {
+    IQHOST_TRY(((PhyloSuperTree *)h)->genBootSamples(nsamples, seed));
+}
+// first_row >= 0: the two neighbours' per-pattern values go to rows first_row, first_row + 1 of every member's store
+int iqhost_super_nni_for_branch_rows(void *h, int a, int b, int nni5, int first_row, double *out) {
     IQHOST_TRY({
         PhyloTree::NNIMove mv[2];
-        ((PhyloSuperTree *)h)->getBestNNIForBran(a, b, nni5 != 0, mv);
+        const int rows[2] = {first_row, first_row + 1};
+        if (first_row >= 0) ((PhyloSuperTree *)h)->reservePtnlhRows(first_row + 2);
+        ((PhyloSuperTree *)h)->getBestNNIForBran(a, b, nni5 != 0, mv, first_row >= 0 ? rows : nullptr);
         for (int c = 0; c < 2; c++) {
             out[c * 8 + 0] = mv[c].newloglh;
             out[c * 8 + 1] = mv[c].node1_nei;
@@ -1515,13 +1521,28 @@ int iqhost_super_nni_for_branch(void *h, int a, int b, int nni5, double *out) {
         }
     });
 }
-int iqhost_super_evaluate_nnis_list(void *h, int nni5, const int *branches, int nbranches, int *ids, double *vals, int cap, int *n) {
+// ... without rows
+int iqhost_super_nni_for_branch(void *h, int a, int b, int nni5, double *out) {
+    return iqhost_super_nni_for_branch_rows(h, a, b, nni5, -1, out);
+}
+// first_row >= 0 (nni5 only): candidate k's per-pattern values go to row first_row + k of every member's store
+int iqhost_super_evaluate_nnis_list_rows(void *h, int nni5, const int *branches, int nbranches, int first_row, int *ids,
+                                         double *vals, int cap, int *n) {
     IQHOST_TRY({
         PhyloSuperTree *t = (PhyloSuperTree *)h;
         PhyloTree::BranchList list;
         for (int q = 0; branches && q < nbranches; q++) list.push_back({branches[2 * q], branches[2 * q + 1]});
         std::vector<PhyloTree::NNIMove> mv;
-        if (nni5) t->evaluateNNIs5Batch(mv, branches ? &list : nullptr);
+        if (first_row >= 0 && !nni5) throw std::runtime_error("per-pattern rows need the nni5 evaluation");
+        if (first_row >= 0) {
+            std::vector<PhyloNode *> n1, n2;
+            t->super.internalBranches(n1, n2);
+            const size_t nc = 2 * (branches ? list.size() : n1.size());
+            std::vector<int> rows(nc);
+            for (size_t k = 0; k < nc; k++) rows[k] = first_row + (int)k;
+            t->reservePtnlhRows(first_row + (int)nc);
+            t->evaluateNNIs5Batch(mv, rows.data(), branches ? &list : nullptr);
+        } else if (nni5) t->evaluateNNIs5Batch(mv, branches ? &list : nullptr);
         else t->evaluateNNIsBatch(mv, branches ? &list : nullptr);
         if ((int)mv.size() > cap) throw std::runtime_error("output too small");
         *n = (int)mv.size();
@@ -1533,6 +1554,11 @@ int iqhost_super_evaluate_nnis_list(void *h, int nni5, const int *branches, int 
             vals[w * k + w - 1] = mv[k].newloglh;
         }
     });
+}
+
+// ... without rows
+int iqhost_super_evaluate_nnis_list(void *h, int nni5, const int *branches, int nbranches, int *ids, double *vals, int cap, int *n) {
+    return iqhost_super_evaluate_nnis_list_rows(h, nni5, branches, nbranches, -1, ids, vals, cap, n);
 }
 
 }  // extern "C"

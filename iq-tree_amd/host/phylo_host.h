@@ -221,8 +221,19 @@ public:
         virtual ~NNIBackend() {}
         // every directed vector valid (all), or the four around each listed branch; the tree's keys and next_key in step
         virtual void pendingVectors(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2, bool all) = 0;
-        virtual void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) = 0;
-        virtual void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2]) = 0;   // the branch-by-branch path
+        // rows (or nullptr): per task the row of the backend's per-pattern stores that takes its values (< 0: none)
+        virtual void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res,
+                                 const int32_t *rows) = 0;
+        // the branch-by-branch path; ptnlh_rows (or nullptr): the store rows of the two neighbours
+        virtual void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2], const int *ptnlh_rows) = 0;
+        // the device side of the UFBoot bookkeeping below, for the tree without an engine: the state, the store rows and
+        // the sample matrices are the backend's
+        virtual void ufbootInit(int nsamples) = 0;
+        virtual void ufbootReserveRows(int nrows) = 0;
+        virtual void ufbootPutCurrentRow(int row) = 0;   // the current tree's per-pattern values into `row`
+        virtual void ufbootUpdate(const iqhip_ufboot_tree *ent, int n, double epsilon, double logl_cutoff, int64_t counts[3],
+                                  double *min_orig_logl) = 0;
+        virtual void ufbootFetchTrees(int64_t *boot_tree) = 0;
     };
     NNIBackend *nni_backend = nullptr;
     // the internal branches in the order both NNI evaluations list them (node1->id < node2->id)
@@ -588,6 +599,7 @@ private:
     void finishParsimonyTree();   // node and branch counts, branch ids in traversal order
     void renumberBranches();
     void ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc);
+    void needUFBootDevice(const char *who) const;   // needDevice, or an NNI backend that stands in for the engine
     bool ufbootFeed(std::vector<iqhip_ufboot_tree> &ent, std::vector<int64_t> &boot_tree);
 
     AllReduceHook allreduce_hook = nullptr;

@@ -230,8 +230,7 @@ void PhyloTree::submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, c
     sum_scale.assign(nops, 0.0);
     res.resize(n);
     if (nni_backend) {   // (the backend's lnL carries the scale-factor terms: the per-op sums stay 0)
-        if (rows) throw std::runtime_error("per-pattern rows are not available through an NNI backend");
-        nni_backend->submitTasks(tasks, res);
+        nni_backend->submitTasks(tasks, res, rows);
     } else if (rows)
         check(iqhip_optimize_branch_batch_rows(engine, tasks.data(), (int)n, sum_scale.data(), res.data(), rows),
               "iqhip_optimize_branch_batch_rows");
@@ -248,7 +247,7 @@ void PhyloTree::submitBranchTasks(const std::vector<iqhip_branch_task> &tasks, c
 
 // the fallback of a diverged solve: this tree's own getBestNNIForBran, or the backend's
 void PhyloTree::branchByBranch(PhyloNode *node1, PhyloNode *node2, bool nni5, NNIMove moves[2], const int *ptnlh_rows) {
-    if (nni_backend) nni_backend->bestNNIForBran(node1->id, node2->id, nni5, moves);
+    if (nni_backend) nni_backend->bestNNIForBran(node1->id, node2->id, nni5, moves, ptnlh_rows);
     else getBestNNIForBran(node1, node2, nni5, moves, ptnlh_rows);
 }
 

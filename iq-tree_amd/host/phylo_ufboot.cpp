@@ -49,11 +49,18 @@ double PhyloTree::ufbootRand(uint64_t seed, int64_t tree_id) {
     return (double)(z >> 11) * 0x1.0p-53;
 }
 
+void PhyloTree::needUFBootDevice(const char *who) const {
+    if (!nni_backend) needDevice(who);
+}
+
 void PhyloTree::initUFBoot(int nsamples, uint64_t seed) {
-    needDevice("initUFBoot");
+    needUFBootDevice("initUFBoot");
     noCallerCollective("initUFBoot");
-    pushInputs();
-    check(iqhip_ufboot_init(engine, nsamples), "iqhip_ufboot_init");
+    if (nni_backend) nni_backend->ufbootInit(nsamples);
+    else {
+        pushInputs();
+        check(iqhip_ufboot_init(engine, nsamples), "iqhip_ufboot_init");
+    }
     ufboot_nsamples = nsamples;
     ufboot_seed = seed;
     ufboot_next_id = 0;
@@ -116,20 +123,29 @@ bool PhyloTree::ufbootFeed(std::vector<iqhip_ufboot_tree> &ent, std::vector<int6
         t.tree_id = ufboot_next_id++;
         t.rand = ufbootRand(ufboot_seed, t.tree_id);
     }
-    check(iqhip_ufboot_update(engine, ent.data(), (int)ent.size(), ufboot_epsilon, ufboot_logl_cutoff, ufboot_counts, &ufboot_min_orig_logl),
-          "iqhip_ufboot_update");
+    if (nni_backend)
+        nni_backend->ufbootUpdate(ent.data(), (int)ent.size(), ufboot_epsilon, ufboot_logl_cutoff, ufboot_counts, &ufboot_min_orig_logl);
+    else
+        check(iqhip_ufboot_update(engine, ent.data(), (int)ent.size(), ufboot_epsilon, ufboot_logl_cutoff, ufboot_counts, &ufboot_min_orig_logl),
+              "iqhip_ufboot_update");
     if (ufboot_counts[2] == 0) return false;
     boot_tree.resize((size_t)ufboot_nsamples);
-    check(iqhip_ufboot_fetch(engine, nullptr, nullptr, nullptr, boot_tree.data()), "iqhip_ufboot_fetch");
+    if (nni_backend) nni_backend->ufbootFetchTrees(boot_tree.data());
+    else check(iqhip_ufboot_fetch(engine, nullptr, nullptr, nullptr, boot_tree.data()), "iqhip_ufboot_fetch");
     return true;
 }
 
 void PhyloTree::saveCurrentTree(double logl) {
-    needDevice("saveCurrentTree");
+    needUFBootDevice("saveCurrentTree");
     if (ufboot_nsamples < 1) throw std::runtime_error("saveCurrentTree before initUFBoot");
-    if (!current_it) throw std::runtime_error("saveCurrentTree before computeLikelihood");
-    check(iqhip_ptnlh_reserve(engine, 1), "iqhip_ptnlh_reserve");
-    check(iqhip_ptnlh_put_current(engine, 0, branchEnd(current_it), branchEnd(current_it_back)), "iqhip_ptnlh_put_current");
+    if (nni_backend) {
+        nni_backend->ufbootReserveRows(1);
+        nni_backend->ufbootPutCurrentRow(0);
+    } else {
+        if (!current_it) throw std::runtime_error("saveCurrentTree before computeLikelihood");
+        check(iqhip_ptnlh_reserve(engine, 1), "iqhip_ptnlh_reserve");
+        check(iqhip_ptnlh_put_current(engine, 0, branchEnd(current_it), branchEnd(current_it_back)), "iqhip_ptnlh_put_current");
+    }
     std::vector<iqhip_ufboot_tree> ent(1);   // (row 0)
     ent[0].logl = logl;
     std::vector<int64_t> boot_tree;
@@ -139,14 +155,15 @@ void PhyloTree::saveCurrentTree(double logl) {
 }
 
 void PhyloTree::saveNNITrees() {
-    needDevice("saveNNITrees");
+    needUFBootDevice("saveNNITrees");
     if (ufboot_nsamples < 1) throw std::runtime_error("saveNNITrees before initUFBoot");
     if (lh_mem_save != LM_ALL_BRANCH) throw std::runtime_error("saveNNITrees needs LM_ALL_BRANCH");
     std::vector<PhyloNode *> n1, n2;
     internalBranches(n1, n2);
     const size_t nc = 2 * n1.size();
     if (nc == 0) return;
-    check(iqhip_ptnlh_reserve(engine, (int)(1 + nc)), "iqhip_ptnlh_reserve");
+    if (nni_backend) nni_backend->ufbootReserveRows((int)(1 + nc));
+    else check(iqhip_ptnlh_reserve(engine, (int)(1 + nc)), "iqhip_ptnlh_reserve");
     std::vector<int> rows(nc);
     for (size_t k = 0; k < nc; k++) rows[k] = (int)(1 + k);
     std::vector<NNIMove> moves;
@@ -157,7 +174,7 @@ void PhyloTree::saveNNITrees() {
 }
 
 void PhyloTree::saveNNITrees(const std::vector<NNIMove> &moves) {
-    needDevice("saveNNITrees");
+    needUFBootDevice("saveNNITrees");
     if (ufboot_nsamples < 1) throw std::runtime_error("saveNNITrees before initUFBoot");
     const size_t nc = moves.size();
     if (nc == 0) return;
@@ -180,11 +197,12 @@ void PhyloTree::saveNNITrees(const std::vector<NNIMove> &moves) {
 
 // the winner of every replicate (out.boot_trees, out.distinct_trees) and the split counts of the winners
 void PhyloTree::ufbootWinners(UFBootSummary &out, ufboot::SplitCounts &sc) {
-    needDevice("summarizeBootstrap");
+    needUFBootDevice("summarizeBootstrap");
     if (ufboot_nsamples < 1) throw std::runtime_error("summarizeBootstrap before initUFBoot");
     const size_t S = (size_t)ufboot_nsamples;
     std::vector<int64_t> boot_tree(S);
-    check(iqhip_ufboot_fetch(engine, nullptr, nullptr, nullptr, boot_tree.data()), "iqhip_ufboot_fetch");
+    if (nni_backend) nni_backend->ufbootFetchTrees(boot_tree.data());
+    else check(iqhip_ufboot_fetch(engine, nullptr, nullptr, nullptr, boot_tree.data()), "iqhip_ufboot_fetch");
     out = UFBootSummary();
     sc = ufboot::SplitCounts(leafNum);
     out.boot_trees.resize(S);

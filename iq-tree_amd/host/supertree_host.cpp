@@ -424,7 +424,7 @@ void PhyloSuperTree::clearAllPartialLH() {
     }
 }
 
-PhyloSuperTree::NNIMove PhyloSuperTree::getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2]) {
+PhyloSuperTree::NNIMove PhyloSuperTree::getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2], const int *ptnlh_rows) {
     needGroup();
     if (a < 0 || b < 0 || a >= super.nodeNum || b >= super.nodeNum) throw std::runtime_error("getBestNNIForBran: bad node id");
     PhyloNode *node1 = super.nodes[(size_t)a], *node2 = super.nodes[(size_t)b];
@@ -453,6 +453,10 @@ PhyloSuperTree::NNIMove PhyloSuperTree::getBestNNIForBran(int a, int b, bool nni
         if (nni5)
             for (int y : others(node2, node1)) m.newLen[i++] = optimizeOneBranch(b, y, true, PhyloTree::NNI_MAX_NR_STEP);
         m.newloglh = sumScores();
+        if (ptnlh_rows && ptnlh_rows[cnt] >= 0) {   // computePatternLikelihood(nni.ptnlh), phylosupertreeplen.cpp:1367-1372
+            ufbootPutCurrentRow(ptnlh_rows[cnt]);
+            m.ptnlh_row = ptnlh_rows[cnt];
+        }
         doNNI(m);   // (the same move again restores the tree, neighbour order included; the lengths stay for the second swap)
     }
     restoreBranchLengths(saved);
@@ -495,10 +499,11 @@ void PhyloSuperTree::pendingVectors(const std::vector<PhyloNode *> &n1, const st
     for (PhyloTree *t : parts) t->next_key = std::max(t->next_key, after);
 }
 
-void PhyloSuperTree::submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) {
+void PhyloSuperTree::submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res,
+                                 const int32_t *rows) {
     num_group_batches++;
-    hip(iqhip_partition_optimize_branch_batch(group, tasks.data(), (int)tasks.size(), res.data(), nullptr),
-        "iqhip_partition_optimize_branch_batch");
+    hip(iqhip_partition_optimize_branch_batch_rows(group, tasks.data(), (int)tasks.size(), res.data(), nullptr, rows),
+        "iqhip_partition_optimize_branch_batch_rows");
     for (const iqhip_branch_result &r : res)
         for (PhyloTree *t : parts) t->num_derv_calls += r.nsteps;
 }
@@ -508,9 +513,60 @@ void PhyloSuperTree::evaluateNNIsBatch(std::vector<NNIMove> &moves, const Branch
     super.evaluateNNIsBatch(moves, branches);
 }
 
-void PhyloSuperTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const BranchList *branches) {
+void PhyloSuperTree::evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows, const BranchList *branches) {
     needGroup();
-    super.evaluateNNIs5Batch(moves, nullptr, branches);
+    super.evaluateNNIs5Batch(moves, ptnlh_rows, branches);
+}
+
+// ---- UFBoot on the super tree -------------------------------------------------------------------------------------------------
+void PhyloSuperTree::genBootSamples(int nsamples, uint64_t seed) {
+    needGroup();
+    for (size_t p = 0; p < parts.size(); p++)
+        parts[p]->genBootSamples(nsamples, (int64_t)llround(parts[p]->getAlnNSite()), seed, (uint32_t)p, 0);
+}
+
+void PhyloSuperTree::setBootSamples(int part, const float *samples, int nsamples) {
+    needGroup();
+    if (part < 0 || part >= size()) throw std::runtime_error("PhyloSuperTree::setBootSamples: no such partition");
+    parts[(size_t)part]->setBootSamples(samples, nsamples);
+}
+
+void PhyloSuperTree::reservePtnlhRows(int nrows) {
+    needGroup();
+    hip(iqhip_partition_ptnlh_reserve(group, nrows), "iqhip_partition_ptnlh_reserve");
+}
+
+void PhyloSuperTree::ufbootInit(int nsamples) {
+    needGroup();
+    for (PhyloTree *t : parts) t->pushInputs();
+    hip(iqhip_partition_ufboot_init(group, nsamples), "iqhip_partition_ufboot_init");
+}
+
+void PhyloSuperTree::ufbootPutCurrentRow(int row) {
+    needGroup();
+    // every member's likelihood on its current branch (the branch of the last joint solve or computeLikelihood; any branch
+    // of the tree where there was none), then the pattern values of that evaluation with the scaling events put back
+    for (PhyloTree *t : parts) {
+        if (!t->current_it || !t->current_it_back) {
+            PhyloNode *leaf = t->findFarthestLeaf();
+            t->current_it = leaf->neighbors[0];
+            t->current_it_back = t->current_it->node->findNeighbor(leaf);
+        }
+        t->computeLikelihoodBranch(t->current_it, t->current_it_back->node);
+        hip(iqhip_ptnlh_put_current(t->engine, row, t->branchEnd(t->current_it), t->branchEnd(t->current_it_back)),
+            "iqhip_ptnlh_put_current");
+    }
+}
+
+void PhyloSuperTree::ufbootUpdate(const iqhip_ufboot_tree *ent, int n, double epsilon, double logl_cutoff, int64_t counts[3],
+                                  double *min_orig_logl) {
+    needGroup();
+    hip(iqhip_partition_ufboot_update(group, ent, n, epsilon, logl_cutoff, counts, min_orig_logl), "iqhip_partition_ufboot_update");
+}
+
+void PhyloSuperTree::ufbootFetchTrees(int64_t *boot_tree) {
+    needGroup();
+    hip(iqhip_partition_ufboot_fetch(group, nullptr, nullptr, nullptr, boot_tree), "iqhip_partition_ufboot_fetch");
 }
 
 double PhyloSuperTree::optimizeParameters(bool fixed_len, double logl_epsilon, double gradient_epsilon) {

@@ -21,6 +21,10 @@
 //   optimizeParameters     PartitionModelPlen::optimizeParameters (:107-200).  DEVIATION: the per-partition
 //                          substitution parameters are taken as given (no optimizeParametersOnly, no linked alpha):
 //                          rates and branch lengths only
+//   initUFBoot / saveCurrentTree / saveNNITrees / summarizeBootstrap   PhyloSuperTreePlen::getBestNNIForBran's
+//                          computePatternLikelihood + saveCurrentTree (:1367-1372): PhyloTree's own bookkeeping run on
+//                          `super`, its device calls sent to the group (iqhip_partition_ufboot_*); sites are resampled
+//                          within partitions (superalignment.cpp:360-370), every member keeps its own sample matrix
 #pragma once
 #include <string>
 #include <vector>
@@ -113,11 +117,33 @@ public:
     // is made on every tree, the central branch (nni5: the two at node1, the central one, the two at node2) solved jointly
     // with optimizeOneBranch in the reference's order, the summed lnL taken, and the swap undone; the second swap starts
     // from the lengths the first left, and all lengths are restored at the end.  Every member vector is dropped.
-    NNIMove getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2]);
+    // ptnlh_rows (optional, 2 entries): the row of every member's store that receives the per-pattern values of the two
+    // neighbours (phylosupertreeplen.cpp:1367-1372)
+    NNIMove getBestNNIForBran(int a, int b, bool nni5, NNIMove moves[2], const int *ptnlh_rows = nullptr);
     // the two / ten rounds of phylo_nni.cpp run on `super`, one iqhip_partition_optimize_branch_batch per round; a
     // candidate whose solve diverged (optx > 0.95 max_branch_length) takes the branch-by-branch path.  setAllBranchMode.
     void evaluateNNIsBatch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr);
-    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr);
+    // ptnlh_rows (optional, 2 per branch in move order): the last of the five rounds goes through
+    // iqhip_partition_optimize_branch_batch_rows, so candidate k's per-pattern values land in row ptnlh_rows[k] of every member
+    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const int *ptnlh_rows, const BranchList *branches);
+    void evaluateNNIs5Batch(std::vector<NNIMove> &moves, const BranchList *branches = nullptr) { evaluateNNIs5Batch(moves, nullptr, branches); }
+
+    // ---- UFBoot on the super tree (PhyloSuperTreePlen::getBestNNIForBran's computePatternLikelihood + saveCurrentTree).
+    //      Sites are resampled WITHIN partitions (superalignment.cpp:360-370): every member keeps its own sample matrix.  The
+    //      per-replicate state is the GROUP's (iqhip_partition_ufboot_*); the bookkeeping -- ids, tie draws, the strings of
+    //      taken candidates, winners, split counts -- is PhyloTree's own, run on `super` with the device calls sent here.
+    //      The members' own ufboot_nsamples stay 0.
+    // member p: nsamples replicates of its own site count, drawn with stream p
+    void genBootSamples(int nsamples, uint64_t seed);
+    void setBootSamples(int part, const float *samples, int nsamples);   // [nsamples][member's nptn]
+    void reservePtnlhRows(int nrows);
+    void initUFBoot(int nsamples, uint64_t seed) { needGroup(); super.initUFBoot(nsamples, seed); }
+    // the current tree's row on every member (row 0), then one update
+    void saveCurrentTree(double logl) { needGroup(); super.saveCurrentTree(logl); }
+    void saveNNITrees() { needGroup(); super.saveNNITrees(); }
+    void saveNNITrees(const std::vector<NNIMove> &evaluated) { needGroup(); super.saveNNITrees(evaluated); }
+    void ufbootNextIteration() { super.ufbootNextIteration(); }
+    void summarizeBootstrap(PhyloTree::UFBootSummary &out) { needGroup(); super.summarizeBootstrap(out); }
 
     // counters (tests, bench): joint solves, batches of joint solves, group traversals, diverged-Newton resets; of the last
     // optimizeGeneRate: Brent evaluations per member and lockstep rounds
@@ -128,8 +154,16 @@ public:
 private:
     // PhyloTree::NNIBackend for `super`
     void pendingVectors(const std::vector<PhyloNode *> &n1, const std::vector<PhyloNode *> &n2, bool all) override;
-    void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res) override;
-    void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2]) override { getBestNNIForBran(node1, node2, nni5, moves); }
+    void submitTasks(const std::vector<iqhip_branch_task> &tasks, std::vector<iqhip_branch_result> &res, const int32_t *rows) override;
+    void bestNNIForBran(int node1, int node2, bool nni5, NNIMove moves[2], const int *ptnlh_rows) override {
+        getBestNNIForBran(node1, node2, nni5, moves, ptnlh_rows);
+    }
+    void ufbootInit(int nsamples) override;
+    void ufbootReserveRows(int nrows) override { reservePtnlhRows(nrows); }
+    void ufbootPutCurrentRow(int row) override;
+    void ufbootUpdate(const iqhip_ufboot_tree *ent, int n, double epsilon, double logl_cutoff, int64_t counts[3],
+                      double *min_orig_logl) override;
+    void ufbootFetchTrees(int64_t *boot_tree) override;
     void needGroup() const;
     void pushLengths();                   // member lengths = rate x super lengths; all member vectors dropped
     void prepareBranch(int a, int b);     // current_it + pending partials + theta of (a, b) on every member

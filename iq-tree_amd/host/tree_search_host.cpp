@@ -63,6 +63,9 @@ void TreeSearch::checkEligible(const char *who) const {
             if (batched && m->lh_mem_save != LM_ALL_BRANCH)
                 throw std::runtime_error(w + "the batched NNI evaluation needs setAllBranchMode on the super tree");
         }
+        // (the super tree's own UFBoot state lives on the group: initUFBoot on the PhyloSuperTree, the members' stay 0)
+        if (t.ufboot_nsamples > 0 && batched && !nni5)
+            throw std::runtime_error(w + "UFBoot with the batched evaluation needs nni5 (the nni1 batch keeps no per-pattern rows)");
         return;
     }
     if (!t.engine) throw std::runtime_error(w + "the tree has no engine");
@@ -98,26 +101,28 @@ void TreeSearch::evaluate(const BranchList &branches, bool all, std::vector<NNIM
             n2.push_back(t.nodes[(size_t)std::max(br.first, br.second)]);
         }
     moves.clear();
-    if (stree) {
-        if (batched) {
-            if (nni5) stree->evaluateNNIs5Batch(moves, all ? nullptr : &branches);
-            else stree->evaluateNNIsBatch(moves, all ? nullptr : &branches);
-        } else {
-            for (size_t q = 0; q < n1.size(); q++) {
-                NNIMove two[2];
-                stree->getBestNNIForBran(n1[q]->id, n2[q]->id, nni5, two);
-                moves.push_back(two[0]);
-                moves.push_back(two[1]);
-            }
-        }
-        return;
-    }
     const bool boot = t.ufboot_nsamples > 0;
     std::vector<int> rows;
     if (boot) {   // store row 0 is saveCurrentTree's, row 1 + k candidate k's
         rows.resize(2 * n1.size());
         for (size_t k = 0; k < rows.size(); k++) rows[k] = (int)(1 + k);
-        if (iqhip_ptnlh_reserve(t.engine, (int)(1 + rows.size())) != 0) throw std::runtime_error(iqhip_last_error());
+        if (stree) stree->reservePtnlhRows((int)(1 + rows.size()));
+        else if (iqhip_ptnlh_reserve(t.engine, (int)(1 + rows.size())) != 0) throw std::runtime_error(iqhip_last_error());
+    }
+    if (stree) {
+        if (batched) {
+            if (nni5) stree->evaluateNNIs5Batch(moves, boot ? rows.data() : nullptr, all ? nullptr : &branches);
+            else stree->evaluateNNIsBatch(moves, all ? nullptr : &branches);
+        } else {
+            for (size_t q = 0; q < n1.size(); q++) {
+                NNIMove two[2];
+                stree->getBestNNIForBran(n1[q]->id, n2[q]->id, nni5, two, boot ? rows.data() + 2 * q : nullptr);
+                moves.push_back(two[0]);
+                moves.push_back(two[1]);
+            }
+        }
+        if (boot) stree->saveNNITrees(moves);
+        return;
     }
     if (batched) {
         if (nni5) t.evaluateNNIs5Batch(moves, boot ? rows.data() : nullptr, all ? nullptr : &branches);

@@ -47,7 +47,8 @@ public:
     // over the super tree of an edge-linked partition model: `tree` is its topology (super), every edit and evaluation goes
     // to the super tree and all members (a candidate tree is re-read by every tree, PhyloSuperTree::readTreeString).
     // optimizeNNI, doRandomNNIs and doTreeSearch; partition rates and models are taken as given inside the loop, as the
-    // model is on a plain tree
+    // model is on a plain tree.  With PhyloSuperTree::initUFBoot done the search feeds the group's UFBoot state (rows out of
+    // the group's batched solves, saveNNITrees(moves), the current tree per step) and the correlation rule applies
     explicit TreeSearch(PhyloSuperTree *super_tree);
 
     // ---- parameters (the reference's defaults) ------------------------------------------------------------------------
@@ -117,7 +118,8 @@ public:
     // `batched` without LM_ALL_BRANCH, UFBoot together with mixtures, +ASC or the batched nni1 evaluation (it keeps no
     // per-pattern rows), numInitTrees > 0 on engines the parsimony calls refuse (anything but 4, 20 or 64 states):
     // throws std::runtime_error, the tree is not touched.  Every entry point calls it first.  On a super tree: multifurcations,
-    // fewer than 4 taxa, no engines, UFBoot on a member, numInitTrees > 0, `batched` without setAllBranchMode
+    // fewer than 4 taxa, no engines, UFBoot on a MEMBER (the super tree's own state lives on the group), numInitTrees > 0,
+    // `batched` without setAllBranchMode, UFBoot with the batched nni1 evaluation
     void checkEligible(const char *who) const;
 
     PhyloTree *tree;
