@@ -10,7 +10,7 @@ CSRC       := $(PKG)/csrc
 HOST       := $(PKG)/host
 LIBDIR     := $(PKG)/lib
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
-HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/ptnlh.hip $(CSRC)/classlh.hip $(CSRC)/pairdist.hip $(CSRC)/quartet.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_partnewton.hip $(CSRC)/kernels_partboot.hip $(CSRC)/partition.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_em.hip $(CSRC)/kernels_mixem.hip $(CSRC)/kernels_classlnl.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_ufboot.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_quartet.hip $(CSRC)/kernels_bionj.hip $(CSRC)/kernels_pars.hip $(CSRC)/kernels_spr.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
+HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/ptnlh.hip $(CSRC)/classlh.hip $(CSRC)/pairdist.hip $(CSRC)/quartet.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_partnewton.hip $(CSRC)/kernels_partboot.hip $(CSRC)/kernels_partdist.hip $(CSRC)/partition.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_em.hip $(CSRC)/kernels_mixem.hip $(CSRC)/kernels_classlnl.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_ufboot.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_quartet.hip $(CSRC)/kernels_bionj.hip $(CSRC)/kernels_pars.hip $(CSRC)/kernels_spr.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(HIP_SRCS))
 
 all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/liblh_oracle.so
@@ -18,7 +18,7 @@ all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/lib
 $(LIBDIR):
 	mkdir -p $(LIBDIR)
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/trav_phases.h $(CSRC)/pars_spr_check.h $(CSRC)/ufboot_rule.h include/iqhip.h | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/trav_phases.h $(CSRC)/pars_spr_check.h $(CSRC)/ufboot_rule.h $(CSRC)/pair_eval.h $(CSRC)/partpair_layout.h include/iqhip.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the topology tests compare sums bit for bit with a plain IEEE evaluation of the reference's expressions
@@ -28,6 +28,7 @@ $(LIBDIR)/kernels_ufboot.o: HIPFLAGS += -ffp-contract=off
 $(LIBDIR)/kernels_partboot.o: HIPFLAGS += -ffp-contract=off
 # ... and the pairwise distances follow a numpy restatement step for step
 $(LIBDIR)/kernels_dist.o: HIPFLAGS += -ffp-contract=off
+$(LIBDIR)/kernels_partdist.o: HIPFLAGS += -ffp-contract=off
 # ... and the quartet likelihoods of likelihood mapping likewise
 $(LIBDIR)/kernels_quartet.o: HIPFLAGS += -ffp-contract=off
 $(LIBDIR)/quartet.o: HIPFLAGS += -ffp-contract=off
@@ -38,7 +39,7 @@ $(LIBDIR)/libiqhip.so: $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HIP_OBJS) -ldl
 
 HOST_SRCS  := $(HOST)/phylo_host.cpp $(HOST)/phylo_nni.cpp $(HOST)/phylo_support.cpp $(HOST)/phylo_dist.cpp $(HOST)/phylo_pars.cpp $(HOST)/phylo_em.cpp $(HOST)/phylo_ufboot.cpp $(HOST)/iqhost_c.cpp $(HOST)/model_host.cpp $(HOST)/alignment_host.cpp $(HOST)/iqmodel_c.cpp $(HOST)/model_opt_host.cpp $(HOST)/supertree_host.cpp $(HOST)/tree_search_host.cpp $(HOST)/pars_forest_host.cpp
-HOST_HDRS  := $(HOST)/search_host.h $(HOST)/tree_search_host.h $(HOST)/pars_forest_host.h $(HOST)/pars_forest_plan.h $(HOST)/phylo_host.h $(HOST)/mirror_policy.h $(HOST)/brent_host.h $(HOST)/bfgs_host.h $(HOST)/model_host.h $(HOST)/model_opt_host.h $(HOST)/alignment_host.h $(HOST)/ufboot_splits.h $(HOST)/supertree_host.h $(HOST)/partition_spec.h $(HOST)/lmap_host.h include/iqhip.h include/iqhip_adapter.h
+HOST_HDRS  := $(HOST)/search_host.h $(HOST)/tree_search_host.h $(HOST)/pars_forest_host.h $(HOST)/pars_forest_plan.h $(HOST)/phylo_host.h $(HOST)/mirror_policy.h $(HOST)/brent_host.h $(HOST)/bfgs_host.h $(HOST)/model_host.h $(HOST)/model_opt_host.h $(HOST)/alignment_host.h $(HOST)/ufboot_splits.h $(HOST)/supertree_host.h $(HOST)/supertree_brlen.h $(HOST)/partition_spec.h $(HOST)/lmap_host.h include/iqhip.h include/iqhip_adapter.h
 
 $(LIBDIR)/libiqhost.so: $(HOST_SRCS) $(HOST_HDRS) $(LIBDIR)/libiqhip.so
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -o $@ $(HOST_SRCS) -L$(LIBDIR) -liqhip -Wl,-rpath,'$$ORIGIN'

@@ -93,8 +93,13 @@
 // above (JC2 / GTR2 name binary columns); every partition keeps every taxon.  PartitionModelPlen::optimizeParameters runs
 // with the substitution parameters as given (-blfix: fixed branch lengths too).  It prints "Partition-specific rates:  r1
 // r2 ..." (-spp only), one line "Partition <name>: <nsite> sites, <nptn> patterns, lnL <value>" per partition and "Optimal
-// log-likelihood: <sum>", and writes <prefix>.treefile with the super tree's lengths.  -q / -spp exclude -m, -alrt, -z, -bb,
-// -mldist, -pars*, -bionjtree, -emrates, -mixweights, -optmodel and -lmap.
+// log-likelihood: <sum>", and writes <prefix>.treefile with the super tree's lengths.  With -bionjtree [-mldist <file>] and
+// no -te / -t the starting tree is built first (PhyloSuperTreePlen::computeDist, computeBioNJ, fixNegativeBranch): from a
+// star tree, all rates 1 and the models as the file gives them, every pair of sequences is solved jointly over the
+// partitions on the device, the matrix is written (<prefix>.mldist unless -mldist names the file) and read back, the BIONJ
+// tree goes to <prefix>.bionj, fixNegativeBranch(false) runs, the lines of the plain -bionjtree path and "Log-likelihood of
+// the input tree" are printed, and the run goes on as -te <prefix>.bionj does (with -search: as -t).  -q / -spp exclude -m,
+// -alrt, -z, -bb, -pars*, -emrates, -mixweights, -optmodel and -lmap, and -bionjtree / -mldist next to -te / -t.
 // With -lmap N [-wql] [-seed S] it runs likelihood mapping (PhyloTree::doLikelihoodMapping) under the model after the tree's
 // lnL and branch optimisation: N quartets drawn from -seed (N = 0 or N >= C(n,4): every unique quartet), the three trees of
 // each optimised on the device in one call.  It prints "Computing N quartet likelihoods", "Quartets in region k: .." for
@@ -226,6 +231,40 @@ static void writeText(const std::string &file, const std::string &text) {
     out << text;
 }
 
+// the distance matrix in the reference's .mldist format (alignment.cpp:2586-2606)
+static void writeMldist(const std::string &file, const std::vector<std::string> &names, const std::vector<double> &dist,
+                        double min_branch_length) {
+    const int nseq = (int)names.size();
+    size_t max_len = 10;
+    for (int i = 0; i < nseq; i++) max_len = std::max(max_len, names[i].size());
+    std::ofstream out(file.c_str());
+    if (!out) throw std::runtime_error("cannot write " + file);
+    out << nseq << std::endl;
+    out.precision(std::max((int)ceil(-log10(min_branch_length)) + 1, 6));   // alignment.cpp:2592
+    out << std::fixed;
+    for (int i = 0; i < nseq; i++) {
+        out.width((std::streamsize)max_len);
+        out << std::left << names[i] << " ";
+        for (int j = 0; j < nseq; j++) out << dist[(size_t)i * nseq + j] << " ";
+        out << std::endl;
+    }
+}
+
+// ... and the matrix as the file holds it
+static void readMldist(const std::string &file, const std::vector<std::string> &names, std::vector<double> &dist) {
+    const int nseq = (int)names.size();
+    dist.assign((size_t)nseq * nseq, 0.0);
+    std::ifstream in(file.c_str());
+    int n_in = 0;
+    if (!(in >> n_in) || n_in != nseq) throw std::runtime_error("cannot read " + file);
+    std::string name;
+    for (int i = 0; i < nseq; i++) {
+        if (!(in >> name) || name != names[i]) throw std::runtime_error("unexpected sequence name in " + file);
+        for (int j = 0; j < nseq; j++)
+            if (!(in >> dist[(size_t)i * nseq + j])) throw std::runtime_error("cannot read " + file);
+    }
+}
+
 // a topology string of taxon ids with the ids replaced by the sequence names
 static std::string namedTopology(const std::string &ids, const std::vector<std::string> &names) {
     std::string out;
@@ -253,15 +292,26 @@ struct SearchOptions {
 // -q / -spp: the edge-linked partition model on a fixed topology, or with -search / -t the NNI tree search on the super tree
 // between two optimizeParameters (rates with -spp, and lengths); the partition rates and models are taken as given inside
 // the search loop
+// With -bionjtree and no -te / -t the starting tree is built as the plain path builds it (PhyloSuperTreePlen::computeDist,
+// computeBioNJ, fixNegativeBranch): from a star tree, all rates 1 and the models as the partition file gives them, the joint
+// ML distance of every pair is written to mldist_file and read back, the BIONJ tree of that text goes to <prefix>.bionj,
+// fixNegativeBranch(false) replaces the negative lengths, and the run goes on as -te <prefix>.bionj does
 static int runPartitionModel(const std::string &aln_file, const std::string &part_file, const std::string &tree_file,
-                             const std::string &prefix, bool proportional, bool blfix, int dev, const SearchOptions &so) {
+                             const std::string &prefix, bool proportional, bool blfix, int dev, const SearchOptions &so,
+                             bool bionjtree, const std::string &mldist_file) {
     std::vector<std::string> names;
     std::vector<PartitionInput> parts;
     readPartitionRaxml(aln_file, part_file, names, parts);
-    std::ifstream tin(tree_file.c_str());
-    if (!tin) throw std::runtime_error("cannot open tree file " + tree_file);
     std::stringstream tss;
-    tss << tin.rdbuf();
+    if (bionjtree) {   // a star of all taxa: only the taxa matter until the tree is built
+        tss << "(";
+        for (size_t i = 0; i < names.size(); i++) tss << (i ? "," : "") << names[i] << ":0.1";
+        tss << ");";
+    } else {
+        std::ifstream tin(tree_file.c_str());
+        if (!tin) throw std::runtime_error("cannot open tree file " + tree_file);
+        tss << tin.rdbuf();
+    }
     PhyloSuperTree tree;
     tree.readTreeString(tss.str(), names);
     if (tree.super.leafNum != (int)names.size()) throw std::runtime_error("Tree and alignment have different numbers of taxa");
@@ -270,6 +320,26 @@ static int runPartitionModel(const std::string &aln_file, const std::string &par
     if (so.on) tree.setAllBranchMode();   // the batched NNI evaluation needs every directed vector
     tree.attachEngines(dev);
     printf("Edge-linked partition model with %d partitions (%s)\n", tree.size(), proportional ? "-spp" : "-q");
+    if (bionjtree) {
+        const int nseq = (int)names.size();
+        std::vector<double> dist((size_t)nseq * nseq);
+        auto t0 = std::chrono::steady_clock::now();
+        tree.computeDist(dist.data(), nullptr);
+        double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        writeMldist(mldist_file, names, dist, tree.min_branch_length);
+        printf("ML distances of %d pairs: %.4f s, printed to %s\n", nseq * (nseq - 1) / 2, sec, mldist_file.c_str());
+        readMldist(mldist_file, names, dist);   // the tree is a function of the file, as in the reference
+        t0 = std::chrono::steady_clock::now();
+        std::string nwk;
+        tree.computeBioNJ(dist.data(), nullptr, &nwk);
+        sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        writeText(prefix + ".bionj", nwk + "\n");
+        printf("BIONJ tree: %.4f s, printed to %s.bionj\n", sec, prefix.c_str());
+        const int fixed = tree.fixNegativeBranch(false);   // phyloanalysis.cpp:1832-1837
+        printf("%d negative branch lengths fixed\n", fixed);
+        tree.readTreeString(tree.getTreeString(), names);   // from here on what -te does with a tree file
+        printf("Log-likelihood of the input tree: %.17g\n", tree.computeLikelihood());
+    }
     tree.optimizeParameters(blfix, 0.001, 0.001);   // params.modeps defaults
     if (so.on) {
         TreeSearch ts(&tree);
@@ -326,7 +396,8 @@ static void usage() {
             "                  the best m optimised by NNI before the search loop)\n"
             "       iqhip_lnl -s <alignment> -parstree [-sprrad <r>] -m <model> [-seed <s>] ...   (parsimony starting tree instead of -te)\n"
             "       iqhip_lnl -s <alignment> -bionjtree -m <model> ...              (BIONJ starting tree instead of -te)\n"
-            "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
+            "       iqhip_lnl -s <alignment> -q|-spp <partition file> -te <newick file> | -bionjtree [-mldist <file>]\n"
+            "                 [-blfix] [-pre <prefix>] [-dev <gpu>]\n"
             "                 [-search | -t <newick file>] [-n <iterations>] [-numstop <n>] [-pers <p>] [-popsize <k>] [-nni1] [-allnni]\n"
             "                 (edge-linked partition model instead of -m; lines 'MODEL, name = 1-100, 250-400, 401-500\\3';\n"
             "                  -q: all partition rates 1, -spp: rates estimated)\n"
@@ -443,19 +514,21 @@ int main(int argc, char **argv) {
     }
     if (!part_file.empty()) {
         const char *with = numpars > 0 ? "-numpars" : !model_str.empty() ? "-m" : alrt > 0 || lbp > 0 ? "-alrt / -lbp" : !treeset_file.empty() || zb > 0 ? "-z" : bb > 0 ? "-bb"
-                           : !mldist_file.empty() ? "-mldist" : pars || parstree || sprrad > 0 ? "-pars / -parstree / -sprrad"
-                           : bionjtree ? "-bionjtree" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : lmap >= 0 ? "-lmap" : nullptr;
+                           : !mldist_file.empty() && !tree_file.empty() ? "-mldist and a tree (-te / -t): the distances belong to -bionjtree"
+                           : pars || parstree || sprrad > 0 ? "-pars / -parstree / -sprrad"
+                           : bionjtree && !tree_file.empty() ? "-bionjtree and a tree (-te / -t)" : emrates ? "-emrates" : mixweights ? "-mixweights" : optmodel ? "-optmodel" : lmap >= 0 ? "-lmap" : nullptr;
         if (with) {
-            fprintf(stderr, "error: -q / -spp cannot be combined with %s (the models come from the partition file; the partition model evaluates a fixed topology)\n", with);
+            fprintf(stderr, "error: -q / -spp cannot be combined with %s (the models come from the partition file; the tree comes from -te / -t or from -bionjtree)\n", with);
             return 2;
         }
-        if (aln_file.empty() || tree_file.empty()) { usage(); return 2; }
+        if (aln_file.empty() || (tree_file.empty() && !bionjtree)) { usage(); return 2; }
         if (prefix.empty()) prefix = part_file;
+        if (bionjtree && mldist_file.empty()) mldist_file = prefix + ".mldist";
         try {
             SearchOptions so;
             so.on = search; so.nni5 = nni5; so.allnni = allnni; so.n_given = n_given; so.n_iter = n_iter;
             so.numstop = numstop; so.popsize = popsize; so.pers = pers; so.seed = seed;
-            return runPartitionModel(aln_file, part_file, tree_file, prefix, part_proportional, blfix, dev, so);
+            return runPartitionModel(aln_file, part_file, tree_file, prefix, part_proportional, blfix, dev, so, bionjtree, mldist_file);
         } catch (const std::exception &ex) {
             fprintf(stderr, "error: %s\n", ex.what());
             return 1;
@@ -592,35 +665,12 @@ int main(int argc, char **argv) {
             auto t0 = std::chrono::steady_clock::now();
             tree.computeDist(nullptr, dist.data(), d2l.data());
             const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            size_t max_len = 10;
-            for (int i = 0; i < nseq; i++) max_len = std::max(max_len, aln.seq_names[i].size());
-            std::ofstream out(mldist_file.c_str());
-            if (!out) throw std::runtime_error("cannot write " + mldist_file);
-            out << nseq << std::endl;
-            out.precision(std::max((int)ceil(-log10(tree.min_branch_length)) + 1, 6));   // alignment.cpp:2592
-            out << std::fixed;
-            for (int i = 0; i < nseq; i++) {
-                out.width((std::streamsize)max_len);
-                out << std::left << aln.seq_names[i] << " ";
-                for (int j = 0; j < nseq; j++) out << dist[(size_t)i * nseq + j] << " ";
-                out << std::endl;
-            }
+            writeMldist(mldist_file, aln.seq_names, dist, tree.min_branch_length);
             printf("ML distances of %d pairs: %.4f s, printed to %s\n", nseq * (nseq - 1) / 2, sec, mldist_file.c_str());
         }
         if (bionjtree) {
-            const int nseq = aln.getNSeq();
-            std::vector<double> dist((size_t)nseq * nseq);
-            {   // the matrix as the file holds it
-                std::ifstream in(mldist_file.c_str());
-                int n_in = 0;
-                if (!(in >> n_in) || n_in != nseq) throw std::runtime_error("cannot read " + mldist_file);
-                std::string name;
-                for (int i = 0; i < nseq; i++) {
-                    if (!(in >> name) || name != aln.seq_names[i]) throw std::runtime_error("unexpected sequence name in " + mldist_file);
-                    for (int j = 0; j < nseq; j++)
-                        if (!(in >> dist[(size_t)i * nseq + j])) throw std::runtime_error("cannot read " + mldist_file);
-                }
-            }
+            std::vector<double> dist;
+            readMldist(mldist_file, aln.seq_names, dist);   // the matrix as the file holds it
             auto t0 = std::chrono::steady_clock::now();
             std::string nwk;
             tree.computeBioNJ(dist.data(), nullptr, &nwk);

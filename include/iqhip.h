@@ -1053,6 +1053,42 @@ int iqhip_partition_ufboot_fetch(iqhip_partition *g, double *boot_logl, double *
                                  int64_t *boot_tree);
 int iqhip_debug_partition_ufboot_timing(iqhip_partition *g, double *ms /* 2: products, update */, int64_t *launches);
 
+/* ---- Joint pairwise distances of a partition group (PhyloSuperTreePlen::computeDist, phylosupertreeplen.cpp:361-371, per
+ * pair SuperAlignmentPairwisePlen, :18-45): what an edge-linked partition run computes before it has a tree; the matrix
+ * feeds iqhip_bionj and is written as .mldist.
+ * iqhip_partition_pair_distances: the arguments and the [T][T] symmetric outputs dist, d2l (or NULL), nsteps (or NULL) are
+ *   those of iqhip_pair_distances; T = the members' common taxon count; an init entry of 0 (or init NULL) means "use the JC
+ *   start".  For the pair (i, j), counts_p being member p's iqhip_pair_counts table and r_p the group's current rate
+ *   (iqhip_partition_set_rates):
+ *   Start: init[i][j] when non-zero, otherwise SuperAlignment::computeDist (superalignment.cpp:384-421): total = sum_p sum
+ *     counts_p, same = sum_p trace(counts_p); total == 0 -> 9; z = n_0 / (n_0 - 1) with n_0 the state count of MEMBER 0
+ *     (the reference reads partitions[0]->num_states, whatever the other partitions hold); x = 1 - z (total - same) / total;
+ *     x <= 0 -> 9, else -log(x) / z.  Integer-valued pattern frequencies make the sums exact in any order.
+ *   DIFFERENCE from iqhip_pair_distances: a start equal to 9 (MAX_GENETIC_DIST; an init entry of exactly 9 included) is
+ *     returned as it is, without a solve: dist = 9, d2l = 0, nsteps = 0 (phylosupertree.cpp:697, phylosupertreeplen.cpp:365).
+ *     The plain call solves from 9.
+ *   Solve: Optimization::minimizeNewton (the rule of iqhip_newton_branch) on df = sum_p r_p df_p(r_p x), ddf = sum_p r_p^2
+ *     ddf_p(r_p x), summed in member order, (df_p, ddf_p) being exactly what iqhip_pair_distances evaluates for member p
+ *     alone (non-zero cells only, P < 0 -> 0, S > 0, props-weighted category sums).  A member in which the pair shares no
+ *     column contributes 0: the reference's "taxon absent from the partition".  A one-member group at rate 1 gives the
+ *     bits of iqhip_pair_distances on that member for every pair whose start is not 9.
+ *   Returns as iqhip_pair_distances: IQHIP_ERR_INVALID with the matrices filled when a pair ends in one of minimizeNewton's
+ *     two errors.
+ *   One wave per pair, no host round trip per step; the pairs go in chunks whose counts, all members together (sum_p n_p^2
+ *     x 8 bytes per pair), fit 64 MB (IQHIP_PAIR_CHUNK, read per call, overrides the pairs per chunk).  The same bits on
+ *     every run and for every chunk size.
+ * IQHIP_ERR_UNSUPPORTED: a member iqhip_pair_distances refuses (embedded state counts, mixtures; sharded and +ASC members
+ *   cannot be in a group at all); members whose shapes put the LDS of the solve, 8 (max_p nstates_p ncat_p + 2 max_p
+ *   nstates_p) bytes, above 64 KB (a codon member with more than 126 categories).  IQHIP_ERR_INVALID: a null g or dist, members with different taxon counts, x1 > x2,
+ *   xacc <= 0, max_steps < 1, a negative or non-finite init entry.  All checked before the first launch: after a refused
+ *   call the group works as before.
+ * iqhip_debug_partition_pair_timing: with iqhip_timing_enable on the FIRST member, the device time (HIP events,
+ *   milliseconds) the last call spent in the members' count launches (summed over members, which run side by side) and in
+ *   its solve launches; iqhip_debug_partition_timing's *launches = the kernels that call enqueued. */
+int iqhip_partition_pair_distances(iqhip_partition *g, const double *init, double x1, double x2, double xacc, int max_steps,
+                                   double *dist, double *d2l, int32_t *nsteps);
+int iqhip_debug_partition_pair_timing(iqhip_partition *g, double *counts_ms, double *solve_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,7 @@ IQHIP_SYMBOLS = [
     "iqhip_partition_optimize_branch_batch",
     "iqhip_partition_ptnlh_reserve", "iqhip_partition_optimize_branch_batch_rows", "iqhip_partition_ptnlh_rell",
     "iqhip_partition_ufboot_init", "iqhip_partition_ufboot_update", "iqhip_partition_ufboot_fetch",
+    "iqhip_partition_pair_distances", "iqhip_debug_partition_pair_timing",
     "iqhip_debug_partition_ufboot_timing",
 ]
 
@@ -295,6 +296,8 @@ def libiqhip():
     lib.iqhip_partition_ufboot_init.argtypes = [vp, C.c_int]
     lib.iqhip_partition_ufboot_update.argtypes = [vp, C.POINTER(UFBootTree), C.c_int, C.c_double, C.c_double, i64p, dp]
     lib.iqhip_partition_ufboot_fetch.argtypes = [vp, dp, dp, i32p, i64p]
+    lib.iqhip_partition_pair_distances.argtypes = [vp, dp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp, i32p]
+    lib.iqhip_debug_partition_pair_timing.argtypes = [vp, dp, dp]
     lib.iqhip_debug_partition_ufboot_timing.argtypes = [vp, dp, i64p]
     lib._iq_typed = True
     return lib
@@ -413,6 +416,9 @@ def libiqhost():
     lib.iqhost_super_branch_order.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
     lib.iqhost_super_tree_string.argtypes = [vp, C.c_char_p, C.c_int]
     lib.iqhost_super_counters.argtypes = [vp, C.POINTER(C.c_long)]
+    lib.iqhost_super_compute_dist.argtypes = [vp, dp, dp, dp]
+    lib.iqhost_super_compute_bionj.argtypes = [vp, dp, dp, C.c_char_p, C.c_int, ipp]
+    lib.iqhost_super_fix_negative_branch.argtypes = [vp, C.c_int, ipp]
     lib.iqhost_super_group_batches.argtypes = [vp]
     lib.iqhost_super_group_batches.restype = C.c_long
     lib.iqhost_super_set_all_branch_mode.argtypes = [vp]
@@ -2497,6 +2503,24 @@ class PartitionGroup:
         results = [dict(optx=r.optx, d2l=r.d2l, lnl=r.lnl, nsteps=r.nsteps, status=r.status) for r in res[:n]]
         return results, out
 
+    def pair_distances(self, init=None, x1=1e-6, x2=9.0, xacc=1e-6, max_steps=100, ntaxa=None):
+        """iqhip_partition_pair_distances: every pair of taxa solved jointly over the members at the group's rates
+        -> (dist, d2l, nsteps), each [ntaxa, ntaxa] symmetric.  init: None or [ntaxa, ntaxa], 0 = the pooled JC start; a start
+        of exactly 9 is returned without a solve.  ntaxa: the members' taxon count (taken from a PhyloTree member if None)."""
+        n = int(ntaxa if ntaxa is not None else self.members[0].num_leaves)
+        dist, d2l, ns = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n), dtype=np.int32)
+        ini = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+        if ini is not None and ini.shape != (n, n):
+            raise ValueError("init must be [ntaxa, ntaxa]")
+        self._chk(self.lib.iqhip_partition_pair_distances(self.h, None if ini is None else _dptr(ini), x1, x2, xacc, max_steps,
+                                                          _dptr(dist), _dptr(d2l), _iptr(ns)))
+        return dist, d2l, ns
+
+    def pair_timing(self):
+        """iqhip_debug_partition_pair_timing -> (device ms of the members' count launches, of the solve launches) of the last
+        pair_distances (0 unless timing is enabled on member 0)"""
+        return _group_pair_timing(self.lib, self.h)
+
     def timing(self):
         """-> {"derv_ms", "update_ms", "launches"} of the last call (the times need iqhip_timing_enable on member 0)"""
         ms = (C.c_double * 2)()
@@ -2569,6 +2593,12 @@ def _group_ufboot_timing(lib, g):
     n = C.c_int64()
     _gchk(lib, lib.iqhip_debug_partition_ufboot_timing(g, ms, C.byref(n)))
     return ms[0], ms[1], n.value
+
+
+def _group_pair_timing(lib, g):
+    a, b = C.c_double(), C.c_double()
+    _gchk(lib, lib.iqhip_debug_partition_pair_timing(g, C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def parse_partition_spec(text, nsite):
@@ -2957,6 +2987,48 @@ class PhyloSuperTree:
         return dict(support_tree=lines[0], consensus_tree=lines[1], boot_trees=lines[2:2 + self._ufboot],
                     supports=[(int(ids[2 * q]), int(ids[2 * q + 1]), int(sup[q])) for q in range(n.value)],
                     distinct_trees=distinct.value)
+
+    # ---- the starting tree of a partitioned alignment: joint ML distances, BIONJ, fixNegativeBranch
+    def compute_dist(self, init=None, want_d2l=False):
+        """PhyloSuperTreePlen::computeDist for all pairs (iqhip_partition_pair_distances at the current rates): dist[ntaxa,
+        ntaxa], symmetric with a zero diagonal; with want_d2l also minimizeNewton's d2l per pair.  init: None or [ntaxa,
+        ntaxa], 0 = the pooled JC start (SuperAlignment::computeDist); a start of 9 is returned without a solve."""
+        n = self.num_leaves
+        dist, d2l = np.zeros((n, n)), np.zeros((n, n))
+        ini = None if init is None else np.ascontiguousarray(init, dtype=np.float64)
+        if ini is not None and ini.shape != (n, n):
+            raise ValueError("init must be [ntaxa, ntaxa]")
+        self._chk(self.lib.iqhost_super_compute_dist(self.h, None if ini is None else _dptr(ini), _dptr(dist), _dptr(d2l)))
+        return (dist, d2l) if want_d2l else dist
+
+    def compute_bionj(self, dist=None, var=None):
+        """PhyloTree::computeBioNJ on the super tree: the BIONJ tree of dist (None: compute_dist() first) is read into the
+        super tree and every member -> the reference's Newick string (lengths may be negative: fix_negative_branch(False))"""
+        n = self.num_leaves
+        d = self.compute_dist() if dist is None else np.ascontiguousarray(dist, dtype=np.float64)
+        v = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+        if d.shape != (n, n) or (v is not None and v.shape != (n, n)):
+            raise ValueError("dist and var must be [ntaxa, ntaxa]")
+        cap = 1 << 20
+        while True:
+            buf, need = C.create_string_buffer(cap), C.c_int()
+            self._chk(self.lib.iqhost_super_compute_bionj(self.h, _dptr(d), None if v is None else _dptr(v), buf, cap, C.byref(need)))
+            if need.value <= cap:
+                return buf.value.decode()
+            cap = need.value   # (the call is repeated with room for the string and gives the same tree)
+
+    def fix_negative_branch(self, force=True):
+        """PhyloSuperTreePlen::fixNegativeBranch: every member's fixNegativeBranch(force) on its own lengths; if any branch
+        was fixed the super-tree lengths become the site-weighted means of the members' and the members get rate x super
+        length again -> the number of fixed member branches"""
+        out = C.c_int()
+        self._chk(self.lib.iqhost_super_fix_negative_branch(self.h, int(force), C.byref(out)))
+        return out.value
+
+    def partition_pair_timing(self):
+        """iqhip_debug_partition_pair_timing of the last compute_dist -> (counts_ms, solve_ms); the times need
+        iqhip_timing_enable on member 0"""
+        return _group_pair_timing(libiqhip(), self.lib.iqhost_super_group(self.h))
 
     def partition_timing(self):
         """iqhip_debug_partition_timing of the group's last call (times need iqhip_timing_enable on member 0)"""

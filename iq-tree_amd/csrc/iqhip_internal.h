@@ -1330,6 +1330,36 @@ struct PairSolveArgs {
 hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts);
 hipError_t launch_pair_coef(iqhip_engine *e, double *d_coef);
 hipError_t launch_pair_solve(iqhip_engine *e, const PairSolveArgs &a, int npairs);
+// pairdist.hip: what iqhip_pair_distances shares with the group's call (partition.hip).  pair_require: the engines both
+// accept; pair_list: the pairs i < j of T taxa in the order both process them; pair_tiles: the tiles of m listed pairs
+// appended to `tiles`, pair k of the list in slot k
+int pair_require(iqhip_engine *e, const char *what);
+void pair_list(int T, std::vector<int32_t> &pairs);
+void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<PairTile> &tiles);
+
+// kernels_partdist.hip: the joint pairwise distances of a partition group (SuperAlignmentPairwisePlen).  One descriptor per
+// member; slot s of a chunk is pair first_pair + s of the call.  The kernel compacts the non-zero cells of every member's
+// counts of the slot into `cells` (nnz[slot][member] of them) once per pair and evaluates them per Newton step
+struct __attribute__((aligned(16))) PartPairDesc {
+    const double *counts;   // [chunk][n * n], what launch_pair_counts wrote for the member
+    const double *coef;     // [n][n][n] (launch_pair_coef)
+    const double *eval, *rates, *props;
+    uint16_t *cells;        // [chunk][n * n]
+    int32_t n, ncat;
+    double rate;
+};
+struct PartPairArgs {
+    const PartPairDesc *desc;   // [nparts]
+    int32_t *nnz;               // [chunk][nparts]
+    const double *init;         // [npairs] or nullptr
+    double *out;                // [npairs][4] = {optx, d2l, derivative evaluations, status of NewtonState}
+    int64_t first_pair;
+    int32_t nparts, max_steps;
+    int32_t e_doubles, max_n;   // LDS: e[e_doubles] ++ lam[max_n] ++ lam2[max_n]; the largest ncat * n and n of the members
+    double x1, x2, xacc;
+};
+size_t partpair_solve_lds_bytes(int e_doubles, int max_n);
+hipError_t launch_partpair_solve(hipStream_t s, const PartPairArgs &a, int npairs);
 
 // kernels_quartet.hip: likelihood mapping.  launch_quartet_cells: quartet s of the chunk (taxa d_quartets[4 s ..]) ->
 // d_cells[s][256], d_nother[s], d_other[s * nptn ..].  launch_quartet_solve: one workgroup per (slot, topology); slot s is

@@ -13,17 +13,16 @@
 //   k_pair_solve   one wave per pair: the JC start (Alignment::computeJCDist), then minimizeNewton over
 //       AlignmentPairwise::computeFuncDerv's default branch -- newton_init / newton_update of iqhip_internal.h, the one
 //       restatement of the reference's update rule -- until the pair is done; only the cells with a non-zero count are
-//       evaluated (compacted once per pair).  No host round trip per step.
+//       evaluated (compacted once per pair; the evaluation itself is pair_eval.h).  No host round trip per step.
 // Built with -ffp-contract=off (Makefile), like kernels_topo.hip: the arithmetic is the one a plain IEEE restatement does.
 #include <hip/hip_runtime.h>
 
 #include "iqhip_internal.h"
+#include "pair_eval.h"
 
 #pragma clang fp contract(off)
 
 namespace iqhip {
-
-constexpr double kMaxGeneticDist = 9.0;   // MAX_GENETIC_DIST, tools.h
 
 // ---- counts -------------------------------------------------------------------------------------------------------------
 // 4 states: wave w of the workgroup owns the pairs (x, y), x in {2 (w >> 1), +1}, y in {2 (w & 1), +1} of the tile
@@ -145,18 +144,8 @@ __global__ __launch_bounds__(64) void k_pair_solve(const PairSolveArgs A) {
     uint16_t *s_cell = reinterpret_cast<uint16_t *>(s_lam2 + n);
     const double *cnt = A.counts + (size_t)slot * nn;
     // the non-zero cells in cell order, and the two sums of the JC start
-    int nnz = 0;
     double total = 0.0, same = 0.0;
-    for (int base = 0; base < nn; base += 64) {
-        const int cell = base + lane;
-        const double c = cell < nn ? cnt[cell] : 0.0;
-        const bool nz = c > 0.0;
-        const unsigned long long mask = __ballot(nz);
-        if (nz) s_cell[nnz + __popcll(mask & ((1ull << lane) - 1ull))] = (uint16_t)cell;
-        nnz += __popcll(mask);
-        total += c;
-        if (nz && cell / n == cell % n) same += c;
-    }
+    const int nnz = pair_compact_cells(cnt, n, lane, s_cell, &total, &same);
     for (int k = lane; k < n; k += 64) {
         const double l = A.eval[k];
         s_lam[k] = l;
@@ -176,39 +165,11 @@ __global__ __launch_bounds__(64) void k_pair_solve(const PairSolveArgs A) {
     }
     NewtonState st;
     newton_init(st, guess, A.x1, A.x2, A.xacc, A.max_steps);
+    const PairEval E = {cnt, A.coef, A.rates, A.props, s_cell, s_lam, s_lam2, s_e, n, ncat, nnz};
     while (!st.done) {   // (wave-uniform: every lane advances the same state with the same sums)
-        const double t = st.rts;
-        __syncthreads();
-        for (int idx = lane; idx < ncat * n; idx += 64) s_e[idx] = exp(t * A.rates[idx / n] * s_lam[idx % n]);
-        __syncthreads();
-        double d1_sum = 0.0, d2_sum = 0.0;
-        for (int q = lane; q < nnz; q += 64) {
-            const int cell = s_cell[q];
-            const double *cf = A.coef + (size_t)cell * n;
-            double S = 0.0, S1 = 0.0, S2 = 0.0;
-            for (int c = 0; c < ncat; c++) {
-                const double *ec = s_e + (size_t)c * n;
-                double P = 0.0, P1 = 0.0, P2 = 0.0;
-                for (int k = 0; k < n; k++) {
-                    const double ce = cf[k] * ec[k];
-                    P += ce;
-                    P1 += ce * s_lam[k];
-                    P2 += ce * s_lam2[k];
-                }
-                if (P < 0.0) P = 0.0;   // (computeTransDerv clamps the probability only)
-                const double r = A.rates[c], pr = A.props[c];
-                S += pr * P;
-                S1 += pr * r * P1;
-                S2 += pr * (r * r) * P2;
-            }
-            if (S > 0.0) {
-                const double d1 = S1 / S;
-                d1_sum += cnt[cell] * d1;
-                d2_sum += cnt[cell] * (S2 / S - d1 * d1);
-            }
-        }
-        // computeFuncDerv's df = -d1_sum, ddf = -d2_sum; newton_update takes the likelihood's derivatives and negates
-        const double pdf = __shfl(wave_sum64(d1_sum), 0), pddf = __shfl(wave_sum64(d2_sum), 0);
+        // computeFuncDerv's df = -pdf, ddf = -pddf; newton_update takes the likelihood's derivatives and negates
+        double pdf, pddf;
+        pair_func_derv(E, st.rts, lane, &pdf, &pddf);
         newton_update(st, pdf, pddf);
     }
     if (lane == 0) {

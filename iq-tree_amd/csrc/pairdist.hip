@@ -10,10 +10,12 @@ using namespace iqhip;
 // ---- pairwise ML distances (PhyloTree::computeDist, phylotree.cpp:2432-2541; kernels_dist.hip) -----------------------
 // single-device plain engines of 4 / 20 / 64 states with model and alignment; mixtures are refused behind that: a mixture
 // without an alignment is an invalid call here, not an unsupported model
-static int pair_require(iqhip_engine *e, const char *what) {
+namespace iqhip {
+int pair_require(iqhip_engine *e, const char *what) {
     int rc = require(e, what, REQ_SINGLE_DEVICE | REQ_PLAIN_STATES | REQ_STATES_4_20_64 | REQ_MODEL_ALN);
     return rc ? rc : require(e, what, REQ_NO_MIXTURE);
 }
+}  // namespace iqhip
 
 // pairs per chunk: the counts of a chunk stay within 64 MB; IQHIP_PAIR_CHUNK (read per call) overrides
 static int64_t pair_chunk(const iqhip_engine *e, int64_t npairs) {
@@ -24,7 +26,8 @@ static int64_t pair_chunk(const iqhip_engine *e, int64_t npairs) {
 
 // tiles of 4 x 4 taxa for the m pairs of a chunk: pair k goes to slot k.  Pairs of one block of taxa share a tile, whatever
 // their order in the list; a pair listed twice opens a new tile
-static void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<PairTile> &tiles) {
+namespace iqhip {
+void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<PairTile> &tiles) {
     std::unordered_map<uint64_t, size_t> open;
     for (int64_t k = 0; k < m; k++) {
         const int i = pairs[2 * k], j = pairs[2 * k + 1];
@@ -45,6 +48,20 @@ static void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<P
         tiles[it->second].out[cell] = (int32_t)k;
     }
 }
+
+// the pairs i < j block by block of 4 x 4 taxa, so that the pairs of a tile are neighbours in the list (and in a chunk)
+void pair_list(int T, std::vector<int32_t> &pairs) {
+    pairs.clear();
+    pairs.reserve((size_t)T * (T - 1));
+    for (int I = 0; I < T; I += 4)
+        for (int J = I; J < T; J += 4)
+            for (int i = I; i < std::min(I + 4, T); i++)
+                for (int j = std::max(J, i + 1); j < std::min(J + 4, T); j++) {
+                    pairs.push_back(i);
+                    pairs.push_back(j);
+                }
+}
+}  // namespace iqhip
 
 extern "C" int iqhip_pair_counts(iqhip_engine *e, const int32_t *pairs, int npairs, double *counts) {
     int rc = pair_require(e, "iqhip_pair_counts");
@@ -80,16 +97,8 @@ extern "C" int iqhip_pair_distances(iqhip_engine *e, const double *init, double 
         return fail(IQHIP_ERR_INVALID, "iqhip_pair_distances: bad bounds / tolerance / step count (x1 <= x2, max_steps >= 1)");
     const int T = e->ntaxa, n = e->n;
     const int64_t npairs = (int64_t)T * (T - 1) / 2;
-    // the pairs i < j block by block of 4 x 4 taxa, so that the pairs of a tile are neighbours in the list (and in a chunk)
     std::vector<int32_t> pairs;
-    pairs.reserve((size_t)2 * npairs);
-    for (int I = 0; I < T; I += 4)
-        for (int J = I; J < T; J += 4)
-            for (int i = I; i < std::min(I + 4, T); i++)
-                for (int j = std::max(J, i + 1); j < std::min(J + 4, T); j++) {
-                    pairs.push_back(i);
-                    pairs.push_back(j);
-                }
+    pair_list(T, pairs);
     std::vector<double> h_init;
     if (init) {
         h_init.resize((size_t)npairs);

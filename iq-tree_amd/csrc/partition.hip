@@ -10,6 +10,8 @@
 // Streams: every call first makes the group's stream wait for an event recorded on each member's stream (the thetas and
 // vectors the group reads are complete), and after its last launch makes every member's stream wait for an event of the
 // group's stream (no member overwrites theta while the group still reads it).  The host waits once, for the group's stream.
+// The joint pairwise distances (end of the file; kernel in kernels_partdist.hip) follow the same rule chunk by chunk: the
+// members count a chunk of pairs on their own streams, the group solves it, and no member counts the next chunk before.
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "iqhip_internal.h"
+#include "partpair_layout.h"
 
 using namespace iqhip;
 
@@ -66,6 +69,16 @@ struct iqhip_partition {
         double ms[2] = {0.0, 0.0};   // iqhip_debug_partition_ufboot_timing: the members' products, the update kernels
         int64_t launches = 0;
     } ufb;
+    // iqhip_partition_pair_distances: the members' descriptors, the compacted cell lists [chunk][sum_p n_p^2] (member p's at
+    // chunk * sum_{q < p} n_q^2) and their lengths [chunk][nparts] of one chunk of pairs, per pair the initial distance and
+    // the result {optx, d2l, evaluations, status}
+    struct {
+        PairBuf<PartPairDesc> desc;
+        DevBuf<uint16_t> cells;
+        DevBuf<int32_t> nnz;
+        DevBuf<double> init, out;
+        double ms[2] = {0.0, 0.0};   // iqhip_debug_partition_pair_timing: the members' count launches, the solve launches
+    } pdist;
 };
 
 namespace {
@@ -928,5 +941,171 @@ extern "C" int iqhip_debug_partition_ufboot_timing(iqhip_partition *g, double *m
     ms[0] = g->ufb.ms[0];
     ms[1] = g->ufb.ms[1];
     if (launches) *launches = g->ufb.launches;
+    return IQHIP_OK;
+}
+
+// ---- joint pairwise distances (include/iqhip.h, "Joint pairwise distances of a partition group") ------------------------------
+// Per chunk of pairs: every member's launch_pair_counts on its own stream into its own pd.counts, then ONE k_partpair_solve
+// on the group's stream behind the members' events, then the members wait for the group (the next chunk's counts overwrite
+// what the solve read).  P + 1 launches per chunk, P more per call for the members' coefficient tables; no host round trip.
+extern "C" int iqhip_partition_pair_distances(iqhip_partition *g, const double *init, double x1, double x2, double xacc,
+                                              int max_steps, double *dist, double *d2l, int32_t *nsteps) {
+    const char *what = "iqhip_partition_pair_distances";
+    if (!g) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null group");
+    if (!dist) return fail(IQHIP_ERR_INVALID, std::string(what) + ": null argument");
+    if (!(x1 >= 0.0) || x1 > x2 || !std::isfinite(x2) || !(xacc > 0.0) || max_steps < 1)
+        return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad bounds / tolerance / step count (x1 <= x2, max_steps >= 1)");
+    int rc = use_group(g, what);
+    if (rc) return rc;
+    const int P = g->nparts, T = g->m[0]->ntaxa;
+    std::vector<int> nstates;
+    int e_doubles = 0, max_n = 0;
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        if ((rc = pair_require(e, what))) return rc;
+        if (e->ntaxa != T)
+            return fail(IQHIP_ERR_INVALID, std::string(what) + ": member " + std::to_string(p) + " has another number of taxa than member 0");
+        nstates.push_back(e->n);
+        e_doubles = std::max(e_doubles, e->n * e->ncat);
+        max_n = std::max(max_n, e->n);
+    }
+    if (partpair_solve_lds_bytes(e_doubles, max_n) > kPartMaxLdsBytes)
+        return fail(IQHIP_ERR_UNSUPPORTED, std::string(what) + ": nstates * ncat of a member exceeds the solve's LDS");
+    const int64_t npairs = (int64_t)T * (T - 1) / 2;
+    std::vector<int32_t> pairs;
+    pair_list(T, pairs);
+    std::vector<double> h_init;
+    if (init) {
+        h_init.resize((size_t)npairs);
+        for (int64_t k = 0; k < npairs; k++) {
+            const double v = init[(size_t)pairs[2 * k] * T + pairs[2 * k + 1]];
+            if (!(v >= 0.0) || !std::isfinite(v)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": an initial distance is negative or not finite");
+            h_init[(size_t)k] = v;
+        }
+    }
+    for (size_t k = 0; k < (size_t)T * T; k++) {
+        dist[k] = 0.0;
+        if (d2l) d2l[k] = 0.0;
+        if (nsteps) nsteps[k] = 0;
+    }
+    g->pdist.ms[0] = g->pdist.ms[1] = 0.0;
+    g->launches = 0;
+    if (npairs == 0) return IQHIP_OK;
+    // pairs per chunk: all members' counts of a chunk together within 64 MB; IQHIP_PAIR_CHUNK (read per call) overrides
+    const char *pc = getenv("IQHIP_PAIR_CHUNK");
+    const PartPairLayout lay = partpair_layout(nstates.data(), P, npairs, pc ? std::max(1, atoi(pc)) : 0);
+    const int64_t chunk = lay.chunk;
+    const size_t sum_nn = lay.sum_nn;
+    // all tiles up front, chunk by chunk (a chunk's slots start at 0): the same list serves every member
+    std::vector<PairTile> tiles;
+    std::vector<size_t> tile_first;
+    for (int64_t first = 0; first < npairs; first += chunk) {
+        tile_first.push_back(tiles.size());
+        pair_tiles(pairs.data() + 2 * first, std::min<int64_t>(chunk, npairs - first), T, tiles);
+    }
+    tile_first.push_back(tiles.size());
+    HIPCHK(g->pdist.desc.ensure(g->stream, (size_t)P));
+    HIPCHK(g->pdist.cells.ensure(g->stream, (size_t)chunk * sum_nn));
+    HIPCHK(g->pdist.nnz.ensure(g->stream, (size_t)chunk * P));
+    HIPCHK(g->pdist.init.ensure(g->stream, (size_t)npairs));
+    HIPCHK(g->pdist.out.ensure(g->stream, (size_t)4 * npairs));
+    // every buffer first: up to here nothing is enqueued, and a failure returns at once
+    for (int p = 0; p < P; p++) {
+        iqhip_engine *e = g->m[p];
+        const size_t nn = (size_t)e->n * e->n;
+        HIPCHK(e->pd.tiles.ensure(e, tiles.size()));
+        HIPCHK(e->pd.counts.ensure(e, (size_t)chunk * nn));
+        HIPCHK(e->pd.coef.ensure(e, nn * e->n));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    // From the first copy on `tiles` and `h_init` (pageable) are sources of enqueued copies: whatever fails below, the call
+    // leaves through the drain at its end, never straight out
+    const auto enqueue_setup = [&]() -> int {
+        for (int p = 0; p < P; p++) {
+            iqhip_engine *e = g->m[p];
+            HIPCHK(hipMemcpyAsync(e->pd.tiles.p, tiles.data(), sizeof(PairTile) * tiles.size(), hipMemcpyHostToDevice, e->stream));
+            HIPCHK(launch_pair_coef(e, e->pd.coef.p));
+            PartPairDesc &D = g->pdist.desc.h.p[p];
+            D.counts = e->pd.counts.p;
+            D.coef = e->pd.coef.p;
+            D.eval = e->d_eval;
+            D.rates = e->d_rates;
+            D.props = e->d_props;
+            D.cells = g->pdist.cells.p + lay.cell_first[(size_t)p];
+            D.n = e->n;
+            D.ncat = e->ncat;
+            D.rate = g->rate[p];
+        }
+        g->launches += P;
+        HIPCHK(hipSetDevice(g->device));
+        HIPCHK(hipMemcpyAsync(g->pdist.desc.d.p, g->pdist.desc.h.p, sizeof(PartPairDesc) * (size_t)P, hipMemcpyHostToDevice, g->stream));
+        if (init) HIPCHK(hipMemcpyAsync(g->pdist.init.p, h_init.data(), sizeof(double) * h_init.size(), hipMemcpyHostToDevice, g->stream));
+        return IQHIP_OK;
+    };
+    rc = enqueue_setup();
+    PartPairArgs a;
+    a.desc = g->pdist.desc.d.p;
+    a.nnz = g->pdist.nnz.p;
+    a.init = init ? g->pdist.init.p : nullptr;
+    a.out = g->pdist.out.p;
+    a.nparts = P;
+    a.max_steps = max_steps;
+    a.e_doubles = e_doubles;
+    a.max_n = max_n;
+    a.x1 = x1;
+    a.x2 = x2;
+    a.xacc = xacc;
+    const bool timing = g->m[0]->timing;
+    SpanTimer t_counts(timing), t_solve(timing);
+    hipError_t s = hipSuccess;
+    int64_t first = 0;
+    for (size_t c = 0; first < npairs && s == hipSuccess && rc == IQHIP_OK; c++, first += chunk) {
+        const int m = (int)std::min<int64_t>(chunk, npairs - first);
+        a.first_pair = first;
+        // (a member's stream waits for the solve of the chunk before: its counts are not overwritten under it)
+        for (int p = 0; p < P && s == hipSuccess; p++) {
+            iqhip_engine *e = g->m[p];
+            t_counts.mark(e->stream);
+            s = launch_pair_counts(e, e->pd.tiles.p + tile_first[c], (int)(tile_first[c + 1] - tile_first[c]), e->pd.counts.p);
+            t_counts.mark(e->stream);
+        }
+        if (s != hipSuccess || (rc = wait_for_members(g))) break;
+        t_solve.mark(g->stream);
+        s = launch_partpair_solve(g->stream, a, m);
+        t_solve.mark(g->stream);
+        const int rc2 = members_wait(g);
+        if (!rc) rc = rc2;
+        g->launches += P + 1;
+    }
+    std::vector<double> out((size_t)4 * npairs);
+    if (s == hipSuccess && rc == IQHIP_OK)
+        s = hipMemcpyAsync(out.data(), g->pdist.out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, g->stream);
+    // (whatever happened: the host waits for everything enqueued, the members' streams included; the staging is free again)
+    hipError_t drained = hipStreamSynchronize(g->stream);
+    for (int p = 0; p < P; p++) {
+        const hipError_t d = hipStreamSynchronize(g->m[p]->stream);
+        if (drained == hipSuccess) drained = d;
+    }
+    if (rc) return rc;
+    HIPCHK(s);
+    HIPCHK(drained);
+    g->pdist.ms[0] = t_counts.read();
+    g->pdist.ms[1] = t_solve.read();
+    int worst = 0;
+    for (int64_t k = 0; k < npairs; k++) {
+        const size_t ij = (size_t)pairs[2 * k] * T + pairs[2 * k + 1], ji = (size_t)pairs[2 * k + 1] * T + pairs[2 * k];
+        const NewtonResult r(out.data() + 4 * k);
+        dist[ij] = dist[ji] = r.optx;
+        if (d2l) d2l[ij] = d2l[ji] = r.d2l;
+        if (nsteps) nsteps[ij] = nsteps[ji] = r.nsteps;
+        if (r.status && !worst) worst = r.status;
+    }
+    return newton_status(worst);   // (minimizeNewton's two nrerror() exits; the matrices are filled all the same)
+}
+
+extern "C" int iqhip_debug_partition_pair_timing(iqhip_partition *g, double *counts_ms, double *solve_ms) {
+    if (!g) return fail(IQHIP_ERR_INVALID, "iqhip_debug_partition_pair_timing: null group");
+    if (counts_ms) *counts_ms = g->pdist.ms[0];
+    if (solve_ms) *solve_ms = g->pdist.ms[1];
     return IQHIP_OK;
 }

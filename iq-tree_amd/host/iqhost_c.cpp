@@ -1445,6 +1445,22 @@ int iqhost_super_counters(void *h, long *out) {
 }
 long iqhost_super_group_batches(void *h) { return ((PhyloSuperTree *)h)->num_group_batches; }
 
+// ---- the starting tree of a partitioned alignment (supertree_host.h)
+int iqhost_super_compute_dist(void *h, const double *init, double *dist, double *d2l) {
+    IQHOST_TRY(((PhyloSuperTree *)h)->computeDist(dist, d2l, init));
+}
+int iqhost_super_compute_bionj(void *h, const double *dist, const double *var, char *out, int cap, int *need) {
+    IQHOST_TRY({
+        std::string s;
+        ((PhyloSuperTree *)h)->computeBioNJ(dist, var, &s);
+        if (need) *need = (int)s.size() + 1;
+        if (out && (int)s.size() + 1 <= cap) memcpy(out, s.c_str(), s.size() + 1);
+    });
+}
+int iqhost_super_fix_negative_branch(void *h, int force, int *fixed) {
+    IQHOST_TRY(*fixed = ((PhyloSuperTree *)h)->fixNegativeBranch(force != 0));
+}
+
 // ---- NNI on the super tree (supertree_host.h): the layouts of the plain tree's calls above
 int iqhost_super_set_all_branch_mode(void *h) { IQHOST_TRY(((PhyloSuperTree *)h)->setAllBranchMode()); }
 // the super tree's topology as a PhyloTree handle for the read-only calls above (tree string, sorted taxon ids, neighbours);

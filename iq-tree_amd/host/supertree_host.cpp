@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "brent_host.h"
+#include "supertree_brlen.h"
 
 namespace iqhost {
 
@@ -567,6 +568,62 @@ void PhyloSuperTree::ufbootUpdate(const iqhip_ufboot_tree *ent, int n, double ep
 void PhyloSuperTree::ufbootFetchTrees(int64_t *boot_tree) {
     needGroup();
     hip(iqhip_partition_ufboot_fetch(group, nullptr, nullptr, nullptr, boot_tree), "iqhip_partition_ufboot_fetch");
+}
+
+// ---- the starting tree of a partitioned alignment -----------------------------------------------------------------------------
+void PhyloSuperTree::computeDist(double *dist, double *d2l, const double *init) {
+    needGroup();
+    for (PhyloTree *t : parts) t->pushInputs();
+    hip(iqhip_partition_pair_distances(group, init, min_branch_length, PhyloTree::MAX_GENETIC_DIST, min_branch_length, 100, dist, d2l, nullptr),
+        "iqhip_partition_pair_distances");
+}
+
+void PhyloSuperTree::pairTiming(double *counts_ms, double *solve_ms) const {
+    needGroup();
+    hip(iqhip_debug_partition_pair_timing(group, counts_ms, solve_ms), "iqhip_debug_partition_pair_timing");
+}
+
+void PhyloSuperTree::computeBioNJ(const double *dist, const double *var, std::string *newick) {
+    needGroup();
+    const int n = super.leafNum;
+    if (n < 3) throw std::runtime_error("computeBioNJ needs at least 3 taxa");
+    const std::vector<std::string> names = super.leafNames();
+    std::vector<iqhip_bionj_step> steps((size_t)std::max(1, n - 3));
+    int32_t last[3];
+    double last_len[3];
+    hip(iqhip_bionj(parts[0]->engine, n, dist, var, steps.data(), last, last_len), "iqhip_bionj");
+    const std::string nwk = PhyloTree::bionjNewick(steps.data(), n, last, last_len, names);
+    readTreeString(nwk, names);   // the super tree and every member; member lengths = rate x super lengths
+    if (newick) *newick = nwk;
+}
+
+int PhyloSuperTree::fixNegativeBranch(bool force) {
+    needGroup();
+    pushLengths();   // mapTrees
+    int fixed = 0;
+    for (PhyloTree *t : parts) {
+        t->initializeAllPartialPars();
+        fixed += t->fixNegativeBranch(force);
+    }
+    if (!fixed) return 0;
+    // PhyloSuperTree::computeBranchLengths: every branch occurs once in every member
+    const size_t P = parts.size();
+    std::vector<double> len(P), nsite(P);
+    std::vector<char> codon(P);
+    for (size_t p = 0; p < P; p++) {
+        nsite[p] = parts[p]->getAlnNSite();
+        codon[p] = parts[p]->seq_type == SEQ_CODON;
+    }
+    const bool rescale_codon_brlen = rescaleCodonBrlen(codon.data(), P);
+    for (size_t i = 0; i < super.nodes.size(); i++) {
+        const std::vector<PhyloNeighbor *> &dst = super.nodes[i]->neighbors;
+        for (size_t k = 0; k < dst.size(); k++) {
+            for (size_t p = 0; p < P; p++) len[p] = parts[p]->nodes[i]->neighbors[k]->length;
+            dst[k]->length = weightedBranchLength(len.data(), nsite.data(), codon.data(), P, rescale_codon_brlen);
+        }
+    }
+    pushLengths();   // it is necessary to map the branch lengths from supertree into gene trees
+    return fixed;
 }
 
 double PhyloSuperTree::optimizeParameters(bool fixed_len, double logl_epsilon, double gradient_epsilon) {

@@ -25,6 +25,9 @@
 //                          computePatternLikelihood + saveCurrentTree (:1367-1372): PhyloTree's own bookkeeping run on
 //                          `super`, its device calls sent to the group (iqhip_partition_ufboot_*); sites are resampled
 //                          within partitions (superalignment.cpp:360-370), every member keeps its own sample matrix
+//   computeDist / computeBioNJ / fixNegativeBranch   the starting tree of a run without -te: PhyloSuperTreePlen::computeDist
+//                          (:361-371, every pair solved jointly over the members: iqhip_partition_pair_distances),
+//                          PhyloTree::computeBioNJ on that matrix, PhyloSuperTreePlen::fixNegativeBranch (:1710-1729)
 #pragma once
 #include <string>
 #include <vector>
@@ -144,6 +147,25 @@ public:
     void saveNNITrees(const std::vector<NNIMove> &evaluated) { needGroup(); super.saveNNITrees(evaluated); }
     void ufbootNextIteration() { super.ufbootNextIteration(); }
     void summarizeBootstrap(PhyloTree::UFBootSummary &out) { needGroup(); super.summarizeBootstrap(out); }
+
+    // ---- the starting tree of a partitioned alignment (include/iqhip.h, "Joint pairwise distances of a partition group")
+    // PhyloSuperTreePlen::computeDist for all pairs: iqhip_partition_pair_distances with x1 = xacc = min_branch_length, x2 =
+    // MAX_GENETIC_DIST and 100 Newton steps at the current rates.  dist, d2l (or nullptr): [leafNum][leafNum]; init: the same
+    // shape or nullptr, an entry of 0 = the pair's JC start (SuperAlignment::computeDist)
+    void computeDist(double *dist, double *d2l, const double *init = nullptr);
+    // PhyloTree::computeBioNJ: iqhip_bionj on member 0's engine, PhyloTree::bionjNewick, and the tree read into the super tree
+    // and every member (rates and models stay; member lengths = rate x super lengths, negative ones included:
+    // fixNegativeBranch(false) is the caller's next step, as in the reference)
+    void computeBioNJ(const double *dist, const double *var, std::string *newick = nullptr);
+    // PhyloSuperTreePlen::fixNegativeBranch (:1710-1729): every member runs PhyloTree::fixNegativeBranch(force) on its own
+    // lengths (rate x super length); if any branch was fixed, each super-tree branch becomes sum_p len_p nsite_p / sum_p
+    // nsite_p in member order (PhyloSuperTree::computeBranchLengths, phylosupertree.cpp:1353-1398; with codon AND other
+    // members a codon member counts 3 nsite_p in the denominator: rescale_codon_brlen), and the members get rate x super
+    // length again.  Returns the number of fixed member branches.
+    // DEVIATION: a taxon without data in a partition is an all-unknown row here, not a pruned sub-tree: every branch occurs
+    // once in every member, and such a member's parsimony count for a branch behind which it has no data is 0.
+    int fixNegativeBranch(bool force);
+    void pairTiming(double *counts_ms, double *solve_ms) const;   // iqhip_debug_partition_pair_timing
 
     // counters (tests, bench): joint solves, batches of joint solves, group traversals, diverged-Newton resets; of the last
     // optimizeGeneRate: Brent evaluations per member and lockstep rounds
