@@ -916,6 +916,21 @@ int iqhip_debug_plan_shape(iqhip_engine *e, int64_t *out, int n);
 #define IQHIP_PLAN_LAYOUT_NSLOTS 8
 int iqhip_debug_plan_layout(iqhip_engine *e, int32_t *out, int nops);
 
+/* Pair children (4-state engines of at most 8 categories).  A node update whose two children are leaves with
+ * plain rows (states 0 .. 3 and STATE_UNKNOWN only), submitted with scaling rule 0 in a plan whose one later op consumes it, is
+ * not run: its consumer reads a 25-row table, and the vector behind its key exists as that table until someone reads it --
+ * every call that reads a vector by key (fetches, branch ends, solvers, sweeps, NNI evaluators, a later plan) sees the vector
+ * and the all-zero scale_num the update would have written, sum_scale of such an op is exactly 0.0, and iqhip_set_model /
+ * iqhip_set_alignment keep the vectors of the submissions made before them.  Memory: the first plan that removes an update
+ * allocates one device buffer of ntaxa * nptn_pad bytes (pair-code rows), as large as the state matrix.
+ * iqhip_debug_pair_children: node updates removed so far, vectors expanded for a reader so far, updates the last plan removed.
+ * iqhip_debug_planner_plain_taxa (planning-only engines, which have no alignment): plain[t] != 0 -- taxon t's row is plain;
+ * NULL -- nothing known, nothing is removed (the state after iqhip_debug_create_planner).
+ * iqhip_debug_plan_removed (planning-only engines): out[k] = 1 when row k of the last plan's op list was removed. */
+int iqhip_debug_pair_children(iqhip_engine *e, int64_t *ops_removed, int64_t *slabs_expanded, int64_t *last_plan_removed);
+int iqhip_debug_planner_plain_taxa(iqhip_engine *e, const uint8_t *plain);
+int iqhip_debug_plan_removed(iqhip_engine *e, int32_t *out, int nrows);
+
 /* Debugging aids, no reference counterpart: the library's memory accounting.  Every device and pinned-host allocation of
  * every engine and partition group in this process goes through one allocate / free pair, which counts bytes.
  * iqhip_debug_memory: what is live now -- device memory, and pinned or host staging memory (the plain host staging of a

@@ -278,6 +278,12 @@ int iqhip::slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx) {
     auto it = e->key2slab.find(key);
     if (it != e->key2slab.end()) {
         *idx = it->second;
+        Slab &s = e->slabs[*idx];
+        if (s.virt && !create && !e->planner) {   // a reader: the pair table becomes the vector it stands for
+            HIPCHK(launch_pair_expand(e, s));
+            e->pair_slabs_expanded++;
+        }
+        s.virt = false;   // (create: about to be overwritten)
         return IQHIP_OK;
     }
     if (!create) return fail(IQHIP_ERR_INVALID, "unknown partial_lh key (vector never computed)");
@@ -285,6 +291,18 @@ int iqhip::slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx) {
     if (rc) return rc;
     e->key2slab[key] = *idx;
     e->keymap_version++;
+    return IQHIP_OK;
+}
+
+int iqhip::expand_virtual_slabs(iqhip_engine *e) {
+    if (e->planner) return IQHIP_OK;
+    for (Slab &s : e->slabs) {
+        if (!s.virt) continue;
+        HIPCHK(use_device(e));
+        HIPCHK(launch_pair_expand(e, s));
+        e->pair_slabs_expanded++;
+        s.virt = false;
+    }
     return IQHIP_OK;
 }
 
@@ -311,6 +329,7 @@ extern "C" int iqhip_release(iqhip_engine *e, uint64_t key) {
     if (!e->shards.empty()) return sharded::release(e, key);
     auto it = e->key2slab.find(key);
     if (it == e->key2slab.end()) return IQHIP_OK;
+    e->slabs[it->second].virt = false;
     e->free_slabs.push_back(it->second);
     e->key2slab.erase(it);
     e->keymap_version++;
@@ -369,6 +388,10 @@ extern "C" int iqhip_set_alignment(iqhip_engine *e, const uint8_t *states, const
         return fail(IQHIP_ERR_INVALID,
                     "iqhip_set_alignment: call iqhip_set_model first (needs state_unknown)");
     HIPCHK(use_device(e));
+    {   // vectors that exist as pair tables only are those of the old alignment
+        const int rc = expand_virtual_slabs(e);
+        if (rc) return rc;
+    }
     const size_t P = (size_t)e->nptn_pad, N = (size_t)e->nptn;
     // (embedded data: padding patterns and missing characters are the ambiguity code whose tip row is the caller's
     // unknown row -- internal state n -- never the kernels' own unknown state, whose probability-space vector of exactly
@@ -391,6 +414,16 @@ extern "C" int iqhip_set_alignment(iqhip_engine *e, const uint8_t *states, const
     }
     HIPCHK(hipMemcpyAsync(e->d_states.p, tmp.data(), tmp.size(), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    // pair children (plan.hip select_pair_children): which rows hold nothing but states 0 .. 3 and STATE_UNKNOWN; the code rows
+    // and the descriptors that point at them belong to the old alignment
+    e->taxon_plain.assign((size_t)e->ntaxa, 1);
+    for (int t = 0; t < e->ntaxa; t++)
+        for (size_t p = 0; p < P; p++) {
+            const uint8_t st = tmp[(size_t)t * P + p];
+            if (st >= 4 && st != (uint8_t)e->state_unknown) { e->taxon_plain[t] = 0; break; }
+        }
+    e->pair_row_of.clear();
+    e->plan_cache.invalidate();
     e->pars_ready = false;
     int rc = iqhip_set_ptn_freq(e, ptn_freq);
     if (rc) return rc;
@@ -426,6 +459,11 @@ static int set_model_common(iqhip_engine *e, int nclass, const int32_t *cat_clas
     if (e->aln_set && state_unknown != e->state_unknown)
         return fail(IQHIP_ERR_INVALID, "iqhip_set_model: state_unknown changed after set_alignment");
     if (nclass < 1 || nclass > e->ncat) return fail(IQHIP_ERR_INVALID, "bad number of mixture classes");
+    if (e->model_set) {   // vectors that exist as pair tables only are those of the model that is about to go
+        HIPCHK(use_device(e));
+        const int rc = expand_virtual_slabs(e);
+        if (rc) return rc;
+    }
     // Mixtures: 20 states have a kernel of their own (k_traverse_mfma_mix20); 64 and 4 states take the generic
     // matrix-core kernel with per-class A images.  A 4-state engine therefore changes its vector layout (64-pattern
     // tiles of the VALU kernels <-> 16-pattern tiles of the matrix-core kernels) when the model becomes / stops being
@@ -776,7 +814,13 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
     int last_dst = -1;
     Stopwatch watch;
     if (e->debug_sweep) watch.start();
+    e->n_root_end_keys = 0;
+    if (has_root) {
+        if (a.leaf < 0) e->root_end_keys[e->n_root_end_keys++] = a.key;
+        if (b.leaf < 0) e->root_end_keys[e->n_root_end_keys++] = b.key;
+    }
     rc = build_plan(e, ops, nops, &last_dst, explicit_segs, len_ptrs);
+    e->n_root_end_keys = 0;
     if (rc) return rc;
     if (e->debug_sweep) debug_build_us += watch.us();
     DevBranch br;
@@ -1052,6 +1096,33 @@ extern "C" int iqhip_debug_cherry_tables(iqhip_engine *e, int64_t *tables_built,
     return IQHIP_OK;
 }
 
+extern "C" int iqhip_debug_pair_children(iqhip_engine *e, int64_t *ops_removed, int64_t *slabs_expanded, int64_t *last_plan_removed) {
+    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
+    if (!e->shards.empty()) e = e->shards[0];
+    if (ops_removed) *ops_removed = e->pair_ops_removed;
+    if (slabs_expanded) *slabs_expanded = e->pair_slabs_expanded;
+    if (last_plan_removed) *last_plan_removed = (int64_t)e->plan.virt.size();
+    return IQHIP_OK;
+}
+
+// planning-only engines have no alignment: say which taxa hold plain states only (nullptr: none known, nothing is virtualised)
+extern "C" int iqhip_debug_planner_plain_taxa(iqhip_engine *e, const uint8_t *plain) {
+    if (!e || !e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_planner_plain_taxa needs a planning-only engine");
+    e->taxon_plain.clear();
+    if (plain) e->taxon_plain.assign(plain, plain + e->ntaxa);
+    e->plan_cache.invalidate();
+    return IQHIP_OK;
+}
+
+// what the last plan removed: out[k] = 1 when row k of the caller's op list was answered by a pair child
+extern "C" int iqhip_debug_plan_removed(iqhip_engine *e, int32_t *out, int nrows) {
+    if (!e || !e->planner || !out || nrows != e->plan.nrows)
+        return fail(IQHIP_ERR_INVALID, "iqhip_debug_plan_removed needs a planning-only engine and the last plan's row count");
+    std::fill(out, out + nrows, 1);
+    for (int k = 0; k < e->plan.small_nops; k++) out[e->h_ops.p[k].out_row] = 0;
+    return IQHIP_OK;
+}
+
 extern "C" int iqhip_debug_path_counts(iqhip_engine *e, int64_t *out, int n) {
     if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
     if (!out && n > 0) return fail(IQHIP_ERR_INVALID, "null argument");
@@ -1289,9 +1360,13 @@ extern "C" int iqhip_timing_plan_bytes(iqhip_engine *e, double *stored, double *
             for (int u = 0; u <= e->plan.nunits; u++)
                 if (tab[2 * u + 1] > 0 && tab[2 * u] >= 0 && tab[2 * u] < e->last_nops) seg_first[tab[2 * u]] = 1;
         }
-        for (int k = 0; k < e->last_nops && e->h_ops.p; k++) {
+        // (k_traverse4: the ops that pair children replaced are not in the descriptors -- nothing stored, and their consumers
+        // read one code byte per pattern)
+        const int ndev = (!e->mfma && e->last_nops > 0) ? e->plan.small_nops : e->last_nops;
+        for (int k = 0; k < ndev && e->h_ops.p; k++) {
             const DevOp &d = e->h_ops.p[k];
             st += P * (V + 2.0);
+            ld += P * ((d.left_kind == CHILD_PAIR) + (d.right_kind == CHILD_PAIR));
             const double *held = (hands_over && k > 0 && !seg_first[k]) ? e->h_ops.p[k - 1].dst : nullptr;
             if (d.left_kind == CHILD_LEAF) ld += P;
             else if ((d.left_kind == CHILD_PF || d.left_kind == CHILD_LOAD) && d.pf != held) ld += P * (V + 2.0);

@@ -38,7 +38,16 @@ constexpr double kLogScalingThreshold = -177.44567822334599;
 // LEAF: state bytes; LOAD: read now; PREV: previous op's result (registers);
 // PF: read one op ahead into the prefetch registers
 // HOLD: parked in the HOLD registers by the producing op (push_hold) of the same launch
-enum ChildKind : int32_t { CHILD_LEAF = 0, CHILD_LOAD = 1, CHILD_PREV = 2, CHILD_PF = 3, CHILD_HOLD = 4 };
+// PAIR (k_traverse4 only): the result of a leaf-leaf node update that the planner removed from the op list ("virtual", plan.hip
+// select_pair_children) -- a function of the pair of leaf states only, read like a LEAF child from a 25-row table that the
+// chunk fill builds, with the pair-code row 5 * min(sA, 4) + min(sB, 4) as its state row
+enum ChildKind : int32_t { CHILD_LEAF = 0, CHILD_LOAD = 1, CHILD_PREV = 2, CHILD_PF = 3, CHILD_HOLD = 4, CHILD_PAIR = 5 };
+// children read out of a table in LDS with a staged state byte as row index
+constexpr bool child_is_table(int32_t kind) { return kind == CHILD_LEAF || kind == CHILD_PAIR; }
+constexpr int kPairRows = 25;                  // rows of a PAIR child's table
+// LDS region of a child, in blocks of B doubles: [ex][table 5] for a LEAF; [ex][table 25] and the leaf regions [ex][table 5] of the
+// removed op's two leaves, which the fill builds the 25 rows from, for a PAIR; [ex] otherwise
+constexpr int child_region_blocks(int32_t kind) { return kind == CHILD_LEAF ? 6 : (kind == CHILD_PAIR ? 1 + kPairRows + 12 : 1); }
 
 // One node update as the device sees it. 16-byte aligned so that the wave-uniform reads
 // of the descriptor become scalar loads.
@@ -81,6 +90,11 @@ struct __attribute__((aligned(16))) DevOp {
     const double *cherry;
     int32_t chunk_slots;   // 4-state path, on the first op of an LDS chunk: leaf-state slots of the chunk, the dummy slot 0 included
     int32_t _pad_slots;
+    // CHILD_PAIR children: the pendant branch lengths of the removed leaf-leaf op, {left child: its left, its right; right child:
+    // its left, its right}, and the row of the caller's op list the removed op answers (-1: none) -- this op writes that row's
+    // wave partial, always 0.0 (a leaf-leaf update never rescales)
+    double pair_len[4];
+    int32_t pair_row_l, pair_row_r;
 };
 
 #if defined(__HIPCC__)
@@ -222,6 +236,11 @@ struct Plan {
     std::vector<int> cherry_jobs;   // cherry-table slots the plan needs (re)built before its traversal
     bool uses_cherry = false;
     uint64_t cherry_model = 0;      // model version the plan's cherry tables were scheduled for
+    // k_traverse4: leaf-leaf ops the planner removed (select_pair_children).  Their slabs are marked virtual at every submission
+    // of the plan, a cached one included; nrows is the caller's op count (DevOp::out_row < nrows), small_nops the ops left
+    struct Virtual { int slab; int32_t taxon_l, taxon_r; double len_l, len_r; };
+    std::vector<Virtual> virt;
+    int nrows = 0;
 };
 
 // What the descriptors in d_ops were built from: an identical op list (same keys, leaves, lengths) with an unchanged key
@@ -406,6 +425,11 @@ struct PairBuf {
 struct Slab {
     DevBuf<double> plh;
     DevBuf<int16_t> sc;
+    // virtual: the vector is that of the leaf-leaf node update (taxon_l, taxon_r, len_l, len_r), which the planner removed from
+    // the submission that names it; the memory holds something older until slab_for_key(create = false) expands it
+    bool virt = false;
+    int32_t taxon_l = -1, taxon_r = -1;
+    double len_l = 0.0, len_r = 0.0;
 };
 
 }  // namespace iqhip
@@ -731,6 +755,18 @@ struct iqhip_engine {
     hipEvent_t staging_free = nullptr;
     bool staging_busy = false;
 
+    // pair children (CHILD_PAIR).  taxon_plain[t]: the taxon's row holds only states 0 .. 3 and STATE_UNKNOWN (recorded by
+    // iqhip_set_alignment; empty: unknown, nothing is virtualised).  Pair-code rows: slot = ordered pair of taxa, nptn_pad bytes
+    // each, built once per pair by k_pair_codes; the slots start over when a new plan finds them all taken or the alignment changes
+    std::vector<char> taxon_plain;
+    // the keys of the root-branch ends of the submission being planned (submit_traverse): their ops stay real -- the root
+    // pass reads those vectors from memory, a virtual one would be expanded at every submission
+    uint64_t root_end_keys[2] = {0, 0};
+    int n_root_end_keys = 0;
+    iqhip::DevBuf<uint8_t> d_pair_rows;
+    std::unordered_map<uint64_t, int> pair_row_of;   // (taxon_l << 32 | taxon_r) -> slot
+    int64_t pair_ops_removed = 0, pair_slabs_expanded = 0;   // iqhip_debug_pair_children
+
     // key -> slab
     std::unordered_map<uint64_t, int> key2slab;
     std::vector<iqhip::Slab> slabs;
@@ -969,7 +1005,12 @@ struct PhaseTimer {
     bool ok;
     std::vector<hipEvent_t> ev;
 };
-int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);   // engine.hip (create: a new key gets a slab)
+// engine.hip.  create: a new key gets a slab, and a virtual slab becomes an ordinary one that is about to be written;
+// !create: the caller is going to read the slab -- a virtual one is expanded first (launch_pair_expand, on the engine's stream)
+int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);
+int expand_virtual_slabs(iqhip_engine *e);   // all of them: before the model, the tip table or the alignment changes
+hipError_t launch_pair_expand(iqhip_engine *e, const Slab &s);                                        // kernels_valu4.hip
+hipError_t launch_pair_codes(iqhip_engine *e, const uint8_t *row_l, const uint8_t *row_r, uint8_t *out);   // kernels_valu4.hip
 bool cherry_candidate(const iqhip_engine *e);   // engine.hip: the engine uses cherry tables (DevOp::cherry)
 
 // plan.hip -- the planner.  build_plan: one submission's descriptors into h_ops and d_ops, e->plan; *last_dst = the slab

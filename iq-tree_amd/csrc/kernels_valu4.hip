@@ -141,8 +141,10 @@ __device__ __forceinline__ void leaf_cat4(const double *reg /* [ex B][table 5B] 
 // op k+1's streamed child (nx_pf), so the prefetch needs no second register set and no copy.
 // Returns lh_max (0 for LEAF-LEAF, which the reference never rescales).
 // With SP = 2 lanes per pattern a lane owns C = CF/2 of the block's CF categories, starting at `coff`.
+// leafL / leafR say "read from a table": a LEAF child, or a PAIR child (the removed leaf-leaf op below it: 25 rows, its code as
+// the state, never an ambiguity code).  tip_tip says both children are real leaves, the one case the scaling rule exempts.
 template <int C, int CF>
-__device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leafR, const double *regL,
+__device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leafR, bool pairL, bool pairR, const double *regL,
                                                const double *regR, const double *s_tip,
                                                const CONST_AS double *U, const CONST_AS double *uinv,
                                                int sL, int sR, int state_unknown, const char *nx_pf,
@@ -151,12 +153,12 @@ __device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leaf
     bool slowL = false, slowR = false;
     int rowL = 0, rowR = 0;
     if (leafL) {
-        slowL = __any((sL >= 4) && (sL != state_unknown));
-        rowL = sL < 4 ? sL : 4;
+        slowL = !pairL && __any((sL >= 4) && (sL != state_unknown));
+        rowL = pairL ? sL : (sL < 4 ? sL : 4);
     }
     if (leafR) {
-        slowR = __any((sR >= 4) && (sR != state_unknown));
-        rowR = sR < 4 ? sR : 4;
+        slowR = !pairR && __any((sR >= 4) && (sR != state_unknown));
+        rowR = pairR ? sR : (sR < 4 ? sR : 4);
     }
     double lh_max = 0.0;
 #pragma unroll
@@ -223,7 +225,7 @@ __device__ __forceinline__ double node_update4(bool leafL, bool holdL, bool leaf
         *reinterpret_cast<double2 *>(dst + (2 * c + 1) * 1024) = make_double2(prev[c * 4 + 2], prev[c * 4 + 3]);
 #endif
     }
-    return (leafL && leafR) ? 0.0 : lh_max;
+    return (leafL && leafR && !pairL && !pairR) ? 0.0 : lh_max;
 }
 
 // byte-offset addressing: a wave-uniform base (SGPR pair) plus one per-lane 32-bit offset that
@@ -280,8 +282,9 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
     uint8_t *s_states = reinterpret_cast<uint8_t *>(s_reg + A.lds_reg_doubles);  // [wave][slot][64] leaf states (trav_lds.h)
 
     __shared__ double s_model[32];    // U [16], eigenvalues [4], rates [C <= 8]: the chunk fills read them many times
-    __shared__ int s_opi[64][4];      // per op of a fill pass: LDS offsets of its two regions, is-leaf flags
-    __shared__ double s_opl[64][2];   // ... child branch lengths
+    __shared__ int s_opi[64][4];      // per op of a fill pass: LDS offsets of its two regions, their kinds (0 inner, 1 LEAF, 2 PAIR)
+    __shared__ int s_pair[128], s_npair;   // ... its PAIR children, 2 * op + child
+    __shared__ double s_opl[64][6];   // ... child branch lengths; [2 + 2 child + w]: pendant lengths of a PAIR child's two leaves
     __shared__ const uint8_t *s_row[kTrav4RowSlots];   // state rows of the chunk's leaf children, by slot
     // (The prologue's global reads issued together into registers, ahead of every LDS write, changed nothing measurable:
     // profiles/r05/experiments.txt.)
@@ -354,6 +357,7 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
         const int nslots = ops[k].chunk_slots;   // the chunk's leaf children own slots 1 .. nslots - 1, in op order
         [[maybe_unused]] const unsigned long long c0 = T4_CLK();
         __syncthreads();  // the previous chunk's regions are no longer read
+        if (threadIdx.x == 0) s_npair = 0;   // (ordered before the staging's atomics by the barrier below)
         // the state row of every leaf child of the chunk, by slot: what the state requests below read instead of descriptors
         for (int t = threadIdx.x; t < kn; t += kTravWg) {
             // (unconditionally: sl / sr of a non-leaf child point at a valid row and its slot 0 is never requested)
@@ -412,41 +416,99 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
 #pragma unroll 4
             for (int o = wave; o < kn; o += WPB) {
                 const CONST_AS int *w = reinterpret_cast<const CONST_AS int *>(ops + (k + o));
-                touched ^= w[0] ^ w[16] ^ w[32] ^ w[sizeof(DevOp) / 4 - 1];
+                static_assert(sizeof(DevOp) > 192 && sizeof(DevOp) <= 256, "one read per 64 bytes of the descriptor");
+                touched ^= w[0] ^ w[16] ^ w[32] ^ w[48] ^ w[sizeof(DevOp) / 4 - 1];
             }
             asm volatile("" ::"s"(touched));
         }
         [[maybe_unused]] unsigned long long c0a = T4_CLK();
         for (int o0 = 0; o0 < kn; o0 += 64) {
             const int on = kn - o0 < 64 ? kn - o0 : 64;
-            if (o0 > 0) lds_barrier();
+            if (o0 > 0) {   // (the previous pass has read its list)
+                lds_barrier();
+                if (threadIdx.x == 0) s_npair = 0;
+                lds_barrier();
+            }
             for (int t = threadIdx.x; t < on; t += kTravWg) {
                 const CONST_AS DevOp &d = ops[k + o0 + t];
                 s_opi[t][0] = d.lds_left;
                 s_opi[t][1] = d.lds_right;
-                s_opi[t][2] = d.left_kind == CHILD_LEAF;
-                s_opi[t][3] = d.right_kind == CHILD_LEAF;
+                s_opi[t][2] = d.left_kind == CHILD_LEAF ? 1 : (d.left_kind == CHILD_PAIR ? 2 : 0);
+                s_opi[t][3] = d.right_kind == CHILD_LEAF ? 1 : (d.right_kind == CHILD_PAIR ? 2 : 0);
                 s_opl[t][0] = op_child_len(d, 0);
                 s_opl[t][1] = op_child_len(d, 1);
+#pragma unroll
+                for (int q = 0; q < 4; q++) s_opl[t][2 + q] = d.pair_len[q];
+                // (the list's order is whatever the atomics give: every entry is worked on independently)
+                if (d.left_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t;
+                if (d.right_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t + 1;
             }
             lds_barrier();
             for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {  // phase 1: exponentials
                 const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
                 s_reg[s_opi[o][child] + e] = exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][child]));
             }
+            // ... and of the two pendant branches below each PAIR child of the pass (s_pair: the list the staging made), into the
+            // two leaf-shaped regions [ex][table 5] behind its table: the expression above, so they are the bits the removed op
+            // would have made
+            const int np = s_npair;
+            for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {
+                const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
+                s_reg[s_opi[o][child] + (1 + kPairRows + 6 * w) * B + e] =
+                    exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][2 + 2 * child + w]));
+            }
             lds_barrier();
             c0a = T4_CLK();
             // phase 2: leaf tables (K2).  One item = one (op, child, category, x): the four rounded products E = U[x][.] * ex are
             // made once and serve the table's four state rows (A, C, G, T); the fifth row, STATE_UNKNOWN, is exactly 1.0
             // (phylokernel.h:228-232).  (Entry by entry -- every entry remaking its E -- this phase was 14.6 k of a wave's cycles.)
-            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {
-                const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B, c = e >> 2, x = e & 3;
-                if (!s_opi[o][2 + child]) continue;
-                double *reg = s_reg + s_opi[o][child];
+            auto leaf_table = [&](double *reg, int e) {
+                const int c = e >> 2, x = e & 3;
                 const LeafE4 E = leaf_e4(s_model + x * 4, reg + c * 4);   // (trav_phases.h: rounding and association)
 #pragma unroll
                 for (int row = 0; row < 4; row++) reg[B + row * B + e] = E.entry(s_tip + row * 4);
                 reg[B + 4 * B + e] = 1.0;
+            };
+            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {
+                const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
+                if (s_opi[o][2 + child] == 1) leaf_table(s_reg + s_opi[o][child], e);
+            }
+            if (np == 0) continue;   // (uniform: every thread read the same count)
+            for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {   // the K2 tables of the removed ops' two leaves
+                const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
+                leaf_table(s_reg + s_opi[o][child] + (1 + kPairRows + 6 * w) * B, e);
+            }
+            lds_barrier();
+            // phase 2b: pair tables.  One item = one (PAIR child, category, pair code): the removed leaf-leaf op's result for that
+            // pair of states -- the product of the two K2 entries, the U^-1 contraction in node_update4's shape -- and then what
+            // node_update4 makes of a vector child: ex .* o, U times that.  Every product and fma is the one a lane would have
+            // executed, so the table row is the bits the op loop produced when the op still ran and its vector went through memory.
+            // (U and U^-1 as the op loop takes them, scalar operands: read from the LDS copies this body gathered all its operands at
+            // once, on top of prev, PF and HOLD, which are live across the fill -- 250 VGPRs at four categories, scratch above)
+#pragma unroll 1
+            for (int t = threadIdx.x; t < np * C * kPairRows; t += kTravWg) {
+                const int pi = t / (C * kPairRows), q = t - pi * (C * kPairRows), c = q / kPairRows, code = q - c * kPairRows;
+                const int o = s_pair[pi] >> 1, child = s_pair[pi] & 1, sa = code / 5, sb = code - 5 * sa;
+                double *reg = s_reg + s_opi[o][child];
+                const double *ta = reg + (2 + kPairRows + sa) * B + c * 4, *tb = reg + (8 + kPairRows + sb) * B + c * 4;
+                double tmp[4], l[4];
+#pragma unroll
+                for (int x = 0; x < 4; x++) tmp[x] = __dmul_rn(ta[x], tb[x]);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    double v = __dmul_rn(uinv[i * 4], tmp[0]);
+                    v = fma(uinv[i * 4 + 1], tmp[1], v);
+                    v = fma(uinv[i * 4 + 2], tmp[2], v);
+                    v = fma(uinv[i * 4 + 3], tmp[3], v);
+                    l[i] = __dmul_rn(reg[c * 4 + i], v);
+                }
+#pragma unroll
+                for (int x = 0; x < 4; x++) {
+                    double v = __dmul_rn(U[x * 4], l[0]);
+                    v = fma(U[x * 4 + 1], l[1], v);
+                    v = fma(U[x * 4 + 2], l[2], v);
+                    reg[B + code * B + c * 4 + x] = fma(U[x * 4 + 3], l[3], v);
+                }
             }
         }
         [[maybe_unused]] const unsigned long long c0b = T4_CLK();
@@ -485,9 +547,12 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
         for (int kk = 0; kk < kn; kk++, k++) {
             [[maybe_unused]] const unsigned long long c1 = T4_CLK();
             const CONST_AS DevOp *op = ops + k;
-            const bool leafL = op->left_kind == CHILD_LEAF;
+            const bool pairL = op->left_kind == CHILD_PAIR, pairR = op->right_kind == CHILD_PAIR;
+            const bool leafL = op->left_kind == CHILD_LEAF || pairL;   // (read from a table)
             const bool holdL = op->left_kind == CHILD_HOLD;
-            const bool leafR = op->right_kind == CHILD_LEAF;
+            const bool leafR = op->right_kind == CHILD_LEAF || pairR;
+            const bool tip_tip = leafL && leafR && !pairL && !pairR;   // (the scaling rule's TIP-TIP)
+            const int pair_row_l = op->pair_row_l, pair_row_r = op->pair_row_r;
             // (descriptor fields that only the op's tail needs: requested now, or the tail begins with their round trip)
             int16_t *const dst_sc_p = op->dst_sc;
             const int out_row = op->out_row, rule = op->no_scale, push_hold = op->push_hold;
@@ -512,12 +577,12 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
             if (nreal & 1) pf_sc = *reinterpret_cast<const int16_t *>(reinterpret_cast<const char *>(nx->pf_sc) + soff);
             char *dstp = reinterpret_cast<char *>(op->dst) + voff;
             [[maybe_unused]] const unsigned long long c2 = T4_CLK();
-            double lh_max = node_update4<CL, C>(leafL, holdL, leafR, s_reg + op->lds_left, s_reg + op->lds_right,
+            double lh_max = node_update4<CL, C>(leafL, holdL, leafR, pairL, pairR, s_reg + op->lds_left, s_reg + op->lds_right,
                                                 s_tip, U, uinv, sL, sR, A.state_unknown, nx_pf, dstp, coff, PF, HOLD, prev);
             if (SP == 2) lh_max = fmax(lh_max, __shfl_xor(lh_max, 32, 64));  // both category halves of the pattern
             [[maybe_unused]] const unsigned long long c3 = T4_CLK() + (lh_max == -1.0 ? 1 : 0);   // (after the update's results exist)
             // ---- scaling: the decision is trav_phases.h's, the rewrite of the registers and the fold_store form this kernel's
-            const ScaleChoice ch = scale_choice(rule, leafL && leafR, lh_max, invar);
+            const ScaleChoice ch = scale_choice(rule, tip_tip, lh_max, invar);
             double my_scale = 0.0;
             const unsigned long long any = __ballot(ch.scale);
             if (__builtin_expect(any != 0, 0)) {  // rare, wave-uniform
@@ -553,6 +618,10 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
             if (lane == 0) {
                 fold_store(&A.slab[(size_t)(2 + out_row) * A.nwaves + gw], ws);
                 if (any) fold_flag(A.fold, 2 + out_row);
+                // the rows of the removed ops below this one: a leaf-leaf update never rescales, its partial is 0.0 (and the row
+                // may hold an earlier submission's sum)
+                if (pair_row_l >= 0) fold_store(&A.slab[(size_t)(2 + pair_row_l) * A.nwaves + gw], 0.0);
+                if (pair_row_r >= 0) fold_store(&A.slab[(size_t)(2 + pair_row_r) * A.nwaves + gw], 0.0);
             }
 #ifdef IQHIP_T4_TRACE
             { const unsigned long long c4 = T4_CLK(); t4_head += c2 - c1; t4_upd += c3 - c2; t4_tail += c4 - c3; t4_n++; }
@@ -937,6 +1006,91 @@ hipError_t launch_reduce(iqhip_engine *e, int first_row, int nrows, int nwaves) 
     }
     hipLaunchKernelGGL(k_reduce, dim3(nrows), dim3(256), 0, e->stream, e->d_slab.p, nwaves,
                        first_row, e->d_result, e->d_fold_ticket.p + 1, done, seq);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// pair children (CHILD_PAIR): the code row of an ordered pair of taxa, and the expansion of a virtual slab
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pair_codes(const uint8_t *__restrict__ row_l, const uint8_t *__restrict__ row_r,
+                                                    uint8_t *__restrict__ out, int64_t nptn_pad) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nptn_pad) return;
+    const int a = row_l[p], b = row_r[p];
+    out[p] = (uint8_t)(5 * (a < 4 ? a : 4) + (b < 4 ? b : 4));
+}
+
+hipError_t launch_pair_codes(iqhip_engine *e, const uint8_t *row_l, const uint8_t *row_r, uint8_t *out) {
+    hipLaunchKernelGGL(k_pair_codes, dim3((unsigned)((e->nptn_pad + 255) / 256)), dim3(256), 0, e->stream, row_l, row_r, out, e->nptn_pad);
+    return hipGetLastError();
+}
+
+// The vector and the (all zero) counters of a leaf-leaf node update whose two rows hold only states 0 .. 3 and STATE_UNKNOWN,
+// written as k_traverse4 would have written them: the 25 possible vectors are made once per workgroup with the arithmetic of
+// the chunk fill's phases 1, 2 and 2b up to the U^-1 contraction (the same expressions: the same bits), lane = pattern copies
+// its pair's.
+template <int C>
+__global__ __launch_bounds__(256) void k_pair_expand(const uint8_t *__restrict__ row_l, const uint8_t *__restrict__ row_r, double len_l,
+                                                     double len_r, const double *__restrict__ evec, const double *__restrict__ inv_evec,
+                                                     const double *__restrict__ eval, const double *__restrict__ rates,
+                                                     const double *__restrict__ tip, double *__restrict__ dst,
+                                                     int16_t *__restrict__ dst_sc, int64_t ntiles) {
+    constexpr int B = 4 * C;
+    __shared__ double s_u[16], s_ui[16], s_tip[16], s_ex[2][B], s_tab[kPairRows * B];
+    if (threadIdx.x < 16) {
+        s_u[threadIdx.x] = evec[threadIdx.x];
+        s_ui[threadIdx.x] = inv_evec[threadIdx.x];
+        s_tip[threadIdx.x] = tip[threadIdx.x];
+    }
+    if (threadIdx.x < 2 * B) {
+        const int w = threadIdx.x / B, e = threadIdx.x - w * B;
+        s_ex[w][e] = exp(eval[e & 3] * (rates[e >> 2] * (w ? len_r : len_l)));
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < C * kPairRows; t += 256) {
+        const int c = t / kPairRows, code = t - c * kPairRows, sa = code / 5, sb = code - 5 * sa;
+        double tmp[4];
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            const double a = sa == 4 ? 1.0 : leaf_e4(s_u + x * 4, s_ex[0] + c * 4).entry(s_tip + sa * 4);
+            const double b = sb == 4 ? 1.0 : leaf_e4(s_u + x * 4, s_ex[1] + c * 4).entry(s_tip + sb * 4);
+            tmp[x] = __dmul_rn(a, b);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            double v = __dmul_rn(s_ui[i * 4], tmp[0]);
+            v = fma(s_ui[i * 4 + 1], tmp[1], v);
+            v = fma(s_ui[i * 4 + 2], tmp[2], v);
+            s_tab[code * B + c * 4 + i] = fma(s_ui[i * 4 + 3], tmp[3], v);
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    const int64_t ptn = tile * 64 + lane;
+    const int a = row_l[ptn], b = row_r[ptn];
+    const double *v = s_tab + (5 * (a < 4 ? a : 4) + (b < 4 ? b : 4)) * B;
+    double2 *p = reinterpret_cast<double2 *>(dst + tile * (64 * B)) + lane;
+#pragma unroll
+    for (int j = 0; j < 2 * C; j++) p[j * 64] = make_double2(v[2 * j], v[2 * j + 1]);
+    dst_sc[ptn] = 0;
+}
+
+hipError_t launch_pair_expand(iqhip_engine *e, const Slab &s) {
+    const size_t P = (size_t)e->nptn_pad;
+    const uint8_t *row_l = e->d_states.p + (size_t)s.taxon_l * P, *row_r = e->d_states.p + (size_t)s.taxon_r * P;
+    const int grid = (int)((e->ntiles + 3) / 4);
+#define IQ_PX(Cv)                                                                                                          \
+    case Cv:                                                                                                               \
+        hipLaunchKernelGGL(k_pair_expand<Cv>, dim3(grid), dim3(256), 0, e->stream, row_l, row_r, s.len_l, s.len_r, e->d_evec, \
+                           e->d_inv_evec, e->d_eval, e->d_rates, e->d_tip, s.plh.p, s.sc.p, e->ntiles);                    \
+        break;
+    switch (e->ncat) {
+        IQ_PX(1) IQ_PX(2) IQ_PX(3) IQ_PX(4) IQ_PX(5) IQ_PX(6) IQ_PX(7) IQ_PX(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef IQ_PX
     return hipGetLastError();
 }
 

@@ -51,6 +51,7 @@ void dummy_op(const iqhip_engine *e, DevOp &d) {
     d.pf_sc = d.ld_sc = e->dummy.sc.p;
     d.sl = d.sr = e->d_states.p;
     d.tabL = d.tabR = e->d_leaf_tab.p;
+    d.pair_row_l = d.pair_row_r = -1;
 }
 
 // Same op list as last time and no key created / released / moved since: the descriptors on the device are still the
@@ -59,6 +60,12 @@ bool plan_is_cached(const iqhip_engine *e, const iqhip_node_op *ops, int nops, c
                     const double *const *len_ptrs) {
     const PlanCache &c = e->plan_cache;
     const size_t in_bytes = sizeof(iqhip_node_op) * (size_t)nops;
+    // (a removed op whose result this submission's root pass reads: plan again, with that op real)
+    for (int q = 0; q < e->n_root_end_keys; q++) {
+        const auto it = e->key2slab.find(e->root_end_keys[q]);
+        for (const Plan::Virtual &v : e->plan.virt)
+            if (it != e->key2slab.end() && it->second == v.slab) return false;
+    }
     return !len_ptrs && nops > 0 && c.version == e->keymap_version && c.ops_in.size() == in_bytes &&
            memcmp(c.ops_in.data(), ops, in_bytes) == 0 && !c.uploaded.empty() &&
            (explicit_segs ? c.segs == *explicit_segs : c.segs.empty()) &&
@@ -219,30 +226,146 @@ int cut_units(const iqhip_engine *e, const iqhip_node_op *ops, int nops, const s
     return IQHIP_OK;
 }
 
+// A removed leaf-leaf op as its consumer sees it
+struct PairDef { int32_t taxon_l, taxon_r; double len_l, len_r; int row; const uint8_t *codes; };
+// What select_pair_children leaves: the ops that stay, in the caller's order, with the caller's row of each, and the removed
+// ones by the key of their result
+struct Kept {
+    std::vector<iqhip_node_op> ops;
+    std::vector<int> row;
+    std::unordered_map<uint64_t, PairDef> pairs;
+};
+
+uint64_t pair_key(int32_t tl, int32_t tr) { return ((uint64_t)(uint32_t)tl << 32) | (uint32_t)tr; }
+
+// *row: the pair-code row of an ordered pair of taxa, built if the pair has none yet (nullptr: no slot left, the op stays real)
+int pair_code_row(iqhip_engine *e, int32_t tl, int32_t tr, const uint8_t **row) {
+    const size_t P = (size_t)e->nptn_pad, nslots = e->d_pair_rows.cap / P;
+    *row = nullptr;
+    auto it = e->pair_row_of.find(pair_key(tl, tr));
+    if (it != e->pair_row_of.end()) { *row = e->d_pair_rows.p + (size_t)it->second * P; return IQHIP_OK; }
+    if (e->pair_row_of.size() >= nslots) return IQHIP_OK;
+    const int slot = (int)e->pair_row_of.size();
+    uint8_t *out = e->d_pair_rows.p + (size_t)slot * P;
+    if (!e->planner) HIPCHK(launch_pair_codes(e, e->d_states.p + (size_t)tl * P, e->d_states.p + (size_t)tr * P, out));
+    e->pair_row_of[pair_key(tl, tr)] = slot;
+    *row = out;
+    return IQHIP_OK;
+}
+
+// Leaf-leaf node updates that k_traverse4 need not run (DESIGN.md 3.1 "Pair children"): the vector of such a node depends on
+// the pair of leaf states only, so its one consumer reads a 25-row table instead (CHILD_PAIR), the op leaves the list and its
+// slab is marked virtual.  An op is removed when: both children are leaves whose rows hold only states 0 .. 3 and
+// STATE_UNKNOWN; its scaling rule is 0; exactly one later op of this plan consumes its result, nothing else writes that key
+// and it is not the plan's last op; the plan is cut automatically and takes its lengths from the host (no explicit segments,
+// no sweep pointers).  Consumer and producer then share a segment, because the producer no longer exists.
+// Returns whether anything was removed (then `kept` is the list to plan).
+int select_pair_children(iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *explicit_segs,
+                         const double *const *len_ptrs, Kept &kept, bool *any) {
+    *any = false;
+    if (e->mfma || e->wide4 || e->n != 4 || e->n_user != 4 || e->embed2 || e->scalar_rule_all || explicit_segs || len_ptrs ||
+        nops < 2 || e->taxon_plain.size() != (size_t)e->ntaxa)
+        return IQHIP_OK;
+    std::unordered_map<uint64_t, int> writes, reads, first_read;
+    for (int k = 0; k < nops; k++) {
+        writes[ops[k].dst_key]++;
+        for (int side = 0; side < 2; side++) {
+            if ((side ? ops[k].right_leaf : ops[k].left_leaf) >= 0) continue;
+            const uint64_t key = side ? ops[k].right_key : ops[k].left_key;
+            if (!reads[key]++) first_read[key] = k;
+        }
+    }
+    std::vector<char> removed((size_t)nops, 0);
+    int nremoved = 0;
+    for (int k = 0; k + 1 < nops; k++) {
+        const iqhip_node_op &o = ops[k];
+        if (o.left_leaf < 0 || o.right_leaf < 0 || o.left_leaf >= e->ntaxa || o.right_leaf >= e->ntaxa) continue;
+        if (o.flags & (IQHIP_OP_NO_SCALE | IQHIP_OP_SCALAR_RULE)) continue;
+        if (!e->taxon_plain[o.left_leaf] || !e->taxon_plain[o.right_leaf]) continue;
+        if (!(o.left_len >= 0.0) || !(o.right_len >= 0.0)) continue;   // (refused by fill_descriptors)
+        if (writes[o.dst_key] != 1 || reads[o.dst_key] != 1 || first_read[o.dst_key] <= k) continue;
+        // (a root-branch end of this submission is read from memory by the root pass: cheaper left real than expanded every time)
+        if (std::find(e->root_end_keys, e->root_end_keys + e->n_root_end_keys, o.dst_key) != e->root_end_keys + e->n_root_end_keys) continue;
+        removed[k] = 1;
+        nremoved++;
+    }
+    if (!nremoved) return IQHIP_OK;
+    // the code rows: one buffer of ntaxa slots (a tree has at most ntaxa / 2 leaf-leaf nodes); a search that has walked through
+    // more pairs than that starts over -- kernels still reading the old rows are ahead of the new builds on the stream
+    const size_t P = (size_t)e->nptn_pad;
+    if (e->d_pair_rows.cap < (size_t)e->ntaxa * P) {
+        HIPCHK(e->d_pair_rows.ensure(e, (size_t)e->ntaxa * P));
+        e->pair_row_of.clear();
+    }
+    size_t nmissing = 0;   // pairs of this plan that have no row yet (a pair occurs once in a tree)
+    for (int k = 0; k < nops; k++)
+        nmissing += removed[k] && !e->pair_row_of.count(pair_key(ops[k].left_leaf, ops[k].right_leaf));
+    if (e->pair_row_of.size() + nmissing > e->d_pair_rows.cap / P) e->pair_row_of.clear();
+    for (int k = 0; k < nops; k++) {
+        if (removed[k]) {
+            const iqhip_node_op &o = ops[k];
+            const uint8_t *codes;
+            int rc = pair_code_row(e, o.left_leaf, o.right_leaf, &codes);
+            if (rc) return rc;
+            if (codes) {
+                int didx;
+                rc = slab_for_key(e, o.dst_key, true, &didx);   // (the slab keeps its allocation)
+                if (rc) return rc;
+                kept.pairs[o.dst_key] = {o.left_leaf, o.right_leaf, o.left_len, o.right_len, k, codes};
+                e->plan.virt.push_back({didx, o.left_leaf, o.right_leaf, o.left_len, o.right_len});
+                continue;
+            }
+        }
+        kept.ops.push_back(ops[k]);
+        kept.row.push_back(k);
+    }
+    *any = !kept.pairs.empty();
+    if (e->debug_plan) fprintf(stderr, "[iqhip] plan: %zu of %d ops removed as pair children\n", kept.pairs.size(), nops);
+    return IQHIP_OK;
+}
+
+// the slabs of the plan's removed ops are virtual from this submission on (a cached plan too: every submission "computes" them)
+void mark_virtual_slabs(iqhip_engine *e) {
+    for (const Plan::Virtual &v : e->plan.virt) {
+        Slab &s = e->slabs[v.slab];
+        s.virt = true;
+        s.taxon_l = v.taxon_l; s.taxon_r = v.taxon_r;
+        s.len_l = v.len_l; s.len_r = v.len_r;
+    }
+    e->pair_ops_removed += (int64_t)e->plan.virt.size();
+}
+
 // One DevOp per op, in the staged order: children resolved to slabs / state rows and put in the kernels' canonical
-// form.  *last_dst: the slab the last op writes (-1: none)
+// form.  *last_dst: the slab the last op writes (-1: none).  rows / pairs: select_pair_children's (nullptr: nothing removed)
 int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const Units &u, const double *const *len_ptrs,
-                     int *last_dst) {
+                     int *last_dst, const Kept *kept) {
     int prev_dst = -1;
     for (int k = 0; k < nops; k++) {
         const iqhip_node_op &o = ops[u.order[k]];
         DevOp &d = e->h_ops.p[k];
         dummy_op(e, d);
-        d.out_row = u.order[k];
+        d.out_row = kept ? kept->row[u.order[k]] : u.order[k];
         d.no_scale = (o.flags & IQHIP_OP_NO_SCALE) ? 1 : (((o.flags & IQHIP_OP_SCALAR_RULE) || e->scalar_rule_all) ? 2 : 0);
         if (k > 0 && u.seg_of[k] != u.seg_of[k - 1]) prev_dst = -1;  // another workgroup: no register hand-over
         if (!(o.left_len >= 0.0) || !(o.right_len >= 0.0))
             return fail(IQHIP_ERR_INVALID, "negative or NaN branch length");
         const double *lp, *rp; const int16_t *lsc, *rsc;
         const uint8_t *lst, *rst; int32_t lkind, rkind;
-        int rc = resolve_child(e, o.left_key, o.left_leaf, prev_dst, &lp, &lsc, &lst, &lkind);
+        // (a removed op's result is never looked up as a slab: that would expand it)
+        const PairDef *lpair = nullptr, *rpair = nullptr;
+        if (kept && o.left_leaf < 0 && kept->pairs.count(o.left_key)) lpair = &kept->pairs.at(o.left_key);
+        if (kept && o.right_leaf < 0 && kept->pairs.count(o.right_key)) rpair = &kept->pairs.at(o.right_key);
+        int rc = IQHIP_OK;
+        if (lpair) { lp = nullptr; lsc = nullptr; lst = lpair->codes; lkind = CHILD_PAIR; }
+        else rc = resolve_child(e, o.left_key, o.left_leaf, prev_dst, &lp, &lsc, &lst, &lkind);
         if (rc) return rc;
-        rc = resolve_child(e, o.right_key, o.right_leaf, prev_dst, &rp, &rsc, &rst, &rkind);
+        if (rpair) { rp = nullptr; rsc = nullptr; rst = rpair->codes; rkind = CHILD_PAIR; }
+        else rc = resolve_child(e, o.right_key, o.right_leaf, prev_dst, &rp, &rsc, &rst, &rkind);
         if (rc) return rc;
         int didx;
         rc = slab_for_key(e, o.dst_key, true, &didx);
         if (rc) return rc;
-        if ((lkind != CHILD_LEAF && lp == e->slabs[didx].plh.p) || (rkind != CHILD_LEAF && rp == e->slabs[didx].plh.p))
+        if ((!child_is_table(lkind) && lp == e->slabs[didx].plh.p) || (!child_is_table(rkind) && rp == e->slabs[didx].plh.p))
             return fail(IQHIP_ERR_INVALID, "node update writes onto one of its own children");
         if (lkind == CHILD_PREV && rkind == CHILD_PREV)
             return fail(IQHIP_ERR_INVALID, "node update uses the same vector for both children");
@@ -260,16 +383,18 @@ int fill_descriptors(iqhip_engine *e, const iqhip_node_op *ops, int nops, const 
             // them the previous result -- the kernel reads the second one synchronously.
             auto swap_children = [&]() {
                 std::swap(lp, rp); std::swap(lsc, rsc); std::swap(lst, rst);
-                std::swap(lkind, rkind); std::swap(llen, rlen); std::swap(llen_p, rlen_p);
+                std::swap(lkind, rkind); std::swap(llen, rlen); std::swap(llen_p, rlen_p); std::swap(lpair, rpair);
             };
             if (lkind == CHILD_PREV) swap_children();                              // PREV goes right
-            else if (lkind == CHILD_LEAF && rkind == CHILD_LOAD) swap_children();  // memory child goes left
+            else if (child_is_table(lkind) && rkind == CHILD_LOAD) swap_children();  // memory child goes left
             if (lkind == CHILD_LOAD) lkind = CHILD_PF;
             if (rkind == CHILD_LOAD) (u.seg_of[k] ? e->plan.units_have_load : e->plan.has_load) = true;  // (PF, LOAD)
             if (lkind == CHILD_PF) { d.pf = lp; d.pf_sc = lsc; d.real_mask |= 1; }
             if (rkind == CHILD_LOAD) { d.ld = rp; d.ld_sc = rsc; }
-            if (lkind == CHILD_LEAF) d.sl = lst;
-            if (rkind == CHILD_LEAF) d.sr = rst;
+            if (child_is_table(lkind)) d.sl = lst;
+            if (child_is_table(rkind)) d.sr = rst;
+            if (lpair) { d.pair_len[0] = lpair->len_l; d.pair_len[1] = lpair->len_r; d.pair_row_l = lpair->row; }
+            if (rpair) { d.pair_len[2] = rpair->len_l; d.pair_len[3] = rpair->len_r; d.pair_row_r = rpair->row; }
         }
         d.left_kind = lkind; d.right_kind = rkind;
         d.left_len = llen; d.right_len = rlen;
@@ -434,15 +559,16 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     // a LEAF child's region: 4 states -- exponentials + the 5-row K2 table; 20 states with leaf tables -- the child's
     // whole K2 table [ncat][STATE_UNKNOWN][n], copied from the table buffer when the chunk is filled
     // (wide DNA: as the 4-state kernel, on both of its routes -- the generic kernel reads the exponentials only)
-    const int leaf_sz = (!e->mfma || e->wide4) ? 6 * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
+    const int leaf_sz = (!e->mfma || e->wide4) ? child_region_blocks(CHILD_LEAF) * B : (tables_in_lds ? (int)leaf_table_doubles(e) : B);
+    const int pair_sz = child_region_blocks(CHILD_PAIR) * B;   // (k_traverse4 only: no other plan holds a PAIR child)
     const int slot_sz = e->mfma ? 0 : trav4_lds(B).slot_doubles;   // (slot 0: the non-leaf children's)
     int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
     for (int k = 0; k < nops; k++) {
         DevOp &d = e->h_ops.p[k];
-        const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : B;
-        const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : B;
-        // 4-state path: each leaf child also stages one state byte per thread in LDS
-        const int nleaf = (d.left_kind == CHILD_LEAF) + (d.right_kind == CHILD_LEAF);
+        const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : (d.left_kind == CHILD_PAIR ? pair_sz : B);
+        const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : (d.right_kind == CHILD_PAIR ? pair_sz : B);
+        // 4-state path: each leaf / pair child also stages one state byte per thread in LDS
+        const int nleaf = child_is_table(d.left_kind) + child_is_table(d.right_kind);
         const int need = szl + szr + nleaf * slot_sz;
         if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
         // (k_traverse4 keeps one row pointer per slot of the chunk in a fixed array)
@@ -456,8 +582,8 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         regs += szl + szr;
         used += need;
         if (regs > max_used) max_used = regs;
-        d.sl_slot = d.left_kind == CHILD_LEAF ? slots++ : 0;
-        d.sr_slot = d.right_kind == CHILD_LEAF ? slots++ : 0;
+        d.sl_slot = child_is_table(d.left_kind) ? slots++ : 0;
+        d.sr_slot = child_is_table(d.right_kind) ? slots++ : 0;
         if (slots > max_slots) max_slots = slots;
     }
     if (nops > 0) {
@@ -490,6 +616,11 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         const size_t off = (size_t)(p - e->d_states.p);
         return off % (size_t)e->nptn_pad == 0 && off / (size_t)e->nptn_pad < (size_t)e->ntaxa;
     };
+    auto pair_row = [&](const uint8_t *p) {
+        if (!p || !e->d_pair_rows.p || p < e->d_pair_rows.p) return false;
+        const size_t off = (size_t)(p - e->d_pair_rows.p);
+        return off % (size_t)e->nptn_pad == 0 && off / (size_t)e->nptn_pad < e->pair_row_of.size();
+    };
     auto table = [&](const double *p) {
         if (e->plan.nleaf_tabs == 0 && !e->d_leaf_tab.p) return p == nullptr;  // kernel variant without tables
         if (!p || !e->d_leaf_tab.p || p < e->d_leaf_tab.p || per == 0) return false;
@@ -504,7 +635,15 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         if (!scs.count(d.pf_sc)) return bad(k, "pf_sc is not a counter slab / the dummy");
         if (!vecs.count(d.ld)) return bad(k, "ld (second memory child) is not a vector slab / the dummy slab");
         if (!scs.count(d.ld_sc)) return bad(k, "ld_sc is not a counter slab / the dummy");
-        if (!state_row(d.sl) || !state_row(d.sr)) return bad(k, "sl / sr is not a row of the state matrix");
+        // (a pair-code row holds codes 0 .. 24: read as leaf states it would index past a 5-row table)
+        const bool pl = k < nops && d.left_kind == CHILD_PAIR, pr = k < nops && d.right_kind == CHILD_PAIR;
+        if ((pl || pr) && (e->mfma || e->wide4)) return bad(k, "pair child in a plan of another kernel than k_traverse4");
+        if (!(pl ? pair_row(d.sl) : state_row(d.sl)) || !(pr ? pair_row(d.sr) : state_row(d.sr)))
+            return bad(k, "sl / sr is not a row of the state matrix (a pair-code row for a pair child, and only for one)");
+        if ((pl && !(d.pair_len[0] >= 0.0 && d.pair_len[1] >= 0.0)) || (pr && !(d.pair_len[2] >= 0.0 && d.pair_len[3] >= 0.0)))
+            return bad(k, "pair child with a negative or NaN pendant branch length");
+        if ((pl != (d.pair_row_l >= 0)) || (pr != (d.pair_row_r >= 0)) || d.pair_row_l >= e->plan.nrows || d.pair_row_r >= e->plan.nrows)
+            return bad(k, "pair_row is not the row of a removed op");
         if (!table(d.tabL) || !table(d.tabR)) return bad(k, "tabL / tabR is not a K2 table slot");
         if (d.cherry) {
             const size_t cper = (size_t)e->cherry_npairs * e->block;
@@ -515,16 +654,16 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
         }
         if (k >= nops) continue;  // sentinels: pointers only
         if (d.dst == e->dummy.plh.p || d.dst_sc == e->dummy.sc.p) return bad(k, "a real op writes the dummy slab");
-        const bool lk = d.left_kind == CHILD_LEAF || d.left_kind == CHILD_PF || d.left_kind == CHILD_HOLD ||
+        const bool lk = d.left_kind == CHILD_LEAF || d.left_kind == CHILD_PAIR || d.left_kind == CHILD_PF || d.left_kind == CHILD_HOLD ||
                         (d.left_kind == CHILD_LOAD && e->mfma && !e->mfma_pipelined);
-        const bool rk = d.right_kind == CHILD_LEAF || d.right_kind == CHILD_PREV || d.right_kind == CHILD_LOAD;
+        const bool rk = d.right_kind == CHILD_LEAF || d.right_kind == CHILD_PAIR || d.right_kind == CHILD_PREV || d.right_kind == CHILD_LOAD;
         if (!lk || !rk) return bad(k, "child kinds are not in canonical form");
         if (d.left_kind == CHILD_PF && (d.pf == e->dummy.plh.p || !(d.real_mask & 1))) return bad(k, "streamed child without a real vector");
         if (d.left_kind != CHILD_PF && !(e->mfma && !e->mfma_pipelined) && (d.real_mask & 1)) return bad(k, "real_mask set without a streamed child");
         if (d.right_kind == CHILD_LOAD && d.ld == e->dummy.plh.p) return bad(k, "second memory child without a real vector");
         if (d.dst == d.pf || d.dst == d.ld) return bad(k, "op writes one of its own children");
         if (!(d.left_len >= 0.0) || !(d.right_len >= 0.0)) return bad(k, "negative or NaN branch length");
-        if (d.out_row < 0 || d.out_row >= nops) return bad(k, "out_row outside the caller's op list");
+        if (d.out_row < 0 || d.out_row >= e->plan.nrows) return bad(k, "out_row outside the caller's op list");
         if (d.lds_left < 0 || d.lds_right < 0 || d.lds_left > e->plan.lds_doubles || d.lds_right > e->plan.lds_doubles)
             return bad(k, "LDS region outside the launch's allocation");
         if (d.sl_slot < 0 || d.sr_slot < 0 || d.sl_slot >= e->plan.state_slots || d.sr_slot >= e->plan.state_slots)
@@ -553,18 +692,18 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
             int next = 1, regs = 0;
             for (int q = k; q < k + c.chunk_nops; q++) {
                 const DevOp &d = e->h_ops.p[q];
-                if (d.sl_slot != (d.left_kind == CHILD_LEAF ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
-                next += d.left_kind == CHILD_LEAF;
-                if (d.sr_slot != (d.right_kind == CHILD_LEAF ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
-                next += d.right_kind == CHILD_LEAF;
-                const int szl = (d.left_kind == CHILD_LEAF ? 6 : 1) * e->block, szr = (d.right_kind == CHILD_LEAF ? 6 : 1) * e->block;
+                if (d.sl_slot != (child_is_table(d.left_kind) ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
+                next += child_is_table(d.left_kind);
+                if (d.sr_slot != (child_is_table(d.right_kind) ? next : 0)) return bad(q, "leaf-state slots of the chunk are not 1 .. n in op order");
+                next += child_is_table(d.right_kind);
+                const int szl = child_region_blocks(d.left_kind) * e->block, szr = child_region_blocks(d.right_kind) * e->block;
+                if (d.lds_left < d.lds_right + szr && d.lds_right < d.lds_left + szl) return bad(q, "LDS regions of the two children overlap");
                 regs = std::max(regs, std::max(d.lds_left + szl, d.lds_right + szr));
             }
             if (c.chunk_slots != next) return bad(k, "chunk_slots is not the chunk's slot count");
             if (next > kTrav4RowSlots) return bad(k, "more leaf-state slots than the kernel's row-pointer list holds");
-            if (next > e->plan.state_slots || regs > e->plan.lds_doubles ||
-                regs + next * trav4_lds(e->block).slot_doubles > lds_budget(e))
-                return bad(k, "LDS chunk outside the launch's allocation or over the budget");
+            if (next > e->plan.state_slots || regs > e->plan.lds_doubles) return bad(k, "LDS chunk outside the launch's allocation");
+            if (regs + next * trav4_lds(e->block).slot_doubles > lds_budget(e)) return bad(k, "LDS chunk over the LDS budget");
         }
         k += c.chunk_nops;
     }
@@ -607,7 +746,8 @@ int upload_plan(iqhip_engine *e, size_t nbytes) {
 }
 
 // sentinels, segment table and K2 job list behind the descriptors; the cache key; the small-plan decision; check; upload
-int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units &u, const std::vector<int> *explicit_segs,
+// (ops_in: the caller's list, the cache key; nops: the ops that were planned -- select_pair_children may have removed some)
+int finish_and_upload(iqhip_engine *e, int nops, const iqhip_node_op *ops_in, int nops_in, Units &u, const std::vector<int> *explicit_segs,
                       const double *const *len_ptrs, int last_dst) {
     Plan &p = e->plan;
     for (int q = 0; q < kSentinels; q++) dummy_op(e, e->h_ops.p[nops + q]);  // targets of the look-ahead requests
@@ -627,7 +767,7 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
         memcpy(e->h_ops.p + p.jobs_off, p.tab_jobs.data(), sizeof(TabJob) * p.tab_jobs.size());
     }
     PlanCache &c = e->plan_cache;
-    c.ops_in.assign((const char *)ops, (const char *)(ops + nops));
+    c.ops_in.assign((const char *)ops_in, (const char *)(ops_in + nops_in));
     c.segs = explicit_segs ? *explicit_segs : std::vector<int>();
     c.version = len_ptrs ? 0 : e->keymap_version;  // (slabs created while building are included; a sweep step's plan is never re-used)
     c.dst = last_dst;
@@ -639,6 +779,17 @@ int finish_and_upload(iqhip_engine *e, const iqhip_node_op *ops, int nops, Units
         if (br == "tab") e->h_ops.p[nops - 1].tabL = nullptr;
         else if (br == "sentinel") e->h_ops.p[nops + kSentinels - 1].pf = nullptr;
         else if (br == "states") e->h_ops.p[0].sr = nullptr;
+        else if (br == "pair_row") {   // a pair-code row on a child that is read as a leaf
+            for (int k = 0; k < nops; k++)
+                if (e->h_ops.p[k].left_kind == CHILD_LEAF && !e->pair_row_of.empty()) { e->h_ops.p[k].sl = e->d_pair_rows.p; break; }
+        } else if (br == "pair_region") {   // a pair child's region (and the launch's allocation with it) moved past the LDS budget
+            for (int k = 0; k < nops; k++)
+                if (e->h_ops.p[k].left_kind == CHILD_PAIR) {
+                    e->h_ops.p[k].lds_left = lds_budget(e);
+                    e->plan.lds_doubles = lds_budget(e) + child_region_blocks(CHILD_PAIR) * e->block;
+                    break;
+                }
+        }
         else if (br == "cherry")
             for (int k = 0; k < nops; k++)
                 if (e->h_ops.p[k].cherry) { e->h_ops.p[k].cherry += 8; break; }   // (inside the buffer, not on a table)
@@ -802,6 +953,7 @@ int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_ds
     if (nops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
     if (plan_is_cached(e, ops, nops, explicit_segs, len_ptrs)) {
         *last_dst = e->plan_cache.dst;
+        mark_virtual_slabs(e);
         return IQHIP_OK;
     }
     e->plan_cache.version = 0;
@@ -811,16 +963,25 @@ int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_ds
     }
     e->plan = Plan();
     e->plan.cherry_model = e->model_version;
+    e->plan.nrows = nops;
+    const iqhip_node_op *const ops_in = ops;
+    const int nops_in = nops;
+    Kept kept;
+    bool removed = false;
+    int rc = select_pair_children(e, ops, nops, explicit_segs, len_ptrs, kept, &removed);
+    if (rc) return rc;
+    if (removed) { ops = kept.ops.data(); nops = (int)kept.ops.size(); }
     Units u;
-    int rc = cut_units(e, ops, nops, explicit_segs, u);
+    rc = cut_units(e, ops, nops, explicit_segs, u);
     // (room for the K2 table job list behind the segment table: at most two leaf children per op)
     if (!rc) rc = ensure_plan_capacity(e, nops + kSentinels + segment_table_ops(u) + devops_for(sizeof(TabJob) * (size_t)(2 * nops + 1)));
-    if (!rc) rc = fill_descriptors(e, ops, nops, u, len_ptrs, last_dst);
+    if (!rc) rc = fill_descriptors(e, ops, nops, u, len_ptrs, last_dst, removed ? &kept : nullptr);
     if (!rc) park_operands(e, nops, u.seg_of);
     if (!rc) rc = assign_leaf_tables(e, nops);
     if (!rc) rc = assign_cherry_tables(e, nops, u.seg_of);
     if (!rc) rc = lay_out_lds(e, nops, u.seg_of);
-    if (!rc) rc = finish_and_upload(e, ops, nops, u, explicit_segs, len_ptrs, *last_dst);
+    if (!rc) rc = finish_and_upload(e, nops, ops_in, nops_in, u, explicit_segs, len_ptrs, *last_dst);
+    if (!rc) mark_virtual_slabs(e);
     return rc;
 }
 

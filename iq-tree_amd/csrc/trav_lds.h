@@ -11,7 +11,7 @@ namespace iqhip {
 constexpr int kTravWg = 256;                        // threads per workgroup of every traversal kernel
 constexpr int kTravMaxLdsBytes = 150 * 1024;        // dynamic LDS every matrix-core traversal kernel is allowed ...
 constexpr int kTravGenericMaxLdsBytes = 160 * 1024; // ... and k_traverse_mfma, which has no static arrays
-constexpr int kTrav4MaxLdsBytes = 152 * 1024;       // k_traverse4: 160 KB minus the static arrays (fold_tail 3.1 KB, the fill's descriptor copies 2.3 KB and row pointers 2 KB)
+constexpr int kTrav4MaxLdsBytes = 150 * 1024;       // k_traverse4: 160 KB minus the static arrays (9.4 KB: fold_tail 3.1 KB, the fill's descriptor copies 4.4 KB -- pair lengths included -- and row pointers 2 KB)
 
 __host__ __device__ constexpr int tipx_doubles(int n, int nx) { return nx * n; }   // the [nx][n] tip vectors of the states beyond n
 
