@@ -924,10 +924,15 @@ int iqhip_debug_plan_layout(iqhip_engine *e, int32_t *out, int nops);
  * iqhip_set_alignment keep the vectors of the submissions made before them.  Memory: the first plan that removes an update
  * allocates one device buffer of ntaxa * nptn_pad bytes (pair-code rows), as large as the state matrix.
  * iqhip_debug_pair_children: node updates removed so far, vectors expanded for a reader so far, updates the last plan removed.
+ * iqhip_debug_pair_rows (any engine, a planning-only one included): slots of the pair-code row table in use; how often the table
+ * started over because a plan's missing pairs did not fit beside the rows present (not counted: the clear that goes with the
+ * buffer's allocation, nor the one on an alignment change); leaf-leaf updates so far that met every condition and stayed real
+ * because the table had no slot left for their pair.  Any pointer may be NULL.
  * iqhip_debug_planner_plain_taxa (planning-only engines, which have no alignment): plain[t] != 0 -- taxon t's row is plain;
  * NULL -- nothing known, nothing is removed (the state after iqhip_debug_create_planner).
  * iqhip_debug_plan_removed (planning-only engines): out[k] = 1 when row k of the last plan's op list was removed. */
 int iqhip_debug_pair_children(iqhip_engine *e, int64_t *ops_removed, int64_t *slabs_expanded, int64_t *last_plan_removed);
+int iqhip_debug_pair_rows(iqhip_engine *e, int64_t *slots_in_use, int64_t *restarts, int64_t *kept_real_for_lack_of_a_row);
 int iqhip_debug_planner_plain_taxa(iqhip_engine *e, const uint8_t *plain);
 int iqhip_debug_plan_removed(iqhip_engine *e, int32_t *out, int nrows);
 

@@ -1105,6 +1105,16 @@ extern "C" int iqhip_debug_pair_children(iqhip_engine *e, int64_t *ops_removed, 
     return IQHIP_OK;
 }
 
+// the pair-code row table (plan.hip select_pair_children, pair_code_row); a planning-only engine counts the same way
+extern "C" int iqhip_debug_pair_rows(iqhip_engine *e, int64_t *slots_in_use, int64_t *restarts, int64_t *kept_real_for_lack_of_a_row) {
+    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
+    if (!e->shards.empty()) e = e->shards[0];
+    if (slots_in_use) *slots_in_use = (int64_t)e->pair_row_of.size();
+    if (restarts) *restarts = e->pair_row_restarts;
+    if (kept_real_for_lack_of_a_row) *kept_real_for_lack_of_a_row = e->pair_ops_without_row;
+    return IQHIP_OK;
+}
+
 // planning-only engines have no alignment: say which taxa hold plain states only (nullptr: none known, nothing is virtualised)
 extern "C" int iqhip_debug_planner_plain_taxa(iqhip_engine *e, const uint8_t *plain) {
     if (!e || !e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_planner_plain_taxa needs a planning-only engine");

@@ -766,6 +766,7 @@ struct iqhip_engine {
     iqhip::DevBuf<uint8_t> d_pair_rows;
     std::unordered_map<uint64_t, int> pair_row_of;   // (taxon_l << 32 | taxon_r) -> slot
     int64_t pair_ops_removed = 0, pair_slabs_expanded = 0;   // iqhip_debug_pair_children
+    int64_t pair_row_restarts = 0, pair_ops_without_row = 0; // iqhip_debug_pair_rows
 
     // key -> slab
     std::unordered_map<uint64_t, int> key2slab;

@@ -244,7 +244,7 @@ int pair_code_row(iqhip_engine *e, int32_t tl, int32_t tr, const uint8_t **row) 
     *row = nullptr;
     auto it = e->pair_row_of.find(pair_key(tl, tr));
     if (it != e->pair_row_of.end()) { *row = e->d_pair_rows.p + (size_t)it->second * P; return IQHIP_OK; }
-    if (e->pair_row_of.size() >= nslots) return IQHIP_OK;
+    if (e->pair_row_of.size() >= nslots) { e->pair_ops_without_row++; return IQHIP_OK; }
     const int slot = (int)e->pair_row_of.size();
     uint8_t *out = e->d_pair_rows.p + (size_t)slot * P;
     if (!e->planner) HIPCHK(launch_pair_codes(e, e->d_states.p + (size_t)tl * P, e->d_states.p + (size_t)tr * P, out));
@@ -258,7 +258,11 @@ int pair_code_row(iqhip_engine *e, int32_t tl, int32_t tr, const uint8_t **row) 
 // slab is marked virtual.  An op is removed when: both children are leaves whose rows hold only states 0 .. 3 and
 // STATE_UNKNOWN; its scaling rule is 0; exactly one later op of this plan consumes its result, nothing else writes that key
 // and it is not the plan's last op; the plan is cut automatically and takes its lengths from the host (no explicit segments,
-// no sweep pointers).  Consumer and producer then share a segment, because the producer no longer exists.
+// no sweep pointers); and its consumer still fits a chunk of its own with that child as a pair child -- both children's regions,
+// their state slots and slot 0 within lds_budget(e) (a pair child's region is 38 blocks, a leaf's 6: at a tight IQHIP_LDS_KB an
+// op that fits with a real cherry below it would not with the table).  A consumer of two such ops: both removed if the two pair
+// regions fit together; else the left one removed and the right one real if that fits; else both real.
+// Consumer and producer then share a segment, because the producer no longer exists.
 // Returns whether anything was removed (then `kept` is the list to plan).
 int select_pair_children(iqhip_engine *e, const iqhip_node_op *ops, int nops, const std::vector<int> *explicit_segs,
                          const double *const *len_ptrs, Kept &kept, bool *any) {
@@ -290,6 +294,32 @@ int select_pair_children(iqhip_engine *e, const iqhip_node_op *ops, int nops, co
         nremoved++;
     }
     if (!nremoved) return IQHIP_OK;
+    // the consumers' fit: what lay_out_lds charges an op that opens a chunk (a vector child: one block, no state slot)
+    const int B = e->block, budget = lds_budget(e), slot_sz = trav4_lds(B).slot_doubles;
+    auto child_need = [&](int32_t kind) { return child_region_blocks(kind) * B + (child_is_table(kind) ? slot_sz : 0); };
+    std::unordered_map<uint64_t, int> candidate;   // key -> the op that may be removed
+    for (int k = 0; k < nops; k++)
+        if (removed[k]) candidate[ops[k].dst_key] = k;
+    for (int k = 0; k < nops; k++) {
+        const iqhip_node_op &o = ops[k];
+        const auto li = o.left_leaf < 0 ? candidate.find(o.left_key) : candidate.end();
+        const auto ri = o.right_leaf < 0 ? candidate.find(o.right_key) : candidate.end();
+        const int l = li == candidate.end() ? -1 : li->second, r = ri == candidate.end() ? -1 : ri->second;
+        if (l < 0 && r < 0) continue;
+        const int32_t lkind = o.left_leaf >= 0 ? CHILD_LEAF : CHILD_PF, rkind = o.right_leaf >= 0 ? CHILD_LEAF : CHILD_PF;
+        auto fits = [&](int32_t a, int32_t b) { return slot_sz + child_need(a) + child_need(b) <= budget; };
+        bool keep_l = l >= 0, keep_r = r >= 0;   // (as pair children)
+        if (l >= 0 && r >= 0) {
+            if (!fits(CHILD_PAIR, CHILD_PAIR)) { keep_r = false; keep_l = fits(CHILD_PAIR, CHILD_PF); }
+        } else if (l >= 0) {
+            keep_l = fits(CHILD_PAIR, rkind);
+        } else {
+            keep_r = fits(lkind, CHILD_PAIR);
+        }
+        if (l >= 0 && !keep_l) { removed[l] = 0; nremoved--; }
+        if (r >= 0 && !keep_r) { removed[r] = 0; nremoved--; }
+    }
+    if (!nremoved) return IQHIP_OK;
     // the code rows: one buffer of ntaxa slots (a tree has at most ntaxa / 2 leaf-leaf nodes); a search that has walked through
     // more pairs than that starts over -- kernels still reading the old rows are ahead of the new builds on the stream
     const size_t P = (size_t)e->nptn_pad;
@@ -300,7 +330,10 @@ int select_pair_children(iqhip_engine *e, const iqhip_node_op *ops, int nops, co
     size_t nmissing = 0;   // pairs of this plan that have no row yet (a pair occurs once in a tree)
     for (int k = 0; k < nops; k++)
         nmissing += removed[k] && !e->pair_row_of.count(pair_key(ops[k].left_leaf, ops[k].right_leaf));
-    if (e->pair_row_of.size() + nmissing > e->d_pair_rows.cap / P) e->pair_row_of.clear();
+    if (e->pair_row_of.size() + nmissing > e->d_pair_rows.cap / P) {
+        e->pair_row_of.clear();
+        e->pair_row_restarts++;
+    }
     for (int k = 0; k < nops; k++) {
         if (removed[k]) {
             const iqhip_node_op &o = ops[k];
@@ -570,7 +603,8 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         // 4-state path: each leaf / pair child also stages one state byte per thread in LDS
         const int nleaf = child_is_table(d.left_kind) + child_is_table(d.right_kind);
         const int need = szl + szr + nleaf * slot_sz;
-        if (need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
+        // (an op must fit a chunk of its own, slot 0 included: what check_plan holds every chunk to)
+        if (slot_sz + need > budget) return fail(IQHIP_ERR_UNSUPPORTED, "nstates*ncat too large for the LDS plan regions");
         // (k_traverse4 keeps one row pointer per slot of the chunk in a fixed array)
         const bool rows_full = !e->mfma && slots + nleaf > kTrav4RowSlots;
         if ((used + need > budget || rows_full || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {

@@ -31,9 +31,39 @@ def removed_rows(lib, e, nrows):
     return [k for k in range(nrows) if out[k]]
 
 
-def expected_removed(ops, but=()):
+SLOT_DOUBLES = 32                  # trav_lds.h trav4_lds().slot_doubles: one state byte per thread of the workgroup
+
+
+def expected_removed(ops, but=(), budget=None, block=BLOCK):
     """the rule of select_pair_children, restated: both children plain leaves, scaling rule 0, exactly one later consumer, not
-    the last op"""
+    the last op; and, with `budget` (doubles, lds_budget(e)): the consumer fits a chunk of its own -- slot 0, both children's
+    regions and the state slots of the table children -- with the op as a pair child.  A consumer of two candidates: both if
+    they fit together, else the left one alone (the right one a vector) if that fits, else neither."""
+    cand = candidates(ops, but)
+    if budget is None:
+        return cand
+    need = {"pair": PAIR_BLOCKS * block + SLOT_DOUBLES, "leaf": LEAF_BLOCKS * block + SLOT_DOUBLES, "vector": block}
+
+    def fits(a, b):
+        return SLOT_DOUBLES + need[a] + need[b] <= budget
+    by_key = {ops[k].dst_key: k for k in cand}
+    out = []
+    for p in ops:
+        l = by_key.get(p.left_key) if p.left_leaf < 0 else None
+        r = by_key.get(p.right_key) if p.right_leaf < 0 else None
+        if l is not None and r is not None:
+            if fits("pair", "pair"):
+                out += [l, r]
+            elif fits("pair", "vector"):
+                out.append(l)
+        elif l is not None and fits("pair", "leaf" if p.right_leaf >= 0 else "vector"):
+            out.append(l)
+        elif r is not None and fits("leaf" if p.left_leaf >= 0 else "vector", "pair"):
+            out.append(r)
+    return sorted(out)
+
+
+def candidates(ops, but=()):
     out = []
     for k, o in enumerate(ops[:-1]):
         if o.left_leaf < 0 or o.right_leaf < 0 or o.flags & 3 or o.left_leaf in but or o.right_leaf in but:
