@@ -894,7 +894,11 @@ int iqhip_debug_path_counts(iqhip_engine *e, int64_t *out, int n);
  * iqhip_update_partials would (key -> slab map, canonical child order, staging, LDS chunks, K2 table slots, look-ahead
  * sentinels) and validates the kernels' contract on them: every pointer of every descriptor, used or not, is a live
  * allocation of the right kind (the traversal kernels request op k+1's inputs unconditionally).  The same check runs on
- * a real engine before every plan upload when IQHIP_CHECK_PLAN=1.  Every other entry point fails on a planner. */
+ * a real engine before every plan upload when IQHIP_CHECK_PLAN=1.  Every other entry point fails on a planner.
+ * A planner keeps the plan cache a real engine keeps: iqhip_debug_plan with the op list of the call before it (same keys,
+ * leaves, lengths; nothing created, released or invalidated in between) finds the plan cached, plans nothing and checks
+ * nothing again, and counts what a cached submission counts (pair slabs marked again, cherry ops, the fill image below).
+ * iqhip_debug_planner_plain_taxa and iqhip_debug_planner_event(e, 1) drop the cached plan. */
 int iqhip_debug_create_planner(iqhip_engine **out, int nstates /* 4, 20, 64 */, int ncat, int64_t nptn, int ntaxa,
                                int num_cus, int state_unknown, int nclass);
 int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops);
@@ -935,6 +939,24 @@ int iqhip_debug_pair_children(iqhip_engine *e, int64_t *ops_removed, int64_t *sl
 int iqhip_debug_pair_rows(iqhip_engine *e, int64_t *slots_in_use, int64_t *restarts, int64_t *kept_real_for_lack_of_a_row);
 int iqhip_debug_planner_plain_taxa(iqhip_engine *e, const uint8_t *plain);
 int iqhip_debug_plan_removed(iqhip_engine *e, int32_t *out, int nrows);
+
+/* The fill image of the 4-state traversal (4-state engines of at most 8 categories).  What a chunk fill leaves in
+ * LDS besides the leaf states depends on the plan and the model only.  When a submission finds its plan cached (the same op list,
+ * lengths included, as the one before), the engine builds those LDS contents once into a device buffer, chunk by chunk, and the
+ * traversal's workgroups copy them; a later submission of the same plan under the same model copies them again.  A new plan,
+ * iqhip_set_model and iqhip_set_alignment make the image stale; plans whose lengths lie on the device, plans of a few ops that
+ * travel in the kernel arguments, and a submission that plans anew never use one.  Results are bit-identical either way.
+ * iqhip_debug_fill_image (any engine, a planning-only one included): submissions so far that built the image (planning-only:
+ * would have), submissions that copied an image already built, bytes of the current plan's image (0: it can have none).  Any
+ * pointer may be NULL.
+ * Planning-only engines: iqhip_debug_plan_submit is iqhip_debug_plan with explicit segments (nsegs > 0: segment sizes) or with
+ * every branch length on the device (device_lengths != 0); iqhip_debug_planner_event(e, 0) does to the planner's state what
+ * iqhip_set_model does, (e, 1) what iqhip_set_alignment does; iqhip_debug_fill_image_chunks: out[2 i], out[2 i + 1] = byte
+ * offset and byte extent of chunk i of the last plan's image (at most cap pairs), *nchunks = the plan's chunks. */
+int iqhip_debug_fill_image(iqhip_engine *e, int64_t *built, int64_t *reused, int64_t *bytes);
+int iqhip_debug_plan_submit(iqhip_engine *e, const iqhip_node_op *ops, int nops, const int32_t *segs, int nsegs, int device_lengths);
+int iqhip_debug_planner_event(iqhip_engine *e, int what);
+int iqhip_debug_fill_image_chunks(iqhip_engine *e, int64_t *out, int cap, int *nchunks);
 
 /* Debugging aids, no reference counterpart: the library's memory accounting.  Every device and pinned-host allocation of
  * every engine and partition group in this process goes through one allocate / free pair, which counts bytes.

@@ -38,7 +38,8 @@ IQHIP_SYMBOLS = [
     "iqhip_comm_size", "iqhip_update_partials_async", "iqhip_lnl_from_theta_async",
     "iqhip_newton_host_init", "iqhip_newton_host_update", "iqhip_newton_host_result",
     "iqhip_debug_create_planner", "iqhip_debug_plan", "iqhip_timing_plan_bytes", "iqhip_timing_collective_read", "iqhip_optimize_sweep", "iqhip_debug_cherry_tables",
-    "iqhip_debug_path_counts", "iqhip_debug_plan_shape", "iqhip_debug_plan_layout", "iqhip_debug_pair_children", "iqhip_debug_pair_rows", "iqhip_debug_planner_plain_taxa", "iqhip_debug_plan_removed", "iqhip_debug_memory", "iqhip_debug_fail_alloc",
+    "iqhip_debug_path_counts", "iqhip_debug_plan_shape", "iqhip_debug_plan_layout", "iqhip_debug_pair_children", "iqhip_debug_pair_rows", "iqhip_debug_planner_plain_taxa", "iqhip_debug_plan_removed",
+    "iqhip_debug_fill_image", "iqhip_debug_plan_submit", "iqhip_debug_planner_event", "iqhip_debug_fill_image_chunks", "iqhip_debug_memory", "iqhip_debug_fail_alloc",
     "iqhip_ptnlh_reserve", "iqhip_ptnlh_put_current", "iqhip_ptnlh_fetch", "iqhip_optimize_branch_batch_rows",
     "iqhip_branch_tests", "iqhip_ptnlh_rell",
     "iqhip_ptnlh_upload", "iqhip_gen_boot_samples", "iqhip_ptnlh_diff_variance", "iqhip_tree_tests", "iqhip_multiscale_bp",
@@ -237,6 +238,10 @@ def libiqhip():
     lib.iqhip_debug_plan_shape.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.iqhip_debug_plan_layout.argtypes = [vp, C.POINTER(C.c_int32), C.c_int]
     lib.iqhip_debug_pair_rows.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.iqhip_debug_fill_image.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.iqhip_debug_plan_submit.argtypes = [vp, C.POINTER(NodeOp), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int]
+    lib.iqhip_debug_planner_event.argtypes = [vp, C.c_int]
+    lib.iqhip_debug_fill_image_chunks.argtypes = [vp, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int)]
     lib.iqhip_debug_memory.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.iqhip_debug_memory.restype = None
     lib.iqhip_debug_fail_alloc.argtypes = [C.c_int]

@@ -643,6 +643,7 @@ static int cherry_sync_model(iqhip_engine *e, const double *eval, const double *
         rc = iqhip_create(&e->pair, e->device, e->n, e->ncat, npairs, 2);
         if (rc) return rc;
         e->pair->cherry_on = false;
+        e->pair->fill_image.on = false;
         e->pair->check_plans = e->check_plans;
         rc = iqhip_set_stream(e->pair, e->stream);
         if (rc) return rc;
@@ -846,6 +847,8 @@ int iqhip::submit_traverse(iqhip_engine *e, const iqhip_node_op *ops, int nops, 
     if (e->plan.uses_cherry)
         for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops.p[k].cherry != nullptr;
     timing_begin(e);
+    rc = fill_image_submission(e);   // (k_traverse4: the producer's launch, when the cached plan's image is stale; inside the timed span)
+    if (rc) return rc;
     const int *table = reinterpret_cast<const int *>(e->d_ops.p + e->plan.table_off);
     {   // the stages of independent subtrees, level by level: one launch each, one set of workgroups per unit
         int off = 2;
@@ -1112,6 +1115,17 @@ extern "C" int iqhip_debug_pair_rows(iqhip_engine *e, int64_t *slots_in_use, int
     if (slots_in_use) *slots_in_use = (int64_t)e->pair_row_of.size();
     if (restarts) *restarts = e->pair_row_restarts;
     if (kept_real_for_lack_of_a_row) *kept_real_for_lack_of_a_row = e->pair_ops_without_row;
+    return IQHIP_OK;
+}
+
+// k_traverse4's fill image (plan.hip fill_image_submission): submissions that launched the producer (a planning-only engine:
+// that would have), submissions that copied an image already there, bytes of the current plan's image (0: it can have none)
+extern "C" int iqhip_debug_fill_image(iqhip_engine *e, int64_t *built, int64_t *reused, int64_t *bytes) {
+    if (!e) return fail(IQHIP_ERR_INVALID, "null engine");
+    if (!e->shards.empty()) e = e->shards[0];
+    if (built) *built = e->fill_image.built;
+    if (reused) *reused = e->fill_image.reused;
+    if (bytes) *bytes = (e->plan.image_ok && !e->plan.small) ? e->plan.image_doubles * (int64_t)sizeof(double) : 0;
     return IQHIP_OK;
 }
 
@@ -1475,9 +1489,20 @@ extern "C" int iqhip_debug_create_planner(iqhip_engine **out, int nstates, int n
 // build the descriptors of one submission exactly as iqhip_update_partials would and validate them (check_plan)
 extern "C" int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops) {
     if (!e || !e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_plan needs a planning-only engine");
-    if (nops < 0 || (nops > 0 && !ops)) return fail(IQHIP_ERR_INVALID, "bad ops array");
+    return iqhip_debug_plan_submit(e, ops, nops, nullptr, 0, 0);
+}
+
+// ... with explicit segments (nsegs > 0) or with every length on the device (device_lengths: the pointers are fake addresses)
+extern "C" int iqhip_debug_plan_submit(iqhip_engine *e, const iqhip_node_op *ops, int nops, const int32_t *segs, int nsegs,
+                                       int device_lengths) {
+    if (!e || !e->planner) return fail(IQHIP_ERR_INVALID, "iqhip_debug_plan_submit needs a planning-only engine");
+    if (nops < 0 || (nops > 0 && !ops) || nsegs < 0 || (nsegs > 0 && !segs)) return fail(IQHIP_ERR_INVALID, "bad ops array");
     int last_dst = -1;
-    const int rc = build_plan(e, ops, nops, &last_dst, nullptr);
+    const std::vector<int> seg_list(segs, segs + nsegs);
+    std::vector<const double *> lp;
+    if (device_lengths) lp.assign((size_t)2 * nops, e->dummy.plh.p);
+    int rc = build_plan(e, ops, nops, &last_dst, nsegs > 0 ? &seg_list : nullptr, device_lengths ? lp.data() : nullptr);
+    if (!rc) rc = fill_image_submission(e);
     if (!rc) {   // (what submit_traverse would count: iqhip_debug_cherry_tables)
         e->cherry_built_total += (int64_t)e->plan.cherry_jobs.size();
         for (int slot : e->plan.cherry_jobs) e->cherry_slots[slot].model_version = e->model_version;   // ("built")
@@ -1485,6 +1510,32 @@ extern "C" int iqhip_debug_plan(iqhip_engine *e, const iqhip_node_op *ops, int n
         for (int k = 0; k < nops; k++) e->cherry_ops_total += e->h_ops.p[k].cherry != nullptr;
     }
     return rc;
+}
+
+// what the engine's state goes through between submissions, on a planning-only engine: 0 iqhip_set_model, 1 iqhip_set_alignment
+extern "C" int iqhip_debug_planner_event(iqhip_engine *e, int what) {
+    if (!e || !e->planner || what < 0 || what > 1) return fail(IQHIP_ERR_INVALID, "iqhip_debug_planner_event needs a planning-only engine and event 0 or 1");
+    if (what == 0) e->model_version++;
+    else { e->pair_row_of.clear(); e->plan_cache.invalidate(); }
+    return IQHIP_OK;
+}
+
+// the fill image of the last plan, chunk by chunk: out[2 i] = byte offset, out[2 i + 1] = byte extent of chunk i; returns through
+// *nchunks how many there are (at most `cap` pairs are written)
+extern "C" int iqhip_debug_fill_image_chunks(iqhip_engine *e, int64_t *out, int cap, int *nchunks) {
+    if (!e || !e->planner || !nchunks || (cap > 0 && !out)) return fail(IQHIP_ERR_INVALID, "iqhip_debug_fill_image_chunks needs a planning-only engine");
+    int n = 0;
+    for (int k = 0; k < e->plan.small_nops && !e->mfma; k += e->h_ops.p[k].chunk_nops, n++) {
+        int regs = 0;
+        for (int q = k; q < k + e->h_ops.p[k].chunk_nops; q++) {
+            const DevOp &d = e->h_ops.p[q];
+            regs = std::max(regs, std::max(d.lds_left + child_region_blocks(d.left_kind) * e->block,
+                                           d.lds_right + child_region_blocks(d.right_kind) * e->block));
+        }
+        if (n < cap) { out[2 * n] = (int64_t)e->h_ops.p[k].image_off * 8; out[2 * n + 1] = (int64_t)regs * 8; }
+    }
+    *nchunks = n;
+    return IQHIP_OK;
 }
 
 // the shape of the last plan and of the launches it would get (tests/test_plan_check.py pins them)

@@ -89,7 +89,9 @@ struct __attribute__((aligned(16))) DevOp {
     // keep it in registers (kernels_mfma.hip k_cherry_transpose); nullptr: compute the three matrix products
     const double *cherry;
     int32_t chunk_slots;   // 4-state path, on the first op of an LDS chunk: leaf-state slots of the chunk, the dummy slot 0 included
-    int32_t _pad_slots;
+    // k_traverse4: where the chunk this op belongs to lies in the engine's fill image (doubles from its base, even: 16 bytes;
+    // every op of the chunk carries it, the kernel reads the first op's); 0 in plans of other kernels
+    int32_t image_off;
     // CHILD_PAIR children: the pendant branch lengths of the removed leaf-leaf op, {left child: its left, its right; right child:
     // its left, its right}, and the row of the caller's op list the removed op answers (-1: none) -- this op writes that row's
     // wave partial, always 0.0 (a leaf-leaf update never rescales)
@@ -241,6 +243,10 @@ struct Plan {
     struct Virtual { int slab; int32_t taxon_l, taxon_r; double len_l, len_r; };
     std::vector<Virtual> virt;
     int nrows = 0;
+    // k_traverse4: doubles of the plan's fill image, the sum of its chunks' region extents (0: a plan of another kernel), and
+    // whether the plan may have one at all (lay_out_lds: not with device-side lengths; small plans are excluded at submission)
+    int64_t image_doubles = 0;
+    bool image_ok = false;
 };
 
 // What the descriptors in d_ops were built from: an identical op list (same keys, leaves, lengths) with an unchanged key
@@ -768,6 +774,17 @@ struct iqhip_engine {
     int64_t pair_ops_removed = 0, pair_slabs_expanded = 0;   // iqhip_debug_pair_children
     int64_t pair_row_restarts = 0, pair_ops_without_row = 0; // iqhip_debug_pair_rows
 
+    // k_traverse4's fill image (DESIGN.md 3.1 "Fill image"): every chunk's plan regions as the in-kernel fill leaves them, built by
+    // k_fill4_image for the current plan and model and copied into LDS by the traversal instead of being computed per workgroup.
+    // model: the model_version the image was built at (0: stale -- every build_plan that planned anew resets it).  plan_hit: the
+    // last build_plan found its plan cached.  use: the launches of the submission in progress take the copy path.
+    struct FillImage {
+        iqhip::DevBuf<double> buf;
+        uint64_t model = 0;
+        bool on = true, plan_hit = false, use = false;
+        int64_t built = 0, reused = 0;   // iqhip_debug_fill_image
+    } fill_image;
+
     // key -> slab
     std::unordered_map<uint64_t, int> key2slab;
     std::vector<iqhip::Slab> slabs;
@@ -1012,6 +1029,11 @@ int slab_for_key(iqhip_engine *e, uint64_t key, bool create, int *idx);
 int expand_virtual_slabs(iqhip_engine *e);   // all of them: before the model, the tip table or the alignment changes
 hipError_t launch_pair_expand(iqhip_engine *e, const Slab &s);                                        // kernels_valu4.hip
 hipError_t launch_pair_codes(iqhip_engine *e, const uint8_t *row_l, const uint8_t *row_r, uint8_t *out);   // kernels_valu4.hip
+// k_traverse4's fill image.  fill_image_submission (plan.hip), after every build_plan: decides whether the submission's launches
+// copy the image (e->fill_image.use), counts, and launches the producer when the image is stale -- a planning-only engine counts
+// the same way.  launch_fill4_image (kernels_valu4.hip): one workgroup per (op, child) region of the current plan.
+int fill_image_submission(iqhip_engine *e);
+hipError_t launch_fill4_image(iqhip_engine *e, int nops);
 bool cherry_candidate(const iqhip_engine *e);   // engine.hip: the engine uses cherry tables (DevOp::cherry)
 
 // plan.hip -- the planner.  build_plan: one submission's descriptors into h_ops and d_ops, e->plan; *last_dst = the slab

@@ -83,6 +83,7 @@ struct Trav4Args {
     const double *eval;
     const double *rates;
     const double *props;
+    const double *image;   // the fill image of the plan (chunk at DevOp::image_off doubles); nullptr: fill in the kernel
     double *pattern_lh;
     double *slab;      // [nvals][nwaves] wave partials
     int64_t ntiles;
@@ -422,92 +423,91 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
             asm volatile("" ::"s"(touched));
         }
         [[maybe_unused]] unsigned long long c0a = T4_CLK();
-        for (int o0 = 0; o0 < kn; o0 += 64) {
-            const int on = kn - o0 < 64 ? kn - o0 : 64;
-            if (o0 > 0) {   // (the previous pass has read its list)
-                lds_barrier();
-                if (threadIdx.x == 0) s_npair = 0;
-                lds_barrier();
+        // The regions' contents depend on the plan and the model only.  Where the engine has them as an image (built once by
+        // k_fill4_image below, the same expressions), the workgroup copies its chunk: 16 bytes per lane straight into LDS, a wave
+        // a KiB per instruction, the waves taking the chunk's KiBs in turn.  The chunk's extent is the distance to the next
+        // chunk's offset (the sentinel carries the image's end) and a multiple of 32 bytes, so masking lanes ends the copy
+        // exactly: nothing is written behind the regions, where the state requests above are landing.
+        if (A.image != nullptr) {
+            const int ioff = ops[k].image_off;
+            int ebytes = (ops[k + kn].image_off - ioff) * 8;
+            // (never binds: lay_out_lds makes lds_reg_doubles the largest chunk's extent and check_plan holds every chunk to it;
+            // kept so that no descriptor can make the copy write behind the regions)
+            ebytes = ebytes < A.lds_reg_doubles * 8 ? ebytes : A.lds_reg_doubles * 8;
+            const char *const src = reinterpret_cast<const char *>(A.image + ioff);
+            // (The lane's offset is made here from the thread id, which the fill keeps live anyway, behind an empty asm: as a
+            // loop invariant the compiler kept it and the lane's image address in three registers across the whole op loop,
+            // and the eight-category kernel gained 16 bytes of scratch.)
+            uint32_t tx = threadIdx.x;
+            asm volatile("" : "+v"(tx));
+            const uint32_t l16 = (tx & 63u) * 16u;
+            for (int p = wave * 1024; p < ebytes; p += WPB * 1024) {
+                if (p + (int)l16 < ebytes)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + p + l16),
+                                                     (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(s_reg) + p), 16, 0, 0);
             }
-            for (int t = threadIdx.x; t < on; t += kTravWg) {
-                const CONST_AS DevOp &d = ops[k + o0 + t];
-                s_opi[t][0] = d.lds_left;
-                s_opi[t][1] = d.lds_right;
-                s_opi[t][2] = d.left_kind == CHILD_LEAF ? 1 : (d.left_kind == CHILD_PAIR ? 2 : 0);
-                s_opi[t][3] = d.right_kind == CHILD_LEAF ? 1 : (d.right_kind == CHILD_PAIR ? 2 : 0);
-                s_opl[t][0] = op_child_len(d, 0);
-                s_opl[t][1] = op_child_len(d, 1);
-#pragma unroll
-                for (int q = 0; q < 4; q++) s_opl[t][2 + q] = d.pair_len[q];
-                // (the list's order is whatever the atomics give: every entry is worked on independently)
-                if (d.left_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t;
-                if (d.right_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t + 1;
-            }
-            lds_barrier();
-            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {  // phase 1: exponentials
-                const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-                s_reg[s_opi[o][child] + e] = exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][child]));
-            }
-            // ... and of the two pendant branches below each PAIR child of the pass (s_pair: the list the staging made), into the
-            // two leaf-shaped regions [ex][table 5] behind its table: the expression above, so they are the bits the removed op
-            // would have made
-            const int np = s_npair;
-            for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {
-                const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
-                s_reg[s_opi[o][child] + (1 + kPairRows + 6 * w) * B + e] =
-                    exp(s_model[16 + (e & 3)] * (s_model[20 + (e >> 2)] * s_opl[o][2 + 2 * child + w]));
-            }
-            lds_barrier();
-            c0a = T4_CLK();
-            // phase 2: leaf tables (K2).  One item = one (op, child, category, x): the four rounded products E = U[x][.] * ex are
-            // made once and serve the table's four state rows (A, C, G, T); the fifth row, STATE_UNKNOWN, is exactly 1.0
-            // (phylokernel.h:228-232).  (Entry by entry -- every entry remaking its E -- this phase was 14.6 k of a wave's cycles.)
-            auto leaf_table = [&](double *reg, int e) {
-                const int c = e >> 2, x = e & 3;
-                const LeafE4 E = leaf_e4(s_model + x * 4, reg + c * 4);   // (trav_phases.h: rounding and association)
-#pragma unroll
-                for (int row = 0; row < 4; row++) reg[B + row * B + e] = E.entry(s_tip + row * 4);
-                reg[B + 4 * B + e] = 1.0;
-            };
-            for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {
-                const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
-                if (s_opi[o][2 + child] == 1) leaf_table(s_reg + s_opi[o][child], e);
-            }
-            if (np == 0) continue;   // (uniform: every thread read the same count)
-            for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {   // the K2 tables of the removed ops' two leaves
-                const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
-                leaf_table(s_reg + s_opi[o][child] + (1 + kPairRows + 6 * w) * B, e);
-            }
-            lds_barrier();
-            // phase 2b: pair tables.  One item = one (PAIR child, category, pair code): the removed leaf-leaf op's result for that
-            // pair of states -- the product of the two K2 entries, the U^-1 contraction in node_update4's shape -- and then what
-            // node_update4 makes of a vector child: ex .* o, U times that.  Every product and fma is the one a lane would have
-            // executed, so the table row is the bits the op loop produced when the op still ran and its vector went through memory.
-            // (U and U^-1 as the op loop takes them, scalar operands: read from the LDS copies this body gathered all its operands at
-            // once, on top of prev, PF and HOLD, which are live across the fill -- 250 VGPRs at four categories, scratch above)
-#pragma unroll 1
-            for (int t = threadIdx.x; t < np * C * kPairRows; t += kTravWg) {
-                const int pi = t / (C * kPairRows), q = t - pi * (C * kPairRows), c = q / kPairRows, code = q - c * kPairRows;
-                const int o = s_pair[pi] >> 1, child = s_pair[pi] & 1, sa = code / 5, sb = code - 5 * sa;
-                double *reg = s_reg + s_opi[o][child];
-                const double *ta = reg + (2 + kPairRows + sa) * B + c * 4, *tb = reg + (8 + kPairRows + sb) * B + c * 4;
-                double tmp[4], l[4];
-#pragma unroll
-                for (int x = 0; x < 4; x++) tmp[x] = __dmul_rn(ta[x], tb[x]);
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    double v = __dmul_rn(uinv[i * 4], tmp[0]);
-                    v = fma(uinv[i * 4 + 1], tmp[1], v);
-                    v = fma(uinv[i * 4 + 2], tmp[2], v);
-                    v = fma(uinv[i * 4 + 3], tmp[3], v);
-                    l[i] = __dmul_rn(reg[c * 4 + i], v);
+        } else {
+            for (int o0 = 0; o0 < kn; o0 += 64) {
+                const int on = kn - o0 < 64 ? kn - o0 : 64;
+                if (o0 > 0) {   // (the previous pass has read its list)
+                    lds_barrier();
+                    if (threadIdx.x == 0) s_npair = 0;
+                    lds_barrier();
                 }
-#pragma unroll
-                for (int x = 0; x < 4; x++) {
-                    double v = __dmul_rn(U[x * 4], l[0]);
-                    v = fma(U[x * 4 + 1], l[1], v);
-                    v = fma(U[x * 4 + 2], l[2], v);
-                    reg[B + code * B + c * 4 + x] = fma(U[x * 4 + 3], l[3], v);
+                for (int t = threadIdx.x; t < on; t += kTravWg) {
+                    const CONST_AS DevOp &d = ops[k + o0 + t];
+                    s_opi[t][0] = d.lds_left;
+                    s_opi[t][1] = d.lds_right;
+                    s_opi[t][2] = d.left_kind == CHILD_LEAF ? 1 : (d.left_kind == CHILD_PAIR ? 2 : 0);
+                    s_opi[t][3] = d.right_kind == CHILD_LEAF ? 1 : (d.right_kind == CHILD_PAIR ? 2 : 0);
+                    s_opl[t][0] = op_child_len(d, 0);
+                    s_opl[t][1] = op_child_len(d, 1);
+    #pragma unroll
+                    for (int q = 0; q < 4; q++) s_opl[t][2 + q] = d.pair_len[q];
+                    // (the list's order is whatever the atomics give: every entry is worked on independently)
+                    if (d.left_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t;
+                    if (d.right_kind == CHILD_PAIR) s_pair[atomicAdd(&s_npair, 1)] = 2 * t + 1;
+                }
+                lds_barrier();
+                for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {  // phase 1: exponentials
+                    const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
+                    s_reg[s_opi[o][child] + e] = fill4_exp(s_model, e, s_opl[o][child]);
+                }
+                // ... and of the two pendant branches below each PAIR child of the pass (s_pair: the list the staging made), into the
+                // two leaf-shaped regions [ex][table 5] behind its table: the expression above, so they are the bits the removed op
+                // would have made
+                const int np = s_npair;
+                for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {
+                    const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
+                    s_reg[s_opi[o][child] + (1 + kPairRows + 6 * w) * B + e] = fill4_exp(s_model, e, s_opl[o][2 + 2 * child + w]);
+                }
+                lds_barrier();
+                c0a = T4_CLK();
+                // phase 2: leaf tables (K2).  One item = one (op, child, category, x): the four rounded products E = U[x][.] * ex are
+                // made once and serve the table's four state rows (A, C, G, T); the fifth row, STATE_UNKNOWN, is exactly 1.0
+                // (phylokernel.h:228-232).  (Entry by entry -- every entry remaking its E -- this phase was 14.6 k of a wave's cycles.)
+                auto leaf_table = [&](double *reg, int e) { fill4_leaf_table(reg, B, e, s_model, s_tip); };   // (trav_phases.h: rounding and association)
+                for (int t = threadIdx.x; t < on * 2 * B; t += kTravWg) {
+                    const int o = t / (2 * B), r = t - o * (2 * B), child = r / B, e = r - child * B;
+                    if (s_opi[o][2 + child] == 1) leaf_table(s_reg + s_opi[o][child], e);
+                }
+                if (np == 0) continue;   // (uniform: every thread read the same count)
+                for (int t = threadIdx.x; t < np * 2 * B; t += kTravWg) {   // the K2 tables of the removed ops' two leaves
+                    const int pi = t / (2 * B), r = t - pi * (2 * B), w = r / B, e = r - w * B, o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
+                    leaf_table(s_reg + s_opi[o][child] + (1 + kPairRows + 6 * w) * B, e);
+                }
+                lds_barrier();
+                // phase 2b: pair tables.  One item = one (PAIR child, category, pair code): the removed leaf-leaf op's result for that
+                // pair of states -- the product of the two K2 entries, the U^-1 contraction in node_update4's shape -- and then what
+                // node_update4 makes of a vector child: ex .* o, U times that.  Every product and fma is the one a lane would have
+                // executed, so the table row is the bits the op loop produced when the op still ran and its vector went through memory.
+                // (U and U^-1 as the op loop takes them, scalar operands: read from the LDS copies this body gathered all its operands at
+                // once, on top of prev, PF and HOLD, which are live across the fill -- 250 VGPRs at four categories, scratch above)
+    #pragma unroll 1
+                for (int t = threadIdx.x; t < np * C * kPairRows; t += kTravWg) {
+                    const int pi = t / (C * kPairRows), q = t - pi * (C * kPairRows), c = q / kPairRows, code = q - c * kPairRows;
+                    const int o = s_pair[pi] >> 1, child = s_pair[pi] & 1;
+                    fill4_pair_row(s_reg + s_opi[o][child], B, c, code, U, uinv);
                 }
             }
         }
@@ -516,6 +516,7 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
         // above.  SP = 2 (a lane owns half a pattern's categories, 32 patterns per wave): through registers, sixteen ops =
         // thirty-two bytes in flight at a time, unconditionally -- sl / sr of a non-leaf child point at a valid row and its
         // slot 0 is never read.
+        // (the image's copy, where there is one, is waited for here as well: SP = 2 at the closing barrier)
         if constexpr (SP == 1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else
@@ -538,6 +539,7 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
                 }
             }
         }
+        if constexpr (SP == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the image's copy; the barrier below waits as much)
         __syncthreads();
         if (!active) { k += kn; continue; }
 #ifdef IQHIP_T4_TRACE
@@ -748,6 +750,7 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
     A.eval = e->d_eval;
     A.rates = e->d_rates;
     A.props = e->d_props;
+    A.image = e->fill_image.use ? e->fill_image.buf.p : nullptr;
     A.pattern_lh = e->d_pattern_lh.p;
     A.slab = e->d_slab.p;
     A.ntiles = e->ntiles;
@@ -782,6 +785,65 @@ hipError_t launch_traverse4(iqhip_engine *e, const int *seg_table, int nsegs, bo
         case 8: return launch_trav_c<8>(e, A);
         default: return hipErrorInvalidValue;
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// The fill image's producer: one wave per (op, child) region of the plan in d_ops.  The region is made in LDS with the items of
+// k_traverse4's fill (trav_phases.h 7: phase 1, 2, 2b, a barrier between them as there) and written to its place in the image:
+// chunk offset + the region's LDS offset, so a chunk's part of the image is its s_reg byte for byte.  Regions do not depend on
+// each other; a plan of 34 ops is 68 workgroups of a few hundred items.
+// ---------------------------------------------------------------------------------------
+template <int C>
+__global__ __launch_bounds__(64) void k_fill4_image(const DevOp *__restrict__ ops, const double *__restrict__ evec,
+                                                    const double *__restrict__ inv_evec, const double *__restrict__ eval,
+                                                    const double *__restrict__ rates, const double *__restrict__ tip,
+                                                    double *__restrict__ image) {
+    constexpr int B = 4 * C;
+    __shared__ double s_model[32], s_tip[16], s_r[child_region_blocks(CHILD_PAIR) * B];
+    const int t = threadIdx.x, child = blockIdx.x & 1;
+    const DevOp &d = ops[blockIdx.x >> 1];
+    const int kind = child ? d.right_kind : d.left_kind;
+    if (t < 20 + C) s_model[t] = t < 16 ? evec[t] : (t < 20 ? eval[t - 16] : rates[t - 20]);
+    if (t < 16) s_tip[t] = tip[t];
+    __syncthreads();
+    if (t < B) s_r[t] = fill4_exp(s_model, t, child ? d.right_len : d.left_len);
+    if (kind == CHILD_PAIR && t < 2 * B) {
+        const int w = t / B, e = t - w * B;
+        s_r[(1 + kPairRows + 6 * w) * B + e] = fill4_exp(s_model, e, d.pair_len[2 * child + w]);
+    }
+    __syncthreads();
+    if (kind == CHILD_LEAF && t < B) fill4_leaf_table(s_r, B, t, s_model, s_tip);
+    if (kind == CHILD_PAIR) {   // (uniform: one region per workgroup)
+        if (t < 2 * B) {
+            const int w = t / B, e = t - w * B;
+            fill4_leaf_table(s_r + (1 + kPairRows + 6 * w) * B, B, e, s_model, s_tip);
+        }
+        __syncthreads();
+        const CONST_AS double *U = as_const(evec), *uinv = as_const(inv_evec);
+        for (int q = t; q < C * kPairRows; q += 64) {
+            const int c = q / kPairRows, code = q - c * kPairRows;
+            fill4_pair_row(s_r, B, c, code, U, uinv);
+        }
+    }
+    __syncthreads();
+    double *const out = image + d.image_off + (child ? d.lds_right : d.lds_left);
+    const int n = child_region_blocks(kind) * B;
+    for (int q = t; q < n; q += 64) out[q] = s_r[q];
+}
+
+hipError_t launch_fill4_image(iqhip_engine *e, int nops) {
+    if (nops <= 0) return hipSuccess;
+#define IQ_FI(Cv)                                                                                                         \
+    case Cv:                                                                                                              \
+        hipLaunchKernelGGL(k_fill4_image<Cv>, dim3((unsigned)(2 * nops)), dim3(64), 0, e->stream, e->d_ops.p, e->d_evec,  \
+                           e->d_inv_evec, e->d_eval, e->d_rates, e->d_tip, e->fill_image.buf.p);                          \
+        break;
+    switch (e->ncat) {
+        IQ_FI(1) IQ_FI(2) IQ_FI(3) IQ_FI(4) IQ_FI(5) IQ_FI(6) IQ_FI(7) IQ_FI(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef IQ_FI
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------

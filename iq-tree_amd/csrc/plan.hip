@@ -596,8 +596,20 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
     const int pair_sz = child_region_blocks(CHILD_PAIR) * B;   // (k_traverse4 only: no other plan holds a PAIR child)
     const int slot_sz = e->mfma ? 0 : trav4_lds(B).slot_doubles;   // (slot 0: the non-leaf children's)
     int chunk_start = 0, used = slot_sz, regs = 0, max_used = 0, slots = 1, max_slots = 1;
+    // k_traverse4's fill image: the chunks' regions one behind the other, each chunk its own extent (a multiple of the block:
+    // 16-byte aligned); every op of a chunk carries the chunk's offset
+    int64_t image = 0;
+    bool image_ok = !e->mfma && e->fill_image.on;
+    auto close_chunk = [&](int end) {
+        e->h_ops.p[chunk_start].chunk_nops = end - chunk_start;
+        e->h_ops.p[chunk_start].chunk_slots = slots;
+        if (e->mfma) return;
+        for (int q = chunk_start; q < end; q++) e->h_ops.p[q].image_off = (int32_t)image;
+        image += regs;
+    };
     for (int k = 0; k < nops; k++) {
         DevOp &d = e->h_ops.p[k];
+        if (d.left_len_p || d.right_len_p) image_ok = false;   // (lengths the host does not know)
         const int szl = d.left_kind == CHILD_LEAF ? leaf_sz : (d.left_kind == CHILD_PAIR ? pair_sz : B);
         const int szr = d.right_kind == CHILD_LEAF ? leaf_sz : (d.right_kind == CHILD_PAIR ? pair_sz : B);
         // 4-state path: each leaf / pair child also stages one state byte per thread in LDS
@@ -608,8 +620,7 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         // (k_traverse4 keeps one row pointer per slot of the chunk in a fixed array)
         const bool rows_full = !e->mfma && slots + nleaf > kTrav4RowSlots;
         if ((used + need > budget || rows_full || seg_of[k] != seg_of[k - (k > 0)]) && k > chunk_start) {
-            e->h_ops.p[chunk_start].chunk_nops = k - chunk_start;
-            e->h_ops.p[chunk_start].chunk_slots = slots;
+            close_chunk(k);
             chunk_start = k; used = slot_sz; regs = 0; slots = 1;
         }
         d.lds_left = regs; d.lds_right = regs + szl;
@@ -620,10 +631,10 @@ int lay_out_lds(iqhip_engine *e, int nops, const std::vector<int> &seg_of) {
         d.sr_slot = child_is_table(d.right_kind) ? slots++ : 0;
         if (slots > max_slots) max_slots = slots;
     }
-    if (nops > 0) {
-        e->h_ops.p[chunk_start].chunk_nops = nops - chunk_start;
-        e->h_ops.p[chunk_start].chunk_slots = slots;
-    }
+    if (nops > 0) close_chunk(nops);
+    if (image * (int64_t)sizeof(double) > INT32_MAX) image_ok = false;   // (the kernel's 32-bit byte offsets)
+    e->plan.image_doubles = image;
+    e->plan.image_ok = image_ok && image > 0;
     e->plan.state_slots = max_slots;
     e->plan.lds_doubles = max_used;
     return IQHIP_OK;
@@ -734,6 +745,11 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
                 if (d.lds_left < d.lds_right + szr && d.lds_right < d.lds_left + szl) return bad(q, "LDS regions of the two children overlap");
                 regs = std::max(regs, std::max(d.lds_left + szl, d.lds_right + szr));
             }
+            // the chunk's part of the fill image: 16-byte aligned, inside the image, the same offset on every op of the chunk
+            for (int q = k; q < k + c.chunk_nops; q++)
+                if (e->h_ops.p[q].image_off != c.image_off) return bad(q, "image_off differs within a chunk");
+            if (c.image_off < 0 || c.image_off % 2 != 0 || (int64_t)c.image_off + regs > e->plan.image_doubles)
+                return bad(k, "the chunk's fill image is misaligned or outside the image");
             if (c.chunk_slots != next) return bad(k, "chunk_slots is not the chunk's slot count");
             if (next > kTrav4RowSlots) return bad(k, "more leaf-state slots than the kernel's row-pointer list holds");
             if (next > e->plan.state_slots || regs > e->plan.lds_doubles) return bad(k, "LDS chunk outside the launch's allocation");
@@ -755,9 +771,12 @@ int check_plan(iqhip_engine *e, int nops, int nsentinels) {
 // The descriptors of a repeated plan (model-parameter optimisation re-evaluates the same tree) are already on the
 // device: skip the upload, never the computation.
 int upload_plan(iqhip_engine *e, size_t nbytes) {
-    if (e->planner) return IQHIP_OK;   // (nothing to upload to)
     std::vector<char> &up = e->plan_cache.uploaded;
     const char *h = reinterpret_cast<const char *>(e->h_ops.p);
+    if (e->planner) {   // (nothing to upload to; `uploaded` is what d_ops would hold, so that a repeated plan is found cached)
+        up.assign(h, h + nbytes);
+        return IQHIP_OK;
+    }
     if (e->plan.small) {
         // (rides in the kernel arguments, which the launch copies out of h_ops; `uploaded` is what d_ops would hold)
     } else if (up.size() == nbytes && memcmp(up.data(), h, nbytes) == 0) {
@@ -785,6 +804,7 @@ int finish_and_upload(iqhip_engine *e, int nops, const iqhip_node_op *ops_in, in
                       const double *const *len_ptrs, int last_dst) {
     Plan &p = e->plan;
     for (int q = 0; q < kSentinels; q++) dummy_op(e, e->h_ops.p[nops + q]);  // targets of the look-ahead requests
+    e->h_ops.p[nops].image_off = (int32_t)p.image_doubles;   // (k_traverse4: a chunk's extent is the distance to the next chunk's offset)
     p.table_off = nops + kSentinels;
     const int table_ops = segment_table_ops(u);
     int *tab = reinterpret_cast<int *>(e->h_ops.p + p.table_off);
@@ -869,6 +889,26 @@ int build_branch(iqhip_engine *e, iqhip_branch_end a, iqhip_branch_end b, double
     rc = resolve_child(e, b.key, b.leaf, prev_dst, &br->b, &br->b_sc, &st_unused, &br->b_kind);
     if (rc) return rc;
     br->len = len;
+    return IQHIP_OK;
+}
+
+// Policy A (DESIGN.md 3.1 "Fill image"): a plan that was found cached is going to be submitted again -- its image is built
+// if it is stale (another model since, or never built) and the launches copy it; a plan that was planned anew fills in the
+// kernel and launches nothing.  Never: plans with device-side lengths (not cached, image_ok), plans that travel in the
+// kernel arguments, the pair engine's cherry submissions (fill_image.on).
+int fill_image_submission(iqhip_engine *e) {
+    iqhip_engine::FillImage &f = e->fill_image;
+    f.use = false;
+    if (e->mfma || !f.on || !f.plan_hit || !e->plan.image_ok || e->plan.small) return IQHIP_OK;
+    if (f.model == e->model_version && f.buf.cap >= (size_t)e->plan.image_doubles) {
+        f.reused++;
+    } else {
+        if (f.buf.cap < (size_t)e->plan.image_doubles) HIPCHK(f.buf.ensure(e, (size_t)e->plan.image_doubles + 1024));
+        if (!e->planner) HIPCHK(launch_fill4_image(e, e->plan.small_nops));
+        f.model = e->model_version;
+        f.built++;
+    }
+    f.use = true;
     return IQHIP_OK;
 }
 
@@ -985,11 +1025,14 @@ TravLaunch choose_traverse_mfma(const iqhip_engine *e, bool top_stage, int nsegs
 int build_plan(iqhip_engine *e, const iqhip_node_op *ops, int nops, int *last_dst, const std::vector<int> *explicit_segs,
                const double *const *len_ptrs) {
     if (nops + 2 > e->result_cap) return fail(IQHIP_ERR_INVALID, "too many node updates in one submission");
+    e->fill_image.plan_hit = false;
     if (plan_is_cached(e, ops, nops, explicit_segs, len_ptrs)) {
         *last_dst = e->plan_cache.dst;
         mark_virtual_slabs(e);
+        e->fill_image.plan_hit = true;
         return IQHIP_OK;
     }
+    e->fill_image.model = 0;   // (the image belongs to the plan that is replaced here)
     e->plan_cache.version = 0;
     if (e->staging_busy) {  // the previous submission may still be copying h_ops
         HIPCHK(hipEventSynchronize(e->staging_free));

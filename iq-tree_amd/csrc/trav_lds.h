@@ -63,6 +63,10 @@ constexpr int kWide4LdsKb = 40;   // per workgroup, fixed part included: four wo
 // thread each, i.e. kTravWg / 8 doubles; slot 0 is shared by all non-leaf children.  The state bytes lie [wave][slot][64]
 // (slot < Plan::state_slots): a wave's slots are contiguous, so one LDS-direct dword load fills four of them, each group
 // of 16 lanes fetching the 64 bytes of one leaf child (kernels_valu4.hip, the chunk fill's state requests).
+// The fill image (iqhip_engine::fill_image, built by k_fill4_image) mirrors the plan regions and nothing else: chunk i of the
+// plan lies at DevOp::image_off doubles (16-byte aligned) and is the chunk's s_reg byte for byte -- every region at its
+// lds_left / lds_right, sized by child_region_blocks -- over the chunk's own extent, which is at most Plan::lds_doubles; the
+// copy in k_traverse4 writes [s_reg, s_reg + extent) and never the state slots behind the regions.
 // The row pointers those requests read, s_row[slot], are a static array of kTrav4RowSlots pointers inside the kernel,
 // not part of the dynamic LDS: budget, chunk cuts and launch bytes of a plan do not depend on it.  lay_out_lds ends a
 // chunk before its slots would outgrow the array and check_plan holds every chunk to it.

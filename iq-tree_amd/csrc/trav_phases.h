@@ -82,4 +82,43 @@ __device__ __forceinline__ LeafE4 leaf_e4(const double *Urow, const double *ex4)
 __device__ __forceinline__ double leaf_entry4(const double *Urow, const double *ex4, const double *tip4) {
     return leaf_e4(Urow, ex4).entry(tip4);
 }
+// 7. The items of k_traverse4's staged chunk fill, which k_fill4_image makes once per plan into the fill image: the same
+// expressions, so the same bits.  model: [U 16][eigenvalues 4][rates C]; B = 4 C.
+//   phase 1   element e of a region's exponentials
+__device__ __forceinline__ double fill4_exp(const double *model, int e, double len) {
+    return exp(model[16 + (e & 3)] * (model[20 + (e >> 2)] * len));
+}
+//   phase 2   element e = (c, x) of the four state rows and the unknown row of the K2 table behind a region's exponentials
+__device__ __forceinline__ void fill4_leaf_table(double *reg, int B, int e, const double *model, const double *tip) {
+    const int c = e >> 2, x = e & 3;
+    const LeafE4 E = leaf_e4(model + x * 4, reg + c * 4);
+#pragma unroll
+    for (int row = 0; row < 4; row++) reg[B + row * B + e] = E.entry(tip + row * 4);
+    reg[B + 4 * B + e] = 1.0;
+}
+//   phase 2b  row `code` of category c of a PAIR child's table, from the two leaf tables behind it (kPairRows rows; U, U^-1:
+//   the kernel's scalar-operand views)
+template <typename UPtr>
+__device__ __forceinline__ void fill4_pair_row(double *reg, int B, int c, int code, UPtr U, UPtr uinv) {
+    const int sa = code / 5, sb = code - 5 * sa;
+    const double *ta = reg + (2 + kPairRows + sa) * B + c * 4, *tb = reg + (8 + kPairRows + sb) * B + c * 4;
+    double tmp[4], l[4];
+#pragma unroll
+    for (int x = 0; x < 4; x++) tmp[x] = __dmul_rn(ta[x], tb[x]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        double v = __dmul_rn(uinv[i * 4], tmp[0]);
+        v = fma(uinv[i * 4 + 1], tmp[1], v);
+        v = fma(uinv[i * 4 + 2], tmp[2], v);
+        v = fma(uinv[i * 4 + 3], tmp[3], v);
+        l[i] = __dmul_rn(reg[c * 4 + i], v);
+    }
+#pragma unroll
+    for (int x = 0; x < 4; x++) {
+        double v = __dmul_rn(U[x * 4], l[0]);
+        v = fma(U[x * 4 + 1], l[1], v);
+        v = fma(U[x * 4 + 2], l[2], v);
+        reg[B + code * B + c * 4 + x] = fma(U[x * 4 + 3], l[3], v);
+    }
+}
 }  // namespace iqhip
