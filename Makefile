@@ -10,7 +10,7 @@ CSRC       := $(PKG)/csrc
 HOST       := $(PKG)/host
 LIBDIR     := $(PKG)/lib
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
-HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/ptnlh.hip $(CSRC)/classlh.hip $(CSRC)/pairdist.hip $(CSRC)/quartet.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_partnewton.hip $(CSRC)/kernels_partboot.hip $(CSRC)/kernels_partdist.hip $(CSRC)/partition.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_em.hip $(CSRC)/kernels_mixem.hip $(CSRC)/kernels_classlnl.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_ufboot.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_quartet.hip $(CSRC)/kernels_bionj.hip $(CSRC)/kernels_pars.hip $(CSRC)/kernels_spr.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
+HIP_SRCS   := $(CSRC)/engine.hip $(CSRC)/solve.hip $(CSRC)/plan.hip $(CSRC)/ptnlh.hip $(CSRC)/ufboot.hip $(CSRC)/classlh.hip $(CSRC)/pairdist.hip $(CSRC)/quartet.hip $(CSRC)/kernels_valu4.hip $(CSRC)/kernels_valu4w.hip $(CSRC)/kernels_mfma.hip $(CSRC)/kernels_newton.hip $(CSRC)/kernels_partnewton.hip $(CSRC)/kernels_partboot.hip $(CSRC)/kernels_partdist.hip $(CSRC)/partition.hip $(CSRC)/kernels_sweep.hip $(CSRC)/kernels_rell.hip $(CSRC)/kernels_em.hip $(CSRC)/kernels_mixem.hip $(CSRC)/kernels_classlnl.hip $(CSRC)/kernels_alrt.hip $(CSRC)/kernels_topo.hip $(CSRC)/kernels_ufboot.hip $(CSRC)/kernels_dist.hip $(CSRC)/kernels_quartet.hip $(CSRC)/kernels_bionj.hip $(CSRC)/kernels_pars.hip $(CSRC)/kernels_spr.hip $(CSRC)/pars.hip $(CSRC)/comm.hip $(CSRC)/sharded.hip
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(HIP_SRCS))
 
 all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/liblh_oracle.so
@@ -18,7 +18,7 @@ all: $(LIBDIR)/libiqhip.so $(LIBDIR)/libiqhost.so $(LIBDIR)/iqhip_lnl oracle/lib
 $(LIBDIR):
 	mkdir -p $(LIBDIR)
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/trav_phases.h $(CSRC)/pars_spr_check.h $(CSRC)/ufboot_rule.h $(CSRC)/pair_eval.h $(CSRC)/partpair_layout.h include/iqhip.h | $(LIBDIR)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/iqhip_internal.h $(CSRC)/wg_exchange.h $(CSRC)/trav_lds.h $(CSRC)/trav_phases.h $(CSRC)/pars_spr_check.h $(CSRC)/ufboot_rule.h $(CSRC)/pair_eval.h $(CSRC)/partpair_layout.h $(CSRC)/partition.h include/iqhip.h | $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the topology tests compare sums bit for bit with a plain IEEE evaluation of the reference's expressions

@@ -438,6 +438,21 @@ struct Slab {
     double len_l = 0.0, len_r = 0.0;
 };
 
+// UFBoot bookkeeping of an engine (iqhip_ufboot_*) or of a partition group (iqhip_partition_ufboot_*); ufboot.hip,
+// kernels_ufboot.hip, kernels_partboot.hip.  Per replicate boot_logl, boot_orig_logl [nsamples each, in `dbl`], boot_tree
+// [nsamples], boot_counts [nsamples]; the entries of a call with `row` rewritten to the row of the chunk's sums; res =
+// {replaced slots (64-bit integer), wgmin [workgroups]}.  nsamples == 0: no state (before the owner's init, and after a
+// sample matrix it was initialised on was replaced)
+struct UfbootState {
+    DevBuf<double> dbl, res;
+    DevBuf<int64_t> tree;
+    DevBuf<int32_t> counts;
+    DevBuf<iqhip_ufboot_tree> entries;
+    int nsamples = 0;
+    double ms[2] = {0.0, 0.0};   // the owner's timing read-out: the products, the update kernels (while timing is enabled)
+    int64_t launches = 0;        // kernels the last update enqueued
+};
+
 }  // namespace iqhip
 
 struct iqhip_engine {
@@ -611,19 +626,8 @@ struct iqhip_engine {
         iqhip::DevBuf<double> dbl;      // lh, avg, w_orig [T each] ++ weights [T][T] ++ max_sh, max_elw, sum_l [S each] ++ out [6 T]
         iqhip::DevBuf<int32_t> ints;    // kh_id, w_id [T each] ++ winner [S]; iqhip_multiscale_bp: counters [nscales][T]
     } tt;
-    // UFBoot bookkeeping (iqhip_ufboot_*; ptnlh.hip, kernels_ufboot.hip): per replicate boot_logl, boot_orig_logl [nsamples
-    // each, in `dbl`], boot_tree [nsamples], boot_counts [nsamples]; the entries of a call with `row` rewritten to the row
-    // of the chunk's sums; res = {replaced slots (64-bit integer), wgmin [workgroups]}.  nsamples == 0: no state
-    // (before iqhip_ufboot_init, and after the sample matrix was replaced)
-    struct {
-        iqhip::DevBuf<double> dbl, res;
-        iqhip::DevBuf<int64_t> tree;
-        iqhip::DevBuf<int32_t> counts;
-        iqhip::DevBuf<iqhip_ufboot_tree> entries;
-        int nsamples = 0;
-        double ms[2] = {0.0, 0.0};   // iqhip_debug_ufboot_timing: the products, the update kernels (while timing is enabled)
-        int64_t launches = 0;        // kernels the last iqhip_ufboot_update enqueued
-    } ufb;
+    // UFBoot bookkeeping (iqhip_ufboot_*, read out by iqhip_debug_ufboot_timing)
+    iqhip::UfbootState ufb;
     // EM for +R free-rate models and empirical-Bayes site rates (classlh.hip, kernels_em.hip): what the last E-step left -- the
     // posterior matrix W [ncat][nptn_pad] (category-major, padding patterns 0), per pattern its posterior mean rate and
     // best category -- and the scratch of the sums (workgroup rows, folded values).  valid: an E-step has run for an
@@ -989,20 +993,24 @@ hipError_t raise_lds_ceiling(const iqhip_engine *e, int bytes) {
     if (s == hipSuccess && dev < kLdsCeilingDevices) raised[dev].store(true, std::memory_order_relaxed);
     return s;
 }
-// HIP events around the phases of one feature call; nothing at all while e->timing is off.  mark() records the next
-// boundary on e->stream: a round of nphases phases is nphases + 1 marks, a call may record any number of rounds (one per
-// chunk) and nothing waits inside its loop.  read() waits for the last recorded event, then ms[k] = the time of phase k
-// summed over all rounds; false, ms untouched, while timing is off, nothing was recorded or an event call failed.  A failed
-// event call never fails the feature call: the reading is then missing, not the result.  The destructor destroys every
-// event, on every return path.
+// HIP events around the phases of one feature call, the one event timer of the drivers; nothing at all while `on` is false
+// (an engine's e->timing; a partition group takes that of its member 0).  mark() records the next boundary on the timer's
+// stream, mark(s) on another one (a group's marks around what a member's stream runs): a round of nphases phases is
+// nphases + 1 marks, a call may record any number of rounds (one per chunk, per step, per member) and nothing waits inside
+// its loop.  read() waits for the last recorded event -- a caller whose marks went to several streams has drained them all
+// by then -- then ms[k] = the time of phase k summed over all rounds; false, ms untouched, while timing is off, nothing was
+// recorded or an event call failed.  A failed event call never fails the feature call: the reading is then missing, not the
+// result.  The destructor destroys every event, on every return path.
 struct PhaseTimer {
-    PhaseTimer(iqhip_engine *e_, int nphases_) : e(e_), nphases(nphases_), ok(e_->timing) {}
+    PhaseTimer(bool on, hipStream_t stream_, int nphases_) : stream(stream_), nphases(nphases_), ok(on) {}
+    PhaseTimer(iqhip_engine *e, int nphases_) : PhaseTimer(e->timing, e->stream, nphases_) {}
     PhaseTimer(const PhaseTimer &) = delete; PhaseTimer &operator=(const PhaseTimer &) = delete;
-    void mark() {
+    void mark() { mark(stream); }
+    void mark(hipStream_t s) {
         hipEvent_t x = nullptr;
         if (!ok || !(ok = hipEventCreate(&x) == hipSuccess)) return;
         ev.push_back(x);
-        ok = hipEventRecord(x, e->stream) == hipSuccess;
+        ok = hipEventRecord(x, s) == hipSuccess;
     }
     bool read(double *ms) {
         const size_t round = (size_t)nphases + 1;
@@ -1018,7 +1026,7 @@ struct PhaseTimer {
         return true;
     }
     ~PhaseTimer() { for (hipEvent_t x : ev) hipEventDestroy(x); }
-    iqhip_engine *e;
+    hipStream_t stream;
     int nphases;
     bool ok;
     std::vector<hipEvent_t> ev;
@@ -1333,13 +1341,15 @@ hipError_t launch_ptnlh_rows(iqhip_engine *e, const void *d_tasks, int m, const 
 int alrt_ksplit(const iqhip_engine *e, int nrows, int nsamples);
 // ptnlh.hip: the distinct rows of a row list in first-appearance order (list[0, M)) and, behind them, every entry's index
 // into them; bt_stage: the list into e->bt.rows, e->bt.part and e->bt.sums sized for products of its distinct rows with
-// nsamples replicates (the engine's stream drains)
+// nsamples replicates (the engine's stream drains); row_list_scatter: the sums [M][nsamples] of the distinct rows back to
+// the order of the list the RowList was made from, out [nrows][nsamples]
 struct RowList {
     std::vector<int32_t> list;
     int M;
 };
 RowList row_list(const int32_t *rows, int nrows);
 int bt_stage(iqhip_engine *e, const RowList &rl, int ksplit, size_t nsamples);
+void row_list_scatter(const RowList &rl, const double *sums, int nsamples, double *out);
 hipError_t launch_alrt_product(iqhip_engine *e, const int32_t *d_rows, int nrows, int nsamples, int ksplit, double *part,
                                double *sums);
 hipError_t launch_alrt_stats(iqhip_engine *e, const int32_t *d_idx3, const double *d_lh3, int nbranch, int nsamples,
@@ -1394,12 +1404,6 @@ struct PairSolveArgs {
 hipError_t launch_pair_counts(iqhip_engine *e, const PairTile *d_tiles, int ntiles, double *d_counts);
 hipError_t launch_pair_coef(iqhip_engine *e, double *d_coef);
 hipError_t launch_pair_solve(iqhip_engine *e, const PairSolveArgs &a, int npairs);
-// pairdist.hip: what iqhip_pair_distances shares with the group's call (partition.hip).  pair_require: the engines both
-// accept; pair_list: the pairs i < j of T taxa in the order both process them; pair_tiles: the tiles of m listed pairs
-// appended to `tiles`, pair k of the list in slot k
-int pair_require(iqhip_engine *e, const char *what);
-void pair_list(int T, std::vector<int32_t> &pairs);
-void pair_tiles(const int32_t *pairs, int64_t m, int ntaxa, std::vector<PairTile> &tiles);
 
 // kernels_partdist.hip: the joint pairwise distances of a partition group (SuperAlignmentPairwisePlen).  One descriptor per
 // member; slot s of a chunk is pair first_pair + s of the call.  The kernel compacts the non-zero cells of every member's

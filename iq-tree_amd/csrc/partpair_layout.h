@@ -1,4 +1,4 @@
-// partpair_layout.h -- how a call of iqhip_partition_pair_distances (partition.hip) cuts its pairs into chunks and lays the
+// partpair_layout.h -- how a call of iqhip_partition_pair_distances (pairdist.hip) cuts its pairs into chunks and lays the
 // members' cell lists out.  Plain C++ without a device, so that tools/asan_partition_dist.sh runs it under ASan + UBSan as a
 // stand-alone program.
 #pragma once
@@ -11,7 +11,7 @@
 namespace iqhip {
 
 // One call's chunks.  A pair needs n_p^2 counts (8 bytes) and n_p^2 cell slots (2 bytes) of member p; the counts of a chunk,
-// all members together, stay within 64 MB.  chunk_override > 0 (IQHIP_PAIR_CHUNK) takes its place.  Member p's block of the
+// all members together, stay within 64 MB.  chunk_override > 0 (pairdist.hip pair_chunk_override) takes its place.  Member p's block of the
 // group's cell buffer [chunk * sum_nn] starts at element cell_first[p] = chunk * sum_{q < p} n_q^2 and holds chunk * n_p^2
 struct PartPairLayout {
     int64_t chunk = 1;                // pairs per chunk, 1 <= chunk <= max(1, npairs)

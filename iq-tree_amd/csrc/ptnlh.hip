@@ -1,7 +1,7 @@
 // ptnlh.hip -- drivers of everything that consumes per-pattern log-likelihoods on the device: the scaled pattern-lh fetches,
-// the bootstrap sample matrix and RELL, the store of per-pattern log-likelihood rows, SH-aLRT and local bootstrap, the tree
-// topology tests and UFBoot's per-replicate bookkeeping.  Host code only; the kernels are in kernels_rell.hip,
-// kernels_alrt.hip, kernels_topo.hip and kernels_ufboot.hip.  (What consumes theta per class is in classlh.hip.)
+// the bootstrap sample matrix and RELL, the store of per-pattern log-likelihood rows, SH-aLRT and local bootstrap and the
+// tree topology tests.  Host code only; the kernels are in kernels_rell.hip, kernels_alrt.hip and kernels_topo.hip.  (What
+// consumes theta per class is in classlh.hip, UFBoot's per-replicate bookkeeping on the rows in ufboot.hip.)
 #include <float.h>
 #include <stdlib.h>
 #include <string.h>
@@ -184,6 +184,13 @@ RowList iqhip::row_list(const int32_t *rows, int nrows) {
     return rl;
 }
 
+void iqhip::row_list_scatter(const RowList &rl, const double *sums, int nsamples, double *out) {
+    const int32_t *idx = rl.list.data() + rl.M;
+    const size_t nrows = rl.list.size() - (size_t)rl.M;
+    for (size_t i = 0; i < nrows; i++)
+        memcpy(out + i * nsamples, sums + (size_t)idx[i] * nsamples, sizeof(double) * (size_t)nsamples);
+}
+
 // the list into bt.rows; bt.part and bt.sums sized for products of its distinct rows with nsamples replicates
 int iqhip::bt_stage(iqhip_engine *e, const RowList &rl, int ksplit, size_t nsamples) {
     const size_t sums = (size_t)rl.M * nsamples;
@@ -222,9 +229,7 @@ extern "C" int iqhip_ptnlh_rell(iqhip_engine *e, const int32_t *rows, int nrows,
     std::vector<double> sums((size_t)rl.M * nsamples);
     HIPCHK(hipMemcpyAsync(sums.data(), e->bt.sums.p, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    const int32_t *idx = rl.list.data() + rl.M;
-    for (int i = 0; i < nrows; i++)
-        memcpy(out + (size_t)i * nsamples, sums.data() + (size_t)idx[i] * nsamples, sizeof(double) * (size_t)nsamples);
+    row_list_scatter(rl, sums.data(), nsamples, out);
     return IQHIP_OK;
 }
 
@@ -526,162 +531,5 @@ extern "C" int iqhip_multiscale_bp(iqhip_engine *e, const int32_t *rows, int ntr
     HIPCHK(hipMemcpyAsync(counts.data(), d_counts, sizeof(uint32_t) * ncount, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (size_t i = 0; i < ncount; i++) bp[i] = (double)counts[i] / nsamples;
-    return IQHIP_OK;
-}
-
-// ---- ultrafast bootstrap: saveCurrentTree's per-replicate bookkeeping (iqtree.cpp:2676-2786; kernels_ufboot.hip) -----------
-extern "C" int iqhip_ufboot_init(iqhip_engine *e, int nsamples) {
-    int rc = require(e, "iqhip_ufboot_init", REQ_SINGLE_DEVICE);
-    if (rc) return rc;
-    if (nsamples < 1 || nsamples > e->nboot)
-        return fail(IQHIP_ERR_INVALID, e->nboot == 0 ? "iqhip_ufboot_init: no bootstrap samples (iqhip_gen_boot_samples / iqhip_set_boot_samples)"
-                                                     : "iqhip_ufboot_init: nsamples must be 1 .. the number of uploaded samples");
-    HIPCHK(use_device(e));
-    const size_t S = (size_t)nsamples;
-    e->ufb.nsamples = 0;
-    HIPCHK(e->ufb.dbl.ensure(e, 2 * S));
-    HIPCHK(e->ufb.tree.ensure(e, S));
-    HIPCHK(e->ufb.counts.ensure(e, S));
-    HIPCHK(e->ufb.res.ensure(e, 1 + (size_t)ufboot_workgroups(nsamples)));
-    // iqtree.cpp:308-312
-    std::vector<double> lo(2 * S, -DBL_MAX);
-    std::vector<int64_t> none(S, -1);
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable sources)
-    HIPCHK(hipMemcpyAsync(e->ufb.dbl.p, lo.data(), sizeof(double) * lo.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->ufb.tree.p, none.data(), sizeof(int64_t) * S, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->ufb.counts.p, 0, sizeof(int32_t) * S, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->ufb.nsamples = nsamples;
-    e->ufb.ms[0] = e->ufb.ms[1] = 0.0;
-    e->ufb.launches = 0;
-    return IQHIP_OK;
-}
-
-// the state exists and still belongs to the sample matrix
-static int ufboot_ready(iqhip_engine *e, const char *what) {
-    if (e->ufb.nsamples < 1 || e->ufb.nsamples > e->nboot)
-        return fail(IQHIP_ERR_INVALID, std::string(what) + " needs iqhip_ufboot_init first (again after the sample matrix was replaced)");
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ufboot_update(iqhip_engine *e, const iqhip_ufboot_tree *trees, int ntrees, double epsilon, double logl_cutoff,
-                                   int64_t *counts, double *min_orig_logl) {
-    const char *what = "iqhip_ufboot_update";
-    int rc = require(e, what, REQ_SINGLE_DEVICE);
-    if (rc) return rc;
-    if (!trees || ntrees < 1) return fail(IQHIP_ERR_INVALID, std::string(what) + ": bad tree list");
-    if (!(epsilon >= 0.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": epsilon must be >= 0");
-    if ((rc = ufboot_ready(e, what))) return rc;
-    static_assert(sizeof(iqhip_ufboot_tree) == 32, "iqhip_ufboot_tree is 32 bytes");
-    for (int i = 0; i < ntrees; i++) {
-        const iqhip_ufboot_tree &t = trees[i];
-        if (t.row < 0 || t.row >= e->ptnlh_rows) return fail(IQHIP_ERR_INVALID, std::string(what) + ": row outside the store");
-        if (t.tree_id < 0) return fail(IQHIP_ERR_INVALID, std::string(what) + ": tree_id must be >= 0");
-        if (!(t.rand >= 0.0 && t.rand <= 1.0)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": rand outside [0, 1]");
-        if (!std::isfinite(t.logl)) return fail(IQHIP_ERR_INVALID, std::string(what) + ": log-likelihoods must be finite");
-    }
-    // iqtree.cpp:2678
-    std::vector<iqhip_ufboot_tree> ent;
-    ent.reserve((size_t)ntrees);
-    for (int i = 0; i < ntrees; i++)
-        if (!(logl_cutoff != 0.0 && trees[i].logl < logl_cutoff - 1.0)) ent.push_back(trees[i]);
-    const int n = (int)ent.size(), S = e->ufb.nsamples;
-    HIPCHK(use_device(e));
-    // entries per chunk: part [ksplit][M][S] and sums [M][S] of M <= chunk distinct rows within 256 MB.  The K-split follows
-    // from nsamples, the pattern count and the CU count alone, so a (row, replicate) sum has the same bits whatever the chunk
-    const int ksplit = alrt_ksplit(e, 1, S);
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / ((int64_t)sizeof(double) * S * (ksplit + 1)));
-    if (const char *uc = getenv("IQHIP_UFBOOT_CHUNK")) chunk = std::max(1, atoi(uc));
-    chunk = std::min<int64_t>(chunk, std::max(n, 1));
-    // every chunk's row list, and the entries with `row` rewritten to the row of their chunk's sums
-    std::vector<RowList> lists;
-    std::vector<int32_t> rows((size_t)chunk);
-    for (int first = 0; first < n; first += (int)chunk) {
-        const int m = (int)std::min<int64_t>(chunk, n - first);
-        for (int i = 0; i < m; i++) rows[i] = ent[first + i].row;
-        lists.push_back(row_list(rows.data(), m));
-        const int32_t *idx = lists.back().list.data() + lists.back().M;
-        for (int i = 0; i < m; i++) ent[first + i].row = idx[i];
-    }
-    const size_t nwg = (size_t)ufboot_workgroups(S);
-    HIPCHK(e->ufb.entries.ensure(e, (size_t)std::max(n, 1)));
-    HIPCHK(e->ufb.res.ensure(e, 1 + nwg));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (pageable source, and an earlier launch may still read the entries)
-    if (n > 0)
-        HIPCHK(hipMemcpyAsync(e->ufb.entries.p, ent.data(), sizeof(iqhip_ufboot_tree) * (size_t)n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->ufb.res.p, 0, sizeof(double), e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    unsigned long long *d_replaced = reinterpret_cast<unsigned long long *>(e->ufb.res.p);
-    double *boot_logl = e->ufb.dbl.p, *boot_orig = e->ufb.dbl.p + S;
-    PhaseTimer timer(e, 2);   // per chunk: before the product, between, behind the update
-    int64_t launches = 0;
-    hipError_t s = hipSuccess;
-    if (n == 0) {   // everything fell to the cutoff: the state is only read for its minimum
-        s = launch_ufboot_update(e, nullptr, S, e->ufb.entries.p, 0, epsilon, boot_logl, boot_orig, e->ufb.counts.p, e->ufb.tree.p,
-                                 d_replaced, e->ufb.res.p + 1);
-        launches = 1;
-    }
-    for (size_t c = 0, first = 0; c < lists.size() && s == hipSuccess && rc == IQHIP_OK; c++) {
-        const RowList &rl = lists[c];
-        const int m = (int)(rl.list.size() - (size_t)rl.M);
-        if ((rc = bt_stage(e, rl, ksplit, (size_t)S))) break;
-        timer.mark();
-        s = launch_alrt_product(e, e->bt.rows.p, rl.M, S, ksplit, e->bt.part.p, e->bt.sums.p);
-        timer.mark();
-        if (s == hipSuccess)
-            s = launch_ufboot_update(e, e->bt.sums.p, S, e->ufb.entries.p + first, m, epsilon, boot_logl, boot_orig,
-                                     e->ufb.counts.p, e->ufb.tree.p, d_replaced, e->ufb.res.p + 1);
-        timer.mark();
-        launches += 3;
-        first += (size_t)m;
-    }
-    std::vector<double> res(1 + nwg);
-    if (s == hipSuccess && rc == IQHIP_OK)
-        s = hipMemcpyAsync(res.data(), e->ufb.res.p, sizeof(double) * res.size(), hipMemcpyDeviceToHost, e->stream);
-    const hipError_t drained = hipStreamSynchronize(e->stream);
-    if (s == hipSuccess) s = drained;
-    if (rc) return rc;
-    HIPCHK(s);
-    e->ufb.ms[0] = e->ufb.ms[1] = 0.0;
-    timer.read(e->ufb.ms);
-    e->ufb.launches = launches;
-    if (counts) {
-        unsigned long long replaced;
-        memcpy(&replaced, &res[0], sizeof(replaced));
-        counts[0] = n;
-        counts[1] = ntrees - n;
-        counts[2] = (int64_t)replaced;
-    }
-    if (min_orig_logl) {   // the workgroups' minima in workgroup order
-        double mn = DBL_MAX;
-        for (size_t w = 0; w < nwg; w++)
-            if (res[1 + w] < mn) mn = res[1 + w];
-        *min_orig_logl = mn;
-    }
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_ufboot_fetch(iqhip_engine *e, double *boot_logl, double *boot_orig_logl, int32_t *boot_counts,
-                                  int64_t *boot_tree) {
-    int rc = require(e, "iqhip_ufboot_fetch", REQ_SINGLE_DEVICE);
-    if (rc) return rc;
-    if ((rc = ufboot_ready(e, "iqhip_ufboot_fetch"))) return rc;
-    HIPCHK(use_device(e));
-    const size_t S = (size_t)e->ufb.nsamples;
-    if (boot_logl) HIPCHK(hipMemcpyAsync(boot_logl, e->ufb.dbl.p, sizeof(double) * S, hipMemcpyDeviceToHost, e->stream));
-    if (boot_orig_logl) HIPCHK(hipMemcpyAsync(boot_orig_logl, e->ufb.dbl.p + S, sizeof(double) * S, hipMemcpyDeviceToHost, e->stream));
-    if (boot_counts) HIPCHK(hipMemcpyAsync(boot_counts, e->ufb.counts.p, sizeof(int32_t) * S, hipMemcpyDeviceToHost, e->stream));
-    if (boot_tree) HIPCHK(hipMemcpyAsync(boot_tree, e->ufb.tree.p, sizeof(int64_t) * S, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return IQHIP_OK;
-}
-
-extern "C" int iqhip_debug_ufboot_timing(iqhip_engine *e, double *ms, int64_t *launches) {
-    int rc = require(e, "iqhip_debug_ufboot_timing", REQ_SINGLE_DEVICE);
-    if (rc) return rc;
-    if (!ms) return fail(IQHIP_ERR_INVALID, "iqhip_debug_ufboot_timing: null argument");
-    ms[0] = e->ufb.ms[0];
-    ms[1] = e->ufb.ms[1];
-    if (launches) *launches = e->ufb.launches;
     return IQHIP_OK;
 }
