@@ -324,9 +324,19 @@ __global__ __launch_bounds__(kTravWg, 2) void k_traverse4(const Trav4Args A) {
     const double freq = A.freq[ptn];
     const double invar = A.invar[ptn];
 
-    const CONST_AS double *U = as_const(A.evec);
-    const CONST_AS double *uinv = as_const(A.inv_evec);
-    const CONST_AS DevOp *ops = A.small_plan ? (const CONST_AS DevOp *)(kargs + offsetof(Trav4Args, small_ops)) : as_const(A.ops);
+    // The two pointers are made values of their own behind an empty asm.  As plain kernel arguments they are two registers of
+    // the sixteen that the first 64 bytes of the arguments are loaded into, the register allocator spills that block whole, and
+    // in front of every contraction of a vector child (two children x C categories per op) the op loop restored all sixteen with
+    // v_readlane to get at the pointer to U: 275 v_readlane in the op loop of <4, false, 1>, 18 with the pointers pinned.  The
+    // matrices themselves stay what they were, scalar operands read through the constant address space (held in registers
+    // across the op loop instead -- pinned scalar values, or U in vector registers -- the update was measured slower:
+    // DESIGN.md 3.1 "Operand homes", profiles/r09/experiments.txt).
+    uint64_t u_bits = reinterpret_cast<uint64_t>(A.evec), uinv_bits = reinterpret_cast<uint64_t>(A.inv_evec);
+    asm volatile("" : "+s"(u_bits));
+    asm volatile("" : "+s"(uinv_bits));
+    const CONST_AS double *U = (const CONST_AS double *)u_bits;
+    const CONST_AS double *uinv = (const CONST_AS double *)uinv_bits;
+    const CONST_AS DevOp *ops =A.small_plan ? (const CONST_AS DevOp *)(kargs + offsetof(Trav4Args, small_ops)) : as_const(A.ops);
 
     double prev[BL], PF[BL], HOLD[BL];
     int hold_sc = 0;
